@@ -13,11 +13,13 @@ scene is timed as a side leg (`scene_smooth`).  N > 1: frames are independent, s
 contiguously, the SAME 256 frames per rank at every N (weak scaling; the N = 1 point is the single-GPU headline); each rank re-extracts
 the one frame preceding its shard (halo) instead of receiving it, and the only collective is the gather of map points to rank 0 -
 under --backend nccl through the library's own RCCL entry point (mo_comm_init / mo_gather_map_points) on a side stream beside
-the next step's kernels, drained inside the timed region.  At N > 1 a second timed region with 512 frames per rank is reported
+the next step's kernels, drained inside the timed region.  At N > 1 --full reports a second timed region with 512 frames per rank
 beside the headline (`config5_512_per_gpu`: 8 ranks = BASELINE config 5's 4096 frames).
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 via torch.distributed.run (one rank per GPU).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run times the headline region only; --full adds everything else the line can hold (the
+side legs, the opt-in matcher, the CPU baseline and, at N > 1, the 512-frames-per-rank region).  --dump-outputs DIR writes what the
+last timed step computed (rank 0's shard) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -69,6 +71,46 @@ def metric_name():
             return json.load(f)["metric"]
     except Exception:
         return "frames/sec (extract+match+pose) at 640x480, 2000 ORB, 1/2/4/8 MI355X"
+
+
+DUMP_FRAMES, DUMP_DESC_FRAMES, DUMP_SEED, DUMP_MAX_BYTES = 256, 64, 20251015, 64 * 10 ** 6
+
+
+def dump_outputs(path, kps, desc, counts, midx, mdist, mpass, pose, pts, npts):
+    """--dump-outputs: the arrays the last timed step handed its caller, as DIR/<name>.npy in float32 / float64 (about 48 MB at 256
+    frames).  Frames beyond DUMP_FRAMES and descriptors beyond DUMP_DESC_FRAMES frames are a fixed seeded sample (`frames`,
+    `descriptor_frames`: the indices kept).  Every value written is finite: rows past a frame's keypoint count hold no output and are
+    written as 0, so that two builds compare on what they computed; the library's NaN for "no map point" and "no model" becomes 0 with
+    a 0 in `map_point_valid` / `pose_valid`."""
+    n = counts.shape[0]
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    fr = np.arange(n) if n <= DUMP_FRAMES else np.sort(rng.choice(n, DUMP_FRAMES, replace=False))
+    fd = fr if len(fr) <= DUMP_DESC_FRAMES else np.sort(rng.choice(fr, DUMP_DESC_FRAMES, replace=False))
+    pr = fr[fr < n - 1]   # pairs (frame i, frame i + 1) whose query frame is kept
+    valid = np.arange(CAP)[None, :] < np.minimum(counts, CAP)[:, None]   # [n, CAP]
+    kp = kps.astype(np.float32)
+    kp[..., 5:7] = kps.view(np.int32)[..., 5:7]   # octave, class_id: integer fields of the 28-byte record
+    qv = valid[pr]
+    pv = np.isfinite(pose[pr]).all(axis=1)                        # NaN pose: the pair got no model
+    mv = qv & np.isfinite(pts[pr]).all(axis=2)                    # NaN point: no map point for this query keypoint
+    out = {"frames": fr.astype(np.float64), "descriptor_frames": fd.astype(np.float64),
+           "keypoint_counts": counts[fr].astype(np.float64),
+           "keypoints": np.where(valid[fr][..., None], kp[fr], 0).astype(np.float32),                 # x y size angle response octave class_id
+           "descriptors": np.where(valid[fd][..., None], desc[fd], 0).astype(np.float32),             # 32 bytes per keypoint
+           "match_idx": np.where(qv[..., None], midx[pr], 0).astype(np.float32),                      # train index of the 2 nearest
+           "match_dist": np.where(qv[..., None], mdist[pr], 0).astype(np.float32),                    # their Hamming distances
+           "match_pass": np.where(qv, mpass[pr], 0).astype(np.float32),                               # ratio test passed
+           "pose": np.where(pv[:, None], pose[pr], 0).astype(np.float64),                              # R (9) then t (3)
+           "pose_valid": pv.astype(np.float64),                                                       # the pair has a model
+           "map_points": np.where(mv[..., None], pts[pr], 0).astype(np.float32),                      # per query keypoint
+           "map_point_valid": mv.astype(np.float32),                                                  # the keypoint has a map point
+           "map_point_counts": npts[pr].astype(np.float64)}
+    assert all(np.isfinite(a).all() for a in out.values()), "a non-finite value in the outputs dump"
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, "outputs dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cv2_baseline(frames_u8, n_frames, K):
@@ -178,7 +220,13 @@ def main():
                                                        "profiles/collect.sh generates once and profiles only the pipeline")
     ap.add_argument("--no-check", action="store_true", help="timing-only ablation builds (tools/fast_ablate.sh) produce garbage on purpose: skip the output asserts")
     ap.add_argument("--no-extras", action="store_true", help="skip the side legs (other scene, next rows, H2D-inclusive, single-frame)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline region: side legs, opt-in matcher, CPU baseline, "
+                                                         "the 512-frames-per-rank region at N > 1 (the --no-* switches above thin it out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the last timed step (rank 0's shard) to "
+                                                                      "DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -321,7 +369,8 @@ def main():
                     self.finish(k)
 
     def timed_region(B, scene):
-        """-> (pipeline, elapsed seconds (max over ranks), n_pairs): W warm-up + K timed steps of B frames per rank"""
+        """-> (pipeline, elapsed seconds (max over ranks), n_pairs, map-point buffer of the last step): W warm-up + K timed steps of
+        B frames per rank"""
         first, nb, n_pairs, first_pair = shard(rank, world, B)   # rank > 0 re-extracts the frame preceding its shard (halo)
         pairs_all = [shard(r, world, B)[2] for r in range(world)]
         cache = "%s.%s.%d.%d.npy" % (args.frames_cache, scene, first, nb) if args.frames_cache else ""
@@ -401,18 +450,23 @@ def main():
             k_last = ga.k ^ 1
             a, b = ga.all[0, :n_pairs], pl.pts[k_last][:n_pairs]
             assert torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
-        return pl, elapsed, n_pairs
+        return pl, elapsed, n_pairs, (pl.pts[ga.k ^ 1] if ga else pl.pts[0])
 
     B = args.batch if args.batch > 0 else 256
     second = None
-    if world > 1 and args.batch <= 0:   # BASELINE config 5's shape first: 512 frames per rank (4096 at N = 8)
-        pl5, el5, _ = timed_region(512, args.scene)
+    if args.full and world > 1 and args.batch <= 0:   # BASELINE config 5's shape first: 512 frames per rank (4096 at N = 8)
+        pl5, el5, _, _ = timed_region(512, args.scene)
         second = {"frames_per_gpu": 512, "value": round(world * 512 * args.steps / el5, 2), "unit": "frames/s",
                   "ms_per_step": round(el5 / args.steps * 1e3, 3), "total_frames_per_step": world * 512}
         pl5.ctx.close()
         del pl5
         torch.cuda.empty_cache()
-    pl, elapsed, n_pairs = timed_region(B, args.scene)   # the headline region (its per-stage figures are reported below)
+    pl, elapsed, n_pairs, pts_last = timed_region(B, args.scene)   # the headline region (its per-stage figures are reported below)
+
+    if rank == 0 and args.dump_outputs:   # (before any side leg reuses the buffers)
+        dump_outputs(args.dump_outputs, pl.kps.cpu().numpy(), pl.desc.cpu().numpy(), pl.counts.cpu().numpy(), pl.midx.cpu().numpy(),
+                     pl.mdist.cpu().numpy(), pl.mpass.cpu().numpy(), pl.pose.cpu().numpy(), pts_last[:n_pairs].cpu().numpy(),
+                     pl.npts[:n_pairs].cpu().numpy())
 
     if rank == 0:
         nb = pl.n
@@ -502,7 +556,7 @@ def main():
         }
         if second:
             out["config5_512_per_gpu"] = second
-        single = world == 1 and not args.no_extras
+        single = args.full and world == 1 and not args.no_extras
 
         def timed_calls(leg, n_warm=None):
             """W warm-up + K timed launches of the headline pipeline in its current configuration -> (seconds, stage ms)"""
@@ -536,7 +590,7 @@ def main():
         # Opt-in variant, timed outside the headline region on the same inputs: the matrix-core matcher
         # (VSLAM_AMD_MATCHER=mfma at context creation; identical results).  Its int8 operations (2 * 256 per descriptor
         # pair) are priced against the dense int8 MFMA peak (2 x the bf16 rate, MI355X_MICROARCH.md).
-        if world == 1 and not args.no_optin:
+        if args.full and world == 1 and not args.no_optin:
             os.environ["VSLAM_AMD_MATCHER"] = "mfma"
             try:
                 pl2 = Pipeline(pl.frames, 0, B)
@@ -768,7 +822,7 @@ def main():
                             "Python iterator and are gathered into chunks; track_grid: the detector Tracker uses by default (distribute_keypoints)" % N_HYP)
             out["streaming"] = legs
         out["dev_status"] = dict(status, note="mo_dev_status after every leg's synchronisation: 0 = no capacity flag raised (asserted)")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             nf = min(args.cpu_frames, nb)
             out["cpu_baseline"] = cpu_baseline(pl.frames[:nf].cpu().numpy(), nf, K)
         print(json.dumps(out), flush=True)
