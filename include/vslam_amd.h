@@ -28,7 +28,7 @@ extern "C" {
  * field: their layout belongs to the header a caller was compiled against.  mo_batch_io gets fields APPENDED per round, so a caller built
  * against an older header hands in a shorter struct than the library reads: every caller must be recompiled with the header of the library
  * it loads, and can check that at load time: mo_abi_version() == MO_ABI_VERSION. */
-#define MO_ABI_VERSION 5
+#define MO_ABI_VERSION 6
 int mo_abi_version(void);
 
 #define MO_OK 0
@@ -36,6 +36,7 @@ int mo_abi_version(void);
 #define MO_ERR_HIP (-2)       /* HIP runtime error (see mo_last_error) */
 #define MO_ERR_CAPACITY (-3)  /* caller buffer or internal capacity too small */
 #define MO_ERR_UNSUPPORTED (-4)
+#define MO_ERR_INDEX (-5)     /* a map point names a keyframe or keypoint that does not exist (Python's IndexError) */
 
 #define MO_ORDER_LIBSTDCXX 0 /* retainBest order of cv2 wheels linked against libstdc++ (Linux) */
 #define MO_ORDER_MSVC 1      /* retainBest order of cv2 wheels linked against the MSVC STL (Windows);
@@ -367,6 +368,73 @@ int mo_comm_init(mo_ctx*, const uint8_t id[128], int rank, int world);
 int mo_comm_destroy(mo_ctx*);
 int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows_max, int cap, int root, float* d_all,
                          int32_t* d_rows_all);
+
+/* ---- LocalMapper (local_mapper.py): a device-resident keyframe store and map (map_kernels.hip) ------------------------------------
+ * Keyframes and map points live on the device; the host keeps the reference's dicts around them (vslam_amd/mapper.py).
+ *   mo_map_add_keyframe      LocalMapper.add_keyframe (local_mapper.py:46-77) in one call, one synchronisation: the frame (by token of a
+ *                            resident result slot, else the host arrays) and its P = K [R|t] (row-major 3x4, computed by the caller like
+ *                            utils.compute_projection_matrix) go into the keyframe store; with two keyframes or more, the previous keyframe
+ *                            (query) is matched against this one (train) with `ratio` keeping queries with two neighbours, the fundamental
+ *                            matrix RANSAC runs at thr_px with the sampling stream (seed, pair_index) and its inliers, triangulated, are
+ *                            appended in query order (position X / w, colour of the previous keyframe's image at (int(x), int(y)) - gray
+ *                            [v, v, v], 3 channels as stored, outside [0, 0, 255] - observations {prev: queryIdx, new: trainIdx}, id =
+ *                            map size before the point).  From the second keyframe on, every map point is then culled (fewer than 2 observations, or the first
+ *                            observation in insertion order whose reprojection error with the P of keyframe POSITION kf_id exceeds 5 px),
+ *                            the survivors are compacted in order and the per-keyframe lists rebuilt.  kf_len / kf_redundant [n_kf] receive
+ *                            each list's length and the entries _cull_keyframes counts as redundant (local_mapper.py:270-285).
+ *                            MO_ERR_INDEX when an observation names a keyframe position or keypoint that does not exist (the map then
+ *                            holds the grown points, uncompacted).
+ *   mo_map_add_points        LocalMapper.update_map_points: n points appended as given (obs_off [n + 1] into obs_kf / obs_kp; ids >= 0;
+ *                            dref_kf / dref_row = the descriptor reference, opaque to the library).
+ *   mo_map_remove_keyframes  the removals _cull_keyframes decided: keyframe POSITIONS, renumbering the rest (observations keep stale ids).
+ *   mo_map_sizes             out[0] keyframes, [1] map points, [2] observations, [3] rows of the per-keyframe lists, [4] reserved, [5] slots.
+ *   mo_map_download          one field (MO_MAP_*), bytes = exactly its size.
+ *   mo_map_write_ply         utils.create_point_cloud_ply (utils.py:72-118) of the points with >= min_obs observations, byte for byte:
+ *                            floats as Python's repr of the double value, colours as stored.
+ *   mo_format_floats         that float formatting alone, one value per line (no GPU). */
+typedef struct mo_map mo_map;
+typedef struct {
+    double ratio;            /* 0.8 (local_mapper.py:124) */
+    double thr_px;           /* 3.0 (local_mapper.py:136) */
+    int32_t n_hyp;
+    uint64_t seed;
+    uint64_t pair_index;     /* sampling stream of this keyframe pair: the k-th pair of a run = MO_MODE_KEYFRAME's pair_index_base + k */
+} mo_map_kf_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n1 = keypoints of the previous keyframe */
+    int32_t* match_idx;      /* [n1][2] knn train indices */
+    uint8_t* match_pass;     /* [n1] ratio test */
+    uint8_t* inlier;         /* [n1] F-RANSAC inlier per query keypoint */
+    float* points;           /* [n1][3] triangulated inlier per query keypoint (NaN = none), before the cull */
+    int32_t* kf_len;         /* [n_kf] per-keyframe list lengths after the call */
+    int32_t* kf_redundant;   /* [n_kf] */
+    /* filled by the call */
+    double F[9];             /* NaN: no growth step or no model */
+    int32_t n_new;           /* points the growth step appended */
+    int32_t from_token;      /* 1: the keyframe was copied from its resident slot */
+    int64_t n_points, n_obs; /* map size after the cull */
+} mo_map_kf_out;
+#define MO_MAP_XYZ 0
+#define MO_MAP_COLOR 1
+#define MO_MAP_ID 2
+#define MO_MAP_OBS_OFF 3
+#define MO_MAP_OBS_KF 4
+#define MO_MAP_OBS_KP 5
+#define MO_MAP_DREF_KF 6
+#define MO_MAP_DREF_ROW 7
+#define MO_MAP_LIST_OFF 8
+#define MO_MAP_LIST_IDS 9
+mo_map* mo_map_create(mo_ctx*, int kf_slots, int kf_rows, int64_t pts_cap, int64_t obs_cap); /* initial capacities; NULL: mo_last_error(ctx) */
+void mo_map_destroy(mo_map*);
+int mo_map_add_keyframe(mo_map*, const mo_frame_ref* f, const double P[12], const uint8_t* img, int w, int h, int ch,
+                        const mo_map_kf_params*, mo_map_kf_out*);
+int mo_map_add_points(mo_map*, int n, const float* xyz, const uint8_t* col, const int32_t* id, const int32_t* obs_off, const int32_t* obs_kf,
+                      const int32_t* obs_kp, const int32_t* dref_kf, const int32_t* dref_row);
+int mo_map_remove_keyframes(mo_map*, const int32_t* positions, int n);
+int mo_map_sizes(mo_map*, int64_t out[6]);
+int mo_map_download(mo_map*, int field, void* dst, size_t bytes);
+int mo_map_write_ply(mo_map*, const char* path, int min_obs, int64_t* n_written);
+int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

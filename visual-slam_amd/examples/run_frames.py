@@ -113,6 +113,8 @@ def main(argv=None):
     ap.add_argument("--max-frames", type=int, default=30, help="frames of the synthetic sequence / cap on the input (0 = config's max_frames)")
     ap.add_argument("--grid", action="store_true", help="extract_features(distributed=True), the path Tracker.process_frame takes")
     ap.add_argument("--python-filters", action="store_true", help="tracking step through the per-method API (Python filter loops)")
+    ap.add_argument("--map", default="", help="PATH: keyframes into the device LocalMapper (vslam_amd.mapper), its PLY map written to PATH")
+    ap.add_argument("--keyframe-every", type=int, default=20, help="with --map: a keyframe every N frames (tracker.py:290)")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
@@ -127,7 +129,23 @@ def main(argv=None):
     state, last, poses, n_map, n_seen = "NOT_INITIALIZED", None, [], 0, 0
     t0 = time.perf_counter()
     if args.batch > 0:
+        if args.map:
+            ap.error("--map runs frame by frame: it cannot be combined with --batch")
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
+    mapper, first, ref_pose = None, None, np.eye(4)
+    if args.map:
+        from vslam_amd.mapper import LocalMapper
+        mapper = LocalMapper(K, args.map)
+
+    def track_pose(R, t, frame, kps, desc, idx):
+        """Tracker._update_pose (tracker.py:268-279) and the keyframe every N frames (tracker.py:114-118, 290)"""
+        nonlocal ref_pose
+        T = np.eye(4)
+        T[:3, :3] = R
+        T[:3, 3] = np.asarray(t).reshape(3)
+        ref_pose = ref_pose @ T
+        if mapper is not None and idx % args.keyframe_every == 0:
+            mapper.add_keyframe(frame, kps, desc, ref_pose)
     for idx, frame in enumerate(source):
         if n_seen >= limit:
             break
@@ -143,17 +161,26 @@ def main(argv=None):
         if state == "NOT_INITIALIZED":
             if initializer.first_frame_keypoints is None:
                 initializer.set_first_frame(kps, desc, frame)
+                first = (frame, kps, desc)
             else:
                 ok, R, t, pts, matches = initializer.initialize(kps, desc, matcher, frame)
                 if ok:
                     state, n_map = "TRACKING", len(pts)
                     poses.append((R, t))
                     print("frame %d: initialised, %d map points, t = %s" % (idx, n_map, np.round(t.ravel(), 3)))
+                    if mapper is not None:   # tracker.py:172-189: both frames as keyframes, then the initial map points
+                        T = np.eye(4)
+                        T[:3, :3] = R
+                        T[:3, 3] = np.asarray(t).reshape(3)
+                        mapper.add_keyframe(first[0], first[1], first[2], ref_pose)
+                        mapper.add_keyframe(frame, kps, desc, T)
+                        mapper.update_map_points([p for p in pts if isinstance(p, dict)])
         elif not args.python_filters:
             ok, T, inl = geom.track_from_last_frame(last[0], last[1], kps, desc, K, frame.shape, ratio_threshold=mt["ratio_threshold"],
                                                     threshold_percent=0.02)   # tracker.py:219
             if ok:
                 poses.append((T[:3, :3], T[:3, 3:4]))
+                track_pose(T[:3, :3], T[:3, 3], frame, kps, desc, idx)
                 if idx % 5 == 0:
                     print("frame %d: %d pose inliers, t = %s" % (idx, len(inl), np.round(T[:3, 3], 3)))
         else:
@@ -167,12 +194,16 @@ def main(argv=None):
                 if E is not None:
                     n_in, R, t, _ = geom.recover_pose(E, p1, p2, K, mask)                          # tracker.py:249
                     poses.append((R, t))
+                    track_pose(R, t, frame, kps, desc, idx)
                     if idx % 5 == 0:
                         print("frame %d: %d matches, %d pose inliers, t = %s" % (idx, len(m), n_in, np.round(t.ravel(), 3)))
         last = (kps, desc)
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s (%.1f frames/s through the Python drop-in classes), state %s, %d poses"
           % (n_seen, dt, n_seen / max(dt, 1e-9), state, len(poses)))
+    if mapper is not None:
+        mapper.save_map()
+        print("map statistics: %s" % mapper.get_map_statistics())
     return state, poses, n_map
 
 

@@ -14,8 +14,8 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # VSLAM_AMD_LIB: another build of the same library (A/B timing of kernel variants); default: the in-tree build
 LIB_PATH = os.environ.get("VSLAM_AMD_LIB") or os.path.join(_PKG_ROOT, "libvslam_amd.so")
 
-MO_OK, MO_ERR_ARG, MO_ERR_HIP, MO_ERR_CAPACITY, MO_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
-ABI_VERSION = 5  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
+MO_OK, MO_ERR_ARG, MO_ERR_HIP, MO_ERR_CAPACITY, MO_ERR_UNSUPPORTED, MO_ERR_INDEX = 0, -1, -2, -3, -4, -5
+ABI_VERSION = 6  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
 ORDER_LIBSTDCXX, ORDER_MSVC = 0, 1
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -68,6 +68,16 @@ class PairOut(C.Structure):
                 ("sel_dist", C.c_void_p), ("inlier", C.c_void_p), ("ransac", C.c_void_p), ("X", C.c_void_p),
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("n_sel", C.c_int32), ("n_good", C.c_int32),
                 ("n1", C.c_int32), ("n2", C.c_int32), ("token1", C.c_uint64), ("token2", C.c_uint64)]
+
+
+class MapKfParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("thr_px", C.c_double), ("n_hyp", C.c_int32), ("seed", C.c_uint64), ("pair_index", C.c_uint64)]
+
+
+class MapKfOut(C.Structure):
+    _fields_ = [("match_idx", C.c_void_p), ("match_pass", C.c_void_p), ("inlier", C.c_void_p), ("points", C.c_void_p), ("kf_len", C.c_void_p),
+                ("kf_redundant", C.c_void_p), ("F", C.c_double * 9), ("n_new", C.c_int32), ("from_token", C.c_int32),
+                ("n_points", C.c_int64), ("n_obs", C.c_int64)]
 
 
 class StreamParams(C.Structure):
@@ -139,6 +149,15 @@ SIGNATURES = {
     "mo_dbg_pyramid_level": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mo_dbg_fast_level": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mo_dbg_retain_best": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mo_map_create": (_vp, [_vp, _i, _i, C.c_int64, C.c_int64]),
+    "mo_map_destroy": (None, [_vp]),
+    "mo_map_add_keyframe": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mo_map_add_points": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_remove_keyframes": (_i, [_vp, _vp, _i]),
+    "mo_map_sizes": (_i, [_vp, _vp]),
+    "mo_map_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "mo_map_write_ply": (_i, [_vp, C.c_char_p, _i, _vp]),
+    "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None
@@ -254,6 +273,8 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
+            for m in list(getattr(self, "_maps", ())):  # device maps bound to this context (vslam_amd.mapper) go first
+                m.close()
             self.lib.mo_destroy(self.h)
             self.h = None
 

@@ -1,0 +1,383 @@
+"""LocalMapper on the device: the reference's orbslam2.local_mapper.LocalMapper (local_mapper.py) with its map held in HBM.
+
+The keyframe store, the map points (positions, colours, ids, observations in CSR form) and the per-keyframe lists live in the
+library's mo_map (map_kernels.hip).  One add_keyframe is one native call with one synchronisation: store -> growth of the
+(previous, new) keyframe pair (ratio-0.8 knn match, fundamental-matrix RANSAC at 3 px, triangulation) -> cull of every map point ->
+per-keyframe lists and the counts _cull_keyframes reads.  The host keeps what the reference's callers see: the keyframe dicts, a lazy
+sequence of map-point dicts, the co-visibility graph.
+
+Attach it to the reference's Tracker without editing the reference:
+    Tracker(K, local_mapper=vslam_amd.mapper.LocalMapper(K, "map.ply"))
+"""
+from collections import defaultdict
+from collections.abc import Sequence
+
+import ctypes as C
+import weakref
+
+import numpy as np
+
+import vslam_amd as V
+
+_N_HYP = 1024
+_SEED = 4096
+
+
+class _Keyframe(dict):
+    """a keyframe dict whose 'map_points' is read from the mapper's per-keyframe lists when asked for"""
+    __slots__ = ("_mapper", "_extra")
+
+    def __getitem__(self, key):
+        if key == "map_points" and not dict.__contains__(self, "map_points"):
+            return self._mapper._kf_list(self)
+        return dict.__getitem__(self, key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def __contains__(self, key):
+        return key == "map_points" or dict.__contains__(self, key)
+
+
+class _MapPoints(Sequence):
+    """LocalMapper.map_points: a Sequence of dicts materialised from the device map on access (one download per map version)"""
+
+    def __init__(self, mapper):
+        self._m = mapper
+
+    def __len__(self):
+        return self._m._n_points
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        n = len(self)
+        if i < 0:
+            i += n
+        if not 0 <= i < n:
+            raise IndexError("map point index out of range")
+        return self._m._point(i)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self._m._point(i)
+
+    def __bool__(self):
+        return len(self) > 0
+
+
+class LocalMapper:
+    """Same public methods and attributes as the reference's LocalMapper, with the same results.  Differences: map_points is a lazy
+    sequence (the dicts are built when read), get_map_statistics also works between update_map_points and the next keyframe (the
+    reference raises KeyError there on points without 'observed_keyframes'), positions of injected points are stored as float32."""
+
+    def __init__(self, camera_matrix, output_path=None, save_every_keyframe=True, context=None, n_hyp=_N_HYP, seed=_SEED,
+                 pair_index_base=0, capacity=(64, 2048, 1 << 16, 1 << 17)):
+        self.camera_matrix = camera_matrix
+        self.keyframes = []
+        self.output_path = output_path if output_path else "map.ply"
+        self.co_visibility_graph = defaultdict(lambda: defaultdict(int))
+        self.redundancy_threshold = 0.9
+        self.min_observations = 2
+        self.culling_threshold = 0.05
+        self.save_every_keyframe = save_every_keyframe
+        self.n_hyp, self.seed, self.pair_index_base = int(n_hyp), int(seed), int(pair_index_base)
+        self.ctx = context if context is not None else V.default_context()
+        self.lib = self.ctx.lib
+        kf_slots, rows, pts, obs = capacity
+        self._h = self.lib.mo_map_create(self.ctx.h, int(kf_slots), int(rows), int(pts), int(obs))
+        if not self._h:
+            raise V.NativeError(V.MO_ERR_HIP, self.lib.mo_last_error(self.ctx.h).decode())
+        if not hasattr(self.ctx, "_maps"):
+            self.ctx._maps = weakref.WeakSet()
+        self.ctx._maps.add(self)   # closing the context closes this map first
+        self._records = []        # every keyframe dict ever added, by store slot (the descriptor references)
+        self._rec_n = []          # their keypoint counts
+        self._injected = []       # the dicts given to update_map_points (dref_kf = -(j + 1))
+        self._n_points = 0
+        self._list_rows = []      # keyframe position -> row of the per-keyframe lists (None: empty list)
+        self._version = 0
+        self._cache = None
+        self._lists = None
+        self.last = None          # the growth step of the last add_keyframe (match lists, inlier mask, F, new points)
+        self.map_points = _MapPoints(self)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "h", None):
+            self.lib.mo_map_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc == V.MO_ERR_INDEX:
+            raise IndexError(self.lib.mo_last_error(self.ctx.h).decode())
+        if rc != V.MO_OK:
+            raise V.NativeError(rc, self.lib.mo_last_error(self.ctx.h).decode())
+
+    def set_output_path(self, output_path):
+        self.output_path = output_path
+
+    # ---- the reference's per-keyframe step ------------------------------------------------------------------------------------
+    def add_keyframe(self, image, keypoints, descriptors, pose):
+        from orbslam2.types import keypoints_to_array
+        from orbslam2.utils import compute_projection_matrix
+        kf = _Keyframe({"id": len(self.keyframes), "image": image.copy(), "keypoints": keypoints, "descriptors": descriptors,
+                        "pose": pose.copy()})
+        kf._mapper = self
+        kf._extra = []   # ids appended by a growth step whose cull raised (the reference's lists at that point)
+        slot = len(self._records)
+        token = V.resident_token(self.ctx, descriptors) if descriptors is not None else 0
+        kps_arr = V._resident_kps(descriptors) if token else None
+        if kps_arr is None or len(kps_arr) != len(keypoints):
+            token = 0
+            if isinstance(keypoints, np.ndarray) and keypoints.dtype == V.KP_DTYPE:
+                kps_arr = keypoints
+            else:
+                kps_arr = keypoints_to_array(keypoints) if len(keypoints) else np.zeros(0, V.KP_DTYPE)
+        kps_arr = np.ascontiguousarray(kps_arr, V.KP_DTYPE).reshape(-1)
+        desc = np.ascontiguousarray(descriptors if descriptors is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
+        n = len(kps_arr) if token else min(len(kps_arr), len(desc))
+        ref = V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n)
+        P = np.ascontiguousarray(compute_projection_matrix(pose[:3, :3], pose[:3, 3], self.camera_matrix), np.float64).reshape(12)
+        img = np.ascontiguousarray(image, np.uint8)
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        n_prev = self._rec_n[-1] if self.keyframes else 0
+        n_kf = len(self.keyframes) + 1
+        midx = np.full((max(n_prev, 1), 2), -1, np.int32)
+        mpass = np.zeros(max(n_prev, 1), np.uint8)
+        inl = np.zeros(max(n_prev, 1), np.uint8)
+        gpts = np.full((max(n_prev, 1), 3), np.nan, np.float32)
+        kf_len = np.zeros(n_kf, np.int32)
+        kf_red = np.zeros(n_kf, np.int32)
+        prm = V.MapKfParams(0.8, 3.0, self.n_hyp, self.seed, self.pair_index_base + max(slot - 1, 0))
+        out = V.MapKfOut(midx.ctypes.data, mpass.ctypes.data, inl.ctypes.data, gpts.ctypes.data, kf_len.ctypes.data, kf_red.ctypes.data)
+        self.keyframes.append(kf)
+        self._records.append(kf)
+        self._version += 1
+        self._cache = None
+        self._lists = None
+        rc = self.lib.mo_map_add_keyframe(self._h, C.byref(ref), V._ptr(P), V._ptr(img), img.shape[1], img.shape[0], ch, C.byref(prm), C.byref(out))
+        self._rec_n.append(n)
+        n_before = self._n_points
+        self._sync_size()
+        if rc == V.MO_ERR_INDEX:
+            # the reference raises inside _cull_map_points: the grown points, their list entries and the co-visibility increments
+            # are already there (local_mapper.py:171-187); the lists of the previous cull stay as they were
+            new = list(range(n_before, n_before + int(out.n_new)))
+            if new:
+                self.keyframes[-2]._extra.extend(new); kf._extra.extend(new)
+                self.co_visibility_graph[self.keyframes[-2]["id"]][kf["id"]] += len(new)
+                self.co_visibility_graph[kf["id"]][self.keyframes[-2]["id"]] += len(new)
+            self._list_rows.append(None)
+        self._check(rc)
+        self.last = {"match_idx": midx[:n_prev], "match_pass": mpass[:n_prev].astype(bool), "inlier": inl[:n_prev].astype(bool),
+                     "points": gpts[:n_prev], "kf_len": kf_len, "kf_redundant": kf_red,
+                     "F": np.array(out.F).reshape(3, 3), "n_new": int(out.n_new), "from_token": bool(out.from_token)}
+        if n_kf >= 2 and out.n_new > 0:
+            prev_id, cur_id = self.keyframes[-2]["id"], kf["id"]
+            self.co_visibility_graph[prev_id][cur_id] += int(out.n_new)
+            self.co_visibility_graph[cur_id][prev_id] += int(out.n_new)
+        if n_kf < 2:   # (local_mapper.py:75: no map update, no save, before the second keyframe)
+            self._list_rows = [None]
+            return
+        self._list_rows = list(range(n_kf))
+        for k in self.keyframes:
+            k._extra = []
+        if len(self.keyframes) > 3:
+            self._cull_keyframes(kf_len, kf_red)
+        if self.save_every_keyframe:
+            self._save_map()
+
+    def _cull_keyframes(self, kf_len, kf_red):
+        """local_mapper.py:253-315 on the counts the device produced: list length and the listed ids whose first map point with
+        that id has >= 3 observations in other keyframes"""
+        remove = []
+        for i in range(1, len(self.keyframes) - 2):
+            if kf_len[i] < 20:
+                continue
+            if kf_red[i] / kf_len[i] > self.redundancy_threshold:
+                remove.append(i)
+        if not remove:
+            for i, kf in enumerate(self.keyframes):
+                kf["id"] = i
+            return
+        for idx in sorted(remove, reverse=True):
+            kf_id = self.keyframes[idx]["id"]
+            for other in self.co_visibility_graph[kf_id]:
+                if other != kf_id:
+                    del self.co_visibility_graph[other][kf_id]
+            del self.co_visibility_graph[kf_id]
+            self.keyframes.pop(idx)
+            self._list_rows.pop(idx)
+        pos = np.array(sorted(remove), np.int32)
+        self._check(self.lib.mo_map_remove_keyframes(self._h, V._ptr(pos), len(pos)))
+        for i, kf in enumerate(self.keyframes):
+            kf["id"] = i
+
+    def update_map_points(self, new_map_points):
+        """Appends the points as given.  Points without 'observed_keyframes' (the initializer's carry 'observed_frames') count as
+        0 observations: the next keyframe culls them, as in the reference."""
+        pts = list(new_map_points)
+        if not pts:
+            return
+        n = len(pts)
+        xyz = np.zeros((n, 3), np.float32)
+        col = np.zeros((n, 3), np.uint8)
+        ids = np.zeros(n, np.int32)
+        off = np.zeros(n + 1, np.int32)
+        okf, okp = [], []
+        dkf = np.zeros(n, np.int32)
+        drow = np.zeros(n, np.int32)
+        for i, mp in enumerate(pts):
+            xyz[i] = np.asarray(mp["position"], np.float64).reshape(3)
+            c = np.asarray(mp.get("color", (0, 0, 0))).reshape(-1)
+            col[i] = c[:3] if c.size >= 3 else np.repeat(c[:1], 3)
+            ids[i] = int(mp.get("id", 0))
+            obs = mp.get("observed_keyframes", {})
+            for k, v in obs.items():
+                okf.append(int(k)); okp.append(int(v))
+            off[i + 1] = len(okf)
+            self._injected.append(mp)
+            dkf[i] = -len(self._injected)
+        okf = np.array(okf if okf else [0], np.int32)
+        okp = np.array(okp if okp else [0], np.int32)
+        self._check(self.lib.mo_map_add_points(self._h, n, V._ptr(xyz), V._ptr(col), V._ptr(ids), V._ptr(off), V._ptr(okf), V._ptr(okp),
+                                               V._ptr(dkf), V._ptr(drow)))
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+
+    # ---- device map -> host -----------------------------------------------------------------------------------------------------
+    def _sync_size(self):
+        s = (C.c_int64 * 6)()
+        self._check(self.lib.mo_map_sizes(self._h, s))
+        self._n_points = int(s[1])
+        self._n_obs = int(s[2])
+        self._list_n = int(s[3])
+
+    def _download(self, field, dtype, count, shape=None):
+        a = np.empty(count, dtype)
+        self._check(self.lib.mo_map_download(self._h, field, V._ptr(a) if count else None, a.nbytes))
+        return a.reshape(shape) if shape else a
+
+    def arrays(self):
+        """the map as arrays: xyz [n][3] f32, color [n][3] u8, id, obs_off [n + 1], obs_kf, obs_kp, dref_kf, dref_row"""
+        if self._cache is None:
+            n, no = self._n_points, self._n_obs
+            self._cache = {"xyz": self._download(0, np.float32, n * 3, (n, 3)), "color": self._download(1, np.uint8, n * 3, (n, 3)),
+                           "id": self._download(2, np.int32, n), "obs_off": self._download(3, np.int32, n + 1),
+                           "obs_kf": self._download(4, np.int32, no), "obs_kp": self._download(5, np.int32, no),
+                           "dref_kf": self._download(6, np.int32, n), "dref_row": self._download(7, np.int32, n)}
+        return self._cache
+
+    def list_arrays(self):
+        """per-keyframe lists of the last cull: offsets [rows + 1], ids (rows in the keyframe positions of that cull)"""
+        if self._lists is None:
+            rows = self._list_n
+            if rows == 0:
+                self._lists = (np.zeros(1, np.int32), np.zeros(0, np.int32))
+            else:
+                lo = self._download(8, np.int32, rows + 1)
+                self._lists = (lo, self._download(9, np.int32, int(lo[-1])))
+        return self._lists
+
+    def _kf_list(self, kf):
+        pos = next((i for i, k in enumerate(self.keyframes) if k is kf), None)
+        if pos is None or pos >= len(self._list_rows) or self._list_rows[pos] is None:
+            return list(kf._extra)
+        lo, ids = self.list_arrays()
+        r = self._list_rows[pos]
+        if r + 1 >= len(lo):
+            return list(kf._extra)
+        return ids[lo[r]:lo[r + 1]].tolist() + kf._extra
+
+    def _point(self, i):
+        a = self.arrays()
+        d = int(a["dref_kf"][i])
+        if d < 0:
+            return self._injected[-d - 1]
+        o0, o1 = int(a["obs_off"][i]), int(a["obs_off"][i + 1])
+        return {"id": int(a["id"][i]), "position": a["xyz"][i].copy(), "color": a["color"][i].copy(),
+                "observed_keyframes": dict(zip(a["obs_kf"][o0:o1].tolist(), a["obs_kp"][o0:o1].tolist())),
+                "descriptor": self._records[d]["descriptors"][int(a["dref_row"][i])]}
+
+    def _obs_counts(self):
+        off = self.arrays()["obs_off"]
+        return np.diff(off)
+
+    # ---- output ------------------------------------------------------------------------------------------------------------------
+    def _save_map(self):
+        if self._n_points == 0:
+            return
+        nw = C.c_int64(0)
+        self._check(self.lib.mo_map_write_ply(self._h, str(self.output_path).encode(), self.min_observations, C.byref(nw)))
+        if nw.value:
+            print(f"Saved map with {nw.value} points to {self.output_path}")
+
+    def save_map(self):
+        """writes the PLY now (for save_every_keyframe=False)"""
+        self._save_map()
+
+    def _filter_map_points(self):
+        a = self.arrays()
+        keep = self._obs_counts() >= self.min_observations
+        return a["xyz"][keep], a["color"][keep]
+
+    def get_map_statistics(self):
+        n = self._n_points
+        cnt = self._obs_counts() if n else np.zeros(0)
+        return {"num_keyframes": len(self.keyframes), "num_map_points": n,
+                "num_filtered_points": int((cnt >= self.min_observations).sum()),
+                "avg_observations_per_point": np.mean(cnt) if n else 0,
+                "map_density": n / len(self.keyframes) if len(self.keyframes) > 0 else 0}
+
+    def visualize_map(self, width=800, height=600):
+        """top-down (x, z) drawing of the filtered points and the keyframe trajectory; needs cv2 (drawing is not ported)"""
+        try:
+            import cv2
+        except ImportError as e:
+            raise ImportError("LocalMapper.visualize_map draws with cv2, which is not installed") from e
+        canvas = np.zeros((height, width, 3), np.uint8)
+        pts, cols = self._filter_map_points()
+        if len(pts) == 0:
+            return canvas
+        lo, ext = pts.min(0), pts.max(0) - pts.min(0)
+        m = 50
+        sx = (width - 2 * m) / ext[0] if ext[0] > 0 else 1
+        sz = (height - 2 * m) / ext[2] if ext[2] > 0 else 1
+        sc = min(sx, sz)
+
+        def to_px(p):
+            return int(m + (p[0] - lo[0]) * sc), int(m + (p[2] - lo[2]) * sc)
+        for p, c in zip(pts, cols):
+            cv2.circle(canvas, to_px(p), 1, c.tolist(), -1)
+        centres = self.get_camera_trajectory()
+        if len(self.keyframes) > 1:
+            for a, b in zip(centres[:-1], centres[1:]):
+                cv2.line(canvas, to_px(a), to_px(b), (0, 255, 0), 2)
+            cv2.circle(canvas, to_px(centres[-1]), 5, (0, 0, 255), -1)
+        font = cv2.FONT_HERSHEY_SIMPLEX
+        cv2.putText(canvas, f"Map Points: {len(pts)}", (10, 20), font, 0.5, (255, 255, 255), 1)
+        cv2.putText(canvas, f"Keyframes: {len(self.keyframes)}", (10, 40), font, 0.5, (255, 255, 255), 1)
+        return canvas
+
+    def get_camera_trajectory(self):
+        cs = [-kf["pose"][:3, :3].T @ kf["pose"][:3, 3] for kf in self.keyframes]
+        return np.array(cs) if cs else np.array([])
+
+    def get_keyframe_by_id(self, keyframe_id):
+        return next((kf for kf in self.keyframes if kf["id"] == keyframe_id), None)
+
+    def get_map_point_by_id(self, map_point_id):
+        hit = np.flatnonzero(self.arrays()["id"] == map_point_id) if self._n_points else []
+        return self._point(int(hit[0])) if len(hit) else None
+
+    def find_connected_keyframes(self, keyframe_id, min_connections=15):
+        if keyframe_id not in self.co_visibility_graph:
+            return []
+        return [k for k, n in self.co_visibility_graph[keyframe_id].items() if n >= min_connections]
