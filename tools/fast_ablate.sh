@@ -14,7 +14,7 @@ for v in s1 s2a s2 s3; do
 import sys
 f, v = sys.argv[1], sys.argv[2]
 s = open(f).read()
-stage_end = "    if (tid == 0) s_ncorner = 0;\n    __syncthreads();\n"
+stage_end = "    for (int i = tid; i < ((rows + 2) * SW + 3) >> 2; i += NT) ((uint32_t*)s_score)[i] = 0;  // score 0 unless phase 2b says otherwise\n    __syncthreads();\n"
 assert stage_end in s
 if v == "s1":
     s = s.replace(stage_end, stage_end + "    if (P.nlevels > 0) return;\n", 1)
@@ -25,11 +25,11 @@ elif v == "s2a":
                  ("if (qb > 0) score_one(wq[FAST_STACK - 1 - min(lane, qb - 1)], 0xFF, lane < qb);", 'if (qb > 0) asm volatile("" :: "v"(wq[FAST_STACK - 1 - min(lane, qb - 1)]));')):
         assert a in s, a
         s = s.replace(a, b)
-    a = "    // ---- 3. NMS + border filter on the listed corners"
+    a = "    // ---- 3. NMS + border filter on the pixels with a non-zero score"
     assert a in s
     s = s.replace(a, "    if (P.nlevels > 0) return;\n" + a, 1)
 elif v == "s2":
-    a = "    // ---- 3. NMS + border filter on the listed corners"
+    a = "    // ---- 3. NMS + border filter on the pixels with a non-zero score"
     assert a in s
     s = s.replace(a, "    if (P.nlevels > 0) return;\n" + a, 1)
 elif v == "s3":

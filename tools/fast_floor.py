@@ -15,7 +15,7 @@ network; inlined at four call sites), 3 NMS (9 ds_read_u8 + ds_or), 4 compaction
 Step 2 (tools/fast_floor.sh on the GPU box): SQ_INSTS_VALU / SQ_INSTS_LDS per launch of the full kernel and of the ablation builds
 (tools/fast_ablate.sh: s1 = staging only, s2a = + compass, s2 = + scoring, s3 = + NMS) -> DYNAMIC instruction counts per phase (differences).
 Step 3 (--pmc <json>): floor_ms = sum over phases of dynamic VALU count x (static class mix of the phase's blocks) x class cost / (1024 SIMDs x clock);
-LDS floor likewise per CU; written to profiles/r04_fast_floor.txt.
+LDS floor likewise per CU; written to profiles/r0x_fast_floor.txt (--out).
 """
 import argparse
 import collections
@@ -49,7 +49,7 @@ def classify(ins):
 
 
 def assembly():
-    out = "/tmp/orb_kernels_r04.s"
+    out = "/tmp/orb_kernels_fast_floor.s"
     src = os.path.join(ROOT, "visual-slam_amd", "csrc", "orb_kernels.hip")
     if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S",
@@ -82,7 +82,7 @@ def kernel_blocks(lines, name="_Z6k_fastILi608ELi256EE"):
 def content_of(h, mn):
     """what a block is, by content: 'stage' (global loads + LDS writes), '2a' (compass: masked 16-bit stack pushes + 16-bit min / max), '2b' (the
     score network: >= 40 16-bit min / max), 'nms' (ds_or of the keep bitmap / mulhi + byte reads), '' (control, glue)"""
-    minmax = sum(v for k, v in mn.items() if k.startswith(("v_min_i16", "v_max_i16")))
+    minmax = sum(v for k, v in mn.items() if k.startswith(("v_min_i16", "v_max_i16", "v_min_u16", "v_max_u16")))
     wr = sum(v for k, v in mn.items() if k.startswith("ds_write"))
     rd8 = sum(v for k, v in mn.items() if k.startswith("ds_read_u8"))
     if minmax >= 40:

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "select_replay.h"
+#include "fast_score.h"
 
 __constant__ __attribute__((aligned(16))) int8_t c_pattern[256 * 4] = {
 #include "orb_pattern.inc"
@@ -532,16 +533,19 @@ __device__ __forceinline__ s16x2 pk_max(s16x2 a, s16x2 b) { return __builtin_ele
 //  1. the strip's pixels (+4 rows / +3 columns of halo) are staged in LDS with aligned dword loads
 //  2. FAST-9 score of every pixel of the strip and its 1-px ring -> u8 score band in LDS (0 = no corner);
 //     work is dealt to the 4 wavefronts in (row, 64-column) units
-//  3. 3x3 non-max suppression + border filter + raster-ordered compaction.  Only pixels with a non-zero score (about 7 %
-//     on textured frames) can be kept, so phase 2b also lists them (bounded LDS list); after the barrier one lane per
-//     LISTED corner compares it with its 8 neighbours and sets its bit in a row-major bitmap of the strip, and the
-//     compaction walks the bitmap words (popcount -> block scan -> emit in raster order).  A strip with more corners than
-//     the list holds (noise at threshold 0) falls back to a dense scan of the score band that fills the same bitmap.
+//  3. 3x3 non-max suppression + border filter + raster-ordered compaction.  Only pixels with a non-zero score (about a quarter
+//     on the SURVEY-8d texture) can be kept: the wavefronts scan the score band a dword per lane, compact the non-zero positions
+//     by ballot into per-wavefront LDS queues, and one lane per queued position compares it with its 8 neighbours and sets its
+//     bit in a row-major bitmap of the strip; the compaction walks the bitmap words (popcount -> block scan -> emit in raster order).
 // 16-bit VOP2 forms (values in the low half of a VGPR): on gfx950 v_sub_u16 / v_min_i16 / v_max_i16 issue at the full
 // vector rate while v_min_i32 / v_max_i32 and every packed (VOP3P) form take twice as long (tools/ubench.hip)
 __device__ __forceinline__ int sub16(int a, int b) { int r; asm("v_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ int min16(int a, int b) { int r; asm("v_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ int max16(int a, int b) { int r; asm("v_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ int add16(int a, int b) { int r; asm("v_add_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// unsigned forms for raw pixel values 0..255 (any upper bits of the operands are ignored)
+__device__ __forceinline__ int min16u(int a, int b) { int r; asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ int max16u(int a, int b) { int r; asm("v_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // lane mask of (short)a > (short)b: the compare writes the wave-wide mask directly (inactive lanes read as 0)
 __device__ __forceinline__ unsigned long long ballot_gt16(int a, int b) {
     unsigned long long m;
@@ -558,9 +562,9 @@ __device__ __forceinline__ void lds_store_u16_masked(unsigned long long mask, ui
                  : "=&s"(keep) : "s"(mask), "v"(addr), "v"(val) : "memory", "scc");
 }
 
-#define FAST_CORNER_CAP 896   // listed corners per strip (typical: 300); more -> dense fallback
 #define FAST_KEEP_WORDS 512   // strip_rows * bw <= 16384 candidate positions (mo_build_plan)
 #define FAST_STACK 384        // u16 entries per wavefront: two stacks of <= 191
+#define FAST_NMS_Q 128        // u16 entries per wavefront: the phase-3 queue of <= 64 + 63 positions
 
 template <int TW, int NT>  // TW: LDS tile pitch, a compile-time constant so the 16 circle reads use immediate offsets; NT: threads
 __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict__ strip_tab, uint32_t inv_per, int strip0,
@@ -586,11 +590,10 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     // per-wavefront stacks of the pixels that pass the compass pre-test (row << 12 | column): the darker-arc candidates grow
     // up from [0], the brighter-arc candidates down from [FAST_STACK - 1]; each holds <= 63 + 128 entries
     __shared__ __attribute__((aligned(16))) uint16_t s_wq[NW][FAST_STACK];
-    __shared__ uint16_t s_corner[FAST_CORNER_CAP];  // band positions (row * SW + column) of the pixels with a non-zero score
-    __shared__ int s_ncorner;
-    // bit (rr * bw + xx) set <=> border-region pixel survives the 3x3 NMS; overlays the stacks, which are dead by then
+    // bit (rr * bw + xx) set <=> border-region pixel survives the 3x3 NMS; overlays the stacks, which are dead by then, and is followed
+    // there by the per-wavefront queues of phase 3
     uint32_t* const s_keep = (uint32_t*)&s_wq[0][0];
-    static_assert(sizeof(uint16_t) * NW * FAST_STACK >= 4 * FAST_KEEP_WORDS, "bitmap overlays the stacks");
+    static_assert(sizeof(uint16_t) * NW * FAST_STACK >= 4 * FAST_KEEP_WORDS + sizeof(uint16_t) * NW * FAST_NMS_Q, "bitmap and queues overlay the stacks");
     const uint8_t* img = level_ptr(P, L, gray, pyr, frame);
     const int t = P.fast_threshold;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -624,7 +627,6 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
         }
     }
     for (int i = tid; i < ((rows + 2) * SW + 3) >> 2; i += NT) ((uint32_t*)s_score)[i] = 0;  // score 0 unless phase 2b says otherwise
-    if (tid == 0) s_ncorner = 0;
     __syncthreads();
 
     // ---- 2. scores.
@@ -638,7 +640,6 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     //     cannot exceed -L).  One pixel per lane, 16-bit VOP2 min/max/sub: measured on MI355X (tools/ubench.hip) these issue
     //     at 2.3 cycles per wavefront, twice the rate of the packed (v_pk_*) and 32-bit min/max forms.
     typedef const volatile __attribute__((address_space(3))) uint8_t lds_cvu8;  // volatile: byte reads stay separate
-    const int t_list = max(t, 1);  // a pixel is listed for phase 3 when its stored score (L - 1 for L > t) is non-zero
     // stack entry = row << xbits | column: 16-row strips exist only for bw <= 1024 (strip_rows * bw <= 16384), narrower strips
     // have <= 10 scored rows and bw + 2 <= 4096
     const int xbits = R > 8 ? 11 : 12;
@@ -646,41 +647,24 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     auto score_one = [&](uint32_t e, int flip, bool own) {  // own: not a filler lane
         const int r = e >> xbits, x = e & xmask;
         const int pos = r * SW + x;
-        // flip (wave-uniform) = 0xFF: brighter-arc polarity, bytes complemented: (255 - v) - (255 - p) = p - v
+        // flip (wave-uniform, a constant at every call site) = 0xFF: brighter-arc polarity.  On the raw pixels (fast_score.h): darker arc
+        // L = v - min over arcs of max9(p), brighter arc L = max over arcs of min9(p) - v, the same network with min and max exchanged.
+        // (Written as plain 16-bit C the compiler fuses pairs into v_min3 / v_max3, which issue at half rate: 0.785 against 0.735 ms
+        // per 256 frames, profiles/r03_ab_fast16.txt - hence the VOP2 forms by inline asm.)
         lds_cvu8* p = (lds_cvu8*)&s_tile[(r + 3) * TW + x + 3 + lead];
-        // d = centre - circle pixel for BOTH polarities: the brighter-arc score max over arcs of min9(-d) = -(min over arcs of max9(d)) runs
-        // the same network with min and max exchanged (flip is a constant at every call site) and negates the result, instead of
-        // complementing all 17 pixels.  (Written as plain 16-bit C the compiler fuses pairs into v_min3 / v_max3_i16, which issue at
-        // half rate: 0.785 against 0.735 ms per 256 frames, profiles/r03_ab_fast16.txt - hence the VOP2 forms by inline asm.)
         const int v = (int)p[0];
-        int d[16];
-#define FAST_D(k, o) d[k] = sub16(v, (int)p[o]);
-        FAST_D(0, 3 * TW)        FAST_D(1, 3 * TW + 1)    FAST_D(2, 2 * TW + 2)    FAST_D(3, TW + 3)
-        FAST_D(4, 3)             FAST_D(5, -TW + 3)       FAST_D(6, -2 * TW + 2)   FAST_D(7, -3 * TW + 1)
-        FAST_D(8, -3 * TW)       FAST_D(9, -3 * TW - 1)   FAST_D(10, -2 * TW - 2)  FAST_D(11, -TW - 3)
-        FAST_D(12, -3)           FAST_D(13, TW - 3)       FAST_D(14, 2 * TW - 2)   FAST_D(15, 3 * TW - 1)
-#undef FAST_D
-        auto lo = [flip](int a, int b2) { return flip ? max16(a, b2) : min16(a, b2); };
-        auto hi = [flip](int a, int b2) { return flip ? min16(a, b2) : max16(a, b2); };
-        int mn3[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) mn3[i] = lo(d[i], lo(d[(i + 1) & 15], d[(i + 2) & 15]));
-        int Ls = lo(mn3[0], lo(mn3[3], mn3[6]));
-#pragma unroll
-        for (int i = 1; i < 16; i++) Ls = hi(Ls, lo(mn3[i], lo(mn3[(i + 3) & 15], mn3[(i + 6) & 15])));
-        const int L = flip ? -(int)(short)Ls : (int)(short)Ls;
+        int q[16];
+#define FAST_P(k, o) q[k] = (int)p[o];
+        FAST_P(0, 3 * TW)        FAST_P(1, 3 * TW + 1)    FAST_P(2, 2 * TW + 2)    FAST_P(3, TW + 3)
+        FAST_P(4, 3)             FAST_P(5, -TW + 3)       FAST_P(6, -2 * TW + 2)   FAST_P(7, -3 * TW + 1)
+        FAST_P(8, -3 * TW)       FAST_P(9, -3 * TW - 1)   FAST_P(10, -2 * TW - 2)  FAST_P(11, -TW - 3)
+        FAST_P(12, -3)           FAST_P(13, TW - 3)       FAST_P(14, 2 * TW - 2)   FAST_P(15, 3 * TW - 1)
+#undef FAST_P
+        auto mn = [](int a, int b2) { return min16u(a, b2); };
+        auto mx = [](int a, int b2) { return max16u(a, b2); };
+        const int L = flip ? sub16(fast_arc_extreme(q, mn, mx), v) : sub16(v, fast_arc_extreme(q, mx, mn));
         const int b = (int)(short)L;
         if (own && b > t) s_score[pos] = (uint8_t)(b - 1);  // the band is zero-filled; the other polarity of the pixel writes nothing
-        // list the corners for phase 3 (order is irrelevant): one LDS atomic per wavefront call
-        const bool c = own && b > t_list;
-        const unsigned long long m = __ballot(c);
-        if (m) {  // wave-uniform
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_ncorner, __popcll(m));
-            base = __builtin_amdgcn_readfirstlane(base);
-            const int o = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (c && o < FAST_CORNER_CAP) s_corner[o] = (uint16_t)pos;
-        }
     };
     {
         uint16_t* wq = s_wq[wv];
@@ -691,7 +675,7 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
         int ra = 0, ja = wv, rb = 0, jb = wv + NW;
         while (ja >= nxc) { ja -= nxc; ra++; }
         while (jb >= nxc) { jb -= nxc; rb++; }
-        const int tv = t, ntv = -t;
+        const int tv = t;
         // branch-free: lanes past the last scored column read a clamped (valid) address and are masked out of the result;
         // the window base sits 3 rows and 3 columns before the pixel so that all five reads use non-negative immediates.
         // largest of the four adjacent-pair minima > t <=> two adjacent differences above t; smallest of the pair maxima < -t likewise
@@ -701,19 +685,14 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
             const unsigned long long valid = rem >= 64 ? ~0ull : (1ull << rem) - 1ull;
             const uint8_t* w = &s_tile[r * TW + lead + min(x, SW - 1)];
             const int v = w[3 * TW + 3];
-            const int d0 = sub16(v, w[6 * TW + 3]), d4 = sub16(v, w[3 * TW + 6]), d8 = sub16(v, w[3]), d12 = sub16(v, w[3 * TW]);
-#ifdef FAST_COMPASS_ANY2
-            const int mn_a = min16(d0, d4), mx_a = max16(d0, d4), mn_b = min16(d8, d12), mx_b = max16(d8, d12);
-            const int second_hi = max16(max16(min16(mx_a, mx_b), mn_a), mn_b);
-            const int second_lo = min16(min16(max16(mn_a, mn_b), mx_a), mx_b);
-#else
-            // two ADJACENT compass pixels (a 9-arc holds two or three consecutive multiples of 4): 14 instead of 10 min / max, but 0.62
-            // instead of 0.67 survivors per pixel on the SURVEY-8d texture
-            const int second_hi = max16(max16(min16(d0, d4), min16(d4, d8)), max16(min16(d8, d12), min16(d12, d0)));
-            const int second_lo = min16(min16(max16(d0, d4), max16(d4, d8)), min16(max16(d8, d12), max16(d12, d0)));
-#endif
-            const unsigned long long md = ballot_gt16(second_hi, tv) & valid;   // centre above >= 2 compass pixels by more than t
-            const unsigned long long mb = ballot_gt16(ntv, second_lo) & valid;  // centre below >= 2 compass pixels by more than t
+            const int p0 = w[6 * TW + 3], p4 = w[3 * TW + 6], p8 = w[3], p12 = w[3 * TW];
+            // two ADJACENT compass pixels (a 9-arc holds two or three consecutive multiples of 4; 0.62 instead of 0.67 survivors per pixel
+            // on the SURVEY-8d texture than with any two), on the raw pixels: v - t > (smallest of the adjacent-pair maxima) <=> two
+            // adjacent differences v - p above t; (largest of the adjacent-pair minima) > v + t likewise for the brighter side
+            const int pair_hi = min16u(min16u(max16u(p0, p4), max16u(p4, p8)), min16u(max16u(p8, p12), max16u(p12, p0)));
+            const int pair_lo = max16u(max16u(min16u(p0, p4), min16u(p4, p8)), max16u(min16u(p8, p12), min16u(p12, p0)));
+            const unsigned long long md = ballot_gt16(sub16(v, tv), pair_hi) & valid;  // centre above >= 2 compass pixels by more than t
+            const unsigned long long mb = ballot_gt16(pair_lo, add16(v, tv)) & valid;  // centre below >= 2 compass pixels by more than t
             const uint32_t e = (uint32_t)((r << xbits) | x);
             const uint32_t wq_lds = (uint32_t)(uintptr_t)wq;  // LDS byte address of this wavefront's stacks
             lds_store_u16_masked(md, wq_lds + 2u * (uint32_t)(qd + __builtin_amdgcn_mbcnt_hi((unsigned)(md >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)md, 0u))), e);
@@ -744,34 +723,49 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     for (int i = tid; i < FAST_KEEP_WORDS; i += NT) s_keep[i] = 0;  // the stacks are dead: their space becomes the keep bitmap
     __syncthreads();
 
-    // ---- 3. NMS + border filter on the listed corners -> bitmap -> raster-ordered compaction
+    // ---- 3. NMS + border filter on the pixels with a non-zero score -> bitmap -> raster-ordered compaction
     const int nitems = rows * lv.bw;
     {
-        const int nc = s_ncorner;  // block-uniform
         const uint32_t inv_sw = 0xFFFFFFFFu / (uint32_t)SW + 1u;  // p / SW == mulhi(p, inv_sw) while p * SW < 2^32 (p < 65536, SW <= 16386)
         auto nms_at = [&](int p) {  // band position p = r * SW + x: keep <=> inside the border region and strictly above its 8 neighbours
             const int r = (int)__umulhi((uint32_t)p, inv_sw), x = p - r * SW;
             if (r < 1 || r > rows || x < 1 || x > lv.bw) return;
             const uint8_t* c = &s_score[p];
             const int mid = c[0];
-            const int nb = max(max(max((int)c[-SW - 1], (int)c[-SW]), max((int)c[-SW + 1], (int)c[-1])),
-                               max(max((int)c[1], (int)c[SW - 1]), max((int)c[SW], (int)c[SW + 1])));
-            if (mid > nb) {
+            const int nb = max16u(max16u(max16u((int)c[-SW - 1], (int)c[-SW]), max16u((int)c[-SW + 1], (int)c[-1])),
+                                  max16u(max16u((int)c[1], (int)c[SW - 1]), max16u((int)c[SW], (int)c[SW + 1])));
+            if ((uint16_t)mid > (uint16_t)nb) {
                 const int i = (r - 1) * lv.bw + (x - 1);
                 atomicOr(&s_keep[i >> 5], 1u << (i & 31));
             }
         };
-        if (nc <= FAST_CORNER_CAP) {
-            for (int k = tid; k < nc; k += NT) nms_at(s_corner[k]);
-        } else {  // the list overflowed: dense scan of the score band, one dword (4 positions) per lane and trip
-            const int nband = (rows + 2) * SW;
-            for (int k = tid; 4 * k < nband; k += NT) {
-                uint32_t w = ((const uint32_t*)s_score)[k];
+        // each wavefront scans its share of the band rows 1..rows, one dword (4 positions) per lane and trip, and compacts the positions
+        // with a non-zero score by ballot into its queue (64 + 63 entries at most); every 64 queued positions get one nms_at call with all
+        // 64 lanes busy.  On textured frames about a quarter of the band is non-zero (1330 of the 5800 positions of a 640-wide level-0
+        // strip), more than a fixed list filled in phase 2b could hold within the LDS budget of 8 workgroups per CU.
+        uint16_t* const nq = (uint16_t*)(s_keep + FAST_KEEP_WORDS) + wv * FAST_NMS_Q;
+        const uint32_t nq_lds = (uint32_t)(uintptr_t)nq;
+        const int k_end = ((rows + 1) * SW + 3) >> 2;  // (<= the zero-filled dwords of the band)
+        int qn = 0;  // wave-uniform queue fill
+        for (int k0 = (SW >> 2) + (wv << 6); k0 < k_end; k0 += NT) {
+            const int k = k0 + lane;
+            const uint32_t w = k < k_end ? ((const uint32_t*)s_score)[k] : 0u;
 #pragma unroll
-                for (int bq = 0; bq < 4; bq++)
-                    if (((w >> (8 * bq)) & 0xFFu) && 4 * k + bq < nband) nms_at(4 * k + bq);
+            for (int bq = 0; bq < 4; bq++) {
+                const unsigned long long m = __ballot((w & (0xFFu << (8 * bq))) != 0u);
+                lds_store_u16_masked(m, nq_lds + 2u * (uint32_t)(qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))),
+                                     (uint32_t)(4 * k + bq));
+                qn += __popcll(m);
+                if (qn >= 64) {  // wave-uniform
+                    replay::wave_sync();
+                    qn -= 64;
+                    nms_at(nq[qn + lane]);
+                    replay::wave_sync();  // the entries just read may be overwritten by the next pushes
+                }
             }
         }
+        replay::wave_sync();
+        if (lane < qn) nms_at(nq[lane]);
     }
     __syncthreads();
     const int nwords = (nitems + 31) >> 5, wpt = (nwords + NT - 1) / NT;  // wpt <= 2
