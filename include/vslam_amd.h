@@ -28,7 +28,7 @@ extern "C" {
  * field: their layout belongs to the header a caller was compiled against.  mo_batch_io gets fields APPENDED per round, so a caller built
  * against an older header hands in a shorter struct than the library reads: every caller must be recompiled with the header of the library
  * it loads, and can check that at load time: mo_abi_version() == MO_ABI_VERSION. */
-#define MO_ABI_VERSION 6
+#define MO_ABI_VERSION 7
 int mo_abi_version(void);
 
 #define MO_OK 0
@@ -391,7 +391,20 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *   mo_map_download          one field (MO_MAP_*), bytes = exactly its size.
  *   mo_map_write_ply         utils.create_point_cloud_ply (utils.py:72-118) of the points with >= min_obs observations, byte for byte:
  *                            floats as Python's repr of the double value, colours as stored.
- *   mo_format_floats         that float formatting alone, one value per line (no GPU). */
+ *   mo_format_floats         that float formatting alone, one value per line (no GPU).
+ *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
+ *                            brute-force matching in place of the bag-of-words lookup); reads the map, never changes it.  The frame (by
+ *                            token of a resident result slot, else the host arrays) is matched against every keyframe (query = the frame,
+ *                            train = the keyframe's rows, knn-2 with `ratio` as in mo_map_add_keyframe).  point_of[k][row] = the lowest map
+ *                            point whose observations hold (keyframe position k, row), read like the cull reads them (negative values count
+ *                            from the end; entries naming a position or row that does not exist are skipped).  C_k = the ratio-test
+ *                            survivors q whose best neighbour has a map point, in query order, |C_k| = the score; the candidates are the
+ *                            keyframes with a score >= 15, highest first, ties to the lower position, at most max_candidates.  Per
+ *                            candidate: n_hyp P3P samples of 3 correspondences (the sampling stream (seed, keyframe position, h) of
+ *                            twoview_kernels.hip:sample8), up to 4 poses each; an inlier has depth > 0 and squared reprojection error
+ *                            < thr_px^2 under P = K [R|t] (f64); the best pose has the most inliers (ties to the lower (h, root)), then
+ *                            Gauss-Newton on SE(3) over its inliers (<= 10 steps), re-selection, once more.  The winner has the most final
+ *                            inliers (ties to the lower position); ok = its inliers >= min_inliers.  One synchronisation: the copy-out. */
 typedef struct mo_map mo_map;
 typedef struct {
     double ratio;            /* 0.8 (local_mapper.py:124) */
@@ -414,6 +427,30 @@ typedef struct {
     int32_t from_token;      /* 1: the keyframe was copied from its resident slot */
     int64_t n_points, n_obs; /* map size after the cull */
 } mo_map_kf_out;
+typedef struct {
+    double ratio;            /* Lowe ratio of the keyframe matching (0.75) */
+    double thr_px;           /* inlier: squared reprojection error < thr_px^2 (3.0) */
+    int32_t min_inliers;     /* ok needs this many final inliers (50) */
+    int32_t max_candidates;  /* 1 .. 64 (4) */
+    int32_t n_hyp;           /* P3P samples per candidate, 1 .. 2^20 (512) */
+    uint64_t seed;
+} mo_map_reloc_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n_q = keypoints of the frame */
+    int32_t* point;          /* [n_q] map point of each query keypoint through the winner's point_of (-1: none) */
+    uint8_t* inlier;         /* [n_q] final inlier flag of the winner */
+    int32_t* cand_pos;       /* [max_candidates] keyframe positions of the candidates in rank order (-1 past n_cand) */
+    int32_t* cand_score;     /* [max_candidates] their scores |C_k| */
+    int32_t* cand_inliers;   /* [max_candidates] their final inlier counts */
+    /* filled by the call */
+    double pose[12];         /* [R | t] row-major of the winner (X_cam = R X + t); NaN without a winner */
+    int32_t ok;              /* 1: the winner has >= min_inliers inliers */
+    int32_t kf_pos;          /* keyframe position of the winner (-1: none) */
+    int32_t n_cand;          /* candidates */
+    int32_t n_corr;          /* |C_k| of the winner */
+    int32_t n_inliers;       /* final inliers of the winner */
+    int32_t from_token;      /* 1: the frame was read from its resident slot */
+} mo_map_reloc_out;
 #define MO_MAP_XYZ 0
 #define MO_MAP_COLOR 1
 #define MO_MAP_ID 2
@@ -434,6 +471,7 @@ int mo_map_remove_keyframes(mo_map*, const int32_t* positions, int n);
 int mo_map_sizes(mo_map*, int64_t out[6]);
 int mo_map_download(mo_map*, int field, void* dst, size_t bytes);
 int mo_map_write_ply(mo_map*, const char* path, int min_obs, int64_t* n_written);
+int mo_map_relocalize(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, mo_map_reloc_out*);
 int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and

@@ -16,6 +16,7 @@
 // -ffp-contract=off (Makefile, every file): the reprojection test rounds each product and sum once, in the order numpy's P @ X_h does.
 #include <algorithm>
 #include <charconv>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pnp.h"
 
 #define MAP_SCAN_BLOCK 256
 #define MAP_SCAN_ITEMS 4
@@ -39,6 +41,8 @@ struct MapPts {
     int32_t* okf = nullptr; int32_t* okp = nullptr;   // [ocap]
     size_t pcap = 0, ocap = 0;
 };
+
+struct RelocRes;  // per-call results of mo_map_relocalize (below)
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -72,6 +76,16 @@ struct mo_map {
     int32_t* midx = nullptr; int32_t* mdist = nullptr; uint8_t* mpass = nullptr; uint8_t* inl = nullptr; float* gpts = nullptr;
     double* F = nullptr; int32_t* gnp = nullptr; size_t grow_rows = 0;
     int32_t* h_stat = nullptr;                        // pinned [ST_NWORDS]
+    // relocalization (mo_map_relocalize), grown with the map
+    int32_t* rl_tab = nullptr; size_t rl_tab_bytes = 0;                        // point_of [slot][row]
+    int32_t* rl_qf = nullptr; size_t rl_qf_bytes = 0;                          // [n_kf] query frame of every pair: the spare slot
+    int32_t* rl_midx = nullptr; int32_t* rl_mdist = nullptr; uint8_t* rl_mpass = nullptr;  // [n_kf][row] matcher outputs
+    size_t rl_midx_bytes = 0, rl_mdist_bytes = 0, rl_mpass_bytes = 0;
+    int32_t* rl_score = nullptr; size_t rl_score_bytes = 0;                    // [n_kf] |C_k|
+    int32_t* rl_cq = nullptr; int32_t* rl_cp = nullptr; uint8_t* rl_cinl = nullptr;  // [candidate][row] C_k (query, point), final inliers
+    size_t rl_cq_bytes = 0, rl_cp_bytes = 0, rl_cinl_bytes = 0;
+    int32_t* rl_qpt = nullptr; uint8_t* rl_qinl = nullptr; size_t rl_qpt_bytes = 0, rl_qinl_bytes = 0;  // [row] per query keypoint
+    RelocRes* rl_res = nullptr; RelocRes* h_rl = nullptr;                     // device / pinned
 };
 
 template <class T> static int reserve(mo_ctx* c, T*& p, size_t& have, size_t need) {
@@ -383,6 +397,8 @@ static int pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep
     return MO_OK;
 }
 
+// kkps / kdesc / kcnt hold one slot more than kslots: the spare slot (index kslots) mo_map_relocalize stages its query in, so that
+// one counts array serves both sides of its keyframe matching
 static int kf_reserve(mo_map* m, int rows, int slots) {
     mo_ctx* c = m->c;
     int rc;
@@ -390,8 +406,8 @@ static int kf_reserve(mo_map* m, int rows, int slots) {
         const int nr = (int)(((size_t)rows + 15) & ~(size_t)15);
         const int ns = std::max(slots, m->kslots);
         mo_keypoint* k2 = nullptr; uint8_t* d2 = nullptr;
-        HIPCHK(c, hipMalloc((void**)&k2, (size_t)ns * nr * sizeof(mo_keypoint)));
-        HIPCHK(c, hipMalloc((void**)&d2, (size_t)ns * nr * 32));
+        HIPCHK(c, hipMalloc((void**)&k2, (size_t)(ns + 1) * nr * sizeof(mo_keypoint)));
+        HIPCHK(c, hipMalloc((void**)&d2, (size_t)(ns + 1) * nr * 32));
         if (m->n_slots && m->row) {
             HIPCHK(c, hipMemcpy2DAsync(k2, (size_t)nr * sizeof(mo_keypoint), m->kkps, (size_t)m->row * sizeof(mo_keypoint), (size_t)m->row * sizeof(mo_keypoint),
                                        m->n_slots, hipMemcpyDeviceToDevice, c->stream));
@@ -402,16 +418,16 @@ static int kf_reserve(mo_map* m, int rows, int slots) {
         if (m->kdesc) HIPCHK(c, hipFree(m->kdesc));
         m->kkps = k2; m->kdesc = d2; m->row = nr;
         if (ns > m->kslots) {
-            if ((rc = regrow(c, m->kcnt, 0, (size_t)ns * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
+            if ((rc = regrow(c, m->kcnt, 0, (size_t)(ns + 1) * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
                 return rc;
             m->kslots = ns;
         }
     }
     if (slots > m->kslots) {
         const int ns = std::max(slots, m->kslots * 2);
-        if ((rc = regrow(c, m->kkps, 0, (size_t)ns * m->row * sizeof(mo_keypoint), (size_t)m->n_slots * m->row * sizeof(mo_keypoint))) ||
-            (rc = regrow(c, m->kdesc, 0, (size_t)ns * m->row * 32, (size_t)m->n_slots * m->row * 32)) ||
-            (rc = regrow(c, m->kcnt, 0, (size_t)ns * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
+        if ((rc = regrow(c, m->kkps, 0, (size_t)(ns + 1) * m->row * sizeof(mo_keypoint), (size_t)m->n_slots * m->row * sizeof(mo_keypoint))) ||
+            (rc = regrow(c, m->kdesc, 0, (size_t)(ns + 1) * m->row * 32, (size_t)m->n_slots * m->row * 32)) ||
+            (rc = regrow(c, m->kcnt, 0, (size_t)(ns + 1) * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
             return rc;
         m->kslots = ns;
     }
@@ -456,7 +472,11 @@ extern "C" void mo_map_destroy(mo_map* m) {
         void* pb[] = {p.xyz, p.col, p.id, p.dkf, p.drow, p.off, p.okf, p.okp};
         for (void* b : pb) if (b) hipFree(b);
     }
+    void* rb[] = {m->rl_tab, m->rl_qf, m->rl_midx, m->rl_mdist, m->rl_mpass, m->rl_score, m->rl_cq, m->rl_cp, m->rl_cinl, m->rl_qpt, m->rl_qinl,
+                  m->rl_res};
+    for (void* b : rb) if (b) hipFree(b);
     if (m->h_stat) hipHostFree(m->h_stat);
+    if (m->h_rl) hipHostFree(m->h_rl);
     delete m;
 }
 
@@ -847,5 +867,386 @@ extern "C" int mo_map_write_ply(mo_map* m, const char* path, int min_obs, int64_
     const size_t wr = std::fwrite(s.data(), 1, s.size(), fp);
     const int cl = std::fclose(fp);
     if (wr != s.size() || cl != 0) return mo_fail(c, MO_ERR_ARG, std::string("write failed: ") + path);
+    return MO_OK;
+}
+
+// ---- relocalization (mo_map_relocalize): a lost frame against every keyframe, 2D-3D correspondences through the observations, P3P
+// RANSAC per candidate keyframe.  Read-only on the map; the frame is staged in the spare keyframe slot (kf_reserve).
+// Chain: point_of scatter -> knn-2 matching of the frame against every keyframe (match_launch_pairs, one pair per keyframe) -> scores
+// |C_k| -> ranking -> C_k of the candidates (block scans, query order) -> P3P hypotheses + scoring (one wave per hypothesis, all
+// candidates in one launch) -> best hypothesis + Gauss-Newton refinement (one wave per candidate) -> winner.  One synchronisation.
+#define RL_MAX_CAND 64
+#define RL_MIN_SCORE 15   // ORB-SLAM2's Tracking::Relocalization: keyframes with fewer than 15 matches are discarded
+#define RL_HYP_WAVES 4    // hypotheses per block of k_reloc_hyp (one per wave)
+
+struct RelocRes {
+    double pose[RL_MAX_CAND][12];         // refined [R | t] per candidate
+    unsigned long long best[RL_MAX_CAND]; // (inliers << 32) | ~(h * 4 + root): the largest key is the best hypothesis
+    int32_t cand[RL_MAX_CAND], score[RL_MAX_CAND], ncorr[RL_MAX_CAND], ninl[RL_MAX_CAND];
+    int32_t n_cand, win;
+};
+
+struct RelocGeom {
+    double K[9], Kinv[9], thr2;
+};
+
+// point_of[slot][row] = lowest map point whose observations hold (position, row); entries naming nothing are skipped
+__global__ __launch_bounds__(256) void k_reloc_point_of(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
+                                                        const int32_t* __restrict__ kcnt, int row, int32_t* __restrict__ tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pts) return;
+    const int o0 = src.off[i], o1 = src.off[i + 1];
+    for (int o = o0; o < o1; o++) {
+        int kf = src.okf[o];
+        if (kf < 0) kf += n_kf;
+        if (kf < 0 || kf >= n_kf) continue;
+        const int s = pos_slot[kf];
+        int kp = src.okp[o];
+        const int nk = kcnt[s];
+        if (kp < 0) kp += nk;
+        if (kp < 0 || kp >= nk) continue;
+        atomicMin(tab + (size_t)s * row + kp, i);
+    }
+}
+
+// the map point of query q against keyframe position k (-1: none): the ratio-test survivor's best neighbour through point_of
+__device__ __forceinline__ int reloc_point(int k, int s, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
+                                           const int32_t* __restrict__ tab) {
+    const size_t o = (size_t)k * row + q;
+    if (!mpass[o]) return -1;
+    const int t = midx[2 * o];
+    if (t < 0) return -1;
+    const int p = tab[(size_t)s * row + t];
+    return p == INT_MAX ? -1 : p;
+}
+
+// |C_k|, one block per keyframe position
+__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
+                                                     const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
+                                                     const int32_t* __restrict__ tab, int32_t* __restrict__ score) {
+    __shared__ int lw[4];
+    const int k = blockIdx.x, s = pos_slot[k];
+    const int nq = min(kcnt[spare], row);
+    int n = 0;
+    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(k, s, q, row, midx, mpass, tab) >= 0;
+    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+    if ((threadIdx.x & 63) == 0) lw[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) score[k] = lw[0] + lw[1] + lw[2] + lw[3];
+}
+
+// candidates: scores >= RL_MIN_SCORE, highest first, ties to the lower position; one block, one max reduction per rank
+__global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ score, int n_kf, int max_cand, RelocRes* __restrict__ res) {
+    __shared__ unsigned long long red[256];
+    const int tid = threadIdx.x;
+    if (tid < RL_MAX_CAND) {
+        res->best[tid] = 0; res->ninl[tid] = 0; res->ncorr[tid] = 0; res->cand[tid] = -1; res->score[tid] = 0;
+        for (int j = 0; j < 12; j++) res->pose[tid][j] = __longlong_as_double(0x7ff8000000000000ll);
+    }
+    __syncthreads();
+    unsigned long long prev = ~0ull;
+    int nc = 0;
+    for (int r = 0; r < max_cand; r++) {
+        unsigned long long b = 0;
+        for (int k = tid; k < n_kf; k += 256) {
+            const int s = score[k];
+            const unsigned long long key = ((unsigned long long)(unsigned)s << 32) | (unsigned)(0x7fffffff - k);
+            if (s >= RL_MIN_SCORE && key < prev && key > b) b = key;
+        }
+        red[tid] = b;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (tid < w) red[tid] = max(red[tid], red[tid + w]);
+            __syncthreads();
+        }
+        b = red[0];
+        __syncthreads();
+        if (!b) break;
+        if (tid == 0) { res->cand[r] = 0x7fffffff - (int)(b & 0xffffffffu); res->score[r] = (int)(b >> 32); }
+        nc = r + 1;
+        prev = b;
+    }
+    if (tid == 0) { res->n_cand = nc; res->win = -1; }
+}
+
+// C_k of candidate blockIdx.x in query order (block scans, no atomics)
+__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
+                                                       const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
+                                                       RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
+    __shared__ int lw[40];
+    const int c = blockIdx.x, k = res->cand[c];
+    if (k < 0) return;
+    const int s = pos_slot[k], nq = min(kcnt[spare], row);
+    int added = 0;
+    for (int b = 0; b < nq; b += 1024) {
+        const int q = b + threadIdx.x;
+        const int p = q < nq ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
+        int tot;
+        const int r = block_excl_scan(p >= 0 ? 1 : 0, lw, &tot);
+        if (p >= 0) { cq[(size_t)c * row + added + r] = q; cp[(size_t)c * row + added + r] = p; }
+        added += tot;
+    }
+    if (threadIdx.x == 0) res->ncorr[c] = added;
+}
+
+// the P3P poses of hypothesis h of candidate c (every lane of a wave solves the same sample)
+__device__ __forceinline__ int reloc_solve(const RelocGeom& g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps,
+                                           const int32_t* __restrict__ cq, const int32_t* __restrict__ cp, int m, uint64_t stream, int h,
+                                           double (&R)[4][9], double (&t)[4][3]) {
+    int idx[3];
+    pnp_sample<3>(stream, h, m, idx);
+    double X[3][3], b[3][3];
+    for (int i = 0; i < 3; i++) {
+        const int p = cp[idx[i]];
+        X[i][0] = xyz[(size_t)p * 3]; X[i][1] = xyz[(size_t)p * 3 + 1]; X[i][2] = xyz[(size_t)p * 3 + 2];
+        const mo_keypoint kp = qkps[cq[idx[i]]];
+        const double x = kp.x, y = kp.y;
+        for (int r = 0; r < 3; r++) b[i][r] = g.Kinv[r * 3] * x + g.Kinv[r * 3 + 1] * y + g.Kinv[r * 3 + 2];
+    }
+    return pnp_p3p(X, b, R, t);
+}
+
+// one wave per (hypothesis, candidate): up to 4 poses, each scored over C_k by the 64 lanes; the best key per candidate by atomicMax
+__global__ __launch_bounds__(64 * RL_HYP_WAVES) void k_reloc_hyp(RelocGeom g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps,
+                                                                 int row, int n_hyp, uint64_t seed, const int32_t* __restrict__ cq,
+                                                                 const int32_t* __restrict__ cp, RelocRes* __restrict__ res) {
+    const int c = blockIdx.y, k = res->cand[c];
+    const int h = blockIdx.x * RL_HYP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k < 0 || h >= n_hyp) return;   // wave-uniform
+    const int m = res->ncorr[c];
+    const int32_t* q = cq + (size_t)c * row;
+    const int32_t* p = cp + (size_t)c * row;
+    double R[4][9], t[4][3];
+    const int nr = reloc_solve(g, xyz, qkps, q, p, m, pnp_stream_seed(seed, k), h, R, t);
+    unsigned long long best = 0;
+    for (int r = 0; r < nr; r++) {
+        double P[12];
+        pnp_projection(g.K, R[r], t[r], P);
+        int n = 0;
+        for (int j = lane; j < m; j += 64) {
+            const int pj = p[j];
+            const mo_keypoint kp = qkps[q[j]];
+            double e2;
+            n += pnp_reproj2(P, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, &e2) && e2 < g.thr2;
+        }
+        for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+        const unsigned long long key = ((unsigned long long)(unsigned)n << 32) | (0xffffffffu - (unsigned)(h * 4 + r));
+        if (n > 0 && key > best) best = key;
+    }
+    if (lane == 0 && best) atomicMax(&res->best[c], best);
+}
+
+// a fixed-order wave sum every lane receives (lane 0's tree, broadcast): the same value on every lane, the same on every run
+__device__ __forceinline__ double reloc_wave_sum(double v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return __shfl(v, 0, 64);
+}
+
+// inlier flags of C_k under (R, t) into fl, their number
+__device__ __forceinline__ int reloc_select(const RelocGeom& g, const double* R, const double* t, const float* __restrict__ xyz,
+                                            const mo_keypoint* __restrict__ qkps, const int32_t* __restrict__ q, const int32_t* __restrict__ p,
+                                            int m, uint8_t* __restrict__ fl) {
+    double P[12];
+    pnp_projection(g.K, R, t, P);
+    int n = 0;
+    for (int j = threadIdx.x; j < m; j += 64) {
+        const int pj = p[j];
+        const mo_keypoint kp = qkps[q[j]];
+        double e2;
+        const bool in = pnp_reproj2(P, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, &e2) && e2 < g.thr2;
+        fl[j] = in;
+        n += in;
+    }
+    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+    return n;
+}
+
+// one wave per candidate: the best hypothesis' pose, (Gauss-Newton over its inliers, re-selection) twice
+__global__ __launch_bounds__(64) void k_reloc_refine(RelocGeom g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps, int row,
+                                                     uint64_t seed, const int32_t* __restrict__ cq, const int32_t* __restrict__ cp,
+                                                     uint8_t* __restrict__ cinl, RelocRes* __restrict__ res) {
+    const int c = blockIdx.x, k = res->cand[c];
+    if (k < 0) return;
+    const unsigned long long best = res->best[c];
+    if (!best) return;   // no pose with an inlier: 0 inliers, NaN pose (k_reloc_rank)
+    const int m = res->ncorr[c];
+    const int32_t* q = cq + (size_t)c * row;
+    const int32_t* p = cp + (size_t)c * row;
+    uint8_t* fl = cinl + (size_t)c * row;
+    const unsigned hr = 0xffffffffu - (unsigned)(best & 0xffffffffu);
+    double Rs[4][9], ts[4][3];
+    reloc_solve(g, xyz, qkps, q, p, m, pnp_stream_seed(seed, k), (int)(hr >> 2), Rs, ts);
+    double R[9], t[3];
+    for (int i = 0; i < 9; i++) R[i] = Rs[hr & 3][i];
+    for (int i = 0; i < 3; i++) t[i] = ts[hr & 3][i];
+    int n = reloc_select(g, R, t, xyz, qkps, q, p, m, fl);
+    for (int round = 0; round < 2; round++) {
+        for (int it = 0; it < 10; it++) {
+            double H[21], gr[6];
+            for (int i = 0; i < 21; i++) H[i] = 0.0;
+            for (int i = 0; i < 6; i++) gr[i] = 0.0;
+            for (int j = threadIdx.x; j < m; j += 64) {
+                if (!fl[j]) continue;
+                const int pj = p[j];
+                const mo_keypoint kp = qkps[q[j]];
+                pnp_gn_accumulate(g.K, R, t, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, H, gr);
+            }
+            for (int i = 0; i < 21; i++) H[i] = reloc_wave_sum(H[i]);
+            for (int i = 0; i < 6; i++) gr[i] = reloc_wave_sum(gr[i]);
+            double step;
+            if (!pnp_gn_update(H, gr, R, t, &step) || step < 1e-12) break;
+        }
+        n = reloc_select(g, R, t, xyz, qkps, q, p, m, fl);
+    }
+    if (threadIdx.x == 0) {
+        res->ninl[c] = n;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) res->pose[c][i * 4 + j] = R[i * 3 + j];
+            res->pose[c][i * 4 + 3] = t[i];
+        }
+    }
+}
+
+// the winner (most final inliers, ties to the lower position) and its per-query-keypoint map point and inlier flag
+__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
+                                                      const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
+                                                      const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
+                                                      int32_t* __restrict__ qpt, uint8_t* __restrict__ qinl) {
+    __shared__ int win;
+    if (threadIdx.x == 0) {
+        int w = -1;
+        for (int c = 0; c < res->n_cand; c++)
+            if (w < 0 || res->ninl[c] > res->ninl[w] || (res->ninl[c] == res->ninl[w] && res->cand[c] < res->cand[w])) w = c;
+        win = w;
+        res->win = w;
+    }
+    __syncthreads();
+    const int w = win, k = w >= 0 ? res->cand[w] : -1, s = k >= 0 ? pos_slot[k] : 0;
+    const int nq = min(kcnt[spare], row);
+    for (int q = threadIdx.x; q < nq; q += 256) {
+        qpt[q] = k >= 0 ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
+        qinl[q] = 0;
+    }
+    __syncthreads();
+    if (w < 0 || !res->best[w]) return;
+    const int m = res->ncorr[w];
+    for (int j = threadIdx.x; j < m; j += 256) qinl[cq[(size_t)w * row + j]] = cinl[(size_t)w * row + j];
+}
+
+extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, mo_map_reloc_out* out) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (!f || !K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (prm->max_candidates < 1 || prm->max_candidates > RL_MAX_CAND) return mo_fail(c, MO_ERR_ARG, "max_candidates must be in 1 .. 64");
+    if (prm->n_hyp < 1 || prm->n_hyp > (1 << 20)) return mo_fail(c, MO_ERR_ARG, "n_hyp must be in 1 .. 2^20");
+    if (!(prm->thr_px >= 0.0)) return mo_fail(c, MO_ERR_ARG, "thr_px must be >= 0");
+    RelocGeom g;
+    {
+        const double* A = K;
+        const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
+        const double det = A[0] * c0 + A[1] * c1 + A[2] * c2;
+        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return mo_fail(c, MO_ERR_ARG, "K is singular");
+        const double inv[9] = {c0, A[2] * A[7] - A[1] * A[8], A[1] * A[5] - A[2] * A[4],
+                               c1, A[0] * A[8] - A[2] * A[6], A[2] * A[3] - A[0] * A[5],
+                               c2, A[1] * A[6] - A[0] * A[7], A[0] * A[4] - A[1] * A[3]};
+        for (int i = 0; i < 9; i++) { g.K[i] = K[i]; g.Kinv[i] = inv[i] / det; }
+        g.thr2 = prm->thr_px * prm->thr_px;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HostClock clk(c);
+    const int nc = prm->max_candidates;
+    for (int i = 0; i < 12; i++) out->pose[i] = NAN;
+    out->ok = 0; out->kf_pos = -1; out->n_cand = 0; out->n_corr = 0; out->n_inliers = 0; out->from_token = 0;
+    int rs = -1;
+    if (f->token)
+        for (int s = 0; s < MO_RESULT_SLOTS; s++) if (c->slot_token[s] == f->token) rs = s;
+    const int n = rs >= 0 ? c->slot_n[rs] : f->n;
+    if (n < 0 || (rs < 0 && n > 0 && (!f->kps || !f->desc))) return mo_fail(c, MO_ERR_ARG, "frame token is stale and no host arrays were given");
+    out->from_token = rs >= 0;
+    if (out->point) for (int i = 0; i < n; i++) out->point[i] = -1;
+    if (out->inlier) std::memset(out->inlier, 0, (size_t)n);
+    for (int i = 0; i < nc; i++) {
+        if (out->cand_pos) out->cand_pos[i] = -1;
+        if (out->cand_score) out->cand_score[i] = 0;
+        if (out->cand_inliers) out->cand_inliers[i] = 0;
+    }
+    const int n_kf = (int)m->pos_slot.size();
+    if (n == 0 || n_kf == 0) return MO_OK;   // nothing to match: not relocalized, not an error
+    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    int rc;
+    if ((rc = kf_reserve(m, n, m->n_slots))) return rc;   // (a wider row restrides the store; the map itself is unchanged)
+    const int spare = m->kslots, row = m->row;
+    mo_stage_begin(c);
+    if (rs >= 0) {
+        HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)spare * row, c->d_slot_kps + (size_t)rs * c->slot_cap, (size_t)n * sizeof(mo_keypoint),
+                                 hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)spare * row * 32, c->d_slot_desc + (size_t)rs * c->slot_cap * 32, (size_t)n * 32,
+                                 hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)spare * row, f->kps, (size_t)n * sizeof(mo_keypoint), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)spare * row * 32, f->desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + spare), n, 1, c->stream));
+    const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_kf * row, cand_n = (size_t)nc * row;
+    if ((rc = reserve(c, m->rl_tab, m->rl_tab_bytes, tab_n * 4)) || (rc = reserve(c, m->rl_qf, m->rl_qf_bytes, (size_t)n_kf * 4)) ||
+        (rc = reserve(c, m->rl_midx, m->rl_midx_bytes, pair_n * 8)) || (rc = reserve(c, m->rl_mdist, m->rl_mdist_bytes, pair_n * 8)) ||
+        (rc = reserve(c, m->rl_mpass, m->rl_mpass_bytes, pair_n)) || (rc = reserve(c, m->rl_score, m->rl_score_bytes, (size_t)n_kf * 4)) ||
+        (rc = reserve(c, m->rl_cq, m->rl_cq_bytes, cand_n * 4)) || (rc = reserve(c, m->rl_cp, m->rl_cp_bytes, cand_n * 4)) ||
+        (rc = reserve(c, m->rl_cinl, m->rl_cinl_bytes, cand_n)) || (rc = reserve(c, m->rl_qpt, m->rl_qpt_bytes, (size_t)row * 4)) ||
+        (rc = reserve(c, m->rl_qinl, m->rl_qinl_bytes, (size_t)row)))
+        return rc;
+    if (!m->rl_res) {
+        HIPCHK(c, hipMalloc((void**)&m->rl_res, sizeof(RelocRes)));
+        HIPCHK(c, hipHostMalloc((void**)&m->h_rl, sizeof(RelocRes), hipHostMallocDefault));
+    }
+    if ((rc = upload_pos_slot(m))) return rc;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)m->rl_tab, INT_MAX, tab_n, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)m->rl_qf, spare, (size_t)n_kf, c->stream));
+    const MapPts& src = m->P[m->cur];
+    if (m->n_pts > 0)
+        hipLaunchKernelGGL(k_reloc_point_of, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf,
+                           m->kcnt, row, m->rl_tab);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "reloc_point_of");
+    if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, m->kcnt, m->rl_qf, m->d_pos_slot, 0, 0, n_kf, row, prm->ratio,
+                                 m->rl_midx, m->rl_mdist, m->rl_mpass)))
+        return rc;
+    mo_stage_mark(c, "reloc_match");
+    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab, m->rl_score);
+    hipLaunchKernelGGL(k_reloc_rank, dim3(1), dim3(256), 0, c->stream, m->rl_score, n_kf, nc, m->rl_res);
+    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab,
+                       m->rl_res, m->rl_cq, m->rl_cp);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "reloc_candidates");
+    const mo_keypoint* qk = m->kkps + (size_t)spare * row;
+    hipLaunchKernelGGL(k_reloc_hyp, dim3((unsigned)((prm->n_hyp + RL_HYP_WAVES - 1) / RL_HYP_WAVES), nc), dim3(64 * RL_HYP_WAVES), 0, c->stream, g, src.xyz, qk,
+                       row, prm->n_hyp, prm->seed, m->rl_cq, m->rl_cp, m->rl_res);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "reloc_p3p");
+    hipLaunchKernelGGL(k_reloc_refine, dim3(nc), dim3(64), 0, c->stream, g, src.xyz, qk, row, prm->seed, m->rl_cq, m->rl_cp, m->rl_cinl, m->rl_res);
+    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab, m->rl_cq,
+                       m->rl_cinl, m->rl_res, m->rl_qpt, m->rl_qinl);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "reloc_refine");
+    HIPCHK(c, hipMemcpyAsync(m->h_rl, m->rl_res, sizeof(RelocRes), hipMemcpyDeviceToHost, c->stream));
+    if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, m->rl_qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, m->rl_qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    clk.enqueued();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    clk.waited();
+    const RelocRes& r = *m->h_rl;
+    out->n_cand = r.n_cand;
+    for (int i = 0; i < r.n_cand; i++) {
+        if (out->cand_pos) out->cand_pos[i] = r.cand[i];
+        if (out->cand_score) out->cand_score[i] = r.score[i];
+        if (out->cand_inliers) out->cand_inliers[i] = r.ninl[i];
+    }
+    if (r.win >= 0) {
+        out->kf_pos = r.cand[r.win];
+        out->n_corr = r.ncorr[r.win];
+        out->n_inliers = r.ninl[r.win];
+        for (int i = 0; i < 12; i++) out->pose[i] = r.pose[r.win][i];
+        out->ok = r.ninl[r.win] >= prm->min_inliers && r.best[r.win] != 0;
+    }
     return MO_OK;
 }

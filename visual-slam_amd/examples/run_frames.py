@@ -115,6 +115,8 @@ def main(argv=None):
     ap.add_argument("--python-filters", action="store_true", help="tracking step through the per-method API (Python filter loops)")
     ap.add_argument("--map", default="", help="PATH: keyframes into the device LocalMapper (vslam_amd.mapper), its PLY map written to PATH")
     ap.add_argument("--keyframe-every", type=int, default=20, help="with --map: a keyframe every N frames (tracker.py:290)")
+    ap.add_argument("--relocalize", action="store_true", help="with --map: when the tracking step fails, relocalize the frame against the "
+                    "device map (LocalMapper.relocalize) and go on tracking from it")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
@@ -132,6 +134,8 @@ def main(argv=None):
         if args.map:
             ap.error("--map runs frame by frame: it cannot be combined with --batch")
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
+    if args.relocalize and not args.map:
+        ap.error("--relocalize needs --map")
     mapper, first, ref_pose = None, None, np.eye(4)
     if args.map:
         from vslam_amd.mapper import LocalMapper
@@ -146,6 +150,16 @@ def main(argv=None):
         ref_pose = ref_pose @ T
         if mapper is not None and idx % args.keyframe_every == 0:
             mapper.add_keyframe(frame, kps, desc, ref_pose)
+
+    def relocalize(frame, kps, desc, idx):
+        """the frame against the map (ORB-SLAM2's Tracking::Relocalization); on success tracking goes on from its pose"""
+        nonlocal ref_pose
+        ok, T, info = mapper.relocalize(kps, desc)
+        print("frame %d: relocalize %s, keyframe %s, %d candidates, %d inliers" % (idx, "ok" if ok else "failed", info["kf_pos"],
+                                                                                  len(info["candidates"]), info["n_inliers"]))
+        if ok:
+            ref_pose = T
+            poses.append((T[:3, :3], T[:3, 3:4]))
     for idx, frame in enumerate(source):
         if n_seen >= limit:
             break
@@ -183,6 +197,8 @@ def main(argv=None):
                 track_pose(T[:3, :3], T[:3, 3], frame, kps, desc, idx)
                 if idx % 5 == 0:
                     print("frame %d: %d pose inliers, t = %s" % (idx, len(inl), np.round(T[:3, 3], 3)))
+            elif args.relocalize:
+                relocalize(frame, kps, desc, idx)
         else:
             m = matcher.match(last[1], desc)
             m = matcher.filter_matches_by_geometric_distance(last[0], kps, m, 0.02, frame.shape)   # tracker.py:219-221
@@ -197,6 +213,10 @@ def main(argv=None):
                     track_pose(R, t, frame, kps, desc, idx)
                     if idx % 5 == 0:
                         print("frame %d: %d matches, %d pose inliers, t = %s" % (idx, len(m), n_in, np.round(t.ravel(), 3)))
+                    last = (kps, desc)
+                    continue
+            if args.relocalize:
+                relocalize(frame, kps, desc, idx)
         last = (kps, desc)
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s (%.1f frames/s through the Python drop-in classes), state %s, %d poses"

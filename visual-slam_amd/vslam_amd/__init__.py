@@ -15,7 +15,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("VSLAM_AMD_LIB") or os.path.join(_PKG_ROOT, "libvslam_amd.so")
 
 MO_OK, MO_ERR_ARG, MO_ERR_HIP, MO_ERR_CAPACITY, MO_ERR_UNSUPPORTED, MO_ERR_INDEX = 0, -1, -2, -3, -4, -5
-ABI_VERSION = 6  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
+ABI_VERSION = 7  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
 ORDER_LIBSTDCXX, ORDER_MSVC = 0, 1
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -78,6 +78,17 @@ class MapKfOut(C.Structure):
     _fields_ = [("match_idx", C.c_void_p), ("match_pass", C.c_void_p), ("inlier", C.c_void_p), ("points", C.c_void_p), ("kf_len", C.c_void_p),
                 ("kf_redundant", C.c_void_p), ("F", C.c_double * 9), ("n_new", C.c_int32), ("from_token", C.c_int32),
                 ("n_points", C.c_int64), ("n_obs", C.c_int64)]
+
+
+class MapRelocParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("thr_px", C.c_double), ("min_inliers", C.c_int32), ("max_candidates", C.c_int32), ("n_hyp", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class MapRelocOut(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("inlier", C.c_void_p), ("cand_pos", C.c_void_p), ("cand_score", C.c_void_p), ("cand_inliers", C.c_void_p),
+                ("pose", C.c_double * 12), ("ok", C.c_int32), ("kf_pos", C.c_int32), ("n_cand", C.c_int32), ("n_corr", C.c_int32),
+                ("n_inliers", C.c_int32), ("from_token", C.c_int32)]
 
 
 class StreamParams(C.Structure):
@@ -157,6 +168,7 @@ SIGNATURES = {
     "mo_map_sizes": (_i, [_vp, _vp]),
     "mo_map_download": (_i, [_vp, _i, _vp, C.c_size_t]),
     "mo_map_write_ply": (_i, [_vp, C.c_char_p, _i, _vp]),
+    "mo_map_relocalize": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
 }
 

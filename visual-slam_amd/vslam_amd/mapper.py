@@ -252,6 +252,51 @@ class LocalMapper:
         self._cache = None
         self._sync_size()
 
+    # ---- relocalization -----------------------------------------------------------------------------------------------------------
+    def relocalize(self, keypoints, descriptors, ratio_threshold=0.75, threshold=3.0, min_inliers=50, max_candidates=4, n_hyp=512, seed=None):
+        """The pose of a lost frame against the map as it stands (the map is not changed): the frame is matched against every keyframe
+        (knn-2, Lowe ratio), the matches become 2D-3D correspondences through the map's observations, and a P3P RANSAC with Gauss-Newton
+        refinement runs on the best-scoring keyframes (mo_map_relocalize in include/vslam_amd.h states the rules).  The frame is given
+        like add_keyframe's: the arrays a detect_and_compute returned (resident on the device: nothing is uploaded) or host arrays.
+        Returns (ok, pose, info): pose 4x4 (X_cam = R X + t, the convention add_keyframe takes; None without a winner); info holds
+        kf_pos / kf_id of the winner, the candidates [(position, score, inliers)], and per query keypoint `point` (map point index,
+        -1: none) and `inlier` of the winner."""
+        from orbslam2.types import keypoints_to_array
+        seed = self.seed if seed is None else int(seed)
+        token = V.resident_token(self.ctx, descriptors) if descriptors is not None else 0
+        kps_arr = V._resident_kps(descriptors) if token else None
+        if kps_arr is None or len(kps_arr) != len(keypoints):
+            token = 0
+            if isinstance(keypoints, np.ndarray) and keypoints.dtype == V.KP_DTYPE:
+                kps_arr = keypoints
+            else:
+                kps_arr = keypoints_to_array(keypoints) if len(keypoints) else np.zeros(0, V.KP_DTYPE)
+        kps_arr = np.ascontiguousarray(kps_arr, V.KP_DTYPE).reshape(-1)
+        desc = np.ascontiguousarray(descriptors if descriptors is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
+        n = len(kps_arr) if token else min(len(kps_arr), len(desc))
+        ref = V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        nc = int(max_candidates)
+        point = np.full(max(n, 1), -1, np.int32)
+        inlier = np.zeros(max(n, 1), np.uint8)
+        cpos = np.full(max(nc, 1), -1, np.int32)
+        cscore = np.zeros(max(nc, 1), np.int32)
+        cinl = np.zeros(max(nc, 1), np.int32)
+        prm = V.MapRelocParams(float(ratio_threshold), float(threshold), int(min_inliers), nc, int(n_hyp), seed)
+        out = V.MapRelocOut(point.ctypes.data, inlier.ctypes.data, cpos.ctypes.data, cscore.ctypes.data, cinl.ctypes.data)
+        self._check(self.lib.mo_map_relocalize(self._h, C.byref(ref), V._ptr(K), C.byref(prm), C.byref(out)))
+        kf_pos = int(out.kf_pos)
+        pose = None
+        if kf_pos >= 0:
+            pose = np.eye(4)
+            pose[:3, :] = np.array(out.pose).reshape(3, 4)
+        nk = int(out.n_cand)
+        info = {"kf_pos": kf_pos, "kf_id": self.keyframes[kf_pos]["id"] if kf_pos >= 0 else None,
+                "candidates": [(int(cpos[i]), int(cscore[i]), int(cinl[i])) for i in range(nk)],
+                "n_corr": int(out.n_corr), "n_inliers": int(out.n_inliers), "point": point[:n], "inlier": inlier[:n].astype(bool),
+                "from_token": bool(out.from_token)}
+        return bool(out.ok), pose, info
+
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
     def _sync_size(self):
         s = (C.c_int64 * 6)()
