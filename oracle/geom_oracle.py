@@ -51,6 +51,12 @@ def _design(x1, x2):
                      x2[:, 1], x1[:, 0], x1[:, 1], np.ones(len(x1))], axis=1)
 
 
+def _design9(x1, x2):
+    """the design matrix, padded with zero rows to 9: a reduced SVD of 8 rows has no 9th right singular vector (the null vector)"""
+    A = _design(x1, x2)
+    return A if len(A) >= 9 else np.vstack([A, np.zeros((9 - len(A), 9))])
+
+
 def project_essential(E):
     U, s, Vt = np.linalg.svd(E)
     return U @ np.diag([1.0, 1.0, 0.0]) @ Vt
@@ -110,7 +116,7 @@ def find_essential_ransac8(p1, p2, K, thr_px=3.0, n_hyp=4096, seed=4096, pair=0,
         if c == c_prev and tau2 == tau2_prev:  # same selection size at the same threshold: converged
             break
         c_prev, tau2_prev = c, tau2
-        _, _, Vt = np.linalg.svd(_design(x1[sel], x2[sel]), full_matrices=False)
+        _, _, Vt = np.linalg.svd(_design9(x1[sel], x2[sel]), full_matrices=False)
         E = project_essential(Vt[-1].reshape(3, 3))
         tau2 = min(max(9.0 * float(d[sel].sum()) / c, lo2), thr2)
     mask = sampson(E, x1, x2) <= thr2
@@ -177,18 +183,48 @@ def init_two_view(p1, p2, K, thr_px=3.0, n_hyp=4096, seed=4096, pair=0):
     return dict(E=E, R=R, t=t, ransac_mask=mask, pose_mask=pmask, X=X, n_good=n_good)
 
 
-def synthetic_two_view(seed=4096, n=2000, outlier_frac=0.3, K=None, w=640, h=480):
-    """seeded two-view problem with ground truth."""
+def rodrigues(rv):
+    rv = np.asarray(rv, np.float64)
+    th = np.linalg.norm(rv)
+    if th == 0:
+        return np.eye(3)
+    k = rv / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+
+
+def synthetic_two_view(seed=4096, n=2000, outlier_frac=0.3, K=None, w=640, h=480, rv=(0.02, -0.05, 0.01), t_dir=(1.0, 0.1, 0.05),
+                       depth=None, noise_px=0.0, plane=None):
+    """seeded two-view problem with ground truth.  X2 = R X1 + t with |t| = 1 (depths are in baselines).
+    With the defaults (depth=None) the points fill the box [-4, 4]^2 x [4, 12] in front of camera 1, as this scene always did (many
+    project outside the image).  depth=(lo, hi): every point is seen by both cameras - a pixel drawn uniformly in image 1 at a depth
+    drawn uniformly in [lo, hi], kept only when it projects inside image 2 in front of camera 2.  noise_px: N(0, noise_px) added to
+    both images' pixel coordinates of every point (drawn last, so the noise-free scene is the same).  plane=(nx, ny, nz, d, th):
+    instead of a depth range, each point lies on the plane n.X = d of camera 1, its depth scaled by a factor drawn in [1 - th, 1 + th].
+    -> dict(K, p1, p2 (float32 pixels), R, t (3, 1), X (n, 3) in camera 1, z1 / z2 (n,) true depths in camera 1 / 2, outlier (n,))"""
     rng = np.random.Generator(np.random.PCG64(seed))
     if K is None:
         K = np.array([[320.0, 0, 320.0], [0, 320.0, 240.0], [0, 0, 1.0]])
-    X = np.stack([rng.uniform(-4, 4, n), rng.uniform(-4, 4, n), rng.uniform(4, 12, n)], axis=1)
-    rv = np.array([0.02, -0.05, 0.01])
-    th = np.linalg.norm(rv)
-    k = rv / th
-    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
-    t = np.array([1.0, 0.1, 0.05]); t /= np.linalg.norm(t)
+    K = np.asarray(K, np.float64)
+    R = rodrigues(rv)
+    t = np.asarray(t_dir, np.float64).copy(); t /= np.linalg.norm(t)
+    if depth is None:
+        X = np.stack([rng.uniform(-4, 4, n), rng.uniform(-4, 4, n), rng.uniform(4, 12, n)], axis=1)
+    else:
+        Ki = np.linalg.inv(K)
+        X = np.empty((0, 3))
+        while len(X) < n:
+            k = 2 * (n - len(X)) + 64
+            uv = np.stack([rng.uniform(0, w, k), rng.uniform(0, h, k), np.ones(k)], axis=1)
+            ray = (Ki @ uv.T).T
+            if plane is None:
+                Xk = ray * rng.uniform(depth[0], depth[1], k)[:, None]
+            else:
+                Xk = ray * (plane[3] / (ray @ np.asarray(plane[:3], np.float64)) * rng.uniform(1 - plane[4], 1 + plane[4], k))[:, None]
+            q = (K @ ((R @ Xk.T).T + t).T).T
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ok = (q[:, 2] > 0) & (q[:, 0] >= 0) & (q[:, 0] <= w * q[:, 2]) & (q[:, 1] >= 0) & (q[:, 1] <= h * q[:, 2])
+            X = np.concatenate([X, Xk[ok]])[:n]
     x1 = (K @ X.T).T; p1 = x1[:, :2] / x1[:, 2:3]
     Xc2 = (R @ X.T).T + t
     x2 = (K @ Xc2.T).T; p2 = x2[:, :2] / x2[:, 2:3]
@@ -196,7 +232,48 @@ def synthetic_two_view(seed=4096, n=2000, outlier_frac=0.3, K=None, w=640, h=480
     out = rng.random(n) < outlier_frac
     no = int(out.sum())
     p2[out] = np.stack([rng.uniform(0, w, no), rng.uniform(0, h, no)], axis=1).astype(np.float32)
-    return dict(K=K, p1=p1, p2=p2, R=R, t=t.reshape(3, 1), X=X, outlier=out)
+    if noise_px > 0:
+        p1 = (p1 + rng.normal(0, noise_px, p1.shape)).astype(np.float32)
+        p2 = (p2 + rng.normal(0, noise_px, p2.shape)).astype(np.float32)
+    return dict(K=K, p1=p1, p2=p2, R=R, t=t.reshape(3, 1), X=X, z1=X[:, 2].copy(), z2=Xc2[:, 2].copy(), outlier=out)
+
+
+# Two-view regimes shared by tests/test_oracle_geom.py (the oracle recovers ground truth) and tests/test_gpu_geometry_regimes.py
+# (every two-view entry point against the oracle): keyword arguments of synthetic_two_view.  All but "sideways" see every point in
+# both images.  Disparities: sideways motion at depth z moves a point by f / z pixels.
+_K320 = ((320.0, 0, 320.0), (0, 320.0, 240.0), (0, 0, 1.0))
+REGIMES = {
+    "sideways": dict(),                                                                  # today's scene, exactly
+    "forward": dict(t_dir=(0.0, 0.0, -1.0), depth=(4, 12)),                              # camera 2 moves forward: epipole at the centre
+    "backward": dict(t_dir=(0.05, -0.03, 1.0), depth=(4, 12)),                           # camera 2 moves back; epipole in the image
+    "diagonal": dict(t_dir=(1.0, 1.0, 1.0), depth=(4, 12)),
+    "rot15": dict(rv=tuple(np.radians(15.0) * np.array([0.2, 1.0, 0.3]) / np.linalg.norm([0.2, 1.0, 0.3])), depth=(4, 12)),
+    "rot30": dict(rv=tuple(np.radians(30.0) * np.array([0.3, 0.2, 1.0]) / np.linalg.norm([0.3, 0.2, 1.0])), depth=(4, 12)),
+    # f = 80: 1.8 - 3.2 px of parallax at 25 - 45 baselines, inside the depth cut of 50 (at f = 320 the same parallax lies at
+    # 100 - 300 baselines, where the cheirality vote keeps nothing)
+    "low_parallax": dict(K=((80.0, 0, 160.0), (0, 80.0, 120.0), (0, 0, 1.0)), w=320, h=240, depth=(25, 45), rv=(0.002, -0.005, 0.001)),
+    "far": dict(depth=(4, 120)),                                                         # part of the scene beyond the depth cut
+    "long_f": dict(K=((3000.0, 0, 1920.0), (0, 3000.0, 1080.0), (0, 0, 1.0)), w=3840, h=2160, depth=(4, 12)),
+    "short_f": dict(K=((150.0, 0, 320.0), (0, 150.0, 240.0), (0, 0, 1.0)), w=640, h=480, depth=(4, 12)),  # |x_n| up to 2.1
+    "aniso": dict(K=((300.0, 0, 448.0), (0, 345.0, 144.0), (0, 0, 1.0)), depth=(4, 12)),  # fx != fy, centre off by 20 % of w / h
+    "noise05": dict(depth=(4, 12), noise_px=0.5),
+    # near-planar (depths within 5 % of a tilted plane at 8 baselines), 0.5 px noise, no outliers: a plane leaves the 8-point design
+    # a 3-dimensional null space, so the two smallest eigenvalues of the refits' normal matrix lie close together (ratio 0.9 here) -
+    # the case wave_smallest_eigvec9's repeated squaring of the inverse exists for
+    "planar": dict(depth=(0, 0), plane=(0.3, 0.2, 1.0, 8.0, 0.05), noise_px=0.5, outlier_frac=0.0),
+    "min8": dict(depth=(4, 12), n=8, outlier_frac=0.0),
+    "min9": dict(depth=(4, 12), n=9, outlier_frac=0.0),
+    "m4097": dict(depth=(4, 12), n=4097),
+}
+
+
+def regime_scene(name, seed=4096, n=2000, outlier_frac=0.3):
+    kw = dict(REGIMES[name])
+    kw.setdefault("n", n)
+    kw.setdefault("outlier_frac", outlier_frac)
+    if "K" in kw:
+        kw["K"] = np.array(kw["K"], np.float64)
+    return synthetic_two_view(seed=seed, **kw)
 
 
 # ---- tracking step (reference src/orbslam2/tracker.py:214-254) -------------------------------------------------------
@@ -282,7 +359,7 @@ def find_fundamental_ransac8(p1, p2, thr_px=3.0, n_hyp=4096, seed=4096, pair=0, 
         if c == c_prev and tau2 == tau2_prev:
             break
         c_prev, tau2_prev = c, tau2
-        _, _, Vt = np.linalg.svd(_design(x1[sel], x2[sel]), full_matrices=False)
+        _, _, Vt = np.linalg.svd(_design9(x1[sel], x2[sel]), full_matrices=False)
         F = rank2(Vt[-1].reshape(3, 3))
         tau2 = min(max(9.0 * float(d[sel].sum()) / c, lo2), thr2)
     mask = sampson(F, x1, x2) <= thr2

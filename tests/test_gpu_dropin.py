@@ -552,6 +552,7 @@ def test_bench_workload_all_pairs_properties():
     worst = {int(np.argmin(dot_t)), int(np.argmax(err_R)), 9} | {int(v) for v in rng.choice(nb - 1, 4, replace=False)}
     fr_np = frames.cpu().numpy()
     kp28 = b["kps"].cpu().numpy().view(np.uint8).reshape(nb, cap, 28)
+    tail = []
     for i in sorted(worst):
         n = cn[i]
         ps, idx = mp[i, :n], mi[i, :n]
@@ -568,12 +569,38 @@ def test_bench_workload_all_pairs_properties():
         both = gmask & o["pose_mask"]
         e = np.linalg.norm(X[i, q_of[both]] - o["X"][both], axis=1) / np.linalg.norm(o["X"][both], axis=1)
         # this scene's points sit 19 and 38 baselines away (pan of 16.7 / 8.4 px per frame at f = 320): a relative pose difference d
-        # moves a point by about depth x d, so two poses inside the 1e-4 bound above leave the bulk of the points within 1e-4 of
-        # each other and the tail (measured on the worst pair, 116: 99th percentile 4e-3, maximum 7e-3) a few 1e-3 apart
+        # moves a point by about depth x d; the poses now agree to 1e-12, so that term is below 1e-8 here.  Measured on MI355X with
+        # the 8-step map-point DLT: p75 0 on every checked pair, maximum 2.2e-5 from ONE point of pair 116 ((s4 / s3)^2 = 0.28: 8
+        # inverse-iteration steps did not converge; see dlt_point); with DLT_MAP_IT: p75 0 and maximum 0 on all six pairs
+        # (profiles/twoview_regimes.txt; the 4e-3 / 7e-3 of an earlier kernel no longer occurs).  The flat bounds keep their old
+        # limits; p75 < 1e-6 and max < 1e-5 hold the tail
         worst = int(np.argmax(e))
         info = "pair %d map points vs oracle: median %.2e, 99 %% %.2e, max %.2e at depth %.1f" % (
             i, np.median(e), np.percentile(e, 99), e.max(), o["X"][both][worst, 2])
         assert np.median(e) < 1e-4 and np.percentile(e, 75) < 1e-3 and e.max() < 5e-2, info
+        assert np.percentile(e, 75) < 1e-6 and e.max() < 1e-5, info
+        # (b) the same comparison point by point: X of the kernel's pose against X of the oracle's differs by the pose difference
+        # times each point's sensitivity - measured in f64 by triangulating the oracle's correspondences under BOTH poses (the
+        # directional derivative along the actual pose difference).  Factor 2 covers the second-order terms; 4e-7 the float32
+        # rounding of both outputs (2^-24 sqrt 3 relative each, twice for the division by w) and the kernel's own DLT error (< 1e-7
+        # on these points, checked alone in (a)).
+        qa, qb = p1[both].astype(np.float64), p2[both].astype(np.float64)
+        P1o = K @ np.hstack([np.eye(3), np.zeros((3, 1))])
+        Xa = G.triangulate(P1o, K @ np.hstack([R, t.reshape(3, 1)]), qa, qb)
+        Xb = G.triangulate(P1o, K @ np.hstack([o["R"], o["t"]]), qa, qb)
+        sens = np.linalg.norm(Xa[:, :3] / Xa[:, 3:4] - Xb[:, :3] / Xb[:, 3:4], axis=1) / np.linalg.norm(o["X"][both], axis=1)
+        over = e > 2 * sens + 4e-7
+        assert not over.any(), (i, int(over.sum()), e[over].max(), sens[over].max())
+        # (a) the triangulation alone: the oracle's inliers under the oracle's own P1, P2, through mo_triangulate_points - no pose
+        # difference, so no conditioning tail: every point within 1e-5 of the oracle's SVD
+        pm = o["pose_mask"]
+        P2o = K @ np.hstack([o["R"], o["t"]])
+        X4 = ctx.triangulate_points(P1o, P2o, p1[pm], p2[pm]).astype(np.float64)
+        Xo = G.triangulate(P1o, P2o, p1[pm].astype(np.float64), p2[pm].astype(np.float64))
+        ea = np.linalg.norm(X4[:, :3] / X4[:, 3:4] - Xo[:, :3] / Xo[:, 3:4], axis=1) / np.linalg.norm(Xo[:, :3] / Xo[:, 3:4], axis=1)
+        assert ea.max() <= 1e-5, (i, ea.max())
+        tail.append((i, float(np.percentile(e, 75)), float(e.max()), float(ea.max())))
+    print("bench-frame map points vs oracle (pair, p75, max, triangulation-only max):", tail)
     for f in sorted({0, int(np.argmin(dot_t)), 128, nb - 1}):
         ek, ed = O.detect_and_compute(fr_np[f], O.params(nfeatures=2000))
         n = cn[f]

@@ -1,5 +1,6 @@
 """CPU: the numpy two-view oracle recovers the synthetic ground truth."""
 import numpy as np
+import pytest
 
 from oracle import geom_oracle as G
 
@@ -31,3 +32,83 @@ def test_too_few_points():
     s = G.synthetic_two_view(seed=1, n=7, outlier_frac=0)
     r = G.init_two_view(s["p1"], s["p2"], s["K"])
     assert r["n_good"] == 0 and r["R"] is None
+
+
+# ---- every regime of G.REGIMES (shared with tests/test_gpu_geometry_regimes.py): the oracle itself recovers ground truth, so that a
+# GPU disagreement there points at the kernel
+def _sampson_px(R, t, x1, x2, f):
+    """signed Sampson residual in pixels (first-order geometric distance, std = sigma under N(0, sigma) pixel noise on both images)"""
+    E = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]]) @ R
+    h1 = np.concatenate([x1, np.ones((len(x1), 1))], 1); h2 = np.concatenate([x2, np.ones((len(x2), 1))], 1)
+    Ex1, Etx2 = h1 @ E.T, h2 @ E
+    num = (h2 * Ex1).sum(1)
+    return f * num / np.sqrt(Ex1[:, 0] ** 2 + Ex1[:, 1] ** 2 + Etx2[:, 0] ** 2 + Etx2[:, 1] ** 2)
+
+
+def _pose_jacobian(s, sel):
+    """d(Sampson residual, px) / d(rotation vector (3), tangent of the unit translation (2)) at the true pose, central differences"""
+    K = s["K"]; f = (K[0, 0] + K[1, 1]) / 2
+    x1, x2 = G.normalise(s["p1"][sel], K), G.normalise(s["p2"][sel], K)
+    R0, t0 = s["R"], s["t"].ravel()
+    b1 = np.cross(t0, [1.0, 0, 0] if abs(t0[0]) < 0.9 else [0, 1.0, 0]); b1 /= np.linalg.norm(b1); b2 = np.cross(t0, b1)
+
+    def pose(th):
+        t = t0 + th[3] * b1 + th[4] * b2
+        return G.rodrigues(th[:3]) @ R0, t / np.linalg.norm(t)
+    J = np.empty((len(x1), 5))
+    for k in range(5):
+        d = np.zeros(5); d[k] = 1e-6
+        J[:, k] = (_sampson_px(*pose(d), x1, x2, f) - _sampson_px(*pose(-d), x1, x2, f)) / 2e-6
+    return J, pose
+
+
+NOISE_FREE = [r for r in G.REGIMES if "noise_px" not in G.REGIMES[r]]
+
+
+@pytest.mark.parametrize("regime", NOISE_FREE)
+def test_oracle_ground_truth_noise_free(regime):
+    s = G.regime_scene(regime, outlier_frac=0.0)
+    r = G.init_two_view(s["p1"], s["p2"], s["K"], thr_px=3.0, n_hyp=1024, seed=4096)
+    # the only error left is the float32 rounding of the pixels (<= 2^-24 |u|, about 1e-7 of the parallax at 640 px); a minimal set
+    # has no redundancy and its 8 x 9 design amplifies that by 1 / sigma8 of the design (3.5e-3 on this scene), hence 1e-4 there
+    tol = 1e-4 if regime in ("min8", "min9") else 1e-5
+    assert rel(r["R"], s["R"]) < tol and rel(r["t"], s["t"]) < tol, (regime, rel(r["R"], s["R"]), rel(r["t"], s["t"]))
+    inside = (s["z1"] < 50) & (s["z2"] < 50)   # the cheirality vote keeps depths in (0, 50) in both cameras
+    assert np.array_equal(r["pose_mask"], inside), regime
+    good = r["pose_mask"]
+    e = np.linalg.norm(r["X"][good] - s["X"][good], axis=1) / np.linalg.norm(s["X"][good], axis=1)
+    # per point the same rounding, amplified by depth / (baseline x sin(parallax)): largest next to the epipole of forward motion
+    assert np.median(e) < 1e-5 and e.max() < 1e-4, (regime, np.median(e), e.max())
+
+
+@pytest.mark.parametrize("regime", list(G.REGIMES))
+def test_oracle_ground_truth_with_outliers(regime):
+    """30 % outliers: the final consensus keeps a few chance inliers (outliers within the threshold of their epipolar line) whose
+    residuals tilt the least-squares refits.  Bound, to first order: the pose moves by (J^T J)^-1 J^T r over the consensus rows, where
+    the true inliers contribute their noise (sigma (J^T J)^-1/2, 6 sigma allowed) and each chance inlier i at most
+    |(J^T J)^-1 J_i^T| thr; factor 2 for the linearisation."""
+    s = G.regime_scene(regime)
+    sig = G.REGIMES[regime].get("noise_px", 0.0)
+    r = G.init_two_view(s["p1"], s["p2"], s["K"], thr_px=3.0, n_hyp=1024, seed=4096)
+    assert r["R"] is not None
+    inl = ~s["outlier"]
+    # (planar: the scene nearly fits a 3-parameter family of essential matrices; RANSAC lands on one that the 5 % relief of the scene
+    # puts a few pixels away from part of the true correspondences - the regime exists for the solver, not for the truth)
+    assert r["ransac_mask"][inl].mean() > (0.85 if regime == "planar" else 0.99), regime
+    sel = r["ransac_mask"]
+    if regime == "planar":
+        # not identifiable: a plane fits a 3-parameter family of essential matrices, and 5 % of relief under 0.5 px of noise leaves
+        # RANSAC in another member's basin, where the linearisation below does not reach.  The regime exists for the refits' eigen
+        # solver (kernel against oracle, tests/test_gpu_geometry_regimes.py); here only the consensus size above and a proper pose
+        R = r["R"]
+        assert np.abs(R.T @ R - np.eye(3)).max() < 1e-12 and abs(np.linalg.det(R) - 1) < 1e-12 and abs(np.linalg.norm(r["t"]) - 1) < 1e-12
+        return
+    J, pose = _pose_jacobian(s, sel)
+    Ci = np.linalg.inv(J.T @ J)
+    chance = s["outlier"][sel]
+    dth = 3.0 * np.abs(Ci @ J[chance].T).sum(axis=1) + 6 * max(sig, 1e-4) * np.sqrt(np.diag(Ci))
+    # |dR|_F <= sqrt(2) |d omega|, |R|_F = sqrt 3; |dt| <= |d tangent|
+    bR = 2 * np.sqrt(2.0) * np.linalg.norm(dth[:3]) / np.sqrt(3.0)
+    bt = 2 * np.linalg.norm(dth[3:])
+    eR, et = rel(r["R"], s["R"]), rel(r["t"], s["t"])
+    assert eR < max(bR, 1e-5) and et < max(bt, 1e-5), (regime, eR, bR, et, bt, int(chance.sum()))

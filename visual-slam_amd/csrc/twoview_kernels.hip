@@ -847,8 +847,14 @@ __global__ __launch_bounds__(64 * TV_PARTS) void k_tv_score(TwoViewArgs a, TvWor
 
 // ---------------------------------------------------------------- finish --------------------------
 // DLT null vector of the 4x4 system [x*P3-P1; y*P3-P2] for two views: smallest eigenvector of A^T A by inverse
-// iteration (the matrix is rank 3 up to noise, so two or three steps reach machine precision)
-__device__ void dlt_point(const double* P1, const double* P2, double x1, double y1, double x2, double y2, double* X) {
+// iteration, which gains (s4 / s3)^2 per step and stops once the iterate stops moving.  Typical bench inliers ((s4 / s3)^2 ~ 1e-5) stop
+// after four steps.  A consensus point whose rays nearly miss each other gains far less: on bench pair 116 one map point has
+// (s4 / s3)^2 = 0.28 and needs 25 steps; a cap of 8 left it 2.2e-5 from the SVD's vector (the only point above 1e-7 on the checked
+// pairs).  The map points the caller gets therefore run up to DLT_MAP_IT steps.  The cheirality vote keeps 8: it only needs depth
+// signs away from 0 and the cut at 50, and outliers in recoverPose mode, whose rays miss by as much as they diverge, would run to any cap.
+#define DLT_VOTE_IT 8
+#define DLT_MAP_IT 32
+__device__ void dlt_point(const double* P1, const double* P2, double x1, double y1, double x2, double y2, double* X, int max_it) {
     double A[16];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -863,7 +869,7 @@ __device__ void dlt_point(const double* P1, const double* P2, double x1, double 
 #pragma unroll
         for (int j = i; j < 4; j++, k++) S[k] = A[i] * A[j] + A[4 + i] * A[4 + j] + A[8 + i] * A[8 + j] + A[12 + i] * A[12 + j];
     X[0] = 0.5; X[1] = 0.5; X[2] = 0.5; X[3] = 0.5;
-    smallest_eigvec<4>(S, X, 8);
+    smallest_eigvec<4>(S, X, max_it);
 }
 
 __device__ inline double block_sum(double v, double* s_red) {
@@ -1131,7 +1137,7 @@ __global__ __launch_bounds__(TVF_BLOCK) void k_tv_finish(TwoViewArgs a, TvWork w
                 if (a.d_P1) {  // keyframe map growth (local_mapper.py:148-149): triangulate the inliers with the caller's two projection matrices
                     double Pa[12], Pb[12], X[4];
                     for (int j = 0; j < 12; j++) { Pa[j] = a.d_P1[(size_t)pair * 12 + j]; Pb[j] = a.d_P2[(size_t)pair * 12 + j]; }
-                    dlt_point(Pa, Pb, (double)px[4 * i], (double)px[4 * i + 1], (double)px[4 * i + 2], (double)px[4 * i + 3], X);
+                    dlt_point(Pa, Pb, (double)px[4 * i], (double)px[4 * i + 1], (double)px[4 * i + 2], (double)px[4 * i + 3], X, DLT_MAP_IT);
                     const float xf = (float)X[0], yf = (float)X[1], zf = (float)X[2], wf = (float)X[3];
                     const int o = qidx[i];
                     Xout[3 * o] = xf / wf; Xout[3 * o + 1] = yf / wf; Xout[3 * o + 2] = zf / wf;
@@ -1209,7 +1215,7 @@ __global__ __launch_bounds__(TVF_BLOCK) void k_tv_finish(TwoViewArgs a, TvWork w
             for (int cnd = 0; cnd < 4; cnd++) {
                 double Pc[12], X[4];
                 for (int j = 0; j < 12; j++) Pc[j] = s_P[cnd][j];
-                dlt_point(P0, Pc, x1, y1, x2, y2, X);
+                dlt_point(P0, Pc, x1, y1, x2, y2, X, DLT_VOTE_IT);
                 bool ok = X[2] * X[3] > 0;
                 double iw = 1.0 / X[3];
                 double qx = X[0] * iw, qy = X[1] * iw, qz = X[2] * iw;
@@ -1256,7 +1262,7 @@ __global__ __launch_bounds__(TVF_BLOCK) void k_tv_finish(TwoViewArgs a, TvWork w
         const unsigned bits = cbits[i];
         if (!((bits >> win) & 1u)) continue;
         double X[4];
-        dlt_point(Pa, Pb, (double)px[4 * i], (double)px[4 * i + 1], (double)px[4 * i + 2], (double)px[4 * i + 3], X);
+        dlt_point(Pa, Pb, (double)px[4 * i], (double)px[4 * i + 1], (double)px[4 * i + 2], (double)px[4 * i + 3], X, DLT_MAP_IT);
         float xf = (float)X[0], yf = (float)X[1], zf = (float)X[2], wf = (float)X[3];
         int o = qidx[i];
         Xout[3 * o] = xf / wf; Xout[3 * o + 1] = yf / wf; Xout[3 * o + 2] = zf / wf;
@@ -1270,7 +1276,7 @@ __global__ void k_triangulate(TriArgs t, const float* __restrict__ p1, const flo
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double X[4];
-    dlt_point(t.P1, t.P2, (double)p1[2 * i], (double)p1[2 * i + 1], (double)p2[2 * i], (double)p2[2 * i + 1], X);
+    dlt_point(t.P1, t.P2, (double)p1[2 * i], (double)p1[2 * i + 1], (double)p2[2 * i], (double)p2[2 * i + 1], X, DLT_MAP_IT);
     for (int k = 0; k < 4; k++) X4[4 * i + k] = (float)X[k];
 }
 
