@@ -11,7 +11,11 @@
 // Flag words: kernels raise bits in c->flags_cur[0].  mo_dev_* calls point it at words 0..3 (accumulated until mo_dev_status reads
 // and clears them); host entry points point it at words 4..7, which they clear before and check after their own kernels - a host
 // call between mo_dev_frontend_batch and mo_dev_status neither erases nor inherits the pending device-call bits.
-static inline int* host_flags(mo_ctx* c) { return mo_host_flags(c); }
+int mo_decode_host_flags(mo_ctx* c, int f0, int f1, const char* cap_msg) {
+    if (f0 & 1) { c->tie_overflow = true; c->tie_levels = f1; return mo_fail(c, MO_ERR_CAPACITY, "internal per-level keypoint capacity exceeded (response ties)"); }
+    if (f0 & 2) return mo_fail(c, MO_ERR_CAPACITY, cap_msg);
+    return MO_OK;
+}
 
 extern "C" int mo_set_host_timing(mo_ctx* c, int on) {
     if (!c) return MO_ERR_ARG;
@@ -29,11 +33,9 @@ static bool grow_fin_slots(mo_ctx* c, int levels);
 
 static int check_flags(mo_ctx* c) {
     int f[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(f, host_flags(c), sizeof(f), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(f, mo_host_flags(c), sizeof(f), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (f[0] & 1) { c->tie_overflow = true; c->tie_levels = f[1]; return mo_fail(c, MO_ERR_CAPACITY, "internal per-level keypoint capacity exceeded (response ties)"); }
-    if (f[0] & 2) return mo_fail(c, MO_ERR_CAPACITY, "more keypoints than cap; counts holds the required sizes");
-    return MO_OK;
+    return mo_decode_host_flags(c, f[0], f[1]);
 }
 
 extern "C" int mo_dev_status(mo_ctx* c, int32_t flags[4]) {
@@ -56,8 +58,8 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
     if (rc) return rc;
     if (cap < 1) return mo_fail(c, MO_ERR_ARG, "cap must be >= 1");
     // host calls check their own flag words before they return; mo_dev_* calls accumulate theirs until mo_dev_status
-    c->flags_cur = host_call ? host_flags(c) : c->d_flags;
-    if (host_call == 1) HIPCHK(c, hipMemsetAsync(host_flags(c), 0, 4 * sizeof(int), c->stream));  // (2: the upload kernel cleared them)
+    c->flags_cur = host_call ? mo_host_flags(c) : c->d_flags;
+    if (host_call == 1) HIPCHK(c, hipMemsetAsync(mo_host_flags(c), 0, 4 * sizeof(int), c->stream));  // (2: the upload kernel cleared them)
     if (c->poison >= 0) {  // mo_dbg_set_poison (tests): whatever the margins skip must never reach a result
         HIPCHK(c, hipMemsetAsync(c->d_pyr, c->poison, (size_t)c->batch_alloc * c->plan.pyr_stride, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_blur, c->poison, (size_t)c->batch_alloc * c->plan.blur_stride, c->stream));
@@ -106,19 +108,17 @@ static int run_grid_extract(mo_ctx* c, const mo_orb_params* p, const mo_batch_io
     if (cap < 1) return mo_fail(c, MO_ERR_ARG, "cap must be >= 1");
     const int per_cell = p->nfeatures / 64, slots = 64 * per_cell;
     const size_t B = (size_t)batch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_eig = take(B * w * h * sizeof(float)), o_xy = take(B * slots * 2 * sizeof(float)), o_n = take(B * 66 * sizeof(int)),
-                 o_kb = take(B * 65 * sizeof(int32_t));
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, off))) return rc;
-    uint8_t* b = (uint8_t*)c->d_tmp;
-    float* d_eig = (float*)(b + o_eig);
-    float* d_xy = io->d_grid_xy ? io->d_grid_xy : (float*)(b + o_xy);
-    int* d_n = io->d_grid_n ? io->d_grid_n : (int*)(b + o_n);
+    Layout L;
+    const size_t o_eig = L.take(B * w * h * sizeof(float)), o_xy = L.take(B * slots * 2 * sizeof(float)), o_n = L.take(B * 66 * sizeof(int)),
+                 o_kb = L.take(B * 65 * sizeof(int32_t));
+    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    float* d_eig = L.at<float>(c->d_tmp, o_eig);
+    float* d_xy = io->d_grid_xy ? io->d_grid_xy : L.at<float>(c->d_tmp, o_xy);
+    int* d_n = io->d_grid_n ? io->d_grid_n : L.at<int>(c->d_tmp, o_n);
     c->flags_cur = c->d_flags;
     mo_stage_begin(c);
     if ((rc = gftt_launch(c, io->d_gray, w, h, p->nfeatures, d_eig, d_xy, d_n, batch))) return rc;
-    int32_t* d_kb = (int32_t*)(b + o_kb);
+    int32_t* d_kb = L.at<int32_t>(c->d_tmp, o_kb);
     if ((rc = gftt_records_launch(c, d_xy, d_n, per_cell, w, h, p->edge_threshold, io->d_kps, io->d_grid_kept, cap, io->d_counts, batch, d_kb))) return rc;
     mo_stage_mark(c, "grid_good_features");
     const int blur_margin = (c->plan.edge_threshold - 19) & ~3;
@@ -153,21 +153,13 @@ static int stage_images(mo_ctx* c, const uint8_t* img, int w, int h, int stride,
     return MO_OK;
 }
 
+// output staging of a batched host call (rows f * cap + i: a byte bound per array is enough)
 static int reserve_out(mo_ctx* c, int batch, int cap) {
-    if (c->d_kps && c->out_cap >= cap && c->out_batch >= batch) return MO_OK;
-    // drop all three and the recorded sizes first: a failed hipMalloc below must not leave a size check that passes
-    // with freed pointers
-    if (c->d_kps) hipFree(c->d_kps);
-    if (c->d_desc) hipFree(c->d_desc);
-    if (c->d_counts) hipFree(c->d_counts);
-    c->d_kps = nullptr; c->d_desc = nullptr; c->d_counts = nullptr;
-    c->out_cap = 0; c->out_batch = 0;
-    size_t n = (size_t)batch * cap;
-    HIPCHK(c, hipMalloc((void**)&c->d_kps, n * sizeof(mo_keypoint)));
-    HIPCHK(c, hipMalloc((void**)&c->d_desc, n * 32));
-    HIPCHK(c, hipMalloc((void**)&c->d_counts, (size_t)batch * sizeof(int)));
-    c->out_cap = cap; c->out_batch = batch;
-    return MO_OK;
+    const size_t n = (size_t)batch * cap;
+    int rc = mo_reserve(c, c->d_kps, c->kps_bytes, n * sizeof(mo_keypoint));
+    if (!rc) rc = mo_reserve(c, c->d_desc, c->desc_bytes, n * 32);
+    if (!rc) rc = mo_reserve(c, c->d_counts, c->counts_bytes, (size_t)batch * sizeof(int));
+    return rc;
 }
 
 // pinned host staging owned by the context (small host-API transfers: one copy each way and one synchronisation instead of a blocking
@@ -180,7 +172,6 @@ int mo_host_stage(mo_ctx* c, size_t bytes) {
     c->h_stage_bytes = bytes;
     return MO_OK;
 }
-static int host_stage(mo_ctx* c, size_t bytes) { return mo_host_stage(c, bytes); }
 
 // true when an overflowed level's final-keypoint slot can still grow (then the plan is invalidated so that the next call rebuilds it).
 // retainBest keeps EVERY element that ties with the quota boundary, so a level of a periodic synthetic pattern can keep all its
@@ -194,20 +185,6 @@ static bool grow_fin_slots(mo_ctx* c, int levels) {
         if (((levels >> L) & 1) && c->plan.lv[L].fin_cap < c->plan.lv[L].cand_cap && c->fin_slack[L] < (1 << 24)) { c->fin_slack[L] *= 8; grown = true; }
     c->fin_slack_dirty = c->fin_slack_dirty || grown;
     return grown;
-}
-
-static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
-                               int batch, mo_keypoint* kps, uint8_t* desc, int cap, int* counts);
-
-extern "C" int mo_orb_detect_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
-                                     int batch, mo_keypoint* kps, uint8_t* desc, int cap, int* counts) {
-    if (!c) return MO_ERR_ARG;
-    if (!kps || !counts) return mo_fail(c, MO_ERR_ARG, "kps/counts is NULL");
-    for (;;) {  // (at most 8 rounds: the slots reach the candidate capacity, where no overflow is possible)
-        c->tie_overflow = false; c->tie_levels = 0;
-        const int rc = detect_compute_once(c, p, img, w, h, stride, ch, batch, kps, desc, cap, counts);
-        if (rc != MO_ERR_CAPACITY || !c->tie_overflow || !grow_fin_slots(c, c->tie_levels)) return rc;
-    }
 }
 
 static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
@@ -229,9 +206,9 @@ static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t*
     const size_t n_rows = (size_t)batch * cap, o_cnt = 4 * sizeof(int), o_kps = (o_cnt + (size_t)batch * sizeof(int) + 15) & ~(size_t)15;
     const size_t o_desc = o_kps + n_rows * sizeof(mo_keypoint), total = o_desc + (desc ? n_rows * 32 : 0);
     if (total <= (size_t)2 << 20) {
-        if ((rc = host_stage(c, total))) return rc;
+        if ((rc = mo_host_stage(c, total))) return rc;
         uint8_t* hs = c->h_stage;
-        HIPCHK(c, hipMemcpyAsync(hs, host_flags(c), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hs, mo_host_flags(c), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(hs + o_cnt, c->d_counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(hs + o_kps, c->d_kps, n_rows * sizeof(mo_keypoint), hipMemcpyDeviceToHost, c->stream));
         if (desc) HIPCHK(c, hipMemcpyAsync(hs + o_desc, c->d_desc, n_rows * 32, hipMemcpyDeviceToHost, c->stream));
@@ -240,9 +217,7 @@ static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t*
         HIPCHK(c, hipStreamSynchronize(c->stream));
         clk.waited();
         std::memcpy(counts, hs + o_cnt, (size_t)batch * sizeof(int));  // MO_ERR_CAPACITY: counts already holds the sizes a retry needs
-        const int fl = ((const int*)hs)[0];
-        if (fl & 1) { c->tie_overflow = true; c->tie_levels = ((const int*)hs)[1]; return mo_fail(c, MO_ERR_CAPACITY, "internal per-level keypoint capacity exceeded (response ties)"); }
-        if (fl & 2) return mo_fail(c, MO_ERR_CAPACITY, "more keypoints than cap; counts holds the required sizes");
+        if ((rc = mo_decode_host_flags(c, ((const int*)hs)[0], ((const int*)hs)[1]))) return rc;
         for (int f = 0; f < batch; f++) {
             const int n = std::min(counts[f], cap);
             if (n <= 0) continue;
@@ -265,6 +240,17 @@ static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t*
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MO_OK;
+}
+
+extern "C" int mo_orb_detect_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
+                                     int batch, mo_keypoint* kps, uint8_t* desc, int cap, int* counts) {
+    if (!c) return MO_ERR_ARG;
+    if (!kps || !counts) return mo_fail(c, MO_ERR_ARG, "kps/counts is NULL");
+    for (;;) {  // (at most 8 rounds: the slots reach the candidate capacity, where no overflow is possible)
+        c->tie_overflow = false; c->tie_levels = 0;
+        const int rc = detect_compute_once(c, p, img, w, h, stride, ch, batch, kps, desc, cap, counts);
+        if (rc != MO_ERR_CAPACITY || !c->tie_overflow || !grow_fin_slots(c, c->tie_levels)) return rc;
+    }
 }
 
 extern "C" int mo_orb_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
@@ -313,10 +299,12 @@ extern "C" int mo_orb_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* 
     if ((rc = stage_images(c, img, w, h, stride, ch, 1, &d_gray))) return rc;
     std::vector<mo_keypoint> kk(n);
     for (int i = 0; i < n; i++) kk[i] = kps_in[keep[i]];
-    size_t kb = (size_t)n * sizeof(mo_keypoint);
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, kb + (size_t)n * 32))) return rc;
-    mo_keypoint* d_k = (mo_keypoint*)c->d_tmp;
-    uint8_t* d_d = (uint8_t*)c->d_tmp + kb;
+    const size_t kb = (size_t)n * sizeof(mo_keypoint);
+    Layout L;
+    const size_t o_k = L.take(kb), o_d = L.take((size_t)n * 32);
+    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    mo_keypoint* d_k = L.at<mo_keypoint>(c->d_tmp, o_k);
+    uint8_t* d_d = L.at<uint8_t>(c->d_tmp, o_d);
     HIPCHK(c, hipMemcpyAsync(d_k, kk.data(), kb, hipMemcpyHostToDevice, c->stream));
     mo_stage_begin(c);
     if ((rc = orb_launch_pyramid(c, d_gray, 1, nlevels, 0))) return rc;
@@ -346,10 +334,12 @@ extern "C" int mo_undistort(mo_ctx* c, const uint8_t* img, int w, int h, int str
     if (!(K[0] != 0.0) || !(K[4] != 0.0)) return mo_fail(c, MO_ERR_ARG, "focal length is zero");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t row = (size_t)w * ch, frame = row * h;
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, 2 * frame + 256);
+    Layout L;
+    const size_t o_src = L.take(frame), o_dst = L.take(frame);
+    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
     if (rc) return rc;
-    uint8_t* d_src = (uint8_t*)c->d_tmp;
-    uint8_t* d_dst = d_src + ((frame + 255) & ~(size_t)255);
+    uint8_t* d_src = L.at<uint8_t>(c->d_tmp, o_src);
+    uint8_t* d_dst = L.at<uint8_t>(c->d_tmp, o_dst);
     HIPCHK(c, hipMemcpy2DAsync(d_src, row, img, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
     mo_stage_begin(c);
     if ((rc = undistort_launch(c, d_src, d_dst, w, h, ch, 1, K, dist))) return rc;
@@ -367,13 +357,15 @@ static int gftt_run(mo_ctx* c, const uint8_t* img, int w, int h, int stride, int
     int rc = stage_images(c, img, w, h, stride, ch, 1, &d_gray);
     if (rc) return rc;
     const int per_cell = n_features / 64;
-    size_t eig_b = (size_t)w * h * sizeof(float), xy_b = (size_t)64 * per_cell * 2 * sizeof(float);
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, eig_b + xy_b + 64 * sizeof(int) + 64))) return rc;
-    float* d_eig = (float*)c->d_tmp;
-    float* d_xy = (float*)((uint8_t*)c->d_tmp + eig_b);
-    int* d_n = (int*)((uint8_t*)d_xy + xy_b);
-    c->flags_cur = host_flags(c);
-    HIPCHK(c, hipMemsetAsync(host_flags(c), 0, 4 * sizeof(int), c->stream));
+    const size_t eig_b = (size_t)w * h * sizeof(float), xy_b = (size_t)64 * per_cell * 2 * sizeof(float);
+    Layout L;
+    const size_t o_eig = L.take(eig_b), o_xy = L.take(xy_b), o_n = L.take(64 * sizeof(int));
+    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    float* d_eig = L.at<float>(c->d_tmp, o_eig);
+    float* d_xy = L.at<float>(c->d_tmp, o_xy);
+    int* d_n = L.at<int>(c->d_tmp, o_n);
+    c->flags_cur = mo_host_flags(c);
+    HIPCHK(c, hipMemsetAsync(mo_host_flags(c), 0, 4 * sizeof(int), c->stream));
     mo_stage_begin(c);
     if ((rc = gftt_launch(c, d_gray, w, h, n_features, d_eig, d_xy, d_n))) return rc;
     mo_stage_mark(c, "grid_good_features");
@@ -431,25 +423,23 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
     uint8_t* d_desc = c->d_slot_desc + (size_t)slot * scap * 32;
     int32_t* d_cnt = c->d_slot_cnt + slot;
     const size_t rowb = (size_t)w * ch, in_bytes = rowb * h, eig_b = (size_t)w * h * sizeof(float), xy_b = (size_t)slots * 2 * sizeof(float);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_eig = take(eig_b), o_out = off, o_fl = take(16), o_xy = take(xy_b), o_n = take(66 * sizeof(int)), o_kept = take((size_t)slots * sizeof(int32_t)),
-                 o_desc = take((size_t)slots * 32), out_end = off;
+    Layout L;
+    const size_t o_eig = L.take(eig_b), o_out = L.total, o_fl = L.take(16), o_xy = L.take(xy_b), o_n = L.take(66 * sizeof(int)),
+                 o_kept = L.take((size_t)slots * sizeof(int32_t)), o_desc = L.take((size_t)slots * 32), out_end = L.total;
     if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, out_end))) return rc;
-    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, ((size_t)w * h + 255) & ~(size_t)255))) return rc;
-    const size_t h_out = (in_bytes + 255) & ~(size_t)255;
+    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, mo_align((size_t)w * h, 256)))) return rc;
+    const size_t h_out = mo_align(in_bytes, 256);
     if ((rc = mo_host_stage(c, h_out + (out_end - o_out)))) return rc;
     uint8_t* hs = c->h_stage;
     uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
-    if ((size_t)stride == rowb) std::memcpy(hs, img, in_bytes);
-    else for (int y = 0; y < h; y++) std::memcpy(hs + (size_t)y * rowb, img + (size_t)y * stride, rowb);
+    mo_copy_rows(hs, img, rowb, h, (size_t)stride);
     uint8_t* b = (uint8_t*)c->d_tmp;
-    float* d_eig = (float*)(b + o_eig); float* d_xy = (float*)(b + o_xy); int* d_n = (int*)(b + o_n);
-    int32_t* d_kept = (int32_t*)(b + o_kept);
-    c->flags_cur = host_flags(c);
+    float* d_eig = L.at<float>(b, o_eig); float* d_xy = L.at<float>(b, o_xy); int* d_n = L.at<int>(b, o_n);
+    int32_t* d_kept = L.at<int32_t>(b, o_kept);
+    c->flags_cur = mo_host_flags(c);
     mo_stage_begin(c);
-    if ((rc = orb_launch_ingest(c, hs_dev, w, h, ch, c->d_in, host_flags(c)))) return rc;
+    if ((rc = orb_launch_ingest(c, hs_dev, w, h, ch, c->d_in, mo_host_flags(c)))) return rc;
     mo_stage_mark(c, "h2d");
     const uint8_t* d_gray = c->d_in;
     if ((rc = gftt_launch(c, d_gray, w, h, n_features, d_eig, d_xy, d_n))) return rc;
@@ -460,7 +450,7 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
     mo_stage_mark(c, "compute");
     // descriptors of the kept corners and the flag words into the result region, then the region into the pinned buffer
     HIPCHK(c, hipMemcpyAsync(b + o_desc, d_desc, (size_t)slots * 32, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_fl, host_flags(c), 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_fl, mo_host_flags(c), 16, hipMemcpyDeviceToDevice, c->stream));
     mo_copy_out_launch(c, b + o_out, hs_dev + h_out, out_end - o_out);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "d2h");
@@ -470,8 +460,8 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
     const uint8_t* ho = hs + h_out;
     const int* hn = (const int*)(ho + (o_n - o_out));
     const float* hxy = (const float*)(ho + (o_xy - o_out));
-    const int fl = *(const int*)(ho + (o_fl - o_out));
-    if (fl & 2) return mo_fail(c, MO_ERR_CAPACITY, "more grid corners than the result slot holds");
+    const int* fl = (const int*)(ho + (o_fl - o_out));
+    if ((rc = mo_decode_host_flags(c, fl[0], fl[1], "more grid corners than the result slot holds"))) return rc;
     int n = 0;
     for (int cell = 0; cell < 64; cell++)
         for (int i = 0; i < std::min(hn[cell], per_cell); i++, n++) {
@@ -511,21 +501,14 @@ extern "C" int mo_match_knn2_ratio(mo_ctx* c, const uint8_t* q, int nq, const ui
     int rc;
     if ((rc = mo_reserve(c, c->d_mq, c->m_q_bytes, qb))) return rc;
     if ((rc = mo_reserve(c, c->d_mt, c->m_t_bytes, tb))) return rc;
-    if (n > c->m_n) {
-        if (c->d_midx) hipFree(c->d_midx);
-        if (c->d_mdist) hipFree(c->d_mdist);
-        if (c->d_mpass) hipFree(c->d_mpass);
-        c->d_midx = nullptr; c->d_mdist = nullptr; c->d_mpass = nullptr; c->m_n = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_midx, n * 2 * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_mdist, n * 2 * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_mpass, n));
-        c->m_n = n;
-    }
+    if ((rc = mo_reserve(c, c->d_midx, c->m_idx_bytes, n * 2 * sizeof(int32_t)))) return rc;
+    if ((rc = mo_reserve(c, c->d_mdist, c->m_dist_bytes, n * 2 * sizeof(int32_t)))) return rc;
+    if ((rc = mo_reserve(c, c->d_mpass, c->m_pass_bytes, n))) return rc;
     const size_t tbytes = (size_t)batch * nt * 32, o_t = (qb + 15) & ~(size_t)15, o_idx = (o_t + tbytes + 15) & ~(size_t)15;
     const size_t o_dist = o_idx + n * 2 * sizeof(int32_t), o_pass = o_dist + n * 2 * sizeof(int32_t), total = o_pass + n;
     const bool staged = total <= (size_t)2 << 20;  // the single-pair calls of the drop-in classes
     if (staged) {
-        if ((rc = host_stage(c, total))) return rc;
+        if ((rc = mo_host_stage(c, total))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));  // (the staging buffer of a previous call has been consumed)
         std::memcpy(c->h_stage, q, qb);
         if (nt > 0) std::memcpy(c->h_stage + o_t, t, tbytes);
@@ -580,23 +563,24 @@ extern "C" int mo_init_two_view(mo_ctx* c, const float* p1, const float* p2, int
         for (int i = 0; i < 3 * m; i++) X[i] = NAN;
         return MO_OK;
     }
-    size_t pb = (size_t)m * 2 * sizeof(float);
-    size_t need = 2 * pb + 12 * sizeof(double) + 9 * sizeof(double) + (size_t)m * 3 * sizeof(float) + 2 * (size_t)m + 64;
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, need + 256);
+    const size_t pb = (size_t)m * 2 * sizeof(float);
+    Layout L;
+    const size_t o_pose = L.take(12 * sizeof(double)), o_E = L.take(9 * sizeof(double)), o_n = L.take(sizeof(int32_t)), o_p1 = L.take(pb),
+                 o_p2 = L.take(pb), o_X = L.take((size_t)m * 3 * sizeof(float)), o_inl = L.take(m), o_ran = L.take(m);
+    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
     if (rc) return rc;
     uint8_t* b = (uint8_t*)c->d_tmp;
-    double* d_pose = (double*)b; b += 12 * sizeof(double);
-    double* d_E = (double*)b; b += 9 * sizeof(double);
-    int32_t* d_n = (int32_t*)b; b += 8;
-    float* d_p1 = (float*)b; b += pb;
-    float* d_p2 = (float*)b; b += pb;
-    float* d_X = (float*)b; b += (size_t)m * 3 * sizeof(float);
-    uint8_t* d_inl = b; b += m;
-    uint8_t* d_ran = b;
+    double* d_pose = L.at<double>(b, o_pose);
+    double* d_E = L.at<double>(b, o_E);
+    int32_t* d_n = L.at<int32_t>(b, o_n);
+    float* d_p1 = L.at<float>(b, o_p1);
+    float* d_p2 = L.at<float>(b, o_p2);
+    float* d_X = L.at<float>(b, o_X);
+    uint8_t* d_inl = b + o_inl;
+    uint8_t* d_ran = b + o_ran;
     HIPCHK(c, hipMemcpyAsync(d_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
     TwoViewArgs a;
-    std::memset(&a, 0, sizeof(a));
     a.n_pairs = 1; a.cap = m; a.n_hyp = n_hyp;
     for (int i = 0; i < 9; i++) a.K[i] = K[i];
     a.thr_px = thr_px; a.seed = seed;
@@ -630,11 +614,10 @@ extern "C" int mo_recover_pose(mo_ctx* c, const double E[9], const float* p1, co
     for (int i = 0; i < 3; i++) t[i] = NAN;
     if (m == 0) return MO_OK;
     const size_t pb = (size_t)m * 2 * sizeof(float);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_p1 = take(pb), o_p2 = take(pb), o_E = take(9 * sizeof(double)), o_min = take(m), o_pose = take(12 * sizeof(double)),
-                 o_X = take((size_t)m * 3 * sizeof(float)), o_inl = take(m), o_n = take(sizeof(int32_t));
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, off);
+    Layout L;
+    const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_E = L.take(9 * sizeof(double)), o_min = L.take(m), o_pose = L.take(12 * sizeof(double)),
+                 o_X = L.take((size_t)m * 3 * sizeof(float)), o_inl = L.take(m), o_n = L.take(sizeof(int32_t));
+    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
     if (rc) return rc;
     uint8_t* b = (uint8_t*)c->d_tmp;
     HIPCHK(c, hipMemcpyAsync(b + o_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
@@ -642,13 +625,12 @@ extern "C" int mo_recover_pose(mo_ctx* c, const double E[9], const float* p1, co
     HIPCHK(c, hipMemcpyAsync(b + o_E, E, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (mask_in) HIPCHK(c, hipMemcpyAsync(b + o_min, mask_in, (size_t)m, hipMemcpyHostToDevice, c->stream));
     TwoViewArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.n_pairs = 1; a.cap = m; a.n_hyp = 0;
+    a.n_pairs = 1; a.cap = m;
     for (int i = 0; i < 9; i++) a.K[i] = K[i];
     a.thr_px = 1.0;
-    a.d_p1 = (const float*)(b + o_p1); a.d_p2 = (const float*)(b + o_p2); a.m_fixed = m;
-    a.d_E_in = (const double*)(b + o_E); a.d_mask_in = mask_in ? b + o_min : nullptr;
-    a.d_pose = (double*)(b + o_pose); a.d_points = (float*)(b + o_X); a.d_inlier = b + o_inl; a.d_n_points = (int32_t*)(b + o_n);
+    a.d_p1 = L.at<float>(b, o_p1); a.d_p2 = L.at<float>(b, o_p2); a.m_fixed = m;
+    a.d_E_in = L.at<double>(b, o_E); a.d_mask_in = mask_in ? b + o_min : nullptr;
+    a.d_pose = L.at<double>(b, o_pose); a.d_points = L.at<float>(b, o_X); a.d_inlier = b + o_inl; a.d_n_points = L.at<int32_t>(b, o_n);
     mo_stage_begin(c);
     if ((rc = twoview_launch(c, a))) return rc;
     mo_stage_mark(c, "recover_pose");
@@ -675,22 +657,17 @@ extern "C" int mo_find_fundamental(mo_ctx* c, const float* p1, const float* p2, 
     for (int i = 0; i < 9; i++) F[i] = NAN;
     if (m < 8) { if (m > 0) std::memset(mask, 0, (size_t)m); return MO_OK; }
     const size_t pb = (size_t)m * 2 * sizeof(float);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_p1 = take(pb), o_p2 = take(pb), o_F = take(9 * sizeof(double)), o_X = take((size_t)m * 3 * sizeof(float)),
-                 o_ran = take(m), o_n = take(sizeof(int32_t));
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, off);
+    Layout L;
+    const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_F = L.take(9 * sizeof(double)), o_X = L.take((size_t)m * 3 * sizeof(float)),
+                 o_ran = L.take(m), o_n = L.take(sizeof(int32_t));
+    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
     if (rc) return rc;
     uint8_t* b = (uint8_t*)c->d_tmp;
     HIPCHK(c, hipMemcpyAsync(b + o_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
-    TwoViewArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.n_pairs = 1; a.cap = m; a.n_hyp = n_hyp; a.model = 1;
-    a.K[0] = a.K[4] = a.K[8] = 1.0;
-    a.thr_px = thr_px; a.seed = seed;
-    a.d_p1 = (const float*)(b + o_p1); a.d_p2 = (const float*)(b + o_p2); a.m_fixed = m;
-    a.d_E = (double*)(b + o_F); a.d_points = (float*)(b + o_X); a.d_ransac = b + o_ran; a.d_n_points = (int32_t*)(b + o_n);
+    TwoViewArgs a = tv_fundamental(1, m, n_hyp, thr_px, seed, 0);
+    a.d_p1 = L.at<float>(b, o_p1); a.d_p2 = L.at<float>(b, o_p2); a.m_fixed = m;
+    a.d_E = L.at<double>(b, o_F); a.d_points = L.at<float>(b, o_X); a.d_ransac = b + o_ran; a.d_n_points = L.at<int32_t>(b, o_n);
     mo_stage_begin(c);
     if ((rc = twoview_launch(c, a))) return rc;
     mo_stage_mark(c, "find_fundamental");
@@ -737,12 +714,14 @@ extern "C" int mo_triangulate_points(mo_ctx* c, const double P1[12], const doubl
     if (n < 0 || !P1 || !P2 || (n > 0 && (!p1 || !p2 || !X4))) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (n == 0) return MO_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    size_t pb = (size_t)n * 2 * sizeof(float);
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, 2 * pb + (size_t)n * 4 * sizeof(float) + 64);
+    const size_t pb = (size_t)n * 2 * sizeof(float);
+    Layout L;
+    const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_X = L.take((size_t)n * 4 * sizeof(float));
+    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
     if (rc) return rc;
-    float* d_p1 = (float*)c->d_tmp;
-    float* d_p2 = d_p1 + (size_t)n * 2;
-    float* d_X = d_p2 + (size_t)n * 2;
+    float* d_p1 = L.at<float>(c->d_tmp, o_p1);
+    float* d_p2 = L.at<float>(c->d_tmp, o_p2);
+    float* d_X = L.at<float>(c->d_tmp, o_X);
     HIPCHK(c, hipMemcpyAsync(d_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
     if ((rc = triangulate_launch(c, P1, P2, d_p1, d_p2, n, d_X))) return rc;
@@ -798,11 +777,7 @@ extern "C" int mo_dev_frontend_batch(mo_ctx* c, const mo_orb_params* p, const mo
                                 0, 0, np, io->cap, io->ratio, io->d_match_idx, io->d_match_dist, io->d_match_pass);
         if (rc) return rc;
         mo_stage_mark(c, "match_knn2_ratio");
-        TwoViewArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.n_pairs = np; a.cap = io->cap; a.n_hyp = io->n_hyp; a.model = 1;
-        a.K[0] = a.K[4] = a.K[8] = 1.0;
-        a.thr_px = io->thr_px; a.seed = io->seed; a.pair_base = io->pair_index_base;
+        TwoViewArgs a = tv_fundamental(np, io->cap, io->n_hyp, io->thr_px, io->seed, io->pair_index_base);
         a.d_kps = io->d_kps; a.d_counts = io->d_counts; a.d_match_idx = io->d_match_idx; a.d_match_pass = io->d_match_pass;
         a.d_qf = io->d_kf_query; a.d_tf = io->d_kf_train; a.need_two = 1; a.d_P1 = io->d_kf_P1; a.d_P2 = io->d_kf_P2;
         a.d_E = io->d_kf_F; a.d_points = io->d_points; a.d_n_points = io->d_n_points; a.d_inlier = io->d_pose_mask;
@@ -833,7 +808,6 @@ extern "C" int mo_dev_frontend_batch(mo_ctx* c, const mo_orb_params* p, const mo
     if (io->n_hyp > 0) {
         if (!io->d_points || !io->d_n_points) return mo_fail(c, MO_ERR_ARG, "two-view outputs missing");
         TwoViewArgs a;
-        std::memset(&a, 0, sizeof(a));
         a.n_pairs = n_pairs; a.cap = io->cap; a.n_hyp = io->n_hyp;
         for (int i = 0; i < 9; i++) a.K[i] = io->K[i];
         a.thr_px = io->thr_px; a.seed = io->seed; a.pair_base = io->pair_index_base;

@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <cstring>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vslam_amd.h"
@@ -119,7 +121,7 @@ struct mo_ctx {
     int* flags_cur = nullptr;      // the word block the kernels of the current call raise their bits in
     unsigned lds_attr_done = 0;    // bit per kernel whose max-dynamic-LDS attribute has been raised on this device
     // output staging for the host API (batches of frames)
-    mo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int* d_counts = nullptr; int out_cap = 0, out_batch = 0;
+    mo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int* d_counts = nullptr; size_t kps_bytes = 0, desc_bytes = 0, counts_bytes = 0;
     // Resident results of the last MO_RESULT_SLOTS single-frame extractions of the host API: slot s is "frame s" of these arrays, so the
     // pair stages (matcher, tracking filters, two-view) run on two slots exactly as they run on two frames of a batch, and a Tracker-style
     // caller that hands a frame's token back (mo_pair_frontend) uploads nothing.
@@ -130,7 +132,7 @@ struct mo_ctx {
                                    // kernels idles the GPU for ~ 4.5 us, five of them were 9 % of a single-frame extraction)
     // matcher staging
     uint8_t* d_mq = nullptr; uint8_t* d_mt = nullptr; int32_t* d_midx = nullptr; int32_t* d_mdist = nullptr;
-    uint8_t* d_mpass = nullptr; size_t m_q_bytes = 0, m_t_bytes = 0, m_n = 0;
+    uint8_t* d_mpass = nullptr; size_t m_q_bytes = 0, m_t_bytes = 0, m_idx_bytes = 0, m_dist_bytes = 0, m_pass_bytes = 0;
     uint2* d_match_part = nullptr; size_t match_part_bytes = 0;  // per-slice keys of a split k_match_lds launch
     // two-view work buffers
     void* d_tv = nullptr; size_t tv_bytes = 0;
@@ -162,20 +164,39 @@ int mo_fail(mo_ctx* c, int code, const std::string& msg);
             return mo_fail((c), MO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
     } while (0)
 
-// grow-only device buffer helper
+// grow-only device buffer helper (the pointer and its size are dropped before the free: a failure leaves nothing that passes the check)
 template <class T> int mo_reserve(mo_ctx* c, T*& p, size_t& have_bytes, size_t need_bytes) {
     if (need_bytes <= have_bytes && p) return MO_OK;
-    if (p) HIPCHK(c, hipFree(p));
+    T* old = p;
     p = nullptr; have_bytes = 0;
+    if (old) HIPCHK(c, hipFree(old));
     HIPCHK(c, hipMalloc((void**)&p, need_bytes ? need_bytes : 16));
     have_bytes = need_bytes;
     return MO_OK;
+}
+
+static inline size_t mo_align(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+
+// bump layout of a scratch region (c->d_tmp, a result slab): every piece starts on a 256-byte boundary
+struct Layout {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t o = total; total += mo_align(bytes, 256); return o; }
+    template <class T> static T* at(void* base, size_t off) { return (T*)((uint8_t*)base + off); }
+};
+
+// a strided host image (h rows of `row` bytes, `stride` apart) -> dense rows at dst (pinned staging)
+static inline void mo_copy_rows(uint8_t* dst, const uint8_t* src, size_t row, int h, size_t stride) {
+    if (stride == row) std::memcpy(dst, src, row * h);
+    else for (int y = 0; y < h; y++) std::memcpy(dst + (size_t)y * row, src + (size_t)y * stride, row);
 }
 
 // pinned, device-mapped host staging of the single-call host entry points (grow-only)
 int mo_host_stage(mo_ctx* c, size_t bytes);
 // flag words of the host entry points (see api.hip)
 static inline int* mo_host_flags(mo_ctx* c) { return c->d_flags + 4; }
+// the two host flag words read back after a call: bit 0 = response ties overflowed the final-keypoint slots of the levels in word 1
+// (recorded in c->tie_overflow / c->tie_levels), bit 1 = more results than the caller's cap (cap_msg); MO_OK or MO_ERR_CAPACITY
+int mo_decode_host_flags(mo_ctx* c, int f0, int f1, const char* cap_msg = "more keypoints than cap; counts holds the required sizes");
 
 // Host-side clock of the single-call entry points (mo_host_times): [0] entry -> everything enqueued (staging memcpy, copies, launches),
 // [1] the wait for the stream, [2] unpacking into the caller's arrays, [3] the whole call; microseconds.
@@ -204,6 +225,12 @@ int mo_detect_single(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int 
 int mo_slot_acquire(mo_ctx* c, int rows, int* slot);   // frame_api.hip: resident result slots for the other single-frame entry points
 uint64_t mo_slot_commit(mo_ctx* c, int slot, int n);
 uint8_t* mo_stage_dev(mo_ctx* c);                       // device address of the pinned staging buffer
+// frame_api.hip: a frame named by the token of a resident slot or by host arrays -> *slot (-1: not resident) and its row count *n;
+// MO_ERR_ARG ("<what> token is stale and no host arrays were given") when the token is not alive and the arrays are missing
+int mo_slot_of(const mo_ctx* c, uint64_t token);
+int mo_frame_lookup(mo_ctx* c, const mo_frame_ref* f, const char* what, int* slot, int* n);
+// the n rows of a looked-up frame -> d_kps / d_desc on the context stream: device to device from its slot, else from the host arrays
+int mo_frame_copy_rows(mo_ctx* c, const mo_frame_ref* f, int slot, int n, mo_keypoint* d_kps, uint8_t* d_desc);
 void mo_copy_out_launch(mo_ctx* c, const void* d_src, void* h_dst_dev, size_t bytes);  // device -> pinned staging, one small kernel
 
 // stage timing helpers (hipEvents on the context stream)
@@ -244,32 +271,41 @@ int match_launch_pairs(mo_ctx* c, const uint8_t* d_q, const uint8_t* d_t, size_t
 // gftt_kernels.hip
 int gftt_launch(mo_ctx* c, const uint8_t* d_gray, int w, int h, int n_features, float* d_eig, float* d_xy, int* d_n, int batch = 1);
 // twoview_kernels.hip
-struct TwoViewArgs {
-    int n_pairs, cap, n_hyp;
-    int model;  // 0: essential matrix (K-normalised coordinates, thr_px / focal) + pose + triangulation;
-                // 1: fundamental matrix (pixel coordinates, Hartley-normalised with one common scale): F in d_E, mask in d_ransac
-    double K[9], thr_px;
-    uint64_t seed;
-    uint64_t pair_base;  // global index of pair 0 (sharded batches): the sampling stream of a pair depends on its global index only
+struct TwoViewArgs {  // (an aggregate passed by value to the k_tv_* kernels: every field defaults to zero / null)
+    int n_pairs = 0, cap = 0, n_hyp = 0;
+    int model = 0;  // 0: essential matrix (K-normalised coordinates, thr_px / focal) + pose + triangulation;
+                    // 1: fundamental matrix (pixel coordinates, Hartley-normalised with one common scale): F in d_E, mask in d_ransac
+    double K[9] = {}, thr_px = 0;
+    uint64_t seed = 0;
+    uint64_t pair_base = 0;  // global index of pair 0 (sharded batches): the sampling stream of a pair depends on its global index only
     // per pair: matches are read from the matcher outputs + keypoints, or from explicit point arrays
-    const mo_keypoint* d_kps; const int32_t* d_counts; const int32_t* d_match_idx; const uint8_t* d_match_pass;
-    const int32_t* d_sel; const int32_t* d_sel_n;  // tracking mode: [pairs][cap][2] (queryIdx, trainIdx) in the caller's order + counts;
-                                                   // when set, these replace the ratio-test flags as the list of correspondences
-    const float* d_p1; const float* d_p2; int m_fixed;  // explicit points (host API): [m][2]
-    const int32_t* d_qf; const int32_t* d_tf;           // keyframe mode: [pairs] query / train frame of each pair (null: pair p = frames p, p + 1)
-    int need_two;                                       // keyframe mode: only queries with a second neighbour take part
-    const double* d_P1; const double* d_P2;             // fundamental model + these ([pairs][12], pixel projection matrices): the inliers are
+    const mo_keypoint* d_kps = nullptr; const int32_t* d_counts = nullptr; const int32_t* d_match_idx = nullptr; const uint8_t* d_match_pass = nullptr;
+    const int32_t* d_sel = nullptr; const int32_t* d_sel_n = nullptr;  // tracking mode: [pairs][cap][2] (queryIdx, trainIdx) in the caller's order +
+                                                                       // counts; when set, these replace the ratio-test flags as the list of correspondences
+    const float* d_p1 = nullptr; const float* d_p2 = nullptr; int m_fixed = 0;  // explicit points (host API): [m][2]
+    const int32_t* d_qf = nullptr; const int32_t* d_tf = nullptr;  // keyframe mode: [pairs] query / train frame of each pair (null: pair p = frames p, p + 1)
+    int need_two = 0;                                   // keyframe mode: only queries with a second neighbour take part
+    const double* d_P1 = nullptr; const double* d_P2 = nullptr;  // fundamental model + these ([pairs][12], pixel projection matrices): the inliers are
                                                         // triangulated with them into d_points (local_mapper.py:148-149)
-    const double* d_E_in; const uint8_t* d_mask_in;     // recoverPose on a GIVEN essential matrix ([pairs][9]) and consensus mask
+    const double* d_E_in = nullptr; const uint8_t* d_mask_in = nullptr;  // recoverPose on a GIVEN essential matrix ([pairs][9]) and consensus mask
                                                         // ([pairs][cap] by query index, may be null = all): no RANSAC, no refit
-    double* d_pose;   // [pairs][12]
-    double* d_E;      // [pairs][9] or null
-    float* d_points;  // [pairs][cap][3]
-    uint8_t* d_inlier; // [pairs][cap] pose mask
-    uint8_t* d_ransac; // [pairs][cap] RANSAC (Sampson) mask or null
-    int32_t* d_n_points; // [pairs]
-    int* flags;          // capacity flag word (none raised by this stage any more); set by twoview_launch
+    double* d_pose = nullptr;    // [pairs][12]
+    double* d_E = nullptr;       // [pairs][9] or null
+    float* d_points = nullptr;   // [pairs][cap][3]
+    uint8_t* d_inlier = nullptr; // [pairs][cap] pose mask
+    uint8_t* d_ransac = nullptr; // [pairs][cap] RANSAC (Sampson) mask or null
+    int32_t* d_n_points = nullptr; // [pairs]
+    int* flags = nullptr;        // capacity flag word (none raised by this stage any more); set by twoview_launch
 };
+static_assert(std::is_trivially_copyable<TwoViewArgs>::value, "TwoViewArgs is a kernel argument");
+// the fundamental-matrix RANSAC of the F sites (mo_find_fundamental, MO_MODE_KEYFRAME, the LocalMapper): pixel coordinates, identity K
+static inline TwoViewArgs tv_fundamental(int n_pairs, int cap, int n_hyp, double thr_px, uint64_t seed, uint64_t pair_base) {
+    TwoViewArgs a;
+    a.n_pairs = n_pairs; a.cap = cap; a.n_hyp = n_hyp; a.model = 1;
+    a.K[0] = a.K[4] = a.K[8] = 1.0;
+    a.thr_px = thr_px; a.seed = seed; a.pair_base = pair_base;
+    return a;
+}
 int twoview_launch(mo_ctx* c, const TwoViewArgs& a);
 // undistort_kernels.hip
 int undistort_launch(mo_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int ch, int batch, const double K[9],

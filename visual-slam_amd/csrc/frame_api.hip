@@ -16,13 +16,11 @@
 
 #include "common.h"
 
-static inline size_t al(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-
 // (re)allocates the slot arrays when rows of `cap` records do not fit; growing them invalidates every token (the row stride is the cap).
 // Callers use c->slot_cap - not their own cap - as the row stride afterwards.
 static int slots_reserve(mo_ctx* c, int cap) {
     if (c->d_slot_kps && c->slot_cap >= cap) return MO_OK;
-    cap = (int)al((size_t)cap, 16);
+    cap = (int)mo_align((size_t)cap, 16);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     void* old[] = {c->d_slot_kps, c->d_slot_desc, c->d_slot_cnt, c->d_slot_ids};
     for (void* b : old) if (b) hipFree(b);
@@ -42,11 +40,30 @@ static int slots_reserve(mo_ctx* c, int cap) {
     return MO_OK;
 }
 
-static int slot_of(const mo_ctx* c, uint64_t token) {
+int mo_slot_of(const mo_ctx* c, uint64_t token) {
     if (!token) return -1;
     for (int s = 0; s < MO_RESULT_SLOTS; s++)
         if (c->slot_token[s] == token) return s;
     return -1;
+}
+
+int mo_frame_lookup(mo_ctx* c, const mo_frame_ref* f, const char* what, int* slot, int* n) {
+    *slot = mo_slot_of(c, f->token);
+    *n = *slot >= 0 ? c->slot_n[*slot] : f->n;
+    if (*slot < 0 && (f->n < 0 || (f->n > 0 && (!f->kps || !f->desc))))
+        return mo_fail(c, MO_ERR_ARG, std::string(what) + " token is stale and no host arrays were given");
+    return MO_OK;
+}
+
+int mo_frame_copy_rows(mo_ctx* c, const mo_frame_ref* f, int slot, int n, mo_keypoint* d_kps, uint8_t* d_desc) {
+    if (n <= 0) return MO_OK;
+    const bool dev = slot >= 0;
+    const void* kps = dev ? (const void*)(c->d_slot_kps + (size_t)slot * c->slot_cap) : (const void*)f->kps;
+    const void* desc = dev ? (const void*)(c->d_slot_desc + (size_t)slot * c->slot_cap * 32) : (const void*)f->desc;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIPCHK(c, hipMemcpyAsync(d_kps, kps, (size_t)n * sizeof(mo_keypoint), kind, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_desc, desc, (size_t)n * 32, kind, c->stream));
+    return MO_OK;
 }
 
 // next slot in round-robin order that is not `keep`
@@ -112,8 +129,6 @@ __global__ __launch_bounds__(256) void k_copy_out(const uint4* __restrict__ src,
     if (t < n16) dst[t] = src[t];
 }
 
-static uint8_t* stage_dev(mo_ctx* c) { return mo_stage_dev(c); }
-
 void mo_copy_out_launch(mo_ctx* c, const void* d_src, void* h_dst_dev, size_t bytes) {
     const int n16 = (int)((bytes + 15) / 16);
     hipLaunchKernelGGL(k_copy_out, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const uint4*)d_src, (uint4*)h_dst_dev, n16);
@@ -131,15 +146,14 @@ int mo_detect_single(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int 
     if (rc) return rc;
     if ((rc = slots_reserve(c, cap))) return rc;
     const int scap = c->slot_cap;  // row stride of the slot arrays (>= cap: the kernels write up to scap rows, the caller gets up to cap)
-    const size_t row = (size_t)w * ch, in_bytes = row * h, o_out = al(in_bytes, 256);
-    const size_t o_kps = 32, o_desc = o_kps + al((size_t)scap * 28, 16), out_bytes = o_desc + (size_t)scap * 32;
+    const size_t row = (size_t)w * ch, in_bytes = row * h, o_out = mo_align(in_bytes, 256);
+    const size_t o_kps = 32, o_desc = o_kps + mo_align((size_t)scap * 28, 16), out_bytes = o_desc + (size_t)scap * 32;
     if ((rc = mo_host_stage(c, o_out + out_bytes))) return rc;
-    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, al((size_t)w * h, 256)))) return rc;
+    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, mo_align((size_t)w * h, 256)))) return rc;
     uint8_t* hs = c->h_stage;
-    uint8_t* hs_dev = stage_dev(c);
+    uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
-    if ((size_t)stride == row) std::memcpy(hs, img, in_bytes);
-    else for (int y = 0; y < h; y++) std::memcpy(hs + (size_t)y * row, img + (size_t)y * stride, row);
+    mo_copy_rows(hs, img, row, h, (size_t)stride);
     const int slot = next_slot(c, -1);
     mo_keypoint* d_k = c->d_slot_kps + (size_t)slot * scap;
     uint8_t* d_d = c->d_slot_desc + (size_t)slot * scap * 32;
@@ -155,10 +169,9 @@ int mo_detect_single(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     clk.waited();
     const int* ho = (const int*)(hs + o_out);
-    const int fl = ho[0], total = ho[4];
+    const int total = ho[4];
     counts[0] = total;  // MO_ERR_CAPACITY: counts already holds the size a retry needs
-    if (fl & 1) { c->tie_overflow = true; c->tie_levels = ho[1]; return mo_fail(c, MO_ERR_CAPACITY, "internal per-level keypoint capacity exceeded (response ties)"); }
-    if ((fl & 2) || total > cap) return mo_fail(c, MO_ERR_CAPACITY, "more keypoints than cap; counts holds the required sizes");
+    if ((rc = mo_decode_host_flags(c, ho[0] | (total > cap ? 2 : 0), ho[1]))) return rc;  // (the slot holds up to scap rows, the caller cap)
     const int n = std::min(std::max(total, 0), cap);
     if (n > 0) {
         std::memcpy(kps, hs + o_out + o_kps, (size_t)n * sizeof(mo_keypoint));
@@ -182,15 +195,15 @@ extern "C" int mo_last_token(mo_ctx* c, uint64_t* token) {
 // a frame of the pair -> its slot: the token's when it is alive, else the host arrays are uploaded into the next free slot
 static int resolve_frame(mo_ctx* c, const mo_frame_ref* f, int keep, uint8_t* hs, uint8_t* hs_dev, size_t stage_off, int* slot_out, int* n_out,
                          uint64_t* token_out) {
-    int s = slot_of(c, f->token);
-    if (s >= 0) { *slot_out = s; *n_out = c->slot_n[s]; *token_out = f->token; return MO_OK; }
-    if (f->n < 0 || (f->n > 0 && (!f->kps || !f->desc))) return mo_fail(c, MO_ERR_ARG, "frame token is stale and no host arrays were given");
-    if (f->n > c->slot_cap) return mo_fail(c, MO_ERR_CAPACITY, "frame has more keypoints than the resident slots hold");
+    int s, n;
+    int rc = mo_frame_lookup(c, f, "frame", &s, &n);
+    if (rc) return rc;
+    if (s >= 0) { *slot_out = s; *n_out = n; *token_out = f->token; return MO_OK; }
+    if (n > c->slot_cap) return mo_fail(c, MO_ERR_CAPACITY, "frame has more keypoints than the resident slots hold");
     s = next_slot(c, keep);
-    const int n = f->n;
     if (n > 0) {
         std::memcpy(hs + stage_off, f->kps, (size_t)n * 28);
-        std::memcpy(hs + stage_off + al((size_t)n * 28, 16), f->desc, (size_t)n * 32);
+        std::memcpy(hs + stage_off + mo_align((size_t)n * 28, 16), f->desc, (size_t)n * 32);
     }
     hipLaunchKernelGGL(k_unpack_in, dim3((unsigned)((n * 9 + 255) / 256 + 1)), dim3(256), 0, c->stream, hs_dev + stage_off, n,
                        c->d_slot_kps + (size_t)s * c->slot_cap, c->d_slot_desc + (size_t)s * c->slot_cap * 32, c->d_slot_cnt + s);
@@ -214,31 +227,30 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
     const bool track = pp->mode == MO_MODE_TRACK;
     int rc;
     // slots large enough for both frames (growing them invalidates the tokens: the host arrays then have to be there)
-    int s1 = slot_of(c, f1->token), s2 = slot_of(c, f2->token);
+    int s1 = mo_slot_of(c, f1->token), s2 = mo_slot_of(c, f2->token);
     int need_cap = c->slot_cap;
-    if (s1 < 0) need_cap = std::max(need_cap, (int)al((size_t)std::max(f1->n, 1), 16));
-    if (s2 < 0) need_cap = std::max(need_cap, (int)al((size_t)std::max(f2->n, 1), 16));
+    if (s1 < 0) need_cap = std::max(need_cap, (int)mo_align((size_t)std::max(f1->n, 1), 16));
+    if (s2 < 0) need_cap = std::max(need_cap, (int)mo_align((size_t)std::max(f2->n, 1), 16));
     if (need_cap != c->slot_cap && (rc = slots_reserve(c, need_cap))) return rc;
     const int cap = c->slot_cap;
-    const size_t up_bytes = al((size_t)cap * 28, 16) + (size_t)cap * 32;
+    const size_t up_bytes = mo_align((size_t)cap * 28, 16) + (size_t)cap * 32;
     // device outputs (one region, ordered so that each mode's results are contiguous for ONE copy back)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes, 256); return o; };
-    const size_t o_X = take((size_t)cap * 3 * sizeof(float)), o_ran = take(cap), o_midx = take((size_t)cap * 2 * sizeof(int32_t)),
-                 o_mdist = take((size_t)cap * 2 * sizeof(int32_t)), o_mpass = take(cap), o_sel = take((size_t)cap * 2 * sizeof(int32_t)),
-                 o_seld = take((size_t)cap * sizeof(int32_t)), o_seln = take(sizeof(int32_t)), o_pose = take(12 * sizeof(double)),
-                 o_E = take(9 * sizeof(double)), o_inl = take(cap), o_np = take(sizeof(int32_t)), out_end = off;
+    Layout L;
+    const size_t o_X = L.take((size_t)cap * 3 * sizeof(float)), o_ran = L.take(cap), o_midx = L.take((size_t)cap * 2 * sizeof(int32_t)),
+                 o_mdist = L.take((size_t)cap * 2 * sizeof(int32_t)), o_mpass = L.take(cap), o_sel = L.take((size_t)cap * 2 * sizeof(int32_t)),
+                 o_seld = L.take((size_t)cap * sizeof(int32_t)), o_seln = L.take(sizeof(int32_t)), o_pose = L.take(12 * sizeof(double)),
+                 o_E = L.take(9 * sizeof(double)), o_inl = L.take(cap), o_np = L.take(sizeof(int32_t)), out_end = L.total;
     if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, out_end))) return rc;
-    if ((rc = mo_host_stage(c, std::max(2 * al(up_bytes, 256), out_end)))) return rc;
+    if ((rc = mo_host_stage(c, std::max(2 * mo_align(up_bytes, 256), out_end)))) return rc;
     uint8_t* hs = c->h_stage;
-    uint8_t* hs_dev = stage_dev(c);
+    uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
     uint8_t* b = (uint8_t*)c->d_tmp;
     mo_stage_begin(c);
     int n1 = 0, n2 = 0;
-    s1 = slot_of(c, f1->token);  // (again: a reallocation above dropped the tokens)
-    if ((rc = resolve_frame(c, f1, slot_of(c, f2->token), hs, hs_dev, 0, &s1, &n1, &out->token1))) return rc;
-    if ((rc = resolve_frame(c, f2, s1, hs, hs_dev, al(up_bytes, 256), &s2, &n2, &out->token2))) return rc;
+    s1 = mo_slot_of(c, f1->token);  // (again: a reallocation above dropped the tokens)
+    if ((rc = resolve_frame(c, f1, mo_slot_of(c, f2->token), hs, hs_dev, 0, &s1, &n1, &out->token1))) return rc;
+    if ((rc = resolve_frame(c, f2, s1, hs, hs_dev, mo_align(up_bytes, 256), &s2, &n2, &out->token2))) return rc;
     out->n1 = n1; out->n2 = n2;
     if (n1 == 0 || n2 == 0) { HIPCHK(c, hipStreamSynchronize(c->stream)); return MO_OK; }  // (matcher.py:57-61: no matches)
     mo_stage_mark(c, "h2d");
@@ -262,7 +274,6 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
     }
     if (pose) {
         TwoViewArgs a;
-        std::memset(&a, 0, sizeof(a));
         a.n_pairs = 1; a.cap = cap; a.n_hyp = pp->n_hyp;
         for (int i = 0; i < 9; i++) a.K[i] = pp->K[i];
         a.thr_px = pp->thr_px; a.seed = pp->seed; a.pair_base = pp->pair_index;
@@ -278,11 +289,8 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
     const bool want_match = out->match_idx || out->match_dist || out->match_pass;
     const size_t from = !track ? (pose ? o_X : o_midx) : (want_match ? o_midx : o_sel);
     const size_t to = !track && !pose ? o_sel : out_end;
-    {
-        const int n16 = (int)((to - from) / 16);  // (every offset is a multiple of 256)
-        hipLaunchKernelGGL(k_copy_out, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const uint4*)(b + from), (uint4*)(hs_dev + from), n16);
-        HIPCHK(c, hipGetLastError());
-    }
+    mo_copy_out_launch(c, b + from, hs_dev + from, to - from);
+    HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "d2h");
     clk.enqueued();
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -74,7 +74,8 @@ struct mo_map {
     int32_t* first = nullptr; size_t first_bytes = 0;
     // growth step
     int32_t* midx = nullptr; int32_t* mdist = nullptr; uint8_t* mpass = nullptr; uint8_t* inl = nullptr; float* gpts = nullptr;
-    double* F = nullptr; int32_t* gnp = nullptr; size_t grow_rows = 0;
+    double* F = nullptr; int32_t* gnp = nullptr;
+    size_t midx_bytes = 0, mdist_bytes = 0, mpass_bytes = 0, inl_bytes = 0, gpts_bytes = 0, F_bytes = 0, gnp_bytes = 0;
     int32_t* h_stat = nullptr;                        // pinned [ST_NWORDS]
     // relocalization (mo_map_relocalize), grown with the map
     int32_t* rl_tab = nullptr; size_t rl_tab_bytes = 0;                        // point_of [slot][row]
@@ -581,26 +582,13 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     out->n_new = 0; out->from_token = 0;
     for (int i = 0; i < 9; i++) out->F[i] = NAN;
     // the frame: the resident result slot named by its token, else the host arrays
-    int rs = -1;
-    if (f->token)
-        for (int s = 0; s < MO_RESULT_SLOTS; s++) if (c->slot_token[s] == f->token) rs = s;
-    const int n = rs >= 0 ? c->slot_n[rs] : f->n;
-    if (n < 0 || (rs < 0 && n > 0 && (!f->kps || !f->desc))) return mo_fail(c, MO_ERR_ARG, "keyframe token is stale and no host arrays were given");
+    int rs, n;
+    if ((rc = mo_frame_lookup(c, f, "keyframe", &rs, &n))) return rc;
     const int slot = m->n_slots;
     if ((rc = kf_reserve(m, std::max(n, 1), slot + 1))) return rc;
     mo_stage_begin(c);
-    if (rs >= 0) {
-        if (n) {
-            HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)slot * m->row, c->d_slot_kps + (size_t)rs * c->slot_cap, (size_t)n * sizeof(mo_keypoint),
-                                     hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)slot * m->row * 32, c->d_slot_desc + (size_t)rs * c->slot_cap * 32, (size_t)n * 32,
-                                     hipMemcpyDeviceToDevice, c->stream));
-        }
-        out->from_token = 1;
-    } else if (n) {
-        HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)slot * m->row, f->kps, (size_t)n * sizeof(mo_keypoint), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)slot * m->row * 32, f->desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = mo_frame_copy_rows(c, f, rs, n, m->kkps + (size_t)slot * m->row, m->kdesc + (size_t)slot * m->row * 32))) return rc;
+    out->from_token = rs >= 0;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + slot), n, 1, c->stream));
     HIPCHK(c, hipMemcpyAsync(m->kP + (size_t)slot * 12, P, 96, hipMemcpyHostToDevice, c->stream));
     m->h_kcnt.push_back(n);
@@ -625,15 +613,10 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     if (ps >= 0 && nq > 0 && n > 0) {
         if (prm->n_hyp < 1) return mo_fail(c, MO_ERR_ARG, "n_hyp must be >= 1");
         const size_t rows = (size_t)m->row;
-        if (m->grow_rows < rows) {
-            void* gb[] = {m->midx, m->mdist, m->mpass, m->inl, m->gpts, m->F, m->gnp};
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (void* b : gb) if (b) HIPCHK(c, hipFree(b));
-            HIPCHK(c, hipMalloc((void**)&m->midx, rows * 8)); HIPCHK(c, hipMalloc((void**)&m->mdist, rows * 8));
-            HIPCHK(c, hipMalloc((void**)&m->mpass, rows)); HIPCHK(c, hipMalloc((void**)&m->inl, rows));
-            HIPCHK(c, hipMalloc((void**)&m->gpts, rows * 12)); HIPCHK(c, hipMalloc((void**)&m->F, 9 * 8)); HIPCHK(c, hipMalloc((void**)&m->gnp, 4));
-            m->grow_rows = rows;
-        }
+        if ((rc = reserve(c, m->midx, m->midx_bytes, rows * 8)) || (rc = reserve(c, m->mdist, m->mdist_bytes, rows * 8)) ||
+            (rc = reserve(c, m->mpass, m->mpass_bytes, rows)) || (rc = reserve(c, m->inl, m->inl_bytes, rows)) ||
+            (rc = reserve(c, m->gpts, m->gpts_bytes, rows * 12)) || (rc = reserve(c, m->F, m->F_bytes, 9 * 8)) || (rc = reserve(c, m->gnp, m->gnp_bytes, 4)))
+            return rc;
         bound_new = nq;
         if ((rc = pts_reserve(m, m->cur, (size_t)(m->n_pts + bound_new), (size_t)(m->n_obs + 2 * bound_new), true))) return rc;
         if ((rc = upload_pos_slot(m))) return rc;
@@ -643,11 +626,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
                                      m->mpass)))
             return rc;
         mo_stage_mark(c, "match_knn2_ratio");
-        TwoViewArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.n_pairs = 1; a.cap = (int)rows; a.n_hyp = prm->n_hyp; a.model = 1;
-        a.K[0] = a.K[4] = a.K[8] = 1.0;
-        a.thr_px = prm->thr_px; a.seed = prm->seed; a.pair_base = prm->pair_index;
+        TwoViewArgs a = tv_fundamental(1, (int)rows, prm->n_hyp, prm->thr_px, prm->seed, prm->pair_index);
         a.d_kps = m->kkps; a.d_counts = m->kcnt; a.d_match_idx = m->midx; a.d_match_pass = m->mpass;
         a.d_qf = qf; a.d_tf = tf; a.need_two = 1; a.d_P1 = m->kP + (size_t)ps * 12; a.d_P2 = m->kP + (size_t)slot * 12;
         a.d_E = m->F; a.d_points = m->gpts; a.d_n_points = m->gnp; a.d_inlier = m->inl;
@@ -1157,11 +1136,8 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
     const int nc = prm->max_candidates;
     for (int i = 0; i < 12; i++) out->pose[i] = NAN;
     out->ok = 0; out->kf_pos = -1; out->n_cand = 0; out->n_corr = 0; out->n_inliers = 0; out->from_token = 0;
-    int rs = -1;
-    if (f->token)
-        for (int s = 0; s < MO_RESULT_SLOTS; s++) if (c->slot_token[s] == f->token) rs = s;
-    const int n = rs >= 0 ? c->slot_n[rs] : f->n;
-    if (n < 0 || (rs < 0 && n > 0 && (!f->kps || !f->desc))) return mo_fail(c, MO_ERR_ARG, "frame token is stale and no host arrays were given");
+    int rs, n, rc;
+    if ((rc = mo_frame_lookup(c, f, "frame", &rs, &n))) return rc;
     out->from_token = rs >= 0;
     if (out->point) for (int i = 0; i < n; i++) out->point[i] = -1;
     if (out->inlier) std::memset(out->inlier, 0, (size_t)n);
@@ -1173,19 +1149,10 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
     const int n_kf = (int)m->pos_slot.size();
     if (n == 0 || n_kf == 0) return MO_OK;   // nothing to match: not relocalized, not an error
     if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    int rc;
     if ((rc = kf_reserve(m, n, m->n_slots))) return rc;   // (a wider row restrides the store; the map itself is unchanged)
     const int spare = m->kslots, row = m->row;
     mo_stage_begin(c);
-    if (rs >= 0) {
-        HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)spare * row, c->d_slot_kps + (size_t)rs * c->slot_cap, (size_t)n * sizeof(mo_keypoint),
-                                 hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)spare * row * 32, c->d_slot_desc + (size_t)rs * c->slot_cap * 32, (size_t)n * 32,
-                                 hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(m->kkps + (size_t)spare * row, f->kps, (size_t)n * sizeof(mo_keypoint), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(m->kdesc + (size_t)spare * row * 32, f->desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = mo_frame_copy_rows(c, f, rs, n, m->kkps + (size_t)spare * row, m->kdesc + (size_t)spare * row * 32))) return rc;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + spare), n, 1, c->stream));
     const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_kf * row, cand_n = (size_t)nc * row;
     if ((rc = reserve(c, m->rl_tab, m->rl_tab_bytes, tab_n * 4)) || (rc = reserve(c, m->rl_qf, m->rl_qf_bytes, (size_t)n_kf * 4)) ||
