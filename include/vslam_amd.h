@@ -472,6 +472,62 @@ int mo_map_sizes(mo_map*, int64_t out[6]);
 int mo_map_download(mo_map*, int field, void* dst, size_t bytes);
 int mo_map_write_ply(mo_map*, const char* path, int min_obs, int64_t* n_written);
 int mo_map_relocalize(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, mo_map_reloc_out*);
+
+/* mo_map_track: the pose of a tracked frame against the map as it stands, from a predicted pose (ORB-SLAM2's search by projection and
+ * Optimizer::PoseOptimization, monocular, pose only); reads the map, never changes it.  The frame is given like mo_map_relocalize's.
+ * pose0 = the predicted [R | t] row-major (X_cam = R X + t, the convention of mo_map_add_keyframe and mo_map_relocalize).
+ *   observations  read like the cull reads them (negative keyframe positions and rows count from the end; entries naming a position or
+ *                 row that does not exist are skipped).
+ *   local map     the points with a valid observation in the last `window` keyframe positions (0: every position).
+ *   descriptor    of a point: ComputeDistinctiveDescriptors over all its valid observations: per observation, its distances to all of
+ *                 them (itself included) sorted, median = the element at (n - 1) / 2; the smallest median wins, ties to the earlier
+ *                 observation in insertion order.  ref_octave = the octave of the winner's keypoint.
+ *   candidates    local points whose projection under the pass pose (P = K [R | t], f64, each row summed left to right) has z > 0 and
+ *                 u / z in [0, w), v / z in [0, h).
+ *   search        r = pass radius * scale_factor^ref_octave (repeated products from 1.0); the frame keypoints with |x - u| < r,
+ *                 |y - v| < r and |octave - ref_octave| <= 1; best = the lowest Hamming distance (ties to the lower keypoint), second =
+ *                 the next lowest distance; accepted when best <= max_dist and, if a second exists, best <= ratio * second (double).
+ *   conflicts     a keypoint goes to the point with the lowest distance, ties to the lower point index; the others stay unmatched.
+ *   retry         a pass with fewer than min_matches matches runs once more at twice its radius; still fewer: the call ends (ok = 0).
+ *   refinement    4 rounds of at most 10 Gauss-Newton steps on SE(3) over the round's inliers (all matches in round 0); a round stops at a
+ *                 step below 1e-12 or a Hessian that is not positive definite.  Residual = projection - keypoint, information
+ *                 1 / scale_factor^(2 octave) (octave of the frame keypoint, negative as 0), Huber width sqrt(chi2) in rounds 0 - 2, none
+ *                 in round 3.  After each round every match is reclassified: inlier when z > 0 and information * |residual|^2 <= chi2;
+ *                 fewer than 10 inliers end the refinement.
+ *   passes        pass k + 1 projects from pass k's refined pose and searches from scratch.  ok = the last pass finished with
+ *                 >= min_inliers inliers; pose = the refined pose of the last pass that finished, else pose0.
+ * An empty frame, a map without keyframes or map points: no pass runs, not an error.  No host round trip inside the call: the retry and
+ * the early exits are decided on the device.  One synchronisation: the copy-out. */
+typedef struct {
+    int32_t w, h;            /* a projection is a candidate only inside [0, w) x [0, h) */
+    int32_t window;          /* keyframe positions of the local map, counted from the last (10); 0: all */
+    int32_t n_pass;          /* 1 .. 4 (2) */
+    double radius[4];        /* search half-width of each pass at octave 0 (15, 4) */
+    double scale_factor;     /* scales the window and the information (1.2) */
+    double ratio;            /* best-to-second ratio (0.8) */
+    double chi2;             /* outlier threshold; the Huber width is its square root (5.991) */
+    int32_t max_dist;        /* ORB-SLAM2's TH_HIGH (100) */
+    int32_t min_matches;     /* a pass with fewer matches is retried once at twice its radius (20) */
+    int32_t min_inliers;     /* ok needs this many inliers after the last pass (30) */
+} mo_map_track_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n_q = keypoints of the frame */
+    int32_t* point;          /* [n_q] map point matched to each keypoint by the last pass searched (-1: none) */
+    int32_t* dist;           /* [n_q] its Hamming distance (-1: none) */
+    uint8_t* inlier;         /* [n_q] final classification of that pass's refinement (0 where it did not refine) */
+    /* filled by the call */
+    double pose[12];         /* [R | t] row-major of the last pass that finished, else pose0 */
+    double pass_pose[4][12]; /* refined pose of each pass (NaN: the pass did not finish) */
+    double pass_radius[4];   /* the radius each pass used (twice radius[k] after a retry; 0: did not run) */
+    int32_t pass_cand[4];    /* candidates of each pass (of its last attempt) */
+    int32_t pass_matches[4]; /* matches of each pass (of its last attempt) */
+    int32_t pass_inliers[4]; /* inliers after each pass's refinement */
+    int32_t n_pass_run;      /* passes whose search ran (a pass that ended the call included) */
+    int32_t n_local;         /* points of the local map */
+    int32_t ok;              /* 1: the last pass finished with >= min_inliers inliers */
+    int32_t from_token;      /* 1: the frame was read from its resident slot */
+} mo_map_track_out;
+int mo_map_track(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*, mo_map_track_out*);
 int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and

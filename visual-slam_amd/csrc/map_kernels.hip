@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "map_store.h"
 #include "pnp.h"
 
 #define MAP_SCAN_BLOCK 256
@@ -32,110 +33,7 @@
 #define MAP_LIST_CHUNK 1024   // observation entries per one-wave block of the counting sort
 #define MAP_MAX_KF 16384      // keyframes the counting sort's LDS cursors hold (64 KB)
 
-// status block (device, int32): live counts of the call in flight
-enum { ST_NPTS = 0, ST_NOBS, ST_NNEW, ST_ERR, ST_KEPT, ST_KOBS, ST_NLIST, ST_NWORDS = 8 };
-
-struct MapPts {
-    float* xyz = nullptr; uint8_t* col = nullptr; int32_t* id = nullptr; int32_t* dkf = nullptr; int32_t* drow = nullptr;
-    int32_t* off = nullptr;                           // [pcap + 1]
-    int32_t* okf = nullptr; int32_t* okp = nullptr;   // [ocap]
-    size_t pcap = 0, ocap = 0;
-};
-
-struct RelocRes;  // per-call results of mo_map_relocalize (below)
-
-struct mo_map {
-    mo_ctx* c = nullptr;
-    // keyframe store
-    int row = 0, kslots = 0, n_slots = 0;
-    mo_keypoint* kkps = nullptr; uint8_t* kdesc = nullptr; int32_t* kcnt = nullptr; double* kP = nullptr;
-    std::vector<int32_t> h_kcnt;
-    std::vector<int32_t> pos_slot;                    // keyframe position -> slot
-    int32_t* d_pos_slot = nullptr; size_t pos_slot_bytes = 0;
-    // the previous and the new keyframe image (colours of the grown points)
-    uint8_t* img[2] = {nullptr, nullptr}; size_t img_bytes[2] = {0, 0}; int img_w[2] = {0, 0}, img_h[2] = {0, 0}, img_ch[2] = {0, 0};
-    int img_cur = 0;
-    // map store
-    MapPts P[2]; int cur = 0;
-    int64_t n_pts = 0, n_obs = 0;
-    int64_t id_bound = 0;                             // every id < id_bound (the first-point table of the keyframe counts)
-    // per-keyframe lists of the last cull
-    // two sets: a chain writes the set lcur ^ 1, a successful call flips lcur (after MO_ERR_INDEX the previous lists stay readable)
-    int32_t* loff[2] = {nullptr, nullptr}; size_t loff_bytes[2] = {0, 0}; int32_t* lids[2] = {nullptr, nullptr}; size_t lids_bytes[2] = {0, 0};
-    int lcur = 0, list_rows = 0;
-    int32_t* kf_red = nullptr; size_t kf_red_bytes = 0;
-    // scratch
-    int32_t* st = nullptr;                            // [ST_NWORDS] status
-    int32_t* keep = nullptr; int32_t* kobs = nullptr; int32_t* rank = nullptr; int32_t* obase = nullptr;
-    size_t keep_bytes = 0, kobs_bytes = 0, rank_bytes = 0, obase_bytes = 0;
-    int32_t* part = nullptr; size_t part_bytes = 0;
-    int32_t* ent_id = nullptr; size_t ent_bytes = 0;  // id of the point of every observation entry (compacted map)
-    int32_t* hist = nullptr; int32_t* hbase = nullptr; size_t hist_bytes = 0, hbase_bytes = 0;
-    int32_t* first = nullptr; size_t first_bytes = 0;
-    // growth step
-    int32_t* midx = nullptr; int32_t* mdist = nullptr; uint8_t* mpass = nullptr; uint8_t* inl = nullptr; float* gpts = nullptr;
-    double* F = nullptr; int32_t* gnp = nullptr;
-    size_t midx_bytes = 0, mdist_bytes = 0, mpass_bytes = 0, inl_bytes = 0, gpts_bytes = 0, F_bytes = 0, gnp_bytes = 0;
-    int32_t* h_stat = nullptr;                        // pinned [ST_NWORDS]
-    // relocalization (mo_map_relocalize), grown with the map
-    int32_t* rl_tab = nullptr; size_t rl_tab_bytes = 0;                        // point_of [slot][row]
-    int32_t* rl_qf = nullptr; size_t rl_qf_bytes = 0;                          // [n_kf] query frame of every pair: the spare slot
-    int32_t* rl_midx = nullptr; int32_t* rl_mdist = nullptr; uint8_t* rl_mpass = nullptr;  // [n_kf][row] matcher outputs
-    size_t rl_midx_bytes = 0, rl_mdist_bytes = 0, rl_mpass_bytes = 0;
-    int32_t* rl_score = nullptr; size_t rl_score_bytes = 0;                    // [n_kf] |C_k|
-    int32_t* rl_cq = nullptr; int32_t* rl_cp = nullptr; uint8_t* rl_cinl = nullptr;  // [candidate][row] C_k (query, point), final inliers
-    size_t rl_cq_bytes = 0, rl_cp_bytes = 0, rl_cinl_bytes = 0;
-    int32_t* rl_qpt = nullptr; uint8_t* rl_qinl = nullptr; size_t rl_qpt_bytes = 0, rl_qinl_bytes = 0;  // [row] per query keypoint
-    RelocRes* rl_res = nullptr; RelocRes* h_rl = nullptr;                     // device / pinned
-};
-
-template <class T> static int reserve(mo_ctx* c, T*& p, size_t& have, size_t need) {
-    if (p && need <= have) return MO_OK;
-    need = std::max(need, have + have / 2);
-    return mo_reserve(c, p, have, need);
-}
-
-// grow a buffer keeping its first `keep` bytes (stream-ordered copy)
-template <class T> static int regrow(mo_ctx* c, T*& p, size_t old_bytes, size_t new_bytes, size_t keep) {
-    T* q = nullptr;
-    HIPCHK(c, hipMalloc((void**)&q, std::max(new_bytes, (size_t)16)));
-    if (p && keep) HIPCHK(c, hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, c->stream));
-    if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p)); }
-    p = q;
-    (void)old_bytes;
-    return MO_OK;
-}
-
 // ---- device-wide exclusive scan of int32 (three launches: per-tile scan, one-block scan of the tile sums, add) ------------------
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan of the block's values (blockDim.x = MAP_SCAN_BLOCK or 1024); returns the block total in *total
-__device__ __forceinline__ int block_excl_scan(int v, int* lds_waves, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int inc = wave_incl_scan(v);
-    if (lane == 63) lds_waves[wv] = inc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int s = threadIdx.x < nw ? lds_waves[threadIdx.x] : 0;
-        const int si = wave_incl_scan(s);
-        if (threadIdx.x < nw) lds_waves[16 + threadIdx.x] = si - s;
-        if (threadIdx.x == nw - 1) lds_waves[32] = si;
-    }
-    __syncthreads();
-    const int r = lds_waves[16 + wv] + inc - v;
-    *total = lds_waves[32];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(MAP_SCAN_BLOCK) void k_scan_tiles(const int32_t* __restrict__ in, int32_t* __restrict__ out, int32_t* __restrict__ part, int n) {
     __shared__ int lw[40];
     const size_t base = (size_t)blockIdx.x * MAP_SCAN_TILE + (size_t)threadIdx.x * MAP_SCAN_ITEMS;
@@ -400,7 +298,7 @@ static int pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep
 
 // kkps / kdesc / kcnt hold one slot more than kslots: the spare slot (index kslots) mo_map_relocalize stages its query in, so that
 // one counts array serves both sides of its keyframe matching
-static int kf_reserve(mo_map* m, int rows, int slots) {
+int kf_reserve(mo_map* m, int rows, int slots) {
     mo_ctx* c = m->c;
     int rc;
     if (rows > m->row) {  // a wider row: every keyframe is moved to the new stride
@@ -435,7 +333,7 @@ static int kf_reserve(mo_map* m, int rows, int slots) {
     return MO_OK;
 }
 
-static int upload_pos_slot(mo_map* m) {
+int upload_pos_slot(mo_map* m) {
     mo_ctx* c = m->c;
     int rc = reserve(c, m->d_pos_slot, m->pos_slot_bytes, std::max<size_t>(m->pos_slot.size(), 1) * 4);
     if (rc) return rc;
@@ -478,6 +376,7 @@ extern "C" void mo_map_destroy(mo_map* m) {
     for (void* b : rb) if (b) hipFree(b);
     if (m->h_stat) hipHostFree(m->h_stat);
     if (m->h_rl) hipHostFree(m->h_rl);
+    map_track_free(m);
     delete m;
 }
 

@@ -1,0 +1,527 @@
+// map_track.hip -- tracking a frame against the device map (mo_map_track in include/vslam_amd.h): ORB-SLAM2's search by projection and
+// its monocular pose-only PoseOptimization, on the map as it stands.  Read-only on the map; the frame is staged in the spare keyframe
+// slot (kf_reserve), like mo_map_relocalize's.
+//
+// Chain (one synchronisation, the copy-out; the retry and the early exits are flags in TrackRes that every later kernel reads first):
+//   k_trk_init      result block, per-keypoint keys and outputs
+//   k_trk_rep       one thread per point: local-map membership, representative descriptor ([point][32]) and its octave
+//   k_trk_grid      one block: stable counting sort of the frame keypoints into 64 x 48 cells
+//   per pass, per attempt (the second attempt runs only after a pass with too few matches):
+//     k_trk_search  one thread per local point: projection, window over the cells, 256-bit Hamming distances, best / second, the
+//                   accepted match claims its keypoint by a 64-bit atomicMin of (dist << 32) | point
+//     k_trk_compact one block: the winners in keypoint order (block scans), per-keypoint outputs, the retry / end decision
+//   k_trk_refine    one block of 256: 4 rounds of Gauss-Newton (Huber in rounds 0 - 2), f64 partial sums per thread, fixed-order wave
+//                   and workgroup reductions, one Cholesky solve per step
+// Every device result is the same on every run: integer atomics only (sums and minima commute), fixed-order f64 reductions.
+// -ffp-contract=off (Makefile): the projection rounds like tests/track_restatement.py's elementwise numpy.
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+#include "map_store.h"
+#include "pnp.h"
+
+#define TK_GX 64                        // ORB-SLAM2's FRAME_GRID_COLS x FRAME_GRID_ROWS
+#define TK_GY 48
+#define TK_CELLS (TK_GX * TK_GY)
+#define TK_GRID_BLOCK 1024
+#define TK_CELLS_PER_THREAD (TK_CELLS / TK_GRID_BLOCK)
+#define TK_MAX_PASS 4
+#define TK_REFINE_BLOCK 256
+#define TK_NOT_LOCAL INT_MIN            // octave slot of a point outside the local map
+#define TK_NONE 0xffffffffffffffffull   // keypoint key without a claim
+static_assert(TK_CELLS % TK_GRID_BLOCK == 0, "cells per thread");
+
+struct TrackPrm {
+    double K[9], pose0[12], radius[TK_MAX_PASS], sf, ratio, chi2;
+    int w, h, max_dist, min_matches;
+};
+
+struct TrackRes {
+    double pose[12];                      // projection pose of the next pass: pose0, then each refined pose
+    double pass_pose[TK_MAX_PASS][12];
+    double pass_radius[TK_MAX_PASS];
+    int32_t pass_cand[TK_MAX_PASS], pass_matches[TK_MAX_PASS], pass_inliers[TK_MAX_PASS];
+    int32_t n_local, n_run, n_done;       // points of the local map, passes searched, passes refined
+    int32_t ended, retry;                 // the call has ended (too few matches after the retry); the pass in flight is retried
+    int32_t cand, n_match;                // candidates of the attempt in flight (k_trk_search), matches of the last compaction
+};
+
+struct TrkMatch {                         // one match in keypoint order (32 B): the point's position, the keypoint
+    float X, Y, Z, x, y;
+    int32_t octave, q, p;
+};
+
+struct TrackBufs {
+    uint8_t* rep = nullptr; size_t rep_bytes = 0;                  // [point][32] representative descriptors
+    int32_t* oct = nullptr; size_t oct_bytes = 0;                  // [point] ref_octave (TK_NOT_LOCAL: not in the local map)
+    int32_t* cell = nullptr; size_t cell_bytes = 0;                // [TK_CELLS + 1] first sorted entry of every cell
+    int32_t* sorted = nullptr; size_t sorted_bytes = 0;            // [row] keypoint indices by cell, index order inside a cell
+    unsigned long long* key = nullptr; size_t key_bytes = 0;       // [row] (dist << 32) | point of the claim on each keypoint
+    TrkMatch* match = nullptr; size_t match_bytes = 0;             // [row]
+    uint8_t* minl = nullptr; size_t minl_bytes = 0;                // [row] inlier flag of every match
+    int32_t* qpt = nullptr; int32_t* qdist = nullptr; uint8_t* qinl = nullptr;
+    size_t qpt_bytes = 0, qdist_bytes = 0, qinl_bytes = 0;
+    TrackRes* res = nullptr; TrackRes* h_res = nullptr;            // device / pinned
+};
+
+void map_track_free(mo_map* m) {
+    TrackBufs* b = m->tk;
+    if (!b) return;
+    void* bufs[] = {b->rep, b->oct, b->cell, b->sorted, b->key, b->match, b->minl, b->qpt, b->qdist, b->qinl, b->res};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_res) hipHostFree(b->h_res);
+    delete b;
+    m->tk = nullptr;
+}
+
+// a pass's kernels run when the call has not ended and, for the second attempt, when the first asked for it
+__device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
+    return !res->ended && (attempt == 0 || res->retry);
+}
+
+__device__ __forceinline__ int trk_ham(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b) {
+    const uint4 a0 = *(const uint4*)a, a1 = *(const uint4*)(a + 16), b0 = *(const uint4*)b, b1 = *(const uint4*)(b + 16);
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
+           __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// grid column / row of a coordinate: monotone in it, so the cells of [u - r, u + r] hold every keypoint with |x - u| < r
+__device__ __forceinline__ int trk_cx(double x, int w) {
+    const double v = x * TK_GX / w;
+    return v >= 0.0 ? (v < TK_GX ? (int)v : TK_GX - 1) : 0;
+}
+__device__ __forceinline__ int trk_cy(double y, int h) {
+    const double v = y * TK_GY / h;
+    return v >= 0.0 ? (v < TK_GY ? (int)v : TK_GY - 1) : 0;
+}
+
+// scale_factor^o and the information 1 / scale_factor^(2 o), as repeated products from 1.0 (negative octaves as 0)
+__device__ __forceinline__ double trk_scale(double sf, int o) {
+    double s = 1.0;
+    for (int i = 0; i < o; i++) s *= sf;
+    return s;
+}
+__device__ __forceinline__ double trk_info(double sf, int o) {
+    const double sf2 = sf * sf;
+    double s = 1.0;
+    for (int i = 0; i < o; i++) s *= sf2;
+    return 1.0 / s;
+}
+
+__global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes* __restrict__ res, unsigned long long* __restrict__ key,
+                                                  int32_t* __restrict__ qpt, int32_t* __restrict__ qdist, uint8_t* __restrict__ qinl) {
+    for (int q = threadIdx.x; q < n; q += 256) { key[q] = TK_NONE; qpt[q] = -1; qdist[q] = -1; qinl[q] = 0; }
+    if (threadIdx.x == 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int i = 0; i < 12; i++) res->pose[i] = prm.pose0[i];
+        for (int k = 0; k < TK_MAX_PASS; k++) {
+            for (int i = 0; i < 12; i++) res->pass_pose[k][i] = nan;
+            res->pass_radius[k] = 0.0;
+            res->pass_cand[k] = 0; res->pass_matches[k] = 0; res->pass_inliers[k] = 0;
+        }
+        res->n_local = 0; res->n_run = 0; res->n_done = 0; res->ended = 0; res->retry = 0; res->cand = 0; res->n_match = 0;
+    }
+}
+
+// one thread per point: valid observations read like the cull reads them; local when one of them is at a position >= lo_pos.  The
+// representative is ComputeDistinctiveDescriptors' choice: the observation with the smallest median distance to all of them, ties to
+// the earlier.  Each median is found by bisection on the distance value (count of distances <= v), only below the best so far.
+__global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                                 int row, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc, int lo_pos,
+                                                 uint8_t* __restrict__ rep, int32_t* __restrict__ oct, TrackRes* __restrict__ res) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool local = false;
+    if (i < n_pts) {
+        const int o0 = src.off[i], o1 = src.off[i + 1];
+        // the (slot * row + keypoint) entry of observation o, -1 when it names nothing
+        auto entry = [&](int o, int* pos) -> long long {
+            int kf = src.okf[o];
+            if (kf < 0) kf += n_kf;
+            if (kf < 0 || kf >= n_kf) return -1;
+            const int s = pos_slot[kf];
+            int kp = src.okp[o];
+            const int nk = kcnt[s];
+            if (kp < 0) kp += nk;
+            if (kp < 0 || kp >= nk) return -1;
+            *pos = kf;
+            return (long long)s * row + kp;
+        };
+        int nv = 0, pos = 0;
+        long long best = -1;
+        for (int o = o0; o < o1; o++) {
+            const long long e = entry(o, &pos);
+            if (e < 0) continue;
+            nv++;
+            local |= pos >= lo_pos;
+            if (best < 0) best = e;
+        }
+        if (local && nv > 2) {   // (n <= 2: every median is the distance to itself, 0: the first observation)
+            const int r = (nv - 1) / 2;
+            int best_med = 257;
+            for (int o = o0; o < o1; o++) {
+                const long long ej = entry(o, &pos);
+                if (ej < 0) continue;
+                const uint8_t* dj = kdesc + ej * 32;
+                auto count_le = [&](int v) {
+                    int cnt = 0;
+                    for (int l = o0; l < o1; l++) {
+                        const long long el = entry(l, &pos);
+                        if (el >= 0) cnt += trk_ham(dj, kdesc + el * 32) <= v;
+                    }
+                    return cnt;
+                };
+                int hi = best_med - 1;
+                if (count_le(hi) <= r) continue;   // median >= the best so far: the earlier observation keeps it
+                int lo = 0;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (count_le(mid) > r) hi = mid; else lo = mid + 1;
+                }
+                best_med = lo;
+                best = ej;
+            }
+        }
+        if (local) {
+            const uint4* d = (const uint4*)(kdesc + best * 32);
+            uint4* o = (uint4*)(rep + (size_t)i * 32);
+            o[0] = d[0]; o[1] = d[1];
+            oct[i] = kkps[best].octave;
+        } else {
+            oct[i] = TK_NOT_LOCAL;
+        }
+    }
+    const unsigned long long b = __ballot(local);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&res->n_local, (int)__popcll(b));
+}
+
+// one block: histogram of the cells (LDS), exclusive scan, scatter by LDS cursors, then every cell's run sorted by keypoint index (the
+// cursors' order is arrival order; the sort makes the layout the stable counting sort's)
+__global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* __restrict__ fk, int n, int w, int h, int32_t* __restrict__ cell,
+                                                            int32_t* __restrict__ sorted) {
+    __shared__ int cur[TK_CELLS];
+    __shared__ int lw[40];
+    const int tid = threadIdx.x;
+    for (int c = tid; c < TK_CELLS; c += TK_GRID_BLOCK) cur[c] = 0;
+    __syncthreads();
+    for (int q = tid; q < n; q += TK_GRID_BLOCK) atomicAdd(cur + trk_cy(fk[q].y, h) * TK_GX + trk_cx(fk[q].x, w), 1);
+    __syncthreads();
+    int v[TK_CELLS_PER_THREAD], s = 0;
+    for (int j = 0; j < TK_CELLS_PER_THREAD; j++) { v[j] = cur[tid * TK_CELLS_PER_THREAD + j]; s += v[j]; }
+    int tot;
+    int base = block_excl_scan(s, lw, &tot);
+    for (int j = 0; j < TK_CELLS_PER_THREAD; j++) {
+        cur[tid * TK_CELLS_PER_THREAD + j] = base;
+        cell[tid * TK_CELLS_PER_THREAD + j] = base;
+        base += v[j];
+    }
+    if (tid == 0) cell[TK_CELLS] = tot;
+    __syncthreads();
+    for (int q = tid; q < n; q += TK_GRID_BLOCK) sorted[atomicAdd(cur + trk_cy(fk[q].y, h) * TK_GX + trk_cx(fk[q].x, w), 1)] = q;
+    __syncthreads();
+    for (int j = 0; j < TK_CELLS_PER_THREAD; j++) {
+        const int c = tid * TK_CELLS_PER_THREAD + j, a = cell[c], b = cur[c];
+        for (int x = a + 1; x < b; x++) {
+            const int q = sorted[x];
+            int y = x - 1;
+            while (y >= a && sorted[y] > q) { sorted[y + 1] = sorted[y]; y--; }
+            sorted[y + 1] = q;
+        }
+    }
+}
+
+// one thread per point: candidates of the pass (projection in the image), the best and second distance over the window, the claim
+__global__ __launch_bounds__(256) void k_trk_search(TrackPrm prm, int pass, int attempt, const float* __restrict__ xyz, int n_pts,
+                                                    const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
+                                                    const mo_keypoint* __restrict__ fk, const uint8_t* __restrict__ fdesc,
+                                                    const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                    unsigned long long* __restrict__ key, TrackRes* __restrict__ res) {
+    if (!trk_active(res, attempt)) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int ro = i < n_pts ? oct[i] : TK_NOT_LOCAL;
+    bool cand = false;
+    double uu = 0.0, vv = 0.0;
+    if (ro != TK_NOT_LOCAL) {
+        double R[9], t[3], P[12];
+        for (int j = 0; j < 3; j++) {
+            for (int l = 0; l < 3; l++) R[j * 3 + l] = res->pose[j * 4 + l];
+            t[j] = res->pose[j * 4 + 3];
+        }
+        pnp_projection(prm.K, R, t, P);
+        const double X = xyz[(size_t)i * 3], Y = xyz[(size_t)i * 3 + 1], Z = xyz[(size_t)i * 3 + 2];
+        const double u = P[0] * X + P[1] * Y + P[2] * Z + P[3];
+        const double v = P[4] * X + P[5] * Y + P[6] * Z + P[7];
+        const double z = P[8] * X + P[9] * Y + P[10] * Z + P[11];
+        if (z > 0.0) {
+            uu = u / z; vv = v / z;
+            cand = uu >= 0.0 && uu < prm.w && vv >= 0.0 && vv < prm.h;
+        }
+    }
+    const unsigned long long b = __ballot(cand);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&res->cand, (int)__popcll(b));
+    if (!cand) return;
+    const double r = (attempt ? 2.0 * prm.radius[pass] : prm.radius[pass]) * trk_scale(prm.sf, ro);
+    const int cx0 = trk_cx(uu - r, prm.w), cx1 = trk_cx(uu + r, prm.w), cy0 = trk_cy(vv - r, prm.h), cy1 = trk_cy(vv + r, prm.h);
+    const uint8_t* d = rep + (size_t)i * 32;
+    int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
+    for (int cy = cy0; cy <= cy1; cy++)
+        for (int cx = cx0; cx <= cx1; cx++) {
+            const int c = cy * TK_GX + cx, e1 = cell[c + 1];
+            for (int e = cell[c]; e < e1; e++) {
+                const int q = sorted[e];
+                const mo_keypoint kp = fk[q];
+                if (!(fabs((double)kp.x - uu) < r && fabs((double)kp.y - vv) < r)) continue;
+                const long long dl = (long long)kp.octave - ro;
+                if (dl < -1 || dl > 1) continue;
+                const int dist = trk_ham(d, fdesc + (size_t)q * 32);
+                if (dist < bd || (dist == bd && q < bq)) { sd = bd; bd = dist; bq = q; }
+                else if (dist < sd) sd = dist;
+            }
+        }
+    if (bd == INT_MAX || bd > prm.max_dist) return;
+    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
+    atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+}
+
+// one block: the claimed keypoints in keypoint order -> the match list and the per-keypoint outputs; keys reset for the next attempt;
+// the pass's counts and the retry / end decision
+__global__ __launch_bounds__(1024) void k_trk_compact(TrackPrm prm, int pass, int attempt, int n, const mo_keypoint* __restrict__ fk,
+                                                      const float* __restrict__ xyz, unsigned long long* __restrict__ key,
+                                                      TrkMatch* __restrict__ match, int32_t* __restrict__ qpt, int32_t* __restrict__ qdist,
+                                                      uint8_t* __restrict__ qinl, TrackRes* __restrict__ res) {
+    __shared__ int lw[40];
+    __shared__ int active;
+    if (threadIdx.x == 0) active = trk_active(res, attempt);
+    __syncthreads();
+    if (!active) return;
+    int added = 0;
+    for (int b = 0; b < n; b += 1024) {
+        const int q = b + threadIdx.x;
+        const unsigned long long k = q < n ? key[q] : TK_NONE;
+        const bool has = k != TK_NONE;
+        int tot;
+        const int r = block_excl_scan(has ? 1 : 0, lw, &tot);
+        if (q < n) {
+            const int p = has ? (int)(k & 0xffffffffu) : -1;
+            qpt[q] = p;
+            qdist[q] = has ? (int)(k >> 32) : -1;
+            qinl[q] = 0;
+            key[q] = TK_NONE;
+            if (has) {
+                const mo_keypoint kp = fk[q];
+                TrkMatch mt;
+                mt.X = xyz[(size_t)p * 3]; mt.Y = xyz[(size_t)p * 3 + 1]; mt.Z = xyz[(size_t)p * 3 + 2];
+                mt.x = kp.x; mt.y = kp.y; mt.octave = kp.octave; mt.q = q; mt.p = p;
+                match[added + r] = mt;
+            }
+        }
+        added += tot;
+    }
+    if (threadIdx.x == 0) {
+        res->pass_cand[pass] = res->cand;
+        res->cand = 0;
+        res->pass_matches[pass] = added;
+        res->pass_radius[pass] = attempt ? 2.0 * prm.radius[pass] : prm.radius[pass];
+        res->n_match = added;
+        res->n_run = pass + 1;
+        const int few = added < prm.min_matches;
+        if (few && attempt) res->ended = 1;
+        res->retry = few && !attempt;
+    }
+}
+
+// a fixed-order wave sum every lane receives (lane 0's tree, broadcast)
+__device__ __forceinline__ double trk_wave_sum(double v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return __shfl(v, 0, 64);
+}
+
+// inlier test of one match under (R, t): depth > 0 and information * squared pixel error <= chi2
+__device__ __forceinline__ bool trk_inlier(const TrackPrm& prm, const double* R, const double* t, const TrkMatch& mt) {
+    const double X = mt.X, Y = mt.Y, Z = mt.Z;
+    const double xc = R[0] * X + R[1] * Y + R[2] * Z + t[0];
+    const double yc = R[3] * X + R[4] * Y + R[5] * Z + t[1];
+    const double zc = R[6] * X + R[7] * Y + R[8] * Z + t[2];
+    const double* K = prm.K;
+    const double p0 = K[0] * xc + K[1] * yc + K[2] * zc, p1 = K[3] * xc + K[4] * yc + K[5] * zc, p2 = K[6] * xc + K[7] * yc + K[8] * zc;
+    const double du = p0 / p2 - (double)mt.x, dv = p1 / p2 - (double)mt.y;
+    return zc > 0.0 && trk_info(prm.sf, mt.octave) * (du * du + dv * dv) <= prm.chi2;
+}
+
+// one block of 256: Optimizer::PoseOptimization (monocular, pose only) with Gauss-Newton steps; the pass's outputs
+__global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, int pass, const TrkMatch* __restrict__ match,
+                                                                uint8_t* __restrict__ minl, uint8_t* __restrict__ qinl, TrackRes* __restrict__ res) {
+    constexpr int NW = TK_REFINE_BLOCK / 64;
+    __shared__ double red[NW][27];
+    __shared__ double sRt[12];
+    __shared__ int flag, cnt[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) flag = !res->ended && !res->retry;
+    __syncthreads();
+    if (!flag) return;
+    const int m = res->n_match;
+    double R[9], t[3];
+    for (int j = 0; j < 3; j++) {
+        for (int l = 0; l < 3; l++) R[j * 3 + l] = res->pose[j * 4 + l];
+        t[j] = res->pose[j * 4 + 3];
+    }
+    for (int j = tid; j < m; j += TK_REFINE_BLOCK) minl[j] = 1;
+    int n_inl = m;
+    for (int round = 0; round < 4; round++) {
+        const double huber2 = round < 3 ? prm.chi2 : 0.0;
+        for (int it = 0; it < 10; it++) {
+            double a[27];
+            for (int i = 0; i < 27; i++) a[i] = 0.0;
+            for (int j = tid; j < m; j += TK_REFINE_BLOCK) {
+                if (!minl[j]) continue;
+                const TrkMatch mt = match[j];
+                pnp_gn_accumulate_w(prm.K, R, t, mt.X, mt.Y, mt.Z, mt.x, mt.y, trk_info(prm.sf, mt.octave), huber2, a, a + 21);
+            }
+            for (int i = 0; i < 27; i++) a[i] = trk_wave_sum(a[i]);
+            if (lane == 0)
+                for (int i = 0; i < 27; i++) red[wv][i] = a[i];
+            __syncthreads();
+            if (tid == 0) {
+                double s[27];
+                for (int i = 0; i < 27; i++) {
+                    s[i] = red[0][i];
+                    for (int w = 1; w < NW; w++) s[i] += red[w][i];
+                }
+                double step = 0.0;
+                const bool ok = pnp_gn_update(s, s + 21, R, t, &step);
+                for (int j = 0; j < 9; j++) sRt[j] = R[j];
+                for (int j = 0; j < 3; j++) sRt[9 + j] = t[j];
+                flag = !ok || step < 1e-12;
+            }
+            __syncthreads();
+            for (int j = 0; j < 9; j++) R[j] = sRt[j];
+            for (int j = 0; j < 3; j++) t[j] = sRt[9 + j];
+            const int stop = flag;
+            __syncthreads();
+            if (stop) break;
+        }
+        int n = 0;
+        for (int j = tid; j < m; j += TK_REFINE_BLOCK) {
+            const bool in = trk_inlier(prm, R, t, match[j]);
+            minl[j] = in;
+            n += in;
+        }
+        for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+        if (lane == 0) cnt[wv] = n;
+        __syncthreads();
+        n_inl = 0;
+        for (int w = 0; w < NW; w++) n_inl += cnt[w];
+        __syncthreads();
+        if (n_inl < 10) break;
+    }
+    for (int j = tid; j < m; j += TK_REFINE_BLOCK) qinl[match[j].q] = minl[j];
+    if (tid == 0) {
+        for (int j = 0; j < 3; j++) {
+            for (int l = 0; l < 3; l++) res->pose[j * 4 + l] = res->pass_pose[pass][j * 4 + l] = R[j * 3 + l];
+            res->pose[j * 4 + 3] = res->pass_pose[pass][j * 4 + 3] = t[j];
+        }
+        res->pass_inliers[pass] = n_inl;
+        res->n_done = pass + 1;
+    }
+}
+
+extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
+                            mo_map_track_out* out) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (!f || !K || !pose0 || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (prm->n_pass < 1 || prm->n_pass > TK_MAX_PASS) return mo_fail(c, MO_ERR_ARG, "n_pass must be in 1 .. 4");
+    if (prm->w <= 0 || prm->h <= 0) return mo_fail(c, MO_ERR_ARG, "w and h must be > 0");
+    if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
+    if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
+    if (!(prm->chi2 >= 0.0) || !std::isfinite(prm->ratio)) return mo_fail(c, MO_ERR_ARG, "chi2 must be >= 0 and ratio finite");
+    for (int k = 0; k < prm->n_pass; k++)
+        if (!(prm->radius[k] >= 0.0) || !std::isfinite(prm->radius[k])) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(pose0[i])) return mo_fail(c, MO_ERR_ARG, "pose0 must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    HostClock clk(c);
+    for (int i = 0; i < 12; i++) out->pose[i] = pose0[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) {
+        for (int i = 0; i < 12; i++) out->pass_pose[k][i] = NAN;
+        out->pass_radius[k] = 0.0;
+        out->pass_cand[k] = 0; out->pass_matches[k] = 0; out->pass_inliers[k] = 0;
+    }
+    out->n_pass_run = 0; out->n_local = 0; out->ok = 0; out->from_token = 0;
+    int rs, n, rc;
+    if ((rc = mo_frame_lookup(c, f, "frame", &rs, &n))) return rc;
+    out->from_token = rs >= 0;
+    if (out->point) for (int i = 0; i < n; i++) out->point[i] = -1;
+    if (out->dist) for (int i = 0; i < n; i++) out->dist[i] = -1;
+    if (out->inlier) std::memset(out->inlier, 0, (size_t)n);
+    const int n_kf = (int)m->pos_slot.size();
+    if (n == 0 || n_kf == 0 || m->n_pts == 0) return MO_OK;   // nothing to search: not tracked, not an error
+    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    if ((rc = kf_reserve(m, n, m->n_slots))) return rc;   // (a wider row restrides the store; the map itself is unchanged)
+    const int spare = m->kslots, row = m->row;
+    if (!m->tk) m->tk = new TrackBufs();
+    TrackBufs& b = *m->tk;
+    const size_t np = (size_t)m->n_pts;
+    if ((rc = reserve(c, b.rep, b.rep_bytes, np * 32)) || (rc = reserve(c, b.oct, b.oct_bytes, np * 4)) ||
+        (rc = reserve(c, b.cell, b.cell_bytes, (TK_CELLS + 1) * 4)) || (rc = reserve(c, b.sorted, b.sorted_bytes, (size_t)row * 4)) ||
+        (rc = reserve(c, b.key, b.key_bytes, (size_t)row * 8)) || (rc = reserve(c, b.match, b.match_bytes, (size_t)row * sizeof(TrkMatch))) ||
+        (rc = reserve(c, b.minl, b.minl_bytes, (size_t)row)) || (rc = reserve(c, b.qpt, b.qpt_bytes, (size_t)row * 4)) ||
+        (rc = reserve(c, b.qdist, b.qdist_bytes, (size_t)row * 4)) || (rc = reserve(c, b.qinl, b.qinl_bytes, (size_t)row)))
+        return rc;
+    if (!b.res) {
+        HIPCHK(c, hipMalloc((void**)&b.res, sizeof(TrackRes)));
+        HIPCHK(c, hipHostMalloc((void**)&b.h_res, sizeof(TrackRes), hipHostMallocDefault));
+    }
+    if ((rc = upload_pos_slot(m))) return rc;
+    mo_stage_begin(c);
+    mo_keypoint* fk = m->kkps + (size_t)spare * row;
+    uint8_t* fdesc = m->kdesc + (size_t)spare * row * 32;
+    if ((rc = mo_frame_copy_rows(c, f, rs, n, fk, fdesc))) return rc;
+    TrackPrm p;
+    for (int i = 0; i < 9; i++) p.K[i] = K[i];
+    for (int i = 0; i < 12; i++) p.pose0[i] = pose0[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) p.radius[k] = k < prm->n_pass ? prm->radius[k] : 0.0;
+    p.sf = prm->scale_factor; p.ratio = prm->ratio; p.chi2 = prm->chi2;
+    p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist; p.min_matches = prm->min_matches;
+    const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
+    const MapPts& src = m->P[m->cur];
+    const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
+    hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
+    hipLaunchKernelGGL(k_trk_rep, dim3(pblocks), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf, m->kcnt, row, m->kkps, m->kdesc,
+                       lo_pos, b.rep, b.oct, b.res);
+    hipLaunchKernelGGL(k_trk_grid, dim3(1), dim3(TK_GRID_BLOCK), 0, c->stream, fk, n, prm->w, prm->h, b.cell, b.sorted);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "track_prep");
+    for (int k = 0; k < prm->n_pass; k++) {
+        for (int a = 0; a < 2; a++) {
+            hipLaunchKernelGGL(k_trk_search, dim3(pblocks), dim3(256), 0, c->stream, p, k, a, src.xyz, (int)m->n_pts, b.rep, b.oct, fk, fdesc, b.cell,
+                               b.sorted, b.key, b.res);
+            hipLaunchKernelGGL(k_trk_compact, dim3(1), dim3(1024), 0, c->stream, p, k, a, n, fk, src.xyz, b.key, b.match, b.qpt, b.qdist, b.qinl,
+                               b.res);
+        }
+        HIPCHK(c, hipGetLastError());
+        mo_stage_mark(c, "track_search");
+        hipLaunchKernelGGL(k_trk_refine, dim3(1), dim3(TK_REFINE_BLOCK), 0, c->stream, p, k, b.match, b.minl, b.qinl, b.res);
+        HIPCHK(c, hipGetLastError());
+        mo_stage_mark(c, "track_refine");
+    }
+    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(TrackRes), hipMemcpyDeviceToHost, c->stream));
+    if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out->dist) HIPCHK(c, hipMemcpyAsync(out->dist, b.qdist, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    clk.enqueued();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    clk.waited();
+    const TrackRes& r = *b.h_res;
+    for (int i = 0; i < 12; i++) out->pose[i] = r.pose[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) {
+        for (int i = 0; i < 12; i++) out->pass_pose[k][i] = r.pass_pose[k][i];
+        out->pass_radius[k] = r.pass_radius[k];
+        out->pass_cand[k] = r.pass_cand[k]; out->pass_matches[k] = r.pass_matches[k]; out->pass_inliers[k] = r.pass_inliers[k];
+    }
+    out->n_pass_run = r.n_run;
+    out->n_local = r.n_local;
+    out->ok = r.n_done == prm->n_pass && r.pass_inliers[prm->n_pass - 1] >= prm->min_inliers;
+    return MO_OK;
+}

@@ -285,8 +285,10 @@ PNP_HD bool pnp_reproj2(const double* P, double X, double Y, double Z, double x,
 // ---- Gauss-Newton on SE(3) ------------------------------------------------------------------------------------------------------
 // Left perturbation X_cam' = exp(w) X_cam + rho, delta = (rho, w): R' = exp(w) R, t' = exp(w) t + rho.  H is the upper triangle of
 // J^T J (row-major, 21 entries), g = J^T r with r = projection - observation.
-PNP_HD void pnp_gn_accumulate(const double* K, const double* R, const double* t, double X, double Y, double Z, double x, double y,
-                              double* H, double* g) {
+// Weighted form (tracking's pose refinement): each term times info * w, w = the Huber weight sqrt(huber2 / e2) when
+// e2 = info * |r|^2 exceeds huber2 > 0, else 1.  info = 1, huber2 = 0 is the unweighted sum (a product by 1.0 is exact).
+PNP_HD void pnp_gn_accumulate_w(const double* K, const double* R, const double* t, double X, double Y, double Z, double x, double y,
+                                double info, double huber2, double* H, double* g) {
     const double xc = R[0] * X + R[1] * Y + R[2] * Z + t[0];
     const double yc = R[3] * X + R[4] * Y + R[5] * Z + t[1];
     const double zc = R[6] * X + R[7] * Y + R[8] * Z + t[2];
@@ -304,11 +306,18 @@ PNP_HD void pnp_gn_accumulate(const double* K, const double* R, const double* t,
     // -[c]x = [[0, c2, -c1], [-c2, 0, c0], [c1, -c0, 0]]; J_w = d . (-[c]x)
     Ju[3] = -du[1] * c[2] + du[2] * c[1]; Ju[4] = du[0] * c[2] - du[2] * c[0]; Ju[5] = -du[0] * c[1] + du[1] * c[0];
     Jv[3] = -dv[1] * c[2] + dv[2] * c[1]; Jv[4] = dv[0] * c[2] - dv[2] * c[0]; Jv[5] = -dv[0] * c[1] + dv[1] * c[0];
+    const double e2 = info * (ru * ru + rv * rv);
+    const double wt = huber2 > 0.0 && e2 > huber2 ? info * (sqrt(huber2) / sqrt(e2)) : info;
     int o = 0;
     for (int i = 0; i < 6; i++) {
-        for (int j = i; j < 6; j++) H[o++] += Ju[i] * Ju[j] + Jv[i] * Jv[j];
-        g[i] += Ju[i] * ru + Jv[i] * rv;
+        for (int j = i; j < 6; j++) H[o++] += wt * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+        g[i] += wt * (Ju[i] * ru + Jv[i] * rv);
     }
+}
+
+PNP_HD void pnp_gn_accumulate(const double* K, const double* R, const double* t, double X, double Y, double Z, double x, double y,
+                              double* H, double* g) {
+    pnp_gn_accumulate_w(K, R, t, X, Y, Z, x, y, 1.0, 0.0, H, g);
 }
 
 PNP_HD void pnp_exp_so3(const double* w, double* E) {

@@ -117,6 +117,8 @@ def main(argv=None):
     ap.add_argument("--keyframe-every", type=int, default=20, help="with --map: a keyframe every N frames (tracker.py:290)")
     ap.add_argument("--relocalize", action="store_true", help="with --map: when the tracking step fails, relocalize the frame against the "
                     "device map (LocalMapper.relocalize) and go on tracking from it")
+    ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
+                    "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
@@ -136,9 +138,12 @@ def main(argv=None):
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
     if args.relocalize and not args.map:
         ap.error("--relocalize needs --map")
+    if args.track_map and not args.map:
+        ap.error("--track-map needs --map")
     mapper, first, ref_pose = None, None, np.eye(4)
+    recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     if args.map:
-        from vslam_amd.mapper import LocalMapper
+        from vslam_amd.mapper import LocalMapper, predict_pose
         mapper = LocalMapper(K, args.map)
 
     def track_pose(R, t, frame, kps, desc, idx):
@@ -148,8 +153,26 @@ def main(argv=None):
         T[:3, :3] = R
         T[:3, 3] = np.asarray(t).reshape(3)
         ref_pose = ref_pose @ T
+        recent[:] = recent[-1:] + [ref_pose]
         if mapper is not None and idx % args.keyframe_every == 0:
             mapper.add_keyframe(frame, kps, desc, ref_pose)
+
+    def track_map(frame, kps, desc, idx):
+        """the frame against the device map from the predicted pose (ORB-SLAM2's TrackWithMotionModel + TrackLocalMap); on success its
+        pose becomes the reference pose"""
+        nonlocal ref_pose
+        pred = predict_pose(recent[-2], recent[-1]) if len(recent) >= 2 else ref_pose
+        ok, T, info = mapper.track_local_map(kps, desc, pred)
+        if idx % 5 == 0:
+            print("frame %d: track map %s, %d matches, %d inliers, t = %s" % (idx, "ok" if ok else "failed", info["pass_matches"][-1] if
+                  info["n_pass_run"] else 0, info["pass_inliers"][-1] if info["n_pass_run"] else 0, np.round(T[:3, 3], 3)))
+        if ok:
+            ref_pose = T
+            recent[:] = recent[-1:] + [T]
+            poses.append((T[:3, :3], T[:3, 3:4]))
+            if idx % args.keyframe_every == 0:
+                mapper.add_keyframe(frame, kps, desc, T)
+        return ok
 
     def relocalize(frame, kps, desc, idx):
         """the frame against the map (ORB-SLAM2's Tracking::Relocalization); on success tracking goes on from its pose"""
@@ -159,6 +182,7 @@ def main(argv=None):
                                                                                   len(info["candidates"]), info["n_inliers"]))
         if ok:
             ref_pose = T
+            recent[:] = recent[-1:] + [T]
             poses.append((T[:3, :3], T[:3, 3:4]))
     for idx, frame in enumerate(source):
         if n_seen >= limit:
@@ -189,6 +213,11 @@ def main(argv=None):
                         mapper.add_keyframe(first[0], first[1], first[2], ref_pose)
                         mapper.add_keyframe(frame, kps, desc, T)
                         mapper.update_map_points([p for p in pts if isinstance(p, dict)])
+                        if args.track_map:   # tracking goes on in the map's frame: from the second keyframe's pose
+                            ref_pose = T
+                            recent[:] = [np.eye(4), T]
+        elif args.track_map and track_map(frame, kps, desc, idx):
+            pass
         elif not args.python_filters:
             ok, T, inl = geom.track_from_last_frame(last[0], last[1], kps, desc, K, frame.shape, ratio_threshold=mt["ratio_threshold"],
                                                     threshold_percent=0.02)   # tracker.py:219

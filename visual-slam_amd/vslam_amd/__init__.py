@@ -91,6 +91,18 @@ class MapRelocOut(C.Structure):
                 ("n_inliers", C.c_int32), ("from_token", C.c_int32)]
 
 
+class MapTrackParams(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("window", C.c_int32), ("n_pass", C.c_int32), ("radius", C.c_double * 4),
+                ("scale_factor", C.c_double), ("ratio", C.c_double), ("chi2", C.c_double), ("max_dist", C.c_int32), ("min_matches", C.c_int32),
+                ("min_inliers", C.c_int32)]
+
+
+class MapTrackOut(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("dist", C.c_void_p), ("inlier", C.c_void_p), ("pose", C.c_double * 12), ("pass_pose", (C.c_double * 12) * 4),
+                ("pass_radius", C.c_double * 4), ("pass_cand", C.c_int32 * 4), ("pass_matches", C.c_int32 * 4), ("pass_inliers", C.c_int32 * 4),
+                ("n_pass_run", C.c_int32), ("n_local", C.c_int32), ("ok", C.c_int32), ("from_token", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -169,6 +181,7 @@ SIGNATURES = {
     "mo_map_download": (_i, [_vp, _i, _vp, C.c_size_t]),
     "mo_map_write_ply": (_i, [_vp, C.c_char_p, _i, _vp]),
     "mo_map_relocalize": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_track": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
 }
 

@@ -23,6 +23,13 @@ _N_HYP = 1024
 _SEED = 4096
 
 
+def predict_pose(prev, last):
+    """constant-velocity prediction of the next pose from the two before it (4x4, X_cam = R X + t): the motion prev -> last applied
+    once more, (last @ inv(prev)) @ last"""
+    prev, last = np.asarray(prev, np.float64), np.asarray(last, np.float64)
+    return (last @ np.linalg.inv(prev)) @ last
+
+
 class _Keyframe(dict):
     """a keyframe dict whose 'map_points' is read from the mapper's per-keyframe lists when asked for"""
     __slots__ = ("_mapper", "_extra")
@@ -261,20 +268,8 @@ class LocalMapper:
         Returns (ok, pose, info): pose 4x4 (X_cam = R X + t, the convention add_keyframe takes; None without a winner); info holds
         kf_pos / kf_id of the winner, the candidates [(position, score, inliers)], and per query keypoint `point` (map point index,
         -1: none) and `inlier` of the winner."""
-        from orbslam2.types import keypoints_to_array
         seed = self.seed if seed is None else int(seed)
-        token = V.resident_token(self.ctx, descriptors) if descriptors is not None else 0
-        kps_arr = V._resident_kps(descriptors) if token else None
-        if kps_arr is None or len(kps_arr) != len(keypoints):
-            token = 0
-            if isinstance(keypoints, np.ndarray) and keypoints.dtype == V.KP_DTYPE:
-                kps_arr = keypoints
-            else:
-                kps_arr = keypoints_to_array(keypoints) if len(keypoints) else np.zeros(0, V.KP_DTYPE)
-        kps_arr = np.ascontiguousarray(kps_arr, V.KP_DTYPE).reshape(-1)
-        desc = np.ascontiguousarray(descriptors if descriptors is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
-        n = len(kps_arr) if token else min(len(kps_arr), len(desc))
-        ref = V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n)
+        ref, n, _keep = self._frame_ref(keypoints, descriptors)
         K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
         nc = int(max_candidates)
         point = np.full(max(n, 1), -1, np.int32)
@@ -296,6 +291,64 @@ class LocalMapper:
                 "n_corr": int(out.n_corr), "n_inliers": int(out.n_inliers), "point": point[:n], "inlier": inlier[:n].astype(bool),
                 "from_token": bool(out.from_token)}
         return bool(out.ok), pose, info
+
+    def _frame_ref(self, keypoints, descriptors):
+        """(FrameRef, n, arrays it points into) of a query frame: by token when the arrays are a resident detect_and_compute result,
+        else the host arrays"""
+        from orbslam2.types import keypoints_to_array
+        token = V.resident_token(self.ctx, descriptors) if descriptors is not None else 0
+        kps_arr = V._resident_kps(descriptors) if token else None
+        if kps_arr is None or len(kps_arr) != len(keypoints):
+            token = 0
+            if isinstance(keypoints, np.ndarray) and keypoints.dtype == V.KP_DTYPE:
+                kps_arr = keypoints
+            else:
+                kps_arr = keypoints_to_array(keypoints) if len(keypoints) else np.zeros(0, V.KP_DTYPE)
+        kps_arr = np.ascontiguousarray(kps_arr, V.KP_DTYPE).reshape(-1)
+        desc = np.ascontiguousarray(descriptors if descriptors is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
+        n = len(kps_arr) if token else min(len(kps_arr), len(desc))
+        return V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n), n, (kps_arr, desc)
+
+    # ---- tracking against the map -------------------------------------------------------------------------------------------------
+    def track_local_map(self, keypoints, descriptors, pose, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8,
+                        chi2=5.991, min_matches=20, min_inliers=30, image_size=None):
+        """The pose of a tracked frame in the map's frame and scale, from a predicted pose (ORB-SLAM2's TrackLocalMap: search by projection
+        of the local map, then pose-only optimisation; mo_map_track in include/vslam_amd.h states the rules).  The map is not changed.
+        pose: the predicted 4x4 (X_cam = R X + t; predict_pose gives the constant-velocity one).  window: keyframe positions of the
+        local map, counted from the last (0: all).  radii: one search half-width per pass (1 to 4 passes), at octave 0.  image_size:
+        (w, h) a projection must land in, by default the last keyframe's image.  The frame is given like relocalize's.
+        Returns (ok, pose, info): pose 4x4 of the last pass that finished (the given pose when none did); info holds per keypoint
+        `point` (map point index, -1: none), `dist` (Hamming distance, -1: none) and `inlier` of the last pass searched, per pass
+        `pass_pose`, `pass_radius`, `pass_cand`, `pass_matches`, `pass_inliers` (lists over the passes that ran), `n_local` and
+        `from_token`."""
+        radii = [float(r) for r in radii]
+        if not 1 <= len(radii) <= 4:
+            raise ValueError("radii: one to four passes")
+        if image_size is None:
+            if self.keyframes:
+                image_size = self.keyframes[-1]["image"].shape[1::-1]
+            else:
+                Km = np.asarray(self.camera_matrix, np.float64)
+                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        ref, n, _keep = self._frame_ref(keypoints, descriptors)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        pose0 = np.ascontiguousarray(np.asarray(pose, np.float64)[:3, :4]).reshape(12)
+        point = np.full(max(n, 1), -1, np.int32)
+        dist = np.full(max(n, 1), -1, np.int32)
+        inlier = np.zeros(max(n, 1), np.uint8)
+        prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
+                               float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
+        out = V.MapTrackOut(point.ctypes.data, dist.ctypes.data, inlier.ctypes.data)
+        self._check(self.lib.mo_map_track(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(out)))
+        T = np.eye(4)
+        T[:3, :] = np.array(out.pose).reshape(3, 4)
+        nr = int(out.n_pass_run)
+        info = {"point": point[:n], "dist": dist[:n], "inlier": inlier[:n].astype(bool),
+                "pass_pose": [np.vstack([np.array(out.pass_pose[k]).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(nr)],
+                "pass_radius": [float(out.pass_radius[k]) for k in range(nr)], "pass_cand": [int(out.pass_cand[k]) for k in range(nr)],
+                "pass_matches": [int(out.pass_matches[k]) for k in range(nr)], "pass_inliers": [int(out.pass_inliers[k]) for k in range(nr)],
+                "n_pass_run": nr, "n_local": int(out.n_local), "from_token": bool(out.from_token)}
+        return bool(out.ok), T, info
 
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
     def _sync_size(self):
