@@ -567,6 +567,9 @@ int mo_set_host_timing(mo_ctx*, int on);
    the route of calls on one or two frames) instead of the batched path's kernels: MO_ERR_UNSUPPORTED for a geometry it does not cover */
 int mo_dbg_pyramid_level(mo_ctx*, const mo_orb_params*, const uint8_t* gray, int w, int h, int level, int blurred,
                          uint8_t* out /* lw*lh */, int* lw, int* lh);
+/* the blurred level `level` of frame `frame` as the last extraction on this context left it (no launch); resize_blur (may be NULL):
+   1 when the plan lets the batched path's resize launches write the blurred levels (k_resize2's blurring form) */
+int mo_dbg_blur_level(mo_ctx*, int frame, int level, uint8_t* out /* lw*lh */, int* lw, int* lh, int* resize_blur);
 int mo_dbg_fast_level(mo_ctx*, const mo_orb_params*, const uint8_t* gray, int w, int h, int level,
                       int32_t* xys /* [cap][3] */, int cap, int* n);
 int mo_dbg_min_eigen(mo_ctx*, const uint8_t* gray, int w, int h, float* eig /* [h*w] */);

@@ -67,7 +67,7 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
     if (host_call) mo_stage_mark(c, "h2d");  // (the host call opened its event set before the upload)
     else mo_stage_begin(c);
     // margins of the levels nothing in this pipeline reads (see orb_launch_blur / orb_launch_pyramid)
-    const int blur_margin = (c->plan.edge_threshold - 19) & ~3, pyr_margin = std::max(blur_margin - 4, 0);
+    const int blur_margin = mo_blur_margin(c->plan.edge_threshold), pyr_margin = mo_pyr_margin(c->plan.edge_threshold);
     // (one frame of a host call: the finest level's FAST + selection on a second stream beside the pyramid and the other levels was
     //  measured in round 4 - no gain, level 1's chain is as long as level 0's: profiles/r04_ab_single_split.txt)
     if (batch <= MO_FS_MAX_BATCH && c->fs_ok) {
@@ -77,12 +77,16 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
         mo_stage_mark(c, "pyramid");
         if (d_desc) mo_stage_mark(c, "blur");  // (inside the same launch: the stage keeps its name, its time is in "pyramid")
     } else {
-        if ((rc = orb_launch_pyramid(c, d_gray, batch, c->plan.nlevels, pyr_margin))) return rc;
+        // with descriptors, the resize launch of level L also writes the blurred level L-1 where the plan allows it (k_resize2's
+        // blurring form); the blur stage is then the last level alone, and the blurred levels' time shows under "pyramid"
+        bool blurred = false;
+        if ((rc = orb_launch_pyramid(c, d_gray, batch, c->plan.nlevels, pyr_margin, d_desc ? blur_margin : -1, &blurred))) return rc;
         mo_stage_mark(c, "pyramid");
         // the Gaussian blur only depends on the pyramid: in line, right behind it (an aux-stream fork beside FAST + selection gained <= 1 %
         // in the BATCHED mode in rounds 1 - 2 and was retired there: profiles/r02_ab_serial_blur.txt)
         if (d_desc) {
-            if ((rc = orb_launch_blur(c, d_gray, batch, c->plan.nlevels, blur_margin))) return rc;
+            const int nl = c->plan.nlevels;
+            if ((rc = orb_launch_blur(c, d_gray, batch, nl, blur_margin, blurred ? nl - 1 : 0))) return rc;
             mo_stage_mark(c, "blur");
         }
     }
@@ -854,6 +858,21 @@ extern "C" int mo_dbg_pyramid_level(mo_ctx* c, const mo_orb_params* p, const uin
         const uint8_t* src = level == 0 ? d_gray : c->d_pyr + v.off;
         HIPCHK(c, hipMemcpy2DAsync(out, v.w, src, v.pitch, v.w, v.h, hipMemcpyDeviceToHost, c->stream));
     }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MO_OK;
+}
+
+extern "C" int mo_dbg_blur_level(mo_ctx* c, int frame, int level, uint8_t* out, int* lw, int* lh, int* resize_blur) {
+    if (!c) return MO_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->plan_valid) return mo_fail(c, MO_ERR_ARG, "no extraction has run on this context");
+    if (level < 0 || level >= c->plan.nlevels) return mo_fail(c, MO_ERR_ARG, "level out of range");
+    if (frame < 0 || frame >= c->batch_alloc) return mo_fail(c, MO_ERR_ARG, "frame out of range");
+    const LevelInfo& v = c->plan.lv[level];
+    *lw = v.w; *lh = v.h;
+    if (resize_blur) *resize_blur = c->rb_ok ? 1 : 0;
+    HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->d_blur + (size_t)frame * c->plan.blur_stride + v.boff, v.bpitch, v.w, v.h,
+                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MO_OK;
 }

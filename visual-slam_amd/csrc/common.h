@@ -96,6 +96,10 @@ struct mo_ctx {
     mo_orb_params plan_params{};
     Plan plan{};
     ResizeTab rtab[MO_MAX_LEVELS];
+    // the batched extraction's resize launches can write the blurred levels too (orb_plan_resize_blur held for every level at
+    // the pipeline's margins rb_pyr_margin / rb_margin)
+    bool rb_ok = false;
+    int rb_margin = -1, rb_pyr_margin = -1;
     int batch_alloc = 0;  // frames the work buffers below are sized for
 
     // work buffers (device)
@@ -243,14 +247,22 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch);
 // kernel launchers (orb_kernels.hip)
 int orb_launch_gray(mo_ctx* c, const uint8_t* d_bgr, int w, int h, int batch, uint8_t* d_gray);
 int orb_launch_ingest(mo_ctx* c, const uint8_t* src_mapped, int w, int h, int ch, uint8_t* d_gray, int* flags_clear);
-int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin);
+// margins of the levels nothing in the batched pipeline reads (see orb_launch_blur / orb_launch_pyramid)
+inline int mo_blur_margin(int edge_threshold) { return (edge_threshold - 19) & ~3; }
+inline int mo_pyr_margin(int edge_threshold) { return std::max(mo_blur_margin(edge_threshold) - 4, 0); }
+// blur_margin >= 0: the resize launches may also write the blurred levels 0 .. nlevels-2 (*blurred says whether they did)
+int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin = -1,
+                       bool* blurred = nullptr);
+// plan time (ctx.hip): whether that blurring resize of level L covers level L-1's blur region at these margins
+bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp, const std::vector<uint32_t>& yp, int margin,
+                          int blur_margin);
 // front_single.hip: pyramid + blur of a few frames in ONE launch (single-frame calls); fs_build runs with the plan and leaves
 // c->fs_ok false for geometries it does not cover, which keep orb_launch_pyramid + orb_launch_blur
 #define MO_FS_MAX_BATCH 2
 int fs_build(mo_ctx* c);
 int orb_launch_front_single(mo_ctx* c, const uint8_t* d_gray, int batch, int want_blur);
 void mo_linear_coeffs(int srcsize, int dstsize, std::vector<int>& ofs, std::vector<int>& c1);
-int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin);
+int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int first_level = 0);
 int orb_launch_fast(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo = 0, int level_hi = MO_MAX_LEVELS);
 int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo = 0, int level_hi = MO_MAX_LEVELS);
 int orb_launch_describe(mo_ctx* c, const uint8_t* d_gray, int batch, mo_keypoint* d_kps, uint8_t* d_desc, int cap,

@@ -322,6 +322,9 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
     c->scratch_stride = (size_t)scr_off;
 
     // resize tables
+    c->rb_margin = mo_blur_margin(P.edge_threshold);
+    c->rb_pyr_margin = mo_pyr_margin(P.edge_threshold);
+    c->rb_ok = nl >= 2;
     for (int L = 1; L < nl; L++) {
         std::vector<int> xo, xc, yo, yc;
         mo_linear_coeffs(P.lv[L - 1].w, P.lv[L].w, xo, xc);
@@ -345,6 +348,7 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
             window_ok = std::min(xo[xl] + 1, P.lv[L - 1].w - 1) - xo[x] <= 7;
         }
         c->rtab[L].two_pass_ok = window_ok;
+        c->rb_ok = c->rb_ok && window_ok && orb_plan_resize_blur(P, L, xp, yp, c->rb_pyr_margin, c->rb_margin);
         size_t n = (size_t)wp + hp + 2 * dw + 2 * dh;
         int* d = nullptr;
         HIPCHK(c, hipMalloc((void**)&d, n * sizeof(int)));

@@ -223,12 +223,225 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
 // path for sources that are not (dense caller images whose width is not a multiple of 4).
 #define RS2_ROWS 136  // source rows a 64-row output tile can touch (scale <= 2) + 1
 #define RS2_UNR 5
+
+// pass 1 of one source row for one column group: the three aligned dwords at the group's 4-aligned offset -> 4 x u16 row interpolants
+__device__ __forceinline__ uint2 rs2_hrow(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t sh8, const uint32_t (&sel)[4],
+                                          const uint32_t (&coef)[4]) {
+    const uint32_t u0 = __builtin_amdgcn_alignbyte(w1, w0, sh8), u1 = __builtin_amdgcn_alignbyte(w2, w1, sh8);
+    uint32_t hv[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(u1, u0, sel[k]), coef[k], 0u);
+    return make_uint2(hv[0] | (hv[1] << 16), hv[2] | (hv[3] << 16));
+}
+
+// pass 2 of one output row for one column group: the interpolants of its two source rows -> 4 output bytes
+__device__ __forceinline__ uint32_t rs2_vrow(uint2 a, uint2 b, uint32_t e) {
+    const uint32_t c1 = e >> 16, cy = (256u - c1) | (c1 << 16);
+    const uint32_t v0 = udot2(__builtin_amdgcn_perm(b.x, a.x, 0x05040100u), cy, 32768u);
+    const uint32_t v1 = udot2(__builtin_amdgcn_perm(b.x, a.x, 0x07060302u), cy, 32768u);
+    const uint32_t v2 = udot2(__builtin_amdgcn_perm(b.y, a.y, 0x05040100u), cy, 32768u);
+    const uint32_t v3 = udot2(__builtin_amdgcn_perm(b.y, a.y, 0x07060302u), cy, 32768u);
+    // (v + 32768) >> 16 < 256 is byte 2 of every sum
+    return __builtin_amdgcn_perm(v1, v0, 0x0C0C0602u) | (__builtin_amdgcn_perm(v3, v2, 0x0C0C0602u) << 16);
+}
+
+// ---- 7x7 Gaussian blur, shared by k_blur and the blurring form of k_resize2 ----
+// {sat_u8(a >> 16), sat_u8(b >> 16)} in bits 0-7 and 8-15 (a, b < 2^31): five slow-class instructions pack four outputs instead
+// of a shift, a min and a shift-or each
+__device__ __forceinline__ uint32_t hi16_pair_sat_u8(uint32_t a, uint32_t b) {
+    uint32_t d;
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(__builtin_amdgcn_perm(b, a, 0x07060302u)));
+    return d;
+}
+
+// row pass of one quad: pw points at the dword whose byte 0 is 4 columns left of the quad's first output; rows 2p and 2p+1 (pw0,
+// pw1) -> 4 dwords {u16 sum of row 2p, u16 sum of row 2p+1}.  Each sum <= 257 * 255 = 65535.
+__device__ __forceinline__ uint4 blur_row_quad(const uint32_t* pw0, const uint32_t* pw1, uint32_t g0, uint32_t g1, uint32_t g2,
+                                               uint32_t g3) {
+    const uint32_t ta = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24), tb = g2 | (g1 << 8) | (g0 << 16);
+    uint32_t o[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint32_t* pw = h ? pw1 : pw0;
+        const uint32_t w0 = pw[0], w1 = pw[1], w2 = pw[2];
+        // output column 4q+k is centred on byte k+4: taps over bytes k+1 .. k+7 of (w0, w1, w2)
+        o[h][0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), tb, 0, false), false);
+        o[h][1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), tb, 0, false), false);
+        o[h][2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), tb, 0, false), false);
+        o[h][3] = __builtin_amdgcn_udot4(w1, ta, __builtin_amdgcn_udot4(w2, tb, 0, false), false);
+    }
+    return make_uint4(o[0][0] | (o[1][0] << 16), o[0][1] | (o[1][1] << 16), o[0][2] | (o[1][2] << 16), o[0][3] | (o[1][3] << 16));
+}
+
+// column pass of one quad: sr points at the quad's column in row pair p of the row-sum buffer (pitch: u32 per row pair) -> the 4
+// output bytes of rows 2p (pe) and 2p+1 (po), from row pairs p .. p+3
+__device__ __forceinline__ void blur_col_quad(const uint32_t* sr, int pitch, uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3,
+                                              uint32_t& pe, uint32_t& po) {
+    // even output row 2p   : rows 2p .. 2p+6   = pairs (g0,g1) (g2,g3) (g2,g1) (g0, 0)
+    // odd  output row 2p+1 : rows 2p+1 .. 2p+7 = pairs ( 0,g0) (g1,g2) (g3,g2) (g1,g0)
+    const uint32_t e0 = g0 | (g1 << 16), e1 = g2 | (g3 << 16), e2 = g2 | (g1 << 16), e3 = g0;
+    const uint32_t d0 = g0 << 16, d1 = g1 | (g2 << 16), d2 = g3 | (g2 << 16), d3 = g1 | (g0 << 16);
+    uint4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = *(const uint4*)(sr + j * pitch);
+    uint32_t se[4], so[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t a0 = k == 0 ? v[0].x : k == 1 ? v[0].y : k == 2 ? v[0].z : v[0].w;
+        const uint32_t a1 = k == 0 ? v[1].x : k == 1 ? v[1].y : k == 2 ? v[1].z : v[1].w;
+        const uint32_t a2 = k == 0 ? v[2].x : k == 1 ? v[2].y : k == 2 ? v[2].z : v[2].w;
+        const uint32_t a3 = k == 0 ? v[3].x : k == 1 ? v[3].y : k == 2 ? v[3].z : v[3].w;
+        se[k] = udot2(a0, e0, udot2(a1, e1, udot2(a2, e2, udot2(a3, e3, 1u << 15))));
+        so[k] = udot2(a0, d0, udot2(a1, d1, udot2(a2, d2, udot2(a3, d3, 1u << 15))));
+    }
+    // (sum >> 16) is at most 257: the high halves of two sums -> one dword (v_perm), both saturated to bytes at once
+    pe = hi16_pair_sat_u8(se[0], se[1]) | (hi16_pair_sat_u8(se[2], se[3]) << 16);
+    po = hi16_pair_sat_u8(so[0], so[1]) | (hi16_pair_sat_u8(so[2], so[3]) << 16);
+}
+
+// Blurring form of k_resize2 (RS2_BLUR = true): the launch of level L also writes the blurred level L-1.  Workgroup (bx, by) owns
+// rows [ypk[ty0] & 0x7FFF, the same for by + 1) and 4-aligned columns [xpk[tx0] & 0x7FFC, the same for bx + 1) of level L-1; the
+// first and last row / column of workgroups stretch to the blur region [margin, size - margin), so the partitions tile it exactly.
+// The workgroup stages ONE raw window of level L-1 in LDS - the union of its partition plus the 3-px blur halo (REFLECT_101 at the
+// level border, as k_blur) and the source rows / columns of its resize tile - and both the resize and the blur's row pass read it.
+// Phases (two barriers): stage | resize straight from the window -> level L, blur row pass -> s_row | blur column pass -> blur L-1.
+// The resize interpolates both source rows of every output row along x (rs2_hrow) and then along y (rs2_vrow): the values of
+// pass 1 + pass 2 without their LDS buffer and barrier.  Measured against two other forms (profiles/r06_ab_resize_blur.txt):
+// pass 1 -> s_h | pass 2 | row pass over s_h (four barriers, the same 22.5 KB) was 0.003 ms slower per step; s_h and s_row side by
+// side (two barriers, 33.8 KB, 4 instead of 7 waves per SIMD) 0.04 ms slower - these short-lived workgroups need the occupancy.
+// orb_plan_resize_blur (host) proves for every tile of the plan that the window and partition fit the buffers below; a plan that
+// fails it keeps the unfused k_resize2 + k_blur.
+#define RB_PW 80                      // partition columns (multiple of 4)
+#define RB_PH 80                      // partition rows
+#define RB_WR 88                      // window rows
+#define RB_WP 96                      // window pitch in bytes: window columns + 8 (the resize's third dword may run past it)
+#define RB_SR_BYTES ((RB_PH / 2 + 4) * RB_PW * 4)  // s_row: [row pair][column] u32, partition + 6 halo rows (+ 1 for an odd count)
+struct BlurOut {
+    uint8_t* dst;      // blurred level L-1 of frame 0
+    size_t fstride;    // bytes per frame
+    int pitch, margin;
+    uint32_t taps;     // g0 | g1 << 8 | g2 << 16 | g3 << 24
+};
+
+template <bool RS2_BLUR>
 __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src, size_t src_fstride, int spitch, int sw, int sh,
                                                  uint8_t* __restrict__ dst, size_t dst_fstride, int dpitch, int dw, int dh,
                                                  const uint32_t* __restrict__ xpk, const uint32_t* __restrict__ ypk,
-                                                 uint32_t inv_per, uint32_t inv_gx, int org) {
-    __shared__ __attribute__((aligned(16))) uint2 s_h[RS2_ROWS][16];  // [source row of the tile][column group]: 4 x u16
+                                                 uint32_t inv_per, uint32_t inv_gx, int org, BlurOut bo) {
     const int tid = threadIdx.x;
+    if constexpr (RS2_BLUR) {
+        __shared__ __attribute__((aligned(16))) uint8_t s_px[RB_WR * RB_WP];
+        __shared__ __attribute__((aligned(16))) uint32_t s_row[RB_SR_BYTES / 4];
+        int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+        {  // XCD affinity (speed only), as below
+            int rem;
+            xcd_map(bx + gridDim.x * (by + gridDim.y * bz), gridDim.x * gridDim.y, inv_per, gridDim.z, bz, rem);
+            by = (int)(inv_gx ? __umulhi((uint32_t)rem, inv_gx) : (uint32_t)rem);
+            bx = rem - by * (int)gridDim.x;
+        }
+        const int tx0 = org + bx * RS_TW, ty0 = org + by * RS_TH;
+        // resize tile: source rows [sy0, sy1], source columns [ab0, ax1) (the tables are padded with their last entry)
+        const uint32_t ey0 = ypk[ty0], ey1 = ypk[ty0 + RS_TH - 1], ex1 = xpk[tx0 + RS_TW - 1];
+        const int sy0 = (int)(ey0 & 0x7FFFu), sy1 = (int)(ey1 & 0x7FFFu) + (int)((ey1 >> 15) & 1u);
+        const int ab0 = (int)(xpk[tx0] & 0x7FFCu), ax1 = (int)(ex1 & 0x7FFFu) + (int)((ex1 >> 15) & 1u) + 1;
+        // blur partition of level L-1 and the staged window
+        const int bm = bo.margin;
+        const int r0 = by == 0 ? bm : sy0, r1 = by == (int)gridDim.y - 1 ? sh - bm : (int)(ypk[ty0 + RS_TH] & 0x7FFFu);
+        const int c0 = bx == 0 ? bm : ab0, c1 = bx == (int)gridDim.x - 1 ? (sw - bm + 3) & ~3 : (int)(xpk[tx0 + RS_TW] & 0x7FFCu);
+        const int wy0 = min(r0 - 3, sy0), wy1 = max(r1 + 3, sy1 + 1);
+        const int wx0 = min(c0 - 4, ab0), wx1 = max(c1 + 4, (ax1 + 3) & ~3);
+        const int nwr = wy1 - wy0, ndw = (wx1 - wx0) >> 2;
+        const uint8_t* img = src + (size_t)bz * src_fstride;
+        const int cg = tid & 15, rr = tid >> 4;
+        const uint4 xe = *(const uint4*)(xpk + tx0 + 4 * cg);
+        uint32_t ye[RS_TH / 16];
+#pragma unroll
+        for (int half = 0; half < RS_TH / 16; half++) ye[half] = ypk[ty0 + rr + 16 * half];
+        {  // stage: all loads of a thread issued before the first LDS store (one global round trip)
+            constexpr int TRIPS = (RB_WR * (RB_WP / 4 - 2) + 255) / 256;
+            const uint32_t inv = 0x100000u / (uint32_t)ndw + 1u;  // i / ndw, exact while i * ndw < 2^20
+            const bool inside = wy0 >= 0 && wy1 <= sh && wx0 >= 0 && wx1 <= sw;
+            uint32_t v[TRIPS];
+#pragma unroll
+            for (int t = 0; t < TRIPS; t++) {
+                const int i = min(tid + 256 * t, nwr * ndw - 1);
+                const uint32_t r = ((uint32_t)i * inv) >> 20, c4 = (uint32_t)i - r * (uint32_t)ndw;
+                const int x0 = wx0 + 4 * (int)c4;
+                if (inside) {
+                    v[t] = *(const uint32_t*)(img + (uint32_t)((wy0 + (int)r) * spitch + x0));
+                } else {  // REFLECT_101 rows; a dword that leaves [0, sw) from reflected bytes
+                    const uint8_t* row = img + (uint32_t)(reflect101(wy0 + (int)r, sh) * spitch);
+                    if (x0 >= 0 && x0 + 3 < sw) v[t] = *(const uint32_t*)(row + x0);
+                    else {
+                        uint32_t u = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; b++) u |= (uint32_t)row[reflect101(x0 + b, sw)] << (8 * b);
+                        v[t] = u;
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < TRIPS; t++) {
+                const int i = tid + 256 * t;
+                if (i < nwr * ndw) {
+                    const uint32_t r = ((uint32_t)i * inv) >> 20, c4 = (uint32_t)i - r * (uint32_t)ndw;
+                    ((uint32_t*)(s_px + r * RB_WP))[c4] = v[t];
+                }
+            }
+        }
+        __syncthreads();
+        {  // resize straight from the window: both source rows of an output row along x, then along y
+            const uint32_t xk[4] = {xe.x, xe.y, xe.z, xe.w};
+            const int ox0 = (int)(xk[0] & 0x7FFFu), ab = ox0 & ~3;
+            const uint32_t sh8 = (uint32_t)(ox0 & 3);
+            uint32_t sel[4], coef[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t a = (xk[k] & 0x7FFFu) - (uint32_t)ox0, b = a + ((xk[k] >> 15) & 1u), c1k = xk[k] >> 16;
+                sel[k] = a | (b << 16) | 0x0C000C00u;
+                coef[k] = (256u - c1k) | (c1k << 16);
+            }
+            const int x = tx0 + 4 * cg;
+            const uint32_t* pw = (const uint32_t*)(s_px + (ab - wx0));
+#pragma unroll
+            for (int half = 0; half < RS_TH / 16; half++) {
+                const int y = ty0 + rr + 16 * half;
+                if (x >= dw || y >= dh) break;
+                const uint32_t e = ye[half];
+                const int oy = (int)(e & 0x7FFFu) - wy0, oy1 = oy + (int)((e >> 15) & 1u);
+                const uint32_t* p0 = pw + oy * (RB_WP / 4);
+                const uint32_t* p1 = pw + oy1 * (RB_WP / 4);
+                const uint2 a = rs2_hrow(p0[0], p0[1], p0[2], sh8, sel, coef), b = rs2_hrow(p1[0], p1[1], p1[2], sh8, sel, coef);
+                *(uint32_t*)(dst + (size_t)bz * dst_fstride + (size_t)y * dpitch + x) = rs2_vrow(a, b, e);
+            }
+        }
+        const uint32_t g0 = bo.taps & 255u, g1 = (bo.taps >> 8) & 255u, g2 = (bo.taps >> 16) & 255u, g3 = bo.taps >> 24;
+        const int nq = (c1 - c0) >> 2, npr = (r1 - r0 + 7) >> 1, nop = (r1 - r0 + 1) >> 1;  // quads, row pairs in, row pairs out
+        const uint32_t invq = 0x100000u / (uint32_t)max(nq, 1) + 1u;
+        {  // blur row pass: s_px row (r0 - 3 - wy0) + j <-> level row r0 - 3 + j; byte 0 of a quad's first dword: its column - 4
+            const uint8_t* base = s_px + (r0 - 3 - wy0) * RB_WP + (c0 - 4 - wx0);
+            for (int t = tid; t < npr * nq; t += 256) {
+                const int p = (int)(((uint32_t)t * invq) >> 20), q = t - p * nq;
+                const uint32_t* pw = (const uint32_t*)(base + 2 * p * RB_WP + 4 * q);
+                *(uint4*)(s_row + p * RB_PW + 4 * q) = blur_row_quad(pw, pw + RB_WP / 4, g0, g1, g2, g3);
+            }
+        }
+        __syncthreads();
+        {  // blur column pass
+            uint8_t* out0 = bo.dst + (size_t)bz * bo.fstride;
+            for (int t = tid; t < nop * nq; t += 256) {
+                const int p = (int)(((uint32_t)t * invq) >> 20), q = t - p * nq;
+                uint32_t pe, po;
+                blur_col_quad(s_row + p * RB_PW + 4 * q, RB_PW, g0, g1, g2, g3, pe, po);
+                const int y = r0 + 2 * p;
+                uint8_t* out = out0 + (size_t)y * bo.pitch + c0 + 4 * q;  // pitch is a multiple of 16 >= w: <= 3 bytes of row padding
+                *(uint32_t*)out = pe;
+                if (y + 1 < r1) *(uint32_t*)(out + bo.pitch) = po;
+            }
+        }
+        return;
+    }
+    __shared__ __attribute__((aligned(16))) uint2 s_h[RS2_ROWS][16];  // [source row of the tile][column group]: 4 x u16
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     {  // XCD affinity (speed only): all tiles of a frame on one XCD (the level just written is in its L2)
         int rem;
@@ -274,11 +487,7 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
         for (int i = 0; i < RS2_UNR; i++) {
             const int r = r0 + 16 * i;
             if (r >= nrows) break;
-            const uint32_t u0 = __builtin_amdgcn_alignbyte(w[i][1], w[i][0], sh8), u1 = __builtin_amdgcn_alignbyte(w[i][2], w[i][1], sh8);
-            uint32_t hv[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(u1, u0, sel[k]), coef[k], 0u);
-            s_h[r][cg] = make_uint2(hv[0] | (hv[1] << 16), hv[2] | (hv[3] << 16));
+            s_h[r][cg] = rs2_hrow(w[i][0], w[i][1], w[i][2], sh8, sel, coef);
         }
     }
     __syncthreads();
@@ -288,15 +497,9 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
     for (int half = 0; half < RS_TH / 16; half++) {
         const int y = ty0 + rr + 16 * half;
         if (y >= dh) break;
-        const uint32_t e = ye[half], c1 = e >> 16, cy = (256u - c1) | (c1 << 16);
+        const uint32_t e = ye[half];
         const int oy = (int)(e & 0x7FFFu) - sy0, oy1 = oy + (int)((e >> 15) & 1u);
-        const uint2 a = s_h[oy][cg], b = s_h[oy1][cg];
-        const uint32_t v0 = udot2(__builtin_amdgcn_perm(b.x, a.x, 0x05040100u), cy, 32768u);
-        const uint32_t v1 = udot2(__builtin_amdgcn_perm(b.x, a.x, 0x07060302u), cy, 32768u);
-        const uint32_t v2 = udot2(__builtin_amdgcn_perm(b.y, a.y, 0x05040100u), cy, 32768u);
-        const uint32_t v3 = udot2(__builtin_amdgcn_perm(b.y, a.y, 0x07060302u), cy, 32768u);
-        // (v + 32768) >> 16 < 256 is byte 2 of every sum
-        const uint32_t packed = __builtin_amdgcn_perm(v1, v0, 0x0C0C0602u) | (__builtin_amdgcn_perm(v3, v2, 0x0C0C0602u) << 16);
+        const uint32_t packed = rs2_vrow(s_h[oy][cg], s_h[oy1][cg], e);
         // dpitch is a multiple of 16 >= dw: the <= 3 bytes past dw land in row padding
         *(uint32_t*)(dst + (size_t)bz * dst_fstride + (size_t)y * dpitch + x) = packed;
     }
@@ -306,21 +509,67 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
 // the blur's margin - 4 (8 at edge_threshold 31): FAST stages from column 16 / row 27, the Harris and orientation windows stay
 // 16 px inside, the blur tiling starts at 12 and reads from 8, and the next level's [8, ..) only needs this level's [9, ..).
 // compute() with caller keypoints and the probes pass 0.
-int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin) {
+static int resize_org(const LevelInfo& d, int margin) { return (d.w > 2 * margin + 8 && d.h > 2 * margin + 8) ? margin : 0; }
+
+// Plan time: does the blurring form of k_resize2 cover level L - 1's blur region [blur_margin, size - blur_margin) at this
+// geometry, with every window and partition inside RB_*?  Rows and columns are independent; this restates the kernel's prologue.
+bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp, const std::vector<uint32_t>& yp, int margin,
+                          int blur_margin) {
+    const LevelInfo& s = P.lv[L - 1];
+    const LevelInfo& d = P.lv[L];
+    const int bm = blur_margin, org = resize_org(d, margin);
+    if (bm < 0 || (bm & 3)) return false;
+    const int gx = (d.w - 2 * org + RS_TW - 1) / RS_TW, gy = (d.h - 2 * org + RS_TH - 1) / RS_TH;
+    if (gx < 1 || gy < 1 || (size_t)(org + gx * RS_TW + 1) > xp.size() || (size_t)(org + gy * RS_TH + 1) > yp.size()) return false;
+    for (int by = 0; by < gy; by++) {
+        const int ty0 = org + by * RS_TH;
+        const uint32_t ey1 = yp[ty0 + RS_TH - 1];
+        const int sy0 = (int)(yp[ty0] & 0x7FFFu), sy1 = (int)(ey1 & 0x7FFFu) + (int)((ey1 >> 15) & 1u);
+        const int r0 = by == 0 ? bm : sy0, r1 = by == gy - 1 ? s.h - bm : (int)(yp[ty0 + RS_TH] & 0x7FFFu);
+        const int wy0 = std::min(r0 - 3, sy0), wy1 = std::max(r1 + 3, sy1 + 1);
+        if (r1 <= r0 || r1 - r0 > RB_PH || wy1 - wy0 > RB_WR || r1 + 4 - wy0 > RB_WR || sy1 >= s.h) return false;
+    }
+    for (int bx = 0; bx < gx; bx++) {
+        const int tx0 = org + bx * RS_TW;
+        const uint32_t ex1 = xp[tx0 + RS_TW - 1];
+        const int ab0 = (int)(xp[tx0] & 0x7FFCu), ax1 = (int)(ex1 & 0x7FFFu) + (int)((ex1 >> 15) & 1u) + 1;
+        const int c0 = bx == 0 ? bm : ab0, c1 = bx == gx - 1 ? (s.w - bm + 3) & ~3 : (int)(xp[tx0 + RS_TW] & 0x7FFCu);
+        const int wx0 = std::min(c0 - 4, ab0), wx1 = std::max(c1 + 4, (ax1 + 3) & ~3);
+        if (c1 <= c0 || c1 - c0 > RB_PW || wx1 - wx0 + 8 > RB_WP || ax1 > s.w) return false;
+    }
+    return true;
+}
+
+// blur_margin >= 0 (the batched extraction with descriptors): when the plan allows it (c->rb_ok, orb_plan_resize_blur at this
+// blur margin) and every level takes k_resize2, the launch of level L also writes the blurred level L - 1 and *blurred is set; the
+// caller then blurs only the last level (orb_launch_blur from nlevels - 1).
+int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin, bool* blurred) {
     const Plan& P = c->plan;
+    auto src_of = [&](int L) { return L == 1 ? d_gray : c->d_pyr + P.lv[L - 1].off; };
+    auto sfs_of = [&](int L) { return L == 1 ? (size_t)P.w * P.h : (size_t)P.pyr_stride; };
+    auto al4_of = [&](int L) { return ((((size_t)src_of(L)) | sfs_of(L) | (size_t)P.lv[L - 1].pitch) & 3) == 0 && P.lv[L - 1].pitch >= 12; };
+    bool fuse = blur_margin >= 0 && nlevels == P.nlevels && nlevels >= 2 && c->rb_ok && c->rb_margin == blur_margin &&
+                c->rb_pyr_margin == margin;
+    for (int L = 1; L < nlevels && fuse; L++) fuse = al4_of(L) && c->rtab[L].two_pass_ok;
+    if (blurred) *blurred = fuse;
+    const uint32_t taps = (uint32_t)P.gk[0] | ((uint32_t)P.gk[1] << 8) | ((uint32_t)P.gk[2] << 16) | ((uint32_t)P.gk[3] << 24);
     for (int L = 1; L < nlevels; L++) {
         const LevelInfo& s = P.lv[L - 1];
         const LevelInfo& d = P.lv[L];
-        const uint8_t* src = L == 1 ? d_gray : c->d_pyr + s.off;
-        size_t sfs = L == 1 ? (size_t)P.w * P.h : (size_t)P.pyr_stride;
+        const uint8_t* src = src_of(L);
+        size_t sfs = sfs_of(L);
         const ResizeTab& t = c->rtab[L];
-        const int org = (d.w > 2 * margin + 8 && d.h > 2 * margin + 8) ? margin : 0;
+        const int org = resize_org(d, margin);
         dim3 grid((d.w - 2 * org + RS_TW - 1) / RS_TW, (d.h - 2 * org + RS_TH - 1) / RS_TH, batch);
         const uint32_t per = grid.x * grid.y, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u, inv_gx = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
-        const bool al4 = ((((size_t)src) | sfs | (size_t)s.pitch) & 3) == 0 && s.pitch >= 12;
-        if (al4 && t.two_pass_ok)
-            hipLaunchKernelGGL(k_resize2, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
-                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org);
+        const bool al4 = al4_of(L);
+        if (fuse) {
+            const BlurOut bo{c->d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, blur_margin, taps};
+            hipLaunchKernelGGL(k_resize2<true>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
+                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, bo);
+        } else if (al4 && t.two_pass_ok)
+            hipLaunchKernelGGL(k_resize2<false>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
+                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, BlurOut{});
         else
             hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
                                (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xofs, t.xc1, t.yofs, t.yc1, inv_per, inv_gx, org);
@@ -338,21 +587,13 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
 #define BT_PW (BT_W + 16)  // LDS pixel-tile pitch: 4 (aligned lead-in) + BT_W + 3 halo, rounded to a multiple of 16
 #define BT_ROWS (BT_H + 6)
 
-
-// {sat_u8(a >> 16), sat_u8(b >> 16)} in bits 0-7 and 8-15 (a, b < 2^31): five slow-class instructions pack four outputs instead
-// of a shift, a min and a shift-or each
-__device__ __forceinline__ uint32_t hi16_pair_sat_u8(uint32_t a, uint32_t b) {
-    uint32_t d;
-    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(__builtin_amdgcn_perm(b, a, 0x07060302u)));
-    return d;
-}
-
 // 7x7 Gaussian (8-bit quantised taps, sum 257), separable through LDS: u8 tile -> u16 row sums -> u8 output, all in
 // integer dot instructions.  Row pass: the 7 taps of one output are two v_dot4_u32_u8 on byte windows cut out of three
 // aligned dwords with v_alignbyte.  The u16 row sums of tile rows 2p and 2p+1 are stored interleaved in one dword per
 // column, so the column pass is four v_dot2_u32_u16 per output (tap pairs shifted by one row for odd output rows).
-// Interior tiles are staged with aligned dword loads; tiles touching the level border index with REFLECT_101.
-__global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict__ tile_tab, uint32_t inv_per, int org,
+// Interior tiles are staged with aligned dword loads; tiles touching the level border index with REFLECT_101.  tile0: first
+// entry of tile_tab this launch covers (the batched extraction blurs only its last level here when k_resize2 wrote the others).
+__global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict__ tile_tab, int tile0, uint32_t inv_per, int org,
                                               const uint8_t* __restrict__ gray, const uint8_t* __restrict__ pyr,
                                               uint8_t* __restrict__ blur) {
     __shared__ __attribute__((aligned(16))) uint8_t s_px[BT_ROWS * BT_PW];
@@ -361,7 +602,7 @@ __global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict
     xcd_map(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x, inv_per, gridDim.y, frame, tile);  // XCD affinity (speed only)
     // one wave-uniform table read instead of a level search and two divisions per workgroup (the scalar prologue was as long
     // as the vector body of these short-lived workgroups)
-    const uint32_t te = tile_tab[tile];
+    const uint32_t te = tile_tab[tile0 + tile];
     const int L = te & 0xFF;
     const LevelInfo lv = P.lv[L];
     const int tx0 = org + (int)((te >> 8) & 0xFFF) * BT_W, ty0 = org + (int)(te >> 20) * BT_H;  // org: margin the tiling skips
@@ -408,25 +649,9 @@ __global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict
     const uint32_t g0 = P.gk[0], g1 = P.gk[1], g2 = P.gk[2], g3 = P.gk[3];
 #pragma unroll
     for (int h2 = 0; h2 < BT_ROWS / 2 / BT_PP; h2++) {   // row pass: one task = 4 adjacent outputs of tile rows 2p and 2p+1 (BT_PP row pairs x BT_QW quads per pass)
-        const uint32_t ta = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24), tb = g2 | (g1 << 8) | (g0 << 16);
         const int p = tid / BT_QW + BT_PP * h2, q = tid % BT_QW;
-        uint32_t o[2][4];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const uint32_t* pw = (const uint32_t*)(s_px + (2 * p + h) * BT_PW + 4 * q);
-            const uint32_t w0 = pw[0], w1 = pw[1], w2 = pw[2];
-            // output column 4q+k is centred on s_px column 4q+k+4: taps over bytes k+1 .. k+7 of (w0, w1, w2)
-            o[h][0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), tb, 0, false), false);
-            o[h][1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), tb, 0, false), false);
-            o[h][2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), ta, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), tb, 0, false), false);
-            o[h][3] = __builtin_amdgcn_udot4(w1, ta, __builtin_amdgcn_udot4(w2, tb, 0, false), false);
-        }
-        uint4 packed;  // each sum <= 257 * 255 = 65535
-        packed.x = o[0][0] | (o[1][0] << 16);
-        packed.y = o[0][1] | (o[1][1] << 16);
-        packed.z = o[0][2] | (o[1][2] << 16);
-        packed.w = o[0][3] | (o[1][3] << 16);
-        *(uint4*)(&s_row[p * BT_W + 4 * q]) = packed;
+        const uint32_t* pw = (const uint32_t*)(s_px + 2 * p * BT_PW + 4 * q);
+        *(uint4*)(&s_row[p * BT_W + 4 * q]) = blur_row_quad(pw, pw + BT_PW / 4, g0, g1, g2, g3);
     }
     __syncthreads();
 #pragma unroll
@@ -434,26 +659,8 @@ __global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict
         const int p = tid / BT_QW + BT_PP * h2, c0 = (tid % BT_QW) * 4;
         const int x = tx0 + c0, y = ty0 + 2 * p;
         if (p < BT_H / 2 && y < lv.h && x < lv.w) {
-            // even output row 2p   : rows 2p .. 2p+6   = pairs (g0,g1) (g2,g3) (g2,g1) (g0, 0)
-            // odd  output row 2p+1 : rows 2p+1 .. 2p+7 = pairs ( 0,g0) (g1,g2) (g3,g2) (g1,g0)
-            const uint32_t e0 = g0 | (g1 << 16), e1 = g2 | (g3 << 16), e2 = g2 | (g1 << 16), e3 = g0;
-            const uint32_t d0 = g0 << 16, d1 = g1 | (g2 << 16), d2 = g3 | (g2 << 16), d3 = g1 | (g0 << 16);
-            uint4 v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = *(const uint4*)(&s_row[(p + j) * BT_W + c0]);
-            uint32_t se[4], so[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t a0 = k == 0 ? v[0].x : k == 1 ? v[0].y : k == 2 ? v[0].z : v[0].w;
-                const uint32_t a1 = k == 0 ? v[1].x : k == 1 ? v[1].y : k == 2 ? v[1].z : v[1].w;
-                const uint32_t a2 = k == 0 ? v[2].x : k == 1 ? v[2].y : k == 2 ? v[2].z : v[2].w;
-                const uint32_t a3 = k == 0 ? v[3].x : k == 1 ? v[3].y : k == 2 ? v[3].z : v[3].w;
-                se[k] = udot2(a0, e0, udot2(a1, e1, udot2(a2, e2, udot2(a3, e3, 1u << 15))));
-                so[k] = udot2(a0, d0, udot2(a1, d1, udot2(a2, d2, udot2(a3, d3, 1u << 15))));
-            }
-            // (sum >> 16) is at most 257: the high halves of two sums -> one dword (v_perm), both saturated to bytes at once
-            const uint32_t pe = hi16_pair_sat_u8(se[0], se[1]) | (hi16_pair_sat_u8(se[2], se[3]) << 16);
-            const uint32_t po = hi16_pair_sat_u8(so[0], so[1]) | (hi16_pair_sat_u8(so[2], so[3]) << 16);
+            uint32_t pe, po;
+            blur_col_quad(&s_row[p * BT_W + c0], BT_W, g0, g1, g2, g3, pe, po);
             uint8_t* out = blur + (size_t)frame * P.blur_stride + lv.boff + (size_t)y * lv.bpitch + x;
             *(uint32_t*)out = pe;  // bpitch is a multiple of 16 >= w: the <= 3 bytes past w land in row padding
             if (y + 1 < lv.h) *(uint32_t*)(out + lv.bpitch) = po;
@@ -464,10 +671,11 @@ __global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict
 // margin: the tiling covers [margin, w - margin) x [margin, h - margin) of every level.  The detector's keypoints lie at least
 // edge_threshold from the border and rBRIEF samples within 19 px of them, so the pipeline passes (edge_threshold - 19) & ~3
 // (12 at the default 31: 255 instead of 286 tiles per 640x480 frame); compute() with caller keypoints and the level probes
-// pass 0 (a caller's keypoint on a coarse octave may sample anywhere).
-int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin) {
+// pass 0 (a caller's keypoint on a coarse octave may sample anywhere).  Levels [first_level, nlevels) are blurred.
+int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int first_level) {
     const Plan& P = c->plan;
-    if (nlevels < 1 || nlevels > P.nlevels) return mo_fail(c, MO_ERR_ARG, "blur: level count outside the plan");
+    if (nlevels < 1 || nlevels > P.nlevels || first_level < 0 || first_level >= nlevels)
+        return mo_fail(c, MO_ERR_ARG, "blur: level range outside the plan");
     const int slot = margin > 0 ? 1 : 0;
     if (slot && c->tile_margin != margin && c->d_tile_tab[1]) { hipFree(c->d_tile_tab[1]); c->d_tile_tab[1] = nullptr; }
     if (!c->d_tile_tab[slot]) {  // (re)built with the plan: free_plan_buffers drops it
@@ -484,9 +692,10 @@ int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, in
         HIPCHK(c, hipMemcpy(c->d_tile_tab[slot], tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (slot) c->tile_margin = margin;
     }
-    const uint32_t per = (uint32_t)c->tile_cum[slot][nlevels], inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;  // first nlevels levels
-    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->d_tile_tab[slot], inv_per, margin, d_gray, c->d_pyr,
-                       c->d_blur);
+    const int tile0 = c->tile_cum[slot][first_level];
+    const uint32_t per = (uint32_t)(c->tile_cum[slot][nlevels] - tile0), inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
+    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->d_tile_tab[slot], tile0, inv_per, margin, d_gray,
+                       c->d_pyr, c->d_blur);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }

@@ -170,6 +170,7 @@ SIGNATURES = {
     "mo_stage_times": (_i, [_vp, _vp, _vp, _i]),
     "mo_stage_times_back": (_i, [_vp, _i, _vp, _vp, _i]),
     "mo_dbg_pyramid_level": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mo_dbg_blur_level": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mo_dbg_fast_level": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mo_dbg_retain_best": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "mo_map_create": (_vp, [_vp, _i, _i, C.c_int64, C.c_int64]),
@@ -615,6 +616,14 @@ class Context:
         self._check(self.lib.mo_dbg_pyramid_level(self.h, C.byref(prm), _ptr(g), w, h, level, int(blurred), _ptr(out),
                                                   C.byref(lw), C.byref(lh)))
         return out[:lw.value * lh.value].reshape(lh.value, lw.value).copy()
+
+    def dbg_blur_level(self, frame, level, w, h):
+        """The blurred level of one frame as the last extraction (of w x h frames) left it -> (array, whether the plan blurs inside
+        the resize launches)."""
+        lw, lh, rb = C.c_int(0), C.c_int(0), C.c_int(0)
+        out = np.zeros(w * h, np.uint8)
+        self._check(self.lib.mo_dbg_blur_level(self.h, int(frame), int(level), _ptr(out), C.byref(lw), C.byref(lh), C.byref(rb)))
+        return out[:lw.value * lh.value].reshape(lh.value, lw.value).copy(), bool(rb.value)
 
     def dbg_fast_level(self, gray, prm, level):
         g = np.ascontiguousarray(gray, np.uint8)
