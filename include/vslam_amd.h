@@ -530,6 +530,68 @@ typedef struct {
 int mo_map_track(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*, mo_map_track_out*);
 int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len);
 
+/* mo_map_bundle_adjust: local bundle adjustment on the map as it stands (ORB-SLAM2's Optimizer::LocalBundleAdjustment, monocular): the
+ * poses of the last keyframes and the positions of the points they see are refined together.  poses = [n_kf][12], [R | t] row-major per
+ * keyframe POSITION (X_cam = R X + t; the store itself only holds P = K [R | t]).
+ *   observations  read like the cull and mo_map_track read them (negative positions and rows count from the end; entries naming a position
+ *                 or row that does not exist are skipped).  An edge = one valid observation (point, keyframe position, row).
+ *   window        the candidate positions are the last `window` (0: all) except position 0, which is never free.  More than 16 candidates
+ *                 are refused with MO_ERR_ARG, not truncated.
+ *   local points  the points with >= 2 edges of which at least one is at a candidate position (decided before the gauge rule below).
+ *   keyframes     a position with an edge to a local point takes part: fixed when it is not a candidate, else free.  Gauge: while fewer
+ *                 than two keyframes are fixed, the lowest free position becomes fixed too (two fixed poses pin the 7 degrees of freedom
+ *                 of a monocular map: position, orientation and scale).  Fixed keyframes contribute residuals, not unknowns; positions
+ *                 without an edge to a local point are outside the problem.
+ *   residual      e = keypoint - projection, f64; projection p = K (R X + t), (p0 / p2, p1 / p2) as mo_map_track forms it; information
+ *                 1 / scale_factor^(2 octave) (repeated products from 1.0, negative octaves as 0).  An edge whose projection is not finite
+ *                 contributes nothing and is an outlier.
+ *   rounds        round 0: at most max_steps[0] Levenberg-Marquardt steps over all edges with the Huber cost of width sqrt(chi2) on
+ *                 information * |e|^2 (cost s below chi2, 2 sqrt(chi2 s) - chi2 above; weight sqrt(chi2 / s) above); then every edge is
+ *                 classified (inlier: depth > 0 and information * |e|^2 <= chi2); round 1: at most max_steps[1] steps over the inliers
+ *                 without Huber; then the final classification.
+ *   one step      normal equations of the weighted edges with Jacobians of the projection against the left perturbation (rho, w) of the
+ *                 pose (R' = exp(w) R, t' = exp(w) t + rho) and against the point.  Damping: every diagonal entry times (1 + lambda);
+ *                 lambda is 1e-4 at the start of each round.  Points are eliminated by the Schur complement (per point V 3x3, inverted
+ *                 by Cholesky; a V that is not positive definite holds that point fixed for the step), the reduced camera system
+ *                 (6 n_free <= 96) is solved by Cholesky, the points are back-substituted.  The step is accepted when it lowers the
+ *                 round's cost (lambda / 10), else undone (lambda * 10); both count as a step.  A round ends early at an update below
+ *                 1e-10 (largest absolute entry over all unknowns, accepted or not), at lambda > 1e8, or at a reduced system that is not
+ *                 positive definite (that attempt is not counted).
+ *   writes        xyz of the local points (the f64 result rounded to f32) and, when at least one step was accepted, P = K [R | t] of the free keyframes.  Nothing else: no
+ *                 observation is erased, no point removed; points and keyframes outside the problem keep their bytes.
+ *   returns       ok = the problem ran and n_inliers >= min_inliers.  An empty map, no free keyframe, or no local point: nothing runs,
+ *                 nothing is written, every count is 0, ok = 0, not an error.
+ * Everything is decided on the device (flags in a result block that later kernels read first): no host round trip inside the call, one
+ * synchronisation - the copy-out.  No floating-point atomics: two calls on equal maps give the same bytes. */
+typedef struct {
+    int32_t window;          /* candidate free positions, counted from the last (10); 0: all */
+    int32_t min_inliers;     /* ok needs this many inlier edges at the end (50) */
+    int32_t max_steps[2];    /* steps of round 0 and round 1, each 0 .. 100 (5, 10) */
+    double scale_factor;     /* of the information (1.2) */
+    double chi2;             /* outlier threshold; the Huber width is its square root (5.991) */
+} mo_map_ba_params;
+typedef struct {
+    /* caller-allocated, may be NULL */
+    double* poses_out;       /* [n_kf][12] the free ones refined, the rest as given */
+    int32_t* kf_state;       /* [n_kf] 0 outside the problem, 1 fixed, 2 free */
+    uint8_t* edge_inlier;    /* [n_obs] per entry of the observation arrays: 0 skipped or outside the problem, 1 inlier, 2 outlier */
+    double* points_out;      /* [n_pts][3] f64 positions of the local points, NaN elsewhere */
+    /* filled by the call */
+    double cost[3];          /* robust cost at the start, robust cost after round 0, plain cost of the inliers at the end */
+    double lambda;           /* damping after the last step */
+    int32_t n_free, n_fixed, n_local, n_edges, n_inliers;
+    int32_t steps[2], accepted[2];
+    int32_t ok;
+} mo_map_ba_out;
+int mo_map_bundle_adjust(mo_map*, const double K[9], const double* poses, const mo_map_ba_params*, mo_map_ba_out*);
+/* mo_map_add_observations: the observation (kf_pos, row[i]) is appended to map point point[i] (index into the map as it stands), at the
+ * end of that point's list.  Skipped: point[i] < 0 or out of range, a point that already has a valid observation at kf_pos (for kf_pos == the number of
+ * keyframes: an entry stored with that very position); when two
+ * entries name the same point the lower i wins.  kf_pos == the number of keyframes means the keyframe the next mo_map_add_keyframe
+ * stores (its cull validates the rows: MO_ERR_INDEX for one that does not exist).  The observation arrays are rebuilt into the other
+ * copy of the map store by a scan and a scatter; one synchronisation. */
+int mo_map_add_observations(mo_map*, int kf_pos, int n, const int32_t* point, const int32_t* row);
+
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls
  * neither clears nor pollutes this status.  Synchronises the context stream, copies the flag word to flags[0] (flags may be NULL; [1..3] reserved, 0)

@@ -1,0 +1,727 @@
+// map_ba.hip -- local bundle adjustment on the device map (mo_map_bundle_adjust in include/vslam_amd.h: ORB-SLAM2's
+// Optimizer::LocalBundleAdjustment, monocular) and the call that gives it multi-view tracks (mo_map_add_observations).
+//
+// Chain of one bundle adjustment (one synchronisation, the copy-out; every decision - the gauge, accept / reject, the end of a round -
+// is a flag in BaRes that the later kernels read first):
+//   k_ba_mark      one thread per map point: valid edges read like the cull reads them, local-point flag, keyframes with edges
+//   scans          local rank of every local point, first compact edge of every local point (the map's device-wide scan)
+//   k_ba_setup     one block: free / fixed keyframes and the gauge rule, free index of every position
+//   k_ba_edges     one thread per map point: its edges in CSR order into the compact edge arrays, its position as f64
+//   k_ba_cost      one thread per local point: cost of its edges, classification between the rounds; k_ba_reduce sums in a fixed tree
+//   per Levenberg-Marquardt step:
+//     k_ba_lin     one thread per local point: V (damped, inverted), g_p, its current cost
+//     k_ba_pair    one workgroup per free-keyframe pair (i <= j): the 6x6 block S_ij (and b_i on the diagonal) summed over the local
+//                  points in a fixed thread assignment and a fixed reduction tree; Jacobians are recomputed, not stored
+//     k_ba_solve   one workgroup: the reduced system (<= 96) packed in LDS, left-looking Cholesky across the block, substitution, the
+//                  trial poses
+//     k_ba_back    one thread per local point: back-substitution, trial position, trial cost
+//     k_ba_accept  one workgroup: cost sums, accept / reject, lambda, the end-of-round flags; an accepted step becomes the state
+//   k_ba_write     xyz (f32) of the local points, kP of the free keyframes, the optional outputs
+// No floating-point atomics anywhere: sums are per-thread in index order, then fixed wave / workgroup trees.
+// -ffp-contract=off (Makefile): ba.h rounds on the device as in the host build of tests/native/ba_check.cpp.
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "map_store.h"
+#include "ba.h"
+
+#define BA_BLOCK 256
+#define BA_MAX_PAIRS (BA_MAX_FREE * (BA_MAX_FREE + 1) / 2)
+#define BA_TRI_N (BA_MAX_DIM * (BA_MAX_DIM + 1) / 2)
+#define BA_KF_OUT (-2)    // kf_fidx: the position has no edge to a local point
+#define BA_KF_FIXED (-1)  // kf_fidx: fixed keyframe (>= 0: index among the free ones)
+
+struct BaPrm {
+    double K[9], sf, chi2;
+    int n_kf, lo_pos;
+};
+
+struct BaRes {
+    double cost[3], lambda, upd_c;
+    int32_t n_local, n_edges, n_free, n_fixed, n_inliers;
+    int32_t steps[2], accepted[2], done[2];
+    int32_t run, step_ok;
+    int32_t free_pos[BA_MAX_FREE];
+};
+
+struct BaBufs {
+    // per map point
+    int32_t* loc = nullptr; int32_t* ecnt = nullptr; int32_t* lrank = nullptr; int32_t* ebase = nullptr;
+    size_t loc_bytes = 0, ecnt_bytes = 0, lrank_bytes = 0, ebase_bytes = 0;
+    double* pout = nullptr; size_t pout_bytes = 0;               // [point][3] the optional f64 output
+    // per local point (by local rank)
+    int32_t* lpt = nullptr; int32_t* eoff = nullptr; int32_t* pn = nullptr; uint8_t* pfix = nullptr;
+    double* X = nullptr; double* Xt = nullptr; double* Vi = nullptr; double* gp = nullptr; double* pc = nullptr; double* pt = nullptr; double* pu = nullptr;
+    size_t lpt_bytes = 0, eoff_bytes = 0, pn_bytes = 0, pfix_bytes = 0, X_bytes = 0, Xt_bytes = 0, Vi_bytes = 0, gp_bytes = 0, pc_bytes = 0, pt_bytes = 0,
+           pu_bytes = 0;
+    // per edge (compact, CSR order of the local points)
+    int32_t* e_kf = nullptr; int32_t* e_obs = nullptr; float* e_xy = nullptr; double* e_info = nullptr; uint8_t* e_inl = nullptr;
+    size_t e_kf_bytes = 0, e_obs_bytes = 0, e_xy_bytes = 0, e_info_bytes = 0, e_inl_bytes = 0;
+    uint8_t* einl = nullptr; size_t einl_bytes = 0;              // [observation] 0 / 1 / 2
+    // per keyframe position
+    int32_t* kf_edge = nullptr; int32_t* kf_fidx = nullptr; double* poseC = nullptr; double* poseT = nullptr;
+    size_t kf_edge_bytes = 0, kf_fidx_bytes = 0, poseC_bytes = 0, poseT_bytes = 0;
+    double* S = nullptr;                                         // [96][96] reduced system, [96] right side, [96] solution
+    BaRes* res = nullptr; BaRes* h_res = nullptr;                // device / pinned
+    // mo_map_add_observations
+    int32_t* ao_pt = nullptr; int32_t* ao_row = nullptr; int32_t* ao_claim = nullptr; int32_t* ao_cnt = nullptr; int32_t* ao_base = nullptr;
+    size_t ao_pt_bytes = 0, ao_row_bytes = 0, ao_claim_bytes = 0, ao_cnt_bytes = 0, ao_base_bytes = 0;
+    int32_t* ao_total = nullptr;
+};
+
+void map_ba_free(mo_map* m) {
+    BaBufs* b = m->ba;
+    if (!b) return;
+    void* bufs[] = {b->loc, b->ecnt, b->lrank, b->ebase, b->pout, b->lpt, b->eoff, b->pn, b->pfix, b->X, b->Xt, b->Vi, b->gp, b->pc, b->pt, b->pu,
+                    b->e_kf, b->e_obs, b->e_xy, b->e_info, b->e_inl, b->einl, b->kf_edge, b->kf_fidx, b->poseC, b->poseT, b->S, b->res,
+                    b->ao_pt, b->ao_row, b->ao_claim, b->ao_cnt, b->ao_base, b->ao_total};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_res) hipHostFree(b->h_res);
+    delete b;
+    m->ba = nullptr;
+}
+
+// the keyframe position and store entry of observation o, read like the cull reads it; false when it names nothing
+__device__ __forceinline__ bool ba_obs(const MapPts& src, int o, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                       int* pos, int* slot, int* kp) {
+    int kf = src.okf[o];
+    if (kf < 0) kf += n_kf;
+    if (kf < 0 || kf >= n_kf) return false;
+    const int s = pos_slot[kf];
+    int r = src.okp[o];
+    const int nk = kcnt[s];
+    if (r < 0) r += nk;
+    if (r < 0 || r >= nk) return false;
+    *pos = kf; *slot = s; *kp = r;
+    return true;
+}
+
+// fixed-order sums: lane 0's shuffle tree per wave, then the waves in order; every thread receives the result
+__device__ __forceinline__ double ba_wave_sum(double v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ double ba_block_sum(double v, double* lds) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = ba_wave_sum(v);
+    if (lane == 0) lds[wv] = v;
+    __syncthreads();
+    double s = lds[0];
+    for (int w = 1; w < nw; w++) s += lds[w];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ double ba_block_max(double v, double* lds) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int d = 32; d; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
+    if (lane == 0) lds[wv] = v;
+    __syncthreads();
+    double s = lds[0];
+    for (int w = 1; w < nw; w++) s = fmax(s, lds[w]);
+    __syncthreads();
+    return s;
+}
+
+__global__ void k_ba_init(BaRes* __restrict__ res) {
+    if (threadIdx.x) return;
+    for (int i = 0; i < 3; i++) res->cost[i] = 0.0;
+    res->lambda = 1e-4; res->upd_c = 0.0;
+    res->n_local = 0; res->n_edges = 0; res->n_free = 0; res->n_fixed = 0; res->n_inliers = 0;
+    for (int i = 0; i < 2; i++) { res->steps[i] = 0; res->accepted[i] = 0; res->done[i] = 0; }
+    res->run = 0; res->step_ok = 0;
+    for (int i = 0; i < BA_MAX_FREE; i++) res->free_pos[i] = -1;
+}
+
+// local points: >= 2 edges, one of them at a position the window frees (>= lo_pos, never 0); every position with an edge to a local
+// point is flagged (plain stores of 1: the racing writers agree)
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_mark(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                                      int lo_pos, int32_t* __restrict__ loc, int32_t* __restrict__ ecnt, int32_t* __restrict__ kf_edge) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i >= n_pts) return;
+    const int o0 = src.off[i], o1 = src.off[i + 1];
+    int nv = 0, pos, s, kp;
+    bool fr = false;
+    for (int o = o0; o < o1; o++)
+        if (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) { nv++; fr |= pos >= lo_pos && pos != 0; }
+    const bool local = nv >= 2 && fr;
+    loc[i] = local;
+    ecnt[i] = local ? nv : 0;
+    if (local)
+        for (int o = o0; o < o1; o++)
+            if (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) kf_edge[pos] = 1;
+}
+
+// free and fixed keyframes.  Outside the window a position with edges is fixed; inside, in position order, the lowest ones are fixed
+// too until two keyframes are (the gauge), the rest are free.
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_setup(BaPrm prm, const int32_t* __restrict__ kf_edge, int32_t* __restrict__ kf_fidx, BaRes* __restrict__ res) {
+    __shared__ int nfix;
+    if (threadIdx.x == 0) nfix = 0;
+    __syncthreads();
+    const int lo = prm.lo_pos > 1 ? prm.lo_pos : 1;
+    for (int pos = threadIdx.x; pos < prm.n_kf && pos < lo; pos += BA_BLOCK) {
+        const int has = kf_edge[pos];
+        kf_fidx[pos] = has ? BA_KF_FIXED : BA_KF_OUT;
+        if (has) atomicAdd(&nfix, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x) return;
+    int nfixed = nfix, nfree = 0;
+    for (int pos = lo; pos < prm.n_kf; pos++) {
+        if (!kf_edge[pos]) { kf_fidx[pos] = BA_KF_OUT; continue; }
+        if (nfixed < 2) { kf_fidx[pos] = BA_KF_FIXED; nfixed++; }
+        else if (nfree < BA_MAX_FREE) { kf_fidx[pos] = nfree; res->free_pos[nfree++] = pos; }
+        else kf_fidx[pos] = BA_KF_FIXED;   // (the host refuses windows wider than BA_MAX_FREE: not reached)
+    }
+    res->n_free = nfree; res->n_fixed = nfixed;
+    res->run = nfree > 0 && res->n_local > 0;
+}
+
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_edges(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                                       const mo_keypoint* __restrict__ kkps, int row, double sf, const int32_t* __restrict__ loc,
+                                                       const int32_t* __restrict__ lrank, const int32_t* __restrict__ ebase, int32_t* __restrict__ lpt,
+                                                       int32_t* __restrict__ eoff, double* __restrict__ X, int32_t* __restrict__ e_kf,
+                                                       int32_t* __restrict__ e_obs, float* __restrict__ e_xy, double* __restrict__ e_info,
+                                                       uint8_t* __restrict__ e_inl, const BaRes* __restrict__ res) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i == 0) eoff[res->n_local] = res->n_edges;
+    if (i >= n_pts || !loc[i]) return;
+    const int r = lrank[i];
+    lpt[r] = i;
+    int e = ebase[i];
+    eoff[r] = e;
+    for (int k = 0; k < 3; k++) X[(size_t)r * 3 + k] = src.xyz[(size_t)i * 3 + k];
+    const int o0 = src.off[i], o1 = src.off[i + 1];
+    int pos, s, kp;
+    for (int o = o0; o < o1; o++) {
+        if (!ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) continue;
+        const mo_keypoint q = kkps[(size_t)s * row + kp];
+        e_kf[e] = pos; e_obs[e] = o; e_xy[(size_t)e * 2] = q.x; e_xy[(size_t)e * 2 + 1] = q.y; e_info[e] = ba_info(sf, q.octave); e_inl[e] = 1;
+        e++;
+    }
+}
+
+// mode 0: robust cost of every edge; 1: the same and every edge classified; 2: every edge classified, plain cost of the inliers
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_cost(BaPrm prm, int mode, const int32_t* __restrict__ eoff, const double* __restrict__ X,
+                                                      const int32_t* __restrict__ e_kf, const float* __restrict__ e_xy, const double* __restrict__ e_info,
+                                                      uint8_t* __restrict__ e_inl, const double* __restrict__ pose, double* __restrict__ pc,
+                                                      int32_t* __restrict__ pn, const BaRes* __restrict__ res) {
+    if (!res->run) return;
+    const int r = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (r >= res->n_local) return;
+    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
+    double cost = 0.0;
+    int n = 0;
+    for (int e = eoff[r]; e < eoff[r + 1]; e++) {
+        double er[2], zc;
+        const bool fin = ba_residual(prm.K, pose + (size_t)e_kf[e] * 12, Xp, e_xy[(size_t)e * 2], e_xy[(size_t)e * 2 + 1], er, &zc);
+        const double e2 = fin ? e_info[e] * (er[0] * er[0] + er[1] * er[1]) : 0.0;
+        const bool in = fin && zc > 0.0 && e2 <= prm.chi2;
+        if (mode) e_inl[e] = in;
+        n += in;
+        if (fin && mode < 2) cost += ba_rho(e2, prm.chi2);
+        if (in && mode == 2) cost += e2;
+    }
+    pc[r] = cost;
+    pn[r] = n;
+}
+
+__global__ __launch_bounds__(1024) void k_ba_reduce(int idx, const double* __restrict__ pc, const int32_t* __restrict__ pn, BaRes* __restrict__ res) {
+    __shared__ double lds[16];
+    __shared__ int cnt;
+    if (!res->run) return;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    const int n = res->n_local;
+    double s = 0.0;
+    int c = 0;
+    for (int r = threadIdx.x; r < n; r += 1024) { s += pc[r]; c += pn[r]; }
+    s = ba_block_sum(s, lds);
+    for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&cnt, c);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        res->cost[idx] = s; res->n_inliers = cnt;
+        if (idx == 1) res->lambda = 1e-4;   // every round starts from the same damping
+    }
+}
+
+__device__ __forceinline__ bool ba_active(const BaRes* res, int round) { return res->run && !res->done[round]; }
+
+// residual, weight and Jacobians of edge e at the current state; false when the edge contributes nothing
+__device__ __forceinline__ bool ba_edge_lin(const BaPrm& prm, double huber2, const double* T, const double* Xp, float x, float y, double info, double* er,
+                                            double* w, double* e2, double* Jc, double* Jp) {
+    double zc;
+    if (!ba_residual(prm.K, T, Xp, x, y, er, &zc)) return false;
+    *e2 = info * (er[0] * er[0] + er[1] * er[1]);
+    *w = info * ba_weight(*e2, huber2);
+    return ba_jacobians(prm.K, T, Xp, Jc, Jp);
+}
+
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_lin(BaPrm prm, int round, const int32_t* __restrict__ eoff, const double* __restrict__ X,
+                                                     const int32_t* __restrict__ e_kf, const float* __restrict__ e_xy, const double* __restrict__ e_info,
+                                                     const uint8_t* __restrict__ e_inl, const double* __restrict__ pose, double* __restrict__ Vi,
+                                                     double* __restrict__ gp, uint8_t* __restrict__ pfix, double* __restrict__ pc,
+                                                     const BaRes* __restrict__ res) {
+    if (!ba_active(res, round)) return;
+    const int r = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (r >= res->n_local) return;
+    const double huber2 = round == 0 ? prm.chi2 : 0.0, damp = 1.0 + res->lambda;
+    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
+    double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, cost = 0.0;
+    for (int e = eoff[r]; e < eoff[r + 1]; e++) {
+        if (round && !e_inl[e]) continue;
+        double er[2], w, e2, Jc[12], Jp[6];
+        if (!ba_edge_lin(prm, huber2, pose + (size_t)e_kf[e] * 12, Xp, e_xy[(size_t)e * 2], e_xy[(size_t)e * 2 + 1], e_info[e], er, &w, &e2, Jc, Jp)) continue;
+        cost += ba_rho(e2, huber2);
+        ba_point_terms(Jp, w, er, V, g);
+    }
+    V[0] *= damp; V[3] *= damp; V[5] *= damp;
+    double inv[6] = {0, 0, 0, 0, 0, 0};
+    const bool ok = ba_inv3(V, inv);
+    for (int k = 0; k < 6; k++) Vi[(size_t)r * 6 + k] = inv[k];
+    for (int k = 0; k < 3; k++) gp[(size_t)r * 3 + k] = g[k];
+    pfix[r] = !ok;
+    pc[r] = cost;
+}
+
+// one workgroup per pair of free keyframes (i <= j): S_ij = [i == j] (H_ii + lambda diag H_ii) - sum over points W_i V^-1 W_j^T, and
+// on the diagonal b_i = g_i - sum W_i V^-1 g_p.  Thread t takes the local points t, t + 256, ... in order; 48 sums per thread.
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_pair(BaPrm prm, int round, const int32_t* __restrict__ eoff, const double* __restrict__ X,
+                                                      const int32_t* __restrict__ e_kf, const float* __restrict__ e_xy, const double* __restrict__ e_info,
+                                                      const uint8_t* __restrict__ e_inl, const int32_t* __restrict__ kf_fidx, const double* __restrict__ pose,
+                                                      const double* __restrict__ Vi, const double* __restrict__ gp, const uint8_t* __restrict__ pfix,
+                                                      double* __restrict__ S, const BaRes* __restrict__ res) {
+    constexpr int NW = BA_BLOCK / 64;
+    __shared__ double red[NW][48];
+    if (!ba_active(res, round)) return;
+    const int nf = res->n_free;
+    int fi = 0, rem = blockIdx.x;
+    while (fi < nf && rem >= nf - fi) { rem -= nf - fi; fi++; }
+    if (fi >= nf) return;
+    const int fj = fi + rem;
+    const bool diag = fi == fj;
+    const double huber2 = round == 0 ? prm.chi2 : 0.0, lambda = res->lambda;
+    const int n = res->n_local;
+    double a[48];   // [0, 36) the block, [36, 42) b_i, [42, 48) diag H_ii
+    for (int k = 0; k < 48; k++) a[k] = 0.0;
+    for (int r = threadIdx.x; r < n; r += BA_BLOCK) {
+        const int e0 = eoff[r], e1 = eoff[r + 1];
+        bool hi = false, hj = false;
+        for (int e = e0; e < e1; e++) {
+            if (round && !e_inl[e]) continue;
+            const int f = kf_fidx[e_kf[e]];
+            hi |= f == fi; hj |= f == fj;
+        }
+        if (!hi || !hj) continue;
+        const bool fixedp = pfix[r];
+        if (fixedp && !diag) continue;
+        const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
+        double inv[6], g[3];
+        for (int k = 0; k < 6; k++) inv[k] = Vi[(size_t)r * 6 + k];
+        for (int k = 0; k < 3; k++) g[k] = gp[(size_t)r * 3 + k];
+        for (int ea = e0; ea < e1; ea++) {
+            if ((round && !e_inl[ea]) || kf_fidx[e_kf[ea]] != fi) continue;
+            double era[2], wa, e2a, Jca[12], Jpa[6];
+            if (!ba_edge_lin(prm, huber2, pose + (size_t)e_kf[ea] * 12, Xp, e_xy[(size_t)ea * 2], e_xy[(size_t)ea * 2 + 1], e_info[ea], era, &wa, &e2a, Jca, Jpa))
+                continue;
+            if (diag) {
+                ba_camera_terms(Jca, wa, era, a, a + 36);
+                for (int k = 0; k < 6; k++) a[42 + k] += wa * (Jca[k] * Jca[k] + Jca[6 + k] * Jca[6 + k]);
+                if (!fixedp) ba_schur_rhs(Jca, Jpa, wa, inv, g, a + 36);
+            }
+            if (fixedp) continue;
+            for (int eb = e0; eb < e1; eb++) {
+                if ((round && !e_inl[eb]) || kf_fidx[e_kf[eb]] != fj) continue;
+                double erb[2], wb, e2b, Jcb[12], Jpb[6];
+                if (!ba_edge_lin(prm, huber2, pose + (size_t)e_kf[eb] * 12, Xp, e_xy[(size_t)eb * 2], e_xy[(size_t)eb * 2 + 1], e_info[eb], erb, &wb, &e2b, Jcb,
+                                 Jpb))
+                    continue;
+                ba_schur_pair(Jca, Jpa, wa, Jcb, Jpb, wb, inv, a);
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int k = 0; k < 48; k++) {
+        const double v = ba_wave_sum(a[k]);
+        if (lane == 0) red[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 42) {
+        const int k = threadIdx.x;
+        double s = red[0][k];
+        for (int w = 1; w < NW; w++) s += red[w][k];
+        if (k < 36) {
+            const int rr = k / 6, cc = k % 6;
+            if (diag && rr == cc) {
+                double d = red[0][42 + rr];
+                for (int w = 1; w < NW; w++) d += red[w][42 + rr];
+                s += lambda * d;
+            }
+            S[(size_t)(6 * fi + rr) * BA_MAX_DIM + 6 * fj + cc] = s;
+            if (!diag) S[(size_t)(6 * fj + cc) * BA_MAX_DIM + 6 * fi + rr] = s;
+        } else if (diag) {
+            S[(size_t)BA_MAX_DIM * BA_MAX_DIM + 6 * fi + (k - 36)] = s;
+        }
+    }
+}
+
+// one workgroup: S (lower triangle, packed in LDS) -> Cholesky factor, each entry one thread's dot product in k order as ba_chol_factor
+// forms it; substitution; the trial poses.  A system that is not positive definite ends the round.
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_solve(int round, const double* __restrict__ S, double* __restrict__ dc, const double* __restrict__ poseC,
+                                                       double* __restrict__ poseT, BaRes* __restrict__ res) {
+    __shared__ double L[BA_TRI_N];
+    __shared__ double bl[BA_MAX_DIM], x[BA_MAX_DIM];
+    __shared__ int bad;
+    if (!ba_active(res, round)) return;
+    const int tid = threadIdx.x, nf = res->n_free, n = 6 * nf;
+    for (int i = 0; i < n; i++)
+        for (int j = tid; j <= i; j += BA_BLOCK) L[BA_TRI(i, j)] = S[(size_t)i * BA_MAX_DIM + j];
+    for (int i = tid; i < n; i += BA_BLOCK) bl[i] = S[(size_t)BA_MAX_DIM * BA_MAX_DIM + i];
+    if (tid == 0) bad = 0;
+    __syncthreads();
+    for (int j = 0; j < n; j++) {
+        if (tid == 0) {
+            double s = L[BA_TRI(j, j)];
+            for (int k = 0; k < j; k++) s -= L[BA_TRI(j, k)] * L[BA_TRI(j, k)];
+            if (!(s > 0.0) || !isfinite(s)) bad = 1; else L[BA_TRI(j, j)] = sqrt(s);
+        }
+        __syncthreads();
+        if (bad) break;
+        const double d = L[BA_TRI(j, j)];
+        for (int i = j + 1 + tid; i < n; i += BA_BLOCK) {
+            double v = L[BA_TRI(i, j)];
+            for (int k = 0; k < j; k++) v -= L[BA_TRI(i, k)] * L[BA_TRI(j, k)];
+            L[BA_TRI(i, j)] = v / d;
+        }
+        __syncthreads();
+    }
+    if (bad) {
+        if (tid == 0) { res->done[round] = 1; res->step_ok = 0; }
+        return;
+    }
+    if (tid == 0) {
+        ba_chol_subst(n, L, bl, x);
+        double mx = 0.0;
+        for (int i = 0; i < n; i++) mx = fmax(mx, fabs(x[i]));
+        res->upd_c = mx;
+        res->step_ok = 1;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += BA_BLOCK) dc[i] = x[i];
+    if (tid < nf) {
+        const int pos = res->free_pos[tid];
+        double d[6], T[12], T2[12];
+        for (int k = 0; k < 6; k++) d[k] = x[6 * tid + k];
+        for (int k = 0; k < 12; k++) T[k] = poseC[(size_t)pos * 12 + k];
+        ba_pose_update(d, T, T2);
+        for (int k = 0; k < 12; k++) poseT[(size_t)pos * 12 + k] = T2[k];
+    }
+}
+
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_back(BaPrm prm, int round, const int32_t* __restrict__ eoff, const double* __restrict__ X,
+                                                      const int32_t* __restrict__ e_kf, const float* __restrict__ e_xy, const double* __restrict__ e_info,
+                                                      const uint8_t* __restrict__ e_inl, const int32_t* __restrict__ kf_fidx, const double* __restrict__ poseC,
+                                                      const double* __restrict__ poseT, const double* __restrict__ Vi, const double* __restrict__ gp,
+                                                      const uint8_t* __restrict__ pfix, const double* __restrict__ dc, double* __restrict__ Xt,
+                                                      double* __restrict__ pt, double* __restrict__ pu, const BaRes* __restrict__ res) {
+    if (!ba_active(res, round) || !res->step_ok) return;
+    const int r = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (r >= res->n_local) return;
+    const double huber2 = round == 0 ? prm.chi2 : 0.0;
+    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
+    const int e0 = eoff[r], e1 = eoff[r + 1];
+    double dp[3] = {0, 0, 0};
+    if (!pfix[r]) {
+        double g[3], inv[6];
+        for (int k = 0; k < 3; k++) g[k] = gp[(size_t)r * 3 + k];
+        for (int k = 0; k < 6; k++) inv[k] = Vi[(size_t)r * 6 + k];
+        for (int e = e0; e < e1; e++) {
+            if (round && !e_inl[e]) continue;
+            const int f = kf_fidx[e_kf[e]];
+            if (f < 0) continue;
+            double er[2], w, e2, Jc[12], Jp[6];
+            if (!ba_edge_lin(prm, huber2, poseC + (size_t)e_kf[e] * 12, Xp, e_xy[(size_t)e * 2], e_xy[(size_t)e * 2 + 1], e_info[e], er, &w, &e2, Jc, Jp)) continue;
+            ba_back_edge(Jc, Jp, w, dc + 6 * f, g);
+        }
+        ba_sym3_mul(inv, g, dp);
+    }
+    const double Xn[3] = {Xp[0] + dp[0], Xp[1] + dp[1], Xp[2] + dp[2]};
+    double cost = 0.0;
+    for (int e = e0; e < e1; e++) {
+        if (round && !e_inl[e]) continue;
+        double er[2], zc;
+        if (!ba_residual(prm.K, poseT + (size_t)e_kf[e] * 12, Xn, e_xy[(size_t)e * 2], e_xy[(size_t)e * 2 + 1], er, &zc)) continue;
+        cost += ba_rho(e_info[e] * (er[0] * er[0] + er[1] * er[1]), huber2);
+    }
+    for (int k = 0; k < 3; k++) Xt[(size_t)r * 3 + k] = Xn[k];
+    pt[r] = cost;
+    pu[r] = fmax(fabs(dp[0]), fmax(fabs(dp[1]), fabs(dp[2])));
+}
+
+// one workgroup: current and trial cost, the largest update; accept (the trial becomes the state, lambda / 10) or reject (lambda * 10);
+// the round ends at an update below 1e-10 or lambda above 1e8
+__global__ __launch_bounds__(1024) void k_ba_accept(int round, const double* __restrict__ pc, const double* __restrict__ pt, const double* __restrict__ pu,
+                                                    double* __restrict__ X, const double* __restrict__ Xt, double* __restrict__ poseC,
+                                                    double* __restrict__ poseT, BaRes* __restrict__ res) {
+    __shared__ double lds[16];
+    __shared__ int acc;
+    if (!ba_active(res, round) || !res->step_ok) return;
+    const int n = res->n_local, tid = threadIdx.x;
+    double c0 = 0.0, c1 = 0.0, mu = 0.0;
+    for (int r = tid; r < n; r += 1024) { c0 += pc[r]; c1 += pt[r]; mu = fmax(mu, pu[r]); }
+    c0 = ba_block_sum(c0, lds);
+    c1 = ba_block_sum(c1, lds);
+    mu = ba_block_max(mu, lds);
+    if (tid == 0) {
+        const bool ok = c1 < c0;
+        acc = ok;
+        const double upd = fmax(mu, res->upd_c);
+        const double lam = ok ? res->lambda / 10.0 : res->lambda * 10.0;
+        res->lambda = lam;
+        res->steps[round]++;
+        res->accepted[round] += ok;
+        res->step_ok = 0;
+        if (upd < 1e-10 || lam > 1e8) res->done[round] = 1;
+    }
+    __syncthreads();
+    const int nf = res->n_free;
+    if (acc) {
+        for (int k = tid; k < n * 3; k += 1024) X[k] = Xt[k];
+        for (int k = tid; k < nf * 12; k += 1024) { const size_t o = (size_t)res->free_pos[k / 12] * 12 + k % 12; poseC[o] = poseT[o]; }
+    } else {
+        for (int k = tid; k < nf * 12; k += 1024) { const size_t o = (size_t)res->free_pos[k / 12] * 12 + k % 12; poseT[o] = poseC[o]; }
+    }
+}
+
+// the results into the map: xyz of the local points, kP = K [R | t] of the free keyframes; the optional outputs
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_write(BaPrm prm, int n_pts, int n_obs_edges, const int32_t* __restrict__ loc, const int32_t* __restrict__ lrank,
+                                                       const double* __restrict__ X, float* __restrict__ xyz, double* __restrict__ pout,
+                                                       const int32_t* __restrict__ e_obs, const uint8_t* __restrict__ e_inl, uint8_t* __restrict__ einl,
+                                                       const int32_t* __restrict__ pos_slot, const double* __restrict__ poseC, double* __restrict__ kP,
+                                                       const BaRes* __restrict__ res) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    const bool run = res->run;
+    if (i < n_pts) {
+        const bool local = run && loc[i];
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int k = 0; k < 3; k++) {
+            const double v = local ? X[(size_t)lrank[i] * 3 + k] : nan;
+            if (pout) pout[(size_t)i * 3 + k] = v;
+            if (local) xyz[(size_t)i * 3 + k] = (float)v;
+        }
+    }
+    if (!run) return;
+    if (i < res->n_edges && i < n_obs_edges) einl[e_obs[i]] = e_inl[i] ? 1 : 2;
+    if (i < res->n_free && res->accepted[0] + res->accepted[1] > 0) {   // (no accepted step: the poses are the given ones, kP stays)
+        const int pos = res->free_pos[i];
+        double R[9], t[3], P[12];
+        for (int j = 0; j < 3; j++) {
+            for (int l = 0; l < 3; l++) R[j * 3 + l] = poseC[(size_t)pos * 12 + j * 4 + l];
+            t[j] = poseC[(size_t)pos * 12 + j * 4 + 3];
+        }
+        pnp_projection(prm.K, R, t, P);
+        for (int k = 0; k < 12; k++) kP[(size_t)pos_slot[pos] * 12 + k] = P[k];
+    }
+}
+
+extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* poses, const mo_map_ba_params* prm, mo_map_ba_out* out) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (!K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    const int n_kf = (int)m->pos_slot.size();
+    if (n_kf > 0 && !poses) return mo_fail(c, MO_ERR_ARG, "poses is NULL");
+    if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
+    if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
+    if (!(prm->chi2 >= 0.0) || !std::isfinite(prm->chi2)) return mo_fail(c, MO_ERR_ARG, "chi2 must be finite and >= 0");
+    for (int r = 0; r < 2; r++)
+        if (prm->max_steps[r] < 0 || prm->max_steps[r] > 100) return mo_fail(c, MO_ERR_ARG, "max_steps must be in 0 .. 100");
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(K[i])) return mo_fail(c, MO_ERR_ARG, "K must be finite");
+    for (size_t i = 0; i < (size_t)n_kf * 12; i++)
+        if (!std::isfinite(poses[i])) return mo_fail(c, MO_ERR_ARG, "poses must be finite");
+    const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
+    if (n_kf - std::max(lo_pos, 1) > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a window of at most 16");
+    HIPCHK(c, hipSetDevice(c->device));
+    HostClock clk(c);
+    for (int i = 0; i < 3; i++) out->cost[i] = 0.0;
+    out->lambda = 0.0;
+    out->n_free = out->n_fixed = out->n_local = out->n_edges = out->n_inliers = out->ok = 0;
+    for (int r = 0; r < 2; r++) { out->steps[r] = 0; out->accepted[r] = 0; }
+    const size_t np = (size_t)m->n_pts, no = (size_t)m->n_obs;
+    if (out->poses_out && n_kf) std::memcpy(out->poses_out, poses, (size_t)n_kf * 96);
+    if (out->kf_state) for (int i = 0; i < n_kf; i++) out->kf_state[i] = 0;
+    if (out->edge_inlier && no) std::memset(out->edge_inlier, 0, no);
+    if (out->points_out) for (size_t i = 0; i < np * 3; i++) out->points_out[i] = NAN;
+    if (n_kf == 0 || np == 0 || no == 0) return MO_OK;   // an empty map: nothing runs, not an error
+    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    if (!m->ba) m->ba = new BaBufs();
+    BaBufs& b = *m->ba;
+    int rc;
+    if ((rc = reserve(c, b.loc, b.loc_bytes, np * 4)) || (rc = reserve(c, b.ecnt, b.ecnt_bytes, np * 4)) || (rc = reserve(c, b.lrank, b.lrank_bytes, np * 4)) ||
+        (rc = reserve(c, b.ebase, b.ebase_bytes, np * 4)) || (rc = reserve(c, b.lpt, b.lpt_bytes, np * 4)) || (rc = reserve(c, b.eoff, b.eoff_bytes, (np + 1) * 4)) ||
+        (rc = reserve(c, b.pn, b.pn_bytes, np * 4)) || (rc = reserve(c, b.pfix, b.pfix_bytes, np)) || (rc = reserve(c, b.X, b.X_bytes, np * 24)) ||
+        (rc = reserve(c, b.Xt, b.Xt_bytes, np * 24)) || (rc = reserve(c, b.Vi, b.Vi_bytes, np * 48)) || (rc = reserve(c, b.gp, b.gp_bytes, np * 24)) ||
+        (rc = reserve(c, b.pc, b.pc_bytes, np * 8)) || (rc = reserve(c, b.pt, b.pt_bytes, np * 8)) || (rc = reserve(c, b.pu, b.pu_bytes, np * 8)) ||
+        (rc = reserve(c, b.e_kf, b.e_kf_bytes, no * 4)) || (rc = reserve(c, b.e_obs, b.e_obs_bytes, no * 4)) || (rc = reserve(c, b.e_xy, b.e_xy_bytes, no * 8)) ||
+        (rc = reserve(c, b.e_info, b.e_info_bytes, no * 8)) || (rc = reserve(c, b.e_inl, b.e_inl_bytes, no)) || (rc = reserve(c, b.einl, b.einl_bytes, no)) ||
+        (rc = reserve(c, b.kf_edge, b.kf_edge_bytes, (size_t)n_kf * 4)) || (rc = reserve(c, b.kf_fidx, b.kf_fidx_bytes, (size_t)n_kf * 4)) ||
+        (rc = reserve(c, b.poseC, b.poseC_bytes, (size_t)n_kf * 96)) || (rc = reserve(c, b.poseT, b.poseT_bytes, (size_t)n_kf * 96)))
+        return rc;
+    if (out->points_out && (rc = reserve(c, b.pout, b.pout_bytes, np * 24))) return rc;
+    if (!b.res) {
+        HIPCHK(c, hipMalloc((void**)&b.res, sizeof(BaRes)));
+        HIPCHK(c, hipHostMalloc((void**)&b.h_res, sizeof(BaRes), hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&b.S, (size_t)(BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM) * 8));
+    }
+    if ((rc = upload_pos_slot(m))) return rc;
+    mo_stage_begin(c);
+    HIPCHK(c, hipMemcpyAsync(b.poseC, poses, (size_t)n_kf * 96, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.poseT, b.poseC, (size_t)n_kf * 96, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.kf_edge, 0, (size_t)n_kf * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.einl, 0, no, c->stream));
+    BaPrm p;
+    for (int i = 0; i < 9; i++) p.K[i] = K[i];
+    p.sf = prm->scale_factor; p.chi2 = prm->chi2; p.n_kf = n_kf; p.lo_pos = lo_pos;
+    const MapPts& src = m->P[m->cur];
+    const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
+    const unsigned wblocks = (unsigned)((std::max(np, no) + BA_BLOCK - 1) / BA_BLOCK);
+    double* dcv = b.S + BA_MAX_DIM * BA_MAX_DIM + BA_MAX_DIM;
+    hipLaunchKernelGGL(k_ba_init, dim3(1), dim3(64), 0, c->stream, b.res);
+    hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, lo_pos, b.loc, b.ecnt, b.kf_edge);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, (int32_t*)((char*)b.res + offsetof(BaRes, n_local))))) return rc;
+    if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, (int32_t*)((char*)b.res + offsetof(BaRes, n_edges))))) return rc;
+    hipLaunchKernelGGL(k_ba_setup, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, b.kf_edge, b.kf_fidx, b.res);
+    hipLaunchKernelGGL(k_ba_edges, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, m->kkps, m->row, p.sf, b.loc, b.lrank,
+                       b.ebase, b.lpt, b.eoff, b.X, b.e_kf, b.e_obs, b.e_xy, b.e_info, b.e_inl, b.res);
+    hipLaunchKernelGGL(k_ba_cost, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, 0, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.poseC, b.pc, b.pn, b.res);
+    hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(1024), 0, c->stream, 0, b.pc, b.pn, b.res);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "ba_prep");
+    for (int r = 0; r < 2; r++) {
+        for (int s = 0; s < prm->max_steps[r]; s++) {
+            hipLaunchKernelGGL(k_ba_lin, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, r, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.poseC, b.Vi, b.gp,
+                               b.pfix, b.pc, b.res);
+            hipLaunchKernelGGL(k_ba_pair, dim3(BA_MAX_PAIRS), dim3(BA_BLOCK), 0, c->stream, p, r, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.kf_fidx, b.poseC,
+                               b.Vi, b.gp, b.pfix, b.S, b.res);
+            hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(BA_BLOCK), 0, c->stream, r, b.S, dcv, b.poseC, b.poseT, b.res);
+            hipLaunchKernelGGL(k_ba_back, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, r, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.kf_fidx, b.poseC,
+                               b.poseT, b.Vi, b.gp, b.pfix, dcv, b.Xt, b.pt, b.pu, b.res);
+            hipLaunchKernelGGL(k_ba_accept, dim3(1), dim3(1024), 0, c->stream, r, b.pc, b.pt, b.pu, b.X, b.Xt, b.poseC, b.poseT, b.res);
+        }
+        hipLaunchKernelGGL(k_ba_cost, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, r + 1, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.poseC, b.pc, b.pn,
+                           b.res);
+        hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(1024), 0, c->stream, r + 1, b.pc, b.pn, b.res);
+        HIPCHK(c, hipGetLastError());
+        mo_stage_mark(c, r ? "ba_round1" : "ba_round0");
+    }
+    hipLaunchKernelGGL(k_ba_write, dim3(wblocks), dim3(BA_BLOCK), 0, c->stream, p, (int)np, (int)no, b.loc, b.lrank, b.X, src.xyz,
+                       out->points_out ? b.pout : (double*)nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.poseC, m->kP, b.res);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "ba_write");
+    std::vector<int32_t> fidx(out->kf_state ? (size_t)n_kf : 0);
+    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(BaRes), hipMemcpyDeviceToHost, c->stream));
+    if (out->poses_out) HIPCHK(c, hipMemcpyAsync(out->poses_out, b.poseC, (size_t)n_kf * 96, hipMemcpyDeviceToHost, c->stream));
+    if (out->edge_inlier) HIPCHK(c, hipMemcpyAsync(out->edge_inlier, b.einl, no, hipMemcpyDeviceToHost, c->stream));
+    if (out->points_out) HIPCHK(c, hipMemcpyAsync(out->points_out, b.pout, np * 24, hipMemcpyDeviceToHost, c->stream));
+    if (out->kf_state) HIPCHK(c, hipMemcpyAsync(fidx.data(), b.kf_fidx, (size_t)n_kf * 4, hipMemcpyDeviceToHost, c->stream));
+    clk.enqueued();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    clk.waited();
+    const BaRes& r = *b.h_res;
+    if (!r.run) return MO_OK;   // no free keyframe with an edge, or no local point
+    out->n_local = r.n_local;
+    for (int i = 0; i < 3; i++) out->cost[i] = r.cost[i];
+    out->lambda = r.lambda;
+    out->n_free = r.n_free; out->n_fixed = r.n_fixed; out->n_edges = r.n_edges; out->n_inliers = r.n_inliers;
+    for (int k = 0; k < 2; k++) { out->steps[k] = r.steps[k]; out->accepted[k] = r.accepted[k]; }
+    if (out->kf_state) for (int i = 0; i < n_kf; i++) out->kf_state[i] = fidx[i] >= 0 ? 2 : fidx[i] == BA_KF_FIXED ? 1 : 0;
+    out->ok = r.n_inliers >= prm->min_inliers;
+    return MO_OK;
+}
+
+// ---- mo_map_add_observations ------------------------------------------------------------------------------------------------------
+// entry i claims its point: the lowest i wins (integer minimum)
+__global__ __launch_bounds__(BA_BLOCK) void k_obs_claim(const int32_t* __restrict__ pt, int n, int n_pts, int32_t* __restrict__ claim) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int p = pt[i];
+    if (p >= 0 && p < n_pts) atomicMin(claim + p, i);
+}
+
+// one thread per point: a claimed point that has no valid observation in kf_pos yet gains one; cnt = its new observation count
+__global__ __launch_bounds__(BA_BLOCK) void k_obs_count(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                                        int kf_pos, int32_t* __restrict__ claim, int32_t* __restrict__ cnt) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i >= n_pts) return;
+    const int o0 = src.off[i], o1 = src.off[i + 1];
+    int add = claim[i] != INT_MAX;
+    if (add) {
+        int pos, s, kp;
+        for (int o = o0; o < o1; o++)   // (the next keyframe's position names nothing yet: its entries are compared as stored)
+            if (kf_pos == n_kf ? src.okf[o] == kf_pos : (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp) && pos == kf_pos)) { add = 0; break; }
+        if (!add) claim[i] = INT_MAX;
+    }
+    cnt[i] = o1 - o0 + add;
+}
+
+// every field of every point into the other copy, the observations at their new offsets, the new one behind them
+__global__ __launch_bounds__(BA_BLOCK) void k_obs_scatter(MapPts src, MapPts dst, int n_pts, const int32_t* __restrict__ claim, const int32_t* __restrict__ base,
+                                                          const int32_t* __restrict__ total, int kf_pos, const int32_t* __restrict__ row,
+                                                          int32_t* __restrict__ st) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i == 0) { dst.off[n_pts] = *total; st[ST_NPTS] = n_pts; st[ST_NOBS] = *total; }   // (the next call's live counts)
+    if (i >= n_pts) return;
+    for (int k = 0; k < 3; k++) { dst.xyz[(size_t)i * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)i * 3 + k] = src.col[(size_t)i * 3 + k]; }
+    dst.id[i] = src.id[i]; dst.dkf[i] = src.dkf[i]; dst.drow[i] = src.drow[i];
+    const int o0 = src.off[i], o1 = src.off[i + 1], ob = base[i];
+    dst.off[i] = ob;
+    for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; }
+    const int cl = claim[i];
+    if (cl != INT_MAX) { dst.okf[ob + o1 - o0] = kf_pos; dst.okp[ob + o1 - o0] = row[cl]; }
+}
+
+extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32_t* point, const int32_t* row) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (n < 0 || (n > 0 && (!point || !row))) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    const int n_kf = (int)m->pos_slot.size();
+    if (kf_pos < 0 || kf_pos > n_kf) return mo_fail(c, MO_ERR_ARG, "kf_pos must be a keyframe position, or the number of keyframes for the next one");
+    if (n == 0 || m->n_pts == 0) return MO_OK;
+    if (m->n_pts > INT32_MAX / 2 || m->n_obs + n > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!m->ba) m->ba = new BaBufs();
+    BaBufs& b = *m->ba;
+    const size_t np = (size_t)m->n_pts;
+    int rc;
+    if ((rc = reserve(c, b.ao_pt, b.ao_pt_bytes, (size_t)n * 4)) || (rc = reserve(c, b.ao_row, b.ao_row_bytes, (size_t)n * 4)) ||
+        (rc = reserve(c, b.ao_claim, b.ao_claim_bytes, np * 4)) || (rc = reserve(c, b.ao_cnt, b.ao_cnt_bytes, np * 4)) ||
+        (rc = reserve(c, b.ao_base, b.ao_base_bytes, np * 4)))
+        return rc;
+    if (!b.ao_total) HIPCHK(c, hipMalloc((void**)&b.ao_total, 16));
+    const size_t new_obs = (size_t)m->n_obs + std::min<size_t>((size_t)n, np);
+    if ((rc = map_pts_reserve(m, m->cur ^ 1, np, new_obs, false))) return rc;
+    if ((rc = upload_pos_slot(m))) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.ao_pt, point, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.ao_row, row, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.ao_claim, INT_MAX, np, c->stream));
+    const MapPts& src = m->P[m->cur];
+    const MapPts& dst = m->P[m->cur ^ 1];
+    const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
+    hipLaunchKernelGGL(k_obs_claim, dim3((unsigned)((n + BA_BLOCK - 1) / BA_BLOCK)), dim3(BA_BLOCK), 0, c->stream, b.ao_pt, n, (int)np, b.ao_claim);
+    hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, kf_pos, b.ao_claim, b.ao_cnt);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = map_scan_excl(m, b.ao_cnt, b.ao_base, (int)np, b.ao_total))) return rc;
+    hipLaunchKernelGGL(k_obs_scatter, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, dst, (int)np, b.ao_claim, b.ao_base, b.ao_total, kf_pos, b.ao_row, m->st);
+    HIPCHK(c, hipGetLastError());
+    int32_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, b.ao_total, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    m->cur ^= 1;
+    m->n_obs = total;
+    return MO_OK;
+}

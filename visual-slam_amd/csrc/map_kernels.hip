@@ -82,6 +82,8 @@ static int scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t*
     return MO_OK;
 }
 
+int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total) { return scan_excl(m, in, out, n, d_total); }
+
 // ---- growth: the F-RANSAC inliers of one keyframe pair, in query order, onto the end of the map (local_mapper.py:150-187) --------
 // One block of 1024 threads walks the query keypoints in tiles (ballot + block scan); the map's live counts come from the status block.
 __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__ inl, const int32_t* __restrict__ midx, const float* __restrict__ gpts,
@@ -296,6 +298,8 @@ static int pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep
     return MO_OK;
 }
 
+int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) { return pts_reserve(m, which, pcap, ocap, keep); }
+
 // kkps / kdesc / kcnt hold one slot more than kslots: the spare slot (index kslots) mo_map_relocalize stages its query in, so that
 // one counts array serves both sides of its keyframe matching
 int kf_reserve(mo_map* m, int rows, int slots) {
@@ -377,6 +381,7 @@ extern "C" void mo_map_destroy(mo_map* m) {
     if (m->h_stat) hipHostFree(m->h_stat);
     if (m->h_rl) hipHostFree(m->h_rl);
     map_track_free(m);
+    map_ba_free(m);
     delete m;
 }
 

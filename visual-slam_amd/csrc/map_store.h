@@ -1,5 +1,5 @@
-// map_store.h -- the device-resident map (mo_map) shared by map_kernels.hip (growth, cull, relocalization) and map_track.hip
-// (tracking against the map): the stores, their scratch and the helpers that grow them.  Private to the library.
+// map_store.h -- the device-resident map (mo_map) shared by map_kernels.hip (growth, cull, relocalization), map_track.hip
+// (tracking against the map) and map_ba.hip (bundle adjustment): the stores, their scratch and the helpers that grow them.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -18,6 +18,7 @@ struct MapPts {
 
 struct RelocRes;  // per-call results of mo_map_relocalize (map_kernels.hip)
 struct TrackBufs; // scratch of mo_map_track (map_track.hip)
+struct BaBufs;    // scratch of mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -63,6 +64,7 @@ struct mo_map {
     int32_t* rl_qpt = nullptr; uint8_t* rl_qinl = nullptr; size_t rl_qpt_bytes = 0, rl_qinl_bytes = 0;  // [row] per query keypoint
     RelocRes* rl_res = nullptr; RelocRes* h_rl = nullptr;                     // device / pinned
     TrackBufs* tk = nullptr;                                                   // tracking (mo_map_track), made on first use
+    BaBufs* ba = nullptr;                                                      // bundle adjustment (map_ba.hip), made on first use
 };
 
 template <class T> static int reserve(mo_ctx* c, T*& p, size_t& have, size_t need) {
@@ -116,5 +118,10 @@ __device__ __forceinline__ int block_excl_scan(int v, int* lds_waves, int* total
 // position -> slot table on the device
 int kf_reserve(mo_map* m, int rows, int slots);
 int upload_pos_slot(mo_map* m);
+// map_kernels.hip: the device-wide exclusive scan of int32 (total into *d_total) and the growth of one copy of the map store
+int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total);
+int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
 // map_track.hip: frees the tracking scratch (mo_map_destroy)
 void map_track_free(mo_map* m);
+// map_ba.hip: frees the bundle-adjustment scratch (mo_map_destroy)
+void map_ba_free(mo_map* m);

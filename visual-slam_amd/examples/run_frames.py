@@ -24,6 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
+       [--map PATH [--relocalize] [--track-map [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -119,6 +120,9 @@ def main(argv=None):
                     "device map (LocalMapper.relocalize) and go on tracking from it")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
+    ap.add_argument("--local-ba", action="store_true", help="with --map --track-map: a tracked frame that becomes a keyframe hands its matches to "
+                    "the map (add_keyframe(tracked=)), and local bundle adjustment (LocalMapper.bundle_adjust) runs after it")
+    ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
@@ -140,7 +144,10 @@ def main(argv=None):
         ap.error("--relocalize needs --map")
     if args.track_map and not args.map:
         ap.error("--track-map needs --map")
+    if args.local_ba and not args.track_map:
+        ap.error("--local-ba needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
+    n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
@@ -171,7 +178,20 @@ def main(argv=None):
             recent[:] = recent[-1:] + [T]
             poses.append((T[:3, :3], T[:3, 3:4]))
             if idx % args.keyframe_every == 0:
-                mapper.add_keyframe(frame, kps, desc, T)
+                if args.local_ba:
+                    mapper.add_keyframe(frame, kps, desc, T, tracked=(info["point"], info["inlier"]))
+                    ba_ok, ba = mapper.bundle_adjust(window=args.ba_window)
+                    n_ba[0] += 1
+                    n_ba[1] += ba_ok
+                    print("frame %d: bundle adjust %s, %d free + %d fixed keyframes, %d points, %d of %d edges inliers, cost %.4g -> %.4g, steps %s"
+                          % (idx, "ok" if ba_ok else "not ok", ba["n_free"], ba["n_fixed"], ba["n_local"], ba["n_inliers"], ba["n_edges"],
+                             ba["cost"][0], ba["cost"][2], ba["steps"]))
+                    if ba["n_free"] and mapper.keyframes[-1]["descriptors"] is desc:   # tracking goes on from the refined pose of this keyframe
+                        T = mapper.keyframes[-1]["pose"].copy()
+                        ref_pose = T
+                        recent[-1] = T
+                else:
+                    mapper.add_keyframe(frame, kps, desc, T)
         return ok
 
     def relocalize(frame, kps, desc, idx):
@@ -253,6 +273,8 @@ def main(argv=None):
     if mapper is not None:
         mapper.save_map()
         print("map statistics: %s" % mapper.get_map_statistics())
+        if args.local_ba:
+            print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
     return state, poses, n_map
 
 

@@ -103,6 +103,16 @@ class MapTrackOut(C.Structure):
                 ("n_pass_run", C.c_int32), ("n_local", C.c_int32), ("ok", C.c_int32), ("from_token", C.c_int32)]
 
 
+class MapBaParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("min_inliers", C.c_int32), ("max_steps", C.c_int32 * 2), ("scale_factor", C.c_double), ("chi2", C.c_double)]
+
+
+class MapBaOut(C.Structure):
+    _fields_ = [("poses_out", C.c_void_p), ("kf_state", C.c_void_p), ("edge_inlier", C.c_void_p), ("points_out", C.c_void_p),
+                ("cost", C.c_double * 3), ("lambda_", C.c_double), ("n_free", C.c_int32), ("n_fixed", C.c_int32), ("n_local", C.c_int32),
+                ("n_edges", C.c_int32), ("n_inliers", C.c_int32), ("steps", C.c_int32 * 2), ("accepted", C.c_int32 * 2), ("ok", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -184,6 +194,8 @@ SIGNATURES = {
     "mo_map_relocalize": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_track": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
+    "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

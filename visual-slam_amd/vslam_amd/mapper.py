@@ -130,7 +130,10 @@ class LocalMapper:
         self.output_path = output_path
 
     # ---- the reference's per-keyframe step ------------------------------------------------------------------------------------
-    def add_keyframe(self, image, keypoints, descriptors, pose):
+    def add_keyframe(self, image, keypoints, descriptors, pose, tracked=None):
+        """tracked: (point, inlier) as track_local_map returned them for this very frame against the map as it stands; the inlier
+        matches become observations of their map points in this keyframe (add_observations) before the growth step and the cull, and
+        the co-visibility graph gets the shared-point counts.  None: the reference's step alone."""
         from orbslam2.types import keypoints_to_array
         from orbslam2.utils import compute_projection_matrix
         kf = _Keyframe({"id": len(self.keyframes), "image": image.copy(), "keypoints": keypoints, "descriptors": descriptors,
@@ -168,8 +171,13 @@ class LocalMapper:
         self._version += 1
         self._cache = None
         self._lists = None
+        shared = self._add_tracked(n_kf - 1, tracked) if tracked is not None else None
         rc = self.lib.mo_map_add_keyframe(self._h, C.byref(ref), V._ptr(P), V._ptr(img), img.shape[1], img.shape[0], ch, C.byref(prm), C.byref(out))
         self._rec_n.append(n)
+        if shared and rc == V.MO_OK:
+            for other_id, cnt in shared.items():
+                self.co_visibility_graph[other_id][kf["id"]] += cnt
+                self.co_visibility_graph[kf["id"]][other_id] += cnt
         n_before = self._n_points
         self._sync_size()
         if rc == V.MO_ERR_INDEX:
@@ -199,6 +207,86 @@ class LocalMapper:
             self._cull_keyframes(kf_len, kf_red)
         if self.save_every_keyframe:
             self._save_map()
+
+    # ---- tracked observations and bundle adjustment ---------------------------------------------------------------------------------
+    def _add_tracked(self, kf_pos, tracked):
+        """the inlier matches of a tracked frame as observations of keyframe position kf_pos (the keyframe being added); returns
+        {keyframe id: points shared with it} over the keyframes (positions before this one) the gaining points are observed in"""
+        point, inlier = tracked
+        point = np.asarray(point, np.int64).reshape(-1)
+        inlier = np.asarray(inlier).reshape(-1).astype(bool)
+        if len(point) != len(inlier):
+            raise ValueError("tracked: point and inlier must have one entry per keypoint")
+        pt = np.where(inlier, point, -1).astype(np.int32)
+        if not (pt >= 0).any() or self._n_points == 0:
+            return {}
+        a = self.arrays()
+        rows = np.flatnonzero((pt >= 0) & (pt < self._n_points))
+        gained = np.unique(pt[rows])                      # (the new keyframe holds no observation yet: every named point gains one)
+        self.add_observations(kf_pos, pt)
+        n_before = kf_pos                                 # keyframes in the store
+        off, okf = a["obs_off"], a["obs_kf"]
+        ent = np.concatenate([np.arange(off[i], off[i + 1]) for i in gained.tolist()]) if len(gained) else np.zeros(0, np.int64)
+        pos = okf[ent.astype(np.int64)].astype(np.int64)
+        pos = np.where(pos < 0, pos + n_before, pos)
+        pos = pos[(pos >= 0) & (pos < n_before)]
+        shared = {}
+        for p_, cnt in zip(*np.unique(pos, return_counts=True)):
+            shared[self.keyframes[int(p_)]["id"]] = int(cnt)
+        return shared
+
+    def add_observations(self, kf_position, point, row=None):
+        """Appends the observation (kf_position, row[i]) to map point point[i] (index into the map as it stands); row defaults to
+        0, 1, 2, ... (point has one entry per keypoint of that keyframe, -1: none).  Skipped: point < 0 or out of range, a point that
+        already has a valid observation in that keyframe; of two entries naming one point the first wins (mo_map_add_observations).
+        kf_position == len(keyframes) names the keyframe the next add_keyframe stores."""
+        pt = np.ascontiguousarray(np.asarray(point).reshape(-1), np.int32)
+        rw = np.arange(len(pt), dtype=np.int32) if row is None else np.ascontiguousarray(np.asarray(row).reshape(-1), np.int32)
+        if len(rw) != len(pt):
+            raise ValueError("point and row must have the same length")
+        self._check(self.lib.mo_map_add_observations(self._h, int(kf_position), len(pt), V._ptr(pt), V._ptr(rw)))
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+
+    def bundle_adjust(self, window=10, scale_factor=1.2, chi2=5.991, min_inliers=50, max_steps=(5, 10), want_points=False):
+        """Local bundle adjustment on the map as it stands (ORB-SLAM2's LocalBundleAdjustment; mo_map_bundle_adjust in
+        include/vslam_amd.h states the rules): the poses of the last `window` keyframes (0: all, at most 16, never the first) and the
+        positions of the points they see are refined together, the other keyframes seeing those points held fixed.  The refined poses
+        are written into kf["pose"] of the free keyframes (into the array), the map points move on the device.
+        Returns (ok, info): info holds n_free, n_fixed, n_local, n_edges, n_inliers, cost (3), steps / accepted per round, `free` and
+        `fixed` position lists, `edge_inlier` per observation entry (0 outside, 1 inlier, 2 outlier), `poses` [n_kf][3][4] and, with
+        want_points, `points` [n_points][3] f64 (NaN for points outside the problem)."""
+        n_kf = len(self.keyframes)
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        poses_out = poses.copy()
+        state = np.zeros(max(n_kf, 1), np.int32)
+        einl = np.zeros(max(self._n_obs if self._n_points else 0, 1), np.uint8)
+        pts = np.full((max(self._n_points, 1), 3), np.nan, np.float64) if want_points else None
+        ms = [int(v) for v in max_steps]
+        if len(ms) != 2:
+            raise ValueError("max_steps: one count per round")
+        prm = V.MapBaParams(int(window), int(min_inliers), (C.c_int32 * 2)(*ms), float(scale_factor), float(chi2))
+        out = V.MapBaOut(poses_out.ctypes.data, state.ctypes.data, einl.ctypes.data, pts.ctypes.data if want_points else None)
+        self._check(self.lib.mo_map_bundle_adjust(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        state = state[:n_kf]
+        free = np.flatnonzero(state == 2).tolist()
+        if out.n_free:
+            for i in free:
+                self.keyframes[i]["pose"][:3, :4] = poses_out[i].reshape(3, 4)
+            self._version += 1
+            self._cache = None
+        info = {"n_free": int(out.n_free), "n_fixed": int(out.n_fixed), "n_local": int(out.n_local), "n_edges": int(out.n_edges),
+                "n_inliers": int(out.n_inliers), "cost": [float(v) for v in out.cost], "steps": [int(v) for v in out.steps],
+                "accepted": [int(v) for v in out.accepted], "lambda": float(out.lambda_), "free": free,
+                "fixed": np.flatnonzero(state == 1).tolist(), "edge_inlier": einl[:self._n_obs if self._n_points else 0],
+                "poses": poses_out[:n_kf].reshape(n_kf, 3, 4)}
+        if want_points:
+            info["points"] = pts[:self._n_points]
+        return bool(out.ok), info
 
     def _cull_keyframes(self, kf_len, kf_red):
         """local_mapper.py:253-315 on the counts the device produced: list length and the listed ids whose first map point with
