@@ -165,9 +165,10 @@ def lm_step(K, T, X, E, use, fidx, n_free, h2, lam):
 
 
 def bundle_adjust(obs_off, obs_kf, obs_kp, counts, kf_xy, kf_oct, xyz, K, poses, window=10, scale_factor=1.2, chi2=5.991, min_inliers=50,
-                  max_steps=(5, 10)):
+                  max_steps=(5, 10), trace=None):
     """kf_xy [position] -> [rows][2] f32 keypoints, kf_oct [position] -> octaves, xyz [n][3] f32, poses [n_kf][3][4].  Returns the dict
-    LocalMapper.bundle_adjust's info holds (plus ok, xyz: the f32 positions after the call)."""
+    LocalMapper.bundle_adjust's info holds (plus ok, xyz: the f32 positions after the call).  trace: a list that receives (round, cost
+    before, cost of the trial, largest update) of every step, for tests that must know how close a decision was."""
     K = np.asarray(K, np.float64).reshape(3, 3)
     n_kf, n_pts, n_obs = len(counts), len(obs_off) - 1, int(obs_off[-1]) if len(obs_off) else 0
     poses = np.array(poses, np.float64).reshape(n_kf, 3, 4)
@@ -204,6 +205,8 @@ def bundle_adjust(obs_off, obs_kf, obs_kp, counts, kf_xy, kf_oct, xyz, K, poses,
             X2 = X + dp
             trial = _cost(K, T2, X2, E, use, h2)
             out["steps"][rnd] += 1
+            if trace is not None:
+                trace.append((rnd, cur, trial, float(max(np.abs(dc).max(), np.abs(dp).max()))))
             if trial < cur:
                 T, X = T2, X2
                 lam /= 10.0

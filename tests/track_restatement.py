@@ -90,8 +90,10 @@ def project(K, pose, xyz):
         return u / w, v / w, w
 
 
-def search(K, pose, xyz, rep, ref, kps, desc, w, h, radius, scale_factor=1.2, max_dist=100, ratio=0.8):
-    """one attempt of a pass: (point [nq], dist [nq], candidates).  kps: KP_DTYPE records of the frame."""
+def search(K, pose, xyz, rep, ref, kps, desc, w, h, radius, scale_factor=1.2, max_dist=100, ratio=0.8, octave_gate=True, scale_radius=True):
+    """one attempt of a pass: (point [nq], dist [nq], candidates).  kps: KP_DTYPE records of the frame.  octave_gate=False drops the
+    |octave - ref_octave| <= 1 condition, scale_radius=False searches every point at the octave-0 radius: wrong on purpose, for tests
+    that must show their inputs tell the rule from its absence."""
     nq = len(kps)
     point = np.full(nq, -1, np.int64)
     dist = np.full(nq, -1, np.int64)
@@ -106,8 +108,8 @@ def search(K, pose, xyz, rep, ref, kps, desc, w, h, radius, scale_factor=1.2, ma
         if not (u[i] >= 0 and u[i] < w and v[i] >= 0 and v[i] < h):
             continue
         n_cand += 1
-        r = radius * _power(scale_factor, ref[i])
-        q = np.flatnonzero((np.abs(kx - u[i]) < r) & (np.abs(ky - v[i]) < r) & (np.abs(ko - ref[i]) <= 1))
+        r = radius * (_power(scale_factor, ref[i]) if scale_radius else 1.0)
+        q = np.flatnonzero((np.abs(kx - u[i]) < r) & (np.abs(ky - v[i]) < r) & ((np.abs(ko - ref[i]) <= 1) | (not octave_gate)))
         if len(q) == 0:
             continue
         d = hamming(rep[i:i + 1], desc[q])[0]
@@ -149,12 +151,12 @@ def _exp_so3(w):
     return np.eye(3) + a * W + b * (W @ W)
 
 
-def refine(K, pose, X, x, octave, scale_factor=1.2, chi2=5.991):
+def refine(K, pose, X, x, octave, scale_factor=1.2, chi2=5.991, unit_information=False):
     """PoseOptimization with Gauss-Newton steps: (pose 4x4, inlier mask, inliers).  X [m][3] f64 (the map's f32 values), x [m][2] f64,
-    octave [m] of the frame keypoints."""
+    octave [m] of the frame keypoints.  unit_information=True weighs every match with 1 (wrong on purpose, as search's switches)."""
     K = np.asarray(K, np.float64).reshape(3, 3)
     T = np.array(pose, np.float64)
-    info = np.array([_info(scale_factor, o) for o in octave])
+    info = np.array([1.0 if unit_information else _info(scale_factor, o) for o in octave])
     inl = np.ones(len(X), bool)
     n_inl = len(X)
     for rnd in range(4):
@@ -197,25 +199,32 @@ def refine(K, pose, X, x, octave, scale_factor=1.2, chi2=5.991):
     return T, inl, n_inl
 
 
-def track(K, pose0, xyz, obs_off, obs_kf, obs_kp, kf_desc, kf_oct, kps, desc, w, h, window=10, radii=(15.0, 4.0), scale_factor=1.2,
-          max_dist=100, ratio=0.8, chi2=5.991, min_matches=20, min_inliers=30, refine_pose=True, poses=None):
-    """the whole call: per pass the search (with its retry) and the refinement.  poses: the pose each pass projects from, in place of
-    the previous pass's refinement (to restate one pass from the device's own pose)."""
+def local_map(obs_off, obs_kf, obs_kp, kf_desc, kf_oct, window=10):
+    """(rep, ref_octave, n_local) of the map for a window: everything track() derives before it sees the frame"""
     counts = [len(d) for d in kf_desc]
     obs = valid_observations(obs_off, obs_kf, obs_kp, counts)
     local = local_points(obs, len(counts), window)
     rep, ref = representatives(obs, kf_desc, kf_oct, local)
+    return rep, ref, int(local.sum())
+
+
+def track(K, pose0, xyz, obs_off, obs_kf, obs_kp, kf_desc, kf_oct, kps, desc, w, h, window=10, radii=(15.0, 4.0), scale_factor=1.2,
+          max_dist=100, ratio=0.8, chi2=5.991, min_matches=20, min_inliers=30, refine_pose=True, poses=None, octave_gate=True, scale_radius=True, local_map=None):
+    """the whole call: per pass the search (with its retry) and the refinement.  poses: the pose each pass projects from, in place of
+    the previous pass's refinement (to restate one pass from the device's own pose).  local_map: what local_map() returned for this
+    map and window, to restate several frames against one large map without deriving it again."""
+    rep, ref, n_local = local_map if local_map is not None else globals()["local_map"](obs_off, obs_kf, obs_kp, kf_desc, kf_oct, window)
     xyz = np.asarray(xyz, np.float32)
     pose = np.array(pose0, np.float64)
-    res = {"n_local": int(local.sum()), "passes": [], "ok": False, "pose": pose.copy()}
+    res = {"n_local": n_local, "passes": [], "ok": False, "pose": pose.copy()}
     for k, rad in enumerate(radii):
         if poses is not None:
             pose = np.array(poses[k], np.float64)
-        point, dist, nc = search(K, pose, xyz, rep, ref, kps, desc, w, h, rad, scale_factor, max_dist, ratio)
+        point, dist, nc = search(K, pose, xyz, rep, ref, kps, desc, w, h, rad, scale_factor, max_dist, ratio, octave_gate, scale_radius)
         used = rad
         if (point >= 0).sum() < min_matches:
             used = 2.0 * rad
-            point, dist, nc = search(K, pose, xyz, rep, ref, kps, desc, w, h, used, scale_factor, max_dist, ratio)
+            point, dist, nc = search(K, pose, xyz, rep, ref, kps, desc, w, h, used, scale_factor, max_dist, ratio, octave_gate, scale_radius)
         ps = {"point": point, "dist": dist, "cand": nc, "matches": int((point >= 0).sum()), "radius": used, "from": pose.copy()}
         res["passes"].append(ps)
         if ps["matches"] < min_matches:
