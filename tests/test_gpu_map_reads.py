@@ -444,3 +444,56 @@ def test_representative_ties_go_to_the_earlier_observation(name):
     assert hit >= 10
     assert ctx.dev_status() == 0
     m.close(); ctx.close()
+
+
+TINY = (2, 16, 16, 32)   # keyframe slots, rows per keyframe, map points, observations: the capacities of tests/test_gpu_mapper.py's tiny run
+
+
+def _bytes_of(x):
+    """every array and number below x, in order, as bytes"""
+    if isinstance(x, dict):
+        return [(k, _bytes_of(v)) for k, v in sorted(x.items())]
+    if isinstance(x, (list, tuple)):
+        return [_bytes_of(v) for v in x]
+    return None if x is None else np.asarray(x).tobytes()
+
+
+def _lifetime_pass(ctx, w, poses, xyz, frames):
+    """a map at tiny capacities, one call of each feature that keeps scratch of its own, the map destroyed; every output"""
+    m = build_map(ctx, w, poses=poses, xyz=xyz, capacity=TINY)
+    sizes = (w.n_kf0, max(len(d) for d in w.slot_desc), len(m.map_points), len(m.arrays()["obs_kf"]))
+    assert all(a > b for a, b in zip(sizes, TINY)), sizes   # every store outgrew what it was made with
+    (tk, td, pose0), (rk, rd), (point, row) = frames
+    out = {"track": m.track_local_map(tk, td, pose0, image_size=w.image_size), "reloc": m.relocalize(rk, rd)}
+    assert out["track"][2]["n_local"] > 0
+    out["ba"] = m.bundle_adjust(window=BA_WINDOW, max_steps=BA_STEPS, want_points=True)
+    assert out["ba"][1]["n_edges"] > 0
+    m._cache = None
+    out["after_ba"] = {k: v.copy() for k, v in m.arrays().items()}
+    m.add_observations(3, point, row)
+    out["after_add"] = {k: v.copy() for k, v in m.arrays().items()}
+    assert len(out["after_add"]["obs_kf"]) > len(out["after_ba"]["obs_kf"])
+    out["poses"] = [np.asarray(kf["pose"]).copy() for kf in m.keyframes]
+    m.close()
+    return _bytes_of(out)
+
+
+def test_map_lifetime_twice_in_one_context():
+    """(i) what the buffers' owners guard: the smallest world (448 points, 8 keyframes after the removal) built at capacities every store
+    outgrows, track, relocalize, bundle_adjust and add_observations once each (the three scratch structs made on first use), the map
+    destroyed - and all of it again in the same process and context.  The second pass equals the first bit for bit and the context
+    holds no error: nothing freed twice or too early, nothing of the first map read by the second."""
+    ctx = _ctx()
+    w = world("octave")
+    poses, xyz = perturbed(w)
+    T = pose_near(w, 4)
+    tk, td = w.track_query(T, octave_spread=2, seed=6, wrong=0.0)
+    rng = np.random.default_rng(8)
+    frames = ((tk, td, perturbed_pose(T)), w.reloc_query(3, pose_near(w, 3)),
+              (rng.integers(-5, len(w.obs) + 5, 300).astype(np.int32), rng.integers(0, 50, 300).astype(np.int32)))
+    first = _lifetime_pass(ctx, w, poses, xyz, frames)
+    second = _lifetime_pass(ctx, w, poses, xyz, frames)
+    assert first == second
+    assert ctx.lib.mo_last_error(ctx.h).decode() == ""
+    assert ctx.dev_status() == 0
+    ctx.close()

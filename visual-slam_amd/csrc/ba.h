@@ -18,7 +18,8 @@
 #define BA_MAX_DIM (6 * BA_MAX_FREE)      // unknowns of the reduced camera system
 #define BA_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))   // packed lower triangle, j <= i
 
-// information of an octave: 1 / scale_factor^(2 o), repeated products from 1.0 (negative octaves as 0), as mo_map_track's
+// information of an octave: 1 / scale_factor^(2 o), repeated products from 1.0 (negative octaves as 0); the one definition, for the
+// edges of the bundle adjustment and the matches of mo_map_track's refinement (map_track.hip)
 BA_HD double ba_info(double sf, int o) {
     const double sf2 = sf * sf;
     double s = 1.0;

@@ -3,7 +3,7 @@
 //
 // Chain of one bundle adjustment (one synchronisation, the copy-out; every decision - the gauge, accept / reject, the end of a round -
 // is a flag in BaRes that the later kernels read first):
-//   k_ba_mark      one thread per map point: valid edges read like the cull reads them, local-point flag, keyframes with edges
+//   k_ba_mark      one thread per map point: its valid edges (map_obs), local-point flag, keyframes with edges
 //   scans          local rank of every local point, first compact edge of every local point (the map's device-wide scan)
 //   k_ba_setup     one block: free / fixed keyframes and the gauge rule, free index of every position
 //   k_ba_edges     one thread per map point: its edges in CSR order into the compact edge arrays, its position as f64
@@ -21,7 +21,6 @@
 // -ffp-contract=off (Makefile): ba.h rounds on the device as in the host build of tests/native/ba_check.cpp.
 #include <climits>
 #include <cmath>
-#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -50,64 +49,28 @@ struct BaRes {
 
 struct BaBufs {
     // per map point
-    int32_t* loc = nullptr; int32_t* ecnt = nullptr; int32_t* lrank = nullptr; int32_t* ebase = nullptr;
-    size_t loc_bytes = 0, ecnt_bytes = 0, lrank_bytes = 0, ebase_bytes = 0;
-    double* pout = nullptr; size_t pout_bytes = 0;               // [point][3] the optional f64 output
+    DevBuf<int32_t> loc, ecnt, lrank, ebase;
+    DevBuf<double> pout;                                         // [point][3] the optional f64 output
     // per local point (by local rank)
-    int32_t* lpt = nullptr; int32_t* eoff = nullptr; int32_t* pn = nullptr; uint8_t* pfix = nullptr;
-    double* X = nullptr; double* Xt = nullptr; double* Vi = nullptr; double* gp = nullptr; double* pc = nullptr; double* pt = nullptr; double* pu = nullptr;
-    size_t lpt_bytes = 0, eoff_bytes = 0, pn_bytes = 0, pfix_bytes = 0, X_bytes = 0, Xt_bytes = 0, Vi_bytes = 0, gp_bytes = 0, pc_bytes = 0, pt_bytes = 0,
-           pu_bytes = 0;
+    DevBuf<int32_t> lpt, eoff, pn; DevBuf<uint8_t> pfix;
+    DevBuf<double> X, Xt, Vi, gp, pc, pt, pu;
     // per edge (compact, CSR order of the local points)
-    int32_t* e_kf = nullptr; int32_t* e_obs = nullptr; float* e_xy = nullptr; double* e_info = nullptr; uint8_t* e_inl = nullptr;
-    size_t e_kf_bytes = 0, e_obs_bytes = 0, e_xy_bytes = 0, e_info_bytes = 0, e_inl_bytes = 0;
-    uint8_t* einl = nullptr; size_t einl_bytes = 0;              // [observation] 0 / 1 / 2
+    DevBuf<int32_t> e_kf, e_obs; DevBuf<float> e_xy; DevBuf<double> e_info; DevBuf<uint8_t> e_inl;
+    DevBuf<uint8_t> einl;                                        // [observation] 0 / 1 / 2
     // per keyframe position
-    int32_t* kf_edge = nullptr; int32_t* kf_fidx = nullptr; double* poseC = nullptr; double* poseT = nullptr;
-    size_t kf_edge_bytes = 0, kf_fidx_bytes = 0, poseC_bytes = 0, poseT_bytes = 0;
-    double* S = nullptr;                                         // [96][96] reduced system, [96] right side, [96] solution
-    BaRes* res = nullptr; BaRes* h_res = nullptr;                // device / pinned
+    DevBuf<int32_t> kf_edge, kf_fidx; DevBuf<double> poseC, poseT;
+    DevBuf<double> S;                                            // [96][96] reduced system, [96] right side, [96] solution
+    DevBuf<BaRes> res; PinnedBuf<BaRes> h_res;
     // mo_map_add_observations
-    int32_t* ao_pt = nullptr; int32_t* ao_row = nullptr; int32_t* ao_claim = nullptr; int32_t* ao_cnt = nullptr; int32_t* ao_base = nullptr;
-    size_t ao_pt_bytes = 0, ao_row_bytes = 0, ao_claim_bytes = 0, ao_cnt_bytes = 0, ao_base_bytes = 0;
-    int32_t* ao_total = nullptr;
+    DevBuf<int32_t> ao_pt, ao_row, ao_claim, ao_cnt, ao_base, ao_total;
 };
 
-void map_ba_free(mo_map* m) {
-    BaBufs* b = m->ba;
-    if (!b) return;
-    void* bufs[] = {b->loc, b->ecnt, b->lrank, b->ebase, b->pout, b->lpt, b->eoff, b->pn, b->pfix, b->X, b->Xt, b->Vi, b->gp, b->pc, b->pt, b->pu,
-                    b->e_kf, b->e_obs, b->e_xy, b->e_info, b->e_inl, b->einl, b->kf_edge, b->kf_fidx, b->poseC, b->poseT, b->S, b->res,
-                    b->ao_pt, b->ao_row, b->ao_claim, b->ao_cnt, b->ao_base, b->ao_total};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (b->h_res) hipHostFree(b->h_res);
-    delete b;
-    m->ba = nullptr;
-}
+void map_scratch_free(BaBufs* b) { delete b; }
 
-// the keyframe position and store entry of observation o, read like the cull reads it; false when it names nothing
-__device__ __forceinline__ bool ba_obs(const MapPts& src, int o, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                       int* pos, int* slot, int* kp) {
-    int kf = src.okf[o];
-    if (kf < 0) kf += n_kf;
-    if (kf < 0 || kf >= n_kf) return false;
-    const int s = pos_slot[kf];
-    int r = src.okp[o];
-    const int nk = kcnt[s];
-    if (r < 0) r += nk;
-    if (r < 0 || r >= nk) return false;
-    *pos = kf; *slot = s; *kp = r;
-    return true;
-}
-
-// fixed-order sums: lane 0's shuffle tree per wave, then the waves in order; every thread receives the result
-__device__ __forceinline__ double ba_wave_sum(double v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
+// fixed-order sums: lane 0's shuffle tree per wave (wave_sum), then the waves in order; every thread receives the result
 __device__ __forceinline__ double ba_block_sum(double v, double* lds) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = ba_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0) lds[wv] = v;
     __syncthreads();
     double s = lds[0];
@@ -146,13 +109,13 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_mark(MapPts src, int n_pts, con
     int nv = 0, pos, s, kp;
     bool fr = false;
     for (int o = o0; o < o1; o++)
-        if (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) { nv++; fr |= pos >= lo_pos && pos != 0; }
+        if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) { nv++; fr |= pos >= lo_pos && pos != 0; }
     const bool local = nv >= 2 && fr;
     loc[i] = local;
     ecnt[i] = local ? nv : 0;
     if (local)
         for (int o = o0; o < o1; o++)
-            if (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) kf_edge[pos] = 1;
+            if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) kf_edge[pos] = 1;
 }
 
 // free and fixed keyframes.  Outside the window a position with edges is fixed; inside, in position order, the lowest ones are fixed
@@ -197,7 +160,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_edges(MapPts src, int n_pts, co
     const int o0 = src.off[i], o1 = src.off[i + 1];
     int pos, s, kp;
     for (int o = o0; o < o1; o++) {
-        if (!ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) continue;
+        if (map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) continue;
         const mo_keypoint q = kkps[(size_t)s * row + kp];
         e_kf[e] = pos; e_obs[e] = o; e_xy[(size_t)e * 2] = q.x; e_xy[(size_t)e * 2 + 1] = q.y; e_info[e] = ba_info(sf, q.octave); e_inl[e] = 1;
         e++;
@@ -346,7 +309,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_pair(BaPrm prm, int round, cons
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int k = 0; k < 48; k++) {
-        const double v = ba_wave_sum(a[k]);
+        const double v = wave_sum(a[k]);
         if (lane == 0) red[wv][k] = v;
     }
     __syncthreads();
@@ -561,22 +524,16 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     if (!m->ba) m->ba = new BaBufs();
     BaBufs& b = *m->ba;
     int rc;
-    if ((rc = reserve(c, b.loc, b.loc_bytes, np * 4)) || (rc = reserve(c, b.ecnt, b.ecnt_bytes, np * 4)) || (rc = reserve(c, b.lrank, b.lrank_bytes, np * 4)) ||
-        (rc = reserve(c, b.ebase, b.ebase_bytes, np * 4)) || (rc = reserve(c, b.lpt, b.lpt_bytes, np * 4)) || (rc = reserve(c, b.eoff, b.eoff_bytes, (np + 1) * 4)) ||
-        (rc = reserve(c, b.pn, b.pn_bytes, np * 4)) || (rc = reserve(c, b.pfix, b.pfix_bytes, np)) || (rc = reserve(c, b.X, b.X_bytes, np * 24)) ||
-        (rc = reserve(c, b.Xt, b.Xt_bytes, np * 24)) || (rc = reserve(c, b.Vi, b.Vi_bytes, np * 48)) || (rc = reserve(c, b.gp, b.gp_bytes, np * 24)) ||
-        (rc = reserve(c, b.pc, b.pc_bytes, np * 8)) || (rc = reserve(c, b.pt, b.pt_bytes, np * 8)) || (rc = reserve(c, b.pu, b.pu_bytes, np * 8)) ||
-        (rc = reserve(c, b.e_kf, b.e_kf_bytes, no * 4)) || (rc = reserve(c, b.e_obs, b.e_obs_bytes, no * 4)) || (rc = reserve(c, b.e_xy, b.e_xy_bytes, no * 8)) ||
-        (rc = reserve(c, b.e_info, b.e_info_bytes, no * 8)) || (rc = reserve(c, b.e_inl, b.e_inl_bytes, no)) || (rc = reserve(c, b.einl, b.einl_bytes, no)) ||
-        (rc = reserve(c, b.kf_edge, b.kf_edge_bytes, (size_t)n_kf * 4)) || (rc = reserve(c, b.kf_fidx, b.kf_fidx_bytes, (size_t)n_kf * 4)) ||
-        (rc = reserve(c, b.poseC, b.poseC_bytes, (size_t)n_kf * 96)) || (rc = reserve(c, b.poseT, b.poseT_bytes, (size_t)n_kf * 96)))
+    if ((rc = b.loc.reserve(c, np)) || (rc = b.ecnt.reserve(c, np)) || (rc = b.lrank.reserve(c, np)) || (rc = b.ebase.reserve(c, np)) ||
+        (rc = b.lpt.reserve(c, np)) || (rc = b.eoff.reserve(c, np + 1)) || (rc = b.pn.reserve(c, np)) || (rc = b.pfix.reserve(c, np)) ||
+        (rc = b.X.reserve(c, np * 3)) || (rc = b.Xt.reserve(c, np * 3)) || (rc = b.Vi.reserve(c, np * 6)) || (rc = b.gp.reserve(c, np * 3)) ||
+        (rc = b.pc.reserve(c, np)) || (rc = b.pt.reserve(c, np)) || (rc = b.pu.reserve(c, np)) || (rc = b.e_kf.reserve(c, no)) ||
+        (rc = b.e_obs.reserve(c, no)) || (rc = b.e_xy.reserve(c, no * 2)) || (rc = b.e_info.reserve(c, no)) || (rc = b.e_inl.reserve(c, no)) ||
+        (rc = b.einl.reserve(c, no)) || (rc = b.kf_edge.reserve(c, (size_t)n_kf)) || (rc = b.kf_fidx.reserve(c, (size_t)n_kf)) ||
+        (rc = b.poseC.reserve(c, (size_t)n_kf * 12)) || (rc = b.poseT.reserve(c, (size_t)n_kf * 12)))
         return rc;
-    if (out->points_out && (rc = reserve(c, b.pout, b.pout_bytes, np * 24))) return rc;
-    if (!b.res) {
-        HIPCHK(c, hipMalloc((void**)&b.res, sizeof(BaRes)));
-        HIPCHK(c, hipHostMalloc((void**)&b.h_res, sizeof(BaRes), hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&b.S, (size_t)(BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM) * 8));
-    }
+    if (out->points_out && (rc = b.pout.reserve(c, np * 3))) return rc;
+    if ((rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)) || (rc = b.S.reserve(c, BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
     HIPCHK(c, hipMemcpyAsync(b.poseC, poses, (size_t)n_kf * 96, hipMemcpyHostToDevice, c->stream));
@@ -586,15 +543,15 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     BaPrm p;
     for (int i = 0; i < 9; i++) p.K[i] = K[i];
     p.sf = prm->scale_factor; p.chi2 = prm->chi2; p.n_kf = n_kf; p.lo_pos = lo_pos;
-    const MapPts& src = m->P[m->cur];
+    const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
     const unsigned wblocks = (unsigned)((std::max(np, no) + BA_BLOCK - 1) / BA_BLOCK);
     double* dcv = b.S + BA_MAX_DIM * BA_MAX_DIM + BA_MAX_DIM;
     hipLaunchKernelGGL(k_ba_init, dim3(1), dim3(64), 0, c->stream, b.res);
     hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, lo_pos, b.loc, b.ecnt, b.kf_edge);
     HIPCHK(c, hipGetLastError());
-    if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, (int32_t*)((char*)b.res + offsetof(BaRes, n_local))))) return rc;
-    if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, (int32_t*)((char*)b.res + offsetof(BaRes, n_edges))))) return rc;
+    if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, &b.res.p->n_local))) return rc;
+    if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, &b.res.p->n_edges))) return rc;
     hipLaunchKernelGGL(k_ba_setup, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, b.kf_edge, b.kf_fidx, b.res);
     hipLaunchKernelGGL(k_ba_edges, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, m->kkps, m->row, p.sf, b.loc, b.lrank,
                        b.ebase, b.lpt, b.eoff, b.X, b.e_kf, b.e_obs, b.e_xy, b.e_info, b.e_inl, b.res);
@@ -620,7 +577,7 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         mo_stage_mark(c, r ? "ba_round1" : "ba_round0");
     }
     hipLaunchKernelGGL(k_ba_write, dim3(wblocks), dim3(BA_BLOCK), 0, c->stream, p, (int)np, (int)no, b.loc, b.lrank, b.X, src.xyz,
-                       out->points_out ? b.pout : (double*)nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.poseC, m->kP, b.res);
+                       out->points_out ? b.pout.p : nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.poseC, m->kP, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "ba_write");
     std::vector<int32_t> fidx(out->kf_state ? (size_t)n_kf : 0);
@@ -663,7 +620,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_obs_count(MapPts src, int n_pts, c
     if (add) {
         int pos, s, kp;
         for (int o = o0; o < o1; o++)   // (the next keyframe's position names nothing yet: its entries are compared as stored)
-            if (kf_pos == n_kf ? src.okf[o] == kf_pos : (ba_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp) && pos == kf_pos)) { add = 0; break; }
+            if (kf_pos == n_kf ? src.okf[o] == kf_pos : (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp) && pos == kf_pos)) { add = 0; break; }
         if (!add) claim[i] = INT_MAX;
     }
     cnt[i] = o1 - o0 + add;
@@ -698,19 +655,16 @@ extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32
     BaBufs& b = *m->ba;
     const size_t np = (size_t)m->n_pts;
     int rc;
-    if ((rc = reserve(c, b.ao_pt, b.ao_pt_bytes, (size_t)n * 4)) || (rc = reserve(c, b.ao_row, b.ao_row_bytes, (size_t)n * 4)) ||
-        (rc = reserve(c, b.ao_claim, b.ao_claim_bytes, np * 4)) || (rc = reserve(c, b.ao_cnt, b.ao_cnt_bytes, np * 4)) ||
-        (rc = reserve(c, b.ao_base, b.ao_base_bytes, np * 4)))
+    if ((rc = b.ao_pt.reserve(c, (size_t)n)) || (rc = b.ao_row.reserve(c, (size_t)n)) || (rc = b.ao_claim.reserve(c, np)) ||
+        (rc = b.ao_cnt.reserve(c, np)) || (rc = b.ao_base.reserve(c, np)) || (rc = b.ao_total.reserve(c, 4)))
         return rc;
-    if (!b.ao_total) HIPCHK(c, hipMalloc((void**)&b.ao_total, 16));
     const size_t new_obs = (size_t)m->n_obs + std::min<size_t>((size_t)n, np);
     if ((rc = map_pts_reserve(m, m->cur ^ 1, np, new_obs, false))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     HIPCHK(c, hipMemcpyAsync(b.ao_pt, point, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.ao_row, row, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.ao_claim, INT_MAX, np, c->stream));
-    const MapPts& src = m->P[m->cur];
-    const MapPts& dst = m->P[m->cur ^ 1];
+    const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
     hipLaunchKernelGGL(k_obs_claim, dim3((unsigned)((n + BA_BLOCK - 1) / BA_BLOCK)), dim3(BA_BLOCK), 0, c->stream, b.ao_pt, n, (int)np, b.ao_claim);
     hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, kf_pos, b.ao_claim, b.ao_cnt);

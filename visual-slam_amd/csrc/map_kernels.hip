@@ -1,6 +1,7 @@
-// map_kernels.hip -- the device-resident LocalMapper (reference src/orbslam2/local_mapper.py): keyframe store, map store and the
-// per-keyframe step add_keyframe runs (store -> growth of one keyframe pair -> cull of every map point -> per-keyframe lists and the
-// counts _cull_keyframes reads), one synchronisation per keyframe.
+// map_kernels.hip -- the device-resident LocalMapper (reference src/orbslam2/local_mapper.py): keyframe store, map store, the
+// device-wide scan and the per-keyframe step add_keyframe runs (store -> growth of one keyframe pair -> cull of every map point ->
+// per-keyframe lists and the counts _cull_keyframes reads), one synchronisation per keyframe.  The other users of the map have files
+// of their own (map_reloc.hip, map_track.hip, map_ba.hip, map_io.hip); map_store.h is what they share.
 //
 // Stores (structure of arrays, grown by reallocation):
 //   keyframes  slot s (creation order, never reused): kps [s][row][28 B], desc [s][row][32], count [s], P = K [R|t] [s][12] f64.
@@ -15,17 +16,13 @@
 //
 // -ffp-contract=off (Makefile, every file): the reprojection test rounds each product and sum once, in the order numpy's P @ X_h does.
 #include <algorithm>
-#include <charconv>
 #include <climits>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "map_store.h"
-#include "pnp.h"
 
 #define MAP_SCAN_BLOCK 256
 #define MAP_SCAN_ITEMS 4
@@ -70,10 +67,10 @@ __global__ __launch_bounds__(MAP_SCAN_BLOCK) void k_scan_add(int32_t* __restrict
         if (base + k < (size_t)n) out[base + k] += add;
 }
 
-static int scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total) {
+int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total) {
     mo_ctx* c = m->c;
     const int tiles = std::max(1, (n + MAP_SCAN_TILE - 1) / MAP_SCAN_TILE);
-    int rc = reserve(c, m->part, m->part_bytes, (size_t)tiles * sizeof(int32_t));
+    int rc = m->part.reserve(c, (size_t)tiles);
     if (rc) return rc;
     hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(MAP_SCAN_BLOCK), 0, c->stream, in, out, m->part, n);
     hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, c->stream, m->part, tiles, d_total);
@@ -81,8 +78,6 @@ static int scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t*
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
-
-int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total) { return scan_excl(m, in, out, n, d_total); }
 
 // ---- growth: the F-RANSAC inliers of one keyframe pair, in query order, onto the end of the map (local_mapper.py:150-187) --------
 // One block of 1024 threads walks the query keypoints in tiles (ballot + block scan); the map's live counts come from the status block.
@@ -143,14 +138,9 @@ __global__ __launch_bounds__(256) void k_map_cull(MapPts src, int bound, const i
             k = 1;
             const double X = src.xyz[(size_t)i * 3], Y = src.xyz[(size_t)i * 3 + 1], Z = src.xyz[(size_t)i * 3 + 2];
             for (int o = o0; o < o1; o++) {
-                int kf = src.okf[o];
-                if (kf < 0) kf += n_kf;                 // Python indexing: negative positions count from the end
-                if (kf < 0 || kf >= n_kf) { atomicOr(st + ST_ERR, 1); k = 0; break; }
-                const int s = pos_slot[kf];
-                int kp = src.okp[o];
-                const int nk = kcnt[s];
-                if (kp < 0) kp += nk;
-                if (kp < 0 || kp >= nk) { atomicOr(st + ST_ERR, 2); k = 0; break; }
+                int pos, s, kp;
+                const int bad = map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp);
+                if (bad) { atomicOr(st + ST_ERR, bad); k = 0; break; }   // bit 1: keyframe, bit 2: keypoint
                 const double* P = kP + (size_t)s * 12;
                 const double u = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P[0], X), __dmul_rn(P[1], Y)), __dmul_rn(P[2], Z)), P[3]);
                 const double v = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P[4], X), __dmul_rn(P[5], Y)), __dmul_rn(P[6], Z)), P[7]);
@@ -277,60 +267,55 @@ __global__ __launch_bounds__(256) void k_kf_redundant(const int32_t* __restrict_
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static int pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) {
+int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) {
     mo_ctx* c = m->c;
-    MapPts& p = m->P[which];
+    MapPtsStore& p = m->P[which];
     const size_t np = keep ? (size_t)m->n_pts : 0, no = keep ? (size_t)m->n_obs : 0;
     int rc;
     if (!p.xyz || pcap > p.pcap) {
         pcap = std::max(pcap, p.pcap + p.pcap / 2);
-        if ((rc = regrow(c, p.xyz, 0, pcap * 12, np * 12)) || (rc = regrow(c, p.col, 0, pcap * 3, np * 3)) ||
-            (rc = regrow(c, p.id, 0, pcap * 4, np * 4)) || (rc = regrow(c, p.dkf, 0, pcap * 4, np * 4)) ||
-            (rc = regrow(c, p.drow, 0, pcap * 4, np * 4)) || (rc = regrow(c, p.off, 0, (pcap + 1) * 4, (np + 1) * 4)))
+        if ((rc = p.xyz.regrow(c, pcap * 3, np * 3)) || (rc = p.col.regrow(c, pcap * 3, np * 3)) || (rc = p.id.regrow(c, pcap, np)) ||
+            (rc = p.dkf.regrow(c, pcap, np)) || (rc = p.drow.regrow(c, pcap, np)) || (rc = p.off.regrow(c, pcap + 1, np + 1)))
             return rc;
         p.pcap = pcap;
     }
     if (!p.okf || ocap > p.ocap) {
         ocap = std::max(ocap, p.ocap + p.ocap / 2);
-        if ((rc = regrow(c, p.okf, 0, ocap * 4, no * 4)) || (rc = regrow(c, p.okp, 0, ocap * 4, no * 4))) return rc;
+        if ((rc = p.okf.regrow(c, ocap, no)) || (rc = p.okp.regrow(c, ocap, no))) return rc;
         p.ocap = ocap;
     }
     return MO_OK;
 }
-
-int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) { return pts_reserve(m, which, pcap, ocap, keep); }
 
 // kkps / kdesc / kcnt hold one slot more than kslots: the spare slot (index kslots) mo_map_relocalize stages its query in, so that
 // one counts array serves both sides of its keyframe matching
 int kf_reserve(mo_map* m, int rows, int slots) {
     mo_ctx* c = m->c;
     int rc;
+    const size_t kept = (size_t)m->n_slots;
     if (rows > m->row) {  // a wider row: every keyframe is moved to the new stride
         const int nr = (int)(((size_t)rows + 15) & ~(size_t)15);
         const int ns = std::max(slots, m->kslots);
-        mo_keypoint* k2 = nullptr; uint8_t* d2 = nullptr;
-        HIPCHK(c, hipMalloc((void**)&k2, (size_t)(ns + 1) * nr * sizeof(mo_keypoint)));
-        HIPCHK(c, hipMalloc((void**)&d2, (size_t)(ns + 1) * nr * 32));
-        if (m->n_slots && m->row) {
-            HIPCHK(c, hipMemcpy2DAsync(k2, (size_t)nr * sizeof(mo_keypoint), m->kkps, (size_t)m->row * sizeof(mo_keypoint), (size_t)m->row * sizeof(mo_keypoint),
-                                       m->n_slots, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpy2DAsync(d2, (size_t)nr * 32, m->kdesc, (size_t)m->row * 32, (size_t)m->row * 32, m->n_slots, hipMemcpyDeviceToDevice, c->stream));
+        {
+            DevBuf<mo_keypoint> k2; DevBuf<uint8_t> d2;
+            if ((rc = k2.regrow(c, (size_t)(ns + 1) * nr, 0)) || (rc = d2.regrow(c, (size_t)(ns + 1) * nr * 32, 0))) return rc;
+            if (m->n_slots && m->row) {
+                HIPCHK(c, hipMemcpy2DAsync(k2, (size_t)nr * sizeof(mo_keypoint), m->kkps, (size_t)m->row * sizeof(mo_keypoint), (size_t)m->row * sizeof(mo_keypoint),
+                                           m->n_slots, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpy2DAsync(d2, (size_t)nr * 32, m->kdesc, (size_t)m->row * 32, (size_t)m->row * 32, m->n_slots, hipMemcpyDeviceToDevice, c->stream));
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            m->kkps.swap(k2); m->kdesc.swap(d2); m->row = nr;   // (the old blocks are freed here, behind the synchronisation)
         }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (m->kkps) HIPCHK(c, hipFree(m->kkps));
-        if (m->kdesc) HIPCHK(c, hipFree(m->kdesc));
-        m->kkps = k2; m->kdesc = d2; m->row = nr;
         if (ns > m->kslots) {
-            if ((rc = regrow(c, m->kcnt, 0, (size_t)(ns + 1) * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
-                return rc;
+            if ((rc = m->kcnt.regrow(c, (size_t)ns + 1, kept)) || (rc = m->kP.regrow(c, (size_t)ns * 12, kept * 12))) return rc;
             m->kslots = ns;
         }
     }
     if (slots > m->kslots) {
         const int ns = std::max(slots, m->kslots * 2);
-        if ((rc = regrow(c, m->kkps, 0, (size_t)(ns + 1) * m->row * sizeof(mo_keypoint), (size_t)m->n_slots * m->row * sizeof(mo_keypoint))) ||
-            (rc = regrow(c, m->kdesc, 0, (size_t)(ns + 1) * m->row * 32, (size_t)m->n_slots * m->row * 32)) ||
-            (rc = regrow(c, m->kcnt, 0, (size_t)(ns + 1) * 4, (size_t)m->n_slots * 4)) || (rc = regrow(c, m->kP, 0, (size_t)ns * 96, (size_t)m->n_slots * 96)))
+        if ((rc = m->kkps.regrow(c, (size_t)(ns + 1) * m->row, kept * m->row)) || (rc = m->kdesc.regrow(c, (size_t)(ns + 1) * m->row * 32, kept * m->row * 32)) ||
+            (rc = m->kcnt.regrow(c, (size_t)ns + 1, kept)) || (rc = m->kP.regrow(c, (size_t)ns * 12, kept * 12)))
             return rc;
         m->kslots = ns;
     }
@@ -339,7 +324,7 @@ int kf_reserve(mo_map* m, int rows, int slots) {
 
 int upload_pos_slot(mo_map* m) {
     mo_ctx* c = m->c;
-    int rc = reserve(c, m->d_pos_slot, m->pos_slot_bytes, std::max<size_t>(m->pos_slot.size(), 1) * 4);
+    int rc = m->d_pos_slot.reserve(c, std::max<size_t>(m->pos_slot.size(), 1));
     if (rc) return rc;
     if (!m->pos_slot.empty())
         HIPCHK(c, hipMemcpyAsync(m->d_pos_slot, m->pos_slot.data(), m->pos_slot.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -353,10 +338,10 @@ extern "C" mo_map* mo_map_create(mo_ctx* c, int kf_slots, int kf_rows, int64_t p
     m->c = c;
     int rc = MO_OK;
     if (!rc) rc = kf_reserve(m, std::max(kf_rows, 16), std::max(kf_slots, 2));
-    if (!rc) rc = pts_reserve(m, 0, (size_t)std::max<int64_t>(pts_cap, 16), (size_t)std::max<int64_t>(obs_cap, 32), false);
-    if (!rc) rc = pts_reserve(m, 1, (size_t)std::max<int64_t>(pts_cap, 16), (size_t)std::max<int64_t>(obs_cap, 32), false);
-    if (!rc && hipMalloc((void**)&m->st, ST_NWORDS * sizeof(int32_t)) != hipSuccess) rc = mo_fail(c, MO_ERR_HIP, "hipMalloc status");
-    if (!rc && hipHostMalloc((void**)&m->h_stat, ST_NWORDS * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) rc = mo_fail(c, MO_ERR_HIP, "hipHostMalloc");
+    if (!rc) rc = map_pts_reserve(m, 0, (size_t)std::max<int64_t>(pts_cap, 16), (size_t)std::max<int64_t>(obs_cap, 32), false);
+    if (!rc) rc = map_pts_reserve(m, 1, (size_t)std::max<int64_t>(pts_cap, 16), (size_t)std::max<int64_t>(obs_cap, 32), false);
+    if (!rc) rc = m->st.reserve(c, ST_NWORDS);
+    if (!rc) rc = m->h_stat.reserve(c, ST_NWORDS);
     if (!rc && hipMemsetAsync(m->st, 0, ST_NWORDS * sizeof(int32_t), c->stream) != hipSuccess) rc = mo_fail(c, MO_ERR_HIP, "hipMemset");
     if (!rc && hipMemsetAsync(m->P[0].off, 0, 4, c->stream) != hipSuccess) rc = mo_fail(c, MO_ERR_HIP, "hipMemset");
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = mo_fail(c, MO_ERR_HIP, "sync");
@@ -368,21 +353,7 @@ extern "C" void mo_map_destroy(mo_map* m) {
     if (!m) return;
     hipSetDevice(m->c->device);
     hipStreamSynchronize(m->c->stream);
-    void* bufs[] = {m->kkps, m->kdesc, m->kcnt, m->kP, m->d_pos_slot, m->img[0], m->img[1], m->loff[0], m->loff[1], m->lids[0], m->lids[1], m->kf_red, m->st, m->keep, m->kobs,
-                    m->rank, m->obase, m->part, m->ent_id, m->hist, m->hbase, m->first, m->midx, m->mdist, m->mpass, m->inl, m->gpts, m->F, m->gnp};
-    for (void* b : bufs) if (b) hipFree(b);
-    for (MapPts& p : m->P) {
-        void* pb[] = {p.xyz, p.col, p.id, p.dkf, p.drow, p.off, p.okf, p.okp};
-        for (void* b : pb) if (b) hipFree(b);
-    }
-    void* rb[] = {m->rl_tab, m->rl_qf, m->rl_midx, m->rl_mdist, m->rl_mpass, m->rl_score, m->rl_cq, m->rl_cp, m->rl_cinl, m->rl_qpt, m->rl_qinl,
-                  m->rl_res};
-    for (void* b : rb) if (b) hipFree(b);
-    if (m->h_stat) hipHostFree(m->h_stat);
-    if (m->h_rl) hipHostFree(m->h_rl);
-    map_track_free(m);
-    map_ba_free(m);
-    delete m;
+    delete m;   // every buffer frees itself (DevBuf, PinnedBuf, the scratch structs)
 }
 
 // the list / cull / counts chain on the map in P[cur] with `bound_pts` points at most (status block live); results into P[cur ^ 1]
@@ -393,20 +364,19 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     if (bound_pts > INT32_MAX / 2 || bound_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
     int rc;
     const int bp = (int)std::max<int64_t>(bound_pts, 1), bo = (int)std::max<int64_t>(bound_obs, 1);
-    if ((rc = pts_reserve(m, m->cur ^ 1, (size_t)bp, (size_t)bo, false))) return rc;
-    if ((rc = reserve(c, m->keep, m->keep_bytes, (size_t)bp * 4)) || (rc = reserve(c, m->kobs, m->kobs_bytes, (size_t)bp * 4)) ||
-        (rc = reserve(c, m->rank, m->rank_bytes, (size_t)bp * 4)) || (rc = reserve(c, m->obase, m->obase_bytes, (size_t)bp * 4)))
+    if ((rc = map_pts_reserve(m, m->cur ^ 1, (size_t)bp, (size_t)bo, false))) return rc;
+    if ((rc = m->keep.reserve(c, (size_t)bp)) || (rc = m->kobs.reserve(c, (size_t)bp)) ||
+        (rc = m->rank.reserve(c, (size_t)bp)) || (rc = m->obase.reserve(c, (size_t)bp)))
         return rc;
-    if ((rc = reserve(c, m->ent_id, m->ent_bytes, (size_t)bo * 4))) return rc;
+    if ((rc = m->ent_id.reserve(c, (size_t)bo))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
-    MapPts& src = m->P[m->cur];
-    MapPts& dst = m->P[m->cur ^ 1];
+    const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned gp = (unsigned)((bp + 255) / 256);
     hipLaunchKernelGGL(k_map_cull, dim3(gp), dim3(256), 0, c->stream, src, bp, m->d_pos_slot, n_kf, m->kcnt, m->kkps, m->row, m->kP, 2,
                        m->keep, m->kobs, m->st);
     HIPCHK(c, hipGetLastError());
-    if ((rc = scan_excl(m, m->keep, m->rank, bp, m->st + ST_KEPT))) return rc;
-    if ((rc = scan_excl(m, m->kobs, m->obase, bp, m->st + ST_KOBS))) return rc;
+    if ((rc = map_scan_excl(m, m->keep, m->rank, bp, m->st + ST_KEPT))) return rc;
+    if ((rc = map_scan_excl(m, m->kobs, m->obase, bp, m->st + ST_KOBS))) return rc;
     hipLaunchKernelGGL(k_map_compact, dim3(gp), dim3(256), 0, c->stream, src, dst, bp, m->keep, m->rank, m->obase, m->ent_id, m->st);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "map_cull");
@@ -414,16 +384,16 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     const int n_chunks = (bo + MAP_LIST_CHUNK - 1) / MAP_LIST_CHUNK;
     const size_t hn = (size_t)std::max(n_kf, 1) * n_chunks;
     if (hn > (size_t)INT32_MAX) return mo_fail(c, MO_ERR_CAPACITY, "list histogram too large");
-    if ((rc = reserve(c, m->hist, m->hist_bytes, hn * 4)) || (rc = reserve(c, m->hbase, m->hbase_bytes, hn * 4))) return rc;
+    if ((rc = m->hist.reserve(c, hn)) || (rc = m->hbase.reserve(c, hn))) return rc;
     const int ln = m->lcur ^ 1;
-    if ((rc = reserve(c, m->loff[ln], m->loff_bytes[ln], (size_t)(n_kf + 1) * 4))) return rc;
-    if ((rc = reserve(c, m->lids[ln], m->lids_bytes[ln], (size_t)bo * 4))) return rc;
-    if ((rc = reserve(c, m->kf_red, m->kf_red_bytes, (size_t)std::max(n_kf, 1) * 4))) return rc;
+    if ((rc = m->loff[ln].reserve(c, (size_t)n_kf + 1))) return rc;
+    if ((rc = m->lids[ln].reserve(c, (size_t)bo))) return rc;
+    if ((rc = m->kf_red.reserve(c, (size_t)std::max(n_kf, 1)))) return rc;
     if (n_kf > 0) {
         const size_t lds = (size_t)n_kf * 4;
         hipLaunchKernelGGL(k_list_hist, dim3(n_chunks), dim3(64), lds, c->stream, dst.okf, m->st, n_kf, n_chunks, m->hist);
         HIPCHK(c, hipGetLastError());
-        if ((rc = scan_excl(m, m->hist, m->hbase, (int)hn, m->st + ST_NLIST))) return rc;
+        if ((rc = map_scan_excl(m, m->hist, m->hbase, (int)hn, m->st + ST_NLIST))) return rc;
         hipLaunchKernelGGL(k_list_scatter, dim3(n_chunks), dim3(64), lds, c->stream, dst.okf, m->ent_id, m->st, n_kf, n_chunks, m->hbase, m->lids[ln]);
         HIPCHK(c, hipGetLastError());
     } else {
@@ -435,7 +405,7 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     // keyframe counts
     const int64_t idb = std::max<int64_t>(m->id_bound, 1);
     if (idb > INT32_MAX / 4) return mo_fail(c, MO_ERR_CAPACITY, "map point ids too large for the first-point table");
-    if ((rc = reserve(c, m->first, m->first_bytes, (size_t)idb * 4))) return rc;
+    if ((rc = m->first.reserve(c, (size_t)idb))) return rc;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)m->first, 0x7fffffff, (size_t)idb, c->stream));
     HIPCHK(c, hipMemsetAsync(m->kf_red, 0, (size_t)std::max(n_kf, 1) * 4, c->stream));
     hipLaunchKernelGGL(k_first_index, dim3(gp), dim3(256), 0, c->stream, dst.id, m->st, bp, (int)idb, m->first);
@@ -502,7 +472,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     // the image of this keyframe (the colours of the points the NEXT keyframe grows)
     const int ib = m->img_cur ^ 1;
     if (img) {
-        if ((rc = reserve(c, m->img[ib], m->img_bytes[ib], (size_t)w * h * ch))) return rc;
+        if ((rc = m->img[ib].reserve(c, (size_t)w * h * ch))) return rc;
         HIPCHK(c, hipMemcpyAsync(m->img[ib], img, (size_t)w * h * ch, hipMemcpyHostToDevice, c->stream));
     }
     m->img_w[ib] = img ? w : 0; m->img_h[ib] = img ? h : 0; m->img_ch[ib] = img ? ch : 1;
@@ -517,12 +487,12 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     if (ps >= 0 && nq > 0 && n > 0) {
         if (prm->n_hyp < 1) return mo_fail(c, MO_ERR_ARG, "n_hyp must be >= 1");
         const size_t rows = (size_t)m->row;
-        if ((rc = reserve(c, m->midx, m->midx_bytes, rows * 8)) || (rc = reserve(c, m->mdist, m->mdist_bytes, rows * 8)) ||
-            (rc = reserve(c, m->mpass, m->mpass_bytes, rows)) || (rc = reserve(c, m->inl, m->inl_bytes, rows)) ||
-            (rc = reserve(c, m->gpts, m->gpts_bytes, rows * 12)) || (rc = reserve(c, m->F, m->F_bytes, 9 * 8)) || (rc = reserve(c, m->gnp, m->gnp_bytes, 4)))
+        if ((rc = m->midx.reserve(c, rows * 2)) || (rc = m->mdist.reserve(c, rows * 2)) ||
+            (rc = m->mpass.reserve(c, rows)) || (rc = m->inl.reserve(c, rows)) ||
+            (rc = m->gpts.reserve(c, rows * 3)) || (rc = m->F.reserve(c, 9)) || (rc = m->gnp.reserve(c, 1)))
             return rc;
         bound_new = nq;
-        if ((rc = pts_reserve(m, m->cur, (size_t)(m->n_pts + bound_new), (size_t)(m->n_obs + 2 * bound_new), true))) return rc;
+        if ((rc = map_pts_reserve(m, m->cur, (size_t)(m->n_pts + bound_new), (size_t)(m->n_obs + 2 * bound_new), true))) return rc;
         if ((rc = upload_pos_slot(m))) return rc;
         const int32_t* qf = m->d_pos_slot + (n_kf - 2);
         const int32_t* tf = m->d_pos_slot + (n_kf - 1);
@@ -539,7 +509,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
         const int pi = m->img_cur ^ 1;  // the previous keyframe's image
         if (!m->img[pi]) { m->img_w[pi] = m->img_h[pi] = 0; }
         hipLaunchKernelGGL(k_map_append, dim3(1), dim3(1024), 0, c->stream, m->inl, m->midx, m->gpts, m->F, m->kkps + (size_t)ps * rows, m->kcnt + ps,
-                           m->img[pi] ? m->img[pi] : m->kdesc, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, m->P[m->cur],
+                           m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, m->P[m->cur].view(),
                            m->st);
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "map_append");
@@ -575,9 +545,9 @@ extern "C" int mo_map_add_points(mo_map* m, int n, const float* xyz, const uint8
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t no = obs_off[n] - obs_off[0];
     if (no < 0 || (no > 0 && (!obs_kf || !obs_kp))) return mo_fail(c, MO_ERR_ARG, "bad observation offsets");
-    int rc = pts_reserve(m, m->cur, (size_t)(m->n_pts + n), (size_t)(m->n_obs + no), true);
+    int rc = map_pts_reserve(m, m->cur, (size_t)(m->n_pts + n), (size_t)(m->n_obs + no), true);
     if (rc) return rc;
-    MapPts& p = m->P[m->cur];
+    const MapPts p = m->P[m->cur].view();
     const size_t b = (size_t)m->n_pts;
     HIPCHK(c, hipMemcpyAsync(p.xyz + b * 3, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(p.col + b * 3, col, (size_t)n * 3, hipMemcpyHostToDevice, c->stream));
@@ -629,7 +599,7 @@ extern "C" int mo_map_download(mo_map* m, int field, void* dst, size_t bytes) {
     mo_ctx* c = m->c;
     if (!dst && bytes) return mo_fail(c, MO_ERR_ARG, "NULL destination");
     HIPCHK(c, hipSetDevice(c->device));
-    const MapPts& p = m->P[m->cur];
+    const MapPts p = m->P[m->cur].view();
     const void* src = nullptr; size_t have = 0;
     switch (field) {
         case MO_MAP_XYZ: src = p.xyz; have = (size_t)m->n_pts * 12; break;
@@ -653,471 +623,5 @@ extern "C" int mo_map_download(mo_map* m, int field, void* dst, size_t bytes) {
     if (bytes != have) return mo_fail(c, MO_ERR_CAPACITY, "download size must equal the field's size (" + std::to_string(have) + " bytes)");
     if (have) HIPCHK(c, hipMemcpyAsync(dst, src, have, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MO_OK;
-}
-
-// ---- PLY text (utils.create_point_cloud_ply, utils.py:72-118): floats as Python's repr of the double value ----------------------
-static size_t fmt_double(double v, char* o) {
-    if (std::isnan(v)) { std::memcpy(o, "nan", 3); return 3; }
-    if (std::isinf(v)) { if (v < 0) { std::memcpy(o, "-inf", 4); return 4; } std::memcpy(o, "inf", 3); return 3; }
-    char sci[40];
-    // shortest round-trip digits in scientific form: [-]d[.ddd]e(+|-)XX
-    auto r = std::to_chars(sci, sci + sizeof(sci), v, std::chars_format::scientific);
-    const size_t len = (size_t)(r.ptr - sci);
-    sci[len] = '\0';
-    size_t k = 0;
-    const bool neg = sci[0] == '-';
-    if (neg) k = 1;
-    char dig[24]; int nd = 0;
-    size_t e = k;
-    for (; e < len && sci[e] != 'e'; e++) if (sci[e] != '.') dig[nd++] = sci[e];
-    const int exp10 = std::atoi(sci + e + 1);
-    size_t n = 0;
-    if (neg) o[n++] = '-';
-    if (exp10 < -4 || exp10 >= 16) {
-        o[n++] = dig[0];
-        if (nd > 1) { o[n++] = '.'; for (int i = 1; i < nd; i++) o[n++] = dig[i]; }
-        o[n++] = 'e'; o[n++] = exp10 < 0 ? '-' : '+';
-        const int ae = exp10 < 0 ? -exp10 : exp10;
-        if (ae < 10) o[n++] = '0';
-        char eb[8]; auto er = std::to_chars(eb, eb + 8, ae);
-        for (char* q = eb; q < er.ptr; q++) o[n++] = *q;
-        return n;
-    }
-    if (exp10 < 0) {
-        o[n++] = '0'; o[n++] = '.';
-        for (int i = 0; i < -exp10 - 1; i++) o[n++] = '0';
-        for (int i = 0; i < nd; i++) o[n++] = dig[i];
-        return n;
-    }
-    // exp10 in [0, 16): integer part = first exp10 + 1 digits (zero-padded), then the rest or ".0"
-    for (int i = 0; i <= exp10; i++) o[n++] = i < nd ? dig[i] : '0';
-    o[n++] = '.';
-    if (nd > exp10 + 1) for (int i = exp10 + 1; i < nd; i++) o[n++] = dig[i];
-    else o[n++] = '0';
-    return n;
-}
-
-extern "C" int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len) {
-    if ((!v && n) || !len) return MO_ERR_ARG;
-    size_t w = 0;
-    char buf[48];
-    for (int64_t i = 0; i < n; i++) {
-        const size_t k = fmt_double((double)v[i], buf);
-        if (out && w + k + 1 <= cap) { std::memcpy(out + w, buf, k); out[w + k] = '\n'; }
-        w += k + 1;
-    }
-    *len = w;
-    return out && w > cap ? MO_ERR_CAPACITY : MO_OK;
-}
-
-extern "C" int mo_map_write_ply(mo_map* m, const char* path, int min_obs, int64_t* n_written) {
-    if (!m) return MO_ERR_ARG;
-    mo_ctx* c = m->c;
-    if (!path) return mo_fail(c, MO_ERR_ARG, "NULL path");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)m->n_pts;
-    std::vector<float> xyz(np * 3);
-    std::vector<uint8_t> col(np * 3);
-    std::vector<int32_t> off(np + 1);
-    const MapPts& p = m->P[m->cur];
-    if (np) {
-        HIPCHK(c, hipMemcpyAsync(xyz.data(), p.xyz, np * 12, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(col.data(), p.col, np * 3, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(off.data(), p.off, (np + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    size_t cnt = 0;
-    for (size_t i = 0; i < np; i++) cnt += off[i + 1] - off[i] >= min_obs;
-    if (n_written) *n_written = (int64_t)cnt;
-    if (!cnt) return MO_OK;  // (local_mapper.py:345: nothing to write, no file)
-    std::string s;
-    s.reserve(200 + cnt * 64);
-    s += "ply\nformat ascii 1.0\nelement vertex " + std::to_string(cnt) +
-         "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n";
-    char buf[48];
-    for (size_t i = 0; i < np; i++) {
-        if (off[i + 1] - off[i] < min_obs) continue;
-        for (int k = 0; k < 3; k++) { s.append(buf, fmt_double((double)xyz[i * 3 + k], buf)); s += ' '; }
-        for (int k = 0; k < 3; k++) {
-            auto r = std::to_chars(buf, buf + 8, (int)col[i * 3 + k]);
-            s.append(buf, (size_t)(r.ptr - buf));
-            s += k < 2 ? ' ' : '\n';
-        }
-    }
-    FILE* fp = std::fopen(path, "wb");
-    if (!fp) return mo_fail(c, MO_ERR_ARG, std::string("cannot open ") + path);
-    const size_t wr = std::fwrite(s.data(), 1, s.size(), fp);
-    const int cl = std::fclose(fp);
-    if (wr != s.size() || cl != 0) return mo_fail(c, MO_ERR_ARG, std::string("write failed: ") + path);
-    return MO_OK;
-}
-
-// ---- relocalization (mo_map_relocalize): a lost frame against every keyframe, 2D-3D correspondences through the observations, P3P
-// RANSAC per candidate keyframe.  Read-only on the map; the frame is staged in the spare keyframe slot (kf_reserve).
-// Chain: point_of scatter -> knn-2 matching of the frame against every keyframe (match_launch_pairs, one pair per keyframe) -> scores
-// |C_k| -> ranking -> C_k of the candidates (block scans, query order) -> P3P hypotheses + scoring (one wave per hypothesis, all
-// candidates in one launch) -> best hypothesis + Gauss-Newton refinement (one wave per candidate) -> winner.  One synchronisation.
-#define RL_MAX_CAND 64
-#define RL_MIN_SCORE 15   // ORB-SLAM2's Tracking::Relocalization: keyframes with fewer than 15 matches are discarded
-#define RL_HYP_WAVES 4    // hypotheses per block of k_reloc_hyp (one per wave)
-
-struct RelocRes {
-    double pose[RL_MAX_CAND][12];         // refined [R | t] per candidate
-    unsigned long long best[RL_MAX_CAND]; // (inliers << 32) | ~(h * 4 + root): the largest key is the best hypothesis
-    int32_t cand[RL_MAX_CAND], score[RL_MAX_CAND], ncorr[RL_MAX_CAND], ninl[RL_MAX_CAND];
-    int32_t n_cand, win;
-};
-
-struct RelocGeom {
-    double K[9], Kinv[9], thr2;
-};
-
-// point_of[slot][row] = lowest map point whose observations hold (position, row); entries naming nothing are skipped
-__global__ __launch_bounds__(256) void k_reloc_point_of(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
-                                                        const int32_t* __restrict__ kcnt, int row, int32_t* __restrict__ tab) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pts) return;
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    for (int o = o0; o < o1; o++) {
-        int kf = src.okf[o];
-        if (kf < 0) kf += n_kf;
-        if (kf < 0 || kf >= n_kf) continue;
-        const int s = pos_slot[kf];
-        int kp = src.okp[o];
-        const int nk = kcnt[s];
-        if (kp < 0) kp += nk;
-        if (kp < 0 || kp >= nk) continue;
-        atomicMin(tab + (size_t)s * row + kp, i);
-    }
-}
-
-// the map point of query q against keyframe position k (-1: none): the ratio-test survivor's best neighbour through point_of
-__device__ __forceinline__ int reloc_point(int k, int s, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
-                                           const int32_t* __restrict__ tab) {
-    const size_t o = (size_t)k * row + q;
-    if (!mpass[o]) return -1;
-    const int t = midx[2 * o];
-    if (t < 0) return -1;
-    const int p = tab[(size_t)s * row + t];
-    return p == INT_MAX ? -1 : p;
-}
-
-// |C_k|, one block per keyframe position
-__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                     const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
-                                                     const int32_t* __restrict__ tab, int32_t* __restrict__ score) {
-    __shared__ int lw[4];
-    const int k = blockIdx.x, s = pos_slot[k];
-    const int nq = min(kcnt[spare], row);
-    int n = 0;
-    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(k, s, q, row, midx, mpass, tab) >= 0;
-    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
-    if ((threadIdx.x & 63) == 0) lw[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) score[k] = lw[0] + lw[1] + lw[2] + lw[3];
-}
-
-// candidates: scores >= RL_MIN_SCORE, highest first, ties to the lower position; one block, one max reduction per rank
-__global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ score, int n_kf, int max_cand, RelocRes* __restrict__ res) {
-    __shared__ unsigned long long red[256];
-    const int tid = threadIdx.x;
-    if (tid < RL_MAX_CAND) {
-        res->best[tid] = 0; res->ninl[tid] = 0; res->ncorr[tid] = 0; res->cand[tid] = -1; res->score[tid] = 0;
-        for (int j = 0; j < 12; j++) res->pose[tid][j] = __longlong_as_double(0x7ff8000000000000ll);
-    }
-    __syncthreads();
-    unsigned long long prev = ~0ull;
-    int nc = 0;
-    for (int r = 0; r < max_cand; r++) {
-        unsigned long long b = 0;
-        for (int k = tid; k < n_kf; k += 256) {
-            const int s = score[k];
-            const unsigned long long key = ((unsigned long long)(unsigned)s << 32) | (unsigned)(0x7fffffff - k);
-            if (s >= RL_MIN_SCORE && key < prev && key > b) b = key;
-        }
-        red[tid] = b;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (tid < w) red[tid] = max(red[tid], red[tid + w]);
-            __syncthreads();
-        }
-        b = red[0];
-        __syncthreads();
-        if (!b) break;
-        if (tid == 0) { res->cand[r] = 0x7fffffff - (int)(b & 0xffffffffu); res->score[r] = (int)(b >> 32); }
-        nc = r + 1;
-        prev = b;
-    }
-    if (tid == 0) { res->n_cand = nc; res->win = -1; }
-}
-
-// C_k of candidate blockIdx.x in query order (block scans, no atomics)
-__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                       const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                       RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
-    __shared__ int lw[40];
-    const int c = blockIdx.x, k = res->cand[c];
-    if (k < 0) return;
-    const int s = pos_slot[k], nq = min(kcnt[spare], row);
-    int added = 0;
-    for (int b = 0; b < nq; b += 1024) {
-        const int q = b + threadIdx.x;
-        const int p = q < nq ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
-        int tot;
-        const int r = block_excl_scan(p >= 0 ? 1 : 0, lw, &tot);
-        if (p >= 0) { cq[(size_t)c * row + added + r] = q; cp[(size_t)c * row + added + r] = p; }
-        added += tot;
-    }
-    if (threadIdx.x == 0) res->ncorr[c] = added;
-}
-
-// the P3P poses of hypothesis h of candidate c (every lane of a wave solves the same sample)
-__device__ __forceinline__ int reloc_solve(const RelocGeom& g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps,
-                                           const int32_t* __restrict__ cq, const int32_t* __restrict__ cp, int m, uint64_t stream, int h,
-                                           double (&R)[4][9], double (&t)[4][3]) {
-    int idx[3];
-    pnp_sample<3>(stream, h, m, idx);
-    double X[3][3], b[3][3];
-    for (int i = 0; i < 3; i++) {
-        const int p = cp[idx[i]];
-        X[i][0] = xyz[(size_t)p * 3]; X[i][1] = xyz[(size_t)p * 3 + 1]; X[i][2] = xyz[(size_t)p * 3 + 2];
-        const mo_keypoint kp = qkps[cq[idx[i]]];
-        const double x = kp.x, y = kp.y;
-        for (int r = 0; r < 3; r++) b[i][r] = g.Kinv[r * 3] * x + g.Kinv[r * 3 + 1] * y + g.Kinv[r * 3 + 2];
-    }
-    return pnp_p3p(X, b, R, t);
-}
-
-// one wave per (hypothesis, candidate): up to 4 poses, each scored over C_k by the 64 lanes; the best key per candidate by atomicMax
-__global__ __launch_bounds__(64 * RL_HYP_WAVES) void k_reloc_hyp(RelocGeom g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps,
-                                                                 int row, int n_hyp, uint64_t seed, const int32_t* __restrict__ cq,
-                                                                 const int32_t* __restrict__ cp, RelocRes* __restrict__ res) {
-    const int c = blockIdx.y, k = res->cand[c];
-    const int h = blockIdx.x * RL_HYP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (k < 0 || h >= n_hyp) return;   // wave-uniform
-    const int m = res->ncorr[c];
-    const int32_t* q = cq + (size_t)c * row;
-    const int32_t* p = cp + (size_t)c * row;
-    double R[4][9], t[4][3];
-    const int nr = reloc_solve(g, xyz, qkps, q, p, m, pnp_stream_seed(seed, k), h, R, t);
-    unsigned long long best = 0;
-    for (int r = 0; r < nr; r++) {
-        double P[12];
-        pnp_projection(g.K, R[r], t[r], P);
-        int n = 0;
-        for (int j = lane; j < m; j += 64) {
-            const int pj = p[j];
-            const mo_keypoint kp = qkps[q[j]];
-            double e2;
-            n += pnp_reproj2(P, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, &e2) && e2 < g.thr2;
-        }
-        for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
-        const unsigned long long key = ((unsigned long long)(unsigned)n << 32) | (0xffffffffu - (unsigned)(h * 4 + r));
-        if (n > 0 && key > best) best = key;
-    }
-    if (lane == 0 && best) atomicMax(&res->best[c], best);
-}
-
-// a fixed-order wave sum every lane receives (lane 0's tree, broadcast): the same value on every lane, the same on every run
-__device__ __forceinline__ double reloc_wave_sum(double v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
-    return __shfl(v, 0, 64);
-}
-
-// inlier flags of C_k under (R, t) into fl, their number
-__device__ __forceinline__ int reloc_select(const RelocGeom& g, const double* R, const double* t, const float* __restrict__ xyz,
-                                            const mo_keypoint* __restrict__ qkps, const int32_t* __restrict__ q, const int32_t* __restrict__ p,
-                                            int m, uint8_t* __restrict__ fl) {
-    double P[12];
-    pnp_projection(g.K, R, t, P);
-    int n = 0;
-    for (int j = threadIdx.x; j < m; j += 64) {
-        const int pj = p[j];
-        const mo_keypoint kp = qkps[q[j]];
-        double e2;
-        const bool in = pnp_reproj2(P, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, &e2) && e2 < g.thr2;
-        fl[j] = in;
-        n += in;
-    }
-    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
-    return n;
-}
-
-// one wave per candidate: the best hypothesis' pose, (Gauss-Newton over its inliers, re-selection) twice
-__global__ __launch_bounds__(64) void k_reloc_refine(RelocGeom g, const float* __restrict__ xyz, const mo_keypoint* __restrict__ qkps, int row,
-                                                     uint64_t seed, const int32_t* __restrict__ cq, const int32_t* __restrict__ cp,
-                                                     uint8_t* __restrict__ cinl, RelocRes* __restrict__ res) {
-    const int c = blockIdx.x, k = res->cand[c];
-    if (k < 0) return;
-    const unsigned long long best = res->best[c];
-    if (!best) return;   // no pose with an inlier: 0 inliers, NaN pose (k_reloc_rank)
-    const int m = res->ncorr[c];
-    const int32_t* q = cq + (size_t)c * row;
-    const int32_t* p = cp + (size_t)c * row;
-    uint8_t* fl = cinl + (size_t)c * row;
-    const unsigned hr = 0xffffffffu - (unsigned)(best & 0xffffffffu);
-    double Rs[4][9], ts[4][3];
-    reloc_solve(g, xyz, qkps, q, p, m, pnp_stream_seed(seed, k), (int)(hr >> 2), Rs, ts);
-    double R[9], t[3];
-    for (int i = 0; i < 9; i++) R[i] = Rs[hr & 3][i];
-    for (int i = 0; i < 3; i++) t[i] = ts[hr & 3][i];
-    int n = reloc_select(g, R, t, xyz, qkps, q, p, m, fl);
-    for (int round = 0; round < 2; round++) {
-        for (int it = 0; it < 10; it++) {
-            double H[21], gr[6];
-            for (int i = 0; i < 21; i++) H[i] = 0.0;
-            for (int i = 0; i < 6; i++) gr[i] = 0.0;
-            for (int j = threadIdx.x; j < m; j += 64) {
-                if (!fl[j]) continue;
-                const int pj = p[j];
-                const mo_keypoint kp = qkps[q[j]];
-                pnp_gn_accumulate(g.K, R, t, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, H, gr);
-            }
-            for (int i = 0; i < 21; i++) H[i] = reloc_wave_sum(H[i]);
-            for (int i = 0; i < 6; i++) gr[i] = reloc_wave_sum(gr[i]);
-            double step;
-            if (!pnp_gn_update(H, gr, R, t, &step) || step < 1e-12) break;
-        }
-        n = reloc_select(g, R, t, xyz, qkps, q, p, m, fl);
-    }
-    if (threadIdx.x == 0) {
-        res->ninl[c] = n;
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) res->pose[c][i * 4 + j] = R[i * 3 + j];
-            res->pose[c][i * 4 + 3] = t[i];
-        }
-    }
-}
-
-// the winner (most final inliers, ties to the lower position) and its per-query-keypoint map point and inlier flag
-__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                      const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                      const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
-                                                      int32_t* __restrict__ qpt, uint8_t* __restrict__ qinl) {
-    __shared__ int win;
-    if (threadIdx.x == 0) {
-        int w = -1;
-        for (int c = 0; c < res->n_cand; c++)
-            if (w < 0 || res->ninl[c] > res->ninl[w] || (res->ninl[c] == res->ninl[w] && res->cand[c] < res->cand[w])) w = c;
-        win = w;
-        res->win = w;
-    }
-    __syncthreads();
-    const int w = win, k = w >= 0 ? res->cand[w] : -1, s = k >= 0 ? pos_slot[k] : 0;
-    const int nq = min(kcnt[spare], row);
-    for (int q = threadIdx.x; q < nq; q += 256) {
-        qpt[q] = k >= 0 ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
-        qinl[q] = 0;
-    }
-    __syncthreads();
-    if (w < 0 || !res->best[w]) return;
-    const int m = res->ncorr[w];
-    for (int j = threadIdx.x; j < m; j += 256) qinl[cq[(size_t)w * row + j]] = cinl[(size_t)w * row + j];
-}
-
-extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, mo_map_reloc_out* out) {
-    if (!m) return MO_ERR_ARG;
-    mo_ctx* c = m->c;
-    if (!f || !K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
-    if (prm->max_candidates < 1 || prm->max_candidates > RL_MAX_CAND) return mo_fail(c, MO_ERR_ARG, "max_candidates must be in 1 .. 64");
-    if (prm->n_hyp < 1 || prm->n_hyp > (1 << 20)) return mo_fail(c, MO_ERR_ARG, "n_hyp must be in 1 .. 2^20");
-    if (!(prm->thr_px >= 0.0)) return mo_fail(c, MO_ERR_ARG, "thr_px must be >= 0");
-    RelocGeom g;
-    {
-        const double* A = K;
-        const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
-        const double det = A[0] * c0 + A[1] * c1 + A[2] * c2;
-        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return mo_fail(c, MO_ERR_ARG, "K is singular");
-        const double inv[9] = {c0, A[2] * A[7] - A[1] * A[8], A[1] * A[5] - A[2] * A[4],
-                               c1, A[0] * A[8] - A[2] * A[6], A[2] * A[3] - A[0] * A[5],
-                               c2, A[1] * A[6] - A[0] * A[7], A[0] * A[4] - A[1] * A[3]};
-        for (int i = 0; i < 9; i++) { g.K[i] = K[i]; g.Kinv[i] = inv[i] / det; }
-        g.thr2 = prm->thr_px * prm->thr_px;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HostClock clk(c);
-    const int nc = prm->max_candidates;
-    for (int i = 0; i < 12; i++) out->pose[i] = NAN;
-    out->ok = 0; out->kf_pos = -1; out->n_cand = 0; out->n_corr = 0; out->n_inliers = 0; out->from_token = 0;
-    int rs, n, rc;
-    if ((rc = mo_frame_lookup(c, f, "frame", &rs, &n))) return rc;
-    out->from_token = rs >= 0;
-    if (out->point) for (int i = 0; i < n; i++) out->point[i] = -1;
-    if (out->inlier) std::memset(out->inlier, 0, (size_t)n);
-    for (int i = 0; i < nc; i++) {
-        if (out->cand_pos) out->cand_pos[i] = -1;
-        if (out->cand_score) out->cand_score[i] = 0;
-        if (out->cand_inliers) out->cand_inliers[i] = 0;
-    }
-    const int n_kf = (int)m->pos_slot.size();
-    if (n == 0 || n_kf == 0) return MO_OK;   // nothing to match: not relocalized, not an error
-    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    if ((rc = kf_reserve(m, n, m->n_slots))) return rc;   // (a wider row restrides the store; the map itself is unchanged)
-    const int spare = m->kslots, row = m->row;
-    mo_stage_begin(c);
-    if ((rc = mo_frame_copy_rows(c, f, rs, n, m->kkps + (size_t)spare * row, m->kdesc + (size_t)spare * row * 32))) return rc;
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + spare), n, 1, c->stream));
-    const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_kf * row, cand_n = (size_t)nc * row;
-    if ((rc = reserve(c, m->rl_tab, m->rl_tab_bytes, tab_n * 4)) || (rc = reserve(c, m->rl_qf, m->rl_qf_bytes, (size_t)n_kf * 4)) ||
-        (rc = reserve(c, m->rl_midx, m->rl_midx_bytes, pair_n * 8)) || (rc = reserve(c, m->rl_mdist, m->rl_mdist_bytes, pair_n * 8)) ||
-        (rc = reserve(c, m->rl_mpass, m->rl_mpass_bytes, pair_n)) || (rc = reserve(c, m->rl_score, m->rl_score_bytes, (size_t)n_kf * 4)) ||
-        (rc = reserve(c, m->rl_cq, m->rl_cq_bytes, cand_n * 4)) || (rc = reserve(c, m->rl_cp, m->rl_cp_bytes, cand_n * 4)) ||
-        (rc = reserve(c, m->rl_cinl, m->rl_cinl_bytes, cand_n)) || (rc = reserve(c, m->rl_qpt, m->rl_qpt_bytes, (size_t)row * 4)) ||
-        (rc = reserve(c, m->rl_qinl, m->rl_qinl_bytes, (size_t)row)))
-        return rc;
-    if (!m->rl_res) {
-        HIPCHK(c, hipMalloc((void**)&m->rl_res, sizeof(RelocRes)));
-        HIPCHK(c, hipHostMalloc((void**)&m->h_rl, sizeof(RelocRes), hipHostMallocDefault));
-    }
-    if ((rc = upload_pos_slot(m))) return rc;
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)m->rl_tab, INT_MAX, tab_n, c->stream));
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)m->rl_qf, spare, (size_t)n_kf, c->stream));
-    const MapPts& src = m->P[m->cur];
-    if (m->n_pts > 0)
-        hipLaunchKernelGGL(k_reloc_point_of, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf,
-                           m->kcnt, row, m->rl_tab);
-    HIPCHK(c, hipGetLastError());
-    mo_stage_mark(c, "reloc_point_of");
-    if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, m->kcnt, m->rl_qf, m->d_pos_slot, 0, 0, n_kf, row, prm->ratio,
-                                 m->rl_midx, m->rl_mdist, m->rl_mpass)))
-        return rc;
-    mo_stage_mark(c, "reloc_match");
-    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab, m->rl_score);
-    hipLaunchKernelGGL(k_reloc_rank, dim3(1), dim3(256), 0, c->stream, m->rl_score, n_kf, nc, m->rl_res);
-    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab,
-                       m->rl_res, m->rl_cq, m->rl_cp);
-    HIPCHK(c, hipGetLastError());
-    mo_stage_mark(c, "reloc_candidates");
-    const mo_keypoint* qk = m->kkps + (size_t)spare * row;
-    hipLaunchKernelGGL(k_reloc_hyp, dim3((unsigned)((prm->n_hyp + RL_HYP_WAVES - 1) / RL_HYP_WAVES), nc), dim3(64 * RL_HYP_WAVES), 0, c->stream, g, src.xyz, qk,
-                       row, prm->n_hyp, prm->seed, m->rl_cq, m->rl_cp, m->rl_res);
-    HIPCHK(c, hipGetLastError());
-    mo_stage_mark(c, "reloc_p3p");
-    hipLaunchKernelGGL(k_reloc_refine, dim3(nc), dim3(64), 0, c->stream, g, src.xyz, qk, row, prm->seed, m->rl_cq, m->rl_cp, m->rl_cinl, m->rl_res);
-    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, m->rl_midx, m->rl_mpass, m->rl_tab, m->rl_cq,
-                       m->rl_cinl, m->rl_res, m->rl_qpt, m->rl_qinl);
-    HIPCHK(c, hipGetLastError());
-    mo_stage_mark(c, "reloc_refine");
-    HIPCHK(c, hipMemcpyAsync(m->h_rl, m->rl_res, sizeof(RelocRes), hipMemcpyDeviceToHost, c->stream));
-    if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, m->rl_qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, m->rl_qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
-    const RelocRes& r = *m->h_rl;
-    out->n_cand = r.n_cand;
-    for (int i = 0; i < r.n_cand; i++) {
-        if (out->cand_pos) out->cand_pos[i] = r.cand[i];
-        if (out->cand_score) out->cand_score[i] = r.score[i];
-        if (out->cand_inliers) out->cand_inliers[i] = r.ninl[i];
-    }
-    if (r.win >= 0) {
-        out->kf_pos = r.cand[r.win];
-        out->n_corr = r.ncorr[r.win];
-        out->n_inliers = r.ninl[r.win];
-        for (int i = 0; i < 12; i++) out->pose[i] = r.pose[r.win][i];
-        out->ok = r.ninl[r.win] >= prm->min_inliers && r.best[r.win] != 0;
-    }
     return MO_OK;
 }

@@ -1,14 +1,61 @@
-// map_store.h -- the device-resident map (mo_map) shared by map_kernels.hip (growth, cull, relocalization), map_track.hip
-// (tracking against the map) and map_ba.hip (bundle adjustment): the stores, their scratch and the helpers that grow them.  Private to the library.
+// map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
+// map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations) and map_io.hip (PLY
+// text).  Here: the owning buffer types, the stores, the one reader of an observation, the helpers every map kernel file shares.
+// Private to the library.
 #pragma once
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "common.h"
 
+// A device buffer that owns its memory: freed by its destructor, never copied.  Kernels and copies receive the raw pointer (the
+// conversion).  Sizes are element counts.
+template <class T> struct DevBuf {
+    T* p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) hipFree(p); }
+    operator T*() const { return p; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    // room for n elements, the contents dropped; grows by half at least (the old block is freed before the new one is made)
+    int reserve(mo_ctx* c, size_t n) {
+        size_t need = n * sizeof(T);
+        if (p && need <= bytes) return MO_OK;
+        need = std::max(need, bytes + bytes / 2);
+        return mo_reserve(c, p, bytes, need);
+    }
+    // a new block of n elements that keeps the first `keep`: allocated, copied on the context stream, synchronised, the old one freed
+    int regrow(mo_ctx* c, size_t n, size_t keep) {
+        DevBuf q;
+        q.bytes = std::max(n * sizeof(T), (size_t)16);
+        HIPCHK(c, hipMalloc((void**)&q.p, q.bytes));
+        if (p && keep) HIPCHK(c, hipMemcpyAsync(q.p, p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+        if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
+        swap(q);
+        return MO_OK;
+    }
+};
+
+// a pinned host block, made once
+template <class T> struct PinnedBuf {
+    T* p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) hipHostFree(p); }
+    operator T*() const { return p; }
+    int reserve(mo_ctx* c, size_t n) {
+        if (!p) HIPCHK(c, hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault));
+        return MO_OK;
+    }
+};
+
 // status block (device, int32): live counts of the call in flight
 enum { ST_NPTS = 0, ST_NOBS, ST_NNEW, ST_ERR, ST_KEPT, ST_KOBS, ST_NLIST, ST_NWORDS = 8 };
 
+// one copy of the map store as the kernels receive it (by value)
 struct MapPts {
     float* xyz = nullptr; uint8_t* col = nullptr; int32_t* id = nullptr; int32_t* dkf = nullptr; int32_t* drow = nullptr;
     int32_t* off = nullptr;                           // [pcap + 1]
@@ -16,73 +63,83 @@ struct MapPts {
     size_t pcap = 0, ocap = 0;
 };
 
-struct RelocRes;  // per-call results of mo_map_relocalize (map_kernels.hip)
-struct TrackBufs; // scratch of mo_map_track (map_track.hip)
-struct BaBufs;    // scratch of mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
+// ... and its storage (map_pts_reserve grows it)
+struct MapPtsStore {
+    DevBuf<float> xyz; DevBuf<uint8_t> col; DevBuf<int32_t> id, dkf, drow, off, okf, okp;
+    size_t pcap = 0, ocap = 0;
+    MapPts view() const { return MapPts{xyz, col, id, dkf, drow, off, okf, okp, pcap, ocap}; }
+};
+
+// scratch of one feature each, made on its first call and freed with the map (map_scratch_free: `delete`, next to the struct)
+struct RelocBufs;   // mo_map_relocalize (map_reloc.hip)
+struct TrackBufs;   // mo_map_track (map_track.hip)
+struct BaBufs;      // mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
+void map_scratch_free(RelocBufs* b);
+void map_scratch_free(TrackBufs* b);
+void map_scratch_free(BaBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
     // keyframe store
     int row = 0, kslots = 0, n_slots = 0;
-    mo_keypoint* kkps = nullptr; uint8_t* kdesc = nullptr; int32_t* kcnt = nullptr; double* kP = nullptr;
+    DevBuf<mo_keypoint> kkps; DevBuf<uint8_t> kdesc; DevBuf<int32_t> kcnt; DevBuf<double> kP;
     std::vector<int32_t> h_kcnt;
     std::vector<int32_t> pos_slot;                    // keyframe position -> slot
-    int32_t* d_pos_slot = nullptr; size_t pos_slot_bytes = 0;
+    DevBuf<int32_t> d_pos_slot;
     // the previous and the new keyframe image (colours of the grown points)
-    uint8_t* img[2] = {nullptr, nullptr}; size_t img_bytes[2] = {0, 0}; int img_w[2] = {0, 0}, img_h[2] = {0, 0}, img_ch[2] = {0, 0};
+    DevBuf<uint8_t> img[2]; int img_w[2] = {0, 0}, img_h[2] = {0, 0}, img_ch[2] = {0, 0};
     int img_cur = 0;
     // map store
-    MapPts P[2]; int cur = 0;
+    MapPtsStore P[2]; int cur = 0;
     int64_t n_pts = 0, n_obs = 0;
     int64_t id_bound = 0;                             // every id < id_bound (the first-point table of the keyframe counts)
     // per-keyframe lists of the last cull
     // two sets: a chain writes the set lcur ^ 1, a successful call flips lcur (after MO_ERR_INDEX the previous lists stay readable)
-    int32_t* loff[2] = {nullptr, nullptr}; size_t loff_bytes[2] = {0, 0}; int32_t* lids[2] = {nullptr, nullptr}; size_t lids_bytes[2] = {0, 0};
+    DevBuf<int32_t> loff[2], lids[2];
     int lcur = 0, list_rows = 0;
-    int32_t* kf_red = nullptr; size_t kf_red_bytes = 0;
+    DevBuf<int32_t> kf_red;
     // scratch
-    int32_t* st = nullptr;                            // [ST_NWORDS] status
-    int32_t* keep = nullptr; int32_t* kobs = nullptr; int32_t* rank = nullptr; int32_t* obase = nullptr;
-    size_t keep_bytes = 0, kobs_bytes = 0, rank_bytes = 0, obase_bytes = 0;
-    int32_t* part = nullptr; size_t part_bytes = 0;
-    int32_t* ent_id = nullptr; size_t ent_bytes = 0;  // id of the point of every observation entry (compacted map)
-    int32_t* hist = nullptr; int32_t* hbase = nullptr; size_t hist_bytes = 0, hbase_bytes = 0;
-    int32_t* first = nullptr; size_t first_bytes = 0;
+    DevBuf<int32_t> st;                               // [ST_NWORDS] status
+    DevBuf<int32_t> keep, kobs, rank, obase;
+    DevBuf<int32_t> part;                             // tile sums of the device-wide scan
+    DevBuf<int32_t> ent_id;                           // id of the point of every observation entry (compacted map)
+    DevBuf<int32_t> hist, hbase, first;
     // growth step
-    int32_t* midx = nullptr; int32_t* mdist = nullptr; uint8_t* mpass = nullptr; uint8_t* inl = nullptr; float* gpts = nullptr;
-    double* F = nullptr; int32_t* gnp = nullptr;
-    size_t midx_bytes = 0, mdist_bytes = 0, mpass_bytes = 0, inl_bytes = 0, gpts_bytes = 0, F_bytes = 0, gnp_bytes = 0;
-    int32_t* h_stat = nullptr;                        // pinned [ST_NWORDS]
-    // relocalization (mo_map_relocalize), grown with the map
-    int32_t* rl_tab = nullptr; size_t rl_tab_bytes = 0;                        // point_of [slot][row]
-    int32_t* rl_qf = nullptr; size_t rl_qf_bytes = 0;                          // [n_kf] query frame of every pair: the spare slot
-    int32_t* rl_midx = nullptr; int32_t* rl_mdist = nullptr; uint8_t* rl_mpass = nullptr;  // [n_kf][row] matcher outputs
-    size_t rl_midx_bytes = 0, rl_mdist_bytes = 0, rl_mpass_bytes = 0;
-    int32_t* rl_score = nullptr; size_t rl_score_bytes = 0;                    // [n_kf] |C_k|
-    int32_t* rl_cq = nullptr; int32_t* rl_cp = nullptr; uint8_t* rl_cinl = nullptr;  // [candidate][row] C_k (query, point), final inliers
-    size_t rl_cq_bytes = 0, rl_cp_bytes = 0, rl_cinl_bytes = 0;
-    int32_t* rl_qpt = nullptr; uint8_t* rl_qinl = nullptr; size_t rl_qpt_bytes = 0, rl_qinl_bytes = 0;  // [row] per query keypoint
-    RelocRes* rl_res = nullptr; RelocRes* h_rl = nullptr;                     // device / pinned
-    TrackBufs* tk = nullptr;                                                   // tracking (mo_map_track), made on first use
-    BaBufs* ba = nullptr;                                                      // bundle adjustment (map_ba.hip), made on first use
+    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass, inl; DevBuf<float> gpts;
+    DevBuf<double> F; DevBuf<int32_t> gnp;
+    PinnedBuf<int32_t> h_stat;                        // [ST_NWORDS]
+    RelocBufs* rl = nullptr;
+    TrackBufs* tk = nullptr;
+    BaBufs* ba = nullptr;
+    // (mo_map_destroy selects the device and drains the stream first)
+    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); }
 };
 
-template <class T> static int reserve(mo_ctx* c, T*& p, size_t& have, size_t need) {
-    if (p && need <= have) return MO_OK;
-    need = std::max(need, have + have / 2);
-    return mo_reserve(c, p, have, need);
+// ---- the one reader of an observation -----------------------------------------------------------------------------------------------
+// Observation o of a map names keyframe position okf[o] and row okp[o] of that keyframe; negative values index from the end (Python
+// indexing); anything out of range names nothing.  Returns OBS_OK with the position, the keyframe's slot and the row, else which
+// index was out of range (the values are the cull's ST_ERR bits; every other caller skips the observation).
+enum { OBS_OK = 0, OBS_BAD_KF = 1, OBS_BAD_KP = 2 };
+__device__ __forceinline__ int map_obs(const MapPts& src, int o, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
+                                       int* pos, int* slot, int* kp) {
+    int kf = src.okf[o];
+    if (kf < 0) kf += n_kf;
+    if (kf < 0 || kf >= n_kf) return OBS_BAD_KF;
+    const int s = pos_slot[kf];
+    int r = src.okp[o];
+    const int nk = kcnt[s];
+    if (r < 0) r += nk;
+    if (r < 0 || r >= nk) return OBS_BAD_KP;
+    *pos = kf; *slot = s; *kp = r;
+    return OBS_OK;
 }
 
-// grow a buffer keeping its first `keep` bytes (stream-ordered copy)
-template <class T> static int regrow(mo_ctx* c, T*& p, size_t old_bytes, size_t new_bytes, size_t keep) {
-    T* q = nullptr;
-    HIPCHK(c, hipMalloc((void**)&q, std::max(new_bytes, (size_t)16)));
-    if (p && keep) HIPCHK(c, hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, c->stream));
-    if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p)); }
-    p = q;
-    (void)old_bytes;
-    return MO_OK;
+// ---- fixed-order f64 wave sum: lane 0's shuffle tree, the same on every run; lane 0 holds the sum, wave_sum_all gives it to every lane
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
 }
+__device__ __forceinline__ double wave_sum_all(double v) { return __shfl(wave_sum(v), 0, 64); }
 
 // ---- block scans (one-block exclusive scan of int32 in thread order, used by the device-wide scan and the compactions)
 __device__ __forceinline__ int wave_incl_scan(int v) {
@@ -114,14 +171,34 @@ __device__ __forceinline__ int block_excl_scan(int v, int* lds_waves, int* total
     return r;
 }
 
-// map_kernels.hip: the keyframe store grown to `rows` per slot and `slots` slots (+ the spare slot a query frame is staged in); the
-// position -> slot table on the device
+// ---- map_kernels.hip ---------------------------------------------------------------------------------------------------------------
+// the keyframe store grown to `rows` per slot and `slots` slots (+ the spare slot a query frame is staged in); the position -> slot
+// table on the device
 int kf_reserve(mo_map* m, int rows, int slots);
 int upload_pos_slot(mo_map* m);
-// map_kernels.hip: the device-wide exclusive scan of int32 (total into *d_total) and the growth of one copy of the map store
+// the device-wide exclusive scan of int32 (total into *d_total) and the growth of one copy of the map store
 int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total);
 int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
-// map_track.hip: frees the tracking scratch (mo_map_destroy)
-void map_track_free(mo_map* m);
-// map_ba.hip: frees the bundle-adjustment scratch (mo_map_destroy)
-void map_ba_free(mo_map* m);
+
+// A query frame staged in the spare keyframe slot (mo_map_track, mo_map_relocalize; read-only on the map): the frame looked up,
+// *from_token set, defaults(n) run (the caller's per-keypoint output defaults), then - unless there is nothing to search, which leaves
+// *fk NULL and returns MO_OK - the int32 bound checked, the store grown (a wider row restrides it), the position table uploaded, the
+// call's stage set opened and the rows copied to *fk / *fdesc with kcnt[spare] = n.  The spare slot is m->kslots, its stride m->row.
+template <class Defaults> int map_stage_frame(mo_map* m, const mo_frame_ref* f, bool need_points, int32_t* from_token, Defaults defaults, int* n,
+                                              mo_keypoint** fk, uint8_t** fdesc) {
+    mo_ctx* c = m->c;
+    int rs, rc;
+    *fk = nullptr; *fdesc = nullptr;
+    if ((rc = mo_frame_lookup(c, f, "frame", &rs, n))) return rc;
+    *from_token = rs >= 0;
+    defaults(*n);
+    if (*n == 0 || m->pos_slot.empty() || (need_points && m->n_pts == 0)) return MO_OK;
+    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    if ((rc = kf_reserve(m, *n, m->n_slots)) || (rc = upload_pos_slot(m))) return rc;
+    const size_t at = (size_t)m->kslots * m->row;
+    mo_stage_begin(c);
+    if ((rc = mo_frame_copy_rows(c, f, rs, *n, m->kkps + at, m->kdesc + at * 32))) return rc;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + m->kslots), *n, 1, c->stream));
+    *fk = m->kkps + at; *fdesc = m->kdesc + at * 32;
+    return MO_OK;
+}

@@ -1,6 +1,6 @@
 // map_track.hip -- tracking a frame against the device map (mo_map_track in include/vslam_amd.h): ORB-SLAM2's search by projection and
 // its monocular pose-only PoseOptimization, on the map as it stands.  Read-only on the map; the frame is staged in the spare keyframe
-// slot (kf_reserve), like mo_map_relocalize's.
+// slot (map_stage_frame), like mo_map_relocalize's.
 //
 // Chain (one synchronisation, the copy-out; the retry and the early exits are flags in TrackRes that every later kernel reads first):
 //   k_trk_init      result block, per-keypoint keys and outputs
@@ -20,7 +20,7 @@
 
 #include "common.h"
 #include "map_store.h"
-#include "pnp.h"
+#include "ba.h"   // ba_info (pnp.h comes with it)
 
 #define TK_GX 64                        // ORB-SLAM2's FRAME_GRID_COLS x FRAME_GRID_ROWS
 #define TK_GY 48
@@ -54,27 +54,18 @@ struct TrkMatch {                         // one match in keypoint order (32 B):
 };
 
 struct TrackBufs {
-    uint8_t* rep = nullptr; size_t rep_bytes = 0;                  // [point][32] representative descriptors
-    int32_t* oct = nullptr; size_t oct_bytes = 0;                  // [point] ref_octave (TK_NOT_LOCAL: not in the local map)
-    int32_t* cell = nullptr; size_t cell_bytes = 0;                // [TK_CELLS + 1] first sorted entry of every cell
-    int32_t* sorted = nullptr; size_t sorted_bytes = 0;            // [row] keypoint indices by cell, index order inside a cell
-    unsigned long long* key = nullptr; size_t key_bytes = 0;       // [row] (dist << 32) | point of the claim on each keypoint
-    TrkMatch* match = nullptr; size_t match_bytes = 0;             // [row]
-    uint8_t* minl = nullptr; size_t minl_bytes = 0;                // [row] inlier flag of every match
-    int32_t* qpt = nullptr; int32_t* qdist = nullptr; uint8_t* qinl = nullptr;
-    size_t qpt_bytes = 0, qdist_bytes = 0, qinl_bytes = 0;
-    TrackRes* res = nullptr; TrackRes* h_res = nullptr;            // device / pinned
+    DevBuf<uint8_t> rep;                  // [point][32] representative descriptors
+    DevBuf<int32_t> oct;                  // [point] ref_octave (TK_NOT_LOCAL: not in the local map)
+    DevBuf<int32_t> cell;                 // [TK_CELLS + 1] first sorted entry of every cell
+    DevBuf<int32_t> sorted;               // [row] keypoint indices by cell, index order inside a cell
+    DevBuf<unsigned long long> key;       // [row] (dist << 32) | point of the claim on each keypoint
+    DevBuf<TrkMatch> match;               // [row]
+    DevBuf<uint8_t> minl;                 // [row] inlier flag of every match
+    DevBuf<int32_t> qpt, qdist; DevBuf<uint8_t> qinl;   // [row] per frame keypoint
+    DevBuf<TrackRes> res; PinnedBuf<TrackRes> h_res;
 };
 
-void map_track_free(mo_map* m) {
-    TrackBufs* b = m->tk;
-    if (!b) return;
-    void* bufs[] = {b->rep, b->oct, b->cell, b->sorted, b->key, b->match, b->minl, b->qpt, b->qdist, b->qinl, b->res};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (b->h_res) hipHostFree(b->h_res);
-    delete b;
-    m->tk = nullptr;
-}
+void map_scratch_free(TrackBufs* b) { delete b; }
 
 // a pass's kernels run when the call has not ended and, for the second attempt, when the first asked for it
 __device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
@@ -97,17 +88,11 @@ __device__ __forceinline__ int trk_cy(double y, int h) {
     return v >= 0.0 ? (v < TK_GY ? (int)v : TK_GY - 1) : 0;
 }
 
-// scale_factor^o and the information 1 / scale_factor^(2 o), as repeated products from 1.0 (negative octaves as 0)
+// scale_factor^o as repeated products from 1.0 (negative octaves as 0); the information of an octave is ba.h's ba_info
 __device__ __forceinline__ double trk_scale(double sf, int o) {
     double s = 1.0;
     for (int i = 0; i < o; i++) s *= sf;
     return s;
-}
-__device__ __forceinline__ double trk_info(double sf, int o) {
-    const double sf2 = sf * sf;
-    double s = 1.0;
-    for (int i = 0; i < o; i++) s *= sf2;
-    return 1.0 / s;
 }
 
 __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes* __restrict__ res, unsigned long long* __restrict__ key,
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes*
     }
 }
 
-// one thread per point: valid observations read like the cull reads them; local when one of them is at a position >= lo_pos.  The
+// one thread per point: its valid observations (map_obs); local when one of them is at a position >= lo_pos.  The
 // representative is ComputeDistinctiveDescriptors' choice: the observation with the smallest median distance to all of them, ties to
 // the earlier.  Each median is found by bisection on the distance value (count of distances <= v), only below the best so far.
 __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
@@ -137,16 +122,8 @@ __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const in
         const int o0 = src.off[i], o1 = src.off[i + 1];
         // the (slot * row + keypoint) entry of observation o, -1 when it names nothing
         auto entry = [&](int o, int* pos) -> long long {
-            int kf = src.okf[o];
-            if (kf < 0) kf += n_kf;
-            if (kf < 0 || kf >= n_kf) return -1;
-            const int s = pos_slot[kf];
-            int kp = src.okp[o];
-            const int nk = kcnt[s];
-            if (kp < 0) kp += nk;
-            if (kp < 0 || kp >= nk) return -1;
-            *pos = kf;
-            return (long long)s * row + kp;
+            int s, kp;
+            return map_obs(src, o, pos_slot, n_kf, kcnt, pos, &s, &kp) ? -1 : (long long)s * row + kp;
         };
         int nv = 0, pos = 0;
         long long best = -1;
@@ -331,12 +308,6 @@ __global__ __launch_bounds__(1024) void k_trk_compact(TrackPrm prm, int pass, in
     }
 }
 
-// a fixed-order wave sum every lane receives (lane 0's tree, broadcast)
-__device__ __forceinline__ double trk_wave_sum(double v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
-    return __shfl(v, 0, 64);
-}
-
 // inlier test of one match under (R, t): depth > 0 and information * squared pixel error <= chi2
 __device__ __forceinline__ bool trk_inlier(const TrackPrm& prm, const double* R, const double* t, const TrkMatch& mt) {
     const double X = mt.X, Y = mt.Y, Z = mt.Z;
@@ -346,7 +317,7 @@ __device__ __forceinline__ bool trk_inlier(const TrackPrm& prm, const double* R,
     const double* K = prm.K;
     const double p0 = K[0] * xc + K[1] * yc + K[2] * zc, p1 = K[3] * xc + K[4] * yc + K[5] * zc, p2 = K[6] * xc + K[7] * yc + K[8] * zc;
     const double du = p0 / p2 - (double)mt.x, dv = p1 / p2 - (double)mt.y;
-    return zc > 0.0 && trk_info(prm.sf, mt.octave) * (du * du + dv * dv) <= prm.chi2;
+    return zc > 0.0 && ba_info(prm.sf, mt.octave) * (du * du + dv * dv) <= prm.chi2;
 }
 
 // one block of 256: Optimizer::PoseOptimization (monocular, pose only) with Gauss-Newton steps; the pass's outputs
@@ -376,9 +347,9 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
             for (int j = tid; j < m; j += TK_REFINE_BLOCK) {
                 if (!minl[j]) continue;
                 const TrkMatch mt = match[j];
-                pnp_gn_accumulate_w(prm.K, R, t, mt.X, mt.Y, mt.Z, mt.x, mt.y, trk_info(prm.sf, mt.octave), huber2, a, a + 21);
+                pnp_gn_accumulate_w(prm.K, R, t, mt.X, mt.Y, mt.Z, mt.x, mt.y, ba_info(prm.sf, mt.octave), huber2, a, a + 21);
             }
-            for (int i = 0; i < 27; i++) a[i] = trk_wave_sum(a[i]);
+            for (int i = 0; i < 27; i++) a[i] = wave_sum_all(a[i]);
             if (lane == 0)
                 for (int i = 0; i < 27; i++) red[wv][i] = a[i];
             __syncthreads();
@@ -449,35 +420,23 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
         out->pass_cand[k] = 0; out->pass_matches[k] = 0; out->pass_inliers[k] = 0;
     }
     out->n_pass_run = 0; out->n_local = 0; out->ok = 0; out->from_token = 0;
-    int rs, n, rc;
-    if ((rc = mo_frame_lookup(c, f, "frame", &rs, &n))) return rc;
-    out->from_token = rs >= 0;
-    if (out->point) for (int i = 0; i < n; i++) out->point[i] = -1;
-    if (out->dist) for (int i = 0; i < n; i++) out->dist[i] = -1;
-    if (out->inlier) std::memset(out->inlier, 0, (size_t)n);
-    const int n_kf = (int)m->pos_slot.size();
-    if (n == 0 || n_kf == 0 || m->n_pts == 0) return MO_OK;   // nothing to search: not tracked, not an error
-    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    if ((rc = kf_reserve(m, n, m->n_slots))) return rc;   // (a wider row restrides the store; the map itself is unchanged)
-    const int spare = m->kslots, row = m->row;
+    int n, rc;
+    mo_keypoint* fk; uint8_t* fdesc;
+    auto defaults = [&](int nq) {
+        if (out->point) for (int i = 0; i < nq; i++) out->point[i] = -1;
+        if (out->dist) for (int i = 0; i < nq; i++) out->dist[i] = -1;
+        if (out->inlier) std::memset(out->inlier, 0, (size_t)nq);
+    };
+    if ((rc = map_stage_frame(m, f, true, &out->from_token, defaults, &n, &fk, &fdesc)) || !fk) return rc;   // (nothing to search: not tracked, not an error)
+    const int n_kf = (int)m->pos_slot.size(), row = m->row;
     if (!m->tk) m->tk = new TrackBufs();
     TrackBufs& b = *m->tk;
     const size_t np = (size_t)m->n_pts;
-    if ((rc = reserve(c, b.rep, b.rep_bytes, np * 32)) || (rc = reserve(c, b.oct, b.oct_bytes, np * 4)) ||
-        (rc = reserve(c, b.cell, b.cell_bytes, (TK_CELLS + 1) * 4)) || (rc = reserve(c, b.sorted, b.sorted_bytes, (size_t)row * 4)) ||
-        (rc = reserve(c, b.key, b.key_bytes, (size_t)row * 8)) || (rc = reserve(c, b.match, b.match_bytes, (size_t)row * sizeof(TrkMatch))) ||
-        (rc = reserve(c, b.minl, b.minl_bytes, (size_t)row)) || (rc = reserve(c, b.qpt, b.qpt_bytes, (size_t)row * 4)) ||
-        (rc = reserve(c, b.qdist, b.qdist_bytes, (size_t)row * 4)) || (rc = reserve(c, b.qinl, b.qinl_bytes, (size_t)row)))
+    if ((rc = b.rep.reserve(c, np * 32)) || (rc = b.oct.reserve(c, np)) || (rc = b.cell.reserve(c, TK_CELLS + 1)) || (rc = b.sorted.reserve(c, (size_t)row)) ||
+        (rc = b.key.reserve(c, (size_t)row)) || (rc = b.match.reserve(c, (size_t)row)) || (rc = b.minl.reserve(c, (size_t)row)) ||
+        (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qdist.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) ||
+        (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
         return rc;
-    if (!b.res) {
-        HIPCHK(c, hipMalloc((void**)&b.res, sizeof(TrackRes)));
-        HIPCHK(c, hipHostMalloc((void**)&b.h_res, sizeof(TrackRes), hipHostMallocDefault));
-    }
-    if ((rc = upload_pos_slot(m))) return rc;
-    mo_stage_begin(c);
-    mo_keypoint* fk = m->kkps + (size_t)spare * row;
-    uint8_t* fdesc = m->kdesc + (size_t)spare * row * 32;
-    if ((rc = mo_frame_copy_rows(c, f, rs, n, fk, fdesc))) return rc;
     TrackPrm p;
     for (int i = 0; i < 9; i++) p.K[i] = K[i];
     for (int i = 0; i < 12; i++) p.pose0[i] = pose0[i];
@@ -485,7 +444,7 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
     p.sf = prm->scale_factor; p.ratio = prm->ratio; p.chi2 = prm->chi2;
     p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist; p.min_matches = prm->min_matches;
     const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
-    const MapPts& src = m->P[m->cur];
+    const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
     hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
     hipLaunchKernelGGL(k_trk_rep, dim3(pblocks), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf, m->kcnt, row, m->kkps, m->kdesc,

@@ -1,4 +1,4 @@
-// Absolute pose from 2D-3D correspondences, shared by the relocalization kernels (map_kernels.hip) and the CPU test of the solver
+// Absolute pose from 2D-3D correspondences, shared by the relocalization kernels (map_reloc.hip) and the CPU test of the solver
 // (tests/native/pnp_check.cpp): the sampling stream, a P3P solver, the reprojection test and one Gauss-Newton step on SE(3).
 // Everything is f64; built with -ffp-contract=off on both sides, so a host build computes what the device computes.
 //
