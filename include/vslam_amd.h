@@ -392,6 +392,7 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *   mo_map_write_ply         utils.create_point_cloud_ply (utils.py:72-118) of the points with >= min_obs observations, byte for byte:
  *                            floats as Python's repr of the double value, colours as stored.
  *   mo_format_floats         that float formatting alone, one value per line (no GPU).
+ *   mo_map_fuse              duplicate map points merged, missing observations gained (the comment at its declaration below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
  *                            brute-force matching in place of the bag-of-words lookup); reads the map, never changes it.  The frame (by
  *                            token of a resident result slot, else the host arrays) is matched against every keyframe (query = the frame,
@@ -591,6 +592,56 @@ int mo_map_bundle_adjust(mo_map*, const double K[9], const double* poses, const 
  * stores (its cull validates the rows: MO_ERR_INDEX for one that does not exist).  The observation arrays are rebuilt into the other
  * copy of the map store by a scan and a scatter; one synchronisation. */
 int mo_map_add_observations(mo_map*, int kf_pos, int n, const int32_t* point, const int32_t* row);
+
+/* mo_map_fuse: map points that are the same 3D feature are merged, and points gain the observations they lack (ORB-SLAM2's
+ * LocalMapping::SearchInNeighbors / ORBmatcher::Fuse / MapPoint::Replace), on the map as it stands.  Opt-in: no other call runs it.
+ *   observations  read like the cull and mo_map_track read them (negative positions and rows count from the end; entries naming a position
+ *                 or row that does not exist are skipped; "valid" below means an entry that names something).
+ *   targets       the last `window` keyframe positions (0: every position).
+ *   local points  the points with a valid observation at a target: mo_map_track's local map, with its representative descriptor and
+ *                 ref_octave (ComputeDistinctiveDescriptors, ties to the earlier observation).
+ *   pairs         every (local point i, target k) where i has no valid observation at k.
+ *   candidate     a pair whose projection under the store's own P of k (what mo_map_add_keyframe stored or mo_map_bundle_adjust wrote
+ *                 back: the call takes no poses; f64, each row summed left to right, z = P[8..11] . (X, 1)) has z > 0 and u / z in [0, w),
+ *                 v / z in [0, h).
+ *   search        r = radius * scale_factor^ref_octave (repeated products from 1.0); the keypoints of k with |x - u| < r, |y - v| < r,
+ *                 |octave - ref_octave| <= 1 and information(octave) * ((x - u)^2 + (y - v)^2) <= chi2 (information = 1 /
+ *                 scale_factor^(2 octave), negative octaves as 0); best = the lowest Hamming distance to the representative, ties to the
+ *                 lower row; accepted when best <= max_dist.  No ratio test (Fuse has none).  An accepted pair is a proposal
+ *                 (i, k, row, dist).
+ *   claims        per (k, row) the proposal with the lowest (dist, i) wins; the others are dropped.
+ *   owner         of (k, row): the lowest map point with a valid observation (k, row) (mo_map_relocalize's point_of).  A winning
+ *                 proposal on an owned row is a merge edge {i, owner}; on a free row it is a gained observation (i, k, row).
+ *   components    the connected components of the merge edges over all points; survivor = the member with the most valid observations,
+ *                 ties to the lowest index.
+ *   merged list   of a survivor, in this order: (1) its own entries as stored (stale ones included, bytes unchanged); (2) the valid
+ *                 entries of the other members by (member index, insertion order), written as non-negative (position, row); (3) the gained
+ *                 observations of all members by (member index, position).  An entry of (2) or (3) is dropped when the list already holds
+ *                 a valid observation at its position (Replace's "already in keyframe").  A point in no merge edge is a component of one:
+ *                 it keeps (1) and takes (3).
+ *   writes        absorbed members are removed; survivors keep xyz, colour, id and descriptor reference; the map is compacted in index
+ *                 order into the other copy of the store, as the cull does.  The per-keyframe lists stay those of the last cull, as after
+ *                 mo_map_add_observations.  Points outside the local map and in no merge edge keep their bytes.
+ *   no work       an empty map or no keyframes: every count is 0.  No local point or no proposal: nothing is written, n_targets, n_local,
+ *                 n_pairs and n_cand are reported, the other counts are 0, into is the identity.  Never an error.
+ * Everything is decided on the device (later kernels read n_proposals first): no host round trip inside the call, one synchronisation -
+ * the copy-out.  Integer atomics only: two calls on equal maps give the same bytes. */
+typedef struct {
+    int32_t w, h;            /* a projection is a candidate only inside [0, w) x [0, h) */
+    int32_t window;          /* target keyframe positions, counted from the last (10); 0: all */
+    double radius;           /* search half-width at octave 0 (3.0) */
+    double scale_factor;     /* scales the window and the information (1.2) */
+    int32_t max_dist;        /* ORB-SLAM2's TH_LOW (50) */
+    double chi2;             /* gate on information * squared pixel distance (5.991) */
+} mo_map_fuse_params;
+typedef struct {
+    /* caller-allocated, may be NULL */
+    int32_t* into;           /* [map points before the call] the new index of the point each old point now is */
+    /* filled by the call */
+    int32_t n_targets, n_local, n_pairs, n_cand, n_proposals, n_gained, n_edges, n_absorbed;
+    int64_t n_points, n_obs; /* after the call */
+} mo_map_fuse_out;
+int mo_map_fuse(mo_map*, const mo_map_fuse_params*, mo_map_fuse_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

@@ -20,17 +20,13 @@
 
 #include "common.h"
 #include "map_store.h"
-#include "ba.h"   // ba_info (pnp.h comes with it)
+#include "map_search.h"   // the grid geometry, trk_ham / trk_cx / trk_cy / trk_scale, the launchers mo_map_fuse shares
+#include "ba.h"           // ba_info (pnp.h comes with it)
 
-#define TK_GX 64                        // ORB-SLAM2's FRAME_GRID_COLS x FRAME_GRID_ROWS
-#define TK_GY 48
-#define TK_CELLS (TK_GX * TK_GY)
 #define TK_GRID_BLOCK 1024
 #define TK_CELLS_PER_THREAD (TK_CELLS / TK_GRID_BLOCK)
 #define TK_MAX_PASS 4
 #define TK_REFINE_BLOCK 256
-#define TK_NOT_LOCAL INT_MIN            // octave slot of a point outside the local map
-#define TK_NONE 0xffffffffffffffffull   // keypoint key without a claim
 static_assert(TK_CELLS % TK_GRID_BLOCK == 0, "cells per thread");
 
 struct TrackPrm {
@@ -72,29 +68,6 @@ __device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
     return !res->ended && (attempt == 0 || res->retry);
 }
 
-__device__ __forceinline__ int trk_ham(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b) {
-    const uint4 a0 = *(const uint4*)a, a1 = *(const uint4*)(a + 16), b0 = *(const uint4*)b, b1 = *(const uint4*)(b + 16);
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-           __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// grid column / row of a coordinate: monotone in it, so the cells of [u - r, u + r] hold every keypoint with |x - u| < r
-__device__ __forceinline__ int trk_cx(double x, int w) {
-    const double v = x * TK_GX / w;
-    return v >= 0.0 ? (v < TK_GX ? (int)v : TK_GX - 1) : 0;
-}
-__device__ __forceinline__ int trk_cy(double y, int h) {
-    const double v = y * TK_GY / h;
-    return v >= 0.0 ? (v < TK_GY ? (int)v : TK_GY - 1) : 0;
-}
-
-// scale_factor^o as repeated products from 1.0 (negative octaves as 0); the information of an octave is ba.h's ba_info
-__device__ __forceinline__ double trk_scale(double sf, int o) {
-    double s = 1.0;
-    for (int i = 0; i < o; i++) s *= sf;
-    return s;
-}
-
 __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes* __restrict__ res, unsigned long long* __restrict__ key,
                                                   int32_t* __restrict__ qpt, int32_t* __restrict__ qdist, uint8_t* __restrict__ qinl) {
     for (int q = threadIdx.x; q < n; q += 256) { key[q] = TK_NONE; qpt[q] = -1; qdist[q] = -1; qinl[q] = 0; }
@@ -115,7 +88,7 @@ __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes*
 // the earlier.  Each median is found by bisection on the distance value (count of distances <= v), only below the best so far.
 __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
                                                  int row, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc, int lo_pos,
-                                                 uint8_t* __restrict__ rep, int32_t* __restrict__ oct, TrackRes* __restrict__ res) {
+                                                 uint8_t* __restrict__ rep, int32_t* __restrict__ oct, int32_t* __restrict__ n_local) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool local = false;
     if (i < n_pts) {
@@ -170,13 +143,19 @@ __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const in
         }
     }
     const unsigned long long b = __ballot(local);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&res->n_local, (int)__popcll(b));
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_local, (int)__popcll(b));
 }
 
-// one block: histogram of the cells (LDS), exclusive scan, scatter by LDS cursors, then every cell's run sorted by keypoint index (the
+// one block per grid: histogram of the cells (LDS), exclusive scan, scatter by LDS cursors, then every cell's run sorted by keypoint index (the
 // cursors' order is arrival order; the sort makes the layout the stable counting sort's)
-__global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* __restrict__ fk, int n, int w, int h, int32_t* __restrict__ cell,
+__global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* __restrict__ kkps, int row, const int32_t* __restrict__ kcnt,
+                                                            const int32_t* __restrict__ slots, int slot0, int w, int h, int32_t* __restrict__ cell,
                                                             int32_t* __restrict__ sorted) {
+    const int slot = slots ? slots[blockIdx.x] : slot0;
+    const mo_keypoint* __restrict__ fk = kkps + (size_t)slot * row;
+    const int n = min(kcnt[slot], row);
+    cell += (size_t)blockIdx.x * (TK_CELLS + 1);
+    sorted += (size_t)blockIdx.x * row;
     __shared__ int cur[TK_CELLS];
     __shared__ int lw[40];
     const int tid = threadIdx.x;
@@ -397,6 +376,21 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
     }
 }
 
+int trk_launch_rep(mo_map* m, const MapPts& src, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local) {
+    mo_ctx* c = m->c;
+    hipLaunchKernelGGL(k_trk_rep, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
+                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, lo_pos, rep, oct, n_local);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
+int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted) {
+    mo_ctx* c = m->c;
+    hipLaunchKernelGGL(k_trk_grid, dim3((unsigned)n_grids), dim3(TK_GRID_BLOCK), 0, c->stream, m->kkps, m->row, m->kcnt, slots, slot0, w, h, cell, sorted);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
 extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
                             mo_map_track_out* out) {
     if (!m) return MO_ERR_ARG;
@@ -447,10 +441,9 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
     const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
     hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
-    hipLaunchKernelGGL(k_trk_rep, dim3(pblocks), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf, m->kcnt, row, m->kkps, m->kdesc,
-                       lo_pos, b.rep, b.oct, b.res);
-    hipLaunchKernelGGL(k_trk_grid, dim3(1), dim3(TK_GRID_BLOCK), 0, c->stream, fk, n, prm->w, prm->h, b.cell, b.sorted);
-    HIPCHK(c, hipGetLastError());
+    if ((rc = trk_launch_rep(m, src, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
+        (rc = trk_launch_grid(m, nullptr, m->kslots, 1, prm->w, prm->h, b.cell, b.sorted)))   // (the staged frame: the spare slot)
+        return rc;
     mo_stage_mark(c, "track_prep");
     for (int k = 0; k < prm->n_pass; k++) {
         for (int a = 0; a < 2; a++) {

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize] [--track-map [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize] [--track-map [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -122,6 +122,8 @@ def main(argv=None):
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--local-ba", action="store_true", help="with --map --track-map: a tracked frame that becomes a keyframe hands its matches to "
                     "the map (add_keyframe(tracked=)), and local bundle adjustment (LocalMapper.bundle_adjust) runs after it")
+    ap.add_argument("--fuse", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, duplicate map points "
+                    "are merged and missing observations gained (LocalMapper.fuse_map_points), before the bundle adjustment of --local-ba")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
@@ -146,8 +148,11 @@ def main(argv=None):
         ap.error("--track-map needs --map")
     if args.local_ba and not args.track_map:
         ap.error("--local-ba needs --map and --track-map")
+    if args.fuse and not args.track_map:
+        ap.error("--fuse needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
     n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
+    n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
@@ -163,6 +168,14 @@ def main(argv=None):
         recent[:] = recent[-1:] + [ref_pose]
         if mapper is not None and idx % args.keyframe_every == 0:
             mapper.add_keyframe(frame, kps, desc, ref_pose)
+
+    def fuse(idx):
+        fi = mapper.fuse_map_points(window=args.ba_window)
+        n_fuse[0] += 1
+        n_fuse[1] += fi["n_absorbed"]
+        n_fuse[2] += fi["n_gained"]
+        print("frame %d: fuse %d absorbed, %d gained (%d proposals of %d candidates), %d map points"
+              % (idx, fi["n_absorbed"], fi["n_gained"], fi["n_proposals"], fi["n_cand"], fi["n_points"]))
 
     def track_map(frame, kps, desc, idx):
         """the frame against the device map from the predicted pose (ORB-SLAM2's TrackWithMotionModel + TrackLocalMap); on success its
@@ -180,6 +193,8 @@ def main(argv=None):
             if idx % args.keyframe_every == 0:
                 if args.local_ba:
                     mapper.add_keyframe(frame, kps, desc, T, tracked=(info["point"], info["inlier"]))
+                    if args.fuse:
+                        fuse(idx)
                     ba_ok, ba = mapper.bundle_adjust(window=args.ba_window)
                     n_ba[0] += 1
                     n_ba[1] += ba_ok
@@ -192,6 +207,8 @@ def main(argv=None):
                         recent[-1] = T
                 else:
                     mapper.add_keyframe(frame, kps, desc, T)
+                    if args.fuse:
+                        fuse(idx)
         return ok
 
     def relocalize(frame, kps, desc, idx):
@@ -275,6 +292,8 @@ def main(argv=None):
         print("map statistics: %s" % mapper.get_map_statistics())
         if args.local_ba:
             print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
+        if args.fuse:
+            print("fusion: %d calls, %d points absorbed, %d observations gained" % (n_fuse[0], n_fuse[1], n_fuse[2]))
     return state, poses, n_map
 
 

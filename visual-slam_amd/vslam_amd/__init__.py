@@ -113,6 +113,17 @@ class MapBaOut(C.Structure):
                 ("n_edges", C.c_int32), ("n_inliers", C.c_int32), ("steps", C.c_int32 * 2), ("accepted", C.c_int32 * 2), ("ok", C.c_int32)]
 
 
+class MapFuseParams(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("window", C.c_int32), ("radius", C.c_double), ("scale_factor", C.c_double),
+                ("max_dist", C.c_int32), ("chi2", C.c_double)]
+
+
+class MapFuseOut(C.Structure):
+    _fields_ = [("into", C.c_void_p), ("n_targets", C.c_int32), ("n_local", C.c_int32), ("n_pairs", C.c_int32), ("n_cand", C.c_int32),
+                ("n_proposals", C.c_int32), ("n_gained", C.c_int32), ("n_edges", C.c_int32), ("n_absorbed", C.c_int32),
+                ("n_points", C.c_int64), ("n_obs", C.c_int64)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -196,6 +207,7 @@ SIGNATURES = {
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
     "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mo_map_fuse": (_i, [_vp, _vp, _vp]),
 }
 
 _lib = None

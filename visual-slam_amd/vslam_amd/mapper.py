@@ -288,6 +288,82 @@ class LocalMapper:
             info["points"] = pts[:self._n_points]
         return bool(out.ok), info
 
+    # ---- fusion of duplicate map points ---------------------------------------------------------------------------------------------
+    def _valid_positions(self, a, i, counts):
+        """the keyframe positions map point i of the arrays a validly observes (the library's reading of an observation)"""
+        n_kf = len(counts)
+        out = set()
+        for o in range(int(a["obs_off"][i]), int(a["obs_off"][i + 1])):
+            k, r = int(a["obs_kf"][o]), int(a["obs_kp"][o])
+            k = k + n_kf if k < 0 else k
+            if not 0 <= k < n_kf:
+                continue
+            r = r + counts[k] if r < 0 else r
+            if 0 <= r < counts[k]:
+                out.add(k)
+        return out
+
+    def fuse_map_points(self, window=10, radius=3.0, scale_factor=1.2, max_dist=50, chi2=5.991, image_size=None):
+        """Merges map points that are the same 3D feature and gives points the observations they lack (ORB-SLAM2's SearchInNeighbors /
+        Fuse / Replace; mo_map_fuse in include/vslam_amd.h states the rules): every point the last `window` keyframes (0: all) see is
+        projected, under the store's own projection matrices, into each of those keyframes that does not observe it; a keypoint it
+        matches within `radius` (at octave 0), `chi2` and `max_dist` either belongs to another point - the two are merged, the one with
+        more observations survives and takes the other's - or to none, and becomes an observation of the point.  image_size as in
+        track_local_map.  The co-visibility graph follows: per changed point, the keyframe pairs that observe it after the call less
+        those that observed its parts before.
+        Returns info: n_targets, n_local, n_pairs, n_cand, n_proposals, n_gained, n_edges, n_absorbed, n_points, n_obs and `into`
+        (the new index of the point each old point now is)."""
+        if image_size is None:
+            if self.keyframes:
+                image_size = self.keyframes[-1]["image"].shape[1::-1]
+            else:
+                Km = np.asarray(self.camera_matrix, np.float64)
+                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        n0 = self._n_points
+        before = self.arrays() if n0 else None
+        into = np.arange(max(n0, 1), dtype=np.int32)
+        prm = V.MapFuseParams(int(image_size[0]), int(image_size[1]), int(window), float(radius), float(scale_factor), int(max_dist), float(chi2))
+        out = V.MapFuseOut(into.ctypes.data)
+        self._check(self.lib.mo_map_fuse(self._h, C.byref(prm), C.byref(out)))
+        into = into[:n0]
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+        info = {k: int(getattr(out, k)) for k in ("n_targets", "n_local", "n_pairs", "n_cand", "n_proposals", "n_gained", "n_edges", "n_absorbed",
+                                                  "n_points", "n_obs")}
+        info["into"] = into
+        if info["n_proposals"]:
+            self._fuse_co_visibility(before, self.arrays(), into)
+        return info
+
+    def _fuse_co_visibility(self, before, after, into):
+        slot_of = {id(r): s for s, r in enumerate(self._records)}
+        counts = [self._rec_n[slot_of[id(kf)]] for kf in self.keyframes]
+        members = np.bincount(into, minlength=len(after["id"]))
+        n_before, n_after = np.diff(before["obs_off"]), np.diff(after["obs_off"])
+        changed = np.unique(into[(members[into] > 1) | (n_before != n_after[into])])
+        if not len(changed):
+            return
+        order = np.argsort(into, kind="stable")
+        first = np.searchsorted(into[order], changed)
+        delta = defaultdict(int)
+
+        def pairs(pos, sign):
+            pos = sorted(pos)
+            for x in range(len(pos)):
+                for y in range(x + 1, len(pos)):
+                    delta[(pos[x], pos[y])] += sign
+        for j, f in zip(changed.tolist(), first.tolist()):
+            pairs(self._valid_positions(after, j, counts), 1)
+            for i in order[f:f + members[j]].tolist():
+                pairs(self._valid_positions(before, i, counts), -1)
+        g = self.co_visibility_graph
+        for (p, q), d in delta.items():
+            if d:
+                a, b = self.keyframes[p]["id"], self.keyframes[q]["id"]
+                g[a][b] = max(0, g[a][b] + d)
+                g[b][a] = max(0, g[b][a] + d)
+
     def _cull_keyframes(self, kf_len, kf_red):
         """local_mapper.py:253-315 on the counts the device produced: list length and the listed ids whose first map point with
         that id has >= 3 observations in other keyframes"""
