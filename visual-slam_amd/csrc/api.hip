@@ -61,8 +61,8 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
     c->flags_cur = host_call ? mo_host_flags(c) : c->d_flags;
     if (host_call == 1) HIPCHK(c, hipMemsetAsync(mo_host_flags(c), 0, 4 * sizeof(int), c->stream));  // (2: the upload kernel cleared them)
     if (c->poison >= 0) {  // mo_dbg_set_poison (tests): whatever the margins skip must never reach a result
-        HIPCHK(c, hipMemsetAsync(c->d_pyr, c->poison, (size_t)c->batch_alloc * c->plan.pyr_stride, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_blur, c->poison, (size_t)c->batch_alloc * c->plan.blur_stride, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->pb.d_pyr, c->poison, (size_t)c->pb.batch_alloc * c->plan.pyr_stride, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->pb.d_blur, c->poison, (size_t)c->pb.batch_alloc * c->plan.blur_stride, c->stream));
     }
     if (host_call) mo_stage_mark(c, "h2d");  // (the host call opened its event set before the upload)
     else mo_stage_begin(c);
@@ -70,7 +70,7 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
     const int blur_margin = mo_blur_margin(c->plan.edge_threshold), pyr_margin = mo_pyr_margin(c->plan.edge_threshold);
     // (one frame of a host call: the finest level's FAST + selection on a second stream beside the pyramid and the other levels was
     //  measured in round 4 - no gain, level 1's chain is as long as level 0's: profiles/r04_ab_single_split.txt)
-    if (batch <= MO_FS_MAX_BATCH && c->fs_ok) {
+    if (batch <= MO_FS_MAX_BATCH && c->pb.fs_ok) {
         // one or two frames: pyramid and blur in ONE launch whose workgroups chain the levels of their own tile through LDS
         // (front_single.hip; the seven dependent resize launches + the blur were 62 of 202 us of a one-frame call)
         if ((rc = orb_launch_front_single(c, d_gray, batch, d_desc != nullptr))) return rc;
@@ -115,7 +115,7 @@ static int run_grid_extract(mo_ctx* c, const mo_orb_params* p, const mo_batch_io
     Layout L;
     const size_t o_eig = L.take(B * w * h * sizeof(float)), o_xy = L.take(B * slots * 2 * sizeof(float)), o_n = L.take(B * 66 * sizeof(int)),
                  o_kb = L.take(B * 65 * sizeof(int32_t));
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    if ((rc = c->d_tmp.reserve_exact(c, L.total))) return rc;
     float* d_eig = L.at<float>(c->d_tmp, o_eig);
     float* d_xy = io->d_grid_xy ? io->d_grid_xy : L.at<float>(c->d_tmp, o_xy);
     int* d_n = io->d_grid_n ? io->d_grid_n : L.at<int>(c->d_tmp, o_n);
@@ -143,11 +143,11 @@ static int stage_images(mo_ctx* c, const uint8_t* img, int w, int h, int stride,
     if (ch != 1 && ch != 3) return mo_fail(c, MO_ERR_ARG, "ch must be 1 (gray) or 3 (BGR)");
     if (stride < w * ch) return mo_fail(c, MO_ERR_ARG, "stride smaller than a row");
     size_t row = (size_t)w * ch, frame = row * h;
-    int rc = mo_reserve(c, c->d_in, c->d_in_bytes, frame * batch);
+    int rc = c->d_in.reserve_exact(c, frame * batch);
     if (rc) return rc;
     HIPCHK(c, hipMemcpy2DAsync(c->d_in, row, img, (size_t)stride, row, (size_t)h * batch, hipMemcpyHostToDevice, c->stream));
     if (ch == 3) {
-        rc = mo_reserve(c, c->d_gray, c->d_gray_bytes, (size_t)w * h * batch);
+        rc = c->d_gray.reserve_exact(c, (size_t)w * h * batch);
         if (rc) return rc;
         if ((rc = orb_launch_gray(c, c->d_in, w, h, batch, c->d_gray))) return rc;
         *d_gray = c->d_gray;
@@ -160,21 +160,16 @@ static int stage_images(mo_ctx* c, const uint8_t* img, int w, int h, int stride,
 // output staging of a batched host call (rows f * cap + i: a byte bound per array is enough)
 static int reserve_out(mo_ctx* c, int batch, int cap) {
     const size_t n = (size_t)batch * cap;
-    int rc = mo_reserve(c, c->d_kps, c->kps_bytes, n * sizeof(mo_keypoint));
-    if (!rc) rc = mo_reserve(c, c->d_desc, c->desc_bytes, n * 32);
-    if (!rc) rc = mo_reserve(c, c->d_counts, c->counts_bytes, (size_t)batch * sizeof(int));
+    int rc = c->d_kps.reserve_exact(c, n);
+    if (!rc) rc = c->d_desc.reserve_exact(c, n * 32);
+    if (!rc) rc = c->d_counts.reserve_exact(c, (size_t)batch);
     return rc;
 }
 
 // pinned host staging owned by the context (small host-API transfers: one copy each way and one synchronisation instead of a blocking
 // round trip per pageable array).  Mapped + coherent: k_ingest / k_pack_out read and write it from the device.
 int mo_host_stage(mo_ctx* c, size_t bytes) {
-    if (c->h_stage_bytes >= bytes) return MO_OK;
-    if (c->h_stage) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_bytes = 0; }
-    bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    HIPCHK(c, hipHostMalloc((void**)&c->h_stage, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    c->h_stage_bytes = bytes;
-    return MO_OK;
+    return c->h_stage.reserve(c, mo_align(bytes, (size_t)1 << 20), hipHostMallocMapped | hipHostMallocCoherent);
 }
 
 // true when an overflowed level's final-keypoint slot can still grow (then the plan is invalidated so that the next call rebuilds it).
@@ -306,7 +301,7 @@ extern "C" int mo_orb_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* 
     const size_t kb = (size_t)n * sizeof(mo_keypoint);
     Layout L;
     const size_t o_k = L.take(kb), o_d = L.take((size_t)n * 32);
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    if ((rc = c->d_tmp.reserve_exact(c, L.total))) return rc;
     mo_keypoint* d_k = L.at<mo_keypoint>(c->d_tmp, o_k);
     uint8_t* d_d = L.at<uint8_t>(c->d_tmp, o_d);
     HIPCHK(c, hipMemcpyAsync(d_k, kk.data(), kb, hipMemcpyHostToDevice, c->stream));
@@ -340,7 +335,7 @@ extern "C" int mo_undistort(mo_ctx* c, const uint8_t* img, int w, int h, int str
     const size_t row = (size_t)w * ch, frame = row * h;
     Layout L;
     const size_t o_src = L.take(frame), o_dst = L.take(frame);
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
     if (rc) return rc;
     uint8_t* d_src = L.at<uint8_t>(c->d_tmp, o_src);
     uint8_t* d_dst = L.at<uint8_t>(c->d_tmp, o_dst);
@@ -364,7 +359,7 @@ static int gftt_run(mo_ctx* c, const uint8_t* img, int w, int h, int stride, int
     const size_t eig_b = (size_t)w * h * sizeof(float), xy_b = (size_t)64 * per_cell * 2 * sizeof(float);
     Layout L;
     const size_t o_eig = L.take(eig_b), o_xy = L.take(xy_b), o_n = L.take(64 * sizeof(int));
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total))) return rc;
+    if ((rc = c->d_tmp.reserve_exact(c, L.total))) return rc;
     float* d_eig = L.at<float>(c->d_tmp, o_eig);
     float* d_xy = L.at<float>(c->d_tmp, o_xy);
     int* d_n = L.at<int>(c->d_tmp, o_n);
@@ -430,15 +425,15 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
     Layout L;
     const size_t o_eig = L.take(eig_b), o_out = L.total, o_fl = L.take(16), o_xy = L.take(xy_b), o_n = L.take(66 * sizeof(int)),
                  o_kept = L.take((size_t)slots * sizeof(int32_t)), o_desc = L.take((size_t)slots * 32), out_end = L.total;
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, out_end))) return rc;
-    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, mo_align((size_t)w * h, 256)))) return rc;
+    if ((rc = c->d_tmp.reserve_exact(c, out_end))) return rc;
+    if ((rc = c->d_in.reserve_exact(c, mo_align((size_t)w * h, 256)))) return rc;
     const size_t h_out = mo_align(in_bytes, 256);
     if ((rc = mo_host_stage(c, h_out + (out_end - o_out)))) return rc;
     uint8_t* hs = c->h_stage;
     uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
     mo_copy_rows(hs, img, rowb, h, (size_t)stride);
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     float* d_eig = L.at<float>(b, o_eig); float* d_xy = L.at<float>(b, o_xy); int* d_n = L.at<int>(b, o_n);
     int32_t* d_kept = L.at<int32_t>(b, o_kept);
     c->flags_cur = mo_host_flags(c);
@@ -503,11 +498,11 @@ extern "C" int mo_match_knn2_ratio(mo_ctx* c, const uint8_t* q, int nq, const ui
     HostClock clk(c);
     size_t qb = (size_t)batch * nq * 32, tb = (size_t)batch * std::max(nt, 1) * 32, n = (size_t)batch * nq;
     int rc;
-    if ((rc = mo_reserve(c, c->d_mq, c->m_q_bytes, qb))) return rc;
-    if ((rc = mo_reserve(c, c->d_mt, c->m_t_bytes, tb))) return rc;
-    if ((rc = mo_reserve(c, c->d_midx, c->m_idx_bytes, n * 2 * sizeof(int32_t)))) return rc;
-    if ((rc = mo_reserve(c, c->d_mdist, c->m_dist_bytes, n * 2 * sizeof(int32_t)))) return rc;
-    if ((rc = mo_reserve(c, c->d_mpass, c->m_pass_bytes, n))) return rc;
+    if ((rc = c->d_mq.reserve_exact(c, qb))) return rc;
+    if ((rc = c->d_mt.reserve_exact(c, tb))) return rc;
+    if ((rc = c->d_midx.reserve_exact(c, n * 2))) return rc;
+    if ((rc = c->d_mdist.reserve_exact(c, n * 2))) return rc;
+    if ((rc = c->d_mpass.reserve_exact(c, n))) return rc;
     const size_t tbytes = (size_t)batch * nt * 32, o_t = (qb + 15) & ~(size_t)15, o_idx = (o_t + tbytes + 15) & ~(size_t)15;
     const size_t o_dist = o_idx + n * 2 * sizeof(int32_t), o_pass = o_dist + n * 2 * sizeof(int32_t), total = o_pass + n;
     const bool staged = total <= (size_t)2 << 20;  // the single-pair calls of the drop-in classes
@@ -571,9 +566,9 @@ extern "C" int mo_init_two_view(mo_ctx* c, const float* p1, const float* p2, int
     Layout L;
     const size_t o_pose = L.take(12 * sizeof(double)), o_E = L.take(9 * sizeof(double)), o_n = L.take(sizeof(int32_t)), o_p1 = L.take(pb),
                  o_p2 = L.take(pb), o_X = L.take((size_t)m * 3 * sizeof(float)), o_inl = L.take(m), o_ran = L.take(m);
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     double* d_pose = L.at<double>(b, o_pose);
     double* d_E = L.at<double>(b, o_E);
     int32_t* d_n = L.at<int32_t>(b, o_n);
@@ -621,9 +616,9 @@ extern "C" int mo_recover_pose(mo_ctx* c, const double E[9], const float* p1, co
     Layout L;
     const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_E = L.take(9 * sizeof(double)), o_min = L.take(m), o_pose = L.take(12 * sizeof(double)),
                  o_X = L.take((size_t)m * 3 * sizeof(float)), o_inl = L.take(m), o_n = L.take(sizeof(int32_t));
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     HIPCHK(c, hipMemcpyAsync(b + o_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_E, E, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -664,9 +659,9 @@ extern "C" int mo_find_fundamental(mo_ctx* c, const float* p1, const float* p2, 
     Layout L;
     const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_F = L.take(9 * sizeof(double)), o_X = L.take((size_t)m * 3 * sizeof(float)),
                  o_ran = L.take(m), o_n = L.take(sizeof(int32_t));
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     HIPCHK(c, hipMemcpyAsync(b + o_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
     TwoViewArgs a = tv_fundamental(1, m, n_hyp, thr_px, seed, 0);
@@ -721,7 +716,7 @@ extern "C" int mo_triangulate_points(mo_ctx* c, const double P1[12], const doubl
     const size_t pb = (size_t)n * 2 * sizeof(float);
     Layout L;
     const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_X = L.take((size_t)n * 4 * sizeof(float));
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, L.total);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
     if (rc) return rc;
     float* d_p1 = L.at<float>(c->d_tmp, o_p1);
     float* d_p2 = L.at<float>(c->d_tmp, o_p2);
@@ -794,17 +789,16 @@ extern "C" int mo_dev_frontend_batch(mo_ctx* c, const mo_orb_params* p, const mo
     if (!io->d_match_dist || !io->d_match_pass) return mo_fail(c, MO_ERR_ARG, "match outputs missing");
     // (query, train) frame of every pair: written once per batch size into a buffer of its own (it was a 5 us launch per call)
     if (c->pair_frames_n < n_pairs) {
-        if (c->d_pair_frames) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->d_pair_frames)); c->d_pair_frames = nullptr; }
         c->pair_frames_n = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_pair_frames, (size_t)n_pairs * 2 * sizeof(int32_t)));
+        if (c->d_pair_frames) HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((rc = c->d_pair_frames.reserve_exact(c, (size_t)n_pairs * 2))) return rc;
         hipLaunchKernelGGL(k_pair_frames, dim3((n_pairs + 255) / 256), dim3(256), 0, c->stream, c->d_pair_frames, c->d_pair_frames + n_pairs,
                            n_pairs);
         HIPCHK(c, hipGetLastError());
         c->pair_frames_n = n_pairs;
-        c->pair_frames_split = n_pairs;
     }
     int32_t* qf = c->d_pair_frames;
-    int32_t* tf = qf + c->pair_frames_split;
+    int32_t* tf = qf + c->pair_frames_n;
     rc = match_launch_pairs(c, io->d_desc, io->d_desc, (size_t)io->cap * 32, (size_t)io->cap * 32, io->d_counts, qf, tf, 0, 0,
                             n_pairs, io->cap, io->ratio, io->d_match_idx, io->d_match_dist, io->d_match_pass);
     if (rc) return rc;
@@ -844,18 +838,18 @@ extern "C" int mo_dbg_pyramid_level(mo_ctx* c, const mo_orb_params* p, const uin
     const bool fused = (blurred & 2) != 0;  // bit 1: through the single-frame kernel (front_single.hip) instead of k_resize2 / k_blur
     blurred &= 1;
     if (fused) {
-        if (!c->fs_ok) return mo_fail(c, MO_ERR_UNSUPPORTED, std::string("the single-frame pyramid kernel does not cover this geometry: ") + c->fs_why);
-        HIPCHK(c, hipMemsetAsync(c->d_pyr, 0xA5, (size_t)c->plan.pyr_stride, c->stream));   // whatever it does not write shows
-        HIPCHK(c, hipMemsetAsync(c->d_blur, 0xA5, (size_t)c->plan.blur_stride, c->stream));
+        if (!c->pb.fs_ok) return mo_fail(c, MO_ERR_UNSUPPORTED, std::string("the single-frame pyramid kernel does not cover this geometry: ") + c->pb.fs_why);
+        HIPCHK(c, hipMemsetAsync(c->pb.d_pyr, 0xA5, (size_t)c->plan.pyr_stride, c->stream));   // whatever it does not write shows
+        HIPCHK(c, hipMemsetAsync(c->pb.d_blur, 0xA5, (size_t)c->plan.blur_stride, c->stream));
         if ((rc = orb_launch_front_single(c, d_gray, 1, 1))) return rc;
     } else if ((rc = orb_launch_pyramid(c, d_gray, 1, c->plan.nlevels, 0))) return rc;
     const LevelInfo& v = c->plan.lv[level];
     *lw = v.w; *lh = v.h;
     if (blurred) {
         if (!fused && (rc = orb_launch_blur(c, d_gray, 1, c->plan.nlevels, 0))) return rc;
-        HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->d_blur + v.boff, v.bpitch, v.w, v.h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->pb.d_blur + v.boff, v.bpitch, v.w, v.h, hipMemcpyDeviceToHost, c->stream));
     } else {
-        const uint8_t* src = level == 0 ? d_gray : c->d_pyr + v.off;
+        const uint8_t* src = level == 0 ? d_gray : c->pb.d_pyr + v.off;
         HIPCHK(c, hipMemcpy2DAsync(out, v.w, src, v.pitch, v.w, v.h, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -867,11 +861,11 @@ extern "C" int mo_dbg_blur_level(mo_ctx* c, int frame, int level, uint8_t* out, 
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->plan_valid) return mo_fail(c, MO_ERR_ARG, "no extraction has run on this context");
     if (level < 0 || level >= c->plan.nlevels) return mo_fail(c, MO_ERR_ARG, "level out of range");
-    if (frame < 0 || frame >= c->batch_alloc) return mo_fail(c, MO_ERR_ARG, "frame out of range");
+    if (frame < 0 || frame >= c->pb.batch_alloc) return mo_fail(c, MO_ERR_ARG, "frame out of range");
     const LevelInfo& v = c->plan.lv[level];
     *lw = v.w; *lh = v.h;
     if (resize_blur) *resize_blur = c->rb_ok ? 1 : 0;
-    HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->d_blur + (size_t)frame * c->plan.blur_stride + v.boff, v.bpitch, v.w, v.h,
+    HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->pb.d_blur + (size_t)frame * c->plan.blur_stride + v.boff, v.bpitch, v.w, v.h,
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MO_OK;
@@ -892,8 +886,8 @@ extern "C" int mo_dbg_fast_level(mo_ctx* c, const mo_orb_params* p, const uint8_
     std::vector<int> cnt(std::max(v.nstrips, 1));
     std::vector<uint32_t> ent((size_t)std::max(v.cand_cap, 1));
     if (v.nstrips > 0) {
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_strip_cnt + v.strip_base, v.nstrips * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(ent.data(), c->d_cand + v.cand_off, (size_t)v.cand_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->pb.d_strip_cnt + v.strip_base, v.nstrips * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ent.data(), c->pb.d_cand + v.cand_off, (size_t)v.cand_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int k = 0;
@@ -912,17 +906,13 @@ extern "C" int mo_dbg_retain_best(mo_ctx* c, const float* resp, int n, int n_poi
     if (!c) return MO_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (n <= 0) { *n_out = 0; return MO_OK; }
-    float* d_r = nullptr; int32_t* d_o = nullptr; int* d_n = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_r, (size_t)n * sizeof(float)));
-    HIPCHK(c, hipMalloc((void**)&d_o, (size_t)n * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc((void**)&d_n, sizeof(int)));
+    DevBuf<float> d_r; DevBuf<int32_t> d_o; DevBuf<int> d_n;  // (freed on every return)
+    int rc;
+    if ((rc = d_r.reserve_exact(c, (size_t)n)) || (rc = d_o.reserve_exact(c, (size_t)n)) || (rc = d_n.reserve_exact(c, 1))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_r, resp, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc = orb_launch_retain_probe(c, d_r, n, n_points, select_order, d_o, d_n);
-    if (!rc) {
-        HIPCHK(c, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(order, d_o, (size_t)(*n_out) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    hipFree(d_r); hipFree(d_o); hipFree(d_n);
-    return rc;
+    if ((rc = orb_launch_retain_probe(c, d_r, n, n_points, select_order, d_o, d_n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(order, d_o, (size_t)(*n_out) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MO_OK;
 }

@@ -112,7 +112,7 @@ extern "C" int mo_gather_map_points(mo_ctx* c, const float* d_local, int rows_lo
     // (a word of its own: the gather may run on a side stream beside the next call's kernels, which use the context's other buffers;
     //  the count travels as a kernel argument: an async copy from this function's stack would outlive the variable)
     int rc;
-    if (!c->d_comm_cnt) HIPCHK(c, hipMalloc((void**)&c->d_comm_cnt, 256));
+    if ((rc = c->d_comm_cnt.reserve_exact(c, 64))) return rc;
     hipLaunchKernelGGL(k_store_i32, dim3(1), dim3(1), 0, c->stream, c->d_comm_cnt, (int32_t)rows_local);
     HIPCHK(c, hipGetLastError());
     if ((rc = r.AllGather(c->d_comm_cnt, d_rows_all, 1, NCCL_INT32, comm, c->stream)) != 0) return nccl_fail(c, "ncclAllGather", rc);

@@ -1,11 +1,13 @@
 // common.h -- context, plan and helpers shared by the HIP translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <stdint.h>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/vslam_amd.h"
@@ -58,12 +60,99 @@ struct FinalKp {  // 8 bytes: survivor of both retainBest passes, level coordina
     float response;
 };
 
-struct ResizeTab {  // device arrays of one level's INTER_LINEAR_EXACT coefficients (one allocation, base = xpk)
+struct mo_ctx;
+int mo_fail(mo_ctx* c, int code, const std::string& msg);
+
+#define HIPCHK(c, expr)                                                                              \
+    do {                                                                                             \
+        hipError_t e__ = (expr);                                                                     \
+        if (e__ != hipSuccess)                                                                       \
+            return mo_fail((c), MO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
+    } while (0)
+
+// A device buffer that owns its memory: freed by its destructor, moved but never copied.  Kernels and copies receive the raw pointer
+// (the conversion).  Sizes are element counts.  Every hipMalloc / hipFree of the library is in here.
+template <class T> struct DevBuf {
+    T* p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { DevBuf t(std::move(o)); swap(t); return *this; }
+    ~DevBuf() { if (p) hipFree(p); }
+    operator T*() const { return p; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    void reset() { DevBuf().swap(*this); }
+    // room for n elements, the contents dropped.  reserve_exact allocates what is asked for (the context's buffers: some are sized
+    // for whole 4095 x 4095 frames); reserve grows by half at least (the map's stores, which grow a little with every keyframe).
+    int reserve_exact(mo_ctx* c, size_t n) { return n * sizeof(T) <= bytes && p ? MO_OK : realloc_bytes(c, n * sizeof(T)); }
+    int reserve(mo_ctx* c, size_t n) { return n * sizeof(T) <= bytes && p ? MO_OK : realloc_bytes(c, std::max(n * sizeof(T), bytes + bytes / 2)); }
+    // a new block of n elements that keeps the first `keep`: allocated, copied on the context stream, synchronised, the old one freed
+    int regrow(mo_ctx* c, size_t n, size_t keep);
+    // a table built on the host: a new block of exactly v.size() elements with the vector copied into it (a failure leaves the old block)
+    int upload(mo_ctx* c, const std::vector<T>& v) {
+        DevBuf q;
+        if (int rc = q.realloc_bytes(c, v.size() * sizeof(T))) return rc;
+        HIPCHK(c, hipMemcpy(q.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        swap(q);
+        return MO_OK;
+    }
+private:
+    // (the pointer and its size are dropped before the free: a failure leaves nothing that passes the size check)
+    int realloc_bytes(mo_ctx* c, size_t need) {
+        T* old = p;
+        p = nullptr; bytes = 0;
+        if (old) HIPCHK(c, hipFree(old));
+        need = std::max(need, (size_t)16);
+        HIPCHK(c, hipMalloc((void**)&p, need));
+        bytes = need;
+        return MO_OK;
+    }
+};
+
+// a pinned host block; a larger one replaces it once the context stream has drained (the device may still be reading the old one)
+template <class T> struct PinnedBuf {
+    T* p = nullptr; size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept { swap(o); }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { PinnedBuf t(std::move(o)); swap(t); return *this; }
+    ~PinnedBuf() { if (p) hipHostFree(p); }
+    operator T*() const { return p; }
+    void swap(PinnedBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    void reset() { PinnedBuf().swap(*this); }
+    int reserve(mo_ctx* c, size_t n, unsigned flags = hipHostMallocDefault);
+};
+
+struct ResizeTab {  // views into one level's INTER_LINEAR_EXACT coefficients (one block, PlanBufs::rblock; base = xpk)
     // packed per output column / row, padded to a multiple of 64 entries with the last one: source offset (15 bits) |
     // (right / lower neighbour offset - offset) << 15 | weight of that neighbour in 1/256 units << 16 (k_resize2)
     uint32_t* xpk = nullptr; uint32_t* ypk = nullptr;
     int* xofs = nullptr; int* xc1 = nullptr; int* yofs = nullptr; int* yc1 = nullptr;  // the same, unpacked (k_resize)
     bool two_pass_ok = true;  // k_resize2's 8-byte source window holds every group of 4 output columns
+};
+
+// Everything a plan allocates, with the counts that describe its tables.  A rebuild drops it whole (c->pb = PlanBufs()): a buffer
+// added here needs no line anywhere else to be freed.  The tables are uploaded on their first use under the plan.
+struct PlanBufs {
+    int batch_alloc = 0;           // frames the work buffers below are sized for
+    DevBuf<uint8_t> d_pyr;         // [batch][pyr_stride]
+    DevBuf<uint8_t> d_blur;        // [batch][blur_stride]
+    DevBuf<uint32_t> d_cand;       // [batch][cand_stride]
+    DevBuf<int> d_strip_cnt;       // [batch][strips_per_frame]
+    DevBuf<uint64_t> d_scratch;    // [batch][nlevels] overflow scratch for the selection replay
+    DevBuf<FinalKp> d_fin;         // [batch][fin_stride]
+    DevBuf<int> d_fin_cnt;         // [batch][MO_MAX_LEVELS]
+    DevBuf<uint32_t> rblock[MO_MAX_LEVELS];                // resize coefficients of level L: the block the views of rtab[L] point into
+    ResizeTab rtab[MO_MAX_LEVELS];
+    DevBuf<uint32_t> d_tile_tab[2];                        // blur: tile -> level | tile column << 8 | tile row << 20; [0]: whole levels, [1]: without the margin tile_margin
+    int tile_cum[2][MO_MAX_LEVELS + 1] = {};               // tiles of levels < L (the tables are level-major: a prefix blurs the first levels)
+    int tile_margin = 0;
+    DevBuf<uint32_t> d_fs_tab; int fs_tiles = 0, fs_stride = 0, fs_lds = 0; bool fs_ok = false; int fs_geom[10] = {}; const char* fs_why = "";  // k_front_single: per-tile headers + coefficient slices (fs_build)
+    DevBuf<uint32_t> d_strip_tab;                          // FAST: strip of a frame -> level | strip of the level << 8
+    DevBuf<uint32_t> d_dtile_tab; int n_dtiles = 0, dtile_icw_off = 0;  // k_describe_tiles: tile -> level | column << 8 | row << 20, then the centroid weights
+    DevBuf<int> d_dtodo;           // k_describe_tiles -> k_describe_tiles_rare: [0] count, then frame * tiles + tile
 };
 
 #define MO_RESULT_SLOTS 4
@@ -95,63 +184,45 @@ struct mo_ctx {
     int tie_levels = 0;                     // ... on these levels (bit L)
     mo_orb_params plan_params{};
     Plan plan{};
-    ResizeTab rtab[MO_MAX_LEVELS];
     // the batched extraction's resize launches can write the blurred levels too (orb_plan_resize_blur held for every level at
     // the pipeline's margins rb_pyr_margin / rb_margin)
     bool rb_ok = false;
     int rb_margin = -1, rb_pyr_margin = -1;
-    int batch_alloc = 0;  // frames the work buffers below are sized for
+    size_t scratch_stride = 0;     // u64 entries per frame of overflow scratch
+    PlanBufs pb;                   // what the plan allocated
 
     // work buffers (device)
-    uint8_t* d_in = nullptr;       size_t d_in_bytes = 0;      // staged host images (any ch)
-    uint8_t* d_gray = nullptr;     size_t d_gray_bytes = 0;    // gray level 0 when converted / staged
-    uint8_t* d_pyr = nullptr;      // [batch][pyr_stride]
-    uint8_t* d_blur = nullptr;     // [batch][blur_stride]
-    uint32_t* d_cand = nullptr;    // [batch][cand_stride]
-    int* d_strip_cnt = nullptr;    // [batch][strips_per_frame]
-    uint64_t* d_scratch = nullptr; // [batch][nlevels] overflow scratch for the selection replay
-    size_t scratch_stride = 0;     // u64 entries per frame of overflow scratch
-    FinalKp* d_fin = nullptr;      // [batch][fin_stride]
-    int* d_fin_cnt = nullptr;      // [batch][MO_MAX_LEVELS]
-    uint32_t* d_tile_tab[2] = {nullptr, nullptr};          // blur: tile -> level | tile column << 8 | tile row << 20 (built with the plan); [0]: whole levels, [1]: without the margin tile_margin
-    int tile_cum[2][MO_MAX_LEVELS + 1] = {};               // tiles of levels < L (the tables are level-major: a prefix blurs the first levels)
-    int tile_margin = 0;
-    uint32_t* d_fs_tab = nullptr; int fs_tiles = 0, fs_stride = 0, fs_lds = 0; bool fs_ok = false; int fs_geom[10] = {}; const char* fs_why = "";  // k_front_single: per-tile headers + coefficient slices (built with the plan)
-    uint32_t* d_strip_tab = nullptr; int n_strip_tab = 0;  // FAST: strip of a frame -> level | strip of the level << 8
-    uint32_t* d_dtile_tab = nullptr; int n_dtiles = 0, dtile_icw_off = 0;  // k_describe_tiles: tile -> level | column << 8 | row << 20, then the centroid weights
-    int* d_dtodo = nullptr; size_t dtodo_bytes = 0;  // k_describe_tiles -> k_describe_tiles_rare: [0] count, then frame * tiles + tile
-    int* d_flags = nullptr;        // [8] error flags raised by kernels: words 0..3 belong to the mo_dev_* calls (they accumulate until
+    DevBuf<uint8_t> d_in;          // staged host images (any ch)
+    DevBuf<uint8_t> d_gray;        // gray level 0 when converted / staged
+    DevBuf<int> d_flags;           // [8] error flags raised by kernels: words 0..3 belong to the mo_dev_* calls (they accumulate until
                                    // mo_dev_status), words 4..7 to the host entry points (cleared and checked inside each call)
     int* flags_cur = nullptr;      // the word block the kernels of the current call raise their bits in
-    unsigned lds_attr_done = 0;    // bit per kernel whose max-dynamic-LDS attribute has been raised on this device
+    std::vector<const void*> dyn_lds_raised;  // kernels whose max-dynamic-LDS attribute has been raised on this device (mo_raise_dyn_lds)
     // output staging for the host API (batches of frames)
-    mo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int* d_counts = nullptr; size_t kps_bytes = 0, desc_bytes = 0, counts_bytes = 0;
+    DevBuf<mo_keypoint> d_kps; DevBuf<uint8_t> d_desc; DevBuf<int> d_counts;
     // Resident results of the last MO_RESULT_SLOTS single-frame extractions of the host API: slot s is "frame s" of these arrays, so the
     // pair stages (matcher, tracking filters, two-view) run on two slots exactly as they run on two frames of a batch, and a Tracker-style
     // caller that hands a frame's token back (mo_pair_frontend) uploads nothing.
-    mo_keypoint* d_slot_kps = nullptr; uint8_t* d_slot_desc = nullptr; int32_t* d_slot_cnt = nullptr; int32_t* d_slot_ids = nullptr;
+    DevBuf<mo_keypoint> d_slot_kps; DevBuf<uint8_t> d_slot_desc; DevBuf<int32_t> d_slot_cnt, d_slot_ids;
     int slot_cap = 0, slot_cur = -1;
     uint64_t slot_token[MO_RESULT_SLOTS] = {}; int slot_n[MO_RESULT_SLOTS] = {}; uint64_t token_next = 1, last_token = 0;
     bool host_timing = false;      // stage events inside the single-call host entry points (mo_set_host_timing; an event between two
                                    // kernels idles the GPU for ~ 4.5 us, five of them were 9 % of a single-frame extraction)
     // matcher staging
-    uint8_t* d_mq = nullptr; uint8_t* d_mt = nullptr; int32_t* d_midx = nullptr; int32_t* d_mdist = nullptr;
-    uint8_t* d_mpass = nullptr; size_t m_q_bytes = 0, m_t_bytes = 0, m_idx_bytes = 0, m_dist_bytes = 0, m_pass_bytes = 0;
-    uint2* d_match_part = nullptr; size_t match_part_bytes = 0;  // per-slice keys of a split k_match_lds launch
-    // two-view work buffers
-    void* d_tv = nullptr; size_t tv_bytes = 0;
-    float* d_stream_pts = nullptr; size_t stream_pts_bytes = 0;  // mo_stream: map-point scratch of chunks whose caller does not want them
-    uint32_t* d_track_keys = nullptr; size_t track_keys_bytes = 0;  // k_track_select: key arrays of frames too large for LDS
-    // generic temp
-    void* d_tmp = nullptr; size_t tmp_bytes = 0;
+    DevBuf<uint8_t> d_mq, d_mt, d_mpass; DevBuf<int32_t> d_midx, d_mdist;
+    DevBuf<uint2> d_match_part;     // per-slice keys of a split k_match_lds launch
+    DevBuf<uint8_t> d_tv;           // two-view work buffers (carved by twoview_launch)
+    DevBuf<float> d_stream_pts;     // mo_stream: map-point scratch of chunks whose caller does not want them
+    DevBuf<uint32_t> d_track_keys;  // k_track_select: key arrays of frames too large for LDS
+    DevBuf<uint8_t> d_tmp;          // generic temp (carved with Layout)
 
     // RCCL communicator of the sharded batched mode (comm.hip); null until mo_comm_init
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
-    int32_t* d_comm_cnt = nullptr;  // this rank's row count for mo_gather_map_points' all-gather
+    DevBuf<int32_t> d_comm_cnt;     // this rank's row count for mo_gather_map_points' all-gather
 
     double host_us[4] = {0, 0, 0, 0};  // mo_host_times: enqueue / wait / unpack / total of the last single-call host entry point
-    uint8_t* h_stage = nullptr; size_t h_stage_bytes = 0;   // pinned host staging of small host-API results
-    int32_t* d_pair_frames = nullptr; int pair_frames_n = 0, pair_frames_split = 0;  // mo_dev_frontend_batch: qf[i] = i, tf[i] = i + 1
+    PinnedBuf<uint8_t> h_stage;        // pinned (mapped, coherent) host staging of small host-API results
+    DevBuf<int32_t> d_pair_frames; int pair_frames_n = 0;  // mo_dev_frontend_batch: qf[i] = i, tf[i] = i + 1 ([2][pair_frames_n])
     // stage timing: a ring of event sets, one per mo_* call (mo_stage_begin advances it), so that a caller can enqueue many calls
     // back to back and read the per-stage times of the last MO_TIMING_SLOTS of them after ONE synchronisation (mo_stage_times_back)
     TimingSet tsets[MO_TIMING_SLOTS];
@@ -159,25 +230,25 @@ struct mo_ctx {
     bool timing = true;
 };
 
-int mo_fail(mo_ctx* c, int code, const std::string& msg);
-
-#define HIPCHK(c, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess)                                                                       \
-            return mo_fail((c), MO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
-    } while (0)
-
-// grow-only device buffer helper (the pointer and its size are dropped before the free: a failure leaves nothing that passes the check)
-template <class T> int mo_reserve(mo_ctx* c, T*& p, size_t& have_bytes, size_t need_bytes) {
-    if (need_bytes <= have_bytes && p) return MO_OK;
-    T* old = p;
-    p = nullptr; have_bytes = 0;
-    if (old) HIPCHK(c, hipFree(old));
-    HIPCHK(c, hipMalloc((void**)&p, need_bytes ? need_bytes : 16));
-    have_bytes = need_bytes;
+template <class T> int DevBuf<T>::regrow(mo_ctx* c, size_t n, size_t keep) {
+    DevBuf q;
+    if (int rc = q.realloc_bytes(c, n * sizeof(T))) return rc;
+    if (p && keep) HIPCHK(c, hipMemcpyAsync(q.p, p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
+    swap(q);
     return MO_OK;
 }
+
+template <class T> int PinnedBuf<T>::reserve(mo_ctx* c, size_t n, unsigned flags) {
+    if (p && n * sizeof(T) <= bytes) return MO_OK;
+    if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); reset(); }
+    HIPCHK(c, hipHostMalloc((void**)&p, n * sizeof(T), flags));
+    bytes = n * sizeof(T);
+    return MO_OK;
+}
+
+// the kernel's max-dynamic-LDS attribute raised to `bytes`, once per kernel function and context (ctx.hip)
+int mo_raise_dyn_lds(mo_ctx* c, const void* kernel, int bytes);
 
 static inline size_t mo_align(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 

@@ -66,7 +66,7 @@ extern "C" mo_ctx* mo_create(int device, int max_w, int max_h, int max_batch) {
     const unsigned evf = (unsigned)hipEventDisableSystemFence;
     for (TimingSet& t : c->tsets)
         for (int i = 0; i <= MO_NSTAGES; i++) hipEventCreateWithFlags(&t.ev[i], evf);
-    if (hipMalloc((void**)&c->d_flags, 8 * sizeof(int)) != hipSuccess) {
+    if (c->d_flags.reserve_exact(c, 8) != MO_OK) {
         g_create_err = "mo_create: hipMalloc failed";
         delete c;
         return nullptr;
@@ -76,21 +76,16 @@ extern "C" mo_ctx* mo_create(int device, int max_w, int max_h, int max_batch) {
     return c;
 }
 
+// raises a kernel's limit of dynamic LDS once per kernel function: the launchers call this on every launch
+int mo_raise_dyn_lds(mo_ctx* c, const void* kernel, int bytes) {
+    if (std::find(c->dyn_lds_raised.begin(), c->dyn_lds_raised.end(), kernel) != c->dyn_lds_raised.end()) return MO_OK;
+    HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    c->dyn_lds_raised.push_back(kernel);
+    return MO_OK;
+}
+
 static void free_plan_buffers(mo_ctx* c) {
-    for (int L = 0; L < MO_MAX_LEVELS; L++) {
-        ResizeTab& t = c->rtab[L];
-        if (t.xpk) hipFree(t.xpk);
-        t = ResizeTab();
-    }
-    void* bufs[] = {c->d_pyr, c->d_blur, c->d_cand, c->d_strip_cnt, c->d_scratch, c->d_fin, c->d_fin_cnt, c->d_tile_tab[0], c->d_tile_tab[1], c->d_strip_tab, c->d_dtile_tab};
-    c->d_dtile_tab = nullptr; c->n_dtiles = 0;
-    if (c->d_fs_tab) hipFree(c->d_fs_tab);
-    c->d_fs_tab = nullptr; c->fs_ok = false;
-    for (void* b : bufs) if (b) hipFree(b);
-    c->d_tile_tab[0] = c->d_tile_tab[1] = nullptr; c->d_strip_tab = nullptr; c->n_strip_tab = 0;
-    c->d_pyr = c->d_blur = nullptr; c->d_cand = nullptr; c->d_strip_cnt = nullptr; c->d_scratch = nullptr;
-    c->d_fin = nullptr; c->d_fin_cnt = nullptr;
-    c->batch_alloc = 0;
+    c->pb = PlanBufs();
     c->plan_valid = false;
 }
 
@@ -99,17 +94,11 @@ extern "C" void mo_destroy(mo_ctx* c) {
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     mo_comm_destroy(c);
-    free_plan_buffers(c);
-    void* bufs[] = {c->d_in, c->d_gray, c->d_flags, c->d_kps, c->d_desc, c->d_counts, c->d_mq, c->d_mt,
-                    c->d_midx, c->d_mdist, c->d_mpass, c->d_match_part, c->d_tv, c->d_tmp, c->d_pair_frames, c->d_dtodo, c->d_comm_cnt,
-                    c->d_slot_kps, c->d_slot_desc, c->d_slot_cnt, c->d_slot_ids, c->d_track_keys, c->d_stream_pts};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (c->h_stage) hipHostFree(c->h_stage);
     for (TimingSet& t : c->tsets) {
         for (int i = 0; i <= MO_NSTAGES; i++) if (t.ev[i]) hipEventDestroy(t.ev[i]);
     }
     if (c->own_stream) hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;  // every buffer frees itself (DevBuf, PinnedBuf)
 }
 
 extern "C" const char* mo_last_error(mo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -201,6 +190,8 @@ static bool params_equal(const mo_orb_params& a, const mo_orb_params& b) {
     return std::memcmp(&a, &b, sizeof(a)) == 0;
 }
 
+static int fill_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch);
+
 int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
     if (!p) return mo_fail(c, MO_ERR_ARG, "params is NULL");
     if (w < 64 || h < 64 || w > c->max_w || h > c->max_h)
@@ -221,10 +212,15 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
     const bool same = same_key && !c->fin_slack_dirty;
     if (!same_key)   // another image size / parameter set: the grown slots were that one's
         for (int L = 0; L < MO_MAX_LEVELS; L++) c->fin_slack[L] = 1;
-    if (same && batch <= c->batch_alloc) return MO_OK;
+    if (same && batch <= c->pb.batch_alloc) return MO_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_plan_buffers(c);
+    const int rc = fill_plan(c, p, w, h, batch);
+    if (rc) free_plan_buffers(c);  // no half plan stays behind
+    return rc;
+}
 
+static int fill_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
     Plan& P = c->plan;
     std::memset(&P, 0, sizeof(P));
     P.w = w; P.h = h; P.nlevels = p->nlevels;
@@ -347,38 +343,31 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
             const int xl = std::min(x + 3, dw - 1);
             window_ok = std::min(xo[xl] + 1, P.lv[L - 1].w - 1) - xo[x] <= 7;
         }
-        c->rtab[L].two_pass_ok = window_ok;
+        c->pb.rtab[L].two_pass_ok = window_ok;
         c->rb_ok = c->rb_ok && window_ok && orb_plan_resize_blur(P, L, xp, yp, c->rb_pyr_margin, c->rb_margin);
-        size_t n = (size_t)wp + hp + 2 * dw + 2 * dh;
-        int* d = nullptr;
-        HIPCHK(c, hipMalloc((void**)&d, n * sizeof(int)));
-        ResizeTab& t = c->rtab[L];
-        t.xpk = (uint32_t*)d; t.ypk = t.xpk + wp;
-        t.xofs = d + wp + hp; t.xc1 = t.xofs + dw; t.yofs = t.xc1 + dw; t.yc1 = t.yofs + dh;
-        HIPCHK(c, hipMemcpy(t.xpk, xp.data(), xp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.ypk, yp.data(), yp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.xofs, xo.data(), xo.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.xc1, xc.data(), xc.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.yofs, yo.data(), yo.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.yc1, yc.data(), yc.size() * sizeof(int), hipMemcpyHostToDevice));
+        // one block per level: xpk [wp] | ypk [hp] | xofs [dw] | xc1 [dw] | yofs [dh] | yc1 [dh]
+        std::vector<uint32_t> all(xp);
+        all.insert(all.end(), yp.begin(), yp.end());
+        for (const std::vector<int>* v : {&xo, &xc, &yo, &yc}) all.insert(all.end(), v->begin(), v->end());
+        if (int rc = c->pb.rblock[L].upload(c, all)) return rc;
+        ResizeTab& t = c->pb.rtab[L];
+        t.xpk = c->pb.rblock[L]; t.ypk = t.xpk + wp;
+        t.xofs = (int*)t.ypk + hp; t.xc1 = t.xofs + dw; t.yofs = t.xc1 + dw; t.yc1 = t.yofs + dh;
     }
 
     // work buffers for `batch` frames
     size_t B = (size_t)batch;
-    HIPCHK(c, hipMalloc((void**)&c->d_pyr, B * P.pyr_stride));
-    HIPCHK(c, hipMalloc((void**)&c->d_blur, B * P.blur_stride));
-    HIPCHK(c, hipMalloc((void**)&c->d_cand, B * P.cand_stride * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc((void**)&c->d_strip_cnt, B * P.strips_per_frame * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->d_scratch, B * c->scratch_stride * sizeof(uint64_t)));
-    if (hipMalloc((void**)&c->d_fin, B * P.fin_stride * sizeof(FinalKp)) != hipSuccess)
+    int rc;
+    if ((rc = c->pb.d_pyr.reserve_exact(c, B * P.pyr_stride)) || (rc = c->pb.d_blur.reserve_exact(c, B * P.blur_stride)) ||
+        (rc = c->pb.d_cand.reserve_exact(c, B * P.cand_stride)) || (rc = c->pb.d_strip_cnt.reserve_exact(c, B * P.strips_per_frame)) ||
+        (rc = c->pb.d_scratch.reserve_exact(c, B * c->scratch_stride)))
+        return rc;
+    if (c->pb.d_fin.reserve_exact(c, B * P.fin_stride) != MO_OK)
         return mo_fail(c, MO_ERR_HIP, "hipMalloc of the final-keypoint slots failed: " + std::to_string(B * P.fin_stride * sizeof(FinalKp)) +
                                           " bytes (" + std::to_string(batch) + " frames x " + std::to_string(P.fin_stride) + " slots; slots grow with response ties)");
-    HIPCHK(c, hipMalloc((void**)&c->d_fin_cnt, B * MO_MAX_LEVELS * sizeof(int)));
-    {
-        const int rc_fs = fs_build(c);  // single-frame pyramid + blur kernel: tile boxes of this plan
-        if (rc_fs) return rc_fs;
-    }
-    c->batch_alloc = batch;
+    if ((rc = c->pb.d_fin_cnt.reserve_exact(c, B * MO_MAX_LEVELS))) return rc;
+    if ((rc = fs_build(c))) return rc;  // single-frame pyramid + blur kernel: tile boxes of this plan
+    c->pb.batch_alloc = batch;
     c->plan_params = *p;
     c->plan_valid = true;
     c->fin_slack_dirty = false;

@@ -19,19 +19,16 @@
 // (re)allocates the slot arrays when rows of `cap` records do not fit; growing them invalidates every token (the row stride is the cap).
 // Callers use c->slot_cap - not their own cap - as the row stride afterwards.
 static int slots_reserve(mo_ctx* c, int cap) {
-    if (c->d_slot_kps && c->slot_cap >= cap) return MO_OK;
-    cap = (int)mo_align((size_t)cap, 16);
+    cap = (int)mo_align((size_t)std::max(cap, 1), 16);
+    if (c->slot_cap >= cap) return MO_OK;  // (slot_cap is a multiple of 16, and 0 until all four arrays stand)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    void* old[] = {c->d_slot_kps, c->d_slot_desc, c->d_slot_cnt, c->d_slot_ids};
-    for (void* b : old) if (b) hipFree(b);
-    c->d_slot_kps = nullptr; c->d_slot_desc = nullptr; c->d_slot_cnt = nullptr; c->d_slot_ids = nullptr;
     c->slot_cap = 0; c->slot_cur = -1;
     for (int s = 0; s < MO_RESULT_SLOTS; s++) { c->slot_token[s] = 0; c->slot_n[s] = 0; }
     const size_t rows = (size_t)MO_RESULT_SLOTS * cap;
-    HIPCHK(c, hipMalloc((void**)&c->d_slot_kps, rows * sizeof(mo_keypoint)));
-    HIPCHK(c, hipMalloc((void**)&c->d_slot_desc, rows * 32));
-    HIPCHK(c, hipMalloc((void**)&c->d_slot_cnt, MO_RESULT_SLOTS * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc((void**)&c->d_slot_ids, MO_RESULT_SLOTS * sizeof(int32_t)));
+    int rc;
+    if ((rc = c->d_slot_kps.reserve_exact(c, rows)) || (rc = c->d_slot_desc.reserve_exact(c, rows * 32)) ||
+        (rc = c->d_slot_cnt.reserve_exact(c, MO_RESULT_SLOTS)) || (rc = c->d_slot_ids.reserve_exact(c, MO_RESULT_SLOTS)))
+        return rc;
     int32_t ids[MO_RESULT_SLOTS];
     for (int s = 0; s < MO_RESULT_SLOTS; s++) ids[s] = s;
     HIPCHK(c, hipMemcpy(c->d_slot_ids, ids, sizeof(ids), hipMemcpyHostToDevice));
@@ -149,7 +146,7 @@ int mo_detect_single(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int 
     const size_t row = (size_t)w * ch, in_bytes = row * h, o_out = mo_align(in_bytes, 256);
     const size_t o_kps = 32, o_desc = o_kps + mo_align((size_t)scap * 28, 16), out_bytes = o_desc + (size_t)scap * 32;
     if ((rc = mo_host_stage(c, o_out + out_bytes))) return rc;
-    if ((rc = mo_reserve(c, c->d_in, c->d_in_bytes, mo_align((size_t)w * h, 256)))) return rc;
+    if ((rc = c->d_in.reserve_exact(c, mo_align((size_t)w * h, 256)))) return rc;
     uint8_t* hs = c->h_stage;
     uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
@@ -240,12 +237,12 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
                  o_mdist = L.take((size_t)cap * 2 * sizeof(int32_t)), o_mpass = L.take(cap), o_sel = L.take((size_t)cap * 2 * sizeof(int32_t)),
                  o_seld = L.take((size_t)cap * sizeof(int32_t)), o_seln = L.take(sizeof(int32_t)), o_pose = L.take(12 * sizeof(double)),
                  o_E = L.take(9 * sizeof(double)), o_inl = L.take(cap), o_np = L.take(sizeof(int32_t)), out_end = L.total;
-    if ((rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, out_end))) return rc;
+    if ((rc = c->d_tmp.reserve_exact(c, out_end))) return rc;
     if ((rc = mo_host_stage(c, std::max(2 * mo_align(up_bytes, 256), out_end)))) return rc;
     uint8_t* hs = c->h_stage;
     uint8_t* hs_dev = mo_stage_dev(c);
     if (!hs_dev) return mo_fail(c, MO_ERR_HIP, "the pinned staging buffer is not mapped into the device");
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     mo_stage_begin(c);
     int n1 = 0, n2 = 0;
     s1 = mo_slot_of(c, f1->token);  // (again: a reallocation above dropped the tokens)

@@ -81,13 +81,13 @@ static inline int fs_reflect(int p, int len) {
 }
 
 // a geometry the kernel does not take: the reason is kept for the probe's message (tools/fuzz_front_single.py tallies them)
-static int fs_no(mo_ctx* c, const char* why) { c->fs_why = why; return MO_OK; }
+static int fs_no(mo_ctx* c, const char* why) { c->pb.fs_why = why; return MO_OK; }
 
-// Builds the per-tile headers and coefficient slices of the current plan (c->d_fs_tab).  Leaves c->fs_ok false - the callers then
+// Builds the per-tile headers and coefficient slices of the current plan (c->pb.d_fs_tab).  Leaves c->pb.fs_ok false - the callers then
 // take orb_launch_pyramid / orb_launch_blur - when there is nothing to fuse or a tile does not fit in LDS.
 int fs_build(mo_ctx* c) {
-    c->fs_ok = false; c->fs_why = "";
-    if (c->d_fs_tab) { hipFree(c->d_fs_tab); c->d_fs_tab = nullptr; }
+    c->pb.fs_ok = false; c->pb.fs_why = "";
+    c->pb.d_fs_tab.reset();
     const Plan& P = c->plan;
     const int nl = P.nlevels;
     if (nl < 2) return fs_no(c, "one level: nothing to chain");
@@ -220,14 +220,13 @@ int fs_build(mo_ctx* c) {
     const size_t stride = (max_ints + 3) & ~(size_t)3;
     std::vector<uint32_t> all(stride * ntiles, 0u);
     for (int t = 0; t < ntiles; t++) std::copy(blobs[t].begin(), blobs[t].end(), all.begin() + (size_t)t * stride);
-    HIPCHK(c, hipMalloc((void**)&c->d_fs_tab, all.size() * sizeof(uint32_t)));
-    HIPCHK(c, hipMemcpy(c->d_fs_tab, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->fs_tiles = ntiles;
-    static_assert(sizeof(FsGeom) == sizeof(c->fs_geom), "FsGeom and mo_ctx::fs_geom");
-    std::memcpy(c->fs_geom, &G, sizeof(G));
-    c->fs_stride = (int)stride;
-    c->fs_lds = (int)max_lds;
-    c->fs_ok = true;
+    if (int rc = c->pb.d_fs_tab.upload(c, all)) return rc;
+    c->pb.fs_tiles = ntiles;
+    static_assert(sizeof(FsGeom) == sizeof(c->pb.fs_geom), "FsGeom and PlanBufs::fs_geom");
+    std::memcpy(c->pb.fs_geom, &G, sizeof(G));
+    c->pb.fs_stride = (int)stride;
+    c->pb.fs_lds = (int)max_lds;
+    c->pb.fs_ok = true;
     return MO_OK;
 }
 
@@ -397,17 +396,14 @@ __global__ __launch_bounds__(FS_NT) void k_front_single(Plan P, FsGeom G, const 
     }
 }
 
-// pyramid levels 1.. and (want_blur) the blurred levels 0.. of `batch` frames; the caller has checked c->fs_ok
+// pyramid levels 1.. and (want_blur) the blurred levels 0.. of `batch` frames; the caller has checked c->pb.fs_ok
 int orb_launch_front_single(mo_ctx* c, const uint8_t* d_gray, int batch, int want_blur) {
-    if (!c->fs_ok || !c->d_fs_tab) return mo_fail(c, MO_ERR_ARG, "front_single: no tile table for this plan");
-    if (!(c->lds_attr_done & 64u)) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_front_single, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_LDS));
-        c->lds_attr_done |= 64u;
-    }
+    if (!c->pb.fs_ok || !c->pb.d_fs_tab) return mo_fail(c, MO_ERR_ARG, "front_single: no tile table for this plan");
+    if (int rc = mo_raise_dyn_lds(c, (const void*)k_front_single, FS_MAX_LDS)) return rc;
     FsGeom G;
-    std::memcpy(&G, c->fs_geom, sizeof(G));
-    hipLaunchKernelGGL(k_front_single, dim3((unsigned)G.nx, (unsigned)G.ny, (unsigned)batch), dim3(FS_NT), (size_t)c->fs_lds, c->stream, c->plan, G,
-                       c->d_fs_tab, c->fs_stride, d_gray, c->d_pyr, c->d_blur, want_blur);
+    std::memcpy(&G, c->pb.fs_geom, sizeof(G));
+    hipLaunchKernelGGL(k_front_single, dim3((unsigned)G.nx, (unsigned)G.ny, (unsigned)batch), dim3(FS_NT), (size_t)c->pb.fs_lds, c->stream, c->plan, G,
+                       c->pb.d_fs_tab, c->pb.fs_stride, d_gray, c->pb.d_pyr, c->pb.d_blur, want_blur);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points) and map_io.hip (PLY text).  Here: the owning buffer types, the stores, the one reader of an observation, the helpers every map kernel file shares.
+// of duplicate points) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
 // Private to the library.
 #pragma once
 #include <algorithm>
@@ -8,49 +8,6 @@
 #include <vector>
 
 #include "common.h"
-
-// A device buffer that owns its memory: freed by its destructor, never copied.  Kernels and copies receive the raw pointer (the
-// conversion).  Sizes are element counts.
-template <class T> struct DevBuf {
-    T* p = nullptr; size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) hipFree(p); }
-    operator T*() const { return p; }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
-    // room for n elements, the contents dropped; grows by half at least (the old block is freed before the new one is made)
-    int reserve(mo_ctx* c, size_t n) {
-        size_t need = n * sizeof(T);
-        if (p && need <= bytes) return MO_OK;
-        need = std::max(need, bytes + bytes / 2);
-        return mo_reserve(c, p, bytes, need);
-    }
-    // a new block of n elements that keeps the first `keep`: allocated, copied on the context stream, synchronised, the old one freed
-    int regrow(mo_ctx* c, size_t n, size_t keep) {
-        DevBuf q;
-        q.bytes = std::max(n * sizeof(T), (size_t)16);
-        HIPCHK(c, hipMalloc((void**)&q.p, q.bytes));
-        if (p && keep) HIPCHK(c, hipMemcpyAsync(q.p, p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-        if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
-        swap(q);
-        return MO_OK;
-    }
-};
-
-// a pinned host block, made once
-template <class T> struct PinnedBuf {
-    T* p = nullptr;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(const PinnedBuf&) = delete;
-    ~PinnedBuf() { if (p) hipHostFree(p); }
-    operator T*() const { return p; }
-    int reserve(mo_ctx* c, size_t n) {
-        if (!p) HIPCHK(c, hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault));
-        return MO_OK;
-    }
-};
 
 // status block (device, int32): live counts of the call in flight
 enum { ST_NPTS = 0, ST_NOBS, ST_NNEW, ST_ERR, ST_KEPT, ST_KOBS, ST_NLIST, ST_NWORDS = 8 };

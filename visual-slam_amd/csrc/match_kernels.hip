@@ -350,8 +350,7 @@ int match_launch_pairs(mo_ctx* c, const uint8_t* d_q, const uint8_t* d_t, size_t
     const int ntile = (nt_max + ML_TILE - 1) / ML_TILE, blocks = (int)grid.x * n_pairs;
     const int n_split = blocks <= ML_SPLIT_BLOCKS ? std::min(std::min(ntile, ML_SPLIT_MAX), 256 / blocks) : 1;
     if (n_split > 1) {
-        const size_t need = (size_t)n_pairs * n_split * out_stride * sizeof(uint2);
-        if (int rc = mo_reserve(c, c->d_match_part, c->match_part_bytes, need)) return rc;
+        if (int rc = c->d_match_part.reserve_exact(c, (size_t)n_pairs * n_split * out_stride)) return rc;
         grid.z = n_split;
         hipLaunchKernelGGL(k_match_lds, grid, dim3(ML_THREADS), 0, c->stream, d_q, d_t, q_stride, t_stride, d_counts, d_qf,
                            d_tf, nq_fixed, nt_fixed, out_stride, ratio, d_idx, d_dist, d_pass, c->d_match_part);

@@ -545,12 +545,12 @@ bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp,
 // caller then blurs only the last level (orb_launch_blur from nlevels - 1).
 int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin, bool* blurred) {
     const Plan& P = c->plan;
-    auto src_of = [&](int L) { return L == 1 ? d_gray : c->d_pyr + P.lv[L - 1].off; };
+    auto src_of = [&](int L) { return L == 1 ? d_gray : c->pb.d_pyr + P.lv[L - 1].off; };
     auto sfs_of = [&](int L) { return L == 1 ? (size_t)P.w * P.h : (size_t)P.pyr_stride; };
     auto al4_of = [&](int L) { return ((((size_t)src_of(L)) | sfs_of(L) | (size_t)P.lv[L - 1].pitch) & 3) == 0 && P.lv[L - 1].pitch >= 12; };
     bool fuse = blur_margin >= 0 && nlevels == P.nlevels && nlevels >= 2 && c->rb_ok && c->rb_margin == blur_margin &&
                 c->rb_pyr_margin == margin;
-    for (int L = 1; L < nlevels && fuse; L++) fuse = al4_of(L) && c->rtab[L].two_pass_ok;
+    for (int L = 1; L < nlevels && fuse; L++) fuse = al4_of(L) && c->pb.rtab[L].two_pass_ok;
     if (blurred) *blurred = fuse;
     const uint32_t taps = (uint32_t)P.gk[0] | ((uint32_t)P.gk[1] << 8) | ((uint32_t)P.gk[2] << 16) | ((uint32_t)P.gk[3] << 24);
     for (int L = 1; L < nlevels; L++) {
@@ -558,20 +558,20 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
         const LevelInfo& d = P.lv[L];
         const uint8_t* src = src_of(L);
         size_t sfs = sfs_of(L);
-        const ResizeTab& t = c->rtab[L];
+        const ResizeTab& t = c->pb.rtab[L];
         const int org = resize_org(d, margin);
         dim3 grid((d.w - 2 * org + RS_TW - 1) / RS_TW, (d.h - 2 * org + RS_TH - 1) / RS_TH, batch);
         const uint32_t per = grid.x * grid.y, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u, inv_gx = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
         const bool al4 = al4_of(L);
         if (fuse) {
-            const BlurOut bo{c->d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, blur_margin, taps};
-            hipLaunchKernelGGL(k_resize2<true>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
+            const BlurOut bo{c->pb.d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, blur_margin, taps};
+            hipLaunchKernelGGL(k_resize2<true>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
                                (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, bo);
         } else if (al4 && t.two_pass_ok)
-            hipLaunchKernelGGL(k_resize2<false>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
+            hipLaunchKernelGGL(k_resize2<false>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
                                (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, BlurOut{});
         else
-            hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->d_pyr + d.off,
+            hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
                                (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xofs, t.xc1, t.yofs, t.yc1, inv_per, inv_gx, org);
     }
     HIPCHK(c, hipGetLastError());
@@ -677,25 +677,24 @@ int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, in
     if (nlevels < 1 || nlevels > P.nlevels || first_level < 0 || first_level >= nlevels)
         return mo_fail(c, MO_ERR_ARG, "blur: level range outside the plan");
     const int slot = margin > 0 ? 1 : 0;
-    if (slot && c->tile_margin != margin && c->d_tile_tab[1]) { hipFree(c->d_tile_tab[1]); c->d_tile_tab[1] = nullptr; }
-    if (!c->d_tile_tab[slot]) {  // (re)built with the plan: free_plan_buffers drops it
+    if (slot && c->pb.tile_margin != margin) c->pb.d_tile_tab[1].reset();
+    if (!c->pb.d_tile_tab[slot]) {  // (re)built with the plan: free_plan_buffers drops it
         std::vector<uint32_t> tab;
         for (int L = 0; L < P.nlevels; L++) {
             const int cw = std::max(P.lv[L].w - 2 * margin, 1), chh = std::max(P.lv[L].h - 2 * margin, 1);
             const int tx = (cw + BT_W - 1) / BT_W, ty = (chh + BT_H - 1) / BT_H;
-            c->tile_cum[slot][L] = (int)tab.size();
+            c->pb.tile_cum[slot][L] = (int)tab.size();
             for (int y = 0; y < ty; y++)
                 for (int x = 0; x < tx; x++) tab.push_back((uint32_t)L | ((uint32_t)x << 8) | ((uint32_t)y << 20));
         }
-        c->tile_cum[slot][P.nlevels] = (int)tab.size();
-        HIPCHK(c, hipMalloc((void**)&c->d_tile_tab[slot], tab.size() * sizeof(uint32_t)));
-        HIPCHK(c, hipMemcpy(c->d_tile_tab[slot], tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (slot) c->tile_margin = margin;
+        c->pb.tile_cum[slot][P.nlevels] = (int)tab.size();
+        if (int rc = c->pb.d_tile_tab[slot].upload(c, tab)) return rc;
+        if (slot) c->pb.tile_margin = margin;
     }
-    const int tile0 = c->tile_cum[slot][first_level];
-    const uint32_t per = (uint32_t)(c->tile_cum[slot][nlevels] - tile0), inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
-    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->d_tile_tab[slot], tile0, inv_per, margin, d_gray,
-                       c->d_pyr, c->d_blur);
+    const int tile0 = c->pb.tile_cum[slot][first_level];
+    const uint32_t per = (uint32_t)(c->pb.tile_cum[slot][nlevels] - tile0), inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
+    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->pb.d_tile_tab[slot], tile0, inv_per, margin, d_gray,
+                       c->pb.d_pyr, c->pb.d_blur);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -1018,22 +1017,16 @@ template <int TW, int NT> static int launch_fast_tw(mo_ctx* c, const uint8_t* d_
     const Plan& P = c->plan;
     size_t lds = score_bytes + (size_t)(max_rows + 8) * TW + 16;
     if (lds > 128 * 1024) return mo_fail(c, MO_ERR_UNSUPPORTED, "level too wide for the FAST strip kernel");
-    const unsigned bit = (TW == 704 ? 1u : TW == 1344 ? 2u : TW == 2112 ? 4u : TW == 608 ? 32u : 8u) << (NT == 512 ? 8 : 0);
-    if (!(c->lds_attr_done & bit)) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_fast<TW, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        c->lds_attr_done |= bit;
-    }
-    if (!c->d_strip_tab) {  // (re)built with the plan: free_plan_buffers drops it
+    if (int rc = mo_raise_dyn_lds(c, (const void*)k_fast<TW, NT>, 128 * 1024)) return rc;
+    if (!c->pb.d_strip_tab) {  // (re)built with the plan: free_plan_buffers drops it
         std::vector<uint32_t> tab((size_t)P.strips_per_frame, 0xFFFFFF00u);  // (no level has that many strips: the kernel returns)
         for (int L = 0; L < P.nlevels; L++)
             for (int st = 0; st < P.lv[L].nstrips; st++) tab[(size_t)P.lv[L].strip_base + st] = (uint32_t)L | ((uint32_t)st << 8);
-        HIPCHK(c, hipMalloc((void**)&c->d_strip_tab, tab.size() * sizeof(uint32_t)));
-        HIPCHK(c, hipMemcpy(c->d_strip_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->n_strip_tab = (int)tab.size();
+        if (int rc = c->pb.d_strip_tab.upload(c, tab)) return rc;
     }
     const uint32_t per = (uint32_t)nstrips, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
-    hipLaunchKernelGGL((k_fast<TW, NT>), dim3(nstrips, batch), dim3(NT), lds, c->stream, P, c->d_strip_tab, inv_per, strip0, d_gray,
-                       c->d_pyr, c->d_cand, c->d_strip_cnt, (int)score_bytes);
+    hipLaunchKernelGGL((k_fast<TW, NT>), dim3(nstrips, batch), dim3(NT), lds, c->stream, P, c->pb.d_strip_tab, inv_per, strip0, d_gray,
+                       c->pb.d_pyr, c->pb.d_cand, c->pb.d_strip_cnt, (int)score_bytes);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -1313,11 +1306,10 @@ int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo,
     for (int L = 0; L < P.nlevels; L++) max_strips = std::max(max_strips, P.lv[L].nstrips);
     const size_t pref_bytes = (((size_t)max_strips + 1) * sizeof(int) + 15) & ~(size_t)15;
     const size_t attr_bytes = SEL_BUF_BYTES + ((((size_t)SEL_MAXSTRIPS + 1) * sizeof(int) + 15) & ~(size_t)15);
-    if (!(c->lds_attr_done & 16u)) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_select<SEL_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_bytes));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_select<SEL_THREADS_LATENCY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_bytes));
-        c->lds_attr_done |= 16u;
-    }
+    int rc;  // (both forms at the first launch of either)
+    if ((rc = mo_raise_dyn_lds(c, (const void*)k_select<SEL_THREADS>, (int)attr_bytes)) ||
+        (rc = mo_raise_dyn_lds(c, (const void*)k_select<SEL_THREADS_LATENCY>, (int)attr_bytes)))
+        return rc;
     // One launch, every workgroup with the full LDS record window (3 resident per CU at 256 threads), levels in dispatch order from fine
     // to coarse: the replays are latency-bound chains whose length grows with the candidate count, so the long level-0 tasks start first
     // and the short coarse-level tasks fill the slots that free up (longest-task-first packing).  A level that outgrows the window falls
@@ -1325,13 +1317,14 @@ int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo,
     // levels with a smaller window (8 - 24 KB, more workgroups per CU): 0.23 - 0.25 ms against 0.20 ms; selecting the finest level on the
     // auxiliary stream beside FAST of the others: no gain (the coarse levels alone take 0.19 ms: the kernel is bound by the sum of the
     // replays, not by the finest level).  One or two frames (the single-frame host calls): 16 wavefronts per workgroup.
+    // (c->pb.d_dtodo is null at the first selection under a plan: orb_launch_describe makes and clears the list, the kernel tests for null)
     const dim3 grid(batch, level_hi - level_lo);
     if (batch <= 2)
-        hipLaunchKernelGGL(k_select<SEL_THREADS_LATENCY>, grid, dim3(SEL_THREADS_LATENCY), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->d_pyr, c->d_cand,
-                           c->d_strip_cnt, c->d_scratch, c->scratch_stride, c->d_fin, c->d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->d_dtodo);
+        hipLaunchKernelGGL(k_select<SEL_THREADS_LATENCY>, grid, dim3(SEL_THREADS_LATENCY), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->pb.d_pyr, c->pb.d_cand,
+                           c->pb.d_strip_cnt, c->pb.d_scratch, c->scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
     else
-        hipLaunchKernelGGL(k_select<SEL_THREADS>, grid, dim3(SEL_THREADS), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->d_pyr, c->d_cand,
-                           c->d_strip_cnt, c->d_scratch, c->scratch_stride, c->d_fin, c->d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->d_dtodo);
+        hipLaunchKernelGGL(k_select<SEL_THREADS>, grid, dim3(SEL_THREADS), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->pb.d_pyr, c->pb.d_cand,
+                           c->pb.d_strip_cnt, c->pb.d_scratch, c->scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -1351,9 +1344,9 @@ __global__ __launch_bounds__(SEL_THREADS) void k_retain_probe(const float* resp,
 int orb_launch_retain_probe(mo_ctx* c, const float* d_resp, int n, int n_points, int order, int32_t* d_order, int* d_nout) {
     size_t nn = (size_t)std::max(n, 1);
     size_t rec_b = nn * sizeof(uint64_t), rpos_b = ((nn / 2 + 4) * 2 + 7) & ~(size_t)7, bl_b = (nn / 64 + 8) * 8;
-    int rc = mo_reserve(c, c->d_tmp, c->tmp_bytes, rec_b + rpos_b + bl_b);
+    int rc = c->d_tmp.reserve_exact(c, rec_b + rpos_b + bl_b);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)c->d_tmp;
+    uint8_t* b = c->d_tmp;
     hipLaunchKernelGGL(k_retain_probe, dim3(1), dim3(SEL_THREADS), 0, c->stream, d_resp, n, n_points, order, (uint64_t*)b,
                        (uint16_t*)(b + rec_b), (unsigned long long*)(b + rec_b + rpos_b), d_order, d_nout);
     HIPCHK(c, hipGetLastError());
@@ -1783,16 +1776,16 @@ __global__ __launch_bounds__(DT_NT) void k_describe_tiles_rare(Plan P, const uin
 
 int orb_launch_describe(mo_ctx* c, const uint8_t* d_gray, int batch, mo_keypoint* d_kps, uint8_t* d_desc, int cap, int* d_counts) {
     const Plan& P = c->plan;
-    if (!c->d_dtile_tab) {  // (re)built with the plan: free_plan_buffers drops it
+    if (!c->pb.d_dtile_tab) {  // (re)built with the plan: free_plan_buffers drops it
         // tile table (level | tile column << 8 | tile row << 20, level-major) followed by the intensity-centroid weights
         // [32 rows][8 weight + 8 mask dwords]
         std::vector<uint32_t> tab;
         for (int L = 0; L < P.nlevels; L++)
             for (int y = 0; y < (P.lv[L].bh + DT_H - 1) / DT_H; y++)
                 for (int x = 0; x < (P.lv[L].bw + DT_W - 1) / DT_W; x++) tab.push_back((uint32_t)L | ((uint32_t)x << 8) | ((uint32_t)y << 20));
-        c->n_dtiles = (int)tab.size();
+        c->pb.n_dtiles = (int)tab.size();
         while (tab.size() % 4) tab.push_back(0);  // the weight rows are read as uint4
-        c->dtile_icw_off = (int)tab.size();
+        c->pb.dtile_icw_off = (int)tab.size();
         tab.resize(tab.size() + 512, 0u);
         for (int r = 0; r < 31; r++) {
             const int d = P.umax[r < 15 ? 15 - r : r - 15];
@@ -1802,43 +1795,39 @@ int orb_launch_describe(mo_ctx* c, const uint8_t* d_gray, int batch, mo_keypoint
                     const int u = 4 * c4 - 15 + b;
                     if (u >= -d && u <= d) { wv |= (uint32_t)(u + 16) << (8 * b); mv |= 1u << (8 * b); }
                 }
-                tab[c->dtile_icw_off + r * 16 + c4] = wv;
-                tab[c->dtile_icw_off + r * 16 + 8 + c4] = mv;
+                tab[c->pb.dtile_icw_off + r * 16 + c4] = wv;
+                tab[c->pb.dtile_icw_off + r * 16 + 8 + c4] = mv;
             }
         }
-        HIPCHK(c, hipMalloc((void**)&c->d_dtile_tab, tab.size() * sizeof(uint32_t)));
-        HIPCHK(c, hipMemcpy(c->d_dtile_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = c->pb.d_dtile_tab.upload(c, tab)) return rc;
     }
-    if (c->n_dtiles == 0) {  // no level has a border region: every frame has zero keypoints
+    if (c->pb.n_dtiles == 0) {  // no level has a border region: every frame has zero keypoints
         HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)batch * sizeof(int), c->stream));
         return MO_OK;
     }
     // one or two frames: DT_SPLIT_LATENCY workgroups per tile, each describing the keypoints of one residue class of the level's list.  A coarse
     // level is one or two tiles holding all of its ~ 120 keypoints - eight passes of 16 in one workgroup while most CUs sit idle; the tile is
     // loaded once per sharing workgroup, which costs nothing there (profiles/r04_ab_describe_split.txt)
-    const dim3 grid(c->n_dtiles, batch, batch <= 2 ? DT_SPLIT_LATENCY : 1);
+    const dim3 grid(c->pb.n_dtiles, batch, batch <= 2 ? DT_SPLIT_LATENCY : 1);
     const uint32_t inv_per = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
     // todo list of the tiles the one-pass kernel leaves to k_describe_tiles_rare: [0] count (cleared by k_select of the same call), then
     // frame * tiles + tile entries; sized for every tile of the largest batch
-    const size_t todo_need = (1 + (size_t)c->n_dtiles * c->batch_alloc * DT_SPLIT_LATENCY) * sizeof(int);  // (each sharing workgroup may leave an entry)
-    if (c->dtodo_bytes < todo_need) {
-        if (c->d_dtodo) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->d_dtodo)); c->d_dtodo = nullptr; c->dtodo_bytes = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->d_dtodo, todo_need));
-        HIPCHK(c, hipMemsetAsync(c->d_dtodo, 0, sizeof(int), c->stream));
-        c->dtodo_bytes = todo_need;
+    if (!c->pb.d_dtodo) {  // made with the plan's first describe: n_dtiles and batch_alloc are the plan's
+        if (int rc = c->pb.d_dtodo.reserve_exact(c, 1 + (size_t)c->pb.n_dtiles * c->pb.batch_alloc * DT_SPLIT_LATENCY)) return rc;  // (each sharing workgroup may leave an entry)
+        HIPCHK(c, hipMemsetAsync(c->pb.d_dtodo, 0, sizeof(int), c->stream));
     }
-    const uint32_t* icw = c->d_dtile_tab + c->dtile_icw_off;
-    const dim3 rare_grid(std::min(c->n_dtiles * batch, 256));
+    const uint32_t* icw = c->pb.d_dtile_tab + c->pb.dtile_icw_off;
+    const dim3 rare_grid(std::min(c->pb.n_dtiles * batch, 256));
     if (d_desc) {
-        hipLaunchKernelGGL(k_describe_tiles<true>, grid, dim3(DT_NT), 0, c->stream, P, c->d_dtile_tab, inv_per, d_gray, c->d_pyr, c->d_blur,
-                           c->d_fin, c->d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->d_dtodo);
-        hipLaunchKernelGGL(k_describe_tiles_rare<true>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->d_dtile_tab, c->n_dtiles, d_gray, c->d_pyr,
-                           c->d_blur, c->d_fin, c->d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->d_dtodo);
+        hipLaunchKernelGGL(k_describe_tiles<true>, grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
+                           c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
+        hipLaunchKernelGGL(k_describe_tiles_rare<true>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
+                           c->pb.d_blur, c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
     } else {
-        hipLaunchKernelGGL(k_describe_tiles<false>, grid, dim3(DT_NT), 0, c->stream, P, c->d_dtile_tab, inv_per, d_gray, c->d_pyr, c->d_blur,
-                           c->d_fin, c->d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->d_dtodo);
-        hipLaunchKernelGGL(k_describe_tiles_rare<false>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->d_dtile_tab, c->n_dtiles, d_gray, c->d_pyr,
-                           c->d_blur, c->d_fin, c->d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->d_dtodo);
+        hipLaunchKernelGGL(k_describe_tiles<false>, grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
+                           c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
+        hipLaunchKernelGGL(k_describe_tiles_rare<false>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
+                           c->pb.d_blur, c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
     }
     HIPCHK(c, hipGetLastError());
     return MO_OK;
@@ -1915,7 +1904,7 @@ int orb_launch_describe_cells(mo_ctx* c, const mo_keypoint* d_kps, const int32_t
     const int cw = P.w / 8, ch = P.h / 8;
     const int tpitch = (cw + 38 + 7 + 7) & ~7;
     if ((size_t)tpitch * (ch + 38) > DC_TILE_BYTES || P.edge_threshold < 19) return MO_ERR_UNSUPPORTED;  // (the caller falls back)
-    hipLaunchKernelGGL(k_describe_cells, dim3(64, batch), dim3(256), 0, c->stream, P, c->d_blur, d_kps, d_kbase, d_desc, cap, cw, ch, tpitch);
+    hipLaunchKernelGGL(k_describe_cells, dim3(64, batch), dim3(256), 0, c->stream, P, c->pb.d_blur, d_kps, d_kbase, d_desc, cap, cw, ch, tpitch);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -1945,7 +1934,7 @@ int orb_launch_describe_given(mo_ctx* c, const uint8_t* d_gray, const mo_keypoin
                               int n_stride) {
     if (n <= 0) return MO_OK;
     const Plan& P = c->plan;
-    hipLaunchKernelGGL(k_describe_given, dim3((n + 3) / 4, batch), dim3(256), 0, c->stream, P, d_gray, c->d_pyr, c->d_blur, d_kps,
+    hipLaunchKernelGGL(k_describe_given, dim3((n + 3) / 4, batch), dim3(256), 0, c->stream, P, d_gray, c->pb.d_pyr, c->pb.d_blur, d_kps,
                        n, d_n, n_stride, d_desc);
     HIPCHK(c, hipGetLastError());
     return MO_OK;

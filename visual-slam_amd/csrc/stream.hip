@@ -74,11 +74,11 @@ private:
 };
 
 struct Lane {
-    uint8_t* h_in = nullptr;    // pinned [chunk + 1][h][w][ch]
-    uint8_t* d_in = nullptr;    // device, the same
-    uint8_t* d_gray = nullptr;  // device [chunk + 1][h][w] (ch == 3 only; ch == 1: d_in is the gray batch)
-    uint8_t* d_out = nullptr;   // device results, one slab (offsets in mo_stream)
-    uint8_t* h_out = nullptr;   // pinned, the same layout
+    PinnedBuf<uint8_t> h_in;    // pinned [chunk + 1][h][w][ch]
+    DevBuf<uint8_t> d_in;       // device, the same
+    DevBuf<uint8_t> d_gray;     // device [chunk + 1][h][w] (ch == 3 only; ch == 1: d_in is the gray batch)
+    DevBuf<uint8_t> d_out;      // device results, one slab (offsets in mo_stream)
+    PinnedBuf<uint8_t> h_out;   // pinned, the same layout
     hipEvent_t copied = nullptr, computed = nullptr, done = nullptr;
     int n_frames = 0;           // frames of the chunk in flight (without the halo); 0 = lane free
     int halo = 0;               // 1: frame 0 of the batch is the previous chunk's last frame
@@ -119,17 +119,12 @@ extern "C" void mo_stream_destroy(mo_stream* s) {
     if (s->copy_s) { hipStreamSynchronize(s->copy_s); hipStreamDestroy(s->copy_s); }
     if (s->down_s) { hipStreamSynchronize(s->down_s); hipStreamDestroy(s->down_s); }
     for (Lane& l : s->lane) {
-        if (l.h_in) hipHostFree(l.h_in);
-        if (l.h_out) hipHostFree(l.h_out);
-        if (l.d_in) hipFree(l.d_in);
-        if (l.d_gray) hipFree(l.d_gray);
-        if (l.d_out) hipFree(l.d_out);
         if (l.copied) hipEventDestroy(l.copied);
         if (l.done) hipEventDestroy(l.done);
         if (l.computed) hipEventDestroy(l.computed);
     }
     delete s->pool;
-    delete s;
+    delete s;  // (the lanes' buffers free themselves)
 }
 
 extern "C" mo_stream* mo_stream_create(mo_ctx* c, const mo_orb_params* orb, const mo_stream_params* p) {
@@ -157,11 +152,11 @@ extern "C" mo_stream* mo_stream_create(mo_ctx* c, const mo_orb_params* orb, cons
     s->out_bytes = L.total;
     bool ok = hipStreamCreateWithFlags(&s->copy_s, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&s->down_s, hipStreamNonBlocking) == hipSuccess;
     for (Lane& l : s->lane) {
-        ok = ok && hipHostMalloc((void**)&l.h_in, B * s->frame_in, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&l.h_out, s->out_bytes, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipMalloc((void**)&l.d_in, B * s->frame_in) == hipSuccess;
-        if (p->ch == 3) ok = ok && hipMalloc((void**)&l.d_gray, B * s->frame_px) == hipSuccess;
-        ok = ok && hipMalloc((void**)&l.d_out, s->out_bytes) == hipSuccess;
+        ok = ok && l.h_in.reserve(c, B * s->frame_in) == MO_OK;
+        ok = ok && l.h_out.reserve(c, s->out_bytes) == MO_OK;
+        ok = ok && l.d_in.reserve_exact(c, B * s->frame_in) == MO_OK;
+        if (p->ch == 3) ok = ok && l.d_gray.reserve_exact(c, B * s->frame_px) == MO_OK;
+        ok = ok && l.d_out.reserve_exact(c, s->out_bytes) == MO_OK;
         ok = ok && hipEventCreateWithFlags(&l.copied, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&l.done, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&l.computed, hipEventDisableTiming) == hipSuccess;
@@ -227,7 +222,7 @@ extern "C" int mo_stream_submit(mo_stream* s, const uint8_t* frames, int n, int 
     float* d_pts = nullptr;
     if (s->p.want_points) d_pts = (float*)(o + s->o_pts);
     else {
-        if ((rc = mo_reserve(c, c->d_stream_pts, c->stream_pts_bytes, (size_t)s->p.chunk * s->p.cap * 3 * sizeof(float)))) return rc;
+        if ((rc = c->d_stream_pts.reserve_exact(c, (size_t)s->p.chunk * s->p.cap * 3))) return rc;
         d_pts = c->d_stream_pts;
     }
     io.d_points = d_pts;

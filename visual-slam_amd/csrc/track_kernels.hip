@@ -174,7 +174,7 @@ int track_select_launch(mo_ctx* c, const mo_keypoint* d_kps, const int32_t* d_co
     uint32_t* gkeys = nullptr;
     size_t lds = (size_t)cap * 2 * sizeof(uint32_t);
     if (cap > TS_LDS_CAP) {  // frames beyond 6 000 keypoints: the key arrays in an HBM scratch slot per pair
-        int rc = mo_reserve(c, c->d_track_keys, c->track_keys_bytes, (size_t)n_pairs * cap * 2 * sizeof(uint32_t));
+        int rc = c->d_track_keys.reserve_exact(c, (size_t)n_pairs * cap * 2);
         if (rc) return rc;
         gkeys = c->d_track_keys;
         lds = 0;

@@ -1296,7 +1296,7 @@ int twoview_launch(mo_ctx* c, const TwoViewArgs& a_in) {
     a.flags = c->flags_cur ? c->flags_cur : c->d_flags;
     if (!a.d_E_in && (a.n_hyp < 1 || a.n_hyp > (1 << 20))) return mo_fail(c, MO_ERR_ARG, "n_hyp out of range");
     size_t need = twoview_workspace_bytes(a.n_pairs, a.cap, a.n_hyp);
-    int rc = mo_reserve(c, c->d_tv, c->tv_bytes, need);
+    int rc = c->d_tv.reserve_exact(c, need);
     if (rc) return rc;
     TvWork w = carve(c->d_tv, a.n_pairs, a.cap, a.n_hyp);
     hipLaunchKernelGGL(k_tv_prep, dim3(a.n_pairs), dim3(TV_BLOCK), 0, c->stream, a, w);
