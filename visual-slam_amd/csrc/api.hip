@@ -125,7 +125,7 @@ static int run_grid_extract(mo_ctx* c, const mo_orb_params* p, const mo_batch_io
     int32_t* d_kb = L.at<int32_t>(c->d_tmp, o_kb);
     if ((rc = gftt_records_launch(c, d_xy, d_n, per_cell, w, h, p->edge_threshold, io->d_kps, io->d_grid_kept, cap, io->d_counts, batch, d_kb))) return rc;
     mo_stage_mark(c, "grid_good_features");
-    const int blur_margin = (c->plan.edge_threshold - 19) & ~3;
+    const int blur_margin = mo_blur_margin(c->plan.edge_threshold);
     if ((rc = orb_launch_blur(c, io->d_gray, batch, 1, blur_margin))) return rc;  // the records all sit on octave 0
     mo_stage_mark(c, "blur");
     // descriptors out of one blurred LDS tile per grid cell; cells too large for the tile (frames beyond ~ 720 x 480) take the
@@ -864,7 +864,7 @@ extern "C" int mo_dbg_blur_level(mo_ctx* c, int frame, int level, uint8_t* out, 
     if (frame < 0 || frame >= c->pb.batch_alloc) return mo_fail(c, MO_ERR_ARG, "frame out of range");
     const LevelInfo& v = c->plan.lv[level];
     *lw = v.w; *lh = v.h;
-    if (resize_blur) *resize_blur = c->rb_ok ? 1 : 0;
+    if (resize_blur) *resize_blur = c->pb.rb_ok ? 1 : 0;
     HIPCHK(c, hipMemcpy2DAsync(out, v.w, c->pb.d_blur + (size_t)frame * c->plan.blur_stride + v.boff, v.bpitch, v.w, v.h,
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -11,49 +11,7 @@
 #include <vector>
 
 #include "../../include/vslam_amd.h"
-
-#define MO_MAX_LEVELS 12
-#define MO_HALF_PATCH 15
-#define MO_STRIP_ROWS 8
-// rows per FAST strip in a context for one or two frames at a time (max_batch <= 2): such a call waits for the longest strip's chain, so
-// shorter strips on more workgroups cut it (FAST stage of one 640x480 frame: 26.3 / 18.2 / 15.5 / 14.2 us at 8 / 4 / 3 / 2 rows; the
-// selection's gather pays 2 us for the extra strips; 1 row: slower again; profiles/r04_ab_strip_rows_single.txt)
-#ifndef MO_STRIP_ROWS_LATENCY
-#define MO_STRIP_ROWS_LATENCY 2
-#endif
-#define SEL_MAXSTRIPS 2047  // strips of one level that k_select's prefix table (dynamic LDS, behind the record window) holds
-
-// per-level geometry, uploaded by value as a kernel argument
-struct LevelInfo {
-    int w, h, pitch;      // level size and row pitch in bytes (level 0: pitch = w, aliases the input)
-    int off;              // byte offset of the level inside one frame's raw pyramid slab (level 0: unused)
-    int bpitch, boff;     // row pitch / byte offset inside one frame's blurred pyramid slab
-    float scale;          // (float)pow((double)scale_factor, L)
-    int quota;            // features wanted on this level
-    int bx0, by0, bw, bh; // border region [bx0, bx0+bw) x [by0, by0+bh): keypoints allowed here
-    uint32_t inv_bw;      // floor(2^32 / bw) + 1 for bw > 1: i / bw == mulhi(i, inv_bw) while i * bw < 2^32
-    int strip_rows;       // rows per FAST strip
-    int nstrips;          // strips covering the border region
-    int strip_cap;        // entries per strip slot
-    int strip_base;       // index of this level's first strip among one frame's strips
-    int cand_off;         // entry offset of this level's first strip slot in one frame's candidate slab
-    int cand_cap;         // total candidate capacity of the level (nstrips * strip_cap)
-    int fin_off, fin_cap; // final-keypoint slot of the level in one frame's slab
-    int scr_off;          // u64 offset of the level's overflow scratch inside one frame's scratch slab
-};
-
-struct Plan {
-    int w, h, nlevels;
-    int edge_threshold, fast_threshold, select_order, nfeatures;
-    int pyr_stride;      // bytes per frame of the raw pyramid slab (levels 1..n-1)
-    int blur_stride;     // bytes per frame of the blurred pyramid slab (levels 0..n-1)
-    int strips_per_frame;
-    int cand_stride;     // candidate entries (u32) per frame
-    int fin_stride;      // final entries per frame
-    int umax[MO_HALF_PATCH + 1];
-    int gk[7];           // 7-tap Gaussian, 8 fractional bits
-    LevelInfo lv[MO_MAX_LEVELS];
-};
+#include "plan_tables.h"  // LevelInfo, Plan, PlanTables and the constants they are sized by
 
 struct FinalKp {  // 8 bytes: survivor of both retainBest passes, level coordinates
     uint16_t x, y;
@@ -125,34 +83,25 @@ template <class T> struct PinnedBuf {
     int reserve(mo_ctx* c, size_t n, unsigned flags = hipHostMallocDefault);
 };
 
-struct ResizeTab {  // views into one level's INTER_LINEAR_EXACT coefficients (one block, PlanBufs::rblock; base = xpk)
-    // packed per output column / row, padded to a multiple of 64 entries with the last one: source offset (15 bits) |
-    // (right / lower neighbour offset - offset) << 15 | weight of that neighbour in 1/256 units << 16 (k_resize2)
-    uint32_t* xpk = nullptr; uint32_t* ypk = nullptr;
-    int* xofs = nullptr; int* xc1 = nullptr; int* yofs = nullptr; int* yc1 = nullptr;  // the same, unpacked (k_resize)
-    bool two_pass_ok = true;  // k_resize2's 8-byte source window holds every group of 4 output columns
-};
-
-// Everything a plan allocates, with the counts that describe its tables.  A rebuild drops it whole (c->pb = PlanBufs()): a buffer
-// added here needs no line anywhere else to be freed.  The tables are uploaded on their first use under the plan.
-struct PlanBufs {
+// Everything a plan owns on top of the Plan itself: the launch constants and table offsets (PlanTables), the one block all the
+// tables are uploaded in, and the work buffers.  fill_plan (ctx.hip) makes all of it, tables included, before any launcher runs; a
+// rebuild drops it whole (c->pb = PlanBufs()): a field added here needs no line anywhere else to be freed or reset.
+struct PlanBufs : PlanTables {
     int batch_alloc = 0;           // frames the work buffers below are sized for
+    // the batched extraction's resize launches can write the blurred levels too (orb_plan_resize_blur held for every level at
+    // the pipeline's margins rb_pyr_margin / rb_margin)
+    bool rb_ok = false;
+    int rb_margin = -1, rb_pyr_margin = -1;
+    DevBuf<uint32_t> d_tables;     // the block of plan_build_tables: the offsets of PlanTables index it
     DevBuf<uint8_t> d_pyr;         // [batch][pyr_stride]
     DevBuf<uint8_t> d_blur;        // [batch][blur_stride]
     DevBuf<uint32_t> d_cand;       // [batch][cand_stride]
     DevBuf<int> d_strip_cnt;       // [batch][strips_per_frame]
-    DevBuf<uint64_t> d_scratch;    // [batch][nlevels] overflow scratch for the selection replay
+    DevBuf<uint64_t> d_scratch;    // [batch][scratch_stride] overflow scratch for the selection replay
     DevBuf<FinalKp> d_fin;         // [batch][fin_stride]
     DevBuf<int> d_fin_cnt;         // [batch][MO_MAX_LEVELS]
-    DevBuf<uint32_t> rblock[MO_MAX_LEVELS];                // resize coefficients of level L: the block the views of rtab[L] point into
-    ResizeTab rtab[MO_MAX_LEVELS];
-    DevBuf<uint32_t> d_tile_tab[2];                        // blur: tile -> level | tile column << 8 | tile row << 20; [0]: whole levels, [1]: without the margin tile_margin
-    int tile_cum[2][MO_MAX_LEVELS + 1] = {};               // tiles of levels < L (the tables are level-major: a prefix blurs the first levels)
-    int tile_margin = 0;
+    DevBuf<int> d_dtodo;           // k_describe_tiles -> k_describe_tiles_rare: [0] count, then frame * tiles + tile; [1 + n_dtiles * batch * DT_SPLIT_LATENCY]
     DevBuf<uint32_t> d_fs_tab; int fs_tiles = 0, fs_stride = 0, fs_lds = 0; bool fs_ok = false; int fs_geom[10] = {}; const char* fs_why = "";  // k_front_single: per-tile headers + coefficient slices (fs_build)
-    DevBuf<uint32_t> d_strip_tab;                          // FAST: strip of a frame -> level | strip of the level << 8
-    DevBuf<uint32_t> d_dtile_tab; int n_dtiles = 0, dtile_icw_off = 0;  // k_describe_tiles: tile -> level | column << 8 | row << 20, then the centroid weights
-    DevBuf<int> d_dtodo;           // k_describe_tiles -> k_describe_tiles_rare: [0] count, then frame * tiles + tile
 };
 
 #define MO_RESULT_SLOTS 4
@@ -184,11 +133,6 @@ struct mo_ctx {
     int tie_levels = 0;                     // ... on these levels (bit L)
     mo_orb_params plan_params{};
     Plan plan{};
-    // the batched extraction's resize launches can write the blurred levels too (orb_plan_resize_blur held for every level at
-    // the pipeline's margins rb_pyr_margin / rb_margin)
-    bool rb_ok = false;
-    int rb_margin = -1, rb_pyr_margin = -1;
-    size_t scratch_stride = 0;     // u64 entries per frame of overflow scratch
     PlanBufs pb;                   // what the plan allocated
 
     // work buffers (device)
@@ -249,8 +193,6 @@ template <class T> int PinnedBuf<T>::reserve(mo_ctx* c, size_t n, unsigned flags
 
 // the kernel's max-dynamic-LDS attribute raised to `bytes`, once per kernel function and context (ctx.hip)
 int mo_raise_dyn_lds(mo_ctx* c, const void* kernel, int bytes);
-
-static inline size_t mo_align(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
 // bump layout of a scratch region (c->d_tmp, a result slab): every piece starts on a 256-byte boundary
 struct Layout {
@@ -318,21 +260,17 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch);
 // kernel launchers (orb_kernels.hip)
 int orb_launch_gray(mo_ctx* c, const uint8_t* d_bgr, int w, int h, int batch, uint8_t* d_gray);
 int orb_launch_ingest(mo_ctx* c, const uint8_t* src_mapped, int w, int h, int ch, uint8_t* d_gray, int* flags_clear);
-// margins of the levels nothing in the batched pipeline reads (see orb_launch_blur / orb_launch_pyramid)
-inline int mo_blur_margin(int edge_threshold) { return (edge_threshold - 19) & ~3; }
-inline int mo_pyr_margin(int edge_threshold) { return std::max(mo_blur_margin(edge_threshold) - 4, 0); }
 // blur_margin >= 0: the resize launches may also write the blurred levels 0 .. nlevels-2 (*blurred says whether they did)
 int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin = -1,
                        bool* blurred = nullptr);
 // plan time (ctx.hip): whether that blurring resize of level L covers level L-1's blur region at these margins
-bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp, const std::vector<uint32_t>& yp, int margin,
-                          int blur_margin);
+// (xp / yp: the level's packed column / row coefficients, nx / ny entries)
+bool orb_plan_resize_blur(const Plan& P, int L, const uint32_t* xp, size_t nx, const uint32_t* yp, size_t ny, int margin, int blur_margin);
 // front_single.hip: pyramid + blur of a few frames in ONE launch (single-frame calls); fs_build runs with the plan and leaves
 // c->fs_ok false for geometries it does not cover, which keep orb_launch_pyramid + orb_launch_blur
 #define MO_FS_MAX_BATCH 2
 int fs_build(mo_ctx* c);
 int orb_launch_front_single(mo_ctx* c, const uint8_t* d_gray, int batch, int want_blur);
-void mo_linear_coeffs(int srcsize, int dstsize, std::vector<int>& ofs, std::vector<int>& c1);
 int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int first_level = 0);
 int orb_launch_fast(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo = 0, int level_hi = MO_MAX_LEVELS);
 int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo = 0, int level_hi = MO_MAX_LEVELS);

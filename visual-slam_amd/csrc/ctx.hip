@@ -1,10 +1,7 @@
 // ctx.hip -- context lifetime, the per-(w,h,params) plan, work-buffer sizing and stage timing.
 //
-// The plan holds everything the kernels need that OpenCV derives on the host inside
-// ORB_Impl::detectAndCompute (level scales and sizes, per-level quotas, the circular-patch umax table,
-// the INTER_LINEAR_EXACT coefficient tables, the quantised Gaussian taps).  It is host arithmetic done
-// once per image size, in the same float/double expressions cv2 uses (reference call site:
-// src/orbslam2/extractor.py:38-48,65).
+// What a plan is, and the host arithmetic that derives it once per image size, is in plan_tables.h; fill_plan below turns it
+// into device memory: the table block in one upload, then the work buffers.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -20,10 +17,6 @@ int mo_fail(mo_ctx* c, int code, const std::string& msg) {
 }
 
 static std::string g_create_err;
-
-static inline int cv_round_f(float v) { return (int)lrintf(v); }
-static inline int cv_round_d(double v) { return (int)lrint(v); }
-static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 extern "C" int mo_abi_version(void) { return MO_ABI_VERSION; }
 
@@ -157,35 +150,6 @@ extern "C" int mo_stage_times_back(mo_ctx* c, int back, const char*** names, flo
 
 extern "C" int mo_stage_times(mo_ctx* c, const char*** names, float* ms, int cap) { return mo_stage_times_back(c, 0, names, ms, cap); }
 
-// INTER_LINEAR_EXACT coefficient table of one axis (interpolationLinear<ufixedpoint16>::getCoeffs):
-// offset + the weight of the right/lower neighbour in 1/256 units (left weight = 256 - c1).
-void mo_linear_coeffs(int srcsize, int dstsize, std::vector<int>& ofs, std::vector<int>& c1) {
-    ofs.assign(dstsize, 0);
-    c1.assign(dstsize, 0);
-    double inv_scale = (double)dstsize / (double)srcsize;
-    double scale = 1.0 / inv_scale;
-    int minofst = 0, maxofst = dstsize;
-    for (int val = 0; val < dstsize; val++) {
-        double fval = scale * ((double)val + 0.5) - 0.5;
-        int ival = (int)std::floor(fval);
-        if (ival >= 0 && srcsize > 1) {
-            if (ival < srcsize - 1) {
-                ofs[val] = ival;
-                c1[val] = cv_round_d((fval - (double)ival) * 256.0);
-            } else {
-                ofs[val] = srcsize - 1;
-                maxofst = std::min(maxofst, val);
-            }
-        } else {
-            minofst = std::max(minofst, val + 1);
-        }
-    }
-    for (int val = 0; val < dstsize; val++) {
-        if (val < minofst) { ofs[val] = 0; c1[val] = 0; }
-        if (val >= maxofst) { ofs[val] = srcsize - 1; c1[val] = 0; }
-    }
-}
-
 static bool params_equal(const mo_orb_params& a, const mo_orb_params& b) {
     return std::memcmp(&a, &b, sizeof(a)) == 0;
 }
@@ -222,152 +186,40 @@ int mo_build_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
 
 static int fill_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch) {
     Plan& P = c->plan;
-    std::memset(&P, 0, sizeof(P));
-    P.w = w; P.h = h; P.nlevels = p->nlevels;
-    P.edge_threshold = p->edge_threshold;
-    P.fast_threshold = std::min(std::max(p->fast_threshold, 0), 255);
-    P.select_order = p->select_order;
-    P.nfeatures = p->nfeatures;
+    PlanBufs& pb = c->pb;
+    const char* why = "";
+    if (int rc = plan_geometry(P, pb, p, w, h, c->max_batch, c->fin_slack, &why)) return mo_fail(c, rc, why);
 
-    // per-level quotas (computeKeyPoints)
-    int nl = p->nlevels;
-    {
-        float factor = (float)(1.0 / (double)p->scale_factor);
-        float nd = p->nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nl));
-        int sum = 0;
-        for (int L = 0; L < nl - 1; L++) {
-            P.lv[L].quota = cv_round_f(nd);
-            sum += P.lv[L].quota;
-            nd *= factor;
-        }
-        P.lv[nl - 1].quota = std::max(p->nfeatures - sum, 0);
-    }
-    // umax of the radius-15 disc
-    {
-        int umax[MO_HALF_PATCH + 2];
-        int vmax = (int)std::floor(MO_HALF_PATCH * std::sqrt(2.f) / 2 + 1);
-        int vmin = (int)std::ceil(MO_HALF_PATCH * std::sqrt(2.f) / 2);
-        for (int v = 0; v <= vmax; ++v) umax[v] = cv_round_d(std::sqrt((double)MO_HALF_PATCH * MO_HALF_PATCH - v * v));
-        for (int v = MO_HALF_PATCH, v0 = 0; v >= vmin; --v) {
-            while (umax[v0] == umax[v0 + 1]) ++v0;
-            umax[v] = v0;
-            ++v0;
-        }
-        for (int v = 0; v <= MO_HALF_PATCH; v++) P.umax[v] = umax[v];
-    }
-    // Gaussian 7 taps, sigma 2, quantised to 8 fractional bits (sepFilter2D 8u path)
-    {
-        double k[7], sum = 0;
-        for (int i = 0; i < 7; i++) {
-            double x = 2.0 * i - 6.0;
-            k[i] = std::exp(x * x * (-0.125 / 4.0));
-            sum += k[i];
-        }
-        double mul1 = 1.0 / sum;
-        for (int i = 0; i < 7; i++) P.gk[i] = cv_round_f((float)(k[i] * mul1) * 256.f);
-    }
-
-    int et = p->edge_threshold;
-    int pyr_off = 0, blur_off = 0, strip_base = 0, cand_off = 0, fin_off = 0, scr_off = 0;
-    for (int L = 0; L < nl; L++) {
-        LevelInfo& v = P.lv[L];
-        v.scale = (float)std::pow((double)p->scale_factor, (double)L);
-        float inv_scale = 1.0f / v.scale;
-        v.w = cv_round_f((float)w * inv_scale);
-        v.h = cv_round_f((float)h * inv_scale);
-        if (v.w < 1 || v.h < 1) return mo_fail(c, MO_ERR_ARG, "pyramid level collapses to zero size; reduce nlevels");
-        if (L == 0) { v.pitch = w; v.off = 0; }
-        else {
-            v.pitch = align_up(v.w, 16);
-            v.off = pyr_off;
-            pyr_off += align_up(v.pitch * v.h, 256);
-        }
-        v.bpitch = align_up(v.w, 16);
-        v.boff = blur_off;
-        blur_off += align_up(v.bpitch * v.h, 256);
-        if (v.w <= 2 * et || v.h <= 2 * et) { v.bx0 = v.by0 = et; v.bw = v.bh = 0; }
-        else { v.bx0 = et; v.by0 = et; v.bw = v.w - 2 * et; v.bh = v.h - 2 * et; }
-        v.inv_bw = v.bw > 1 ? 0xFFFFFFFFu / (uint32_t)v.bw + 1u : 0u;
-        // (a context for one or two frames at a time: shorter strips, more workgroups - MO_STRIP_ROWS_LATENCY in common.h)
-        v.strip_rows = c->max_batch <= 2 ? MO_STRIP_ROWS_LATENCY : MO_STRIP_ROWS;
-        while (v.strip_rows > 1 && v.strip_rows * v.bw > 16384) v.strip_rows /= 2;
-        // (short strips only while the level stays below the selection kernel's strip limit; mo_create caps frames at 4095 px = 2017 two-row
-        //  strips, so this matters only if that cap is raised)
-        while (v.strip_rows < MO_STRIP_ROWS && v.bh > 0 && (v.bh + v.strip_rows - 1) / v.strip_rows > SEL_MAXSTRIPS && 2 * v.strip_rows * v.bw <= 16384)
-            v.strip_rows *= 2;
-        if (v.bw > 16384) return mo_fail(c, MO_ERR_UNSUPPORTED, "level too wide");
-        v.nstrips = v.bh > 0 ? (v.bh + v.strip_rows - 1) / v.strip_rows : 0;
-        v.strip_cap = ((v.strip_rows + 1) / 2) * ((v.bw + 1) / 2);
-        v.strip_base = strip_base;
-        strip_base += v.nstrips;
-        v.cand_off = cand_off;
-        v.cand_cap = v.nstrips * v.strip_cap;
-        cand_off += v.cand_cap;
-        v.fin_off = fin_off;
-        v.fin_cap = (int)std::max<long long>(1, std::min<long long>(v.cand_cap, (4ll * v.quota + 256) * c->fin_slack[L]));
-        fin_off += v.fin_cap;
-        v.scr_off = scr_off;
-        // u64 records B + u32 records A + u16 partner positions + u64 ballots, in u64 units
-        scr_off += v.cand_cap + (v.cand_cap + 1) / 2 + (v.cand_cap / 2 + 8) / 4 + 2 + v.cand_cap / 64 + 12;
-    }
-    P.pyr_stride = std::max(pyr_off, 256);
-    P.blur_stride = blur_off;
-    P.strips_per_frame = std::max(strip_base, 1);
-    P.cand_stride = std::max(cand_off, 1);
-    P.fin_stride = fin_off;
-    c->scratch_stride = (size_t)scr_off;
-
-    // resize tables
-    c->rb_margin = mo_blur_margin(P.edge_threshold);
-    c->rb_pyr_margin = mo_pyr_margin(P.edge_threshold);
-    c->rb_ok = nl >= 2;
-    for (int L = 1; L < nl; L++) {
-        std::vector<int> xo, xc, yo, yc;
-        mo_linear_coeffs(P.lv[L - 1].w, P.lv[L].w, xo, xc);
-        mo_linear_coeffs(P.lv[L - 1].h, P.lv[L].h, yo, yc);
-        const int dw = P.lv[L].w, dh = P.lv[L].h, wp = ((dw + 63) & ~63) + 64, hp = ((dh + 63) & ~63) + 64;  // + 64: the tiling may start at a margin
-        auto pack = [](const std::vector<int>& o, const std::vector<int>& c1, int srcsize, int padded) {
-            std::vector<uint32_t> t((size_t)padded);
-            for (int i = 0; i < padded; i++) {
-                const int j = std::min(i, (int)o.size() - 1), o1 = std::min(o[j] + 1, srcsize - 1);
-                t[i] = (uint32_t)o[j] | ((uint32_t)(o1 - o[j]) << 15) | ((uint32_t)c1[j] << 16);
-            }
-            return t;
-        };
-        const std::vector<uint32_t> xp = pack(xo, xc, P.lv[L - 1].w, wp), yp = pack(yo, yc, P.lv[L - 1].h, hp);
-        // k_resize2 takes the source bytes of 4 adjacent output columns from ONE 8-byte window: right neighbour of the last
-        // column - offset of the first <= 7.  Always true below a level ratio of 2; rounded level widths can put the ratio a
-        // little above it at scale_factor 2 (333 -> 166), and such a level keeps the gather kernel
-        bool window_ok = true;
-        for (int x = 0; x < dw && window_ok; x++) {
-            const int xl = std::min(x + 3, dw - 1);
-            window_ok = std::min(xo[xl] + 1, P.lv[L - 1].w - 1) - xo[x] <= 7;
-        }
-        c->pb.rtab[L].two_pass_ok = window_ok;
-        c->rb_ok = c->rb_ok && window_ok && orb_plan_resize_blur(P, L, xp, yp, c->rb_pyr_margin, c->rb_margin);
-        // one block per level: xpk [wp] | ypk [hp] | xofs [dw] | xc1 [dw] | yofs [dh] | yc1 [dh]
-        std::vector<uint32_t> all(xp);
-        all.insert(all.end(), yp.begin(), yp.end());
-        for (const std::vector<int>* v : {&xo, &xc, &yo, &yc}) all.insert(all.end(), v->begin(), v->end());
-        if (int rc = c->pb.rblock[L].upload(c, all)) return rc;
-        ResizeTab& t = c->pb.rtab[L];
-        t.xpk = c->pb.rblock[L]; t.ypk = t.xpk + wp;
-        t.xofs = (int*)t.ypk + hp; t.xc1 = t.xofs + dw; t.yofs = t.xc1 + dw; t.yc1 = t.yofs + dh;
+    // the tables: one block, one upload
+    std::vector<uint32_t> blk;
+    plan_build_tables(P, pb, blk);
+    int rc;
+    if ((rc = pb.d_tables.upload(c, blk))) return rc;
+    const int nl = P.nlevels;
+    pb.rb_margin = mo_blur_margin(P.edge_threshold);
+    pb.rb_pyr_margin = mo_pyr_margin(P.edge_threshold);
+    pb.rb_ok = nl >= 2;
+    for (int L = 1; L < nl && pb.rb_ok; L++) {
+        const PlanTables::Resize& t = pb.rs[L];
+        pb.rb_ok = t.two_pass_ok && orb_plan_resize_blur(P, L, &blk[t.xpk], t.ypk - t.xpk, &blk[t.ypk], t.xofs - t.ypk, pb.rb_pyr_margin, pb.rb_margin);
     }
 
     // work buffers for `batch` frames
     size_t B = (size_t)batch;
-    int rc;
-    if ((rc = c->pb.d_pyr.reserve_exact(c, B * P.pyr_stride)) || (rc = c->pb.d_blur.reserve_exact(c, B * P.blur_stride)) ||
-        (rc = c->pb.d_cand.reserve_exact(c, B * P.cand_stride)) || (rc = c->pb.d_strip_cnt.reserve_exact(c, B * P.strips_per_frame)) ||
-        (rc = c->pb.d_scratch.reserve_exact(c, B * c->scratch_stride)))
+    if ((rc = pb.d_pyr.reserve_exact(c, B * P.pyr_stride)) || (rc = pb.d_blur.reserve_exact(c, B * P.blur_stride)) ||
+        (rc = pb.d_cand.reserve_exact(c, B * P.cand_stride)) || (rc = pb.d_strip_cnt.reserve_exact(c, B * P.strips_per_frame)) ||
+        (rc = pb.d_scratch.reserve_exact(c, B * pb.scratch_stride)))
         return rc;
-    if (c->pb.d_fin.reserve_exact(c, B * P.fin_stride) != MO_OK)
+    if (pb.d_fin.reserve_exact(c, B * P.fin_stride) != MO_OK)
         return mo_fail(c, MO_ERR_HIP, "hipMalloc of the final-keypoint slots failed: " + std::to_string(B * P.fin_stride * sizeof(FinalKp)) +
                                           " bytes (" + std::to_string(batch) + " frames x " + std::to_string(P.fin_stride) + " slots; slots grow with response ties)");
-    if ((rc = c->pb.d_fin_cnt.reserve_exact(c, B * MO_MAX_LEVELS))) return rc;
+    if ((rc = pb.d_fin_cnt.reserve_exact(c, B * MO_MAX_LEVELS))) return rc;
+    // the describe kernels' list of left-over tiles (each sharing workgroup may leave an entry); every call's k_select clears the
+    // count again
+    if ((rc = pb.d_dtodo.reserve_exact(c, 1 + (size_t)pb.n_dtiles * B * DT_SPLIT_LATENCY))) return rc;
+    HIPCHK(c, hipMemsetAsync(pb.d_dtodo, 0, sizeof(int), c->stream));
     if ((rc = fs_build(c))) return rc;  // single-frame pyramid + blur kernel: tile boxes of this plan
-    c->pb.batch_alloc = batch;
+    pb.batch_alloc = batch;
     c->plan_params = *p;
     c->plan_valid = true;
     c->fin_slack_dirty = false;

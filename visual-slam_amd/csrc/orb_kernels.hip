@@ -513,14 +513,13 @@ static int resize_org(const LevelInfo& d, int margin) { return (d.w > 2 * margin
 
 // Plan time: does the blurring form of k_resize2 cover level L - 1's blur region [blur_margin, size - blur_margin) at this
 // geometry, with every window and partition inside RB_*?  Rows and columns are independent; this restates the kernel's prologue.
-bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp, const std::vector<uint32_t>& yp, int margin,
-                          int blur_margin) {
+bool orb_plan_resize_blur(const Plan& P, int L, const uint32_t* xp, size_t nx, const uint32_t* yp, size_t ny, int margin, int blur_margin) {
     const LevelInfo& s = P.lv[L - 1];
     const LevelInfo& d = P.lv[L];
     const int bm = blur_margin, org = resize_org(d, margin);
     if (bm < 0 || (bm & 3)) return false;
     const int gx = (d.w - 2 * org + RS_TW - 1) / RS_TW, gy = (d.h - 2 * org + RS_TH - 1) / RS_TH;
-    if (gx < 1 || gy < 1 || (size_t)(org + gx * RS_TW + 1) > xp.size() || (size_t)(org + gy * RS_TH + 1) > yp.size()) return false;
+    if (gx < 1 || gy < 1 || (size_t)(org + gx * RS_TW + 1) > nx || (size_t)(org + gy * RS_TH + 1) > ny) return false;
     for (int by = 0; by < gy; by++) {
         const int ty0 = org + by * RS_TH;
         const uint32_t ey1 = yp[ty0 + RS_TH - 1];
@@ -540,7 +539,7 @@ bool orb_plan_resize_blur(const Plan& P, int L, const std::vector<uint32_t>& xp,
     return true;
 }
 
-// blur_margin >= 0 (the batched extraction with descriptors): when the plan allows it (c->rb_ok, orb_plan_resize_blur at this
+// blur_margin >= 0 (the batched extraction with descriptors): when the plan allows it (c->pb.rb_ok, orb_plan_resize_blur at this
 // blur margin) and every level takes k_resize2, the launch of level L also writes the blurred level L - 1 and *blurred is set; the
 // caller then blurs only the last level (orb_launch_blur from nlevels - 1).
 int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin, bool* blurred) {
@@ -548,9 +547,9 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
     auto src_of = [&](int L) { return L == 1 ? d_gray : c->pb.d_pyr + P.lv[L - 1].off; };
     auto sfs_of = [&](int L) { return L == 1 ? (size_t)P.w * P.h : (size_t)P.pyr_stride; };
     auto al4_of = [&](int L) { return ((((size_t)src_of(L)) | sfs_of(L) | (size_t)P.lv[L - 1].pitch) & 3) == 0 && P.lv[L - 1].pitch >= 12; };
-    bool fuse = blur_margin >= 0 && nlevels == P.nlevels && nlevels >= 2 && c->rb_ok && c->rb_margin == blur_margin &&
-                c->rb_pyr_margin == margin;
-    for (int L = 1; L < nlevels && fuse; L++) fuse = al4_of(L) && c->pb.rtab[L].two_pass_ok;
+    bool fuse = blur_margin >= 0 && nlevels == P.nlevels && nlevels >= 2 && c->pb.rb_ok && c->pb.rb_margin == blur_margin &&
+                c->pb.rb_pyr_margin == margin;
+    for (int L = 1; L < nlevels && fuse; L++) fuse = al4_of(L) && c->pb.rs[L].two_pass_ok;
     if (blurred) *blurred = fuse;
     const uint32_t taps = (uint32_t)P.gk[0] | ((uint32_t)P.gk[1] << 8) | ((uint32_t)P.gk[2] << 16) | ((uint32_t)P.gk[3] << 24);
     for (int L = 1; L < nlevels; L++) {
@@ -558,7 +557,8 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
         const LevelInfo& d = P.lv[L];
         const uint8_t* src = src_of(L);
         size_t sfs = sfs_of(L);
-        const ResizeTab& t = c->pb.rtab[L];
+        const PlanTables::Resize& t = c->pb.rs[L];
+        const uint32_t* const tb = c->pb.d_tables;
         const int org = resize_org(d, margin);
         dim3 grid((d.w - 2 * org + RS_TW - 1) / RS_TW, (d.h - 2 * org + RS_TH - 1) / RS_TH, batch);
         const uint32_t per = grid.x * grid.y, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u, inv_gx = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
@@ -566,24 +566,22 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
         if (fuse) {
             const BlurOut bo{c->pb.d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, blur_margin, taps};
             hipLaunchKernelGGL(k_resize2<true>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
-                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, bo);
+                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, tb + t.xpk, tb + t.ypk, inv_per, inv_gx, org, bo);
         } else if (al4 && t.two_pass_ok)
             hipLaunchKernelGGL(k_resize2<false>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
-                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xpk, t.ypk, inv_per, inv_gx, org, BlurOut{});
+                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, tb + t.xpk, tb + t.ypk, inv_per, inv_gx, org, BlurOut{});
         else
             hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
-                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, t.xofs, t.xc1, t.yofs, t.yc1, inv_per, inv_gx, org);
+                               (size_t)P.pyr_stride, d.pitch, d.w, d.h, (const int*)tb + t.xofs, (const int*)tb + t.xc1, (const int*)tb + t.yofs, (const int*)tb + t.yc1, inv_per, inv_gx, org);
     }
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
 
 // ------------------------------------------------------------------ blur ----------------------------
-#define BT_W 64
+// (BT_W x BT_H output pixels per tile: plan_tables.h, where the tile tables are built)
 #define BT_QW (BT_W / 4)      // quads (4 adjacent outputs) per tile row
 #define BT_PP (256 / BT_QW)   // row pairs one pass of the workgroup covers
-#define BT_H 58   // output rows per tile: 58 + 6 halo rows = 32 row pairs, two passes of 16 (round 1: 26 rows; half the workgroups,
-                  // 10 % instead of 23 % halo rows)
 #define BT_PW (BT_W + 16)  // LDS pixel-tile pitch: 4 (aligned lead-in) + BT_W + 3 halo, rounded to a multiple of 16
 #define BT_ROWS (BT_H + 6)
 
@@ -669,31 +667,18 @@ __global__ __launch_bounds__(256) void k_blur(Plan P, const uint32_t* __restrict
 }
 
 // margin: the tiling covers [margin, w - margin) x [margin, h - margin) of every level.  The detector's keypoints lie at least
-// edge_threshold from the border and rBRIEF samples within 19 px of them, so the pipeline passes (edge_threshold - 19) & ~3
+// edge_threshold from the border and rBRIEF samples within 19 px of them, so the pipeline passes mo_blur_margin(edge_threshold)
 // (12 at the default 31: 255 instead of 286 tiles per 640x480 frame); compute() with caller keypoints and the level probes
 // pass 0 (a caller's keypoint on a coarse octave may sample anywhere).  Levels [first_level, nlevels) are blurred.
 int orb_launch_blur(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int first_level) {
     const Plan& P = c->plan;
     if (nlevels < 1 || nlevels > P.nlevels || first_level < 0 || first_level >= nlevels)
         return mo_fail(c, MO_ERR_ARG, "blur: level range outside the plan");
-    const int slot = margin > 0 ? 1 : 0;
-    if (slot && c->pb.tile_margin != margin) c->pb.d_tile_tab[1].reset();
-    if (!c->pb.d_tile_tab[slot]) {  // (re)built with the plan: free_plan_buffers drops it
-        std::vector<uint32_t> tab;
-        for (int L = 0; L < P.nlevels; L++) {
-            const int cw = std::max(P.lv[L].w - 2 * margin, 1), chh = std::max(P.lv[L].h - 2 * margin, 1);
-            const int tx = (cw + BT_W - 1) / BT_W, ty = (chh + BT_H - 1) / BT_H;
-            c->pb.tile_cum[slot][L] = (int)tab.size();
-            for (int y = 0; y < ty; y++)
-                for (int x = 0; x < tx; x++) tab.push_back((uint32_t)L | ((uint32_t)x << 8) | ((uint32_t)y << 20));
-        }
-        c->pb.tile_cum[slot][P.nlevels] = (int)tab.size();
-        if (int rc = c->pb.d_tile_tab[slot].upload(c, tab)) return rc;
-        if (slot) c->pb.tile_margin = margin;
-    }
+    const int slot = margin == 0 ? 0 : 1;  // the plan's two tile tables: whole levels, levels without the pipeline's margin
+    if (slot && margin != c->pb.rb_margin) return mo_fail(c, MO_ERR_ARG, "blur: a margin the plan has no tile table for");
     const int tile0 = c->pb.tile_cum[slot][first_level];
     const uint32_t per = (uint32_t)(c->pb.tile_cum[slot][nlevels] - tile0), inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
-    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->pb.d_tile_tab[slot], tile0, inv_per, margin, d_gray,
+    hipLaunchKernelGGL(k_blur, dim3(per, batch), dim3(256), 0, c->stream, P, c->pb.d_tables + c->pb.tile_tab[slot], tile0, inv_per, margin, d_gray,
                        c->pb.d_pyr, c->pb.d_blur);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
@@ -1012,20 +997,12 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     if (tid == 0) strip_cnt[(size_t)frame * P.strips_per_frame + lv.strip_base + strip] = min(total, lv.strip_cap);
 }
 
-template <int TW, int NT> static int launch_fast_tw(mo_ctx* c, const uint8_t* d_gray, int batch, size_t score_bytes, int max_rows,
-                                                    int strip0, int nstrips) {
+template <int TW, int NT> static int launch_fast_tw(mo_ctx* c, const uint8_t* d_gray, int batch, int strip0, int nstrips) {
     const Plan& P = c->plan;
-    size_t lds = score_bytes + (size_t)(max_rows + 8) * TW + 16;
-    if (lds > 128 * 1024) return mo_fail(c, MO_ERR_UNSUPPORTED, "level too wide for the FAST strip kernel");
+    const size_t score_bytes = c->pb.score_bytes, lds = score_bytes + (size_t)(c->pb.max_rows + 8) * TW + 16;  // (<= 128 KB: plan_geometry)
     if (int rc = mo_raise_dyn_lds(c, (const void*)k_fast<TW, NT>, 128 * 1024)) return rc;
-    if (!c->pb.d_strip_tab) {  // (re)built with the plan: free_plan_buffers drops it
-        std::vector<uint32_t> tab((size_t)P.strips_per_frame, 0xFFFFFF00u);  // (no level has that many strips: the kernel returns)
-        for (int L = 0; L < P.nlevels; L++)
-            for (int st = 0; st < P.lv[L].nstrips; st++) tab[(size_t)P.lv[L].strip_base + st] = (uint32_t)L | ((uint32_t)st << 8);
-        if (int rc = c->pb.d_strip_tab.upload(c, tab)) return rc;
-    }
     const uint32_t per = (uint32_t)nstrips, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u;
-    hipLaunchKernelGGL((k_fast<TW, NT>), dim3(nstrips, batch), dim3(NT), lds, c->stream, P, c->pb.d_strip_tab, inv_per, strip0, d_gray,
+    hipLaunchKernelGGL((k_fast<TW, NT>), dim3(nstrips, batch), dim3(NT), lds, c->stream, P, c->pb.d_tables + c->pb.strip_tab, inv_per, strip0, d_gray,
                        c->pb.d_pyr, c->pb.d_cand, c->pb.d_strip_cnt, (int)score_bytes);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
@@ -1039,22 +1016,15 @@ int orb_launch_fast(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo, i
     const int strip0 = P.lv[level_lo].strip_base;
     const int nstrips = (level_hi < P.nlevels ? P.lv[level_hi].strip_base : P.strips_per_frame) - strip0;
     if (nstrips < 1) return MO_OK;
-    size_t score_bytes = 0;
-    int tw_need = 0, max_rows = 1;
-    for (int L = 0; L < P.nlevels; L++) {
-        const LevelInfo& v = P.lv[L];
-        score_bytes = std::max(score_bytes, (((size_t)(v.strip_rows + 2) * (v.bw + 2) + 15) & ~(size_t)15));
-        tw_need = std::max(tw_need, (v.bw + 2 + 6 + 15 + 15) & ~15);
-        max_rows = std::max(max_rows, v.strip_rows);
-    }
-    if (P.strips_per_frame < 1) return MO_OK;
     // (the kernel is written for any MO_STRIP_ROWS / thread count; 16-row strips with 512-thread workgroups - half the workgroups,
     // 12 % instead of 25 % ring rows - measured 3 % SLOWER than 8 rows x 256 threads on MI355X: eight wavefronts per barrier)
-    if (tw_need <= 608) return launch_fast_tw<608, 256>(c, d_gray, batch, score_bytes, max_rows, strip0, nstrips);  // 640-wide frames: 8 workgroups per CU
-    if (tw_need <= 704) return launch_fast_tw<704, 256>(c, d_gray, batch, score_bytes, max_rows, strip0, nstrips);
-    if (tw_need <= 1344) return launch_fast_tw<1344, 256>(c, d_gray, batch, score_bytes, max_rows, strip0, nstrips);
-    if (tw_need <= 2112) return launch_fast_tw<2112, 256>(c, d_gray, batch, score_bytes, max_rows, strip0, nstrips);
-    return launch_fast_tw<4160, 256>(c, d_gray, batch, score_bytes, max_rows, strip0, nstrips);
+    switch (mo_fast_tw(c->pb.tw_need)) {
+    case 608: return launch_fast_tw<608, 256>(c, d_gray, batch, strip0, nstrips);
+    case 704: return launch_fast_tw<704, 256>(c, d_gray, batch, strip0, nstrips);
+    case 1344: return launch_fast_tw<1344, 256>(c, d_gray, batch, strip0, nstrips);
+    case 2112: return launch_fast_tw<2112, 256>(c, d_gray, batch, strip0, nstrips);
+    default: return launch_fast_tw<4160, 256>(c, d_gray, batch, strip0, nstrips);
+    }
 }
 
 // ------------------------------------------------------------------ select --------------------------
@@ -1225,7 +1195,7 @@ __global__ __launch_bounds__(NT) void k_select(Plan P, const uint8_t* __restrict
     __shared__ replay::WgScratch<NT> s_ws;
     __shared__ uint32_t s_hw[NT / HG][27];          // Harris windows, one per 8-lane group
     const int L = level0 + blockIdx.y, frame = blockIdx.x, tid = threadIdx.x;  // dispatch order: all frames of the finest level first
-    if (desc_todo && frame == 0 && blockIdx.y == 0 && tid == 0) desc_todo[0] = 0;  // k_describe_tiles' list of left-over tiles (this call's)
+    if (desc_todo && frame == 0 && blockIdx.y == 0 && tid == 0) desc_todo[0] = 0;  // k_describe_tiles' list of left-over tiles (this call's; the plan's d_dtodo, never null)
     const LevelInfo lv = P.lv[L];
     int* fin_cnt_out = &fin_cnt[(size_t)frame * MO_MAX_LEVELS + L];
     if (lv.nstrips == 0) {
@@ -1300,11 +1270,7 @@ int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo,
     const Plan& P = c->plan;
     level_lo = std::max(level_lo, 0); level_hi = std::min(level_hi, P.nlevels);
     if (level_lo >= level_hi) return MO_OK;
-    for (int L = 0; L < P.nlevels; L++)
-        if (P.lv[L].nstrips > SEL_MAXSTRIPS) return mo_fail(c, MO_ERR_UNSUPPORTED, "too many strips per level");
-    int max_strips = 1;
-    for (int L = 0; L < P.nlevels; L++) max_strips = std::max(max_strips, P.lv[L].nstrips);
-    const size_t pref_bytes = (((size_t)max_strips + 1) * sizeof(int) + 15) & ~(size_t)15;
+    const size_t pref_bytes = (((size_t)c->pb.max_strips + 1) * sizeof(int) + 15) & ~(size_t)15;
     const size_t attr_bytes = SEL_BUF_BYTES + ((((size_t)SEL_MAXSTRIPS + 1) * sizeof(int) + 15) & ~(size_t)15);
     int rc;  // (both forms at the first launch of either)
     if ((rc = mo_raise_dyn_lds(c, (const void*)k_select<SEL_THREADS>, (int)attr_bytes)) ||
@@ -1317,14 +1283,14 @@ int orb_launch_select(mo_ctx* c, const uint8_t* d_gray, int batch, int level_lo,
     // levels with a smaller window (8 - 24 KB, more workgroups per CU): 0.23 - 0.25 ms against 0.20 ms; selecting the finest level on the
     // auxiliary stream beside FAST of the others: no gain (the coarse levels alone take 0.19 ms: the kernel is bound by the sum of the
     // replays, not by the finest level).  One or two frames (the single-frame host calls): 16 wavefronts per workgroup.
-    // (c->pb.d_dtodo is null at the first selection under a plan: orb_launch_describe makes and clears the list, the kernel tests for null)
+    // (c->pb.d_dtodo: the describe kernels' list of left-over tiles, a work buffer of the plan; the kernel clears its count for this call)
     const dim3 grid(batch, level_hi - level_lo);
     if (batch <= 2)
         hipLaunchKernelGGL(k_select<SEL_THREADS_LATENCY>, grid, dim3(SEL_THREADS_LATENCY), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->pb.d_pyr, c->pb.d_cand,
-                           c->pb.d_strip_cnt, c->pb.d_scratch, c->scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
+                           c->pb.d_strip_cnt, c->pb.d_scratch, c->pb.scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
     else
         hipLaunchKernelGGL(k_select<SEL_THREADS>, grid, dim3(SEL_THREADS), SEL_BUF_BYTES + pref_bytes, c->stream, P, d_gray, c->pb.d_pyr, c->pb.d_cand,
-                           c->pb.d_strip_cnt, c->pb.d_scratch, c->scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
+                           c->pb.d_strip_cnt, c->pb.d_scratch, c->pb.scratch_stride, c->pb.d_fin, c->pb.d_fin_cnt, c->flags_cur, level_lo, SEL_BUF_BYTES, c->pb.d_dtodo);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -1463,10 +1429,7 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 //     from LDS for every keypoint, ~70 VGPRs
 //   * tile pitches of 25 / 27 dwords (odd): the 16 lanes of a group read 16 different rows conflict-free in the centroid phase
 // Results are those of that kernel bit for bit (same integer sums, same float expressions, same sample addresses).
-#ifndef DT_W
-#define DT_W 128   // measured on MI355X (profiles/r03_ab_describe.txt): 64 x 64 tiles of 128 threads 0.334 ms, 128 x 64 tiles of 256 threads 0.273 ms
-#endif
-#define DT_H 64
+// (DT_W x DT_H keypoint positions per tile and DT_SPLIT_LATENCY: plan_tables.h, where the tile table is built)
 #define DT_RAW_P ((DT_W + 30 + 7 + 7) & ~7)  // raw tile pitch: DT_W + 30 columns + <= 7 alignment lead-in, 8-byte pieces (104: 26 dwords, the 16
                                              // rows the lanes of a group read in the centroid phase fall into 16 different banks)
 #define DT_RAW_ROWS (DT_H + 30)
@@ -1474,9 +1437,6 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 #define DT_BLR_ROWS (DT_H + 38)
 #ifndef DT_NT
 #define DT_NT 256                    // 16 keypoint groups of 16 lanes
-#ifndef DT_SPLIT_LATENCY
-#define DT_SPLIT_LATENCY 4           // workgroups per tile in calls on one or two frames (a power of two)
-#endif
 #endif
 #ifdef DT_WAVES
 #define DT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(DT_WAVES, 8)))
@@ -1776,31 +1736,6 @@ __global__ __launch_bounds__(DT_NT) void k_describe_tiles_rare(Plan P, const uin
 
 int orb_launch_describe(mo_ctx* c, const uint8_t* d_gray, int batch, mo_keypoint* d_kps, uint8_t* d_desc, int cap, int* d_counts) {
     const Plan& P = c->plan;
-    if (!c->pb.d_dtile_tab) {  // (re)built with the plan: free_plan_buffers drops it
-        // tile table (level | tile column << 8 | tile row << 20, level-major) followed by the intensity-centroid weights
-        // [32 rows][8 weight + 8 mask dwords]
-        std::vector<uint32_t> tab;
-        for (int L = 0; L < P.nlevels; L++)
-            for (int y = 0; y < (P.lv[L].bh + DT_H - 1) / DT_H; y++)
-                for (int x = 0; x < (P.lv[L].bw + DT_W - 1) / DT_W; x++) tab.push_back((uint32_t)L | ((uint32_t)x << 8) | ((uint32_t)y << 20));
-        c->pb.n_dtiles = (int)tab.size();
-        while (tab.size() % 4) tab.push_back(0);  // the weight rows are read as uint4
-        c->pb.dtile_icw_off = (int)tab.size();
-        tab.resize(tab.size() + 512, 0u);
-        for (int r = 0; r < 31; r++) {
-            const int d = P.umax[r < 15 ? 15 - r : r - 15];
-            for (int c4 = 0; c4 < 8; c4++) {
-                uint32_t wv = 0, mv = 0;
-                for (int b = 0; b < 4; b++) {
-                    const int u = 4 * c4 - 15 + b;
-                    if (u >= -d && u <= d) { wv |= (uint32_t)(u + 16) << (8 * b); mv |= 1u << (8 * b); }
-                }
-                tab[c->pb.dtile_icw_off + r * 16 + c4] = wv;
-                tab[c->pb.dtile_icw_off + r * 16 + 8 + c4] = mv;
-            }
-        }
-        if (int rc = c->pb.d_dtile_tab.upload(c, tab)) return rc;
-    }
     if (c->pb.n_dtiles == 0) {  // no level has a border region: every frame has zero keypoints
         HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)batch * sizeof(int), c->stream));
         return MO_OK;
@@ -1810,23 +1745,20 @@ int orb_launch_describe(mo_ctx* c, const uint8_t* d_gray, int batch, mo_keypoint
     // loaded once per sharing workgroup, which costs nothing there (profiles/r04_ab_describe_split.txt)
     const dim3 grid(c->pb.n_dtiles, batch, batch <= 2 ? DT_SPLIT_LATENCY : 1);
     const uint32_t inv_per = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
-    // todo list of the tiles the one-pass kernel leaves to k_describe_tiles_rare: [0] count (cleared by k_select of the same call), then
-    // frame * tiles + tile entries; sized for every tile of the largest batch
-    if (!c->pb.d_dtodo) {  // made with the plan's first describe: n_dtiles and batch_alloc are the plan's
-        if (int rc = c->pb.d_dtodo.reserve_exact(c, 1 + (size_t)c->pb.n_dtiles * c->pb.batch_alloc * DT_SPLIT_LATENCY)) return rc;  // (each sharing workgroup may leave an entry)
-        HIPCHK(c, hipMemsetAsync(c->pb.d_dtodo, 0, sizeof(int), c->stream));
-    }
-    const uint32_t* icw = c->pb.d_dtile_tab + c->pb.dtile_icw_off;
+    // c->pb.d_dtodo: the tiles the one-pass kernel leaves to k_describe_tiles_rare, [0] count (cleared by k_select of the same call), then
+    // frame * tiles + tile entries; sized with the plan for every tile of its largest batch
+    const uint32_t* const dtile_tab = c->pb.d_tables + c->pb.dtile_tab;
+    const uint32_t* icw = c->pb.d_tables + c->pb.dtile_icw;
     const dim3 rare_grid(std::min(c->pb.n_dtiles * batch, 256));
     if (d_desc) {
-        hipLaunchKernelGGL(k_describe_tiles<true>, grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
+        hipLaunchKernelGGL(k_describe_tiles<true>, grid, dim3(DT_NT), 0, c->stream, P, dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
                            c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
-        hipLaunchKernelGGL(k_describe_tiles_rare<true>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
+        hipLaunchKernelGGL(k_describe_tiles_rare<true>, rare_grid, dim3(DT_NT), 0, c->stream, P, dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
                            c->pb.d_blur, c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
     } else {
-        hipLaunchKernelGGL(k_describe_tiles<false>, grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
+        hipLaunchKernelGGL(k_describe_tiles<false>, grid, dim3(DT_NT), 0, c->stream, P, dtile_tab, inv_per, d_gray, c->pb.d_pyr, c->pb.d_blur,
                            c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
-        hipLaunchKernelGGL(k_describe_tiles_rare<false>, rare_grid, dim3(DT_NT), 0, c->stream, P, c->pb.d_dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
+        hipLaunchKernelGGL(k_describe_tiles_rare<false>, rare_grid, dim3(DT_NT), 0, c->stream, P, dtile_tab, c->pb.n_dtiles, d_gray, c->pb.d_pyr,
                            c->pb.d_blur, c->pb.d_fin, c->pb.d_fin_cnt, d_kps, d_desc, cap, d_counts, c->flags_cur, icw, c->pb.d_dtodo);
     }
     HIPCHK(c, hipGetLastError());
