@@ -1,7 +1,8 @@
 // track_kernels.hip -- the two match filters of the reference's per-frame tracking step, fused behind the matcher
 // (reference src/orbslam2/tracker.py:214-254):
 //   matcher.py:109-142  filter_matches_by_geometric_distance(kp_prev, kp_cur, matches, 0.02, (h, w)):
-//                       keep  hypot(pt_cur - pt_prev) <= ((w + h) / 2) * 0.02          (Python floats = IEEE double)
+//                       keep  hypot(pt_cur - pt_prev) <= ((w + h) / 2) * 0.02          (Python floats = IEEE double; math.hypot is
+//                       the correctly rounded root of the exact sum of squares: ts_within_gate)
 //   matcher.py:144-169  filter_matches_by_distance(matches): stable sort by distance, keep distance < 2 * np.median
 // The survivors, IN THE REFERENCE'S ORDER (ascending distance, ties in query order), are what Tracker feeds to
 // cv2.findEssentialMat(..., RANSAC, 0.999, 1.0) and cv2.recoverPose (tracker.py:242-249): k_track_select writes that list
@@ -26,6 +27,48 @@ __device__ __forceinline__ void ts_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// a + b = s + e exactly (Knuth)
+__device__ __forceinline__ void ts_two_sum(double a, double b, double& s, double& e) {
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+
+// The displacement gate of matcher.py:139-140: hypot(dx, dy) <= max_disp on Python floats, i.e. the CORRECTLY ROUNDED root of the exact
+// dx^2 + dy^2 against the limit.  The root of the rounded sum is within 2 ulp of that, so it decides unless it lands within a few ulp
+// of the limit (disp_frac is the caller's double: the limit can be any of them).  There the exact sum - error-free products and sums -
+// is compared with the square of the midpoint m between the limit and the double above it:
+//   RN(sqrt(S)) <= max_disp  <=>  S < m^2, or S == m^2 and the tie rounds down to a max_disp with an even mantissa.
+// (-ffp-contract=off for this file: no product below is fused into the sum that follows it)
+__device__ __noinline__ bool ts_gate_at_the_edge(double dx, double dy, double max_disp) {
+    const double h = 0.5 * (nextafter(max_disp, (double)INFINITY) - max_disp);   // m = max_disp + h, m^2 = max_disp^2 + 2 max_disp h + h^2
+    double t[8];
+    t[0] = dx * dx; t[1] = fma(dx, dx, -t[0]);
+    t[2] = dy * dy; t[3] = fma(dy, dy, -t[2]);
+    t[4] = -(max_disp * max_disp); t[5] = -fma(max_disp, max_disp, t[4]);
+    t[6] = -2.0 * max_disp * h; t[7] = -(h * h);
+    // Shewchuk's grow-expansion: e[] stays a non-overlapping expansion of the exact running sum, smallest component first
+    double e[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        double q = t[k];
+#pragma unroll
+        for (int i = 0; i < k; i++) ts_two_sum(q, e[i], q, e[i]);
+        e[k] = q;
+    }
+    double top = 0.0;   // the sign of the sum is that of its largest non-zero component
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (e[k] != 0.0) top = e[k];
+    if (top != 0.0) return top < 0.0;
+    return (__double_as_longlong(max_disp) & 1ll) == 0;
+}
+
+__device__ __forceinline__ bool ts_within_gate(double dx, double dy, double max_disp) {
+    const double r = sqrt(dx * dx + dy * dy);
+    const bool edge = fabs(r - max_disp) <= max_disp * 0x1p-48 && max_disp > 0x1p-400 && max_disp < 0x1p400;  // (squares stay normal)
+    return edge ? ts_gate_at_the_edge(dx, dy, max_disp) : r <= max_disp;
 }
 
 __global__ __launch_bounds__(TS_BLOCK) void k_track_select(const mo_keypoint* __restrict__ kps, const int32_t* __restrict__ counts,
@@ -75,7 +118,7 @@ __global__ __launch_bounds__(TS_BLOCK) void k_track_select(const mo_keypoint* __
             if (ok[u]) {
                 const mo_keypoint* kb = k2 + max(j[u], 0);
                 const double dx = (double)kb->x - (double)x1[u], dy = (double)kb->y - (double)y1[u];
-                ok[u] = sqrt(dx * dx + dy * dy) <= max_disp;
+                ok[u] = ts_within_gate(dx, dy, max_disp);
                 d[u] = min(max(d[u], 0), 256);
             }
         }
