@@ -393,6 +393,7 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *                            floats as Python's repr of the double value, colours as stored.
  *   mo_format_floats         that float formatting alone, one value per line (no GPU).
  *   mo_map_fuse              duplicate map points merged, missing observations gained (the comment at its declaration below).
+ *   mo_map_grow              new map points for the last keyframe from its neighbour keyframes (the comment at its declaration below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
  *                            brute-force matching in place of the bag-of-words lookup); reads the map, never changes it.  The frame (by
  *                            token of a resident result slot, else the host arrays) is matched against every keyframe (query = the frame,
@@ -642,6 +643,85 @@ typedef struct {
     int64_t n_points, n_obs; /* after the call */
 } mo_map_fuse_out;
 int mo_map_fuse(mo_map*, const mo_map_fuse_params*, mo_map_fuse_out*);
+
+/* mo_map_grow: new map points for the last keyframe from its neighbour keyframes (ORB-SLAM2's LocalMapping::CreateNewMapPoints /
+ * ORBmatcher::SearchForTriangulation), on the map as it stands: every keypoint of the last keyframe that no map point observes is
+ * searched along its epipolar line among the unobserved keypoints of the neighbours, triangulated and gated.  Opt-in: no other call
+ * runs it.  poses = [n_kf][12], [R | t] row-major per keyframe POSITION, as mo_map_bundle_adjust takes them.  Everything is f64; every
+ * sum runs left to right as written; s(o) = scale_factor^o and s2(o) = (scale_factor * scale_factor)^o are repeated products from 1.0
+ * (negative octaves as 0; 1 / s2(o) is the information of mo_map_track).
+ *   observations  read like every other reader of the map (negative positions and rows count from the end; entries naming a position
+ *                 or row that does not exist are skipped).
+ *   target        the last keyframe position T = n_kf - 1; its image is the one the last mo_map_add_keyframe stored.
+ *   neighbours    the positions max(0, T - window) .. T - 1 (window 0: every earlier position).  Fewer than 2 keyframes: no work, every
+ *                 count is 0, not an error.
+ *   free row      a row of a keyframe that no map point validly observes (the complement of mo_map_relocalize's point_of).  Only free
+ *                 rows take part, on both sides.
+ *   camera        fx = K[0], fy = K[4], cx = K[2], cy = K[5]; of a keypoint xn = (x - cx) / fx, yn = (y - cy) / fy.
+ *   pair          target (R1, t1), neighbour k (R2, t2):
+ *                 R12[i][j] = R1[i][0] R2[j][0] + R1[i][1] R2[j][1] + R1[i][2] R2[j][2];
+ *                 t12[i] = t1[i] - (R12[i][0] t2[0] + R12[i][1] t2[1] + R12[i][2] t2[2]);
+ *                 E = [t12]x R12: E[0][j] = t12[1] R12[2][j] - t12[2] R12[1][j], E[1][j] = t12[2] R12[0][j] - t12[0] R12[2][j],
+ *                 E[2][j] = t12[0] R12[1][j] - t12[1] R12[0][j];
+ *                 G = E K^-1: G[i][0] = E[i][0] (1 / fx), G[i][1] = E[i][1] (1 / fy), G[i][2] = (E[i][2] - G[i][0] cx) - G[i][1] cy;
+ *                 F = K^-T G: F[0][j] = G[0][j] (1 / fx), F[1][j] = G[1][j] (1 / fy), F[2][j] = (G[2][j] - F[0][j] cx) - F[1][j] cy;
+ *                 C1[i] = -(R1[0][i] t1[0] + R1[1][i] t1[1] + R1[2][i] t1[2]) (C2 likewise);
+ *                 c2[i] = R2[i][0] C1[0] + R2[i][1] C1[1] + R2[i][2] C1[2] + t2[i]; the epipole ex = (fx c2[0]) / c2[2] + cx,
+ *                 ey = (fy c2[1]) / c2[2] + cy in plain IEEE arithmetic: a non-finite epipole excludes nothing.
+ *   search        free target row (x1, y1) against free neighbour row (x2, y2, o2): a = x1 F[0][0] + y1 F[1][0] + F[2][0], b and c
+ *                 likewise from columns 1 and 2; den = a a + b b; rejected when den == 0; rejected when
+ *                 (ex - x2)^2 + (ey - y2)^2 < epipole_r2 s(o2); num = a x2 + b y2 + c; passes when (num num) / den < epi_chi2 s2(o2).
+ *                 Among the passing rows best = the lowest Hamming distance, ties to the lower row; accepted when best <= max_dist.
+ *                 No ratio test (SearchForTriangulation has none) and no orientation histogram (left out).
+ *   claims        per (k, row2) the accepted target row with the lowest (dist, row1) wins; the others lose that neighbour.
+ *   base pair     of a target row with at least one won match: rays r1[i] = R1[0][i] xn1 + R1[1][i] yn1 + R1[2][i], r2 likewise;
+ *                 cosp = (r1 . r2) / (sqrt(r1 . r1) sqrt(r2 . r2)); a match is usable when 0 < cosp < cos_max; the base pair is the
+ *                 usable match with the lowest cosp, ties to the lower position.  No usable match: no point.
+ *   triangulation of the base pair: the rows xn T[2] - T[0] and yn T[2] - T[1] of the target, then of the neighbour (T = [R | t], four
+ *                 entries each), taken inhomogeneously: A the first three columns, a4 the fourth;
+ *                 N[i][j] = A[0][i] A[0][j] + A[1][i] A[1][j] + A[2][i] A[2][j] + A[3][i] A[3][j],
+ *                 g[i] = -(A[0][i] a4[0] + A[1][i] a4[1] + A[2][i] a4[2] + A[3][i] a4[3]); Cholesky N = L L^T:
+ *                 l00 = sqrt(N00), l10 = N10 / l00, l20 = N20 / l00, l11 = sqrt(N11 - l10 l10), l21 = (N21 - l20 l10) / l11,
+ *                 l22 = sqrt((N22 - l20 l20) - l21 l21); y0 = g0 / l00, y1 = (g1 - l10 y0) / l11, y2 = ((g2 - l20 y0) - l21 y1) / l22;
+ *                 X2 = y2 / l22, X1 = (y1 - l21 X2) / l11, X0 = ((y0 - l10 X1) - l20 X2) / l00.  A radicand that is not > 0: no point.
+ *   gates         on the base pair, in both views: Xc[i] = R[i][0] X0 + R[i][1] X1 + R[i][2] X2 + t[i]; depth Xc[2] > 0; u = (fx Xc[0]) /
+ *                 Xc[2] + cx, v likewise; information(octave) ((u - x)^2 + (v - y)^2) <= chi2; d1 = |X - C1| and d2 = |X - C2| (sqrt of
+ *                 the squares summed x, y, z) both > 0; with rd = d2 / d1 and ro = s(o1) / s(o2): rejected when rd ratio_factor < ro or
+ *                 rd > ro ratio_factor.  A failure means no point: there is no fallback to another pair.
+ *   further obs.  the row's other won matches become observations of the new point when depth > 0 and the reprojection gate hold in
+ *                 that neighbour; otherwise they are dropped.
+ *   writes        the new points are appended to the live copy of the store in order of target row: xyz = the f64 result rounded to
+ *                 f32; colour read as mo_map_add_keyframe's growth reads it, from the target's stored image ((0, 0, 255) without an
+ *                 image or outside it); id = its index at creation; descriptor reference = (target slot, row); observations written
+ *                 non-negative, the neighbours in ascending position, then the target.  The per-keyframe lists stay those of the last
+ *                 cull, as after mo_map_fuse.  Existing points keep their bytes.
+ * Everything is decided on the device (later kernels read the counts first): no host round trip inside the call, one synchronisation -
+ * the copy-out.  Integer atomics only: two calls on equal maps give the same bytes. */
+typedef struct {
+    int32_t window;          /* neighbour positions before the last (10); 0: all */
+    int32_t max_dist;        /* ORB-SLAM2's TH_LOW (50) */
+    double scale_factor;     /* of the pyramid (1.2) */
+    double epi_chi2;         /* gate on the squared epipolar distance over s2(octave) (3.84) */
+    double chi2;             /* gate on information * squared reprojection error (5.991) */
+    double cos_max;          /* parallax: the rays' cosine must be below it (0.9998) */
+    double ratio_factor;     /* scale consistency (1.5 * scale_factor) */
+    double epipole_r2;       /* squared radius of the zone round the epipole at octave 0 (100) */
+} mo_map_grow_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n_rows = keypoints of the last keyframe */
+    int32_t* point;          /* [n_rows] index of the map point each row created (-1: none) */
+    double* points;          /* [n_rows][3], the first n_new filled: the new points in f64, in order */
+    /* filled by the call */
+    int32_t n_neighbours;
+    int32_t n_free;          /* free target rows */
+    int32_t n_accepted;      /* (row1, k) with an accepted best row */
+    int32_t n_matches;       /* of them, those that won their claim */
+    int32_t n_new;           /* points created */
+    int32_t n_obs_new;       /* their observations */
+    int64_t n_epi;           /* (row1, k, row2) that passed the epipole and the epipolar gate */
+    int64_t n_points, n_obs; /* after the call */
+} mo_map_grow_out;
+int mo_map_grow(mo_map*, const double K[9], const double* poses, const mo_map_grow_params*, mo_map_grow_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

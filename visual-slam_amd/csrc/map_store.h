@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
+// of duplicate points), map_grow.hip (new points from neighbour keyframes) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
 // Private to the library.
 #pragma once
 #include <algorithm>
@@ -32,10 +32,12 @@ struct RelocBufs;   // mo_map_relocalize (map_reloc.hip)
 struct TrackBufs;   // mo_map_track (map_track.hip)
 struct BaBufs;      // mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
 struct FuseBufs;    // mo_map_fuse (map_fuse.hip)
+struct GrowBufs;    // mo_map_grow (map_grow.hip)
 void map_scratch_free(RelocBufs* b);
 void map_scratch_free(TrackBufs* b);
 void map_scratch_free(BaBufs* b);
 void map_scratch_free(FuseBufs* b);
+void map_scratch_free(GrowBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -71,8 +73,9 @@ struct mo_map {
     TrackBufs* tk = nullptr;
     BaBufs* ba = nullptr;
     FuseBufs* fu = nullptr;
+    GrowBufs* gr = nullptr;
     // (mo_map_destroy selects the device and drains the stream first)
-    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); }
+    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); }
 };
 
 // ---- the one reader of an observation -----------------------------------------------------------------------------------------------

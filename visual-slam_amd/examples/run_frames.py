@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize] [--track-map [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize] [--track-map [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -124,6 +124,9 @@ def main(argv=None):
                     "the map (add_keyframe(tracked=)), and local bundle adjustment (LocalMapper.bundle_adjust) runs after it")
     ap.add_argument("--fuse", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, duplicate map points "
                     "are merged and missing observations gained (LocalMapper.fuse_map_points), before the bundle adjustment of --local-ba")
+    ap.add_argument("--grow-neighbours", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, its "
+                    "keypoints without a map point are searched along their epipolar lines in the neighbour keyframes and triangulated "
+                    "(LocalMapper.create_new_map_points with its default window of 10 neighbours), before --fuse and the bundle adjustment of --local-ba")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
@@ -150,9 +153,12 @@ def main(argv=None):
         ap.error("--local-ba needs --map and --track-map")
     if args.fuse and not args.track_map:
         ap.error("--fuse needs --map and --track-map")
+    if args.grow_neighbours and not args.track_map:
+        ap.error("--grow-neighbours needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
     n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
+    n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
@@ -177,6 +183,14 @@ def main(argv=None):
         print("frame %d: fuse %d absorbed, %d gained (%d proposals of %d candidates), %d map points"
               % (idx, fi["n_absorbed"], fi["n_gained"], fi["n_proposals"], fi["n_cand"], fi["n_points"]))
 
+    def grow(idx):
+        gi = mapper.create_new_map_points()   # (its own window of 10 neighbours; --ba-window belongs to --local-ba and --fuse)
+        n_grow[0] += 1
+        n_grow[1] += gi["n_new"]
+        n_grow[2] += gi["n_obs_new"]
+        print("frame %d: grow %d new points with %d observations (%d matches of %d free rows, %d neighbours), %d map points"
+              % (idx, gi["n_new"], gi["n_obs_new"], gi["n_matches"], gi["n_free"], gi["n_neighbours"], gi["n_points"]))
+
     def track_map(frame, kps, desc, idx):
         """the frame against the device map from the predicted pose (ORB-SLAM2's TrackWithMotionModel + TrackLocalMap); on success its
         pose becomes the reference pose"""
@@ -193,6 +207,8 @@ def main(argv=None):
             if idx % args.keyframe_every == 0:
                 if args.local_ba:
                     mapper.add_keyframe(frame, kps, desc, T, tracked=(info["point"], info["inlier"]))
+                    if args.grow_neighbours:
+                        grow(idx)
                     if args.fuse:
                         fuse(idx)
                     ba_ok, ba = mapper.bundle_adjust(window=args.ba_window)
@@ -207,6 +223,8 @@ def main(argv=None):
                         recent[-1] = T
                 else:
                     mapper.add_keyframe(frame, kps, desc, T)
+                    if args.grow_neighbours:
+                        grow(idx)
                     if args.fuse:
                         fuse(idx)
         return ok
@@ -292,6 +310,8 @@ def main(argv=None):
         print("map statistics: %s" % mapper.get_map_statistics())
         if args.local_ba:
             print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
+        if args.grow_neighbours:
+            print("growth from neighbours: %d calls, %d points created with %d observations" % (n_grow[0], n_grow[1], n_grow[2]))
         if args.fuse:
             print("fusion: %d calls, %d points absorbed, %d observations gained" % (n_fuse[0], n_fuse[1], n_fuse[2]))
     return state, poses, n_map

@@ -80,6 +80,17 @@ class MapKfOut(C.Structure):
                 ("n_points", C.c_int64), ("n_obs", C.c_int64)]
 
 
+class MapGrowParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("max_dist", C.c_int32), ("scale_factor", C.c_double), ("epi_chi2", C.c_double), ("chi2", C.c_double),
+                ("cos_max", C.c_double), ("ratio_factor", C.c_double), ("epipole_r2", C.c_double)]
+
+
+class MapGrowOut(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("points", C.c_void_p), ("n_neighbours", C.c_int32), ("n_free", C.c_int32), ("n_accepted", C.c_int32),
+                ("n_matches", C.c_int32), ("n_new", C.c_int32), ("n_obs_new", C.c_int32), ("n_epi", C.c_int64), ("n_points", C.c_int64),
+                ("n_obs", C.c_int64)]
+
+
 class MapRelocParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("thr_px", C.c_double), ("min_inliers", C.c_int32), ("max_candidates", C.c_int32), ("n_hyp", C.c_int32),
                 ("seed", C.c_uint64)]
@@ -208,6 +219,7 @@ SIGNATURES = {
     "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),
     "mo_map_fuse": (_i, [_vp, _vp, _vp]),
+    "mo_map_grow": (_i, [_vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

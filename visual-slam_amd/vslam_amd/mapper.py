@@ -364,6 +364,50 @@ class LocalMapper:
                 g[a][b] = max(0, g[a][b] + d)
                 g[b][a] = max(0, g[b][a] + d)
 
+    # ---- new map points from neighbour keyframes ------------------------------------------------------------------------------------
+    def create_new_map_points(self, window=10, max_dist=50, scale_factor=1.2, epi_chi2=3.84, chi2=5.991, cos_max=0.9998, want_points=False,
+                              ratio_factor=None, epipole_r2=100.0):
+        """New map points for the last keyframe from its `window` neighbours (0: every earlier keyframe; ORB-SLAM2's CreateNewMapPoints /
+        SearchForTriangulation; mo_map_grow in include/vslam_amd.h states the rules): every keypoint of the last keyframe that no map
+        point observes is searched along its epipolar line among the unobserved keypoints of each neighbour (`epi_chi2`, `max_dist`),
+        triangulated from the match with the most parallax (`cos_max`) and kept when depth, reprojection error (`chi2`) and scale
+        consistency (ratio_factor, by default 1.5 * scale_factor) hold; its other matches become observations.  The poses are the
+        keyframes' kf["pose"].  The co-visibility graph gains 1 for every pair of keyframes in each new point's observations.
+        Returns info: n_neighbours, n_free, n_epi, n_accepted, n_matches, n_new, n_obs_new, n_points, n_obs, `point` (per keypoint of
+        the last keyframe the index of the map point it created, -1: none) and, with want_points, `points` [n_new][3] f64."""
+        n_kf = len(self.keyframes)
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        n_rows = self._rec_n[next(s for s, r in enumerate(self._records) if r is self.keyframes[-1])] if n_kf else 0
+        point = np.full(max(n_rows, 1), -1, np.int32)
+        pts = np.full((max(n_rows, 1), 3), np.nan, np.float64) if want_points else None
+        rf = 1.5 * float(scale_factor) if ratio_factor is None else float(ratio_factor)
+        prm = V.MapGrowParams(int(window), int(max_dist), float(scale_factor), float(epi_chi2), float(chi2), float(cos_max), rf, float(epipole_r2))
+        out = V.MapGrowOut(point.ctypes.data, pts.ctypes.data if want_points else None)
+        n0 = self._n_points   # (the map before the call: the new points are appended behind it)
+        self._check(self.lib.mo_map_grow(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+        info = {k: int(getattr(out, k)) for k in ("n_neighbours", "n_free", "n_epi", "n_accepted", "n_matches", "n_new", "n_obs_new", "n_points",
+                                                  "n_obs")}
+        info["point"] = point[:n_rows]
+        if want_points:
+            info["points"] = pts[:info["n_new"]]
+        if info["n_new"]:
+            a = self.arrays()
+            g = self.co_visibility_graph
+            for i in range(n0, self._n_points):   # (written non-negative, one entry per position)
+                pos = a["obs_kf"][a["obs_off"][i]:a["obs_off"][i + 1]].tolist()
+                for x in range(len(pos)):
+                    for y in range(x + 1, len(pos)):
+                        p, q = self.keyframes[pos[x]]["id"], self.keyframes[pos[y]]["id"]
+                        g[p][q] += 1
+                        g[q][p] += 1
+        return info
+
     def _cull_keyframes(self, kf_len, kf_red):
         """local_mapper.py:253-315 on the counts the device produced: list length and the listed ids whose first map point with
         that id has >= 3 observations in other keyframes"""
