@@ -723,6 +723,54 @@ typedef struct {
 } mo_map_grow_out;
 int mo_map_grow(mo_map*, const double K[9], const double* poses, const mo_map_grow_params*, mo_map_grow_out*);
 
+/* Covisibility on the device map, and the local keyframes ORB-SLAM2's Tracking::UpdateLocalKeyFrames picks from it; both read the map,
+ * neither changes it.  Opt-in: mo_map_track, mo_map_bundle_adjust, mo_map_fuse and mo_map_grow keep their recency windows.
+ *
+ * mo_map_covisibility: the matrix W [n_kf][n_kf] (int32, row-major, by keyframe POSITION) into `weights` (host, may be NULL: compute
+ * only) and the number of keyframes into *n_kf.  W stays resident on the device for the calls below.
+ *   observations  an observation counts when the one reader of the map (the cull's, mo_map_track's) accepts it: negative positions
+ *                 and rows count from the end; entries naming a position or row that does not exist name nothing.
+ *   W[p][q]       p != q: the number of map points with at least one valid observation at position p and at least one at q.
+ *   W[p][p]       the number of map points with a valid observation at p.
+ *   duplicates    a point observed twice in one keyframe counts once for that keyframe.
+ *   W is symmetric.  It is recomputed on every call: the map carries no version to cache against.  No map points: all zeros.  No
+ *   keyframes: *n_kf = 0, MO_OK, nothing is written to `weights`.
+ * Integer atomics only (sums commute): the same exact matrix on every run, whichever of the two accumulation paths (a copy per workgroup
+ * in LDS up to 128 keyframes, global atomics beyond) runs.
+ *
+ * mo_map_local_keyframes: W is computed first; the selection runs on the device from it.
+ *   votes         every seed entry (an index into the map points; < 0 or >= the number of points: skipped) votes once for each position
+ *                 its point validly observes (twice in one keyframe: one vote).  An index given twice votes twice.
+ *   K1            the positions with at least one vote.  ref = the position with the most votes, ties to the later position.  Nothing
+ *                 voted (n_seed = 0 included): K1 = {ref_pos} and ref = ref_pos; ref_pos = -1 names the last keyframe.
+ *   K2            for each p in K1 the n_best positions q != p with the largest W[p][q] among those with W[p][q] >= max(min_weight, 1),
+ *                 ties to the later position.
+ *   local         K1 and K2 together: local[k] = 1 for K1, 2 for K2 only, 0 otherwise.
+ *   errors        MO_ERR_ARG for NULL arguments, n_best < 0, n_seed < 0, n_seed > 0 with NULL seed_points, and - when the map has at
+ *                 least one keyframe - ref_pos outside -1 .. n_kf - 1.  No keyframes: MO_OK, every count 0, ref = -1.
+ *
+ * mo_map_track_covisible: mo_map_track with one difference: a point is in the local map when it has a valid observation at a local
+ * keyframe of mo_map_local_keyframes (K1 or K2).  prm->window is validated as mo_map_track validates it and not used.  The matrix, the
+ * selection and the tracking kernels run on the context stream behind each other; one synchronisation, the copy-out.  A selection that
+ * makes every keyframe local gives mo_map_track's bytes at window = 0. */
+typedef struct {
+    const int32_t* seed_points; /* host, map point indices; < 0 or >= n_pts: skipped */
+    int32_t n_seed;             /* 0: no seeds, K1 = {ref_pos} */
+    int32_t ref_pos;            /* used when no seed votes; -1: the last keyframe */
+    int32_t n_best;             /* neighbours taken per K1 keyframe, >= 0 (10) */
+    int32_t min_weight;         /* a neighbour needs W >= max(min_weight, 1) (15) */
+} mo_map_local_params;
+typedef struct {
+    /* caller-allocated, may be NULL */
+    uint8_t* local;             /* [n_kf] 1 = K1, 2 = K2 only, 0 = not local */
+    /* filled by the call */
+    int32_t n_k1, n_local_kf, ref; /* ref: the K1 position with the most votes */
+} mo_map_local_out;
+int mo_map_covisibility(mo_map*, int32_t* weights, int32_t* n_kf);
+int mo_map_local_keyframes(mo_map*, const mo_map_local_params*, mo_map_local_out*);
+int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
+                           const mo_map_local_params*, mo_map_local_out*, mo_map_track_out*);
+
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls
  * neither clears nor pollutes this status.  Synchronises the context stream, copies the flag word to flags[0] (flags may be NULL; [1..3] reserved, 0)

@@ -40,6 +40,8 @@ __device__ __forceinline__ double trk_scale(double sf, int o) {
 // k_trk_rep on the map in `src` (the position table uploaded by the caller): rep [point][32], oct [point] (TK_NOT_LOCAL outside the
 // local map of the positions >= lo_pos), *n_local += the local points (zeroed by the caller)
 int trk_launch_rep(mo_map* m, const MapPts& src, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local);
+// the same with the local map of a keyframe set: lmask [n_kf] on the device, non-zero at a local keyframe (map_covis.hip's selection)
+int trk_launch_rep_mask(mo_map* m, const MapPts& src, const uint8_t* lmask, uint8_t* rep, int32_t* oct, int32_t* n_local);
 // k_trk_grid, one block per grid: block b sorts the keypoints of keyframe slot (slots ? slots[b] : slot0) - kcnt[slot] rows at
 // kkps + slot * row - into cell [b][TK_CELLS + 1] and sorted [b][row]
 int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted);

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
 // Private to the library.
 #pragma once
 #include <algorithm>
@@ -33,11 +33,13 @@ struct TrackBufs;   // mo_map_track (map_track.hip)
 struct BaBufs;      // mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
 struct FuseBufs;    // mo_map_fuse (map_fuse.hip)
 struct GrowBufs;    // mo_map_grow (map_grow.hip)
+struct CovisBufs;   // mo_map_covisibility, mo_map_local_keyframes and mo_map_track_covisible (map_covis.hip)
 void map_scratch_free(RelocBufs* b);
 void map_scratch_free(TrackBufs* b);
 void map_scratch_free(BaBufs* b);
 void map_scratch_free(FuseBufs* b);
 void map_scratch_free(GrowBufs* b);
+void map_scratch_free(CovisBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -74,8 +76,9 @@ struct mo_map {
     BaBufs* ba = nullptr;
     FuseBufs* fu = nullptr;
     GrowBufs* gr = nullptr;
+    CovisBufs* cv = nullptr;
     // (mo_map_destroy selects the device and drains the stream first)
-    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); }
+    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); }
 };
 
 // ---- the one reader of an observation -----------------------------------------------------------------------------------------------
@@ -142,6 +145,18 @@ int upload_pos_slot(mo_map* m);
 // the device-wide exclusive scan of int32 (total into *d_total) and the growth of one copy of the map store
 int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total);
 int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
+
+// ---- map_covis.hip -----------------------------------------------------------------------------------------------------------------
+// The pieces of mo_map_local_keyframes, for a caller that runs them inside a chain of its own (mo_map_track_covisible): the argument
+// rules; the matrix W and the selection enqueued on the context stream (the position table uploaded and the stage set opened by the
+// caller, at least one keyframe; stage marks "covis" and "covis_select"); the copies of the result enqueued; after the caller's
+// synchronisation, the result read into *out.  covis_mask: [n_kf] on the device, non-zero at a local keyframe, valid behind the selection.
+int covis_check(mo_map* m, const mo_map_local_params* prm, const mo_map_local_out* out);
+int covis_enqueue(mo_map* m);
+int covis_select_enqueue(mo_map* m, const mo_map_local_params* prm);
+int covis_copy_enqueue(mo_map* m, mo_map_local_out* out);
+void covis_finish(mo_map* m, mo_map_local_out* out);
+const uint8_t* covis_mask(const mo_map* m);
 
 // A query frame staged in the spare keyframe slot (mo_map_track, mo_map_relocalize; read-only on the map): the frame looked up,
 // *from_token set, defaults(n) run (the caller's per-keypoint output defaults), then - unless there is nothing to search, which leaves

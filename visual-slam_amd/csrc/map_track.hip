@@ -5,6 +5,7 @@
 // Chain (one synchronisation, the copy-out; the retry and the early exits are flags in TrackRes that every later kernel reads first):
 //   k_trk_init      result block, per-keypoint keys and outputs
 //   k_trk_rep       one thread per point: local-map membership, representative descriptor ([point][32]) and its octave
+//                   (mo_map_track_covisible: k_covis and k_covis_select of map_covis.hip run in front of it and give it the local keyframes)
 //   k_trk_grid      one block: stable counting sort of the frame keypoints into 64 x 48 cells
 //   per pass, per attempt (the second attempt runs only after a pass with too few matches):
 //     k_trk_search  one thread per local point: projection, window over the cells, 256-bit Hamming distances, best / second, the
@@ -83,12 +84,14 @@ __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes*
     }
 }
 
-// one thread per point: its valid observations (map_obs); local when one of them is at a position >= lo_pos.  The
+// one thread per point: its valid observations (map_obs); local when one of them is at a local keyframe: a position >= lo_pos, or with
+// MASK a position whose byte of lmask is not zero.  The
 // representative is ComputeDistinctiveDescriptors' choice: the observation with the smallest median distance to all of them, ties to
 // the earlier.  Each median is found by bisection on the distance value (count of distances <= v), only below the best so far.
-__global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                                 int row, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc, int lo_pos,
-                                                 uint8_t* __restrict__ rep, int32_t* __restrict__ oct, int32_t* __restrict__ n_local) {
+template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
+                                                                      const int32_t* __restrict__ kcnt, int row, const mo_keypoint* __restrict__ kkps,
+                                                                      const uint8_t* __restrict__ kdesc, int lo_pos, const uint8_t* __restrict__ lmask,
+                                                                      uint8_t* __restrict__ rep, int32_t* __restrict__ oct, int32_t* __restrict__ n_local) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool local = false;
     if (i < n_pts) {
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const in
             const long long e = entry(o, &pos);
             if (e < 0) continue;
             nv++;
-            local |= pos >= lo_pos;
+            local |= MASK ? lmask[pos] != 0 : pos >= lo_pos;
             if (best < 0) best = e;
         }
         if (local && nv > 2) {   // (n <= 2: every median is the distance to itself, 0: the first observation)
@@ -378,8 +381,16 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
 
 int trk_launch_rep(mo_map* m, const MapPts& src, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local) {
     mo_ctx* c = m->c;
-    hipLaunchKernelGGL(k_trk_rep, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
-                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, lo_pos, rep, oct, n_local);
+    hipLaunchKernelGGL(k_trk_rep<false>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
+                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, lo_pos, nullptr, rep, oct, n_local);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
+int trk_launch_rep_mask(mo_map* m, const MapPts& src, const uint8_t* lmask, uint8_t* rep, int32_t* oct, int32_t* n_local) {
+    mo_ctx* c = m->c;
+    hipLaunchKernelGGL(k_trk_rep<true>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
+                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, 0, lmask, rep, oct, n_local);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -391,9 +402,9 @@ int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int
     return MO_OK;
 }
 
-extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
-                            mo_map_track_out* out) {
-    if (!m) return MO_ERR_ARG;
+// mo_map_track (lprm NULL: the local map of the window) and mo_map_track_covisible (the local map of the local keyframes)
+static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
+                     const mo_map_local_params* lprm, mo_map_local_out* lout, mo_map_track_out* out) {
     mo_ctx* c = m->c;
     if (!f || !K || !pose0 || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (prm->n_pass < 1 || prm->n_pass > TK_MAX_PASS) return mo_fail(c, MO_ERR_ARG, "n_pass must be in 1 .. 4");
@@ -421,7 +432,8 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
         if (out->dist) for (int i = 0; i < nq; i++) out->dist[i] = -1;
         if (out->inlier) std::memset(out->inlier, 0, (size_t)nq);
     };
-    if ((rc = map_stage_frame(m, f, true, &out->from_token, defaults, &n, &fk, &fdesc)) || !fk) return rc;   // (nothing to search: not tracked, not an error)
+    if ((rc = map_stage_frame(m, f, true, &out->from_token, defaults, &n, &fk, &fdesc))) return rc;
+    if (!fk) return lprm ? mo_map_local_keyframes(m, lprm, lout) : MO_OK;   // (nothing to search: not tracked, not an error)
     const int n_kf = (int)m->pos_slot.size(), row = m->row;
     if (!m->tk) m->tk = new TrackBufs();
     TrackBufs& b = *m->tk;
@@ -441,7 +453,9 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
     const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
     hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
-    if ((rc = trk_launch_rep(m, src, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
+    if (lprm && ((rc = covis_enqueue(m)) || (rc = covis_select_enqueue(m, lprm)))) return rc;
+    if ((rc = lprm ? trk_launch_rep_mask(m, src, covis_mask(m), b.rep, b.oct, &b.res.p->n_local)
+                   : trk_launch_rep(m, src, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
         (rc = trk_launch_grid(m, nullptr, m->kslots, 1, prm->w, prm->h, b.cell, b.sorted)))   // (the staged frame: the spare slot)
         return rc;
     mo_stage_mark(c, "track_prep");
@@ -462,9 +476,11 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
     if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->dist) HIPCHK(c, hipMemcpyAsync(out->dist, b.qdist, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (lprm && (rc = covis_copy_enqueue(m, lout))) return rc;
     clk.enqueued();
     HIPCHK(c, hipStreamSynchronize(c->stream));
     clk.waited();
+    if (lprm) covis_finish(m, lout);
     const TrackRes& r = *b.h_res;
     for (int i = 0; i < 12; i++) out->pose[i] = r.pose[i];
     for (int k = 0; k < TK_MAX_PASS; k++) {
@@ -476,4 +492,19 @@ extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9],
     out->n_local = r.n_local;
     out->ok = r.n_done == prm->n_pass && r.pass_inliers[prm->n_pass - 1] >= prm->min_inliers;
     return MO_OK;
+}
+
+extern "C" int mo_map_track(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
+                            mo_map_track_out* out) {
+    if (!m) return MO_ERR_ARG;
+    return track_run(m, f, K, pose0, prm, nullptr, nullptr, out);
+}
+
+extern "C" int mo_map_track_covisible(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
+                                      const mo_map_local_params* lprm, mo_map_local_out* lout, mo_map_track_out* out) {
+    if (!m) return MO_ERR_ARG;
+    int rc;
+    if ((rc = covis_check(m, lprm, lout))) return rc;
+    lout->n_k1 = 0; lout->n_local_kf = 0; lout->ref = -1;
+    return track_run(m, f, K, pose0, prm, lprm, lout, out);
 }

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize] [--track-map [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -120,6 +120,9 @@ def main(argv=None):
                     "device map (LocalMapper.relocalize) and go on tracking from it")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
+    ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
+                    "see (track_local_map(local=\"covisible\"): the keyframes observing the points the previous frame matched, and their best "
+                    "covisible neighbours) instead of what the last 10 keyframes see")
     ap.add_argument("--local-ba", action="store_true", help="with --map --track-map: a tracked frame that becomes a keyframe hands its matches to "
                     "the map (add_keyframe(tracked=)), and local bundle adjustment (LocalMapper.bundle_adjust) runs after it")
     ap.add_argument("--fuse", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, duplicate map points "
@@ -149,6 +152,8 @@ def main(argv=None):
         ap.error("--relocalize needs --map")
     if args.track_map and not args.map:
         ap.error("--track-map needs --map")
+    if args.covisible and not args.track_map:
+        ap.error("--covisible needs --map and --track-map")
     if args.local_ba and not args.track_map:
         ap.error("--local-ba needs --map and --track-map")
     if args.fuse and not args.track_map:
@@ -160,6 +165,7 @@ def main(argv=None):
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
+    seeds = [None]   # --covisible: the previous frame's matched map points (indices into the map as it stands: dropped when the map changes)
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
         mapper = LocalMapper(K, args.map)
@@ -196,7 +202,11 @@ def main(argv=None):
         pose becomes the reference pose"""
         nonlocal ref_pose
         pred = predict_pose(recent[-2], recent[-1]) if len(recent) >= 2 else ref_pose
-        ok, T, info = mapper.track_local_map(kps, desc, pred)
+        if args.covisible:
+            ok, T, info = mapper.track_local_map(kps, desc, pred, local="covisible", seed_points=seeds[0])
+            seeds[0] = info["point"] if ok else None
+        else:
+            ok, T, info = mapper.track_local_map(kps, desc, pred)
         if idx % 5 == 0:
             print("frame %d: track map %s, %d matches, %d inliers, t = %s" % (idx, "ok" if ok else "failed", info["pass_matches"][-1] if
                   info["n_pass_run"] else 0, info["pass_inliers"][-1] if info["n_pass_run"] else 0, np.round(T[:3, 3], 3)))
@@ -205,6 +215,7 @@ def main(argv=None):
             recent[:] = recent[-1:] + [T]
             poses.append((T[:3, :3], T[:3, 3:4]))
             if idx % args.keyframe_every == 0:
+                seeds[0] = None   # (the cull and the fusion below renumber the map points)
                 if args.local_ba:
                     mapper.add_keyframe(frame, kps, desc, T, tracked=(info["point"], info["inlier"]))
                     if args.grow_neighbours:

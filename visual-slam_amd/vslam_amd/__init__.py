@@ -135,6 +135,14 @@ class MapFuseOut(C.Structure):
                 ("n_points", C.c_int64), ("n_obs", C.c_int64)]
 
 
+class MapLocalParams(C.Structure):
+    _fields_ = [("seed_points", C.c_void_p), ("n_seed", C.c_int32), ("ref_pos", C.c_int32), ("n_best", C.c_int32), ("min_weight", C.c_int32)]
+
+
+class MapLocalOut(C.Structure):
+    _fields_ = [("local", C.c_void_p), ("n_k1", C.c_int32), ("n_local_kf", C.c_int32), ("ref", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -220,6 +228,9 @@ SIGNATURES = {
     "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),
     "mo_map_fuse": (_i, [_vp, _vp, _vp]),
     "mo_map_grow": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_covisibility": (_i, [_vp, _vp, _vp]),
+    "mo_map_local_keyframes": (_i, [_vp, _vp, _vp]),
+    "mo_map_track_covisible": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -519,7 +519,7 @@ class LocalMapper:
 
     # ---- tracking against the map -------------------------------------------------------------------------------------------------
     def track_local_map(self, keypoints, descriptors, pose, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8,
-                        chi2=5.991, min_matches=20, min_inliers=30, image_size=None):
+                        chi2=5.991, min_matches=20, min_inliers=30, image_size=None, local="window", seed_points=None, n_best=10, min_weight=15):
         """The pose of a tracked frame in the map's frame and scale, from a predicted pose (ORB-SLAM2's TrackLocalMap: search by projection
         of the local map, then pose-only optimisation; mo_map_track in include/vslam_amd.h states the rules).  The map is not changed.
         pose: the predicted 4x4 (X_cam = R X + t; predict_pose gives the constant-velocity one).  window: keyframe positions of the
@@ -528,7 +528,13 @@ class LocalMapper:
         Returns (ok, pose, info): pose 4x4 of the last pass that finished (the given pose when none did); info holds per keypoint
         `point` (map point index, -1: none), `dist` (Hamming distance, -1: none) and `inlier` of the last pass searched, per pass
         `pass_pose`, `pass_radius`, `pass_cand`, `pass_matches`, `pass_inliers` (lists over the passes that ran), `n_local` and
-        `from_token`."""
+        `from_token`.
+        local: "window" - the local map is what the last `window` keyframes see; "covisible" - what the local keyframes of
+        local_keyframes(seed_points, None, n_best, min_weight) see (mo_map_track_covisible; `window` is not used): seed_points is the
+        `point` array a previous track_local_map on this map returned (-1 entries are skipped; None: the last keyframe and its
+        neighbours).  info then also holds `local_keyframes` (positions) and `ref_keyframe`."""
+        if local not in ("window", "covisible"):
+            raise ValueError("local: \"window\" or \"covisible\"")
         radii = [float(r) for r in radii]
         if not 1 <= len(radii) <= 4:
             raise ValueError("radii: one to four passes")
@@ -547,7 +553,12 @@ class LocalMapper:
         prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
                                float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
         out = V.MapTrackOut(point.ctypes.data, dist.ctypes.data, inlier.ctypes.data)
-        self._check(self.lib.mo_map_track(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(out)))
+        if local == "covisible":
+            lprm, lout, mask, _seeds = self._local_args(seed_points, None, n_best, min_weight)
+            self._check(self.lib.mo_map_track_covisible(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(lprm), C.byref(lout),
+                                                        C.byref(out)))
+        else:
+            self._check(self.lib.mo_map_track(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(out)))
         T = np.eye(4)
         T[:3, :] = np.array(out.pose).reshape(3, 4)
         nr = int(out.n_pass_run)
@@ -556,7 +567,42 @@ class LocalMapper:
                 "pass_radius": [float(out.pass_radius[k]) for k in range(nr)], "pass_cand": [int(out.pass_cand[k]) for k in range(nr)],
                 "pass_matches": [int(out.pass_matches[k]) for k in range(nr)], "pass_inliers": [int(out.pass_inliers[k]) for k in range(nr)],
                 "n_pass_run": nr, "n_local": int(out.n_local), "from_token": bool(out.from_token)}
+        if local == "covisible":
+            info["local_keyframes"] = np.flatnonzero(mask[:len(self.keyframes)]).tolist()
+            info["ref_keyframe"] = int(lout.ref)
         return bool(out.ok), T, info
+
+    # ---- covisibility ---------------------------------------------------------------------------------------------------------------
+    def covisibility(self):
+        """W (n_kf, n_kf) int32 by keyframe position, computed on the device from the map as it stands (mo_map_covisibility in
+        include/vslam_amd.h states the rules): W[p][q] = the map points with a valid observation at both positions, W[p][p] = those
+        with one at p.  The true shared-point counts: co_visibility_graph keeps the reference's increments instead."""
+        n = len(self.keyframes)
+        W = np.zeros((n, n), np.int32)
+        n_kf = C.c_int32(0)
+        self._check(self.lib.mo_map_covisibility(self._h, V._ptr(W) if n else None, C.byref(n_kf)))
+        assert n_kf.value == n
+        return W
+
+    def _local_args(self, seed_points, ref, n_best, min_weight):
+        seeds = None if seed_points is None else np.ascontiguousarray(np.asarray(seed_points).reshape(-1), np.int32)
+        mask = np.zeros(max(len(self.keyframes), 1), np.uint8)
+        prm = V.MapLocalParams(seeds.ctypes.data if seeds is not None and len(seeds) else None, 0 if seeds is None else len(seeds),
+                               -1 if ref is None else int(ref), int(n_best), int(min_weight))
+        return prm, V.MapLocalOut(mask.ctypes.data), mask, seeds
+
+    def local_keyframes(self, seed_points=None, ref=None, n_best=10, min_weight=15):
+        """The local keyframes of ORB-SLAM2's UpdateLocalKeyFrames on the device covisibility matrix (mo_map_local_keyframes states the
+        rules): K1 = the positions observing the map points in seed_points (indices; -1 and out-of-range entries are skipped), or
+        {ref} (None: the last keyframe) when nothing votes; K2 = per K1 keyframe its n_best neighbours by shared points, each with at
+        least max(min_weight, 1).  Returns {"local", "k1", "k2", "ref"}: position lists (k2: those not in k1) and the K1 position with
+        the most votes."""
+        prm, out, mask, _seeds = self._local_args(seed_points, ref, n_best, min_weight)
+        self._check(self.lib.mo_map_local_keyframes(self._h, C.byref(prm), C.byref(out)))
+        mask = mask[:len(self.keyframes)]
+        assert int(out.n_k1) == int((mask == 1).sum()) and int(out.n_local_kf) == int((mask != 0).sum())
+        return {"local": np.flatnonzero(mask).tolist(), "k1": np.flatnonzero(mask == 1).tolist(), "k2": np.flatnonzero(mask == 2).tolist(),
+                "ref": int(out.ref)}
 
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
     def _sync_size(self):
