@@ -394,6 +394,8 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *   mo_format_floats         that float formatting alone, one value per line (no GPU).
  *   mo_map_fuse              duplicate map points merged, missing observations gained (the comment at its declaration below).
  *   mo_map_grow              new map points for the last keyframe from its neighbour keyframes (the comment at its declaration below).
+ *   mo_map_query_keyframes, mo_map_relocalize_pre   place recognition over a binary vocabulary and relocalization against the keyframes
+ *                            it selects (the comment above mo_vocab_train below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
  *                            brute-force matching in place of the bag-of-words lookup); reads the map, never changes it.  The frame (by
  *                            token of a resident result slot, else the host arrays) is matched against every keyframe (query = the frame,
@@ -770,6 +772,75 @@ int mo_map_covisibility(mo_map*, int32_t* weights, int32_t* n_kf);
 int mo_map_local_keyframes(mo_map*, const mo_map_local_params*, mo_map_local_out*);
 int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
                            const mo_map_local_params*, mo_map_local_out*, mo_map_track_out*);
+
+/* ---- Place recognition: a binary vocabulary, the keyframe database of a map, relocalization with preselection (bow.hip) ----------------
+ * "Which keyframes look like this frame": DBoW2's L1 score of tf-idf vectors over a flat vocabulary of binary words.  Everything is
+ * integer work except the logarithm of the weights (host, once per training) and the one division of the score; tests/bow_restatement.py
+ * restates every rule below in numpy and the device results equal it bit for bit.
+ *   vocabulary    W words of 32 bytes and one int32 weight per word, 2 <= W <= MO_BOW_MAX_WORDS (8192).  The limit: the score kernel
+ *                 keeps q_w of every word in LDS as one int32, 32 KB at 8192 words, so five workgroups still share a CU's 160 KB; the
+ *                 histogram kernel's counters take the same.  Any W in range, not only multiples of 64.  0 <= weight <= 14 * 1024.
+ *   quantisation  the word of a descriptor is the word with the lowest Hamming distance, ties to the lower word index (the matcher's
+ *                 best neighbour with the words as train rows).
+ *   training      mo_vocab_train: desc = host descriptors [n][32], img_off [n_img + 1] = the image (keyframe) boundaries as in obs_off
+ *                 (img_off[0] = 0, img_off[n_img] = n, not decreasing).  MO_ERR_ARG unless n >= W, 1 <= n_img <= 2^20, iters >= 0.
+ *                 Initial word j = training row floor(j * n / W) (int64).  An iteration quantises every row, then sets bit b of a word
+ *                 to 1 iff 2 * (members with bit b set) > members; a word without members keeps its bits.  Training stops after `iters`
+ *                 iterations or after the first one that changes no word (*iters_run = iterations run).  Duplicate words are allowed:
+ *                 the higher index then has no members and stays.  n_w = the images with at least one row quantised to word w under
+ *                 the final words (integers, on the device); weight_w = rint(log(n_img / max(n_w, 1)) * 1024) in f64 on the host
+ *                 (n_img <= 2^20 keeps it <= 14 * 1024).  One synchronisation per iteration: training is offline.
+ *   mo_vocab_create     a vocabulary from host arrays (words [W][32], weights [W]): a trained one survives the process as those two arrays.
+ *   mo_vocab_download   the two arrays back (either may be NULL); mo_vocab_words: W.  mo_vocab_destroy: detach it from every map first.
+ *   database      mo_map_set_vocabulary attaches a vocabulary to a map (NULL detaches; the map does not own it).  The database is dense:
+ *                 one row of W term counts per keyframe slot and one for the spare slot a query frame is staged in.  A count is a
+ *                 uint16: a count cannot exceed the rows of its frame, so frames and keyframes of up to MO_BOW_MAX_ROWS (65535) rows
+ *                 never wrap one; a query on a frame, or with a keyframe not yet counted, of more rows returns MO_ERR_UNSUPPORTED.
+ *                 Rows are made lazily: the keyframe store bumps a per-slot serial whenever mo_map_add_keyframe stores rows in a slot,
+ *                 the database remembers the serial it counted, and a query first brings every stale slot up to date in one quantise
+ *                 launch (one pair per stale keyframe, one for the frame) and one histogram launch.  Keyframes stored before the
+ *                 vocabulary was attached, slots stored after mo_map_remove_keyframes and a store restrided between two queries are
+ *                 all covered by that rule: rows are kept by slot, not by position, and do not depend on the store's row stride.
+ *   query         mo_map_query_keyframes: the frame is given and staged like mo_map_track's; one chain, one synchronisation; reads the
+ *                 map, never changes it.  With count_w the frame's term counts: q_w = count_w * weight_w, |q| = sum_w q_w (int64; k_w
+ *                 and |k| likewise for keyframe k).  D_k = sum_w |q_w * |k| - k_w * |q||, int64: counts of a frame sum to <= 65535 and
+ *                 weights are <= 14336, so |q|, |k| < 2^30, every term < 2^60 and D_k <= 2 |q| |k| < 2^61.
+ *                 score_k = 1.0 - 0.5 * (double)D_k / ((double)|q| * (double)|k|), exactly those f64 operations; 0 when either norm is 0.
+ *                 (DBoW2's L1 score of the L1-normalised vectors, 1 - 0.5 * sum |q/|q| - k/|k||, the weights fixed in the vocabulary.)
+ *                 Result: the keyframe positions with score > 0, highest first, ties to the lower position, at most n_best; pos = -1
+ *                 and score = 0 past n.  An empty frame, a map without keyframes and n_best = 0 give n = 0 and are not errors;
+ *                 MO_ERR_ARG without a vocabulary.  Stage marks bow_quantise, bow_hist, bow_score, bow_rank (mo_stage_times).
+ *   mo_map_relocalize_pre   mo_map_relocalize with one difference: when n_pre < the number of keyframes, the frame is matched only
+ *                 against the keyframes the query above ranks in its first n_pre places (those with score > 0: fewer than n_pre when
+ *                 fewer score above 0, none when none does); |C_k| = 0 for every other keyframe.  The selection stays on the device: the
+ *                 rank kernel writes the matcher's pair list, and there is still one synchronisation.  When n_pre >= the number of
+ *                 keyframes every keyframe is matched and the result is mo_map_relocalize's, byte for byte.  Everything after the
+ *                 matching is mo_map_relocalize's own body.  MO_ERR_ARG for n_pre < 1 or without a vocabulary. */
+#define MO_BOW_MAX_WORDS 8192
+#define MO_BOW_MAX_WEIGHT (14 * 1024)
+#define MO_BOW_MAX_ROWS 65535
+#define MO_BOW_MAX_IMAGES (1 << 20)
+typedef struct mo_vocab mo_vocab;
+typedef struct {
+    int32_t n_best;          /* places asked for, >= 0 (10) */
+} mo_map_query_params;
+typedef struct {
+    /* caller-allocated */
+    int32_t* pos;            /* [n_best] keyframe positions in rank order (-1 past n) */
+    double* score;           /* [n_best] their scores (0 past n) */
+    /* filled by the call */
+    int32_t n;               /* places filled */
+    int32_t from_token;      /* 1: the frame was read from its resident slot */
+} mo_map_query_out;
+int mo_vocab_train(mo_ctx*, const uint8_t* desc, int32_t n, const int32_t* img_off, int32_t n_img, int32_t n_words, int32_t iters, mo_vocab** out,
+                   int32_t* iters_run);
+int mo_vocab_create(mo_ctx*, const uint8_t* words, const int32_t* weights, int32_t n_words, mo_vocab** out);
+int mo_vocab_words(const mo_vocab*);
+int mo_vocab_download(const mo_vocab*, uint8_t* words, int32_t* weights);
+void mo_vocab_destroy(mo_vocab*);
+int mo_map_set_vocabulary(mo_map*, mo_vocab*);
+int mo_map_query_keyframes(mo_map*, const mo_frame_ref* f, const mo_map_query_params*, mo_map_query_out*);
+int mo_map_relocalize_pre(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, int32_t n_pre, mo_map_reloc_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

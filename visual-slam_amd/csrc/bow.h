@@ -1,0 +1,35 @@
+// bow.h -- place recognition on the device map (bow.hip): the binary vocabulary (mo_vocab), the keyframe database a map carries once a
+// vocabulary is attached, and the preselection mo_map_relocalize_pre runs inside its own chain.  The rules are stated above
+// mo_vocab_train in include/vslam_amd.h.  Private to the library.
+#pragma once
+#include <vector>
+
+#include "common.h"
+#include "map_store.h"
+
+// a vocabulary: W words of 32 bytes and one weight per word, on the device and as the host copy mo_vocab_download hands out; rows and
+// weights are padded to Wp (a multiple of 8: the database rows are read 16 bytes at a time), the padding weights are 0
+struct mo_vocab {
+    mo_ctx* c = nullptr;
+    int W = 0, Wp = 0;
+    DevBuf<uint8_t> words;       // [W][32]
+    DevBuf<int32_t> weights;     // [Wp]
+    std::vector<uint8_t> h_words;
+    std::vector<int32_t> h_weights;
+};
+
+// What the preselection leaves on the device for the matching of mo_map_relocalize_pre (valid behind bow_select_enqueue, on the
+// context stream): pair j < n_pre matches frame qf[j] against keyframe slot tf[j] with the row counts cnt; a pair past the selected
+// keyframes names an empty query frame, so the matcher does nothing for it.  mrow[k] = the pair of keyframe position k, -1: not selected.
+struct BowSel {
+    const int32_t* cnt = nullptr;
+    const int32_t* qf = nullptr;
+    const int32_t* tf = nullptr;
+    const int32_t* mrow = nullptr;
+};
+
+// MO_ERR_ARG unless a vocabulary is attached to the map
+int bow_require(mo_map* m);
+// the query chain of mo_map_query_keyframes for the frame staged in the spare slot (n rows), ranked to n_pre places, enqueued on the
+// context stream inside the caller's stage set (marks bow_quantise, bow_hist, bow_score, bow_rank); no synchronisation
+int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel);

@@ -466,6 +466,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(m->kcnt + slot), n, 1, c->stream));
     HIPCHK(c, hipMemcpyAsync(m->kP + (size_t)slot * 12, P, 96, hipMemcpyHostToDevice, c->stream));
     m->h_kcnt.push_back(n);
+    m->kserial.resize((size_t)slot + 1, 0); m->kserial[slot]++;
     m->n_slots = slot + 1;
     m->pos_slot.push_back(slot);
     const int n_kf = (int)m->pos_slot.size();

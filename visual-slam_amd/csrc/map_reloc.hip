@@ -1,7 +1,9 @@
-// map_reloc.hip -- relocalization against the device map (mo_map_relocalize in include/vslam_amd.h): a lost frame against every
-// keyframe, 2D-3D correspondences through the observations, P3P RANSAC per candidate keyframe (pnp.h).  Read-only on the map; the
-// frame is staged in the spare keyframe slot (map_stage_frame).
-// Chain: point_of scatter -> knn-2 matching of the frame against every keyframe (match_launch_pairs, one pair per keyframe) -> scores
+// map_reloc.hip -- relocalization against the device map (mo_map_relocalize and mo_map_relocalize_pre in include/vslam_amd.h): a lost
+// frame against every keyframe - or against the keyframes the place-recognition query of bow.hip selects on the device -, 2D-3D
+// correspondences through the observations, P3P RANSAC per candidate keyframe (pnp.h).  Read-only on the map; the frame is staged in
+// the spare keyframe slot (map_stage_frame).
+// Chain: [preselection: bow_select_enqueue ->] point_of scatter -> knn-2 matching of the frame against every (selected) keyframe
+// (match_launch_pairs, one pair per keyframe) -> scores
 // |C_k| -> ranking -> C_k of the candidates (block scans, query order) -> P3P hypotheses + scoring (one wave per hypothesis, all
 // candidates in one launch) -> best hypothesis + Gauss-Newton refinement (one wave per candidate) -> winner.  One synchronisation.
 // -ffp-contract=off (Makefile, every map file): pnp.h rounds on the device as in the host build of tests/native/pnp_check.cpp.
@@ -10,6 +12,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "bow.h"
 #include "map_store.h"
 #include "pnp.h"
 
@@ -31,7 +34,7 @@ struct RelocGeom {
 struct RelocBufs {
     DevBuf<int32_t> tab;                      // point_of [slot][row]
     DevBuf<int32_t> qf;                       // [n_kf] query frame of every pair: the spare slot
-    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass;   // [n_kf][row] matcher outputs
+    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass;   // [pair][row] matcher outputs (a pair per keyframe, or per preselected keyframe)
     DevBuf<int32_t> score;                    // [n_kf] |C_k|
     DevBuf<int32_t> cq, cp; DevBuf<uint8_t> cinl;         // [candidate][row] C_k (query, point), final inliers
     DevBuf<int32_t> qpt; DevBuf<uint8_t> qinl;            // [row] per query keypoint
@@ -51,10 +54,15 @@ __global__ __launch_bounds__(256) void k_reloc_point_of(MapPts src, int n_pts, c
         if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) atomicMin(tab + (size_t)s * row + kp, i);
 }
 
-// the map point of query q against keyframe position k (-1: none): the ratio-test survivor's best neighbour through point_of
-__device__ __forceinline__ int reloc_point(int k, int s, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
+// the row of the matcher outputs that holds keyframe position k: k itself when every keyframe was matched (mrow NULL), else the pair the
+// preselection gave it, -1: not matched
+__device__ __forceinline__ int reloc_mrow(const int32_t* __restrict__ mrow, int k) { return mrow ? mrow[k] : k; }
+
+// the map point of query q against the keyframe in slot s matched in row mr (-1: none): the ratio-test survivor's best neighbour through point_of
+__device__ __forceinline__ int reloc_point(int mr, int s, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
                                            const int32_t* __restrict__ tab) {
-    const size_t o = (size_t)k * row + q;
+    if (mr < 0) return -1;
+    const size_t o = (size_t)mr * row + q;
     if (!mpass[o]) return -1;
     const int t = midx[2 * o];
     if (t < 0) return -1;
@@ -65,12 +73,12 @@ __device__ __forceinline__ int reloc_point(int k, int s, int q, int row, const i
 // |C_k|, one block per keyframe position
 __global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
                                                      const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
-                                                     const int32_t* __restrict__ tab, int32_t* __restrict__ score) {
+                                                     const int32_t* __restrict__ tab, const int32_t* __restrict__ mrow, int32_t* __restrict__ score) {
     __shared__ int lw[4];
-    const int k = blockIdx.x, s = pos_slot[k];
+    const int k = blockIdx.x, s = pos_slot[k], mr = reloc_mrow(mrow, k);
     const int nq = min(kcnt[spare], row);
     int n = 0;
-    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(k, s, q, row, midx, mpass, tab) >= 0;
+    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(mr, s, q, row, midx, mpass, tab) >= 0;
     for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
     if ((threadIdx.x & 63) == 0) lw[threadIdx.x >> 6] = n;
     __syncthreads();
@@ -114,15 +122,15 @@ __global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ 
 // C_k of candidate blockIdx.x in query order (block scans, no atomics)
 __global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
                                                        const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                       RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
+                                                       const int32_t* __restrict__ mrow, RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
     __shared__ int lw[40];
     const int c = blockIdx.x, k = res->cand[c];
     if (k < 0) return;
-    const int s = pos_slot[k], nq = min(kcnt[spare], row);
+    const int s = pos_slot[k], nq = min(kcnt[spare], row), mr = reloc_mrow(mrow, k);
     int added = 0;
     for (int b = 0; b < nq; b += 1024) {
         const int q = b + threadIdx.x;
-        const int p = q < nq ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
+        const int p = q < nq ? reloc_point(mr, s, q, row, midx, mpass, tab) : -1;
         int tot;
         const int r = block_excl_scan(p >= 0 ? 1 : 0, lw, &tot);
         if (p >= 0) { cq[(size_t)c * row + added + r] = q; cp[(size_t)c * row + added + r] = p; }
@@ -246,7 +254,7 @@ __global__ __launch_bounds__(64) void k_reloc_refine(RelocGeom g, const float* _
 // the winner (most final inliers, ties to the lower position) and its per-query-keypoint map point and inlier flag
 __global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
                                                       const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                      const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
+                                                      const int32_t* __restrict__ mrow, const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
                                                       int32_t* __restrict__ qpt, uint8_t* __restrict__ qinl) {
     __shared__ int win;
     if (threadIdx.x == 0) {
@@ -257,10 +265,10 @@ __global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict_
         res->win = w;
     }
     __syncthreads();
-    const int w = win, k = w >= 0 ? res->cand[w] : -1, s = k >= 0 ? pos_slot[k] : 0;
+    const int w = win, k = w >= 0 ? res->cand[w] : -1, s = k >= 0 ? pos_slot[k] : 0, mr = k >= 0 ? reloc_mrow(mrow, k) : -1;
     const int nq = min(kcnt[spare], row);
     for (int q = threadIdx.x; q < nq; q += 256) {
-        qpt[q] = k >= 0 ? reloc_point(k, s, q, row, midx, mpass, tab) : -1;
+        qpt[q] = reloc_point(mr, s, q, row, midx, mpass, tab);
         qinl[q] = 0;
     }
     __syncthreads();
@@ -269,10 +277,15 @@ __global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict_
     for (int j = threadIdx.x; j < m; j += 256) qinl[cq[(size_t)w * row + j]] = cinl[(size_t)w * row + j];
 }
 
-extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, mo_map_reloc_out* out) {
+// mo_map_relocalize (n_pre < 0) and mo_map_relocalize_pre: one body; they differ in which keyframes are matched
+static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, int n_pre, mo_map_reloc_out* out) {
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;
     if (!f || !K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (n_pre >= 0) {
+        if (n_pre < 1) return mo_fail(c, MO_ERR_ARG, "n_pre must be >= 1");
+        if (int rv = bow_require(m)) return rv;
+    }
     if (prm->max_candidates < 1 || prm->max_candidates > RL_MAX_CAND) return mo_fail(c, MO_ERR_ARG, "max_candidates must be in 1 .. 64");
     if (prm->n_hyp < 1 || prm->n_hyp > (1 << 20)) return mo_fail(c, MO_ERR_ARG, "n_hyp must be in 1 .. 2^20");
     if (!(prm->thr_px >= 0.0)) return mo_fail(c, MO_ERR_ARG, "thr_px must be >= 0");
@@ -306,30 +319,36 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
     };
     if ((rc = map_stage_frame(m, f, false, &out->from_token, defaults, &n, &qk, &qdesc)) || !qk) return rc;   // (nothing to match: not relocalized, not an error)
     const int n_kf = (int)m->pos_slot.size(), spare = m->kslots, row = m->row;
+    // the keyframes that are matched: all of them, or - with fewer than all asked for - the n_pre the query selects on the device
+    const bool pre = n_pre >= 0 && n_pre < n_kf;
+    const int n_pairs = pre ? n_pre : n_kf;
+    BowSel sel;
+    if (pre && (rc = bow_select_enqueue(m, n, n_pre, &sel))) return rc;
     if (!m->rl) m->rl = new RelocBufs();
     RelocBufs& b = *m->rl;
-    const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_kf * row, cand_n = (size_t)nc * row;
+    const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_pairs * row, cand_n = (size_t)nc * row;
     if ((rc = b.tab.reserve(c, tab_n)) || (rc = b.qf.reserve(c, (size_t)n_kf)) || (rc = b.midx.reserve(c, pair_n * 2)) ||
         (rc = b.mdist.reserve(c, pair_n * 2)) || (rc = b.mpass.reserve(c, pair_n)) || (rc = b.score.reserve(c, (size_t)n_kf)) ||
         (rc = b.cq.reserve(c, cand_n)) || (rc = b.cp.reserve(c, cand_n)) || (rc = b.cinl.reserve(c, cand_n)) ||
         (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
         return rc;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.tab, INT_MAX, tab_n, c->stream));
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.qf, spare, (size_t)n_kf, c->stream));
+    if (!pre) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.qf, spare, (size_t)n_kf, c->stream));
     const MapPts src = m->P[m->cur].view();
     if (m->n_pts > 0)
         hipLaunchKernelGGL(k_reloc_point_of, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf,
                            m->kcnt, row, b.tab);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_point_of");
-    if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, m->kcnt, b.qf, m->d_pos_slot, 0, 0, n_kf, row, prm->ratio,
+    if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, pre ? sel.cnt : (const int32_t*)m->kcnt,
+                                 pre ? sel.qf : (const int32_t*)b.qf, pre ? sel.tf : (const int32_t*)m->d_pos_slot, 0, 0, n_pairs, row, prm->ratio,
                                  b.midx, b.mdist, b.mpass)))
         return rc;
     mo_stage_mark(c, "reloc_match");
-    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, b.score);
+    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.score);
     hipLaunchKernelGGL(k_reloc_rank, dim3(1), dim3(256), 0, c->stream, b.score, n_kf, nc, b.res);
     hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab,
-                       b.res, b.cq, b.cp);
+                       sel.mrow, b.res, b.cq, b.cp);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_candidates");
     hipLaunchKernelGGL(k_reloc_hyp, dim3((unsigned)((prm->n_hyp + RL_HYP_WAVES - 1) / RL_HYP_WAVES), nc), dim3(64 * RL_HYP_WAVES), 0, c->stream, g, src.xyz, qk,
@@ -337,7 +356,7 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_p3p");
     hipLaunchKernelGGL(k_reloc_refine, dim3(nc), dim3(64), 0, c->stream, g, src.xyz, qk, row, prm->seed, b.cq, b.cp, b.cinl, b.res);
-    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, b.cq,
+    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.cq,
                        b.cinl, b.res, b.qpt, b.qinl);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_refine");
@@ -362,4 +381,13 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
         out->ok = r.ninl[r.win] >= prm->min_inliers && r.best[r.win] != 0;
     }
     return MO_OK;
+}
+
+extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, mo_map_reloc_out* out) {
+    return reloc_run(m, f, K, prm, -1, out);
+}
+
+extern "C" int mo_map_relocalize_pre(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, int32_t n_pre,
+                                     mo_map_reloc_out* out) {
+    return reloc_run(m, f, K, prm, n_pre < 0 ? 0 : n_pre, out);
 }

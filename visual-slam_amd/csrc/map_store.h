@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
 // Private to the library.
 #pragma once
 #include <algorithm>
@@ -34,12 +34,14 @@ struct BaBufs;      // mo_map_bundle_adjust and mo_map_add_observations (map_ba.
 struct FuseBufs;    // mo_map_fuse (map_fuse.hip)
 struct GrowBufs;    // mo_map_grow (map_grow.hip)
 struct CovisBufs;   // mo_map_covisibility, mo_map_local_keyframes and mo_map_track_covisible (map_covis.hip)
+struct BowBufs;     // mo_map_set_vocabulary: the keyframe database of mo_map_query_keyframes and mo_map_relocalize_pre (bow.hip)
 void map_scratch_free(RelocBufs* b);
 void map_scratch_free(TrackBufs* b);
 void map_scratch_free(BaBufs* b);
 void map_scratch_free(FuseBufs* b);
 void map_scratch_free(GrowBufs* b);
 void map_scratch_free(CovisBufs* b);
+void map_scratch_free(BowBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -47,6 +49,7 @@ struct mo_map {
     int row = 0, kslots = 0, n_slots = 0;
     DevBuf<mo_keypoint> kkps; DevBuf<uint8_t> kdesc; DevBuf<int32_t> kcnt; DevBuf<double> kP;
     std::vector<int32_t> h_kcnt;
+    std::vector<uint32_t> kserial;                    // by slot: bumped whenever mo_map_add_keyframe stores rows there (the keyframe database's staleness test)
     std::vector<int32_t> pos_slot;                    // keyframe position -> slot
     DevBuf<int32_t> d_pos_slot;
     // the previous and the new keyframe image (colours of the grown points)
@@ -77,8 +80,9 @@ struct mo_map {
     FuseBufs* fu = nullptr;
     GrowBufs* gr = nullptr;
     CovisBufs* cv = nullptr;
+    BowBufs* bow = nullptr;
     // (mo_map_destroy selects the device and drains the stream first)
-    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); }
+    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); }
 };
 
 // ---- the one reader of an observation -----------------------------------------------------------------------------------------------

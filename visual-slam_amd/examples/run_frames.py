@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -118,6 +118,11 @@ def main(argv=None):
     ap.add_argument("--keyframe-every", type=int, default=20, help="with --map: a keyframe every N frames (tracker.py:290)")
     ap.add_argument("--relocalize", action="store_true", help="with --map: when the tracking step fails, relocalize the frame against the "
                     "device map (LocalMapper.relocalize) and go on tracking from it")
+    ap.add_argument("--vocabulary", default="", help="with --map --relocalize: PATH of a place-recognition vocabulary (.npz of vslam_amd.Vocabulary.save) "
+                    "attached to the map; a file that does not exist is trained from the map's keyframes (up to 1024 words) at the first "
+                    "relocalization and saved there")
+    ap.add_argument("--reloc-preselect", type=int, default=0, help="with --vocabulary: N > 0: relocalize matches the frame only against the N "
+                    "keyframes the vocabulary query ranks first (LocalMapper.relocalize(preselect=N))")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
@@ -150,6 +155,12 @@ def main(argv=None):
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
     if args.relocalize and not args.map:
         ap.error("--relocalize needs --map")
+    if args.vocabulary and not args.relocalize:
+        ap.error("--vocabulary needs --map and --relocalize")
+    if args.reloc_preselect and not args.vocabulary:
+        ap.error("--reloc-preselect needs --vocabulary")
+    if args.reloc_preselect < 0:
+        ap.error("--reloc-preselect must be >= 0")
     if args.track_map and not args.map:
         ap.error("--track-map needs --map")
     if args.covisible and not args.track_map:
@@ -169,6 +180,10 @@ def main(argv=None):
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
         mapper = LocalMapper(K, args.map)
+        if args.vocabulary and os.path.exists(args.vocabulary):
+            import vslam_amd
+            mapper.set_vocabulary(vslam_amd.Vocabulary.load(args.vocabulary, context=mapper.ctx))
+            print("vocabulary: %d words from %s" % (len(mapper.vocabulary), args.vocabulary))
 
     def track_pose(R, t, frame, kps, desc, idx):
         """Tracker._update_pose (tracker.py:268-279) and the keyframe every N frames (tracker.py:114-118, 290)"""
@@ -243,9 +258,18 @@ def main(argv=None):
     def relocalize(frame, kps, desc, idx):
         """the frame against the map (ORB-SLAM2's Tracking::Relocalization); on success tracking goes on from its pose"""
         nonlocal ref_pose
-        ok, T, info = mapper.relocalize(kps, desc)
-        print("frame %d: relocalize %s, keyframe %s, %d candidates, %d inliers" % (idx, "ok" if ok else "failed", info["kf_pos"],
-                                                                                  len(info["candidates"]), info["n_inliers"]))
+        if args.vocabulary and mapper.vocabulary is None and mapper.keyframes:
+            rows = sum(len(kf["descriptors"]) for kf in mapper.keyframes)
+            if rows >= 2:
+                v = mapper.train_vocabulary(min(1024, rows))
+                v.save(args.vocabulary)
+                print("frame %d: vocabulary of %d words trained on %d rows of %d keyframes in %d iterations, saved to %s"
+                      % (idx, len(v), rows, len(mapper.keyframes), v.iterations, args.vocabulary))
+        pre = args.reloc_preselect if args.reloc_preselect > 0 and mapper.vocabulary is not None else None
+        ok, T, info = mapper.relocalize(kps, desc, preselect=pre)
+        print("frame %d: relocalize %s, keyframe %s, %d candidates, %d inliers%s" % (idx, "ok" if ok else "failed", info["kf_pos"],
+                                                                                    len(info["candidates"]), info["n_inliers"],
+                                                                                    "" if pre is None else " (preselect %d)" % pre))
         if ok:
             ref_pose = T
             recent[:] = recent[-1:] + [T]

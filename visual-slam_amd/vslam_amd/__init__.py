@@ -143,6 +143,14 @@ class MapLocalOut(C.Structure):
     _fields_ = [("local", C.c_void_p), ("n_k1", C.c_int32), ("n_local_kf", C.c_int32), ("ref", C.c_int32)]
 
 
+class MapQueryParams(C.Structure):
+    _fields_ = [("n_best", C.c_int32)]
+
+
+class MapQueryOut(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("score", C.c_void_p), ("n", C.c_int32), ("from_token", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -231,6 +239,14 @@ SIGNATURES = {
     "mo_map_covisibility": (_i, [_vp, _vp, _vp]),
     "mo_map_local_keyframes": (_i, [_vp, _vp, _vp]),
     "mo_map_track_covisible": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_vocab_train": (_i, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "mo_vocab_create": (_i, [_vp, _vp, _vp, C.c_int32, _vp]),
+    "mo_vocab_words": (_i, [_vp]),
+    "mo_vocab_download": (_i, [_vp, _vp, _vp]),
+    "mo_vocab_destroy": (None, [_vp]),
+    "mo_map_set_vocabulary": (_i, [_vp, _vp]),
+    "mo_map_query_keyframes": (_i, [_vp, _vp, _vp, _vp]),
+    "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
 }
 
 _lib = None
@@ -348,6 +364,8 @@ class Context:
         if getattr(self, "h", None):
             for m in list(getattr(self, "_maps", ())):  # device maps bound to this context (vslam_amd.mapper) go first
                 m.close()
+            for v in list(getattr(self, "_vocabs", ())):
+                v.close()
             self.lib.mo_destroy(self.h)
             self.h = None
 
@@ -690,6 +708,70 @@ class Context:
 
 
 _default_ctx = None
+
+
+class Vocabulary:
+    """A flat binary vocabulary for place recognition: `words` [W][32] uint8 and `weights` [W] int32 (the comment above mo_vocab_train
+    in include/vslam_amd.h states every rule).  Trained on the device from the caller's own descriptors; it survives a process as
+    the two arrays (save / load: an .npz).  Attach it with LocalMapper.set_vocabulary."""
+
+    def __init__(self, ctx, handle, iterations=None):
+        self.ctx, self.h, self.iterations = ctx, handle, iterations
+        W = ctx.lib.mo_vocab_words(handle)
+        self.words = np.zeros((W, 32), np.uint8)
+        self.weights = np.zeros(W, np.int32)
+        ctx._check(ctx.lib.mo_vocab_download(handle, _ptr(self.words), _ptr(self.weights)))
+        self.words.flags.writeable = False
+        self.weights.flags.writeable = False
+        if not hasattr(ctx, "_vocabs"):
+            ctx._vocabs = weakref.WeakSet()
+        ctx._vocabs.add(self)   # closing the context closes this vocabulary (after the maps)
+
+    @classmethod
+    def train(cls, descriptor_arrays, words, iters=10, context=None):
+        """descriptor_arrays: one [n_i][32] uint8 array per image (keyframe); `words` words, at most `iters` iterations"""
+        ctx = context if context is not None else default_context()
+        arrays = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descriptor_arrays]
+        desc = np.ascontiguousarray(np.vstack(arrays)) if arrays else np.zeros((0, 32), np.uint8)
+        off = np.zeros(len(arrays) + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in arrays])
+        h, ran = C.c_void_p(), C.c_int32(0)
+        ctx._check(ctx.lib.mo_vocab_train(ctx.h, _ptr(desc), len(desc), _ptr(off), len(arrays), int(words), int(iters), C.byref(h), C.byref(ran)))
+        return cls(ctx, h, int(ran.value))
+
+    @classmethod
+    def from_arrays(cls, words, weights, context=None):
+        ctx = context if context is not None else default_context()
+        w = np.ascontiguousarray(words, np.uint8).reshape(-1, 32)
+        wt = np.ascontiguousarray(weights, np.int32).reshape(-1)
+        if len(w) != len(wt):
+            raise ValueError("one weight per word")
+        h = C.c_void_p()
+        ctx._check(ctx.lib.mo_vocab_create(ctx.h, _ptr(w), _ptr(wt), len(w), C.byref(h)))
+        return cls(ctx, h)
+
+    def save(self, path):
+        with open(path, "wb") as fh:   # (the path as given: np.savez would append .npz to a name without it)
+            np.savez(fh, words=self.words, weights=self.weights)
+
+    @classmethod
+    def load(cls, path, context=None):
+        with np.load(path) as z:
+            return cls.from_arrays(z["words"], z["weights"], context)
+
+    def __len__(self):
+        return len(self.weights)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.mo_vocab_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def default_context():

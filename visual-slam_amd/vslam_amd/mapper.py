@@ -108,11 +108,13 @@ class LocalMapper:
         self._lists = None
         self.last = None          # the growth step of the last add_keyframe (match lists, inlier mask, F, new points)
         self.map_points = _MapPoints(self)
+        self.vocabulary = None
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "h", None):
             self.lib.mo_map_destroy(self._h)
         self._h = None
+        self.vocabulary = None
 
     def __del__(self):
         try:
@@ -468,14 +470,45 @@ class LocalMapper:
         self._sync_size()
 
     # ---- relocalization -----------------------------------------------------------------------------------------------------------
-    def relocalize(self, keypoints, descriptors, ratio_threshold=0.75, threshold=3.0, min_inliers=50, max_candidates=4, n_hyp=512, seed=None):
+    # ---- place recognition ----------------------------------------------------------------------------------------------------------
+    def set_vocabulary(self, vocabulary):
+        """Attaches a vslam_amd.Vocabulary (None detaches): the map then keeps a database of term counts per keyframe, made lazily by
+        the next query_keyframes or relocalize(preselect=...).  The mapper keeps the vocabulary alive while it is attached."""
+        if vocabulary is not None and vocabulary.h is None:
+            raise ValueError("the vocabulary is closed")
+        self._check(self.lib.mo_map_set_vocabulary(self._h, vocabulary.h if vocabulary is not None else None))
+        self.vocabulary = vocabulary
+
+    def train_vocabulary(self, words, iters=10):
+        """A vocabulary trained on the descriptors of this map's keyframes (one image per keyframe), attached and returned"""
+        v = V.Vocabulary.train([kf["descriptors"] for kf in self.keyframes if kf["descriptors"] is not None], words, iters, context=self.ctx)
+        self.set_vocabulary(v)
+        return v
+
+    def query_keyframes(self, keypoints, descriptors, n_best=10):
+        """The keyframes that look like the frame (mo_map_query_keyframes in include/vslam_amd.h states the rules): DBoW2's L1 score of
+        the frame's and each keyframe's tf-idf vector over the attached vocabulary.  The frame is given like relocalize's; the map is
+        not changed.  Returns (positions, scores): the keyframe positions with a score > 0, highest first, at most n_best."""
+        ref, n, _keep = self._frame_ref(keypoints, descriptors)
+        nb = int(n_best)
+        pos = np.full(max(nb, 1), -1, np.int32)
+        score = np.zeros(max(nb, 1), np.float64)
+        prm = V.MapQueryParams(nb)
+        out = V.MapQueryOut(pos.ctypes.data, score.ctypes.data)
+        self._check(self.lib.mo_map_query_keyframes(self._h, C.byref(ref), C.byref(prm), C.byref(out)))
+        return pos[:int(out.n)].copy(), score[:int(out.n)].copy()
+
+    def relocalize(self, keypoints, descriptors, ratio_threshold=0.75, threshold=3.0, min_inliers=50, max_candidates=4, n_hyp=512, seed=None,
+                   preselect=None):
         """The pose of a lost frame against the map as it stands (the map is not changed): the frame is matched against every keyframe
         (knn-2, Lowe ratio), the matches become 2D-3D correspondences through the map's observations, and a P3P RANSAC with Gauss-Newton
         refinement runs on the best-scoring keyframes (mo_map_relocalize in include/vslam_amd.h states the rules).  The frame is given
         like add_keyframe's: the arrays a detect_and_compute returned (resident on the device: nothing is uploaded) or host arrays.
         Returns (ok, pose, info): pose 4x4 (X_cam = R X + t, the convention add_keyframe takes; None without a winner); info holds
         kf_pos / kf_id of the winner, the candidates [(position, score, inliers)], and per query keypoint `point` (map point index,
-        -1: none) and `inlier` of the winner."""
+        -1: none) and `inlier` of the winner.
+        preselect=N: the frame is matched only against the N keyframes query_keyframes ranks first (selected on the device, no host
+        round trip; mo_map_relocalize_pre); needs a vocabulary.  N >= the number of keyframes gives the plain call's result."""
         seed = self.seed if seed is None else int(seed)
         ref, n, _keep = self._frame_ref(keypoints, descriptors)
         K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
@@ -487,7 +520,10 @@ class LocalMapper:
         cinl = np.zeros(max(nc, 1), np.int32)
         prm = V.MapRelocParams(float(ratio_threshold), float(threshold), int(min_inliers), nc, int(n_hyp), seed)
         out = V.MapRelocOut(point.ctypes.data, inlier.ctypes.data, cpos.ctypes.data, cscore.ctypes.data, cinl.ctypes.data)
-        self._check(self.lib.mo_map_relocalize(self._h, C.byref(ref), V._ptr(K), C.byref(prm), C.byref(out)))
+        if preselect is None:
+            self._check(self.lib.mo_map_relocalize(self._h, C.byref(ref), V._ptr(K), C.byref(prm), C.byref(out)))
+        else:
+            self._check(self.lib.mo_map_relocalize_pre(self._h, C.byref(ref), V._ptr(K), C.byref(prm), int(preselect), C.byref(out)))
         kf_pos = int(out.kf_pos)
         pose = None
         if kf_pos >= 0:
