@@ -389,6 +389,29 @@ def world(name):
     return _W[name]
 
 
+# relocalization with preselection on the clean world: the vocabulary size, the keyframes preselected, the queries (the positions of
+# test_relocalize_after_removal, with its pose offsets)
+PRE_WORDS, PRE_N, PRE_QUERIES = 256, 3, (3, 6, 0)
+_VOC = {}
+
+
+def clean_vocabulary():
+    """(words, weights, iterations) of tests/bow_restatement.train on the clean world's keyframes by position, PRE_WORDS words and 10
+    iterations, trained once per process"""
+    from tests import bow_restatement as B
+    from tests.bow_worlds import rows_of
+    if "clean" not in _VOC:
+        _VOC["clean"] = B.train(*rows_of(world("clean").kf_desc), PRE_WORDS, 10)
+    return _VOC["clean"]
+
+
+def clean_reloc_query(pos):
+    """(keypoints, descriptors, pose) of the relocalization query near position pos of the clean world"""
+    w = world("clean")
+    T = pose_near(w, pos, (0.02, -0.03, 0.01), (0.08, -0.05, 0.1))
+    return w.reloc_query(pos, T) + (T,)
+
+
 def pose_near(w, pos, d_rot=(0.01, -0.02, 0.01), d_c=(0.1, -0.05, 0.05)):
     return w.kf_poses[pos] @ pose(rot(list(d_rot)), np.array(d_c))
 

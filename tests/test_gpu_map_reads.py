@@ -10,8 +10,9 @@ import pytest
 
 from tests import track_restatement as TR
 from tests.ba_restatement import add_observations as restate_add
-from tests.map_worlds import (BA_STEPS, BA_WINDOW, STALE_BA_STEPS, MapWorld, ba_case, ba_restated, build_map, cull_after_ba, flip,
-                              kps_array, perturbed, perturbed_pose, pose_near, project, stale_queries, track, world)
+from tests.map_worlds import (BA_STEPS, BA_WINDOW, PRE_N, PRE_QUERIES, PRE_WORDS, STALE_BA_STEPS, MapWorld, ba_case, ba_restated, build_map,
+                              clean_reloc_query, clean_vocabulary, cull_after_ba, flip, kps_array, perturbed, perturbed_pose, pose_near, project,
+                              stale_queries, track, world)
 from tests.reloc_restatement import restate
 
 pytestmark = pytest.mark.gpu
@@ -133,6 +134,42 @@ def test_relocalize_after_removal():
         _same_reloc(res, twin.relocalize(kps, desc))
         _unchanged(m, snap)
     print("relocalize after removal: largest |pose - truth| %.3g (bound %.3g)" % (worst, POSE_TRUTH))
+    assert ctx.dev_status() == 0
+    m.close(); twin.close(); ctx.close()
+
+
+def test_relocalize_preselected_after_removal():
+    """(a') the same world and queries with relocalize(preselect=3): the point_of table is indexed by POSITION and only the preselected
+    keyframes are matched, on a map whose position -> slot table is not the identity.  The vocabulary (256 words: the true position
+    ranks first, tests/test_map_worlds_cpu.py) is byte-equal on the map and its twin and equal to the restatement's; per query the
+    ranking equals the restatement on both maps, the preselected call gives the same bytes on the map and on its twin, and its winner,
+    counts, pose bytes and per-keypoint arrays are the plain call's, which still equals the relocalization's restatement."""
+    from tests import bow_restatement as B
+    ctx = _ctx()
+    w = world("clean")
+    m, twin = build_map(ctx, w), build_map(ctx, w, twin=True)
+    v, vt = m.train_vocabulary(PRE_WORDS, 10), twin.train_vocabulary(PRE_WORDS, 10)
+    words, weights, ran = clean_vocabulary()
+    assert v.words.tobytes() == vt.words.tobytes() and v.weights.tobytes() == vt.weights.tobytes() and v.iterations == vt.iterations
+    assert v.words.tobytes() == words.tobytes() and v.weights.tobytes() == weights.tobytes() and v.iterations == ran
+    for pos in PRE_QUERIES:   # slots 5, 8, 0
+        kps, desc, T = clean_reloc_query(pos)
+        rpos, rsc = B.query(desc, w.kf_desc, words, weights, PRE_N)
+        for mm in (m, twin):
+            qp, qs = mm.query_keyframes(kps, desc, PRE_N)
+            assert qp.tolist() == rpos and qs.tolist() == rsc, (qp.tolist(), rpos)
+        assert pos in rpos
+        snap = _snapshot(m)
+        pre = m.relocalize(kps, desc, preselect=PRE_N)
+        _same_reloc(pre, twin.relocalize(kps, desc, preselect=PRE_N))
+        plain = m.relocalize(kps, desc)
+        (ok, pose, info), (okp, posep, infop) = plain, pre
+        assert ok and okp and infop["kf_pos"] == info["kf_pos"] == pos
+        assert infop["n_corr"] == info["n_corr"] and infop["n_inliers"] == info["n_inliers"] and posep.tobytes() == pose.tobytes()
+        assert np.array_equal(infop["point"], info["point"]) and np.array_equal(infop["inlier"], info["inlier"])
+        assert set(c[0] for c in infop["candidates"]) <= set(rpos)
+        _reloc_equals_restatement(m, desc, info)
+        _unchanged(m, snap)
     assert ctx.dev_status() == 0
     m.close(); twin.close(); ctx.close()
 

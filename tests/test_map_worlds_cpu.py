@@ -4,8 +4,9 @@ how many entries tell the two apart.  No GPU."""
 import numpy as np
 
 from tests import track_restatement as TR
-from tests.map_worlds import (BA_FIRST_FREE, REMOVED, STALE_BA_STEPS, ba_case, ba_problem_edges, ba_restated, cull_after_ba,
-                              decisions_are_clear, perturbed, perturbed_pose, pose_near, project, stale_queries, track, world)
+from tests.map_worlds import (BA_FIRST_FREE, PRE_N, PRE_QUERIES, PRE_WORDS, REMOVED, STALE_BA_STEPS, ba_case, ba_problem_edges, ba_restated,
+                              clean_reloc_query, clean_vocabulary, cull_after_ba, decisions_are_clear, perturbed, perturbed_pose, pose_near,
+                              project, stale_queries, track, world)
 from tests.reloc_restatement import restate
 
 def test_the_builder_is_consistent():
@@ -77,6 +78,23 @@ def test_skipping_the_table_changes_every_read_path():
     assert n_e > 0
     # a free and a fixed keyframe sit in a slot that is not their position
     assert any(bw.survivors[p] != p for p in fr) and any(bw.survivors[p] != p for p in fx)
+
+
+def test_the_preselection_keeps_the_true_keyframe_on_the_clean_world():
+    """the premise of test_relocalize_preselected_after_removal (tests/test_gpu_map_reads.py): with PRE_WORDS words the restated query
+    ranks the true position among the first PRE_N for each of its queries, so relocalize(preselect=PRE_N) has the plain call's winner
+    among the keyframes it matches; and the clean world's position -> slot table is not the identity at two of the three positions"""
+    from tests import bow_restatement as B
+    w = world("clean")
+    words, weights, _ = clean_vocabulary()
+    assert len(words) == PRE_WORDS and PRE_N < len(w.survivors)
+    for pos in PRE_QUERIES:
+        _, qd, _ = clean_reloc_query(pos)
+        first, sc = B.query(qd, w.kf_desc, words, weights, len(w.survivors))
+        print("query near position %d (slot %d): first %s scores %s" % (pos, w.survivors[pos], first[:PRE_N + 1], ["%.3f" % x for x in sc[:PRE_N + 1]]))
+        assert pos in first[:PRE_N], (pos, first)
+        assert len(set(sc[:PRE_N + 1])) == len(sc[:PRE_N + 1])   # no tie at the cut: the selection does not hang on a tie rule
+    assert sum(w.survivors[p] != p for p in PRE_QUERIES) >= 2
 
 
 def test_the_octave_world_tells_the_gate_the_scaling_and_the_weights():

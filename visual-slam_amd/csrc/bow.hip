@@ -442,8 +442,5 @@ extern "C" int mo_map_query_keyframes(mo_map* m, const mo_frame_ref* f, const mo
     HIPCHK(c, hipMemcpyAsync(out->pos, b.out_pos, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out->score, b.out_score, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&out->n, b.out_n, 4, hipMemcpyDeviceToHost, c->stream));
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
-    return MO_OK;
+    return map_sync(c, clk);
 }

@@ -101,21 +101,16 @@ __global__ void k_ba_init(BaRes* __restrict__ res) {
 
 // local points: >= 2 edges, one of them at a position the window frees (>= lo_pos, never 0); every position with an edge to a local
 // point is flagged (plain stores of 1: the racing writers agree)
-__global__ __launch_bounds__(BA_BLOCK) void k_ba_mark(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                                      int lo_pos, int32_t* __restrict__ loc, int32_t* __restrict__ ecnt, int32_t* __restrict__ kf_edge) {
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_mark(MapView v, int lo_pos, int32_t* __restrict__ loc, int32_t* __restrict__ ecnt, int32_t* __restrict__ kf_edge) {
     const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
-    if (i >= n_pts) return;
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    int nv = 0, pos, s, kp;
+    if (i >= v.n_pts) return;
+    int nv = 0;
     bool fr = false;
-    for (int o = o0; o < o1; o++)
-        if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) { nv++; fr |= pos >= lo_pos && pos != 0; }
+    map_each_obs(v, i, [&](int, int pos, int, int) { nv++; fr |= pos >= lo_pos && pos != 0; return false; });
     const bool local = nv >= 2 && fr;
     loc[i] = local;
     ecnt[i] = local ? nv : 0;
-    if (local)
-        for (int o = o0; o < o1; o++)
-            if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) kf_edge[pos] = 1;
+    if (local) map_each_obs(v, i, [&](int, int pos, int, int) { kf_edge[pos] = 1; return false; });
 }
 
 // free and fixed keyframes.  Outside the window a position with edges is fixed; inside, in position order, the lowest ones are fixed
@@ -143,28 +138,25 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_setup(BaPrm prm, const int32_t*
     res->run = nfree > 0 && res->n_local > 0;
 }
 
-__global__ __launch_bounds__(BA_BLOCK) void k_ba_edges(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                                       const mo_keypoint* __restrict__ kkps, int row, double sf, const int32_t* __restrict__ loc,
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_edges(MapView v, const mo_keypoint* __restrict__ kkps, double sf, const int32_t* __restrict__ loc,
                                                        const int32_t* __restrict__ lrank, const int32_t* __restrict__ ebase, int32_t* __restrict__ lpt,
                                                        int32_t* __restrict__ eoff, double* __restrict__ X, int32_t* __restrict__ e_kf,
                                                        int32_t* __restrict__ e_obs, float* __restrict__ e_xy, double* __restrict__ e_info,
                                                        uint8_t* __restrict__ e_inl, const BaRes* __restrict__ res) {
     const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
     if (i == 0) eoff[res->n_local] = res->n_edges;
-    if (i >= n_pts || !loc[i]) return;
+    if (i >= v.n_pts || !loc[i]) return;
     const int r = lrank[i];
     lpt[r] = i;
     int e = ebase[i];
     eoff[r] = e;
-    for (int k = 0; k < 3; k++) X[(size_t)r * 3 + k] = src.xyz[(size_t)i * 3 + k];
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    int pos, s, kp;
-    for (int o = o0; o < o1; o++) {
-        if (map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) continue;
-        const mo_keypoint q = kkps[(size_t)s * row + kp];
+    for (int k = 0; k < 3; k++) X[(size_t)r * 3 + k] = v.src.xyz[(size_t)i * 3 + k];
+    map_each_obs(v, i, [&](int o, int pos, int s, int kp) {
+        const mo_keypoint q = kkps[(size_t)s * v.row + kp];
         e_kf[e] = pos; e_obs[e] = o; e_xy[(size_t)e * 2] = q.x; e_xy[(size_t)e * 2 + 1] = q.y; e_info[e] = ba_info(sf, q.octave); e_inl[e] = 1;
         e++;
-    }
+        return false;
+    });
 }
 
 // mode 0: robust cost of every edge; 1: the same and every edge classified; 2: every edge classified, plain cost of the inliers
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(1024) void k_ba_reduce(int idx, const double* __res
     int c = 0;
     for (int r = threadIdx.x; r < n; r += 1024) { s += pc[r]; c += pn[r]; }
     s = ba_block_sum(s, lds);
-    for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+    c = wave_sum_int(c);
     if ((threadIdx.x & 63) == 0) atomicAdd(&cnt, c);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -482,10 +474,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_write(BaPrm prm, int n_pts, int
     if (i < res->n_free && res->accepted[0] + res->accepted[1] > 0) {   // (no accepted step: the poses are the given ones, kP stays)
         const int pos = res->free_pos[i];
         double R[9], t[3], P[12];
-        for (int j = 0; j < 3; j++) {
-            for (int l = 0; l < 3; l++) R[j * 3 + l] = poseC[(size_t)pos * 12 + j * 4 + l];
-            t[j] = poseC[(size_t)pos * 12 + j * 4 + 3];
-        }
+        pose_split(poseC + (size_t)pos * 12, R, t);
         pnp_projection(prm.K, R, t, P);
         for (int k = 0; k < 12; k++) kP[(size_t)pos_slot[pos] * 12 + k] = P[k];
     }
@@ -506,7 +495,7 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         if (!std::isfinite(K[i])) return mo_fail(c, MO_ERR_ARG, "K must be finite");
     for (size_t i = 0; i < (size_t)n_kf * 12; i++)
         if (!std::isfinite(poses[i])) return mo_fail(c, MO_ERR_ARG, "poses must be finite");
-    const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
+    const int lo_pos = map_window_lo(prm->window, n_kf);
     if (n_kf - std::max(lo_pos, 1) > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a window of at most 16");
     HIPCHK(c, hipSetDevice(c->device));
     HostClock clk(c);
@@ -520,10 +509,10 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     if (out->edge_inlier && no) std::memset(out->edge_inlier, 0, no);
     if (out->points_out) for (size_t i = 0; i < np * 3; i++) out->points_out[i] = NAN;
     if (n_kf == 0 || np == 0 || no == 0) return MO_OK;   // an empty map: nothing runs, not an error
-    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    int rc;
+    if ((rc = map_int32_guard(m))) return rc;
     if (!m->ba) m->ba = new BaBufs();
     BaBufs& b = *m->ba;
-    int rc;
     if ((rc = b.loc.reserve(c, np)) || (rc = b.ecnt.reserve(c, np)) || (rc = b.lrank.reserve(c, np)) || (rc = b.ebase.reserve(c, np)) ||
         (rc = b.lpt.reserve(c, np)) || (rc = b.eoff.reserve(c, np + 1)) || (rc = b.pn.reserve(c, np)) || (rc = b.pfix.reserve(c, np)) ||
         (rc = b.X.reserve(c, np * 3)) || (rc = b.Xt.reserve(c, np * 3)) || (rc = b.Vi.reserve(c, np * 6)) || (rc = b.gp.reserve(c, np * 3)) ||
@@ -543,18 +532,18 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     BaPrm p;
     for (int i = 0; i < 9; i++) p.K[i] = K[i];
     p.sf = prm->scale_factor; p.chi2 = prm->chi2; p.n_kf = n_kf; p.lo_pos = lo_pos;
-    const MapPts src = m->P[m->cur].view();
+    const MapView v = map_view(m);
     const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
     const unsigned wblocks = (unsigned)((std::max(np, no) + BA_BLOCK - 1) / BA_BLOCK);
     double* dcv = b.S + BA_MAX_DIM * BA_MAX_DIM + BA_MAX_DIM;
     hipLaunchKernelGGL(k_ba_init, dim3(1), dim3(64), 0, c->stream, b.res);
-    hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, lo_pos, b.loc, b.ecnt, b.kf_edge);
+    hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, lo_pos, b.loc, b.ecnt, b.kf_edge);
     HIPCHK(c, hipGetLastError());
     if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, &b.res.p->n_local))) return rc;
     if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, &b.res.p->n_edges))) return rc;
     hipLaunchKernelGGL(k_ba_setup, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, b.kf_edge, b.kf_fidx, b.res);
-    hipLaunchKernelGGL(k_ba_edges, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, m->kkps, m->row, p.sf, b.loc, b.lrank,
-                       b.ebase, b.lpt, b.eoff, b.X, b.e_kf, b.e_obs, b.e_xy, b.e_info, b.e_inl, b.res);
+    hipLaunchKernelGGL(k_ba_edges, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, m->kkps, p.sf, b.loc, b.lrank, b.ebase, b.lpt, b.eoff, b.X, b.e_kf, b.e_obs,
+                       b.e_xy, b.e_info, b.e_inl, b.res);
     hipLaunchKernelGGL(k_ba_cost, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, 0, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.poseC, b.pc, b.pn, b.res);
     hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(1024), 0, c->stream, 0, b.pc, b.pn, b.res);
     HIPCHK(c, hipGetLastError());
@@ -576,7 +565,7 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, r ? "ba_round1" : "ba_round0");
     }
-    hipLaunchKernelGGL(k_ba_write, dim3(wblocks), dim3(BA_BLOCK), 0, c->stream, p, (int)np, (int)no, b.loc, b.lrank, b.X, src.xyz,
+    hipLaunchKernelGGL(k_ba_write, dim3(wblocks), dim3(BA_BLOCK), 0, c->stream, p, (int)np, (int)no, b.loc, b.lrank, b.X, v.src.xyz,
                        out->points_out ? b.pout.p : nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.poseC, m->kP, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "ba_write");
@@ -586,9 +575,7 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     if (out->edge_inlier) HIPCHK(c, hipMemcpyAsync(out->edge_inlier, b.einl, no, hipMemcpyDeviceToHost, c->stream));
     if (out->points_out) HIPCHK(c, hipMemcpyAsync(out->points_out, b.pout, np * 24, hipMemcpyDeviceToHost, c->stream));
     if (out->kf_state) HIPCHK(c, hipMemcpyAsync(fidx.data(), b.kf_fidx, (size_t)n_kf * 4, hipMemcpyDeviceToHost, c->stream));
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     const BaRes& r = *b.h_res;
     if (!r.run) return MO_OK;   // no free keyframe with an edge, or no local point
     out->n_local = r.n_local;
@@ -611,16 +598,17 @@ __global__ __launch_bounds__(BA_BLOCK) void k_obs_claim(const int32_t* __restric
 }
 
 // one thread per point: a claimed point that has no valid observation in kf_pos yet gains one; cnt = its new observation count
-__global__ __launch_bounds__(BA_BLOCK) void k_obs_count(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                                        int kf_pos, int32_t* __restrict__ claim, int32_t* __restrict__ cnt) {
+__global__ __launch_bounds__(BA_BLOCK) void k_obs_count(MapView v, int kf_pos, int32_t* __restrict__ claim, int32_t* __restrict__ cnt) {
     const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
-    if (i >= n_pts) return;
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    int add = claim[i] != INT_MAX;
+    if (i >= v.n_pts) return;
+    const int o0 = v.src.off[i], o1 = v.src.off[i + 1];
+    bool add = claim[i] != INT_MAX;
     if (add) {
-        int pos, s, kp;
-        for (int o = o0; o < o1; o++)   // (the next keyframe's position names nothing yet: its entries are compared as stored)
-            if (kf_pos == n_kf ? src.okf[o] == kf_pos : (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp) && pos == kf_pos)) { add = 0; break; }
+        if (kf_pos == v.n_kf) {   // (the next keyframe's position names nothing yet: its entries are compared as stored)
+            for (int o = o0; o < o1 && add; o++) add = v.src.okf[o] != kf_pos;
+        } else {
+            add = !map_observes(v, i, kf_pos);
+        }
         if (!add) claim[i] = INT_MAX;
     }
     cnt[i] = o1 - o0 + add;
@@ -667,7 +655,7 @@ extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32
     const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned pblocks = (unsigned)((np + BA_BLOCK - 1) / BA_BLOCK);
     hipLaunchKernelGGL(k_obs_claim, dim3((unsigned)((n + BA_BLOCK - 1) / BA_BLOCK)), dim3(BA_BLOCK), 0, c->stream, b.ao_pt, n, (int)np, b.ao_claim);
-    hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, (int)np, m->d_pos_slot, n_kf, m->kcnt, kf_pos, b.ao_claim, b.ao_cnt);
+    hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, map_view(m), kf_pos, b.ao_claim, b.ao_cnt);
     HIPCHK(c, hipGetLastError());
     if ((rc = map_scan_excl(m, b.ao_cnt, b.ao_base, (int)np, b.ao_total))) return rc;
     hipLaunchKernelGGL(k_obs_scatter, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, dst, (int)np, b.ao_claim, b.ao_base, b.ao_total, kf_pos, b.ao_row, m->st);

@@ -38,38 +38,26 @@ struct CovisBufs {
 
 void map_scratch_free(CovisBufs* b) { delete b; }
 
-// observation o of a point whose list starts at o0 names a position no earlier observation of the list names
-__device__ __forceinline__ bool cv_first(const MapPts& src, int o0, int o, int pos, const int32_t* __restrict__ pos_slot, int n_kf,
-                                         const int32_t* __restrict__ kcnt) {
-    int p, s, kp;
-    for (int l = o0; l < o; l++)
-        if (!map_obs(src, l, pos_slot, n_kf, kcnt, &p, &s, &kp) && p == pos) return false;
-    return true;
-}
-
 __device__ __forceinline__ int cv_pop(unsigned long long& lo, unsigned long long& hi) {   // the lowest position of the set, removed
     if (lo) { const int p = __ffsll(lo) - 1; lo &= lo - 1; return p; }
     const int p = __ffsll(hi) - 1; hi &= hi - 1;
     return 64 + p;
 }
 
-template <bool LDS> __global__ __launch_bounds__(CV_BLOCK) void k_covis(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
-                                                                        const int32_t* __restrict__ kcnt, int32_t* __restrict__ W) {
+template <bool LDS> __global__ __launch_bounds__(CV_BLOCK) void k_covis(MapView v, int32_t* __restrict__ W) {
     extern __shared__ int32_t sW[];   // [n_kf][n_kf], cells p <= q used
-    const int cells = n_kf * n_kf;
+    const int n_kf = v.n_kf, cells = n_kf * n_kf;
     if (LDS) {
         for (int c = threadIdx.x; c < cells; c += CV_BLOCK) sW[c] = 0;
         __syncthreads();
     }
-    for (int i = blockIdx.x * CV_BLOCK + threadIdx.x; i < n_pts; i += gridDim.x * CV_BLOCK) {
-        const int o0 = src.off[i], o1 = src.off[i + 1];
-        int pa, pb, s, kp;
+    for (int i = blockIdx.x * CV_BLOCK + threadIdx.x; i < v.n_pts; i += gridDim.x * CV_BLOCK) {
         if (LDS) {
             unsigned long long lo = 0, hi = 0;   // the point's positions as a set: duplicates fold
-            for (int o = o0; o < o1; o++) {
-                if (map_obs(src, o, pos_slot, n_kf, kcnt, &pa, &s, &kp)) continue;
+            map_each_obs(v, i, [&](int, int pa, int, int) {
                 if (pa < 64) lo |= 1ull << pa; else hi |= 1ull << (pa - 64);
-            }
+                return false;
+            });
             while (lo | hi) {
                 const int p = cv_pop(lo, hi);
                 atomicAdd(sW + p * n_kf + p, 1);
@@ -77,15 +65,18 @@ template <bool LDS> __global__ __launch_bounds__(CV_BLOCK) void k_covis(MapPts s
                 while (l2 | h2) atomicAdd(sW + p * n_kf + cv_pop(l2, h2), 1);
             }
         } else {
-            for (int a = o0; a < o1; a++) {
-                if (map_obs(src, a, pos_slot, n_kf, kcnt, &pa, &s, &kp) || !cv_first(src, o0, a, pa, pos_slot, n_kf, kcnt)) continue;
+            const int o1 = v.src.off[i + 1];
+            map_each_obs(v, i, [&](int a, int pa, int, int) {
+                if (map_observes(v, i, pa, a)) return false;
                 atomicAdd(W + (size_t)pa * n_kf + pa, 1);
+                int pb, s, kp;
                 for (int b = a + 1; b < o1; b++) {   // (a first occurrence behind a: another position)
-                    if (map_obs(src, b, pos_slot, n_kf, kcnt, &pb, &s, &kp) || !cv_first(src, o0, b, pb, pos_slot, n_kf, kcnt)) continue;
+                    if (map_obs(v, b, &pb, &s, &kp) || map_observes(v, i, pb, b)) continue;
                     atomicAdd(W + (size_t)pa * n_kf + pb, 1);
                     atomicAdd(W + (size_t)pb * n_kf + pa, 1);
                 }
-            }
+                return false;
+            });
         }
     }
     if (LDS) {
@@ -102,23 +93,21 @@ template <bool LDS> __global__ __launch_bounds__(CV_BLOCK) void k_covis(MapPts s
 __device__ __forceinline__ int cv_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // one workgroup.  votes and loc arrive zeroed and are written by atomics and read by cv_load only (the atomics execute behind the L1)
-__global__ __launch_bounds__(CV_BLOCK) void k_covis_select(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
-                                                           const int32_t* __restrict__ kcnt, const int32_t* __restrict__ W,
-                                                           const int32_t* __restrict__ seeds, int n_seed, int ref_pos, int n_best, int min_w,
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_select(MapView v, const int32_t* __restrict__ W, const int32_t* __restrict__ seeds, int n_seed, int ref_pos, int n_best, int min_w,
                                                            int32_t* __restrict__ votes, int32_t* __restrict__ loc, uint8_t* __restrict__ mask,
                                                            CovisRes* __restrict__ res) {
     __shared__ unsigned long long top;
     __shared__ int cnt[2];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n_kf = v.n_kf;
     if (tid == 0) { top = 0; cnt[0] = 0; cnt[1] = 0; }
     __syncthreads();
     for (int e = tid; e < n_seed; e += CV_BLOCK) {
         const int i = seeds[e];
-        if (i < 0 || i >= n_pts) continue;
-        const int o0 = src.off[i], o1 = src.off[i + 1];
-        int p, s, kp;
-        for (int o = o0; o < o1; o++)
-            if (!map_obs(src, o, pos_slot, n_kf, kcnt, &p, &s, &kp) && cv_first(src, o0, o, p, pos_slot, n_kf, kcnt)) atomicAdd(votes + p, 1);
+        if (i < 0 || i >= v.n_pts) continue;
+        map_each_obs(v, i, [&](int o, int p, int, int) {   // (a vote per position: its first valid observation)
+            if (!map_observes(v, i, p, o)) atomicAdd(votes + p, 1);
+            return false;
+        });
     }
     __syncthreads();
     unsigned long long mine = 0;
@@ -180,22 +169,20 @@ int covis_check(mo_map* m, const mo_map_local_params* prm, const mo_map_local_ou
 int covis_enqueue(mo_map* m) {
     mo_ctx* c = m->c;
     const size_t n_kf = m->pos_slot.size();
-    if (n_kf * n_kf > (size_t)INT32_MAX || m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2)
-        return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    int rc;
+    if (n_kf * n_kf > (size_t)INT32_MAX) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
+    if ((rc = map_int32_guard(m))) return rc;
     if (!m->cv) m->cv = new CovisBufs();
     CovisBufs& b = *m->cv;
-    int rc;
     if ((rc = b.W.reserve(c, n_kf * n_kf))) return rc;
     HIPCHK(c, hipMemsetAsync(b.W, 0, n_kf * n_kf * 4, c->stream));
     if (m->n_pts > 0) {
         const unsigned blocks = (unsigned)std::min<int64_t>((m->n_pts + CV_BLOCK - 1) / CV_BLOCK, CV_MAX_BLOCKS);
-        const MapPts src = m->P[m->cur].view();
         if (n_kf <= CV_LDS_MAX_KF) {
             if ((rc = mo_raise_dyn_lds(c, (const void*)k_covis<true>, CV_LDS_MAX_BYTES))) return rc;
-            hipLaunchKernelGGL(k_covis<true>, dim3(blocks), dim3(CV_BLOCK), n_kf * n_kf * 4, c->stream, src, (int)m->n_pts, m->d_pos_slot, (int)n_kf,
-                               m->kcnt, b.W);
+            hipLaunchKernelGGL(k_covis<true>, dim3(blocks), dim3(CV_BLOCK), n_kf * n_kf * 4, c->stream, map_view(m), b.W);
         } else {
-            hipLaunchKernelGGL(k_covis<false>, dim3(blocks), dim3(CV_BLOCK), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, (int)n_kf, m->kcnt, b.W);
+            hipLaunchKernelGGL(k_covis<false>, dim3(blocks), dim3(CV_BLOCK), 0, c->stream, map_view(m), b.W);
         }
         HIPCHK(c, hipGetLastError());
     }
@@ -218,8 +205,7 @@ int covis_select_enqueue(mo_map* m, const mo_map_local_params* prm) {
     HIPCHK(c, hipMemsetAsync(b.votes, 0, n_kf * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(b.loc, 0, n_kf * 4, c->stream));
     const int ref_pos = prm->ref_pos < 0 ? (int)n_kf - 1 : prm->ref_pos;
-    hipLaunchKernelGGL(k_covis_select, dim3(1), dim3(CV_BLOCK), 0, c->stream, m->P[m->cur].view(), (int)m->n_pts, m->d_pos_slot, (int)n_kf, m->kcnt,
-                       b.W, b.seeds, (int)ns, ref_pos, prm->n_best, std::max(prm->min_weight, 1), b.votes, b.loc, b.mask, b.res);
+    hipLaunchKernelGGL(k_covis_select, dim3(1), dim3(CV_BLOCK), 0, c->stream, map_view(m), b.W, b.seeds, (int)ns, ref_pos, prm->n_best, std::max(prm->min_weight, 1), b.votes, b.loc, b.mask, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "covis_select");
     return MO_OK;
@@ -254,9 +240,7 @@ extern "C" int mo_map_covisibility(mo_map* m, int32_t* weights, int32_t* n_kf) {
     mo_stage_begin(c);
     if ((rc = covis_enqueue(m))) return rc;
     if (weights) HIPCHK(c, hipMemcpyAsync(weights, m->cv->W, n * n * 4, hipMemcpyDeviceToHost, c->stream));
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     return MO_OK;
 }
 
@@ -272,9 +256,7 @@ extern "C" int mo_map_local_keyframes(mo_map* m, const mo_map_local_params* prm,
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
     if ((rc = covis_enqueue(m)) || (rc = covis_select_enqueue(m, prm)) || (rc = covis_copy_enqueue(m, out))) return rc;
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     covis_finish(m, out);
     return MO_OK;
 }

@@ -32,7 +32,6 @@
 struct FusePrm {
     double radius, sf, chi2;
     int w, h, max_dist;
-    int lo_pos, n_targets, n_kf, row, n_pts;
 };
 
 struct FuseRes {
@@ -56,26 +55,19 @@ struct FuseBufs {
 
 void map_scratch_free(FuseBufs* b) { delete b; }
 
-// what the merge kernels read (by value)
+// what the fuse kernels read (by value): the map, and fuse's own tables and window
 struct FuseView {
-    MapPts src;
-    const int32_t* pos_slot; const int32_t* kcnt;
+    MapView map;
     const int32_t* prop; const unsigned long long* key; const int32_t* tab;
-    int n_kf, row, lo_pos, n_targets, n_pts;
+    int lo_pos, n_targets;
 };
 
 // one thread per point: valid observations counted, those at a target entered into point_of; tables of the later kernels reset
 __global__ __launch_bounds__(FU_BLOCK) void k_fuse_prep(FuseView v, int32_t* __restrict__ tab, int32_t* __restrict__ nval, int32_t* __restrict__ parent,
                                                          int32_t* __restrict__ mcnt, int32_t* __restrict__ mcur, unsigned long long* __restrict__ surv) {
     const int i = blockIdx.x * FU_BLOCK + threadIdx.x;
-    if (i >= v.n_pts) return;
-    int n = 0, pos, s, kp;
-    for (int o = v.src.off[i]; o < v.src.off[i + 1]; o++) {
-        if (map_obs(v.src, o, v.pos_slot, v.n_kf, v.kcnt, &pos, &s, &kp)) continue;
-        n++;
-        if (pos >= v.lo_pos) atomicMin(tab + (size_t)(pos - v.lo_pos) * v.row + kp, i);
-    }
-    nval[i] = n; parent[i] = i; mcnt[i] = 0; mcur[i] = 0; surv[i] = TK_NONE;
+    if (i >= v.map.n_pts) return;
+    nval[i] = map_point_of(v.map, i, v.lo_pos, tab); parent[i] = i; mcnt[i] = 0; mcur[i] = 0; surv[i] = TK_NONE;
 }
 
 // one thread per (point, target): the pair's proposal
@@ -84,60 +76,29 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FusePrm prm, FuseView 
                                                            const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
                                                            unsigned long long* __restrict__ key, int32_t* __restrict__ prop, FuseRes* __restrict__ res) {
     const int t = blockIdx.y, i = blockIdx.x * FU_BLOCK + threadIdx.x;
-    const int pos = prm.lo_pos + t, slot = v.pos_slot[pos];
-    const int ro = i < prm.n_pts ? oct[i] : TK_NOT_LOCAL;
-    bool pair = ro != TK_NOT_LOCAL, cand = false;
-    if (pair) {
-        int p, s, kp;
-        for (int o = v.src.off[i]; o < v.src.off[i + 1]; o++)
-            if (!map_obs(v.src, o, v.pos_slot, v.n_kf, v.kcnt, &p, &s, &kp) && p == pos) { pair = false; break; }
-    }
+    const MapView& mv = v.map;
+    const int pos = v.lo_pos + t, slot = mv.pos_slot[pos];
+    const int ro = i < mv.n_pts ? oct[i] : TK_NOT_LOCAL;
+    const bool pair = ro != TK_NOT_LOCAL && !map_observes(mv, i, pos);
     double uu = 0.0, vv = 0.0;
-    if (pair) {
-        const double* P = kP + (size_t)slot * 12;
-        const double X = v.src.xyz[(size_t)i * 3], Y = v.src.xyz[(size_t)i * 3 + 1], Z = v.src.xyz[(size_t)i * 3 + 2];
-        const double u = P[0] * X + P[1] * Y + P[2] * Z + P[3];
-        const double w = P[4] * X + P[5] * Y + P[6] * Z + P[7];
-        const double z = P[8] * X + P[9] * Y + P[10] * Z + P[11];
-        if (z > 0.0) {
-            uu = u / z; vv = w / z;
-            cand = uu >= 0.0 && uu < prm.w && vv >= 0.0 && vv < prm.h;
-        }
-    }
+    const bool cand = pair && trk_project(kP + (size_t)slot * 12, mv.src.xyz[(size_t)i * 3], mv.src.xyz[(size_t)i * 3 + 1], mv.src.xyz[(size_t)i * 3 + 2],
+                                          prm.w, prm.h, &uu, &vv);
     int bd = INT_MAX, bq = INT_MAX;
     if (cand) {
-        const double r = prm.radius * trk_scale(prm.sf, ro);
-        const int cx0 = trk_cx(uu - r, prm.w), cx1 = trk_cx(uu + r, prm.w), cy0 = trk_cy(vv - r, prm.h), cy1 = trk_cy(vv + r, prm.h);
-        const mo_keypoint* __restrict__ fk = kkps + (size_t)slot * prm.row;
-        const uint8_t* __restrict__ fdesc = kdesc + (size_t)slot * prm.row * 32;
-        const int32_t* __restrict__ cl = cell + (size_t)t * (TK_CELLS + 1);
-        const int32_t* __restrict__ so = sorted + (size_t)t * prm.row;
+        const uint8_t* __restrict__ fdesc = kdesc + (size_t)slot * mv.row * 32;
         const uint8_t* d = rep + (size_t)i * 32;
-        for (int cy = cy0; cy <= cy1; cy++)
-            for (int cx = cx0; cx <= cx1; cx++) {
-                const int c = cy * TK_GX + cx, e1 = cl[c + 1];
-                for (int e = cl[c]; e < e1; e++) {
-                    const int q = so[e];
-                    const mo_keypoint kp = fk[q];
-                    const double dx = (double)kp.x - uu, dy = (double)kp.y - vv;
-                    if (!(fabs(dx) < r && fabs(dy) < r)) continue;
-                    const long long dl = (long long)kp.octave - ro;
-                    if (dl < -1 || dl > 1) continue;
-                    if (!(ba_info(prm.sf, kp.octave) * (dx * dx + dy * dy) <= prm.chi2)) continue;
-                    const int dist = trk_ham(d, fdesc + (size_t)q * 32);
-                    if (dist < bd || (dist == bd && q < bq)) { bd = dist; bq = q; }
-                }
-            }
+        trk_window(uu, vv, prm.radius * trk_scale(prm.sf, ro), ro, prm.w, prm.h, cell + (size_t)t * (TK_CELLS + 1), sorted + (size_t)t * mv.row,
+                   kkps + (size_t)slot * mv.row, [&](int q, const mo_keypoint& kp, double dx, double dy) {
+                       if (!(ba_info(prm.sf, kp.octave) * (dx * dx + dy * dy) <= prm.chi2)) return;
+                       trk_take(trk_ham(d, fdesc + (size_t)q * 32), q, bd, bq);
+                   });
     }
     const bool acc = bd != INT_MAX && bd <= prm.max_dist;
-    if (acc) atomicMin(key + (size_t)t * prm.row + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
-    if (i < prm.n_pts) prop[(size_t)t * prm.n_pts + i] = acc ? bq : -1;
-    const unsigned long long bp = __ballot(pair), bc = __ballot(cand), ba = __ballot(acc);
-    if ((threadIdx.x & 63) == 0) {
-        if (bp) atomicAdd(&res->n_pairs, (int)__popcll(bp));
-        if (bc) atomicAdd(&res->n_cand, (int)__popcll(bc));
-        if (ba) atomicAdd(&res->n_proposals, (int)__popcll(ba));
-    }
+    if (acc) atomicMin(key + (size_t)t * mv.row + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+    if (i < mv.n_pts) prop[(size_t)t * mv.n_pts + i] = acc ? bq : -1;
+    wave_count_add(pair, &res->n_pairs);
+    wave_count_add(cand, &res->n_cand);
+    wave_count_add(acc, &res->n_proposals);
 }
 
 __device__ __forceinline__ int fuse_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -171,11 +132,8 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_resolve(int row, const int32_
             if (edge) fuse_unite(parent, (int)(k & 0xffffffffu), owner);
         }
     }
-    const unsigned long long bg = __ballot(gain), be = __ballot(edge);
-    if ((threadIdx.x & 63) == 0) {
-        if (bg) atomicAdd(&res->n_gained, (int)__popcll(bg));
-        if (be) atomicAdd(&res->n_edges, (int)__popcll(be));
-    }
+    wave_count_add(gain, &res->n_gained);
+    wave_count_add(edge, &res->n_edges);
 }
 
 __global__ __launch_bounds__(FU_BLOCK) void k_fuse_flatten(int n_pts, const int32_t* __restrict__ parent, const int32_t* __restrict__ nval,
@@ -202,9 +160,9 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_members(int n_pts, const int3
 
 // the gained observation of point j at target t: the row it proposed, won, and that no point owns
 __device__ __forceinline__ bool fuse_gained(const FuseView& v, int j, int t, int* r) {
-    const int pr = v.prop[(size_t)t * v.n_pts + j];
+    const int pr = v.prop[(size_t)t * v.map.n_pts + j];
     if (pr < 0) return false;
-    const size_t e = (size_t)t * v.row + pr;
+    const size_t e = (size_t)t * v.map.row + pr;
     if ((int)(v.key[e] & 0xffffffffu) != j || v.tab[e] != INT_MAX) return false;
     *r = pr;
     return true;
@@ -214,20 +172,14 @@ __device__ __forceinline__ bool fuse_gained(const FuseView& v, int j, int t, int
 // entries, (1) the valid entries of the other members, (2) the gained observations of all members by (member, position).
 // f(index, kind, position, row) -> true stops the walk.
 template <class F> __device__ __forceinline__ void fuse_walk(const FuseView& v, int s, const int32_t* __restrict__ mem, int nm, F f) {
-    int idx = 0, pos, sl, kp;
-    for (int o = v.src.off[s]; o < v.src.off[s + 1]; o++)
-        if (!map_obs(v.src, o, v.pos_slot, v.n_kf, v.kcnt, &pos, &sl, &kp) && f(idx++, 0, pos, kp)) return;
-    for (int a = 0; a < nm; a++) {
-        const int j = mem[a];
-        if (j == s) continue;
-        for (int o = v.src.off[j]; o < v.src.off[j + 1]; o++)
-            if (!map_obs(v.src, o, v.pos_slot, v.n_kf, v.kcnt, &pos, &sl, &kp) && f(idx++, 1, pos, kp)) return;
-    }
-    for (int a = 0; a < nm; a++) {
-        const int j = mem[a];
+    int idx = 0, kp;
+    bool stop = false;
+    map_each_obs(v.map, s, [&](int, int pos, int, int r) { return stop = f(idx++, 0, pos, r); });
+    for (int a = 0; a < nm && !stop; a++)
+        if (mem[a] != s) map_each_obs(v.map, mem[a], [&](int, int pos, int, int r) { return stop = f(idx++, 1, pos, r); });
+    for (int a = 0; a < nm && !stop; a++)
         for (int t = 0; t < v.n_targets; t++)
-            if (fuse_gained(v, j, t, &kp) && f(idx++, 2, v.lo_pos + t, kp)) return;
-    }
+            if (fuse_gained(v, mem[a], t, &kp) && f(idx++, 2, v.lo_pos + t, kp)) return;
 }
 
 // The merged list of survivor s behind its own entries: an entry of kinds 1 and 2 is kept when no earlier candidate stands at its
@@ -256,7 +208,7 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_count(FuseView v, const int32
     if (!res->n_proposals) return;
     const int i = blockIdx.x * FU_BLOCK + threadIdx.x;
     bool gone = false;
-    if (i < v.n_pts) {
+    if (i < v.map.n_pts) {
         const int r = root[i];
         const bool k = (int)(surv[r] & 0xffffffffu) == i;
         gone = !k;
@@ -264,18 +216,12 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_count(FuseView v, const int32
         if (k) {
             int32_t* run = mem + mbase[r];
             const int nm = mcnt[r];
-            for (int x = 1; x < nm; x++) {
-                const int q = run[x];
-                int y = x - 1;
-                while (y >= 0 && run[y] > q) { run[y + 1] = run[y]; y--; }
-                run[y + 1] = q;
-            }
-            n = v.src.off[i + 1] - v.src.off[i] + fuse_merge(v, i, run, nm, [](int, int) {});
+            sort_run(run, nm);
+            n = v.map.src.off[i + 1] - v.map.src.off[i] + fuse_merge(v, i, run, nm, [](int, int) {});
         }
         keep[i] = k; cnt[i] = n;
     }
-    const unsigned long long b = __ballot(gone);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&res->n_absorbed, (int)__popcll(b));
+    wave_count_add(gone, &res->n_absorbed);
 }
 
 // every field of every survivor to its new index, its own entries as stored, the merged entries behind them
@@ -286,11 +232,11 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_scatter(FuseView v, MapPts ds
     if (!res->n_proposals) return;
     const int i = blockIdx.x * FU_BLOCK + threadIdx.x;
     if (i == 0) { dst.off[res->n_points] = res->n_obs; st[ST_NPTS] = res->n_points; st[ST_NOBS] = res->n_obs; }   // (the next call's live counts)
-    if (i >= v.n_pts) return;
+    if (i >= v.map.n_pts) return;
     const int rt = root[i];
     into[i] = rank[(int)(surv[rt] & 0xffffffffu)];
     if (!keep[i]) return;
-    const MapPts& src = v.src;
+    const MapPts& src = v.map.src;
     const int r = rank[i], ob = obase[i];
     for (int k = 0; k < 3; k++) { dst.xyz[(size_t)r * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)r * 3 + k] = src.col[(size_t)i * 3 + k]; }
     dst.id[r] = src.id[i]; dst.dkf[r] = src.dkf[i]; dst.drow[r] = src.drow[i];
@@ -317,7 +263,7 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     if (out->into) for (int64_t i = 0; i < m->n_pts; i++) out->into[i] = (int32_t)i;
     const int n_kf = (int)m->pos_slot.size();
     if (n_kf == 0 || m->n_pts == 0) return MO_OK;   // (nothing to fuse: not an error)
-    const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
+    const int lo_pos = map_window_lo(prm->window, n_kf);
     const int nt = n_kf - lo_pos, row = m->row;
     if (nt > FU_MAX_TARGETS) return mo_fail(c, MO_ERR_UNSUPPORTED, "more target keyframes than one call searches (16384)");
     const size_t np = (size_t)m->n_pts;
@@ -343,17 +289,14 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     HIPCHK(c, hipMemsetAsync(b.res, 0, sizeof(FuseRes), c->stream));
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.tab.p, INT_MAX, trow, c->stream));
     HIPCHK(c, hipMemsetAsync(b.key, 0xff, trow * 8, c->stream));
-    const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
-    const FuseView v{src, m->d_pos_slot, m->kcnt, b.prop, b.key, b.tab, n_kf, row, lo_pos, nt, (int)np};
-    FusePrm p;
-    p.radius = prm->radius; p.sf = prm->scale_factor; p.chi2 = prm->chi2;
-    p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist;
-    p.lo_pos = lo_pos; p.n_targets = nt; p.n_kf = n_kf; p.row = row; p.n_pts = (int)np;
+    const MapPts dst = m->P[m->cur ^ 1].view();
+    const FuseView v{map_view(m), b.prop, b.key, b.tab, lo_pos, nt};
+    const FusePrm p{prm->radius, prm->scale_factor, prm->chi2, prm->w, prm->h, prm->max_dist};
     const unsigned pblocks = (unsigned)((np + FU_BLOCK - 1) / FU_BLOCK);
     const int32_t* slots = m->d_pos_slot + lo_pos;
     hipLaunchKernelGGL(k_fuse_prep, dim3(pblocks), dim3(FU_BLOCK), 0, c->stream, v, b.tab, b.nval, b.parent, b.mcnt, b.mcur, b.surv);
     HIPCHK(c, hipGetLastError());
-    if ((rc = trk_launch_rep(m, src, lo_pos, b.rep, b.oct, &b.res.p->n_local)) || (rc = trk_launch_grid(m, slots, 0, nt, prm->w, prm->h, b.cell, b.sorted)))
+    if ((rc = trk_launch_rep(m, lo_pos, b.rep, b.oct, &b.res.p->n_local)) || (rc = trk_launch_grid(m, slots, 0, nt, prm->w, prm->h, b.cell, b.sorted)))
         return rc;
     mo_stage_mark(c, "fuse_prep");
     hipLaunchKernelGGL(k_fuse_search, dim3(pblocks, (unsigned)nt), dim3(FU_BLOCK), 0, c->stream, p, v, m->kkps, m->kdesc, m->kP, b.rep, b.oct, b.cell, b.sorted,
@@ -380,9 +323,7 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
         into.resize(np);
         HIPCHK(c, hipMemcpyAsync(into.data(), b.into, np * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     const FuseRes& r = *b.h_res;
     out->n_targets = nt; out->n_local = r.n_local; out->n_pairs = r.n_pairs; out->n_cand = r.n_cand;
     if (!r.n_proposals) return MO_OK;   // (nothing was written)

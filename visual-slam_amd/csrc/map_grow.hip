@@ -5,7 +5,7 @@
 //
 // Chain (one synchronisation, the copy-out, into pinned buffers like the upload; the pair geometry - F, epipole, poses per neighbour -
 // is formed on the host from the poses the caller passes and uploaded before the first kernel; every kernel behind k_grow_free reads n_free first, the append n_new):
-//   k_grow_prep     one thread per point: the owners of the rows of the target and the neighbours (atomicMin into point_of)
+//   k_point_of      one thread per point: the owners of the rows of the target and the neighbours (map_launch_point_of, map_kernels.hip)
 //   k_grow_free     one block: the free rows of the target next to each other, in row order (block scan)
 //   k_grow_search   one wave per (tile of 64 free target rows, neighbour): the neighbour's free keypoints staged in LDS (x, y and the two
 //                   octave-scaled thresholds, in tiles of GR_TILE rows), each lane's epipolar line in registers against the tile;
@@ -76,10 +76,7 @@ void map_scratch_free(GrowBufs* b) { delete b; }
 // ---- host: the geometry of the pairs, in the header's operation order ---------------------------------------------------------------
 static GrowCam grow_cam(const double* T, int slot, int pos) {
     GrowCam c;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) c.R[i * 3 + j] = T[i * 4 + j];
-        c.t[i] = T[i * 4 + 3];
-    }
+    pose_split(T, c.R, c.t);
     for (int i = 0; i < 3; i++) c.C[i] = -(c.R[i] * c.t[0] + c.R[3 + i] * c.t[1] + c.R[6 + i] * c.t[2]);
     c.slot = slot; c.pos = pos;
     return c;
@@ -114,18 +111,6 @@ static void grow_pair(const GrowPrm& p, GrowPair* q) {
 }
 
 // ---- device ---------------------------------------------------------------------------------------------------------------------------
-// one thread per point: its valid observations at the target and the neighbours entered into point_of
-__global__ __launch_bounds__(GR_BLOCK) void k_grow_prep(MapPts src, const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int n_kf, int row,
-                                                         int lo_pos, int n_pts, int32_t* __restrict__ tab) {
-    const int i = blockIdx.x * GR_BLOCK + threadIdx.x;
-    if (i >= n_pts) return;
-    int pos, s, kp;
-    for (int o = src.off[i]; o < src.off[i + 1]; o++) {
-        if (map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) continue;
-        if (pos >= lo_pos) atomicMin(tab + (size_t)(pos - lo_pos) * row + kp, i);
-    }
-}
-
 // one block: the free rows of the target in row order
 __global__ __launch_bounds__(1024) void k_grow_free(const int32_t* __restrict__ ttab, int n_rows, int32_t* __restrict__ frow, GrowRes* __restrict__ res) {
     __shared__ int lw[40];
@@ -193,7 +178,7 @@ __global__ __launch_bounds__(GR_WAVE) void k_grow_search(GrowPrm prm, const Grow
                 n_epi++;
                 const int q = lrow[j];
                 const int dist = trk_ham(dsc1, d2 + (size_t)q * 32);
-                if (dist < bd || (dist == bd && q < bq)) { bd = dist; bq = q; }
+                trk_take(dist, q, bd, bq);
             }
         __syncthreads();
     }
@@ -201,11 +186,8 @@ __global__ __launch_bounds__(GR_WAVE) void k_grow_search(GrowPrm prm, const Grow
     if (acc) atomicMin(key + (size_t)nb * prm.row + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)row1);
     if (live) prop[(size_t)nb * prm.row + f] = acc ? bq : -1;
     for (int o = 32; o; o >>= 1) n_epi += __shfl_down(n_epi, o, 64);
-    const unsigned long long ba = __ballot(acc);
-    if (threadIdx.x == 0) {
-        if (n_epi) atomicAdd(&res->n_epi, n_epi);
-        if (ba) atomicAdd(&res->n_accepted, (int)__popcll(ba));
-    }
+    if (threadIdx.x == 0 && n_epi) atomicAdd(&res->n_epi, n_epi);
+    wave_count_add(acc, &res->n_accepted);
 }
 
 __device__ __forceinline__ void grow_cam_point(const GrowCam& c, const double* X, double* Xc) {
@@ -328,7 +310,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_grow_points(GrowPrm prm, const Gro
             isnew[f] = 1; nobs[f] = kept;
         }
     }
-    for (int o = 32; o; o >>= 1) won += __shfl_down(won, o, 64);
+    won = wave_sum_int(won);
     if ((threadIdx.x & 63) == 0 && won) atomicAdd(&res->n_matches, won);
 }
 
@@ -387,7 +369,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     if (n_kf < 2) return MO_OK;   // (no neighbour: not an error)
     if (!poses) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     const int T = n_kf - 1;
-    const int lo_pos = prm->window > 0 && prm->window < T ? T - prm->window : 0;
+    const int lo_pos = map_window_lo(prm->window, T);
     const int nb = T - lo_pos, row = m->row;
     out->n_neighbours = nb;
     if (n_rows == 0) return MO_OK;
@@ -422,12 +404,10 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     mo_stage_begin(c);
     HIPCHK(c, hipMemcpyAsync(b.pairs, b.h_pairs.p, (size_t)nb * sizeof(GrowPair), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(b.res, 0, sizeof(GrowRes), c->stream));
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.tab.p, INT_MAX, trow, c->stream));
     HIPCHK(c, hipMemsetAsync(b.key, 0xff, nrow * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(b.point, 0xff, (size_t)row * 4, c->stream));
     const MapPts dst = m->P[m->cur].view();
-    if (np) hipLaunchKernelGGL(k_grow_prep, dim3((unsigned)((np + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, c->stream, dst, m->d_pos_slot, m->kcnt, n_kf, row,
-                               lo_pos, (int)np, b.tab);
+    if ((rc = map_launch_point_of(m, lo_pos, nb + 1, b.tab))) return rc;
     hipLaunchKernelGGL(k_grow_free, dim3(1), dim3(1024), 0, c->stream, b.tab + nrow, n_rows, b.frow, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "grow_prep");
@@ -453,9 +433,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     if (out->points) {
         HIPCHK(c, hipMemcpyAsync(b.h_X.p, b.outX, (size_t)n_rows * 24, hipMemcpyDeviceToHost, c->stream));
     }
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     const GrowRes& r = *b.h_res;
     out->n_free = r.n_free; out->n_epi = (int64_t)r.n_epi; out->n_accepted = r.n_accepted; out->n_matches = r.n_matches;
     if (!r.n_new) return MO_OK;   // (nothing was written)

@@ -123,11 +123,12 @@ __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__
 }
 
 // ---- cull (local_mapper.py:207-240): one thread per point, observations in insertion order --------------------------------------
-__global__ __launch_bounds__(256) void k_map_cull(MapPts src, int bound, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                                  const mo_keypoint* __restrict__ kkps, int row, const double* __restrict__ kP, int min_obs,
+// (for `bound` points at most, the live count in st: mv.n_pts is the map before the growth step and is not read)
+__global__ __launch_bounds__(256) void k_map_cull(MapView mv, int bound, const mo_keypoint* __restrict__ kkps, const double* __restrict__ kP, int min_obs,
                                                   int32_t* __restrict__ keep, int32_t* __restrict__ kobs, int32_t* __restrict__ st) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= bound) return;
+    const MapPts& src = mv.src;
     const int n = st[ST_NPTS];
     int k = 0;
     int nob = 0;
@@ -139,13 +140,13 @@ __global__ __launch_bounds__(256) void k_map_cull(MapPts src, int bound, const i
             const double X = src.xyz[(size_t)i * 3], Y = src.xyz[(size_t)i * 3 + 1], Z = src.xyz[(size_t)i * 3 + 2];
             for (int o = o0; o < o1; o++) {
                 int pos, s, kp;
-                const int bad = map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp);
+                const int bad = map_obs(mv, o, &pos, &s, &kp);
                 if (bad) { atomicOr(st + ST_ERR, bad); k = 0; break; }   // bit 1: keyframe, bit 2: keypoint
                 const double* P = kP + (size_t)s * 12;
                 const double u = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P[0], X), __dmul_rn(P[1], Y)), __dmul_rn(P[2], Z)), P[3]);
                 const double v = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P[4], X), __dmul_rn(P[5], Y)), __dmul_rn(P[6], Z)), P[7]);
                 const double z = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P[8], X), __dmul_rn(P[9], Y)), __dmul_rn(P[10], Z)), P[11]);
-                const mo_keypoint kq = kkps[(size_t)s * row + kp];
+                const mo_keypoint kq = kkps[(size_t)s * mv.row + kp];
                 const double du = u / z - (double)kq.x, dv = v / z - (double)kq.y;
                 const double err = sqrt(__dadd_rn(__dmul_rn(du, du), __dmul_rn(dv, dv)));
                 if (err > 5.0) { k = 0; break; }
@@ -266,7 +267,21 @@ __global__ __launch_bounds__(256) void k_kf_redundant(const int32_t* __restrict_
     }
 }
 
+// ---- point_of (map_store.h's map_point_of): one thread per point; relocalization over every position, growth over its window ----
+__global__ __launch_bounds__(256) void k_point_of(MapView v, int lo_pos, int32_t* __restrict__ tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < v.n_pts) map_point_of(v, i, lo_pos, tab);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
+int map_launch_point_of(mo_map* m, int lo_pos, int n_tab_kf, int32_t* tab) {
+    mo_ctx* c = m->c;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)tab, INT_MAX, (size_t)n_tab_kf * m->row, c->stream));
+    if (m->n_pts > 0) hipLaunchKernelGGL(k_point_of, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, map_view(m), lo_pos, tab);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
 int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) {
     mo_ctx* c = m->c;
     MapPtsStore& p = m->P[which];
@@ -372,8 +387,7 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     if ((rc = upload_pos_slot(m))) return rc;
     const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned gp = (unsigned)((bp + 255) / 256);
-    hipLaunchKernelGGL(k_map_cull, dim3(gp), dim3(256), 0, c->stream, src, bp, m->d_pos_slot, n_kf, m->kcnt, m->kkps, m->row, m->kP, 2,
-                       m->keep, m->kobs, m->st);
+    hipLaunchKernelGGL(k_map_cull, dim3(gp), dim3(256), 0, c->stream, map_view(m), bp, m->kkps, m->kP, 2, m->keep, m->kobs, m->st);
     HIPCHK(c, hipGetLastError());
     if ((rc = map_scan_excl(m, m->keep, m->rank, bp, m->st + ST_KEPT))) return rc;
     if ((rc = map_scan_excl(m, m->kobs, m->obase, bp, m->st + ST_KOBS))) return rc;
@@ -527,9 +541,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
         if (out->points) HIPCHK(c, hipMemcpyAsync(out->points, m->gpts, (size_t)nq * 12, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(out->F, m->F, 72, hipMemcpyDeviceToHost, c->stream));
     }
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     out->n_new = m->h_stat[ST_NNEW] * (bound_new ? 1 : 0);
     HIPCHK(c, hipMemsetAsync(m->st + ST_NNEW, 0, 4, c->stream));
     if (cull && (rc = finish_chain(m, n_kf, out->kf_len, out->kf_redundant))) return rc;

@@ -32,7 +32,7 @@ struct RelocGeom {
 };
 
 struct RelocBufs {
-    DevBuf<int32_t> tab;                      // point_of [slot][row]
+    DevBuf<int32_t> tab;                      // point_of [position][row] (map_launch_point_of)
     DevBuf<int32_t> qf;                       // [n_kf] query frame of every pair: the spare slot
     DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass;   // [pair][row] matcher outputs (a pair per keyframe, or per preselected keyframe)
     DevBuf<int32_t> score;                    // [n_kf] |C_k|
@@ -43,43 +43,31 @@ struct RelocBufs {
 
 void map_scratch_free(RelocBufs* b) { delete b; }
 
-// point_of[slot][row] = lowest map point whose observations hold (position, row); observations naming nothing are skipped
-__global__ __launch_bounds__(256) void k_reloc_point_of(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
-                                                        const int32_t* __restrict__ kcnt, int row, int32_t* __restrict__ tab) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pts) return;
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    int pos, s, kp;
-    for (int o = o0; o < o1; o++)
-        if (!map_obs(src, o, pos_slot, n_kf, kcnt, &pos, &s, &kp)) atomicMin(tab + (size_t)s * row + kp, i);
-}
-
 // the row of the matcher outputs that holds keyframe position k: k itself when every keyframe was matched (mrow NULL), else the pair the
 // preselection gave it, -1: not matched
 __device__ __forceinline__ int reloc_mrow(const int32_t* __restrict__ mrow, int k) { return mrow ? mrow[k] : k; }
 
-// the map point of query q against the keyframe in slot s matched in row mr (-1: none): the ratio-test survivor's best neighbour through point_of
-__device__ __forceinline__ int reloc_point(int mr, int s, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
+// the map point of query q against the keyframe at position k matched in row mr (-1: none): the ratio-test survivor's best neighbour through point_of
+__device__ __forceinline__ int reloc_point(int mr, int k, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
                                            const int32_t* __restrict__ tab) {
     if (mr < 0) return -1;
     const size_t o = (size_t)mr * row + q;
     if (!mpass[o]) return -1;
     const int t = midx[2 * o];
     if (t < 0) return -1;
-    const int p = tab[(size_t)s * row + t];
+    const int p = tab[(size_t)k * row + t];
     return p == INT_MAX ? -1 : p;
 }
 
 // |C_k|, one block per keyframe position
-__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                     const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
-                                                     const int32_t* __restrict__ tab, const int32_t* __restrict__ mrow, int32_t* __restrict__ score) {
+__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx,
+                                                     const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab, const int32_t* __restrict__ mrow, int32_t* __restrict__ score) {
     __shared__ int lw[4];
-    const int k = blockIdx.x, s = pos_slot[k], mr = reloc_mrow(mrow, k);
+    const int k = blockIdx.x, mr = reloc_mrow(mrow, k);
     const int nq = min(kcnt[spare], row);
     int n = 0;
-    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(mr, s, q, row, midx, mpass, tab) >= 0;
-    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(mr, k, q, row, midx, mpass, tab) >= 0;
+    n = wave_sum_int(n);
     if ((threadIdx.x & 63) == 0) lw[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) score[k] = lw[0] + lw[1] + lw[2] + lw[3];
@@ -120,17 +108,16 @@ __global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ 
 }
 
 // C_k of candidate blockIdx.x in query order (block scans, no atomics)
-__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                       const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
+__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
                                                        const int32_t* __restrict__ mrow, RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
     __shared__ int lw[40];
     const int c = blockIdx.x, k = res->cand[c];
     if (k < 0) return;
-    const int s = pos_slot[k], nq = min(kcnt[spare], row), mr = reloc_mrow(mrow, k);
+    const int nq = min(kcnt[spare], row), mr = reloc_mrow(mrow, k);
     int added = 0;
     for (int b = 0; b < nq; b += 1024) {
         const int q = b + threadIdx.x;
-        const int p = q < nq ? reloc_point(mr, s, q, row, midx, mpass, tab) : -1;
+        const int p = q < nq ? reloc_point(mr, k, q, row, midx, mpass, tab) : -1;
         int tot;
         const int r = block_excl_scan(p >= 0 ? 1 : 0, lw, &tot);
         if (p >= 0) { cq[(size_t)c * row + added + r] = q; cp[(size_t)c * row + added + r] = p; }
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(64 * RL_HYP_WAVES) void k_reloc_hyp(RelocGeom g, co
             double e2;
             n += pnp_reproj2(P, xyz[(size_t)pj * 3], xyz[(size_t)pj * 3 + 1], xyz[(size_t)pj * 3 + 2], kp.x, kp.y, &e2) && e2 < g.thr2;
         }
-        for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+        n = wave_sum_int(n);
         const unsigned long long key = ((unsigned long long)(unsigned)n << 32) | (0xffffffffu - (unsigned)(h * 4 + r));
         if (n > 0 && key > best) best = key;
     }
@@ -201,8 +188,7 @@ __device__ __forceinline__ int reloc_select(const RelocGeom& g, const double* R,
         fl[j] = in;
         n += in;
     }
-    for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
-    return n;
+    return wave_sum_int(n);
 }
 
 // one wave per candidate: the best hypothesis' pose, (Gauss-Newton over its inliers, re-selection) twice
@@ -252,8 +238,7 @@ __global__ __launch_bounds__(64) void k_reloc_refine(RelocGeom g, const float* _
 }
 
 // the winner (most final inliers, ties to the lower position) and its per-query-keypoint map point and inlier flag
-__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ kcnt, int spare, int row,
-                                                      const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
+__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
                                                       const int32_t* __restrict__ mrow, const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
                                                       int32_t* __restrict__ qpt, uint8_t* __restrict__ qinl) {
     __shared__ int win;
@@ -265,10 +250,10 @@ __global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict_
         res->win = w;
     }
     __syncthreads();
-    const int w = win, k = w >= 0 ? res->cand[w] : -1, s = k >= 0 ? pos_slot[k] : 0, mr = k >= 0 ? reloc_mrow(mrow, k) : -1;
+    const int w = win, k = w >= 0 ? res->cand[w] : -1, mr = k >= 0 ? reloc_mrow(mrow, k) : -1;
     const int nq = min(kcnt[spare], row);
     for (int q = threadIdx.x; q < nq; q += 256) {
-        qpt[q] = reloc_point(mr, s, q, row, midx, mpass, tab);
+        qpt[q] = reloc_point(mr, k, q, row, midx, mpass, tab);
         qinl[q] = 0;
     }
     __syncthreads();
@@ -326,29 +311,25 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if (pre && (rc = bow_select_enqueue(m, n, n_pre, &sel))) return rc;
     if (!m->rl) m->rl = new RelocBufs();
     RelocBufs& b = *m->rl;
-    const size_t tab_n = (size_t)m->n_slots * row, pair_n = (size_t)n_pairs * row, cand_n = (size_t)nc * row;
+    const size_t tab_n = (size_t)n_kf * row, pair_n = (size_t)n_pairs * row, cand_n = (size_t)nc * row;
     if ((rc = b.tab.reserve(c, tab_n)) || (rc = b.qf.reserve(c, (size_t)n_kf)) || (rc = b.midx.reserve(c, pair_n * 2)) ||
         (rc = b.mdist.reserve(c, pair_n * 2)) || (rc = b.mpass.reserve(c, pair_n)) || (rc = b.score.reserve(c, (size_t)n_kf)) ||
         (rc = b.cq.reserve(c, cand_n)) || (rc = b.cp.reserve(c, cand_n)) || (rc = b.cinl.reserve(c, cand_n)) ||
         (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
         return rc;
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.tab, INT_MAX, tab_n, c->stream));
     if (!pre) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.qf, spare, (size_t)n_kf, c->stream));
     const MapPts src = m->P[m->cur].view();
-    if (m->n_pts > 0)
-        hipLaunchKernelGGL(k_reloc_point_of, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot, n_kf,
-                           m->kcnt, row, b.tab);
-    HIPCHK(c, hipGetLastError());
+    if ((rc = map_launch_point_of(m, 0, n_kf, b.tab))) return rc;
     mo_stage_mark(c, "reloc_point_of");
     if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, pre ? sel.cnt : (const int32_t*)m->kcnt,
                                  pre ? sel.qf : (const int32_t*)b.qf, pre ? sel.tf : (const int32_t*)m->d_pos_slot, 0, 0, n_pairs, row, prm->ratio,
                                  b.midx, b.mdist, b.mpass)))
         return rc;
     mo_stage_mark(c, "reloc_match");
-    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.score);
+    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.score);
     hipLaunchKernelGGL(k_reloc_rank, dim3(1), dim3(256), 0, c->stream, b.score, n_kf, nc, b.res);
-    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab,
-                       sel.mrow, b.res, b.cq, b.cp);
+    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.res, b.cq,
+                       b.cp);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_candidates");
     hipLaunchKernelGGL(k_reloc_hyp, dim3((unsigned)((prm->n_hyp + RL_HYP_WAVES - 1) / RL_HYP_WAVES), nc), dim3(64 * RL_HYP_WAVES), 0, c->stream, g, src.xyz, qk,
@@ -356,16 +337,14 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_p3p");
     hipLaunchKernelGGL(k_reloc_refine, dim3(nc), dim3(64), 0, c->stream, g, src.xyz, qk, row, prm->seed, b.cq, b.cp, b.cinl, b.res);
-    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->d_pos_slot, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.cq,
-                       b.cinl, b.res, b.qpt, b.qinl);
+    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.cq, b.cinl, b.res,
+                       b.qpt, b.qinl);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_refine");
     HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(RelocRes), hipMemcpyDeviceToHost, c->stream));
     if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     const RelocRes& r = *b.h_res;
     out->n_cand = r.n_cand;
     for (int i = 0; i < r.n_cand; i++) {

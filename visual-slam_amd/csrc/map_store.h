@@ -1,6 +1,14 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition) and map_io.hip (PLY text).  Here: the stores (their owning buffer types DevBuf / PinnedBuf are common.h's), the one reader of an observation, the helpers every map kernel file shares.
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition) and map_io.hip (PLY text).
+// Here, in this order:
+//   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's) and mo_map;
+//   MapView / map_view: the live map as every kernel receives it (by value);
+//   map_obs: the one reader of an observation; map_each_obs / map_observes: the walks over a point's valid observations;
+//   map_point_of: the one rule of the point_of tables (k_point_of / map_launch_point_of in map_kernels.hip, k_fuse_prep);
+//   wave_sum / wave_sum_all (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
+//   host helpers: map_window_lo, map_int32_guard, map_sync, map_stage_frame.
+// A new reader of the map takes a MapView and these; it does not spell out the stores or restate a rule.
 // Private to the library.
 #pragma once
 #include <algorithm>
@@ -85,23 +93,59 @@ struct mo_map {
     ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); }
 };
 
+// ---- the live map as the kernels receive it (by value): the live copy of the store, the uploaded position table, the keyframe counts
+struct MapView {
+    MapPts src;
+    const int32_t* pos_slot; const int32_t* kcnt;
+    int n_kf, row, n_pts;
+};
+inline MapView map_view(const mo_map* m) {
+    return MapView{m->P[m->cur].view(), m->d_pos_slot, m->kcnt, (int)m->pos_slot.size(), m->row, (int)m->n_pts};
+}
+
 // ---- the one reader of an observation -----------------------------------------------------------------------------------------------
 // Observation o of a map names keyframe position okf[o] and row okp[o] of that keyframe; negative values index from the end (Python
 // indexing); anything out of range names nothing.  Returns OBS_OK with the position, the keyframe's slot and the row, else which
 // index was out of range (the values are the cull's ST_ERR bits; every other caller skips the observation).
 enum { OBS_OK = 0, OBS_BAD_KF = 1, OBS_BAD_KP = 2 };
-__device__ __forceinline__ int map_obs(const MapPts& src, int o, const int32_t* __restrict__ pos_slot, int n_kf, const int32_t* __restrict__ kcnt,
-                                       int* pos, int* slot, int* kp) {
-    int kf = src.okf[o];
-    if (kf < 0) kf += n_kf;
-    if (kf < 0 || kf >= n_kf) return OBS_BAD_KF;
-    const int s = pos_slot[kf];
-    int r = src.okp[o];
-    const int nk = kcnt[s];
+__device__ __forceinline__ int map_obs(const MapView& v, int o, int* pos, int* slot, int* kp) {
+    int kf = v.src.okf[o];
+    if (kf < 0) kf += v.n_kf;
+    if (kf < 0 || kf >= v.n_kf) return OBS_BAD_KF;
+    const int s = v.pos_slot[kf];
+    int r = v.src.okp[o];
+    const int nk = v.kcnt[s];
     if (r < 0) r += nk;
     if (r < 0 || r >= nk) return OBS_BAD_KP;
     *pos = kf; *slot = s; *kp = r;
     return OBS_OK;
+}
+
+// f(o, pos, slot, kp) -> bool for every valid observation of point i, in stored order; true stops the walk
+template <class F> __device__ __forceinline__ void map_each_obs(const MapView& v, int i, F f) {
+    int pos, slot, kp;
+    for (int o = v.src.off[i], o1 = v.src.off[i + 1]; o < o1; o++)
+        if (!map_obs(v, o, &pos, &slot, &kp) && f(o, pos, slot, kp)) return;
+}
+
+// a valid observation of point i in front of entry o_end (-1: any of them) names position pos
+__device__ __forceinline__ bool map_observes(const MapView& v, int i, int pos, int o_end = -1) {
+    int p, slot, kp;
+    for (int o = v.src.off[i], o1 = o_end < 0 ? v.src.off[i + 1] : o_end; o < o1; o++)
+        if (!map_obs(v, o, &p, &slot, &kp) && p == pos) return true;
+    return false;
+}
+
+// point_of: tab [position - lo_pos][row] (preset to INT_MAX) = the lowest point with a valid observation of (position, row), for the
+// positions >= lo_pos.  Point i's part of it; returns the number of its valid observations.
+__device__ __forceinline__ int map_point_of(const MapView& v, int i, int lo_pos, int32_t* __restrict__ tab) {
+    int n = 0;
+    map_each_obs(v, i, [&](int, int pos, int, int kp) {
+        n++;
+        if (pos >= lo_pos) atomicMin(tab + (size_t)(pos - lo_pos) * v.row + kp, i);
+        return false;
+    });
+    return n;
 }
 
 // ---- fixed-order f64 wave sum: lane 0's shuffle tree, the same on every run; lane 0 holds the sum, wave_sum_all gives it to every lane
@@ -110,6 +154,34 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 __device__ __forceinline__ double wave_sum_all(double v) { return __shfl(wave_sum(v), 0, 64); }
+
+// ---- integer wave sum (every lane receives it) and the counter idiom: the wave's set flags added to *counter by lane 0, one atomic
+__device__ __forceinline__ int wave_sum_int(int v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ void wave_count_add(bool flag, int32_t* counter) {
+    const unsigned long long b = __ballot(flag);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(counter, (int)__popcll(b));
+}
+
+// ---- a short run sorted ascending in place (insertion sort: the runs are a grid cell's keypoints, a component's members)
+__device__ __forceinline__ void sort_run(int32_t* run, int n) {
+    for (int x = 1; x < n; x++) {
+        const int q = run[x];
+        int y = x - 1;
+        while (y >= 0 && run[y] > q) { run[y + 1] = run[y]; y--; }
+        run[y + 1] = q;
+    }
+}
+
+// ---- [R | t] as 3 x 4 row-major -> R [9], t [3]
+__host__ __device__ inline void pose_split(const double* pose12, double* R, double* t) {
+    for (int j = 0; j < 3; j++) {
+        for (int l = 0; l < 3; l++) R[j * 3 + l] = pose12[j * 4 + l];
+        t[j] = pose12[j * 4 + 3];
+    }
+}
 
 // ---- block scans (one-block exclusive scan of int32 in thread order, used by the device-wide scan and the compactions)
 __device__ __forceinline__ int wave_incl_scan(int v) {
@@ -149,6 +221,24 @@ int upload_pos_slot(mo_map* m);
 // the device-wide exclusive scan of int32 (total into *d_total) and the growth of one copy of the map store
 int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_total);
 int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
+// point_of of the live map for the positions lo_pos .. lo_pos + n_tab_kf - 1 into tab [n_tab_kf][row]: the INT_MAX fill and k_point_of,
+// enqueued (the position table uploaded by the caller)
+int map_launch_point_of(mo_map* m, int lo_pos, int n_tab_kf, int32_t* tab);
+
+// ---- host helpers of the calls ---------------------------------------------------------------------------------------------------
+// the first position of a window of the last `window` keyframes (0: all of them)
+inline int map_window_lo(int window, int n_kf) { return window > 0 && window < n_kf ? n_kf - window : 0; }
+// points and observations stay below half of int32 (sums of two of them are formed in int)
+inline int map_int32_guard(mo_map* m) {
+    return m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2 ? mo_fail(m->c, MO_ERR_CAPACITY, "map larger than int32 indexing") : MO_OK;
+}
+// the end of a call's chain: everything is enqueued, the one synchronisation
+inline int map_sync(mo_ctx* c, HostClock& clk) {
+    clk.enqueued();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    clk.waited();
+    return MO_OK;
+}
 
 // ---- map_covis.hip -----------------------------------------------------------------------------------------------------------------
 // The pieces of mo_map_local_keyframes, for a caller that runs them inside a chain of its own (mo_map_track_covisible): the argument
@@ -175,8 +265,7 @@ template <class Defaults> int map_stage_frame(mo_map* m, const mo_frame_ref* f, 
     *from_token = rs >= 0;
     defaults(*n);
     if (*n == 0 || m->pos_slot.empty() || (need_points && m->n_pts == 0)) return MO_OK;
-    if (m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    if ((rc = kf_reserve(m, *n, m->n_slots)) || (rc = upload_pos_slot(m))) return rc;
+    if ((rc = map_int32_guard(m)) || (rc = kf_reserve(m, *n, m->n_slots)) || (rc = upload_pos_slot(m))) return rc;
     const size_t at = (size_t)m->kslots * m->row;
     mo_stage_begin(c);
     if ((rc = mo_frame_copy_rows(c, f, rs, *n, m->kkps + at, m->kdesc + at * 32))) return rc;

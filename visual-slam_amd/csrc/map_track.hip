@@ -21,7 +21,7 @@
 
 #include "common.h"
 #include "map_store.h"
-#include "map_search.h"   // the grid geometry, trk_ham / trk_cx / trk_cy / trk_scale, the launchers mo_map_fuse shares
+#include "map_search.h"   // the grid geometry, the projected-window search, the launchers mo_map_fuse shares
 #include "ba.h"           // ba_info (pnp.h comes with it)
 
 #define TK_GRID_BLOCK 1024
@@ -88,18 +88,17 @@ __global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes*
 // MASK a position whose byte of lmask is not zero.  The
 // representative is ComputeDistinctiveDescriptors' choice: the observation with the smallest median distance to all of them, ties to
 // the earlier.  Each median is found by bisection on the distance value (count of distances <= v), only below the best so far.
-template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapPts src, int n_pts, const int32_t* __restrict__ pos_slot, int n_kf,
-                                                                      const int32_t* __restrict__ kcnt, int row, const mo_keypoint* __restrict__ kkps,
-                                                                      const uint8_t* __restrict__ kdesc, int lo_pos, const uint8_t* __restrict__ lmask,
-                                                                      uint8_t* __restrict__ rep, int32_t* __restrict__ oct, int32_t* __restrict__ n_local) {
+template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapView v, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc,
+                                                                      int lo_pos, const uint8_t* __restrict__ lmask, uint8_t* __restrict__ rep,
+                                                                      int32_t* __restrict__ oct, int32_t* __restrict__ n_local) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool local = false;
-    if (i < n_pts) {
-        const int o0 = src.off[i], o1 = src.off[i + 1];
+    if (i < v.n_pts) {
+        const int o0 = v.src.off[i], o1 = v.src.off[i + 1];
         // the (slot * row + keypoint) entry of observation o, -1 when it names nothing
         auto entry = [&](int o, int* pos) -> long long {
             int s, kp;
-            return map_obs(src, o, pos_slot, n_kf, kcnt, pos, &s, &kp) ? -1 : (long long)s * row + kp;
+            return map_obs(v, o, pos, &s, &kp) ? -1 : (long long)s * v.row + kp;
         };
         int nv = 0, pos = 0;
         long long best = -1;
@@ -117,11 +116,11 @@ template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapPts src
                 const long long ej = entry(o, &pos);
                 if (ej < 0) continue;
                 const uint8_t* dj = kdesc + ej * 32;
-                auto count_le = [&](int v) {
+                auto count_le = [&](int d) {
                     int cnt = 0;
                     for (int l = o0; l < o1; l++) {
                         const long long el = entry(l, &pos);
-                        if (el >= 0) cnt += trk_ham(dj, kdesc + el * 32) <= v;
+                        if (el >= 0) cnt += trk_ham(dj, kdesc + el * 32) <= d;
                     }
                     return cnt;
                 };
@@ -145,8 +144,7 @@ template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapPts src
             oct[i] = TK_NOT_LOCAL;
         }
     }
-    const unsigned long long b = __ballot(local);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_local, (int)__popcll(b));
+    wave_count_add(local, n_local);
 }
 
 // one block per grid: histogram of the cells (LDS), exclusive scan, scatter by LDS cursors, then every cell's run sorted by keypoint index (the
@@ -180,13 +178,8 @@ __global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* _
     for (int q = tid; q < n; q += TK_GRID_BLOCK) sorted[atomicAdd(cur + trk_cy(fk[q].y, h) * TK_GX + trk_cx(fk[q].x, w), 1)] = q;
     __syncthreads();
     for (int j = 0; j < TK_CELLS_PER_THREAD; j++) {
-        const int c = tid * TK_CELLS_PER_THREAD + j, a = cell[c], b = cur[c];
-        for (int x = a + 1; x < b; x++) {
-            const int q = sorted[x];
-            int y = x - 1;
-            while (y >= a && sorted[y] > q) { sorted[y + 1] = sorted[y]; y--; }
-            sorted[y + 1] = q;
-        }
+        const int c = tid * TK_CELLS_PER_THREAD + j;
+        sort_run(sorted + cell[c], cur[c] - cell[c]);
     }
 }
 
@@ -203,41 +196,20 @@ __global__ __launch_bounds__(256) void k_trk_search(TrackPrm prm, int pass, int 
     double uu = 0.0, vv = 0.0;
     if (ro != TK_NOT_LOCAL) {
         double R[9], t[3], P[12];
-        for (int j = 0; j < 3; j++) {
-            for (int l = 0; l < 3; l++) R[j * 3 + l] = res->pose[j * 4 + l];
-            t[j] = res->pose[j * 4 + 3];
-        }
+        pose_split(res->pose, R, t);
         pnp_projection(prm.K, R, t, P);
-        const double X = xyz[(size_t)i * 3], Y = xyz[(size_t)i * 3 + 1], Z = xyz[(size_t)i * 3 + 2];
-        const double u = P[0] * X + P[1] * Y + P[2] * Z + P[3];
-        const double v = P[4] * X + P[5] * Y + P[6] * Z + P[7];
-        const double z = P[8] * X + P[9] * Y + P[10] * Z + P[11];
-        if (z > 0.0) {
-            uu = u / z; vv = v / z;
-            cand = uu >= 0.0 && uu < prm.w && vv >= 0.0 && vv < prm.h;
-        }
+        cand = trk_project(P, xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2], prm.w, prm.h, &uu, &vv);
     }
-    const unsigned long long b = __ballot(cand);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&res->cand, (int)__popcll(b));
+    wave_count_add(cand, &res->cand);
     if (!cand) return;
     const double r = (attempt ? 2.0 * prm.radius[pass] : prm.radius[pass]) * trk_scale(prm.sf, ro);
-    const int cx0 = trk_cx(uu - r, prm.w), cx1 = trk_cx(uu + r, prm.w), cy0 = trk_cy(vv - r, prm.h), cy1 = trk_cy(vv + r, prm.h);
     const uint8_t* d = rep + (size_t)i * 32;
     int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
-    for (int cy = cy0; cy <= cy1; cy++)
-        for (int cx = cx0; cx <= cx1; cx++) {
-            const int c = cy * TK_GX + cx, e1 = cell[c + 1];
-            for (int e = cell[c]; e < e1; e++) {
-                const int q = sorted[e];
-                const mo_keypoint kp = fk[q];
-                if (!(fabs((double)kp.x - uu) < r && fabs((double)kp.y - vv) < r)) continue;
-                const long long dl = (long long)kp.octave - ro;
-                if (dl < -1 || dl > 1) continue;
-                const int dist = trk_ham(d, fdesc + (size_t)q * 32);
-                if (dist < bd || (dist == bd && q < bq)) { sd = bd; bd = dist; bq = q; }
-                else if (dist < sd) sd = dist;
-            }
-        }
+    trk_window(uu, vv, r, ro, prm.w, prm.h, cell, sorted, fk, [&](int q, const mo_keypoint&, double, double) {
+        const int dist = trk_ham(d, fdesc + (size_t)q * 32), was = bd;
+        if (trk_take(dist, q, bd, bq)) sd = was;
+        else if (dist < sd) sd = dist;
+    });
     if (bd == INT_MAX || bd > prm.max_dist) return;
     if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
     atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
@@ -315,10 +287,7 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
     if (!flag) return;
     const int m = res->n_match;
     double R[9], t[3];
-    for (int j = 0; j < 3; j++) {
-        for (int l = 0; l < 3; l++) R[j * 3 + l] = res->pose[j * 4 + l];
-        t[j] = res->pose[j * 4 + 3];
-    }
+    pose_split(res->pose, R, t);
     for (int j = tid; j < m; j += TK_REFINE_BLOCK) minl[j] = 1;
     int n_inl = m;
     for (int round = 0; round < 4; round++) {
@@ -360,7 +329,7 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
             minl[j] = in;
             n += in;
         }
-        for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+        n = wave_sum_int(n);
         if (lane == 0) cnt[wv] = n;
         __syncthreads();
         n_inl = 0;
@@ -379,18 +348,18 @@ __global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, in
     }
 }
 
-int trk_launch_rep(mo_map* m, const MapPts& src, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local) {
+int trk_launch_rep(mo_map* m, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local) {
     mo_ctx* c = m->c;
-    hipLaunchKernelGGL(k_trk_rep<false>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
-                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, lo_pos, nullptr, rep, oct, n_local);
+    hipLaunchKernelGGL(k_trk_rep<false>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, map_view(m), m->kkps, m->kdesc, lo_pos, nullptr, rep,
+                       oct, n_local);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
 
-int trk_launch_rep_mask(mo_map* m, const MapPts& src, const uint8_t* lmask, uint8_t* rep, int32_t* oct, int32_t* n_local) {
+int trk_launch_rep_mask(mo_map* m, const uint8_t* lmask, uint8_t* rep, int32_t* oct, int32_t* n_local) {
     mo_ctx* c = m->c;
-    hipLaunchKernelGGL(k_trk_rep<true>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, src, (int)m->n_pts, m->d_pos_slot,
-                       (int)m->pos_slot.size(), m->kcnt, m->row, m->kkps, m->kdesc, 0, lmask, rep, oct, n_local);
+    hipLaunchKernelGGL(k_trk_rep<true>, dim3((unsigned)((m->n_pts + 255) / 256)), dim3(256), 0, c->stream, map_view(m), m->kkps, m->kdesc, 0, lmask, rep, oct,
+                       n_local);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
 }
@@ -449,13 +418,13 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     for (int k = 0; k < TK_MAX_PASS; k++) p.radius[k] = k < prm->n_pass ? prm->radius[k] : 0.0;
     p.sf = prm->scale_factor; p.ratio = prm->ratio; p.chi2 = prm->chi2;
     p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist; p.min_matches = prm->min_matches;
-    const int lo_pos = prm->window > 0 && prm->window < n_kf ? n_kf - prm->window : 0;
+    const int lo_pos = map_window_lo(prm->window, n_kf);
     const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
     hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
     if (lprm && ((rc = covis_enqueue(m)) || (rc = covis_select_enqueue(m, lprm)))) return rc;
-    if ((rc = lprm ? trk_launch_rep_mask(m, src, covis_mask(m), b.rep, b.oct, &b.res.p->n_local)
-                   : trk_launch_rep(m, src, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
+    if ((rc = lprm ? trk_launch_rep_mask(m, covis_mask(m), b.rep, b.oct, &b.res.p->n_local)
+                   : trk_launch_rep(m, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
         (rc = trk_launch_grid(m, nullptr, m->kslots, 1, prm->w, prm->h, b.cell, b.sorted)))   // (the staged frame: the spare slot)
         return rc;
     mo_stage_mark(c, "track_prep");
@@ -477,9 +446,7 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if (out->dist) HIPCHK(c, hipMemcpyAsync(out->dist, b.qdist, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (lprm && (rc = covis_copy_enqueue(m, lout))) return rc;
-    clk.enqueued();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    clk.waited();
+    if ((rc = map_sync(c, clk))) return rc;
     if (lprm) covis_finish(m, lout);
     const TrackRes& r = *b.h_res;
     for (int i = 0; i < 12; i++) out->pose[i] = r.pose[i];
