@@ -842,6 +842,76 @@ int mo_map_set_vocabulary(mo_map*, mo_vocab*);
 int mo_map_query_keyframes(mo_map*, const mo_frame_ref* f, const mo_map_query_params*, mo_map_query_out*);
 int mo_map_relocalize_pre(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, int32_t n_pre, mo_map_reloc_out*);
 
+/* ---- Loop candidates (map_loop.hip) --------------------------------------------------------------------------------------------------------
+ * "Which old keyframe, if any, does this keyframe close a loop with, and which map points of the two correspond": ORB-SLAM2's
+ * KeyFrameDatabase::DetectLoopCandidates on the keyframe database above and on mo_map_covisibility's matrix, then the map-point matching
+ * that opens ComputeSim3.  Reads the map, never changes it.  Integer work and a fixed sequence of f64 operations:
+ * tests/loop_restatement.py restates every rule below in numpy and the device result equals it bit for bit.
+ * mo_map_loop_candidates: p = the asking keyframe position (kf_pos; -1: the last).  The database is brought up to date first by the
+ * query's lazy rule (no frame is staged), then W = mo_map_covisibility's matrix is computed; count_k[w] and weight_w are the database's
+ * term counts and the vocabulary's weights.
+ *   connected(k)  the positions q != k with W[k][q] >= max(min_weight, 1).  There is NO fallback to "the single best neighbour" when none
+ *                 reaches it (ORB-SLAM2's UpdateConnections keeps the best one then): such a keyframe is connected to nothing.
+ *                 connected[q] = 1 for q in connected(p) and for p itself; n_connected = |connected(p)| (p not counted).
+ *   score_k       mo_map_query_keyframes' D_k and score with keyframe p's own database row as the query (q_w = count_p[w] * weight_w).
+ *   min_score     the lowest score_q over q in connected(p); 1.0 when connected(p) is empty (ORB-SLAM2's initial value).
+ *   common_k      for k != p and k not in connected(p): the number of words w with weight_w > 0, count_p[w] > 0 and count_k[w] > 0; 0 for p
+ *                 and for connected keyframes, which take no part below.  max_common = max_k common_k; 0: no candidates.  Counted in
+ *                 the pass over the database rows that forms D_k.
+ *   S             common_k > (4 * max_common) / 5 in integer division (ORB-SLAM2's int(maxCommonWords * 0.8f)).  n_scored = |S|.
+ *   M             k in S with score_k >= min_score.  n_passed = |M|.
+ *   group         of k in M: N_k = the n_best positions q != k with the largest W[k][q] among connected(k), ties to the later position
+ *                 (mo_map_local_keyframes' K2 rule, in that rank order).  acc_k = score_k, then acc_k = acc_k + score_q for each q in
+ *                 N_k that is in S, in rank order: plain f64 adds in exactly that order.  best_k = k, replaced by such a q whenever
+ *                 score_q is strictly greater than the best score so far, walking the same order.
+ *   retained      k in M with acc_k > 0.75 * max_{k in M} acc_k (one f64 multiply, a strict compare).
+ *   candidates    the distinct best_k of the retained k, each with the largest acc_k that named it and its own score, ordered by that
+ *                 acc, highest first, ties to the lower position.  n_found counts them all; the first max_cand are returned
+ *                 (n_cand = min(n_found, max_cand)); cand = -1, acc = score = 0 past n_cand.
+ *   group[c]      [n_kf] 1 at the candidate's position and at connected(candidate); all 0 past n_cand.
+ *   matching      per returned candidate c, with p's rows as queries and c's rows as train rows: the matcher's knn-2, ties to the lower
+ *                 train row, passing when (double)d0 < ratio * (double)d1; a train frame of one row passes its only neighbour, one of
+ *                 no rows matches nothing (mo_map_relocalize's behaviour).  cur_point[i] = the lowest map point with a valid
+ *                 observation (p, i) (mo_map_relocalize's point_of), -1: none; the candidate's rows are looked up the same way.  A
+ *                 passing match i -> j counts when a = cur_point[i] >= 0, b = point_of(c, j) >= 0 and a != b.  When several query rows
+ *                 name the same train row j, the one with the lowest distance keeps it, ties to the lower query row; the others get -1.
+ *                 match_point[c][i] = b, match_row[c][i] = j of the rows kept, -1 elsewhere; n_match[c] = the rows kept.
+ *                 cur_point is written when it is given or max_cand > 0.
+ *   chain         database update, k_covis, score and common words, selection (one workgroup, any number of keyframes), point_of,
+ *                 matcher, gather, copy-out on the context stream; one synchronisation.  The selection kernel writes the matcher's
+ *                 pair list on the device (pairs past n_cand name the empty frame): no host round trip between candidates and matching.
+ *                 Stage marks bow_quantise, bow_hist, covis, loop_score, loop_select, loop_match, loop_gather (the last two only when
+ *                 something is matched or cur_point is asked for).
+ *   errors        MO_ERR_ARG for NULL params or out, kf_pos outside -1 .. n_kf - 1, n_best < 0, max_cand outside 0 .. 16, ratio not in
+ *                 (0, 1], and without a vocabulary; MO_ERR_UNSUPPORTED as for the query on a keyframe of more than 65535 rows.  A map
+ *                 without keyframes: MO_OK, every count 0, min_score 1.0.  max_cand = 0 is legal: the counts and min_score are
+ *                 returned, nothing is matched.
+ * Integer atomics only (minima and maxima commute): two calls on equal maps give the same bytes. */
+typedef struct {
+    int32_t kf_pos;      /* the keyframe that asks, by position; -1: the last */
+    int32_t min_weight;  /* q is connected to p when W[p][q] >= max(min_weight, 1) (15) */
+    int32_t n_best;      /* covisible neighbours a candidate's group score takes, >= 0 (10) */
+    int32_t max_cand;    /* candidates returned and matched, 0 .. 16 (4) */
+    double  ratio;       /* Lowe ratio of the matching (0.75) */
+} mo_map_loop_params;
+typedef struct {
+    /* caller-allocated; any may be NULL */
+    int32_t* cand;        /* [max_cand] candidate positions, -1 past n_cand */
+    double*  acc;         /* [max_cand] accumulated group score */
+    double*  score;       /* [max_cand] the candidate's own score against p */
+    uint8_t* connected;   /* [n_kf] 1: connected to p (p itself included) */
+    uint8_t* group;       /* [max_cand][n_kf] 1: the candidate or connected to it */
+    int32_t* cur_point;   /* [rows of p] map point of each keypoint row of p, -1: none */
+    int32_t* match_point; /* [max_cand][rows of p] the candidate's map point matched to that row, -1 */
+    int32_t* match_row;   /* [max_cand][rows of p] its keypoint row in the candidate, -1 */
+    int32_t* n_match;     /* [max_cand] */
+    /* filled by the call */
+    int32_t n_cand, n_found;   /* n_found: distinct candidates before the cut at max_cand */
+    int32_t n_connected, max_common, n_scored, n_passed;
+    double  min_score;
+} mo_map_loop_out;
+int mo_map_loop_candidates(mo_map*, const mo_map_loop_params*, mo_map_loop_out*);
+
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls
  * neither clears nor pollutes this status.  Synchronises the context stream, copies the flag word to flags[0] (flags may be NULL; [1..3] reserved, 0)

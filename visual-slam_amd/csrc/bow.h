@@ -33,3 +33,20 @@ int bow_require(mo_map* m);
 // the query chain of mo_map_query_keyframes for the frame staged in the spare slot (n rows), ranked to n_pre places, enqueued on the
 // context stream inside the caller's stage set (marks bow_quantise, bow_hist, bow_score, bow_rank); no synchronisation
 int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel);
+
+// What the scoring of mo_map_loop_candidates (map_loop.hip) leaves on the device, valid behind bow_loop_score_enqueue on the context
+// stream: cnt = the row counts by keyframe slot as the database update uploaded them (frame `empty` has 0 rows), score [n_kf] and
+// common [n_kf] by keyframe position.
+struct BowLoop {
+    const int32_t* cnt = nullptr;
+    const double* score = nullptr;
+    const int32_t* common = nullptr;
+    int empty = 0;
+};
+// every stale row of the database brought up to date, no frame staged: the spare slot's row is neither counted nor cleared, and with
+// no stale keyframe nothing is launched (marks bow_quantise, bow_hist either way); enqueued, no synchronisation
+int bow_update_enqueue(mo_map* m);
+// mo_map_query_keyframes' D_k and score of every keyframe with the database row of the keyframe at position q_pos as the query, and in
+// the same pass the common-word counts (0 for q_pos and for every k with wrow[k] >= min_w; wrow = row q_pos of the covisibility matrix,
+// on the device); mark loop_score; behind bow_update_enqueue
+int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w, BowLoop* out);

@@ -27,6 +27,7 @@ struct BowBufs {
     const int32_t* cnt = nullptr; const int32_t* lst = nullptr; const int32_t* ltf = nullptr;
     DevBuf<int32_t> qidx, qdist; DevBuf<uint8_t> qpass;   // [pair][stride] matcher outputs
     DevBuf<double> score;                // [n_kf]
+    DevBuf<int32_t> common;              // [n_kf] common words with the asking keyframe (mo_map_loop_candidates)
     DevBuf<int32_t> out_pos, out_n; DevBuf<double> out_score;
     DevBuf<int32_t> sel_qf, sel_tf, mrow;
 };
@@ -83,9 +84,19 @@ __device__ __forceinline__ long long bow_term(int q, unsigned k, int w, long lon
     return d < 0 ? -d : d;
 }
 
-__global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ pos_slot, int n_kf, int spare, const uint16_t* __restrict__ db,
-                                                   const long long* __restrict__ norm, const int32_t* __restrict__ weights, int Wp,
-                                                   double* __restrict__ score) {
+// COMMON (mo_map_loop_candidates, the query slot then is the asking keyframe's own): the same pass also counts, per keyframe, the words
+// with q_w > 0 (weight and query count both non-zero) that the keyframe has too - no second walk over the rows.  The asking keyframe
+// (q_pos) and the keyframes connected to it (wrow[k] >= min_w, wrow = its row of the covisibility matrix) get 0.  The plain query's
+// instantiation takes an empty argument and compiles to the kernel it was before the template.
+template <bool COMMON> struct BowCommonArg {};
+template <> struct BowCommonArg<true> {
+    const int32_t* wrow; int q_pos, min_w;
+    int32_t* common;
+};
+
+template <bool COMMON> __global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ pos_slot, int n_kf, int spare, const uint16_t* __restrict__ db,
+                                                                          const long long* __restrict__ norm, const int32_t* __restrict__ weights, int Wp,
+                                                                          double* __restrict__ score, BowCommonArg<COMMON> ca) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int32_t* s_q = (int32_t*)smem;
     long long* red = (long long*)(smem + (size_t)Wp * 4);
@@ -104,6 +115,7 @@ __global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ p
         const long long nk = norm[s];
         const uint4* krow = (const uint4*)(db + (size_t)s * Wp);
         long long D = 0;
+        int cw = 0;
         for (int g = tid; g < Wp / 8; g += 256) {
             const uint4 c = krow[g];
             const int4 w0 = *(const int4*)(weights + 8 * g), w1 = *(const int4*)(weights + 8 * g + 4);
@@ -112,9 +124,17 @@ __global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ p
                  bow_term(q0.z, c.y & 0xffffu, w0.z, nq, nk) + bow_term(q0.w, c.y >> 16, w0.w, nq, nk) +
                  bow_term(q1.x, c.z & 0xffffu, w1.x, nq, nk) + bow_term(q1.y, c.z >> 16, w1.y, nq, nk) +
                  bow_term(q1.z, c.w & 0xffffu, w1.z, nq, nk) + bow_term(q1.w, c.w >> 16, w1.w, nq, nk);
+            if constexpr (COMMON)
+                cw += (int)(q0.x > 0 && (c.x & 0xffffu)) + (int)(q0.y > 0 && (c.x >> 16)) + (int)(q0.z > 0 && (c.y & 0xffffu)) +
+                      (int)(q0.w > 0 && (c.y >> 16)) + (int)(q1.x > 0 && (c.z & 0xffffu)) + (int)(q1.y > 0 && (c.z >> 16)) +
+                      (int)(q1.z > 0 && (c.w & 0xffffu)) + (int)(q1.w > 0 && (c.w >> 16));
         }
         D = bow_block_sum(D, red);
         if (tid == 0) score[k] = (nq == 0 || nk == 0) ? 0.0 : 1.0 - 0.5 * (double)D / ((double)nq * (double)nk);
+        if constexpr (COMMON) {
+            const long long n = bow_block_sum(cw, red + 4);   // (the second half of the reduction scratch)
+            if (tid == 0) ca.common[k] = (k == ca.q_pos || ca.wrow[k] >= ca.min_w) ? 0 : (int32_t)n;
+        }
         __syncthreads();   // (red is written again by the next keyframe)
     }
 }
@@ -345,8 +365,9 @@ int bow_require(mo_map* m) {
 }
 
 // every stale row and the frame's row brought up to date: one quantise launch (a pair per stale keyframe and one for the frame), one
-// histogram launch
-static int bow_update(mo_map* m, int n) {
+// histogram launch.  frame false (mo_map_loop_candidates: no frame is staged): the spare slot is in neither list and its row stays as
+// it is; with no stale keyframe nothing is launched, the two stage marks are still set.
+static int bow_update(mo_map* m, int n, bool frame = true) {
     mo_ctx* c = m->c;
     BowBufs& b = *m->bow;
     const mo_vocab& v = *b.v;
@@ -360,7 +381,7 @@ static int bow_update(mo_map* m, int n) {
             if (m->h_kcnt[s] > MO_BOW_MAX_ROWS) return mo_fail(c, MO_ERR_UNSUPPORTED, "a keyframe of more than 65535 rows would wrap a term count");
             b.h_lst.push_back(s);
         }
-    b.h_lst.push_back(spare);
+    if (frame) b.h_lst.push_back(spare);
     const int n_list = (int)b.h_lst.size();
     if (rows > b.db_rows) {   // the store gained slots: the rows made so far move with it (the spare row is made again by every call)
         const size_t keep = (size_t)std::min(b.db_rows, m->n_slots);
@@ -372,7 +393,7 @@ static int bow_update(mo_map* m, int n) {
     const size_t out_n = (size_t)n_list * stride;
     b.h_up.assign((size_t)rows + 2 + 2 * (size_t)n_list, 0);
     std::copy(m->h_kcnt.begin(), m->h_kcnt.begin() + m->n_slots, b.h_up.begin());
-    b.h_up[spare] = n; b.h_up[rows] = v.W;
+    b.h_up[spare] = frame ? n : 0; b.h_up[rows] = v.W;
     std::copy(b.h_lst.begin(), b.h_lst.end(), b.h_up.begin() + rows + 2);
     std::fill(b.h_up.begin() + rows + 2 + n_list, b.h_up.end(), rows);
     if ((rc = b.up.reserve(c, b.h_up.size())) || (rc = b.qidx.reserve(c, out_n * 2)) || (rc = b.qdist.reserve(c, out_n * 2)) ||
@@ -384,11 +405,13 @@ static int bow_update(mo_map* m, int n) {
     if ((rc = match_launch_pairs(c, m->kdesc, v.words, (size_t)row * 32, 0, b.cnt, b.lst, b.ltf, 0, 0, n_list, stride, -1.0, b.qidx, b.qdist, b.qpass)))
         return rc;
     mo_stage_mark(c, "bow_quantise");
-    hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.qidx, v.W, b.Wp,
-                       v.weights, b.db, b.norm);
-    HIPCHK(c, hipGetLastError());
+    if (n_list > 0) {
+        hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.qidx, v.W, b.Wp,
+                           v.weights, b.db, b.norm);
+        HIPCHK(c, hipGetLastError());
+    }
     mo_stage_mark(c, "bow_hist");
-    for (int i = 0; i + 1 < n_list; i++) b.done[b.h_lst[i]] = m->kserial[b.h_lst[i]];
+    for (int i = 0; i < n_list - (frame ? 1 : 0); i++) b.done[b.h_lst[i]] = m->kserial[b.h_lst[i]];
     return MO_OK;
 }
 
@@ -403,8 +426,8 @@ static int bow_enqueue(mo_map* m, int n, int n_best, bool sel) {
     if ((rc = b.score.reserve(c, (size_t)n_kf)) || (rc = b.out_pos.reserve(c, nb)) || (rc = b.out_score.reserve(c, nb)) || (rc = b.out_n.reserve(c, 1)) ||
         (sel && ((rc = b.sel_qf.reserve(c, nb)) || (rc = b.sel_tf.reserve(c, nb)) || (rc = b.mrow.reserve(c, (size_t)n_kf)))))
         return rc;
-    hipLaunchKernelGGL(k_bow_score, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf, spare,
-                       b.db, b.norm, b.v->weights, b.Wp, b.score);
+    hipLaunchKernelGGL(k_bow_score<false>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf, spare,
+                       b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<false>{});
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "bow_score");
     hipLaunchKernelGGL(k_bow_rank, dim3(1), dim3(1024), 1024 * 8 + 16, c->stream, b.score, n_kf, n_best, b.out_pos, b.out_score, b.out_n, m->d_pos_slot, spare,
@@ -418,6 +441,22 @@ int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel) {
     if (int rc = bow_enqueue(m, n, n_pre, true)) return rc;
     BowBufs& b = *m->bow;
     sel->cnt = b.cnt; sel->qf = b.sel_qf; sel->tf = b.sel_tf; sel->mrow = b.mrow;
+    return MO_OK;
+}
+
+int bow_update_enqueue(mo_map* m) { return bow_update(m, 0, false); }
+
+int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w, BowLoop* out) {
+    mo_ctx* c = m->c;
+    BowBufs& b = *m->bow;
+    const int n_kf = (int)m->pos_slot.size(), q_slot = m->pos_slot[q_pos];
+    int rc;
+    if ((rc = b.score.reserve(c, (size_t)n_kf)) || (rc = b.common.reserve(c, (size_t)n_kf))) return rc;
+    hipLaunchKernelGGL(k_bow_score<true>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf,
+                       q_slot, b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<true>{wrow, q_pos, min_w, b.common});
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "loop_score");
+    out->cnt = b.cnt; out->score = b.score; out->common = b.common; out->empty = m->kslots + 2;
     return MO_OK;
 }
 

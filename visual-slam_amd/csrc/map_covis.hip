@@ -225,6 +225,7 @@ void covis_finish(mo_map* m, mo_map_local_out* out) {
 }
 
 const uint8_t* covis_mask(const mo_map* m) { return m->cv->mask; }
+const int32_t* covis_weights(const mo_map* m) { return m->cv->W; }
 
 extern "C" int mo_map_covisibility(mo_map* m, int32_t* weights, int32_t* n_kf) {
     if (!m) return MO_ERR_ARG;

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition) and map_io.hip (PLY text).
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates) and map_io.hip (PLY text).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's) and mo_map;
 //   MapView / map_view: the live map as every kernel receives it (by value);
@@ -43,6 +43,7 @@ struct FuseBufs;    // mo_map_fuse (map_fuse.hip)
 struct GrowBufs;    // mo_map_grow (map_grow.hip)
 struct CovisBufs;   // mo_map_covisibility, mo_map_local_keyframes and mo_map_track_covisible (map_covis.hip)
 struct BowBufs;     // mo_map_set_vocabulary: the keyframe database of mo_map_query_keyframes and mo_map_relocalize_pre (bow.hip)
+struct LoopBufs;    // mo_map_loop_candidates (map_loop.hip)
 void map_scratch_free(RelocBufs* b);
 void map_scratch_free(TrackBufs* b);
 void map_scratch_free(BaBufs* b);
@@ -50,6 +51,7 @@ void map_scratch_free(FuseBufs* b);
 void map_scratch_free(GrowBufs* b);
 void map_scratch_free(CovisBufs* b);
 void map_scratch_free(BowBufs* b);
+void map_scratch_free(LoopBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -89,8 +91,9 @@ struct mo_map {
     GrowBufs* gr = nullptr;
     CovisBufs* cv = nullptr;
     BowBufs* bow = nullptr;
+    LoopBufs* lp = nullptr;
     // (mo_map_destroy selects the device and drains the stream first)
-    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); }
+    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); map_scratch_free(lp); }
 };
 
 // ---- the live map as the kernels receive it (by value): the live copy of the store, the uploaded position table, the keyframe counts
@@ -251,6 +254,8 @@ int covis_select_enqueue(mo_map* m, const mo_map_local_params* prm);
 int covis_copy_enqueue(mo_map* m, mo_map_local_out* out);
 void covis_finish(mo_map* m, mo_map_local_out* out);
 const uint8_t* covis_mask(const mo_map* m);
+// W [n_kf][n_kf] on the device, valid behind covis_enqueue on the context stream (mo_map_loop_candidates reads it)
+const int32_t* covis_weights(const mo_map* m);
 
 // A query frame staged in the spare keyframe slot (mo_map_track, mo_map_relocalize; read-only on the map): the frame looked up,
 // *from_token set, defaults(n) run (the caller's per-keypoint output defaults), then - unless there is nothing to search, which leaves

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -123,6 +123,9 @@ def main(argv=None):
                     "relocalization and saved there")
     ap.add_argument("--reloc-preselect", type=int, default=0, help="with --vocabulary: N > 0: relocalize matches the frame only against the N "
                     "keyframes the vocabulary query ranks first (LocalMapper.relocalize(preselect=N))")
+    ap.add_argument("--detect-loops", action="store_true", help="with --map --vocabulary: after each keyframe, look for a loop (LocalMapper.detect_loop: "
+                    "place-recognition candidates on the covisibility graph, three consistent detections in a row, map-point matches); one "
+                    "line per keyframe with candidates, one when a loop is found")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
@@ -155,8 +158,10 @@ def main(argv=None):
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
     if args.relocalize and not args.map:
         ap.error("--relocalize needs --map")
-    if args.vocabulary and not args.relocalize:
-        ap.error("--vocabulary needs --map and --relocalize")
+    if args.vocabulary and not ((args.relocalize or args.detect_loops) and args.map):
+        ap.error("--vocabulary needs --map and --relocalize or --detect-loops")
+    if args.detect_loops and not args.vocabulary:
+        ap.error("--detect-loops needs --map and --vocabulary")
     if args.reloc_preselect and not args.vocabulary:
         ap.error("--reloc-preselect needs --vocabulary")
     if args.reloc_preselect < 0:
@@ -176,6 +181,7 @@ def main(argv=None):
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
+    n_loop = [0, 0]   # --detect-loops: calls, loops found
     seeds = [None]   # --covisible: the previous frame's matched map points (indices into the map as it stands: dropped when the map changes)
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
@@ -184,6 +190,34 @@ def main(argv=None):
             import vslam_amd
             mapper.set_vocabulary(vslam_amd.Vocabulary.load(args.vocabulary, context=mapper.ctx))
             print("vocabulary: %d words from %s" % (len(mapper.vocabulary), args.vocabulary))
+
+    def ensure_vocabulary(idx):
+        """--vocabulary names a file that does not exist: trained from the map's keyframes at its first use and saved there"""
+        if args.vocabulary and mapper.vocabulary is None and mapper.keyframes:
+            rows = sum(len(kf["descriptors"]) for kf in mapper.keyframes)
+            if rows >= 2:
+                v = mapper.train_vocabulary(min(1024, rows))
+                v.save(args.vocabulary)
+                print("frame %d: vocabulary of %d words trained on %d rows of %d keyframes in %d iterations, saved to %s"
+                      % (idx, len(v), rows, len(mapper.keyframes), v.iterations, args.vocabulary))
+
+    def detect_loop(idx):
+        """--detect-loops, after a keyframe was added (ORB-SLAM2's LoopClosing::DetectLoop up to the point correspondences)"""
+        if not args.detect_loops:
+            return
+        ensure_vocabulary(idx)
+        if mapper.vocabulary is None:
+            return
+        found, info = mapper.detect_loop()
+        n_loop[0] += 1
+        if info["candidates"]:
+            print("frame %d: keyframe %d loop candidates %s" % (idx, info["kf_pos"], ", ".join(
+                "%d (score %.3f, group score %.3f, consistency %d, %d matches)" % (c["pos"], c["score"], c["acc"], c["consistency"], c["n_match"])
+                for c in info["candidates"])))
+        if found:
+            n_loop[1] += 1
+            acc = info["accepted"]
+            print("frame %d: loop found: keyframe %d closes with keyframe %d, %d map-point correspondences" % (idx, info["kf_pos"], acc["pos"], acc["n_match"]))
 
     def track_pose(R, t, frame, kps, desc, idx):
         """Tracker._update_pose (tracker.py:268-279) and the keyframe every N frames (tracker.py:114-118, 290)"""
@@ -195,6 +229,7 @@ def main(argv=None):
         recent[:] = recent[-1:] + [ref_pose]
         if mapper is not None and idx % args.keyframe_every == 0:
             mapper.add_keyframe(frame, kps, desc, ref_pose)
+            detect_loop(idx)
 
     def fuse(idx):
         fi = mapper.fuse_map_points(window=args.ba_window)
@@ -253,18 +288,13 @@ def main(argv=None):
                         grow(idx)
                     if args.fuse:
                         fuse(idx)
+                detect_loop(idx)
         return ok
 
     def relocalize(frame, kps, desc, idx):
         """the frame against the map (ORB-SLAM2's Tracking::Relocalization); on success tracking goes on from its pose"""
         nonlocal ref_pose
-        if args.vocabulary and mapper.vocabulary is None and mapper.keyframes:
-            rows = sum(len(kf["descriptors"]) for kf in mapper.keyframes)
-            if rows >= 2:
-                v = mapper.train_vocabulary(min(1024, rows))
-                v.save(args.vocabulary)
-                print("frame %d: vocabulary of %d words trained on %d rows of %d keyframes in %d iterations, saved to %s"
-                      % (idx, len(v), rows, len(mapper.keyframes), v.iterations, args.vocabulary))
+        ensure_vocabulary(idx)
         pre = args.reloc_preselect if args.reloc_preselect > 0 and mapper.vocabulary is not None else None
         ok, T, info = mapper.relocalize(kps, desc, preselect=pre)
         print("frame %d: relocalize %s, keyframe %s, %d candidates, %d inliers%s" % (idx, "ok" if ok else "failed", info["kf_pos"],
@@ -347,6 +377,8 @@ def main(argv=None):
             print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
         if args.grow_neighbours:
             print("growth from neighbours: %d calls, %d points created with %d observations" % (n_grow[0], n_grow[1], n_grow[2]))
+        if args.detect_loops:
+            print("loop detection: %d calls, %d loops found" % (n_loop[0], n_loop[1]))
         if args.fuse:
             print("fusion: %d calls, %d points absorbed, %d observations gained" % (n_fuse[0], n_fuse[1], n_fuse[2]))
     return state, poses, n_map

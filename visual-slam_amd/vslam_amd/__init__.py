@@ -151,6 +151,17 @@ class MapQueryOut(C.Structure):
     _fields_ = [("pos", C.c_void_p), ("score", C.c_void_p), ("n", C.c_int32), ("from_token", C.c_int32)]
 
 
+class MapLoopParams(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("min_weight", C.c_int32), ("n_best", C.c_int32), ("max_cand", C.c_int32), ("ratio", C.c_double)]
+
+
+class MapLoopOut(C.Structure):
+    _fields_ = [("cand", C.c_void_p), ("acc", C.c_void_p), ("score", C.c_void_p), ("connected", C.c_void_p), ("group", C.c_void_p),
+                ("cur_point", C.c_void_p), ("match_point", C.c_void_p), ("match_row", C.c_void_p), ("n_match", C.c_void_p),
+                ("n_cand", C.c_int32), ("n_found", C.c_int32), ("n_connected", C.c_int32), ("max_common", C.c_int32),
+                ("n_scored", C.c_int32), ("n_passed", C.c_int32), ("min_score", C.c_double)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -247,6 +258,7 @@ SIGNATURES = {
     "mo_map_set_vocabulary": (_i, [_vp, _vp]),
     "mo_map_query_keyframes": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
 }
 
 _lib = None

@@ -32,7 +32,7 @@ def predict_pose(prev, last):
 
 class _Keyframe(dict):
     """a keyframe dict whose 'map_points' is read from the mapper's per-keyframe lists when asked for"""
-    __slots__ = ("_mapper", "_extra")
+    __slots__ = ("_mapper", "_extra", "_rows")
 
     def __getitem__(self, key):
         if key == "map_points" and not dict.__contains__(self, "map_points"):
@@ -103,6 +103,9 @@ class LocalMapper:
         self._injected = []       # the dicts given to update_map_points (dref_kf = -(j + 1))
         self._n_points = 0
         self._list_rows = []      # keyframe position -> row of the per-keyframe lists (None: empty list)
+        self._kf_serials = []     # keyframe position -> creation serial (positions are renumbered by every keyframe cull, serials never)
+        self._next_serial = 0
+        self._loop_consistency = None
         self._version = 0
         self._cache = None
         self._lists = None
@@ -142,6 +145,7 @@ class LocalMapper:
                         "pose": pose.copy()})
         kf._mapper = self
         kf._extra = []   # ids appended by a growth step whose cull raised (the reference's lists at that point)
+        kf._rows = 0     # its keypoint rows in the store (set below)
         slot = len(self._records)
         token = V.resident_token(self.ctx, descriptors) if descriptors is not None else 0
         kps_arr = V._resident_kps(descriptors) if token else None
@@ -155,6 +159,7 @@ class LocalMapper:
         desc = np.ascontiguousarray(descriptors if descriptors is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
         n = len(kps_arr) if token else min(len(kps_arr), len(desc))
         ref = V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n)
+        kf._rows = n
         P = np.ascontiguousarray(compute_projection_matrix(pose[:3, :3], pose[:3, 3], self.camera_matrix), np.float64).reshape(12)
         img = np.ascontiguousarray(image, np.uint8)
         ch = 1 if img.ndim == 2 else img.shape[2]
@@ -169,6 +174,8 @@ class LocalMapper:
         prm = V.MapKfParams(0.8, 3.0, self.n_hyp, self.seed, self.pair_index_base + max(slot - 1, 0))
         out = V.MapKfOut(midx.ctypes.data, mpass.ctypes.data, inl.ctypes.data, gpts.ctypes.data, kf_len.ctypes.data, kf_red.ctypes.data)
         self.keyframes.append(kf)
+        self._kf_serials.append(self._next_serial)
+        self._next_serial += 1
         self._records.append(kf)
         self._version += 1
         self._cache = None
@@ -431,6 +438,7 @@ class LocalMapper:
             del self.co_visibility_graph[kf_id]
             self.keyframes.pop(idx)
             self._list_rows.pop(idx)
+            self._kf_serials.pop(idx)
         pos = np.array(sorted(remove), np.int32)
         self._check(self.lib.mo_map_remove_keyframes(self._h, V._ptr(pos), len(pos)))
         for i, kf in enumerate(self.keyframes):
@@ -639,6 +647,61 @@ class LocalMapper:
         assert int(out.n_k1) == int((mask == 1).sum()) and int(out.n_local_kf) == int((mask != 0).sum())
         return {"local": np.flatnonzero(mask).tolist(), "k1": np.flatnonzero(mask == 1).tolist(), "k2": np.flatnonzero(mask == 2).tolist(),
                 "ref": int(out.ref)}
+
+    # ---- loop detection --------------------------------------------------------------------------------------------------------------
+    def loop_candidates(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75):
+        """The old keyframes keyframe `kf_position` (-1: the last) may close a loop with, and the map points of the two that correspond
+        (ORB-SLAM2's DetectLoopCandidates and the matching that opens ComputeSim3; mo_map_loop_candidates in include/vslam_amd.h states
+        the rules).  Needs a vocabulary; stateless; the map is not changed.  Returns a dict: `candidates`, a list of dicts in rank order
+        with `pos`, `acc` (accumulated group score), `score` (its own), `group` (the positions of the candidate and the keyframes
+        connected to it), `n_match`, `cur_point` (the asking keyframe's map point per keypoint row, -1: none), `match_point` (the
+        candidate's map point matched to that row, -1) and `match_row` (its keypoint row in the candidate, -1); `cur_point` once more at the top (also there
+        without a candidate); `connected` (positions connected to the asking keyframe, itself included), `min_score`, `max_common`, `n_scored`, `n_passed`, `n_found` (candidates
+        before the cut at max_candidates) and `n_connected`."""
+        n_kf, mc = len(self.keyframes), int(max_candidates)
+        p = n_kf - 1 if int(kf_position) < 0 else int(kf_position)
+        n_p = self.keyframes[p]._rows if 0 <= p < n_kf else 0
+        m1 = max(mc, 1)
+        cand = np.full(m1, -1, np.int32)
+        acc, score = np.zeros(m1, np.float64), np.zeros(m1, np.float64)
+        connected = np.zeros(max(n_kf, 1), np.uint8)
+        group = np.zeros((m1, max(n_kf, 1)), np.uint8)
+        cur = np.full(max(n_p, 1), -1, np.int32)
+        mpt, mrow = np.full((m1, max(n_p, 1)), -1, np.int32), np.full((m1, max(n_p, 1)), -1, np.int32)
+        n_match = np.zeros(m1, np.int32)
+        prm = V.MapLoopParams(int(kf_position), int(min_weight), int(n_best), mc, float(ratio))
+        out = V.MapLoopOut(cand.ctypes.data, acc.ctypes.data, score.ctypes.data, connected.ctypes.data, group.ctypes.data, cur.ctypes.data,
+                           mpt.ctypes.data, mrow.ctypes.data, n_match.ctypes.data)
+        self._check(self.lib.mo_map_loop_candidates(self._h, C.byref(prm), C.byref(out)))
+        # (the device writes the arrays packed: [max_cand][n_kf] and [max_cand][rows], which is their shape whenever they hold anything)
+        cur = cur[:n_p]
+        cands = [{"pos": int(cand[i]), "acc": float(acc[i]), "score": float(score[i]), "group": np.flatnonzero(group[i, :n_kf]).tolist(),
+                  "n_match": int(n_match[i]), "cur_point": cur, "match_point": mpt[i, :n_p], "match_row": mrow[i, :n_p]}
+                 for i in range(int(out.n_cand))]
+        return {"candidates": cands, "cur_point": cur, "connected": np.flatnonzero(connected[:n_kf]).tolist(), "min_score": float(out.min_score),
+                "max_common": int(out.max_common), "n_scored": int(out.n_scored), "n_passed": int(out.n_passed), "n_found": int(out.n_found),
+                "n_connected": int(out.n_connected), "kf_pos": p}
+
+    def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3):
+        """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
+        (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
+        the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
+        n_match >= min_matches; info is loop_candidates' dict, each candidate also with `serial`, `consistency`, `consistent` and
+        `enough_matches`, and `accepted`: the first candidate in order with both flags (None: no loop), with its correspondence arrays."""
+        from vslam_amd.loop import LoopConsistency
+        if self._loop_consistency is None or self._loop_consistency.threshold != int(consistency):
+            self._loop_consistency = LoopConsistency(consistency)
+        info = self.loop_candidates(kf_position, min_weight, n_best, max_candidates, ratio)
+        cands = info["candidates"]
+        ser = self._kf_serials
+        reported, cons = self._loop_consistency.update([(ser[c["pos"]], [ser[q] for q in c["group"]]) for c in cands])
+        for c, n in zip(cands, cons):
+            c["serial"] = ser[c["pos"]]
+            c["consistency"] = n
+            c["consistent"] = c["serial"] in reported
+            c["enough_matches"] = c["n_match"] >= int(min_matches)
+        info["accepted"] = next((c for c in cands if c["consistent"] and c["enough_matches"]), None)
+        return info["accepted"] is not None, info
 
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
     def _sync_size(self):
