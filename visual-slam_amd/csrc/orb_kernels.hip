@@ -316,6 +316,7 @@ __device__ __forceinline__ void blur_col_quad(const uint32_t* sr, int pitch, uin
 #define RB_WR 88                      // window rows
 #define RB_WP 96                      // window pitch in bytes: window columns + 8 (the resize's third dword may run past it)
 #define RB_SR_BYTES ((RB_PH / 2 + 4) * RB_PW * 4)  // s_row: [row pair][column] u32, partition + 6 halo rows (+ 1 for an odd count)
+struct __attribute__((packed, aligned(4))) Dwords4 { uint32_t x, y, z, w; };  // 16 bytes at dword alignment: one load on this target
 struct BlurOut {
     uint8_t* dst;      // blurred level L-1 of frame 0
     size_t fstride;    // bytes per frame
@@ -357,10 +358,29 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
         uint32_t ye[RS_TH / 16];
 #pragma unroll
         for (int half = 0; half < RS_TH / 16; half++) ye[half] = ypk[ty0 + rr + 16 * half];
-        {  // stage: all loads of a thread issued before the first LDS store (one global round trip)
+        const bool inside = wy0 >= 0 && wy1 <= sh && wx0 >= 0 && wx1 <= sw;
+        const int np16 = (ndw + 3) >> 2;  // 16-byte pieces per window row (<= RB_WP / 16: ndw <= RB_WP / 4 - 2)
+        if (inside && wx0 + 16 * np16 <= spitch) {
+            // stage, the window inside the level (block-uniform; every tile of a plan whose blur margin is >= 3): 8 lanes per row, one
+            // 16-byte piece each (dword-aligned loads, 16-byte aligned LDS stores), 32 rows per trip.  Row and piece are split once per
+            // thread; a trip adds a constant stride.  The last piece may run <= 12 bytes past the window, inside the row's pitch and
+            // inside the LDS row (bytes nothing reads).
+            constexpr int TRIPS = (RB_WR + 31) / 32;
+            static_assert(RB_WP % 16 == 0 && RB_WP / 16 <= 8, "a window row is at most 8 pieces of 16 bytes");
+            const int p = tid & 7, r = tid >> 3;
+            const int rows_left = p < np16 ? nwr - r : 0;
+            const uint32_t goff = (uint32_t)((wy0 + r) * spitch + wx0 + 16 * p);
+            uint8_t* const lrow = s_px + r * RB_WP + 16 * p;
+            Dwords4 v[TRIPS];
+#pragma unroll
+            for (int t = 0; t < TRIPS; t++)
+                if (32 * t < rows_left) v[t] = *(const Dwords4*)(img + (size_t)(32 * t) * (uint32_t)spitch + goff);
+#pragma unroll
+            for (int t = 0; t < TRIPS; t++)
+                if (32 * t < rows_left) *(uint4*)(lrow + 32 * t * RB_WP) = make_uint4(v[t].x, v[t].y, v[t].z, v[t].w);
+        } else {  // stage, a window that leaves the level: all loads of a thread issued before the first LDS store (one global round trip)
             constexpr int TRIPS = (RB_WR * (RB_WP / 4 - 2) + 255) / 256;
             const uint32_t inv = 0x100000u / (uint32_t)ndw + 1u;  // i / ndw, exact while i * ndw < 2^20
-            const bool inside = wy0 >= 0 && wy1 <= sh && wx0 >= 0 && wx1 <= sw;
             uint32_t v[TRIPS];
 #pragma unroll
             for (int t = 0; t < TRIPS; t++) {
@@ -1427,14 +1447,17 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 //   * line requests per frame: 214 tiles x ~390 instead of 2000 keypoints x ~130 (levels 2.. are dense: 20 - 60 keypoints per tile)
 //   * no window registers: the per-row intensity-centroid weights (constant per lane) live in registers instead of being re-read
 //     from LDS for every keypoint, ~70 VGPRs
-//   * tile pitches of 25 / 27 dwords (odd): the 16 lanes of a group read 16 different rows conflict-free in the centroid phase
+//   * a raw tile pitch of 44 dwords (an odd multiple of 4): the 16 lanes of a group read 16 different rows conflict-free in the centroid phase
 // Results are those of that kernel bit for bit (same integer sums, same float expressions, same sample addresses).
 // (DT_W x DT_H keypoint positions per tile and DT_SPLIT_LATENCY: plan_tables.h, where the tile table is built)
-#define DT_RAW_P ((DT_W + 30 + 7 + 7) & ~7)  // raw tile pitch: DT_W + 30 columns + <= 7 alignment lead-in, 8-byte pieces (104: 26 dwords, the 16
-                                             // rows the lanes of a group read in the centroid phase fall into 16 different banks)
+#define DT_RAW_P ((DT_W + 30 + 15 + 15) & ~15)  // raw tile pitch: DT_W + 30 columns + <= 15 alignment lead-in, 16-byte pieces (176: 44 dwords, an odd
+                                                // multiple of 4 - the 16 rows the lanes of a group read in the centroid phase fall into 16 different banks)
 #define DT_RAW_ROWS (DT_H + 30)
-#define DT_BLR_P ((DT_W + 38 + 7 + 7) & ~7)  // blurred tile pitch: DT_W + 38 columns + <= 7 lead-in (112)
+#define DT_BLR_P ((DT_W + 38 + 15 + 15) & ~15)  // blurred tile pitch: DT_W + 38 columns + <= 15 lead-in (192); phase C samples single bytes, no bank pattern to keep
 #define DT_BLR_ROWS (DT_H + 38)
+#define DT_RAW_NQ ((DT_W + 30 + 7 + 7) >> 3)    // 8-byte pieces per row of the 8-byte form (<= 7 lead-in): 21
+#define DT_BLR_NQ ((DT_W + 38 + 7 + 7) >> 3)    // 22
+static_assert(((DT_RAW_P / 4) & 1) || ((DT_RAW_P / 4) & 7) == 4, "raw tile pitch: odd, or an odd multiple of 4 dwords");
 #ifndef DT_NT
 #define DT_NT 256                    // 16 keypoint groups of 16 lanes
 #endif
@@ -1445,29 +1468,73 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 #endif
 #define DT_CHUNK 512                 // entries of the level's list examined per pass (a 2000-feature level 0 holds 434)
 #define DT_LIST (DT_NT > 160 ? DT_NT : 160)  // keypoints of the tile described per pass (typical: 6 on level 0, 60 on level 7; a sub-pass examines DT_NT records); 7 workgroups per CU
-#define DT_RAW_LD ((DT_RAW_ROWS * (DT_RAW_P / 8) + DT_NT - 1) / DT_NT)   // 8-byte loads per thread: 10
-#define DT_BLR_LD ((DT_BLR_ROWS * (DT_BLR_P / 8) + DT_NT - 1) / DT_NT)   // 12
+#define DT_RAW_LD ((DT_RAW_ROWS * DT_RAW_NQ + DT_NT - 1) / DT_NT)   // 8-byte loads per thread: 8
+#define DT_BLR_LD ((DT_BLR_ROWS * DT_BLR_NQ + DT_NT - 1) / DT_NT)   // 9
+#define DT_RAW_NP (DT_RAW_P / 16)                                  // 16-byte pieces per row of the 16-byte form: 11
+#define DT_BLR_NP (DT_BLR_P / 16)                                  // 12
+#define DT_RAW_LD16 ((DT_RAW_ROWS + DT_NT / DT_RAW_NP - 1) / (DT_NT / DT_RAW_NP))   // 16-byte loads per thread: 23 rows per trip, 5
+#define DT_BLR_LD16 ((DT_BLR_ROWS + DT_NT / DT_BLR_NP - 1) / (DT_NT / DT_BLR_NP))   // 21 rows per trip, 5
+#define DT_MAX2(a, b) ((a) > (b) ? (a) : (b))
+// dwords a thread holds between issue and store: ONE array for either tile in either form, so that the forms share its registers
+#define DT_STAGE_REGS DT_MAX2(DT_MAX2(2 * DT_RAW_LD, 2 * DT_BLR_LD), DT_MAX2(4 * DT_RAW_LD16, 4 * DT_BLR_LD16))
 
-// rows [ry0, ry0 + NROWS) x 8-byte columns [cx_al, cx_al + 8 NQ) of a level -> registers (tile_issue), then LDS (tile_store): every load
+// The 8-byte form (a level that is 8- but not 16-byte aligned, or a window that leaves the level):
+// rows [ry0, ry0 + NROWS) x 8-byte columns [cx_al, cx_al + 8 NQ) of a level -> registers (tile_issue), then LDS (tile_store, pitch LP): every load
 // of both tiles is in flight before the first store - one global round trip per workgroup.  Rows are clamped into the level,
 // 8-byte columns into the row pitch (clamped data is never sampled: a keypoint keeps edge_threshold >= 19 from the border).
 template <int NROWS, int NQ, int NLD>
-__device__ __forceinline__ void tile_issue(const uint8_t* img, int pitch, int h, int ry0, int cx_al, int tid, uint2 (&v)[NLD]) {
+__device__ __forceinline__ void tile_issue(const uint8_t* img, int pitch, int h, int ry0, int cx_al, int tid, uint32_t (&v)[DT_STAGE_REGS]) {
     const int last_q = (pitch >> 3) - 1;
 #pragma unroll
     for (int u = 0; u < NLD; u++) {
         const int t = min(tid + u * DT_NT, NROWS * NQ - 1), r = t / NQ, c = t - r * NQ;  // (constant divisor)
         const int y = min(max(ry0 + r, 0), h - 1), q = min(max((cx_al >> 3) + c, 0), last_q);
-        v[u] = ((const uint2*)(img + (size_t)y * pitch))[q];
+        const uint2 d = ((const uint2*)(img + (size_t)y * pitch))[q];
+        v[2 * u] = d.x; v[2 * u + 1] = d.y;
     }
 }
-template <int NROWS, int NQ, int NLD>
-__device__ __forceinline__ void tile_store(uint8_t* lds, int tid, const uint2 (&v)[NLD]) {
+template <int NROWS, int NQ, int LP, int NLD>
+__device__ __forceinline__ void tile_store(uint8_t* lds, int tid, const uint32_t (&v)[DT_STAGE_REGS]) {
 #pragma unroll
     for (int u = 0; u < NLD; u++) {
         const int t = tid + u * DT_NT, r = t / NQ, c = t - r * NQ;
-        if (t < NROWS * NQ) *(uint2*)(lds + r * (NQ * 8) + 8 * c) = v[u];
+        if (t < NROWS * NQ) *(uint2*)(lds + r * LP + 8 * c) = make_uint2(v[2 * u], v[2 * u + 1]);
     }
+}
+// The 16-byte form, for a window that lies inside the level (rows in [0, h), bytes in [0, pitch)) with a 16-byte aligned base, pitch
+// and first column.  NP consecutive threads own the NP 16-byte pieces of a row and the workgroup covers DT_NT / NP rows per trip, so
+// row and column are decomposed once per thread (tile_lane16: the only division) and every further load is one add of a constant stride
+// on a 32-bit offset - no clamps, no 64-bit multiply.  Only the rows and pieces a keypoint of the tile can sample are staged
+// (nrows, ncols: the window bounded by the level's border region): a thread past the last piece, and a trip past the last row,
+// stores nothing and re-reads a line it or its neighbour has just read.
+typedef uint32_t dt_u32x4 __attribute__((ext_vector_type(4)));
+// goff / loff: byte offset of the thread's first piece from the level's base / inside the LDS tile; rows_left: rows from the thread's
+// first row to the end of the window (<= 0: nothing to store); last: byte offset of the thread's last row from its first.  Every
+// load is unconditional - a trip past the thread's last row reads that row again, a thread without a piece the window's first
+// piece - so that all of them are in flight together; only the stores are predicated.
+template <int NP>
+__device__ __forceinline__ void tile_lane16(int pitch, int ry0, int cx_al, int nrows, int ncols, int tid, uint32_t& goff, uint32_t& loff, int& rows_left,
+                                            uint32_t& last) {
+    const int g = tid / NP, l = tid - g * NP;
+    const bool on = g < DT_NT / NP && 16 * l < ncols && g < nrows;
+    rows_left = on ? nrows - g : 0;
+    goff = (uint32_t)(ry0 * pitch + cx_al) + (on ? (uint32_t)(g * pitch + 16 * l) : 0u);
+    loff = (uint32_t)(g * (NP * 16) + 16 * l);
+    last = on ? (uint32_t)((rows_left - 1) / (DT_NT / NP) * (DT_NT / NP) * pitch) : 0u;
+}
+template <int NP, int NLD>
+__device__ __forceinline__ void tile_issue16(const uint8_t* img, int pitch, uint32_t goff, uint32_t last, uint32_t (&v)[DT_STAGE_REGS]) {
+#pragma unroll
+    for (int u = 0; u < NLD; u++) {
+        const dt_u32x4 d = *(const dt_u32x4*)(img + (goff + min((uint32_t)(u * (DT_NT / NP) * pitch), last)));
+        v[4 * u] = d.x; v[4 * u + 1] = d.y; v[4 * u + 2] = d.z; v[4 * u + 3] = d.w;
+    }
+}
+template <int NP, int NLD>
+__device__ __forceinline__ void tile_store16(uint8_t* lds, uint32_t loff, int rows_left, const uint32_t (&v)[DT_STAGE_REGS]) {
+#pragma unroll
+    for (int u = 0; u < NLD; u++)
+        if (u * (DT_NT / NP) < rows_left) *(dt_u32x4*)(lds + loff + u * (DT_NT / NP) * (NP * 16)) = dt_u32x4{v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]};
 }
 // rows that are not 8-byte aligned (a caller image whose width is not a multiple of 8): bytes
 __device__ __forceinline__ void tile_load_bytes(const uint8_t* img, int pitch, int w, int h, int ry0, int nrows, int cx0, int lp, uint8_t* lds, int tid) {
@@ -1491,7 +1558,7 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
                                               uint8_t* __restrict__ desc, int cap, int* __restrict__ counts, int* flags,
                                               const uint32_t* __restrict__ icw, int* __restrict__ todo) {
     // ONE tile buffer: the raw tile (intensity centroid, phase A) is replaced by the blurred tile (rBRIEF, phase C) once phase A is
-    // done; the blurred tile's loads are in flight since the prologue and wait in registers (18 per thread)
+    // done; the blurred tile's loads are issued behind phase A and wait in the registers the raw tile's used (vs)
     __shared__ __attribute__((aligned(16))) uint8_t s_tile[HAS_DESC ? DT_BLR_ROWS * DT_BLR_P : DT_RAW_ROWS * DT_RAW_P];
     __shared__ __attribute__((aligned(16))) float4 s_pat[HAS_DESC ? 256 : 1];  // rBRIEF pattern as floats, [test k of a lane][lane]
     __shared__ uint32_t s_list[DT_LIST];  // index in the chunk | dx << 9 | dy << 17
@@ -1528,27 +1595,44 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
     const uint8_t* bl = blur + (size_t)frame * P.blur_stride + P.lv[L].boff;
     const bool al_raw = (lpitch & 7) == 0 && (((size_t)img) & 7) == 0;
     const bool al_blr = (((size_t)bl) & 7) == 0;  // (blurred rows have a pitch of a multiple of 16)
-    const int xr_al = al_raw ? (x0 - 15) & ~7 : x0 - 15, lead_r = (x0 - 15) - xr_al;   // raw tile column 0 = level column xr_al
-    const int xb_al = al_blr ? (x0 - 19) & ~7 : x0 - 19;
+    // the window a keypoint of this tile can sample: the tile cut to the level's border region, plus the halo.  The 16-byte form
+    // (w16_*) takes it when base, pitch and first column are 16-byte aligned and it lies inside the level - with edge_threshold >= 19
+    // every tile of such a level, the last tile column and row staging only their part; otherwise the clamped 8-byte form (al_*)
+    // or bytes stage the full window
+    const int nkc = min(DT_W, P.lv[L].bx0 + P.lv[L].bw - x0), nkr = min(DT_H, P.lv[L].by0 + P.lv[L].bh - y0);
+    const int lead_r16 = (x0 - 15) & 15, lead_b16 = (x0 - 19) & 15;
+    const int ncols_r = lead_r16 + nkc + 30, ncols_b = lead_b16 + nkc + 38;
+    const bool w16_raw = !RARE && ((lpitch | (int)(size_t)img) & 15) == 0 && y0 - 15 >= 0 && y0 + nkr + 15 <= lh && x0 - 15 - lead_r16 >= 0 &&
+                         x0 - 15 - lead_r16 + ((ncols_r + 15) & ~15) <= lpitch;
+    const bool w16_blr = !RARE && ((lbpitch | (int)(size_t)bl) & 15) == 0 && y0 - 19 >= 0 && y0 + nkr + 19 <= lh && x0 - 19 - lead_b16 >= 0 &&
+                         x0 - 19 - lead_b16 + ((ncols_b + 15) & ~15) <= lbpitch;
+    const int xr_al = w16_raw ? x0 - 15 - lead_r16 : al_raw ? (x0 - 15) & ~7 : x0 - 15, lead_r = (x0 - 15) - xr_al;   // raw tile column 0 = level column xr_al
+    const int xb_al = w16_blr ? x0 - 19 - lead_b16 : al_blr ? (x0 - 19) & ~7 : x0 - 19;
     const FinalKp* fin = fin_all + (size_t)frame * P.fin_stride + P.lv[L].fin_off;
     // ---- the prologue's global reads, in flight together: the first chunk of the level's list, the raw tile (empty tiles are rare: it is
-    //      loaded unconditionally), the lane's centroid weights, the pattern
+    //      loaded unconditionally), the pattern
     FinalKp fk[DT_CHUNK / DT_NT];
-    uint2 vr[DT_RAW_LD], vb[DT_BLR_LD];  // (vb stays unused, and is dropped by the compiler, without descriptors)
+    uint32_t vs[DT_STAGE_REGS];  // the raw tile's loads, later the blurred tile's
+    uint32_t goff = 0, loff = 0, last = 0;
+    int rows_left = 0;
     if (!RARE) {
 #pragma unroll
         for (int u = 0; u < DT_CHUNK / DT_NT; u++) fk[u] = fin[min(tid + u * DT_NT, nL - 1)];
-        if (al_raw) tile_issue<DT_RAW_ROWS, DT_RAW_P / 8, DT_RAW_LD>(img, lpitch, lh, y0 - 15, xr_al, tid, vr);
+        if (w16_raw) {
+            tile_lane16<DT_RAW_NP>(lpitch, y0 - 15, xr_al, nkr + 30, ncols_r, tid, goff, loff, rows_left, last);
+            tile_issue16<DT_RAW_NP, DT_RAW_LD16>(img, lpitch, goff, last, vs);
+        } else if (al_raw) tile_issue<DT_RAW_ROWS, DT_RAW_NQ, DT_RAW_LD>(img, lpitch, lh, y0 - 15, xr_al, tid, vs);
     }
     // the two disc rows of this lane: rows gl and 30 - gl of the 31 (lane 15: row 15 once) have the same half-width, hence the same
-    // weight bytes (u + 16 inside the disc) and mask bytes (1 inside): 16 registers, fetched once per workgroup
+    // weight bytes (u + 16 inside the disc) and mask bytes (1 inside): 16 registers, fetched once per workgroup - AFTER the raw tile
+    // has left its registers for LDS (beside the tile's loads they cost the sixth wavefront per SIMD), in flight over the list phase
     uint32_t wt[8], mk[8];
-    {
+    auto load_icw = [&]() {
         const uint4* w = (const uint4*)(icw + gl * 16);
         const uint4 w0 = w[0], w1 = w[1], k0 = w[2], k1 = w[3];
         wt[0] = w0.x; wt[1] = w0.y; wt[2] = w0.z; wt[3] = w0.w; wt[4] = w1.x; wt[5] = w1.y; wt[6] = w1.z; wt[7] = w1.w;
         mk[0] = k0.x; mk[1] = k0.y; mk[2] = k0.z; mk[3] = k0.w; mk[4] = k1.x; mk[5] = k1.y; mk[6] = k1.z; mk[7] = k1.w;
-    }
+    };
     if (HAS_DESC && tid < 256 && DT_NT >= 256) {  // thread t = lane l, test k of the lane: pattern row 16 l + k -> s_pat[k][l]
         const int l = tid & 15, k = tid >> 4;
         const int8_t* pt = &c_pattern[(l * 16 + k) * 4];
@@ -1654,8 +1738,10 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
     if (!RARE) {
         // ---- the common case in one pass: raw tile -> LDS, list, phase A, blurred tile over the raw one, phases B and C
         if (tid == 0) s_n = 0;
-        if (al_raw) tile_store<DT_RAW_ROWS, DT_RAW_P / 8, DT_RAW_LD>(s_tile, tid, vr);
+        if (w16_raw) tile_store16<DT_RAW_NP, DT_RAW_LD16>(s_tile, loff, rows_left, vs);
+        else if (al_raw) tile_store<DT_RAW_ROWS, DT_RAW_NQ, DT_RAW_P, DT_RAW_LD>(s_tile, tid, vs);
         else tile_load_bytes(img, lpitch, lw, lh, y0 - 15, DT_RAW_ROWS, xr_al, DT_RAW_P, s_tile, tid);
+        load_icw();
         __syncthreads();
         select(0, -1);
         __syncthreads();
@@ -1669,16 +1755,21 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
         if (HAS_DESC) {
             // the blurred tile's loads are issued HERE, not in the prologue (held in registers through phase A they cost 18 VGPRs and the
             // sixth wavefront per SIMD: 91 -> 73); they are in flight during the barrier and the sincos phase
-            if (al_blr) tile_issue<DT_BLR_ROWS, DT_BLR_P / 8, DT_BLR_LD>(bl, lbpitch, lh, y0 - 19, xb_al, tid, vb);
+            if (w16_blr) {
+                tile_lane16<DT_BLR_NP>(lbpitch, y0 - 19, xb_al, nkr + 38, ncols_b, tid, goff, loff, rows_left, last);
+                tile_issue16<DT_BLR_NP, DT_BLR_LD16>(bl, lbpitch, goff, last, vs);
+            } else if (al_blr) tile_issue<DT_BLR_ROWS, DT_BLR_NQ, DT_BLR_LD>(bl, lbpitch, lh, y0 - 19, xb_al, tid, vs);
             __syncthreads();  // phase A is done with the raw tile, the angles are in the list
             phase_b(n0);
-            if (al_blr) tile_store<DT_BLR_ROWS, DT_BLR_P / 8, DT_BLR_LD>(s_tile, tid, vb);
+            if (w16_blr) tile_store16<DT_BLR_NP, DT_BLR_LD16>(s_tile, loff, rows_left, vs);
+            else if (al_blr) tile_store<DT_BLR_ROWS, DT_BLR_NQ, DT_BLR_P, DT_BLR_LD>(s_tile, tid, vs);
             else tile_load_bytes(bl, lbpitch, lw, lh, y0 - 19, DT_BLR_ROWS, xb_al, DT_BLR_P, s_tile, tid);
             __syncthreads();
             phase_c(0, n0);
         }
         return;
     }
+    load_icw();
     // ---- the rare case: chunks of DT_CHUNK records, each as DT_CHUNK / DT_NT passes over DT_NT records
     for (int c0 = 0; c0 < nL; c0 += DT_CHUNK) {
 #pragma unroll
