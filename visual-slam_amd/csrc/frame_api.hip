@@ -12,6 +12,7 @@
 //                      (tracker.py:214-254) in ONE call with one synchronisation.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 #include "common.h"
@@ -211,6 +212,20 @@ static int resolve_frame(mo_ctx* c, const mo_frame_ref* f, int keep, uint8_t* hs
     return MO_OK;
 }
 
+// the caller's arrays where a stage did not run: no neighbour (-1 at INT32_MAX, as the matcher leaves a missing one; `matches`: an empty
+// frame, matcher.py:57-61), no consensus, no map point.  Every array a caller handed in is defined on return, whatever route the call took.
+static void pair_out_blank(mo_pair_out* out, int n1, bool track, bool matches) {
+    if (matches) {
+        if (out->match_idx) std::fill_n(out->match_idx, (size_t)n1 * 2, (int32_t)-1);
+        if (out->match_dist) std::fill_n(out->match_dist, (size_t)n1 * 2, INT32_MAX);
+        if (out->match_pass) std::memset(out->match_pass, 0, (size_t)n1);
+    }
+    if (track) return;  // (sel_idx / sel_dist / inlier hold n_sel rows)
+    if (out->inlier) std::memset(out->inlier, 0, (size_t)n1);
+    if (out->ransac) std::memset(out->ransac, 0, (size_t)n1);
+    if (out->X) std::fill_n(out->X, (size_t)n1 * 3, NAN);
+}
+
 extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_frame_ref* f2, const mo_pair_params* pp, mo_pair_out* out) {
     if (!c) return MO_ERR_ARG;
     if (!f1 || !f2 || !pp || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
@@ -249,7 +264,11 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
     if ((rc = resolve_frame(c, f1, mo_slot_of(c, f2->token), hs, hs_dev, 0, &s1, &n1, &out->token1))) return rc;
     if ((rc = resolve_frame(c, f2, s1, hs, hs_dev, mo_align(up_bytes, 256), &s2, &n2, &out->token2))) return rc;
     out->n1 = n1; out->n2 = n2;
-    if (n1 == 0 || n2 == 0) { HIPCHK(c, hipStreamSynchronize(c->stream)); return MO_OK; }  // (matcher.py:57-61: no matches)
+    if (n1 == 0 || n2 == 0) {  // (matcher.py:57-61: no matches)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        pair_out_blank(out, n1, track, true);
+        return MO_OK;
+    }
     mo_stage_mark(c, "h2d");
     c->flags_cur = mo_host_flags(c);
     HIPCHK(c, hipMemsetAsync(mo_host_flags(c), 0, 4 * sizeof(int), c->stream));
@@ -325,6 +344,6 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
         if (out->inlier) std::memcpy(out->inlier, hs + o_inl, (size_t)n1);
         if (out->ransac) std::memcpy(out->ransac, hs + o_ran, (size_t)n1);
         if (out->X) std::memcpy(out->X, hs + o_X, (size_t)n1 * 3 * sizeof(float));
-    }
+    } else pair_out_blank(out, n1, false, false);  // n_hyp == 0: the matcher alone
     return MO_OK;
 }

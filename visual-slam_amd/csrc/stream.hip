@@ -147,8 +147,11 @@ extern "C" mo_stream* mo_stream_create(mo_ctx* c, const mo_orb_params* orb, cons
     s->o_flags = L.take(16); s->o_counts = L.take(B * 4); s->o_kps = L.take(B * cap * sizeof(mo_keypoint)); s->o_desc = L.take(B * cap * 32);
     s->o_sel = L.take(P * cap * 8); s->o_seld = L.take(P * cap * 4); s->o_seln = L.take(P * 4);
     s->o_pose = L.take(P * 12 * sizeof(double)); s->o_mask = L.take(P * cap); s->o_npts = L.take(P * 4);
+    // the optional parts last, the map points AHEAD of the knn lists: one download [0, upto) then serves every combination - a
+    // MO_MODE_TRACK stream without want_matches stops in front of the knn lists and still carries the points it was asked for (a stream
+    // without want_points has no points region: that download is as long as it ever was)
+    s->o_pts = L.take(p->want_points ? P * cap * 3 * sizeof(float) : 0);
     s->o_midx = L.take(P * cap * 8); s->o_mdist = L.take(P * cap * 8); s->o_mpass = L.take(P * cap);
-    s->o_pts = L.take(p->want_points ? P * cap * 3 * sizeof(float) : 16);
     s->out_bytes = L.total;
     bool ok = hipStreamCreateWithFlags(&s->copy_s, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&s->down_s, hipStreamNonBlocking) == hipSuccess;
     for (Lane& l : s->lane) {
@@ -237,7 +240,7 @@ extern "C" int mo_stream_submit(mo_stream* s, const uint8_t* frames, int n, int 
     // ... on a THIRD stream: the compute stream goes straight on to the next chunk, and the upload stream is never held up behind a
     // download that waits for a compute (one copy stream for both directions serialised upload (k + 1) behind compute (k): 38 k frames/s
     // at any chunk size)
-    const size_t upto = s->p.mode == MO_MODE_TRACK && !s->p.want_matches ? s->o_midx : s->p.want_points ? s->out_bytes : s->o_pts;
+    const size_t upto = s->p.mode == MO_MODE_TRACK && !s->p.want_matches ? s->o_midx : s->out_bytes;  // (the points lie in front of o_midx)
     SCHK(s, hipEventRecord(l.computed, c->stream));
     SCHK(s, hipStreamWaitEvent(s->down_s, l.computed, 0));
     // This call, 4 us as a rule, holds the host for 5.6 - 7.3 ms at chunks 2, 6 and 11 of the FIRST stream of a process and never again (later

@@ -558,8 +558,11 @@ class Context:
         """q (nq,32) or (B,nq,32), t likewise -> idx (..,nq,2) i32, dist (..,nq,2) i32, pass (..,nq) bool"""
         if getattr(q, "ndim", 0) == 2 and _resident:
             tq, tt = resident_token(self, q), resident_token(self, t)
-            if tq and tt:  # both frames are still on the device: the matcher alone through the pair call, nothing uploaded
-                r = self.pair_frontend(_resident_kps(q), q, _resident_kps(t), t, MODE_INIT, np.eye(3), ratio=ratio, n_hyp=0, token1=tq, token2=tt)
+            kq, kt = _resident_kps(q), _resident_kps(t)
+            # both frames are still on the device: the matcher alone through the pair call, nothing uploaded.  (A caller that dropped the
+            # keypoint arrays - `_, des = detect_and_compute(img)` - has only descriptors left: the upload path below needs nothing else)
+            if tq and tt and kq is not None and kt is not None:
+                r = self.pair_frontend(kq, q, kt, t, MODE_INIT, np.eye(3), ratio=ratio, n_hyp=0, token1=tq, token2=tt)
                 return r["idx"], r["dist"], r["keep"]
         q = np.ascontiguousarray(q, np.uint8)
         t = np.ascontiguousarray(t, np.uint8)

@@ -162,9 +162,11 @@ def _view(ptr, shape, dtype):
 class FrameStream:
     def __init__(self, K, width=640, height=480, channels=1, chunk=64, n_features=2000, cap=None, detector=DETECT_ORB, mode=MODE_TRACK,
                  ratio=0.75, disp_frac=0.02, thr_px=None, n_hyp=4096, seed=4096, prm=None, device=0, want_matches=False, want_points=False,
-                 copy=True):
+                 copy=True, pair_index_base=0):
         """copy=True: every yielded array is the caller's own (a copy out of the pinned result buffer); copy=False: views that stay valid
-        until two more chunks have been submitted (the benchmark's rate without the per-frame copies)"""
+        until two more chunks have been submitted (the benchmark's rate without the per-frame copies).  pair_index_base: global index of
+        the sequence's first pair (a stream that takes a longer sequence up at frame b passes b: sampling streams and PairResult.pair_index
+        then are those of the whole sequence)"""
         self.prm = prm if prm is not None else orb_params(nfeatures=n_features)
         self.cap = int(cap or ((self.prm.nfeatures + 48 + 63) // 64 * 64))   # (retainBest keeps ties: a few rows beyond nfeatures)
         self.chunk, self.w, self.h, self.ch, self.mode, self.copy = int(chunk), int(width), int(height), int(channels), int(mode), bool(copy)
@@ -176,7 +178,7 @@ class FrameStream:
         Kc = np.ascontiguousarray(K, np.float64).reshape(9)
         for i in range(9):
             sp.K[i] = Kc[i]
-        sp.n_hyp, sp.seed, sp.pair_index_base = int(n_hyp), int(seed), 0
+        sp.n_hyp, sp.seed, sp.pair_index_base = int(n_hyp), int(seed), int(pair_index_base)
         sp.want_matches, sp.want_points = int(bool(want_matches) or mode == MODE_INIT), int(bool(want_points))
         self.sp = sp
         self.h_stream = self.ctx.lib.mo_stream_create(self.ctx.h, C.byref(self.prm), C.byref(sp))
@@ -201,11 +203,22 @@ class FrameStream:
 
     # ---- chunk level -----------------------------------------------------------------------------------------------------
     def submit(self, block):
-        """block: (n, H, W[, 3]) uint8, n <= chunk; returns without waiting for the GPU"""
-        a = np.ascontiguousarray(block, np.uint8)
-        if a.shape[1] != self.h or a.shape[2] != self.w or (a.ndim == 4) != (self.ch == 3):
+        """block: (n, H, W[, 3]) uint8, n <= chunk; returns without waiting for the GPU.  A view with dense pixels and uniform row and
+        frame strides (a window of a larger stack) is staged straight from where it lies; anything else is made contiguous first."""
+        a = np.asarray(block)
+        if a.ndim not in (3, 4) or a.shape[1] != self.h or a.shape[2] != self.w or (a.ndim == 4) != (self.ch == 3) or (a.ndim == 4 and a.shape[3] != 3):
             raise ValueError("frames of shape %s do not fit the stream (%d x %d x %d)" % (a.shape[1:], self.h, self.w, self.ch))
-        rc = self.ctx.lib.mo_stream_submit(self.h_stream, a.ctypes.data_as(C.c_void_p), int(a.shape[0]), 0, 0)
+        row = self.w * self.ch
+        dense_px = a.dtype == np.uint8 and a.strides[-1] == 1 and (a.ndim == 3 or a.strides[2] == 3)
+        stride = frame_stride = 0                      # (0: dense)
+        if a.dtype == np.uint8 and a.flags.c_contiguous:
+            pass
+        # (any positive frame stride will do, one below h * stride too: overlapping windows are only read)
+        elif dense_px and row <= a.strides[1] < 2 ** 31 and (a.shape[0] == 1 or a.strides[0] > 0):
+            stride, frame_stride = int(a.strides[1]), (int(a.strides[0]) if a.shape[0] > 1 else 0)
+        else:
+            a = np.ascontiguousarray(a, np.uint8)
+        rc = self.ctx.lib.mo_stream_submit(self.h_stream, a.ctypes.data_as(C.c_void_p), int(a.shape[0]), stride, frame_stride)
         if rc != MO_OK:
             raise NativeError(rc, self.ctx.lib.mo_stream_last_error(self.h_stream).decode())
         self._in_flight += 1
@@ -248,7 +261,7 @@ class FrameStream:
         c.ok = (finite & (c.seln >= 8)) if c.track else finite   # tracker.py:234: fewer than 8 kept matches -> no pose
         c.stream, c.serial = self, self._submitted - self._in_flight   # (index of this chunk + 1 among the submitted ones)
         c.off = 1 if r.first_pair == r.first_frame else 0   # first chunk: frame row 0 has no pair in front of it
-        c.prev_count, c.first_frame, c.first_pair = int(r.prev_count), int(r.first_frame), int(r.first_pair)
+        c.prev_count, c.first_frame, c.first_pair = int(r.prev_count), int(r.first_frame), int(r.first_pair) + int(self.sp.pair_index_base)
         first = c.first_frame
         return [FrameResult(first + f, c, f) for f in range(nf)]
 
