@@ -955,7 +955,13 @@ int mo_dbg_blur_level(mo_ctx*, int frame, int level, uint8_t* out /* lw*lh */, i
 int mo_dbg_fast_level(mo_ctx*, const mo_orb_params*, const uint8_t* gray, int w, int h, int level,
                       int32_t* xys /* [cap][3] */, int cap, int* n);
 int mo_dbg_min_eigen(mo_ctx*, const uint8_t* gray, int w, int h, float* eig /* [h*w] */);
-int mo_dbg_set_poison(mo_ctx*, int byte /* 0..255: the pyramid buffers are filled with it before every extraction; -1: off */);
+/* byte 0..255: every device block the library allocates from now on is filled with it before its first use, and every scratch buffer -
+   the pyramid buffers among them - is filled with it over its whole capacity at the start of every call: the context's and the plan's
+   at every host and mo_dev_* entry point, a map's at every mo_map_* call on it, a stream lane's at every submit.  Scratch is what no
+   call may read before its own chain wrote it; no result may move.  -1 (the default): off.  Either way the totals below start at 0. */
+int mo_dbg_set_poison(mo_ctx*, int byte);
+/* buffers and bytes filled since the last mo_dbg_set_poison (either may be NULL) */
+int mo_dbg_poison_filled(mo_ctx*, int64_t* n_buffers, int64_t* n_bytes);
 int mo_dbg_retain_best(mo_ctx*, const float* resp, int n, int n_points, int select_order, int32_t* order, int* n_out);
 
 #ifdef __cplusplus

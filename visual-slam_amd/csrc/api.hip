@@ -40,7 +40,7 @@ static int check_flags(mo_ctx* c) {
 
 extern "C" int mo_dev_status(mo_ctx* c, int32_t flags[4]) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     int f[4] = {0, 0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(f, c->d_flags, sizeof(f), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 4 * sizeof(int), c->stream));
@@ -60,10 +60,8 @@ int mo_run_extract(mo_ctx* c, const mo_orb_params* p, const uint8_t* d_gray, int
     // host calls check their own flag words before they return; mo_dev_* calls accumulate theirs until mo_dev_status
     c->flags_cur = host_call ? mo_host_flags(c) : c->d_flags;
     if (host_call == 1) HIPCHK(c, hipMemsetAsync(mo_host_flags(c), 0, 4 * sizeof(int), c->stream));  // (2: the upload kernel cleared them)
-    if (c->poison >= 0) {  // mo_dbg_set_poison (tests): whatever the margins skip must never reach a result
-        HIPCHK(c, hipMemsetAsync(c->pb.d_pyr, c->poison, (size_t)c->pb.batch_alloc * c->plan.pyr_stride, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->pb.d_blur, c->poison, (size_t)c->pb.batch_alloc * c->plan.blur_stride, c->stream));
-    }
+    // (mo_dbg_set_poison: the entry point filled d_pyr and d_blur with the rest of the scratch, and a plan built above came filled:
+    //  whatever the margins skip must never reach a result)
     if (host_call) mo_stage_mark(c, "h2d");  // (the host call opened its event set before the upload)
     else mo_stage_begin(c);
     // margins of the levels nothing in this pipeline reads (see orb_launch_blur / orb_launch_pyramid)
@@ -188,7 +186,7 @@ static bool grow_fin_slots(mo_ctx* c, int levels) {
 
 static int detect_compute_once(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch,
                                int batch, mo_keypoint* kps, uint8_t* desc, int cap, int* counts) {
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     // one frame (the drop-in classes, a Tracker): pinned staging both ways, a resident result slot, one synchronisation (frame_api.hip)
     if (batch == 1 && (size_t)w * h * ch + (size_t)cap * 60 <= (size_t)64 << 20) return mo_detect_single(c, p, img, w, h, stride, ch, kps, desc, cap, counts);
     HostClock clk(c);
@@ -256,7 +254,7 @@ extern "C" int mo_orb_compute(mo_ctx* c, const mo_orb_params* p, const uint8_t* 
                               const mo_keypoint* kps_in, int n_in, int32_t* kept_idx, uint8_t* desc, int* n_out) {
     if (!c) return MO_ERR_ARG;
     if (!p || !n_out || (n_in > 0 && (!kps_in || !kept_idx || !desc))) return mo_fail(c, MO_ERR_ARG, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     *n_out = 0;
     // host-side list logic of Feature2D::compute / ORB_Impl::detectAndCompute(useProvidedKeypoints):
     // level count from the octaves, border filter on the full image, regroup by octave when unsorted
@@ -321,7 +319,7 @@ extern "C" int mo_dev_undistort(mo_ctx* c, const uint8_t* d_src, int w, int h, i
     if (!d_src || !d_dst || !K || !dist || d_src == d_dst) return mo_fail(c, MO_ERR_ARG, "NULL argument (or in-place)");
     if (w < 1 || h < 1 || batch < 1 || (ch != 1 && ch != 3)) return mo_fail(c, MO_ERR_ARG, "bad size / channel count");
     if (!(K[0] != 0.0) || !(K[4] != 0.0)) return mo_fail(c, MO_ERR_ARG, "focal length is zero");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     return undistort_launch(c, d_src, d_dst, w, h, ch, batch, K, dist);
 }
 
@@ -331,7 +329,7 @@ extern "C" int mo_undistort(mo_ctx* c, const uint8_t* img, int w, int h, int str
     if (!img || !out || !K || !dist) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (w < 1 || h < 1 || (ch != 1 && ch != 3) || stride < w * ch) return mo_fail(c, MO_ERR_ARG, "bad size / stride / channel count");
     if (!(K[0] != 0.0) || !(K[4] != 0.0)) return mo_fail(c, MO_ERR_ARG, "focal length is zero");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     const size_t row = (size_t)w * ch, frame = row * h;
     Layout L;
     const size_t o_src = L.take(frame), o_dst = L.take(frame);
@@ -389,7 +387,7 @@ extern "C" int mo_orb_grid_good_features(mo_ctx* c, const uint8_t* img, int w, i
                                          float* xy, int* n_out) {
     if (!c) return MO_ERR_ARG;
     if (!img || !xy || !n_out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     return gftt_run(c, img, w, h, stride, ch, n_features, xy, n_out, nullptr);
 }
 
@@ -401,7 +399,7 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
                                           int n_features, float* xy, int* n_xy, int32_t* kept_idx, uint8_t* desc, int* n_kept) {
     if (!c) return MO_ERR_ARG;
     if (!p || !img || !xy || !n_xy || !kept_idx || !desc || !n_kept) return mo_fail(c, MO_ERR_ARG, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     HostClock clk(c);
     *n_xy = 0; *n_kept = 0;
     c->last_token = 0;
@@ -479,12 +477,20 @@ extern "C" int mo_orb_grid_detect_compute(mo_ctx* c, const mo_orb_params* p, con
 extern "C" int mo_dbg_set_poison(mo_ctx* c, int byte) {
     if (!c) return MO_ERR_ARG;
     c->poison = byte < 0 ? -1 : (byte & 255);
+    c->poison_bufs = 0; c->poison_bytes = 0;
+    return MO_OK;
+}
+
+extern "C" int mo_dbg_poison_filled(mo_ctx* c, int64_t* n_buffers, int64_t* n_bytes) {
+    if (!c) return MO_ERR_ARG;
+    if (n_buffers) *n_buffers = c->poison_bufs;
+    if (n_bytes) *n_bytes = c->poison_bytes;
     return MO_OK;
 }
 
 extern "C" int mo_dbg_min_eigen(mo_ctx* c, const uint8_t* gray, int w, int h, float* eig) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     return gftt_run(c, gray, w, h, w, 1, 64, nullptr, nullptr, eig);
 }
 
@@ -494,7 +500,7 @@ extern "C" int mo_match_knn2_ratio(mo_ctx* c, const uint8_t* q, int nq, const ui
     if (nq < 0 || nt < 0 || batch < 1) return mo_fail(c, MO_ERR_ARG, "bad sizes");
     if (nq == 0) return MO_OK;
     if (!q || !train_idx || !dist || !pass || (nt > 0 && !t)) return mo_fail(c, MO_ERR_ARG, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     HostClock clk(c);
     size_t qb = (size_t)batch * nq * 32, tb = (size_t)batch * std::max(nt, 1) * 32, n = (size_t)batch * nq;
     int rc;
@@ -551,7 +557,7 @@ extern "C" int mo_init_two_view(mo_ctx* c, const float* p1, const float* p2, int
     if (!c) return MO_ERR_ARG;
     if (!p1 || !p2 || !K || !R || !t || !inlier || !X || !n_good) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (m < 0) return mo_fail(c, MO_ERR_ARG, "m must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     *n_good = 0;
     if (m < 8) {
         for (int i = 0; i < 9; i++) R[i] = NAN;
@@ -607,7 +613,7 @@ extern "C" int mo_recover_pose(mo_ctx* c, const double E[9], const float* p1, co
                                const uint8_t* mask_in, double R[9], double t[3], uint8_t* mask_out, float* X, int* n_good) {
     if (!c) return MO_ERR_ARG;
     if (!E || !K || !R || !t || !n_good || m < 0 || (m > 0 && (!p1 || !p2 || !mask_out))) return mo_fail(c, MO_ERR_ARG, "NULL / negative argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     *n_good = 0;
     for (int i = 0; i < 9; i++) R[i] = NAN;
     for (int i = 0; i < 3; i++) t[i] = NAN;
@@ -651,7 +657,7 @@ extern "C" int mo_find_fundamental(mo_ctx* c, const float* p1, const float* p2, 
     (void)prob;
     if (!c) return MO_ERR_ARG;
     if (!F || !n_inliers || m < 0 || (m > 0 && (!p1 || !p2 || !mask))) return mo_fail(c, MO_ERR_ARG, "NULL / negative argument");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     *n_inliers = 0;
     for (int i = 0; i < 9; i++) F[i] = NAN;
     if (m < 8) { if (m > 0) std::memset(mask, 0, (size_t)m); return MO_OK; }
@@ -712,7 +718,7 @@ extern "C" int mo_triangulate_points(mo_ctx* c, const double P1[12], const doubl
     if (!c) return MO_ERR_ARG;
     if (n < 0 || !P1 || !P2 || (n > 0 && (!p1 || !p2 || !X4))) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (n == 0) return MO_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     const size_t pb = (size_t)n * 2 * sizeof(float);
     Layout L;
     const size_t o_p1 = L.take(pb), o_p2 = L.take(pb), o_X = L.take((size_t)n * 4 * sizeof(float));
@@ -734,7 +740,7 @@ extern "C" int mo_dev_orb_detect_compute(mo_ctx* c, const mo_orb_params* p, cons
                                          mo_keypoint* d_kps, uint8_t* d_desc, int cap, int32_t* d_counts) {
     if (!c) return MO_ERR_ARG;
     if (!d_gray || !d_kps || !d_counts) return mo_fail(c, MO_ERR_ARG, "NULL device pointer");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     return mo_run_extract(c, p, d_gray, w, h, batch, d_kps, d_desc, cap, d_counts, false);
 }
 
@@ -743,7 +749,7 @@ extern "C" int mo_dev_match_pairs(mo_ctx* c, const uint8_t* d_desc, const int32_
                                   uint8_t* d_pass) {
     if (!c) return MO_ERR_ARG;
     if (!d_desc || !d_counts || !d_idx || !d_dist || !d_pass) return mo_fail(c, MO_ERR_ARG, "NULL device pointer");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     mo_stage_begin(c);
     int rc = match_launch_pairs(c, d_desc, d_desc, (size_t)cap * 32, (size_t)cap * 32, d_counts, d_qf, d_tf, 0, 0, n_pairs, cap,
                                 ratio, d_idx, d_dist, d_pass);
@@ -759,7 +765,7 @@ __global__ void k_pair_frames(int32_t* qf, int32_t* tf, int n) {
 extern "C" int mo_dev_frontend_batch(mo_ctx* c, const mo_orb_params* p, const mo_batch_io* io) {
     if (!c) return MO_ERR_ARG;
     if (!io || !io->d_gray || !io->d_kps || !io->d_desc || !io->d_counts) return mo_fail(c, MO_ERR_ARG, "NULL in mo_batch_io");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     if (io->detector != MO_DETECT_ORB && io->detector != MO_DETECT_GRID) return mo_fail(c, MO_ERR_ARG, "mo_batch_io.detector must be MO_DETECT_ORB or MO_DETECT_GRID");
     int rc = io->detector == MO_DETECT_GRID ? run_grid_extract(c, p, io)
                                             : mo_run_extract(c, p, io->d_gray, io->w, io->h, io->batch, io->d_kps, io->d_desc, io->cap, io->d_counts, false);
@@ -829,7 +835,7 @@ extern "C" int mo_dev_frontend_batch(mo_ctx* c, const mo_orb_params* p, const mo
 extern "C" int mo_dbg_pyramid_level(mo_ctx* c, const mo_orb_params* p, const uint8_t* gray, int w, int h, int level,
                                     int blurred, uint8_t* out, int* lw, int* lh) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     int rc = mo_build_plan(c, p, w, h, 1);
     if (rc) return rc;
     if (level < 0 || level >= c->plan.nlevels) return mo_fail(c, MO_ERR_ARG, "level out of range");
@@ -858,7 +864,7 @@ extern "C" int mo_dbg_pyramid_level(mo_ctx* c, const mo_orb_params* p, const uin
 
 extern "C" int mo_dbg_blur_level(mo_ctx* c, int frame, int level, uint8_t* out, int* lw, int* lh, int* resize_blur) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));  // (not MO_ENTER: what the last extraction left in d_blur is what this probe reads)
     if (!c->plan_valid) return mo_fail(c, MO_ERR_ARG, "no extraction has run on this context");
     if (level < 0 || level >= c->plan.nlevels) return mo_fail(c, MO_ERR_ARG, "level out of range");
     if (frame < 0 || frame >= c->pb.batch_alloc) return mo_fail(c, MO_ERR_ARG, "frame out of range");
@@ -874,7 +880,7 @@ extern "C" int mo_dbg_blur_level(mo_ctx* c, int frame, int level, uint8_t* out, 
 extern "C" int mo_dbg_fast_level(mo_ctx* c, const mo_orb_params* p, const uint8_t* gray, int w, int h, int level,
                                  int32_t* xys, int cap, int* n) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     int rc = mo_build_plan(c, p, w, h, 1);
     if (rc) return rc;
     if (level < 0 || level >= c->plan.nlevels) return mo_fail(c, MO_ERR_ARG, "level out of range");
@@ -904,7 +910,7 @@ extern "C" int mo_dbg_fast_level(mo_ctx* c, const mo_orb_params* p, const uint8_
 extern "C" int mo_dbg_retain_best(mo_ctx* c, const float* resp, int n, int n_points, int select_order, int32_t* order,
                                   int* n_out) {
     if (!c) return MO_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     if (n <= 0) { *n_out = 0; return MO_OK; }
     DevBuf<float> d_r; DevBuf<int32_t> d_o; DevBuf<int> d_n;  // (freed on every return)
     int rc;

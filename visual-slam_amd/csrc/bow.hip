@@ -30,9 +30,15 @@ struct BowBufs {
     DevBuf<int32_t> common;              // [n_kf] common words with the asking keyframe (mo_map_loop_candidates)
     DevBuf<int32_t> out_pos, out_n; DevBuf<double> out_score;
     DevBuf<int32_t> sel_qf, sel_tf, mrow;
+    // scratch: what every call's chain writes before it reads.  db and norm are state (the rows `done` vouches for are read by later
+    // calls); a DevBuf added above is named here or in this sentence
+    template <class F> void each_scratch(F f) {
+        f(up); f(qidx); f(qdist); f(qpass); f(score); f(common); f(out_pos); f(out_n); f(out_score); f(sel_qf); f(sel_tf); f(mrow);
+    }
 };
 
 void map_scratch_free(BowBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, BowBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // ---- block sum of int64 over 256 threads, scratch = 4 values in LDS; thread 0 holds the sum ---------------------------------------------
 __device__ __forceinline__ long long bow_block_sum(long long v, long long* red) {
@@ -267,7 +273,7 @@ extern "C" int mo_vocab_create(mo_ctx* c, const uint8_t* words, const int32_t* w
     if (n_words < 2 || n_words > MO_BOW_MAX_WORDS) return mo_fail(c, MO_ERR_ARG, "a vocabulary has 2 .. 8192 words");
     for (int w = 0; w < n_words; w++)
         if (weights[w] < 0 || weights[w] > MO_BOW_MAX_WEIGHT) return mo_fail(c, MO_ERR_ARG, "a word weight must be in 0 .. 14 * 1024");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     return vocab_make(c, words, weights, n_words, out);
 }
 
@@ -301,7 +307,7 @@ extern "C" int mo_vocab_train(mo_ctx* c, const uint8_t* desc, int32_t n, const i
     if (img_off[0] != 0 || img_off[n_img] != n) return mo_fail(c, MO_ERR_ARG, "image offsets must run from 0 to n");
     for (int i = 0; i < n_img; i++)
         if (img_off[i + 1] < img_off[i]) return mo_fail(c, MO_ERR_ARG, "image offsets must not decrease");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     std::vector<uint8_t> h_words((size_t)W * 32);
     for (int j = 0; j < W; j++) std::memcpy(&h_words[(size_t)j * 32], desc + (size_t)(((int64_t)j * n) / W) * 32, 32);
     DevBuf<uint8_t> d_desc, d_words, d_pass;
@@ -348,7 +354,7 @@ extern "C" int mo_map_set_vocabulary(mo_map* m, mo_vocab* v) {
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;
     if (v && v->c != c) return mo_fail(c, MO_ERR_ARG, "the vocabulary belongs to another context");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     map_scratch_free(m->bow);
     m->bow = nullptr;
@@ -468,7 +474,7 @@ extern "C" int mo_map_query_keyframes(mo_map* m, const mo_frame_ref* f, const mo
     if (prm->n_best > 0 && (!out->pos || !out->score)) return mo_fail(c, MO_ERR_ARG, "pos and score must hold n_best entries");
     int rc;
     if ((rc = bow_require(m))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     const int nb = prm->n_best;
     out->n = 0; out->from_token = 0;

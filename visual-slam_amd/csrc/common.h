@@ -29,7 +29,8 @@ int mo_fail(mo_ctx* c, int code, const std::string& msg);
     } while (0)
 
 // A device buffer that owns its memory: freed by its destructor, moved but never copied.  Kernels and copies receive the raw pointer
-// (the conversion).  Sizes are element counts.  Every hipMalloc / hipFree of the library is in here.
+// (the conversion).  Sizes are element counts.  Every hipMalloc / hipFree of the library is in here, and so is the one place a new
+// block is filled with the poison byte of mo_dbg_set_poison (realloc_bytes, below mo_ctx).
 template <class T> struct DevBuf {
     T* p = nullptr; size_t bytes = 0;
     DevBuf() = default;
@@ -56,16 +57,7 @@ template <class T> struct DevBuf {
         return MO_OK;
     }
 private:
-    // (the pointer and its size are dropped before the free: a failure leaves nothing that passes the size check)
-    int realloc_bytes(mo_ctx* c, size_t need) {
-        T* old = p;
-        p = nullptr; bytes = 0;
-        if (old) HIPCHK(c, hipFree(old));
-        need = std::max(need, (size_t)16);
-        HIPCHK(c, hipMalloc((void**)&p, need));
-        bytes = need;
-        return MO_OK;
-    }
+    int realloc_bytes(mo_ctx* c, size_t need);
 };
 
 // a pinned host block; a larger one replaces it once the context stream has drained (the device may still be reading the old one)
@@ -102,6 +94,9 @@ struct PlanBufs : PlanTables {
     DevBuf<int> d_fin_cnt;         // [batch][MO_MAX_LEVELS]
     DevBuf<int> d_dtodo;           // k_describe_tiles -> k_describe_tiles_rare: [0] count, then frame * tiles + tile; [1 + n_dtiles * batch * DT_SPLIT_LATENCY]
     DevBuf<uint32_t> d_fs_tab; int fs_tiles = 0, fs_stride = 0, fs_lds = 0; bool fs_ok = false; int fs_geom[10] = {}; const char* fs_why = "";  // k_front_single: per-tile headers + coefficient slices (fs_build)
+    // the work buffers no call reads before its own chain wrote them (mo_dbg_set_poison fills them at every entry point); d_tables and
+    // d_fs_tab are state: built with the plan, read by every call
+    template <class F> void each_scratch(F f) { f(d_pyr); f(d_blur); f(d_cand); f(d_strip_cnt); f(d_scratch); f(d_fin); f(d_fin_cnt); f(d_dtodo); }
 };
 
 #define MO_RESULT_SLOTS 4
@@ -119,7 +114,8 @@ struct mo_ctx {
     int max_w = 0, max_h = 0, max_batch = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     int match_mode = 0;        // VSLAM_AMD_MATCHER: 0 default (XOR + popcount, train tiles through LDS), 1 "mfma" opt-in matrix-core matcher
-    int poison = -1;           // mo_dbg_set_poison (tests): fill the pyramid buffers with that byte before every extraction
+    int poison = -1;           // mo_dbg_set_poison (tests): >= 0: every new block and, at every entry point, every scratch buffer is filled with that byte
+    int64_t poison_bufs = 0, poison_bytes = 0;  // mo_dbg_poison_filled: fills since the last mo_dbg_set_poison
     std::string err;
 
     // plan (rebuilt when w, h or the ORB parameters change)
@@ -172,7 +168,53 @@ struct mo_ctx {
     TimingSet tsets[MO_TIMING_SLOTS];
     int tcur = 0;
     bool timing = true;
+    // The context's scratch: what no call reads before its own chain wrote it.  State, and so not listed: d_flags (words 0..3 accumulate
+    // until mo_dev_status), d_slot_* (resident results), d_pair_frames (written once per size), d_comm_cnt.  A DevBuf added to this
+    // struct is named here or in that sentence.
+    template <class F> void each_scratch(F f) {
+        f(d_in); f(d_gray); f(d_kps); f(d_desc); f(d_counts); f(d_mq); f(d_mt); f(d_mpass); f(d_midx); f(d_mdist); f(d_match_part); f(d_tv);
+        f(d_stream_pts); f(d_track_keys); f(d_tmp);
+    }
 };
+
+// (the pointer and its size are dropped before the free: a failure leaves nothing that passes the size check)
+template <class T> int DevBuf<T>::realloc_bytes(mo_ctx* c, size_t need) {
+    T* old = p;
+    p = nullptr; bytes = 0;
+    if (old) HIPCHK(c, hipFree(old));
+    need = std::max(need, (size_t)16);
+    HIPCHK(c, hipMalloc((void**)&p, need));
+    bytes = need;
+    if (c->poison >= 0) {  // mo_dbg_set_poison: no owner may rely on what a fresh block holds (drained: its first use may be on any stream)
+        HIPCHK(c, hipMemsetAsync(p, c->poison, need, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->poison_bufs++; c->poison_bytes += (int64_t)need;
+    }
+    return MO_OK;
+}
+
+// mo_dbg_set_poison: one buffer filled over its whole capacity on the context stream; every buffer of a struct's each_scratch list
+template <class T> int mo_poison_buf(mo_ctx* c, DevBuf<T>& b) {
+    if (!b.p) return MO_OK;
+    HIPCHK(c, hipMemsetAsync(b.p, c->poison, b.bytes, c->stream));
+    c->poison_bufs++; c->poison_bytes += (int64_t)b.bytes;
+    return MO_OK;
+}
+template <class S> int mo_poison_scratch(mo_ctx* c, S& s) {
+    int rc = MO_OK;
+    s.each_scratch([&](auto& b) { if (!rc) rc = mo_poison_buf(c, b); });
+    return rc;
+}
+// The first line of every host and mo_dev_* entry point: the device selected and, while a poison byte is set, the context's and the
+// plan's scratch filled with it (one branch when it is not).  mo_dbg_blur_level alone selects the device itself: it reads what the last
+// extraction left in d_blur.
+inline int mo_enter(mo_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->poison < 0) return MO_OK;
+    if (int rc = mo_poison_scratch(c, *c)) return rc;
+    return mo_poison_scratch(c, c->pb);
+}
+#define MO_ENTER(c) do { if (int e__ = mo_enter(c)) return e__; } while (0)
 
 template <class T> int DevBuf<T>::regrow(mo_ctx* c, size_t n, size_t keep) {
     DevBuf q;

@@ -134,7 +134,7 @@ void mo_copy_out_launch(mo_ctx* c, const void* d_src, void* h_dst_dev, size_t by
 
 int mo_detect_single(mo_ctx* c, const mo_orb_params* p, const uint8_t* img, int w, int h, int stride, int ch, mo_keypoint* kps,
                      uint8_t* desc, int cap, int* counts) {
-    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));  // (behind detect_compute_once's MO_ENTER)
     HostClock clk(c);
     if (!img) return mo_fail(c, MO_ERR_ARG, "img is NULL");
     if (ch != 1 && ch != 3) return mo_fail(c, MO_ERR_ARG, "ch must be 1 (gray) or 3 (BGR)");
@@ -231,7 +231,7 @@ extern "C" int mo_pair_frontend(mo_ctx* c, const mo_frame_ref* f1, const mo_fram
     if (!f1 || !f2 || !pp || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (pp->mode != MO_MODE_INIT && pp->mode != MO_MODE_TRACK) return mo_fail(c, MO_ERR_ARG, "mode must be MO_MODE_INIT or MO_MODE_TRACK");
     if (pp->n_hyp < 0) return mo_fail(c, MO_ERR_ARG, "n_hyp must be >= 0 (0 = matcher only)");
-    HIPCHK(c, hipSetDevice(c->device));
+    MO_ENTER(c);
     HostClock clk(c);
     out->n_sel = 0; out->n_good = 0; out->n1 = 0; out->n2 = 0; out->token1 = 0; out->token2 = 0;
     for (int i = 0; i < 9; i++) { out->R[i] = NAN; out->E[i] = NAN; }

@@ -63,9 +63,16 @@ struct BaBufs {
     DevBuf<BaRes> res; PinnedBuf<BaRes> h_res;
     // mo_map_add_observations
     DevBuf<int32_t> ao_pt, ao_row, ao_claim, ao_cnt, ao_base, ao_total;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) {
+        f(loc); f(ecnt); f(lrank); f(ebase); f(pout); f(lpt); f(eoff); f(pn); f(pfix); f(X); f(Xt); f(Vi); f(gp); f(pc); f(pt); f(pu);
+        f(e_kf); f(e_obs); f(e_xy); f(e_info); f(e_inl); f(einl); f(kf_edge); f(kf_fidx); f(poseC); f(poseT); f(S); f(res);
+        f(ao_pt); f(ao_row); f(ao_claim); f(ao_cnt); f(ao_base); f(ao_total);
+    }
 };
 
 void map_scratch_free(BaBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, BaBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // fixed-order sums: lane 0's shuffle tree per wave (wave_sum), then the waves in order; every thread receives the result
 __device__ __forceinline__ double ba_block_sum(double v, double* lds) {
@@ -497,7 +504,7 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         if (!std::isfinite(poses[i])) return mo_fail(c, MO_ERR_ARG, "poses must be finite");
     const int lo_pos = map_window_lo(prm->window, n_kf);
     if (n_kf - std::max(lo_pos, 1) > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a window of at most 16");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     for (int i = 0; i < 3; i++) out->cost[i] = 0.0;
     out->lambda = 0.0;
@@ -638,7 +645,7 @@ extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32
     if (kf_pos < 0 || kf_pos > n_kf) return mo_fail(c, MO_ERR_ARG, "kf_pos must be a keyframe position, or the number of keyframes for the next one");
     if (n == 0 || m->n_pts == 0) return MO_OK;
     if (m->n_pts > INT32_MAX / 2 || m->n_obs + n > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     if (!m->ba) m->ba = new BaBufs();
     BaBufs& b = *m->ba;
     const size_t np = (size_t)m->n_pts;

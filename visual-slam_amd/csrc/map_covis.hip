@@ -34,9 +34,13 @@ struct CovisBufs {
     DevBuf<uint8_t> mask;                 // [n_kf] loc as bytes (the output, and k_trk_rep's local-keyframe predicate)
     DevBuf<int32_t> seeds; PinnedBuf<int32_t> h_seeds;
     DevBuf<CovisRes> res; PinnedBuf<CovisRes> h_res;
+    // all of it is scratch, W included: every reader (the three calls above, mo_map_loop_candidates) runs covis_enqueue in its own chain
+    // first (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) { f(W); f(votes); f(loc); f(mask); f(seeds); f(res); }
 };
 
 void map_scratch_free(CovisBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, CovisBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 __device__ __forceinline__ int cv_pop(unsigned long long& lo, unsigned long long& hi) {   // the lowest position of the set, removed
     if (lo) { const int p = __ffsll(lo) - 1; lo &= lo - 1; return p; }
@@ -234,7 +238,7 @@ extern "C" int mo_map_covisibility(mo_map* m, int32_t* weights, int32_t* n_kf) {
     const size_t n = m->pos_slot.size();
     *n_kf = (int32_t)n;
     if (n == 0) return MO_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     int rc;
     if ((rc = upload_pos_slot(m))) return rc;
@@ -252,7 +256,7 @@ extern "C" int mo_map_local_keyframes(mo_map* m, const mo_map_local_params* prm,
     if ((rc = covis_check(m, prm, out))) return rc;
     out->n_k1 = 0; out->n_local_kf = 0; out->ref = -1;
     if (m->pos_slot.empty()) return MO_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);

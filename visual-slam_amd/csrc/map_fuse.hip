@@ -51,9 +51,14 @@ struct FuseBufs {
     DevBuf<int32_t> mcnt, mbase, mcur, mem;   // [point] members per root, their first entry, scatter cursors, the member lists
     DevBuf<int32_t> into;                 // [point] new index of the point each old point now is
     DevBuf<FuseRes> res; PinnedBuf<FuseRes> h_res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) {
+        f(rep); f(oct); f(cell); f(sorted); f(tab); f(key); f(prop); f(parent); f(root); f(nval); f(surv); f(mcnt); f(mbase); f(mcur); f(mem); f(into); f(res);
+    }
 };
 
 void map_scratch_free(FuseBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, FuseBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // what the fuse kernels read (by value): the map, and fuse's own tables and window
 struct FuseView {
@@ -256,7 +261,7 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     if (!(prm->radius >= 0.0) || !std::isfinite(prm->radius)) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
     if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
     if (!(prm->chi2 >= 0.0)) return mo_fail(c, MO_ERR_ARG, "chi2 must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     out->n_targets = out->n_local = out->n_pairs = out->n_cand = out->n_proposals = out->n_gained = out->n_edges = out->n_absorbed = 0;
     out->n_points = m->n_pts; out->n_obs = m->n_obs;

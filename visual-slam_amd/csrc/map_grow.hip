@@ -69,9 +69,12 @@ struct GrowBufs {
     DevBuf<int32_t> point;                // [row] the new point of each target row
     PinnedBuf<int32_t> h_point; PinnedBuf<double> h_X;   // the copy-out
     DevBuf<GrowRes> res; PinnedBuf<GrowRes> h_res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) { f(pairs); f(tab); f(frow); f(key); f(prop); f(X); f(outX); f(point); f(res); }
 };
 
 void map_scratch_free(GrowBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, GrowBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // ---- host: the geometry of the pairs, in the header's operation order ---------------------------------------------------------------
 static GrowCam grow_cam(const double* T, int slot, int pos) {
@@ -358,7 +361,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     if (!(prm->epi_chi2 >= 0.0) || !(prm->chi2 >= 0.0) || !(prm->epipole_r2 >= 0.0) || !(prm->ratio_factor > 0.0))
         return mo_fail(c, MO_ERR_ARG, "epi_chi2, chi2 and epipole_r2 must be >= 0, ratio_factor > 0");
     if (!(K[0] != 0.0) || !(K[4] != 0.0)) return mo_fail(c, MO_ERR_ARG, "K: focal lengths must not be 0");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     out->n_neighbours = out->n_free = out->n_accepted = out->n_matches = out->n_new = out->n_obs_new = 0;
     out->n_epi = 0;

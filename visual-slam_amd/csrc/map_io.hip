@@ -68,7 +68,7 @@ extern "C" int mo_map_write_ply(mo_map* m, const char* path, int min_obs, int64_
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;
     if (!path) return mo_fail(c, MO_ERR_ARG, "NULL path");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     const size_t np = (size_t)m->n_pts;
     std::vector<float> xyz(np * 3);
     std::vector<uint8_t> col(np * 3);

@@ -346,6 +346,16 @@ int upload_pos_slot(mo_map* m) {
     return MO_OK;
 }
 
+int map_poison(mo_map* m) {
+    mo_ctx* c = m->c;
+    int rc;
+    if ((rc = mo_poison_scratch(c, *m)) || (rc = map_scratch_poison(c, m->rl)) || (rc = map_scratch_poison(c, m->tk)) || (rc = map_scratch_poison(c, m->ba)) ||
+        (rc = map_scratch_poison(c, m->fu)) || (rc = map_scratch_poison(c, m->gr)) || (rc = map_scratch_poison(c, m->cv)) ||
+        (rc = map_scratch_poison(c, m->bow)) || (rc = map_scratch_poison(c, m->lp)))
+        return rc;
+    return MO_OK;
+}
+
 extern "C" mo_map* mo_map_create(mo_ctx* c, int kf_slots, int kf_rows, int64_t pts_cap, int64_t obs_cap) {
     if (!c) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess) { mo_fail(c, MO_ERR_HIP, "hipSetDevice"); return nullptr; }
@@ -464,7 +474,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     mo_ctx* c = m->c;
     if (!f || !P || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (img && (w < 1 || h < 1 || (ch != 1 && ch != 3))) return mo_fail(c, MO_ERR_ARG, "image must be h x w x ch u8 with ch 1 or 3");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     int rc;
     out->n_new = 0; out->from_token = 0;
@@ -555,7 +565,7 @@ extern "C" int mo_map_add_points(mo_map* m, int n, const float* xyz, const uint8
     mo_ctx* c = m->c;
     if (n < 0 || (n > 0 && (!xyz || !col || !id || !obs_off || !dref_kf || !dref_row))) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (n == 0) return MO_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     const int64_t no = obs_off[n] - obs_off[0];
     if (no < 0 || (no > 0 && (!obs_kf || !obs_kp))) return mo_fail(c, MO_ERR_ARG, "bad observation offsets");
     int rc = map_pts_reserve(m, m->cur, (size_t)(m->n_pts + n), (size_t)(m->n_obs + no), true);
@@ -611,7 +621,7 @@ extern "C" int mo_map_download(mo_map* m, int field, void* dst, size_t bytes) {
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;
     if (!dst && bytes) return mo_fail(c, MO_ERR_ARG, "NULL destination");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     const MapPts p = m->P[m->cur].view();
     const void* src = nullptr; size_t have = 0;
     switch (field) {

@@ -46,9 +46,14 @@ struct LoopBufs {
     DevBuf<unsigned long long> claim;         // [pair][row] per train row: (distance << 32) | query row of the match that keeps it
     DevBuf<int32_t> cur, mpt, mrow;           // [row], [pair][row], [pair][row]
     DevBuf<LoopRes> res; PinnedBuf<LoopRes> h_res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) {
+        f(flag); f(acc); f(best); f(cacc); f(connected); f(group); f(qf); f(tf); f(tab); f(midx); f(mdist); f(mpass); f(claim); f(cur); f(mpt); f(mrow); f(res);
+    }
 };
 
 void map_scratch_free(LoopBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, LoopBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 __device__ __forceinline__ unsigned long long lp_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -257,7 +262,7 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
     const int p = prm->kf_pos < 0 ? n_kf - 1 : prm->kf_pos, q_slot = m->pos_slot[p], n_p = m->h_kcnt[q_slot], row = m->row;
     const int min_w = std::max(prm->min_weight, 1);
     const bool match = mc > 0, need_tab = match || out->cur_point;
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);

@@ -39,9 +39,12 @@ struct RelocBufs {
     DevBuf<int32_t> cq, cp; DevBuf<uint8_t> cinl;         // [candidate][row] C_k (query, point), final inliers
     DevBuf<int32_t> qpt; DevBuf<uint8_t> qinl;            // [row] per query keypoint
     DevBuf<RelocRes> res; PinnedBuf<RelocRes> h_res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) { f(tab); f(qf); f(midx); f(mdist); f(mpass); f(score); f(cq); f(cp); f(cinl); f(qpt); f(qinl); f(res); }
 };
 
 void map_scratch_free(RelocBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, RelocBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // the row of the matcher outputs that holds keyframe position k: k itself when every keyframe was matched (mrow NULL), else the pair the
 // preselection gave it, -1: not matched
@@ -286,7 +289,7 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         for (int i = 0; i < 9; i++) { g.K[i] = K[i]; g.Kinv[i] = inv[i] / det; }
         g.thr2 = prm->thr_px * prm->thr_px;
     }
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     const int nc = prm->max_candidates;
     for (int i = 0; i < 12; i++) out->pose[i] = NAN;

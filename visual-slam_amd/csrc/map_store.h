@@ -52,6 +52,15 @@ void map_scratch_free(GrowBufs* b);
 void map_scratch_free(CovisBufs* b);
 void map_scratch_free(BowBufs* b);
 void map_scratch_free(LoopBufs* b);
+// mo_dbg_set_poison: the struct's each_scratch list filled (null: the feature has not run yet), each next to its struct
+int map_scratch_poison(mo_ctx* c, RelocBufs* b);
+int map_scratch_poison(mo_ctx* c, TrackBufs* b);
+int map_scratch_poison(mo_ctx* c, BaBufs* b);
+int map_scratch_poison(mo_ctx* c, FuseBufs* b);
+int map_scratch_poison(mo_ctx* c, GrowBufs* b);
+int map_scratch_poison(mo_ctx* c, CovisBufs* b);
+int map_scratch_poison(mo_ctx* c, BowBufs* b);
+int map_scratch_poison(mo_ctx* c, LoopBufs* b);
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -92,6 +101,13 @@ struct mo_map {
     CovisBufs* cv = nullptr;
     BowBufs* bow = nullptr;
     LoopBufs* lp = nullptr;
+    // The map's own scratch: what no call reads before its own chain wrote it.  State, and so not listed: the keyframe store (kkps, kdesc,
+    // kcnt, kP), d_pos_slot, img, both copies of the map store P, loff / lids, kf_red, and st, whose ST_NPTS / ST_NOBS / ST_NNEW words
+    // carry the live counts from one call to the next.  A DevBuf added to this struct is named here or in that sentence.
+    template <class Fn> void each_scratch(Fn f) {
+        f(keep); f(kobs); f(rank); f(obase); f(part); f(ent_id); f(hist); f(hbase); f(first);
+        f(midx); f(mdist); f(mpass); f(inl); f(gpts); f(F); f(gnp);
+    }
     // (mo_map_destroy selects the device and drains the stream first)
     ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); map_scratch_free(lp); }
 };
@@ -235,6 +251,14 @@ inline int map_window_lo(int window, int n_kf) { return window > 0 && window < n
 inline int map_int32_guard(mo_map* m) {
     return m->n_pts > INT32_MAX / 2 || m->n_obs > INT32_MAX / 2 ? mo_fail(m->c, MO_ERR_CAPACITY, "map larger than int32 indexing") : MO_OK;
 }
+// The first line of every mo_map_* call that touches the device: mo_enter (common.h) and, while a poison byte is set, this map's
+// scratch and the scratch of every feature that has run on it filled with the byte (map_kernels.hip)
+int map_poison(mo_map* m);
+inline int map_enter(mo_map* m) {
+    if (int rc = mo_enter(m->c)) return rc;
+    return m->c->poison < 0 ? MO_OK : map_poison(m);
+}
+#define MAP_ENTER(m) do { if (int e__ = map_enter(m)) return e__; } while (0)
 // the end of a call's chain: everything is enqueued, the one synchronisation
 inline int map_sync(mo_ctx* c, HostClock& clk) {
     clk.enqueued();

@@ -60,9 +60,12 @@ struct TrackBufs {
     DevBuf<uint8_t> minl;                 // [row] inlier flag of every match
     DevBuf<int32_t> qpt, qdist; DevBuf<uint8_t> qinl;   // [row] per frame keypoint
     DevBuf<TrackRes> res; PinnedBuf<TrackRes> h_res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) { f(rep); f(oct); f(cell); f(sorted); f(key); f(match); f(minl); f(qpt); f(qdist); f(qinl); f(res); }
 };
 
 void map_scratch_free(TrackBufs* b) { delete b; }
+int map_scratch_poison(mo_ctx* c, TrackBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // a pass's kernels run when the call has not ended and, for the second attempt, when the first asked for it
 __device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
@@ -385,7 +388,7 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         if (!(prm->radius[k] >= 0.0) || !std::isfinite(prm->radius[k])) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
     for (int i = 0; i < 12; i++)
         if (!std::isfinite(pose0[i])) return mo_fail(c, MO_ERR_ARG, "pose0 must be finite");
-    HIPCHK(c, hipSetDevice(c->device));
+    MAP_ENTER(m);
     HostClock clk(c);
     for (int i = 0; i < 12; i++) out->pose[i] = pose0[i];
     for (int k = 0; k < TK_MAX_PASS; k++) {

@@ -202,6 +202,12 @@ extern "C" int mo_stream_submit(mo_stream* s, const uint8_t* frames, int n, int 
     stage_frames(s->pool, l.h_in + (size_t)halo * s->frame_in, frames, n, s->frame_in, row, s->p.h, (size_t)stride, frame_stride);
     l.n_frames = n; l.halo = halo; l.first_frame = s->frames_in;
     const int nb = n + halo;
+    if (c->poison >= 0) {  // mo_dbg_set_poison reaches the lane's slabs too: all three are scratch (the chunk's upload and chain write what is read)
+        SCHK(s, hipMemsetAsync(l.d_in, c->poison, l.d_in.bytes, s->copy_s));
+        if (l.d_gray) SCHK(s, hipMemsetAsync(l.d_gray, c->poison, l.d_gray.bytes, c->stream));
+        SCHK(s, hipMemsetAsync(l.d_out, c->poison, l.d_out.bytes, c->stream));
+        c->poison_bufs += l.d_gray ? 3 : 2; c->poison_bytes += (int64_t)(l.d_in.bytes + l.d_gray.bytes + l.d_out.bytes);
+    }
     SCHK(s, hipMemcpyAsync(l.d_in, l.h_in, (size_t)nb * s->frame_in, hipMemcpyHostToDevice, s->copy_s));
     SCHK(s, hipEventRecord(l.copied, s->copy_s));
     SCHK(s, hipStreamWaitEvent(c->stream, l.copied, 0));

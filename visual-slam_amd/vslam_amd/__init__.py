@@ -199,6 +199,7 @@ SIGNATURES = {
     "mo_orb_grid_detect_compute": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_min_eigen": (_i, [_vp, _vp, _i, _i, _vp]),
     "mo_dbg_set_poison": (_i, [_vp, _i]),
+    "mo_dbg_poison_filled": (_i, [_vp, _vp, _vp]),
     "mo_undistort": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mo_dev_undistort": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mo_match_knn2_ratio": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
