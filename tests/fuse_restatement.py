@@ -35,10 +35,11 @@ def lists_of(a):
             for i in range(len(a["obs_off"]) - 1)]
 
 
-def fuse(a, kf_P, kf_xy, kf_oct, kf_desc, w, h, window=10, radius=3.0, scale_factor=1.2, max_dist=50, chi2=5.991):
+def fuse(a, kf_P, kf_xy, kf_oct, kf_desc, w, h, window=10, radius=3.0, scale_factor=1.2, max_dist=50, chi2=5.991, ties=1):
     """(fused arrays, into, counts, margins).  a: the map arrays (FIELDS); kf_P / kf_xy / kf_oct / kf_desc by keyframe position.
     margins: per kind of threshold decision ("z", "border", "r", "chi2", "max_dist") the smallest distance of any decided value from its
-    threshold over all pairs, and "min" over the kinds."""
+    threshold over all pairs, and "min" over the kinds.  ties = -1 is the WRONG rule - equal distances go to the higher keypoint row - for
+    the tests that show a tie case would notice it (tests/test_fuse_cpu.py)."""
     off, okf, okp = a["obs_off"], a["obs_kf"], a["obs_kp"]
     n, n_kf = len(off) - 1, len(kf_desc)
     cnt = dict.fromkeys(COUNTS, 0)
@@ -98,7 +99,7 @@ def fuse(a, kf_P, kf_xy, kf_oct, kf_desc, w, h, window=10, radius=3.0, scale_fac
             if len(q) == 0:
                 continue
             d = hamming(rep[i:i + 1], kf_desc[k][q])[0]
-            order = np.lexsort((q, d))   # lowest distance, ties to the lower row
+            order = np.lexsort((ties * q, d))   # lowest distance, ties to the lower row
             bd, bq = int(d[order[0]]), int(q[order[0]])
             margins["max_dist"] = min(margins["max_dist"], abs(bd - (max_dist + 0.5)))
             if bd > max_dist:

@@ -100,11 +100,13 @@ def triangulate(cam1, xn1, yn1, cam2, xn2, yn2, note=lambda kind, v: None):
 
 
 def grow(a, K, poses, kf_xy, kf_oct, kf_desc, window=10, max_dist=50, scale_factor=1.2, epi_chi2=3.84, chi2=5.991, cos_max=0.9998,
-         ratio_factor=None, epipole_r2=100.0, image=None, target_slot=None):
+         ratio_factor=None, epipole_r2=100.0, image=None, target_slot=None, ties=1):
     """(arrays after, point [rows of the target], points [n_new][3] f64, counts, margins).  a: the map arrays (FIELDS); poses [n_kf] 4x4 or
     3x4 and kf_xy / kf_oct / kf_desc by keyframe position; image: the target's stored image (None: none); target_slot: the store slot
     of the last keyframe (None: its position).  margins: per kind of
-    threshold decision (KINDS) the smallest distance of any decided value from its threshold, and "min" over the kinds."""
+    threshold decision (KINDS) the smallest distance of any decided value from its threshold, and "min" over the kinds.
+    ties = -1 is the WRONG rule - equal distances go to the higher neighbour row and the higher target row - for the tests that show a
+    tie case would notice it (tests/test_grow_cpu.py)."""
     ratio_factor = 1.5 * scale_factor if ratio_factor is None else ratio_factor
     n_kf = len(kf_desc)
     same = {f: np.array(a[f]).copy() for f in FIELDS}
@@ -176,14 +178,14 @@ def grow(a, K, poses, kf_xy, kf_oct, kf_desc, window=10, max_dist=50, scale_fact
                 continue
             qq = q[ok]
             d = hamming(kf_desc[T][r1:r1 + 1], kf_desc[k][qq])[0]
-            order = np.lexsort((qq, d))   # lowest distance, ties to the lower row
+            order = np.lexsort((ties * qq, d))   # lowest distance, ties to the lower row
             bd, bq = int(d[order[0]]), int(qq[order[0]])
             note("max_dist", bd, max_dist + 0.5)
             if bd > max_dist:
                 continue
             cnt["n_accepted"] += 1
             accepted[(r1, k)] = bq
-            if (k, bq) not in claim or (bd, r1) < claim[(k, bq)]:
+            if (k, bq) not in claim or (bd, ties * r1) < (claim[(k, bq)][0], ties * claim[(k, bq)][1]):
                 claim[(k, bq)] = (bd, r1)
     # points, in order of target row
     oct1 = np.asarray(kf_oct[T])

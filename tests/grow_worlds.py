@@ -5,7 +5,9 @@ withheld_points_world: a skip world in which every map point observed at the las
 keypoints stay in the keyframes: what the call should give back.
 Hand maps: camera f = 100, centre (50, 50), image 100 x 100; keyframe k looks down z from x = k (poses()), so a point (a, b, 10) lands
 at (50 + 10 a - 10 k, 50 + 10 b): the epipolar lines are the image rows, the epipoles lie at infinity, two neighbouring keyframes see a
-point at depth 10 under 5.7 degrees."""
+point at depth 10 under 5.7 degrees.
+large_world: the withheld world at the mapper's keyframe size (about 2000 rows); row_cases: hand maps of up to 2049 rows at the row
+edges of k_grow_free and k_grow_search (csrc/map_grow.hip)."""
 import numpy as np
 
 from tests import fuse_worlds as FW
@@ -181,3 +183,180 @@ def hand(ctx, kfs, obs, xyz, T, image=None, capacity=None):
                        np.array([p[2] for p in kf], np.uint8).reshape(-1, 32), P)
         assert m.last["n_new"] == 0
     return m
+
+
+# ---- worlds at the keyframe size the mapper runs at -------------------------------------------------------------------------------------
+LARGE = dict(n_w=4000, n_kf=4)
+LARGE_STALE = dict(n_w=3400, n_kf=6, removed=(1,), seed=43, decorated=True)
+_LARGE = {}
+
+
+def large_world(stale=False):
+    """withheld_points_world at about 2000 rows per keyframe, built once.  Checked on the CPU (tests/test_grow_cpu.py):
+    LARGE:       rows [921, 1117, 1924, 1830]; window 0: 1830 free target rows, 847 new points, margins["min"] 2.3e-4
+    LARGE_STALE: slots [548, 765, 693, 1087, 1785, 1656], position 1 removed: rows [548, 693, 1087, 1785, 1656], slot != position from
+                 position 1 on, keys decorated; window 0: 1656 free target rows, 953 new points, margins["min"] 2.6e-4
+    In both no pair of consecutive keyframes (in slot order, as build_map adds them) has a descriptor match that survives the ratio
+    test at 0.8, so no growth step of build_map finds a model.  The target and at least one neighbour exceed 1024 rows: k_grow_free
+    takes a second trip, k_grow_search a second tile; nothing exceeds 2100 rows, to keep the tests at a few seconds."""
+    if stale not in _LARGE:
+        w, held = withheld_points_world(**(LARGE_STALE if stale else LARGE))
+        free = GR.free_rows(FW.world_inputs(w)[0], w.counts)
+        assert free[-1].sum() > 1024 and max(len(f) for f in free[:-1]) > 1024 and 4 <= len(w.counts) <= 6 and w.counts.max() <= 2100, w.counts
+        _LARGE[stale] = (w, held)
+    return _LARGE[stale]
+
+
+# ---- hand maps at the row edges of the search ---------------------------------------------------------------------------------------------
+# The camera and poses of cases(): a neighbour at x = 0, the target at x = 1; a feature is (60, y, d) in the neighbour and (50, y, d) in
+# the target (the point (1, (y - 50) / 10, 10)); other x on the same image row are the same line at another depth (disparity 6 .. 14 px:
+# depth 16.7 .. 7.1, parallax 3.4 .. 8 degrees, exact reprojection: every gate behind the search is passed by far).
+TILE = 1024                  # GR_TILE of csrc/map_grow.hip, and the rows k_grow_free takes per trip
+Y_FILL = (90.0, 10.0)        # the image rows of the fillers: neighbours, target.  The lines used are y = 30, 40, 60: 20 px or more away
+FILL = 15                    # the code word of the plain fillers
+
+
+def padded(n, rows, y_fill):
+    """a keyframe of n rows: `rows` = {row: (x, y, descriptor[, octave])}, every other row a filler on the image row y_fill, where no
+    epipolar line of the case comes within the gate (2 px at octave 0).  Fillers carry the code word FILL, except one for each
+    descriptor of `rows` that stands once: it carries a copy.  Every descriptor then stands at least twice in the keyframe: for any
+    query the best two distances are equal, the ratio test of add_keyframe's own growth step keeps nothing and hand_map's n_new == 0
+    holds (the device of tests/map_worlds.py)."""
+    once = {}
+    for p in rows.values():
+        once.setdefault(bytes(p[2]), []).append(p[2])
+    copies = [v[0] for v in once.values() if len(v) == 1]
+    n_fill = n - len(rows)
+    assert n_fill >= len(copies) and n_fill - len(copies) != 1 and all(0 <= r < n for r in rows), (n, len(rows), len(copies))
+    out = []
+    for r in range(n):
+        if r in rows:
+            out.append(tuple(rows[r]))
+        else:
+            out.append((5.0 + r % 91, y_fill, copies.pop() if copies else desc(FILL)))
+    return out
+
+
+def owned(key, rows):
+    """(obs, xyz) of one single-observation map point per row of keyframe `key`, as in the `occupied` case"""
+    rows = list(rows)
+    return [[(key, r)] for r in rows], [[0.0, -2.0, 10.0]] * len(rows)
+
+
+def row_cases():
+    """hand maps that put the search of csrc/map_grow.hip at its row edges: name -> (kfs, obs, xyz, poses, keyword arguments,
+    expectations), as cases().  expectations: counts (a subset of GR.COUNTS), `point_rows` = the target rows that made a point, `new_lists`
+    = the observation lists of the new points (in the order they are appended: by target row), `dref_row` of the new points.  A name's
+    part before the first ":" is its family; tests/test_grow_cpu.py shows for every family a wrong reading of the rows it fails under."""
+    c = {}
+    two = poses((0.0, 1.0))
+    D = [desc(j) for j in range(16)]
+    tgt1 = padded(2, {0: (50, 30, D[0])}, Y_FILL[1])          # one feature on the line y = 30 and its copy among the fillers: n_free = 2
+    one = dict(n_free=2, n_accepted=1, n_matches=1, n_new=1, n_obs_new=2, point_rows=[0])
+    # tile_counts: the only row of the neighbour on the line is its last, n2 - 1: the last row of a full tile (1024, 2048), of a tile one
+    # short (1023), the single row of a further tile (1025, 2049).  One row passes the gate, one point observing it
+    for n2 in (TILE - 1, TILE, TILE + 1, 2 * TILE, 2 * TILE + 1):
+        c["tile_counts:%d" % n2] = ([padded(n2, {n2 - 1: (60, 30, D[0])}, Y_FILL[0]), tgt1], [], [], two, {},
+                                    dict(one, n_epi=1, new_lists=[[(0, n2 - 1), (1, 0)]]))
+    # first_tile_owned: rows 0 .. 1023 of the neighbour all owned, among them row 5 on the line with the target's very descriptor; the
+    # free row 1030 on the line is 3 bits off.  Only free rows are staged: the first tile stages none (n = 0), n_epi = 1, row 1030
+    ob, X = owned(0, range(TILE))
+    c["first_tile_owned:second_tile_free"] = ([padded(TILE + 16, {5: (60, 30, D[0]), 1030: (61, 30, desc(0, (0, 1, 2)))}, Y_FILL[0]), tgt1], ob, X, two, {},
+                                              dict(one, n_epi=1, n_points=TILE + 1, new_lists=[[(0, 1030), (1, 0)]]))
+    # ... and the whole second tile owned (the decoy in row 1029), the match in row 5 of the first
+    ob, X = owned(0, range(TILE, 2 * TILE))
+    c["first_tile_owned:second_tile_owned"] = ([padded(2 * TILE, {1029: (60, 30, D[0]), 5: (61, 30, desc(0, (0, 1, 2)))}, Y_FILL[0]), tgt1], ob, X, two, {},
+                                               dict(one, n_epi=1, n_points=TILE + 1, new_lists=[[(0, 5), (1, 0)]]))
+    # tie_across_tiles: rows 5 and 1029 on the line, both 2 bits off (other bits): the best of the first tile is carried into the
+    # second and keeps the tie, row 5.  With row 1029 only 1 bit off it is taken
+    for name, far, row in (("equal", (100, 101), 5), ("second_closer", (100,), 1029)):
+        c["tie_across_tiles:" + name] = ([padded(TILE + 16, {5: (60, 30, desc(0, (0, 1))), 1029: (61, 30, desc(0, far))}, Y_FILL[0]), tgt1], [], [], two, {},
+                                         dict(one, n_epi=2, new_lists=[[(0, row), (1, 0)]]))
+    # tie_inside_a_tile: rows 7, 15, .. 1023 (128 rows over the whole tile) on the line at x = 56 + j / 16, row 7 + 8 j 2 bits off the
+    # target's descriptor at bits 2 j, 2 j + 1: 128 rows pass the gate at distance 2, each with another descriptor and another depth.
+    # The staging order is that of an LDS atomic; the lowest row, 7, whatever it was
+    c["tie_inside_a_tile"] = ([padded(TILE, {7 + 8 * j: (56 + j / 16.0, 30, desc(0, (2 * j, 2 * j + 1))) for j in range(128)}, Y_FILL[0]), tgt1], [], [], two, {},
+                              dict(one, n_epi=128, new_lists=[[(0, 7), (1, 0)]]))
+    # two_waves_one_row: 72 free target rows are two waves of the search (free indices 0 .. 63, 64 .. 71; every row is free, so a row is its
+    # own free index).  Rows 3 and 70 lie on the line y = 30, both 3 bits (other bits) off the neighbour's row 0: they meet in the atomicMin
+    # on row 0's key only, the lower target row wins, row 70 makes no point.  Rows 4 and 69 on y = 60 against the neighbour's row 1: 3 bits
+    # against 2, row 69 wins.  4 gate passes, 4 accepted, 2 matches won
+    tgt = padded(72, {3: (50, 30, desc(0, (0, 1, 2))), 70: (50.5, 30, desc(0, (100, 101, 102))),
+                      4: (50, 60, desc(1, (0, 1, 2))), 69: (50.5, 60, desc(1, (100, 101)))}, Y_FILL[1])
+    c["two_waves_one_row"] = ([[(60, 30, D[0]), (60, 60, D[1])], tgt], [], [], two, {},
+                              dict(n_free=72, n_epi=4, n_accepted=4, n_matches=2, n_new=2, n_obs_new=4, point_rows=[3, 69],
+                                   new_lists=[[(0, 0), (1, 3)], [(0, 1), (1, 69)]], dref_row=[3, 69]))
+    # free_rows_past_1024: a target of 1100 rows, its three features in rows 1030, 1060, 1099 (lines y = 30, 40, 60; the neighbour's rows 0, 1,
+    # 2).  n_free = 1024 and 1025: 76 and 75 owned rows sprinkled below 1024 (rows 1, 14, 27, ..): the second trip of k_grow_free writes
+    # behind the 948 / 949 free rows of the first.  n_free = 63, 64, 65: every row owned but the three and 60, 61, 62 others (rows 2, 19, 36,
+    # .. 1022, 1039): one wave short of a lane, one full wave and no second, a second wave with one live lane - row 1099, the last free
+    # row, which has a match.  Three gate passes, three points, appended in row order
+    nb = [(60, 30, D[0]), (60, 40, D[1]), (60, 60, D[2])]
+    feats = {1030: (50, 30, D[0]), 1060: (50, 40, D[1]), 1099: (50, 60, D[2])}
+    tgt = padded(1100, feats, Y_FILL[1])
+    n_frees = (63, 64, 65, TILE, TILE + 1)
+    for nf in n_frees:
+        if nf >= TILE:
+            taken = [1 + 13 * i for i in range(1100 - nf)]
+            assert max(taken) < TILE
+        else:
+            free = sorted(set(feats) | {2 + 17 * i for i in range(nf - 3)})
+            assert len(free) == nf and min(free) < TILE
+            taken = [r for r in range(1100) if r not in free]
+        assert 1100 - len(taken) == nf and not set(taken) & set(feats)
+        ob, X = owned(1, taken)
+        c["free_rows_past_1024:%d" % nf] = ([nb, tgt], ob, X, two, {},
+                                            dict(n_free=nf, n_epi=3, n_accepted=3, n_matches=3, n_new=3, n_obs_new=6, point_rows=sorted(feats),
+                                                 new_lists=[[(0, j), (1, r)] for j, r in enumerate(sorted(feats))], dref_row=sorted(feats)))
+    # empty_and_full_neighbours: four keyframes at x = 0 .. 3, the feature is the point (3, -2, 10): (50, 30) in the target, (60, 30) at
+    # position 2, (80, 30) at position 0.  Position 0: two rows on the line with the target's descriptor, both owned.  Position 1: no row.
+    # Position 2: rows 0 and 1 on the line, both 2 bits off: row 0.  Counts as for position 2 alone: 2 gate passes, one accepted
+    four = poses((0.0, 1.0, 2.0, 3.0))
+    ob, X = owned(0, range(2))
+    kfs = [[(80, 30, D[0]), (80.5, 30, D[0])], [], [(60, 30, desc(0, (0, 1))), (60.5, 30, desc(0, (100, 101)))], tgt1]
+    c["empty_and_full_neighbours"] = (kfs, ob, X, four, {}, dict(one, n_neighbours=3, n_epi=2, n_points=3, new_lists=[[(2, 0), (3, 0)]]))
+    # what the cases must cover, whatever is edited above
+    assert {int(k.split(":")[1]) for k in c if k.startswith("tile_counts:")} == {1023, 1024, 1025, 2048, 2049}
+    assert {v[5]["n_free"] for k, v in c.items() if k.startswith("free_rows_past_1024:")} == {63, 64, 65, 1024, 1025}
+    assert all(len(kf) <= 2 * TILE + 1 for v in c.values() for kf in v[0]) and all(len(v[0]) <= 4 for v in c.values())
+    return c
+
+
+def families(c):
+    return sorted({k.split(":")[0] for k in c})
+
+
+def missed(want, a, point, cnt, n_old):
+    """the expectations of a case (cases() / row_cases()) that a result does not meet: [] when it holds"""
+    bad = [k for k in want if k in GR.COUNTS and cnt[k] != want[k]]
+    lists = FW.FR.lists_of(a)
+    if "point" in want and (point >= 0).tolist() != want["point"]:
+        bad.append("point")
+    if "point_rows" in want and np.flatnonzero(point >= 0).tolist() != want["point_rows"]:
+        bad.append("point_rows")
+    if "lists" in want and lists != want["lists"]:
+        bad.append("lists")
+    if "new_lists" in want and lists[n_old:] != want["new_lists"]:
+        bad.append("new_lists")
+    if "dref_row" in want and a["dref_row"][n_old:].tolist() != want["dref_row"]:
+        bad.append("dref_row")
+    return bad
+
+
+# the wrong readings of the rows that a row case must notice (tests/test_grow_cpu.py): what a kernel would compute that
+MUTATIONS = ("neighbours_cut", "target_cut", "ties_high")   # stopped after a neighbour's first tile / after k_grow_free's first trip / took ties upward
+
+
+def run_mutated(kfs, obs, xyz, T, kw, mutation):
+    """run() of a case under one wrong reading.  The cuts are made on the inputs: a keyframe cut to its first TILE rows (an observation
+    of a row behind the cut names no row and is skipped, as any stale key); `point` is filled up to the target's rows again"""
+    n_t = len(kfs[-1])
+    if mutation == "neighbours_cut":
+        kfs = [kf[:TILE] for kf in kfs[:-1]] + [kfs[-1]]
+    elif mutation == "target_cut":
+        kfs = list(kfs[:-1]) + [kfs[-1][:TILE]]
+    else:
+        assert mutation == "ties_high"
+        kw = dict(kw, ties=-1)
+    a, point, points, cnt, margins = run(kfs, obs, xyz, T, **kw)
+    return a, np.concatenate([point, np.full(n_t - len(point), -1, np.int32)]), points, cnt, margins

@@ -157,3 +157,64 @@ def C_sizes():
 
     import vslam_amd as V
     return C.sizeof(V.MapFuseParams), C.sizeof(V.MapFuseOut)
+
+
+# ---- keyframes past 1024 rows: the worlds and row cases of tests/fuse_worlds.py, which tests/test_gpu_fuse.py runs on the device ---------
+def test_large_split_world_is_put_together_again():
+    """rows [921, 1117, 1924, 1830]: 1693 points in two, every one put together again; the observation sets are the unsplit world's"""
+    from tests import fuse_worlds as FW
+    from tests.test_grow_cpu import ratio_survivors
+    w, unsplit, n_split = FW.large_split_world()
+    assert w.counts.tolist() == [921, 1117, 1924, 1830] and n_split == 1693 and set(ratio_survivors(w)) == {0}
+    out, into, cnt, margins = FW.restate_world(w, window=0)
+    assert margins["min"] > 1e-7 > 1e-9, margins
+    assert cnt["n_absorbed"] == n_split and cnt["n_points"] == len(unsplit.obs) and cnt["n_gained"] == 0 and cnt["n_edges"] == 2 * n_split
+    u = FW.world_inputs(unsplit)[0]
+    assert sorted(map(sorted, FW.obs_sets(out, w.counts))) == sorted(map(sorted, FW.obs_sets(u, w.counts)))
+    # with the rows behind the first 1024 of every keyframe missing, fewer points find their other half
+    cut = ([x[:FW.TILE] for x in w.kf_xy], [x[:FW.TILE] for x in w.kf_oct], [x[:FW.TILE] for x in w.kf_desc], FW.world_inputs(w)[1])
+    assert FW.restate_world(w, lists=cut, window=0)[2]["n_absorbed"] < n_split - 100
+
+
+def test_large_stale_split_world():
+    """six keyframes, position 1 removed, keys decorated: rows [548, 693, 1087, 1785, 1656]; read without the position -> slot table the
+    restatement gives another map"""
+    from orbslam2.utils import compute_projection_matrix
+    from tests import fuse_worlds as FW
+    from tests.test_grow_cpu import ratio_survivors
+    w, unsplit, n_split = FW.large_split_world(stale=True)
+    assert w.counts.tolist() == [548, 693, 1087, 1785, 1656] and w.survivors == [0, 2, 3, 4, 5] and set(ratio_survivors(w)) == {0}
+    kinds = [(k < 0, r < 0, k >= 50) for k, r in zip(w.obs_kf.tolist(), w.obs_kp.tolist())]
+    assert min(sum(x[j] for x in kinds) for j in range(3)) >= 100
+    out, into, cnt, margins = FW.restate_world(w, window=0)
+    assert margins["min"] > 1e-6 > 1e-9, margins
+    assert n_split == 1928 and cnt["n_absorbed"] == n_split
+    xy, octv, desc, poses = w.slot_order()
+    P = [np.ascontiguousarray(compute_projection_matrix(T[:3, :3], T[:3, 3], w.K), np.float64) for T in poses]
+    wrong = FW.restate_world(w, lists=(xy, octv, desc, P), window=0)
+    assert wrong[2]["n_points"] != cnt["n_points"]
+
+
+def _row_cases():
+    from tests import fuse_worlds as FW
+    return FW.row_cases()
+
+
+def test_row_cases():
+    from tests import fuse_worlds as FW
+    for name, (kfs, xyz, obs, want) in _row_cases().items():
+        out, into, cnt, margins = FW.run_rows(kfs, xyz, obs)
+        assert margins["min"] > 0.2 > 1e-9, (name, margins)
+        assert FW.missed(want, out, into, cnt) == [], (name, cnt, FR.lists_of(out))
+
+
+def test_row_cases_fail_under_a_wrong_reading():
+    """the wrong readings each row case must fail under, by its construction: a target row behind the first 1024 is the answer
+    (target_row_past_1024, crowded_cell); the answer is the lower of two rows at equal distance (crowded_cell, empty_target)"""
+    from tests import fuse_worlds as FW
+    bites = {"target_row_past_1024": {"targets_cut"}, "crowded_cell": {"targets_cut", "ties_high"}, "empty_target": {"ties_high"}}
+    cases = _row_cases()
+    assert set(cases) == set(bites)
+    for name, (kfs, xyz, obs, want) in cases.items():
+        got = {mu for mu in FW.MUTATIONS if FW.missed(want, *FW.run_rows(kfs, xyz, obs, mutation=mu)[:3])}
+        assert got == bites[name] != set(), (name, got)

@@ -263,3 +263,53 @@ def test_no_work_determinism_and_growth_from_a_tiny_capacity():
     assert out[0] == out[1] == out[2] and out[0][-3] > 100   # (n_absorbed)
     assert ctx.dev_status() == 0
     ctx.close()
+
+
+# ---- keyframes past 1024 rows (tests/fuse_worlds.py: large_split_world, row_cases) ---------------------------------------------------------
+def test_large_split_world_is_put_together_again():
+    """(9) the split world at the mapper's keyframe size, rows [921, 1117, 1924, 1830]: three targets past 1024 rows (k_trk_grid's strided
+    loops take a second trip, keypoints in rows >= 1024 are matched and owned).  One point absorbed per split, the observation sets
+    are the unsplit world's"""
+    ctx = _ctx()
+    w, unsplit, n_split = FW.large_split_world()
+    m = build_map(ctx, w)
+    assert (w.counts > 1024).sum() >= 2
+    info, want, cnt, before = _fuse_equals_restatement(m, w.image_size, window=0)
+    assert n_split > 1000 and info["n_absorbed"] == n_split and info["n_points"] == len(unsplit.obs) and info["n_gained"] == 0
+    a = m.arrays()
+    u = FW.world_inputs(unsplit)[0]
+    assert sorted(map(sorted, FW.obs_sets(a, w.counts))) == sorted(map(sorted, FW.obs_sets(u, w.counts)))
+    assert np.array_equal(np.sort(a["id"]), np.sort(u["id"]))
+    assert ctx.dev_status() == 0
+    m.close(); ctx.close()
+
+
+def test_large_stale_world_position_is_not_slot():
+    """(10) six keyframes of up to 1785 rows, position 1 removed, keys decorated: slot != position behind tables strided by the row
+    capacity, read past row 1024"""
+    from orbslam2.utils import compute_projection_matrix
+    ctx = _ctx()
+    w, unsplit, n_split = FW.large_split_world(stale=True)
+    m = build_map(ctx, w)
+    assert [w.survivors[p] != p for p in range(len(w.survivors))].count(True) == 4 and (w.counts > 1024).sum() >= 3
+    info, want, cnt, before = _fuse_equals_restatement(m, w.image_size, window=0)
+    assert info["n_absorbed"] >= 0.5 * n_split > 500
+    xy, octv, desc, poses = w.slot_order()
+    P = [np.ascontiguousarray(compute_projection_matrix(T[:3, :3], T[:3, 3], w.K), np.float64) for T in poses]
+    wrong = FW.restate_world(w, lists=(xy, octv, desc, P), window=0)
+    assert wrong[2] != cnt and wrong[2]["n_points"] != cnt["n_points"]
+    assert ctx.dev_status() == 0
+    m.close(); ctx.close()
+
+
+def test_row_cases_on_hand_made_maps():
+    """(11) the row cases of tests/test_fuse_cpu.py on the device: the matched keypoint in the last row of targets of 1025 and 2049 rows,
+    free and owned; 200 keypoints of a 1500-row target in the cell under the projection with a tie for the best; a target without a row"""
+    ctx = _ctx()
+    for name, (kfs, xyz, obs, want) in sorted(FW.row_cases().items()):
+        m = _hand(ctx, kfs, xyz, obs)
+        info, _, _, _ = _fuse_equals_restatement(m, (100, 100), window=0)
+        assert FW.missed(want, m.arrays(), info["into"], {k: info[k] for k in FR.COUNTS}) == [], (name, info)
+        m.close()
+    assert ctx.dev_status() == 0
+    ctx.close()

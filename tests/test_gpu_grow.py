@@ -203,3 +203,104 @@ def test_the_grown_map_serves_every_reader():
     assert set(map(bytes, a["xyz"][n0:])) <= set(map(bytes, c["xyz"]))
     assert ctx.dev_status() == 0
     m.close(); ctx.close()
+
+
+# ---- keyframes past 1024 rows (tests/grow_worlds.py: large_world, row_cases) --------------------------------------------------------------
+@pytest.mark.parametrize("window", [0, 2])
+def test_large_world_withheld_points_come_back(window):
+    """(8) the withheld world at the mapper's keyframe size, rows [921, 1117, 1924, 1830]: k_grow_free takes two trips over the target's
+    1830 free rows, the search 29 waves per neighbour and two tiles in the neighbour of 1924 rows.  Every withheld point with two
+    observations inside the window is back with exactly those"""
+    from tests.test_grow_cpu import check_recovery
+    ctx = _ctx()
+    w, held = GW.large_world()
+    m = build_map(ctx, w)
+    info, want, point, points, cnt = _grow_equals_restatement(m, window=window)
+    assert info["n_free"] > 1024 and max(w.counts[:-1]) > 1024 and info["n_neighbours"] == (2 if window else 3) and info["n_new"] > 500
+    check_recovery(w, held, m.arrays(), info["point"], info["points"], cnt, 1 if window else 0)
+    assert ctx.dev_status() == 0
+    m.close(); ctx.close()
+
+
+def test_large_stale_world_position_is_not_slot():
+    """(9) six keyframes of up to 1785 rows, position 1 removed, keys decorated: slot != position behind tables strided by the row
+    capacity, read past row 1024"""
+    ctx = _ctx()
+    w, held = GW.large_world(stale=True)
+    m = build_map(ctx, w)
+    assert [w.survivors[p] != p for p in range(len(w.survivors))].count(True) == 4 and (w.counts > 1024).sum() >= 3
+    info, want, point, points, cnt = _grow_equals_restatement(m, window=0)
+    assert info["n_new"] > 500 and (m.arrays()["dref_kf"][-info["n_new"]:] == w.survivors[-1]).all()
+    wrong = GW.restate_world(w, lists=w.slot_order(), window=0)
+    assert wrong[3] != cnt and wrong[3]["n_new"] != cnt["n_new"]
+    assert ctx.dev_status() == 0
+    m.close(); ctx.close()
+
+
+def test_large_world_from_a_tiny_capacity():
+    """(10) the large world in a map made with capacities every store outgrows - the keyframe store regrows its row stride across 1024
+    rows - gives the bytes of the default build"""
+    ctx = _ctx()
+    w, held = GW.large_world()
+    out = []
+    for cap in (None, TINY):
+        m = build_map(ctx, w, capacity=cap)
+        info = m.create_new_map_points(window=0, want_points=True)
+        a = m.arrays()
+        out.append([a[f].tobytes() for f in GR.FIELDS] + [info["point"].tobytes(), info["points"].tobytes()] + [info[k] for k in GR.COUNTS])
+        m.close()
+    assert out[0] == out[1] and out[0][-4] > 500   # (n_new)
+    assert ctx.dev_status() == 0
+    ctx.close()
+
+
+def test_the_grown_large_map_serves_every_reader():
+    """(11) the reader checks of (7) on the grown large map: a second call creates nothing, track_local_map and
+    bundle_adjust(max_steps=(0, 0)) agree with their restatements on the grown arrays, fuse_map_points merges none of the new points"""
+    from tests.ba_restatement import bundle_adjust as restate_ba
+    ctx = _ctx()
+    w, held = GW.large_world()
+    size = w.image_size
+    m = build_map(ctx, w)
+    info, want, point, points, cnt = _grow_equals_restatement(m, window=0)
+    n0 = cnt["n_points"] - cnt["n_new"]
+    a = {f: v.copy() for f, v in m.arrays().items()}
+    info2, _, _, _, _ = _grow_equals_restatement(m, window=0)
+    assert info2["n_new"] == 0 and info2["n_free"] == info["n_free"] - info["n_new"] and info2["n_points"] == cnt["n_points"]
+    assert all(m.arrays()[f].tobytes() == a[f].tobytes() for f in a)
+    T = pose_near(w, 2)
+    kps, desc = w.world0.track_query(T, wrong=0.0)
+    pose0 = perturbed_pose(T)
+    ok, pose, ti = m.track_local_map(kps, desc, pose0, radii=(15.0,), image_size=size)
+    r = TR.track(w.K, pose0, a["xyz"], a["obs_off"], a["obs_kf"], a["obs_kp"], w.kf_desc, w.kf_oct, kps, desc, size[0], size[1], radii=(15.0,),
+                 refine_pose=False)
+    assert ti["n_local"] == r["n_local"] and np.array_equal(ti["point"], r["passes"][0]["point"]) and np.array_equal(ti["dist"], r["passes"][0]["dist"])
+    assert (ti["point"] >= n0).sum() >= 500
+    okb, bi = m.bundle_adjust(window=6, max_steps=(0, 0), want_points=True)
+    rb = restate_ba(a["obs_off"], a["obs_kf"], a["obs_kp"], w.counts, w.kf_xy, w.kf_oct, a["xyz"], w.K, np.array([T_[:3, :4] for T_ in w.kf_poses]),
+                    window=6, max_steps=(0, 0))
+    for k in ("n_free", "n_fixed", "n_local", "n_edges", "n_inliers", "free", "fixed"):
+        assert bi[k] == rb[k], (k, bi[k], rb[k])
+    assert np.array_equal(bi["edge_inlier"], rb["edge_inlier"]) and bi["n_edges"] > 1000
+    fi = m.fuse_map_points(image_size=size, window=0)
+    assert (np.bincount(fi["into"])[fi["into"][n0:]] == 1).all()
+    assert np.array_equal(m.arrays()["xyz"][fi["into"][n0:]], a["xyz"][n0:])
+    assert ctx.dev_status() == 0
+    m.close(); ctx.close()
+
+
+@pytest.mark.parametrize("family", GW.families(GW.row_cases()))
+def test_row_cases_on_hand_made_maps(family):
+    """(12) the row cases of tests/test_grow_cpu.py on the device: tile counts of the neighbour, tiles without a free row, ties across and
+    inside a tile and between two waves, free target rows behind row 1024 with n_free at the edges of a wave, neighbours without a
+    (free) row"""
+    ctx = _ctx()
+    for name, (kfs, obs, xyz, T, kw, want) in sorted(GW.row_cases().items()):
+        if name.split(":")[0] != family:
+            continue
+        m = GW.hand(ctx, kfs, obs, xyz, T)
+        info, a, point, points, cnt = _grow_equals_restatement(m, window=0, **kw)
+        assert GW.missed(want, m.arrays(), info["point"], {k: info[k] for k in GR.COUNTS}, len(obs)) == [], (name, info)
+        m.close()
+    assert ctx.dev_status() == 0
+    ctx.close()

@@ -124,3 +124,107 @@ def test_library_exports_the_call():
     assert (C.sizeof(V.MapGrowParams), C.sizeof(V.MapGrowOut)) == (56, 64)
     from vslam_amd.mapper import LocalMapper
     assert callable(LocalMapper.create_new_map_points)
+
+
+# ---- keyframes past 1024 rows: the worlds and row cases of tests/grow_worlds.py, which tests/test_gpu_grow.py runs on the device ---------
+_L = {}
+ROWS = GW.row_cases()
+
+
+def large(stale, window):
+    """a large world and its restated call, computed once"""
+    if (stale, window) not in _L:
+        _L[stale, window] = GW.restate_world(GW.large_world(stale)[0], window=window)
+    return GW.large_world(stale) + _L[stale, window]
+
+
+def ratio_survivors(w):
+    """per pair of consecutive keyframes in slot order (the order build_map adds them in): the rows of the earlier one whose best match
+    in the later one passes the ratio test at 0.8"""
+    from tests.reloc_restatement import hamming
+    out = []
+    for k in range(1, len(w.slot_desc)):
+        d = np.sort(hamming(w.slot_desc[k - 1], w.slot_desc[k]).astype(np.int64), axis=1)[:, :2]
+        out.append(int((d[:, 0] < 0.8 * d[:, 1]).sum()))
+    return out
+
+
+@pytest.mark.parametrize("window", [0, 2])
+def test_large_world_withheld_points_come_back(window):
+    """rows [921, 1117, 1924, 1830]: the target's 1830 free rows are two trips of k_grow_free and 29 waves, the neighbour of 1924 rows two
+    tiles.  847 withheld points have two observations; with window 2 (positions 1 and 2) the same, since a point seen at position 3
+    is seen at position 1 and never at 0 or 2 (the skip pattern)"""
+    w, held, a, point, points, cnt, margins = large(False, window)
+    assert margins["min"] > 1e-4 > MARGIN, margins
+    assert w.counts.tolist() == [921, 1117, 1924, 1830] and cnt["n_free"] == 1830 and cnt["n_neighbours"] == (2 if window else 3)
+    assert cnt["n_new"] == 847 and cnt["n_epi"] > 20000
+    check_recovery(w, held, a, point, points, cnt, 1 if window else 0)
+    assert (np.flatnonzero(point >= 0) >= 1024).sum() > 300   # points made by rows of the second trip
+
+
+def test_large_worlds_have_no_match_for_a_growth_step():
+    for stale in (False, True):
+        assert set(ratio_survivors(GW.large_world(stale)[0])) == {0}
+
+
+def test_large_stale_world():
+    """six keyframes, position 1 removed, keys decorated: rows [548, 693, 1087, 1785, 1656].  Read without the position -> slot table, or
+    with the rows behind the first 1024 of the neighbours or of the target missing, the restatement gives another map"""
+    w, held, a, point, points, cnt, margins = large(True, 0)
+    assert margins["min"] > 1e-4 > MARGIN, margins
+    assert w.counts.tolist() == [548, 693, 1087, 1785, 1656] and w.survivors == [0, 2, 3, 4, 5]
+    assert (w.obs_kf < 0).sum() >= 100 and (w.obs_kp < 0).sum() >= 100 and (w.obs_kf >= 50).sum() >= 100
+    assert cnt["n_free"] == 1656 and cnt["n_new"] == 953
+    check_recovery(w, held, a, point, points, cnt, 0)
+    wrong = GW.restate_world(w, lists=w.slot_order(), window=0)
+    assert wrong[3]["n_new"] != cnt["n_new"]
+    lists = (w.kf_xy, w.kf_oct, w.kf_desc, w.kf_poses)
+    cut_nb = tuple([x[:GW.TILE] for x in f[:-1]] + [f[-1]] for f in lists[:3]) + (w.kf_poses,)
+    cut_tgt = tuple(list(f[:-1]) + [f[-1][:GW.TILE]] for f in lists[:3]) + (w.kf_poses,)
+    for cut in (cut_nb, cut_tgt):
+        assert GW.restate_world(w, lists=cut, window=0)[3]["n_new"] < cnt["n_new"]
+
+
+@pytest.mark.parametrize("name", sorted(ROWS))
+def test_row_cases(name):
+    kfs, obs, xyz, T, kw, want = ROWS[name]
+    a, point, points, cnt, margins = GW.run(kfs, obs, xyz, T, **kw)
+    assert margins["min"] > 1e-3 > MARGIN, margins
+    assert GW.missed(want, a, point, cnt, len(obs)) == [], cnt
+    assert len(points) == cnt["n_new"] and np.array_equal(a["xyz"][len(obs):], points.astype(np.float32))
+    assert len(a["id"]) == len(obs) + cnt["n_new"] and FW.FR.lists_of(a)[:len(obs)] == [list(o) for o in obs]
+    if name == "empty_and_full_neighbours":   # the counts of the normal neighbour alone
+        alone = GW.run(kfs[2:], T=T[2:], **kw)[3]
+        assert all(alone[k] == cnt[k] for k in GR.COUNTS[1:7]) and alone["n_neighbours"] == 1
+
+
+# the wrong readings each family of row cases must fail under, by its construction: a neighbour row behind the first tile is (or
+# takes part in) the answer; the answer comes from target rows behind k_grow_free's first trip; the answer is the lower of two rows at
+# equal distance.  tile_counts fails for n2 = 1025, 2048, 2049 (1023 and 1024 are the edge below: the same answer from one tile);
+# first_tile_owned fails in the variant with the match in the second tile
+BITES = {"tile_counts": {"neighbours_cut"}, "first_tile_owned": {"neighbours_cut"}, "tie_across_tiles": {"neighbours_cut", "ties_high"},
+         "tie_inside_a_tile": {"ties_high"}, "two_waves_one_row": {"ties_high"}, "free_rows_past_1024": {"target_cut"},
+         "empty_and_full_neighbours": {"ties_high"}}
+
+
+def bitten(name):
+    kfs, obs, xyz, T, kw, want = ROWS[name]
+    out = set()
+    for mu in GW.MUTATIONS:
+        a, point, _, cnt, _ = GW.run_mutated(kfs, obs, xyz, T, kw, mu)
+        if GW.missed(want, a, point, cnt, len(obs)):
+            out.add(mu)
+    return out
+
+
+@pytest.mark.parametrize("family", GW.families(ROWS))
+def test_row_cases_fail_under_a_wrong_reading(family):
+    """every family's expectations stop holding under at least one wrong reading of the rows - the ones its construction aims at"""
+    per_case = {name: bitten(name) for name in ROWS if name.split(":")[0] == family}
+    assert set().union(*per_case.values()) == BITES[family] != set(), per_case
+    if family == "tile_counts":
+        assert {n for n, b in per_case.items() if b} == {"tile_counts:1025", "tile_counts:2048", "tile_counts:2049"}
+    if family == "free_rows_past_1024":
+        assert all(b == {"target_cut"} for b in per_case.values())
+    if family == "tie_across_tiles":
+        assert per_case == {"tie_across_tiles:equal": {"neighbours_cut", "ties_high"}, "tie_across_tiles:second_closer": {"neighbours_cut"}}
