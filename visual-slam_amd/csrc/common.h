@@ -114,6 +114,8 @@ struct mo_ctx {
     int max_w = 0, max_h = 0, max_batch = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     int match_mode = 0;        // VSLAM_AMD_MATCHER: 0 default (XOR + popcount, train tiles through LDS), 1 "mfma" opt-in matrix-core matcher
+    int match_slices = 0;      // VSLAM_AMD_MATCHER=valu1|valu2|valu4|valu8: that many train slices in every k_match_lds launch; 0: match_launch_pairs' rule
+    int n_cu = 0;              // compute units of the device (what the slicing rule fills)
     int poison = -1;           // mo_dbg_set_poison (tests): >= 0: every new block and, at every entry point, every scratch buffer is filled with that byte
     int64_t poison_bufs = 0, poison_bytes = 0;  // mo_dbg_poison_filled: fills since the last mo_dbg_set_poison
     std::string err;

@@ -51,8 +51,18 @@ extern "C" mo_ctx* mo_create(int device, int max_w, int max_h, int max_batch) {
     }
     c->stream = c->own_stream;
     // the one environment switch of the library: VSLAM_AMD_MATCHER=mfma selects the opt-in matrix-core matcher (identical results;
-    // north_star prescribes XOR + popcount as the default, bench.py times the opt-in beside it)
-    if (const char* e = getenv("VSLAM_AMD_MATCHER")) c->match_mode = std::strcmp(e, "mfma") == 0 ? 1 : 0;
+    // north_star prescribes XOR + popcount as the default, bench.py times the opt-in beside it); valu1 | valu2 | valu4 | valu8 keep the
+    // default kernel and force the number of train slices of every launch (A/B and tests; valu = the launch rule)
+    if (const char* e = getenv("VSLAM_AMD_MATCHER")) {
+        c->match_mode = std::strcmp(e, "mfma") == 0 ? 1 : 0;
+        for (int s : {1, 2, 4, 8})
+            if (std::strcmp(e, ("valu" + std::to_string(s)).c_str()) == 0) c->match_slices = s;
+    }
+    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->n_cu <= 0) {
+        g_create_err = "mo_create: the device does not report its compute units";
+        delete c;
+        return nullptr;
+    }
     // hipEventDisableSystemFence: these events order work of ONE device (kernel boundaries already release / acquire at agent
     // scope); the default system-scope fence of an event record writes the L2 back and cost 6 - 17 us of idle GPU at every stage mark
     // (kernel trace: gaps only where an event sits between two kernels), 0.06 ms of a 2.2 ms step (profiles/r02_ab_event_fence.txt).

@@ -59,8 +59,8 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
 #define ML_THREADS 256
 #define ML_Q 2
 #define ML_PER_BLOCK (ML_THREADS * ML_Q)
-#define ML_SPLIT_BLOCKS 32  // launches with at most this many workgroups slice the train set ...
-#define ML_SPLIT_MAX 32     // ... into at most this many slices
+#define ML_RESIDENT 8       // workgroups a CU holds at once: 8 wavefronts per SIMD (63 VGPRs), 8.3 KB of LDS each
+#define ML_SPLIT_MAX 32     // slices of the train set at most (match_launch_pairs)
 #define ML_TILE 128  // train descriptors per tile: 256 threads x 16 B
 
 __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restrict__ qbase, const uint8_t* __restrict__ tbase,
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
         a[m][4] = hi.x; a[m][5] = hi.y; a[m][6] = hi.z; a[m][7] = hi.w;
         k0[m] = KEY_NONE; k1[m] = KEY_NONE;
     }
-    // gridDim.z > 1 (few pairs, see match_launch_pairs): this workgroup folds only its slice of the train tiles and leaves its
+    // gridDim.z > 1 (see match_launch_pairs): this workgroup folds only its slice of the train tiles and leaves its
     // two best keys in `part`; k_match_merge folds the slices - keys carry the global train index, so the result is the same
     const int ntile_all = (nt + ML_TILE - 1) / ML_TILE, per_z = (ntile_all + gridDim.z - 1) / gridDim.z;
     const int tile_lo = blockIdx.z * per_z, ntile = min(ntile_all, tile_lo + per_z);
@@ -103,6 +103,15 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
         for (int k = 0; k < 8; k++) asm volatile("" : "+v"(a[m][k]));
     __syncthreads();
     for (int tile = tile_lo; tile < ntile; tile++) {
+        // The wavefronts that share a SIMD are served oldest first: of the equal workgroups of a launch the first ends after half the
+        // launch and the last ones finish on SIMDs with too few wavefronts to issue at full rate (profiles/match_placement.txt).  A
+        // wavefront's priority therefore falls with the quarter of its tiles it is in: whoever is ahead yields to those behind, and the
+        // workgroups of a CU reach their last quarter together.
+        const int done4 = (tile - tile_lo) * 4, span = ntile - tile_lo;  // wave-uniform
+        if (done4 < span) __builtin_amdgcn_s_setprio(3);
+        else if (done4 < 2 * span) __builtin_amdgcn_s_setprio(2);
+        else if (done4 < 3 * span) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
         const bool more = tile + 1 < ntile;
         uint4 nxt = make_uint4(0, 0, 0, 0);
         if (more) {
@@ -345,10 +354,17 @@ int match_launch_pairs(mo_ctx* c, const uint8_t* d_q, const uint8_t* d_t, size_t
     if (((((size_t)d_q) | ((size_t)d_t) | q_stride | t_stride) & 15) != 0)
         return mo_fail(c, MO_ERR_ARG, "descriptor arrays must be 16-byte aligned (base pointers and row strides)");
     dim3 grid((nq_max + ML_PER_BLOCK - 1) / ML_PER_BLOCK, n_pairs);
-    // a handful of workgroups (the single-pair calls of the host API) would leave most of the 256 CUs idle: slice the train
-    // tiles over gridDim.z and merge the per-slice keys
+    // Fewer workgroups than the device holds at once (ML_RESIDENT per CU) leave wavefront slots empty for the whole launch - the four
+    // workgroups of a single-pair call most of the chip: the train tiles are then sliced over gridDim.z as far as the slices are still
+    // all resident together, and k_match_merge folds the per-slice keys.  (More slices than that, refilled by the dispatcher, measured
+    // no better once k_match_lds balances its wavefronts itself: profiles/match_balance_ab.txt.)  Slices are equal whole tiles.
     const int ntile = (nt_max + ML_TILE - 1) / ML_TILE, blocks = (int)grid.x * n_pairs;
-    const int n_split = blocks <= ML_SPLIT_BLOCKS ? std::min(std::min(ntile, ML_SPLIT_MAX), 256 / blocks) : 1;
+    int n_split = c->match_slices;  // forced: taken as it is, slices without a tile included
+    if (!n_split) {
+        n_split = std::max(1, std::min(std::min(c->n_cu * ML_RESIDENT / blocks, ML_SPLIT_MAX), ntile));
+        const int per_slice = (ntile + n_split - 1) / n_split;
+        n_split = std::max(1, (ntile + per_slice - 1) / std::max(1, per_slice));
+    }
     if (n_split > 1) {
         if (int rc = c->d_match_part.reserve_exact(c, (size_t)n_pairs * n_split * out_stride)) return rc;
         grid.z = n_split;
