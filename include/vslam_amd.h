@@ -962,6 +962,13 @@ int mo_dbg_min_eigen(mo_ctx*, const uint8_t* gray, int w, int h, float* eig /* [
 int mo_dbg_set_poison(mo_ctx*, int byte);
 /* buffers and bytes filled since the last mo_dbg_set_poison (either may be NULL) */
 int mo_dbg_poison_filled(mo_ctx*, int64_t* n_buffers, int64_t* n_bytes);
+/* what the last mo_map_relocalize / mo_map_relocalize_pre on this map downloaded, per candidate in rank order (arrays of 64; entries past
+   n_cand: cand -1, the rest 0 and a NaN pose): cand = keyframe position, best = the winning hypothesis' key (inliers << 32) |
+   ~(h * 4 + root), 0: no pose had an inlier; ncorr = |C_k|; ninl = final inliers; pose[c][12] = the refined [R | t] (NaN without a key).
+   Read from the call's pinned result block: no launch, no copy from the device, no synchronisation.  MO_ERR_ARG when no
+   relocalization has finished its chain on the map (a call that found nothing to match - no keyframe, no keypoint - runs none). */
+int mo_dbg_map_reloc_last(mo_map*, int32_t* n_cand, int32_t* cand /* [64] */, uint64_t* best /* [64] */, int32_t* ncorr /* [64] */,
+                          int32_t* ninl /* [64] */, double* pose /* [64][12] */);
 int mo_dbg_retain_best(mo_ctx*, const float* resp, int n, int n_points, int select_order, int32_t* order, int* n_out);
 
 #ifdef __cplusplus

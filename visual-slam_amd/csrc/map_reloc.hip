@@ -6,7 +6,9 @@
 // (match_launch_pairs, one pair per keyframe) -> scores
 // |C_k| -> ranking -> C_k of the candidates (block scans, query order) -> P3P hypotheses + scoring (one wave per hypothesis, all
 // candidates in one launch) -> best hypothesis + Gauss-Newton refinement (one wave per candidate) -> winner.  One synchronisation.
-// -ffp-contract=off (Makefile, every map file): pnp.h rounds on the device as in the host build of tests/native/pnp_check.cpp.
+// -ffp-contract=off (Makefile, every map file): pnp.h rounds on the device as in a host build.  tests/test_gpu_reloc_replay.py holds
+// the device to that: the chain from C_k on, restated on the host over the same pnp.h (tests/native/reloc_replay.cpp), gives the same
+// keys, counts, flags and winner, and the same poses up to libm's sin / cos.
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -320,6 +322,7 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         (rc = b.cq.reserve(c, cand_n)) || (rc = b.cp.reserve(c, cand_n)) || (rc = b.cinl.reserve(c, cand_n)) ||
         (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
         return rc;
+    b.h_res.p->n_cand = -1;  // until this call's copy-out lands: mo_dbg_map_reloc_last reports no relocalization
     if (!pre) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.qf, spare, (size_t)n_kf, c->stream));
     const MapPts src = m->P[m->cur].view();
     if ((rc = map_launch_point_of(m, 0, n_kf, b.tab))) return rc;
@@ -372,4 +375,16 @@ extern "C" int mo_map_relocalize(mo_map* m, const mo_frame_ref* f, const double 
 extern "C" int mo_map_relocalize_pre(mo_map* m, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params* prm, int32_t n_pre,
                                      mo_map_reloc_out* out) {
     return reloc_run(m, f, K, prm, n_pre < 0 ? 0 : n_pre, out);
+}
+
+// what the map's last relocalization downloaded (the pinned RelocRes): no launch, no copy, no synchronisation
+extern "C" int mo_dbg_map_reloc_last(mo_map* m, int32_t* n_cand, int32_t* cand, uint64_t* best, int32_t* ncorr, int32_t* ninl, double* pose) {
+    if (!m) return MO_ERR_ARG;
+    if (!n_cand || !cand || !best || !ncorr || !ninl || !pose) return mo_fail(m->c, MO_ERR_ARG, "NULL argument");
+    if (!m->rl || !m->rl->h_res.p || m->rl->h_res.p->n_cand < 0) return mo_fail(m->c, MO_ERR_ARG, "no relocalization has run on this map");
+    const RelocRes& r = *m->rl->h_res;
+    *n_cand = r.n_cand;
+    for (int i = 0; i < RL_MAX_CAND; i++) { cand[i] = r.cand[i]; best[i] = r.best[i]; ncorr[i] = r.ncorr[i]; ninl[i] = r.ninl[i]; }
+    std::memcpy(pose, r.pose, sizeof(r.pose));
+    return MO_OK;
 }

@@ -242,6 +242,7 @@ SIGNATURES = {
     "mo_map_download": (_i, [_vp, _i, _vp, C.c_size_t]),
     "mo_map_write_ply": (_i, [_vp, C.c_char_p, _i, _vp]),
     "mo_map_relocalize": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_dbg_map_reloc_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_track": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
     "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
