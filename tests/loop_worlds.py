@@ -183,6 +183,36 @@ def tiny_world(n_kf):
     return _W[("tiny", n_kf)]
 
 
+FEATURE_WORDS = 8
+
+
+def feature_world():
+    """4 keyframes of 8 rows and 12 points: the smallest tiny world, for the tests that only need every map feature to have run"""
+    if "features" not in _W:
+        _W["features"] = TinyWorld(4, FEATURE_WORDS)
+    return _W["features"]
+
+
+def feature_steps(m, w, vocabulary):
+    """[(name, fn)]: one call of each of the eight map features on the built feature_world, covisibility first; keyframe 0 is the query
+    frame.  Place recognition is the attached vocabulary and a query; the loop candidates need it and come behind it.  Every call gets
+    past its argument checks and runs its chain on the device, whatever it finds on a map of random points."""
+    from tests.map_worlds import kps_array
+    kps, desc = kps_array(w.kf_xy[0]), w.kf_desc[0]
+
+    def place():
+        m.set_vocabulary(vocabulary)
+        return m.query_keyframes(kps, desc, 3)
+    return [("covisibility", m.covisibility),
+            ("relocalize", lambda: m.relocalize(kps, desc, n_hyp=8)),
+            ("track", lambda: m.track_local_map(kps, desc, np.eye(4), window=0, min_matches=1)),
+            ("bundle_adjust", lambda: m.bundle_adjust(window=4)),
+            ("fuse", lambda: m.fuse_map_points(image_size=w.image_size, window=0)),
+            ("grow", lambda: m.create_new_map_points(window=0)),
+            ("place", place),
+            ("loop", lambda: m.loop_candidates(3, TINY_MIN_WEIGHT, 2, 2))]
+
+
 # ---- hand cases -----------------------------------------------------------------------------------------------------------------------
 def _word_desc(w, n_words=8):
     """a descriptor 0 bits from word w of hand_words()"""

@@ -106,3 +106,51 @@ def test_refused_calls_leave_the_context_usable(frames):
     assert last_error() == refused
     assert ctx.dev_status() == 0
     ctx.close()
+
+
+def _reloc_last(m):
+    """(rc, everything mo_dbg_map_reloc_last wrote)"""
+    import ctypes as C
+    n = C.c_int32(-7)
+    cand, ncorr, ninl = (np.full(64, -7, np.int32) for _ in range(3))
+    best = np.full(64, 7, np.uint64)
+    pose = np.full((64, 12), 7.0)
+    rc = m.lib.mo_dbg_map_reloc_last(m._h, C.byref(n), V._ptr(cand), V._ptr(best), V._ptr(ncorr), V._ptr(ninl), V._ptr(pose))
+    return rc, _bytes_of([n.value, cand, best, ncorr, ninl, pose])
+
+
+def test_map_features_live_and_die_with_their_map(frames):
+    """every feature has run on one map; the vocabulary is replaced and the query answers against the new one; the last relocalization
+    stays readable; the map goes, and the context extracts what it extracted before the map existed; a map that has run nothing has no
+    relocalization to report"""
+    from tests import bow_restatement as B
+    from tests import loop_worlds as LW
+    from tests.map_worlds import kps_array
+    small, _ = frames
+    ctx = V.Context(max_w=128, max_h=128, max_batch=1)
+    prm = V.orb_params(nfeatures=100, nlevels=3)
+    before = _bytes_of(ctx.orb_detect_compute(small[0], prm))
+    w = LW.feature_world()
+    m = w.build(ctx)
+    voc = V.Vocabulary.from_arrays(w.words, w.weights, context=ctx)
+    for name, fn in LW.feature_steps(m, w, voc):
+        fn()
+    rc, last = _reloc_last(m)
+    assert rc == V.MO_OK
+    # another vocabulary: the words in reverse order, the weights 1, 2, 3, ...
+    words2 = np.ascontiguousarray(w.words[::-1])
+    weights2 = np.arange(1, len(words2) + 1, dtype=np.int32)
+    voc2 = V.Vocabulary.from_arrays(words2, weights2, context=ctx)
+    m.set_vocabulary(voc2)
+    kps, desc = kps_array(w.kf_xy[1]), w.kf_desc[1]
+    pos, score = m.query_keyframes(kps, desc, 4)
+    want_pos, want_score = B.query(desc, w.kf_desc, words2, weights2, 4)
+    assert len(pos) > 0 and pos.tolist() == list(want_pos) and np.array_equal(score, np.asarray(want_score, np.float64))
+    assert _reloc_last(m) == (V.MO_OK, last)
+    _clean(ctx)
+    m.close()
+    assert _bytes_of(ctx.orb_detect_compute(small[0], prm)) == before
+    m2 = LW.new_mapper(ctx, w.K, (8, 16, 16, 32))
+    assert _reloc_last(m2)[0] == V.MO_ERR_ARG
+    m2.close(); voc.close(); voc2.close()
+    ctx.close()

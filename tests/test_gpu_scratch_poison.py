@@ -488,3 +488,33 @@ def test_vocabulary_training_hand_cases():
              ("split, none", lambda c: train(c, BW.hand_split(), iters=0)), ("as many words as rows", lambda c: train(c, BW.hand_split(), W=8)),
              ("duplicates", lambda c: train(c, BW.hand_duplicates()))]
     _sweep(_ctx, calls, fresh=False)
+
+
+# ---- no map feature leaves the audit ------------------------------------------------------------------------------------------------------
+# What one covisibility() fills under a poison byte on loop_worlds.feature_world: after covisibility alone, then after each further
+# feature of feature_steps has run once.  Measured on the commit before the features registered themselves with the map (its library
+# through VSLAM_AMD_LIB, this test printing the sequence); a feature that registers nothing, or one the fill walks past, changes a count.
+FEATURE_FILLS = [18, 30, 41, 68, 85, 94, 102, 120]
+
+
+def test_every_map_feature_joins_the_poison_fill():
+    import vslam_amd as V
+    from tests import loop_worlds as LW
+    ctx = _ctx()
+    w = LW.feature_world()
+    m = w.build(ctx)
+    voc = V.Vocabulary.from_arrays(w.words, w.weights, context=ctx)
+    _set(ctx, 90)
+    steps = LW.feature_steps(m, w, voc)
+    assert [name for name, _ in steps][0] == "covisibility" and len(steps) == 8
+    fills = []
+    for name, fn in steps:
+        fn()
+        before = _filled(ctx)[0]
+        m.covisibility()
+        fills.append(_filled(ctx)[0] - before)
+    print("buffers one covisibility() fills after each feature:", fills)
+    assert all(b > a for a, b in zip(fills, fills[1:])), fills   # every feature added at least one buffer
+    assert fills == FEATURE_FILLS
+    assert ctx.dev_status() == 0
+    m.close(); voc.close(); ctx.close()

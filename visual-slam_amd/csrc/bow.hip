@@ -13,7 +13,7 @@
 // every kernel here keeps all of its LDS in the dynamic region, whose base is 16-byte aligned
 #define BOW_RED_BYTES 64   // the block-reduction scratch behind the per-word array
 
-struct BowBufs {
+struct BowBufs : MapFeature {
     mo_vocab* v = nullptr;
     int Wp = 0, db_rows = 0;
     DevBuf<uint16_t> db;                 // [db_rows][Wp] term counts by keyframe slot; the row of the spare slot is the query frame's
@@ -25,7 +25,7 @@ struct BowBufs {
     // frame of every quantisation pair
     std::vector<int32_t> h_up; DevBuf<int32_t> up;
     const int32_t* cnt = nullptr; const int32_t* lst = nullptr; const int32_t* ltf = nullptr;
-    DevBuf<int32_t> qidx, qdist; DevBuf<uint8_t> qpass;   // [pair][stride] matcher outputs
+    MatchBufs match;                     // [pair][stride]: idx[2 * r] is the word of query row r (the layout is emit_match's, match_kernels.hip)
     DevBuf<double> score;                // [n_kf]
     DevBuf<int32_t> common;              // [n_kf] common words with the asking keyframe (mo_map_loop_candidates)
     DevBuf<int32_t> out_pos, out_n; DevBuf<double> out_score;
@@ -33,12 +33,10 @@ struct BowBufs {
     // scratch: what every call's chain writes before it reads.  db and norm are state (the rows `done` vouches for are read by later
     // calls); a DevBuf added above is named here or in this sentence
     template <class F> void each_scratch(F f) {
-        f(up); f(qidx); f(qdist); f(qpass); f(score); f(common); f(out_pos); f(out_n); f(out_score); f(sel_qf); f(sel_tf); f(mrow);
+        f(up); match.each_scratch(f); f(score); f(common); f(out_pos); f(out_n); f(out_score); f(sel_qf); f(sel_tf); f(mrow);
     }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(BowBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, BowBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // ---- block sum of int64 over 256 threads, scratch = 4 values in LDS; thread 0 holds the sum ---------------------------------------------
 __device__ __forceinline__ long long bow_block_sum(long long v, long long* red) {
@@ -356,18 +354,17 @@ extern "C" int mo_map_set_vocabulary(mo_map* m, mo_vocab* v) {
     if (v && v->c != c) return mo_fail(c, MO_ERR_ARG, "the vocabulary belongs to another context");
     MAP_ENTER(m);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    map_scratch_free(m->bow);
-    m->bow = nullptr;
+    map_feature_drop<BowBufs>(m);
     if (v) {
-        m->bow = new BowBufs();
-        m->bow->v = v;
-        m->bow->Wp = v->Wp;
+        BowBufs& b = map_feature<BowBufs>(m);
+        b.v = v;
+        b.Wp = v->Wp;
     }
     return MO_OK;
 }
 
 int bow_require(mo_map* m) {
-    return m->bow ? MO_OK : mo_fail(m->c, MO_ERR_ARG, "no vocabulary attached to the map (mo_map_set_vocabulary)");
+    return map_feature_if<BowBufs>(m) ? MO_OK : mo_fail(m->c, MO_ERR_ARG, "no vocabulary attached to the map (mo_map_set_vocabulary)");
 }
 
 // every stale row and the frame's row brought up to date: one quantise launch (a pair per stale keyframe and one for the frame), one
@@ -375,7 +372,7 @@ int bow_require(mo_map* m) {
 // it is; with no stale keyframe nothing is launched, the two stage marks are still set.
 static int bow_update(mo_map* m, int n, bool frame = true) {
     mo_ctx* c = m->c;
-    BowBufs& b = *m->bow;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
     const mo_vocab& v = *b.v;
     const int spare = m->kslots, rows = m->kslots + 1, row = m->row;
     int rc;
@@ -402,17 +399,15 @@ static int bow_update(mo_map* m, int n, bool frame = true) {
     b.h_up[spare] = frame ? n : 0; b.h_up[rows] = v.W;
     std::copy(b.h_lst.begin(), b.h_lst.end(), b.h_up.begin() + rows + 2);
     std::fill(b.h_up.begin() + rows + 2 + n_list, b.h_up.end(), rows);
-    if ((rc = b.up.reserve(c, b.h_up.size())) || (rc = b.qidx.reserve(c, out_n * 2)) || (rc = b.qdist.reserve(c, out_n * 2)) ||
-        (rc = b.qpass.reserve(c, out_n)))
-        return rc;
+    if ((rc = mo_reserve(c, b.up, b.h_up.size(), b.match, out_n))) return rc;
     b.cnt = b.up; b.lst = b.up + rows + 2; b.ltf = b.lst + n_list;
     HIPCHK(c, hipMemcpyAsync(b.up, b.h_up.data(), b.h_up.size() * 4, hipMemcpyHostToDevice, c->stream));
     // train frame `rows` of a stride of 0 bytes: the words themselves
-    if ((rc = match_launch_pairs(c, m->kdesc, v.words, (size_t)row * 32, 0, b.cnt, b.lst, b.ltf, 0, 0, n_list, stride, -1.0, b.qidx, b.qdist, b.qpass)))
+    if ((rc = match_launch_pairs(c, m->kdesc, v.words, (size_t)row * 32, 0, b.cnt, b.lst, b.ltf, 0, 0, n_list, stride, -1.0, b.match.idx, b.match.dist, b.match.pass)))
         return rc;
     mo_stage_mark(c, "bow_quantise");
     if (n_list > 0) {
-        hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.qidx, v.W, b.Wp,
+        hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.match.idx, v.W, b.Wp,
                            v.weights, b.db, b.norm);
         HIPCHK(c, hipGetLastError());
     }
@@ -424,13 +419,13 @@ static int bow_update(mo_map* m, int n, bool frame = true) {
 // update, scores and ranking for the frame staged in the spare slot, enqueued; sel: also the matcher's pair list
 static int bow_enqueue(mo_map* m, int n, int n_best, bool sel) {
     mo_ctx* c = m->c;
-    BowBufs& b = *m->bow;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
     const int n_kf = (int)m->pos_slot.size(), spare = m->kslots;
     int rc;
     if ((rc = bow_update(m, n))) return rc;
     const size_t nb = (size_t)std::max(n_best, 1);
-    if ((rc = b.score.reserve(c, (size_t)n_kf)) || (rc = b.out_pos.reserve(c, nb)) || (rc = b.out_score.reserve(c, nb)) || (rc = b.out_n.reserve(c, 1)) ||
-        (sel && ((rc = b.sel_qf.reserve(c, nb)) || (rc = b.sel_tf.reserve(c, nb)) || (rc = b.mrow.reserve(c, (size_t)n_kf)))))
+    if ((rc = mo_reserve(c, b.score, (size_t)n_kf, b.out_pos, nb, b.out_score, nb, b.out_n, 1)) ||
+        (sel && (rc = mo_reserve(c, b.sel_qf, nb, b.sel_tf, nb, b.mrow, (size_t)n_kf))))
         return rc;
     hipLaunchKernelGGL(k_bow_score<false>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf, spare,
                        b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<false>{});
@@ -445,7 +440,7 @@ static int bow_enqueue(mo_map* m, int n, int n_best, bool sel) {
 
 int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel) {
     if (int rc = bow_enqueue(m, n, n_pre, true)) return rc;
-    BowBufs& b = *m->bow;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
     sel->cnt = b.cnt; sel->qf = b.sel_qf; sel->tf = b.sel_tf; sel->mrow = b.mrow;
     return MO_OK;
 }
@@ -454,10 +449,10 @@ int bow_update_enqueue(mo_map* m) { return bow_update(m, 0, false); }
 
 int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w, BowLoop* out) {
     mo_ctx* c = m->c;
-    BowBufs& b = *m->bow;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
     const int n_kf = (int)m->pos_slot.size(), q_slot = m->pos_slot[q_pos];
     int rc;
-    if ((rc = b.score.reserve(c, (size_t)n_kf)) || (rc = b.common.reserve(c, (size_t)n_kf))) return rc;
+    if ((rc = mo_reserve(c, b.score, (size_t)n_kf, b.common, (size_t)n_kf))) return rc;
     hipLaunchKernelGGL(k_bow_score<true>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf,
                        q_slot, b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<true>{wrow, q_pos, min_w, b.common});
     HIPCHK(c, hipGetLastError());
@@ -483,7 +478,7 @@ extern "C" int mo_map_query_keyframes(mo_map* m, const mo_frame_ref* f, const mo
     mo_keypoint* qk; uint8_t* qdesc;
     if ((rc = map_stage_frame(m, f, false, &out->from_token, [](int) {}, &n, &qk, &qdesc)) || !qk || nb == 0) return rc;   // (nothing to rank: not an error)
     if ((rc = bow_enqueue(m, n, nb, false))) return rc;
-    BowBufs& b = *m->bow;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
     HIPCHK(c, hipMemcpyAsync(out->pos, b.out_pos, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out->score, b.out_score, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&out->n, b.out_n, 4, hipMemcpyDeviceToHost, c->stream));

@@ -47,7 +47,7 @@ struct BaRes {
     int32_t free_pos[BA_MAX_FREE];
 };
 
-struct BaBufs {
+struct BaBufs : MapFeature {
     // per map point
     DevBuf<int32_t> loc, ecnt, lrank, ebase;
     DevBuf<double> pout;                                         // [point][3] the optional f64 output
@@ -60,7 +60,7 @@ struct BaBufs {
     // per keyframe position
     DevBuf<int32_t> kf_edge, kf_fidx; DevBuf<double> poseC, poseT;
     DevBuf<double> S;                                            // [96][96] reduced system, [96] right side, [96] solution
-    DevBuf<BaRes> res; PinnedBuf<BaRes> h_res;
+    ResBlock<BaRes> res;
     // mo_map_add_observations
     DevBuf<int32_t> ao_pt, ao_row, ao_claim, ao_cnt, ao_base, ao_total;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
@@ -69,10 +69,8 @@ struct BaBufs {
         f(e_kf); f(e_obs); f(e_xy); f(e_info); f(e_inl); f(einl); f(kf_edge); f(kf_fidx); f(poseC); f(poseT); f(S); f(res);
         f(ao_pt); f(ao_row); f(ao_claim); f(ao_cnt); f(ao_base); f(ao_total);
     }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(BaBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, BaBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // fixed-order sums: lane 0's shuffle tree per wave (wave_sum), then the waves in order; every thread receives the result
 __device__ __forceinline__ double ba_block_sum(double v, double* lds) {
@@ -518,18 +516,13 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     if (n_kf == 0 || np == 0 || no == 0) return MO_OK;   // an empty map: nothing runs, not an error
     int rc;
     if ((rc = map_int32_guard(m))) return rc;
-    if (!m->ba) m->ba = new BaBufs();
-    BaBufs& b = *m->ba;
-    if ((rc = b.loc.reserve(c, np)) || (rc = b.ecnt.reserve(c, np)) || (rc = b.lrank.reserve(c, np)) || (rc = b.ebase.reserve(c, np)) ||
-        (rc = b.lpt.reserve(c, np)) || (rc = b.eoff.reserve(c, np + 1)) || (rc = b.pn.reserve(c, np)) || (rc = b.pfix.reserve(c, np)) ||
-        (rc = b.X.reserve(c, np * 3)) || (rc = b.Xt.reserve(c, np * 3)) || (rc = b.Vi.reserve(c, np * 6)) || (rc = b.gp.reserve(c, np * 3)) ||
-        (rc = b.pc.reserve(c, np)) || (rc = b.pt.reserve(c, np)) || (rc = b.pu.reserve(c, np)) || (rc = b.e_kf.reserve(c, no)) ||
-        (rc = b.e_obs.reserve(c, no)) || (rc = b.e_xy.reserve(c, no * 2)) || (rc = b.e_info.reserve(c, no)) || (rc = b.e_inl.reserve(c, no)) ||
-        (rc = b.einl.reserve(c, no)) || (rc = b.kf_edge.reserve(c, (size_t)n_kf)) || (rc = b.kf_fidx.reserve(c, (size_t)n_kf)) ||
-        (rc = b.poseC.reserve(c, (size_t)n_kf * 12)) || (rc = b.poseT.reserve(c, (size_t)n_kf * 12)))
+    BaBufs& b = map_feature<BaBufs>(m);
+    if ((rc = mo_reserve(c, b.loc, np, b.ecnt, np, b.lrank, np, b.ebase, np, b.lpt, np, b.eoff, np + 1, b.pn, np, b.pfix, np, b.X, np * 3, b.Xt, np * 3,
+                         b.Vi, np * 6, b.gp, np * 3, b.pc, np, b.pt, np, b.pu, np, b.e_kf, no, b.e_obs, no, b.e_xy, no * 2, b.e_info, no, b.e_inl, no,
+                         b.einl, no, b.kf_edge, (size_t)n_kf, b.kf_fidx, (size_t)n_kf, b.poseC, (size_t)n_kf * 12, b.poseT, (size_t)n_kf * 12)))
         return rc;
-    if (out->points_out && (rc = b.pout.reserve(c, np * 3))) return rc;
-    if ((rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)) || (rc = b.S.reserve(c, BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM))) return rc;
+    if (out->points_out && (rc = mo_reserve(c, b.pout, np * 3))) return rc;
+    if ((rc = mo_reserve(c, b.res, b.S, BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
     HIPCHK(c, hipMemcpyAsync(b.poseC, poses, (size_t)n_kf * 96, hipMemcpyHostToDevice, c->stream));
@@ -577,13 +570,13 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "ba_write");
     std::vector<int32_t> fidx(out->kf_state ? (size_t)n_kf : 0);
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(BaRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     if (out->poses_out) HIPCHK(c, hipMemcpyAsync(out->poses_out, b.poseC, (size_t)n_kf * 96, hipMemcpyDeviceToHost, c->stream));
     if (out->edge_inlier) HIPCHK(c, hipMemcpyAsync(out->edge_inlier, b.einl, no, hipMemcpyDeviceToHost, c->stream));
     if (out->points_out) HIPCHK(c, hipMemcpyAsync(out->points_out, b.pout, np * 24, hipMemcpyDeviceToHost, c->stream));
     if (out->kf_state) HIPCHK(c, hipMemcpyAsync(fidx.data(), b.kf_fidx, (size_t)n_kf * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = map_sync(c, clk))) return rc;
-    const BaRes& r = *b.h_res;
+    const BaRes& r = b.res.host();
     if (!r.run) return MO_OK;   // no free keyframe with an edge, or no local point
     out->n_local = r.n_local;
     for (int i = 0; i < 3; i++) out->cost[i] = r.cost[i];
@@ -646,13 +639,10 @@ extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32
     if (n == 0 || m->n_pts == 0) return MO_OK;
     if (m->n_pts > INT32_MAX / 2 || m->n_obs + n > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
     MAP_ENTER(m);
-    if (!m->ba) m->ba = new BaBufs();
-    BaBufs& b = *m->ba;
+    BaBufs& b = map_feature<BaBufs>(m);
     const size_t np = (size_t)m->n_pts;
     int rc;
-    if ((rc = b.ao_pt.reserve(c, (size_t)n)) || (rc = b.ao_row.reserve(c, (size_t)n)) || (rc = b.ao_claim.reserve(c, np)) ||
-        (rc = b.ao_cnt.reserve(c, np)) || (rc = b.ao_base.reserve(c, np)) || (rc = b.ao_total.reserve(c, 4)))
-        return rc;
+    if ((rc = mo_reserve(c, b.ao_pt, (size_t)n, b.ao_row, (size_t)n, b.ao_claim, np, b.ao_cnt, np, b.ao_base, np, b.ao_total, 4))) return rc;
     const size_t new_obs = (size_t)m->n_obs + std::min<size_t>((size_t)n, np);
     if ((rc = map_pts_reserve(m, m->cur ^ 1, np, new_obs, false))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;

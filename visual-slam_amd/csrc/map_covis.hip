@@ -28,19 +28,17 @@ static_assert(CV_LDS_MAX_KF <= 128, "k_covis holds a point's positions in two 64
 
 struct CovisRes { int32_t n_k1, n_local_kf, ref; };
 
-struct CovisBufs {
+struct CovisBufs : MapFeature {
     DevBuf<int32_t> W;                    // [n_kf][n_kf] of the last mo_map_covisibility / mo_map_local_keyframes / mo_map_track_covisible
     DevBuf<int32_t> votes, loc;           // [n_kf] votes of the seeds; 1 = K1, 2 = K2 only
     DevBuf<uint8_t> mask;                 // [n_kf] loc as bytes (the output, and k_trk_rep's local-keyframe predicate)
     DevBuf<int32_t> seeds; PinnedBuf<int32_t> h_seeds;
-    DevBuf<CovisRes> res; PinnedBuf<CovisRes> h_res;
+    ResBlock<CovisRes> res;
     // all of it is scratch, W included: every reader (the three calls above, mo_map_loop_candidates) runs covis_enqueue in its own chain
     // first (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) { f(W); f(votes); f(loc); f(mask); f(seeds); f(res); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(CovisBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, CovisBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 __device__ __forceinline__ int cv_pop(unsigned long long& lo, unsigned long long& hi) {   // the lowest position of the set, removed
     if (lo) { const int p = __ffsll(lo) - 1; lo &= lo - 1; return p; }
@@ -176,8 +174,7 @@ int covis_enqueue(mo_map* m) {
     int rc;
     if (n_kf * n_kf > (size_t)INT32_MAX) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
     if ((rc = map_int32_guard(m))) return rc;
-    if (!m->cv) m->cv = new CovisBufs();
-    CovisBufs& b = *m->cv;
+    CovisBufs& b = map_feature<CovisBufs>(m);
     if ((rc = b.W.reserve(c, n_kf * n_kf))) return rc;
     HIPCHK(c, hipMemsetAsync(b.W, 0, n_kf * n_kf * 4, c->stream));
     if (m->n_pts > 0) {
@@ -196,12 +193,10 @@ int covis_enqueue(mo_map* m) {
 
 int covis_select_enqueue(mo_map* m, const mo_map_local_params* prm) {
     mo_ctx* c = m->c;
-    CovisBufs& b = *m->cv;
+    CovisBufs& b = map_feature<CovisBufs>(m);
     const size_t n_kf = m->pos_slot.size(), ns = (size_t)prm->n_seed;
     int rc;
-    if ((rc = b.votes.reserve(c, n_kf)) || (rc = b.loc.reserve(c, n_kf)) || (rc = b.mask.reserve(c, n_kf)) || (rc = b.res.reserve(c, 1)) ||
-        (rc = b.h_res.reserve(c, 1)) || (rc = b.seeds.reserve(c, std::max(ns, (size_t)1))) || (rc = b.h_seeds.reserve(c, std::max(ns, (size_t)1))))
-        return rc;
+    if ((rc = mo_reserve(c, b.votes, n_kf, b.loc, n_kf, b.mask, n_kf, b.res, b.seeds, std::max(ns, (size_t)1), b.h_seeds, std::max(ns, (size_t)1)))) return rc;
     if (ns) {   // (through a pinned block of the map's own: the caller's array is free again when the call returns, whatever the copy does)
         std::memcpy(b.h_seeds.p, prm->seed_points, ns * 4);
         HIPCHK(c, hipMemcpyAsync(b.seeds, b.h_seeds, ns * 4, hipMemcpyHostToDevice, c->stream));
@@ -217,19 +212,19 @@ int covis_select_enqueue(mo_map* m, const mo_map_local_params* prm) {
 
 int covis_copy_enqueue(mo_map* m, mo_map_local_out* out) {
     mo_ctx* c = m->c;
-    CovisBufs& b = *m->cv;
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(CovisRes), hipMemcpyDeviceToHost, c->stream));
+    CovisBufs& b = map_feature<CovisBufs>(m);
+    if (int rc = b.res.download(c)) return rc;
     if (out->local) HIPCHK(c, hipMemcpyAsync(out->local, b.mask, m->pos_slot.size(), hipMemcpyDeviceToHost, c->stream));
     return MO_OK;
 }
 
 void covis_finish(mo_map* m, mo_map_local_out* out) {
-    const CovisRes& r = *m->cv->h_res;
+    const CovisRes& r = map_feature<CovisBufs>(m).res.host();
     out->n_k1 = r.n_k1; out->n_local_kf = r.n_local_kf; out->ref = r.ref;
 }
 
-const uint8_t* covis_mask(const mo_map* m) { return m->cv->mask; }
-const int32_t* covis_weights(const mo_map* m) { return m->cv->W; }
+const uint8_t* covis_mask(const mo_map* m) { return map_feature_if<CovisBufs>(m)->mask; }
+const int32_t* covis_weights(const mo_map* m) { return map_feature_if<CovisBufs>(m)->W; }
 
 extern "C" int mo_map_covisibility(mo_map* m, int32_t* weights, int32_t* n_kf) {
     if (!m) return MO_ERR_ARG;
@@ -244,7 +239,7 @@ extern "C" int mo_map_covisibility(mo_map* m, int32_t* weights, int32_t* n_kf) {
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
     if ((rc = covis_enqueue(m))) return rc;
-    if (weights) HIPCHK(c, hipMemcpyAsync(weights, m->cv->W, n * n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (weights) HIPCHK(c, hipMemcpyAsync(weights, covis_weights(m), n * n * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = map_sync(c, clk))) return rc;
     return MO_OK;
 }

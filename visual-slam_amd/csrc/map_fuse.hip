@@ -39,7 +39,7 @@ struct FuseRes {
     int32_t n_points, n_obs, n_members;
 };
 
-struct FuseBufs {
+struct FuseBufs : MapFeature {
     DevBuf<uint8_t> rep;                  // [point][32] representative descriptors
     DevBuf<int32_t> oct;                  // [point] ref_octave (TK_NOT_LOCAL: not in the local map)
     DevBuf<int32_t> cell, sorted;         // [target][TK_CELLS + 1], [target][row]: the keypoint grids
@@ -50,15 +50,13 @@ struct FuseBufs {
     DevBuf<unsigned long long> surv;      // [point] at a root: (~valid observations << 32) | point of the survivor
     DevBuf<int32_t> mcnt, mbase, mcur, mem;   // [point] members per root, their first entry, scatter cursors, the member lists
     DevBuf<int32_t> into;                 // [point] new index of the point each old point now is
-    DevBuf<FuseRes> res; PinnedBuf<FuseRes> h_res;
+    ResBlock<FuseRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) {
         f(rep); f(oct); f(cell); f(sorted); f(tab); f(key); f(prop); f(parent); f(root); f(nval); f(surv); f(mcnt); f(mbase); f(mcur); f(mem); f(into); f(res);
     }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(FuseBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, FuseBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // what the fuse kernels read (by value): the map, and fuse's own tables and window
 struct FuseView {
@@ -278,16 +276,12 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     if (m->n_pts > INT32_MAX / 2 || (size_t)m->n_obs + gain_bound > (size_t)(INT32_MAX / 2) || np * (size_t)nt > (size_t)INT32_MAX ||
         (size_t)nt * row > (size_t)INT32_MAX)
         return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    if (!m->fu) m->fu = new FuseBufs();
-    FuseBufs& b = *m->fu;
+    FuseBufs& b = map_feature<FuseBufs>(m);
     int rc;
     const size_t trow = (size_t)nt * row;
-    if ((rc = b.rep.reserve(c, np * 32)) || (rc = b.oct.reserve(c, np)) || (rc = b.cell.reserve(c, (size_t)nt * (TK_CELLS + 1))) ||
-        (rc = b.sorted.reserve(c, trow)) || (rc = b.tab.reserve(c, trow)) || (rc = b.key.reserve(c, trow)) || (rc = b.prop.reserve(c, np * nt)) ||
-        (rc = b.parent.reserve(c, np)) || (rc = b.root.reserve(c, np)) || (rc = b.nval.reserve(c, np)) || (rc = b.surv.reserve(c, np)) ||
-        (rc = b.mcnt.reserve(c, np)) || (rc = b.mbase.reserve(c, np)) || (rc = b.mcur.reserve(c, np)) || (rc = b.mem.reserve(c, np)) ||
-        (rc = b.into.reserve(c, np)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)) || (rc = m->keep.reserve(c, np)) ||
-        (rc = m->kobs.reserve(c, np)) || (rc = m->rank.reserve(c, np)) || (rc = m->obase.reserve(c, np)))
+    if ((rc = mo_reserve(c, b.rep, np * 32, b.oct, np, b.cell, (size_t)nt * (TK_CELLS + 1), b.sorted, trow, b.tab, trow, b.key, trow, b.prop, np * nt,
+                         b.parent, np, b.root, np, b.nval, np, b.surv, np, b.mcnt, np, b.mbase, np, b.mcur, np, b.mem, np, b.into, np, b.res,
+                         m->keep, np, m->kobs, np, m->rank, np, m->obase, np)))
         return rc;
     if ((rc = map_pts_reserve(m, m->cur ^ 1, np, (size_t)m->n_obs + gain_bound, false)) || (rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
@@ -321,7 +315,7 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
                        b.into, m->st, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "fuse_merge");
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(FuseRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     // (into is read only after a call that fused: the kernel behind the flag leaves it unwritten otherwise, and the identity above stays)
     std::vector<int32_t> into;
     if (out->into) {
@@ -329,7 +323,7 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
         HIPCHK(c, hipMemcpyAsync(into.data(), b.into, np * 4, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = map_sync(c, clk))) return rc;
-    const FuseRes& r = *b.h_res;
+    const FuseRes& r = b.res.host();
     out->n_targets = nt; out->n_local = r.n_local; out->n_pairs = r.n_pairs; out->n_cand = r.n_cand;
     if (!r.n_proposals) return MO_OK;   // (nothing was written)
     out->n_proposals = r.n_proposals; out->n_gained = r.n_gained; out->n_edges = r.n_edges; out->n_absorbed = r.n_absorbed;

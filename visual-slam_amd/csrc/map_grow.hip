@@ -57,7 +57,7 @@ struct GrowRes {
     int32_t n_free, n_accepted, n_matches, n_new, n_obs_new, pad;
 };
 
-struct GrowBufs {
+struct GrowBufs : MapFeature {
     PinnedBuf<GrowPair> h_pairs;          // [neighbour] as formed on the host
     DevBuf<GrowPair> pairs;               // [neighbour]
     DevBuf<int32_t> tab;                  // [neighbour .. target][row] point_of (INT_MAX: a free row)
@@ -68,13 +68,11 @@ struct GrowBufs {
     DevBuf<double> outX;                  // [n_new][3]
     DevBuf<int32_t> point;                // [row] the new point of each target row
     PinnedBuf<int32_t> h_point; PinnedBuf<double> h_X;   // the copy-out
-    DevBuf<GrowRes> res; PinnedBuf<GrowRes> h_res;
+    ResBlock<GrowRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) { f(pairs); f(tab); f(frow); f(key); f(prop); f(X); f(outX); f(point); f(res); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(GrowBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, GrowBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // ---- host: the geometry of the pairs, in the header's operation order ---------------------------------------------------------------
 static GrowCam grow_cam(const double* T, int slot, int pos) {
@@ -380,17 +378,13 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     const size_t np = (size_t)m->n_pts, bound_obs = (size_t)n_rows * ((size_t)nb + 1);
     if (np + (size_t)n_rows > (size_t)(INT32_MAX / 2) || (size_t)m->n_obs + bound_obs > (size_t)(INT32_MAX / 2) || ((size_t)nb + 1) * row > (size_t)INT32_MAX)
         return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
-    if (!m->gr) m->gr = new GrowBufs();
-    GrowBufs& b = *m->gr;
+    GrowBufs& b = map_feature<GrowBufs>(m);
     int rc;
     const size_t nrow = (size_t)nb * row, trow = nrow + row;
-    if ((rc = b.pairs.reserve(c, (size_t)nb)) || (rc = b.tab.reserve(c, trow)) || (rc = b.frow.reserve(c, (size_t)row)) || (rc = b.key.reserve(c, nrow)) ||
-        (rc = b.prop.reserve(c, nrow)) || (rc = b.X.reserve(c, (size_t)row * 3)) ||
-        (rc = b.outX.reserve(c, (size_t)row * 3)) || (rc = b.point.reserve(c, (size_t)row)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)) ||
-        (rc = b.h_pairs.reserve(c, (size_t)nb)) || (out->point && (rc = b.h_point.reserve(c, (size_t)row))) ||
-        (out->points && (rc = b.h_X.reserve(c, (size_t)row * 3))) ||
-        (rc = m->keep.reserve(c, (size_t)row)) || (rc = m->kobs.reserve(c, (size_t)row)) || (rc = m->rank.reserve(c, (size_t)row)) ||
-        (rc = m->obase.reserve(c, (size_t)row)))
+    if ((rc = mo_reserve(c, b.pairs, (size_t)nb, b.tab, trow, b.frow, (size_t)row, b.key, nrow, b.prop, nrow, b.X, (size_t)row * 3, b.outX, (size_t)row * 3,
+                         b.point, (size_t)row, b.res, b.h_pairs, (size_t)nb, m->keep, (size_t)row, m->kobs, (size_t)row, m->rank, (size_t)row,
+                         m->obase, (size_t)row)) ||
+        (out->point && (rc = mo_reserve(c, b.h_point, (size_t)row))) || (out->points && (rc = mo_reserve(c, b.h_X, (size_t)row * 3))))
         return rc;
     // capacity for a point per free target row (bounded by the target's rows) with an observation in every keyframe of the call
     if ((rc = map_pts_reserve(m, m->cur, np + (size_t)n_rows, (size_t)m->n_obs + bound_obs, true)) || (rc = upload_pos_slot(m))) return rc;
@@ -429,7 +423,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
                        (int)m->n_obs, dst, b.outX, b.point, m->st, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "grow_points");
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(GrowRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     if (out->point) {
         HIPCHK(c, hipMemcpyAsync(b.h_point.p, b.point, (size_t)n_rows * 4, hipMemcpyDeviceToHost, c->stream));
     }
@@ -437,7 +431,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
         HIPCHK(c, hipMemcpyAsync(b.h_X.p, b.outX, (size_t)n_rows * 24, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = map_sync(c, clk))) return rc;
-    const GrowRes& r = *b.h_res;
+    const GrowRes& r = b.res.host();
     out->n_free = r.n_free; out->n_epi = (int64_t)r.n_epi; out->n_accepted = r.n_accepted; out->n_matches = r.n_matches;
     if (!r.n_new) return MO_OK;   // (nothing was written)
     out->n_new = r.n_new; out->n_obs_new = r.n_obs_new;

@@ -81,6 +81,7 @@ int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_
 
 // ---- growth: the F-RANSAC inliers of one keyframe pair, in query order, onto the end of the map (local_mapper.py:150-187) --------
 // One block of 1024 threads walks the query keypoints in tiles (ballot + block scan); the map's live counts come from the status block.
+// midx: MatchBufs::idx of the one pair, midx[2 * q] the best neighbour of query q (the layout is emit_match's, match_kernels.hip).
 __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__ inl, const int32_t* __restrict__ midx, const float* __restrict__ gpts,
                                                      const double* __restrict__ F, const mo_keypoint* __restrict__ qkps, const int32_t* __restrict__ qcnt,
                                                      const uint8_t* __restrict__ img, int w, int h, int ch, int prev_id, int cur_id, int prev_slot,
@@ -348,11 +349,9 @@ int upload_pos_slot(mo_map* m) {
 
 int map_poison(mo_map* m) {
     mo_ctx* c = m->c;
-    int rc;
-    if ((rc = mo_poison_scratch(c, *m)) || (rc = map_scratch_poison(c, m->rl)) || (rc = map_scratch_poison(c, m->tk)) || (rc = map_scratch_poison(c, m->ba)) ||
-        (rc = map_scratch_poison(c, m->fu)) || (rc = map_scratch_poison(c, m->gr)) || (rc = map_scratch_poison(c, m->cv)) ||
-        (rc = map_scratch_poison(c, m->bow)) || (rc = map_scratch_poison(c, m->lp)))
-        return rc;
+    if (int rc = mo_poison_scratch(c, *m)) return rc;
+    for (const auto& f : m->features)
+        if (int rc = f->poison(c)) return rc;
     return MO_OK;
 }
 
@@ -378,7 +377,7 @@ extern "C" void mo_map_destroy(mo_map* m) {
     if (!m) return;
     hipSetDevice(m->c->device);
     hipStreamSynchronize(m->c->stream);
-    delete m;   // every buffer frees itself (DevBuf, PinnedBuf, the scratch structs)
+    delete m;   // every buffer frees itself (DevBuf, PinnedBuf, the features)
 }
 
 // the list / cull / counts chain on the map in P[cur] with `bound_pts` points at most (status block live); results into P[cur ^ 1]
@@ -390,10 +389,7 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     int rc;
     const int bp = (int)std::max<int64_t>(bound_pts, 1), bo = (int)std::max<int64_t>(bound_obs, 1);
     if ((rc = map_pts_reserve(m, m->cur ^ 1, (size_t)bp, (size_t)bo, false))) return rc;
-    if ((rc = m->keep.reserve(c, (size_t)bp)) || (rc = m->kobs.reserve(c, (size_t)bp)) ||
-        (rc = m->rank.reserve(c, (size_t)bp)) || (rc = m->obase.reserve(c, (size_t)bp)))
-        return rc;
-    if ((rc = m->ent_id.reserve(c, (size_t)bo))) return rc;
+    if ((rc = mo_reserve(c, m->keep, (size_t)bp, m->kobs, (size_t)bp, m->rank, (size_t)bp, m->obase, (size_t)bp, m->ent_id, (size_t)bo))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned gp = (unsigned)((bp + 255) / 256);
@@ -408,7 +404,7 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     const int n_chunks = (bo + MAP_LIST_CHUNK - 1) / MAP_LIST_CHUNK;
     const size_t hn = (size_t)std::max(n_kf, 1) * n_chunks;
     if (hn > (size_t)INT32_MAX) return mo_fail(c, MO_ERR_CAPACITY, "list histogram too large");
-    if ((rc = m->hist.reserve(c, hn)) || (rc = m->hbase.reserve(c, hn))) return rc;
+    if ((rc = mo_reserve(c, m->hist, hn, m->hbase, hn))) return rc;
     const int ln = m->lcur ^ 1;
     if ((rc = m->loff[ln].reserve(c, (size_t)n_kf + 1))) return rc;
     if ((rc = m->lids[ln].reserve(c, (size_t)bo))) return rc;
@@ -512,28 +508,25 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     if (ps >= 0 && nq > 0 && n > 0) {
         if (prm->n_hyp < 1) return mo_fail(c, MO_ERR_ARG, "n_hyp must be >= 1");
         const size_t rows = (size_t)m->row;
-        if ((rc = m->midx.reserve(c, rows * 2)) || (rc = m->mdist.reserve(c, rows * 2)) ||
-            (rc = m->mpass.reserve(c, rows)) || (rc = m->inl.reserve(c, rows)) ||
-            (rc = m->gpts.reserve(c, rows * 3)) || (rc = m->F.reserve(c, 9)) || (rc = m->gnp.reserve(c, 1)))
-            return rc;
+        if ((rc = mo_reserve(c, m->match, rows, m->inl, rows, m->gpts, rows * 3, m->F, 9, m->gnp, 1))) return rc;
         bound_new = nq;
         if ((rc = map_pts_reserve(m, m->cur, (size_t)(m->n_pts + bound_new), (size_t)(m->n_obs + 2 * bound_new), true))) return rc;
         if ((rc = upload_pos_slot(m))) return rc;
         const int32_t* qf = m->d_pos_slot + (n_kf - 2);
         const int32_t* tf = m->d_pos_slot + (n_kf - 1);
-        if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, rows * 32, rows * 32, m->kcnt, qf, tf, 0, 0, 1, (int)rows, prm->ratio, m->midx, m->mdist,
-                                     m->mpass)))
+        if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, rows * 32, rows * 32, m->kcnt, qf, tf, 0, 0, 1, (int)rows, prm->ratio, m->match.idx,
+                                     m->match.dist, m->match.pass)))
             return rc;
         mo_stage_mark(c, "match_knn2_ratio");
         TwoViewArgs a = tv_fundamental(1, (int)rows, prm->n_hyp, prm->thr_px, prm->seed, prm->pair_index);
-        a.d_kps = m->kkps; a.d_counts = m->kcnt; a.d_match_idx = m->midx; a.d_match_pass = m->mpass;
+        a.d_kps = m->kkps; a.d_counts = m->kcnt; a.d_match_idx = m->match.idx; a.d_match_pass = m->match.pass;
         a.d_qf = qf; a.d_tf = tf; a.need_two = 1; a.d_P1 = m->kP + (size_t)ps * 12; a.d_P2 = m->kP + (size_t)slot * 12;
         a.d_E = m->F; a.d_points = m->gpts; a.d_n_points = m->gnp; a.d_inlier = m->inl;
         if ((rc = twoview_launch(c, a))) return rc;
         mo_stage_mark(c, "keyframe_f_ransac_triangulate");
         const int pi = m->img_cur ^ 1;  // the previous keyframe's image
         if (!m->img[pi]) { m->img_w[pi] = m->img_h[pi] = 0; }
-        hipLaunchKernelGGL(k_map_append, dim3(1), dim3(1024), 0, c->stream, m->inl, m->midx, m->gpts, m->F, m->kkps + (size_t)ps * rows, m->kcnt + ps,
+        hipLaunchKernelGGL(k_map_append, dim3(1), dim3(1024), 0, c->stream, m->inl, m->match.idx, m->gpts, m->F, m->kkps + (size_t)ps * rows, m->kcnt + ps,
                            m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, m->P[m->cur].view(),
                            m->st);
         HIPCHK(c, hipGetLastError());
@@ -545,8 +538,8 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     if (cull && (rc = run_cull_chain(m, m->n_pts + bound_new, m->n_obs + 2 * bound_new))) return rc;
     HIPCHK(c, hipMemcpyAsync(m->h_stat, m->st, ST_NWORDS * 4, hipMemcpyDeviceToHost, c->stream));
     if (bound_new) {
-        if (out->match_idx) HIPCHK(c, hipMemcpyAsync(out->match_idx, m->midx, (size_t)nq * 8, hipMemcpyDeviceToHost, c->stream));
-        if (out->match_pass) HIPCHK(c, hipMemcpyAsync(out->match_pass, m->mpass, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+        if (out->match_idx) HIPCHK(c, hipMemcpyAsync(out->match_idx, m->match.idx, (size_t)nq * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out->match_pass) HIPCHK(c, hipMemcpyAsync(out->match_pass, m->match.pass, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
         if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, m->inl, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
         if (out->points) HIPCHK(c, hipMemcpyAsync(out->points, m->gpts, (size_t)nq * 12, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(out->F, m->F, 72, hipMemcpyDeviceToHost, c->stream));

@@ -34,7 +34,7 @@ struct LoopRes {
     int32_t n_cand, n_found, n_connected, max_common, n_scored, n_passed;
 };
 
-struct LoopBufs {
+struct LoopBufs : MapFeature {
     DevBuf<uint8_t> flag;                     // [n_kf] bit 0: in S, bit 1: in M
     DevBuf<double> acc;                       // [n_kf] accumulated group score of a keyframe of M
     DevBuf<int32_t> best;                     // [n_kf] best_k
@@ -42,18 +42,16 @@ struct LoopBufs {
     DevBuf<uint8_t> connected, group;         // [n_kf], [max_cand][n_kf]
     DevBuf<int32_t> qf, tf;                   // [LP_MAX_CAND] the matcher's pair list
     DevBuf<int32_t> tab;                      // point_of [position][row] (map_launch_point_of)
-    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass;   // [pair][row] matcher outputs
+    MatchBufs match;                          // [pair][row]
     DevBuf<unsigned long long> claim;         // [pair][row] per train row: (distance << 32) | query row of the match that keeps it
     DevBuf<int32_t> cur, mpt, mrow;           // [row], [pair][row], [pair][row]
-    DevBuf<LoopRes> res; PinnedBuf<LoopRes> h_res;
+    ResBlock<LoopRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) {
-        f(flag); f(acc); f(best); f(cacc); f(connected); f(group); f(qf); f(tf); f(tab); f(midx); f(mdist); f(mpass); f(claim); f(cur); f(mpt); f(mrow); f(res);
+        f(flag); f(acc); f(best); f(cacc); f(connected); f(group); f(qf); f(tf); f(tab); match.each_scratch(f); f(claim); f(cur); f(mpt); f(mrow); f(res);
     }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(LoopBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, LoopBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 __device__ __forceinline__ unsigned long long lp_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -191,6 +189,10 @@ __global__ __launch_bounds__(LP_BLOCK) void k_loop_select(const double* __restri
     }
 }
 
+// lp_match restates map_match_point's rule (map_store.h) instead of calling it, and k_loop_claim / k_loop_gather keep their pointer tails
+// instead of a MatchView: behind the shared function the compiler merges the four refusals into one sentinel test where this form
+// leaves the lane at each of them (k_loop_claim 103 -> 119 instructions, k_loop_gather 148 -> 155; profiles/map_features_isa.txt).
+// A change to the rule is made in both places.
 // the match of query row i of pair c that counts: *j its train row, *b the candidate's map point there, *key its claim; a = cur_point[i]
 __device__ __forceinline__ bool lp_match(int c, int i, int row, int a, int ck, const int32_t* __restrict__ midx, const int32_t* __restrict__ mdist,
                                          const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab, int* j, int* b, unsigned long long* key) {
@@ -270,12 +272,10 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
     const int32_t* W = covis_weights(m);
     BowLoop sc;
     if ((rc = bow_loop_score_enqueue(m, p, W + (size_t)p * n_kf, min_w, &sc))) return rc;
-    if (!m->lp) m->lp = new LoopBufs();
-    LoopBufs& b = *m->lp;
+    LoopBufs& b = map_feature<LoopBufs>(m);
     const size_t nk = (size_t)n_kf, pair_n = (size_t)std::max(mc, 1) * row;
-    if ((rc = b.flag.reserve(c, nk)) || (rc = b.acc.reserve(c, nk)) || (rc = b.best.reserve(c, nk)) || (rc = b.cacc.reserve(c, nk)) ||
-        (rc = b.connected.reserve(c, nk)) || (rc = b.group.reserve(c, nk * std::max(mc, 1))) || (rc = b.qf.reserve(c, LP_MAX_CAND)) ||
-        (rc = b.tf.reserve(c, LP_MAX_CAND)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
+    if ((rc = mo_reserve(c, b.flag, nk, b.acc, nk, b.best, nk, b.cacc, nk, b.connected, nk, b.group, nk * std::max(mc, 1), b.qf, LP_MAX_CAND,
+                         b.tf, LP_MAX_CAND, b.res)))
         return rc;
     if (mc) HIPCHK(c, hipMemsetAsync(b.group, 0, nk * mc, c->stream));
     hipLaunchKernelGGL(k_loop_select, dim3(1), dim3(LP_BLOCK), 0, c->stream, sc.score, sc.common, W, n_kf, p, min_w, prm->n_best, mc, m->d_pos_slot, sc.empty,
@@ -283,31 +283,28 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "loop_select");
     if (need_tab) {
-        if ((rc = b.tab.reserve(c, nk * row)) || (rc = b.midx.reserve(c, pair_n * 2)) || (rc = b.mdist.reserve(c, pair_n * 2)) ||
-            (rc = b.mpass.reserve(c, pair_n)) || (rc = b.claim.reserve(c, pair_n)) || (rc = b.cur.reserve(c, (size_t)row)) ||
-            (rc = b.mpt.reserve(c, pair_n)) || (rc = b.mrow.reserve(c, pair_n)))
-            return rc;
+        if ((rc = mo_reserve(c, b.tab, nk * row, b.match, pair_n, b.claim, pair_n, b.cur, (size_t)row, b.mpt, pair_n, b.mrow, pair_n))) return rc;
         if ((rc = map_launch_point_of(m, 0, n_kf, b.tab))) return rc;
         if (match) {
             HIPCHK(c, hipMemsetAsync(b.claim, 0xff, pair_n * 8, c->stream));
             HIPCHK(c, hipMemsetAsync(b.mpt, 0xff, pair_n * 4, c->stream));
             HIPCHK(c, hipMemsetAsync(b.mrow, 0xff, pair_n * 4, c->stream));
-            if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, sc.cnt, b.qf, b.tf, 0, 0, mc, row, prm->ratio, b.midx,
-                                         b.mdist, b.mpass)))
+            if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, sc.cnt, b.qf, b.tf, 0, 0, mc, row, prm->ratio,
+                                         b.match.idx, b.match.dist, b.match.pass)))
                 return rc;
         }
         mo_stage_mark(c, "loop_match");
         if (n_p > 0) {
             const dim3 grid((unsigned)((n_p + 255) / 256), (unsigned)std::max(mc, 1));
-            hipLaunchKernelGGL(k_loop_claim, grid, dim3(256), 0, c->stream, sc.cnt, q_slot, p, row, b.midx, b.mdist, b.mpass, b.tab, b.res, b.cur, b.claim);
+            const MatchBufs& mb = b.match;
+            hipLaunchKernelGGL(k_loop_claim, grid, dim3(256), 0, c->stream, sc.cnt, q_slot, p, row, mb.idx, mb.dist, mb.pass, b.tab, b.res, b.cur, b.claim);
             if (match)
-                hipLaunchKernelGGL(k_loop_gather, grid, dim3(256), 0, c->stream, sc.cnt, q_slot, p, row, b.midx, b.mdist, b.mpass, b.tab, b.claim, b.res, b.mpt,
-                                   b.mrow);
+                hipLaunchKernelGGL(k_loop_gather, grid, dim3(256), 0, c->stream, sc.cnt, q_slot, p, row, mb.idx, mb.dist, mb.pass, b.tab, b.claim, b.res, b.mpt, b.mrow);
             HIPCHK(c, hipGetLastError());
         }
         mo_stage_mark(c, "loop_gather");
     }
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(LoopRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     if (out->connected) HIPCHK(c, hipMemcpyAsync(out->connected, b.connected, nk, hipMemcpyDeviceToHost, c->stream));
     if (out->group && mc) HIPCHK(c, hipMemcpyAsync(out->group, b.group, nk * mc, hipMemcpyDeviceToHost, c->stream));
     if (n_p > 0) {
@@ -317,7 +314,7 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
         if (out->match_row && match) HIPCHK(c, hipMemcpy2DAsync(out->match_row, w, b.mrow, (size_t)row * 4, w, (size_t)mc, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = map_sync(c, clk))) return rc;
-    const LoopRes& r = *b.h_res;
+    const LoopRes& r = b.res.host();
     out->n_cand = r.n_cand; out->n_found = r.n_found; out->n_connected = r.n_connected; out->max_common = r.max_common;
     out->n_scored = r.n_scored; out->n_passed = r.n_passed; out->min_score = r.min_score;
     for (int i = 0; i < mc; i++) {

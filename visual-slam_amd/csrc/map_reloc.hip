@@ -33,45 +33,31 @@ struct RelocGeom {
     double K[9], Kinv[9], thr2;
 };
 
-struct RelocBufs {
+struct RelocBufs : MapFeature {
     DevBuf<int32_t> tab;                      // point_of [position][row] (map_launch_point_of)
     DevBuf<int32_t> qf;                       // [n_kf] query frame of every pair: the spare slot
-    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass;   // [pair][row] matcher outputs (a pair per keyframe, or per preselected keyframe)
+    MatchBufs match;                          // [pair][row] (a pair per keyframe, or per preselected keyframe)
     DevBuf<int32_t> score;                    // [n_kf] |C_k|
     DevBuf<int32_t> cq, cp; DevBuf<uint8_t> cinl;         // [candidate][row] C_k (query, point), final inliers
     DevBuf<int32_t> qpt; DevBuf<uint8_t> qinl;            // [row] per query keypoint
-    DevBuf<RelocRes> res; PinnedBuf<RelocRes> h_res;
+    ResBlock<RelocRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
-    template <class F> void each_scratch(F f) { f(tab); f(qf); f(midx); f(mdist); f(mpass); f(score); f(cq); f(cp); f(cinl); f(qpt); f(qinl); f(res); }
+    template <class F> void each_scratch(F f) { f(tab); f(qf); match.each_scratch(f); f(score); f(cq); f(cp); f(cinl); f(qpt); f(qinl); f(res); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(RelocBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, RelocBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // the row of the matcher outputs that holds keyframe position k: k itself when every keyframe was matched (mrow NULL), else the pair the
 // preselection gave it, -1: not matched
 __device__ __forceinline__ int reloc_mrow(const int32_t* __restrict__ mrow, int k) { return mrow ? mrow[k] : k; }
 
-// the map point of query q against the keyframe at position k matched in row mr (-1: none): the ratio-test survivor's best neighbour through point_of
-__device__ __forceinline__ int reloc_point(int mr, int k, int q, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass,
-                                           const int32_t* __restrict__ tab) {
-    if (mr < 0) return -1;
-    const size_t o = (size_t)mr * row + q;
-    if (!mpass[o]) return -1;
-    const int t = midx[2 * o];
-    if (t < 0) return -1;
-    const int p = tab[(size_t)k * row + t];
-    return p == INT_MAX ? -1 : p;
-}
-
 // |C_k|, one block per keyframe position
-__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx,
-                                                     const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab, const int32_t* __restrict__ mrow, int32_t* __restrict__ score) {
+__global__ __launch_bounds__(256) void k_reloc_score(const int32_t* __restrict__ kcnt, int spare, MatchView mv, const int32_t* __restrict__ mrow,
+                                                     int32_t* __restrict__ score) {
     __shared__ int lw[4];
     const int k = blockIdx.x, mr = reloc_mrow(mrow, k);
-    const int nq = min(kcnt[spare], row);
+    const int nq = min(kcnt[spare], mv.row);
     int n = 0;
-    for (int q = threadIdx.x; q < nq; q += 256) n += reloc_point(mr, k, q, row, midx, mpass, tab) >= 0;
+    for (int q = threadIdx.x; q < nq; q += 256) n += map_match_point(mv, mr, k, q) >= 0;
     n = wave_sum_int(n);
     if ((threadIdx.x & 63) == 0) lw[threadIdx.x >> 6] = n;
     __syncthreads();
@@ -113,16 +99,16 @@ __global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ 
 }
 
 // C_k of candidate blockIdx.x in query order (block scans, no atomics)
-__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                       const int32_t* __restrict__ mrow, RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
+__global__ __launch_bounds__(1024) void k_reloc_gather(const int32_t* __restrict__ kcnt, int spare, MatchView mv, const int32_t* __restrict__ mrow,
+                                                       RelocRes* __restrict__ res, int32_t* __restrict__ cq, int32_t* __restrict__ cp) {
     __shared__ int lw[40];
     const int c = blockIdx.x, k = res->cand[c];
     if (k < 0) return;
-    const int nq = min(kcnt[spare], row), mr = reloc_mrow(mrow, k);
+    const int row = mv.row, nq = min(kcnt[spare], row), mr = reloc_mrow(mrow, k);
     int added = 0;
     for (int b = 0; b < nq; b += 1024) {
         const int q = b + threadIdx.x;
-        const int p = q < nq ? reloc_point(mr, k, q, row, midx, mpass, tab) : -1;
+        const int p = q < nq ? map_match_point(mv, mr, k, q) : -1;
         int tot;
         const int r = block_excl_scan(p >= 0 ? 1 : 0, lw, &tot);
         if (p >= 0) { cq[(size_t)c * row + added + r] = q; cp[(size_t)c * row + added + r] = p; }
@@ -243,8 +229,8 @@ __global__ __launch_bounds__(64) void k_reloc_refine(RelocGeom g, const float* _
 }
 
 // the winner (most final inliers, ties to the lower position) and its per-query-keypoint map point and inlier flag
-__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ kcnt, int spare, int row, const int32_t* __restrict__ midx, const uint8_t* __restrict__ mpass, const int32_t* __restrict__ tab,
-                                                      const int32_t* __restrict__ mrow, const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
+__global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict__ kcnt, int spare, MatchView mv, const int32_t* __restrict__ mrow,
+                                                      const int32_t* __restrict__ cq, const uint8_t* __restrict__ cinl, RelocRes* __restrict__ res,
                                                       int32_t* __restrict__ qpt, uint8_t* __restrict__ qinl) {
     __shared__ int win;
     if (threadIdx.x == 0) {
@@ -256,9 +242,9 @@ __global__ __launch_bounds__(256) void k_reloc_finish(const int32_t* __restrict_
     }
     __syncthreads();
     const int w = win, k = w >= 0 ? res->cand[w] : -1, mr = k >= 0 ? reloc_mrow(mrow, k) : -1;
-    const int nq = min(kcnt[spare], row);
+    const int row = mv.row, nq = min(kcnt[spare], row);
     for (int q = threadIdx.x; q < nq; q += 256) {
-        qpt[q] = reloc_point(mr, k, q, row, midx, mpass, tab);
+        qpt[q] = map_match_point(mv, mr, k, q);
         qinl[q] = 0;
     }
     __syncthreads();
@@ -314,27 +300,25 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     const int n_pairs = pre ? n_pre : n_kf;
     BowSel sel;
     if (pre && (rc = bow_select_enqueue(m, n, n_pre, &sel))) return rc;
-    if (!m->rl) m->rl = new RelocBufs();
-    RelocBufs& b = *m->rl;
+    RelocBufs& b = map_feature<RelocBufs>(m);
     const size_t tab_n = (size_t)n_kf * row, pair_n = (size_t)n_pairs * row, cand_n = (size_t)nc * row;
-    if ((rc = b.tab.reserve(c, tab_n)) || (rc = b.qf.reserve(c, (size_t)n_kf)) || (rc = b.midx.reserve(c, pair_n * 2)) ||
-        (rc = b.mdist.reserve(c, pair_n * 2)) || (rc = b.mpass.reserve(c, pair_n)) || (rc = b.score.reserve(c, (size_t)n_kf)) ||
-        (rc = b.cq.reserve(c, cand_n)) || (rc = b.cp.reserve(c, cand_n)) || (rc = b.cinl.reserve(c, cand_n)) ||
-        (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) || (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
+    if ((rc = mo_reserve(c, b.tab, tab_n, b.qf, (size_t)n_kf, b.match, pair_n, b.score, (size_t)n_kf, b.cq, cand_n, b.cp, cand_n, b.cinl, cand_n,
+                         b.qpt, (size_t)row, b.qinl, (size_t)row, b.res)))
         return rc;
-    b.h_res.p->n_cand = -1;  // until this call's copy-out lands: mo_dbg_map_reloc_last reports no relocalization
+    b.res.host().n_cand = -1;  // until this call's copy-out lands: mo_dbg_map_reloc_last reports no relocalization
     if (!pre) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.qf, spare, (size_t)n_kf, c->stream));
     const MapPts src = m->P[m->cur].view();
     if ((rc = map_launch_point_of(m, 0, n_kf, b.tab))) return rc;
     mo_stage_mark(c, "reloc_point_of");
     if ((rc = match_launch_pairs(c, m->kdesc, m->kdesc, (size_t)row * 32, (size_t)row * 32, pre ? sel.cnt : (const int32_t*)m->kcnt,
                                  pre ? sel.qf : (const int32_t*)b.qf, pre ? sel.tf : (const int32_t*)m->d_pos_slot, 0, 0, n_pairs, row, prm->ratio,
-                                 b.midx, b.mdist, b.mpass)))
+                                 b.match.idx, b.match.dist, b.match.pass)))
         return rc;
     mo_stage_mark(c, "reloc_match");
-    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.score);
+    const MatchView mv{b.match.idx, b.match.dist, b.match.pass, b.tab, row};
+    hipLaunchKernelGGL(k_reloc_score, dim3(n_kf), dim3(256), 0, c->stream, m->kcnt, spare, mv, sel.mrow, b.score);
     hipLaunchKernelGGL(k_reloc_rank, dim3(1), dim3(256), 0, c->stream, b.score, n_kf, nc, b.res);
-    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.res, b.cq,
+    hipLaunchKernelGGL(k_reloc_gather, dim3(nc), dim3(1024), 0, c->stream, m->kcnt, spare, mv, sel.mrow, b.res, b.cq,
                        b.cp);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_candidates");
@@ -343,15 +327,15 @@ static int reloc_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_p3p");
     hipLaunchKernelGGL(k_reloc_refine, dim3(nc), dim3(64), 0, c->stream, g, src.xyz, qk, row, prm->seed, b.cq, b.cp, b.cinl, b.res);
-    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->kcnt, spare, row, b.midx, b.mpass, b.tab, sel.mrow, b.cq, b.cinl, b.res,
+    hipLaunchKernelGGL(k_reloc_finish, dim3(1), dim3(256), 0, c->stream, m->kcnt, spare, mv, sel.mrow, b.cq, b.cinl, b.res,
                        b.qpt, b.qinl);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "reloc_refine");
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(RelocRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = map_sync(c, clk))) return rc;
-    const RelocRes& r = *b.h_res;
+    const RelocRes& r = b.res.host();
     out->n_cand = r.n_cand;
     for (int i = 0; i < r.n_cand; i++) {
         if (out->cand_pos) out->cand_pos[i] = r.cand[i];
@@ -381,8 +365,9 @@ extern "C" int mo_map_relocalize_pre(mo_map* m, const mo_frame_ref* f, const dou
 extern "C" int mo_dbg_map_reloc_last(mo_map* m, int32_t* n_cand, int32_t* cand, uint64_t* best, int32_t* ncorr, int32_t* ninl, double* pose) {
     if (!m) return MO_ERR_ARG;
     if (!n_cand || !cand || !best || !ncorr || !ninl || !pose) return mo_fail(m->c, MO_ERR_ARG, "NULL argument");
-    if (!m->rl || !m->rl->h_res.p || m->rl->h_res.p->n_cand < 0) return mo_fail(m->c, MO_ERR_ARG, "no relocalization has run on this map");
-    const RelocRes& r = *m->rl->h_res;
+    const RelocBufs* b = map_feature_if<RelocBufs>(m);
+    if (!b || !b->res.pinned.p || b->res.host().n_cand < 0) return mo_fail(m->c, MO_ERR_ARG, "no relocalization has run on this map");
+    const RelocRes& r = b->res.host();
     *n_cand = r.n_cand;
     for (int i = 0; i < RL_MAX_CAND; i++) { cand[i] = r.cand[i]; best[i] = r.best[i]; ncorr[i] = r.ncorr[i]; ninl[i] = r.ninl[i]; }
     std::memcpy(pose, r.pose, sizeof(r.pose));

@@ -2,8 +2,13 @@
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
 // of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates) and map_io.hip (PLY text).
 // Here, in this order:
-//   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's) and mo_map;
+//   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
+//   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),
+//   mo_reserve (every reservation of a call in one statement), MatchBufs (the matcher's outputs);
+//   mo_map and its registry of features, map_feature / map_feature_if / map_feature_drop: where feature scratch lives, is poisoned
+//   (map_poison walks the registry) and dies; a new feature edits nothing here;
 //   MapView / map_view: the live map as every kernel receives it (by value);
+//   MatchView / map_match_point: the matcher's outputs read through a point_of table (restated only by lp_match of map_loop.hip, which says why);
 //   map_obs: the one reader of an observation; map_each_obs / map_observes: the walks over a point's valid observations;
 //   map_point_of: the one rule of the point_of tables (k_point_of / map_launch_point_of in map_kernels.hip, k_fuse_prep);
 //   wave_sum / wave_sum_all (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
@@ -12,6 +17,8 @@
 // Private to the library.
 #pragma once
 #include <algorithm>
+#include <climits>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -35,32 +42,46 @@ struct MapPtsStore {
     MapPts view() const { return MapPts{xyz, col, id, dkf, drow, off, okf, okp, pcap, ocap}; }
 };
 
-// scratch of one feature each, made on its first call and freed with the map (map_scratch_free: `delete`, next to the struct)
-struct RelocBufs;   // mo_map_relocalize (map_reloc.hip)
-struct TrackBufs;   // mo_map_track (map_track.hip)
-struct BaBufs;      // mo_map_bundle_adjust and mo_map_add_observations (map_ba.hip)
-struct FuseBufs;    // mo_map_fuse (map_fuse.hip)
-struct GrowBufs;    // mo_map_grow (map_grow.hip)
-struct CovisBufs;   // mo_map_covisibility, mo_map_local_keyframes and mo_map_track_covisible (map_covis.hip)
-struct BowBufs;     // mo_map_set_vocabulary: the keyframe database of mo_map_query_keyframes and mo_map_relocalize_pre (bow.hip)
-struct LoopBufs;    // mo_map_loop_candidates (map_loop.hip)
-void map_scratch_free(RelocBufs* b);
-void map_scratch_free(TrackBufs* b);
-void map_scratch_free(BaBufs* b);
-void map_scratch_free(FuseBufs* b);
-void map_scratch_free(GrowBufs* b);
-void map_scratch_free(CovisBufs* b);
-void map_scratch_free(BowBufs* b);
-void map_scratch_free(LoopBufs* b);
-// mo_dbg_set_poison: the struct's each_scratch list filled (null: the feature has not run yet), each next to its struct
-int map_scratch_poison(mo_ctx* c, RelocBufs* b);
-int map_scratch_poison(mo_ctx* c, TrackBufs* b);
-int map_scratch_poison(mo_ctx* c, BaBufs* b);
-int map_scratch_poison(mo_ctx* c, FuseBufs* b);
-int map_scratch_poison(mo_ctx* c, GrowBufs* b);
-int map_scratch_poison(mo_ctx* c, CovisBufs* b);
-int map_scratch_poison(mo_ctx* c, BowBufs* b);
-int map_scratch_poison(mo_ctx* c, LoopBufs* b);
+// A feature's scratch (RelocBufs in map_reloc.hip, TrackBufs, BaBufs, FuseBufs, GrowBufs, CovisBufs, BowBufs in bow.hip, LoopBufs): a
+// struct in the feature's own file that derives from this, lists its scratch buffers in an each_scratch and implements poison as
+// mo_poison_scratch(c, *this).  The map owns it (mo_map::features): made by map_feature<T> on the feature's first call, filled by
+// map_poison while a poison byte is set, freed with the map.  Nothing outside its file names it.
+struct MapFeature {
+    virtual ~MapFeature() = default;
+    virtual int poison(mo_ctx* c) = 0;
+};
+
+// A call's result block: the device copy (the DevBuf it is: a kernel argument, an entry of the owner's each_scratch) and the pinned copy
+// the host reads.  How the device copy is initialised is the feature's business.
+template <class T> struct ResBlock : DevBuf<T> {
+    PinnedBuf<T> pinned;
+    int reserve(mo_ctx* c) { if (int rc = DevBuf<T>::reserve(c, 1)) return rc; return pinned.reserve(c, 1); }
+    // the one copy of the block, enqueued on the context stream
+    int download(mo_ctx* c) { HIPCHK(c, hipMemcpyAsync(pinned.p, this->p, sizeof(T), hipMemcpyDeviceToHost, c->stream)); return MO_OK; }
+    // valid behind map_sync
+    T& host() const { return *pinned.p; }
+};
+
+// mo_reserve(c, buf, n, buf, n, ..., block, ...): room for n elements in every DevBuf / PinnedBuf / MatchBufs and for every ResBlock
+// (which takes no count), in the order written; the first failure is returned and nothing after it is reserved
+inline int mo_reserve(mo_ctx*) { return MO_OK; }
+template <class T, class... Rest> int mo_reserve(mo_ctx* c, ResBlock<T>& b, Rest&&... rest);
+template <class B, class... Rest> int mo_reserve(mo_ctx* c, B& b, size_t n, Rest&&... rest) {
+    if (int rc = b.reserve(c, n)) return rc;
+    return mo_reserve(c, rest...);
+}
+template <class T, class... Rest> int mo_reserve(mo_ctx* c, ResBlock<T>& b, Rest&&... rest) {
+    if (int rc = b.reserve(c)) return rc;
+    return mo_reserve(c, rest...);
+}
+
+// The matcher's outputs for `rows` = pairs x stride query rows, in the layout emit_match (match_kernels.hip) defines: idx and dist
+// [pair][row][2] (best, second), pass [pair][row].  An owner's each_scratch forwards to this one.
+struct MatchBufs {
+    DevBuf<int32_t> idx, dist; DevBuf<uint8_t> pass;
+    int reserve(mo_ctx* c, size_t rows) { return mo_reserve(c, idx, rows * 2, dist, rows * 2, pass, rows); }
+    template <class F> void each_scratch(F f) { f(idx); f(dist); f(pass); }
+};
 
 struct mo_map {
     mo_ctx* c = nullptr;
@@ -90,27 +111,34 @@ struct mo_map {
     DevBuf<int32_t> ent_id;                           // id of the point of every observation entry (compacted map)
     DevBuf<int32_t> hist, hbase, first;
     // growth step
-    DevBuf<int32_t> midx, mdist; DevBuf<uint8_t> mpass, inl; DevBuf<float> gpts;
+    MatchBufs match; DevBuf<uint8_t> inl; DevBuf<float> gpts;
     DevBuf<double> F; DevBuf<int32_t> gnp;
     PinnedBuf<int32_t> h_stat;                        // [ST_NWORDS]
-    RelocBufs* rl = nullptr;
-    TrackBufs* tk = nullptr;
-    BaBufs* ba = nullptr;
-    FuseBufs* fu = nullptr;
-    GrowBufs* gr = nullptr;
-    CovisBufs* cv = nullptr;
-    BowBufs* bow = nullptr;
-    LoopBufs* lp = nullptr;
+    std::vector<std::unique_ptr<MapFeature>> features;   // in the order of their first calls (map_feature)
     // The map's own scratch: what no call reads before its own chain wrote it.  State, and so not listed: the keyframe store (kkps, kdesc,
     // kcnt, kP), d_pos_slot, img, both copies of the map store P, loff / lids, kf_red, and st, whose ST_NPTS / ST_NOBS / ST_NNEW words
     // carry the live counts from one call to the next.  A DevBuf added to this struct is named here or in that sentence.
     template <class Fn> void each_scratch(Fn f) {
         f(keep); f(kobs); f(rank); f(obase); f(part); f(ent_id); f(hist); f(hbase); f(first);
-        f(midx); f(mdist); f(mpass); f(inl); f(gpts); f(F); f(gnp);
+        match.each_scratch(f); f(inl); f(gpts); f(F); f(gnp);
     }
-    // (mo_map_destroy selects the device and drains the stream first)
-    ~mo_map() { map_scratch_free(rl); map_scratch_free(tk); map_scratch_free(ba); map_scratch_free(fu); map_scratch_free(gr); map_scratch_free(cv); map_scratch_free(bow); map_scratch_free(lp); }
 };
+
+// The feature T of a map: null before its first call (map_feature_if), made on first use (map_feature), dropped (map_feature_drop).  A
+// lookup by type in a handful of entries, once per call.
+template <class T> T* map_feature_if(const mo_map* m) {
+    for (const auto& f : m->features)
+        if (T* t = dynamic_cast<T*>(f.get())) return t;
+    return nullptr;
+}
+template <class T> T& map_feature(mo_map* m) {
+    if (T* t = map_feature_if<T>(m)) return *t;
+    m->features.emplace_back(new T());
+    return static_cast<T&>(*m->features.back());
+}
+template <class T> void map_feature_drop(mo_map* m) {
+    m->features.erase(std::remove_if(m->features.begin(), m->features.end(), [](const auto& f) { return dynamic_cast<T*>(f.get()) != nullptr; }), m->features.end());
+}
 
 // ---- the live map as the kernels receive it (by value): the live copy of the store, the uploaded position table, the keyframe counts
 struct MapView {
@@ -165,6 +193,27 @@ __device__ __forceinline__ int map_point_of(const MapView& v, int i, int lo_pos,
         return false;
     });
     return n;
+}
+
+// The matcher's outputs (MatchBufs) and a point_of table as a kernel reads them together (by value): pair `match_row` is the matching
+// of a query frame against the keyframe at position kf_pos, tab [position][row] covers that position.
+struct MatchView {
+    const int32_t* idx; const int32_t* dist; const uint8_t* pass; const int32_t* tab;
+    int row;
+};
+// The rule of relocalization and loop matching: the map point a ratio-test survivor's best neighbour belongs to, through point_of.  Query row q of
+// pair match_row (-1: the keyframe was not matched); -1: none, else the point and, if asked for, *train_row = the neighbour's row.
+// pass is read before idx, idx before tab: a row that fails the ratio test may hold anything in idx.
+__device__ __forceinline__ int map_match_point(const MatchView& v, int match_row, int kf_pos, int q, int* train_row = nullptr) {
+    if (match_row < 0) return -1;
+    const size_t o = (size_t)match_row * v.row + q;
+    if (!v.pass[o]) return -1;
+    const int t = v.idx[2 * o];
+    if (t < 0) return -1;
+    const int p = v.tab[(size_t)kf_pos * v.row + t];
+    if (p == INT_MAX) return -1;
+    if (train_row) *train_row = t;
+    return p;
 }
 
 // ---- fixed-order f64 wave sum: lane 0's shuffle tree, the same on every run; lane 0 holds the sum, wave_sum_all gives it to every lane

@@ -50,7 +50,7 @@ struct TrkMatch {                         // one match in keypoint order (32 B):
     int32_t octave, q, p;
 };
 
-struct TrackBufs {
+struct TrackBufs : MapFeature {
     DevBuf<uint8_t> rep;                  // [point][32] representative descriptors
     DevBuf<int32_t> oct;                  // [point] ref_octave (TK_NOT_LOCAL: not in the local map)
     DevBuf<int32_t> cell;                 // [TK_CELLS + 1] first sorted entry of every cell
@@ -59,13 +59,11 @@ struct TrackBufs {
     DevBuf<TrkMatch> match;               // [row]
     DevBuf<uint8_t> minl;                 // [row] inlier flag of every match
     DevBuf<int32_t> qpt, qdist; DevBuf<uint8_t> qinl;   // [row] per frame keypoint
-    DevBuf<TrackRes> res; PinnedBuf<TrackRes> h_res;
+    ResBlock<TrackRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) { f(rep); f(oct); f(cell); f(sorted); f(key); f(match); f(minl); f(qpt); f(qdist); f(qinl); f(res); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-void map_scratch_free(TrackBufs* b) { delete b; }
-int map_scratch_poison(mo_ctx* c, TrackBufs* b) { return b ? mo_poison_scratch(c, *b) : MO_OK; }
 
 // a pass's kernels run when the call has not ended and, for the second attempt, when the first asked for it
 __device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
@@ -407,13 +405,10 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if ((rc = map_stage_frame(m, f, true, &out->from_token, defaults, &n, &fk, &fdesc))) return rc;
     if (!fk) return lprm ? mo_map_local_keyframes(m, lprm, lout) : MO_OK;   // (nothing to search: not tracked, not an error)
     const int n_kf = (int)m->pos_slot.size(), row = m->row;
-    if (!m->tk) m->tk = new TrackBufs();
-    TrackBufs& b = *m->tk;
+    TrackBufs& b = map_feature<TrackBufs>(m);
     const size_t np = (size_t)m->n_pts;
-    if ((rc = b.rep.reserve(c, np * 32)) || (rc = b.oct.reserve(c, np)) || (rc = b.cell.reserve(c, TK_CELLS + 1)) || (rc = b.sorted.reserve(c, (size_t)row)) ||
-        (rc = b.key.reserve(c, (size_t)row)) || (rc = b.match.reserve(c, (size_t)row)) || (rc = b.minl.reserve(c, (size_t)row)) ||
-        (rc = b.qpt.reserve(c, (size_t)row)) || (rc = b.qdist.reserve(c, (size_t)row)) || (rc = b.qinl.reserve(c, (size_t)row)) ||
-        (rc = b.res.reserve(c, 1)) || (rc = b.h_res.reserve(c, 1)))
+    if ((rc = mo_reserve(c, b.rep, np * 32, b.oct, np, b.cell, TK_CELLS + 1, b.sorted, (size_t)row, b.key, (size_t)row, b.match, (size_t)row,
+                         b.minl, (size_t)row, b.qpt, (size_t)row, b.qdist, (size_t)row, b.qinl, (size_t)row, b.res)))
         return rc;
     TrackPrm p;
     for (int i = 0; i < 9; i++) p.K[i] = K[i];
@@ -444,14 +439,14 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "track_refine");
     }
-    HIPCHK(c, hipMemcpyAsync(b.h_res, b.res, sizeof(TrackRes), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = b.res.download(c))) return rc;
     if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->dist) HIPCHK(c, hipMemcpyAsync(out->dist, b.qdist, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out->inlier) HIPCHK(c, hipMemcpyAsync(out->inlier, b.qinl, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (lprm && (rc = covis_copy_enqueue(m, lout))) return rc;
     if ((rc = map_sync(c, clk))) return rc;
     if (lprm) covis_finish(m, lout);
-    const TrackRes& r = *b.h_res;
+    const TrackRes& r = b.res.host();
     for (int i = 0; i < 12; i++) out->pose[i] = r.pose[i];
     for (int k = 0; k < TK_MAX_PASS; k++) {
         for (int i = 0; i < 12; i++) out->pass_pose[k][i] = r.pass_pose[k][i];
