@@ -912,6 +912,67 @@ typedef struct {
 } mo_map_loop_out;
 int mo_map_loop_candidates(mo_map*, const mo_map_loop_params*, mo_map_loop_out*);
 
+/* ---- Loop alignment (map_sim3.hip, sim3.h) ------------------------------------------------------------------------------------------------
+ * "Is the candidate the same place, and at which relative scale": ORB-SLAM2's ComputeSim3 on the correspondences
+ * mo_map_loop_candidates returned - a 3-point RANSAC over Horn's closed form, then Gauss-Newton on sim(3).  Reads the map, never changes
+ * it.  The consistency bookkeeping of a loop detector sits between the two calls on the host, so the match lists come back in as host
+ * arrays; any list of the same shape may be given.  tests/native/sim3_replay.cpp restates the chain from the pairs on over the same
+ * sim3.h; integers are equal, models agree to the rounding of exp / sin / cos.
+ * mo_map_loop_sim3: p = kf_pos, the asking keyframe; poses [n_kf][12] are the keyframes' [R | t] (mo_map_bundle_adjust's convention).
+ *   model         X1 = s R X2 + t takes a point of the candidate's camera frame (2) into p's camera frame (1).
+ *   pairs         of candidate c, in row order: the rows i of p with a = cur_point[i], b = match_point[c][i], j = match_row[c][i] all >= 0,
+ *                 a and b map points that exist, j a row of the candidate.  Anything else is dropped.  n_corr[c] counts the pairs.
+ *                 X1 = R1 xyz[a] + t1, X2 = R2 xyz[b] + t2 (f64, each row summed left to right); keypoints (p, i) and (cand[c], j) with
+ *                 information = 1 / scale_factor^(2 octave) (repeated products from 1.0, negative octaves as 0: mo_map_track's).
+ *   hypotheses    h = 0 .. n_hyp - 1 per candidate with at least 3 pairs: three distinct pairs drawn by the relocalization's sampler on
+ *                 the stream (seed, cand[c]); Horn's closed form (symmetric 4x4 by cyclic Jacobi).  No model: a non-finite value, a
+ *                 denominator or scale not > 0, or a largest eigenvalue not separated from the second (collinear or coincident points).
+ *   inlier        a pair is an inlier when X2 taken into frame 1 has z > 0 and information1 * squared pixel error < chi2 against p's
+ *                 keypoint, and X1 taken into frame 2 has z > 0 and information2 * squared pixel error < chi2 against the candidate's
+ *                 (strict).  ORB-SLAM2 compares with the projections of the 3D points; here the keypoints are the measurement.
+ *   best          per candidate the hypothesis with the most inliers, ties to the lower h: key (inliers << 32) | ~h, 0: no model.
+ *   refinement    the best hypothesis re-solved, its inliers selected; then twice, while at least 3 inliers remain: at most 10
+ *                 Gauss-Newton steps on (translation, rotation, log-scale) over both reprojection residuals of the inliers (points
+ *                 fixed, information weights, Huber width sqrt(chi2); a step below 1e-12 or a normal matrix that is not positive
+ *                 definite ends the round), then the inliers are selected again.
+ *   outputs       per candidate scale, R, t (NaN without a model), n_corr, n_inliers, inlier [rows of p] (1 at the rows of final
+ *                 inliers).  win = the candidate with a model and the most final inliers, ties to the earlier one in the given order,
+ *                 -1: none; win_inliers its count; ok = win_inliers >= min_inliers.
+ *   chain         uploads, gather (one workgroup per candidate, block scans), hypotheses (one wave each, all candidates in one launch),
+ *                 refinement (one wave per candidate), winner, copy-out; one synchronisation.  Stage marks sim3_gather, sim3_hyp,
+ *                 sim3_refine, sim3_finish.
+ *   errors        MO_ERR_ARG for NULL params, out, K or poses, non-finite K or poses, kf_pos or a cand entry outside the map, n_cand
+ *                 outside 0 .. 16, n_hyp outside 1 .. 2^20, chi2 not finite or < 0, scale_factor not finite or not > 0, and for NULL
+ *                 cand / cur_point / match_point / match_row when n_cand > 0.  n_cand = 0 or a map without keyframes: MO_OK, win = -1,
+ *                 ok = 0.
+ * Integer atomics only (maxima commute): two calls on equal inputs give the same bytes. */
+typedef struct {
+    int32_t kf_pos;              /* the asking keyframe, by position */
+    int32_t n_cand;              /* 0 .. 16 */
+    const int32_t* cand;         /* [n_cand] candidate keyframe positions */
+    const int32_t* cur_point;    /* [rows of p] mo_map_loop_candidates' cur_point */
+    const int32_t* match_point;  /* [n_cand][rows of p] */
+    const int32_t* match_row;    /* [n_cand][rows of p] */
+    int32_t n_hyp;               /* 1 .. 2^20 (300) */
+    int32_t min_inliers;         /* ok needs this many final inliers (20) */
+    uint64_t seed;
+    double chi2;                 /* 9.210 */
+    double scale_factor;         /* of the information (1.2) */
+} mo_map_sim3_params;
+typedef struct {
+    /* caller-allocated; any may be NULL */
+    double*  scale;       /* [n_cand] */
+    double*  R;           /* [n_cand][9] */
+    double*  t;           /* [n_cand][3] */
+    int32_t* n_corr;      /* [n_cand] */
+    int32_t* n_inliers;   /* [n_cand] */
+    uint8_t* inlier;      /* [n_cand][rows of p] */
+    /* filled by the call */
+    int32_t win, ok;      /* win: index into cand, -1: none */
+    int32_t win_inliers;  /* n_inliers of the winner (the array above holds every candidate's) */
+} mo_map_sim3_out;
+int mo_map_loop_sim3(mo_map*, const double K[9], const double* poses, const mo_map_sim3_params*, mo_map_sim3_out*);
+
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls
  * neither clears nor pollutes this status.  Synchronises the context stream, copies the flag word to flags[0] (flags may be NULL; [1..3] reserved, 0)
@@ -969,6 +1030,13 @@ int mo_dbg_poison_filled(mo_ctx*, int64_t* n_buffers, int64_t* n_bytes);
    relocalization has finished its chain on the map (a call that found nothing to match - no keyframe, no keypoint - runs none). */
 int mo_dbg_map_reloc_last(mo_map*, int32_t* n_cand, int32_t* cand /* [64] */, uint64_t* best /* [64] */, int32_t* ncorr /* [64] */,
                           int32_t* ninl /* [64] */, double* pose /* [64][12] */);
+/* what the last mo_map_loop_sim3 on this map downloaded, per candidate in the given order (arrays of 16; entries past n_cand: cand -1, the
+   rest 0 and a NaN model): best = the winning hypothesis' key (inliers << 32) | ~h, 0: no model; ncorr = the pairs; ninl = final
+   inliers; model[c][13] = s, R [9], t [3] (NaN without a key); *win as the call returned it.  Read from the call's pinned result block:
+   no launch, no copy from the device, no synchronisation.  MO_ERR_ARG when no alignment has finished its chain on the map (a call
+   with n_cand = 0 or on a map without keyframes runs none). */
+int mo_dbg_map_sim3_last(mo_map*, int32_t* n_cand, int32_t* win, int32_t* cand /* [16] */, uint64_t* best /* [16] */, int32_t* ncorr /* [16] */,
+                         int32_t* ninl /* [16] */, double* model /* [16][13] */);
 int mo_dbg_retain_best(mo_ctx*, const float* resp, int n, int n_points, int select_order, int32_t* order, int* n_out);
 
 #ifdef __cplusplus

@@ -162,6 +162,17 @@ class MapLoopOut(C.Structure):
                 ("n_scored", C.c_int32), ("n_passed", C.c_int32), ("min_score", C.c_double)]
 
 
+class MapSim3Params(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("n_cand", C.c_int32), ("cand", C.c_void_p), ("cur_point", C.c_void_p), ("match_point", C.c_void_p),
+                ("match_row", C.c_void_p), ("n_hyp", C.c_int32), ("min_inliers", C.c_int32), ("seed", C.c_uint64), ("chi2", C.c_double),
+                ("scale_factor", C.c_double)]
+
+
+class MapSim3Out(C.Structure):
+    _fields_ = [("scale", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p), ("n_corr", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("inlier", C.c_void_p), ("win", C.c_int32), ("ok", C.c_int32), ("win_inliers", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -261,6 +272,8 @@ SIGNATURES = {
     "mo_map_query_keyframes": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
+    "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_dbg_map_sim3_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

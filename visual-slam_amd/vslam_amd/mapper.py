@@ -682,12 +682,76 @@ class LocalMapper:
                 "max_common": int(out.max_common), "n_scored": int(out.n_scored), "n_passed": int(out.n_passed), "n_found": int(out.n_found),
                 "n_connected": int(out.n_connected), "kf_pos": p}
 
-    def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3):
+    def compute_sim3(self, info_or_candidates, n_hyp=300, seed=0, chi2=9.210, scale_factor=1.2, min_inliers=20, kf_position=None):
+        """The similarity that aligns the asking keyframe with its loop candidates (ORB-SLAM2's ComputeSim3; mo_map_loop_sim3 in
+        include/vslam_amd.h states the rules): per candidate a 3-point RANSAC over Horn's closed form on the matched map points, scored
+        by reprojection into both keyframes, then Gauss-Newton on sim(3).  The map is not changed.  Takes loop_candidates()'s dict, or a
+        list of its candidate dicts such as [info["accepted"]] (then the asking keyframe is kf_position, by default the last).  Poses
+        come from kf["pose"], K from camera_matrix.
+        Returns (ok, info): ok when the winner - the candidate with the most final inliers - has at least min_inliers.  info holds
+        `candidates`, a list of dicts with `pos`, `scale`, `R` (3, 3), `t` (3), `n_corr`, `n_inliers` and `inlier` (bool per keypoint row
+        of the asking keyframe); `win` (index into that list, -1: none), `n_inliers` of the winner, `kf_pos`, and `world`: the 4x4
+        similarity in the map frame that takes the candidate's side onto the asking side, T1^-1 S12 T2 (None without a winner).
+        X1 = scale R X2 + t takes a point of the candidate's camera frame into the asking keyframe's."""
+        n_kf = len(self.keyframes)
+        if isinstance(info_or_candidates, dict):
+            cands = list(info_or_candidates["candidates"])
+            p = info_or_candidates.get("kf_pos") if kf_position is None else kf_position
+            cur = info_or_candidates.get("cur_point")
+        else:
+            cands = list(info_or_candidates)
+            p, cur = kf_position, None
+        p = n_kf - 1 if p is None or int(p) < 0 else int(p)
+        nc = len(cands)
+        n_p = self.keyframes[p]._rows if 0 <= p < n_kf else 0
+        if cur is None and nc:
+            cur = cands[0]["cur_point"]
+        w = max(n_p, 1)   # (the library reads the lists packed [n_cand][rows of p]: the arrays' shape whenever they hold anything)
+        cur_a = np.full(w, -1, np.int32)
+        mpt, mrow = np.full((max(nc, 1), w), -1, np.int32), np.full((max(nc, 1), w), -1, np.int32)
+        if nc and n_p:
+            cur_a[:n_p] = np.asarray(cur, np.int32).reshape(-1)[:n_p]
+            for i, cd in enumerate(cands):
+                mpt[i, :n_p] = np.asarray(cd["match_point"], np.int32).reshape(-1)[:n_p]
+                mrow[i, :n_p] = np.asarray(cd["match_row"], np.int32).reshape(-1)[:n_p]
+        pos = np.array([int(cd["pos"]) for cd in cands] or [0], np.int32)
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        m1 = max(nc, 1)
+        scale, R, t = np.full(m1, np.nan), np.full((m1, 9), np.nan), np.full((m1, 3), np.nan)
+        n_corr, n_inl = np.zeros(m1, np.int32), np.zeros(m1, np.int32)
+        inl = np.zeros((m1, w), np.uint8)
+        prm = V.MapSim3Params(p, nc, pos.ctypes.data, cur_a.ctypes.data, mpt.ctypes.data, mrow.ctypes.data, int(n_hyp), int(min_inliers),
+                              int(seed), float(chi2), float(scale_factor))
+        out = V.MapSim3Out(scale.ctypes.data, R.ctypes.data, t.ctypes.data, n_corr.ctypes.data, n_inl.ctypes.data, inl.ctypes.data)
+        self._check(self.lib.mo_map_loop_sim3(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        inl = inl[:nc, :n_p].astype(bool)
+        res = [{"pos": int(pos[i]), "scale": float(scale[i]), "R": R[i].reshape(3, 3).copy(), "t": t[i].copy(), "n_corr": int(n_corr[i]),
+                "n_inliers": int(n_inl[i]), "inlier": inl[i]} for i in range(nc)]
+        win = int(out.win)
+        world = None
+        if win >= 0:
+            S = np.eye(4)
+            S[:3, :3] = res[win]["scale"] * res[win]["R"]
+            S[:3, 3] = res[win]["t"]
+            T1, T2 = np.eye(4), np.eye(4)
+            T1[:3, :] = poses[p].reshape(3, 4)
+            T2[:3, :] = poses[res[win]["pos"]].reshape(3, 4)
+            world = np.linalg.inv(T1) @ S @ T2
+        return bool(out.ok), {"candidates": res, "win": win, "n_inliers": int(out.win_inliers), "kf_pos": p, "world": world}
+
+    def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3, sim3=False,
+                    **sim3_kw):
         """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
         (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
         the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
         n_match >= min_matches; info is loop_candidates' dict, each candidate also with `serial`, `consistency`, `consistent` and
-        `enough_matches`, and `accepted`: the first candidate in order with both flags (None: no loop), with its correspondence arrays."""
+        `enough_matches`, and `accepted`: the first candidate in order with both flags (None: no loop), with its correspondence arrays.
+        sim3=True: such a candidate is accepted only when compute_sim3 on it (keyword arguments in sim3_kw) is ok; `accepted` then also
+        holds `sim3`: that candidate's alignment (scale, R, t, n_corr, n_inliers, inlier) with `world`, and every candidate that was
+        tried holds `sim3_ok`."""
         from vslam_amd.loop import LoopConsistency
         if self._loop_consistency is None or self._loop_consistency.threshold != int(consistency):
             self._loop_consistency = LoopConsistency(consistency)
@@ -700,7 +764,19 @@ class LocalMapper:
             c["consistency"] = n
             c["consistent"] = c["serial"] in reported
             c["enough_matches"] = c["n_match"] >= int(min_matches)
-        info["accepted"] = next((c for c in cands if c["consistent"] and c["enough_matches"]), None)
+        if not sim3:
+            info["accepted"] = next((c for c in cands if c["consistent"] and c["enough_matches"]), None)
+            return info["accepted"] is not None, info
+        info["accepted"] = None
+        for c in cands:
+            if not (c["consistent"] and c["enough_matches"]):
+                continue
+            ok, al = self.compute_sim3([c], kf_position=info["kf_pos"], **sim3_kw)
+            c["sim3_ok"] = ok
+            if ok:
+                c["sim3"] = dict(al["candidates"][0], world=al["world"])
+                info["accepted"] = c
+                break
         return info["accepted"] is not None, info
 
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
