@@ -973,6 +973,99 @@ typedef struct {
 } mo_map_sim3_out;
 int mo_map_loop_sim3(mo_map*, const double K[9], const double* poses, const mo_map_sim3_params*, mo_map_sim3_out*);
 
+/* ---- Loop confirmation (map_confirm.hip) ----------------------------------------------------------------------------------------------------
+ * "Which map points of the loop side does each keypoint of the asking keyframe correspond to": the second half of ORB-SLAM2's
+ * ComputeSim3 - SearchBySim3 guided by the similarities mo_map_loop_sim3 found, OptimizeSim3 on the larger set, SearchByProjection of
+ * the loop keyframe's neighbourhood - and its acceptance rule (40 matches).  Reads the map, never changes it.  tests/confirm_restatement.py
+ * restates every rule but the refit in numpy, tests/native/confirm_replay.cpp the refit over the same sim3.h; integers are equal, models
+ * agree to the rounding of exp / sin / cos.
+ * mo_map_loop_confirm: p = kf_pos; K, poses, cand, cur_point, match_point, match_row as for mo_map_loop_sim3; scale / R / t its models
+ * (X1 = s R X2 + t), inlier its flags (NULL: every listed row counts as flagged), group mo_map_loop_candidates' (NULL: the candidate alone).
+ *   take part     a candidate whose model has a non-finite entry or a scale not > 0 takes no part: n_pairs = n_guided = n_inliers = 0, its
+ *                 model out is NaN, fwd / bwd -1.  Not an error.
+ *   representatives  L = p, every candidate, every keyframe of every group.  Every point with a valid observation in L has
+ *                 mo_map_track's representative descriptor rep and ref_octave (over all its valid observations); other points take part
+ *                 in nothing below.
+ *   seeds         of candidate c: the rows i of p that mo_map_loop_sim3 would pair (a = cur_point[i], b = match_point[c][i] points that
+ *                 exist, j = match_row[c][i] a row of the candidate) with inlier[c][i] != 0.  When several such rows name one j, the
+ *                 lowest i is the seed; the others are no seeds.  Row i of p and row j of c of a seed are taken.
+ *   guided search per candidate, both ways.  1 -> 2: every row i of p that is not taken with a = cur_point[i] a point that exists and
+ *                 has a representative: X1 = R1 xyz[a] + t1 (f64, each row summed left to right), Y = S21 X1 (S21 = the inverse as
+ *                 mo_map_loop_sim3 forms it, Y[d] = s21 * (row d of R21 . X1) + t21[d]), pixel = K Y (rows summed left to right, two
+ *                 divisions); a source when the third row is > 0 and the pixel lies in [0, w) x [0, h).  Among the candidate's rows that are not taken,
+ *                 with |dx| < r and |dy| < r, r = radius_guided * scale_factor^ref_octave[a] (repeated products), and octave within 1 of
+ *                 ref_octave[a]: the lowest Hamming distance to rep[a], ties to the lower row, accepted when <= max_dist (no ratio
+ *                 test).  fwd[c][i] = that row, else -1.  2 -> 1: every row j of c that is not taken with b = point_of(c, j) >= 0 having
+ *                 a representative: X2 = R2 xyz[b] + t2, Y = S12 X2, the same search over p's rows that are not taken, with rep[b];
+ *                 bwd[c][j] = the row of p, else -1.  A guided match is (i, j) with fwd[c][i] = j, bwd[c][j] = i and a != b.
+ *                 Deviation from ORB-SLAM2: the octave is the representative observation's with a +-1 gate (mo_map_track, mo_map_fuse),
+ *                 not a level predicted from the distance.
+ *   refit         pairs of c = seeds and guided matches in row order of p, packed as mo_map_loop_sim3's pairs (b of a guided match is
+ *                 point_of(c, j)); n_pairs, n_guided count them.  From the given model: mo_map_loop_sim3's inlier selection, then its
+ *                 refinement rounds unchanged (twice, while at least 3 inliers remain: at most 10 Gauss-Newton steps, re-selection).
+ *                 n_inliers = the final count, pair_inlier = 1 at the rows of final inliers.  Fewer than 3 pairs: the model out is the
+ *                 model in, n_inliers = 0.
+ *   winner        the candidate that takes part with n_inliers >= min_inliers and the most, ties to the earlier in the given order; -1:
+ *                 none.  For its final inlier pairs loop_point[i] = b, source[i] = 1 (seed) or 2 (guided).
+ *   projection    winner only.  Loop points: the points with a valid observation at a keyframe of group[win] (n_loop_points).  One is
+ *                 skipped when it is the b of a final inlier pair or has a valid observation at p.  The others: X2 = R2 xyz[x] + t2 with
+ *                 the winner's pose, Y = S12 X2 with the refined model, projected as above (n_proj_cand counts those in the image).
+ *                 Over p's rows without a loop_point, |dx|, |dy| < radius_proj * scale_factor^ref_octave[x], octave within 1: the lowest
+ *                 distance to rep[x], ties to the lower row, accepted when <= max_dist.  Per row the lowest (distance, x) wins, one
+ *                 round, losers are not searched again: loop_point[i] = x, source[i] = 3 (n_proj counts them).  Deviation: ORB-SLAM2
+ *                 hands out rows in list order; here the better match wins and the result does not depend on order.
+ *   outputs       n_total = rows with a loop_point; ok = win >= 0 and n_total >= min_matches.  bwd is [n_cand][R2], R2 = the largest row
+ *                 count among the candidates (at least 1).
+ *   chain         uploads, point_of, representatives, keypoint grids (p and the candidates), seeds, guided search (one lane per source
+ *                 row, grid.y = candidate x direction), pairs (one workgroup per candidate, block scans), refit (one wave per candidate),
+ *                 winner, projection (one lane per map point), claims, copy-out; one synchronisation.  Stage marks confirm_prep,
+ *                 confirm_seed, confirm_guided, confirm_pairs, confirm_refit, confirm_win, confirm_proj, confirm_claim.
+ *   errors        as mo_map_loop_sim3 for the arguments they share; also MO_ERR_ARG for w or h < 1, radius_guided / radius_proj /
+ *                 scale_factor not finite or not > 0, chi2 not finite or < 0, max_dist outside 0 .. 256, min_inliers or min_matches < 0,
+ *                 NULL scale / R / t with n_cand > 0.  n_cand = 0 or a map without keyframes: MO_OK, win = -1, ok = 0, every count 0.  An
+ *                 asking keyframe without rows or a map without points: MO_OK, nothing is searched, a model comes back as given.
+ * Integer atomics only (minima, counts): two calls on equal inputs give the same bytes. */
+typedef struct {
+    int32_t kf_pos;              /* the asking keyframe, by position */
+    int32_t n_cand;              /* 0 .. 16 */
+    const int32_t* cand;         /* [n_cand] candidate keyframe positions */
+    const int32_t* cur_point;    /* [rows of p] */
+    const int32_t* match_point;  /* [n_cand][rows of p] */
+    const int32_t* match_row;    /* [n_cand][rows of p] */
+    const uint8_t* inlier;       /* [n_cand][rows of p] mo_map_loop_sim3's flags; NULL: all */
+    const double*  scale;        /* [n_cand] mo_map_loop_sim3's models */
+    const double*  R;            /* [n_cand][9] */
+    const double*  t;            /* [n_cand][3] */
+    const uint8_t* group;        /* [n_cand][n_kf] mo_map_loop_candidates' group; NULL: the candidate alone */
+    int32_t w, h;                /* image size */
+    int32_t max_dist;            /* 0 .. 256 (50) */
+    int32_t min_inliers;         /* the winner needs this many final inliers (20) */
+    int32_t min_matches;         /* ok needs this many loop points (40) */
+    double radius_guided;        /* 7.5 */
+    double radius_proj;          /* 10.0 */
+    double chi2;                 /* 9.210 */
+    double scale_factor;         /* 1.2 */
+} mo_map_confirm_params;
+typedef struct {
+    /* caller-allocated; any may be NULL */
+    double*  scale;        /* [n_cand] refined */
+    double*  R;            /* [n_cand][9] */
+    double*  t;            /* [n_cand][3] */
+    int32_t* n_pairs;      /* [n_cand] */
+    int32_t* n_guided;     /* [n_cand] */
+    int32_t* n_inliers;    /* [n_cand] */
+    uint8_t* pair_inlier;  /* [n_cand][rows of p] */
+    int32_t* fwd;          /* [n_cand][rows of p] */
+    int32_t* bwd;          /* [n_cand][R2] */
+    int32_t* loop_point;   /* [rows of p] -1: none */
+    uint8_t* source;       /* [rows of p] 0 none, 1 seed, 2 guided, 3 projection */
+    /* filled by the call */
+    int32_t win, ok;       /* win: index into cand, -1: none */
+    int32_t win_inliers;
+    int32_t n_loop_points, n_proj_cand, n_proj, n_total;
+} mo_map_confirm_out;
+int mo_map_loop_confirm(mo_map*, const double K[9], const double* poses, const mo_map_confirm_params*, mo_map_confirm_out*);
+
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls
  * neither clears nor pollutes this status.  Synchronises the context stream, copies the flag word to flags[0] (flags may be NULL; [1..3] reserved, 0)

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -129,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--loop-sim3", action="store_true", help="with --detect-loops: a loop is found only when the candidate also aligns with the "
                     "keyframe by a similarity (LocalMapper.detect_loop(sim3=True): 3-point RANSAC and refinement on the matched map points); "
                     "the line of a found loop then carries the relative scale and the inlier count")
+    ap.add_argument("--loop-confirm", action="store_true", help="with --detect-loops (switches --loop-sim3 on): an aligned candidate is accepted only "
+                    "when the guided search, the refit and the projection of its neighbourhood (LocalMapper.detect_loop(sim3=True, confirm=True)) "
+                    "give 40 loop points; the line of a found loop then carries their number and the split by source")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
@@ -165,6 +168,9 @@ def main(argv=None):
         ap.error("--vocabulary needs --map and --relocalize or --detect-loops")
     if args.detect_loops and not args.vocabulary:
         ap.error("--detect-loops needs --map and --vocabulary")
+    if args.loop_confirm and not args.detect_loops:
+        ap.error("--loop-confirm needs --detect-loops")
+    args.loop_sim3 = args.loop_sim3 or args.loop_confirm
     if args.loop_sim3 and not args.detect_loops:
         ap.error("--loop-sim3 needs --detect-loops")
     if args.reloc_preselect and not args.vocabulary:
@@ -213,7 +219,7 @@ def main(argv=None):
         ensure_vocabulary(idx)
         if mapper.vocabulary is None:
             return
-        found, info = mapper.detect_loop(sim3=args.loop_sim3)
+        found, info = mapper.detect_loop(sim3=args.loop_sim3, confirm=args.loop_confirm)
         n_loop[0] += 1
         if info["candidates"]:
             print("frame %d: keyframe %d loop candidates %s" % (idx, info["kf_pos"], ", ".join(
@@ -222,9 +228,14 @@ def main(argv=None):
         if found:
             n_loop[1] += 1
             acc = info["accepted"]
-            print("frame %d: loop found: keyframe %d closes with keyframe %d, %d map-point correspondences%s"
+            confirmed = ""
+            if args.loop_confirm:
+                cf = acc["confirm"]
+                by = [int((cf["source"] == k).sum()) for k in (1, 2, 3)]
+                confirmed = "; confirmed by %d loop points (%d seeds, %d guided, %d projected)" % (cf["n_total"], by[0], by[1], by[2])
+            print("frame %d: loop found: keyframe %d closes with keyframe %d, %d map-point correspondences%s%s"
                   % (idx, info["kf_pos"], acc["pos"], acc["n_match"],
-                     ", relative scale %.4f with %d inliers" % (acc["sim3"]["scale"], acc["sim3"]["n_inliers"]) if args.loop_sim3 else ""))
+                     ", relative scale %.4f with %d inliers" % (acc["sim3"]["scale"], acc["sim3"]["n_inliers"]) if args.loop_sim3 else "", confirmed))
 
     def track_pose(R, t, frame, kps, desc, idx):
         """Tracker._update_pose (tracker.py:268-279) and the keyframe every N frames (tracker.py:114-118, 290)"""

@@ -173,6 +173,21 @@ class MapSim3Out(C.Structure):
                 ("inlier", C.c_void_p), ("win", C.c_int32), ("ok", C.c_int32), ("win_inliers", C.c_int32)]
 
 
+class MapConfirmParams(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("n_cand", C.c_int32), ("cand", C.c_void_p), ("cur_point", C.c_void_p), ("match_point", C.c_void_p),
+                ("match_row", C.c_void_p), ("inlier", C.c_void_p), ("scale", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p),
+                ("group", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("max_dist", C.c_int32), ("min_inliers", C.c_int32),
+                ("min_matches", C.c_int32), ("radius_guided", C.c_double), ("radius_proj", C.c_double), ("chi2", C.c_double),
+                ("scale_factor", C.c_double)]
+
+
+class MapConfirmOut(C.Structure):
+    _fields_ = [("scale", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p), ("n_pairs", C.c_void_p), ("n_guided", C.c_void_p),
+                ("n_inliers", C.c_void_p), ("pair_inlier", C.c_void_p), ("fwd", C.c_void_p), ("bwd", C.c_void_p), ("loop_point", C.c_void_p),
+                ("source", C.c_void_p), ("win", C.c_int32), ("ok", C.c_int32), ("win_inliers", C.c_int32), ("n_loop_points", C.c_int32),
+                ("n_proj_cand", C.c_int32), ("n_proj", C.c_int32), ("n_total", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -273,6 +288,7 @@ SIGNATURES = {
     "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
     "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_map_sim3_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

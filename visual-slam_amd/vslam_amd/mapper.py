@@ -742,8 +742,104 @@ class LocalMapper:
             world = np.linalg.inv(T1) @ S @ T2
         return bool(out.ok), {"candidates": res, "win": win, "n_inliers": int(out.win_inliers), "kf_pos": p, "world": world}
 
+    def confirm_loop(self, candidates, sim3, group=None, kf_position=None, image_size=None, radius_guided=7.5, radius_proj=10.0, max_dist=50,
+                     chi2=9.210, scale_factor=1.2, min_inliers=20, min_matches=40):
+        """Confirms a loop whose candidates compute_sim3 aligned (the second half of ORB-SLAM2's ComputeSim3; mo_map_loop_confirm in
+        include/vslam_amd.h states the rules): both keyframes are searched again guided by the similarity, the similarity is refitted on
+        the seeds (the alignment's inliers) and the guided matches, and the points the winner's group observes are projected into the
+        asking keyframe.  The map is not changed.  `candidates` are loop_candidates' candidate dicts (or its whole dict), `sim3` is
+        compute_sim3's info or its list of per-candidate dicts, in the same order.  `group`: per candidate the keyframe positions whose
+        points are projected; by default each candidate dict's `group` when it has one, else the candidate alone.  The asking keyframe is
+        kf_position, by default sim3's `kf_pos`, else the last.  image_size (w, h) defaults to twice the principal point of K, rounded up.
+        Returns (ok, info): ok when a candidate with at least min_inliers final inliers won and n_total >= min_matches.  info holds
+        `candidates`, a list of dicts with `pos`, the refined `scale`, `R`, `t`, `n_pairs`, `n_guided`, `n_inliers`, `inlier` (bool per
+        row of the asking keyframe), `fwd` (per row of the asking keyframe the candidate row the guided search found, -1) and `bwd` (per
+        candidate row the asking row, -1); `win`, `loop_point` (per row of the asking keyframe the loop-side map point, -1: none), `source`
+        (0 none, 1 seed, 2 guided, 3 projection), `n_total`, `n_proj`, `n_proj_cand`, `n_loop_points`, `n_inliers` of the winner, `kf_pos`,
+        and `world` as in compute_sim3, from the refined model."""
+        n_kf = len(self.keyframes)
+        if isinstance(candidates, dict):
+            cands = list(candidates["candidates"])
+            cur = candidates.get("cur_point")
+        else:
+            cands, cur = list(candidates), None
+        p = kf_position
+        if isinstance(sim3, dict):
+            models = list(sim3["candidates"])
+            p = sim3.get("kf_pos") if p is None else p
+        else:
+            models = list(sim3)
+        if len(models) != len(cands):
+            raise ValueError("confirm_loop needs one alignment per candidate")
+        p = n_kf - 1 if p is None or int(p) < 0 else int(p)
+        nc = len(cands)
+        n_p = self.keyframes[p]._rows if 0 <= p < n_kf else 0
+        if cur is None and nc:
+            cur = cands[0]["cur_point"]
+        w = max(n_p, 1)
+        m1 = max(nc, 1)
+        cur_a = np.full(w, -1, np.int32)
+        mpt, mrow = np.full((m1, w), -1, np.int32), np.full((m1, w), -1, np.int32)
+        seed = np.ones((m1, w), np.uint8)
+        if nc and n_p:
+            cur_a[:n_p] = np.asarray(cur, np.int32).reshape(-1)[:n_p]
+            for i, (cd, md) in enumerate(zip(cands, models)):
+                mpt[i, :n_p] = np.asarray(cd["match_point"], np.int32).reshape(-1)[:n_p]
+                mrow[i, :n_p] = np.asarray(cd["match_row"], np.int32).reshape(-1)[:n_p]
+                if md.get("inlier") is not None:
+                    seed[i, :n_p] = np.asarray(md["inlier"]).reshape(-1)[:n_p] != 0
+        pos = np.array([int(cd["pos"]) for cd in cands] or [0], np.int32)
+        s_in = np.array([float(md["scale"]) for md in models] or [np.nan], np.float64)
+        R_in = np.array([np.asarray(md["R"], np.float64).reshape(9) for md in models] or [np.full(9, np.nan)], np.float64)
+        t_in = np.array([np.asarray(md["t"], np.float64).reshape(3) for md in models] or [np.full(3, np.nan)], np.float64)
+        gmask = np.zeros((m1, max(n_kf, 1)), np.uint8)
+        for i, cd in enumerate(cands):
+            g = group[i] if group is not None else cd.get("group")
+            for q in ([int(cd["pos"])] if g is None else g):
+                if 0 <= int(q) < n_kf:
+                    gmask[i, int(q)] = 1
+        rows2 = max([self.keyframes[int(k)]._rows if 0 <= int(k) < n_kf else 0 for k in pos[:nc]] + [1])
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        if image_size is None:
+            image_size = (max(int(np.ceil(2 * K[2])), 1), max(int(np.ceil(2 * K[5])), 1))
+        scale, R, t = np.full(m1, np.nan), np.full((m1, 9), np.nan), np.full((m1, 3), np.nan)
+        n_pairs, n_guided, n_inl = np.zeros(m1, np.int32), np.zeros(m1, np.int32), np.zeros(m1, np.int32)
+        inl = np.zeros((m1, w), np.uint8)
+        fwd, bwd = np.full((m1, w), -1, np.int32), np.full((m1, rows2), -1, np.int32)
+        lpt, src = np.full(w, -1, np.int32), np.zeros(w, np.uint8)
+        flagged = any(md.get("inlier") is not None for md in models)   # (no flags at all: NULL, every listed row is a seed)
+        prm = V.MapConfirmParams(p, nc, pos.ctypes.data, cur_a.ctypes.data, mpt.ctypes.data, mrow.ctypes.data, seed.ctypes.data if flagged else None, s_in.ctypes.data,
+                                 R_in.ctypes.data, t_in.ctypes.data, gmask.ctypes.data, int(image_size[0]), int(image_size[1]), int(max_dist),
+                                 int(min_inliers), int(min_matches), float(radius_guided), float(radius_proj), float(chi2), float(scale_factor))
+        out = V.MapConfirmOut(scale.ctypes.data, R.ctypes.data, t.ctypes.data, n_pairs.ctypes.data, n_guided.ctypes.data, n_inl.ctypes.data,
+                              inl.ctypes.data, fwd.ctypes.data, bwd.ctypes.data, lpt.ctypes.data, src.ctypes.data)
+        self._check(self.lib.mo_map_loop_confirm(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        # (the library writes the arrays packed: [n_cand][rows of p] and [n_cand][R2], which is their shape whenever they hold anything)
+        res = []
+        for i in range(nc):
+            n2 = self.keyframes[int(pos[i])]._rows
+            res.append({"pos": int(pos[i]), "scale": float(scale[i]), "R": R[i].reshape(3, 3).copy(), "t": t[i].copy(), "n_pairs": int(n_pairs[i]),
+                        "n_guided": int(n_guided[i]), "n_inliers": int(n_inl[i]), "inlier": inl[i, :n_p].astype(bool), "fwd": fwd[i, :n_p].copy(),
+                        "bwd": bwd[i, :n2].copy()})
+        win = int(out.win)
+        world = None
+        if win >= 0:
+            S = np.eye(4)
+            S[:3, :3] = res[win]["scale"] * res[win]["R"]
+            S[:3, 3] = res[win]["t"]
+            T1, T2 = np.eye(4), np.eye(4)
+            T1[:3, :] = poses[p].reshape(3, 4)
+            T2[:3, :] = poses[res[win]["pos"]].reshape(3, 4)
+            world = np.linalg.inv(T1) @ S @ T2
+        return bool(out.ok), {"candidates": res, "win": win, "n_inliers": int(out.win_inliers), "loop_point": lpt[:n_p].copy(), "source": src[:n_p].copy(),
+                              "n_total": int(out.n_total), "n_proj": int(out.n_proj), "n_proj_cand": int(out.n_proj_cand),
+                              "n_loop_points": int(out.n_loop_points), "kf_pos": p, "world": world}
+
     def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3, sim3=False,
-                    **sim3_kw):
+                    confirm=False, confirm_kw=None, **sim3_kw):
         """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
         (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
         the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
@@ -751,8 +847,12 @@ class LocalMapper:
         `enough_matches`, and `accepted`: the first candidate in order with both flags (None: no loop), with its correspondence arrays.
         sim3=True: such a candidate is accepted only when compute_sim3 on it (keyword arguments in sim3_kw) is ok; `accepted` then also
         holds `sim3`: that candidate's alignment (scale, R, t, n_corr, n_inliers, inlier) with `world`, and every candidate that was
-        tried holds `sim3_ok`."""
+        tried holds `sim3_ok`.
+        confirm=True (needs sim3=True): an aligned candidate is accepted only when confirm_loop on it (keyword arguments in confirm_kw) is ok
+        too; `accepted` then also holds `confirm`: confirm_loop's info, and every candidate that was aligned holds `confirm_ok`."""
         from vslam_amd.loop import LoopConsistency
+        if confirm and not sim3:
+            raise ValueError("confirm=True needs sim3=True")
         if self._loop_consistency is None or self._loop_consistency.threshold != int(consistency):
             self._loop_consistency = LoopConsistency(consistency)
         info = self.loop_candidates(kf_position, min_weight, n_best, max_candidates, ratio)
@@ -773,6 +873,11 @@ class LocalMapper:
                 continue
             ok, al = self.compute_sim3([c], kf_position=info["kf_pos"], **sim3_kw)
             c["sim3_ok"] = ok
+            if ok and confirm:
+                ok, cf = self.confirm_loop([c], al, kf_position=info["kf_pos"], **(confirm_kw or {}))
+                c["confirm_ok"] = ok
+                if ok:
+                    c["confirm"] = cf
             if ok:
                 c["sim3"] = dict(al["candidates"][0], world=al["world"])
                 info["accepted"] = c
