@@ -394,6 +394,8 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *   mo_format_floats         that float formatting alone, one value per line (no GPU).
  *   mo_map_fuse              duplicate map points merged, missing observations gained (the comment at its declaration below).
  *   mo_map_grow              new map points for the last keyframe from its neighbour keyframes (the comment at its declaration below).
+ *   mo_map_loop_correct      a confirmed loop corrected: the asking side moved, re-posed and fused into the old side (the comment at its
+ *                            declaration below).
  *   mo_map_query_keyframes, mo_map_relocalize_pre   place recognition over a binary vocabulary and relocalization against the keyframes
  *                            it selects (the comment above mo_vocab_train below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
@@ -1065,6 +1067,68 @@ typedef struct {
     int32_t n_loop_points, n_proj_cand, n_proj, n_total;
 } mo_map_confirm_out;
 int mo_map_loop_confirm(mo_map*, const double K[9], const double* poses, const mo_map_confirm_params*, mo_map_confirm_out*);
+
+/* ---- Loop correction (map_correct.hip) ------------------------------------------------------------------------------------------------------
+ * mo_map_loop_correct: a confirmed loop corrected on the map as it stands (the first half of ORB-SLAM2's LoopClosing::CorrectLoop): the
+ * similarity is carried to the asking keyframe's neighbourhood, the neighbourhood's points and poses move, and the loop side's points
+ * replace and absorb the neighbourhood's duplicates (SearchAndFuse).  The essential-graph optimisation and global bundle adjustment are
+ * not part of it.  Opt-in: no other call runs it.  tests/correct_restatement.py restates every rule in numpy.  p = kf_pos; K, poses [n_kf][12] as for mo_map_loop_confirm; cand_pos the winning
+ * candidate; scale, R, t its confirmed model, X_p = scale R X_cand + t in camera coordinates (mo_map_loop_sim3's convention); corrected
+ * [n_kf]: non-zero at the keyframes that move; group [n_kf] (NULL: empty): non-zero at the old side, whose points are the loop points (a
+ * point with a valid observation at a group position: mo_map_loop_confirm's rule; "valid" as for mo_map_fuse); loop_point [rows of p]:
+ * mo_map_loop_confirm's output (NULL: all -1).  Rules, in this order:
+ *   1 transform     S_cw' = S_pc o T_cand; A = S_cw'^-1 o T_p, of scale 1 / scale: the map-frame transform that takes the drifted side
+ *                   onto the old side (the inverse of confirm's `world`).  In exact arithmetic ORB-SLAM2's per-keyframe
+ *                   CorrectedSwi o NonCorrectedSiw is this same A for every corrected keyframe: one transform, no owner rule.  Formed
+ *                   on the host in f64, each row summed left to right: Rq = R R_cand, tq = scale (R t_cand) + t, RA = Rq^T R_p,
+ *                   tA = Rq^T (t_p - tq), A = (1 / scale) [RA | tA].  Returned in A [12] (3 x 4, row-major) and A_scale.
+ *   2 poses         for every corrected position i: S_iw' = T_i o A^-1; the new pose is [R_i' | t_i' / scale] with R_i' = R_i RA^T and
+ *                   t_i' = t_i - R_i' tA.  poses_out holds them, the other positions as given.  kP of those slots becomes
+ *                   K [R_i' | t_i' / scale] (the product order of mo_map_bundle_adjust's write-back).
+ *   3 moved points  a point with a valid observation at a corrected position and none at a group position moves to A (X, 1), computed in
+ *                   f64 from the f32 store, each row summed left to right, rounded once to f32.  ORB-SLAM2 also moves a loop point that
+ *                   a corrected keyframe happens to see; this call does not: the old side is the anchor.  moved [point] is per old index.
+ *   4 direct        a row r of p with loop_point[r] = L in [0, points) (other values are skipped): when the owner of (p, r) is a point
+ *                   o != L, {o, L} is a merge edge; when the row is free and L has no valid observation at p, L gains (p, r); when two
+ *                   rows name one L, the lower row wins the gain and the other row stays free.
+ *   5 search        pairs are every (loop point i, corrected position k) where i has no valid observation at k.  From there on,
+ *                   under the new P of k, the candidate, search, claim and owner rules are mo_map_fuse's, word for word (projection, window
+ *                   of radius * scale_factor^ref_octave, octave +-1, information * d^2 <= chi2, Hamming <= max_dist, claims by the lowest
+ *                   (dist, i), owner = the lowest point with a valid observation of the row).  A row that rule 4 gave to a loop point
+ *                   counts as owned by it.  More than 16384 corrected positions: MO_ERR_UNSUPPORTED.
+ *   6 components    the connected components of the edges of rules 4 and 5.  Survivor: a loop point beats any other member; within that
+ *                   the most valid observations, then the lowest index.  Merged lists, compaction into the other copy of the store and
+ *                   `into` as mo_map_fuse states them; a member's gains are its gain of rule 4, then those of rule 5 by position.  The
+ *                   survivor keeps its own xyz: for a loop point the unmoved one.
+ *   7 nothing fuses (no edge, no gain, no proposal): moved xyz and kP are still written, in place in the live copy; the store is not
+ *                   flipped and `into` is the identity.
+ *   8 no work       an empty map or no keyframes: all counts 0, A the identity, poses_out = poses, MO_OK.  MO_ERR_ARG: kf_pos or
+ *                   cand_pos out of range; corrected[kf_pos] == 0; a position in both masks; a scale that is not finite or <= 0;
+ *                   non-finite R, t, K or poses; w or h <= 0; radius < 0; scale_factor <= 0; chi2 < 0.
+ * Everything is decided on the device: one chain, one synchronisation.  Integer atomics only: two calls on equal inputs give equal bytes. */
+typedef struct {
+    int32_t kf_pos, cand_pos;
+    double scale, R[9], t[3];
+    const uint8_t* corrected;    /* [n_kf] */
+    const uint8_t* group;        /* [n_kf], may be NULL */
+    const int32_t* loop_point;   /* [rows of p], may be NULL */
+    int32_t w, h;                /* image size */
+    double radius;               /* 4.0 */
+    double scale_factor;         /* 1.2 */
+    int32_t max_dist;            /* 50 */
+    double chi2;                 /* 5.991 */
+} mo_map_correct_params;
+typedef struct {
+    /* caller-allocated; any may be NULL */
+    double*  poses_out;          /* [n_kf][12] */
+    int32_t* into;               /* [map points before the call] the new index of the point each old point now is */
+    uint8_t* moved;              /* [map points before the call] */
+    /* filled by the call */
+    double A[12], A_scale;
+    int32_t n_corrected, n_moved, n_loop_points, n_direct_edges, n_direct_gained, n_pairs, n_cand, n_proposals, n_gained, n_edges, n_absorbed;
+    int64_t n_points, n_obs;     /* after the call */
+} mo_map_correct_out;
+int mo_map_loop_correct(mo_map*, const double K[9], const double* poses, const mo_map_correct_params*, mo_map_correct_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

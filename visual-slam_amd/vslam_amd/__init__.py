@@ -188,6 +188,19 @@ class MapConfirmOut(C.Structure):
                 ("n_proj_cand", C.c_int32), ("n_proj", C.c_int32), ("n_total", C.c_int32)]
 
 
+class MapCorrectParams(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("cand_pos", C.c_int32), ("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("corrected", C.c_void_p), ("group", C.c_void_p), ("loop_point", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32),
+                ("radius", C.c_double), ("scale_factor", C.c_double), ("max_dist", C.c_int32), ("chi2", C.c_double)]
+
+
+class MapCorrectOut(C.Structure):
+    _fields_ = [("poses_out", C.c_void_p), ("into", C.c_void_p), ("moved", C.c_void_p), ("A", C.c_double * 12), ("A_scale", C.c_double),
+                ("n_corrected", C.c_int32), ("n_moved", C.c_int32), ("n_loop_points", C.c_int32), ("n_direct_edges", C.c_int32),
+                ("n_direct_gained", C.c_int32), ("n_pairs", C.c_int32), ("n_cand", C.c_int32), ("n_proposals", C.c_int32),
+                ("n_gained", C.c_int32), ("n_edges", C.c_int32), ("n_absorbed", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -289,6 +302,7 @@ SIGNATURES = {
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
     "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_loop_correct": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_map_sim3_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -30,6 +30,30 @@ def predict_pose(prev, last):
     return (last @ np.linalg.inv(prev)) @ last
 
 
+def positions_sharing_points(a, counts, positions):
+    """{position: set of the keyframe positions that validly observe a map point the position validly observes} (itself included once it
+    observes anything) on the map arrays a; counts: rows per keyframe position.  An observation is read as the library reads it:
+    negative positions and rows count from the end, entries that name nothing are skipped."""
+    counts = np.asarray(counts, np.int64)
+    n_kf, n = len(counts), len(a["obs_off"]) - 1
+    if n_kf == 0 or n == 0:
+        return {int(i): set() for i in positions}
+    k, r = np.asarray(a["obs_kf"], np.int64), np.asarray(a["obs_kp"], np.int64)
+    k = np.where(k < 0, k + n_kf, k)
+    ok = (k >= 0) & (k < n_kf)
+    kc = np.clip(k, 0, n_kf - 1)
+    r = np.where(r < 0, r + counts[kc], r)
+    ok &= (r >= 0) & (r < counts[kc])
+    pt = np.repeat(np.arange(n), np.diff(np.asarray(a["obs_off"], np.int64)))[ok]
+    k = k[ok]
+    out = {}
+    for i in positions:
+        sees = np.zeros(n, bool)
+        sees[pt[k == i]] = True
+        out[int(i)] = set(np.unique(k[sees[pt]]).tolist())
+    return out
+
+
 class _Keyframe(dict):
     """a keyframe dict whose 'map_points' is read from the mapper's per-keyframe lists when asked for"""
     __slots__ = ("_mapper", "_extra", "_rows")
@@ -838,8 +862,92 @@ class LocalMapper:
                               "n_total": int(out.n_total), "n_proj": int(out.n_proj), "n_proj_cand": int(out.n_proj_cand),
                               "n_loop_points": int(out.n_loop_points), "kf_pos": p, "world": world}
 
+    def correct_loop(self, confirm, kf_position=None, corrected=None, group=None, min_weight=15, image_size=None, radius=4.0, scale_factor=1.2,
+                     max_dist=50, chi2=5.991):
+        """Corrects a confirmed loop on the map (the first half of ORB-SLAM2's CorrectLoop; mo_map_loop_correct in include/vslam_amd.h
+        states the rules): the similarity is carried to the asking keyframe's neighbourhood, whose keyframes and points move onto the old
+        side, and the old side's points replace and absorb the neighbourhood's duplicates - confirm's loop points directly, the rest of
+        the group's points by fuse_map_points' search under the corrected poses.  The essential-graph optimisation and global bundle
+        adjustment are not part of it.  `confirm` is confirm_loop's info, or an `accepted` candidate of detect_loop(confirm=True) (its
+        `confirm` entry is used, its `group` is the default group).  The asking keyframe is kf_position, by default confirm's `kf_pos`.
+        `corrected`: the positions that move; by default p and the positions whose covisibility() weight with p is at least min_weight,
+        less the group's.  `group`: the old side's positions; by default the winning candidate's group, else the candidate alone.
+        image_size as in confirm_loop.  kf["pose"] of the corrected keyframes is rewritten and the co-visibility graph follows the
+        fusion as in fuse_map_points.
+        Returns info: the counts n_corrected, n_moved, n_loop_points, n_direct_edges, n_direct_gained, n_pairs, n_cand, n_proposals,
+        n_gained, n_edges, n_absorbed, n_points, n_obs; `into` (the new index of the point each old point now is), `moved` (bool per
+        old point), `A` (3, 4) and `A_scale`: the map-frame transform the moved points took, `corrected` and `group` (position lists),
+        `poses` [n_kf][3][4] and `loop_connections`: {corrected keyframe id: sorted ids of the keyframes, not corrected ones, it shares
+        a point with after the call and shared none with before} (ORB-SLAM2's LoopConnections)."""
+        n_kf = len(self.keyframes)
+        acc = confirm if "confirm" in confirm else None
+        cf = confirm["confirm"] if acc is not None else confirm
+        win = int(cf["win"])
+        if win < 0:
+            raise ValueError("correct_loop needs a confirmation with a winner")
+        model = cf["candidates"][win]
+        p = cf.get("kf_pos") if kf_position is None else kf_position
+        p = n_kf - 1 if p is None or int(p) < 0 else int(p)
+        q = int(model["pos"])
+        if group is None:
+            group = acc.get("group") if acc is not None and acc.get("group") is not None else [q]
+        gmask = np.zeros(max(n_kf, 1), np.uint8)
+        for k in group:
+            if 0 <= int(k) < n_kf:
+                gmask[int(k)] = 1
+        cmask = np.zeros(max(n_kf, 1), np.uint8)
+        if corrected is None:
+            W = self.covisibility()
+            if 0 <= p < n_kf:
+                cmask[:n_kf] = (W[p] >= max(int(min_weight), 1)) & (gmask[:n_kf] == 0)
+                cmask[p] = 1
+        else:
+            for k in corrected:
+                if 0 <= int(k) < n_kf:
+                    cmask[int(k)] = 1
+        n_p = self.keyframes[p]._rows if 0 <= p < n_kf else 0
+        lpt = np.full(max(n_p, 1), -1, np.int32)
+        if cf.get("loop_point") is not None and n_p:
+            lpt[:n_p] = np.asarray(cf["loop_point"], np.int32).reshape(-1)[:n_p]
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        if image_size is None:
+            image_size = (max(int(np.ceil(2 * K[2])), 1), max(int(np.ceil(2 * K[5])), 1))
+        n0 = self._n_points
+        before = self.arrays() if n0 else None
+        into = np.arange(max(n0, 1), dtype=np.int32)
+        moved = np.zeros(max(n0, 1), np.uint8)
+        poses_out = poses.copy()
+        prm = V.MapCorrectParams(p, q, float(model["scale"]), (C.c_double * 9)(*np.asarray(model["R"], np.float64).reshape(9)),
+                                 (C.c_double * 3)(*np.asarray(model["t"], np.float64).reshape(3)), cmask.ctypes.data, gmask.ctypes.data, lpt.ctypes.data,
+                                 int(image_size[0]), int(image_size[1]), float(radius), float(scale_factor), int(max_dist), float(chi2))
+        out = V.MapCorrectOut(poses_out.ctypes.data, into.ctypes.data, moved.ctypes.data)
+        self._check(self.lib.mo_map_loop_correct(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        into = into[:n0]
+        cpos = np.flatnonzero(cmask[:n_kf]).tolist() if out.n_corrected else []
+        for i in cpos:
+            self.keyframes[i]["pose"][:3, :4] = poses_out[i].reshape(3, 4)
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+        info = {k: int(getattr(out, k)) for k in ("n_corrected", "n_moved", "n_loop_points", "n_direct_edges", "n_direct_gained", "n_pairs", "n_cand",
+                                                  "n_proposals", "n_gained", "n_edges", "n_absorbed", "n_points", "n_obs")}
+        info.update(into=into, moved=moved[:n0].astype(bool), A=np.array(out.A, np.float64).reshape(3, 4), A_scale=float(out.A_scale), corrected=cpos,
+                    group=np.flatnonzero(gmask[:n_kf]).tolist(), poses=poses_out[:n_kf].reshape(n_kf, 3, 4), kf_pos=p, loop_connections={})
+        if info["n_proposals"] or info["n_direct_edges"] or info["n_direct_gained"]:
+            after = self.arrays()
+            self._fuse_co_visibility(before, after, into)
+            slot_of = {id(r): s for s, r in enumerate(self._records)}
+            counts = np.array([self._rec_n[slot_of[id(kf)]] for kf in self.keyframes], np.int64)
+            nb0, nb1 = positions_sharing_points(before, counts, cpos), positions_sharing_points(after, counts, cpos)
+            cset = set(cpos)
+            info["loop_connections"] = {self.keyframes[i]["id"]: sorted(self.keyframes[k]["id"] for k in nb1[i] - nb0[i] - cset) for i in cpos}
+        return info
+
     def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3, sim3=False,
-                    confirm=False, confirm_kw=None, **sim3_kw):
+                    confirm=False, confirm_kw=None, correct=False, correct_kw=None, **sim3_kw):
         """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
         (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
         the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
@@ -849,10 +957,14 @@ class LocalMapper:
         holds `sim3`: that candidate's alignment (scale, R, t, n_corr, n_inliers, inlier) with `world`, and every candidate that was
         tried holds `sim3_ok`.
         confirm=True (needs sim3=True): an aligned candidate is accepted only when confirm_loop on it (keyword arguments in confirm_kw) is ok
-        too; `accepted` then also holds `confirm`: confirm_loop's info, and every candidate that was aligned holds `confirm_ok`."""
+        too; `accepted` then also holds `confirm`: confirm_loop's info, and every candidate that was aligned holds `confirm_ok`.
+        correct=True (needs confirm=True): an accepted loop is corrected by correct_loop (keyword arguments in correct_kw): the map
+        changes, and `accepted` also holds `correct`: correct_loop's info."""
         from vslam_amd.loop import LoopConsistency
         if confirm and not sim3:
             raise ValueError("confirm=True needs sim3=True")
+        if correct and not confirm:
+            raise ValueError("correct=True needs confirm=True")
         if self._loop_consistency is None or self._loop_consistency.threshold != int(consistency):
             self._loop_consistency = LoopConsistency(consistency)
         info = self.loop_candidates(kf_position, min_weight, n_best, max_candidates, ratio)
@@ -881,6 +993,8 @@ class LocalMapper:
             if ok:
                 c["sim3"] = dict(al["candidates"][0], world=al["world"])
                 info["accepted"] = c
+                if correct:
+                    c["correct"] = self.correct_loop(c, kf_position=info["kf_pos"], min_weight=min_weight, **(correct_kw or {}))
                 break
         return info["accepted"] is not None, info
 
