@@ -396,6 +396,8 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *   mo_map_grow              new map points for the last keyframe from its neighbour keyframes (the comment at its declaration below).
  *   mo_map_loop_correct      a confirmed loop corrected: the asking side moved, re-posed and fused into the old side (the comment at its
  *                            declaration below).
+ *   mo_map_pose_graph        the essential graph optimised behind such a correction: Sim(3) pose graph over the keyframes, the points
+ *                            follow (the comment at its declaration below).
  *   mo_map_query_keyframes, mo_map_relocalize_pre   place recognition over a binary vocabulary and relocalization against the keyframes
  *                            it selects (the comment above mo_vocab_train below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
@@ -1071,8 +1073,8 @@ int mo_map_loop_confirm(mo_map*, const double K[9], const double* poses, const m
 /* ---- Loop correction (map_correct.hip) ------------------------------------------------------------------------------------------------------
  * mo_map_loop_correct: a confirmed loop corrected on the map as it stands (the first half of ORB-SLAM2's LoopClosing::CorrectLoop): the
  * similarity is carried to the asking keyframe's neighbourhood, the neighbourhood's points and poses move, and the loop side's points
- * replace and absorb the neighbourhood's duplicates (SearchAndFuse).  The essential-graph optimisation and global bundle adjustment are
- * not part of it.  Opt-in: no other call runs it.  tests/correct_restatement.py restates every rule in numpy.  p = kf_pos; K, poses [n_kf][12] as for mo_map_loop_confirm; cand_pos the winning
+ * replace and absorb the neighbourhood's duplicates (SearchAndFuse).  The essential-graph optimisation is mo_map_pose_graph below, a call
+ * of its own; global bundle adjustment is not built.  Opt-in: no other call runs it.  tests/correct_restatement.py restates every rule in numpy.  p = kf_pos; K, poses [n_kf][12] as for mo_map_loop_confirm; cand_pos the winning
  * candidate; scale, R, t its confirmed model, X_p = scale R X_cand + t in camera coordinates (mo_map_loop_sim3's convention); corrected
  * [n_kf]: non-zero at the keyframes that move; group [n_kf] (NULL: empty): non-zero at the old side, whose points are the loop points (a
  * point with a valid observation at a group position: mo_map_loop_confirm's rule; "valid" as for mo_map_fuse); loop_point [rows of p]:
@@ -1129,6 +1131,74 @@ typedef struct {
     int64_t n_points, n_obs;     /* after the call */
 } mo_map_correct_out;
 int mo_map_loop_correct(mo_map*, const double K[9], const double* poses, const mo_map_correct_params*, mo_map_correct_out*);
+
+/* ---- Essential-graph optimisation (map_posegraph.hip, posegraph.h) ------------------------------------------------------------------------
+ * mo_map_pose_graph: the second half of ORB-SLAM2's LoopClosing::CorrectLoop, Optimizer::OptimizeEssentialGraph (monocular: the scale is
+ * free): after mo_map_loop_correct moved one end of a loop, the error that is left sits at the edge of the corrected set; this call
+ * spreads it along the trajectory.  Opt-in: no other call runs it.  tests/native/posegraph_replay.cpp is the whole call on the host,
+ * tests/posegraph_restatement.py restates rule 1 in numpy.  A vertex is a similarity S_i = (s, R, t), X_cam = s R X + t, one per keyframe
+ * position; delta = (rho, w, lambda) moves it as mo_map_loop_sim3's refinement does: s' = e^lambda s, R' = exp(w) R,
+ * t' = e^lambda exp(w) t + rho.  An edge (a, b), a < b, carries M_ba, which should equal S_b o S_a^-1; its residual is the 7-vector
+ * (t_E, log R_E, ln s_E) of E = M_ba o S_a o S_b^-1, its information the identity.
+ * poses [n_kf][12]: [R | t] of every position before the correction, at scale 1: the measurement source.  init [n_kf][13]: s, R [9], t [3]
+ * per position: for a corrected keyframe T_i o A^-1 with its scale (mo_map_loop_correct's S_iw'), for every other its pose with s = 1.
+ * fixed [n_kf]: non-zero at the positions that do not move; extra_a / extra_b [n_extra]: the loop connections and earlier loop edges.
+ * Rules, in this order:
+ *   1 edges       from the covisibility matrix W of the map as it stands (mo_map_covisibility's, so after the fusion).  parent[b], b >= 1:
+ *                 the position a < b of the largest W[a][b], ties to the lowest; b - 1 when that weight is 0.  This is a stand-in for
+ *                 ORB-SLAM2's spanning tree, which is maintained at keyframe insertion: it keeps the graph connected to position 0.
+ *                 The edges are the unordered pairs {a, b} that are an extra edge (kind 0), else {parent[b], b} (kind 1), else have
+ *                 W[a][b] >= min_weight (kind 2; min_weight < 1 counts as 1), less the pairs of two fixed positions; each once, ordered by
+ *                 (a, b).  Measurement of an extra edge: S_b,init o S_a,init^-1 (its residual starts at 0, as ORB-SLAM2's loop edges do;
+ *                 it is never measured from poses); of any other edge: T_b o T_a^-1 from poses.  More edges than 32 n_kf + n_extra:
+ *                 MO_ERR_CAPACITY, nothing written.
+ *   2 steps       Levenberg-Marquardt on the free vertices with mo_map_bundle_adjust's conventions: the diagonal of the normal equations
+ *                 times (1 + lambda), lambda 1e-4 at the start; a step is accepted when the cost (the sum of the squared residuals)
+ *                 falls, then lambda / 10, otherwise it is undone and lambda * 10.  The end: max_steps, a largest update below step_tol,
+ *                 lambda > 1e8.
+ *   3 solve       every step's linear system by block-sparse conjugate gradient from 0, preconditioned by the inverse of the damped 7x7
+ *                 diagonal blocks (a block that is not positive definite holds its vertex for the step); it ends at
+ *                 r.z <= cg_tol^2 r0.z0 or after max_cg iterations.  A truncated solve is legitimate: rule 2 accepts on the true cost.
+ *   4 writes      when at least one step was accepted: every free position's pose becomes [R | t / s] and its kP K [R | t / s]
+ *                 (mo_map_bundle_adjust's product order); a point whose reference - the position of its first valid observation in
+ *                 list order - is free becomes S_r,final^-1 (S_r,init X), computed in f64 and rounded once to f32.  A point without a
+ *                 valid observation or with a fixed reference keeps its bytes.  No observation or point is added or removed.
+ *   5 no work     an empty map, one keyframe, no free position, max_steps = 0, no accepted step: nothing is written, ok = 0 (the first
+ *                 three: every count 0 and the output arrays untouched).  MO_ERR_ARG: no fixed position; non-finite poses, init or K;
+ *                 a scale of init <= 0; an extra edge out of range or with a == b; max_steps outside 0 .. 100; max_cg < 1; a negative
+ *                 tolerance.  The int32 and n_kf^2 guards of mo_map_covisibility apply.
+ * Everything is decided on the device: one chain, one synchronisation.  No floating-point atomics, every sum a fixed tree: two calls
+ * on equal inputs give equal bytes.
+ * poses_out [n_kf][12]: [R | t / s] of every position's final similarity (the initial one where nothing moved); sim3_out [n_kf][13];
+ * edge_a / edge_b / edge_kind: the first edge_cap edges (n_edges is the full count); moved [map points]; cost: before the first step and at the end
+ * (0 when no step ran); cg_iters: the iterations of all solves. */
+typedef struct {
+    const uint8_t* fixed;        /* [n_kf] */
+    const int32_t* extra_a;      /* [n_extra], may be NULL when n_extra is 0 */
+    const int32_t* extra_b;
+    int32_t n_extra;
+    int32_t min_weight;          /* 100 */
+    int32_t max_steps;           /* 20 */
+    int32_t max_cg;              /* 200 */
+    double cg_tol;               /* 1e-8 */
+    double step_tol;             /* 1e-10 */
+    double K[9];
+} mo_map_pg_params;
+typedef struct {
+    /* caller-allocated; any may be NULL */
+    double*  poses_out;          /* [n_kf][12] */
+    double*  sim3_out;           /* [n_kf][13] */
+    int32_t* edge_a;             /* [edge_cap] */
+    int32_t* edge_b;             /* [edge_cap] */
+    uint8_t* edge_kind;          /* [edge_cap] 0 extra, 1 parent, 2 covisibility */
+    uint8_t* moved;              /* [map points] */
+    int32_t  edge_cap;
+    /* filled by the call */
+    int32_t steps, accepted, cg_iters;
+    int32_t n_free, n_fixed, n_edges, n_extra_used, n_moved, ok;
+    double cost[2], lambda;
+} mo_map_pg_out;
+int mo_map_pose_graph(mo_map*, const double* poses, const double* init, const mo_map_pg_params*, mo_map_pg_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

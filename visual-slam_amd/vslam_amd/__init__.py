@@ -201,6 +201,18 @@ class MapCorrectOut(C.Structure):
                 ("n_gained", C.c_int32), ("n_edges", C.c_int32), ("n_absorbed", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64)]
 
 
+class MapPgParams(C.Structure):
+    _fields_ = [("fixed", C.c_void_p), ("extra_a", C.c_void_p), ("extra_b", C.c_void_p), ("n_extra", C.c_int32), ("min_weight", C.c_int32),
+                ("max_steps", C.c_int32), ("max_cg", C.c_int32), ("cg_tol", C.c_double), ("step_tol", C.c_double), ("K", C.c_double * 9)]
+
+
+class MapPgOut(C.Structure):
+    _fields_ = [("poses_out", C.c_void_p), ("sim3_out", C.c_void_p), ("edge_a", C.c_void_p), ("edge_b", C.c_void_p), ("edge_kind", C.c_void_p),
+                ("moved", C.c_void_p), ("edge_cap", C.c_int32), ("steps", C.c_int32), ("accepted", C.c_int32), ("cg_iters", C.c_int32),
+                ("n_free", C.c_int32), ("n_fixed", C.c_int32), ("n_edges", C.c_int32), ("n_extra_used", C.c_int32), ("n_moved", C.c_int32),
+                ("ok", C.c_int32), ("cost", C.c_double * 2), ("lambda_", C.c_double)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -303,6 +315,7 @@ SIGNATURES = {
     "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_correct": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_pose_graph": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_map_sim3_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -867,8 +867,8 @@ class LocalMapper:
         """Corrects a confirmed loop on the map (the first half of ORB-SLAM2's CorrectLoop; mo_map_loop_correct in include/vslam_amd.h
         states the rules): the similarity is carried to the asking keyframe's neighbourhood, whose keyframes and points move onto the old
         side, and the old side's points replace and absorb the neighbourhood's duplicates - confirm's loop points directly, the rest of
-        the group's points by fuse_map_points' search under the corrected poses.  The essential-graph optimisation and global bundle
-        adjustment are not part of it.  `confirm` is confirm_loop's info, or an `accepted` candidate of detect_loop(confirm=True) (its
+        the group's points by fuse_map_points' search under the corrected poses.  The essential-graph optimisation is
+        optimize_essential_graph, a call of its own; global bundle adjustment is not built.  `confirm` is confirm_loop's info, or an `accepted` candidate of detect_loop(confirm=True) (its
         `confirm` entry is used, its `group` is the default group).  The asking keyframe is kf_position, by default confirm's `kf_pos`.
         `corrected`: the positions that move; by default p and the positions whose covisibility() weight with p is at least min_weight,
         less the group's.  `group`: the old side's positions; by default the winning candidate's group, else the candidate alone.
@@ -946,8 +946,90 @@ class LocalMapper:
             info["loop_connections"] = {self.keyframes[i]["id"]: sorted(self.keyframes[k]["id"] for k in nb1[i] - nb0[i] - cset) for i in cpos}
         return info
 
+    def optimize_essential_graph(self, correct, poses_before=None, fixed=None, min_weight=100, extra_edges=None, max_steps=20, max_cg=200,
+                                 cg_tol=1e-8, step_tol=1e-10, want_edges=True):
+        """Optimises the essential graph behind a loop correction (the second half of ORB-SLAM2's CorrectLoop, OptimizeEssentialGraph;
+        mo_map_pose_graph in include/vslam_amd.h states the rules): a Sim(3) pose graph over all keyframes whose edges come from the
+        covisibility matrix (a parent per keyframe, the pairs of at least min_weight common points) and from the loop; the error the
+        correction left at the edge of the corrected set is spread along the trajectory, and every point follows its reference keyframe.
+        `correct` is correct_loop's info, or an `accepted` candidate of detect_loop(correct=True) (its `correct` entry is used and its
+        `pos` is the winning candidate).  poses_before: the [R | t] of every keyframe before that correction (n_kf arrays of at least
+        3 x 4); by default they are reconstructed in f64 from correct["poses"], A and A_scale (R_i = R_i' RA, t_i = s t_pose + R_i' tA
+        with s = 1 / A_scale, RA | tA = s A).  `fixed`: the positions that stay; by default the winning candidate's (given correct_loop's info alone,
+        which does not name it, the lowest position of its group).  correct["loop_connections"] (keyframe ids) become position pairs and join extra_edges (position pairs).
+        kf["pose"] of the free keyframes is rewritten when a step was accepted.
+        Returns info: ok, cost (start, end), lambda, steps, accepted, cg_iters, n_free, n_fixed, n_edges, n_extra_used, n_moved, `poses`
+        [n_kf][3][4], `sim3` [n_kf][13] (s, R, t), `moved` (bool per point), `fixed` (positions) and `edges`: (a, b, kind) arrays."""
+        n_kf = len(self.keyframes)
+        winner = None
+        if "correct" in correct:
+            winner, correct = int(correct["pos"]), correct["correct"]
+        cpos = [int(k) for k in correct["corrected"]]
+        s = 1.0 / float(correct["A_scale"])
+        A = np.asarray(correct["A"], np.float64).reshape(3, 4)
+        RA, tA = s * A[:, :3], s * A[:, 3]
+        after = np.asarray(correct["poses"], np.float64).reshape(-1, 3, 4) if n_kf else np.zeros((0, 3, 4))
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        init = np.zeros((max(n_kf, 1), 13), np.float64)
+        cset = set(cpos)
+        for i in range(n_kf):
+            if poses_before is not None:
+                T = np.asarray(poses_before[i], np.float64)[:3, :4]
+            elif i in cset:
+                Ri = after[i][:, :3] @ RA
+                T = np.hstack([Ri, (s * after[i][:, 3] + after[i][:, :3] @ tA).reshape(3, 1)])
+            else:
+                T = after[i]
+            poses[i] = T.reshape(12)
+            if i in cset:   # S_iw' = T_i o A^-1: the corrected pose with its translation back at scale s
+                init[i, 0] = s
+                init[i, 1:10] = after[i][:, :3].reshape(9)
+                init[i, 10:] = s * after[i][:, 3]
+            else:
+                init[i, 0] = 1.0
+                init[i, 1:10] = T[:, :3].reshape(9)
+                init[i, 10:] = T[:, 3]
+        if fixed is None:
+            fixed = [winner] if winner is not None else sorted(correct["group"])[:1]
+        fmask = np.zeros(max(n_kf, 1), np.uint8)
+        for k in fixed:
+            if 0 <= int(k) < n_kf:
+                fmask[int(k)] = 1
+        pos_of = {kf["id"]: i for i, kf in enumerate(self.keyframes)}
+        pairs = [(int(a), int(b)) for a, b in (extra_edges or [])]
+        for a, others in (correct.get("loop_connections") or {}).items():
+            pairs += [(pos_of[a], pos_of[b]) for b in others if a in pos_of and b in pos_of]
+        xa = np.array([a for a, _ in pairs] or [0], np.int32)
+        xb = np.array([b for _, b in pairs] or [0], np.int32)
+        cap = max(n_kf * (n_kf - 1) // 2, 1) if want_edges else 0
+        ea, eb, ek = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.uint8)
+        n0 = self._n_points
+        moved = np.zeros(max(n0, 1), np.uint8)
+        poses_out = np.zeros((max(n_kf, 1), 12), np.float64)
+        sim3_out = init.copy()
+        for i in range(n_kf):
+            poses_out[i] = np.hstack([init[i, 1:10].reshape(3, 3), (init[i, 10:] / init[i, 0]).reshape(3, 1)]).reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        prm = V.MapPgParams(fmask.ctypes.data, xa.ctypes.data, xb.ctypes.data, len(pairs), int(min_weight), int(max_steps), int(max_cg), float(cg_tol),
+                            float(step_tol), (C.c_double * 9)(*K))
+        out = V.MapPgOut(poses_out.ctypes.data, sim3_out.ctypes.data, ea.ctypes.data, eb.ctypes.data, ek.ctypes.data, moved.ctypes.data, cap)
+        self._check(self.lib.mo_map_pose_graph(self._h, V._ptr(poses), V._ptr(init), C.byref(prm), C.byref(out)))
+        ok = bool(out.ok)
+        if ok:
+            for i in range(n_kf):
+                if not fmask[i]:
+                    self.keyframes[i]["pose"][:3, :4] = poses_out[i].reshape(3, 4)
+        self._version += 1
+        self._cache = None
+        info = {k: int(getattr(out, k)) for k in ("steps", "accepted", "cg_iters", "n_free", "n_fixed", "n_edges", "n_extra_used", "n_moved")}
+        ne = min(info["n_edges"], cap)
+        info.update(ok=ok, cost=(float(out.cost[0]), float(out.cost[1])), poses=poses_out[:n_kf].reshape(n_kf, 3, 4), sim3=sim3_out[:n_kf],
+                    moved=moved[:n0].astype(bool), fixed=np.flatnonzero(fmask[:n_kf]).tolist(), edges=(ea[:ne].copy(), eb[:ne].copy(), ek[:ne].copy()))
+        info["lambda"] = float(out.lambda_)
+        return info
+
     def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3, sim3=False,
-                    confirm=False, confirm_kw=None, correct=False, correct_kw=None, **sim3_kw):
+                    confirm=False, confirm_kw=None, correct=False, correct_kw=None, optimize=False, optimize_kw=None, **sim3_kw):
         """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
         (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
         the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
@@ -959,12 +1041,16 @@ class LocalMapper:
         confirm=True (needs sim3=True): an aligned candidate is accepted only when confirm_loop on it (keyword arguments in confirm_kw) is ok
         too; `accepted` then also holds `confirm`: confirm_loop's info, and every candidate that was aligned holds `confirm_ok`.
         correct=True (needs confirm=True): an accepted loop is corrected by correct_loop (keyword arguments in correct_kw): the map
-        changes, and `accepted` also holds `correct`: correct_loop's info."""
+        changes, and `accepted` also holds `correct`: correct_loop's info.
+        optimize=True (needs correct=True): the essential graph is optimised behind the correction by optimize_essential_graph (keyword
+        arguments in optimize_kw) from the poses as they were before it, and `accepted` also holds `optimize`: its info."""
         from vslam_amd.loop import LoopConsistency
         if confirm and not sim3:
             raise ValueError("confirm=True needs sim3=True")
         if correct and not confirm:
             raise ValueError("correct=True needs confirm=True")
+        if optimize and not correct:
+            raise ValueError("optimize=True needs correct=True")
         if self._loop_consistency is None or self._loop_consistency.threshold != int(consistency):
             self._loop_consistency = LoopConsistency(consistency)
         info = self.loop_candidates(kf_position, min_weight, n_best, max_candidates, ratio)
@@ -994,7 +1080,10 @@ class LocalMapper:
                 c["sim3"] = dict(al["candidates"][0], world=al["world"])
                 info["accepted"] = c
                 if correct:
+                    before = [np.asarray(kf["pose"], np.float64)[:3, :4].copy() for kf in self.keyframes] if optimize else None
                     c["correct"] = self.correct_loop(c, kf_position=info["kf_pos"], min_weight=min_weight, **(correct_kw or {}))
+                    if optimize:
+                        c["optimize"] = self.optimize_essential_graph(c, poses_before=before, **(optimize_kw or {}))
                 break
         return info["accepted"] is not None, info
 
