@@ -1,6 +1,8 @@
 // tools/ubench.hip -- instruction-rate microbenchmark for gfx950 (diagnostic tool, not part of the library).
 // For each vector instruction: cycles per wave-instruction as seen by one wave (s_memtime) with 1, 2, 4, 8 waves per SIMD,
-// independent (16 registers) and dependent (one register chain) streams.  Build: make -C tools; run on the GPU box.
+// independent (16 registers) and dependent (one register chain) streams.  Scalar classes (s_add_i32, s_and_b64, s_bcnt1_i32_b64, s_cselect_b64, s_lshl_b64,
+// writes of EXEC, s_nop 0, s_waitcnt) and vector : scalar mixes with 1, 2 or 4 busy SIMDs per CU.  Build: make -C tools; run on the GPU box:
+// _build/ubench [workgroups [vector|scalar|all]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -171,6 +173,57 @@ __global__ void k_clock(unsigned long long* o, int iters) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { o[0] = t1 - t0; o[1] = r1 - r0; o[2] = r; }
 }
 
+// ---- scalar classes.  One trip = 32 blocks of 4 instructions on 4 independent scalar registers (128 per trip, so the loop's own
+// s_add / s_cmp / s_cbranch are under 3 % of the stream).  Only the waves on SIMDs [0, nsimd) of their CU run the loop, the others leave
+// at once: with one workgroup per CU that gives 1, 2 or 4 busy SIMDs at any number of waves per SIMD, which tells a per-CU limit
+// (cycles per instruction grow with the number of busy SIMDs) from a per-SIMD one (they do not).
+#define SREP 32
+#define S_PROLOGUE                                                                                        \
+    const uint32_t simd = __builtin_amdgcn_s_getreg((4 << 0) | (4 << 6) | (1 << 11)); /* HW_ID bits 5:4 */ \
+    const int wslot = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);                                \
+    if ((int)simd >= nsimd) { if ((threadIdx.x & 63) == 0) cyc[wslot] = 0; return; }                      \
+    uint32_t a0 = __builtin_amdgcn_readfirstlane(iters), a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, c = a0 | 5; \
+    unsigned long long b0 = 0x0123456789abcdefull ^ a0, b1 = b0 + 1, b2 = b0 + 2, b3 = b0 + 3, ones;       \
+    asm volatile("s_mov_b64 %0, -1" : "=s"(ones));                                                        \
+    uint32_t v0 = threadIdx.x, v1 = v0 + 1, v2 = v0 + 2, v3 = v0 + 3, vc = threadIdx.x | 0x01010101u;
+#define S_EPILOGUE                                                                                        \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ (uint32_t)(b0 ^ b1 ^ b2 ^ b3) ^ v0 ^ v1 ^ v2 ^ v3; \
+    if ((threadIdx.x & 63) == 0) cyc[wslot] = t1 - t0;
+#define S_OPERANDS : "+s"(a0), "+s"(a1), "+s"(a2), "+s"(a3), "+s"(b0), "+s"(b1), "+s"(b2), "+s"(b3), "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3) \
+                   : "s"(c), "s"(ones), "v"(vc) : "scc"
+// operands: %0-%3 32-bit scalar, %4-%7 64-bit scalar, %8-%11 vector, %12 scalar constant, %13 all-ones lane mask, %14 vector constant
+#define DEFS(NAME, ASM)                                                                                   \
+    __global__ __launch_bounds__(1024) void ks_##NAME(uint32_t* out, int iters, unsigned long long* cyc, int nsimd) { \
+        S_PROLOGUE                                                                                        \
+        unsigned long long t0 = __builtin_amdgcn_s_memtime();                                             \
+        for (int i = 0; i < iters; i++) {                                                                 \
+            _Pragma("unroll") for (int k = 0; k < SREP; k++) asm volatile(ASM S_OPERANDS);                \
+        }                                                                                                 \
+        unsigned long long t1 = __builtin_amdgcn_s_memtime();                                             \
+        S_EPILOGUE                                                                                        \
+    }
+DEFS(s_add_i32, "s_add_i32 %0, %0, %12\n\ts_add_i32 %1, %1, %12\n\ts_add_i32 %2, %2, %12\n\ts_add_i32 %3, %3, %12")
+DEFS(s_mul_i32, "s_mul_i32 %0, %0, %12\n\ts_mul_i32 %1, %1, %12\n\ts_mul_i32 %2, %2, %12\n\ts_mul_i32 %3, %3, %12")
+DEFS(s_and_b64, "s_and_b64 %4, %4, %13\n\ts_and_b64 %5, %5, %13\n\ts_and_b64 %6, %6, %13\n\ts_and_b64 %7, %7, %13")
+DEFS(s_bcnt1_i32_b64, "s_bcnt1_i32_b64 %0, %4\n\ts_bcnt1_i32_b64 %1, %5\n\ts_bcnt1_i32_b64 %2, %6\n\ts_bcnt1_i32_b64 %3, %7")
+DEFS(s_cselect_b64, "s_cselect_b64 %4, %4, %13\n\ts_cselect_b64 %5, %5, %13\n\ts_cselect_b64 %6, %6, %13\n\ts_cselect_b64 %7, %7, %13")
+DEFS(s_lshl_b64, "s_lshl_b64 %4, %4, 1\n\ts_lshl_b64 %5, %5, 1\n\ts_lshl_b64 %6, %6, 1\n\ts_lshl_b64 %7, %7, 1")
+DEFS(s_cmp_lt_i32, "s_cmp_lt_i32 %0, %12\n\ts_cmp_lt_i32 %1, %12\n\ts_cmp_lt_i32 %2, %12\n\ts_cmp_lt_i32 %3, %12")
+DEFS(exec_mov, "s_mov_b64 exec, %13\n\ts_mov_b64 exec, %13\n\ts_mov_b64 exec, %13\n\ts_mov_b64 exec, %13")  // EXEC stays all ones
+DEFS(exec_and, "s_and_b64 exec, exec, %13\n\ts_and_b64 exec, exec, %13\n\ts_and_b64 exec, exec, %13\n\ts_and_b64 exec, exec, %13")
+DEFS(s_nop0, "s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0")
+DEFS(s_waitcnt, "s_waitcnt lgkmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_waitcnt lgkmcnt(0)")
+// the push of k_fast: EXEC narrowed around one vector instruction (3 scalar + 1 vector per block of 4; EXEC stays all ones)
+DEFS(exec_push, "s_mov_b64 %4, exec\n\ts_and_b64 exec, exec, %13\n\tv_xor_b32 %8, %8, %14\n\ts_mov_b64 exec, %4")
+// fast-class vector instructions alone, then mixed with s_add_i32 at vector : scalar = 2:1, 1:1, 1:2 (blocks of 4, 6, 4, 6 instructions)
+DEFS(v_xor, "v_xor_b32 %8, %8, %14\n\tv_xor_b32 %9, %9, %14\n\tv_xor_b32 %10, %10, %14\n\tv_xor_b32 %11, %11, %14")
+DEFS(mix_v2s1, "v_xor_b32 %8, %8, %14\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %0, %0, %12\n\tv_xor_b32 %10, %10, %14\n\tv_xor_b32 %11, %11, %14\n\ts_add_i32 %1, %1, %12")
+DEFS(mix_v1s1, "v_xor_b32 %8, %8, %14\n\ts_add_i32 %0, %0, %12\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %1, %1, %12")
+DEFS(mix_v1s2, "v_xor_b32 %8, %8, %14\n\ts_add_i32 %0, %0, %12\n\ts_add_i32 %1, %1, %12\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %2, %2, %12\n\ts_add_i32 %3, %3, %12")
+typedef void (*skern_t)(uint32_t*, int, unsigned long long*, int);
+struct SEntry { const char* name; skern_t k; int per_block; };
+#define SE(NAME, N) {#NAME, ks_##NAME, N}
+
 typedef void (*kern_t)(uint32_t*, int, unsigned long long*);
 struct Entry { const char* name; kern_t ind, dep; };
 #define E(NAME) {#NAME, ki_##NAME, kd_##NAME}
@@ -194,6 +247,7 @@ int main(int argc, char** argv) {
     hipMalloc(&d_out, (size_t)maxw * 64 * 4);
     hipMalloc(&d_cyc, (size_t)maxw * 8);
     std::vector<unsigned long long> h(maxw);
+    double ghz = 2.4;
     {   // warm the clocks, then relate s_memtime to s_memrealtime (100 MHz) and to the host's event clock
         for (int i = 0; i < 40; i++) hipLaunchKernelGGL(k_clock, dim3(2048), dim3(256), 0, 0, d_cyc, 40000);
         hipDeviceSynchronize();
@@ -202,6 +256,7 @@ int main(int argc, char** argv) {
         unsigned long long o[3];
         hipMemcpy(o, d_cyc, sizeof(o), hipMemcpyDeviceToHost);
         printf("clock: s_memtime %llu ticks over %.1f us of s_memrealtime -> %.3f GHz\n", o[0], o[1] / 100.0, o[0] / (o[1] * 10.0));
+        ghz = o[0] / (o[1] * 10.0);
     }
     // geometry: w <= 4 -> ncu blocks of 256 w threads (one per CU if the dispatcher spreads them); w = 8 -> 2 ncu blocks of 1024
     const int nblk = argc > 1 ? atoi(argv[1]) : ncu;
@@ -224,10 +279,13 @@ int main(int argc, char** argv) {
         for (int c : persimd) { sused += c > 0; smx = std::max(smx, c); }
         printf("census w=%d: %d waves on %d CUs (max %d per CU), %d SIMDs (max %d per SIMD)\n", w, nw, used, mx, sused, smx);
     }
+    const std::string what = argc > 2 ? argv[2] : "all";  // "vector", "scalar" or "all"
+    if (what != "scalar") {
     printf("device %s, %d CUs; ticks (shader cycles) per wave-instruction seen by a wave, median over waves / the same divided by waves per SIMD; launch wall\n", prop.name, ncu);
     printf("%-16s %-4s", "op", "");
     for (int w : {1, 2, 4, 8}) printf("  w/SIMD=%d [min p10 med p90 max] wall   ", w);
     printf("\n");
+    }
     auto run = [&](const char* name, const char* kind, auto launch, double per_trip) {
         printf("%-16s %-4s", name, kind);
         for (int w : {1, 2, 4, 8}) {
@@ -249,6 +307,61 @@ int main(int argc, char** argv) {
         }
         printf("\n");
     };
+    if (what != "vector") {
+        // scalar classes: busy SIMDs per CU x waves per busy SIMD; per cell the median over the running waves of shader cycles per instruction as a
+        // wave sees them, and (in brackets) the CU's issue rate in instructions per cycle = running waves on the CU / that figure
+        const int siters = 3000;
+        std::vector<SEntry> ss = {SE(s_add_i32, 4), SE(s_mul_i32, 4), SE(s_and_b64, 4), SE(s_bcnt1_i32_b64, 4), SE(s_cselect_b64, 4), SE(s_lshl_b64, 4), SE(s_cmp_lt_i32, 4),
+                                  SE(exec_mov, 4), SE(exec_and, 4), SE(s_nop0, 4), SE(s_waitcnt, 4), SE(exec_push, 4), SE(v_xor, 4), SE(mix_v2s1, 6), SE(mix_v1s1, 4), SE(mix_v1s2, 6)};
+        // per launch: median and maximum over the running waves of the cycles per instruction a wave sees, and the launch's wall time (events) in
+        // shader cycles per instruction per busy SIMD = wall x clock / (waves per SIMD x instructions per wave).  The SIMD's arbiter favours its
+        // oldest waves, so at 4 and 8 waves per SIMD the waves do not run at one speed and only the wall figure is a throughput.
+        struct Cell { double med, mx, wall; };
+        auto srun = [&](const SEntry& e, int blocks, int threads, int nsimd, int wps) {
+            Cell c = {0, 0, 0};
+            float ms = 0;
+            for (int pass = 0; pass < 2; pass++) {  // first pass warms
+                hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+                hipEventRecord(e0);
+                hipLaunchKernelGGL(e.k, dim3(blocks), dim3(threads), 0, 0, d_out, siters, d_cyc, nsimd);
+                hipEventRecord(e1);
+                hipDeviceSynchronize();
+                hipEventElapsedTime(&ms, e0, e1);
+                hipEventDestroy(e0); hipEventDestroy(e1);
+            }
+            const int nw = blocks * threads / 64;
+            hipMemcpy(h.data(), d_cyc, (size_t)nw * 8, hipMemcpyDeviceToHost);
+            std::vector<unsigned long long> run;
+            for (int i = 0; i < nw; i++) if (h[i]) run.push_back(h[i]);
+            if (run.empty()) return c;
+            std::sort(run.begin(), run.end());
+            const double per_wave = (double)siters * SREP * e.per_block;
+            c.med = run[run.size() / 2] / per_wave;
+            c.mx = run.back() / per_wave;
+            c.wall = ms * 1e-3 * ghz * 1e9 / (wps * per_wave);
+            return c;
+        };
+        printf("\nscalar classes, %d workgroups (one per CU; two of 1024 threads per CU at 8 waves per SIMD), S<busy SIMDs per CU>w<waves per busy SIMD>\n", nblk);
+        printf("per cell: median/maximum over the waves of cycles per instruction as a wave sees them | wall time in cycles per instruction per busy SIMD\n");
+        printf("%-16s", "op");
+        for (int t : {64, 128, 256}) printf(" wg%-3d            ", t);
+        for (int ns : {1, 2, 4}) for (int w : {1, 2, 4, 8}) printf(" S%dw%d              ", ns, w);
+        printf("\n");
+        for (auto& e : ss) {
+            printf("%-16s", e.name);
+            for (int threads : {64, 128, 256}) {  // one wave on 1, 2, 4 SIMDs of a CU by the workgroup size alone
+                Cell c = srun(e, nblk, threads, 4, 1);
+                printf(" %5.2f/%5.2f|%5.2f", c.med, c.mx, c.wall);
+            }
+            for (int ns : {1, 2, 4}) for (int w : {1, 2, 4, 8}) {
+                int blocks, threads; geom(w, blocks, threads);
+                Cell c = srun(e, blocks, threads, ns, w);
+                printf(" %5.2f/%5.2f|%5.2f", c.med, c.mx, c.wall);
+            }
+            printf("\n");
+        }
+        if (what == "scalar") return 0;
+    }
     for (auto& e : es) {
         std::string nm(e.name); double per = 16.0 * (nm == "cmp_cndmask" || nm == "mix" ? 2 : nm == "xor" || nm == "bcnt" || nm == "fma_f64" ? 1 : 4);
         run(e.name, "ind", [&](int b, int t) { hipLaunchKernelGGL(e.ind, dim3(b), dim3(t), 0, 0, d_out, iters, d_cyc); }, per);

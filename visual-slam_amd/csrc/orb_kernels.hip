@@ -15,6 +15,7 @@
 //             (16 per lane); compute() with caller keypoints: one wavefront per keypoint, 4 tests per lane
 // All arithmetic is integer or non-contracted float32 (compile with -ffp-contract=off) so results are
 // bit-identical to the CPU oracle.
+#include <type_traits>
 #include <cstring>
 
 #include "common.h"
@@ -767,16 +768,28 @@ __device__ __forceinline__ unsigned long long ballot_gt16(int a, int b) {
 }
 
 // ds_write_b16 of val at LDS byte address addr by exactly the lanes of mask (a wave mask the caller already holds in scalar
-// registers): EXEC is narrowed to the mask around the store instead of rebuilding a per-lane predicate from it (two v_and, a
-// 64-bit compare and a branch per push otherwise).  A store with EXEC = 0 is a no-op.
-__device__ __forceinline__ void lds_store_u16_masked(unsigned long long mask, uint32_t addr, uint32_t val) {
-    unsigned long long keep;
-    asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %1\n\tds_write_b16 %2, %3\n\ts_mov_b64 exec, %0"
-                 : "=&s"(keep) : "s"(mask), "v"(addr), "v"(val) : "memory", "scc");
+// registers): EXEC is set to the mask around the store instead of rebuilding a per-lane predicate from it (two v_and, a
+// 64-bit compare and a branch per push otherwise).  A store with EXEC = 0 is a no-op.  all = the EXEC the caller runs with
+// (wave_exec(), read once per phase: the pushes sit in wave-uniform control flow) and mask a subset of it, as every ballot taken
+// under it is, so one s_mov sets EXEC and one puts it back.  A SIMD issues one scalar-ALU instruction per 4.3 cycles
+// (profiles/scalar_ubench.txt), which bound the compass loop while every push saved, narrowed and restored EXEC.
+__device__ __forceinline__ unsigned long long wave_exec() {
+    unsigned long long all;
+    asm volatile("s_mov_b64 %0, exec" : "=s"(all));
+    return all;
+}
+__device__ __forceinline__ void lds_store_u16_masked(unsigned long long mask, uint32_t addr, uint32_t val, unsigned long long all) {
+    asm volatile("s_mov_b64 exec, %0\n\tds_write_b16 %1, %2\n\ts_mov_b64 exec, %3" : : "s"(mask), "v"(addr), "v"(val), "s"(all) : "memory");
+}
+// two such stores of one value (the two stacks of the compass loop) between one pair of EXEC writes
+__device__ __forceinline__ void lds_store2_u16_masked(unsigned long long mask0, uint32_t addr0, unsigned long long mask1, uint32_t addr1, uint32_t val,
+                                                      unsigned long long all) {
+    asm volatile("s_mov_b64 exec, %0\n\tds_write_b16 %1, %4\n\ts_mov_b64 exec, %2\n\tds_write_b16 %3, %4\n\ts_mov_b64 exec, %5"
+                 : : "s"(mask0), "v"(addr0), "s"(mask1), "v"(addr1), "v"(val), "s"(all) : "memory");
 }
 
 #define FAST_KEEP_WORDS 512   // strip_rows * bw <= 16384 candidate positions (mo_build_plan)
-#define FAST_STACK 384        // u16 entries per wavefront: two stacks of <= 191
+#define FAST_STACK 384        // u16 entries per wavefront: two stacks of <= 127 (sized for 191)
 #define FAST_NMS_Q 128        // u16 entries per wavefront: the phase-3 queue of <= 64 + 63 positions
 
 template <int TW, int NT>  // TW: LDS tile pitch, a compile-time constant so the 16 circle reads use immediate offsets; NT: threads
@@ -801,7 +814,7 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     constexpr int NW = NT / 64;
     __shared__ int s_wsum[NW];
     // per-wavefront stacks of the pixels that pass the compass pre-test (row << 12 | column): the darker-arc candidates grow
-    // up from [0], the brighter-arc candidates down from [FAST_STACK - 1]; each holds <= 63 + 128 entries
+    // up from [0], the brighter-arc candidates down from [FAST_STACK - 1]; each holds <= 63 + 64 entries
     __shared__ __attribute__((aligned(16))) uint16_t s_wq[NW][FAST_STACK];
     // bit (rr * bw + xx) set <=> border-region pixel survives the 3x3 NMS; overlays the stacks, which are dead by then, and is followed
     // there by the per-wavefront queues of phase 3
@@ -881,22 +894,30 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
     };
     {
         uint16_t* wq = s_wq[wv];
+        const uint32_t wq_lds = (uint32_t)(uintptr_t)wq;  // LDS byte address of this wavefront's stacks
+        const unsigned long long all = wave_exec();
         const int nxc = (SW + 63) >> 6;
         int qd = 0, qb = 0;  // wave-uniform stack fills (darker-arc / brighter-arc candidates)
-        // 64-pixel chunks of the scored rows, numbered row-major; each trip takes two of them (chunk c and c + 4).
-        // r*, j*, qd, qb are wave-uniform (scalar registers).
-        int ra = 0, ja = wv, rb = 0, jb = wv + NW;
-        while (ja >= nxc) { ja -= nxc; ra++; }
-        while (jb >= nxc) { jb -= nxc; rb++; }
+        // 64-pixel chunks of the scored rows, numbered row-major; wavefront wv takes chunks wv, wv + NW, ...  Everything that steers the
+        // loop is wave-uniform (scalar registers) and kept to a few scalar instructions per chunk: the chunk is tracked by ONE running
+        // offset a = row * TW + first column (the address of its windows in the tile), stepped by 64 * NW and compared with alast, the
+        // offset of the row's last chunk; the stack entries (row << xbits | column) are vd + a with the per-lane vd corrected at a row
+        // change; only a row's last chunk (a == alast) masks and clamps its lanes.
+        const int xrow = nxc << 6, xlast = xrow - 64;  // columns covered by a row's chunks; first column of its last chunk
+        const int remt = SW - xlast;                   // scored columns of the last chunk (1 .. 64)
+        const unsigned long long tail = remt >= 64 ? ~0ull : (1ull << remt) - 1ull;
+        int r = 0, x0 = wv << 6;
+        while (x0 >= xrow) { x0 -= xrow; r++; }
+        int a = r * TW + x0, alast = r * TW + xlast;
+        int vd = lane + (r << xbits) - r * TW;
         const int tv = t;
-        // branch-free: lanes past the last scored column read a clamped (valid) address and are masked out of the result;
         // the window base sits 3 rows and 3 columns before the pixel so that all five reads use non-negative immediates.
         // largest of the four adjacent-pair minima > t <=> two adjacent differences above t; smallest of the pair maxima < -t likewise
-        auto chunk = [&](int r, int j) {
-            const int x = (j << 6) + lane;
-            const int rem = SW - (j << 6);  // scored columns left from this chunk on (wave-uniform, >= 1)
-            const unsigned long long valid = rem >= 64 ? ~0ull : (1ull << rem) - 1ull;
-            const uint8_t* w = &s_tile[r * TW + lead + min(x, SW - 1)];
+        auto compass = [&](auto last, unsigned long long& md, unsigned long long& mb) {
+            int o = a + lane;
+            // branch-free last chunk: lanes past the last scored column read a clamped (valid) address and are masked out of the result
+            if constexpr (decltype(last)::value) o = min(o, alast + remt - 1);
+            const uint8_t* w = &s_tile[lead + o];
             const int v = w[3 * TW + 3];
             const int p0 = w[6 * TW + 3], p4 = w[3 * TW + 6], p8 = w[3], p12 = w[3 * TW];
             // two ADJACENT compass pixels (a 9-arc holds two or three consecutive multiples of 4; 0.62 instead of 0.67 survivors per pixel
@@ -904,28 +925,31 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
             // adjacent differences v - p above t; (largest of the adjacent-pair minima) > v + t likewise for the brighter side
             const int pair_hi = min16u(min16u(max16u(p0, p4), max16u(p4, p8)), min16u(max16u(p8, p12), max16u(p12, p0)));
             const int pair_lo = max16u(max16u(min16u(p0, p4), min16u(p4, p8)), max16u(min16u(p8, p12), min16u(p12, p0)));
-            const unsigned long long md = ballot_gt16(sub16(v, tv), pair_hi) & valid;  // centre above >= 2 compass pixels by more than t
-            const unsigned long long mb = ballot_gt16(pair_lo, add16(v, tv)) & valid;  // centre below >= 2 compass pixels by more than t
-            const uint32_t e = (uint32_t)((r << xbits) | x);
-            const uint32_t wq_lds = (uint32_t)(uintptr_t)wq;  // LDS byte address of this wavefront's stacks
-            lds_store_u16_masked(md, wq_lds + 2u * (uint32_t)(qd + __builtin_amdgcn_mbcnt_hi((unsigned)(md >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)md, 0u))), e);
-            qd += __popcll(md);
-            lds_store_u16_masked(mb, wq_lds + 2u * (uint32_t)(FAST_STACK - 1 - qb - (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb, 0u))), e);
-            qb += __popcll(mb);
+            md = ballot_gt16(sub16(v, tv), pair_hi);  // centre above >= 2 compass pixels by more than t
+            mb = ballot_gt16(pair_lo, add16(v, tv));  // centre below >= 2 compass pixels by more than t
+            if constexpr (decltype(last)::value) { md &= tail; mb &= tail; }
         };
-        while (ra < rows + 2) {
-            chunk(ra, ja);
-            if (rb < rows + 2) chunk(rb, jb);  // wave-uniform
-            if (qd >= 64 || qb >= 64) {
+        auto chunk = [&](auto last) {  // test the chunk at a, push its survivors, score 64 of them once a stack holds that many
+            unsigned long long md, mb;
+            compass(last, md, mb);
+            const uint32_t e = (uint32_t)(vd + a);
+            lds_store2_u16_masked(md, wq_lds + 2u * (uint32_t)(qd + __builtin_amdgcn_mbcnt_hi((unsigned)(md >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)md, 0u))),
+                                  mb, wq_lds + 2u * (uint32_t)(FAST_STACK - 1 - qb - (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb, 0u))),
+                                  e, all);
+            qd += __popcll(md);
+            qb += __popcll(mb);
+            if ((qd | qb) >= 64) {  // a stack holds <= 63 + 64 entries
                 replay::wave_sync();  // stack writes of this wavefront are visible to all its lanes
-                while (qd >= 64) { qd -= 64; score_one(wq[qd + lane], 0, true); }
-                while (qb >= 64) { qb -= 64; score_one(wq[FAST_STACK - 1 - qb - lane], 0xFF, true); }
+                if (qd >= 64) { qd -= 64; score_one(wq[qd + lane], 0, true); }
+                if (qb >= 64) { qb -= 64; score_one(wq[FAST_STACK - 1 - qb - lane], 0xFF, true); }
                 replay::wave_sync();  // the entries just read may be overwritten by the next pushes
             }
-            ja += 2 * NW;
-            while (ja >= nxc) { ja -= nxc; ra++; }
-            jb += 2 * NW;
-            while (jb >= nxc) { jb -= nxc; rb++; }
+        };
+        while (r < rows + 2) {
+            for (; a < alast; a += 64 * NW) chunk(std::false_type{});
+            if (a == alast) { chunk(std::true_type{}); a += 64 * NW; }
+            // next row(s): the offsets of a row's chunks are multiples of 64 apart, so a > alast <=> past the row
+            do { a += TW - xrow; alast += TW; vd += (1 << xbits) - TW; r++; } while (a > alast);
         }
         replay::wave_sync();
         // wave-uniform tails; lanes past a stack re-read its last entry
@@ -960,6 +984,7 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
         const uint32_t nq_lds = (uint32_t)(uintptr_t)nq;
         const int k_end = ((rows + 1) * SW + 3) >> 2;  // (<= the zero-filled dwords of the band)
         int qn = 0;  // wave-uniform queue fill
+        const unsigned long long all = wave_exec();
         for (int k0 = (SW >> 2) + (wv << 6); k0 < k_end; k0 += NT) {
             const int k = k0 + lane;
             const uint32_t w = k < k_end ? ((const uint32_t*)s_score)[k] : 0u;
@@ -967,7 +992,7 @@ __global__ __launch_bounds__(NT) void k_fast(Plan P, const uint32_t* __restrict_
             for (int bq = 0; bq < 4; bq++) {
                 const unsigned long long m = __ballot((w & (0xFFu << (8 * bq))) != 0u);
                 lds_store_u16_masked(m, nq_lds + 2u * (uint32_t)(qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))),
-                                     (uint32_t)(4 * k + bq));
+                                     (uint32_t)(4 * k + bq), all);
                 qn += __popcll(m);
                 if (qn >= 64) {  // wave-uniform
                     replay::wave_sync();
