@@ -81,10 +81,9 @@ template <class T> struct PinnedBuf {
 struct PlanBufs : PlanTables {
     int batch_alloc = 0;           // frames the work buffers below are sized for
     // the batched extraction's resize launches can write the blurred levels too (orb_plan_resize_blur held for every level at
-    // the pipeline's margins rb_pyr_margin / rb_margin)
+    // the pipeline's margins rb_pyr_margin / rb_margin, the ones the tile records are built for)
     bool rb_ok = false;
-    int rb_margin = -1, rb_pyr_margin = -1;
-    DevBuf<uint32_t> d_tables;     // the block of plan_build_tables: the offsets of PlanTables index it
+    DevBuf<uint32_t> d_tables;     // the block of plan_build_tables and, behind it at word tile_rec, the tile records: the offsets of PlanTables index it
     DevBuf<uint8_t> d_pyr;         // [batch][pyr_stride]
     DevBuf<uint8_t> d_blur;        // [batch][blur_stride]
     DevBuf<uint32_t> d_cand;       // [batch][cand_stride]
@@ -307,9 +306,6 @@ int orb_launch_ingest(mo_ctx* c, const uint8_t* src_mapped, int w, int h, int ch
 // blur_margin >= 0: the resize launches may also write the blurred levels 0 .. nlevels-2 (*blurred says whether they did)
 int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels, int margin, int blur_margin = -1,
                        bool* blurred = nullptr);
-// plan time (ctx.hip): whether that blurring resize of level L covers level L-1's blur region at these margins
-// (xp / yp: the level's packed column / row coefficients, nx / ny entries)
-bool orb_plan_resize_blur(const Plan& P, int L, const uint32_t* xp, size_t nx, const uint32_t* yp, size_t ny, int margin, int blur_margin);
 // front_single.hip: pyramid + blur of a few frames in ONE launch (single-frame calls); fs_build runs with the plan and leaves
 // c->fs_ok false for geometries it does not cover, which keep orb_launch_pyramid + orb_launch_blur
 #define MO_FS_MAX_BATCH 2

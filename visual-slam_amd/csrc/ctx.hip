@@ -200,19 +200,18 @@ static int fill_plan(mo_ctx* c, const mo_orb_params* p, int w, int h, int batch)
     const char* why = "";
     if (int rc = plan_geometry(P, pb, p, w, h, c->max_batch, c->fin_slack, &why)) return mo_fail(c, rc, why);
 
-    // the tables: one block, one upload
-    std::vector<uint32_t> blk;
+    // the tables and, behind them, the tile records (at the margins of the batched pipeline): one buffer, one upload
+    std::vector<uint32_t> blk, rec;
     plan_build_tables(P, pb, blk);
+    plan_build_tile_records(P, pb, blk, mo_pyr_margin(P.edge_threshold), mo_blur_margin(P.edge_threshold), rec);
+    const int nl = P.nlevels;
+    pb.rb_ok = nl >= 2;
+    for (int L = 1; L < nl && pb.rb_ok; L++) pb.rb_ok = pb.rs[L].two_pass_ok && orb_plan_resize_blur(P, pb, L, rec.data());
+    pb.tile_rec = (uint32_t)mo_align(blk.size(), 64);
+    blk.resize(pb.tile_rec, 0u);
+    blk.insert(blk.end(), rec.begin(), rec.end());
     int rc;
     if ((rc = pb.d_tables.upload(c, blk))) return rc;
-    const int nl = P.nlevels;
-    pb.rb_margin = mo_blur_margin(P.edge_threshold);
-    pb.rb_pyr_margin = mo_pyr_margin(P.edge_threshold);
-    pb.rb_ok = nl >= 2;
-    for (int L = 1; L < nl && pb.rb_ok; L++) {
-        const PlanTables::Resize& t = pb.rs[L];
-        pb.rb_ok = t.two_pass_ok && orb_plan_resize_blur(P, L, &blk[t.xpk], t.ypk - t.xpk, &blk[t.ypk], t.xofs - t.ypk, pb.rb_pyr_margin, pb.rb_margin);
-    }
 
     // work buffers for `batch` frames
     size_t B = (size_t)batch;

@@ -119,8 +119,7 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b), c, false);
 }
 
-#define RS_TW 64
-#define RS_TH 64
+// (RS_TW x RS_TH output pixels per tile: plan_tables.h)
 #define RS_SRC_ROWS 136   // source rows a 64-row output tile can touch (scale <= 2) + 1
 #define RS_SRC_PITCH 144  // source columns a 64-column output tile can touch (scale <= 2) + alignment lead-in
 
@@ -303,6 +302,9 @@ __device__ __forceinline__ void blur_col_quad(const uint32_t* sr, int pitch, uin
 // Blurring form of k_resize2 (RS2_BLUR = true): the launch of level L also writes the blurred level L-1.  Workgroup (bx, by) owns
 // rows [ypk[ty0] & 0x7FFF, the same for by + 1) and 4-aligned columns [xpk[tx0] & 0x7FFC, the same for bx + 1) of level L-1; the
 // first and last row / column of workgroups stretch to the blur region [margin, size - margin), so the partitions tile it exactly.
+// All of that is a function of (level, tile): the plan states it once per tile (plan_build_tile_records, plan_tables.h) and the
+// workgroup fetches its record (RBR_*) with one wave-uniform load, where it used to derive it from six dependent table reads and
+// some 160 scalar instructions per wavefront (profiles/tile_records_floor_before.txt).
 // The workgroup stages ONE raw window of level L-1 in LDS - the union of its partition plus the 3-px blur halo (REFLECT_101 at the
 // level border, as k_blur) and the source rows / columns of its resize tile - and both the resize and the blur's row pass read it.
 // Phases (two barriers): stage | resize straight from the window -> level L, blur row pass -> s_row | blur column pass -> blur L-1.
@@ -312,17 +314,15 @@ __device__ __forceinline__ void blur_col_quad(const uint32_t* sr, int pitch, uin
 // side (two barriers, 33.8 KB, 4 instead of 7 waves per SIMD) 0.04 ms slower - these short-lived workgroups need the occupancy.
 // orb_plan_resize_blur (host) proves for every tile of the plan that the window and partition fit the buffers below; a plan that
 // fails it keeps the unfused k_resize2 + k_blur.
-#define RB_PW 80                      // partition columns (multiple of 4)
-#define RB_PH 80                      // partition rows
-#define RB_WR 88                      // window rows
-#define RB_WP 96                      // window pitch in bytes: window columns + 8 (the resize's third dword may run past it)
+// (RB_PW, RB_PH, RB_WR, RB_WP: plan_tables.h, where the records are built)
 #define RB_SR_BYTES ((RB_PH / 2 + 4) * RB_PW * 4)  // s_row: [row pair][column] u32, partition + 6 halo rows (+ 1 for an odd count)
 struct __attribute__((packed, aligned(4))) Dwords4 { uint32_t x, y, z, w; };  // 16 bytes at dword alignment: one load on this target
 struct BlurOut {
     uint8_t* dst;      // blurred level L-1 of frame 0
     size_t fstride;    // bytes per frame
-    int pitch, margin;
+    int pitch;
     uint32_t taps;     // g0 | g1 << 8 | g2 << 16 | g3 << 24
+    const uint32_t* rec;  // the level's tile records, RB_REC_WORDS words per tile of the launch grid (64-byte aligned)
 };
 
 template <bool RS2_BLUR>
@@ -334,35 +334,24 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
     if constexpr (RS2_BLUR) {
         __shared__ __attribute__((aligned(16))) uint8_t s_px[RB_WR * RB_WP];
         __shared__ __attribute__((aligned(16))) uint32_t s_row[RB_SR_BYTES / 4];
-        int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-        {  // XCD affinity (speed only), as below
-            int rem;
-            xcd_map(bx + gridDim.x * (by + gridDim.y * bz), gridDim.x * gridDim.y, inv_per, gridDim.z, bz, rem);
-            by = (int)(inv_gx ? __umulhi((uint32_t)rem, inv_gx) : (uint32_t)rem);
-            bx = rem - by * (int)gridDim.x;
-        }
-        const int tx0 = org + bx * RS_TW, ty0 = org + by * RS_TH;
-        // resize tile: source rows [sy0, sy1], source columns [ab0, ax1) (the tables are padded with their last entry)
-        const uint32_t ey0 = ypk[ty0], ey1 = ypk[ty0 + RS_TH - 1], ex1 = xpk[tx0 + RS_TW - 1];
-        const int sy0 = (int)(ey0 & 0x7FFFu), sy1 = (int)(ey1 & 0x7FFFu) + (int)((ey1 >> 15) & 1u);
-        const int ab0 = (int)(xpk[tx0] & 0x7FFCu), ax1 = (int)(ex1 & 0x7FFFu) + (int)((ex1 >> 15) & 1u) + 1;
-        // blur partition of level L-1 and the staged window
-        const int bm = bo.margin;
-        const int r0 = by == 0 ? bm : sy0, r1 = by == (int)gridDim.y - 1 ? sh - bm : (int)(ypk[ty0 + RS_TH] & 0x7FFFu);
-        const int c0 = bx == 0 ? bm : ab0, c1 = bx == (int)gridDim.x - 1 ? (sw - bm + 3) & ~3 : (int)(xpk[tx0 + RS_TW] & 0x7FFCu);
-        const int wy0 = min(r0 - 3, sy0), wy1 = max(r1 + 3, sy1 + 1);
-        const int wx0 = min(c0 - 4, ab0), wx1 = max(c1 + 4, (ax1 + 3) & ~3);
-        const int nwr = wy1 - wy0, ndw = (wx1 - wx0) >> 2;
+        int bz, tile;
+        xcd_map(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.x * gridDim.y, inv_per, gridDim.z, bz, tile);  // XCD affinity (speed only), as below
+        // the tile's record: resize tile, blur partition of level L-1 and the staged window
+        const uint4* const rp = (const uint4*)__builtin_assume_aligned(bo.rec, 64) + (RB_REC_WORDS / 4) * tile;
+        const uint4 ra = rp[0], rb = rp[1], rc = rp[2], rd = rp[3];  // TX0 TY0 GOFF GEO | FLG LDS_RS LDS_ROW R | C Q INVQ W0 | SRC0 SRC1 BOUT NT
+        static_assert(RBR_GEO == 3 && RBR_R == 7 && RBR_W0 == 11 && RBR_NT == 15 && RB_REC_WORDS == 16, "the record's words as read here");
+        const int tx0 = (int)ra.x, ty0 = (int)ra.y;
+        const int nwr = (int)(ra.w & 0xFFFFu), np16 = (int)(rb.x & 0xFFu);
+        const int lds_rs = (int)rb.y;
         const uint8_t* img = src + (size_t)bz * src_fstride;
         const int cg = tid & 15, rr = tid >> 4;
         const uint4 xe = *(const uint4*)(xpk + tx0 + 4 * cg);
         uint32_t ye[RS_TH / 16];
 #pragma unroll
         for (int half = 0; half < RS_TH / 16; half++) ye[half] = ypk[ty0 + rr + 16 * half];
-        const bool inside = wy0 >= 0 && wy1 <= sh && wx0 >= 0 && wx1 <= sw;
-        const int np16 = (ndw + 3) >> 2;  // 16-byte pieces per window row (<= RB_WP / 16: ndw <= RB_WP / 4 - 2)
-        if (inside && wx0 + 16 * np16 <= spitch) {
-            // stage, the window inside the level (block-uniform; every tile of a plan whose blur margin is >= 3): 8 lanes per row, one
+        if (rb.x & 0x100u) {  // the record's interior flag; np16: 16-byte pieces per window row (<= RB_WP / 16: ndw <= RB_WP / 4 - 2)
+            // stage, every byte a value depends on inside the level and every piece inside its row's pitch (the record's interior flag;
+            // block-uniform; at a blur margin >= 3 every tile but the last-column ones whose last piece would leave the pitch): 8 lanes per row, one
             // 16-byte piece each (dword-aligned loads, 16-byte aligned LDS stores), 32 rows per trip.  Row and piece are split once per
             // thread; a trip adds a constant stride.  The last piece may run <= 12 bytes past the window, inside the row's pitch and
             // inside the LDS row (bytes nothing reads).
@@ -370,7 +359,7 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
             static_assert(RB_WP % 16 == 0 && RB_WP / 16 <= 8, "a window row is at most 8 pieces of 16 bytes");
             const int p = tid & 7, r = tid >> 3;
             const int rows_left = p < np16 ? nwr - r : 0;
-            const uint32_t goff = (uint32_t)((wy0 + r) * spitch + wx0 + 16 * p);
+            const uint32_t goff = ra.z + (uint32_t)(r * spitch + 16 * p);
             uint8_t* const lrow = s_px + r * RB_WP + 16 * p;
             Dwords4 v[TRIPS];
 #pragma unroll
@@ -381,6 +370,8 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
                 if (32 * t < rows_left) *(uint4*)(lrow + 32 * t * RB_WP) = make_uint4(v[t].x, v[t].y, v[t].z, v[t].w);
         } else {  // stage, a window that leaves the level: all loads of a thread issued before the first LDS store (one global round trip)
             constexpr int TRIPS = (RB_WR * (RB_WP / 4 - 2) + 255) / 256;
+            const int ndw = (int)(ra.w >> 16), wy0 = (int)(short)(rc.w & 0xFFFFu), wx0 = (int)rc.w >> 16;
+            const bool inside = (rb.x & 0x200u) != 0;
             const uint32_t inv = 0x100000u / (uint32_t)ndw + 1u;  // i / ndw, exact while i * ndw < 2^20
             uint32_t v[TRIPS];
 #pragma unroll
@@ -423,25 +414,25 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
                 coef[k] = (256u - c1k) | (c1k << 16);
             }
             const int x = tx0 + 4 * cg;
-            const uint32_t* pw = (const uint32_t*)(s_px + (ab - wx0));
+            const int pwo = lds_rs + ab;  // level pixel (y, ab) lies at byte pwo + y * RB_WP of the window
 #pragma unroll
             for (int half = 0; half < RS_TH / 16; half++) {
                 const int y = ty0 + rr + 16 * half;
                 if (x >= dw || y >= dh) break;
                 const uint32_t e = ye[half];
-                const int oy = (int)(e & 0x7FFFu) - wy0, oy1 = oy + (int)((e >> 15) & 1u);
-                const uint32_t* p0 = pw + oy * (RB_WP / 4);
-                const uint32_t* p1 = pw + oy1 * (RB_WP / 4);
+                const int oy = (int)(e & 0x7FFFu), oy1 = oy + (int)((e >> 15) & 1u);
+                const uint32_t* p0 = (const uint32_t*)(s_px + (pwo + oy * RB_WP));
+                const uint32_t* p1 = (const uint32_t*)(s_px + (pwo + oy1 * RB_WP));
                 const uint2 a = rs2_hrow(p0[0], p0[1], p0[2], sh8, sel, coef), b = rs2_hrow(p1[0], p1[1], p1[2], sh8, sel, coef);
                 *(uint32_t*)(dst + (size_t)bz * dst_fstride + (size_t)y * dpitch + x) = rs2_vrow(a, b, e);
             }
         }
         const uint32_t g0 = bo.taps & 255u, g1 = (bo.taps >> 8) & 255u, g2 = (bo.taps >> 16) & 255u, g3 = bo.taps >> 24;
-        const int nq = (c1 - c0) >> 2, npr = (r1 - r0 + 7) >> 1, nop = (r1 - r0 + 1) >> 1;  // quads, row pairs in, row pairs out
-        const uint32_t invq = 0x100000u / (uint32_t)max(nq, 1) + 1u;
+        const int nq = (int)(rc.y & 0xFFu), nrow = (int)(rd.w & 0xFFFFu), ncol = (int)(rd.w >> 16);  // quads per row; items of the row / column pass
+        const uint32_t invq = rc.z;
         {  // blur row pass: s_px row (r0 - 3 - wy0) + j <-> level row r0 - 3 + j; byte 0 of a quad's first dword: its column - 4
-            const uint8_t* base = s_px + (r0 - 3 - wy0) * RB_WP + (c0 - 4 - wx0);
-            for (int t = tid; t < npr * nq; t += 256) {
+            const uint8_t* base = s_px + rb.z;
+            for (int t = tid; t < nrow; t += 256) {
                 const int p = (int)(((uint32_t)t * invq) >> 20), q = t - p * nq;
                 const uint32_t* pw = (const uint32_t*)(base + 2 * p * RB_WP + 4 * q);
                 *(uint4*)(s_row + p * RB_PW + 4 * q) = blur_row_quad(pw, pw + RB_WP / 4, g0, g1, g2, g3);
@@ -449,15 +440,15 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
         }
         __syncthreads();
         {  // blur column pass
-            uint8_t* out0 = bo.dst + (size_t)bz * bo.fstride;
-            for (int t = tid; t < nop * nq; t += 256) {
+            uint8_t* out0 = bo.dst + (size_t)bz * bo.fstride + rd.z;  // the partition's first output, level row r0
+            const int nr = (int)(rb.w >> 16) - (int)(rb.w & 0xFFFFu);  // partition rows r1 - r0
+            for (int t = tid; t < ncol; t += 256) {
                 const int p = (int)(((uint32_t)t * invq) >> 20), q = t - p * nq;
                 uint32_t pe, po;
                 blur_col_quad(s_row + p * RB_PW + 4 * q, RB_PW, g0, g1, g2, g3, pe, po);
-                const int y = r0 + 2 * p;
-                uint8_t* out = out0 + (size_t)y * bo.pitch + c0 + 4 * q;  // pitch is a multiple of 16 >= w: <= 3 bytes of row padding
+                uint8_t* out = out0 + (size_t)(2 * p) * bo.pitch + 4 * q;  // pitch is a multiple of 16 >= w: <= 3 bytes of row padding
                 *(uint32_t*)out = pe;
-                if (y + 1 < r1) *(uint32_t*)(out + bo.pitch) = po;
+                if (2 * p + 1 < nr) *(uint32_t*)(out + bo.pitch) = po;
             }
         }
         return;
@@ -526,39 +517,7 @@ __global__ __launch_bounds__(256) void k_resize2(const uint8_t* __restrict__ src
     }
 }
 
-// margin: only [margin, w - margin) x [margin, h - margin) of levels 1.. is produced (a multiple of 4).  The pipeline passes
-// the blur's margin - 4 (8 at edge_threshold 31): FAST stages from column 16 / row 27, the Harris and orientation windows stay
-// 16 px inside, the blur tiling starts at 12 and reads from 8, and the next level's [8, ..) only needs this level's [9, ..).
-// compute() with caller keypoints and the probes pass 0.
-static int resize_org(const LevelInfo& d, int margin) { return (d.w > 2 * margin + 8 && d.h > 2 * margin + 8) ? margin : 0; }
-
-// Plan time: does the blurring form of k_resize2 cover level L - 1's blur region [blur_margin, size - blur_margin) at this
-// geometry, with every window and partition inside RB_*?  Rows and columns are independent; this restates the kernel's prologue.
-bool orb_plan_resize_blur(const Plan& P, int L, const uint32_t* xp, size_t nx, const uint32_t* yp, size_t ny, int margin, int blur_margin) {
-    const LevelInfo& s = P.lv[L - 1];
-    const LevelInfo& d = P.lv[L];
-    const int bm = blur_margin, org = resize_org(d, margin);
-    if (bm < 0 || (bm & 3)) return false;
-    const int gx = (d.w - 2 * org + RS_TW - 1) / RS_TW, gy = (d.h - 2 * org + RS_TH - 1) / RS_TH;
-    if (gx < 1 || gy < 1 || (size_t)(org + gx * RS_TW + 1) > nx || (size_t)(org + gy * RS_TH + 1) > ny) return false;
-    for (int by = 0; by < gy; by++) {
-        const int ty0 = org + by * RS_TH;
-        const uint32_t ey1 = yp[ty0 + RS_TH - 1];
-        const int sy0 = (int)(yp[ty0] & 0x7FFFu), sy1 = (int)(ey1 & 0x7FFFu) + (int)((ey1 >> 15) & 1u);
-        const int r0 = by == 0 ? bm : sy0, r1 = by == gy - 1 ? s.h - bm : (int)(yp[ty0 + RS_TH] & 0x7FFFu);
-        const int wy0 = std::min(r0 - 3, sy0), wy1 = std::max(r1 + 3, sy1 + 1);
-        if (r1 <= r0 || r1 - r0 > RB_PH || wy1 - wy0 > RB_WR || r1 + 4 - wy0 > RB_WR || sy1 >= s.h) return false;
-    }
-    for (int bx = 0; bx < gx; bx++) {
-        const int tx0 = org + bx * RS_TW;
-        const uint32_t ex1 = xp[tx0 + RS_TW - 1];
-        const int ab0 = (int)(xp[tx0] & 0x7FFCu), ax1 = (int)(ex1 & 0x7FFFu) + (int)((ex1 >> 15) & 1u) + 1;
-        const int c0 = bx == 0 ? bm : ab0, c1 = bx == gx - 1 ? (s.w - bm + 3) & ~3 : (int)(xp[tx0 + RS_TW] & 0x7FFCu);
-        const int wx0 = std::min(c0 - 4, ab0), wx1 = std::max(c1 + 4, (ax1 + 3) & ~3);
-        if (c1 <= c0 || c1 - c0 > RB_PW || wx1 - wx0 + 8 > RB_WP || ax1 > s.w) return false;
-    }
-    return true;
-}
+// (resize_org, the margin of the level nothing reads, and orb_plan_resize_blur, the plan-time check of the blurring form: plan_tables.h)
 
 // blur_margin >= 0 (the batched extraction with descriptors): when the plan allows it (c->pb.rb_ok, orb_plan_resize_blur at this
 // blur margin) and every level takes k_resize2, the launch of level L also writes the blurred level L - 1 and *blurred is set; the
@@ -585,7 +544,7 @@ int orb_launch_pyramid(mo_ctx* c, const uint8_t* d_gray, int batch, int nlevels,
         const uint32_t per = grid.x * grid.y, inv_per = per > 1 ? 0xFFFFFFFFu / per + 1u : 0u, inv_gx = grid.x > 1 ? 0xFFFFFFFFu / grid.x + 1u : 0u;
         const bool al4 = al4_of(L);
         if (fuse) {
-            const BlurOut bo{c->pb.d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, blur_margin, taps};
+            const BlurOut bo{c->pb.d_blur + s.boff, (size_t)P.blur_stride, s.bpitch, taps, tb + c->pb.tile_rec + c->pb.rb[L].rec};
             hipLaunchKernelGGL(k_resize2<true>, grid, dim3(256), 0, c->stream, src, sfs, s.pitch, s.w, s.h, c->pb.d_pyr + d.off,
                                (size_t)P.pyr_stride, d.pitch, d.w, d.h, tb + t.xpk, tb + t.ypk, inv_per, inv_gx, org, bo);
         } else if (al4 && t.two_pass_ok)

@@ -4,8 +4,9 @@
 // sizes, per-level quotas, the circular-patch umax table, the INTER_LINEAR_EXACT coefficient tables, the quantised Gaussian taps), in
 // the same float/double expressions cv2 uses (reference call site: src/orbslam2/extractor.py:38-48,65), and the tables and constants
 // of this library's own launches.  plan_geometry fills the Plan (a kernel argument) and the launch constants, plan_build_tables
-// appends every lookup table to ONE block of 32-bit words and records where each starts.  Plain C++ without a HIP call: fill_plan
-// (ctx.hip) uploads the block, tests/native/plan_check.cpp walks it on the CPU.
+// appends every lookup table to ONE block of 32-bit words and records where each starts, plan_build_tile_records writes the per-tile
+// records of the blurring k_resize2 into a second vector.  Plain C++ without a HIP call: fill_plan (ctx.hip) uploads the block with the
+// records behind it, tests/native/plan_check.cpp and tests/native/tile_records_check.cpp walk them on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -37,6 +38,36 @@
 #ifndef DT_SPLIT_LATENCY
 #define DT_SPLIT_LATENCY 4           // workgroups per describe tile in calls on one or two frames (a power of two)
 #endif
+#define RS_TW 64   // k_resize2 / k_resize: output tile of one workgroup
+#define RS_TH 64
+// the blurring form of k_resize2 (orb_kernels.hip): the partition of level L-1 one workgroup blurs and the window it stages
+#define RB_PW 80                      // partition columns (multiple of 4)
+#define RB_PH 80                      // partition rows
+#define RB_WR 88                      // window rows
+#define RB_WP 96                      // window pitch in bytes: window columns + 8 (the resize's third dword may run past it)
+
+// One record per workgroup of the blurring k_resize2: what that kernel's prologue derived from its arguments and six dependent reads of
+// xpk / ypk, for every (level L >= 1, tile by * gx + bx of the launch grid).  A function of the plan alone, so plan_build_tile_records states
+// it once and the kernel fetches its record with one wave-uniform 64-byte load.  Words:
+#define RB_REC_WORDS 16
+enum {
+    RBR_TX0, RBR_TY0,  // first output column / row of the resize tile
+    RBR_GOFF,          // byte offset of the window's first pixel in level L-1: wy0 * pitch + wx0
+    RBR_GEO,           // window rows nwr | window dwords per row ndw << 16
+    RBR_FLG,           // 16-byte pieces per window row np16 | interior << 8 (the 16-byte staging form: see plan_build_tile_records) | inside << 9
+                       // (the whole window inside the level: the dword staging form needs no REFLECT_101)
+    RBR_LDS_RS,        // level pixel (y, x) lies at byte LDS_RS + y * RB_WP + x of the window buffer: -(wy0 * RB_WP + wx0)
+    RBR_LDS_ROW,       // byte offset in the window buffer of the blur row pass' first dword: (r0 - 3 - wy0) * RB_WP + (c0 - 4 - wx0)
+    RBR_R, RBR_C,      // blur partition rows r0 | r1 << 16 and columns c0 | c1 << 16 (signed halves: rbr_lo / rbr_hi)
+    RBR_Q,             // quads per partition row nq | row pairs in npr << 8 | row pairs out nop << 16
+    RBR_INVQ,          // 2^20 / nq + 1: (t * invq) >> 20 == t / nq for t < npr * nq
+    RBR_W0,            // window origin wy0 | wx0 << 16 (signed halves)
+    RBR_SRC0, RBR_SRC1,  // source rows / columns of the resize tile: sy0 | ab0 << 16, sy1 | ax1 << 16
+    RBR_BOUT,          // byte offset of the partition's first output in the blurred level L-1: r0 * bpitch + c0
+    RBR_NT             // work items of the row pass npr * nq | of the column pass nop * nq << 16
+};
+static inline int rbr_lo(uint32_t v) { return (int)(int16_t)(v & 0xFFFFu); }
+static inline int rbr_hi(uint32_t v) { return (int)(int16_t)(v >> 16); }
 
 // per-level geometry, uploaded by value as a kernel argument
 struct LevelInfo {
@@ -99,6 +130,11 @@ struct PlanTables {
     uint32_t strip_tab = 0;                    // k_fast: strip of a frame -> level | strip of the level << 8
     uint32_t dtile_tab = 0, dtile_icw = 0;     // k_describe_tiles: tile -> level | column << 8 | row << 20; the intensity-centroid weights [32 rows][8 weight + 8 mask dwords]
     int n_dtiles = 0;
+    // the tile records (plan_build_tile_records), uploaded behind the block: tile_rec is their word offset in that buffer, rb[L].rec the
+    // word offset of level L's gx * gy resize/blur records among them (no records: gx = gy = 0), built for the margins rb_pyr_margin / rb_margin
+    uint32_t tile_rec = 0;
+    struct RbLevel { uint32_t rec = 0; int gx = 0, gy = 0, org = 0; } rb[MO_MAX_LEVELS];
+    int rb_margin = -1, rb_pyr_margin = -1;
 };
 
 static inline int cv_round_f(float v) { return (int)lrintf(v); }
@@ -323,4 +359,101 @@ inline void plan_build_tables(const Plan& P, PlanTables& T, std::vector<uint32_t
             blk[T.dtile_icw + r * 16 + 8 + c4] = mv;
         }
     }
+}
+
+// margin: only [margin, w - margin) x [margin, h - margin) of levels 1.. is produced (a multiple of 4).  The pipeline passes
+// the blur's margin - 4 (8 at edge_threshold 31): FAST stages from column 16 / row 27, the Harris and orientation windows stay
+// 16 px inside, the blur tiling starts at 12 and reads from 8, and the next level's [8, ..) only needs this level's [9, ..).
+// compute() with caller keypoints and the probes pass 0.
+static inline int resize_org(const LevelInfo& d, int margin) { return (d.w > 2 * margin + 8 && d.h > 2 * margin + 8) ? margin : 0; }
+
+// The resize/blur records of every level L >= 1 (RBR_* above) appended to out, level-major, tile by * gx + bx within a level, for a
+// pipeline that produces the pyramid from pyr_margin and blurs from blur_margin; blk: the block of plan_build_tables (xpk / ypk).  Workgroup
+// (bx, by) of the launch of level L owns rows [ypk[ty0] & 0x7FFF, the same for by + 1) and 4-aligned columns [xpk[tx0] & 0x7FFC, the same for
+// bx + 1) of level L-1; the first and last row / column of workgroups stretch to the blur region, so the partitions tile it.  Its window is
+// the union of the partition plus the blur halo (3 rows, 4 columns) and the source rows / columns of its resize tile.  Rows and columns are
+// independent.  A level whose tables do not hold the tiling, or a margin the form does not take, gets no records.
+inline void plan_build_tile_records(const Plan& P, PlanTables& T, const std::vector<uint32_t>& blk, int pyr_margin, int blur_margin,
+                                    std::vector<uint32_t>& out) {
+    out.clear();
+    T.rb_margin = blur_margin; T.rb_pyr_margin = pyr_margin;
+    const int bm = blur_margin;
+    for (int L = 0; L < MO_MAX_LEVELS; L++) T.rb[L] = PlanTables::RbLevel();
+    for (int L = 1; L < P.nlevels; L++) {
+        const LevelInfo &s = P.lv[L - 1], &d = P.lv[L];
+        const PlanTables::Resize& t = T.rs[L];
+        const uint32_t *xp = &blk[t.xpk], *yp = &blk[t.ypk];
+        const size_t nx = t.ypk - t.xpk, ny = t.xofs - t.ypk;
+        PlanTables::RbLevel& rl = T.rb[L];
+        const int org = rl.org = resize_org(d, pyr_margin);
+        const int gx = (d.w - 2 * org + RS_TW - 1) / RS_TW, gy = (d.h - 2 * org + RS_TH - 1) / RS_TH;
+        if (bm < 0 || (bm & 3) || gx < 1 || gy < 1 || (size_t)(org + gx * RS_TW + 1) > nx || (size_t)(org + gy * RS_TH + 1) > ny) continue;
+        rl.rec = (uint32_t)out.size(); rl.gx = gx; rl.gy = gy;
+        struct Axis { int t0, s0, s1, p0, p1, w0, w1; };  // tile start, source span [s0, s1], partition [p0, p1), window [w0, w1)
+        std::vector<Axis> ys((size_t)gy), xs((size_t)gx);
+        for (int by = 0; by < gy; by++) {
+            Axis& a = ys[(size_t)by];
+            a.t0 = org + by * RS_TH;
+            const uint32_t ey1 = yp[a.t0 + RS_TH - 1];
+            a.s0 = (int)(yp[a.t0] & 0x7FFFu); a.s1 = (int)(ey1 & 0x7FFFu) + (int)((ey1 >> 15) & 1u);
+            a.p0 = by == 0 ? bm : a.s0; a.p1 = by == gy - 1 ? s.h - bm : (int)(yp[a.t0 + RS_TH] & 0x7FFFu);
+            a.w0 = std::min(a.p0 - 3, a.s0); a.w1 = std::max(a.p1 + 3, a.s1 + 1);
+        }
+        for (int bx = 0; bx < gx; bx++) {
+            Axis& a = xs[(size_t)bx];
+            a.t0 = org + bx * RS_TW;
+            const uint32_t ex1 = xp[a.t0 + RS_TW - 1];
+            a.s0 = (int)(xp[a.t0] & 0x7FFCu); a.s1 = (int)(ex1 & 0x7FFFu) + (int)((ex1 >> 15) & 1u) + 1;  // [ab0, ax1)
+            a.p0 = bx == 0 ? bm : a.s0; a.p1 = bx == gx - 1 ? (s.w - bm + 3) & ~3 : (int)(xp[a.t0 + RS_TW] & 0x7FFCu);
+            a.w0 = std::min(a.p0 - 4, a.s0); a.w1 = std::max(a.p1 + 4, (a.s1 + 3) & ~3);
+        }
+        auto pack = [](int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); };
+        for (int by = 0; by < gy; by++)
+            for (int bx = 0; bx < gx; bx++) {
+                const Axis &y = ys[(size_t)by], &x = xs[(size_t)bx];
+                const int nwr = y.w1 - y.w0, ndw = (x.w1 - x.w0) >> 2, np16 = (ndw + 3) >> 2;
+                const bool inside = y.w0 >= 0 && y.w1 <= s.h && x.w0 >= 0 && x.w1 <= s.w;
+                // the 16-byte staging form copies level bytes as they lie: its rows must be rows of the level, its pieces end inside the row's
+                // pitch, and every byte a value depends on - the taps of the partition's last column x.p1 - 1, the resize's source columns
+                // below x.s1 - must be a pixel.  The window itself is rounded up to dwords and may run <= 3 bytes past the level's width
+                // into the row's padding (the last tile column of a level whose width is no multiple of 4): bytes no value depends on.
+                const bool interior = y.w0 >= 0 && y.w1 <= s.h && x.w0 >= 0 && x.w0 + 16 * np16 <= s.pitch && std::max(x.p1 + 3, x.s1) <= s.w;
+                const int nq = (x.p1 - x.p0) >> 2, npr = (y.p1 - y.p0 + 7) >> 1, nop = (y.p1 - y.p0 + 1) >> 1;  // quads, row pairs in, row pairs out
+                uint32_t r[RB_REC_WORDS];
+                r[RBR_TX0] = (uint32_t)x.t0; r[RBR_TY0] = (uint32_t)y.t0;
+                r[RBR_GOFF] = (uint32_t)(y.w0 * s.pitch + x.w0);
+                r[RBR_GEO] = pack(nwr, ndw);
+                r[RBR_FLG] = ((uint32_t)np16 & 0xFFu) | (interior ? 1u << 8 : 0u) | (inside ? 1u << 9 : 0u);
+                r[RBR_LDS_RS] = (uint32_t)(-(y.w0 * RB_WP + x.w0));
+                r[RBR_LDS_ROW] = (uint32_t)((y.p0 - 3 - y.w0) * RB_WP + (x.p0 - 4 - x.w0));
+                r[RBR_R] = pack(y.p0, y.p1); r[RBR_C] = pack(x.p0, x.p1);
+                r[RBR_Q] = ((uint32_t)nq & 0xFFu) | (((uint32_t)npr & 0xFFu) << 8) | ((uint32_t)nop << 16);
+                r[RBR_INVQ] = 0x100000u / (uint32_t)std::max(nq, 1) + 1u;
+                r[RBR_W0] = pack(y.w0, x.w0);
+                r[RBR_SRC0] = pack(y.s0, x.s0); r[RBR_SRC1] = pack(y.s1, x.s1);
+                r[RBR_BOUT] = (uint32_t)(y.p0 * s.bpitch + x.p0);
+                r[RBR_NT] = pack(npr * nq, nop * nq);
+                out.insert(out.end(), r, r + RB_REC_WORDS);
+            }
+    }
+}
+
+// Plan time: does the blurring form of k_resize2 cover level L - 1's blur region [rb_margin, size - rb_margin) at this geometry, with
+// every window and partition inside RB_*?  Read from the records the kernel will read (rec: the vector of plan_build_tile_records); a
+// level without records fails.
+inline bool orb_plan_resize_blur(const Plan& P, const PlanTables& T, int L, const uint32_t* rec) {
+    const LevelInfo& s = P.lv[L - 1];
+    const PlanTables::RbLevel& rl = T.rb[L];
+    if (rl.gx < 1 || rl.gy < 1) return false;
+    for (int by = 0; by < rl.gy; by++) {  // (rows: the same in every record of a tile row)
+        const uint32_t* r = rec + rl.rec + (size_t)by * rl.gx * RB_REC_WORDS;
+        const int r0 = rbr_lo(r[RBR_R]), r1 = rbr_hi(r[RBR_R]), wy0 = rbr_lo(r[RBR_W0]), nwr = rbr_lo(r[RBR_GEO]), sy1 = rbr_lo(r[RBR_SRC1]);
+        if (r1 <= r0 || r1 - r0 > RB_PH || nwr > RB_WR || r1 + 4 - wy0 > RB_WR || sy1 >= s.h) return false;
+    }
+    for (int bx = 0; bx < rl.gx; bx++) {
+        const uint32_t* r = rec + rl.rec + (size_t)bx * RB_REC_WORDS;
+        const int c0 = rbr_lo(r[RBR_C]), c1 = rbr_hi(r[RBR_C]), ndw = rbr_hi(r[RBR_GEO]), ax1 = rbr_hi(r[RBR_SRC1]);
+        if (c1 <= c0 || c1 - c0 > RB_PW || 4 * ndw + 8 > RB_WP || ax1 > s.w) return false;
+    }
+    return true;
 }
