@@ -398,6 +398,8 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *                            declaration below).
  *   mo_map_pose_graph        the essential graph optimised behind such a correction: Sim(3) pose graph over the keyframes, the points
  *                            follow (the comment at its declaration below).
+ *   mo_map_global_ba         global bundle adjustment behind that: all keyframes and points, matrix-free Schur conjugate gradient (the
+ *                            comment at its declaration below).
  *   mo_map_query_keyframes, mo_map_relocalize_pre   place recognition over a binary vocabulary and relocalization against the keyframes
  *                            it selects (the comment above mo_vocab_train below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
@@ -1074,7 +1076,7 @@ int mo_map_loop_confirm(mo_map*, const double K[9], const double* poses, const m
  * mo_map_loop_correct: a confirmed loop corrected on the map as it stands (the first half of ORB-SLAM2's LoopClosing::CorrectLoop): the
  * similarity is carried to the asking keyframe's neighbourhood, the neighbourhood's points and poses move, and the loop side's points
  * replace and absorb the neighbourhood's duplicates (SearchAndFuse).  The essential-graph optimisation is mo_map_pose_graph below, a call
- * of its own; global bundle adjustment is not built.  Opt-in: no other call runs it.  tests/correct_restatement.py restates every rule in numpy.  p = kf_pos; K, poses [n_kf][12] as for mo_map_loop_confirm; cand_pos the winning
+ * of its own, and so is the global bundle adjustment behind it, mo_map_global_ba.  Opt-in: no other call runs it.  tests/correct_restatement.py restates every rule in numpy.  p = kf_pos; K, poses [n_kf][12] as for mo_map_loop_confirm; cand_pos the winning
  * candidate; scale, R, t its confirmed model, X_p = scale R X_cand + t in camera coordinates (mo_map_loop_sim3's convention); corrected
  * [n_kf]: non-zero at the keyframes that move; group [n_kf] (NULL: empty): non-zero at the old side, whose points are the loop points (a
  * point with a valid observation at a group position: mo_map_loop_confirm's rule; "valid" as for mo_map_fuse); loop_point [rows of p]:
@@ -1199,6 +1201,75 @@ typedef struct {
     double cost[2], lambda;
 } mo_map_pg_out;
 int mo_map_pose_graph(mo_map*, const double* poses, const double* init, const mo_map_pg_params*, mo_map_pg_out*);
+
+/* ---- Global bundle adjustment (map_gba.hip, gba.h) -------------------------------------------------------------------------------------
+ * mo_map_global_ba: the last link of ORB-SLAM2's loop closing, Optimizer::GlobalBundleAdjustemnt (monocular): the poses of all keyframes
+ * that are not held fixed and every point with at least two observations are refined together.  mo_map_pose_graph spreads a loop's error
+ * with identity information and drags the points behind their reference keyframes; this call puts the map back onto its reprojection
+ * minimum.  Opt-in: no other call runs it.  The reduced camera system is never formed: Levenberg-Marquardt with the points eliminated,
+ * each step's system solved by a block-Jacobi-preconditioned conjugate gradient whose operator is applied matrix-free over the edges, so
+ * there is no limit of 16 free keyframes (mo_map_bundle_adjust keeps its own).  tests/gba_restatement.py restates the rules in numpy with
+ * a dense solve.  K, poses [n_kf][12] as for mo_map_bundle_adjust.  Rules:
+ *   1 edges       an edge = one valid observation, read as mo_map_bundle_adjust reads it; edges are numbered point by point in index
+ *                 order, within a point in list order.  Problem points: the points with >= 2 edges.  A position with an edge to a
+ *                 problem point takes part: fixed when fixed[pos] is non-zero, else free; fixed == NULL: position 0 only (ORB-SLAM2's
+ *                 gauge: the scale is held only by the damping).  MO_ERR_ARG when the problem has points and no fixed position takes part.
+ *                 n_free goes up to the number of keyframes, under the int32 guards of the other calls.
+ *   2 cost        residual, information and the Huber cost of width sqrt(chi2) as in round 0 of mo_map_bundle_adjust.  One round of at
+ *                 most max_steps steps (0 .. 100), no outlier round.  At the end every edge is classified (inlier: depth > 0 and
+ *                 information * |e|^2 <= chi2) into edge_inlier and n_inliers: reported only, nothing is erased.
+ *   3 one step    damping (every diagonal entry times (1 + lambda), lambda 1e-4 at the start, / 10 after an accepted step, * 10 after
+ *                 a rejected one), acceptance on the true robust cost, the end at an update below step_tol or lambda > 1e8, and a point
+ *                 whose V is not positive definite (held for the step) as in mo_map_bundle_adjust.  Per problem point: the damped V,
+ *                 V^-1, g_p.  Per free keyframe k, over its edges in ascending edge order: the damped H_kk, b_k = g_k - sum W_e V^-1 g_p
+ *                 and the preconditioner block M_k = H_kk - sum_e W_e V^-1 W_e^T (same-edge terms only), factored by 6x6 Cholesky; if M_k
+ *                 is not positive definite the damped H_kk is factored instead; if that fails too the vertex is held for the step.
+ *   4 solve       S x = b by preconditioned conjugate gradient from x = 0, S p = H p - W V^-1 W^T p in two passes: per point
+ *                 q = V^-1 sum_e W_e^T p_kf(e) in edge order, per free keyframe y_k = H_kk p_k - sum_e W_e q_pt(e) in ascending edge order.
+ *                 It ends at r.z <= cg_tol^2 r0.z0, after max_cg iterations, or when p.Sp is not positive and finite; the x so far is
+ *                 used.  When that happens at iteration 0, or r0.z0 is not a finite number >= 0, the step counts as rejected (lambda * 10,
+ *                 no test against step_tol).  A truncated solve is legitimate: rule 3 accepts on the true cost.  The points are
+ *                 back-substituted as in mo_map_bundle_adjust.
+ *   5 writes      when at least one step was accepted: xyz of every problem point (the f64 result rounded once to f32) and
+ *                 P = K [R | t] of every free position (mo_map_bundle_adjust's product order).  Otherwise nothing is written.  Points and
+ *                 keyframes outside the problem keep their bytes.  ok = the problem ran and n_inliers >= min_inliers.  An empty map, no
+ *                 free position, no problem point or max_steps = 0: every count is 0, ok = 0, not an error.  MO_ERR_ARG: NULL arguments;
+ *                 non-finite K or poses; scale_factor not finite and > 0; chi2 or a tolerance not finite and >= 0; max_steps outside
+ *                 0 .. 100; max_cg < 1; the gauge of rule 1.
+ *   6 determinism no floating-point atomics.  Per-point sums are serial in edge order; per-keyframe sums take the edges strided over the
+ *                 lanes, each lane in order, then the wave's shuffle tree, then the waves in order; the dot products over 6 n_free use a
+ *                 fixed assignment and tree.  Two calls on equal maps return equal bytes.  Integer atomics count (the keyframe-side
+ *                 edge lists, which are then sorted).
+ *   7 decisions   every decision is a flag in a result block that later kernels read first.  The host waits on that block after the
+ *                 set-up, between steps and between chunks of 32 conjugate-gradient iterations, only to stop enqueuing: the results do
+ *                 not depend on where it waits.
+ * poses_out [n_kf][12]: the free ones refined, the rest as given; kf_state as mo_map_bundle_adjust's; edge_inlier [n_obs] per entry of
+ * the observation arrays (0 skipped or outside the problem, 1 inlier, 2 outlier); points_out [n_pts][3]: f64 positions of the problem
+ * points, NaN elsewhere; cost: the robust cost at the start and at the end; cg_iters: the iterations of all solves. */
+typedef struct {
+    const uint8_t* fixed;    /* [n_kf] non-zero: the position is held; NULL: position 0 only */
+    int32_t max_steps;       /* 0 .. 100 (10) */
+    int32_t max_cg;          /* 200 */
+    double cg_tol;           /* 1e-8 */
+    double step_tol;         /* 1e-10 */
+    int32_t min_inliers;     /* ok needs this many inlier edges at the end (50) */
+    double scale_factor;     /* of the information (1.2) */
+    double chi2;             /* outlier threshold; the Huber width is its square root (5.991) */
+} mo_map_gba_params;
+typedef struct {
+    /* caller-allocated, may be NULL */
+    double* poses_out;       /* [n_kf][12] */
+    int32_t* kf_state;       /* [n_kf] 0 outside the problem, 1 fixed, 2 free */
+    uint8_t* edge_inlier;    /* [n_obs] */
+    double* points_out;      /* [n_pts][3] */
+    /* filled by the call */
+    double cost[2];
+    double lambda;           /* damping after the last step */
+    int32_t n_free, n_fixed, n_points, n_edges, n_inliers;
+    int32_t steps, accepted, cg_iters;
+    int32_t ok;
+} mo_map_gba_out;
+int mo_map_global_ba(mo_map*, const double K[9], const double* poses, const mo_map_gba_params*, mo_map_gba_out*);
 
 /* Status of the mo_dev_* calls enqueued since the last mo_dev_status: the kernels never fault on overflow, they clamp and
  * raise a bit.  Host entry points keep their own flag words (checked inside each call): interleaving them with mo_dev_* calls

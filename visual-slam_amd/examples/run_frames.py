@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
 """
 import argparse
 import os
@@ -138,6 +138,9 @@ def main(argv=None):
     ap.add_argument("--loop-optimize", action="store_true", help="with --detect-loops (switches --loop-correct on): the essential graph is optimised "
                     "behind the correction (LocalMapper.detect_loop(..., optimize=True)): a Sim(3) pose graph over all keyframes spreads what the "
                     "correction left along the trajectory; the line of a found loop then carries the cost before and after")
+    ap.add_argument("--loop-global-ba", action="store_true", help="with --detect-loops (switches --loop-optimize on): a global bundle adjustment runs "
+                    "behind the essential graph (LocalMapper.detect_loop(..., global_ba=True)): every keyframe but the first and every point with two "
+                    "observations; the line of a found loop then carries its cost before and after")
     ap.add_argument("--track-map", action="store_true", help="with --map: track every frame against the device map from the constant-velocity "
                     "prediction (LocalMapper.track_local_map); the essential-matrix step runs only when that fails")
     ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
@@ -174,6 +177,9 @@ def main(argv=None):
         ap.error("--vocabulary needs --map and --relocalize or --detect-loops")
     if args.detect_loops and not args.vocabulary:
         ap.error("--detect-loops needs --map and --vocabulary")
+    if args.loop_global_ba and not args.detect_loops:
+        ap.error("--loop-global-ba needs --detect-loops")
+    args.loop_optimize = args.loop_optimize or args.loop_global_ba
     if args.loop_optimize and not args.detect_loops:
         ap.error("--loop-optimize needs --detect-loops")
     args.loop_correct = args.loop_correct or args.loop_optimize
@@ -231,7 +237,8 @@ def main(argv=None):
         ensure_vocabulary(idx)
         if mapper.vocabulary is None:
             return
-        found, info = mapper.detect_loop(sim3=args.loop_sim3, confirm=args.loop_confirm, correct=args.loop_correct, optimize=args.loop_optimize)
+        found, info = mapper.detect_loop(sim3=args.loop_sim3, confirm=args.loop_confirm, correct=args.loop_correct, optimize=args.loop_optimize,
+                                          global_ba=args.loop_global_ba)
         n_loop[0] += 1
         if info["candidates"]:
             print("frame %d: keyframe %d loop candidates %s" % (idx, info["kf_pos"], ", ".join(
@@ -255,6 +262,10 @@ def main(argv=None):
                 og = acc["optimize"]
                 confirmed += "; essential graph of %d edges over %d free keyframes optimised in %d steps (%d accepted, %d solver iterations): cost %.6g -> %.6g, %d points followed" % (
                     og["n_edges"], og["n_free"], og["steps"], og["accepted"], og["cg_iters"], og["cost"][0], og["cost"][1], og["n_moved"])
+            if args.loop_global_ba:
+                gb = acc["global_ba"]
+                confirmed += "; global bundle adjustment of %d free keyframes, %d points and %d edges in %d steps (%d accepted, %d solver iterations): cost %.6g -> %.6g, %d inlier edges" % (
+                    gb["n_free"], gb["n_points"], gb["n_edges"], gb["steps"], gb["accepted"], gb["cg_iters"], gb["cost"][0], gb["cost"][1], gb["n_inliers"])
             print("frame %d: loop found: keyframe %d closes with keyframe %d, %d map-point correspondences%s%s"
                   % (idx, info["kf_pos"], acc["pos"], acc["n_match"],
                      ", relative scale %.4f with %d inliers" % (acc["sim3"]["scale"], acc["sim3"]["n_inliers"]) if args.loop_sim3 else "", confirmed))

@@ -213,6 +213,18 @@ class MapPgOut(C.Structure):
                 ("ok", C.c_int32), ("cost", C.c_double * 2), ("lambda_", C.c_double)]
 
 
+class MapGbaParams(C.Structure):
+    _fields_ = [("fixed", C.c_void_p), ("max_steps", C.c_int32), ("max_cg", C.c_int32), ("cg_tol", C.c_double), ("step_tol", C.c_double),
+                ("min_inliers", C.c_int32), ("scale_factor", C.c_double), ("chi2", C.c_double)]
+
+
+class MapGbaOut(C.Structure):
+    _fields_ = [("poses_out", C.c_void_p), ("kf_state", C.c_void_p), ("edge_inlier", C.c_void_p), ("points_out", C.c_void_p),
+                ("cost", C.c_double * 2), ("lambda_", C.c_double), ("n_free", C.c_int32), ("n_fixed", C.c_int32), ("n_points", C.c_int32),
+                ("n_edges", C.c_int32), ("n_inliers", C.c_int32), ("steps", C.c_int32), ("accepted", C.c_int32), ("cg_iters", C.c_int32),
+                ("ok", C.c_int32)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ch", C.c_int32), ("chunk", C.c_int32), ("cap", C.c_int32), ("detector", C.c_int32),
                 ("mode", C.c_int32), ("ratio", C.c_double), ("disp_frac", C.c_double), ("K", C.c_double * 9), ("thr_px", C.c_double),
@@ -316,6 +328,7 @@ SIGNATURES = {
     "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_correct": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_pose_graph": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mo_map_global_ba": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_map_sim3_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -321,6 +321,53 @@ class LocalMapper:
             info["points"] = pts[:self._n_points]
         return bool(out.ok), info
 
+    def global_bundle_adjust(self, fixed=None, max_steps=10, max_cg=200, cg_tol=1e-8, step_tol=1e-10, min_inliers=50, scale_factor=1.2,
+                             chi2=5.991, want_points=False):
+        """Global bundle adjustment on the map as it stands (ORB-SLAM2's GlobalBundleAdjustemnt, the step behind a loop correction and
+        optimize_essential_graph; mo_map_global_ba in include/vslam_amd.h states the rules): the poses of all keyframes that are not
+        held fixed and every point with at least two observations are refined together, with no limit on the number of keyframes: the
+        reduced camera system is solved matrix-free by a preconditioned conjugate gradient.  `fixed`: the positions that stay; None:
+        position 0 only (the scale is then held by the damping alone).  One robust round of at most max_steps steps; no observation is
+        erased.  The refined poses are written into kf["pose"] of the free keyframes when a step was accepted, the points move on the
+        device.
+        Returns (ok, info): info holds n_free, n_fixed, n_points, n_edges, n_inliers, cost (start, end), lambda, steps, accepted,
+        cg_iters, `free` and `fixed` position lists, `edge_inlier` per observation entry (0 outside, 1 inlier, 2 outlier), `poses`
+        [n_kf][3][4] and, with want_points, `points` [n_points][3] f64 (NaN for points outside the problem)."""
+        n_kf = len(self.keyframes)
+        poses = np.zeros((max(n_kf, 1), 12), np.float64)
+        for i, kf in enumerate(self.keyframes):
+            poses[i] = np.asarray(kf["pose"], np.float64)[:3, :4].reshape(12)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        fmask = None
+        if fixed is not None:
+            fmask = np.zeros(max(n_kf, 1), np.uint8)
+            for k in fixed:
+                if 0 <= int(k) < n_kf:
+                    fmask[int(k)] = 1
+        poses_out = poses.copy()
+        state = np.zeros(max(n_kf, 1), np.int32)
+        n_obs = self._n_obs if self._n_points else 0
+        einl = np.zeros(max(n_obs, 1), np.uint8)
+        pts = np.full((max(self._n_points, 1), 3), np.nan, np.float64) if want_points else None
+        prm = V.MapGbaParams(fmask.ctypes.data if fmask is not None else None, int(max_steps), int(max_cg), float(cg_tol), float(step_tol),
+                             int(min_inliers), float(scale_factor), float(chi2))
+        out = V.MapGbaOut(poses_out.ctypes.data, state.ctypes.data, einl.ctypes.data, pts.ctypes.data if want_points else None)
+        self._check(self.lib.mo_map_global_ba(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        state = state[:n_kf]
+        free = np.flatnonzero(state == 2).tolist()
+        if out.accepted:
+            for i in free:
+                self.keyframes[i]["pose"][:3, :4] = poses_out[i].reshape(3, 4)
+            self._version += 1
+            self._cache = None
+        info = {k: int(getattr(out, k)) for k in ("n_free", "n_fixed", "n_points", "n_edges", "n_inliers", "steps", "accepted", "cg_iters")}
+        info.update(cost=[float(v) for v in out.cost], free=free, fixed=np.flatnonzero(state == 1).tolist(), edge_inlier=einl[:n_obs],
+                    poses=poses_out[:n_kf].reshape(n_kf, 3, 4))
+        info["lambda"] = float(out.lambda_)
+        if want_points:
+            info["points"] = pts[:self._n_points]
+        return bool(out.ok), info
+
     # ---- fusion of duplicate map points ---------------------------------------------------------------------------------------------
     def _valid_positions(self, a, i, counts):
         """the keyframe positions map point i of the arrays a validly observes (the library's reading of an observation)"""
@@ -868,7 +915,7 @@ class LocalMapper:
         states the rules): the similarity is carried to the asking keyframe's neighbourhood, whose keyframes and points move onto the old
         side, and the old side's points replace and absorb the neighbourhood's duplicates - confirm's loop points directly, the rest of
         the group's points by fuse_map_points' search under the corrected poses.  The essential-graph optimisation is
-        optimize_essential_graph, a call of its own; global bundle adjustment is not built.  `confirm` is confirm_loop's info, or an `accepted` candidate of detect_loop(confirm=True) (its
+        optimize_essential_graph, a call of its own, and so is the global bundle adjustment behind it, global_bundle_adjust.  `confirm` is confirm_loop's info, or an `accepted` candidate of detect_loop(confirm=True) (its
         `confirm` entry is used, its `group` is the default group).  The asking keyframe is kf_position, by default confirm's `kf_pos`.
         `corrected`: the positions that move; by default p and the positions whose covisibility() weight with p is at least min_weight,
         less the group's.  `group`: the old side's positions; by default the winning candidate's group, else the candidate alone.
@@ -1029,7 +1076,8 @@ class LocalMapper:
         return info
 
     def detect_loop(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, min_matches=20, consistency=3, sim3=False,
-                    confirm=False, confirm_kw=None, correct=False, correct_kw=None, optimize=False, optimize_kw=None, **sim3_kw):
+                    confirm=False, confirm_kw=None, correct=False, correct_kw=None, optimize=False, optimize_kw=None, global_ba=False,
+                    global_ba_kw=None, **sim3_kw):
         """ORB-SLAM2's DetectLoop up to the point correspondences: loop_candidates for the keyframe, the consistent-group bookkeeping
         (vslam_amd.loop.LoopConsistency, kept on the mapper from call to call on keyframe serials; call it once per new keyframe), and
         the match count.  Returns (found, info): found when a candidate whose group was consistent `consistency` times in a row has
@@ -1043,8 +1091,12 @@ class LocalMapper:
         correct=True (needs confirm=True): an accepted loop is corrected by correct_loop (keyword arguments in correct_kw): the map
         changes, and `accepted` also holds `correct`: correct_loop's info.
         optimize=True (needs correct=True): the essential graph is optimised behind the correction by optimize_essential_graph (keyword
-        arguments in optimize_kw) from the poses as they were before it, and `accepted` also holds `optimize`: its info."""
+        arguments in optimize_kw) from the poses as they were before it, and `accepted` also holds `optimize`: its info.
+        global_ba=True (needs optimize=True): global_bundle_adjust (keyword arguments in global_ba_kw) runs behind the essential graph,
+        and `accepted` also holds `global_ba`: its info with `ok`."""
         from vslam_amd.loop import LoopConsistency
+        if global_ba and not optimize:
+            raise ValueError("global_ba=True needs optimize=True")
         if confirm and not sim3:
             raise ValueError("confirm=True needs sim3=True")
         if correct and not confirm:
@@ -1084,6 +1136,9 @@ class LocalMapper:
                     c["correct"] = self.correct_loop(c, kf_position=info["kf_pos"], min_weight=min_weight, **(correct_kw or {}))
                     if optimize:
                         c["optimize"] = self.optimize_essential_graph(c, poses_before=before, **(optimize_kw or {}))
+                    if global_ba:
+                        gok, ginfo = self.global_bundle_adjust(**(global_ba_kw or {}))
+                        c["global_ba"] = dict(ginfo, ok=gok)
                 break
         return info["accepted"] is not None, info
 
