@@ -135,6 +135,53 @@ int mo_init_two_view(mo_ctx*, const float* p1, const float* p2, int m, const dou
                      uint8_t* ransac_inlier /* [m] findEssentialMat mask, may be NULL */, uint8_t* inlier, float* X,
                      int* n_good);
 
+/* Two-view initialisation with ORB-SLAM2's model selection (Initializer.cc: FindHomography / FindFundamental, CheckHomography /
+ * CheckFundamental, RH = SH / (SH + SF), ReconstructH with CheckRT); the reference has no counterpart - its initializer knows the
+ * essential matrix only and reports a wrong pose as success on a plane or under pure rotation.  The call runs the unchanged
+ * essential chain of mo_init_two_view and, on the same stream, the homography chain: n_hyp_h four-point hypotheses in closed
+ * form (the first four indices of the essential path's sampling stream), MSAC ranking on the symmetric transfer error truncated at
+ * 5.991 sigma^2, at most 5 DLT refits on the inliers, SH, SF = CheckFundamental of K^-T E K^-1 for the essential path's E,
+ * Faugeras' eight (R, t, n) candidates, CheckRT of each over the H inliers (reprojection within 4 sigma^2, parallax = the value at
+ * index min(50, count - 1) of the ascending cos values).  One synchronisation.
+ * model = 1 (H) when RH > rh_threshold, else 0 (F); -1 when m < 8 or the essential path found no model (everything NaN / 0).
+ * Selected outputs (R, t, pose_mask, X, n_good) are the chosen model's: for model 0 the bytes mo_init_two_view returns for the same
+ * arguments, accepted = n_good > min_triangulated; for model 1 the best candidate's, accepted = second < 0.75 best && parallax >=
+ * min_parallax_deg && best > min_triangulated && best > 0.9 H inliers (n_good counts every point that passed CheckRT, pose_mask
+ * and X hold those of them with cos(parallax) < 0.99998, as ORB-SLAM2's vbTriangulated). */
+typedef struct {
+    double thr_px;           /* essential path: Sampson threshold in pixels (3.0) */
+    int32_t n_hyp;           /* essential path: hypotheses (4096) */
+    int32_t n_hyp_h;         /* homography hypotheses (512) */
+    uint64_t seed;           /* both sampling streams (4096) */
+    double sigma;            /* pixel noise of CheckHomography / CheckFundamental / CheckRT (1.0) */
+    double rh_threshold;     /* 0.40 */
+    double min_parallax_deg; /* 1.0 */
+    int32_t min_triangulated; /* 50 */
+    int32_t reserved;
+} mo_hf_params;
+
+typedef struct {
+    /* caller-allocated arrays, all required */
+    uint8_t* pose_mask;      /* [m] selected model */
+    float* X;                /* [m][3] selected model, NaN outside pose_mask */
+    uint8_t* ransac_mask;    /* [m] essential path: Sampson inliers */
+    uint8_t* h_mask;         /* [m] homography: both transfer directions inside the threshold */
+    /* filled by the call */
+    int32_t model, accepted, n_good, n_good_e;
+    double R[9], t[3];       /* selected model; t unit norm */
+    double E[9], R_e[9], t_e[3];  /* essential path (mo_init_two_view's E, R, t; n_good_e) */
+    double H[9];             /* pixels, unit Frobenius norm; NaN: no homography model */
+    double SH, SF, RH;
+    double parallax_h[8];    /* degrees; 0 for a candidate without a passed point */
+    int32_t n_good_h[8];
+    int32_t best_h, second_h;  /* candidate indices, -1: none */
+    int32_t n_inliers_h, accepted_h, winner_h /* winning hypothesis, -1: no model */, refits_h;
+    double R_h[9], t_h[3];   /* best candidate (NaN: none) */
+} mo_hf_result;
+
+int mo_init_two_view_hf(mo_ctx*, const float* p1, const float* p2, int m, const double K[9], const mo_hf_params* params,
+                        mo_hf_result* out);
+
 /* Replaces cv2.recoverPose(E, p1, p2, K, mask)   (utils.py:129-134) for ANY essential matrix the caller holds: decomposition
  * (U W V^T, U W^T V^T, +-u3), cheirality vote over the four candidates on the points selected by mask_in (NULL = all; depth in
  * (0, 50) in both cameras, as cv2), winner's R, t, its mask, and the DLT points of the surviving correspondences.

@@ -609,6 +609,102 @@ extern "C" int mo_init_two_view(mo_ctx* c, const float* p1, const float* p2, int
     return MO_OK;
 }
 
+extern "C" int mo_init_two_view_hf(mo_ctx* c, const float* p1, const float* p2, int m, const double K[9], const mo_hf_params* pr,
+                                   mo_hf_result* o) {
+    if (!c) return MO_ERR_ARG;
+    if (!p1 || !p2 || !K || !pr || !o || !o->pose_mask || !o->X || !o->ransac_mask || !o->h_mask) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (m < 0) return mo_fail(c, MO_ERR_ARG, "m must be >= 0");
+    if (!(pr->sigma > 0.0) || !(pr->min_parallax_deg >= 0.0) || !(pr->min_parallax_deg < 180.0) || !(pr->rh_threshold == pr->rh_threshold) ||
+        pr->min_triangulated < 0)
+        return mo_fail(c, MO_ERR_ARG, "sigma must be positive, min_parallax_deg in [0, 180), rh_threshold a number, min_triangulated >= 0");
+    if (pr->n_hyp < 1 || pr->n_hyp > (1 << 20) || pr->n_hyp_h < 1 || pr->n_hyp_h > (1 << 20)) return mo_fail(c, MO_ERR_ARG, "n_hyp / n_hyp_h out of range");
+    MO_ENTER(c);
+    // the no-model result
+    uint8_t* const pm = o->pose_mask; float* const X = o->X; uint8_t* const rm = o->ransac_mask; uint8_t* const hm = o->h_mask;
+    *o = mo_hf_result{};
+    o->pose_mask = pm; o->X = X; o->ransac_mask = rm; o->h_mask = hm;
+    o->model = -1; o->best_h = o->second_h = o->winner_h = -1;
+    for (double* v : {o->R, o->E, o->R_e, o->H, o->R_h}) std::fill(v, v + 9, (double)NAN);
+    for (double* v : {o->t, o->t_e, o->t_h}) std::fill(v, v + 3, (double)NAN);
+    std::memset(pm, 0, (size_t)m); std::memset(rm, 0, (size_t)m); std::memset(hm, 0, (size_t)m);
+    for (int i = 0; i < 3 * m; i++) X[i] = NAN;
+    if (m < 8) return MO_OK;
+    const size_t pb = (size_t)m * 2 * sizeof(float), xb = (size_t)m * 3 * sizeof(float);
+    Layout L;
+    const size_t o_pose = L.take(12 * sizeof(double)), o_E = L.take(9 * sizeof(double)), o_n = L.take(sizeof(int32_t)), o_p1 = L.take(pb),
+                 o_p2 = L.take(pb), o_X = L.take(xb), o_inl = L.take(m), o_ran = L.take(m), o_H = L.take(9 * sizeof(double)),
+                 o_stat = L.take(HF_NSTAT * sizeof(double)), o_info = L.take(HF_NINFO * sizeof(int32_t)), o_hm = L.take(m), o_good = L.take(m),
+                 o_Xh = L.take(xb);
+    int rc = c->d_tmp.reserve_exact(c, L.total);
+    if (rc) return rc;
+    uint8_t* b = c->d_tmp;
+    float* d_p1 = L.at<float>(b, o_p1);
+    float* d_p2 = L.at<float>(b, o_p2);
+    HIPCHK(c, hipMemcpyAsync(d_p1, p1, pb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_p2, p2, pb, hipMemcpyHostToDevice, c->stream));
+    TwoViewArgs a;  // the essential chain, argument for argument what mo_init_two_view launches
+    a.n_pairs = 1; a.cap = m; a.n_hyp = pr->n_hyp;
+    for (int i = 0; i < 9; i++) a.K[i] = K[i];
+    a.thr_px = pr->thr_px; a.seed = pr->seed;
+    a.d_p1 = d_p1; a.d_p2 = d_p2; a.m_fixed = m;
+    a.d_pose = L.at<double>(b, o_pose); a.d_E = L.at<double>(b, o_E); a.d_points = L.at<float>(b, o_X); a.d_inlier = b + o_inl;
+    a.d_ransac = b + o_ran; a.d_n_points = L.at<int32_t>(b, o_n);
+    HfArgs h;
+    h.n_pairs = 1; h.cap = m; h.n_hyp = pr->n_hyp_h; h.m_fixed = m;
+    for (int i = 0; i < 9; i++) h.K[i] = K[i];
+    h.sigma = pr->sigma; h.cos_max = std::cos(pr->min_parallax_deg * (M_PI / 180.0)); h.min_triangulated = pr->min_triangulated;
+    h.seed = pr->seed;
+    h.d_p1 = d_p1; h.d_p2 = d_p2; h.d_E = a.d_E;
+    h.d_H = L.at<double>(b, o_H); h.d_stat = L.at<double>(b, o_stat); h.d_info = L.at<int32_t>(b, o_info);
+    h.d_hmask = b + o_hm; h.d_good = b + o_good; h.d_X = L.at<float>(b, o_Xh);
+    mo_stage_begin(c);
+    if ((rc = twoview_launch(c, a))) return rc;
+    mo_stage_mark(c, "two_view");
+    if ((rc = twoview_h_launch(c, h))) return rc;
+    mo_stage_mark(c, "two_view_h");
+    double pose[12], stat[HF_NSTAT];
+    int32_t ng = 0, info[HF_NINFO];
+    std::vector<uint8_t> inl_e((size_t)m), good_h((size_t)m);
+    std::vector<float> X_e((size_t)m * 3), X_h((size_t)m * 3);
+    HIPCHK(c, hipMemcpyAsync(pose, a.d_pose, sizeof(pose), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o->E, a.d_E, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&ng, a.d_n_points, sizeof(ng), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(X_e.data(), a.d_points, xb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(inl_e.data(), a.d_inlier, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rm, a.d_ransac, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o->H, h.d_H, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stat, h.d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(info, h.d_info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hm, h.d_hmask, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(good_h.data(), h.d_good, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(X_h.data(), h.d_X, xb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 9; i++) { o->R_e[i] = pose[i]; o->R_h[i] = stat[11 + i]; }
+    for (int i = 0; i < 3; i++) { o->t_e[i] = pose[9 + i]; o->t_h[i] = stat[20 + i]; }
+    o->n_good_e = ng;
+    o->SH = stat[0]; o->SF = stat[1]; o->RH = stat[2];
+    for (int k = 0; k < 8; k++) {
+        o->n_good_h[k] = info[k];
+        const double cs = stat[3 + k];  // 2: no passed point
+        o->parallax_h[k] = cs > 1.5 ? 0.0 : std::acos(std::fmin(std::fmax(cs, -1.0), 1.0)) * (180.0 / M_PI);
+    }
+    o->best_h = info[8]; o->second_h = info[9]; o->n_inliers_h = info[10]; o->accepted_h = info[11]; o->winner_h = info[12]; o->refits_h = info[13];
+    if (!(o->E[0] == o->E[0])) {  // the essential path reports no model: so does the call (the raw homography fields stay for inspection)
+        std::memset(rm, 0, (size_t)m);
+        return MO_OK;
+    }
+    if (o->RH > pr->rh_threshold) {
+        o->model = 1; o->accepted = o->accepted_h; o->n_good = o->best_h >= 0 ? o->n_good_h[o->best_h] : 0;
+        std::memcpy(o->R, o->R_h, sizeof(o->R)); std::memcpy(o->t, o->t_h, sizeof(o->t));
+        std::memcpy(pm, good_h.data(), (size_t)m); std::memcpy(X, X_h.data(), xb);
+    } else {
+        o->model = 0; o->accepted = ng > pr->min_triangulated ? 1 : 0; o->n_good = ng;
+        std::memcpy(o->R, o->R_e, sizeof(o->R)); std::memcpy(o->t, o->t_e, sizeof(o->t));
+        std::memcpy(pm, inl_e.data(), (size_t)m); std::memcpy(X, X_e.data(), xb);
+    }
+    return MO_OK;
+}
+
 extern "C" int mo_recover_pose(mo_ctx* c, const double E[9], const float* p1, const float* p2, int m, const double K[9],
                                const uint8_t* mask_in, double R[9], double t[3], uint8_t* mask_out, float* X, int* n_good) {
     if (!c) return MO_ERR_ARG;

@@ -153,6 +153,7 @@ struct mo_ctx {
     DevBuf<uint8_t> d_mq, d_mt, d_mpass; DevBuf<int32_t> d_midx, d_mdist;
     DevBuf<uint2> d_match_part;     // per-slice keys of a split k_match_lds launch
     DevBuf<uint8_t> d_tv;           // two-view work buffers (carved by twoview_launch)
+    DevBuf<uint8_t> d_hf;           // homography branch of the two-view stage (carved by twoview_h_launch)
     DevBuf<float> d_stream_pts;     // mo_stream: map-point scratch of chunks whose caller does not want them
     DevBuf<uint32_t> d_track_keys;  // k_track_select: key arrays of frames too large for LDS
     DevBuf<uint8_t> d_tmp;          // generic temp (carved with Layout)
@@ -173,7 +174,7 @@ struct mo_ctx {
     // until mo_dev_status), d_slot_* (resident results), d_pair_frames (written once per size), d_comm_cnt.  A DevBuf added to this
     // struct is named here or in that sentence.
     template <class F> void each_scratch(F f) {
-        f(d_in); f(d_gray); f(d_kps); f(d_desc); f(d_counts); f(d_mq); f(d_mt); f(d_mpass); f(d_midx); f(d_mdist); f(d_match_part); f(d_tv);
+        f(d_in); f(d_gray); f(d_kps); f(d_desc); f(d_counts); f(d_mq); f(d_mt); f(d_mpass); f(d_midx); f(d_mdist); f(d_match_part); f(d_tv); f(d_hf);
         f(d_stream_pts); f(d_track_keys); f(d_tmp);
     }
 };
@@ -368,6 +369,27 @@ static inline TwoViewArgs tv_fundamental(int n_pairs, int cap, int n_hyp, double
     return a;
 }
 int twoview_launch(mo_ctx* c, const TwoViewArgs& a);
+// twoview_h.hip: the homography branch (ORB-SLAM2's H model beside the essential path: hypotheses, CheckHomography scores, DLT refits,
+// SH / SF / RH, ReconstructH with CheckRT over the eight candidates).  Explicit correspondences only, batched over pairs.
+#define HF_NSTAT 23  // doubles per pair: SH, SF, RH, cos of the parallax of the 8 candidates (2 = none), R (9) and t (3) of the best one
+#define HF_NINFO 16  // ints per pair: n_good[8], best, second (-1: none), H inliers, accepted, winning hypothesis (-1: no model), refits, decomposed
+struct HfArgs {  // (an aggregate passed by value to the k_h_* kernels)
+    int n_pairs = 0, cap = 0, n_hyp = 0, m_fixed = 0;
+    double K[9] = {}, sigma = 1.0;
+    double cos_max = 0;          // cos(min_parallax): a candidate's parallax is large enough when its cos is at most this
+    int min_triangulated = 50;
+    uint64_t seed = 0, pair_base = 0;
+    const float* d_p1 = nullptr; const float* d_p2 = nullptr;  // [pairs][m_fixed][2] pixels
+    const double* d_E = nullptr;  // [pairs][9] the essential path's result for the same pairs (NaN: none): SF is its CheckFundamental score
+    double* d_H = nullptr;        // [pairs][9] pixels, unit Frobenius norm (NaN: no model)
+    double* d_stat = nullptr;     // [pairs][HF_NSTAT]
+    int32_t* d_info = nullptr;    // [pairs][HF_NINFO]
+    uint8_t* d_hmask = nullptr;   // [pairs][cap] H inliers (both transfer directions inside the threshold)
+    uint8_t* d_good = nullptr;    // [pairs][cap] map points of the best candidate (CheckRT passed with parallax)
+    float* d_X = nullptr;         // [pairs][cap][3] their coordinates in camera 1 (NaN elsewhere)
+};
+static_assert(std::is_trivially_copyable<HfArgs>::value, "HfArgs is a kernel argument");
+int twoview_h_launch(mo_ctx* c, const HfArgs& a);
 // undistort_kernels.hip
 int undistort_launch(mo_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int ch, int batch, const double K[9],
                      const double dist[5]);

@@ -154,6 +154,8 @@ def main(argv=None):
                     "keypoints without a map point are searched along their epipolar lines in the neighbour keyframes and triangulated "
                     "(LocalMapper.create_new_map_points with its default window of 10 neighbours), before --fuse and the bundle adjustment of --local-ba")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
+    ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
+                    "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
@@ -161,7 +163,7 @@ def main(argv=None):
     extractor = ORBExtractor(n_features=orb["n_features"], scale_factor=orb["scale_factor"], n_levels=orb["n_levels"],
                              ini_threshold=orb["ini_threshold"], min_threshold=orb["min_threshold"])
     matcher = DescriptorMatcher(mt["matcher_type"], ratio_threshold=mt["ratio_threshold"])
-    initializer = MapInitializer(K)
+    initializer = MapInitializer(K, model_selection=args.init_model_selection)
     limit = args.max_frames or cfg.get("max_frames", 0) or 10 ** 9
     skip = int(cfg.get("skip_frames", 0) or 0)
     source = frames_from(args.frames) if args.frames else synthetic_sequence(limit if limit < 10 ** 9 else 30)
@@ -373,6 +375,7 @@ def main(argv=None):
                 first = (frame, kps, desc)
             else:
                 ok, R, t, pts, matches = initializer.initialize(kps, desc, matcher, frame)
+                _print_selection(idx, initializer)
                 if ok:
                     state, n_map = "TRACKING", len(pts)
                     poses.append((R, t))
@@ -435,6 +438,15 @@ def main(argv=None):
     return state, poses, n_map
 
 
+def _print_selection(idx, initializer):
+    """--init-model-selection: what the last initialize() decided"""
+    sel = initializer.last_selection if initializer.model_selection else None
+    if sel is not None:
+        print("frame %d: model %s, RH %.3f, parallax %.2f deg, good %d (H candidates %s), %s" % (
+            idx, {1: "H", 0: "F"}.get(sel["model"], "none"), sel["RH"], sel["parallax"], sel["n_good"], list(map(int, sel["n_good_h"])),
+            "accepted" if sel["accepted"] else "refused"))
+
+
 def run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0):
     """--batch N: the frame loop above with the extraction and the tracking step of EVERY frame taken from FrameStream (one batched
     device call per N frames).  Initialisation (the first frame pair that yields a map) goes through MapInitializer on the streamed
@@ -491,6 +503,7 @@ def run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0):
                     initializer.set_first_frame(kps, desc, frame_at(r.index))
                 else:
                     ok, R, t, pts, matches = initializer.initialize(kps, desc, matcher, frame_at(r.index))
+                    _print_selection(r.index, initializer)
                     if ok:
                         state[0], n_map = "TRACKING", len(pts)
                         kept.clear()

@@ -12,6 +12,11 @@ matcher, two (matcher.match, then mo_init_two_view) with any other matcher objec
   4. keep points in front of both cameras, sample colours, build the map-point dictionaries (host bookkeeping)
 Return conventions follow the reference: (False, None, None, None, None) without a first frame, (False, None, None, None,
 matches) when matching or geometry is insufficient, R 3x3 / t 3x1 float64 on success.
+
+model_selection=True (keyword only, not in the reference): ORB-SLAM2's homography / fundamental model selection.  initialize() then
+takes the per-stage path with mo_init_two_view_hf in place of mo_init_two_view: a plane initialises through the homography's
+decomposition, and a pair whose selected model is not accepted (pure rotation, too little parallax, an ambiguous decomposition)
+returns the failure tuple instead of a map built on a wrong pose.  The last call's decision is kept in `last_selection`.
 """
 import numpy as np
 
@@ -25,8 +30,10 @@ def _pixels(keypoints, indices):
 
 
 class MapInitializer:
-    def __init__(self, camera_matrix, min_matches=10, min_inliers_ratio=0.9):
+    def __init__(self, camera_matrix, min_matches=10, min_inliers_ratio=0.9, *, model_selection=False):
         self.camera_matrix = camera_matrix
+        self.model_selection = bool(model_selection)
+        self.last_selection = None  # model_selection: dict(model, accepted, RH, parallax, n_good, n_good_h) of the last initialize()
         self.min_matches = min_matches
         self.min_inliers_ratio = min_inliers_ratio  # kept for API parity; the reference never reads it either
         self.initialization_done = False
@@ -91,7 +98,7 @@ class MapInitializer:
             return self._failure(None)
         from .types import dmatches_from_arrays
         fused = None
-        if current_descriptors is not None and len(ref_desc) and len(current_descriptors):
+        if not self.model_selection and current_descriptors is not None and len(ref_desc) and len(current_descriptors):
             fused = self._device_pair(ref_kps, ref_desc, current_keypoints, current_descriptors, matcher)
         if fused is not None:
             # one call, one synchronisation: knn + ratio list, E at 3 px, pose, pose mask and map points by query keypoint
@@ -122,7 +129,15 @@ class MapInitializer:
             # essential matrix at 3 px, recoverPose and the triangulation of the pose-mask survivors with P = K [I | 0], K [R | t]
             # (initializer.py:79-95) are ONE native call: it returns what the three cv2 calls of the reference return
             import vslam_amd
-            g = vslam_amd.default_context().init_two_view(xy_ref, xy_cur, K, thr_px=3.0, n_hyp=_geom.N_HYPOTHESES, seed=_geom.SEED)
+            if self.model_selection:
+                g = vslam_amd.default_context().init_two_view_hf(xy_ref, xy_cur, K, thr_px=3.0, n_hyp=_geom.N_HYPOTHESES, seed=_geom.SEED)
+                best = max(g["best_h"], 0)
+                self.last_selection = dict(model=g["model"], accepted=g["accepted"], RH=g["RH"], parallax=float(g["parallax_h"][best]),
+                                           n_good=g["n_good"], n_good_h=g["n_good_h"])
+                if not g["accepted"]:
+                    return self._failure(putative)
+            else:
+                g = vslam_amd.default_context().init_two_view(xy_ref, xy_cur, K, thr_px=3.0, n_hyp=_geom.N_HYPOTHESES, seed=_geom.SEED)
             if not np.isfinite(g["E"]).all():
                 return self._failure(putative)
             R, t = g["R"], np.asarray(g["t"], np.float64).reshape(3, 1)

@@ -240,6 +240,20 @@ class StreamResult(C.Structure):
                 ("points", C.c_void_p)]
 
 
+class HfParams(C.Structure):
+    _fields_ = [("thr_px", C.c_double), ("n_hyp", C.c_int32), ("n_hyp_h", C.c_int32), ("seed", C.c_uint64), ("sigma", C.c_double),
+                ("rh_threshold", C.c_double), ("min_parallax_deg", C.c_double), ("min_triangulated", C.c_int32), ("reserved", C.c_int32)]
+
+
+class HfResult(C.Structure):
+    _fields_ = [("pose_mask", C.c_void_p), ("X", C.c_void_p), ("ransac_mask", C.c_void_p), ("h_mask", C.c_void_p),
+                ("model", C.c_int32), ("accepted", C.c_int32), ("n_good", C.c_int32), ("n_good_e", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("R_e", C.c_double * 9), ("t_e", C.c_double * 3),
+                ("H", C.c_double * 9), ("SH", C.c_double), ("SF", C.c_double), ("RH", C.c_double), ("parallax_h", C.c_double * 8),
+                ("n_good_h", C.c_int32 * 8), ("best_h", C.c_int32), ("second_h", C.c_int32), ("n_inliers_h", C.c_int32),
+                ("accepted_h", C.c_int32), ("winner_h", C.c_int32), ("refits_h", C.c_int32), ("R_h", C.c_double * 9), ("t_h", C.c_double * 3)]
+
+
 MODE_INIT, MODE_TRACK, MODE_KEYFRAME = 0, 1, 2
 DETECT_ORB, DETECT_GRID = 0, 1
 TIMING_SLOTS = 64  # MO_TIMING_SLOTS of the library: event sets kept for Context.stage_times(back)
@@ -267,6 +281,7 @@ SIGNATURES = {
     "mo_dev_undistort": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mo_match_knn2_ratio": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "mo_init_two_view": (_i, [_vp, _vp, _vp, _i, _vp, _d, _d, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_init_two_view_hf": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mo_recover_pose": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_find_fundamental": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, C.c_uint64, _vp, _vp, _vp]),
     "mo_track_pair": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _d, _d, _vp, _d, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -665,6 +680,31 @@ class Context:
                                               _ptr(inl), _ptr(X), C.byref(ng)))
         return dict(R=R.reshape(3, 3), t=t.reshape(3, 1), E=E.reshape(3, 3), ransac_mask=ran[:m].astype(bool),
                     pose_mask=inl[:m].astype(bool), X=X[:m], n_good=ng.value)
+
+    def init_two_view_hf(self, p1, p2, K, thr_px=3.0, n_hyp=4096, seed=4096, n_hyp_h=512, sigma=1.0, rh_threshold=0.40,
+                         min_parallax_deg=1.0, min_triangulated=50):
+        """Two-view initialisation with ORB-SLAM2's homography / fundamental model selection (mo_init_two_view_hf) -> dict:
+        model (1 = H, 0 = F, -1 = none), accepted, R, t, pose_mask, X, n_good of the selected model; E, ransac_mask, R_e, t_e, n_good_e of
+        the essential path (what init_two_view returns); H, h_mask, SH, SF, RH, n_good_h (8,), parallax_h (8,) degrees, best_h, second_h,
+        n_inliers_h, accepted_h, winner_h, refits_h, R_h, t_h of the homography path."""
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        Kc = np.ascontiguousarray(K, np.float64).reshape(9)
+        m = len(p1)
+        pm = np.zeros(max(m, 1), np.uint8); ran = np.zeros(max(m, 1), np.uint8); hm = np.zeros(max(m, 1), np.uint8)
+        X = np.zeros((max(m, 1), 3), np.float32)
+        prm = HfParams(float(thr_px), int(n_hyp), int(n_hyp_h), int(seed), float(sigma), float(rh_threshold), float(min_parallax_deg),
+                       int(min_triangulated), 0)
+        r = HfResult()
+        r.pose_mask, r.X, r.ransac_mask, r.h_mask = pm.ctypes.data, X.ctypes.data, ran.ctypes.data, hm.ctypes.data
+        self._check(self.lib.mo_init_two_view_hf(self.h, _ptr(p1), _ptr(p2), m, _ptr(Kc), C.byref(prm), C.byref(r)))
+        a = lambda f, *shape: np.array(f, np.float64).reshape(*shape)  # noqa: E731
+        return dict(model=r.model, accepted=bool(r.accepted), R=a(r.R, 3, 3), t=a(r.t, 3, 1), pose_mask=pm[:m].astype(bool), X=X[:m],
+                    n_good=r.n_good, E=a(r.E, 3, 3), ransac_mask=ran[:m].astype(bool), R_e=a(r.R_e, 3, 3), t_e=a(r.t_e, 3, 1),
+                    n_good_e=r.n_good_e, H=a(r.H, 3, 3), h_mask=hm[:m].astype(bool), SH=r.SH, SF=r.SF, RH=r.RH,
+                    n_good_h=np.array(r.n_good_h, np.int32), parallax_h=a(r.parallax_h, 8), best_h=r.best_h, second_h=r.second_h,
+                    n_inliers_h=r.n_inliers_h, accepted_h=bool(r.accepted_h), winner_h=r.winner_h, refits_h=r.refits_h,
+                    R_h=a(r.R_h, 3, 3), t_h=a(r.t_h, 3, 1))
 
     def recover_pose(self, E, p1, p2, K, mask=None):
         """cv2.recoverPose(E, p1, p2, K, mask) for any E -> dict(n_good, R, t, mask (m,) bool, X (m, 3) float32)"""
