@@ -826,6 +826,84 @@ int mo_map_local_keyframes(mo_map*, const mo_map_local_params*, mo_map_local_out
 int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
                            const mo_map_local_params*, mo_map_local_out*, mo_map_track_out*);
 
+/* ---- Point views and the frustum mode of the searches (map_view_geom.hip, map_search.h) -----------------------------------------------
+ * Where a map point was seen from, and ORB-SLAM2's use of it (MapPoint::UpdateNormalAndDepth, Frame::isInFrustum, MapPoint::PredictScale,
+ * the level gate of ORBmatcher::SearchByProjection and Fuse).  Opt-in: mo_map_track, mo_map_track_covisible and mo_map_fuse decide from
+ * ref_octave as before.  Everything below is f64 unless it says f32; every sum runs left to right as written; s(o) = scale_factor^o as
+ * repeated products from 1.0 (negative o as 0).  tests/view_restatement.py restates it in numpy, operation for operation.
+ *
+ * mo_map_point_views: read-only on the map; one chain, one synchronisation - the copy-out.  Nothing is stored: the calls below recompute
+ * the same values (for their local points) inside their own chains.
+ *   centre        of keyframe position k, from the store's own P = K [R | t] (what mo_map_add_keyframe stored or a bundle adjustment
+ *                 wrote back; the call takes no poses): M = P[:, :3], p = P[:, 3];
+ *                   a00 = m11 m22 - m12 m21   a01 = m02 m21 - m01 m22   a02 = m01 m12 - m02 m11
+ *                   a10 = m12 m20 - m10 m22   a11 = m00 m22 - m02 m20   a12 = m02 m10 - m00 m12
+ *                   a20 = m10 m21 - m11 m20   a21 = m01 m20 - m00 m21   a22 = m00 m11 - m01 m10
+ *                 det = m00 a00 + m01 a10 + m02 a20;  C_i = -((a_i0 p0 + a_i1 p1 + a_i2 p2) / det).  det == 0 or a C_i that is not
+ *                 finite: the keyframe has no centre, reported as three NaN, and its observations are skipped below.
+ *   observations  read like the cull and mo_map_track read them, in stored order; usable = valid and at a keyframe with a centre.
+ *   per usable observation at keyframe k: d = X - C_k (X: the point's f32 position), dist = sqrt(dx dx + dy dy + dz dz).
+ *   reference     the first usable observation: ref_pos = its position, ref_octave = the octave of its keypoint,
+ *                 max_dist = dist_ref * s(ref_octave), rounded to f32.  (ORB-SLAM2's mpRefKF, which also passes to the next observation
+ *                 when a keyframe goes.)  None: ref_pos = -1, ref_octave = 0, max_dist = 0.
+ *   normal        the usable observations with dist > 0 counted in n_valid: sum of (dx / dist, dy / dist, dz / dist) in stored order,
+ *                 each component divided by n_valid and rounded to f32 (0 when n_valid = 0).  Not renormalised, as in ORB-SLAM2: its
+ *                 length says how much the viewing directions agree, and the angle test below relies on that.
+ *   min_dist      f32(max_dist) / s(n_levels - 1), rounded to f32; wherever it is needed it is derived from the stored f32 max_dist.
+ *   A point with max_dist = 0 (no usable observation, or standing in its reference centre) is never a candidate of the searches below.
+ *   An empty map: nothing is written.  No keyframes: every point reports "none".  Never an error. */
+typedef struct {
+    double scale_factor;     /* (1.2) */
+    int32_t n_levels;        /* pyramid levels of the extractor, >= 1 (8) */
+} mo_map_view_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n = map points, n_kf = keyframes */
+    float* normal;           /* [n][3] */
+    float* min_dist;         /* [n] */
+    float* max_dist;         /* [n] */
+    int32_t* ref_pos;        /* [n] keyframe position of the reference observation (-1: none) */
+    int32_t* ref_octave;     /* [n] */
+    int32_t* n_valid;        /* [n] observations summed in normal */
+    double* centre;          /* [n_kf][3] by keyframe position (NaN: no centre) */
+    /* filled by the call */
+    int64_t n_points;
+    int32_t n_kf;
+} mo_map_view_out;
+int mo_map_point_views(mo_map*, const mo_map_view_params*, mo_map_view_out*);
+
+/* The frustum mode: mo_map_track / mo_map_track_covisible (lprm NULL / given) and mo_map_fuse as documented above, with three changes.
+ * Behind k_trk_rep the view record {normal, max_dist} (f32, 16 bytes) of every local point is computed as mo_map_point_views computes
+ * it, with the call's scale_factor.
+ *   frustum       of point X with its record, seen from the camera centre C: PO = X - C, dist = sqrt(POx POx + POy POy + POz POz),
+ *                 max = f32 max_dist, min = max / s(n_levels - 1).  The point is NOT searched when dist is not > 0, max is not > 0,
+ *                 dist < range_lo * min, dist > range_hi * max, or POx nx + POy ny + POz nz < min_cos * dist.
+ *                 C of a tracking pass = -R^T t of the pass pose: C_j = -(R[0][j] t0 + R[1][j] t1 + R[2][j] t2); C of a fusion target =
+ *                 its centre above (a target without a centre searches nothing).
+ *   level         L = the smallest L >= 0 with dist * s(L) >= max, at most n_levels - 1: ORB-SLAM2's ceil(log(max / dist) /
+ *                 log(scale_factor)) clamped to [0, n_levels - 1], without a logarithm.
+ *   (1) candidates  must also pass the frustum test: pass_cand / n_cand count those; pass_in_image counts the plain candidates.
+ *   (2) radius      r = radius * s(L) in place of s(ref_octave).
+ *   (3) octave gate L - 1 <= octave <= L in place of |octave - ref_octave| <= 1.
+ * The ratio rule, max_dist, claims, the retry, the refinement, fusion's chi2 gate, owners, components and merged lists are unchanged.
+ * Not restated from ORB-SLAM2: the 2.5 / 4.0 radius factor by viewing cosine, the "same level" condition of the ratio test, the
+ * mnVisible / mnFound counters.  One synchronisation per call, no host round trip, integer atomics only: equal maps give equal bytes. */
+typedef struct {
+    int32_t n_levels;        /* pyramid levels of the extractor, >= 1 (8) */
+    double range_lo;         /* (0.8) */
+    double range_hi;         /* (1.2) */
+    double min_cos;          /* (0.5: within 60 degrees of the mean viewing direction) */
+} mo_map_frustum_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n_q = keypoints of the frame */
+    int32_t* level;          /* [n_q] predicted level of the point matched to each keypoint by the last pass searched (-1: none) */
+    /* filled by the call */
+    int32_t pass_in_image[4];/* plain candidates of each pass (of its last attempt): projections inside the image */
+} mo_map_frustum_out;
+int mo_map_track_frustum(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
+                         const mo_map_local_params* local_or_null, const mo_map_frustum_params*, mo_map_track_out*,
+                         mo_map_local_out* local_out_or_null, mo_map_frustum_out*);
+int mo_map_fuse_frustum(mo_map*, const mo_map_fuse_params*, const mo_map_frustum_params*, mo_map_fuse_out*);
+
 /* ---- Place recognition: a binary vocabulary, the keyframe database of a map, relocalization with preselection (bow.hip) ----------------
  * "Which keyframes look like this frame": DBoW2's L1 score of tf-idf vectors over a flat vocabulary of binary words.  Everything is
  * integer work except the logarithm of the weights (host, once per training) and the one division of the score; tests/bow_restatement.py

@@ -8,6 +8,8 @@ the projection of point r and carry one descriptor (each descriptor on two rows 
 Per (keyframes, map points): the device time of the first call (sum of its stage events; it merges) and the median of the later calls
 (nothing left to fuse: preparation and search alone), the device time of one warm track_local_map call on the same map, the ratio.
 The fuse call projects every local point into each of `window` keyframes, about window times the projections of one tracking pass.
+--frustum: after the plain calls, the same later call as fuse_map_points(frustum=True) on the same map (nothing left to fuse either
+way: preparation, the view kernels and the search), with the time it adds and the share of fuse_prep that is.
 python tools/fuse_rate.py   (one MI355X; under rocprofv3 --kernel-trace --stats for the per-kernel times)
 """
 import argparse
@@ -78,6 +80,7 @@ def main():
     ap.add_argument("--points", default="100000,1000000")
     ap.add_argument("--window", type=int, default=10)
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--frustum", action="store_true", help="also time fuse_map_points(frustum=True) on the same map")
     args = ap.parse_args()
     rng = np.random.default_rng(1)
     ctx = V.Context(device=0, max_w=W, max_h=H, max_batch=1)
@@ -105,6 +108,19 @@ def main():
                   % (n_kf, ROWS, n_pts, args.window, first["n_local"], first["n_pairs"], first["n_cand"], f_ms, first["n_absorbed"], first["n_gained"],
                      "  ".join("%s %.3f" % kv for kv in f_st.items()), np.median(later), info["n_proposals"],
                      "  ".join("%s %.3f" % kv for kv in med.items()), t, ok, ti["pass_matches"], f_ms / t, np.median(later) / t), flush=True)
+            if args.frustum:
+                m.fuse_map_points(window=args.window, image_size=(W, H), frustum=True)
+                fl, fstages = [], []
+                for _ in range(args.calls):
+                    fi = m.fuse_map_points(window=args.window, image_size=(W, H), frustum=True)
+                    ms, st = _device_ms(ctx)
+                    fl.append(ms); fstages.append(st)
+                fmed = {k: np.median([s.get(k, 0.0) for s in fstages]) for k in fstages[0]}
+                add = np.median(fl) - np.median(later)
+                print("keyframes %3d  rows %d  map_points %8d  window %2d  frustum later fuse median %.3f ms (%.3f .. %.3f; %d candidates, %d proposals: %s)"
+                      "  | plain later fuse %.3f ms (%.3f .. %.3f)  | frustum adds %.3f ms = %.2f of fuse_prep"
+                      % (n_kf, ROWS, n_pts, args.window, np.median(fl), min(fl), max(fl), fi["n_cand"], fi["n_proposals"],
+                         "  ".join("%s %.3f" % kv for kv in fmed.items()), np.median(later), min(later), max(later), add, add / fmed["fuse_prep"]), flush=True)
             m.close()
     ctx.close()
 

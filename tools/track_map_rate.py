@@ -6,6 +6,8 @@ keyframes are observed whatever the map size.  The frame sees points 0 .. 1999 (
 from a pose 1 degree and 3 cm away from the predicted one; every other point in view is a candidate whose search finds nothing.
 Per (keyframes, map points, window): the device time of one warm call (sum of its stage events, median of 10), its wall time, the
 matches and inliers of the last pass, the local-map size.
+--frustum: every line twice, the plain call and then track_local_map(frustum=True) on the same map in the same run, the second with
+the time it adds and the share of the preparation stage (track_prep: k_trk_rep and the keypoint grid) that is.
 python tools/track_map_rate.py   (one MI355X; under rocprofv3 --kernel-trace --stats for the per-kernel times)
 """
 import argparse
@@ -70,6 +72,7 @@ def main():
     ap.add_argument("--points", default="100000,1000000")
     ap.add_argument("--windows", default="10,0")
     ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--frustum", action="store_true", help="also time track_local_map(frustum=True) on the same map")
     args = ap.parse_args()
     rng = np.random.default_rng(1)
     ctx = V.Context(device=0, max_w=640, max_h=480, max_batch=1)
@@ -78,23 +81,33 @@ def main():
         for n_pts in [int(x) for x in args.points.split(",")]:
             m, qk, qd, pose0 = build(ctx, n_kf, n_pts, rng)
             for window in [int(x) for x in args.windows.split(",")]:
-                m.track_local_map(qk, qd, pose0, window=window)   # warm: buffers sized
-                wall, dev, stages = [], [], []
-                for _ in range(args.calls):
-                    t0 = time.perf_counter()
-                    ok, pose, info = m.track_local_map(qk, qd, pose0, window=window)
-                    wall.append(time.perf_counter() - t0)
-                    st = ctx.stage_times()
-                    dev.append(sum(ms for _, ms in st))
-                    agg = {}
-                    for name, ms in st:
-                        agg[name] = agg.get(name, 0.0) + ms
-                    stages.append(agg)
-                med = {k: np.median([s.get(k, 0.0) for s in stages]) for k in stages[0]}
-                print("keyframes %3d  rows %d  map_points %8d  window %2d  local %8d  track device median %.3f ms  wall median %.3f ms  ok %s  "
-                      "matches %s inliers %s  | %s"
-                      % (n_kf, ROWS, n_pts, window, info["n_local"], np.median(dev), 1e3 * np.median(wall), ok, info["pass_matches"],
-                         info["pass_inliers"], "  ".join("%s %.3f" % kv for kv in med.items())), flush=True)
+                plain = None
+                for frustum in ([False, True] if args.frustum else [False]):
+                    kw = {"frustum": True} if frustum else {}
+                    m.track_local_map(qk, qd, pose0, window=window, **kw)   # warm: buffers sized
+                    wall, dev, stages = [], [], []
+                    for _ in range(args.calls):
+                        t0 = time.perf_counter()
+                        ok, pose, info = m.track_local_map(qk, qd, pose0, window=window, **kw)
+                        wall.append(time.perf_counter() - t0)
+                        st = ctx.stage_times()
+                        dev.append(sum(ms for _, ms in st))
+                        agg = {}
+                        for name, ms in st:
+                            agg[name] = agg.get(name, 0.0) + ms
+                        stages.append(agg)
+                    med = {k: np.median([s.get(k, 0.0) for s in stages]) for k in stages[0]}
+                    extra = ""
+                    if frustum:
+                        extra = "  | frustum adds %.3f ms = %.2f of track_prep (repeats of the plain call: %.3f .. %.3f ms)" % (
+                            np.median(dev) - np.median(plain), (np.median(dev) - np.median(plain)) / med["track_prep"], min(plain), max(plain))
+                    else:
+                        plain = dev
+                    print("keyframes %3d  rows %d  map_points %8d  window %2d  %s  local %8d  track device median %.3f ms (%.3f .. %.3f)  wall median %.3f ms"
+                          "  ok %s  matches %s inliers %s  | %s%s"
+                          % (n_kf, ROWS, n_pts, window, "frustum" if frustum else "plain  ", info["n_local"], np.median(dev), min(dev), max(dev),
+                             1e3 * np.median(wall), ok, info["pass_matches"], info["pass_inliers"], "  ".join("%s %.3f" % kv for kv in med.items()), extra),
+                          flush=True)
             m.close()
     ctx.close()
 

@@ -16,6 +16,8 @@
 //   map_scan_excl + k_fuse_members   the members of every component next to each other
 //   k_fuse_count    one thread per point: survivors sort their members by index and count their merged list
 //   map_scan_excl x 2 + k_fuse_scatter   new indices and offsets; every field of every survivor into the other copy
+// mo_map_fuse_frustum: the same chain with k_view_centres and k_view_points (map_view_geom.hip, through view_enqueue) behind k_trk_rep and
+// k_fuse_search_frustum in place of k_fuse_search.
 // Integer atomics only (minima, sums, a compare-and-swap whose outcome - the component's lowest index - is the same in any order):
 // equal maps give equal bytes.  -ffp-contract=off (Makefile): the projection and the gates round like tests/fuse_restatement.py.
 #include <climits>
@@ -73,28 +75,50 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_prep(FuseView v, int32_t* __r
     nval[i] = map_point_of(v.map, i, v.lo_pos, tab); parent[i] = i; mcnt[i] = 0; mcur[i] = 0; surv[i] = TK_NONE;
 }
 
-// one thread per (point, target): the pair's proposal
-__global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FusePrm prm, FuseView v, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc,
-                                                           const double* __restrict__ kP, const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
-                                                           const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
-                                                           unsigned long long* __restrict__ key, int32_t* __restrict__ prop, FuseRes* __restrict__ res) {
+// what the frustum mode (mo_map_fuse_frustum) adds to the search's arguments (by value): the view records of the local points and the
+// camera centres of the keyframe positions (map_view_geom.hip)
+struct FuseFrustum {
+    FrustumPrm f;
+    const ViewRec* rec;
+    const double* centre;
+};
+
+// one thread per (point, target): the pair's proposal.  FR = false is mo_map_fuse's search (fr unused); FR = true: a candidate also lies
+// in the point's frustum seen from the target's centre, and is searched at its predicted level L with the octave gate [L - 1, L].
+template <bool FR> __device__ __forceinline__ void fuse_search(const FusePrm& prm, const FuseView& v, const mo_keypoint* __restrict__ kkps,
+                                                               const uint8_t* __restrict__ kdesc, const double* __restrict__ kP,
+                                                               const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
+                                                               const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                               unsigned long long* __restrict__ key, int32_t* __restrict__ prop, FuseRes* __restrict__ res,
+                                                               const FuseFrustum* fr) {
     const int t = blockIdx.y, i = blockIdx.x * FU_BLOCK + threadIdx.x;
     const MapView& mv = v.map;
     const int pos = v.lo_pos + t, slot = mv.pos_slot[pos];
     const int ro = i < mv.n_pts ? oct[i] : TK_NOT_LOCAL;
     const bool pair = ro != TK_NOT_LOCAL && !map_observes(mv, i, pos);
     double uu = 0.0, vv = 0.0;
-    const bool cand = pair && trk_project(kP + (size_t)slot * 12, mv.src.xyz[(size_t)i * 3], mv.src.xyz[(size_t)i * 3 + 1], mv.src.xyz[(size_t)i * 3 + 2],
-                                          prm.w, prm.h, &uu, &vv);
+    bool cand = pair && trk_project(kP + (size_t)slot * 12, mv.src.xyz[(size_t)i * 3], mv.src.xyz[(size_t)i * 3 + 1], mv.src.xyz[(size_t)i * 3 + 2],
+                                    prm.w, prm.h, &uu, &vv);
+    int lv = ro;   // the octave the window is scaled by
+    if constexpr (FR) {
+        if (cand)
+            cand = trk_frustum(fr->f, fr->rec[i], fr->centre + (size_t)pos * 3, mv.src.xyz[(size_t)i * 3], mv.src.xyz[(size_t)i * 3 + 1],
+                               mv.src.xyz[(size_t)i * 3 + 2], &lv);
+    }
     int bd = INT_MAX, bq = INT_MAX;
     if (cand) {
         const uint8_t* __restrict__ fdesc = kdesc + (size_t)slot * mv.row * 32;
         const uint8_t* d = rep + (size_t)i * 32;
-        trk_window(uu, vv, prm.radius * trk_scale(prm.sf, ro), ro, prm.w, prm.h, cell + (size_t)t * (TK_CELLS + 1), sorted + (size_t)t * mv.row,
-                   kkps + (size_t)slot * mv.row, [&](int q, const mo_keypoint& kp, double dx, double dy) {
-                       if (!(ba_info(prm.sf, kp.octave) * (dx * dx + dy * dy) <= prm.chi2)) return;
-                       trk_take(trk_ham(d, fdesc + (size_t)q * 32), q, bd, bq);
-                   });
+        auto visit = [&](int q, const mo_keypoint& kp, double dx, double dy) {
+            if (!(ba_info(prm.sf, kp.octave) * (dx * dx + dy * dy) <= prm.chi2)) return;
+            trk_take(trk_ham(d, fdesc + (size_t)q * 32), q, bd, bq);
+        };
+        if constexpr (FR)
+            trk_window_oct(uu, vv, prm.radius * trk_scale(prm.sf, lv), lv - 1, lv, prm.w, prm.h, cell + (size_t)t * (TK_CELLS + 1), sorted + (size_t)t * mv.row,
+                           kkps + (size_t)slot * mv.row, visit);
+        else
+            trk_window(uu, vv, prm.radius * trk_scale(prm.sf, ro), ro, prm.w, prm.h, cell + (size_t)t * (TK_CELLS + 1), sorted + (size_t)t * mv.row,
+                       kkps + (size_t)slot * mv.row, visit);
     }
     const bool acc = bd != INT_MAX && bd <= prm.max_dist;
     if (acc) atomicMin(key + (size_t)t * mv.row + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
@@ -102,6 +126,22 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FusePrm prm, FuseView 
     wave_count_add(pair, &res->n_pairs);
     wave_count_add(cand, &res->n_cand);
     wave_count_add(acc, &res->n_proposals);
+}
+
+__global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FusePrm prm, FuseView v, const mo_keypoint* __restrict__ kkps, const uint8_t* __restrict__ kdesc,
+                                                           const double* __restrict__ kP, const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
+                                                           const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                           unsigned long long* __restrict__ key, int32_t* __restrict__ prop, FuseRes* __restrict__ res) {
+    fuse_search<false>(prm, v, kkps, kdesc, kP, rep, oct, cell, sorted, key, prop, res, nullptr);
+}
+
+__global__ __launch_bounds__(FU_BLOCK) void k_fuse_search_frustum(FusePrm prm, FuseFrustum fr, FuseView v, const mo_keypoint* __restrict__ kkps,
+                                                                   const uint8_t* __restrict__ kdesc, const double* __restrict__ kP,
+                                                                   const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
+                                                                   const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                                   unsigned long long* __restrict__ key, int32_t* __restrict__ prop,
+                                                                   FuseRes* __restrict__ res) {
+    fuse_search<true>(prm, v, kkps, kdesc, kP, rep, oct, cell, sorted, key, prop, res, &fr);
 }
 
 __device__ __forceinline__ int fuse_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -250,10 +290,12 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_scatter(FuseView v, MapPts ds
     fuse_merge(v, i, mem + mbase[rt], mcnt[rt], [&](int pos, int kp) { dst.okf[at] = pos; dst.okp[at] = kp; at++; });
 }
 
-extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse_out* out) {
-    if (!m) return MO_ERR_ARG;
+// mo_map_fuse (fprm NULL: the plain search and exactly the launches it had) and mo_map_fuse_frustum
+static int fuse_run(mo_map* m, const mo_map_fuse_params* prm, const mo_map_frustum_params* fprm, mo_map_fuse_out* out) {
     mo_ctx* c = m->c;
     if (!prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (fprm && (fprm->n_levels < 1 || !std::isfinite(fprm->range_lo) || !std::isfinite(fprm->range_hi) || !std::isfinite(fprm->min_cos)))
+        return mo_fail(c, MO_ERR_ARG, "n_levels must be >= 1, range_lo, range_hi and min_cos finite");
     if (prm->w <= 0 || prm->h <= 0) return mo_fail(c, MO_ERR_ARG, "w and h must be > 0");
     if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
     if (!(prm->radius >= 0.0) || !std::isfinite(prm->radius)) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
@@ -298,8 +340,15 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     if ((rc = trk_launch_rep(m, lo_pos, b.rep, b.oct, &b.res.p->n_local)) || (rc = trk_launch_grid(m, slots, 0, nt, prm->w, prm->h, b.cell, b.sorted)))
         return rc;
     mo_stage_mark(c, "fuse_prep");
-    hipLaunchKernelGGL(k_fuse_search, dim3(pblocks, (unsigned)nt), dim3(FU_BLOCK), 0, c->stream, p, v, m->kkps, m->kdesc, m->kP, b.rep, b.oct, b.cell, b.sorted,
-                       b.key, b.prop, b.res);
+    if (fprm) {   // the view records of the local points behind k_trk_rep, the centres of the targets with them
+        FuseFrustum fr{FrustumPrm{prm->scale_factor, fprm->range_lo, fprm->range_hi, fprm->min_cos, fprm->n_levels}, nullptr, nullptr};
+        if ((rc = view_enqueue(m, b.oct, prm->scale_factor, &fr.rec, &fr.centre))) return rc;
+        mo_stage_mark(c, "fuse_view");
+        hipLaunchKernelGGL(k_fuse_search_frustum, dim3(pblocks, (unsigned)nt), dim3(FU_BLOCK), 0, c->stream, p, fr, v, m->kkps, m->kdesc, m->kP, b.rep, b.oct,
+                           b.cell, b.sorted, b.key, b.prop, b.res);
+    } else
+        hipLaunchKernelGGL(k_fuse_search, dim3(pblocks, (unsigned)nt), dim3(FU_BLOCK), 0, c->stream, p, v, m->kkps, m->kdesc, m->kP, b.rep, b.oct, b.cell,
+                           b.sorted, b.key, b.prop, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "fuse_search");
     hipLaunchKernelGGL(k_fuse_resolve, dim3((unsigned)((row + FU_BLOCK - 1) / FU_BLOCK), (unsigned)nt), dim3(FU_BLOCK), 0, c->stream, row, m->kcnt, slots, b.key,
@@ -332,4 +381,15 @@ extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse
     m->n_pts = r.n_points; m->n_obs = r.n_obs;
     out->n_points = m->n_pts; out->n_obs = m->n_obs;
     return MO_OK;
+}
+
+extern "C" int mo_map_fuse(mo_map* m, const mo_map_fuse_params* prm, mo_map_fuse_out* out) {
+    if (!m) return MO_ERR_ARG;
+    return fuse_run(m, prm, nullptr, out);
+}
+
+extern "C" int mo_map_fuse_frustum(mo_map* m, const mo_map_fuse_params* prm, const mo_map_frustum_params* fprm, mo_map_fuse_out* out) {
+    if (!m) return MO_ERR_ARG;
+    if (!fprm) return mo_fail(m->c, MO_ERR_ARG, "NULL argument");
+    return fuse_run(m, prm, fprm, out);
 }

@@ -3,7 +3,10 @@
 // (k_trk_rep) and the keypoint grid (k_trk_grid) are defined in map_track.hip and launched through the functions at the end.  Inline
 // here, the one projected-window search: trk_project (projection and image test), trk_scale (radius per octave), trk_window (cell range,
 // cell walk, box and octave gates, a visitor per keypoint that passes), trk_ham (256-bit distance), trk_take (the (dist, q) tie rule;
-// map_grow.hip's epipolar search takes its best row by it too).  Private to the library.
+// map_grow.hip's epipolar search takes its best row by it too).  The frustum mode of both searches (mo_map_track_frustum,
+// mo_map_fuse_frustum) adds trk_window_oct (the window with an octave interval), ViewRec / trk_frustum (the view record of a point, the
+// distance and angle tests, the predicted level) and trk_centre; the records come from map_view_geom.hip through view_enqueue.
+// Private to the library.
 #pragma once
 #include <climits>
 
@@ -70,6 +73,58 @@ template <class V> __device__ __forceinline__ void trk_window(double u, double v
         }
 }
 
+// trk_window with the octave gate lo <= octave <= hi in place of ro +- 1 (the frustum mode: [L - 1, L]).  Beside trk_window, not under it:
+// the plain searches keep the code they had.
+template <class V> __device__ __forceinline__ void trk_window_oct(double u, double v, double r, int lo, int hi, int w, int h,
+                                                                  const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                                  const mo_keypoint* __restrict__ fk, V visit) {
+    const int cx0 = trk_cx(u - r, w), cx1 = trk_cx(u + r, w), cy0 = trk_cy(v - r, h), cy1 = trk_cy(v + r, h);
+    for (int cy = cy0; cy <= cy1; cy++)
+        for (int cx = cx0; cx <= cx1; cx++) {
+            const int c = cy * TK_GX + cx, e1 = cell[c + 1];
+            for (int e = cell[c]; e < e1; e++) {
+                const int q = sorted[e];
+                const mo_keypoint kp = fk[q];
+                const double dx = (double)kp.x - u, dy = (double)kp.y - v;
+                if (!(fabs(dx) < r && fabs(dy) < r)) continue;
+                if (kp.octave < lo || kp.octave > hi) continue;
+                visit(q, kp, dx, dy);
+            }
+        }
+}
+
+// ---- the frustum mode (mo_map_point_views, mo_map_track_frustum, mo_map_fuse_frustum in include/vslam_amd.h) ---------------------------
+// the view record of a point: its mean viewing direction (not renormalised) and max_dist, one 16-byte load per search lane
+struct __attribute__((aligned(16))) ViewRec { float nx, ny, nz, max_dist; };
+// what the frustum test takes besides the point and the camera: mo_map_frustum_params and the scale factor of the search
+struct FrustumPrm {
+    double sf, range_lo, range_hi, min_cos;
+    int n_levels;
+};
+
+// the camera centre -R^T t of a pose
+__device__ __forceinline__ void trk_centre(const double* R, const double* t, double* C) {
+    for (int j = 0; j < 3; j++) C[j] = -(R[j] * t[0] + R[3 + j] * t[1] + R[6 + j] * t[2]);
+}
+
+// Frame::isInFrustum's distance and angle tests and PredictScale for the point (X, Y, Z) with record rc seen from the centre C: false
+// when the point is not searched, else *L = the smallest level >= 0 with dist * sf^L >= max_dist, capped at n_levels - 1.  Sums left to
+// right; a centre that is not a number (a keyframe without one) fails the first test.
+__device__ __forceinline__ bool trk_frustum(const FrustumPrm& f, const ViewRec& rc, const double* C, double X, double Y, double Z, int* L) {
+    const double px = X - C[0], py = Y - C[1], pz = Z - C[2];
+    const double dist = sqrt(px * px + py * py + pz * pz);
+    const double mx = (double)rc.max_dist;
+    if (!(dist > 0.0) || !(mx > 0.0)) return false;
+    const double mn = mx / trk_scale(f.sf, f.n_levels - 1);
+    if (dist < f.range_lo * mn || dist > f.range_hi * mx) return false;
+    if (px * (double)rc.nx + py * (double)rc.ny + pz * (double)rc.nz < f.min_cos * dist) return false;
+    double s = 1.0;
+    int l = 0;
+    while (l < f.n_levels - 1 && dist * s < mx) { s *= f.sf; l++; }
+    *L = l;
+    return true;
+}
+
 // the best match so far (bd, bq) against (dist, q): the lower distance, ties to the lower keypoint; true when (dist, q) took its place
 __device__ __forceinline__ bool trk_take(int dist, int q, int& bd, int& bq) {
     if (!(dist < bd || (dist == bd && q < bq))) return false;
@@ -85,3 +140,7 @@ int trk_launch_rep_mask(mo_map* m, const uint8_t* lmask, uint8_t* rep, int32_t* 
 // k_trk_grid, one block per grid: block b sorts the keypoints of keyframe slot (slots ? slots[b] : slot0) - kcnt[slot] rows at
 // kkps + slot * row - into cell [b][TK_CELLS + 1] and sorted [b][row]
 int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted);
+// map_view_geom.hip: k_view_centres and k_view_points on the live map (the position table uploaded by the caller), enqueued: *centre
+// [n_kf][3] by keyframe position (NaN: no centre) and *rec [point] for the points with oct[point] != TK_NOT_LOCAL (oct NULL: every
+// point), in the scratch of the view feature; both valid for the kernels enqueued behind on the context stream
+int view_enqueue(mo_map* m, const int32_t* oct, double sf, const ViewRec** rec, const double** centre);

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph) and map_io.hip (PLY text).
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views) and map_io.hip (PLY text).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
 //   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),

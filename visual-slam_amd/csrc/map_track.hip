@@ -13,6 +13,8 @@
 //     k_trk_compact one block: the winners in keypoint order (block scans), per-keypoint outputs, the retry / end decision
 //   k_trk_refine    one block of 256: 4 rounds of Gauss-Newton (Huber in rounds 0 - 2), f64 partial sums per thread, fixed-order wave
 //                   and workgroup reductions, one Cholesky solve per step
+// mo_map_track_frustum: the same chain with k_view_centres and k_view_points (map_view_geom.hip, through view_enqueue) behind k_trk_rep,
+// k_trk_search_frustum in place of k_trk_search, and k_trk_level (the predicted level per matched keypoint) behind the last pass.
 // Every device result is the same on every run: integer atomics only (sums and minima commute), fixed-order f64 reductions.
 // -ffp-contract=off (Makefile): the projection rounds like tests/track_restatement.py's elementwise numpy.
 #include <climits>
@@ -184,6 +186,28 @@ __global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* _
     }
 }
 
+// What the frustum mode adds to a tracking call (mo_map_track_frustum): its scratch, a feature of its own, so that the plain call's
+// TrackBufs is what it was.
+struct FrustumRes {
+    int32_t in_image[TK_MAX_PASS][2];     // projections inside the image, per pass and attempt
+    int32_t attempt[TK_MAX_PASS];         // the last attempt of each pass that searched
+};
+struct TrackFrustumBufs : MapFeature {
+    DevBuf<int32_t> lvl;                  // [point] predicted level of the candidates of the last attempt searched
+    DevBuf<int32_t> qlvl;                 // [row] per frame keypoint: the level of its point
+    ResBlock<FrustumRes> fres;
+    // all of it is scratch: every call's chain writes what it reads
+    template <class F> void each_scratch(F f) { f(lvl); f(qlvl); f(fres); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
+};
+// ... and what its search kernel receives on top of the plain one's arguments (by value)
+struct TrkFrustum {
+    FrustumPrm f;
+    const ViewRec* rec;
+    int32_t* lvl;
+    FrustumRes* fres;
+};
+
 // one thread per point: candidates of the pass (projection in the image), the best and second distance over the window, the claim
 __global__ __launch_bounds__(256) void k_trk_search(TrackPrm prm, int pass, int attempt, const float* __restrict__ xyz, int n_pts,
                                                     const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
@@ -214,6 +238,58 @@ __global__ __launch_bounds__(256) void k_trk_search(TrackPrm prm, int pass, int 
     if (bd == INT_MAX || bd > prm.max_dist) return;
     if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
     atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+}
+
+// k_trk_search under the frustum (mo_map_track_frustum): a candidate also lies in its point's frustum seen from the pass camera, and is
+// searched at its predicted level L with the octave gate [L - 1, L].  A kernel beside the plain one, not a mode of it: as a template
+// instance the plain search came out with another scalar register allocation (profiles/frustum_isa.txt), and it is to stay what it was.
+__global__ __launch_bounds__(256) void k_trk_search_frustum(TrackPrm prm, TrkFrustum fr, int pass, int attempt, const float* __restrict__ xyz, int n_pts,
+                                                            const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
+                                                            const mo_keypoint* __restrict__ fk, const uint8_t* __restrict__ fdesc,
+                                                            const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
+                                                            unsigned long long* __restrict__ key, TrackRes* __restrict__ res) {
+    if (!trk_active(res, attempt)) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int ro = i < n_pts ? oct[i] : TK_NOT_LOCAL;
+    bool in_image = false, cand = false;
+    double uu = 0.0, vv = 0.0;
+    int lv = 0;
+    if (ro != TK_NOT_LOCAL) {
+        double R[9], t[3], P[12], C[3];
+        pose_split(res->pose, R, t);
+        pnp_projection(prm.K, R, t, P);
+        const double X = xyz[(size_t)i * 3], Y = xyz[(size_t)i * 3 + 1], Z = xyz[(size_t)i * 3 + 2];
+        in_image = trk_project(P, X, Y, Z, prm.w, prm.h, &uu, &vv);
+        if (in_image) {
+            trk_centre(R, t, C);
+            cand = trk_frustum(fr.f, fr.rec[i], C, X, Y, Z, &lv);
+            if (cand) fr.lvl[i] = lv;
+        }
+    }
+    if (i == 0) fr.fres->attempt[pass] = attempt;
+    wave_count_add(in_image, &fr.fres->in_image[pass][attempt]);
+    wave_count_add(cand, &res->cand);
+    if (!cand) return;
+    const double r = (attempt ? 2.0 * prm.radius[pass] : prm.radius[pass]) * trk_scale(prm.sf, lv);
+    const uint8_t* d = rep + (size_t)i * 32;
+    int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
+    trk_window_oct(uu, vv, r, lv - 1, lv, prm.w, prm.h, cell, sorted, fk, [&](int q, const mo_keypoint&, double, double) {
+        const int dist = trk_ham(d, fdesc + (size_t)q * 32), was = bd;
+        if (trk_take(dist, q, bd, bq)) sd = was;
+        else if (dist < sd) sd = dist;
+    });
+    if (bd == INT_MAX || bd > prm.max_dist) return;
+    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
+    atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+}
+
+// one thread per frame keypoint, behind the last pass: the predicted level of the point it was matched to (the level and the match are
+// of the same attempt: every search that ran was followed by its compaction)
+__global__ __launch_bounds__(256) void k_trk_level(int n, const int32_t* __restrict__ qpt, const int32_t* __restrict__ lvl, int32_t* __restrict__ qlvl) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const int p = qpt[q];
+    qlvl[q] = p >= 0 ? lvl[p] : -1;
 }
 
 // one block: the claimed keypoints in keypoint order -> the match list and the per-keypoint outputs; keys reset for the next attempt;
@@ -372,11 +448,15 @@ int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int
     return MO_OK;
 }
 
-// mo_map_track (lprm NULL: the local map of the window) and mo_map_track_covisible (the local map of the local keyframes)
+// mo_map_track (lprm NULL: the local map of the window) and mo_map_track_covisible (the local map of the local keyframes); fprm: the
+// frustum mode of either (mo_map_track_frustum), NULL: the plain search and exactly the launches it had
 static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
-                     const mo_map_local_params* lprm, mo_map_local_out* lout, mo_map_track_out* out) {
+                     const mo_map_local_params* lprm, mo_map_local_out* lout, mo_map_track_out* out, const mo_map_frustum_params* fprm = nullptr,
+                     mo_map_frustum_out* fout = nullptr) {
     mo_ctx* c = m->c;
     if (!f || !K || !pose0 || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    if (fprm && (fprm->n_levels < 1 || !std::isfinite(fprm->range_lo) || !std::isfinite(fprm->range_hi) || !std::isfinite(fprm->min_cos)))
+        return mo_fail(c, MO_ERR_ARG, "n_levels must be >= 1, range_lo, range_hi and min_cos finite");
     if (prm->n_pass < 1 || prm->n_pass > TK_MAX_PASS) return mo_fail(c, MO_ERR_ARG, "n_pass must be in 1 .. 4");
     if (prm->w <= 0 || prm->h <= 0) return mo_fail(c, MO_ERR_ARG, "w and h must be > 0");
     if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
@@ -395,9 +475,11 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         out->pass_cand[k] = 0; out->pass_matches[k] = 0; out->pass_inliers[k] = 0;
     }
     out->n_pass_run = 0; out->n_local = 0; out->ok = 0; out->from_token = 0;
+    if (fout) for (int k = 0; k < TK_MAX_PASS; k++) fout->pass_in_image[k] = 0;
     int n, rc;
     mo_keypoint* fk; uint8_t* fdesc;
     auto defaults = [&](int nq) {
+        if (fout && fout->level) for (int i = 0; i < nq; i++) fout->level[i] = -1;
         if (out->point) for (int i = 0; i < nq; i++) out->point[i] = -1;
         if (out->dist) for (int i = 0; i < nq; i++) out->dist[i] = -1;
         if (out->inlier) std::memset(out->inlier, 0, (size_t)nq);
@@ -426,10 +508,25 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         (rc = trk_launch_grid(m, nullptr, m->kslots, 1, prm->w, prm->h, b.cell, b.sorted)))   // (the staged frame: the spare slot)
         return rc;
     mo_stage_mark(c, "track_prep");
+    TrackFrustumBufs* fb = nullptr;
+    TrkFrustum fr{};
+    if (fprm) {   // the view records of the local points behind k_trk_rep
+        fb = &map_feature<TrackFrustumBufs>(m);
+        const double* centre;
+        if ((rc = mo_reserve(c, fb->lvl, np, fb->qlvl, (size_t)row, fb->fres)) || (rc = view_enqueue(m, b.oct, prm->scale_factor, &fr.rec, &centre))) return rc;
+        HIPCHK(c, hipMemsetAsync(fb->fres, 0, sizeof(FrustumRes), c->stream));
+        fr.f = FrustumPrm{prm->scale_factor, fprm->range_lo, fprm->range_hi, fprm->min_cos, fprm->n_levels};
+        fr.lvl = fb->lvl; fr.fres = fb->fres;
+        mo_stage_mark(c, "track_view");
+    }
     for (int k = 0; k < prm->n_pass; k++) {
         for (int a = 0; a < 2; a++) {
-            hipLaunchKernelGGL(k_trk_search, dim3(pblocks), dim3(256), 0, c->stream, p, k, a, src.xyz, (int)m->n_pts, b.rep, b.oct, fk, fdesc, b.cell,
-                               b.sorted, b.key, b.res);
+            if (fprm)
+                hipLaunchKernelGGL(k_trk_search_frustum, dim3(pblocks), dim3(256), 0, c->stream, p, fr, k, a, src.xyz, (int)m->n_pts, b.rep, b.oct, fk, fdesc,
+                                   b.cell, b.sorted, b.key, b.res);
+            else
+                hipLaunchKernelGGL(k_trk_search, dim3(pblocks), dim3(256), 0, c->stream, p, k, a, src.xyz, (int)m->n_pts, b.rep, b.oct, fk, fdesc, b.cell,
+                                   b.sorted, b.key, b.res);
             hipLaunchKernelGGL(k_trk_compact, dim3(1), dim3(1024), 0, c->stream, p, k, a, n, fk, src.xyz, b.key, b.match, b.qpt, b.qdist, b.qinl,
                                b.res);
         }
@@ -438,6 +535,12 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         hipLaunchKernelGGL(k_trk_refine, dim3(1), dim3(TK_REFINE_BLOCK), 0, c->stream, p, k, b.match, b.minl, b.qinl, b.res);
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "track_refine");
+    }
+    if (fprm) {
+        hipLaunchKernelGGL(k_trk_level, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, b.qpt, fb->lvl, fb->qlvl);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = fb->fres.download(c))) return rc;
+        if (fout->level) HIPCHK(c, hipMemcpyAsync(fout->level, fb->qlvl, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = b.res.download(c))) return rc;
     if (out->point) HIPCHK(c, hipMemcpyAsync(out->point, b.qpt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -452,6 +555,10 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
         for (int i = 0; i < 12; i++) out->pass_pose[k][i] = r.pass_pose[k][i];
         out->pass_radius[k] = r.pass_radius[k];
         out->pass_cand[k] = r.pass_cand[k]; out->pass_matches[k] = r.pass_matches[k]; out->pass_inliers[k] = r.pass_inliers[k];
+    }
+    if (fprm) {
+        const FrustumRes& fres = fb->fres.host();
+        for (int k = 0; k < r.n_run; k++) fout->pass_in_image[k] = fres.in_image[k][fres.attempt[k] ? 1 : 0];
     }
     out->n_pass_run = r.n_run;
     out->n_local = r.n_local;
@@ -472,4 +579,17 @@ extern "C" int mo_map_track_covisible(mo_map* m, const mo_frame_ref* f, const do
     if ((rc = covis_check(m, lprm, lout))) return rc;
     lout->n_k1 = 0; lout->n_local_kf = 0; lout->ref = -1;
     return track_run(m, f, K, pose0, prm, lprm, lout, out);
+}
+
+extern "C" int mo_map_track_frustum(mo_map* m, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params* prm,
+                                    const mo_map_local_params* lprm, const mo_map_frustum_params* fprm, mo_map_track_out* out, mo_map_local_out* lout,
+                                    mo_map_frustum_out* fout) {
+    if (!m) return MO_ERR_ARG;
+    if (!fprm || !fout) return mo_fail(m->c, MO_ERR_ARG, "NULL argument");
+    if (lprm) {
+        int rc;
+        if ((rc = covis_check(m, lprm, lout))) return rc;
+        lout->n_k1 = 0; lout->n_local_kf = 0; lout->ref = -1;
+    }
+    return track_run(m, f, K, pose0, prm, lprm, lprm ? lout : nullptr, out, fprm, fout);
 }

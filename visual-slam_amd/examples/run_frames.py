@@ -146,6 +146,8 @@ def main(argv=None):
     ap.add_argument("--covisible", action="store_true", help="with --map --track-map: the local map of a frame is what the covisible keyframes "
                     "see (track_local_map(local=\"covisible\"): the keyframes observing the points the previous frame matched, and their best "
                     "covisible neighbours) instead of what the last 10 keyframes see")
+    ap.add_argument("--frustum", action="store_true", help="with --map --track-map (and --fuse): search by projection under ORB-SLAM2's frustum "
+                    "test and predicted pyramid level (track_local_map / fuse_map_points with frustum=True) with the extractor's levels and scale factor")
     ap.add_argument("--local-ba", action="store_true", help="with --map --track-map: a tracked frame that becomes a keyframe hands its matches to "
                     "the map (add_keyframe(tracked=)), and local bundle adjustment (LocalMapper.bundle_adjust) runs after it")
     ap.add_argument("--fuse", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, duplicate map points "
@@ -284,8 +286,10 @@ def main(argv=None):
             mapper.add_keyframe(frame, kps, desc, ref_pose)
             detect_loop(idx)
 
+    frustum_kw = {"frustum": True, "n_levels": int(orb["n_levels"]), "scale_factor": float(orb["scale_factor"])} if args.frustum else {}
+
     def fuse(idx):
-        fi = mapper.fuse_map_points(window=args.ba_window)
+        fi = mapper.fuse_map_points(window=args.ba_window, **frustum_kw)
         n_fuse[0] += 1
         n_fuse[1] += fi["n_absorbed"]
         n_fuse[2] += fi["n_gained"]
@@ -306,10 +310,10 @@ def main(argv=None):
         nonlocal ref_pose
         pred = predict_pose(recent[-2], recent[-1]) if len(recent) >= 2 else ref_pose
         if args.covisible:
-            ok, T, info = mapper.track_local_map(kps, desc, pred, local="covisible", seed_points=seeds[0])
+            ok, T, info = mapper.track_local_map(kps, desc, pred, local="covisible", seed_points=seeds[0], **frustum_kw)
             seeds[0] = info["point"] if ok else None
         else:
-            ok, T, info = mapper.track_local_map(kps, desc, pred)
+            ok, T, info = mapper.track_local_map(kps, desc, pred, **frustum_kw)
         if idx % 5 == 0:
             print("frame %d: track map %s, %d matches, %d inliers, t = %s" % (idx, "ok" if ok else "failed", info["pass_matches"][-1] if
                   info["n_pass_run"] else 0, info["pass_inliers"][-1] if info["n_pass_run"] else 0, np.round(T[:3, 3], 3)))

@@ -143,6 +143,23 @@ class MapLocalOut(C.Structure):
     _fields_ = [("local", C.c_void_p), ("n_k1", C.c_int32), ("n_local_kf", C.c_int32), ("ref", C.c_int32)]
 
 
+class MapViewParams(C.Structure):
+    _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32)]
+
+
+class MapViewOut(C.Structure):
+    _fields_ = [("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("ref_pos", C.c_void_p), ("ref_octave", C.c_void_p),
+                ("n_valid", C.c_void_p), ("centre", C.c_void_p), ("n_points", C.c_int64), ("n_kf", C.c_int32)]
+
+
+class MapFrustumParams(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("range_lo", C.c_double), ("range_hi", C.c_double), ("min_cos", C.c_double)]
+
+
+class MapFrustumOut(C.Structure):
+    _fields_ = [("level", C.c_void_p), ("pass_in_image", C.c_int32 * 4)]
+
+
 class MapQueryParams(C.Structure):
     _fields_ = [("n_best", C.c_int32)]
 
@@ -330,6 +347,9 @@ SIGNATURES = {
     "mo_map_covisibility": (_i, [_vp, _vp, _vp]),
     "mo_map_local_keyframes": (_i, [_vp, _vp, _vp]),
     "mo_map_track_covisible": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_point_views": (_i, [_vp, _vp, _vp]),
+    "mo_map_track_frustum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_fuse_frustum": (_i, [_vp, _vp, _vp, _vp]),
     "mo_vocab_train": (_i, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "mo_vocab_create": (_i, [_vp, _vp, _vp, C.c_int32, _vp]),
     "mo_vocab_words": (_i, [_vp]),

@@ -383,7 +383,8 @@ class LocalMapper:
                 out.add(k)
         return out
 
-    def fuse_map_points(self, window=10, radius=3.0, scale_factor=1.2, max_dist=50, chi2=5.991, image_size=None):
+    def fuse_map_points(self, window=10, radius=3.0, scale_factor=1.2, max_dist=50, chi2=5.991, image_size=None, frustum=False, n_levels=8,
+                        view_range=(0.8, 1.2), min_cos=0.5):
         """Merges map points that are the same 3D feature and gives points the observations they lack (ORB-SLAM2's SearchInNeighbors /
         Fuse / Replace; mo_map_fuse in include/vslam_amd.h states the rules): every point the last `window` keyframes (0: all) see is
         projected, under the store's own projection matrices, into each of those keyframes that does not observe it; a keypoint it
@@ -391,6 +392,10 @@ class LocalMapper:
         more observations survives and takes the other's - or to none, and becomes an observation of the point.  image_size as in
         track_local_map.  The co-visibility graph follows: per changed point, the keyframe pairs that observe it after the call less
         those that observed its parts before.
+        frustum=True (mo_map_fuse_frustum): a point is projected into a keyframe only when that keyframe's centre lies within view_range
+        of the point's scale-invariance range and within acos(min_cos) of its mean viewing direction (point_views), and it is searched at
+        the pyramid level L its distance predicts, against keypoints of octave L - 1 or L; n_cand then counts those.  n_levels: the
+        extractor's pyramid levels.
         Returns info: n_targets, n_local, n_pairs, n_cand, n_proposals, n_gained, n_edges, n_absorbed, n_points, n_obs and `into`
         (the new index of the point each old point now is)."""
         if image_size is None:
@@ -404,7 +409,11 @@ class LocalMapper:
         into = np.arange(max(n0, 1), dtype=np.int32)
         prm = V.MapFuseParams(int(image_size[0]), int(image_size[1]), int(window), float(radius), float(scale_factor), int(max_dist), float(chi2))
         out = V.MapFuseOut(into.ctypes.data)
-        self._check(self.lib.mo_map_fuse(self._h, C.byref(prm), C.byref(out)))
+        if frustum:
+            fprm = V.MapFrustumParams(int(n_levels), float(view_range[0]), float(view_range[1]), float(min_cos))
+            self._check(self.lib.mo_map_fuse_frustum(self._h, C.byref(prm), C.byref(fprm), C.byref(out)))
+        else:
+            self._check(self.lib.mo_map_fuse(self._h, C.byref(prm), C.byref(out)))
         into = into[:n0]
         self._version += 1
         self._cache = None
@@ -634,7 +643,8 @@ class LocalMapper:
 
     # ---- tracking against the map -------------------------------------------------------------------------------------------------
     def track_local_map(self, keypoints, descriptors, pose, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8,
-                        chi2=5.991, min_matches=20, min_inliers=30, image_size=None, local="window", seed_points=None, n_best=10, min_weight=15):
+                        chi2=5.991, min_matches=20, min_inliers=30, image_size=None, local="window", seed_points=None, n_best=10, min_weight=15,
+                        frustum=False, n_levels=8, view_range=(0.8, 1.2), min_cos=0.5):
         """The pose of a tracked frame in the map's frame and scale, from a predicted pose (ORB-SLAM2's TrackLocalMap: search by projection
         of the local map, then pose-only optimisation; mo_map_track in include/vslam_amd.h states the rules).  The map is not changed.
         pose: the predicted 4x4 (X_cam = R X + t; predict_pose gives the constant-velocity one).  window: keyframe positions of the
@@ -647,7 +657,13 @@ class LocalMapper:
         local: "window" - the local map is what the last `window` keyframes see; "covisible" - what the local keyframes of
         local_keyframes(seed_points, None, n_best, min_weight) see (mo_map_track_covisible; `window` is not used): seed_points is the
         `point` array a previous track_local_map on this map returned (-1 entries are skipped; None: the last keyframe and its
-        neighbours).  info then also holds `local_keyframes` (positions) and `ref_keyframe`."""
+        neighbours).  info then also holds `local_keyframes` (positions) and `ref_keyframe`.
+        frustum=True (mo_map_track_frustum, with either local map): ORB-SLAM2's isInFrustum and PredictScale - a point is searched only
+        when the pass camera stands within view_range = (0.8, 1.2) of its scale-invariance range [min_dist, max_dist] and within
+        acos(min_cos) of its mean viewing direction (point_views gives both), at the pyramid level L its distance predicts and against
+        keypoints of octave L - 1 or L, in place of the representative observation's octave +- 1.  n_levels: the extractor's pyramid
+        levels.  pass_cand then counts the points that passed; info also holds `pass_in_image` (the plain candidates) and per keypoint
+        `level` (the predicted level of its point, -1: none)."""
         if local not in ("window", "covisible"):
             raise ValueError("local: \"window\" or \"covisible\"")
         radii = [float(r) for r in radii]
@@ -668,7 +684,16 @@ class LocalMapper:
         prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
                                float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
         out = V.MapTrackOut(point.ctypes.data, dist.ctypes.data, inlier.ctypes.data)
-        if local == "covisible":
+        if frustum:
+            level = np.full(max(n, 1), -1, np.int32)
+            fprm = V.MapFrustumParams(int(n_levels), float(view_range[0]), float(view_range[1]), float(min_cos))
+            fout = V.MapFrustumOut(level.ctypes.data)
+            lprm = lout = None
+            if local == "covisible":
+                lprm, lout, mask, _seeds = self._local_args(seed_points, None, n_best, min_weight)
+            self._check(self.lib.mo_map_track_frustum(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(lprm) if lprm else None,
+                                                      C.byref(fprm), C.byref(out), C.byref(lout) if lout else None, C.byref(fout)))
+        elif local == "covisible":
             lprm, lout, mask, _seeds = self._local_args(seed_points, None, n_best, min_weight)
             self._check(self.lib.mo_map_track_covisible(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(lprm), C.byref(lout),
                                                         C.byref(out)))
@@ -682,10 +707,30 @@ class LocalMapper:
                 "pass_radius": [float(out.pass_radius[k]) for k in range(nr)], "pass_cand": [int(out.pass_cand[k]) for k in range(nr)],
                 "pass_matches": [int(out.pass_matches[k]) for k in range(nr)], "pass_inliers": [int(out.pass_inliers[k]) for k in range(nr)],
                 "n_pass_run": nr, "n_local": int(out.n_local), "from_token": bool(out.from_token)}
+        if frustum:
+            info["level"] = level[:n]
+            info["pass_in_image"] = [int(fout.pass_in_image[k]) for k in range(nr)]
         if local == "covisible":
             info["local_keyframes"] = np.flatnonzero(mask[:len(self.keyframes)]).tolist()
             info["ref_keyframe"] = int(lout.ref)
         return bool(out.ok), T, info
+
+    def point_views(self, scale_factor=1.2, n_levels=8):
+        """Where every map point was seen from (ORB-SLAM2's UpdateNormalAndDepth; mo_map_point_views in include/vslam_amd.h states the
+        rules), computed on the device from the map as it stands and the store's own projection matrices; the map is not changed.
+        Returns a dict of arrays: `normal` (n, 3) f32 the mean unit viewing direction (not renormalised), `min_dist` / `max_dist` (n,)
+        f32 the scale-invariance range, `ref_pos` (n,) the keyframe position of the reference observation (-1: none), `ref_octave`,
+        `n_valid` (the observations in the mean) and `centre` (n_kf, 3) f64 the camera centres by position (NaN: none)."""
+        n, n_kf = self._n_points, len(self.keyframes)
+        res = {"normal": np.zeros((n, 3), np.float32), "min_dist": np.zeros(n, np.float32), "max_dist": np.zeros(n, np.float32),
+               "ref_pos": np.full(n, -1, np.int32), "ref_octave": np.zeros(n, np.int32), "n_valid": np.zeros(n, np.int32),
+               "centre": np.full((n_kf, 3), np.nan)}
+        prm = V.MapViewParams(float(scale_factor), int(n_levels))
+        out = V.MapViewOut(*[res[f].ctypes.data if res[f].size else None for f in ("normal", "min_dist", "max_dist", "ref_pos", "ref_octave", "n_valid",
+                                                                                    "centre")])
+        self._check(self.lib.mo_map_point_views(self._h, C.byref(prm), C.byref(out)))
+        assert int(out.n_points) == n and int(out.n_kf) == n_kf
+        return res
 
     # ---- covisibility ---------------------------------------------------------------------------------------------------------------
     def covisibility(self):
