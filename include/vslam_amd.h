@@ -447,6 +447,8 @@ int mo_gather_map_points(mo_ctx*, const float* d_local, int rows_local, int rows
  *                            follow (the comment at its declaration below).
  *   mo_map_global_ba         global bundle adjustment behind that: all keyframes and points, matrix-free Schur conjugate gradient (the
  *                            comment at its declaration below).
+ *   mo_map_kf_redundancy, mo_map_erase_keyframes, mo_map_cull_keyframes   ORB-SLAM2's KeyFrameCulling decided on the device, and a removal
+ *                            that rewrites the observations (the comment at their declarations below).
  *   mo_map_query_keyframes, mo_map_relocalize_pre   place recognition over a binary vocabulary and relocalization against the keyframes
  *                            it selects (the comment above mo_vocab_train below).
  *   mo_map_relocalize        the absolute pose of a lost frame against the map as it stands (ORB-SLAM2's Tracking::Relocalization with
@@ -825,6 +827,75 @@ int mo_map_covisibility(mo_map*, int32_t* weights, int32_t* n_kf);
 int mo_map_local_keyframes(mo_map*, const mo_map_local_params*, mo_map_local_out*);
 int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
                            const mo_map_local_params*, mo_map_local_out*, mo_map_track_out*);
+
+/* ---- Keyframe culling by ORB-SLAM2's rule, and a removal that leaves an exact map (map_kfcull.hip) ---------------------------------------
+ * Opt-in: mo_map_add_keyframe's own counts (kf_len / kf_redundant) and mo_map_remove_keyframes are unchanged.
+ * tests/kfcull_restatement.py restates all of it in numpy.
+ *
+ * mo_map_kf_redundancy: ORB-SLAM2's LocalMapping::KeyFrameCulling for a monocular map, decided on the device from the map as it stands;
+ * read-only, nothing is stored.
+ *   asking        p = kf_pos, -1: the last keyframe.
+ *   candidates    the positions q != p with W[p][q] >= max(min_weight, 1), W the matrix of mo_map_covisibility; ordered by W[p][q]
+ *                 descending, ties to the later position (the tie rule of mo_map_local_keyframes).  n_local = their number.
+ *   observation   valid as above.  Of several valid observations of one point at one keyframe the first in entry order is that keyframe's
+ *                 observation of the point: its row, and the octave of that stored keypoint (a negative octave counts as 0).
+ *   per candidate c, in that order:
+ *                 n_points     the points with a valid observation at c (= W[c][c]).
+ *                 n_redundant  those of them that at least min_observers OTHER positions observe validly at an octave <= the octave at
+ *                              c + scale_gap.  The observers are all keyframes of the map, candidates or not; positions removed earlier in
+ *                              this call do not count.
+ *                 removed      (double)n_redundant > ratio * (double)n_points, in f64 (one product, one compare) - except position 0 and
+ *                              the positions with protect[q] != 0 (the caller's SetNotErase), which are counted and reported and stay.
+ *   sequential    the decision for c sees the removals decided before it in the order (ORB-SLAM2's SetBadFlag inside the loop): of two
+ *                 keyframes that are redundant only through each other, the first in the order goes.
+ *   outputs       in candidate order, each [n_kf] (entries from n_local on: pos -1, the rest 0); n_local, n_removed.
+ *   empty         fewer than two keyframes or no map points: MO_OK, n_local = 0, the arrays are not written.
+ *   errors        MO_ERR_ARG for NULL arguments, min_observers < 1, a ratio that is not finite, walk outside 0 .. 2 and - when the map has
+ *                 at least one keyframe - kf_pos outside -1 .. n_kf - 1.  MO_ERR_CAPACITY beyond 4096 keyframes.
+ *   The matrix, the order, the per-candidate lists and the decisions run behind each other on the context stream; one synchronisation, the
+ *   copy-out; the host takes no part in a decision.  Integer atomics only: equal maps give equal results, whichever way the candidates
+ *   are walked (walk: one launch per candidate - the default, 0 - or one workgroup through all of them, 1, which is slower).
+ *
+ * mo_map_erase_keyframes: the keyframes at `positions` (duplicates allowed) removed so that the map is the map that never had them.
+ *   observations  rebuilt into the other copy of the store: a point keeps, in entry order, its valid observations at surviving positions,
+ *                 the key rewritten to the non-negative position AFTER the removal, the row to the non-negative row.  Observations at
+ *                 erased positions and entries that name nothing are dropped.
+ *   points        xyz, colour, id and the descriptor reference are unchanged in count, order and bytes: point indices stay valid.  A
+ *                 point may be left with one observation or none and stays - a stated deviation from ORB-SLAM2, whose EraseObservation
+ *                 kills a point at two observations or fewer.  The next mo_map_add_keyframe culls it by its own rule; bundle adjustment
+ *                 ignores it already.
+ *   positions     the position table is shortened as mo_map_remove_keyframes shortens it: survivors keep their store slots (freed slots
+ *                 are not reused) and so their entries of the keyframe database.
+ *   errors        a position outside 0 .. n_kf - 1: MO_ERR_ARG, the map unchanged.  n = 0: MO_OK, nothing happens.
+ *   One synchronisation: the new observation count.
+ *
+ * mo_map_cull_keyframes: with erase = 0 mo_map_kf_redundancy; with erase = 1 the decision and the erase of what it removed in one chain:
+ * the rewrite kernels read the decision flags on the device, the host learns them and the new observation count at the one
+ * synchronisation and then shortens the position table.  When nothing is removed the map keeps its bytes. */
+typedef struct {
+    int32_t kf_pos;          /* the asking keyframe; -1: the last */
+    int32_t min_weight;      /* a candidate needs W >= max(min_weight, 1) (15) */
+    int32_t min_observers;   /* >= 1 (3) */
+    int32_t scale_gap;       /* (1) */
+    double ratio;            /* finite (0.9) */
+    const uint8_t* protect;  /* host [n_kf] by position, non-zero: never removed; may be NULL */
+    int32_t erase;           /* mo_map_cull_keyframes: 1 erases what was removed */
+    int32_t walk;            /* 0: the library's choice (one launch per candidate), 1: one workgroup walks the candidates, 2: one launch per candidate */
+} mo_map_kfcull_params;
+typedef struct {
+    /* caller-allocated [n_kf] each, may be NULL; in candidate order */
+    int32_t* pos;
+    int32_t* weight;
+    int32_t* n_points;
+    int32_t* n_redundant;
+    int32_t* removed;
+    /* filled by the call */
+    int32_t n_local, n_removed;
+    int64_t n_obs;           /* observations of the map after the call */
+} mo_map_kfcull_out;
+int mo_map_kf_redundancy(mo_map*, const mo_map_kfcull_params*, mo_map_kfcull_out*);
+int mo_map_erase_keyframes(mo_map*, const int32_t* positions, int n);
+int mo_map_cull_keyframes(mo_map*, const mo_map_kfcull_params*, mo_map_kfcull_out*);
 
 /* ---- Point views and the frustum mode of the searches (map_view_geom.hip, map_search.h) -----------------------------------------------
  * Where a map point was seen from, and ORB-SLAM2's use of it (MapPoint::UpdateNormalAndDepth, Frame::isInFrustum, MapPoint::PredictScale,

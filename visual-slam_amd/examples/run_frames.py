@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]] [--cull-keyframes]]
 """
 import argparse
 import os
@@ -155,6 +155,9 @@ def main(argv=None):
     ap.add_argument("--grow-neighbours", action="store_true", help="with --map --track-map: after each keyframe added from a tracked frame, its "
                     "keypoints without a map point are searched along their epipolar lines in the neighbour keyframes and triangulated "
                     "(LocalMapper.create_new_map_points with its default window of 10 neighbours), before --fuse and the bundle adjustment of --local-ba")
+    ap.add_argument("--cull-keyframes", action="store_true", help="with --map: after each keyframe's mapping steps, ORB-SLAM2's KeyFrameCulling asked "
+                    "from the new keyframe (LocalMapper.cull_keyframes: decided and erased on the device); the reference's own keyframe cull is "
+                    "switched off (redundancy_threshold = inf), since it leaves stale observation keys behind")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
@@ -207,11 +210,14 @@ def main(argv=None):
         ap.error("--local-ba needs --map and --track-map")
     if args.fuse and not args.track_map:
         ap.error("--fuse needs --map and --track-map")
+    if args.cull_keyframes and not args.map:
+        ap.error("--cull-keyframes needs --map")
     if args.grow_neighbours and not args.track_map:
         ap.error("--grow-neighbours needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
     n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
+    n_cull = [0, 0]      # --cull-keyframes: calls, keyframes removed
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     n_loop = [0, 0]   # --detect-loops: calls, loops found
@@ -219,6 +225,8 @@ def main(argv=None):
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
         mapper = LocalMapper(K, args.map)
+        if args.cull_keyframes:
+            mapper.redundancy_threshold = float("inf")
         if args.vocabulary and os.path.exists(args.vocabulary):
             import vslam_amd
             mapper.set_vocabulary(vslam_amd.Vocabulary.load(args.vocabulary, context=mapper.ctx))
@@ -284,6 +292,7 @@ def main(argv=None):
         recent[:] = recent[-1:] + [ref_pose]
         if mapper is not None and idx % args.keyframe_every == 0:
             mapper.add_keyframe(frame, kps, desc, ref_pose)
+            cull(idx)
             detect_loop(idx)
 
     frustum_kw = {"frustum": True, "n_levels": int(orb["n_levels"]), "scale_factor": float(orb["scale_factor"])} if args.frustum else {}
@@ -295,6 +304,15 @@ def main(argv=None):
         n_fuse[2] += fi["n_gained"]
         print("frame %d: fuse %d absorbed, %d gained (%d proposals of %d candidates), %d map points"
               % (idx, fi["n_absorbed"], fi["n_gained"], fi["n_proposals"], fi["n_cand"], fi["n_points"]))
+
+    def cull(idx):
+        if not args.cull_keyframes:
+            return
+        removed, ci = mapper.cull_keyframes()
+        n_cull[0] += 1
+        n_cull[1] += len(removed)
+        print("frame %d: keyframe cull removed %s of %d candidates (redundant points %s of %s), %d keyframes, %d observations"
+              % (idx, removed, ci["n_local"], ci["n_redundant"].tolist(), ci["n_points"].tolist(), len(mapper.keyframes), ci["n_obs"]))
 
     def grow(idx):
         gi = mapper.create_new_map_points()   # (its own window of 10 neighbours; --ba-window belongs to --local-ba and --fuse)
@@ -345,6 +363,7 @@ def main(argv=None):
                         grow(idx)
                     if args.fuse:
                         fuse(idx)
+                cull(idx)
                 detect_loop(idx)
         return ok
 
@@ -437,6 +456,10 @@ def main(argv=None):
             print("growth from neighbours: %d calls, %d points created with %d observations" % (n_grow[0], n_grow[1], n_grow[2]))
         if args.detect_loops:
             print("loop detection: %d calls, %d loops found" % (n_loop[0], n_loop[1]))
+        if args.cull_keyframes:
+            a = mapper.arrays()
+            print("keyframe cull: %d calls, %d keyframes removed, %d kept; %d map points, %.2f observations per point"
+                  % (n_cull[0], n_cull[1], len(mapper.keyframes), len(mapper.map_points), len(a["obs_kf"]) / max(len(mapper.map_points), 1)))
         if args.fuse:
             print("fusion: %d calls, %d points absorbed, %d observations gained" % (n_fuse[0], n_fuse[1], n_fuse[2]))
     return state, poses, n_map

@@ -143,6 +143,16 @@ class MapLocalOut(C.Structure):
     _fields_ = [("local", C.c_void_p), ("n_k1", C.c_int32), ("n_local_kf", C.c_int32), ("ref", C.c_int32)]
 
 
+class MapKfCullParams(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("min_weight", C.c_int32), ("min_observers", C.c_int32), ("scale_gap", C.c_int32), ("ratio", C.c_double),
+                ("protect", C.c_void_p), ("erase", C.c_int32), ("walk", C.c_int32)]
+
+
+class MapKfCullOut(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("weight", C.c_void_p), ("n_points", C.c_void_p), ("n_redundant", C.c_void_p), ("removed", C.c_void_p),
+                ("n_local", C.c_int32), ("n_removed", C.c_int32), ("n_obs", C.c_int64)]
+
+
 class MapViewParams(C.Structure):
     _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32)]
 
@@ -347,6 +357,9 @@ SIGNATURES = {
     "mo_map_covisibility": (_i, [_vp, _vp, _vp]),
     "mo_map_local_keyframes": (_i, [_vp, _vp, _vp]),
     "mo_map_track_covisible": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_kf_redundancy": (_i, [_vp, _vp, _vp]),
+    "mo_map_erase_keyframes": (_i, [_vp, _vp, _i]),
+    "mo_map_cull_keyframes": (_i, [_vp, _vp, _vp]),
     "mo_map_point_views": (_i, [_vp, _vp, _vp]),
     "mo_map_track_frustum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_fuse_frustum": (_i, [_vp, _vp, _vp, _vp]),

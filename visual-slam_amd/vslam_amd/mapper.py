@@ -510,6 +510,15 @@ class LocalMapper:
             for i, kf in enumerate(self.keyframes):
                 kf["id"] = i
             return
+        self._forget_keyframes(remove)
+        pos = np.array(sorted(remove), np.int32)
+        self._check(self.lib.mo_map_remove_keyframes(self._h, V._ptr(pos), len(pos)))
+        for i, kf in enumerate(self.keyframes):
+            kf["id"] = i
+
+    def _forget_keyframes(self, remove):
+        """the host's part of removing the keyframes at the positions `remove` (the loop that ends the reference's _cull_keyframes):
+        their co-visibility entries, their dicts, list rows and serials; the caller renumbers the ids"""
         for idx in sorted(remove, reverse=True):
             kf_id = self.keyframes[idx]["id"]
             for other in self.co_visibility_graph[kf_id]:
@@ -519,10 +528,57 @@ class LocalMapper:
             self.keyframes.pop(idx)
             self._list_rows.pop(idx)
             self._kf_serials.pop(idx)
-        pos = np.array(sorted(remove), np.int32)
-        self._check(self.lib.mo_map_remove_keyframes(self._h, V._ptr(pos), len(pos)))
+
+    # ---- keyframe culling by ORB-SLAM2's rule ---------------------------------------------------------------------------------------
+    def _keyframes_erased(self, removed):
+        """behind a device erase: _cull_keyframes' bookkeeping, and every cached view of the map dropped"""
+        self._forget_keyframes(removed)
         for i, kf in enumerate(self.keyframes):
             kf["id"] = i
+        self._version += 1
+        self._cache = None
+        self._lists = None
+        self._sync_size()
+
+    def cull_keyframes(self, kf_position=-1, min_weight=15, min_observers=3, ratio=0.9, scale_gap=1, protect=None, erase=True, walk=0):
+        """ORB-SLAM2's KeyFrameCulling asked from keyframe `kf_position` (-1: the last), decided on the device from the map as it stands
+        (mo_map_kf_redundancy / mo_map_cull_keyframes in include/vslam_amd.h state the rules): the candidates are the positions sharing
+        at least max(min_weight, 1) map points with it, most shared points first; one is removed when more than `ratio` of the points it
+        observes are observed by at least `min_observers` other keyframes at an octave no coarser than its own + `scale_gap`, keyframes
+        removed earlier in the same call not counting.  Position 0 and the positions where `protect` ([n_kf], non-zero) is set stay.
+        erase=True removes them from the map (erase_keyframes' rewrite, in the same device chain) and from the host's lists; erase=False
+        only reports.  Returns (removed_positions, info): positions ascending, as they were before the call; info holds `pos`, `weight`,
+        `n_points`, `n_redundant`, `removed` per candidate in candidate order, `n_local`, `n_removed` and `n_obs`."""
+        n_kf = len(self.keyframes)
+        names = ("pos", "weight", "n_points", "n_redundant", "removed")
+        arr = {k: np.zeros(max(n_kf, 1), np.int32) for k in names}
+        prot = None
+        if protect is not None:
+            prot = np.ascontiguousarray(np.asarray(protect).reshape(-1) != 0, np.uint8)
+            if len(prot) != n_kf:
+                raise ValueError("protect must have one entry per keyframe")
+        prm = V.MapKfCullParams(int(kf_position), int(min_weight), int(min_observers), int(scale_gap), float(ratio),
+                                prot.ctypes.data if prot is not None and n_kf else None, 1 if erase else 0, int(walk))
+        out = V.MapKfCullOut(*[arr[k].ctypes.data for k in names])
+        self._check(self.lib.mo_map_cull_keyframes(self._h, C.byref(prm), C.byref(out)))
+        n_local = int(out.n_local)
+        info = {k: arr[k][:n_local].copy() for k in names}
+        info["removed"] = info["removed"].astype(bool)
+        info.update(n_local=n_local, n_removed=int(out.n_removed), n_obs=int(out.n_obs))
+        removed = sorted(info["pos"][info["removed"]].tolist())
+        assert len(removed) == info["n_removed"]
+        if erase and removed:
+            self._keyframes_erased(removed)
+        return removed, info
+
+    def erase_keyframes(self, positions):
+        """Removes the keyframes at `positions` so that the map is the map that never had them (mo_map_erase_keyframes): every point
+        keeps its valid observations at the surviving keyframes, keyed by the positions after the removal; the points themselves, and
+        their indices, stay - also one left with a single observation or none.  The host's lists follow as after _cull_keyframes."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int64).reshape(-1), np.int32)
+        self._check(self.lib.mo_map_erase_keyframes(self._h, V._ptr(pos) if len(pos) else None, len(pos)))
+        if len(pos):
+            self._keyframes_erased(sorted(set(pos.tolist())))
 
     def update_map_points(self, new_map_points):
         """Appends the points as given.  Points without 'observed_keyframes' (the initializer's carry 'observed_frames') count as
