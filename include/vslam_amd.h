@@ -861,9 +861,9 @@ int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], co
  *                 the key rewritten to the non-negative position AFTER the removal, the row to the non-negative row.  Observations at
  *                 erased positions and entries that name nothing are dropped.
  *   points        xyz, colour, id and the descriptor reference are unchanged in count, order and bytes: point indices stay valid.  A
- *                 point may be left with one observation or none and stays - a stated deviation from ORB-SLAM2, whose EraseObservation
- *                 kills a point at two observations or fewer.  The next mo_map_add_keyframe culls it by its own rule; bundle adjustment
- *                 ignores it already.
+ *                 point may be left with one observation or none and stays: ORB-SLAM2's EraseObservation kills a point at two
+ *                 observations or fewer, and here that is mo_map_cull_points' part (its orphan_obs rule, below).  Without that call the
+ *                 next mo_map_add_keyframe culls the point by its own rule; bundle adjustment ignores it already.
  *   positions     the position table is shortened as mo_map_remove_keyframes shortens it: survivors keep their store slots (freed slots
  *                 are not reused) and so their entries of the keyframe database.
  *   errors        a position outside 0 .. n_kf - 1: MO_ERR_ARG, the map unchanged.  n = 0: MO_OK, nothing happens.
@@ -956,8 +956,9 @@ int mo_map_point_views(mo_map*, const mo_map_view_params*, mo_map_view_out*);
  *   (2) radius      r = radius * s(L) in place of s(ref_octave).
  *   (3) octave gate L - 1 <= octave <= L in place of |octave - ref_octave| <= 1.
  * The ratio rule, max_dist, claims, the retry, the refinement, fusion's chi2 gate, owners, components and merged lists are unchanged.
- * Not restated from ORB-SLAM2: the 2.5 / 4.0 radius factor by viewing cosine, the "same level" condition of the ratio test, the
- * mnVisible / mnFound counters.  One synchronisation per call, no host round trip, integer atomics only: equal maps give equal bytes. */
+ * Not restated from ORB-SLAM2: the 2.5 / 4.0 radius factor by viewing cosine, the "same level" condition of the ratio test.  The
+ * mnVisible / mnFound counters are mo_map_note_tracking's (below): the searches themselves stay read-only.
+ * One synchronisation per call, no host round trip, integer atomics only: equal maps give equal bytes. */
 typedef struct {
     int32_t n_levels;        /* pyramid levels of the extractor, >= 1 (8) */
     double range_lo;         /* (0.8) */
@@ -974,6 +975,96 @@ int mo_map_track_frustum(mo_map*, const mo_frame_ref* f, const double K[9], cons
                          const mo_map_local_params* local_or_null, const mo_map_frustum_params*, mo_map_track_out*,
                          mo_map_local_out* local_out_or_null, mo_map_frustum_out*);
 int mo_map_fuse_frustum(mo_map*, const mo_map_fuse_params*, const mo_map_frustum_params*, mo_map_fuse_out*);
+
+/* ---- The life of a map point: found / visible counters, culling by ORB-SLAM2's rule, an exact erase (map_ptcull.hip) -------------------
+ * Opt-in: no call above returns anything different, mo_map_add_keyframe's own cull is unchanged.  tests/ptcull_restatement.py restates all
+ * of it in numpy.
+ *
+ * The life record: int32 {visible, found, born, 0} per map point, part of the store (ORB-SLAM2's mnVisible, mnFound, mnFirstKFid).
+ *   ordinal       the k-th keyframe mo_map_add_keyframe stores has ordinal k, from 0 (ORB-SLAM2's mnId).  Removing or erasing keyframes
+ *                 never changes ordinals.  now = the ordinal of the last stored keyframe, 0 on a map without keyframes.
+ *   created       {1, 1, now, 0}: by the growth step of mo_map_add_keyframe (now = the ordinal of the keyframe being added), by mo_map_grow
+ *                 and by mo_map_add_points.
+ *   carried       every call that rebuilds the store (mo_map_add_keyframe's cull, mo_map_add_observations, mo_map_erase_keyframes,
+ *                 mo_map_fuse, mo_map_loop_correct, mo_map_erase_points, capacity growth) moves the record with its point, byte for byte.
+ *   merged        the survivor of a component of mo_map_fuse / mo_map_loop_correct takes visible = the sum of its members' visible and
+ *                 found = the sum of their found, formed in int64 and clamped to INT32_MAX, and keeps its own born (MapPoint::Replace).
+ *   mo_map_point_life copies the records ([n][4]) and now.  The record is not a field of mo_map_download.
+ *
+ * mo_map_note_tracking: one tracked frame recorded; mo_map_track* stay read-only, this call takes what they returned.
+ *   local         point i has a valid observation at a local position: one of the last `window` positions (0: all), or, with local_mask
+ *                 (host [n_kf]), a position whose byte is not zero.
+ *   seen[i]       i is local and its projection under P = K [R | t] lies in front of the camera and inside [0, w) x [0, h), as mo_map_track
+ *                 decides a candidate; with `frustum`, it also passes the frustum test above from C = -R^T t, its view record computed as
+ *                 mo_map_track_frustum computes it (scale_factor, frustum->n_levels).
+ *   matched[i]    some q in 0 .. n_q - 1 has point[q] == i (entries outside 0 .. n - 1 are ignored); hit[i]: some such q has inlier[q] != 0.
+ *   update        once per point and call, whatever the number of q: visible += (seen || matched), found += hit, each saturating at
+ *                 INT32_MAX.  No atomic touches a record: equal inputs give equal bytes.
+ *   outputs       n_local, n_seen, n_matched, n_found (the points with hit).  One chain, one synchronisation.
+ *   empty         no map points or no keyframes: MO_OK, zeros, nothing happens.
+ *   errors        MO_ERR_ARG for NULL arguments, K or pose not finite, w or h <= 0, window < 0, a scale_factor that is not finite and > 0,
+ *                 frustum parameters mo_map_track_frustum refuses.
+ *
+ * mo_map_points_bad: ORB-SLAM2's LocalMapping::MapPointCulling, stateless through born; read-only.
+ *   age           now - born.  tested = max_age < 0 || age <= max_age (ORB-SLAM2 drops a point from its recent list once its age reaches 3:
+ *                 with one cull per keyframe the same points are tested).
+ *   n_obs         the positions at which the point has a valid observation; of several entries at one position the first counts.
+ *   reason 1      tested && (double)found < ratio * (double)visible, in f64: one product, one compare.
+ *   reason 2      tested && not reason 1 && age >= min_age && n_obs <= max_obs.
+ *   reason 3      neither of them && n_obs <= orphan_obs, whatever the age (-1: off).  This is what mo_map_erase_keyframes leaves behind.
+ *   removed       reason != 0 && !(protect && protect[i]): a protected point reports its reason and stays.
+ *   outputs       reason [n], removed [n] (u8, may be NULL), n_tested, n_removed, n_reason[4] (points per reason, 0: none), now.
+ *   empty         no map points: MO_OK, nothing is written.  MO_ERR_ARG for NULL arguments, a ratio that is not finite, min_age < 0.
+ *
+ * mo_map_erase_points: the points with remove[i] != 0 (host [n]) leave; the map is the map the survivors alone would have built.
+ *   survivors     in their order into the other copy of the store: every point field and the life record byte for byte, every observation
+ *                 entry as stored, in entry order - entries that name nothing included.  remap[i] (may be NULL) = the new index, -1: removed.
+ *   lists         the per-keyframe lists stay those of the last cull, as after mo_map_fuse.
+ *   nothing       removed: the map keeps its bytes, remap is the identity.
+ *   One synchronisation: the new counts.
+ *
+ * mo_map_cull_points: with erase = 0 mo_map_points_bad; with erase = 1 the decision and the erase of what it removed in one chain: the
+ * scatter reads the flags on the device, the host learns the counts at the one synchronisation; remap is filled. */
+typedef struct {
+    int32_t w, h;            /* the image a projection must land in */
+    int32_t window;          /* local positions, counted from the last (0: all); not used with local_mask (10) */
+    double scale_factor;     /* > 0 (1.2): the view records of the frustum test */
+    const uint8_t* local_mask;               /* host [n_kf] by position, non-zero: local; may be NULL */
+    const mo_map_frustum_params* frustum;    /* may be NULL: the plain candidates count as seen */
+} mo_map_note_params;
+typedef struct {
+    int32_t n_local, n_seen, n_matched, n_found;
+} mo_map_note_out;
+typedef struct {
+    double ratio;            /* finite (0.25) */
+    int32_t min_age;         /* >= 0 (2) */
+    int32_t max_age;         /* < 0: every point is tested (3) */
+    int32_t max_obs;         /* (2) */
+    int32_t orphan_obs;      /* -1: off (1) */
+    const uint8_t* protect;  /* host [n] by point, non-zero: never removed; may be NULL */
+    int32_t erase;           /* mo_map_cull_points: 1 erases what was removed */
+} mo_map_ptcull_params;
+typedef struct {
+    /* caller-allocated [n] each, may be NULL */
+    uint8_t* reason;
+    uint8_t* removed;
+    int32_t* remap;          /* written by an erasing mo_map_cull_points */
+    /* filled by the call */
+    int32_t n_tested, n_removed;
+    int32_t n_reason[4];
+    int64_t now;
+    int64_t n_points, n_obs; /* of the map after the call */
+} mo_map_ptcull_out;
+typedef struct {
+    int32_t n_removed;
+    int64_t n_points, n_obs; /* of the map after the call */
+} mo_map_pterase_out;
+int mo_map_point_life(mo_map*, int32_t* life /* [n][4] */, int64_t* now);
+int mo_map_note_tracking(mo_map*, const double K[9], const double pose[12], const mo_map_note_params*, int32_t n_q, const int32_t* point,
+                         const uint8_t* inlier, mo_map_note_out*);
+int mo_map_points_bad(mo_map*, const mo_map_ptcull_params*, mo_map_ptcull_out*);
+int mo_map_erase_points(mo_map*, const uint8_t* remove, int32_t* remap, mo_map_pterase_out*);
+int mo_map_cull_points(mo_map*, const mo_map_ptcull_params*, mo_map_ptcull_out*);
 
 /* ---- Place recognition: a binary vocabulary, the keyframe database of a map, relocalization with preselection (bow.hip) ----------------
  * "Which keyframes look like this frame": DBoW2's L1 score of tf-idf vectors over a flat vocabulary of binary words.  Everything is

@@ -621,8 +621,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_obs_scatter(MapPts src, MapPts dst
     const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
     if (i == 0) { dst.off[n_pts] = *total; st[ST_NPTS] = n_pts; st[ST_NOBS] = *total; }   // (the next call's live counts)
     if (i >= n_pts) return;
-    for (int k = 0; k < 3; k++) { dst.xyz[(size_t)i * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)i * 3 + k] = src.col[(size_t)i * 3 + k]; }
-    dst.id[i] = src.id[i]; dst.dkf[i] = src.dkf[i]; dst.drow[i] = src.drow[i];
+    map_point_copy(src, i, dst, i);
     const int o0 = src.off[i], o1 = src.off[i + 1], ob = base[i];
     dst.off[i] = ob;
     for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; }

@@ -281,8 +281,8 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_scatter(FuseView v, MapPts ds
     if (!keep[i]) return;
     const MapPts& src = v.map.src;
     const int r = rank[i], ob = obase[i];
-    for (int k = 0; k < 3; k++) { dst.xyz[(size_t)r * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)r * 3 + k] = src.col[(size_t)i * 3 + k]; }
-    dst.id[r] = src.id[i]; dst.dkf[r] = src.dkf[i]; dst.drow[r] = src.drow[i];
+    map_point_copy(src, i, dst, r);
+    if (mcnt[rt] > 1) map_life_merge(src, i, mem + mbase[rt], mcnt[rt], dst, r);
     dst.off[r] = ob;
     const int o0 = src.off[i], o1 = src.off[i + 1];
     for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; }

@@ -8,6 +8,7 @@
 //              The reference indexes keyframes by list POSITION (local_mapper.py:223 self.keyframes[kf_id]); position -> slot is a
 //              small table the host rewrites when keyframes are removed (_cull_keyframes pops them and renumbers the ids).
 //   map points in the reference's list order: xyz f32 [n][3], colour u8 [n][3], id i32, descriptor reference (keyframe slot, row),
+//              the life record {visible, found, born, 0} (map_store.h: map_life_new, map_point_copy; map_ptcull.hip reads and feeds it),
 //              observations in CSR form (off [n + 1], keyframe id, keypoint index) in the dict's insertion order.  Two copies: the cull
 //              compacts from one into the other, and the host flips them once the call has succeeded.
 //
@@ -85,7 +86,7 @@ int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_
 __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__ inl, const int32_t* __restrict__ midx, const float* __restrict__ gpts,
                                                      const double* __restrict__ F, const mo_keypoint* __restrict__ qkps, const int32_t* __restrict__ qcnt,
                                                      const uint8_t* __restrict__ img, int w, int h, int ch, int prev_id, int cur_id, int prev_slot,
-                                                     MapPts dst, int32_t* __restrict__ st) {
+                                                     int born, MapPts dst, int32_t* __restrict__ st) {
     __shared__ int lw[40];
     const int nq = *qcnt;
     const int n0 = st[ST_NPTS], o0 = st[ST_NOBS];
@@ -110,6 +111,7 @@ __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__
             dst.col[(size_t)i * 3 + 0] = c0; dst.col[(size_t)i * 3 + 1] = c1; dst.col[(size_t)i * 3 + 2] = c2;
             dst.id[i] = i;                             // len(self.map_points) at creation
             dst.dkf[i] = prev_slot; dst.drow[i] = q;
+            map_life_new(dst, i, born);
             const int o = o0 + 2 * (added + r);
             dst.off[i] = o;
             dst.okf[o] = prev_id; dst.okp[o] = q;
@@ -165,10 +167,8 @@ __global__ __launch_bounds__(256) void k_map_compact(MapPts src, MapPts dst, int
     if (i == 0 && !st[ST_ERR]) dst.off[st[ST_KEPT]] = st[ST_KOBS];
     if (i >= bound || !keep[i]) return;
     const int r = rank[i], ob = obase[i];
-    dst.xyz[(size_t)r * 3] = src.xyz[(size_t)i * 3]; dst.xyz[(size_t)r * 3 + 1] = src.xyz[(size_t)i * 3 + 1]; dst.xyz[(size_t)r * 3 + 2] = src.xyz[(size_t)i * 3 + 2];
-    dst.col[(size_t)r * 3] = src.col[(size_t)i * 3]; dst.col[(size_t)r * 3 + 1] = src.col[(size_t)i * 3 + 1]; dst.col[(size_t)r * 3 + 2] = src.col[(size_t)i * 3 + 2];
+    map_point_copy(src, i, dst, r);
     const int id = src.id[i];
-    dst.id[r] = id; dst.dkf[r] = src.dkf[i]; dst.drow[r] = src.drow[i];
     dst.off[r] = ob;
     const int o0 = src.off[i], o1 = src.off[i + 1];
     for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; ent_id[ob + o - o0] = id; }
@@ -291,7 +291,8 @@ int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep) {
     if (!p.xyz || pcap > p.pcap) {
         pcap = std::max(pcap, p.pcap + p.pcap / 2);
         if ((rc = p.xyz.regrow(c, pcap * 3, np * 3)) || (rc = p.col.regrow(c, pcap * 3, np * 3)) || (rc = p.id.regrow(c, pcap, np)) ||
-            (rc = p.dkf.regrow(c, pcap, np)) || (rc = p.drow.regrow(c, pcap, np)) || (rc = p.off.regrow(c, pcap + 1, np + 1)))
+            (rc = p.dkf.regrow(c, pcap, np)) || (rc = p.drow.regrow(c, pcap, np)) || (rc = p.off.regrow(c, pcap + 1, np + 1)) ||
+            (rc = p.life.regrow(c, pcap, np)))
             return rc;
         p.pcap = pcap;
     }
@@ -527,8 +528,8 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
         const int pi = m->img_cur ^ 1;  // the previous keyframe's image
         if (!m->img[pi]) { m->img_w[pi] = m->img_h[pi] = 0; }
         hipLaunchKernelGGL(k_map_append, dim3(1), dim3(1024), 0, c->stream, m->inl, m->match.idx, m->gpts, m->F, m->kkps + (size_t)ps * rows, m->kcnt + ps,
-                           m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, m->P[m->cur].view(),
-                           m->st);
+                           m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, map_now(m),
+                           m->P[m->cur].view(), m->st);
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "map_append");
         m->id_bound = std::max<int64_t>(m->id_bound, m->n_pts + bound_new);
@@ -578,6 +579,8 @@ extern "C" int mo_map_add_points(mo_map* m, int n, const float* xyz, const uint8
         mx = std::max<int64_t>(mx, (int64_t)id[i] + 1);
     }
     HIPCHK(c, hipMemcpyAsync(p.off + b, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const std::vector<int4> life((size_t)n, make_int4(1, 1, map_now(m), 0));   // (new points: map_life_new's record)
+    HIPCHK(c, hipMemcpyAsync(p.life + b, life.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice, c->stream));
     if (no) {
         HIPCHK(c, hipMemcpyAsync(p.okf + m->n_obs, obs_kf + obs_off[0], (size_t)no * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(p.okp + m->n_obs, obs_kp + obs_off[0], (size_t)no * 4, hipMemcpyHostToDevice, c->stream));

@@ -248,8 +248,7 @@ __global__ __launch_bounds__(KC_BLOCK) void k_kc_escatter(MapView v, MapPts dst,
     if (i == 0) { dst.off[v.n_pts] = res->n_obs; st[ST_NPTS] = v.n_pts; st[ST_NOBS] = res->n_obs; }   // (the next call's live counts)
     if (i >= v.n_pts) return;
     const MapPts& src = v.src;
-    for (int k = 0; k < 3; k++) { dst.xyz[(size_t)i * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)i * 3 + k] = src.col[(size_t)i * 3 + k]; }
-    dst.id[i] = src.id[i]; dst.dkf[i] = src.dkf[i]; dst.drow[i] = src.drow[i];
+    map_point_copy(src, i, dst, i);
     int at = base[i];
     dst.off[i] = at;
     map_each_obs(v, i, [&](int, int pos, int, int kp) {

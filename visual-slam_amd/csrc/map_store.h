@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views) and map_io.hip (PLY text).
+// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase) and map_io.hip (PLY text).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
 //   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),
@@ -10,9 +10,10 @@
 //   MapView / map_view: the live map as every kernel receives it (by value);
 //   MatchView / map_match_point: the matcher's outputs read through a point_of table (restated only by lp_match of map_loop.hip, which says why);
 //   map_obs: the one reader of an observation; map_each_obs / map_observes: the walks over a point's valid observations;
+//   map_point_copy / map_life_new / map_life_merge: a point's own fields, its life record among them, through every rebuild;
 //   map_point_of: the one rule of the point_of tables (k_point_of / map_launch_point_of in map_kernels.hip, k_fuse_prep);
 //   wave_sum / wave_sum_all (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
-//   host helpers: map_window_lo, map_int32_guard, map_sync, map_stage_frame.
+//   host helpers: map_now, map_window_lo, map_int32_guard, map_sync, map_stage_frame.
 // A new reader of the map takes a MapView and these; it does not spell out the stores or restate a rule.
 // Private to the library.
 #pragma once
@@ -32,14 +33,15 @@ struct MapPts {
     float* xyz = nullptr; uint8_t* col = nullptr; int32_t* id = nullptr; int32_t* dkf = nullptr; int32_t* drow = nullptr;
     int32_t* off = nullptr;                           // [pcap + 1]
     int32_t* okf = nullptr; int32_t* okp = nullptr;   // [ocap]
+    int4* life = nullptr;                             // [pcap] {visible, found, born, 0}: map_life_new / map_point_copy / map_life_merge
     size_t pcap = 0, ocap = 0;
 };
 
 // ... and its storage (map_pts_reserve grows it)
 struct MapPtsStore {
-    DevBuf<float> xyz; DevBuf<uint8_t> col; DevBuf<int32_t> id, dkf, drow, off, okf, okp;
+    DevBuf<float> xyz; DevBuf<uint8_t> col; DevBuf<int32_t> id, dkf, drow, off, okf, okp; DevBuf<int4> life;
     size_t pcap = 0, ocap = 0;
-    MapPts view() const { return MapPts{xyz, col, id, dkf, drow, off, okf, okp, pcap, ocap}; }
+    MapPts view() const { return MapPts{xyz, col, id, dkf, drow, off, okf, okp, life, pcap, ocap}; }
 };
 
 // A feature's scratch (RelocBufs in map_reloc.hip, TrackBufs, BaBufs, FuseBufs, GrowBufs, CovisBufs, BowBufs in bow.hip, LoopBufs): a
@@ -183,6 +185,24 @@ __device__ __forceinline__ bool map_observes(const MapView& v, int i, int pos, i
     return false;
 }
 
+// ---- a point's own fields (everything but its observations) from one copy of the store into the other -------------------------------
+// Every rebuild moves a point through this, so that a field added to MapPts is added here once.  The life record {visible, found, born, 0}
+// (ORB-SLAM2's mnVisible, mnFound, mnFirstKFid; include/vslam_amd.h states its rules) moves as one 16-byte load and store.
+__device__ __forceinline__ void map_point_copy(const MapPts& src, int i, const MapPts& dst, int r) {
+    for (int k = 0; k < 3; k++) { dst.xyz[(size_t)r * 3 + k] = src.xyz[(size_t)i * 3 + k]; dst.col[(size_t)r * 3 + k] = src.col[(size_t)i * 3 + k]; }
+    dst.id[r] = src.id[i]; dst.dkf[r] = src.dkf[i]; dst.drow[r] = src.drow[i];
+    dst.life[r] = src.life[i];
+}
+// the record of a point made while the keyframe of ordinal `born` is the last stored one
+__device__ __forceinline__ void map_life_new(const MapPts& dst, int i, int born) { dst.life[i] = make_int4(1, 1, born, 0); }
+// ... and of the survivor s of a merged component with the members mem[0 .. nm) (s among them), behind map_point_copy(src, s, dst, r):
+// visible and found are the members' sums, formed in int64 and clamped to INT32_MAX; born stays the survivor's (MapPoint::Replace)
+__device__ __forceinline__ void map_life_merge(const MapPts& src, int s, const int32_t* __restrict__ mem, int nm, const MapPts& dst, int r) {
+    long long vis = 0, fnd = 0;
+    for (int a = 0; a < nm; a++) { const int4 l = src.life[mem[a]]; vis += l.x; fnd += l.y; }
+    dst.life[r] = make_int4((int)(vis > INT32_MAX ? INT32_MAX : vis), (int)(fnd > INT32_MAX ? INT32_MAX : fnd), src.life[s].z, 0);
+}
+
 // point_of: tab [position - lo_pos][row] (preset to INT_MAX) = the lowest point with a valid observation of (position, row), for the
 // positions >= lo_pos.  Point i's part of it; returns the number of its valid observations.
 __device__ __forceinline__ int map_point_of(const MapView& v, int i, int lo_pos, int32_t* __restrict__ tab) {
@@ -294,6 +314,9 @@ int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
 int map_launch_point_of(mo_map* m, int lo_pos, int n_tab_kf, int32_t* tab);
 
 // ---- host helpers of the calls ---------------------------------------------------------------------------------------------------
+// the ordinal of the last stored keyframe (0 on a map without one): slots are handed out in creation order and never reused, so the slot
+// count is the number of keyframes stored so far, whatever was removed since (ORB-SLAM2's mnId)
+inline int map_now(const mo_map* m) { return m->n_slots > 0 ? m->n_slots - 1 : 0; }
 // the first position of a window of the last `window` keyframes (0: all of them)
 inline int map_window_lo(int window, int n_kf) { return window > 0 && window < n_kf ? n_kf - window : 0; }
 // points and observations stay below half of int32 (sums of two of them are formed in int)

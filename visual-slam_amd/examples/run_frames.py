@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]]] [--cull-keyframes]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]] [--cull-points]] [--cull-keyframes]]
 """
 import argparse
 import os
@@ -158,6 +158,10 @@ def main(argv=None):
     ap.add_argument("--cull-keyframes", action="store_true", help="with --map: after each keyframe's mapping steps, ORB-SLAM2's KeyFrameCulling asked "
                     "from the new keyframe (LocalMapper.cull_keyframes: decided and erased on the device); the reference's own keyframe cull is "
                     "switched off (redundancy_threshold = inf), since it leaves stale observation keys behind")
+    ap.add_argument("--cull-points", action="store_true", help="with --map --track-map: every tracked frame is recorded in the map points' found / "
+                    "visible counters (LocalMapper.note_tracking, with the frame's local map and --frustum setting), and after each keyframe's "
+                    "mapping steps ORB-SLAM2's MapPointCulling removes the bad points (LocalMapper.cull_map_points), before --cull-keyframes; use it with "
+                    "--cull-keyframes: the reference's own keyframe cull leaves stale observation keys, which its map-point cull then raises on")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
@@ -214,11 +218,14 @@ def main(argv=None):
         ap.error("--cull-keyframes needs --map")
     if args.grow_neighbours and not args.track_map:
         ap.error("--grow-neighbours needs --map and --track-map")
+    if args.cull_points and not args.track_map:
+        ap.error("--cull-points needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
     n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
     n_cull = [0, 0]      # --cull-keyframes: calls, keyframes removed
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
+    n_ptcull = [0, 0, 0, 0]   # --cull-points: frames noted, culls, points removed, points tested
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     n_loop = [0, 0]   # --detect-loops: calls, loops found
     seeds = [None]   # --covisible: the previous frame's matched map points (indices into the map as it stands: dropped when the map changes)
@@ -306,6 +313,13 @@ def main(argv=None):
               % (idx, fi["n_absorbed"], fi["n_gained"], fi["n_proposals"], fi["n_cand"], fi["n_points"]))
 
     def cull(idx):
+        if args.cull_points:
+            removed, pi = mapper.cull_map_points()
+            n_ptcull[1] += 1
+            n_ptcull[2] += len(removed)
+            n_ptcull[3] += pi["n_tested"]
+            print("frame %d: point cull removed %d of %d tested (found ratio %d, observations %d, orphans %d), %d map points, %d observations"
+                  % (idx, len(removed), pi["n_tested"], pi["n_reason"][1], pi["n_reason"][2], pi["n_reason"][3], pi["n_points"], pi["n_obs"]))
         if not args.cull_keyframes:
             return
         removed, ci = mapper.cull_keyframes()
@@ -336,6 +350,9 @@ def main(argv=None):
             print("frame %d: track map %s, %d matches, %d inliers, t = %s" % (idx, "ok" if ok else "failed", info["pass_matches"][-1] if
                   info["n_pass_run"] else 0, info["pass_inliers"][-1] if info["n_pass_run"] else 0, np.round(T[:3, 3], 3)))
         if ok:
+            if args.cull_points:   # (before the keyframe below changes the map the matches index)
+                mapper.note_tracking(T, info, **frustum_kw)
+                n_ptcull[0] += 1
             ref_pose = T
             recent[:] = recent[-1:] + [T]
             poses.append((T[:3, :3], T[:3, 3:4]))
@@ -456,6 +473,10 @@ def main(argv=None):
             print("growth from neighbours: %d calls, %d points created with %d observations" % (n_grow[0], n_grow[1], n_grow[2]))
         if args.detect_loops:
             print("loop detection: %d calls, %d loops found" % (n_loop[0], n_loop[1]))
+        if args.cull_points:
+            a = mapper.arrays()
+            print("point cull: %d frames noted, %d calls, %d points removed of %d tested; %d map points, %.2f observations per point"
+                  % (tuple(n_ptcull) + (len(mapper.map_points), len(a["obs_kf"]) / max(len(mapper.map_points), 1))))
         if args.cull_keyframes:
             a = mapper.arrays()
             print("keyframe cull: %d calls, %d keyframes removed, %d kept; %d map points, %.2f observations per point"

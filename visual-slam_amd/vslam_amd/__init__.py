@@ -153,6 +153,29 @@ class MapKfCullOut(C.Structure):
                 ("n_local", C.c_int32), ("n_removed", C.c_int32), ("n_obs", C.c_int64)]
 
 
+class MapNoteParams(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("window", C.c_int32), ("scale_factor", C.c_double), ("local_mask", C.c_void_p),
+                ("frustum", C.c_void_p)]
+
+
+class MapNoteOut(C.Structure):
+    _fields_ = [("n_local", C.c_int32), ("n_seen", C.c_int32), ("n_matched", C.c_int32), ("n_found", C.c_int32)]
+
+
+class MapPtCullParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("min_age", C.c_int32), ("max_age", C.c_int32), ("max_obs", C.c_int32), ("orphan_obs", C.c_int32),
+                ("protect", C.c_void_p), ("erase", C.c_int32)]
+
+
+class MapPtCullOut(C.Structure):
+    _fields_ = [("reason", C.c_void_p), ("removed", C.c_void_p), ("remap", C.c_void_p), ("n_tested", C.c_int32), ("n_removed", C.c_int32),
+                ("n_reason", C.c_int32 * 4), ("now", C.c_int64), ("n_points", C.c_int64), ("n_obs", C.c_int64)]
+
+
+class MapPtEraseOut(C.Structure):
+    _fields_ = [("n_removed", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64)]
+
+
 class MapViewParams(C.Structure):
     _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32)]
 
@@ -360,6 +383,11 @@ SIGNATURES = {
     "mo_map_kf_redundancy": (_i, [_vp, _vp, _vp]),
     "mo_map_erase_keyframes": (_i, [_vp, _vp, _i]),
     "mo_map_cull_keyframes": (_i, [_vp, _vp, _vp]),
+    "mo_map_point_life": (_i, [_vp, _vp, _vp]),
+    "mo_map_note_tracking": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "mo_map_points_bad": (_i, [_vp, _vp, _vp]),
+    "mo_map_erase_points": (_i, [_vp, _vp, _vp, _vp]),
+    "mo_map_cull_points": (_i, [_vp, _vp, _vp]),
     "mo_map_point_views": (_i, [_vp, _vp, _vp]),
     "mo_map_track_frustum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_fuse_frustum": (_i, [_vp, _vp, _vp, _vp]),

@@ -580,6 +580,114 @@ class LocalMapper:
         if len(pos):
             self._keyframes_erased(sorted(set(pos.tolist())))
 
+    # ---- the life of a map point: found / visible counters, culling by ORB-SLAM2's rule -----------------------------------------------
+    def point_life(self):
+        """The life records of the map points (mo_map_point_life; include/vslam_amd.h states their rules): a dict of `visible` and
+        `found` (ORB-SLAM2's mnVisible / mnFound), `born` (the ordinal of the last stored keyframe when the point was made), each (n,)
+        int32, and `now` (that ordinal today).  Ordinals count the keyframes ever stored and never shift."""
+        n = self._n_points
+        life = np.zeros((max(n, 1), 4), np.int32)
+        now = C.c_int64(0)
+        self._check(self.lib.mo_map_point_life(self._h, V._ptr(life), C.byref(now)))
+        life = life[:n]
+        return {"visible": life[:, 0].copy(), "found": life[:, 1].copy(), "born": life[:, 2].copy(), "now": int(now.value)}
+
+    def note_tracking(self, pose, info, window=10, local_keyframes=None, frustum=False, n_levels=8, view_range=(0.8, 1.2), min_cos=0.5,
+                      scale_factor=1.2, image_size=None):
+        """Records one tracked frame in the life records (mo_map_note_tracking): `visible` grows by one for every local point that the
+        frame at `pose` (4x4) sees - its projection lies in the image and, with frustum=True, it passes track_local_map's frustum test
+        with the same parameters - or that a keypoint was matched to; `found` by one for every point an inlier match names.  info:
+        track_local_map's dict (`point`, `inlier`; its `local_keyframes`, when there, are the local map unless local_keyframes names
+        positions itself; else the last `window` keyframes, 0: all).  Returns n_local, n_seen, n_matched, n_found."""
+        if image_size is None:
+            if self.keyframes:
+                image_size = self.keyframes[-1]["image"].shape[1::-1]
+            else:
+                Km = np.asarray(self.camera_matrix, np.float64)
+                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        n_kf = len(self.keyframes)
+        if local_keyframes is None:
+            local_keyframes = info.get("local_keyframes")
+        mask = None
+        if local_keyframes is not None:
+            mask = np.zeros(max(n_kf, 1), np.uint8)
+            mask[np.asarray(local_keyframes, np.int64).reshape(-1)] = 1
+        point = np.ascontiguousarray(np.asarray(info["point"]).reshape(-1), np.int32)
+        inlier = np.ascontiguousarray(np.asarray(info["inlier"]).reshape(-1) != 0, np.uint8)
+        if len(point) != len(inlier):
+            raise ValueError("info: point and inlier must have one entry per keypoint")
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        pose12 = np.ascontiguousarray(np.asarray(pose, np.float64)[:3, :4]).reshape(12)
+        fprm = V.MapFrustumParams(int(n_levels), float(view_range[0]), float(view_range[1]), float(min_cos)) if frustum else None
+        prm = V.MapNoteParams(int(image_size[0]), int(image_size[1]), int(window), float(scale_factor), mask.ctypes.data if mask is not None else None,
+                              C.addressof(fprm) if fprm is not None else None)
+        out = V.MapNoteOut()
+        self._check(self.lib.mo_map_note_tracking(self._h, V._ptr(K), V._ptr(pose12), C.byref(prm), len(point), V._ptr(point) if len(point) else None,
+                                                  V._ptr(inlier) if len(point) else None, C.byref(out)))
+        return {k: int(getattr(out, k)) for k in ("n_local", "n_seen", "n_matched", "n_found")}
+
+    def _points_erased(self):
+        """behind a device erase of map points: what add_keyframe does after its own compaction.  Nothing on the host is keyed by point
+        index but the cached arrays (injected dicts are found through dref_kf, the per-keyframe lists hold ids and stay those of the last
+        cull); the co-visibility graph keeps the reference's increments, as after add_keyframe's cull."""
+        self._version += 1
+        self._cache = None
+        self._sync_size()
+
+    def cull_map_points(self, ratio=0.25, min_age=2, max_age=3, max_obs=2, orphan_obs=1, protect=None, erase=True):
+        """ORB-SLAM2's MapPointCulling decided on the device from the life records (mo_map_points_bad / mo_map_cull_points in
+        include/vslam_amd.h state the rules).  With age = now - born, a point of age <= max_age (max_age < 0: any) is removed when
+        found < ratio * visible (reason 1), or else when age >= min_age and at most max_obs keyframes observe it (reason 2); a point of
+        any age when at most orphan_obs keyframes observe it (reason 3; -1: off).  Points where `protect` ([n], non-zero) is set report
+        their reason and stay.  erase=True removes them in the same device chain (erase_map_points' rebuild); erase=False only reports.
+        Returns (removed_indices, info): indices ascending, as before the call; info holds `reason` and `removed` per point, `n_tested`,
+        `n_removed`, `n_reason` (4), `now`, `n_points`, `n_obs` and, when erasing, `remap` (new index per old point, -1: removed)."""
+        n = self._n_points
+        reason = np.zeros(max(n, 1), np.uint8)
+        removed = np.zeros(max(n, 1), np.uint8)
+        remap = np.arange(max(n, 1), dtype=np.int32)
+        prot = None
+        if protect is not None:
+            prot = np.ascontiguousarray(np.asarray(protect).reshape(-1) != 0, np.uint8)
+            if len(prot) != n:
+                raise ValueError("protect must have one entry per map point")
+        prm = V.MapPtCullParams(float(ratio), int(min_age), int(max_age), int(max_obs), int(orphan_obs),
+                                prot.ctypes.data if prot is not None and n else None, 1 if erase else 0)
+        out = V.MapPtCullOut(reason.ctypes.data, removed.ctypes.data, remap.ctypes.data)
+        self._check(self.lib.mo_map_cull_points(self._h, C.byref(prm), C.byref(out)))
+        info = {"reason": reason[:n], "removed": removed[:n].astype(bool), "n_tested": int(out.n_tested), "n_removed": int(out.n_removed),
+                "n_reason": [int(x) for x in out.n_reason], "now": int(out.now), "n_points": int(out.n_points), "n_obs": int(out.n_obs)}
+        gone = np.flatnonzero(info["removed"]).tolist()
+        assert len(gone) == info["n_removed"]
+        if erase:
+            info["remap"] = remap[:n]
+            if gone:
+                self._points_erased()
+        return gone, info
+
+    def erase_map_points(self, indices_or_mask):
+        """Removes map points so that the map is the map the others alone would have built (mo_map_erase_points): the survivors keep their
+        order, every field, their life records and their observation entries as stored.  indices_or_mask: point indices, or a bool mask
+        with one entry per point.  Returns remap (n,) int32: the new index of every old point, -1: removed."""
+        n = self._n_points
+        sel = np.asarray(indices_or_mask)
+        if sel.dtype == np.bool_:
+            if sel.shape != (n,):
+                raise ValueError("a mask must have one entry per map point")
+            mask = np.ascontiguousarray(sel, np.uint8)
+        else:
+            idx = sel.astype(np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= n):
+                raise IndexError("map point index out of range")
+            mask = np.zeros(n, np.uint8)
+            mask[idx] = 1
+        remap = np.arange(max(n, 1), dtype=np.int32)
+        out = V.MapPtEraseOut()
+        self._check(self.lib.mo_map_erase_points(self._h, V._ptr(mask) if n else None, V._ptr(remap), C.byref(out)))
+        if int(out.n_removed):
+            self._points_erased()
+        return remap[:n]
+
     def update_map_points(self, new_map_points):
         """Appends the points as given.  Points without 'observed_keyframes' (the initializer's carry 'observed_frames') count as
         0 observations: the next keyframe culls them, as in the reference."""
