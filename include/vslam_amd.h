@@ -617,7 +617,8 @@ int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* l
  *                 1e-10 (largest absolute entry over all unknowns, accepted or not), at lambda > 1e8, or at a reduced system that is not
  *                 positive definite (that attempt is not counted).
  *   writes        xyz of the local points (the f64 result rounded to f32) and, when at least one step was accepted, P = K [R | t] of the free keyframes.  Nothing else: no
- *                 observation is erased, no point removed; points and keyframes outside the problem keep their bytes.
+ *                 observation is erased, no point removed; points and keyframes outside the problem keep their bytes
+ *                 (mo_map_bundle_adjust_local with erase_outliers erases the outlier entries).
  *   returns       ok = the problem ran and n_inliers >= min_inliers.  An empty map, no free keyframe, or no local point: nothing runs,
  *                 nothing is written, every count is 0, ok = 0, not an error.
  * Everything is decided on the device (flags in a result block that later kernels read first): no host round trip inside the call, one
@@ -781,7 +782,8 @@ typedef struct {
 int mo_map_grow(mo_map*, const double K[9], const double* poses, const mo_map_grow_params*, mo_map_grow_out*);
 
 /* Covisibility on the device map, and the local keyframes ORB-SLAM2's Tracking::UpdateLocalKeyFrames picks from it; both read the map,
- * neither changes it.  Opt-in: mo_map_track, mo_map_bundle_adjust, mo_map_fuse and mo_map_grow keep their recency windows.
+ * neither changes it.  Opt-in: mo_map_track, mo_map_bundle_adjust, mo_map_fuse and mo_map_grow keep their recency windows
+ * (mo_map_track_covisible and mo_map_bundle_adjust_local are the covisible forms of the first two).
  *
  * mo_map_covisibility: the matrix W [n_kf][n_kf] (int32, row-major, by keyframe POSITION) into `weights` (host, may be NULL: compute
  * only) and the number of keyframes into *n_kf.  W stays resident on the device for the calls below.
@@ -827,6 +829,65 @@ int mo_map_covisibility(mo_map*, int32_t* weights, int32_t* n_kf);
 int mo_map_local_keyframes(mo_map*, const mo_map_local_params*, mo_map_local_out*);
 int mo_map_track_covisible(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*,
                            const mo_map_local_params*, mo_map_local_out*, mo_map_track_out*);
+
+/* ---- Local bundle adjustment over a set of keyframes, and the erase of single observation entries (map_ba.hip) ---------------------------
+ * Opt-in: mo_map_bundle_adjust keeps its window and erases nothing; every earlier call launches what it launched.
+ *
+ * mo_map_bundle_adjust_local: mo_map_bundle_adjust with one difference: the candidate positions are a set C, not the last `window`.
+ * prm->window is validated as mo_map_bundle_adjust validates it and not used.
+ *   C             free_mask given (host [n_kf], by position): its non-zero positions; more than 16 of them other than position 0 are
+ *                 refused with MO_ERR_ARG, not truncated.  free_mask NULL: kf_pos (-1: the last keyframe) and its n_best (0 .. 15)
+ *                 heaviest covisible neighbours, a neighbour q needing W[kf_pos][q] >= max(min_weight, 1), heaviest first, ties to the
+ *                 later position: mo_map_local_keyframes with n_seed = 0 and ref_pos = kf_pos, run inside this call's chain and read on
+ *                 the device.  Position 0 is dropped from C in both forms: it is never free, and takes part as a fixed keyframe when it
+ *                 has edges.
+ *   rules         every rule of mo_map_bundle_adjust with "candidate position" read as "position in C": a local point has >= 2 edges,
+ *                 one of them at a position in C; a position with an edge to a local point is fixed when it is not in C, else free; the
+ *                 gauge: while fewer than two keyframes are fixed, the lowest position of C that has edges becomes fixed too; a candidate
+ *                 without an edge to a local point is outside the problem.  C = the last w positions gives mo_map_bundle_adjust's bytes at
+ *                 window = w.
+ *   erase         erase_outliers != 0: when the problem ran and n_inliers >= min_inliers, the entries whose final class is 2 (chi2 above
+ *                 the threshold, non-positive depth or a projection that is not finite, after round 1) leave the observation arrays in
+ *                 the same device chain, by mo_map_erase_observations' rule.  Otherwise nothing is erased: a failed adjustment does not
+ *                 strip the map.  edge_inlier is indexed by the entries as they were before the erase.
+ *   deviations    ORB-SLAM2 frees every covisible neighbour and fixes only keyframe 0 and the outside observers; here the dense reduced
+ *                 system caps C at 16 and the two-fixed gauge stands (more keyframes: mo_map_global_ba).  ORB-SLAM2's EraseObservation
+ *                 also drops a point left with two or fewer observations; this call leaves such points in the map and reports n_under;
+ *                 mo_map_cull_points' reason 3 (orphan_obs) removes them.
+ *   errors        MO_ERR_ARG as mo_map_bundle_adjust (but for the window's width), for NULL local arguments, n_best outside 0 .. 15,
+ *                 and - when the map has a keyframe - kf_pos outside -1 .. n_kf - 1.  An empty map: nothing runs, candidate is all 0.
+ * One synchronisation, the copy-out; no floating-point atomics: two calls on equal maps give equal bytes.
+ *
+ * mo_map_erase_observations: the entries o of the observation arrays with erase[o] != 0 (host [n_obs]) leave.  Every point keeps its
+ * index, every field and its life record, and may end with no entries; the surviving entries keep their order and their stored bytes,
+ * entries that name nothing included (such an entry may be flagged too: that is how a caller clears stale keys).  The per-keyframe lists
+ * stay those of the last cull, as after mo_map_fuse.  Nothing flagged: nothing is written and the store is not rebuilt, as
+ * mo_map_erase_points behaves then.  The rebuild is entry-parallel: keep flags, one exclusive scan over the n_obs entries, one thread per
+ * entry for the copy and one per point for the offsets (off[i] = S[off[i]]); one synchronisation. */
+typedef struct {
+    const uint8_t* free_mask; /* host [n_kf] by position, non-zero: candidate; NULL: the covisible set of kf_pos */
+    int32_t kf_pos;           /* the keyframe whose neighbours are taken; -1: the last (-1) */
+    int32_t n_best;           /* neighbours taken, 0 .. 15 (15) */
+    int32_t min_weight;       /* a neighbour needs W >= max(min_weight, 1) (15) */
+    int32_t erase_outliers;   /* != 0: the entries of final class 2 are erased behind a successful adjustment (0) */
+} mo_map_ba_local_params;
+typedef struct {
+    /* caller-allocated, may be NULL */
+    uint8_t* candidate;       /* [n_kf] 1 at a position of C (before the gauge) */
+    /* filled by the call */
+    int32_t n_candidates;
+    int32_t n_erased;         /* entries erased */
+    int32_t n_under;          /* points that lost an entry and now hold fewer than two */
+    int64_t n_obs;            /* entries after the call */
+} mo_map_ba_local_out;
+typedef struct {
+    int32_t n_erased;         /* entries that left */
+    int32_t n_under;          /* points that lost an entry and now hold fewer than two */
+    int64_t n_obs;            /* entries after the call */
+} mo_map_obserase_out;
+int mo_map_bundle_adjust_local(mo_map*, const double K[9], const double* poses, const mo_map_ba_params*, const mo_map_ba_local_params*,
+                               mo_map_ba_out*, mo_map_ba_local_out*);
+int mo_map_erase_observations(mo_map*, const uint8_t* erase, mo_map_obserase_out*);
 
 /* ---- Keyframe culling by ORB-SLAM2's rule, and a removal that leaves an exact map (map_kfcull.hip) ---------------------------------------
  * Opt-in: mo_map_add_keyframe's own counts (kf_len / kf_redundant) and mo_map_remove_keyframes are unchanged.

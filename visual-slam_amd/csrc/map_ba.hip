@@ -19,6 +19,21 @@
 //   k_ba_write     xyz (f32) of the local points, kP of the free keyframes, the optional outputs
 // No floating-point atomics anywhere: sums are per-thread in index order, then fixed wave / workgroup trees.
 // -ffp-contract=off (Makefile): ba.h rounds on the device as in the host build of tests/native/ba_check.cpp.
+//
+// mo_map_bundle_adjust_local is the same chain over a set of candidate positions instead of a window (ba_run enqueues both):
+//   candidates     the caller's mask, or k_covis and k_covis_select of map_covis.hip in this chain (the covis_* pieces, as
+//                  mo_map_track_covisible runs them) and their mask read on the device; k_bal_cand drops position 0 and counts
+//   k_ba_mark_set  k_ba_mark with "position in C" for "position >= lo_pos and != 0"
+//   k_ba_setup_set k_ba_setup with the same substitution: positions outside C are fixed, the gauge takes the lowest ones of C
+//   ... every kernel from k_ba_edges to k_ba_write as above ...
+//   erase_outliers the entry erase below behind k_ba_write, gated on the device by BaRes (run, n_inliers >= min_inliers), class 2 leaves
+// The entry erase (mo_map_erase_observations; entry-parallel, no point walks its own list):
+//   k_oe_keep      one thread per entry: keep[o] (int32)
+//   map_scan_excl  over the n_obs entries: S[o] = the new place of a kept entry, the total = the new n_obs
+//   k_oe_points    one thread per point: its fields (map_point_copy) and off[i] = S[off[i]] into the other copy; the points that lost an
+//                  entry and hold fewer than two are counted in registers, one integer atomic per workgroup
+//   k_oe_entries   one thread per entry: okf / okp of a kept entry to S[o], coalesced reads, ascending writes
+// With nothing flagged both kernels return at once and the host does not flip the copies (mo_map_erase_points' behaviour).
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -485,8 +500,155 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_write(BaPrm prm, int n_pts, int
     }
 }
 
-extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* poses, const mo_map_ba_params* prm, mo_map_ba_out* out) {
-    if (!m) return MO_ERR_ARG;
+// ---- the set form and the entry erase: scratch, kernels ------------------------------------------------------------------------------
+struct BalRes { int32_t n_candidates, n_obs, n_under; };   // C before the gauge; the entries behind the erase; the points left under two
+
+struct BaLocalBufs : MapFeature {
+    DevBuf<uint8_t> cand_in, cand;                    // [n_kf] the caller's mask as given; C (position 0 dropped)
+    DevBuf<uint8_t> flag;                             // [n_obs] the caller's erase flags (mo_map_erase_observations)
+    DevBuf<int32_t> keep, S;                          // [n_obs] 1 at an entry that stays; its exclusive scan
+    ResBlock<BalRes> res;
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) { f(cand_in); f(cand); f(flag); f(keep); f(S); f(res); }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
+};
+
+// C = the non-zero positions of `in` (the caller's mask, or covis_mask: the reference keyframe and its neighbours) except position 0
+__global__ __launch_bounds__(BA_BLOCK) void k_bal_cand(const uint8_t* __restrict__ in, int n_kf, uint8_t* __restrict__ cand, BalRes* __restrict__ res) {
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    int n = 0;
+    for (int p = threadIdx.x; p < n_kf; p += BA_BLOCK) {
+        const bool in_c = p != 0 && in[p] != 0;
+        cand[p] = in_c;
+        n += in_c;
+    }
+    n = wave_sum_int(n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&cnt, n);
+    __syncthreads();
+    if (threadIdx.x == 0) res->n_candidates = cnt;
+}
+
+// k_ba_mark over a set: local points have >= 2 edges, one of them at a position in C
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_mark_set(MapView v, const uint8_t* __restrict__ cand, int32_t* __restrict__ loc, int32_t* __restrict__ ecnt,
+                                                          int32_t* __restrict__ kf_edge) {
+    const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (i >= v.n_pts) return;
+    int nv = 0;
+    bool fr = false;
+    map_each_obs(v, i, [&](int, int pos, int, int) { nv++; fr |= cand[pos] != 0; return false; });
+    const bool local = nv >= 2 && fr;
+    loc[i] = local;
+    ecnt[i] = local ? nv : 0;
+    if (local) map_each_obs(v, i, [&](int, int pos, int, int) { kf_edge[pos] = 1; return false; });
+}
+
+// k_ba_setup over a set: a position with edges outside C is fixed; those of C, in position order, are fixed too until two keyframes are
+// (the gauge), the rest are free
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_setup_set(BaPrm prm, const uint8_t* __restrict__ cand, const int32_t* __restrict__ kf_edge,
+                                                           int32_t* __restrict__ kf_fidx, BaRes* __restrict__ res) {
+    __shared__ int nfix;
+    if (threadIdx.x == 0) nfix = 0;
+    __syncthreads();
+    for (int pos = threadIdx.x; pos < prm.n_kf; pos += BA_BLOCK) {
+        if (cand[pos]) continue;
+        const int has = kf_edge[pos];
+        kf_fidx[pos] = has ? BA_KF_FIXED : BA_KF_OUT;
+        if (has) atomicAdd(&nfix, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x) return;
+    int nfixed = nfix, nfree = 0;
+    for (int pos = 0; pos < prm.n_kf; pos++) {
+        if (!cand[pos]) continue;
+        if (!kf_edge[pos]) { kf_fidx[pos] = BA_KF_OUT; continue; }
+        if (nfixed < 2) { kf_fidx[pos] = BA_KF_FIXED; nfixed++; }
+        else if (nfree < BA_MAX_FREE) { kf_fidx[pos] = nfree; res->free_pos[nfree++] = pos; }
+        else kf_fidx[pos] = BA_KF_FIXED;   // (the host refuses sets of more than BA_MAX_FREE: not reached)
+    }
+    res->n_free = nfree; res->n_fixed = nfixed;
+    res->run = nfree > 0 && res->n_local > 0;
+}
+
+// entry o leaves where the caller's flag is set (gate NULL) or, behind a bundle adjustment, where its final class is 2 and the problem ran
+// and ended with >= min_inliers inliers (a failed adjustment erases nothing)
+__global__ __launch_bounds__(BA_BLOCK) void k_oe_keep(const uint8_t* __restrict__ flag, const BaRes* __restrict__ gate, int min_inliers, int n_obs,
+                                                      int32_t* __restrict__ keep) {
+    const int o = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (o >= n_obs) return;
+    const bool gone = gate ? gate->run && gate->n_inliers >= min_inliers && flag[o] == 2 : flag[o] != 0;
+    keep[o] = !gone;
+}
+
+// the place of entry o behind the erase; o == n_obs (the end of the last list): the total
+__device__ __forceinline__ int oe_place(const int32_t* __restrict__ S, int o, int n_obs, int total) { return o < n_obs ? S[o] : total; }
+
+// every point's fields and its new offset into the other copy (the points keep their indices); workgroups stride over the points and add
+// their count of points that lost an entry and hold fewer than two once
+__global__ __launch_bounds__(BA_BLOCK) void k_oe_points(MapPts src, MapPts dst, int n_pts, int n_obs, const int32_t* __restrict__ S, BalRes* res,
+                                                        int32_t* __restrict__ st) {
+    __shared__ int sw[BA_BLOCK / 64];
+    const int total = res->n_obs;
+    if (total == n_obs) return;   // (nothing leaves: nothing is written, the host does not flip the copies)
+    int under = 0;
+    for (int i = blockIdx.x * BA_BLOCK + threadIdx.x; i < n_pts; i += gridDim.x * BA_BLOCK) {
+        const int a = src.off[i], b = src.off[i + 1];
+        const int na = oe_place(S, a, n_obs, total), nb = oe_place(S, b, n_obs, total);
+        map_point_copy(src, i, dst, i);
+        dst.off[i] = na;
+        under += nb - na < b - a && nb - na < 2;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { dst.off[n_pts] = total; st[ST_NPTS] = n_pts; st[ST_NOBS] = total; }   // (the next call's live counts)
+    under = wave_sum_int(under);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = under;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < BA_BLOCK / 64; w++) t += sw[w];
+        if (t) atomicAdd(&res->n_under, t);
+    }
+}
+
+// a kept entry's stored bytes at its new place
+__global__ __launch_bounds__(BA_BLOCK) void k_oe_entries(MapPts src, MapPts dst, int n_obs, const int32_t* __restrict__ keep, const int32_t* __restrict__ S,
+                                                         const BalRes* __restrict__ res) {
+    const int o = blockIdx.x * BA_BLOCK + threadIdx.x;
+    if (o >= n_obs || res->n_obs == n_obs || !keep[o]) return;
+    const int d = S[o];
+    dst.okf[d] = src.okf[o]; dst.okp[d] = src.okp[o];
+}
+
+#define OE_MAX_BLOCKS 2048   // workgroups of k_oe_points (one atomic each)
+
+// keep -> S and the two copies enqueued (keep, S and the other copy of the store reserved by the caller, res zeroed in front)
+static int oe_enqueue(mo_map* m, BaLocalBufs& lb, const uint8_t* flag, const BaRes* gate, int min_inliers) {
+    mo_ctx* c = m->c;
+    const size_t np = (size_t)m->n_pts, no = (size_t)m->n_obs;
+    const unsigned oblocks = (unsigned)((no + BA_BLOCK - 1) / BA_BLOCK);
+    const unsigned pblocks = (unsigned)std::min<size_t>((np + BA_BLOCK - 1) / BA_BLOCK, OE_MAX_BLOCKS);
+    const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
+    int rc;
+    hipLaunchKernelGGL(k_oe_keep, dim3(oblocks), dim3(BA_BLOCK), 0, c->stream, flag, gate, min_inliers, (int)no, lb.keep);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = map_scan_excl(m, lb.keep, lb.S, (int)no, &lb.res.p->n_obs))) return rc;
+    hipLaunchKernelGGL(k_oe_points, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, src, dst, (int)np, (int)no, lb.S, lb.res, m->st);
+    hipLaunchKernelGGL(k_oe_entries, dim3(oblocks), dim3(BA_BLOCK), 0, c->stream, src, dst, (int)no, lb.keep, lb.S, lb.res);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "obs_erase");
+    return MO_OK;
+}
+
+// behind the synchronisation: the copies flipped, the count taken; returns the number of entries that left
+static int32_t oe_finish(mo_map* m, const BalRes& r) {
+    const int64_t gone = m->n_obs - r.n_obs;
+    if (gone) { m->cur ^= 1; m->n_obs = r.n_obs; }
+    return (int32_t)gone;
+}
+
+// mo_map_bundle_adjust (lprm NULL: the window form and exactly the launches it had) and mo_map_bundle_adjust_local
+static int ba_run(mo_map* m, const double K[9], const double* poses, const mo_map_ba_params* prm, mo_map_ba_out* out, const mo_map_ba_local_params* lprm,
+                  mo_map_ba_local_out* lout) {
     mo_ctx* c = m->c;
     if (!K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     const int n_kf = (int)m->pos_slot.size();
@@ -500,8 +662,18 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         if (!std::isfinite(K[i])) return mo_fail(c, MO_ERR_ARG, "K must be finite");
     for (size_t i = 0; i < (size_t)n_kf * 12; i++)
         if (!std::isfinite(poses[i])) return mo_fail(c, MO_ERR_ARG, "poses must be finite");
-    const int lo_pos = map_window_lo(prm->window, n_kf);
-    if (n_kf - std::max(lo_pos, 1) > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a window of at most 16");
+    const int lo_pos = lprm ? 0 : map_window_lo(prm->window, n_kf);   // (the set form validates the window and does not use it)
+    if (!lprm && n_kf - std::max(lo_pos, 1) > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a window of at most 16");
+    if (lprm) {
+        if (lprm->n_best < 0 || lprm->n_best > BA_MAX_FREE - 1) return mo_fail(c, MO_ERR_ARG, "n_best must be in 0 .. 15");
+        if (n_kf > 0 && (lprm->kf_pos < -1 || lprm->kf_pos >= n_kf)) return mo_fail(c, MO_ERR_ARG, "kf_pos must be -1 or a keyframe position");
+        int n_set = 0;
+        for (int p = 1; lprm->free_mask && p < n_kf; p++) n_set += lprm->free_mask[p] != 0;
+        if (n_set > BA_MAX_FREE) return mo_fail(c, MO_ERR_ARG, "more than 16 free keyframes: give a set of at most 16 positions");
+        if (lout->candidate) std::memset(lout->candidate, 0, (size_t)n_kf);
+        lout->n_candidates = lout->n_erased = lout->n_under = 0;
+        lout->n_obs = m->n_obs;
+    }
     MAP_ENTER(m);
     HostClock clk(c);
     for (int i = 0; i < 3; i++) out->cost[i] = 0.0;
@@ -523,8 +695,28 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
         return rc;
     if (out->points_out && (rc = mo_reserve(c, b.pout, np * 3))) return rc;
     if ((rc = mo_reserve(c, b.res, b.S, BA_MAX_DIM * BA_MAX_DIM + 2 * BA_MAX_DIM))) return rc;
+    BaLocalBufs* lb = lprm ? &map_feature<BaLocalBufs>(m) : nullptr;
+    const bool erase = lprm && lprm->erase_outliers != 0;
+    if (lb && (rc = mo_reserve(c, lb->cand_in, (size_t)n_kf, lb->cand, (size_t)n_kf, lb->res))) return rc;
+    if (erase && ((rc = mo_reserve(c, lb->keep, no, lb->S, no)) || (rc = map_pts_reserve(m, m->cur ^ 1, np, no, false)))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
+    if (lb) {   // C on the device: the caller's set, or the covisible neighbours of kf_pos selected in this chain
+        HIPCHK(c, hipMemsetAsync(lb->res, 0, sizeof(BalRes), c->stream));
+        const uint8_t* in = lb->cand_in;
+        if (lprm->free_mask) {
+            // (from the caller's pageable array, as mo_map_erase_points copies `remove` and mo_map_cull_points `protect`: the runtime stages
+            // a pageable source before hipMemcpyAsync returns, so the array is the caller's again on every return path, the error ones too)
+            HIPCHK(c, hipMemcpyAsync(lb->cand_in, lprm->free_mask, (size_t)n_kf, hipMemcpyHostToDevice, c->stream));
+        } else {
+            mo_map_local_params q{};
+            q.seed_points = nullptr; q.n_seed = 0; q.ref_pos = lprm->kf_pos; q.n_best = lprm->n_best; q.min_weight = lprm->min_weight;
+            if ((rc = covis_enqueue(m)) || (rc = covis_select_enqueue(m, &q))) return rc;
+            in = covis_mask(m);
+        }
+        hipLaunchKernelGGL(k_bal_cand, dim3(1), dim3(BA_BLOCK), 0, c->stream, in, n_kf, lb->cand, lb->res);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipMemcpyAsync(b.poseC, poses, (size_t)n_kf * 96, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.poseT, b.poseC, (size_t)n_kf * 96, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(b.kf_edge, 0, (size_t)n_kf * 4, c->stream));
@@ -537,11 +729,13 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     const unsigned wblocks = (unsigned)((std::max(np, no) + BA_BLOCK - 1) / BA_BLOCK);
     double* dcv = b.S + BA_MAX_DIM * BA_MAX_DIM + BA_MAX_DIM;
     hipLaunchKernelGGL(k_ba_init, dim3(1), dim3(64), 0, c->stream, b.res);
-    hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, lo_pos, b.loc, b.ecnt, b.kf_edge);
+    if (lb) hipLaunchKernelGGL(k_ba_mark_set, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, lb->cand, b.loc, b.ecnt, b.kf_edge);
+    else hipLaunchKernelGGL(k_ba_mark, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, lo_pos, b.loc, b.ecnt, b.kf_edge);
     HIPCHK(c, hipGetLastError());
     if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, &b.res.p->n_local))) return rc;
     if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, &b.res.p->n_edges))) return rc;
-    hipLaunchKernelGGL(k_ba_setup, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, b.kf_edge, b.kf_fidx, b.res);
+    if (lb) hipLaunchKernelGGL(k_ba_setup_set, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, lb->cand, b.kf_edge, b.kf_fidx, b.res);
+    else hipLaunchKernelGGL(k_ba_setup, dim3(1), dim3(BA_BLOCK), 0, c->stream, p, b.kf_edge, b.kf_fidx, b.res);
     hipLaunchKernelGGL(k_ba_edges, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, v, m->kkps, p.sf, b.loc, b.lrank, b.ebase, b.lpt, b.eoff, b.X, b.e_kf, b.e_obs,
                        b.e_xy, b.e_info, b.e_inl, b.res);
     hipLaunchKernelGGL(k_ba_cost, dim3(pblocks), dim3(BA_BLOCK), 0, c->stream, p, 0, b.eoff, b.X, b.e_kf, b.e_xy, b.e_info, b.e_inl, b.poseC, b.pc, b.pn, b.res);
@@ -569,14 +763,24 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
                        out->points_out ? b.pout.p : nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.poseC, m->kP, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "ba_write");
+    if (erase && (rc = oe_enqueue(m, *lb, b.einl, b.res, prm->min_inliers))) return rc;
     std::vector<int32_t> fidx(out->kf_state ? (size_t)n_kf : 0);
     if ((rc = b.res.download(c))) return rc;
+    if (lb) {
+        if ((rc = lb->res.download(c))) return rc;
+        if (lout->candidate) HIPCHK(c, hipMemcpyAsync(lout->candidate, lb->cand, (size_t)n_kf, hipMemcpyDeviceToHost, c->stream));
+    }
     if (out->poses_out) HIPCHK(c, hipMemcpyAsync(out->poses_out, b.poseC, (size_t)n_kf * 96, hipMemcpyDeviceToHost, c->stream));
     if (out->edge_inlier) HIPCHK(c, hipMemcpyAsync(out->edge_inlier, b.einl, no, hipMemcpyDeviceToHost, c->stream));
     if (out->points_out) HIPCHK(c, hipMemcpyAsync(out->points_out, b.pout, np * 24, hipMemcpyDeviceToHost, c->stream));
     if (out->kf_state) HIPCHK(c, hipMemcpyAsync(fidx.data(), b.kf_fidx, (size_t)n_kf * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = map_sync(c, clk))) return rc;
     const BaRes& r = b.res.host();
+    if (lb) {
+        const BalRes& lr = lb->res.host();
+        lout->n_candidates = lr.n_candidates;
+        if (erase) { lout->n_erased = oe_finish(m, lr); lout->n_under = lr.n_under; lout->n_obs = m->n_obs; }
+    }
     if (!r.run) return MO_OK;   // no free keyframe with an edge, or no local point
     out->n_local = r.n_local;
     for (int i = 0; i < 3; i++) out->cost[i] = r.cost[i];
@@ -585,6 +789,41 @@ extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* 
     for (int k = 0; k < 2; k++) { out->steps[k] = r.steps[k]; out->accepted[k] = r.accepted[k]; }
     if (out->kf_state) for (int i = 0; i < n_kf; i++) out->kf_state[i] = fidx[i] >= 0 ? 2 : fidx[i] == BA_KF_FIXED ? 1 : 0;
     out->ok = r.n_inliers >= prm->min_inliers;
+    return MO_OK;
+}
+
+extern "C" int mo_map_bundle_adjust(mo_map* m, const double K[9], const double* poses, const mo_map_ba_params* prm, mo_map_ba_out* out) {
+    if (!m) return MO_ERR_ARG;
+    return ba_run(m, K, poses, prm, out, nullptr, nullptr);
+}
+
+extern "C" int mo_map_bundle_adjust_local(mo_map* m, const double K[9], const double* poses, const mo_map_ba_params* prm, const mo_map_ba_local_params* lprm,
+                                          mo_map_ba_out* out, mo_map_ba_local_out* lout) {
+    if (!m) return MO_ERR_ARG;
+    if (!lprm || !lout) return mo_fail(m->c, MO_ERR_ARG, "NULL argument");
+    return ba_run(m, K, poses, prm, out, lprm, lout);
+}
+
+extern "C" int mo_map_erase_observations(mo_map* m, const uint8_t* erase, mo_map_obserase_out* out) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (!out || (m->n_obs > 0 && !erase)) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    out->n_erased = out->n_under = 0; out->n_obs = m->n_obs;
+    if (m->n_pts == 0 || m->n_obs == 0) return MO_OK;
+    int rc;
+    if ((rc = map_int32_guard(m))) return rc;
+    MAP_ENTER(m);
+    HostClock clk(c);
+    BaLocalBufs& lb = map_feature<BaLocalBufs>(m);
+    const size_t np = (size_t)m->n_pts, no = (size_t)m->n_obs;
+    if ((rc = mo_reserve(c, lb.flag, no, lb.keep, no, lb.S, no, lb.res)) || (rc = map_pts_reserve(m, m->cur ^ 1, np, no, false))) return rc;
+    mo_stage_begin(c);
+    HIPCHK(c, hipMemsetAsync(lb.res, 0, sizeof(BalRes), c->stream));
+    HIPCHK(c, hipMemcpyAsync(lb.flag, erase, no, hipMemcpyHostToDevice, c->stream));   // (pageable, staged by the runtime: see ba_run)
+    mo_stage_mark(c, "obs_flags");   // (the upload apart from the rebuild's stage)
+    if ((rc = oe_enqueue(m, lb, lb.flag, nullptr, 0)) || (rc = lb.res.download(c)) || (rc = map_sync(c, clk))) return rc;
+    const BalRes& r = lb.res.host();
+    out->n_erased = oe_finish(m, r); out->n_under = r.n_under; out->n_obs = m->n_obs;
     return MO_OK;
 }
 

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10]] [--cull-points]] [--cull-keyframes]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes]]
 """
 import argparse
 import os
@@ -163,6 +163,11 @@ def main(argv=None):
                     "mapping steps ORB-SLAM2's MapPointCulling removes the bad points (LocalMapper.cull_map_points), before --cull-keyframes; use it with "
                     "--cull-keyframes: the reference's own keyframe cull leaves stale observation keys, which its map-point cull then raises on")
     ap.add_argument("--ba-window", type=int, default=10, help="with --local-ba: keyframes the bundle adjustment frees, counted from the last (at most 16)")
+    ap.add_argument("--ba-covisible", action="store_true", help="with --local-ba: the bundle adjustment frees the new keyframe and its covisible "
+                    "neighbours (LocalMapper.bundle_adjust(local=\"covisible\"): at most 15 keyframes sharing 15 points with it), not the last --ba-window")
+    ap.add_argument("--ba-erase-outliers", action="store_true", help="with --local-ba: the observations a bundle adjustment ends with as outliers are "
+                    "erased from the map on the device (LocalMapper.bundle_adjust(erase_outliers=True)); with --cull-points the cull that follows "
+                    "removes the points left under-observed")
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
@@ -212,6 +217,8 @@ def main(argv=None):
         ap.error("--covisible needs --map and --track-map")
     if args.local_ba and not args.track_map:
         ap.error("--local-ba needs --map and --track-map")
+    if (args.ba_covisible or args.ba_erase_outliers) and not args.local_ba:
+        ap.error("--ba-covisible and --ba-erase-outliers need --local-ba")
     if args.fuse and not args.track_map:
         ap.error("--fuse needs --map and --track-map")
     if args.cull_keyframes and not args.map:
@@ -222,6 +229,7 @@ def main(argv=None):
         ap.error("--cull-points needs --map and --track-map")
     mapper, first, ref_pose = None, None, np.eye(4)
     n_ba = [0, 0]   # --local-ba: calls, calls that ended ok
+    n_ba_erased = [0, 0]   # --ba-erase-outliers: entries erased, points left with fewer than two
     n_fuse = [0, 0, 0]   # --fuse: calls, points absorbed, observations gained
     n_cull = [0, 0]      # --cull-keyframes: calls, keyframes removed
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
@@ -364,12 +372,21 @@ def main(argv=None):
                         grow(idx)
                     if args.fuse:
                         fuse(idx)
-                    ba_ok, ba = mapper.bundle_adjust(window=args.ba_window)
+                    if args.ba_covisible or args.ba_erase_outliers:
+                        ba_ok, ba = mapper.bundle_adjust(window=args.ba_window, local="covisible" if args.ba_covisible else "window",
+                                                         erase_outliers=args.ba_erase_outliers)
+                    else:
+                        ba_ok, ba = mapper.bundle_adjust(window=args.ba_window)
                     n_ba[0] += 1
                     n_ba[1] += ba_ok
                     print("frame %d: bundle adjust %s, %d free + %d fixed keyframes, %d points, %d of %d edges inliers, cost %.4g -> %.4g, steps %s"
                           % (idx, "ok" if ba_ok else "not ok", ba["n_free"], ba["n_fixed"], ba["n_local"], ba["n_inliers"], ba["n_edges"],
                              ba["cost"][0], ba["cost"][2], ba["steps"]))
+                    if args.ba_covisible or args.ba_erase_outliers:
+                        n_ba_erased[0] += ba["n_erased"]
+                        n_ba_erased[1] += ba["n_under"]
+                        print("frame %d: bundle adjust over the keyframes %s, %d outlier observations erased, %d points left with fewer than two"
+                              % (idx, ba["candidates"], ba["n_erased"], ba["n_under"]))
                     if ba["n_free"] and mapper.keyframes[-1]["descriptors"] is desc:   # tracking goes on from the refined pose of this keyframe
                         T = mapper.keyframes[-1]["pose"].copy()
                         ref_pose = T
@@ -469,6 +486,9 @@ def main(argv=None):
         print("map statistics: %s" % mapper.get_map_statistics())
         if args.local_ba:
             print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
+            if args.ba_covisible or args.ba_erase_outliers:
+                print("bundle adjustment sets: %s, %d outlier observations erased, %d points left with fewer than two"
+                      % ("covisible" if args.ba_covisible else "window", n_ba_erased[0], n_ba_erased[1]))
         if args.grow_neighbours:
             print("growth from neighbours: %d calls, %d points created with %d observations" % (n_grow[0], n_grow[1], n_grow[2]))
         if args.detect_loops:

@@ -124,6 +124,18 @@ class MapBaOut(C.Structure):
                 ("n_edges", C.c_int32), ("n_inliers", C.c_int32), ("steps", C.c_int32 * 2), ("accepted", C.c_int32 * 2), ("ok", C.c_int32)]
 
 
+class MapBaLocalParams(C.Structure):
+    _fields_ = [("free_mask", C.c_void_p), ("kf_pos", C.c_int32), ("n_best", C.c_int32), ("min_weight", C.c_int32), ("erase_outliers", C.c_int32)]
+
+
+class MapBaLocalOut(C.Structure):
+    _fields_ = [("candidate", C.c_void_p), ("n_candidates", C.c_int32), ("n_erased", C.c_int32), ("n_under", C.c_int32), ("n_obs", C.c_int64)]
+
+
+class MapObsEraseOut(C.Structure):
+    _fields_ = [("n_erased", C.c_int32), ("n_under", C.c_int32), ("n_obs", C.c_int64)]
+
+
 class MapFuseParams(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("window", C.c_int32), ("radius", C.c_double), ("scale_factor", C.c_double),
                 ("max_dist", C.c_int32), ("chi2", C.c_double)]
@@ -375,6 +387,8 @@ SIGNATURES = {
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
     "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mo_map_bundle_adjust_local": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_erase_observations": (_i, [_vp, _vp, _vp]),
     "mo_map_fuse": (_i, [_vp, _vp, _vp]),
     "mo_map_grow": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_covisibility": (_i, [_vp, _vp, _vp]),

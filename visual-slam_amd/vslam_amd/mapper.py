@@ -282,14 +282,25 @@ class LocalMapper:
         self._cache = None
         self._sync_size()
 
-    def bundle_adjust(self, window=10, scale_factor=1.2, chi2=5.991, min_inliers=50, max_steps=(5, 10), want_points=False):
+    def bundle_adjust(self, window=10, scale_factor=1.2, chi2=5.991, min_inliers=50, max_steps=(5, 10), want_points=False, local="window",
+                      kf_position=-1, n_best=15, min_weight=15, free=None, erase_outliers=False):
         """Local bundle adjustment on the map as it stands (ORB-SLAM2's LocalBundleAdjustment; mo_map_bundle_adjust in
         include/vslam_amd.h states the rules): the poses of the last `window` keyframes (0: all, at most 16, never the first) and the
         positions of the points they see are refined together, the other keyframes seeing those points held fixed.  The refined poses
         are written into kf["pose"] of the free keyframes (into the array), the map points move on the device.
         Returns (ok, info): info holds n_free, n_fixed, n_local, n_edges, n_inliers, cost (3), steps / accepted per round, `free` and
         `fixed` position lists, `edge_inlier` per observation entry (0 outside, 1 inlier, 2 outlier), `poses` [n_kf][3][4] and, with
-        want_points, `points` [n_points][3] f64 (NaN for points outside the problem)."""
+        want_points, `points` [n_points][3] f64 (NaN for points outside the problem).
+        The set form (mo_map_bundle_adjust_local; `window` is then not used): local="covisible" frees keyframe `kf_position` (-1: the
+        last) and its `n_best` (0 .. 15) heaviest covisible neighbours sharing at least `min_weight` points with it, selected on the
+        device; free= (positions, or a bool mask with one entry per keyframe; at most 16 besides position 0) frees exactly those.
+        Position 0 is never free.  erase_outliers=True erases the observation entries the adjustment ended with as outliers
+        (edge_inlier == 2) in the same device chain, when the adjustment is ok; points left with fewer than two entries stay and are
+        counted (cull_map_points' orphan rule removes them).  With any of these info also holds `candidates` (the positions of the
+        set, before the gauge), `n_erased` and `n_under`; edge_inlier is indexed by the entries as they were before the erase."""
+        if local not in ("window", "covisible"):
+            raise ValueError("local must be 'window' or 'covisible'")
+        set_form = local == "covisible" or free is not None or bool(erase_outliers)
         n_kf = len(self.keyframes)
         poses = np.zeros((max(n_kf, 1), 12), np.float64)
         for i, kf in enumerate(self.keyframes):
@@ -297,14 +308,40 @@ class LocalMapper:
         K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
         poses_out = poses.copy()
         state = np.zeros(max(n_kf, 1), np.int32)
-        einl = np.zeros(max(self._n_obs if self._n_points else 0, 1), np.uint8)
+        n_obs_before = self._n_obs if self._n_points else 0
+        einl = np.zeros(max(n_obs_before, 1), np.uint8)
         pts = np.full((max(self._n_points, 1), 3), np.nan, np.float64) if want_points else None
         ms = [int(v) for v in max_steps]
         if len(ms) != 2:
             raise ValueError("max_steps: one count per round")
         prm = V.MapBaParams(int(window), int(min_inliers), (C.c_int32 * 2)(*ms), float(scale_factor), float(chi2))
         out = V.MapBaOut(poses_out.ctypes.data, state.ctypes.data, einl.ctypes.data, pts.ctypes.data if want_points else None)
-        self._check(self.lib.mo_map_bundle_adjust(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
+        if set_form:
+            fmask = None
+            if free is not None:
+                sel = np.asarray(free)
+                if sel.dtype == np.bool_:
+                    if sel.shape != (n_kf,):
+                        raise ValueError("a mask must have one entry per keyframe")
+                    fmask = np.ascontiguousarray(sel, np.uint8)
+                else:
+                    idx = sel.astype(np.int64).reshape(-1)
+                    if len(idx) and (idx.min() < 0 or idx.max() >= n_kf):
+                        raise IndexError("keyframe position out of range")
+                    fmask = np.zeros(n_kf, np.uint8)
+                    fmask[idx] = 1
+                fmask = np.concatenate([fmask, np.zeros(1, np.uint8)])   # (never empty)
+            elif local == "window":   # erase_outliers alone: the window's own set
+                lo = n_kf - int(window) if 0 < int(window) < n_kf else 0
+                fmask = np.zeros(n_kf + 1, np.uint8)
+                fmask[lo:n_kf] = 1
+            cand = np.zeros(max(n_kf, 1), np.uint8)
+            lprm = V.MapBaLocalParams(fmask.ctypes.data if fmask is not None else None, int(kf_position), int(n_best), int(min_weight),
+                                      1 if erase_outliers else 0)
+            lout = V.MapBaLocalOut(cand.ctypes.data)
+            self._check(self.lib.mo_map_bundle_adjust_local(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(lprm), C.byref(out), C.byref(lout)))
+        else:
+            self._check(self.lib.mo_map_bundle_adjust(self._h, V._ptr(K), V._ptr(poses), C.byref(prm), C.byref(out)))
         state = state[:n_kf]
         free = np.flatnonzero(state == 2).tolist()
         if out.n_free:
@@ -315,11 +352,42 @@ class LocalMapper:
         info = {"n_free": int(out.n_free), "n_fixed": int(out.n_fixed), "n_local": int(out.n_local), "n_edges": int(out.n_edges),
                 "n_inliers": int(out.n_inliers), "cost": [float(v) for v in out.cost], "steps": [int(v) for v in out.steps],
                 "accepted": [int(v) for v in out.accepted], "lambda": float(out.lambda_), "free": free,
-                "fixed": np.flatnonzero(state == 1).tolist(), "edge_inlier": einl[:self._n_obs if self._n_points else 0],
+                "fixed": np.flatnonzero(state == 1).tolist(), "edge_inlier": einl[:n_obs_before],
                 "poses": poses_out[:n_kf].reshape(n_kf, 3, 4)}
         if want_points:
             info["points"] = pts[:self._n_points]
+        if set_form:
+            info.update(candidates=np.flatnonzero(cand[:n_kf]).tolist(), n_erased=int(lout.n_erased), n_under=int(lout.n_under))
+            if info["n_erased"]:
+                self._version += 1
+                self._cache = None
+                self._sync_size()
         return bool(out.ok), info
+
+    def erase_observations(self, entries_or_mask):
+        """Removes single entries of the observation arrays on the device (mo_map_erase_observations): every point keeps its index, its
+        fields and its life record, the surviving entries their order and bytes; a point may end with no entries.  entries_or_mask: entry
+        indices into obs_kf / obs_kp, or a bool mask with one entry per observation entry.  Returns {"n_erased", "n_under" (the points
+        that lost an entry and now hold fewer than two), "n_obs"}."""
+        n = self._n_obs if self._n_points else 0
+        sel = np.asarray(entries_or_mask)
+        if sel.dtype == np.bool_:
+            if sel.shape != (n,):
+                raise ValueError("a mask must have one entry per observation entry")
+            mask = np.ascontiguousarray(sel, np.uint8)
+        else:
+            idx = sel.astype(np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= n):
+                raise IndexError("observation entry out of range")
+            mask = np.zeros(n, np.uint8)
+            mask[idx] = 1
+        out = V.MapObsEraseOut()
+        self._check(self.lib.mo_map_erase_observations(self._h, V._ptr(mask) if n else None, C.byref(out)))
+        if int(out.n_erased):
+            self._version += 1
+            self._cache = None
+            self._sync_size()
+        return {"n_erased": int(out.n_erased), "n_under": int(out.n_under), "n_obs": int(out.n_obs)}
 
     def global_bundle_adjust(self, fixed=None, max_steps=10, max_cg=200, cg_tol=1e-8, step_tol=1e-10, min_inliers=50, scale_factor=1.2,
                              chi2=5.991, want_points=False):
