@@ -587,6 +587,48 @@ typedef struct {
     int32_t from_token;      /* 1: the frame was read from its resident slot */
 } mo_map_track_out;
 int mo_map_track(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_track_params*, mo_map_track_out*);
+
+/* mo_map_track_batch: n_frames frames tracked against the map as it stands in one device chain (the cameras of a rig, a recorded sequence
+ * localised from odometry priors, a set of relocalised frames, the frames of one stream chunk); reads the map, never changes it.
+ *   the rule      for every i, everything the call returns for frame i is what mo_map_track(m, &frames[i], K, pose0 + 12 * i, prm, ...)
+ *                 returns for that frame alone on the same map: every integer equal, every double equal bit for bit (pass_pose, pose
+ *                 and the pose0 a frame that finished no pass falls back to included).  The order and the company of the frames change
+ *                 nothing; a frame that ends early (too few matches after the retry, fewer than 10 inliers in the refinement, a Hessian
+ *                 that is not positive definite) has no effect on any other frame.
+ *   shared        n_local alone: the local map depends on the map and `window`, and is formed once for the batch (mo_map_track reports 0
+ *                 for a frame without keypoints, for which it forms no local map; here n_local is the batch's).  One K, one image
+ *                 size and one parameter set serve every frame.
+ *   layout        frame i's per-keypoint rows start at i * stride; rows past a frame's n are not written.
+ *   no work       n_frames = 0: nothing runs.  A frame without keypoints: no pass runs for it, ok = 0, the others go on.  A map without
+ *                 keyframes or map points: no pass runs for any frame, n_local = 0.  None of these is an error.
+ *   errors        MO_ERR_ARG for a NULL required pointer, n_frames outside 0 .. MO_TRACK_BATCH_MAX, a frame of more than `stride` rows,
+ *                 a pose0 that is not finite, and every parameter mo_map_track refuses.  A token that is no longer resident falls back
+ *                 to the frame's arrays.
+ * One chain on the context stream, one synchronisation (the copy-out): every retry and early exit is a per-frame flag on the device.
+ * Integer atomics and fixed-order f64 reductions only: equal inputs give equal bytes on every run.  Stage marks tb_stage, tb_prep,
+ * tb_search, tb_refine (mo_stage_times). */
+#define MO_TRACK_BATCH_MAX 1024
+typedef struct {
+    /* caller-allocated; the per-keypoint arrays may be NULL.  Frame i's rows start at i * stride. */
+    int32_t stride;          /* rows per frame in the arrays below, >= every frame's n */
+    int32_t* point;          /* [n_frames][stride] as mo_map_track_out.point */
+    int32_t* dist;           /* [n_frames][stride] */
+    uint8_t* inlier;         /* [n_frames][stride] */
+    double* pose;            /* [n_frames][12]     required, like every array below */
+    double* pass_pose;       /* [n_frames][4][12] */
+    double* pass_radius;     /* [n_frames][4] */
+    int32_t* pass_cand;      /* [n_frames][4] */
+    int32_t* pass_matches;   /* [n_frames][4] */
+    int32_t* pass_inliers;   /* [n_frames][4] */
+    int32_t* n_pass_run;     /* [n_frames] */
+    int32_t* ok;             /* [n_frames] */
+    int32_t* from_token;     /* [n_frames] */
+    /* filled by the call */
+    int32_t n_local;         /* points of the local map (one local map for the whole batch) */
+    int32_t n_ok;            /* frames with ok = 1 */
+} mo_map_track_batch_out;
+int mo_map_track_batch(mo_map*, const mo_frame_ref* frames, int32_t n_frames, const double K[9], const double* pose0,
+                       const mo_map_track_params*, mo_map_track_batch_out*);
 int mo_format_floats(const float* v, int64_t n, char* out, size_t cap, size_t* len);
 
 /* mo_map_bundle_adjust: local bundle adjustment on the map as it stands (ORB-SLAM2's Optimizer::LocalBundleAdjustment, monocular): the

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VSLAM_AMD_LIB") or os.path.join(_PKG_ROOT, "libvslam_
 MO_OK, MO_ERR_ARG, MO_ERR_HIP, MO_ERR_CAPACITY, MO_ERR_UNSUPPORTED, MO_ERR_INDEX = 0, -1, -2, -3, -4, -5
 ABI_VERSION = 7  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
 ORDER_LIBSTDCXX, ORDER_MSVC = 0, 1
+TRACK_BATCH_MAX = 1024  # MO_TRACK_BATCH_MAX: frames of one mo_map_track_batch
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4"), ("class_id", "<i4")])
@@ -112,6 +113,13 @@ class MapTrackOut(C.Structure):
     _fields_ = [("point", C.c_void_p), ("dist", C.c_void_p), ("inlier", C.c_void_p), ("pose", C.c_double * 12), ("pass_pose", (C.c_double * 12) * 4),
                 ("pass_radius", C.c_double * 4), ("pass_cand", C.c_int32 * 4), ("pass_matches", C.c_int32 * 4), ("pass_inliers", C.c_int32 * 4),
                 ("n_pass_run", C.c_int32), ("n_local", C.c_int32), ("ok", C.c_int32), ("from_token", C.c_int32)]
+
+
+class MapTrackBatchOut(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("point", C.c_void_p), ("dist", C.c_void_p), ("inlier", C.c_void_p), ("pose", C.c_void_p),
+                ("pass_pose", C.c_void_p), ("pass_radius", C.c_void_p), ("pass_cand", C.c_void_p), ("pass_matches", C.c_void_p),
+                ("pass_inliers", C.c_void_p), ("n_pass_run", C.c_void_p), ("ok", C.c_void_p), ("from_token", C.c_void_p),
+                ("n_local", C.c_int32), ("n_ok", C.c_int32)]
 
 
 class MapBaParams(C.Structure):
@@ -384,6 +392,7 @@ SIGNATURES = {
     "mo_map_relocalize": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_dbg_map_reloc_last": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_track": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_track_batch": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "mo_format_floats": (_i, [_vp, C.c_int64, _vp, C.c_size_t, _vp]),
     "mo_map_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_add_observations": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -947,6 +947,74 @@ class LocalMapper:
             info["ref_keyframe"] = int(lout.ref)
         return bool(out.ok), T, info
 
+    def track_local_map_batch(self, frames, poses, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8, chi2=5.991,
+                              min_matches=20, min_inliers=30, image_size=None):
+        """track_local_map for many frames in one device chain (mo_map_track_batch in include/vslam_amd.h states the rules): the cameras
+        of a rig, a recorded sequence with odometry priors, a set of relocalised frames, the frames of one stream chunk.  frames: a
+        sequence of (keypoints, descriptors) as track_local_map takes them (arrays that still carry a token are used resident); poses:
+        [n][4][4] or [n][3][4] predicted poses.  One camera matrix, image size and parameter set serve every frame; the local map is
+        the window's ("covisible" and the frustum mode are not offered here).
+        Returns (ok [n] bool, poses [n][4][4], infos): every frame's results are what track_local_map returns for it alone on the same
+        map, bit for bit, whatever the order and the company; infos[i] has the keys of track_local_map's info (`n_local` is the
+        batch's: the local map is formed once)."""
+        radii = [float(r) for r in radii]
+        if not 1 <= len(radii) <= 4:
+            raise ValueError("radii: one to four passes")
+        frames = list(frames)
+        nf = len(frames)
+        if nf > V.TRACK_BATCH_MAX:
+            raise ValueError("at most %d frames in a batch" % V.TRACK_BATCH_MAX)
+        for fr in frames:
+            if not isinstance(fr, (tuple, list)) or len(fr) != 2:
+                raise ValueError("frames: a sequence of (keypoints, descriptors) pairs")
+        poses = np.asarray(poses, np.float64)
+        if poses.size == 0 and nf == 0:
+            poses = np.zeros((0, 3, 4))
+        if poses.ndim != 3 or poses.shape[0] != nf or poses.shape[1:] not in ((4, 4), (3, 4)):
+            raise ValueError("poses: [n][4][4] or [n][3][4], one per frame")
+        pose0 = np.ascontiguousarray(poses[:, :3, :4]).reshape(nf, 12)
+        if image_size is None:
+            if self.keyframes:
+                image_size = self.keyframes[-1]["image"].shape[1::-1]
+            else:
+                Km = np.asarray(self.camera_matrix, np.float64)
+                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        refs = (V.FrameRef * max(nf, 1))()
+        ns, keep = [], []
+        for i, (kp, de) in enumerate(frames):
+            ref, n, arrays = self._frame_ref(kp, de)
+            refs[i] = ref
+            ns.append(n)
+            keep.append(arrays)
+        stride = max(ns + [1])
+        m = max(nf, 1)
+        point = np.full((m, stride), -1, np.int32)
+        dist = np.full((m, stride), -1, np.int32)
+        inlier = np.zeros((m, stride), np.uint8)
+        pose = np.zeros((m, 12))
+        pass_pose = np.zeros((m, 4, 12))
+        pass_radius = np.zeros((m, 4))
+        pass_cand, pass_matches, pass_inliers = (np.zeros((m, 4), np.int32) for _ in range(3))
+        n_run, ok, from_token = (np.zeros(m, np.int32) for _ in range(3))
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
+                               float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
+        out = V.MapTrackBatchOut(stride, *[a.ctypes.data for a in (point, dist, inlier, pose, pass_pose, pass_radius, pass_cand, pass_matches,
+                                                                   pass_inliers, n_run, ok, from_token)])
+        self._check(self.lib.mo_map_track_batch(self._h, refs, nf, V._ptr(K), pose0.ctypes.data if nf else None, C.byref(prm), C.byref(out)))
+        Ts = np.tile(np.eye(4), (nf, 1, 1))
+        Ts[:, :3, :] = pose[:nf].reshape(nf, 3, 4)
+        infos = []
+        for i in range(nf):
+            n, nr = ns[i], int(n_run[i])
+            infos.append({"point": point[i, :n], "dist": dist[i, :n], "inlier": inlier[i, :n].astype(bool),
+                          "pass_pose": [np.vstack([pass_pose[i, k].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(nr)],
+                          "pass_radius": [float(pass_radius[i, k]) for k in range(nr)], "pass_cand": [int(pass_cand[i, k]) for k in range(nr)],
+                          "pass_matches": [int(pass_matches[i, k]) for k in range(nr)],
+                          "pass_inliers": [int(pass_inliers[i, k]) for k in range(nr)], "n_pass_run": nr, "n_local": int(out.n_local),
+                          "from_token": bool(from_token[i])})
+        return ok[:nf].astype(bool), Ts, infos
+
     def point_views(self, scale_factor=1.2, n_levels=8):
         """Where every map point was seen from (ORB-SLAM2's UpdateNormalAndDepth; mo_map_point_views in include/vslam_amd.h states the
         rules), computed on the device from the map as it stands and the store's own projection matrices; the map is not changed.
