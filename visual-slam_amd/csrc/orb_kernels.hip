@@ -1427,7 +1427,8 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 // spent 8 - 21 k of its 30 k cycles waiting for them) and parks them in LDS through registers (93 VGPRs, 5 wavefronts per SIMD).
 // Here a workgroup owns a 128 x 64 TILE of one level's border region: it picks the level's final keypoints that fall into the tile
 // (the level's list is <= a few KB, read coalesced), loads the tile + halo of the raw level (15 px: intensity centroid) and of the
-// blurred level (19 px: rBRIEF) ONCE with coalesced row loads, and describes its keypoints out of LDS, 16 lanes each:
+// blurred level (19 px: rBRIEF) ONCE with coalesced row loads, and describes its keypoints out of LDS - the intensity centroid 16 lanes
+// per keypoint, the angle and its (cos, sin) one lane per keypoint, the 256 tests one wavefront per keypoint (profiles/describe_lanes_ab.txt):
 //   * line requests per frame: 214 tiles x ~390 instead of 2000 keypoints x ~130 (levels 2.. are dense: 20 - 60 keypoints per tile)
 //   * no window registers: the per-row intensity-centroid weights (constant per lane) live in registers instead of being re-read
 //     from LDS for every keypoint, ~70 VGPRs
@@ -1443,7 +1444,7 @@ __device__ __forceinline__ uint16_t rbrief_u16_lds(uint32_t lds_base, int ppitch
 #define DT_BLR_NQ ((DT_W + 38 + 7 + 7) >> 3)    // 22
 static_assert(((DT_RAW_P / 4) & 1) || ((DT_RAW_P / 4) & 7) == 4, "raw tile pitch: odd, or an odd multiple of 4 dwords");
 #ifndef DT_NT
-#define DT_NT 256                    // 16 keypoint groups of 16 lanes
+#define DT_NT 256                    // 16 keypoint groups of 16 lanes (phase A), 4 wavefronts of one keypoint each (phase C); a multiple of 64
 #endif
 #ifdef DT_WAVES
 #define DT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(DT_WAVES, 8)))
@@ -1492,6 +1493,7 @@ __device__ __forceinline__ void tile_store(uint8_t* lds, int tid, const uint32_t
 // (nrows, ncols: the window bounded by the level's border region): a thread past the last piece, and a trip past the last row,
 // stores nothing and re-reads a line it or its neighbour has just read.
 typedef uint32_t dt_u32x4 __attribute__((ext_vector_type(4)));
+typedef dt_u32x4 dt_u32x4_a4 __attribute__((aligned(4)));  // a descriptor row of a caller's buffer: dword alignment is all that is assumed
 // goff / loff: byte offset of the thread's first piece from the level's base / inside the LDS tile; rows_left: rows from the thread's
 // first row to the end of the window (<= 0: nothing to store); last: byte offset of the thread's last row from its first.  Every
 // load is unconditional - a trip past the thread's last row reads that row again, a thread without a piece the window's first
@@ -1544,9 +1546,8 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
     // ONE tile buffer: the raw tile (intensity centroid, phase A) is replaced by the blurred tile (rBRIEF, phase C) once phase A is
     // done; the blurred tile's loads are issued behind phase A and wait in the registers the raw tile's used (vs)
     __shared__ __attribute__((aligned(16))) uint8_t s_tile[HAS_DESC ? DT_BLR_ROWS * DT_BLR_P : DT_RAW_ROWS * DT_RAW_P];
-    __shared__ __attribute__((aligned(16))) float4 s_pat[HAS_DESC ? 256 : 1];  // rBRIEF pattern as floats, [test k of a lane][lane]
-    __shared__ uint32_t s_list[DT_LIST];  // index in the chunk | dx << 9 | dy << 17
-    __shared__ float2 s_ab[DT_LIST];      // (-, response) -> (angle, -) -> (cos, sin)
+    __shared__ uint32_t s_list[DT_LIST];  // index in the chunk | dx << 9 | dy << 17; after phase B: index in the chunk | sample offset in the blurred tile << 9
+    __shared__ float2 s_ab[DT_LIST];      // (-, response) -> the moments (m01, m10) as int bits (keypoints only: (angle, -)) -> (cos, sin)
     __shared__ int s_n;
     static_assert(DT_BLR_ROWS * DT_BLR_P >= DT_RAW_ROWS * DT_RAW_P, "the blurred tile is the larger one");
     const uint32_t te = tile_tab[tile];
@@ -1617,17 +1618,14 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
         wt[0] = w0.x; wt[1] = w0.y; wt[2] = w0.z; wt[3] = w0.w; wt[4] = w1.x; wt[5] = w1.y; wt[6] = w1.z; wt[7] = w1.w;
         mk[0] = k0.x; mk[1] = k0.y; mk[2] = k0.z; mk[3] = k0.w; mk[4] = k1.x; mk[5] = k1.y; mk[6] = k1.z; mk[7] = k1.w;
     };
-    if (HAS_DESC && tid < 256 && DT_NT >= 256) {  // thread t = lane l, test k of the lane: pattern row 16 l + k -> s_pat[k][l]
-        const int l = tid & 15, k = tid >> 4;
-        const int8_t* pt = &c_pattern[(l * 16 + k) * 4];
-        s_pat[k * DG + l] = make_float4((float)pt[0], (float)pt[1], (float)pt[2], (float)pt[3]);
-    } else if (HAS_DESC && DT_NT < 256) {
-        for (int i = tid; i < 256; i += DT_NT) {
-            const int l = i & 15, k = i >> 4;
-            const int8_t* pt = &c_pattern[(l * 16 + k) * 4];
-            s_pat[k * DG + l] = make_float4((float)pt[0], (float)pt[1], (float)pt[2], (float)pt[3]);
-        }
-    }
+    // the rBRIEF pattern, test-major: lane l of a wavefront owns tests 64 r + l, r = 0..3 - four packed rows (x0, y0, x1, y1 as int8) fetched
+    // coalesced beside the blurred tile's loads and unpacked to 16 float registers when phase C begins.  No pattern table in LDS (4 KB)
+    // and no LDS read per test
+    uint32_t pq[4] = {0, 0, 0, 0};
+    auto load_pat = [&]() {
+#pragma unroll
+        for (int r = 0; r < 4; r++) pq[r] = ((const uint32_t*)c_pattern)[64 * r + (tid & 63)];
+    };
     const int row_b_w = gl == 15 ? 0 : 1;  // lane 15's second row is row 15 again: counted once
     const uint32_t tile_lds = (uint32_t)(uintptr_t)s_tile;
 
@@ -1648,7 +1646,8 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
             }
         }
     };
-    // phase A, 16 lanes per keypoint: intensity-centroid angle out of the RAW tile, keypoint record; the angle goes into the list
+    // phase A, 16 lanes per keypoint: intensity-centroid moments out of the RAW tile, keypoint record; with descriptors the moments go
+    // into the list and the angle is phase B's, keypoints only (no phase B): the angle here
     auto phase_a = [&](int c0, int n) {
         for (int j = grp; j < n; j += DT_NT / DG) {  // uniform within a 16-lane group; no barriers inside
             const uint32_t e = s_list[j];
@@ -1679,43 +1678,77 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
             }
             m10 = group_sum(m10);
             m01 = group_sum(m01);
-            const float angle = fast_atan2_deg((float)m01, (float)m10);
+            // (fast_atan2_deg in every lane of the group was 52 of the 139 vector instructions of a round)
+            const float angle = HAS_DESC ? 0.f : fast_atan2_deg((float)m01, (float)m10);
             if (gl == 0) {
                 mo_keypoint* o = kps + (size_t)frame * cap + k;
                 o->x = (float)x * lscale; o->y = (float)y * lscale;
                 o->size = 31 * lscale;
-                o->angle = angle;
+                if (!HAS_DESC) o->angle = angle;
                 o->response = s_ab[j].y;
                 o->octave = L;
                 o->class_id = -1;
-                s_ab[j].x = angle;
+                if (HAS_DESC) s_ab[j] = make_float2(__int_as_float(m01), __int_as_float(m10));
             }
         }
     };
-    // phase B, ONE lane per keypoint: (float)cos / (float)sin of the angle through f64 as cv2 computes them - once per keypoint instead
-    // of once per lane of its group (the f64 sincos is the longest straight-line piece of the kernel)
-    auto phase_b = [&](int n) {
+    // phase B, ONE lane per keypoint: the angle of the moments, then (float)cos / (float)sin of it through f64 as cv2 computes them - once
+    // per keypoint instead of once per lane of its group (the f64 sincos is the longest straight-line piece of the kernel)
+    auto phase_b = [&](int c0, int n) {
         for (int j = tid; j < n; j += DT_NT) {
-            float angle = s_ab[j].x;
+            const float2 mm = s_ab[j];
+            float angle = fast_atan2_deg((float)__float_as_int(mm.x), (float)__float_as_int(mm.y));
+            kps[(size_t)frame * cap + base + c0 + (int)(s_list[j] & 0x1FF)].angle = angle;
             angle *= (float)(3.14159265358979323846 / 180.f);
             double sd, cd;
             sincos((double)angle, &sd, &cd);
             s_ab[j] = make_float2((float)cd, (float)sd);
-        }
-    };
-    // phase C, 16 lanes per keypoint: the 256 rotated tests, 16 per lane, out of the BLURRED tile
-    auto phase_c = [&](int c0, int n) {
-        for (int j = grp; j < n; j += DT_NT / DG) {
+            // what phase C needs of the keypoint beside (cos, sin), once per keypoint instead of once per lane: the sample (cx, cy) as a
+            // byte offset into the blurred tile replaces (dx, dy) in the list entry
             const uint32_t ex = s_list[j];
-            const int i = c0 + (int)(ex & 0x1FF), dx = (int)((ex >> 9) & 255), dy = (int)(ex >> 17);
-            const int k = base + i;
+            const int dx = (int)((ex >> 9) & 255), dy = (int)(ex >> 17);
             const float px = (float)(x0 + dx) * lscale, py = (float)(y0 + dy) * lscale, inv = 1.f / lscale;
             const int cx = __float2int_rn(px * inv), cy = __float2int_rn(py * inv);
-            const float2 ab = s_ab[j];
-            int glo = gl;
-            asm volatile("" : "+v"(glo));  // opaque per keypoint: the 16 pattern reads stay in the loop (hoisted, they pin 64 registers)
-            *(uint16_t*)(desc + ((size_t)frame * cap + k) * 32 + 2 * gl) =
-                rbrief_u16_lds(tile_lds + (uint32_t)((cy - (y0 - 19)) * DT_BLR_P + (cx - xb_al)), DT_BLR_P, ab.x, ab.y, s_pat, glo);
+            s_list[j] = (ex & 0x1FF) | ((uint32_t)((cy - (y0 - 19)) * DT_BLR_P + (cx - xb_al)) << 9);
+        }
+    };
+    // phase C, ONE WAVEFRONT per keypoint: the 256 rotated tests out of the BLURRED tile, lane l evaluating tests 64 r + l, r = 0..3.
+    // The keypoint's values are wave-uniform (broadcast LDS reads -> scalar registers), and a wave-wide compare of t0 < t1 is 64
+    // consecutive descriptor bits as they lie in memory (test t = bit t & 7 of byte t >> 3): four masks are the 32 bytes, stored by lane 0.
+    // The float expressions and the sample address are those of rbrief_u16_lds.  A round of the workgroup describes DT_NT / 64
+    // keypoints instead of DT_NT / 16: a quarter of the empty slots in the last round
+    auto phase_c = [&](int c0, int nv) {
+        static_assert(DT_NT % 64 == 0, "phase C works in whole wavefronts");
+        static_assert(DT_BLR_ROWS * DT_BLR_P < (1 << 23), "sample offset beside the 9-bit index");
+        const int n = __builtin_amdgcn_readfirstlane(nv), wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        float4 pt[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            asm volatile("" : "+v"(pq[r]));  // opaque per call: the rare kernel's passes carry four packed registers through phase A, not sixteen floats
+            pt[r] = make_float4((float)(int8_t)pq[r], (float)(int8_t)(pq[r] >> 8), (float)(int8_t)(pq[r] >> 16), (float)(int8_t)(pq[r] >> 24));
+        }
+        for (int j = wv; j < n; j += DT_NT / 64) {
+            const uint32_t ex = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[j]);
+            const float2 abv = s_ab[j];
+            const float a = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(abv.x)));
+            const float b = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(abv.y)));
+            const int k = base + c0 + (int)(ex & 0x1FF);
+            const uint32_t sb = tile_lds + (ex >> 9) - 0x4B400000u - 0x400000u * (uint32_t)DT_BLR_P;  // (the rounding bias of jx, jy: rbrief_u16_lds)
+            uint32_t m[8];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int jx0 = __float_as_int((pt[r].x * a - pt[r].y * b) + 12582912.f), jy0 = __float_as_int((pt[r].x * b + pt[r].y * a) + 12582912.f);
+                const int jx1 = __float_as_int((pt[r].z * a - pt[r].w * b) + 12582912.f), jy1 = __float_as_int((pt[r].z * b + pt[r].w * a) + 12582912.f);
+                const uint32_t a0 = (uint32_t)__mul24(jy0, DT_BLR_P) + (sb + (uint32_t)jx0), a1 = (uint32_t)__mul24(jy1, DT_BLR_P) + (sb + (uint32_t)jx1);
+                const int t0 = *(lds_cu8*)(uintptr_t)a0, t1 = *(lds_cu8*)(uintptr_t)a1;
+                const unsigned long long bits = __ballot(t0 < t1);
+                m[2 * r] = (uint32_t)bits; m[2 * r + 1] = (uint32_t)(bits >> 32);
+            }
+            if ((tid & 63) == 0) {
+                dt_u32x4_a4* o = (dt_u32x4_a4*)(desc + ((size_t)frame * cap + k) * 32);
+                o[0] = dt_u32x4{m[0], m[1], m[2], m[3]};
+                o[1] = dt_u32x4{m[4], m[5], m[6], m[7]};
+            }
         }
     };
 
@@ -1743,8 +1776,9 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
                 tile_lane16<DT_BLR_NP>(lbpitch, y0 - 19, xb_al, nkr + 38, ncols_b, tid, goff, loff, rows_left, last);
                 tile_issue16<DT_BLR_NP, DT_BLR_LD16>(bl, lbpitch, goff, last, vs);
             } else if (al_blr) tile_issue<DT_BLR_ROWS, DT_BLR_NQ, DT_BLR_LD>(bl, lbpitch, lh, y0 - 19, xb_al, tid, vs);
+            load_pat();
             __syncthreads();  // phase A is done with the raw tile, the angles are in the list
-            phase_b(n0);
+            phase_b(0, n0);
             if (w16_blr) tile_store16<DT_BLR_NP, DT_BLR_LD16>(s_tile, loff, rows_left, vs);
             else if (al_blr) tile_store<DT_BLR_ROWS, DT_BLR_NQ, DT_BLR_P, DT_BLR_LD>(s_tile, tid, vs);
             else tile_load_bytes(bl, lbpitch, lw, lh, y0 - 19, DT_BLR_ROWS, xb_al, DT_BLR_P, s_tile, tid);
@@ -1769,9 +1803,10 @@ __device__ __forceinline__ void describe_tile(const Plan& P, int frame, int tile
             const int n = s_n;  // <= DT_NT <= DT_LIST
             phase_a(c0, n);
             if (HAS_DESC) {
+                load_pat();
                 __syncthreads();
                 tile_load_bytes(bl, lbpitch, lw, lh, y0 - 19, DT_BLR_ROWS, xb_al, DT_BLR_P, s_tile, tid);
-                phase_b(n);
+                phase_b(c0, n);
                 __syncthreads();
                 phase_c(c0, n);
             }
