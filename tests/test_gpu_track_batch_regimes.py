@@ -1,7 +1,7 @@
 """LocalMapper.track_local_map_batch (mo_map_track_batch, csrc/map_track_batch.hip) at the sizes where its own code runs, on the worlds of
 tests/track_batch_worlds.py: the strided walk of k_tb_search over a local list longer than two rounds, the compaction of a list that
 is far from dense, k_tb_scan across its chunks of 1024 blocks and a partial last block, the early return behind the workgroup remap,
-the frame indexing up to the maximum batch, and the keypoint-count regimes of k_tb_grid / k_tb_compact that test_track_grid_geometry
+the frame indexing up to the maximum batch, and the keypoint-count regimes of k_trk_grid / k_trk_compact that test_track_grid_geometry
 (tests/test_gpu_map_reads.py) checks for the per-frame kernels.
 
 The rule under test is the header's: every frame of a batch gets what track_local_map returns for it alone - integers equal, doubles
@@ -61,7 +61,7 @@ def test_stride_rounds_and_frame_shape_edges(grid_map):
     """19 frames on the grid world, window 3.  pblocks = ceil(100000 / 256) = 391, lb_per_frame = min(391, max(TB_MIN_LB = 128,
     ceil(TB_SEARCH_WGS = 2048 / 19) = 108)) = 128, n_local = 66481 = 259 * 256 + 177 list entries: workgroup lb of a frame walks the list
     blocks lb, lb + 128 and (lb < 4) lb + 256, the last of them partial; 128 * 19 = 8 * 304, so no workgroup of this launch returns
-    early.  The frames are test_track_grid_geometry's keypoint counts around the 1024 of k_tb_grid / k_tb_compact (1, 1023, 1024, 1025,
+    early.  The frames are test_track_grid_geometry's keypoint counts around the 1024 of k_trk_grid / k_trk_compact (1, 1023, 1024, 1025,
     5000 with 1500 keypoints in one cell, keypoints on and beyond every border), 13 frames of 200 .. 900 rows from other poses and one
     empty frame, at stride 5000.  The n = 1025 frame's matches stand in all three rounds (343 / 340 / 9 in the restatement)."""
     ctx, w, m, frames, pose0, at = grid_map

@@ -1,12 +1,12 @@
-// map_search.h -- what the searches by projection on the device map share: mo_map_track (map_track.hip, a frame against the local map)
-// and mo_map_fuse (map_fuse.hip, the local map against its own keyframes).  The local map with its representative descriptors
-// (k_trk_rep) and the keypoint grid (k_trk_grid) are defined in map_track.hip and launched through the functions at the end.  Inline
-// here, the one projected-window search: trk_project (projection and image test), trk_scale (radius per octave), trk_window (cell range,
-// cell walk, box and octave gates, a visitor per keypoint that passes), trk_ham (256-bit distance), trk_take (the (dist, q) tie rule;
-// map_grow.hip's epipolar search takes its best row by it too).  The frustum mode of both searches (mo_map_track_frustum,
-// mo_map_fuse_frustum) adds trk_window_oct (the window with an octave interval), ViewRec / trk_frustum (the view record of a point, the
-// distance and angle tests, the predicted level) and trk_centre; the records come from map_view_geom.hip through view_enqueue.
-// Private to the library.
+// map_search.h -- what the searches by projection on the device map share: the tracker (map_track.h: mo_map_track and its covisible,
+// frustum and batch forms), mo_map_fuse (map_fuse.hip, the local map against its own keyframes), and the searches of map_confirm.hip and
+// map_correct.hip.  The local map with its representative descriptors (k_trk_rep) and the keypoint grid (k_trk_grid) are defined in
+// map_track.hip and launched through the functions at the end.  Inline here, the one projected-window search: trk_project (projection and
+// image test), trk_scale (radius per octave), trk_window (cell range, cell walk, box and octave gates, a visitor per keypoint that passes),
+// trk_ham (256-bit distance), trk_take (the (dist, q) tie rule; map_grow.hip's epipolar search takes its best row by it too).  The frustum
+// mode of the searches (mo_map_track_frustum, mo_map_fuse_frustum) adds trk_window_oct (the window with an octave interval), ViewRec /
+// trk_frustum (the view record of a point, the distance and angle tests, the predicted level) and trk_centre; the records come from
+// map_view_geom.hip through view_enqueue.  Private to the library.
 #pragma once
 #include <climits>
 
@@ -73,8 +73,9 @@ template <class V> __device__ __forceinline__ void trk_window(double u, double v
         }
 }
 
-// trk_window with the octave gate lo <= octave <= hi in place of ro +- 1 (the frustum mode: [L - 1, L]).  Beside trk_window, not under it:
-// the plain searches keep the code they had.
+// trk_window with the octave gate lo <= octave <= hi in place of ro +- 1 (the frustum mode: [L - 1, L]).  Two walks still: trk_window as
+// trk_window_oct over [ro - 1, ro + 1] keeps every occupancy but moves k_fuse_search, k_cf_guided, k_cf_proj and k_cr_search by 4 - 10
+// instructions and k_tb_search from 74 to 76 VGPRs (profiles/track_unify_isa.txt); the run times of those searches were not measured.
 template <class V> __device__ __forceinline__ void trk_window_oct(double u, double v, double r, int lo, int hi, int w, int h,
                                                                   const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
                                                                   const mo_keypoint* __restrict__ fk, V visit) {
@@ -137,9 +138,13 @@ __device__ __forceinline__ bool trk_take(int dist, int q, int& bd, int& bq) {
 int trk_launch_rep(mo_map* m, int lo_pos, uint8_t* rep, int32_t* oct, int32_t* n_local);
 // the same with the local map of a keyframe set: lmask [n_kf] on the device, non-zero at a local keyframe (map_covis.hip's selection)
 int trk_launch_rep_mask(mo_map* m, const uint8_t* lmask, uint8_t* rep, int32_t* oct, int32_t* n_local);
-// k_trk_grid, one block per grid: block b sorts the keypoints of keyframe slot (slots ? slots[b] : slot0) - kcnt[slot] rows at
-// kkps + slot * row - into cell [b][TK_CELLS + 1] and sorted [b][row]
-int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted);
+// k_trk_grid, one block per grid: block b sorts the keypoints of row s = (slots ? slots[b] : slot0 + b) of kps [.][row] - cnt[s] of
+// them - into cell [b][TK_CELLS + 1] and sorted [b][row].  The second form: kps, row and cnt are the keyframe store's, s a keyframe slot.
+int trk_launch_grid(mo_ctx* c, const mo_keypoint* kps, int row, const int32_t* cnt, const int32_t* slots, int slot0, int n_grids, int w, int h,
+                    int32_t* cell, int32_t* sorted);
+inline int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted) {
+    return trk_launch_grid(m->c, m->kkps, m->row, m->kcnt, slots, slot0, n_grids, w, h, cell, sorted);
+}
 // map_view_geom.hip: k_view_centres and k_view_points on the live map (the position table uploaded by the caller), enqueued: *centre
 // [n_kf][3] by keyframe position (NaN: no centre) and *rec [point] for the points with oct[point] != TK_NOT_LOCAL (oct NULL: every
 // point), in the scratch of the view feature; both valid for the kernels enqueued behind on the context stream

@@ -2,17 +2,21 @@
 // its monocular pose-only PoseOptimization, on the map as it stands.  Read-only on the map; the frame is staged in the spare keyframe
 // slot (map_stage_frame), like mo_map_relocalize's.
 //
+// The tracker's types, the frame view and the candidate tail of the searches are map_track.h's; the single-workgroup stages below
+// (k_trk_init, k_trk_grid, k_trk_compact, k_trk_refine) take blockIdx.x as the frame, and this file launches them with one workgroup over
+// the spare slot's rows (stride m->row, count kcnt[spare]); mo_map_track_batch (map_track_batch.hip) launches them over its frames.
+//
 // Chain (one synchronisation, the copy-out; the retry and the early exits are flags in TrackRes that every later kernel reads first):
 //   k_trk_init      result block, per-keypoint keys and outputs
 //   k_trk_rep       one thread per point: local-map membership, representative descriptor ([point][32]) and its octave
 //                   (mo_map_track_covisible: k_covis and k_covis_select of map_covis.hip run in front of it and give it the local keyframes)
-//   k_trk_grid      one block: stable counting sort of the frame keypoints into 64 x 48 cells
+//   k_trk_grid      one block per grid: stable counting sort of the frame keypoints into 64 x 48 cells
 //   per pass, per attempt (the second attempt runs only after a pass with too few matches):
-//     k_trk_search  one thread per local point: projection, window over the cells, 256-bit Hamming distances, best / second, the
-//                   accepted match claims its keypoint by a 64-bit atomicMin of (dist << 32) | point
-//     k_trk_compact one block: the winners in keypoint order (block scans), per-keypoint outputs, the retry / end decision
-//   k_trk_refine    one block of 256: 4 rounds of Gauss-Newton (Huber in rounds 0 - 2), f64 partial sums per thread, fixed-order wave
-//                   and workgroup reductions, one Cholesky solve per step
+//     k_trk_search  one thread per local point: projection, then trk_claim: window over the cells, 256-bit Hamming distances, best /
+//                   second, the accepted match claims its keypoint by a 64-bit atomicMin of (dist << 32) | point
+//     k_trk_compact one block per frame: the winners in keypoint order (block scans), per-keypoint outputs, the retry / end decision
+//   k_trk_refine    one block of 256 per frame: 4 rounds of Gauss-Newton (Huber in rounds 0 - 2), f64 partial sums per thread, fixed-order
+//                   wave and workgroup reductions, one Cholesky solve per step
 // mo_map_track_frustum: the same chain with k_view_centres and k_view_points (map_view_geom.hip, through view_enqueue) behind k_trk_rep,
 // k_trk_search_frustum in place of k_trk_search, and k_trk_level (the predicted level per matched keypoint) behind the last pass.
 // Every device result is the same on every run: integer atomics only (sums and minima commute), fixed-order f64 reductions.
@@ -23,34 +27,13 @@
 
 #include "common.h"
 #include "map_store.h"
-#include "map_search.h"   // the grid geometry, the projected-window search, the launchers mo_map_fuse shares
-#include "ba.h"           // ba_info (pnp.h comes with it)
+#include "map_track.h"    // the tracker's types, frame view and candidate tail; map_search.h: the grid geometry, the projected-window search
+#include "ba.h"         // ba_info (pnp.h comes with it)
 
 #define TK_GRID_BLOCK 1024
 #define TK_CELLS_PER_THREAD (TK_CELLS / TK_GRID_BLOCK)
-#define TK_MAX_PASS 4
 #define TK_REFINE_BLOCK 256
 static_assert(TK_CELLS % TK_GRID_BLOCK == 0, "cells per thread");
-
-struct TrackPrm {
-    double K[9], pose0[12], radius[TK_MAX_PASS], sf, ratio, chi2;
-    int w, h, max_dist, min_matches;
-};
-
-struct TrackRes {
-    double pose[12];                      // projection pose of the next pass: pose0, then each refined pose
-    double pass_pose[TK_MAX_PASS][12];
-    double pass_radius[TK_MAX_PASS];
-    int32_t pass_cand[TK_MAX_PASS], pass_matches[TK_MAX_PASS], pass_inliers[TK_MAX_PASS];
-    int32_t n_local, n_run, n_done;       // points of the local map, passes searched, passes refined
-    int32_t ended, retry;                 // the call has ended (too few matches after the retry); the pass in flight is retried
-    int32_t cand, n_match;                // candidates of the attempt in flight (k_trk_search), matches of the last compaction
-};
-
-struct TrkMatch {                         // one match in keypoint order (32 B): the point's position, the keypoint
-    float X, Y, Z, x, y;
-    int32_t octave, q, p;
-};
 
 struct TrackBufs : MapFeature {
     DevBuf<uint8_t> rep;                  // [point][32] representative descriptors
@@ -67,23 +50,26 @@ struct TrackBufs : MapFeature {
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
 
-// a pass's kernels run when the call has not ended and, for the second attempt, when the first asked for it
-__device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
-    return !res->ended && (attempt == 0 || res->retry);
-}
-
-__global__ __launch_bounds__(256) void k_trk_init(TrackPrm prm, int n, TrackRes* __restrict__ res, unsigned long long* __restrict__ key,
-                                                  int32_t* __restrict__ qpt, int32_t* __restrict__ qdist, uint8_t* __restrict__ qinl) {
+// one workgroup per frame: its result block, keys and per-keypoint outputs; frame 0 zeroes the local-map counter
+__global__ __launch_bounds__(256) void k_trk_init(TrkFrames fr, TrkPose one, int32_t* __restrict__ n_local) {
+    const int f = blockIdx.x, n = fr.n(f);
+    const size_t at = fr.at(f);
+    unsigned long long* __restrict__ key = fr.key + at;
+    int32_t* __restrict__ qpt = fr.qpt + at;
+    int32_t* __restrict__ qdist = fr.qdist + at;
+    uint8_t* __restrict__ qinl = fr.qinl + at;
     for (int q = threadIdx.x; q < n; q += 256) { key[q] = TK_NONE; qpt[q] = -1; qdist[q] = -1; qinl[q] = 0; }
     if (threadIdx.x == 0) {
+        TrackRes* res = fr.res + f;   // (one frame: *n_local is its n_local)
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
-        for (int i = 0; i < 12; i++) res->pose[i] = prm.pose0[i];
+        for (int i = 0; i < 12; i++) res->pose[i] = fr.pose0 ? fr.pose0[(size_t)f * 12 + i] : one.v[i];
         for (int k = 0; k < TK_MAX_PASS; k++) {
             for (int i = 0; i < 12; i++) res->pass_pose[k][i] = nan;
             res->pass_radius[k] = 0.0;
             res->pass_cand[k] = 0; res->pass_matches[k] = 0; res->pass_inliers[k] = 0;
         }
-        res->n_local = 0; res->n_run = 0; res->n_done = 0; res->ended = 0; res->retry = 0; res->cand = 0; res->n_match = 0;
+        res->n_local = 0; res->n_run = 0; res->n_done = 0; res->ended = n == 0; res->retry = 0; res->cand = 0; res->n_match = 0;
+        if (f == 0) *n_local = 0;
     }
 }
 
@@ -151,11 +137,12 @@ template <bool MASK> __global__ __launch_bounds__(256) void k_trk_rep(MapView v,
 }
 
 // one block per grid: histogram of the cells (LDS), exclusive scan, scatter by LDS cursors, then every cell's run sorted by keypoint index (the
-// cursors' order is arrival order; the sort makes the layout the stable counting sort's)
+// cursors' order is arrival order; the sort makes the layout the stable counting sort's).  Block b sorts the row (slots ? slots[b] :
+// slot0 + b) of kkps [.][row] - keyframe slots of the store, the staged frame in its spare slot, the frames of a batch
 __global__ __launch_bounds__(TK_GRID_BLOCK) void k_trk_grid(const mo_keypoint* __restrict__ kkps, int row, const int32_t* __restrict__ kcnt,
                                                             const int32_t* __restrict__ slots, int slot0, int w, int h, int32_t* __restrict__ cell,
                                                             int32_t* __restrict__ sorted) {
-    const int slot = slots ? slots[blockIdx.x] : slot0;
+    const int slot = slots ? slots[blockIdx.x] : slot0 + (int)blockIdx.x;
     const mo_keypoint* __restrict__ fk = kkps + (size_t)slot * row;
     const int n = min(kcnt[slot], row);
     cell += (size_t)blockIdx.x * (TK_CELLS + 1);
@@ -228,21 +215,12 @@ __global__ __launch_bounds__(256) void k_trk_search(TrackPrm prm, int pass, int 
     wave_count_add(cand, &res->cand);
     if (!cand) return;
     const double r = (attempt ? 2.0 * prm.radius[pass] : prm.radius[pass]) * trk_scale(prm.sf, ro);
-    const uint8_t* d = rep + (size_t)i * 32;
-    int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
-    trk_window(uu, vv, r, ro, prm.w, prm.h, cell, sorted, fk, [&](int q, const mo_keypoint&, double, double) {
-        const int dist = trk_ham(d, fdesc + (size_t)q * 32), was = bd;
-        if (trk_take(dist, q, bd, bq)) sd = was;
-        else if (dist < sd) sd = dist;
-    });
-    if (bd == INT_MAX || bd > prm.max_dist) return;
-    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
-    atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+    trk_claim(prm, i, rep, fdesc, key, [&](auto visit) { trk_window(uu, vv, r, ro, prm.w, prm.h, cell, sorted, fk, visit); });
 }
 
 // k_trk_search under the frustum (mo_map_track_frustum): a candidate also lies in its point's frustum seen from the pass camera, and is
-// searched at its predicted level L with the octave gate [L - 1, L].  A kernel beside the plain one, not a mode of it: as a template
-// instance the plain search came out with another scalar register allocation (profiles/frustum_isa.txt), and it is to stay what it was.
+// searched at its predicted level L with the octave gate [L - 1, L].  A kernel of its own for its candidate test and counters; the
+// tail is the plain search's (trk_claim).
 __global__ __launch_bounds__(256) void k_trk_search_frustum(TrackPrm prm, TrkFrustum fr, int pass, int attempt, const float* __restrict__ xyz, int n_pts,
                                                             const uint8_t* __restrict__ rep, const int32_t* __restrict__ oct,
                                                             const mo_keypoint* __restrict__ fk, const uint8_t* __restrict__ fdesc,
@@ -271,16 +249,7 @@ __global__ __launch_bounds__(256) void k_trk_search_frustum(TrackPrm prm, TrkFru
     wave_count_add(cand, &res->cand);
     if (!cand) return;
     const double r = (attempt ? 2.0 * prm.radius[pass] : prm.radius[pass]) * trk_scale(prm.sf, lv);
-    const uint8_t* d = rep + (size_t)i * 32;
-    int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
-    trk_window_oct(uu, vv, r, lv - 1, lv, prm.w, prm.h, cell, sorted, fk, [&](int q, const mo_keypoint&, double, double) {
-        const int dist = trk_ham(d, fdesc + (size_t)q * 32), was = bd;
-        if (trk_take(dist, q, bd, bq)) sd = was;
-        else if (dist < sd) sd = dist;
-    });
-    if (bd == INT_MAX || bd > prm.max_dist) return;
-    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
-    atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+    trk_claim(prm, i, rep, fdesc, key, [&](auto visit) { trk_window_oct(uu, vv, r, lv - 1, lv, prm.w, prm.h, cell, sorted, fk, visit); });
 }
 
 // one thread per frame keypoint, behind the last pass: the predicted level of the point it was matched to (the level and the match are
@@ -292,17 +261,24 @@ __global__ __launch_bounds__(256) void k_trk_level(int n, const int32_t* __restr
     qlvl[q] = p >= 0 ? lvl[p] : -1;
 }
 
-// one block: the claimed keypoints in keypoint order -> the match list and the per-keypoint outputs; keys reset for the next attempt;
-// the pass's counts and the retry / end decision
-__global__ __launch_bounds__(1024) void k_trk_compact(TrackPrm prm, int pass, int attempt, int n, const mo_keypoint* __restrict__ fk,
-                                                      const float* __restrict__ xyz, unsigned long long* __restrict__ key,
-                                                      TrkMatch* __restrict__ match, int32_t* __restrict__ qpt, int32_t* __restrict__ qdist,
-                                                      uint8_t* __restrict__ qinl, TrackRes* __restrict__ res) {
+// one workgroup per frame: the claimed keypoints in keypoint order -> the match list and the per-keypoint outputs; keys reset for the
+// next attempt; the pass's counts and the retry / end decision
+__global__ __launch_bounds__(1024) void k_trk_compact(TrackPrm prm, TrkFrames fr, int pass, int attempt, const float* __restrict__ xyz) {
     __shared__ int lw[40];
     __shared__ int active;
+    const int f = blockIdx.x;
+    TrackRes* __restrict__ res = fr.res + f;
     if (threadIdx.x == 0) active = trk_active(res, attempt);
     __syncthreads();
     if (!active) return;
+    const size_t at = fr.at(f);
+    const mo_keypoint* __restrict__ fk = fr.fk + at;
+    unsigned long long* __restrict__ key = fr.key + at;
+    TrkMatch* __restrict__ match = fr.match + at;
+    int32_t* __restrict__ qpt = fr.qpt + at;
+    int32_t* __restrict__ qdist = fr.qdist + at;
+    uint8_t* __restrict__ qinl = fr.qinl + at;
+    const int n = fr.n(f);
     int added = 0;
     for (int b = 0; b < n; b += 1024) {
         const int q = b + threadIdx.x;
@@ -351,17 +327,22 @@ __device__ __forceinline__ bool trk_inlier(const TrackPrm& prm, const double* R,
     return zc > 0.0 && ba_info(prm.sf, mt.octave) * (du * du + dv * dv) <= prm.chi2;
 }
 
-// one block of 256: Optimizer::PoseOptimization (monocular, pose only) with Gauss-Newton steps; the pass's outputs
-__global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, int pass, const TrkMatch* __restrict__ match,
-                                                                uint8_t* __restrict__ minl, uint8_t* __restrict__ qinl, TrackRes* __restrict__ res) {
+// one workgroup of 256 per frame: Optimizer::PoseOptimization (monocular, pose only) with Gauss-Newton steps; the pass's outputs.  Per-thread
+// partial sums in match order with stride 256, the wave shuffle tree, the four wave sums added left to right by thread 0
+__global__ __launch_bounds__(TK_REFINE_BLOCK) void k_trk_refine(TrackPrm prm, TrkFrames fr, int pass) {
     constexpr int NW = TK_REFINE_BLOCK / 64;
     __shared__ double red[NW][27];
     __shared__ double sRt[12];
     __shared__ int flag, cnt[NW];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    TrackRes* __restrict__ res = fr.res + blockIdx.x;
     if (tid == 0) flag = !res->ended && !res->retry;
     __syncthreads();
     if (!flag) return;
+    const size_t at = fr.at(blockIdx.x);
+    const TrkMatch* __restrict__ match = fr.match + at;
+    uint8_t* __restrict__ minl = fr.minl + at;
+    uint8_t* __restrict__ qinl = fr.qinl + at;
     const int m = res->n_match;
     double R[9], t[3];
     pose_split(res->pose, R, t);
@@ -441,11 +422,81 @@ int trk_launch_rep_mask(mo_map* m, const uint8_t* lmask, uint8_t* rep, int32_t* 
     return MO_OK;
 }
 
-int trk_launch_grid(mo_map* m, const int32_t* slots, int slot0, int n_grids, int w, int h, int32_t* cell, int32_t* sorted) {
-    mo_ctx* c = m->c;
-    hipLaunchKernelGGL(k_trk_grid, dim3((unsigned)n_grids), dim3(TK_GRID_BLOCK), 0, c->stream, m->kkps, m->row, m->kcnt, slots, slot0, w, h, cell, sorted);
+int trk_launch_grid(mo_ctx* c, const mo_keypoint* kps, int row, const int32_t* cnt, const int32_t* slots, int slot0, int n_grids, int w, int h,
+                    int32_t* cell, int32_t* sorted) {
+    hipLaunchKernelGGL(k_trk_grid, dim3((unsigned)n_grids), dim3(TK_GRID_BLOCK), 0, c->stream, kps, row, cnt, slots, slot0, w, h, cell, sorted);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
+}
+
+int trk_launch_init(mo_ctx* c, const TrkFrames& fr, int n_frames, const double* one, int32_t* n_local) {
+    TrkPose p{};
+    if (one) std::memcpy(p.v, one, sizeof p.v);
+    hipLaunchKernelGGL(k_trk_init, dim3((unsigned)n_frames), dim3(256), 0, c->stream, fr, p, n_local);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
+int trk_launch_compact(mo_ctx* c, const TrackPrm& p, const TrkFrames& fr, int n_frames, int pass, int attempt, const float* xyz) {
+    hipLaunchKernelGGL(k_trk_compact, dim3((unsigned)n_frames), dim3(1024), 0, c->stream, p, fr, pass, attempt, xyz);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
+int trk_launch_refine(mo_ctx* c, const TrackPrm& p, const TrkFrames& fr, int n_frames, int pass) {
+    hipLaunchKernelGGL(k_trk_refine, dim3((unsigned)n_frames), dim3(TK_REFINE_BLOCK), 0, c->stream, p, fr, pass);
+    HIPCHK(c, hipGetLastError());
+    return MO_OK;
+}
+
+// ---- the host front (map_track.h) ------------------------------------------------------------------------------------------------------
+int track_check(mo_ctx* c, const mo_map_track_params* prm, const double* pose0, size_t n_pose) {
+    if (prm->n_pass < 1 || prm->n_pass > TK_MAX_PASS) return mo_fail(c, MO_ERR_ARG, "n_pass must be in 1 .. 4");
+    if (prm->w <= 0 || prm->h <= 0) return mo_fail(c, MO_ERR_ARG, "w and h must be > 0");
+    if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
+    if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
+    if (!(prm->chi2 >= 0.0) || !std::isfinite(prm->ratio)) return mo_fail(c, MO_ERR_ARG, "chi2 must be >= 0 and ratio finite");
+    for (int k = 0; k < prm->n_pass; k++)
+        if (!(prm->radius[k] >= 0.0) || !std::isfinite(prm->radius[k])) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
+    for (size_t i = 0; i < n_pose * 12; i++)
+        if (!std::isfinite(pose0[i])) return mo_fail(c, MO_ERR_ARG, "pose0 must be finite");
+    return MO_OK;
+}
+
+TrackPrm track_prm(const double K[9], const mo_map_track_params* prm) {
+    TrackPrm p;
+    for (int i = 0; i < 9; i++) p.K[i] = K[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) p.radius[k] = k < prm->n_pass ? prm->radius[k] : 0.0;
+    p.sf = prm->scale_factor; p.ratio = prm->ratio; p.chi2 = prm->chi2;
+    p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist; p.min_matches = prm->min_matches;
+    return p;
+}
+
+void track_defaults(const TrackDst& d, const double* pose0) {
+    for (int i = 0; i < 12; i++) d.pose[i] = pose0[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) {
+        for (int i = 0; i < 12; i++) d.pass_pose[k * 12 + i] = NAN;
+        d.pass_radius[k] = 0.0;
+        d.pass_cand[k] = 0; d.pass_matches[k] = 0; d.pass_inliers[k] = 0;
+    }
+    *d.n_pass_run = 0; *d.ok = 0;
+}
+
+void track_row_defaults(const TrackDst& d, int n) {
+    if (d.point) for (int i = 0; i < n; i++) d.point[i] = -1;
+    if (d.dist) for (int i = 0; i < n; i++) d.dist[i] = -1;
+    if (d.inlier) std::memset(d.inlier, 0, (size_t)n);
+}
+
+int track_result(const TrackDst& d, const TrackRes& r, const mo_map_track_params* prm) {
+    for (int i = 0; i < 12; i++) d.pose[i] = r.pose[i];
+    for (int k = 0; k < TK_MAX_PASS; k++) {
+        for (int i = 0; i < 12; i++) d.pass_pose[k * 12 + i] = r.pass_pose[k][i];
+        d.pass_radius[k] = r.pass_radius[k];
+        d.pass_cand[k] = r.pass_cand[k]; d.pass_matches[k] = r.pass_matches[k]; d.pass_inliers[k] = r.pass_inliers[k];
+    }
+    *d.n_pass_run = r.n_run;
+    return *d.ok = r.n_done == prm->n_pass && r.pass_inliers[prm->n_pass - 1] >= prm->min_inliers;
 }
 
 // mo_map_track (lprm NULL: the local map of the window) and mo_map_track_covisible (the local map of the local keyframes); fprm: the
@@ -457,32 +508,19 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if (!f || !K || !pose0 || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     if (fprm && (fprm->n_levels < 1 || !std::isfinite(fprm->range_lo) || !std::isfinite(fprm->range_hi) || !std::isfinite(fprm->min_cos)))
         return mo_fail(c, MO_ERR_ARG, "n_levels must be >= 1, range_lo, range_hi and min_cos finite");
-    if (prm->n_pass < 1 || prm->n_pass > TK_MAX_PASS) return mo_fail(c, MO_ERR_ARG, "n_pass must be in 1 .. 4");
-    if (prm->w <= 0 || prm->h <= 0) return mo_fail(c, MO_ERR_ARG, "w and h must be > 0");
-    if (prm->window < 0) return mo_fail(c, MO_ERR_ARG, "window must be >= 0");
-    if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
-    if (!(prm->chi2 >= 0.0) || !std::isfinite(prm->ratio)) return mo_fail(c, MO_ERR_ARG, "chi2 must be >= 0 and ratio finite");
-    for (int k = 0; k < prm->n_pass; k++)
-        if (!(prm->radius[k] >= 0.0) || !std::isfinite(prm->radius[k])) return mo_fail(c, MO_ERR_ARG, "radius must be finite and >= 0");
-    for (int i = 0; i < 12; i++)
-        if (!std::isfinite(pose0[i])) return mo_fail(c, MO_ERR_ARG, "pose0 must be finite");
+    int n, rc;
+    if ((rc = track_check(c, prm, pose0, 1))) return rc;
     MAP_ENTER(m);
     HostClock clk(c);
-    for (int i = 0; i < 12; i++) out->pose[i] = pose0[i];
-    for (int k = 0; k < TK_MAX_PASS; k++) {
-        for (int i = 0; i < 12; i++) out->pass_pose[k][i] = NAN;
-        out->pass_radius[k] = 0.0;
-        out->pass_cand[k] = 0; out->pass_matches[k] = 0; out->pass_inliers[k] = 0;
-    }
-    out->n_pass_run = 0; out->n_local = 0; out->ok = 0; out->from_token = 0;
+    const TrackDst dst{out->point, out->dist, out->inlier, out->pose, &out->pass_pose[0][0], out->pass_radius, out->pass_cand, out->pass_matches,
+                       out->pass_inliers, &out->n_pass_run, &out->ok};
+    track_defaults(dst, pose0);
+    out->n_local = 0; out->from_token = 0;
     if (fout) for (int k = 0; k < TK_MAX_PASS; k++) fout->pass_in_image[k] = 0;
-    int n, rc;
     mo_keypoint* fk; uint8_t* fdesc;
     auto defaults = [&](int nq) {
         if (fout && fout->level) for (int i = 0; i < nq; i++) fout->level[i] = -1;
-        if (out->point) for (int i = 0; i < nq; i++) out->point[i] = -1;
-        if (out->dist) for (int i = 0; i < nq; i++) out->dist[i] = -1;
-        if (out->inlier) std::memset(out->inlier, 0, (size_t)nq);
+        track_row_defaults(dst, nq);
     };
     if ((rc = map_stage_frame(m, f, true, &out->from_token, defaults, &n, &fk, &fdesc))) return rc;
     if (!fk) return lprm ? mo_map_local_keyframes(m, lprm, lout) : MO_OK;   // (nothing to search: not tracked, not an error)
@@ -492,16 +530,12 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if ((rc = mo_reserve(c, b.rep, np * 32, b.oct, np, b.cell, TK_CELLS + 1, b.sorted, (size_t)row, b.key, (size_t)row, b.match, (size_t)row,
                          b.minl, (size_t)row, b.qpt, (size_t)row, b.qdist, (size_t)row, b.qinl, (size_t)row, b.res)))
         return rc;
-    TrackPrm p;
-    for (int i = 0; i < 9; i++) p.K[i] = K[i];
-    for (int i = 0; i < 12; i++) p.pose0[i] = pose0[i];
-    for (int k = 0; k < TK_MAX_PASS; k++) p.radius[k] = k < prm->n_pass ? prm->radius[k] : 0.0;
-    p.sf = prm->scale_factor; p.ratio = prm->ratio; p.chi2 = prm->chi2;
-    p.w = prm->w; p.h = prm->h; p.max_dist = prm->max_dist; p.min_matches = prm->min_matches;
+    const TrackPrm p = track_prm(K, prm);
+    const TrkFrames one = trk_frames(b, fk, fdesc, m->kcnt + m->kslots, nullptr, row);   // one frame: the spare slot's rows and count
     const int lo_pos = map_window_lo(prm->window, n_kf);
     const MapPts src = m->P[m->cur].view();
     const unsigned pblocks = (unsigned)((m->n_pts + 255) / 256);
-    hipLaunchKernelGGL(k_trk_init, dim3(1), dim3(256), 0, c->stream, p, n, b.res, b.key, b.qpt, b.qdist, b.qinl);
+    if ((rc = trk_launch_init(c, one, 1, pose0, &b.res.p->n_local))) return rc;
     if (lprm && ((rc = covis_enqueue(m)) || (rc = covis_select_enqueue(m, lprm)))) return rc;
     if ((rc = lprm ? trk_launch_rep_mask(m, covis_mask(m), b.rep, b.oct, &b.res.p->n_local)
                    : trk_launch_rep(m, lo_pos, b.rep, b.oct, &b.res.p->n_local)) ||
@@ -527,13 +561,10 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
             else
                 hipLaunchKernelGGL(k_trk_search, dim3(pblocks), dim3(256), 0, c->stream, p, k, a, src.xyz, (int)m->n_pts, b.rep, b.oct, fk, fdesc, b.cell,
                                    b.sorted, b.key, b.res);
-            hipLaunchKernelGGL(k_trk_compact, dim3(1), dim3(1024), 0, c->stream, p, k, a, n, fk, src.xyz, b.key, b.match, b.qpt, b.qdist, b.qinl,
-                               b.res);
+            if ((rc = trk_launch_compact(c, p, one, 1, k, a, src.xyz))) return rc;
         }
-        HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "track_search");
-        hipLaunchKernelGGL(k_trk_refine, dim3(1), dim3(TK_REFINE_BLOCK), 0, c->stream, p, k, b.match, b.minl, b.qinl, b.res);
-        HIPCHK(c, hipGetLastError());
+        if ((rc = trk_launch_refine(c, p, one, 1, k))) return rc;
         mo_stage_mark(c, "track_refine");
     }
     if (fprm) {
@@ -550,19 +581,12 @@ static int track_run(mo_map* m, const mo_frame_ref* f, const double K[9], const 
     if ((rc = map_sync(c, clk))) return rc;
     if (lprm) covis_finish(m, lout);
     const TrackRes& r = b.res.host();
-    for (int i = 0; i < 12; i++) out->pose[i] = r.pose[i];
-    for (int k = 0; k < TK_MAX_PASS; k++) {
-        for (int i = 0; i < 12; i++) out->pass_pose[k][i] = r.pass_pose[k][i];
-        out->pass_radius[k] = r.pass_radius[k];
-        out->pass_cand[k] = r.pass_cand[k]; out->pass_matches[k] = r.pass_matches[k]; out->pass_inliers[k] = r.pass_inliers[k];
-    }
+    track_result(dst, r, prm);
     if (fprm) {
         const FrustumRes& fres = fb->fres.host();
         for (int k = 0; k < r.n_run; k++) fout->pass_in_image[k] = fres.in_image[k][fres.attempt[k] ? 1 : 0];
     }
-    out->n_pass_run = r.n_run;
     out->n_local = r.n_local;
-    out->ok = r.n_done == prm->n_pass && r.pass_inliers[prm->n_pass - 1] >= prm->min_inliers;
     return MO_OK;
 }
 

@@ -874,6 +874,30 @@ class LocalMapper:
         return V.FrameRef(token, V._ptr(kps_arr), V._ptr(desc), n), n, (kps_arr, desc)
 
     # ---- tracking against the map -------------------------------------------------------------------------------------------------
+    def _track_params(self, window, radii, scale_factor, max_dist, ratio, chi2, min_matches, min_inliers, image_size):
+        """MapTrackParams of track_local_map and track_local_map_batch: the radii checked, image_size defaulted to the last keyframe's image"""
+        radii = [float(r) for r in radii]
+        if not 1 <= len(radii) <= 4:
+            raise ValueError("radii: one to four passes")
+        if image_size is None:
+            if self.keyframes:
+                image_size = self.keyframes[-1]["image"].shape[1::-1]
+            else:
+                Km = np.asarray(self.camera_matrix, np.float64)
+                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        return V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
+                                float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
+
+    @staticmethod
+    def _track_info(n, point, dist, inlier, nr, pass_pose, pass_radius, pass_cand, pass_matches, pass_inliers, n_local, from_token):
+        """the info dict of one tracked frame from its per-keypoint rows and per-pass arrays (nr passes ran)"""
+        nr = int(nr)
+        return {"point": point[:n], "dist": dist[:n], "inlier": inlier[:n].astype(bool),
+                "pass_pose": [np.vstack([np.array(pass_pose[k]).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(nr)],
+                "pass_radius": [float(pass_radius[k]) for k in range(nr)], "pass_cand": [int(pass_cand[k]) for k in range(nr)],
+                "pass_matches": [int(pass_matches[k]) for k in range(nr)], "pass_inliers": [int(pass_inliers[k]) for k in range(nr)],
+                "n_pass_run": nr, "n_local": int(n_local), "from_token": bool(from_token)}
+
     def track_local_map(self, keypoints, descriptors, pose, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8,
                         chi2=5.991, min_matches=20, min_inliers=30, image_size=None, local="window", seed_points=None, n_best=10, min_weight=15,
                         frustum=False, n_levels=8, view_range=(0.8, 1.2), min_cos=0.5):
@@ -898,23 +922,13 @@ class LocalMapper:
         `level` (the predicted level of its point, -1: none)."""
         if local not in ("window", "covisible"):
             raise ValueError("local: \"window\" or \"covisible\"")
-        radii = [float(r) for r in radii]
-        if not 1 <= len(radii) <= 4:
-            raise ValueError("radii: one to four passes")
-        if image_size is None:
-            if self.keyframes:
-                image_size = self.keyframes[-1]["image"].shape[1::-1]
-            else:
-                Km = np.asarray(self.camera_matrix, np.float64)
-                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        prm = self._track_params(window, radii, scale_factor, max_dist, ratio, chi2, min_matches, min_inliers, image_size)
         ref, n, _keep = self._frame_ref(keypoints, descriptors)
         K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
         pose0 = np.ascontiguousarray(np.asarray(pose, np.float64)[:3, :4]).reshape(12)
         point = np.full(max(n, 1), -1, np.int32)
         dist = np.full(max(n, 1), -1, np.int32)
         inlier = np.zeros(max(n, 1), np.uint8)
-        prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
-                               float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
         out = V.MapTrackOut(point.ctypes.data, dist.ctypes.data, inlier.ctypes.data)
         if frustum:
             level = np.full(max(n, 1), -1, np.int32)
@@ -934,11 +948,8 @@ class LocalMapper:
         T = np.eye(4)
         T[:3, :] = np.array(out.pose).reshape(3, 4)
         nr = int(out.n_pass_run)
-        info = {"point": point[:n], "dist": dist[:n], "inlier": inlier[:n].astype(bool),
-                "pass_pose": [np.vstack([np.array(out.pass_pose[k]).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(nr)],
-                "pass_radius": [float(out.pass_radius[k]) for k in range(nr)], "pass_cand": [int(out.pass_cand[k]) for k in range(nr)],
-                "pass_matches": [int(out.pass_matches[k]) for k in range(nr)], "pass_inliers": [int(out.pass_inliers[k]) for k in range(nr)],
-                "n_pass_run": nr, "n_local": int(out.n_local), "from_token": bool(out.from_token)}
+        info = self._track_info(n, point, dist, inlier, nr, out.pass_pose, out.pass_radius, out.pass_cand, out.pass_matches, out.pass_inliers,
+                                out.n_local, out.from_token)
         if frustum:
             info["level"] = level[:n]
             info["pass_in_image"] = [int(fout.pass_in_image[k]) for k in range(nr)]
@@ -957,9 +968,6 @@ class LocalMapper:
         Returns (ok [n] bool, poses [n][4][4], infos): every frame's results are what track_local_map returns for it alone on the same
         map, bit for bit, whatever the order and the company; infos[i] has the keys of track_local_map's info (`n_local` is the
         batch's: the local map is formed once)."""
-        radii = [float(r) for r in radii]
-        if not 1 <= len(radii) <= 4:
-            raise ValueError("radii: one to four passes")
         frames = list(frames)
         nf = len(frames)
         if nf > V.TRACK_BATCH_MAX:
@@ -973,12 +981,7 @@ class LocalMapper:
         if poses.ndim != 3 or poses.shape[0] != nf or poses.shape[1:] not in ((4, 4), (3, 4)):
             raise ValueError("poses: [n][4][4] or [n][3][4], one per frame")
         pose0 = np.ascontiguousarray(poses[:, :3, :4]).reshape(nf, 12)
-        if image_size is None:
-            if self.keyframes:
-                image_size = self.keyframes[-1]["image"].shape[1::-1]
-            else:
-                Km = np.asarray(self.camera_matrix, np.float64)
-                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+        prm = self._track_params(window, radii, scale_factor, max_dist, ratio, chi2, min_matches, min_inliers, image_size)
         refs = (V.FrameRef * max(nf, 1))()
         ns, keep = [], []
         for i, (kp, de) in enumerate(frames):
@@ -997,22 +1000,13 @@ class LocalMapper:
         pass_cand, pass_matches, pass_inliers = (np.zeros((m, 4), np.int32) for _ in range(3))
         n_run, ok, from_token = (np.zeros(m, np.int32) for _ in range(3))
         K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
-        prm = V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
-                               float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
         out = V.MapTrackBatchOut(stride, *[a.ctypes.data for a in (point, dist, inlier, pose, pass_pose, pass_radius, pass_cand, pass_matches,
                                                                    pass_inliers, n_run, ok, from_token)])
         self._check(self.lib.mo_map_track_batch(self._h, refs, nf, V._ptr(K), pose0.ctypes.data if nf else None, C.byref(prm), C.byref(out)))
         Ts = np.tile(np.eye(4), (nf, 1, 1))
         Ts[:, :3, :] = pose[:nf].reshape(nf, 3, 4)
-        infos = []
-        for i in range(nf):
-            n, nr = ns[i], int(n_run[i])
-            infos.append({"point": point[i, :n], "dist": dist[i, :n], "inlier": inlier[i, :n].astype(bool),
-                          "pass_pose": [np.vstack([pass_pose[i, k].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(nr)],
-                          "pass_radius": [float(pass_radius[i, k]) for k in range(nr)], "pass_cand": [int(pass_cand[i, k]) for k in range(nr)],
-                          "pass_matches": [int(pass_matches[i, k]) for k in range(nr)],
-                          "pass_inliers": [int(pass_inliers[i, k]) for k in range(nr)], "n_pass_run": nr, "n_local": int(out.n_local),
-                          "from_token": bool(from_token[i])})
+        infos = [self._track_info(ns[i], point[i], dist[i], inlier[i], n_run[i], pass_pose[i], pass_radius[i], pass_cand[i], pass_matches[i],
+                                  pass_inliers[i], out.n_local, from_token[i]) for i in range(nf)]
         return ok[:nf].astype(bool), Ts, infos
 
     def point_views(self, scale_factor=1.2, n_levels=8):
