@@ -2,7 +2,8 @@
 // For each vector instruction: cycles per wave-instruction as seen by one wave (s_memtime) with 1, 2, 4, 8 waves per SIMD,
 // independent (16 registers) and dependent (one register chain) streams.  Scalar classes (s_add_i32, s_and_b64, s_bcnt1_i32_b64, s_cselect_b64, s_lshl_b64,
 // writes of EXEC, s_nop 0, s_waitcnt) and vector : scalar mixes with 1, 2 or 4 busy SIMDs per CU.  Build: make -C tools; run on the GPU box:
-// _build/ubench [workgroups [vector|scalar|all]]
+// _build/ubench [workgroups [vector|scalar|fold|all]]   ("fold": the matcher's top-2 update in 16 and 32 bits, and its whole inner-loop stream,
+// at 8 wavefronts per SIMD in 256-thread workgroups; profiles/match_fold16_ubench.txt)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -220,6 +221,79 @@ DEFS(v_xor, "v_xor_b32 %8, %8, %14\n\tv_xor_b32 %9, %9, %14\n\tv_xor_b32 %10, %1
 DEFS(mix_v2s1, "v_xor_b32 %8, %8, %14\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %0, %0, %12\n\tv_xor_b32 %10, %10, %14\n\tv_xor_b32 %11, %11, %14\n\ts_add_i32 %1, %1, %12")
 DEFS(mix_v1s1, "v_xor_b32 %8, %8, %14\n\ts_add_i32 %0, %0, %12\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %1, %1, %12")
 DEFS(mix_v1s2, "v_xor_b32 %8, %8, %14\n\ts_add_i32 %0, %0, %12\n\ts_add_i32 %1, %1, %12\n\tv_xor_b32 %9, %9, %14\n\ts_add_i32 %2, %2, %12\n\ts_add_i32 %3, %3, %12")
+// ---- the matcher's top-2 fold ("fold" mode): dependent chains and the two whole inner-loop streams of k_match_lds, in the matcher's own
+// launch shape (256-thread workgroups, 8 per CU = 8 wavefronts per SIMD).  %0-%3: chain registers, %4 / %5: lane-varying constants.
+#define DEFF(NAME, ASM)                                                                                   \
+    __global__ __launch_bounds__(256) void kf_##NAME(uint32_t* out, int iters, unsigned long long* cyc) { \
+        uint32_t r0 = (threadIdx.x * 2654435761u) >> 17, r1 = r0 | 0x4000u, r2 = 0, r3 = (threadIdx.x * 40503u + 77u) & 0x7FFFu; \
+        uint32_t c = (threadIdx.x | 0x0101u) & 0x7FFFu, e = threadIdx.x & 127u;                           \
+        unsigned long long t0 = __builtin_amdgcn_s_memtime();                                             \
+        for (int i = 0; i < iters; i++) {                                                                 \
+            _Pragma("unroll") for (int k = 0; k < 16; k++)                                                \
+                asm volatile(ASM : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : "v"(c), "v"(e));              \
+        }                                                                                                 \
+        unsigned long long t1 = __builtin_amdgcn_s_memtime();                                             \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = r0 ^ r1 ^ r2 ^ r3;                                   \
+        if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)] = t1 - t0;  \
+    }
+DEFF(xor, "v_xor_b32 %0, %0, %4")
+DEFF(bcnt, "v_bcnt_u32_b32 %0, %4, %0")
+DEFF(min_u16, "v_min_u16 %0, %0, %4")
+DEFF(max_u16, "v_max_u16 %0, %0, %4")
+DEFF(min_u32, "v_min_u32 %0, %0, %4")
+DEFF(med3_u32, "v_med3_u32 %0, %0, %4, %5")
+DEFF(lshl_or, "v_lshl_or_b32 %0, %0, 7, %5")
+DEFF(fold16, "v_max_u16 %2, %0, %3\n\tv_min_u16 %1, %2, %1\n\tv_min_u16 %0, %0, %3")  // key in %3: the proposed update of (t0, t1)
+DEFF(fold32, "v_med3_u32 %1, %0, %1, %3\n\tv_min_u32 %0, %0, %3")                      // the present update of (k0, k1)
+DEFF(bcnt_lshl_or, "v_bcnt_u32_b32 %0, %4, %0\n\tv_lshl_or_b32 %3, %0, 7, %5")          // the key built beside the popcount chain
+DEFF(key16, "v_bcnt_u32_b32 %3, %4, %0\n\tv_lshl_or_b32 %3, %3, 7, %5\n\tv_max_u16 %2, %0, %3\n\tv_min_u16 %1, %2, %1\n\tv_min_u16 %0, %0, %3")
+DEFF(key32, "v_bcnt_u32_b32 %3, %4, %0\n\tv_lshl_or_b32 %3, %3, 20, %5\n\tv_med3_u32 %1, %0, %1, %3\n\tv_min_u32 %0, %0, %3")
+
+// One trip = 4 train descriptors against the lane's two queries, instruction for instruction the descriptor loop of k_match_lds without its
+// LDS reads: per query 8 x (v_xor + v_bcnt), the key, and the update in 32 bits (19 instructions) or on 16-bit tile-local keys (20).
+template <bool K16>
+__global__ __launch_bounds__(256) void kf_stream(uint32_t* out, int iters, unsigned long long* cyc) {
+    uint32_t a[2][8], b[8], d[2], x[2], lo[2], hi[2], t[2], key[2];
+    for (int k = 0; k < 8; k++) {
+        b[k] = threadIdx.x * 2246822519u + k * 3266489917u;
+        for (int m = 0; m < 2; m++) a[m][k] = threadIdx.x * 2654435761u + (k * 2 + m) * 40503u + 12345u;
+    }
+    for (int m = 0; m < 2; m++) { lo[m] = K16 ? 0xFFFFu : 0xFFFFFFFFu; hi[m] = lo[m]; t[m] = 0; }
+    unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < iters; i++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t jl = __builtin_amdgcn_readfirstlane((i * 4 + j) & 127);
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+#pragma unroll
+                for (int m = 0; m < 2; m++) {
+                    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(x[m]) : "v"(a[m][k]), "v"(b[(k + j) & 7]));
+                    if (k == 0) asm volatile("v_bcnt_u32_b32 %0, %1, 0" : "=v"(d[m]) : "v"(x[m]));
+                    else asm volatile("v_bcnt_u32_b32 %0, %1, %0" : "+v"(d[m]) : "v"(x[m]));
+                }
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                if (K16) {
+                    asm volatile("v_lshl_or_b32 %0, %1, 7, %2" : "=v"(key[m]) : "v"(d[m]), "s"(jl));
+                    asm volatile("v_max_u16 %0, %1, %2" : "=v"(t[m]) : "v"(lo[m]), "v"(key[m]));
+                    asm volatile("v_min_u16 %0, %1, %0" : "+v"(hi[m]) : "v"(t[m]));
+                    asm volatile("v_min_u16 %0, %0, %1" : "+v"(lo[m]) : "v"(key[m]));
+                } else {
+                    asm volatile("v_lshl_or_b32 %0, %1, 20, %2" : "=v"(key[m]) : "v"(d[m]), "s"(jl));
+                    asm volatile("v_med3_u32 %0, %1, %0, %2" : "+v"(hi[m]) : "v"(lo[m]), "v"(key[m]));
+                    asm volatile("v_min_u32 %0, %0, %1" : "+v"(lo[m]) : "v"(key[m]));
+                }
+            }
+        }
+    }
+    unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    out[blockIdx.x * blockDim.x + threadIdx.x] = lo[0] ^ lo[1] ^ hi[0] ^ hi[1];
+    if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)] = t1 - t0;
+}
+struct FEntry { const char* name; void (*k)(uint32_t*, int, unsigned long long*); int per_trip, block; };  // instructions per trip / per printed block
+#define FE(NAME, N) {#NAME, kf_##NAME, 16 * N, N}
+
 typedef void (*skern_t)(uint32_t*, int, unsigned long long*, int);
 struct SEntry { const char* name; skern_t k; int per_block; };
 #define SE(NAME, N) {#NAME, ks_##NAME, N}
@@ -279,7 +353,36 @@ int main(int argc, char** argv) {
         for (int c : persimd) { sused += c > 0; smx = std::max(smx, c); }
         printf("census w=%d: %d waves on %d CUs (max %d per CU), %d SIMDs (max %d per SIMD)\n", w, nw, used, mx, sused, smx);
     }
-    const std::string what = argc > 2 ? argv[2] : "all";  // "vector", "scalar" or "all"
+    const std::string what = argc > 2 ? argv[2] : "all";  // "vector", "scalar", "fold" or "all" (= vector + scalar)
+    if (what == "fold") {
+        // 8 workgroups of 256 threads per CU: 8 wavefronts on every SIMD, as k_match_lds runs.  Per row: cycles per instruction as a wavefront
+        // sees them (median, maximum) and the throughput figure: wall time x clock / (8 wavefronts x instructions per wavefront), best of 3.
+        std::vector<FEntry> fs = {FE(xor, 1), FE(bcnt, 1), FE(min_u16, 1), FE(max_u16, 1), FE(min_u32, 1), FE(med3_u32, 1), FE(lshl_or, 1),
+                                  FE(fold16, 3), FE(fold32, 2), FE(bcnt_lshl_or, 2), FE(key16, 5), FE(key32, 4),
+                                  {"stream19_u32", kf_stream<false>, 4 * 2 * 19, 19}, {"stream20_u16", kf_stream<true>, 4 * 2 * 20, 20}};
+        const int blocks = 8 * nblk, nw = blocks * 4;
+        printf("\nfold mode: %d workgroups of 256 threads (8 wavefronts per SIMD), dependent chains; clock %.3f GHz\n", blocks, ghz);
+        printf("%-14s %6s %9s %9s %12s %14s\n", "row", "instr", "wave med", "wave max", "wall cyc/ins", "cyc/block");
+        for (auto& e : fs) {
+            const double per_wave = (double)iters * e.per_trip;
+            float best = 1e30f;
+            for (int pass = 0; pass < 4; pass++) {  // first pass warms
+                hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+                hipEventRecord(e0);
+                hipLaunchKernelGGL(e.k, dim3(blocks), dim3(256), 0, 0, d_out, iters, d_cyc);
+                hipEventRecord(e1);
+                hipDeviceSynchronize();
+                float ms; hipEventElapsedTime(&ms, e0, e1);
+                if (pass) best = std::min(best, ms);
+                hipEventDestroy(e0); hipEventDestroy(e1);
+            }
+            hipMemcpy(h.data(), d_cyc, (size_t)nw * 8, hipMemcpyDeviceToHost);
+            std::sort(h.begin(), h.begin() + nw);
+            const double wall = best * 1e-3 * ghz * 1e9 / (8 * per_wave);
+            printf("%-14s %6d %9.2f %9.2f %12.3f %14.2f\n", e.name, e.block, h[nw / 2] / per_wave, h[nw - 1] / per_wave, wall, wall * e.block);
+        }
+        return 0;
+    }
     if (what != "scalar") {
     printf("device %s, %d CUs; ticks (shader cycles) per wave-instruction seen by a wave, median over waves / the same divided by waves per SIMD; launch wall\n", prop.name, ncu);
     printf("%-16s %-4s", "op", "");

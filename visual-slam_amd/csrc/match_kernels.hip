@@ -4,8 +4,9 @@
 //
 // Default path (north_star: integer bit work, no MFMA): each lane owns one query descriptor in 8 VGPRs; the train descriptors are
 // walked by every wave in the same order, so their 32 bytes arrive through wave-uniform (scalar) loads and
-// the inner loop is 8 x (v_xor_b32 + v_bcnt_u32_b32) + a packed (distance << 20 | trainIdx) key folded
-// into the running best / second-best with v_med3_u32 + v_min_u32.  Smallest key == smallest distance,
+// the inner loop is 8 x (v_xor_b32 + v_bcnt_u32_b32) + a packed (distance, trainIdx) key folded into a best / second-best
+// pair: per tile of 128 train rows on 16-bit keys (distance << 7 | index in the tile) with v_max_u16 + 2 v_min_u16, and once per
+// tile into the running (distance << 20 | trainIdx) pair with v_med3_u32 + v_min_u32.  Smallest key == smallest distance,
 // ties towards the lower trainIdx, exactly batch_distance.cpp's strict '<' insertion order.
 #include <algorithm>
 #include <climits>
@@ -52,24 +53,43 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
 // A workgroup copies tiles of ML_TILE train descriptors (4 KB, one 16-byte load per thread, register-staged and
 // double-buffered so the next tile's global load is in flight during the current tile's compute; one barrier per tile)
 // and every wavefront reads them back with wave-uniform (broadcast) ds_read_b128: two LDS instructions per train descriptor
-// next to 38 vector instructions, in-order returns (counted lgkmcnt waits, reads issued several descriptors ahead).
+// next to 40 vector instructions, in-order returns (counted lgkmcnt waits, reads issued several descriptors ahead).
+// Bound: vector issue.  Per query and train descriptor 8 v_xor_b32 + 3 16-bit min / max in the fast class (2.26 cycles per wave
+// instruction) and 8 v_bcnt_u32_b32 + v_lshl_or_b32 in the slow one (4.5), plus 0.35 for the tile merge: 65.4 cycles, 0.43 ms per 255 pairs of
+// 2000 x 2000 at 2.43 GHz; measured 0.466 ms.  The 32-bit update it replaces (v_med3_u32 + v_min_u32, both slow: 67.6 cycles) measured
+// 0.499 ms in the same runs (profiles/match_fold16_ab.txt).
 // (Round 1's kernel took them through scalar loads instead: those return out of order, every trip waited for all of them
 // (lgkmcnt(0)) with nothing in flight, and it sat at 0.42 of the vector issue rate (profiles/r01_sq_counters); it lived on as the path
 // for descriptor arrays that are not 16-byte aligned until round 4, which asks for the alignment instead.)
 #define ML_THREADS 256
 #define ML_Q 2
 #define ML_PER_BLOCK (ML_THREADS * ML_Q)
-#define ML_RESIDENT 8       // workgroups a CU holds at once: 8 wavefronts per SIMD (63 VGPRs), 8.3 KB of LDS each
+#define ML_RESIDENT 8       // workgroups a CU holds at once: 8 wavefronts per SIMD (64 VGPRs), 12.4 KB of LDS each (63 and 8.3 KB with the 32-bit fold)
 #define ML_SPLIT_MAX 32     // slices of the train set at most (match_launch_pairs)
 #define ML_TILE 128  // train descriptors per tile: 256 threads x 16 B
+// Inside a tile the key is (distance << 7 | index in the tile): 7 bits of index below 9 bits of distance (256 needs bit 15), at most
+// 32895, so it orders as an unsigned 16-bit number and 0xFFFF is free as "none".
+#define KEY16_NONE 0xFFFFu
+static_assert(ML_TILE <= 128, "the tile-local key holds the index in 7 bits: distance 256 << 7 must still fit bit 15");
+// 16-bit VOP2 min / max issue at the fast rate, v_min_u32 and every v_med3 / v_min3 at the slow one (profiles/match_fold16_ubench.txt).  As
+// asm: from plain C the compiler fuses pairs into v_min3 / v_max3.  On gfx9 they write zeros to the upper half of the register, so keys
+// that enter with a clear upper half keep it and the register reads as the key.
+__device__ __forceinline__ uint32_t min16u(uint32_t a, uint32_t b) { uint32_t r; asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ uint32_t max16u(uint32_t a, uint32_t b) { uint32_t r; asm("v_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-__global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restrict__ qbase, const uint8_t* __restrict__ tbase,
-                                                          size_t q_stride, size_t t_stride, const int32_t* __restrict__ counts,
-                                                          const int32_t* __restrict__ qf, const int32_t* __restrict__ tf,
-                                                          int nq_fixed, int nt_fixed, int out_stride, double ratio,
-                                                          int32_t* __restrict__ oidx, int32_t* __restrict__ odist,
-                                                          uint8_t* __restrict__ opass, uint2* __restrict__ part) {
+// K16 = false keeps the 32-bit update in the descriptor loop (19 instructions per query and train descriptor instead of 20): a wavefront that
+// has its SIMD to itself issues one instruction per 5.5 - 7 cycles whatever the class, so there the count decides, not the class
+// (match_launch_pairs chooses; 1, 2 and 4 pairs of 2000 x 2000 are 0.8 us faster this way, profiles/match_fold16_ab.txt).
+// amdgpu_waves_per_eu(8, 8): the register allocator lands on 65 VGPRs by itself and on 64 (no scratch) when told that 8 wavefronts are wanted
+template <bool K16>
+__global__ __launch_bounds__(ML_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_match_lds(
+    const uint8_t* __restrict__ qbase, const uint8_t* __restrict__ tbase, size_t q_stride, size_t t_stride, const int32_t* __restrict__ counts,
+    const int32_t* __restrict__ qf, const int32_t* __restrict__ tf, int nq_fixed, int nt_fixed, int out_stride, double ratio,
+    int32_t* __restrict__ oidx, int32_t* __restrict__ odist, uint8_t* __restrict__ opass, uint2* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) uint4 s_t[2][ML_TILE * 2 + 4];  // + one look-ahead group past the last descriptor
+    // K16: the running pair (k0, k1) of a lane's queries is touched once per tile.  It waits here, in the lane's own slot, while the
+    // descriptor loop runs: with the tile-local keys beside it in registers the kernel needs 68 VGPRs, one wavefront per SIMD fewer.
+    __shared__ uint2 s_k[K16 ? ML_Q : 1][K16 ? ML_THREADS : 1];
     const int pair = blockIdx.y, tid = threadIdx.x;
     const int qfr = qf ? qf[pair] : pair, tfr = tf ? tf[pair] : pair;
     const int nq = counts ? min(counts[qfr], out_stride) : nq_fixed;
@@ -85,6 +105,7 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
         a[m][0] = lo.x; a[m][1] = lo.y; a[m][2] = lo.z; a[m][3] = lo.w;
         a[m][4] = hi.x; a[m][5] = hi.y; a[m][6] = hi.z; a[m][7] = hi.w;
         k0[m] = KEY_NONE; k1[m] = KEY_NONE;
+        if constexpr (K16) s_k[m][tid] = make_uint2(KEY_NONE, KEY_NONE);
     }
     // gridDim.z > 1 (see match_launch_pairs): this workgroup folds only its slice of the train tiles and leaves its
     // two best keys in `part`; k_match_merge folds the slices - keys carry the global train index, so the result is the same
@@ -120,7 +141,10 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
         }
         const uint4* s = s_t[tile & 1];
         const int j0 = tile * ML_TILE, n = min(ML_TILE, nt - j0);
-        auto fold = [&](const uint4& b0, const uint4& b1, int j) {  // j: wave-uniform train index
+        uint32_t t0[ML_Q], t1[ML_Q];  // the tile's own best / second-best key (d << 7 | jl), t0 <= t1
+#pragma unroll
+        for (int m = 0; m < ML_Q; m++) { t0[m] = KEY16_NONE; t1[m] = KEY16_NONE; }
+        auto fold = [&](const uint4& b0, const uint4& b1, int jl) {  // jl: wave-uniform train index inside the tile
             const uint32_t b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
             uint32_t d[ML_Q];
 #pragma unroll
@@ -131,9 +155,15 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
                 for (int m = 0; m < ML_Q; m++) d[m] = bcnt_acc(a[m][k] ^ b[k], d[m]);
 #pragma unroll
             for (int m = 0; m < ML_Q; m++) {
-                const uint32_t key = (d[m] << 20) | (uint32_t)j;
-                k1[m] = med3_u32(k0[m], k1[m], key);  // k0 <= k1: new second-best = median, new best = minimum
-                k0[m] = min(k0[m], key);
+                if constexpr (K16) {
+                    const uint32_t key = (d[m] << 7) | (uint32_t)jl;
+                    t1[m] = min16u(max16u(t0[m], key), t1[m]);  // t0 <= t1: new second-best = min(t1, max(t0, key)), new best = minimum
+                    t0[m] = min16u(t0[m], key);
+                } else {
+                    const uint32_t key = (d[m] << 20) | (uint32_t)(j0 + jl);
+                    k1[m] = med3_u32(k0[m], k1[m], key);  // k0 <= k1: new second-best = median, new best = minimum
+                    k0[m] = min(k0[m], key);
+                }
             }
         };
         // groups of two descriptors with one group of look-ahead: the broadcast reads of group g+1 are in flight while
@@ -143,28 +173,43 @@ __global__ __launch_bounds__(ML_THREADS) void k_match_lds(const uint8_t* __restr
         int j = 0;
         for (; j + 4 <= n; j += 4) {
             const uint4 e0 = s[2 * j + 4], e1 = s[2 * j + 5], e2 = s[2 * j + 6], e3 = s[2 * j + 7];
-            fold(c0, c1, j0 + j);
-            fold(c2, c3, j0 + j + 1);
+            fold(c0, c1, j);
+            fold(c2, c3, j + 1);
             c0 = s[2 * j + 8]; c1 = s[2 * j + 9]; c2 = s[2 * j + 10]; c3 = s[2 * j + 11];
-            fold(e0, e1, j0 + j + 2);
-            fold(e2, e3, j0 + j + 3);
+            fold(e0, e1, j + 2);
+            fold(e2, e3, j + 3);
         }
         if (j + 2 <= n) {
             const uint4 e0 = s[2 * j + 4], e1 = s[2 * j + 5];
-            fold(c0, c1, j0 + j);
-            fold(c2, c3, j0 + j + 1);
+            fold(c0, c1, j);
+            fold(c2, c3, j + 1);
             c0 = e0; c1 = e1;
             j += 2;
         }
-        if (j < n) fold(c0, c1, j0 + j);
+        if (j < n) fold(c0, c1, j);
+        // the tile's two keys, widened to (distance << 20 | global train index), enter the running pair: the two smallest keys of the whole
+        // train set are among the two smallest of their tiles, and inside a tile (d, jl) orders as (d, j)
+#pragma unroll
+        for (int m = 0; K16 && m < ML_Q; m++) {
+            const uint32_t g0 = t0[m] == KEY16_NONE ? KEY_NONE : ((t0[m] >> 7) << 20) | (uint32_t)(j0 + (int)(t0[m] & 127u));
+            const uint32_t g1 = t1[m] == KEY16_NONE ? KEY_NONE : ((t1[m] >> 7) << 20) | (uint32_t)(j0 + (int)(t1[m] & 127u));
+            uint2 k = s_k[m][tid];
+            k.y = med3_u32(k.x, k.y, g0);  // k.x <= k.y: new second-best = median, new best = minimum
+            k.x = min(k.x, g0);
+            k.y = med3_u32(k.x, k.y, g1);
+            k.x = min(k.x, g1);
+            s_k[m][tid] = k;
+        }
         if (more) s_t[(tile + 1) & 1][tid] = nxt;
         __syncthreads();  // the buffer written here was last read before the previous barrier
     }
 #pragma unroll
     for (int m = 0; m < ML_Q; m++) {
         const int qi = blockIdx.x * ML_PER_BLOCK + m * ML_THREADS + tid;
-        if (qi < nq && part) part[((size_t)pair * gridDim.z + blockIdx.z) * out_stride + qi] = make_uint2(k0[m], k1[m]);
-        if (qi < nq && !part) emit_match_key(k0[m], k1[m], ratio, (size_t)pair * out_stride + qi, oidx, odist, opass);
+        uint2 k = make_uint2(k0[m], k1[m]);
+        if constexpr (K16) k = s_k[m][tid];
+        if (qi < nq && part) part[((size_t)pair * gridDim.z + blockIdx.z) * out_stride + qi] = k;
+        if (qi < nq && !part) emit_match_key(k.x, k.y, ratio, (size_t)pair * out_stride + qi, oidx, odist, opass);
     }
 }
 
@@ -365,10 +410,12 @@ int match_launch_pairs(mo_ctx* c, const uint8_t* d_q, const uint8_t* d_t, size_t
         const int per_slice = (ntile + n_split - 1) / n_split;
         n_split = std::max(1, (ntile + per_slice - 1) / std::max(1, per_slice));
     }
+    // more than one workgroup per CU (= wavefront per SIMD): the 16-bit fold, whose instructions are cheaper; otherwise the 32-bit one, which has fewer
+    auto* const kern = blocks * n_split > c->n_cu ? k_match_lds<true> : k_match_lds<false>;
     if (n_split > 1) {
         if (int rc = c->d_match_part.reserve_exact(c, (size_t)n_pairs * n_split * out_stride)) return rc;
         grid.z = n_split;
-        hipLaunchKernelGGL(k_match_lds, grid, dim3(ML_THREADS), 0, c->stream, d_q, d_t, q_stride, t_stride, d_counts, d_qf,
+        hipLaunchKernelGGL(kern, grid, dim3(ML_THREADS), 0, c->stream, d_q, d_t, q_stride, t_stride, d_counts, d_qf,
                            d_tf, nq_fixed, nt_fixed, out_stride, ratio, d_idx, d_dist, d_pass, c->d_match_part);
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_match_merge, dim3((nq_max + 255) / 256, n_pairs), dim3(256), 0, c->stream,
@@ -377,7 +424,7 @@ int match_launch_pairs(mo_ctx* c, const uint8_t* d_q, const uint8_t* d_t, size_t
         HIPCHK(c, hipGetLastError());
         return MO_OK;
     }
-    hipLaunchKernelGGL(k_match_lds, grid, dim3(ML_THREADS), 0, c->stream, d_q, d_t, q_stride, t_stride, d_counts, d_qf, d_tf,
+    hipLaunchKernelGGL(kern, grid, dim3(ML_THREADS), 0, c->stream, d_q, d_t, q_stride, t_stride, d_counts, d_qf, d_tf,
                        nq_fixed, nt_fixed, out_stride, ratio, d_idx, d_dist, d_pass, (uint2*)nullptr);
     HIPCHK(c, hipGetLastError());
     return MO_OK;
