@@ -494,7 +494,13 @@ def test_vocabulary_training_hand_cases():
 # What one covisibility() fills under a poison byte on loop_worlds.feature_world: after covisibility alone, then after each further
 # feature of feature_steps has run once.  Measured on the commit before the features registered themselves with the map (its library
 # through VSLAM_AMD_LIB, this test printing the sequence); a feature that registers nothing, or one the fill walks past, changes a count.
-FEATURE_FILLS = [18, 30, 41, 68, 85, 94, 102, 120]
+# That sequence was [18, 30, 41, 68, 85, 94, 102, 120].  The step of bundle_adjust(window=4) was 27 buffers, all of BaBufs: 25 problem
+# arrays (pout is not reserved without want_points), S and the result block.  Since the local and the global solver share one problem
+# (BaProblem of csrc/ba_problem.h) it is 28, in two features: 25 - lpt (written and never read: deleted) + e_pt + fpos (the global
+# solver's, which the one reserve of the problem brings; fpos is also where the free positions moved from the local result block) = 26
+# in BaProblem, and S and the result block in BaBufs.  The observation edits left BaBufs for a feature of their own (map_obs.hip) that
+# no step here calls.  So every count from the bundle adjustment on is one higher.
+FEATURE_FILLS = [18, 30, 41, 69, 86, 95, 103, 121]
 
 
 def test_every_map_feature_joins_the_poison_fill():

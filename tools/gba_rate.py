@@ -12,7 +12,7 @@ back-substitution), iterations per step, the wall time; then one call of one ste
 iteration launches returned at their first read (the host looks every 32 iterations); the bytes one iteration has to move (every array
 once per pass, the gathers per edge) against gba_steps per iteration.  --local: on an 18-keyframe map (16 free keyframes) one step of
 mo_map_bundle_adjust beside one step of this call.
-python tools/gba_rate.py   (one MI355X; VSLAM_AMD_LIB names another build of the library: tools/build_defs.sh gba_store_j "-DGBA_STORE_J=1")
+python tools/gba_rate.py   (one MI355X; VSLAM_AMD_LIB names another build of the library)
 """
 import argparse
 import os
@@ -45,13 +45,12 @@ def timed(ctx, call):
     return info, dict(ctx.stage_times()), wall
 
 
-def iteration_bytes(n_points, n_edges, n_free, stored):
+def iteration_bytes(n_points, n_edges, n_free):
     """what one iteration has to move: pass (a) per edge its position, keypoint and information (20 B) and the 48 B of p it gathers, per
     point X, V^-1, the held flag and q (97 B); pass (b) per edge its list entry, point, position, keypoint and information (28 B) and the
-    X and q it gathers (48 B), per keyframe H_kk, p, S p and the partial dot (392 B); the update 6 vectors of 6 n_free.  A stored build
-    reads 152 B per edge and pass instead of keypoint, information, X and pose."""
-    a = n_edges * ((4 + 152 + 48) if stored else (20 + 48)) + n_points * ((48 + 1 + 24) if stored else 97)
-    b = n_edges * ((8 + 152 + 24) if stored else (28 + 48)) + n_free * 392
+    X and q it gathers (48 B), per keyframe H_kk, p, S p and the partial dot (392 B); the update 6 vectors of 6 n_free."""
+    a = n_edges * (20 + 48) + n_points * 97
+    b = n_edges * (28 + 48) + n_free * 392
     return a + b + 6 * 48 * n_free
 
 
@@ -64,10 +63,9 @@ def main():
     ap.add_argument("--max-cg", type=int, default=200)
     ap.add_argument("--local", action="store_true")
     args = ap.parse_args()
-    stored = "store" in os.path.basename(os.environ.get("VSLAM_AMD_LIB", ""))
     ctx = V.Context(device=0, max_w=640, max_h=480, max_batch=1)
     ctx.set_host_timing(True)
-    print("library: %s (%s Jacobians)" % (V.LIB_PATH, "stored" if stored else "recomputed"), flush=True)
+    print("library: %s" % V.LIB_PATH, flush=True)
     m = build(ctx, 18, 36000)                                   # (loads the kernels: every timed call below is warm)
     m.global_bundle_adjust(fixed=[0, 1], max_steps=2)
     m.bundle_adjust(window=16, max_steps=(1, 0))
@@ -92,7 +90,7 @@ def main():
                 info, st, wall = timed(ctx, lambda: m.global_bundle_adjust(max_steps=args.max_steps, max_cg=args.max_cg))
                 steps, its = max(info["steps"], 1), max(info["cg_iters"], 1)
                 dev = sum(st.values())
-                by = iteration_bytes(info["n_points"], info["n_edges"], info["n_free"], stored)
+                by = iteration_bytes(info["n_points"], info["n_edges"], info["n_free"])
                 print("keyframes %4d points %7d call %d: free %d points %d edges %d | device %.3f ms (prep %.3f steps %.3f write %.3f) wall %.3f ms | steps %d accepted %d "
                       "iterations %d (%.1f per step) | %.3f ms per step, %.1f us per iteration | %.2f MB per iteration -> %.1f GB/s | cost %.6g -> %.6g"
                       % (n_kf, n_pts, call, info["n_free"], info["n_points"], info["n_edges"], dev, st.get("gba_prep", 0.0), st.get("gba_steps", 0.0),

@@ -1,4 +1,5 @@
-// Local bundle adjustment, the pieces shared by the kernels (map_ba.hip) and the CPU test of them (tests/native/ba_check.cpp): the
+// Bundle adjustment, the arithmetic shared by the kernels (ba_problem.h: the passes both solvers run; map_ba.hip: the local solver;
+// map_gba.hip with gba.h: the global one) and the CPU test of it (tests/native/ba_check.cpp): the
 // reprojection residual and its Jacobians, the per-edge terms of the normal equations, the 3x3 SPD inverse of a point block, the
 // Schur-complement terms of one point, the dense Cholesky solve of the reduced camera system, back-substitution, the pose update.
 // Everything is f64; built with -ffp-contract=off on both sides, so a host build computes what the device computes.

@@ -1,8 +1,9 @@
-// Global bundle adjustment, the pieces beyond ba.h shared by the kernels (map_gba.hip) and the CPU test of them
+// Global bundle adjustment, the pieces beyond ba.h shared by the solver's own kernels (map_gba.hip) and the CPU test of them
 // (tests/native/gba_check.cpp): the two halves of the matrix-free Schur operator S p = H p - W V^-1 W^T p, the block-Jacobi
 // preconditioner block of one keyframe and its 6x6 factor, and the scalar decisions of the preconditioned conjugate gradient.
-// Residual, Jacobians, weights, the point block, its inverse and the back-substitution are ba.h's, unchanged.  Everything is f64; built
-// with -ffp-contract=off on both sides.
+// Residual, Jacobians, weights, the point block, its inverse and the back-substitution are ba.h's; the kernels that linearise a point,
+// back-substitute, classify and write are ba_problem.h's, the ones the local solver runs.  Everything is f64; built with
+// -ffp-contract=off on both sides.
 #pragma once
 #include "ba.h"
 

@@ -1,20 +1,22 @@
 // map_gba.hip -- global bundle adjustment on the device map (mo_map_global_ba in include/vslam_amd.h: ORB-SLAM2's
 // Optimizer::GlobalBundleAdjustemnt, monocular): every keyframe that is not held fixed and every point with two observations,
-// Levenberg-Marquardt with the points eliminated, the reduced camera system never formed.  ba.h holds the arithmetic of an edge and of a
-// point block (unchanged: map_ba.hip computes what it computed), gba.h the matrix-free operator, the preconditioner block and the
-// scalar decisions of the conjugate gradient; tests/native/gba_check.cpp checks gba.h on the host against ba.h's dense Schur terms.
+// Levenberg-Marquardt with the points eliminated, the reduced camera system never formed.  The problem, the passes over its points and
+// the host code around the optional outputs are ba_problem.h's, shared with the local solver (map_ba.hip); ba.h holds the arithmetic of
+// an edge and of a point block, gba.h the matrix-free operator, the preconditioner block and the scalar decisions of the conjugate
+// gradient; tests/native/gba_check.cpp checks gba.h on the host against ba.h's dense Schur terms.  Here are the per-keyframe edge lists,
+// the conjugate-gradient solve and the accept rule.
 //
 // Chain (every decision - the gauge, the end of a solve, accept / reject, the end - is a flag in GbaRes that the later kernels read first;
-// the host waits on that block after the set-up, between steps and between chunks of GBA_CG_CHUNK iterations, only to stop enqueuing):
+// the host waits on that block after the set-up, between steps and between chunks of GBA_CG_CHUNK iterations, only to stop enqueuing;
+// [shared]: a kernel of ba_problem.h, instantiated without the e_inl mask and with the Huber width chi2 throughout):
 //   k_gba_mark     one thread per map point: its valid edges, problem-point flag, keyframes with edges and their edge counts (integer
 //                  atomics count)
 //   scans          rank of every problem point, first edge of every problem point, first list entry of every position
-//   k_gba_setup    one block: free / fixed / outside per position, the free index, the gauge flag
-//   k_gba_edges    one thread per map point: its edges in CSR order into the compact edge arrays; every edge appended to its position's
-//                  list (integer atomic: the order of arrival)
+//   k_gba_setup    one block: free / fixed / outside per position, the free index and its inverse fpos, the gauge flag
+//   k_ba_edges     [shared, with the lists] the compact edge arrays; every edge appended to its position's list
 //   k_gba_sort     one workgroup per position: its list ranked into ascending edge order
 //   per Levenberg-Marquardt step:
-//     k_gba_lin      one thread per problem point: V (damped, inverted), g_p, its current cost
+//     k_ba_lin       [shared] V (damped, inverted), g_p, the current cost per point
 //     k_gba_diag     one wavefront per free keyframe: H_kk, b_k and the preconditioner block over its edges (strided over the lanes, each
 //                    lane in order, wave_sum); lane 0 damps and factors, and starts the solve: x = 0, r = b, z = M^-1 r, p = z
 //     k_gba_cg_init  one workgroup: r0.z0
@@ -23,30 +25,25 @@
 //       k_gba_mv_kf      one workgroup per free keyframe: y_k = H_kk p_k - sum_e W_e q_pt(e), and p_k . y_k
 //       k_gba_cg_update  one workgroup: p.Sp, alpha, x, r, z, r.z, beta, p; the end of the solve
 //     k_gba_trial    one workgroup: the trial poses, the largest pose update
-//     k_gba_back     one thread per problem point: back-substitution, trial position, trial cost
+//     k_ba_back      [shared] back-substitution, trial position, trial cost
 //     k_gba_accept   one workgroup: cost sums, accept / reject, lambda, the end flag; an accepted step becomes the state
-//   k_gba_final    one thread per problem point: every edge classified, the final robust cost; k_gba_reduce sums
-//   k_gba_write    xyz of the problem points and kP of the free keyframes when a step was accepted; the optional outputs
+//   k_ba_cost      [shared] every edge classified, the final robust cost; k_ba_reduce [shared] sums
+//   k_ba_write     [shared] xyz of the problem points and kP of the free keyframes when a step was accepted; the optional outputs
 // The Jacobians of an edge (J_c 2x6, J_p 2x3, the weight) are recomputed in every pass from pose, point and keypoint, not stored:
-// profiles/gba_rate.txt has the measurement.  No floating-point atomics: sums are per-thread in edge order, then wave_sum, then the
-// waves in order.  -ffp-contract=off (Makefile): gba.h and ba.h round on the device as in the host build of the test.
+// profiles/gba_rate.txt has the measurement of the stored variant, which NOTES.md records as removed.  No floating-point atomics: sums
+// are per-thread in edge order, then wave_sum, then the waves in order.  -ffp-contract=off (Makefile): gba.h and ba.h round on the device
+// as in the host build of the test.
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "common.h"
-#include "map_store.h"
+#include "ba_problem.h"
 #include "gba.h"
 
-#define GBA_BLOCK 256
-#define GBA_THREADS 1024
+#define GBA_BLOCK BA_BLOCK
+#define GBA_THREADS BA_THREADS
 #define GBA_CG_CHUNK 32       // conjugate-gradient iterations enqueued between two looks at the result block
-#ifndef GBA_STORE_J
-#define GBA_STORE_J 0         // diagnostic build (tools/build_defs.sh): the passes of the solve read J_c, J_p and the weight of an edge, stored once per step
-#endif
-#define GBA_KF_OUT (-2)       // kf_fidx: the position has no edge to a problem point
-#define GBA_KF_FIXED (-1)     // kf_fidx: fixed position (>= 0: index among the free ones)
 
 struct GbaPrm {
     double K[9], sf, chi2, step_tol, cg_tol2;
@@ -60,60 +57,33 @@ struct GbaRes {
     int32_t run, err, done;            // the problem runs; no fixed position takes part; the optimisation has ended
     int32_t cg_done, cg_it, reject;    // of the step in flight
 };
+__device__ __forceinline__ bool gba_active(const GbaRes* res) { return res->run && !res->done; }
+__device__ __forceinline__ bool gba_cg_active(const GbaRes* res) { return res->run && !res->done && !res->cg_done; }
+// what the shared kernels ask (ba_problem.h)
+__device__ __forceinline__ bool ba_live(const GbaRes* res, int) { return gba_active(res); }
+__device__ __forceinline__ bool ba_has_trial(const GbaRes* res) { return !res->reject; }
+__device__ __forceinline__ bool ba_step_accepted(const GbaRes* res) { return res->accepted > 0; }
+__device__ __forceinline__ bool ba_xyz_always(const GbaRes*) { return false; }
+__device__ __forceinline__ void ba_store_cost(GbaRes* res, int, double cost, int n_inliers) {
+    if (res->steps == 0) res->cost[0] = cost;
+    res->cost[1] = cost; res->n_inliers = n_inliers;
+}
 
 struct GbaBufs : MapFeature {
-    // per map point
-    DevBuf<int32_t> loc, ecnt, lrank, ebase;
-    DevBuf<double> pout;                                         // [point][3] the optional f64 output
-    // per problem point (by rank)
-    DevBuf<int32_t> eoff, pn; DevBuf<uint8_t> pfix;
-    DevBuf<double> X, Xt, Vi, gp, q, pc, pt, pu;
-    // per edge (compact, CSR order of the problem points)
-    DevBuf<int32_t> e_kf, e_obs, e_pt; DevBuf<float> e_xy; DevBuf<double> e_info; DevBuf<uint8_t> e_inl;
-    DevBuf<uint8_t> einl;                                        // [observation] 0 / 1 / 2
+    DevBuf<double> q;                                            // [problem point][3] V^-1 W^T p
     DevBuf<int32_t> karr, klist;                                 // [edge] the positions' lists in order of arrival, in ascending edge order
-    DevBuf<double> eJ;                                           // [edge][19] J_c, J_p, weight (NaN: the edge contributes nothing); GBA_STORE_J builds only
     // per keyframe position
     DevBuf<uint8_t> fixed;
-    DevBuf<int32_t> kf_edge, kcnt, kbase, kfill, kf_fidx, fpos; DevBuf<double> poseC, poseT;
+    DevBuf<int32_t> kcnt, kbase, kfill;
     // per free keyframe
     DevBuf<double> Hd, L, x, r, z, p, Sp, pdot; DevBuf<uint8_t> kfix;
     ResBlock<GbaRes> res;
     // all of it is scratch: every call's chain writes what it reads
     template <class F> void each_scratch(F f) {
-        f(loc); f(ecnt); f(lrank); f(ebase); f(pout); f(eoff); f(pn); f(pfix); f(X); f(Xt); f(Vi); f(gp); f(q); f(pc); f(pt); f(pu);
-        f(e_kf); f(e_obs); f(e_pt); f(e_xy); f(e_info); f(e_inl); f(einl); f(karr); f(klist); f(eJ); f(fixed); f(kf_edge); f(kcnt); f(kbase); f(kfill);
-        f(kf_fidx); f(fpos); f(poseC); f(poseT); f(Hd); f(L); f(x); f(r); f(z); f(p); f(Sp); f(pdot); f(kfix); f(res);
+        f(q); f(karr); f(klist); f(fixed); f(kcnt); f(kbase); f(kfill); f(Hd); f(L); f(x); f(r); f(z); f(p); f(Sp); f(pdot); f(kfix); f(res);
     }
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
-
-// the edges as the kernels read them (by value)
-struct GbaEdges {
-    const int32_t* eoff; const int32_t* e_kf; const int32_t* e_pt; const float* e_xy; const double* e_info; const double* eJ;
-};
-
-// fixed-order sums and maxima of a workgroup: wave_sum, then the waves in order; every thread receives the result
-__device__ __forceinline__ double gba_block_sum(double v, double* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wave_sum(v);
-    if (lane == 0) lds[wv] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < nw; w++) s += lds[w];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ double gba_block_max(double v, double* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int d = 32; d; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
-    if (lane == 0) lds[wv] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < nw; w++) s = fmax(s, lds[w]);
-    __syncthreads();
-    return s;
-}
 
 __global__ void k_gba_init(GbaRes* __restrict__ res) {
     if (threadIdx.x) return;
@@ -143,38 +113,14 @@ __global__ __launch_bounds__(GBA_BLOCK) void k_gba_setup(GbaPrm prm, const uint8
     if (threadIdx.x) return;
     int nfixed = 0, nfree = 0;
     for (int pos = 0; pos < prm.n_kf; pos++) {
-        if (!kf_edge[pos]) { kf_fidx[pos] = GBA_KF_OUT; continue; }
-        if (fixed[pos]) { kf_fidx[pos] = GBA_KF_FIXED; nfixed++; }
+        if (!kf_edge[pos]) { kf_fidx[pos] = BA_KF_OUT; continue; }
+        if (fixed[pos]) { kf_fidx[pos] = BA_KF_FIXED; nfixed++; }
         else { kf_fidx[pos] = nfree; fpos[nfree++] = pos; }
     }
     kbase[prm.n_kf] = res->n_edges;
     res->n_free = nfree; res->n_fixed = nfixed;
     res->err = res->n_points > 0 && nfixed == 0;
     res->run = nfree > 0 && nfixed > 0 && res->n_points > 0;
-}
-
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_edges(MapView v, const mo_keypoint* __restrict__ kkps, double sf, const int32_t* __restrict__ loc,
-                                                          const int32_t* __restrict__ lrank, const int32_t* __restrict__ ebase,
-                                                          int32_t* __restrict__ eoff, double* __restrict__ X, int32_t* __restrict__ e_kf,
-                                                          int32_t* __restrict__ e_obs, int32_t* __restrict__ e_pt, float* __restrict__ e_xy,
-                                                          double* __restrict__ e_info, const int32_t* __restrict__ kbase, int32_t* __restrict__ kfill,
-                                                          int32_t* __restrict__ karr, const GbaRes* __restrict__ res) {
-    if (!res->run) return;
-    const int i = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    if (i == 0) eoff[res->n_points] = res->n_edges;
-    if (i >= v.n_pts || !loc[i]) return;
-    const int r = lrank[i];
-    int e = ebase[i];
-    eoff[r] = e;
-    for (int k = 0; k < 3; k++) X[(size_t)r * 3 + k] = v.src.xyz[(size_t)i * 3 + k];
-    map_each_obs(v, i, [&](int o, int pos, int s, int kp) {
-        const mo_keypoint kq = kkps[(size_t)s * v.row + kp];
-        e_kf[e] = pos; e_obs[e] = o; e_pt[e] = r; e_xy[(size_t)e * 2] = kq.x; e_xy[(size_t)e * 2 + 1] = kq.y; e_info[e] = ba_info(sf, kq.octave);
-        const int at = atomicAdd(kfill + pos, 1);   // (k_gba_mark counted this very walk: at < kbase[pos + 1] - kbase[pos])
-        karr[kbase[pos] + at] = e;
-        e++;
-        return false;
-    });
 }
 
 // one workgroup per position: its list into ascending edge order (the edges are distinct: the rank of an edge is the number of smaller
@@ -200,83 +146,16 @@ __global__ __launch_bounds__(GBA_BLOCK) void k_gba_sort(const int32_t* __restric
     }
 }
 
-__device__ __forceinline__ bool gba_active(const GbaRes* res) { return res->run && !res->done; }
-__device__ __forceinline__ bool gba_cg_active(const GbaRes* res) { return res->run && !res->done && !res->cg_done; }
-
-// residual, weight and Jacobians of an edge at the current state (round 0 of the local solver); false when it contributes nothing
-__device__ __forceinline__ bool gba_edge_lin(const GbaPrm& prm, const double* T, const double* Xp, float x, float y, double info, double* er, double* w,
-                                             double* e2, double* Jc, double* Jp) {
-    double zc;
-    if (!ba_residual(prm.K, T, Xp, x, y, er, &zc)) return false;
-    *e2 = info * (er[0] * er[0] + er[1] * er[1]);
-    *w = info * ba_weight(*e2, prm.chi2);
-    return ba_jacobians(prm.K, T, Xp, Jc, Jp);
-}
-// ... of edge e of the compact arrays
-__device__ __forceinline__ bool gba_edge_at(const GbaPrm& prm, const GbaEdges& E, int e, const double* __restrict__ pose, const double* __restrict__ X,
+// residual, weight and Jacobians of edge e of the compact arrays at the current state; false when it contributes nothing
+__device__ __forceinline__ bool gba_edge_at(const GbaPrm& prm, const BaEdges& E, int e, const double* __restrict__ pose, const double* __restrict__ X,
                                             double* er, double* w, double* e2, double* Jc, double* Jp) {
     const size_t r = (size_t)E.e_pt[e];
     const double Xp[3] = {X[r * 3], X[r * 3 + 1], X[r * 3 + 2]};
-    return gba_edge_lin(prm, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, w, e2, Jc, Jp);
-}
-
-// J_c, J_p and the weight of edge e as a pass of the solve takes them: recomputed, or read where a GBA_STORE_J build stored them
-__device__ __forceinline__ bool gba_edge_J(const GbaPrm& prm, const GbaEdges& E, int e, const double* __restrict__ pose, const double* __restrict__ X,
-                                           double* w, double* Jc, double* Jp) {
-#if GBA_STORE_J
-    const double* s = E.eJ + (size_t)e * 19;
-    *w = s[18];
-    if (!(*w == *w)) return false;
-    for (int k = 0; k < 12; k++) Jc[k] = s[k];
-    for (int k = 0; k < 6; k++) Jp[k] = s[12 + k];
-    return true;
-#else
-    double er[2], e2;
-    return gba_edge_at(prm, E, e, pose, X, er, w, &e2, Jc, Jp);
-#endif
-}
-
-#if GBA_STORE_J
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_jac(GbaPrm prm, GbaEdges E, const double* __restrict__ X, const double* __restrict__ pose,
-                                                        double* __restrict__ eJ, const GbaRes* __restrict__ res) {
-    if (!gba_active(res)) return;
-    const int e = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    if (e >= res->n_edges) return;
-    double er[2], w, e2, Jc[12], Jp[6];
-    const bool ok = gba_edge_at(prm, E, e, pose, X, er, &w, &e2, Jc, Jp);
-    double* s = eJ + (size_t)e * 19;
-    for (int k = 0; k < 12; k++) s[k] = ok ? Jc[k] : 0.0;
-    for (int k = 0; k < 6; k++) s[12 + k] = ok ? Jp[k] : 0.0;
-    s[18] = ok ? w : __longlong_as_double(0x7ff8000000000000ll);
-}
-#endif
-
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_lin(GbaPrm prm, GbaEdges E, const double* __restrict__ X, const double* __restrict__ pose,
-                                                        double* __restrict__ Vi, double* __restrict__ gp, uint8_t* __restrict__ pfix, double* __restrict__ pc,
-                                                        const GbaRes* __restrict__ res) {
-    if (!gba_active(res)) return;
-    const int r = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    if (r >= res->n_points) return;
-    const double damp = 1.0 + res->lambda;
-    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
-    double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, cost = 0.0;
-    for (int e = E.eoff[r]; e < E.eoff[r + 1]; e++) {
-        double er[2], w, e2, Jc[12], Jp[6];
-        if (!gba_edge_lin(prm, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, &w, &e2, Jc, Jp)) continue;
-        cost += ba_rho(e2, prm.chi2);
-        ba_point_terms(Jp, w, er, V, g);
-    }
-    V[0] *= damp; V[3] *= damp; V[5] *= damp;
-    double inv[6] = {0, 0, 0, 0, 0, 0};
-    const bool ok = ba_inv3(V, inv);
-    for (int k = 0; k < 6; k++) Vi[(size_t)r * 6 + k] = inv[k];
-    for (int k = 0; k < 3; k++) gp[(size_t)r * 3 + k] = g[k];
-    pfix[r] = !ok;
-    pc[r] = cost;
+    return ba_edge_lin(prm, prm.chi2, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, w, e2, Jc, Jp);
 }
 
 // one wavefront per free keyframe: a [0, 36) H_kk, [36, 42) b_k, [42, 78) - sum_e W_e V^-1 W_e^T; lane l takes the list entries l, l + 64, ...
-__global__ __launch_bounds__(64) void k_gba_diag(GbaPrm prm, GbaEdges E, const int32_t* __restrict__ kbase, const int32_t* __restrict__ klist,
+__global__ __launch_bounds__(64) void k_gba_diag(GbaPrm prm, BaEdges E, const int32_t* __restrict__ kbase, const int32_t* __restrict__ klist,
                                                   const int32_t* __restrict__ fpos, const double* __restrict__ X, const double* __restrict__ pose,
                                                   const double* __restrict__ Vi, const double* __restrict__ gp, const uint8_t* __restrict__ pfix,
                                                   double* __restrict__ Hd, double* __restrict__ L, uint8_t* __restrict__ kfix,
@@ -330,7 +209,7 @@ __device__ __forceinline__ double gba_dot6(int nf, const double* __restrict__ a,
     double s = 0.0;
     for (int f = threadIdx.x; f < nf; f += GBA_THREADS)
         for (int k = 0; k < 6; k++) s += a[(size_t)f * 6 + k] * b[(size_t)f * 6 + k];
-    return gba_block_sum(s, lds);
+    return block_sum(s, lds);
 }
 
 __global__ __launch_bounds__(GBA_THREADS) void k_gba_cg_init(const double* __restrict__ r, const double* __restrict__ z, GbaRes* __restrict__ res) {
@@ -344,7 +223,7 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_cg_init(const double* __res
 }
 
 // pass (a): q = V^-1 sum_e W_e^T p_kf(e) over the point's edges at free keyframes, in edge order; 0 at a point held for the step
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_mv_pt(GbaPrm prm, GbaEdges E, const int32_t* __restrict__ kf_fidx, const double* __restrict__ X,
+__global__ __launch_bounds__(GBA_BLOCK) void k_gba_mv_pt(GbaPrm prm, BaEdges E, const int32_t* __restrict__ kf_fidx, const double* __restrict__ X,
                                                           const double* __restrict__ pose, const double* __restrict__ Vi, const uint8_t* __restrict__ pfix,
                                                           const double* __restrict__ p, double* __restrict__ q, const GbaRes* __restrict__ res) {
     if (!gba_cg_active(res)) return;
@@ -352,19 +231,13 @@ __global__ __launch_bounds__(GBA_BLOCK) void k_gba_mv_pt(GbaPrm prm, GbaEdges E,
     if (rk >= res->n_points) return;
     double t[3] = {0, 0, 0}, qq[3] = {0, 0, 0};
     if (!pfix[rk]) {
-#if !GBA_STORE_J
         const double Xp[3] = {X[(size_t)rk * 3], X[(size_t)rk * 3 + 1], X[(size_t)rk * 3 + 2]};
-#endif
         for (int e = E.eoff[rk]; e < E.eoff[rk + 1]; e++) {
             const int f = kf_fidx[E.e_kf[e]];
             if (f < 0) continue;
             double w, Jc[12], Jp[6], pk[6];
-#if GBA_STORE_J
-            if (!gba_edge_J(prm, E, e, pose, X, &w, Jc, Jp)) continue;
-#else
             double er[2], e2;
-            if (!gba_edge_lin(prm, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, &w, &e2, Jc, Jp)) continue;
-#endif
+            if (!ba_edge_lin(prm, prm.chi2, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, &w, &e2, Jc, Jp)) continue;
             for (int k = 0; k < 6; k++) pk[k] = p[(size_t)f * 6 + k];
             gba_wt_p(Jc, Jp, w, pk, t);
         }
@@ -377,7 +250,7 @@ __global__ __launch_bounds__(GBA_BLOCK) void k_gba_mv_pt(GbaPrm prm, GbaEdges E,
 
 // pass (b): one workgroup per free keyframe: y_k = H_kk p_k - sum_e W_e q_pt(e); thread t takes the list entries t, t + blockDim.x, ...
 // (256 threads, or 1024 where the free keyframes are few and their lists long: gba_mv_threads)
-__global__ __launch_bounds__(GBA_THREADS) void k_gba_mv_kf(GbaPrm prm, GbaEdges E, const int32_t* __restrict__ kbase, const int32_t* __restrict__ klist,
+__global__ __launch_bounds__(GBA_THREADS) void k_gba_mv_kf(GbaPrm prm, BaEdges E, const int32_t* __restrict__ kbase, const int32_t* __restrict__ klist,
                                                           const int32_t* __restrict__ fpos, const double* __restrict__ X, const double* __restrict__ pose,
                                                           const uint8_t* __restrict__ pfix, const double* __restrict__ Hd, const uint8_t* __restrict__ kfix,
                                                           const double* __restrict__ p, const double* __restrict__ q, double* __restrict__ Sp,
@@ -398,8 +271,8 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_mv_kf(GbaPrm prm, GbaEdges 
         const int e = klist[c];
         const size_t pr = (size_t)E.e_pt[e];
         if (pfix[pr]) continue;
-        double w, Jc[12], Jp[6];
-        if (!gba_edge_J(prm, E, e, pose, X, &w, Jc, Jp)) continue;
+        double er[2], w, e2, Jc[12], Jp[6];
+        if (!gba_edge_at(prm, E, e, pose, X, er, &w, &e2, Jc, Jp)) continue;
         const double qq[3] = {q[pr * 3], q[pr * 3 + 1], q[pr * 3 + 2]};
         gba_w_q(Jc, Jp, w, qq, a);
     }
@@ -435,7 +308,7 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_cg_update(GbaPrm prm, const
     const int it = res->cg_it;
     double s = 0.0;
     for (int f = tid; f < nf; f += GBA_THREADS) s += pdot[f];
-    const double pSp = gba_block_sum(s, red);
+    const double pSp = block_sum(s, red);
     double alpha;
     if (!gba_cg_alpha(rz, pSp, &alpha)) {
         if (tid == 0) { res->cg_done = 1; res->reject = it == 0; }
@@ -453,7 +326,7 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_cg_update(GbaPrm prm, const
         if (!kfix[f]) gba_solve6(L + (size_t)f * GBA_TRI_N, r6, z6);
         for (int k = 0; k < 6; k++) { z[(size_t)f * 6 + k] = z6[k]; s += r6[k] * z6[k]; }
     }
-    const double rzn = gba_block_sum(s, red);
+    const double rzn = block_sum(s, red);
     double beta = 0.0;
     const bool go = gba_cg_continue(rzn, prm.cg_tol2, rz0, rz, &beta);
     if (go)
@@ -481,45 +354,8 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_trial(const int32_t* __rest
         ba_pose_update(d, T, T2);
         for (int k = 0; k < 12; k++) poseT[(size_t)pos * 12 + k] = T2[k];
     }
-    mu = gba_block_max(mu, red);
+    mu = block_max(mu, red);
     if (threadIdx.x == 0) res->upd_c = mu;
-}
-
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_back(GbaPrm prm, GbaEdges E, const int32_t* __restrict__ kf_fidx, const double* __restrict__ X,
-                                                         const double* __restrict__ poseC, const double* __restrict__ poseT, const double* __restrict__ Vi,
-                                                         const double* __restrict__ gp, const uint8_t* __restrict__ pfix, const double* __restrict__ dc,
-                                                         double* __restrict__ Xt, double* __restrict__ pt, double* __restrict__ pu,
-                                                         const GbaRes* __restrict__ res) {
-    if (!gba_active(res) || res->reject) return;
-    const int r = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    if (r >= res->n_points) return;
-    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
-    const int e0 = E.eoff[r], e1 = E.eoff[r + 1];
-    double dp[3] = {0, 0, 0};
-    if (!pfix[r]) {
-        double g[3], inv[6];
-        for (int k = 0; k < 3; k++) g[k] = gp[(size_t)r * 3 + k];
-        for (int k = 0; k < 6; k++) inv[k] = Vi[(size_t)r * 6 + k];
-        for (int e = e0; e < e1; e++) {
-            const int f = kf_fidx[E.e_kf[e]];
-            if (f < 0) continue;
-            double er[2], w, e2, Jc[12], Jp[6], d6[6];
-            if (!gba_edge_lin(prm, poseC + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], E.e_info[e], er, &w, &e2, Jc, Jp)) continue;
-            for (int k = 0; k < 6; k++) d6[k] = dc[(size_t)f * 6 + k];
-            ba_back_edge(Jc, Jp, w, d6, g);
-        }
-        ba_sym3_mul(inv, g, dp);
-    }
-    const double Xn[3] = {Xp[0] + dp[0], Xp[1] + dp[1], Xp[2] + dp[2]};
-    double cost = 0.0;
-    for (int e = e0; e < e1; e++) {
-        double er[2], zc;
-        if (!ba_residual(prm.K, poseT + (size_t)E.e_kf[e] * 12, Xn, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], er, &zc)) continue;
-        cost += ba_rho(E.e_info[e] * (er[0] * er[0] + er[1] * er[1]), prm.chi2);
-    }
-    for (int k = 0; k < 3; k++) Xt[(size_t)r * 3 + k] = Xn[k];
-    pt[r] = cost;
-    pu[r] = fmax(fabs(dp[0]), fmax(fabs(dp[1]), fabs(dp[2])));
 }
 
 // one workgroup: current and trial cost, the largest update; accept (the trial becomes the state, lambda / 10) or reject (lambda * 10);
@@ -538,9 +374,9 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_accept(GbaPrm prm, const in
         c0 += pc[r];
         if (!rej) { c1 += pt[r]; mu = fmax(mu, pu[r]); }
     }
-    c0 = gba_block_sum(c0, lds);
-    c1 = gba_block_sum(c1, lds);
-    mu = gba_block_max(mu, lds);
+    c0 = block_sum(c0, lds);
+    c1 = block_sum(c1, lds);
+    mu = block_max(mu, lds);
     if (tid == 0) {
         const bool ok = !rej && c1 < c0;
         acc = ok;
@@ -555,84 +391,7 @@ __global__ __launch_bounds__(GBA_THREADS) void k_gba_accept(GbaPrm prm, const in
         if ((!rej && upd < prm.step_tol) || lam > 1e8) res->done = 1;
     }
     __syncthreads();
-    const int nf = res->n_free;
-    if (acc) {
-        for (int k = tid; k < n * 3; k += GBA_THREADS) X[k] = Xt[k];
-        for (int k = tid; k < nf * 12; k += GBA_THREADS) { const size_t o = (size_t)fpos[k / 12] * 12 + k % 12; poseC[o] = poseT[o]; }
-    } else {
-        for (int k = tid; k < nf * 12; k += GBA_THREADS) { const size_t o = (size_t)fpos[k / 12] * 12 + k % 12; poseT[o] = poseC[o]; }
-    }
-}
-
-// every edge classified at the final state, the robust cost of every edge
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_final(GbaPrm prm, GbaEdges E, const double* __restrict__ X, const double* __restrict__ pose,
-                                                          uint8_t* __restrict__ e_inl, double* __restrict__ pc, int32_t* __restrict__ pn,
-                                                          const GbaRes* __restrict__ res) {
-    if (!res->run) return;
-    const int r = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    if (r >= res->n_points) return;
-    const double Xp[3] = {X[(size_t)r * 3], X[(size_t)r * 3 + 1], X[(size_t)r * 3 + 2]};
-    double cost = 0.0;
-    int n = 0;
-    for (int e = E.eoff[r]; e < E.eoff[r + 1]; e++) {
-        double er[2], zc;
-        const bool fin = ba_residual(prm.K, pose + (size_t)E.e_kf[e] * 12, Xp, E.e_xy[(size_t)e * 2], E.e_xy[(size_t)e * 2 + 1], er, &zc);
-        const double e2 = fin ? E.e_info[e] * (er[0] * er[0] + er[1] * er[1]) : 0.0;
-        const bool in = fin && zc > 0.0 && e2 <= prm.chi2;
-        e_inl[e] = in;
-        n += in;
-        if (fin) cost += ba_rho(e2, prm.chi2);
-    }
-    pc[r] = cost;
-    pn[r] = n;
-}
-
-__global__ __launch_bounds__(GBA_THREADS) void k_gba_reduce(const double* __restrict__ pc, const int32_t* __restrict__ pn, GbaRes* __restrict__ res) {
-    __shared__ double lds[GBA_THREADS / 64];
-    __shared__ int cnt;
-    if (!res->run) return;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const int n = res->n_points;
-    double s = 0.0;
-    int c = 0;
-    for (int r = threadIdx.x; r < n; r += GBA_THREADS) { s += pc[r]; c += pn[r]; }
-    s = gba_block_sum(s, lds);
-    c = wave_sum_int(c);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&cnt, c);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (res->steps == 0) res->cost[0] = s;
-        res->cost[1] = s; res->n_inliers = cnt;
-    }
-}
-
-// the results into the map when a step was accepted: xyz of the problem points, kP = K [R | t] of the free keyframes; the optional outputs
-__global__ __launch_bounds__(GBA_BLOCK) void k_gba_write(GbaPrm prm, int n_pts, int n_obs_edges, const int32_t* __restrict__ loc, const int32_t* __restrict__ lrank,
-                                                          const double* __restrict__ X, float* __restrict__ xyz, double* __restrict__ pout,
-                                                          const int32_t* __restrict__ e_obs, const uint8_t* __restrict__ e_inl, uint8_t* __restrict__ einl,
-                                                          const int32_t* __restrict__ pos_slot, const int32_t* __restrict__ fpos, const double* __restrict__ poseC,
-                                                          double* __restrict__ kP, const GbaRes* __restrict__ res) {
-    const int i = blockIdx.x * GBA_BLOCK + threadIdx.x;
-    const bool run = res->run, wr = run && res->accepted > 0;
-    if (i < n_pts) {
-        const bool prob = run && loc[i];
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
-        for (int k = 0; k < 3; k++) {
-            const double v = prob ? X[(size_t)lrank[i] * 3 + k] : nan;
-            if (pout) pout[(size_t)i * 3 + k] = v;
-            if (prob && wr) xyz[(size_t)i * 3 + k] = (float)v;
-        }
-    }
-    if (!run) return;
-    if (i < res->n_edges && i < n_obs_edges) einl[e_obs[i]] = e_inl[i] ? 1 : 2;
-    if (i < res->n_free && wr) {
-        const int pos = fpos[i];
-        double R[9], t[3], P[12];
-        pose_split(poseC + (size_t)pos * 12, R, t);
-        pnp_projection(prm.K, R, t, P);
-        for (int k = 0; k < 12; k++) kP[(size_t)pos_slot[pos] * 12 + k] = P[k];
-    }
+    ba_commit(acc, n, res->n_free, fpos, X, Xt, poseC, poseT);
 }
 
 // the workgroup of k_gba_mv_kf: 1024 threads where a free keyframe's list averages 4096 edges or more (a function of the map alone)
@@ -650,65 +409,55 @@ extern "C" int mo_map_global_ba(mo_map* m, const double K[9], const double* pose
     mo_ctx* c = m->c;
     if (!K || !prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
     const int n_kf = (int)m->pos_slot.size();
-    if (n_kf > 0 && !poses) return mo_fail(c, MO_ERR_ARG, "poses is NULL");
-    if (!(prm->scale_factor > 0.0) || !std::isfinite(prm->scale_factor)) return mo_fail(c, MO_ERR_ARG, "scale_factor must be finite and > 0");
-    if (!(prm->chi2 >= 0.0) || !std::isfinite(prm->chi2)) return mo_fail(c, MO_ERR_ARG, "chi2 must be finite and >= 0");
     if (prm->max_steps < 0 || prm->max_steps > 100) return mo_fail(c, MO_ERR_ARG, "max_steps must be in 0 .. 100");
     if (prm->max_cg < 1) return mo_fail(c, MO_ERR_ARG, "max_cg must be >= 1");
     if (!(prm->cg_tol >= 0.0) || !std::isfinite(prm->cg_tol) || !(prm->step_tol >= 0.0) || !std::isfinite(prm->step_tol))
         return mo_fail(c, MO_ERR_ARG, "cg_tol and step_tol must be finite and >= 0");
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(K[i])) return mo_fail(c, MO_ERR_ARG, "K must be finite");
-    for (size_t i = 0; i < (size_t)n_kf * 12; i++)
-        if (!std::isfinite(poses[i])) return mo_fail(c, MO_ERR_ARG, "poses must be finite");
+    int rc;
+    if ((rc = ba_check_common(c, K, poses, n_kf, prm->scale_factor, prm->chi2))) return rc;
     MAP_ENTER(m);
     HostClock clk(c);
     out->cost[0] = out->cost[1] = 0.0; out->lambda = 0.0;
     out->n_free = out->n_fixed = out->n_points = out->n_edges = out->n_inliers = out->steps = out->accepted = out->cg_iters = out->ok = 0;
     const size_t np = (size_t)m->n_pts, no = (size_t)m->n_obs, nk = (size_t)n_kf;
-    if (out->poses_out && n_kf) std::memcpy(out->poses_out, poses, nk * 96);
-    if (out->kf_state) for (int i = 0; i < n_kf; i++) out->kf_state[i] = 0;
-    if (out->edge_inlier && no) std::memset(out->edge_inlier, 0, no);
-    if (out->points_out) for (size_t i = 0; i < np * 3; i++) out->points_out[i] = NAN;
+    ba_clear_outputs(out, poses, nk, np, no);
     if (n_kf == 0 || np == 0 || no == 0 || prm->max_steps == 0) return MO_OK;   // nothing runs, not an error
-    int rc;
     if ((rc = map_int32_guard(m))) return rc;
     std::vector<uint8_t> fixed(nk, 0);
     if (prm->fixed) { for (size_t i = 0; i < nk; i++) fixed[i] = prm->fixed[i] != 0; }
     else fixed[0] = 1;
+    BaProblem& pb = map_feature<BaProblem>(m);
     GbaBufs& b = map_feature<GbaBufs>(m);
-    if ((rc = mo_reserve(c, b.loc, np, b.ecnt, np, b.lrank, np, b.ebase, np, b.eoff, np + 1, b.pn, np, b.pfix, np, b.X, np * 3, b.Xt, np * 3,
-                         b.Vi, np * 6, b.gp, np * 3, b.q, np * 3, b.pc, np, b.pt, np, b.pu, np, b.e_kf, no, b.e_obs, no, b.e_pt, no, b.e_xy, no * 2,
-                         b.e_info, no, b.e_inl, no, b.einl, no, b.karr, no, b.klist, no, b.eJ, GBA_STORE_J ? no * 19 : 1, b.fixed, nk, b.kf_edge, nk, b.kcnt, nk, b.kbase, nk + 1, b.kfill, nk,
-                         b.kf_fidx, nk, b.fpos, nk, b.poseC, nk * 12, b.poseT, nk * 12, b.Hd, nk * 36, b.L, nk * GBA_TRI_N, b.x, nk * 6,
-                         b.r, nk * 6, b.z, nk * 6, b.p, nk * 6, b.Sp, nk * 6, b.pdot, nk, b.kfix, nk, b.res)))
+    if ((rc = pb.reserve(c, np, no, nk))) return rc;
+    if ((rc = mo_reserve(c, b.q, np * 3, b.karr, no, b.klist, no, b.fixed, nk, b.kcnt, nk, b.kbase, nk + 1, b.kfill, nk, b.Hd, nk * 36, b.L, nk * GBA_TRI_N,
+                         b.x, nk * 6, b.r, nk * 6, b.z, nk * 6, b.p, nk * 6, b.Sp, nk * 6, b.pdot, nk, b.kfix, nk, b.res)))
         return rc;
-    if (out->points_out && (rc = mo_reserve(c, b.pout, np * 3))) return rc;
+    if (out->points_out && (rc = mo_reserve(c, pb.pout, np * 3))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
-    HIPCHK(c, hipMemcpyAsync(b.poseC, poses, nk * 96, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.poseT, b.poseC, nk * 96, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pb.poseC, poses, nk * 96, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pb.poseT, pb.poseC, nk * 96, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.fixed, fixed.data(), nk, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.kf_edge, 0, nk * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(pb.kf_edge, 0, nk * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(b.kcnt, 0, nk * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(b.kfill, 0, nk * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.einl, 0, no, c->stream));
+    HIPCHK(c, hipMemsetAsync(pb.einl, 0, no, c->stream));
     GbaPrm p;
     std::memset(&p, 0, sizeof(p));
     for (int i = 0; i < 9; i++) p.K[i] = K[i];
     p.sf = prm->scale_factor; p.chi2 = prm->chi2; p.step_tol = prm->step_tol; p.cg_tol2 = prm->cg_tol * prm->cg_tol; p.n_kf = n_kf;
     const MapView v = map_view(m);
-    const GbaEdges E{b.eoff, b.e_kf, b.e_pt, b.e_xy, b.e_info, b.eJ};
+    const BaEdges E = pb.edges();
     const unsigned mblocks = (unsigned)((np + GBA_BLOCK - 1) / GBA_BLOCK);
     hipLaunchKernelGGL(k_gba_init, dim3(1), dim3(64), 0, c->stream, b.res);
-    hipLaunchKernelGGL(k_gba_mark, dim3(mblocks), dim3(GBA_BLOCK), 0, c->stream, v, b.loc, b.ecnt, b.kf_edge, b.kcnt);
+    hipLaunchKernelGGL(k_gba_mark, dim3(mblocks), dim3(GBA_BLOCK), 0, c->stream, v, pb.loc, pb.ecnt, pb.kf_edge, b.kcnt);
     HIPCHK(c, hipGetLastError());
-    if ((rc = map_scan_excl(m, b.loc, b.lrank, (int)np, &b.res.p->n_points))) return rc;
-    if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, &b.res.p->n_edges))) return rc;
+    if ((rc = map_scan_excl(m, pb.loc, pb.lrank, (int)np, &b.res.p->n_points))) return rc;
+    if ((rc = map_scan_excl(m, pb.ecnt, pb.ebase, (int)np, &b.res.p->n_edges))) return rc;
     if ((rc = map_scan_excl(m, b.kcnt, b.kbase, n_kf, b.kbase + n_kf))) return rc;
-    hipLaunchKernelGGL(k_gba_setup, dim3(1), dim3(GBA_BLOCK), 0, c->stream, p, b.fixed, b.kf_edge, b.kf_fidx, b.fpos, b.kbase, b.res);
-    hipLaunchKernelGGL(k_gba_edges, dim3(mblocks), dim3(GBA_BLOCK), 0, c->stream, v, m->kkps, p.sf, b.loc, b.lrank, b.ebase, b.eoff, b.X, b.e_kf, b.e_obs,
-                       b.e_pt, b.e_xy, b.e_info, b.kbase, b.kfill, b.karr, b.res);
+    hipLaunchKernelGGL(k_gba_setup, dim3(1), dim3(GBA_BLOCK), 0, c->stream, p, b.fixed, pb.kf_edge, pb.kf_fidx, pb.fpos, b.kbase, b.res);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_edges<true, GbaRes>), dim3(mblocks), dim3(GBA_BLOCK), 0, c->stream, v, m->kkps, p.sf, pb.loc, pb.lrank, pb.ebase, pb.eoff,
+                       pb.X, pb.e_kf, pb.e_obs, pb.e_pt, pb.e_xy, pb.e_info, nullptr, b.kbase, b.kfill, b.karr, b.res);
     hipLaunchKernelGGL(k_gba_sort, dim3((unsigned)n_kf), dim3(GBA_BLOCK), 0, c->stream, b.kbase, b.karr, b.klist, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "gba_prep");
@@ -719,18 +468,15 @@ extern "C" int mo_map_global_ba(mo_map* m, const double K[9], const double* pose
     const int nf = r.n_free;
     const unsigned pblocks = (unsigned)((std::max(r.n_points, 1) + GBA_BLOCK - 1) / GBA_BLOCK), mvt = gba_mv_threads(r.n_edges, nf);
     for (int s = 0; run && s < prm->max_steps && !b.res.host().done; s++) {
-        hipLaunchKernelGGL(k_gba_lin, dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, E, b.X, b.poseC, b.Vi, b.gp, b.pfix, b.pc, b.res);
-#if GBA_STORE_J
-        hipLaunchKernelGGL(k_gba_jac, dim3((unsigned)((std::max(r.n_edges, 1) + GBA_BLOCK - 1) / GBA_BLOCK)), dim3(GBA_BLOCK), 0, c->stream, p, E, b.X, b.poseC, b.eJ.p,
-                           b.res);
-#endif
-        hipLaunchKernelGGL(k_gba_diag, dim3((unsigned)nf), dim3(64), 0, c->stream, p, E, b.kbase, b.klist, b.fpos, b.X, b.poseC, b.Vi, b.gp, b.pfix, b.Hd, b.L,
-                           b.kfix, b.x, b.r, b.z, b.p, b.res);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_lin<false, GbaPrm, GbaRes>), dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, 0, E, pb.X, pb.poseC, pb.Vi, pb.gp,
+                           pb.pfix, pb.pc, b.res);
+        hipLaunchKernelGGL(k_gba_diag, dim3((unsigned)nf), dim3(64), 0, c->stream, p, E, b.kbase, b.klist, pb.fpos, pb.X, pb.poseC, pb.Vi, pb.gp, pb.pfix, b.Hd,
+                           b.L, b.kfix, b.x, b.r, b.z, b.p, b.res);
         hipLaunchKernelGGL(k_gba_cg_init, dim3(1), dim3(GBA_THREADS), 0, c->stream, b.r, b.z, b.res);
         HIPCHK(c, hipGetLastError());
         for (int it = 0; it < prm->max_cg; it++) {
-            hipLaunchKernelGGL(k_gba_mv_pt, dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, E, b.kf_fidx, b.X, b.poseC, b.Vi, b.pfix, b.p, b.q, b.res);
-            hipLaunchKernelGGL(k_gba_mv_kf, dim3((unsigned)nf), dim3(mvt), 0, c->stream, p, E, b.kbase, b.klist, b.fpos, b.X, b.poseC, b.pfix, b.Hd, b.kfix,
+            hipLaunchKernelGGL(k_gba_mv_pt, dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, E, pb.kf_fidx, pb.X, pb.poseC, pb.Vi, pb.pfix, b.p, b.q, b.res);
+            hipLaunchKernelGGL(k_gba_mv_kf, dim3((unsigned)nf), dim3(mvt), 0, c->stream, p, E, b.kbase, b.klist, pb.fpos, pb.X, pb.poseC, pb.pfix, b.Hd, b.kfix,
                                b.p, b.q, b.Sp, b.pdot, b.res);
             hipLaunchKernelGGL(k_gba_cg_update, dim3(1), dim3(GBA_THREADS), 0, c->stream, p, b.L, b.kfix, b.Sp, b.pdot, b.x, b.r, b.z, b.p, b.res);
             if ((it + 1) % GBA_CG_CHUNK == 0 && it + 1 < prm->max_cg) {
@@ -740,35 +486,31 @@ extern "C" int mo_map_global_ba(mo_map* m, const double K[9], const double* pose
             }
         }
         // (the iterations end at max_cg: a solve still open is closed by the trial, which reads x as it stands)
-        hipLaunchKernelGGL(k_gba_trial, dim3(1), dim3(GBA_THREADS), 0, c->stream, b.fpos, b.x, b.poseC, b.poseT, b.res);
-        hipLaunchKernelGGL(k_gba_back, dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, E, b.kf_fidx, b.X, b.poseC, b.poseT, b.Vi, b.gp, b.pfix, b.x, b.Xt, b.pt,
-                           b.pu, b.res);
-        hipLaunchKernelGGL(k_gba_accept, dim3(1), dim3(GBA_THREADS), 0, c->stream, p, b.fpos, b.pc, b.pt, b.pu, b.X, b.Xt, b.poseC, b.poseT, b.res);
+        hipLaunchKernelGGL(k_gba_trial, dim3(1), dim3(GBA_THREADS), 0, c->stream, pb.fpos, b.x, pb.poseC, pb.poseT, b.res);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_back<false, GbaPrm, GbaRes>), dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, 0, E, pb.kf_fidx, pb.X, pb.poseC,
+                           pb.poseT, pb.Vi, pb.gp, pb.pfix, b.x, pb.Xt, pb.pt, pb.pu, b.res);
+        hipLaunchKernelGGL(k_gba_accept, dim3(1), dim3(GBA_THREADS), 0, c->stream, p, pb.fpos, pb.pc, pb.pt, pb.pu, pb.X, pb.Xt, pb.poseC, pb.poseT, b.res);
         HIPCHK(c, hipGetLastError());
         if ((rc = gba_look(c, b))) return rc;
     }
     mo_stage_mark(c, "gba_steps");
-    hipLaunchKernelGGL(k_gba_final, dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, E, b.X, b.poseC, b.e_inl, b.pc, b.pn, b.res);
-    hipLaunchKernelGGL(k_gba_reduce, dim3(1), dim3(GBA_THREADS), 0, c->stream, b.pc, b.pn, b.res);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_cost<false, GbaPrm, GbaRes>), dim3(pblocks), dim3(GBA_BLOCK), 0, c->stream, p, 1, E, pb.X, pb.poseC, pb.e_inl, pb.pc, pb.pn,
+                       b.res);
+    hipLaunchKernelGGL(k_ba_reduce<GbaRes>, dim3(1), dim3(GBA_THREADS), 0, c->stream, 1, pb.pc, pb.pn, b.res);
     const unsigned wblocks = (unsigned)((std::max(np, no) + GBA_BLOCK - 1) / GBA_BLOCK);
-    hipLaunchKernelGGL(k_gba_write, dim3(wblocks), dim3(GBA_BLOCK), 0, c->stream, p, (int)np, (int)no, b.loc, b.lrank, b.X, v.src.xyz,
-                       out->points_out ? b.pout.p : nullptr, b.e_obs, b.e_inl, b.einl, m->d_pos_slot, b.fpos, b.poseC, m->kP, b.res);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_write<GbaPrm, GbaRes>), dim3(wblocks), dim3(GBA_BLOCK), 0, c->stream, p, (int)np, (int)no, pb.loc, pb.lrank, pb.X,
+                       v.src.xyz, out->points_out ? pb.pout.p : nullptr, pb.e_obs, pb.e_inl, pb.einl, m->d_pos_slot, pb.fpos, pb.poseC, m->kP, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "gba_write");
     std::vector<int32_t> fidx(out->kf_state ? nk : 0);
     if ((rc = b.res.download(c))) return rc;
-    if (run) {
-        if (out->poses_out) HIPCHK(c, hipMemcpyAsync(out->poses_out, b.poseC, nk * 96, hipMemcpyDeviceToHost, c->stream));
-        if (out->edge_inlier) HIPCHK(c, hipMemcpyAsync(out->edge_inlier, b.einl, no, hipMemcpyDeviceToHost, c->stream));
-        if (out->points_out) HIPCHK(c, hipMemcpyAsync(out->points_out, b.pout, np * 24, hipMemcpyDeviceToHost, c->stream));
-        if (out->kf_state) HIPCHK(c, hipMemcpyAsync(fidx.data(), b.kf_fidx, nk * 4, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (run && (rc = ba_copy_outputs(c, pb, out, nk, np, no, fidx))) return rc;
     if ((rc = map_sync(c, clk))) return rc;
     if (!run) return MO_OK;   // no free position with an edge, or no problem point
     out->cost[0] = r.cost[0]; out->cost[1] = r.cost[1]; out->lambda = r.lambda;
     out->n_free = r.n_free; out->n_fixed = r.n_fixed; out->n_points = r.n_points; out->n_edges = r.n_edges; out->n_inliers = r.n_inliers;
     out->steps = r.steps; out->accepted = r.accepted; out->cg_iters = r.cg_iters;
-    if (out->kf_state) for (int i = 0; i < n_kf; i++) out->kf_state[i] = fidx[i] >= 0 ? 2 : fidx[i] == GBA_KF_FIXED ? 1 : 0;
+    ba_fill_kf_state(out, fidx, nk);
     out->ok = r.n_inliers >= prm->min_inliers;
     return MO_OK;
 }

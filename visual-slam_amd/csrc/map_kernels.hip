@@ -1,7 +1,7 @@
 // map_kernels.hip -- the device-resident LocalMapper (reference src/orbslam2/local_mapper.py): keyframe store, map store, the
 // device-wide scan and the per-keyframe step add_keyframe runs (store -> growth of one keyframe pair -> cull of every map point ->
 // per-keyframe lists and the counts _cull_keyframes reads), one synchronisation per keyframe.  The other users of the map have files
-// of their own (map_reloc.hip, map_track.hip, map_ba.hip, map_io.hip); map_store.h is what they share.
+// of their own (map_reloc.hip, map_track.hip, map_ba.hip, map_obs.hip, map_io.hip); map_store.h is what they share.
 //
 // Stores (structure of arrays, grown by reallocation):
 //   keyframes  slot s (creation order, never reused): kps [s][row][28 B], desc [s][row][32], count [s], P = K [R|t] [s][12] f64.

@@ -24,7 +24,7 @@
 //   k_pg_write     poses and kP of the free positions, the points, the outputs
 // The solver's shape: one workgroup runs a whole solve, its five vectors in LDS while they fit (PG_LDS_VEC_BYTES), in global scratch
 // beyond: a solve is one launch, a step five.  profiles/posegraph_rate.txt has the numbers and what was not built.
-// No floating-point atomics anywhere: sums are per-thread in index order, then wave_sum, then the waves in order (pg_block_sum;
+// No floating-point atomics anywhere: sums are per-thread in index order, then wave_sum, then the waves in order (block_sum of map_store.h;
 // pg_tree_sum of posegraph.h is the same order on the host).  Integer atomics only count.  -ffp-contract=off (Makefile).
 #include <climits>
 #include <cmath>
@@ -84,28 +84,6 @@ struct PgView {
     const int32_t* rbase; const int32_t* cbase; const int32_t* clist;
     const int32_t* ea; const int32_t* eb;
 };
-
-// fixed-order sums and maxima of a workgroup: every thread receives the result
-__device__ __forceinline__ double pg_block_sum(double v, double* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wave_sum(v);
-    if (lane == 0) lds[wv] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < nw; w++) s += lds[w];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ double pg_block_max(double v, double* lds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int d = 32; d; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
-    if (lane == 0) lds[wv] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < nw; w++) s = fmax(s, lds[w]);
-    __syncthreads();
-    return s;
-}
 
 __global__ void k_pg_init(PgRes* __restrict__ res) {
     if (threadIdx.x) return;
@@ -278,7 +256,7 @@ __device__ __forceinline__ void pg_matvec(const PgView& v, int nf, const double*
 __device__ __forceinline__ double pg_dot(int n, const double* a, const double* b, double* lds) {
     double s = 0.0;
     for (int j = threadIdx.x; j < n; j += blockDim.x) s += a[j] * b[j];
-    return pg_block_sum(s, lds);
+    return block_sum(s, lds);
 }
 
 // one workgroup: (H + lambda diag H) x = -g by preconditioned conjugate gradient from x = 0, then the trial vertices D(x_i) o S_i
@@ -334,7 +312,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgPrm prm, PgView v, co
             for (int k = 0; k < 7; k++) mu = fmax(mu, fabs(d[k]));
         }
     }
-    mu = pg_block_max(mu, red);
+    mu = block_max(mu, red);
     if (tid == 0) { res->upd = mu; res->cg_iters += it; }
 }
 
@@ -360,8 +338,8 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_accept(PgPrm prm, const doubl
     const int ne = res->n_edges, tid = threadIdx.x;
     double c0 = 0.0, c1 = 0.0;
     for (int e = tid; e < ne; e += PG_THREADS) { c0 += ec[e]; c1 += et[e]; }
-    c0 = pg_block_sum(c0, red);
-    c1 = pg_block_sum(c1, red);
+    c0 = block_sum(c0, red);
+    c1 = block_sum(c1, red);
     if (tid == 0) {
         const bool ok = c1 < c0;
         acc = ok;

@@ -1,5 +1,5 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
-// map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip (bundle adjustment, added observations), map_fuse.hip (fusion
+// map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip and map_gba.hip (bundle adjustment; ba_problem.h is what those two share), map_obs.hip (added and erased observations), map_fuse.hip (fusion
 // of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase) and map_io.hip (PLY text).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
@@ -12,7 +12,7 @@
 //   map_obs: the one reader of an observation; map_each_obs / map_observes: the walks over a point's valid observations;
 //   map_point_copy / map_life_new / map_life_merge: a point's own fields, its life record among them, through every rebuild;
 //   map_point_of: the one rule of the point_of tables (k_point_of / map_launch_point_of in map_kernels.hip, k_fuse_prep);
-//   wave_sum / wave_sum_all (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
+//   wave_sum / wave_sum_all / block_sum / block_max (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
 //   host helpers: map_now, map_window_lo, map_int32_guard, map_sync, map_stage_frame.
 // A new reader of the map takes a MapView and these; it does not spell out the stores or restate a rule.
 // Private to the library.
@@ -44,10 +44,10 @@ struct MapPtsStore {
     MapPts view() const { return MapPts{xyz, col, id, dkf, drow, off, okf, okp, life, pcap, ocap}; }
 };
 
-// A feature's scratch (RelocBufs in map_reloc.hip, TrackBufs, BaBufs, FuseBufs, GrowBufs, CovisBufs, BowBufs in bow.hip, LoopBufs): a
+// A feature's scratch (RelocBufs in map_reloc.hip, TrackBufs, BaProblem in ba_problem.h, BaBufs, ObsEditBufs, FuseBufs, GrowBufs, CovisBufs, BowBufs in bow.hip, LoopBufs): a
 // struct in the feature's own file that derives from this, lists its scratch buffers in an each_scratch and implements poison as
 // mo_poison_scratch(c, *this).  The map owns it (mo_map::features): made by map_feature<T> on the feature's first call, filled by
-// map_poison while a poison byte is set, freed with the map.  Nothing outside its file names it.
+// map_poison while a poison byte is set, freed with the map.  Nothing outside its file names it (BaProblem, which the two bundle adjustments share, lives in their header).
 struct MapFeature {
     virtual ~MapFeature() = default;
     virtual int poison(mo_ctx* c) = 0;
@@ -243,6 +243,29 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 __device__ __forceinline__ double wave_sum_all(double v) { return __shfl(wave_sum(v), 0, 64); }
 
+// ---- fixed-order f64 sum and maximum of a workgroup (blockDim.x a multiple of 64, lds [blockDim.x / 64]): wave_sum, then the waves in
+// order; every thread receives the result
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = wave_sum(v);
+    if (lane == 0) lds[wv] = v;
+    __syncthreads();
+    double s = lds[0];
+    for (int w = 1; w < nw; w++) s += lds[w];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ double block_max(double v, double* lds) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int d = 32; d; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
+    if (lane == 0) lds[wv] = v;
+    __syncthreads();
+    double s = lds[0];
+    for (int w = 1; w < nw; w++) s = fmax(s, lds[w]);
+    __syncthreads();
+    return s;
+}
+
 // ---- integer wave sum (every lane receives it) and the counter idiom: the wave's set flags added to *counter by lane 0, one atomic
 __device__ __forceinline__ int wave_sum_int(int v) {
     for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -352,6 +375,14 @@ void covis_finish(mo_map* m, mo_map_local_out* out);
 const uint8_t* covis_mask(const mo_map* m);
 // W [n_kf][n_kf] on the device, valid behind covis_enqueue on the context stream (mo_map_loop_candidates reads it)
 const int32_t* covis_weights(const mo_map* m);
+
+// ---- map_obs.hip -------------------------------------------------------------------------------------------------------------------
+// The entry erase of mo_map_erase_observations for a caller that runs it at the end of a chain of its own (mo_map_bundle_adjust_local):
+// cls [n_obs] on the device; the entries of class 2 leave if, when the chain gets there, *run != 0 and *n_inliers >= min_inliers (device
+// words).  Enqueued with its scratch reserved (stage mark "obs_erase"); after the caller's synchronisation, finish flips the copies of
+// the store, sets m->n_obs and returns the entries that left and the points left with fewer than two.
+int obs_erase_enqueue(mo_map* m, const uint8_t* cls, const int32_t* run, const int32_t* n_inliers, int min_inliers);
+void obs_erase_finish(mo_map* m, int32_t* n_erased, int32_t* n_under);
 
 // A query frame staged in the spare keyframe slot (mo_map_track, mo_map_relocalize; read-only on the map): the frame looked up,
 // *from_token set, defaults(n) run (the caller's per-keypoint output defaults), then - unless there is nothing to search, which leaves

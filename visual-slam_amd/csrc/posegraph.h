@@ -274,8 +274,8 @@ PG_HD void pg_chol7_solve(const double* L, const double* b, double* x) {
 
 // ---- the fixed summation order of a 1024-thread workgroup, as a host loop ---------------------------------------------------------------
 // Thread t adds the elements t, t + PG_THREADS, ... in order; a wave's 64 partial sums fold as wave_sum's shuffle tree does in lane 0
-// (v[l] += v[l + d], d = 32 .. 1); the 16 waves are added in order.  The device does this with its threads (pg_block_sum of
-// map_posegraph.hip); the replay calls this.
+// (v[l] += v[l + d], d = 32 .. 1); the 16 waves are added in order.  The device does this with its threads (block_sum of
+// map_store.h); the replay calls this.
 #define PG_THREADS 1024
 #if !defined(__HIP_DEVICE_COMPILE__)
 template <class F> inline double pg_tree_sum(int n, F f) {
