@@ -9,8 +9,8 @@
 //   k_cf_seed     one workgroup per candidate: the seed rows, the owner of every candidate row a seed names (atomicMin)
 //   k_cf_guided   one lane per source row, grid.y = candidate x direction: the projected-window search of map_search.h
 //   k_cf_pairs    one workgroup per candidate: seeds and guided matches packed in row order (block scans, as k_sim3_gather)
-//   k_cf_refit    one wave per candidate: selection, (Gauss-Newton, selection) twice from the given model (k_sim3_refine's loop; a second
-//                 copy of it: NOTES.md says why)
+//   k_cf_refit    one wave per candidate: selection, (Gauss-Newton, selection) twice from the given model (sim3_refine_rounds of
+//                 sim3_device.h, which k_sim3_refine runs from its own start model)
 //   k_cf_win      one workgroup: the winner, its inlier pairs written to loop_point / source, the claim keys reset
 //   k_cf_proj     one lane per map point: the loop's local map projected into p, the best row claimed by a 64-bit atomicMin
 //   k_cf_claim    one lane per row of p: the claims become loop points
@@ -23,6 +23,7 @@
 #include "map_store.h"
 #include "map_search.h"
 #include "sim3.h"
+#include "sim3_device.h"
 
 #define CF_MAX_CAND 16
 #define CF_BLOCK 256
@@ -71,12 +72,6 @@ struct ConfirmBufs : MapFeature {
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
 
-__device__ __forceinline__ void cf_model(const double* m13, Sim3& S) {
-    S.s = m13[0];
-    for (int i = 0; i < 9; i++) S.R[i] = m13[1 + i];
-    for (int i = 0; i < 3; i++) S.t[i] = m13[10 + i];
-}
-
 // k_sim3_gather's rule for row i of p under candidate c, and the seed flag: what the row names
 __device__ __forceinline__ bool cf_listed(const MapView& v, const CfPrm& prm, const CfIn& in, int c, int i, int n2, int* a, int* b, int* j) {
     const size_t e = (size_t)c * prm.stride + i;
@@ -87,14 +82,6 @@ __device__ __forceinline__ bool cf_listed(const MapView& v, const CfPrm& prm, co
 __device__ __forceinline__ bool cf_seed(const MapView& v, const CfPrm& prm, const CfIn& in, const int32_t* __restrict__ seedj, int c, int i, int n2,
                                         int* a, int* b, int* j) {
     return cf_listed(v, prm, in, c, i, n2, a, b, j) && seedj[(size_t)c * prm.r2 + *j] == i;
-}
-
-// X = R xyz[i] + t (f64, each row summed left to right: k_sim3_gather's)
-__device__ __forceinline__ void cf_camera(const MapView& v, const double* pose12, int i, double* X) {
-    double R[9], t[3];
-    pose_split(pose12, R, t);
-    const float* x = v.src.xyz + (size_t)i * 3;
-    for (int d = 0; d < 3; d++) X[d] = R[d * 3] * (double)x[0] + R[d * 3 + 1] * (double)x[1] + R[d * 3 + 2] * (double)x[2] + t[d];
 }
 
 // one workgroup per candidate: its entry of the result block; every listed row enters itself as owner of the candidate row it names
@@ -133,10 +120,10 @@ __global__ __launch_bounds__(CF_BLOCK) void k_cf_guided(MapView v, CfPrm prm, Cf
     int bd = INT_MAX, bq = INT_MAX;
     if (ro != TK_NOT_LOCAL) {
         Sim3 S, I;
-        cf_model(prm.model[c], S);
+        sim3_model_load(prm.model[c], S);
         sim3_inverse(S, I);
         double X[3], Y[3], uu, vv;
-        cf_camera(v, poses + (size_t)(dir ? k : prm.p) * 12, pt, X);
+        sim3_camera(v, poses + (size_t)(dir ? k : prm.p) * 12, pt, X);
         sim3_apply(dir ? S : I, X, Y);
         if (trk_project(prm.P, Y[0], Y[1], Y[2], prm.w, prm.h, &uu, &vv)) {
             const int g = dir ? 0 : 1 + c, ts = dir ? s1 : s2;
@@ -181,13 +168,7 @@ __global__ __launch_bounds__(1024) void k_cf_pairs(MapView v, CfPrm prm, CfIn in
         int tot;
         const int r = block_excl_scan(kind ? 1 : 0, lw, &tot);
         if (kind) {
-            const mo_keypoint k1 = kkps[(size_t)s1 * v.row + i], k2 = kkps[(size_t)s2 * v.row + j];
-            Sim3Pair o;
-            cf_camera(v, poses + (size_t)prm.p * 12, a, o.X1);
-            cf_camera(v, poses + (size_t)k * 12, b, o.X2);
-            o.x1 = k1.x; o.y1 = k1.y; o.i1 = ba_info(prm.sf, k1.octave);
-            o.x2 = k2.x; o.y2 = k2.y; o.i2 = ba_info(prm.sf, k2.octave);
-            pr[base + added + r] = o;
+            pr[base + added + r] = sim3_pair_pack(v, kkps, prm.sf, poses + (size_t)prm.p * 12, s1, i, a, poses + (size_t)k * 12, s2, j, b);
             prow[base + added + r] = i; pb[base + added + r] = b; pkind[base + added + r] = (uint8_t)kind;
             if (kind == 2) atomicAdd(&ng, 1);
         }
@@ -197,22 +178,7 @@ __global__ __launch_bounds__(1024) void k_cf_pairs(MapView v, CfPrm prm, CfIn in
     if (threadIdx.x == 0) { res->npairs[c] = added; res->nguided[c] = ng; }
 }
 
-// inlier flags of the pairs under S into fl (by row of p), their number (map_sim3.hip's sim3_select)
-__device__ __forceinline__ int cf_select(const CfPrm& prm, const Sim3& S, const Sim3Pair* __restrict__ pr, const int32_t* __restrict__ rows, int m,
-                                         uint8_t* __restrict__ fl) {
-    Sim3 I;
-    sim3_inverse(S, I);
-    int n = 0;
-    for (int j = threadIdx.x; j < m; j += 64) {
-        double e1, e2;
-        const bool in = sim3_inlier(prm.K, S, I, pr[j], prm.chi2, &e1, &e2);
-        fl[rows[j]] = in;
-        n += in;
-    }
-    return wave_sum_int(n);
-}
-
-// one wave per candidate: the given model, its inliers, (Gauss-Newton over them, re-selection) twice: k_sim3_refine's rounds
+// one wave per candidate: the given model, refined by sim3_refine_rounds (sim3_device.h) over seeds and guided matches
 __global__ __launch_bounds__(64) void k_cf_refit(CfPrm prm, const Sim3Pair* __restrict__ pairs, const int32_t* __restrict__ prow, uint8_t* __restrict__ inl,
                                                  CfRes* __restrict__ res) {
     const int c = blockIdx.x;
@@ -222,38 +188,12 @@ __global__ __launch_bounds__(64) void k_cf_refit(CfPrm prm, const Sim3Pair* __re
     const int32_t* rows = prow + (size_t)c * prm.stride;
     uint8_t* fl = inl + (size_t)c * prm.stride;
     Sim3 S;
-    cf_model(prm.model[c], S);
+    sim3_model_load(prm.model[c], S);
     int n = 0;
-    if (m >= 3) {
-        n = cf_select(prm, S, pr, rows, m, fl);
-        for (int round = 0; round < 2 && n >= 3; round++) {
-            for (int it = 0; it < 10; it++) {
-                Sim3 I;
-                sim3_inverse(S, I);
-                double H[28], g[7];
-#pragma unroll
-                for (int i = 0; i < 28; i++) H[i] = 0.0;
-#pragma unroll
-                for (int i = 0; i < 7; i++) g[i] = 0.0;
-                for (int j = threadIdx.x; j < m; j += 64) {
-                    if (!fl[rows[j]]) continue;
-                    sim3_gn_accumulate(prm.K, S, I, pr[j], prm.chi2, H, g);
-                }
-#pragma unroll
-                for (int i = 0; i < 28; i++) H[i] = wave_sum_all(H[i]);
-#pragma unroll
-                for (int i = 0; i < 7; i++) g[i] = wave_sum_all(g[i]);
-                double step;
-                if (!sim3_gn_update(H, g, S, &step) || step < 1e-12) break;
-            }
-            n = cf_select(prm, S, pr, rows, m, fl);
-        }
-    }
+    if (m >= 3) n = sim3_refine_rounds(prm, pr, rows, m, fl, S);   // (fewer pairs: no inlier, the model as given)
     if (threadIdx.x == 0) {
         res->ninl[c] = n;
-        res->model[c][0] = S.s;
-        for (int i = 0; i < 9; i++) res->model[c][1 + i] = S.R[i];
-        for (int i = 0; i < 3; i++) res->model[c][10 + i] = S.t[i];
+        sim3_model_store(S, res->model[c]);
     }
 }
 
@@ -299,9 +239,9 @@ __global__ __launch_bounds__(CF_BLOCK) void k_cf_proj(MapView v, CfPrm prm, cons
     double uu = 0.0, vv = 0.0;
     if (ro != TK_NOT_LOCAL && !at_p && !skip[x]) {
         Sim3 S;
-        cf_model(res->model[win], S);
+        sim3_model_load(res->model[win], S);
         double X[3], Y[3];
-        cf_camera(v, poses + (size_t)prm.cand[win] * 12, x, X);
+        sim3_camera(v, poses + (size_t)prm.cand[win] * 12, x, X);
         sim3_apply(S, X, Y);
         cand = trk_project(prm.P, Y[0], Y[1], Y[2], prm.w, prm.h, &uu, &vv);
     }

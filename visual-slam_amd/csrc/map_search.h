@@ -74,8 +74,9 @@ template <class V> __device__ __forceinline__ void trk_window(double u, double v
 }
 
 // trk_window with the octave gate lo <= octave <= hi in place of ro +- 1 (the frustum mode: [L - 1, L]).  Two walks still: trk_window as
-// trk_window_oct over [ro - 1, ro + 1] keeps every occupancy but moves k_fuse_search, k_cf_guided, k_cf_proj and k_cr_search by 4 - 10
-// instructions and k_tb_search from 74 to 76 VGPRs (profiles/track_unify_isa.txt); the run times of those searches were not measured.
+// trk_window_oct over [ro - 1, ro + 1] keeps every occupancy but moves the searches of fusion and correction (k_merge_search of
+// map_merge.h since), k_cf_guided and k_cf_proj by 4 - 10 instructions and k_tb_search from 74 to 76 VGPRs
+// (profiles/track_unify_isa.txt); the run times of those searches were not measured.
 template <class V> __device__ __forceinline__ void trk_window_oct(double u, double v, double r, int lo, int hi, int w, int h,
                                                                   const int32_t* __restrict__ cell, const int32_t* __restrict__ sorted,
                                                                   const mo_keypoint* __restrict__ fk, V visit) {

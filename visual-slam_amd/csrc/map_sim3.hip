@@ -14,6 +14,7 @@
 #include "common.h"
 #include "map_store.h"
 #include "sim3.h"
+#include "sim3_device.h"
 
 #define S3_MAX_CAND 16
 #define S3_HYP_WAVES 4    // hypotheses per block of k_sim3_hyp (one per wave)
@@ -64,9 +65,6 @@ __global__ __launch_bounds__(1024) void k_sim3_gather(MapView v, const mo_keypoi
         }
     }
     const int s1 = v.pos_slot[prm.p], s2 = v.pos_slot[k], n2 = v.kcnt[s2];
-    double R1[9], t1[3], R2[9], t2[3];
-    pose_split(poses + (size_t)prm.p * 12, R1, t1);
-    pose_split(poses + (size_t)k * 12, R2, t2);
     const size_t base = (size_t)c * prm.stride;
     int added = 0;
     for (int b0 = 0; b0 < prm.n_p; b0 += 1024) {
@@ -77,17 +75,7 @@ __global__ __launch_bounds__(1024) void k_sim3_gather(MapView v, const mo_keypoi
         int tot;
         const int r = block_excl_scan(keep ? 1 : 0, lw, &tot);
         if (keep) {
-            const float* xa = v.src.xyz + (size_t)a * 3;
-            const float* xb = v.src.xyz + (size_t)b * 3;
-            const mo_keypoint k1 = kkps[(size_t)s1 * v.row + i], k2 = kkps[(size_t)s2 * v.row + j];
-            Sim3Pair o;
-            for (int d = 0; d < 3; d++) {
-                o.X1[d] = R1[d * 3] * (double)xa[0] + R1[d * 3 + 1] * (double)xa[1] + R1[d * 3 + 2] * (double)xa[2] + t1[d];
-                o.X2[d] = R2[d * 3] * (double)xb[0] + R2[d * 3 + 1] * (double)xb[1] + R2[d * 3 + 2] * (double)xb[2] + t2[d];
-            }
-            o.x1 = k1.x; o.y1 = k1.y; o.i1 = ba_info(prm.sf, k1.octave);
-            o.x2 = k2.x; o.y2 = k2.y; o.i2 = ba_info(prm.sf, k2.octave);
-            pr[base + added + r] = o;
+            pr[base + added + r] = sim3_pair_pack(v, kkps, prm.sf, poses + (size_t)prm.p * 12, s1, i, a, poses + (size_t)k * 12, s2, j, b);
             prow[base + added + r] = i;
         }
         added += tot;
@@ -129,22 +117,7 @@ __global__ __launch_bounds__(64 * S3_HYP_WAVES) void k_sim3_hyp(Sim3Prm prm, con
     if (lane == 0) atomicMax(&res->best[c], key);
 }
 
-// inlier flags of the pairs under S into fl (by row of p), their number
-__device__ __forceinline__ int sim3_select(const Sim3Prm& prm, const Sim3& S, const Sim3Pair* __restrict__ pr, const int32_t* __restrict__ rows, int m,
-                                           uint8_t* __restrict__ fl) {
-    Sim3 I;
-    sim3_inverse(S, I);
-    int n = 0;
-    for (int j = threadIdx.x; j < m; j += 64) {
-        double e1, e2;
-        const bool in = sim3_inlier(prm.K, S, I, pr[j], prm.chi2, &e1, &e2);
-        fl[rows[j]] = in;
-        n += in;
-    }
-    return wave_sum_int(n);
-}
-
-// one wave per candidate: the best hypothesis' model, (Gauss-Newton over its inliers, re-selection) twice
+// one wave per candidate: the best hypothesis' model, refined by sim3_refine_rounds (sim3_device.h)
 __global__ __launch_bounds__(64) void k_sim3_refine(Sim3Prm prm, const Sim3Pair* __restrict__ pairs, const int32_t* __restrict__ prow,
                                                     uint8_t* __restrict__ inl, Sim3Res* __restrict__ res) {
     const int c = blockIdx.x;
@@ -157,34 +130,10 @@ __global__ __launch_bounds__(64) void k_sim3_refine(Sim3Prm prm, const Sim3Pair*
     const int h = (int)(0xffffffffu - (unsigned)(best & 0xffffffffu));
     Sim3 S;
     if (!sim3_solve(pr, m, pnp_stream_seed(prm.seed, prm.cand[c]), h, S)) return;   // (it had a model in k_sim3_hyp)
-    int n = sim3_select(prm, S, pr, rows, m, fl);
-    for (int round = 0; round < 2 && n >= 3; round++) {
-        for (int it = 0; it < 10; it++) {
-            Sim3 I;
-            sim3_inverse(S, I);
-            double H[28], g[7];
-#pragma unroll
-            for (int i = 0; i < 28; i++) H[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < 7; i++) g[i] = 0.0;
-            for (int j = threadIdx.x; j < m; j += 64) {
-                if (!fl[rows[j]]) continue;
-                sim3_gn_accumulate(prm.K, S, I, pr[j], prm.chi2, H, g);
-            }
-#pragma unroll
-            for (int i = 0; i < 28; i++) H[i] = wave_sum_all(H[i]);
-#pragma unroll
-            for (int i = 0; i < 7; i++) g[i] = wave_sum_all(g[i]);
-            double step;
-            if (!sim3_gn_update(H, g, S, &step) || step < 1e-12) break;
-        }
-        n = sim3_select(prm, S, pr, rows, m, fl);
-    }
+    const int n = sim3_refine_rounds(prm, pr, rows, m, fl, S);
     if (threadIdx.x == 0) {
         res->ninl[c] = n;
-        res->model[c][0] = S.s;
-        for (int i = 0; i < 9; i++) res->model[c][1 + i] = S.R[i];
-        for (int i = 0; i < 3; i++) res->model[c][10 + i] = S.t[i];
+        sim3_model_store(S, res->model[c]);
     }
 }
 

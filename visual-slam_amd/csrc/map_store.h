@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip and map_gba.hip (bundle adjustment; ba_problem.h is what those two share), map_obs.hip (added and erased observations), map_fuse.hip (fusion
-// of duplicate points), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase) and map_io.hip (PLY text).
+// of duplicate points) and map_correct.hip (loop correction; map_merge.h is what those two share), map_sim3.hip and map_confirm.hip (loop alignment and confirmation; sim3_device.h is what those two share), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase) and map_io.hip (PLY text).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
 //   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),
@@ -46,7 +46,7 @@ struct MapPtsStore {
 
 // A feature's scratch (RelocBufs in map_reloc.hip, TrackBufs, BaProblem in ba_problem.h, BaBufs, ObsEditBufs, FuseBufs, GrowBufs, CovisBufs, BowBufs in bow.hip, LoopBufs): a
 // struct in the feature's own file that derives from this, lists its scratch buffers in an each_scratch and implements poison as
-// mo_poison_scratch(c, *this).  The map owns it (mo_map::features): made by map_feature<T> on the feature's first call, filled by
+// mo_poison_scratch(c, *this) (MergeBufs of map_merge.h, like MatchBufs below, is a member of two such structs and forwards its list).  The map owns it (mo_map::features): made by map_feature<T> on the feature's first call, filled by
 // map_poison while a poison byte is set, freed with the map.  Nothing outside its file names it (BaProblem, which the two bundle adjustments share, lives in their header).
 struct MapFeature {
     virtual ~MapFeature() = default;
