@@ -500,6 +500,10 @@ def test_vocabulary_training_hand_cases():
 # solver's, which the one reserve of the problem brings; fpos is also where the free positions moved from the local result block) = 26
 # in BaProblem, and S and the result block in BaBufs.  The observation edits left BaBufs for a feature of their own (map_obs.hip) that
 # no step here calls.  So every count from the bundle adjustment on is one higher.
+# The rebuilds share map_rebuild.h since: KfCullBufs lost ecnt and ebase (15 buffers -> 13), ObsEditBufs ao_cnt, ao_base and ao_total (10 -> 7);
+# the map's kobs / obase and a word of the feature's result block stand in.  Neither feature is among the eight steps (the observation
+# edits as said above, the keyframe cull never was), and the four arrays of the map were already filled from the first step on, so the
+# list stands as it is: 18 + 0, 30 + 0, ... - measured again with the buffers gone, the same eight numbers.
 FEATURE_FILLS = [18, 30, 41, 69, 86, 95, 103, 121]
 
 

@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "common.h"
-#include "map_store.h"
+#include "map_rebuild.h"   // (map_store.h with it)
 #include "map_search.h"
 #include "ba.h"   // ba_info
 
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_grow_append(GrowPrm prm, const Gro
     const int n_new = res->n_new;
     if (!n_new) return;
     const int f = blockIdx.x * GR_BLOCK + threadIdx.x;
-    if (f == 0) { dst.off[n0 + n_new] = o0 + res->n_obs_new; st[ST_NPTS] = n0 + n_new; st[ST_NOBS] = o0 + res->n_obs_new; }   // (the next call's live counts)
+    if (f == 0) map_store_end(dst, st, n0 + n_new, o0 + res->n_obs_new);
     if (f >= res->n_free || !isnew[f]) return;
     const int row1 = frow[f], r = rank[f], i = n0 + r;
     for (int k = 0; k < 3; k++) { const double v = Xo[(size_t)f * 3 + k]; dst.xyz[(size_t)i * 3 + k] = (float)v; outX[(size_t)r * 3 + k] = v; }

@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "common.h"
-#include "map_store.h"
+#include "map_rebuild.h"   // (map_store.h with it)
 
 #define MAP_SCAN_BLOCK 256
 #define MAP_SCAN_ITEMS 4
@@ -120,8 +120,8 @@ __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__
         added += t;
     }
     if (threadIdx.x == 0) {
-        dst.off[n0 + added] = o0 + 2 * added;
-        st[ST_NPTS] = n0 + added; st[ST_NOBS] = o0 + 2 * added; st[ST_NNEW] = added;
+        map_store_end(dst, st, n0 + added, o0 + 2 * added);
+        st[ST_NNEW] = added;
     }
 }
 
@@ -160,18 +160,28 @@ __global__ __launch_bounds__(256) void k_map_cull(MapView mv, int bound, const m
     kobs[i] = k ? nob : 0;
 }
 
-// survivors in order: every SoA field moves together; ent_id[entry] = id of the entry's point (the counting sort's values)
+// survivors in order through map_point_move (map_rebuild.h); the entry rule also writes ent_id[entry] = id of the entry's point (the
+// counting sort's values)
+struct CompactEdit : RebuildEdit {
+    int32_t* ent_id;
+    __device__ int entries(const MapPts& src, int i, int o0, int o1, const MapPts& dst, int ob) const {
+        const int id = src.id[i];
+        return map_entries_copy(src, o0, o1, dst, ob, [&](int at) { ent_id[at] = id; });
+    }
+};
+
+// The chain's own kernel and not k_map_rebuild for two things: it runs over `bound` points at most, the live count being on the device,
+// and an index error (ST_ERR) holds the end of the store back - the host then keeps the map it had (finish_chain).  map_store_end
+// also writes the live counts ST_NPTS / ST_NOBS here; behind a chain without an error finish_chain uploads the same two words again.
+// The upload is redundant since and is kept on purpose in this change (no later kernel of the chain reads the two words; with an error
+// neither is written and the counts in front of the cull stand); dropping it is a change of its own.
 __global__ __launch_bounds__(256) void k_map_compact(MapPts src, MapPts dst, int bound, const int32_t* __restrict__ keep, const int32_t* __restrict__ rank,
                                                      const int32_t* __restrict__ obase, int32_t* __restrict__ ent_id, int32_t* __restrict__ st) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0 && !st[ST_ERR]) dst.off[st[ST_KEPT]] = st[ST_KOBS];
+    const int err = st[ST_ERR], kept = st[ST_KEPT], kobs = st[ST_KOBS];
+    if (i == 0 && !err) map_store_end(dst, st, kept, kobs);
     if (i >= bound || !keep[i]) return;
-    const int r = rank[i], ob = obase[i];
-    map_point_copy(src, i, dst, r);
-    const int id = src.id[i];
-    dst.off[r] = ob;
-    const int o0 = src.off[i], o1 = src.off[i + 1];
-    for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; ent_id[ob + o - o0] = id; }
+    map_point_move(CompactEdit{{}, ent_id}, src, i, dst, rank[i], obase[i]);
 }
 
 // ---- per-keyframe lists (local_mapper.py:243-251): stable counting sort of (keyframe, map order) ----------------------------------
@@ -389,8 +399,7 @@ static int run_cull_chain(mo_map* m, int64_t bound_pts, int64_t bound_obs) {
     if (bound_pts > INT32_MAX / 2 || bound_obs > INT32_MAX / 2) return mo_fail(c, MO_ERR_CAPACITY, "map larger than int32 indexing");
     int rc;
     const int bp = (int)std::max<int64_t>(bound_pts, 1), bo = (int)std::max<int64_t>(bound_obs, 1);
-    if ((rc = map_pts_reserve(m, m->cur ^ 1, (size_t)bp, (size_t)bo, false))) return rc;
-    if ((rc = mo_reserve(c, m->keep, (size_t)bp, m->kobs, (size_t)bp, m->rank, (size_t)bp, m->obase, (size_t)bp, m->ent_id, (size_t)bo))) return rc;
+    if ((rc = rebuild_reserve(m, (size_t)bp, (size_t)bo)) || (rc = m->ent_id.reserve(c, (size_t)bo))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
     const unsigned gp = (unsigned)((bp + 255) / 256);
@@ -446,8 +455,7 @@ static int finish_chain(mo_map* m, int n_kf, int32_t* kf_len, int32_t* kf_red) {
         m->n_pts = s[ST_NPTS]; m->n_obs = s[ST_NOBS];
         return mo_fail(c, MO_ERR_INDEX, s[ST_ERR] & 1 ? "list index out of range (keyframe)" : "list index out of range (keypoint)");
     }
-    m->cur ^= 1;
-    m->n_pts = s[ST_KEPT]; m->n_obs = s[ST_KOBS];
+    map_commit(m, s[ST_KEPT], s[ST_KOBS]);
     m->list_rows = n_kf;
     m->lcur ^= 1;
     // the next call's live counts

@@ -14,8 +14,8 @@
 //     k_kc_walk       one workgroup walks the candidates, the removed flags by position in LDS, a barrier per candidate (walk = 1: the
 //                     slower one at every size measured, kept as the launches' cross-check in the tests)
 //   k_kc_newpos, k_kc_ecount, map_scan_excl, k_kc_escatter   the erase: position -> position after the removal, the surviving valid
-//                   observations per point, their offsets, every field of every point into the other copy.  With no removal decided the
-//                   last two do nothing and the host does not flip the copies.
+//                   observations per point (the map's kobs), their offsets (obase), every field of every point into the other copy.
+//                   With no removal decided the last two do nothing and the host does not commit (map_commit of map_rebuild.h).
 // Integer atomics only; the one floating-point operation is the f64 compare n_redundant > ratio * n_points.
 #include <climits>
 #include <cmath>
@@ -23,7 +23,7 @@
 #include <string>
 
 #include "common.h"
-#include "map_store.h"
+#include "map_rebuild.h"   // (map_store.h with it)
 
 #define KC_BLOCK 256
 #define KC_WALK_BLOCK 1024
@@ -41,12 +41,11 @@ struct KfCullBufs : MapFeature {
     DevBuf<KcEnt> list;                          // [observations] the candidates' lists behind each other
     DevBuf<int32_t> rem, newpos;                 // [n_kf] by position: removed; position after the removal (-1: erased)
     DevBuf<uint8_t> protect; PinnedBuf<uint8_t> h_protect;
-    DevBuf<int32_t> ecnt, ebase;                 // [points] surviving observations, their offsets
     PinnedBuf<int32_t> h_rem;                    // [n_kf] rem as the host reads it behind the synchronisation
     ResBlock<KcRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) {
-        f(cidx); f(cpos); f(cw); f(cnp); f(cred); f(crem); f(lbase); f(lcur); f(list); f(rem); f(newpos); f(protect); f(ecnt); f(ebase); f(res);
+        f(cidx); f(cpos); f(cw); f(cnp); f(cred); f(crem); f(lbase); f(lcur); f(list); f(rem); f(newpos); f(protect); f(res);
     }
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
@@ -240,12 +239,14 @@ __global__ __launch_bounds__(KC_BLOCK) void k_kc_ecount(MapView v, const int32_t
 }
 
 // every field of every point into the other copy; its valid observations at surviving positions, in entry order, as (position after the
-// removal, row), both non-negative
+// removal, row), both non-negative.  Not k_map_rebuild of map_rebuild.h: under that form kfcull_erase measured 3 - 5 us above the
+// parent's runs (0.093 / 0.094 ms against 0.089 / 0.089 at 10^6 points), so the kernel keeps its own text (NOTES.md); it shares
+// map_store_end, rebuild_reserve, the map's kobs / obase and map_commit.
 __global__ __launch_bounds__(KC_BLOCK) void k_kc_escatter(MapView v, MapPts dst, const int32_t* __restrict__ newpos, const int32_t* __restrict__ base,
                                                           const KcRes* __restrict__ res, int32_t* __restrict__ st) {
     const int i = blockIdx.x * KC_BLOCK + threadIdx.x;
     if (!res->n_removed) return;
-    if (i == 0) { dst.off[v.n_pts] = res->n_obs; st[ST_NPTS] = v.n_pts; st[ST_NOBS] = res->n_obs; }   // (the next call's live counts)
+    if (i == 0) map_store_end(dst, st, v.n_pts, res->n_obs);
     if (i >= v.n_pts) return;
     const MapPts& src = v.src;
     map_point_copy(src, i, dst, i);
@@ -316,15 +317,14 @@ static int kc_erase_enqueue(mo_map* m, KfCullBufs& b) {
     mo_ctx* c = m->c;
     const size_t n_kf = m->pos_slot.size(), np = (size_t)m->n_pts;
     int rc;
-    if ((rc = mo_reserve(c, b.newpos, n_kf, b.ecnt, np, b.ebase, np))) return rc;
+    if ((rc = b.newpos.reserve(c, n_kf))) return rc;
     const MapView v = map_view(m);
-    const MapPts dst = m->P[m->cur ^ 1].view();
     const unsigned pblocks = (unsigned)((np + KC_BLOCK - 1) / KC_BLOCK);
     hipLaunchKernelGGL(k_kc_newpos, dim3(1), dim3(KC_WALK_BLOCK), 0, c->stream, b.rem, (int)n_kf, b.newpos, b.res);
-    hipLaunchKernelGGL(k_kc_ecount, dim3(pblocks), dim3(KC_BLOCK), 0, c->stream, v, b.newpos, b.res, b.ecnt);
+    hipLaunchKernelGGL(k_kc_ecount, dim3(pblocks), dim3(KC_BLOCK), 0, c->stream, v, b.newpos, b.res, m->kobs);
     HIPCHK(c, hipGetLastError());
-    if ((rc = map_scan_excl(m, b.ecnt, b.ebase, (int)np, &b.res.p->n_obs))) return rc;
-    hipLaunchKernelGGL(k_kc_escatter, dim3(pblocks), dim3(KC_BLOCK), 0, c->stream, v, dst, b.newpos, b.ebase, b.res, m->st);
+    if ((rc = map_scan_excl(m, m->kobs, m->obase, (int)np, &b.res.p->n_obs))) return rc;
+    hipLaunchKernelGGL(k_kc_escatter, dim3(pblocks), dim3(KC_BLOCK), 0, c->stream, v, m->P[m->cur ^ 1].view(), b.newpos, m->obase, b.res, m->st);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "kfcull_erase");
     HIPCHK(c, hipMemcpyAsync(b.h_rem, b.rem, n_kf * 4, hipMemcpyDeviceToHost, c->stream));
@@ -335,8 +335,7 @@ static int kc_erase_enqueue(mo_map* m, KfCullBufs& b) {
 static void kc_erase_finish(mo_map* m, KfCullBufs& b) {
     const KcRes& r = b.res.host();
     if (!r.n_removed) return;
-    m->cur ^= 1;
-    m->n_obs = r.n_obs;
+    map_commit(m, m->n_pts, r.n_obs);
     for (int q = (int)m->pos_slot.size() - 1; q >= 0; q--)
         if (b.h_rem.p[q]) m->pos_slot.erase(m->pos_slot.begin() + q);
 }
@@ -352,7 +351,7 @@ static int kc_cull(mo_map* m, const mo_map_kfcull_params* prm, mo_map_kfcull_out
     MAP_ENTER(m);
     HostClock clk(c);
     KfCullBufs& b = map_feature<KfCullBufs>(m);
-    if (erase && ((rc = map_pts_reserve(m, m->cur ^ 1, (size_t)m->n_pts, (size_t)m->n_obs, false)) || (rc = b.h_rem.reserve(c, n_kf)))) return rc;
+    if (erase && ((rc = rebuild_reserve(m, (size_t)m->n_pts, (size_t)m->n_obs)) || (rc = b.h_rem.reserve(c, n_kf)))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     mo_stage_begin(c);
     if ((rc = kc_decide_enqueue(m, b, prm))) return rc;
@@ -400,7 +399,7 @@ extern "C" int mo_map_erase_keyframes(mo_map* m, const int32_t* positions, int n
     MAP_ENTER(m);
     HostClock clk(c);
     KfCullBufs& b = map_feature<KfCullBufs>(m);
-    if ((rc = map_pts_reserve(m, m->cur ^ 1, (size_t)m->n_pts, (size_t)m->n_obs, false)) || (rc = mo_reserve(c, b.rem, n_kf, b.h_rem, n_kf, b.res)) ||
+    if ((rc = rebuild_reserve(m, (size_t)m->n_pts, (size_t)m->n_obs)) || (rc = mo_reserve(c, b.rem, n_kf, b.h_rem, n_kf, b.res)) ||
         (rc = upload_pos_slot(m)))
         return rc;
     std::memset(b.h_rem.p, 0, n_kf * 4);

@@ -8,31 +8,31 @@
 //   k_oe_points    one thread per point: its fields (map_point_copy) and off[i] = S[off[i]] into the other copy; the points that lost an
 //                  entry and hold fewer than two are counted in registers, one integer atomic per workgroup
 //   k_oe_entries   one thread per entry: okf / okp of a kept entry to S[o], coalesced reads, ascending writes
-// With nothing flagged both kernels return at once and the host does not flip the copies (mo_map_erase_points' behaviour).
+// With nothing flagged both kernels return at once and the host does not commit (mo_map_erase_points' behaviour).  The erase shares
+// map_store_end and map_commit with the point-parallel rebuilds (map_rebuild.h) and nothing else.
 // Added observations:
 //   k_obs_claim    one thread per given entry: it claims its point, the lowest entry wins
-//   k_obs_count    one thread per point: a claimed point without an observation in kf_pos gains one; its new count
-//   map_scan_excl  the new offsets
-//   k_obs_scatter  every point into the other copy of the store, the new observation behind its old ones
+//   k_obs_count    one thread per point: a claimed point without an observation in kf_pos gains one; its new count (the map's kobs)
+//   rebuild_enqueue (map_rebuild.h) with the edit ObsAdd: every point into the other copy, the new observation behind its old ones
 #include <climits>
 
 #include "common.h"
-#include "map_store.h"
+#include "map_rebuild.h"   // (map_store.h with it)
 
 #define OBS_BLOCK 256
 #define OE_MAX_BLOCKS 2048   // workgroups of k_oe_points (one atomic each)
 
-struct OeRes { int32_t n_obs, n_under; };   // the entries behind the erase; the points left under two
+struct OeRes { int32_t n_obs, n_under; };   // the entries behind the erase or the add; the points an erase left under two
 
 struct ObsEditBufs : MapFeature {
     DevBuf<uint8_t> flag;                             // [n_obs] the caller's erase flags (mo_map_erase_observations)
-    DevBuf<int32_t> keep, S;                          // [n_obs] 1 at an entry that stays; its exclusive scan
+    DevBuf<int32_t> keep, S;                          // [n_obs] 1 at an entry that stays; its exclusive scan (per entry: the map's keep / rank are per point)
     ResBlock<OeRes> res;
     // mo_map_add_observations
-    DevBuf<int32_t> ao_pt, ao_row, ao_claim, ao_cnt, ao_base, ao_total;
+    DevBuf<int32_t> ao_pt, ao_row, ao_claim;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) {
-        f(flag); f(keep); f(S); f(res); f(ao_pt); f(ao_row); f(ao_claim); f(ao_cnt); f(ao_base); f(ao_total);
+        f(flag); f(keep); f(S); f(res); f(ao_pt); f(ao_row); f(ao_claim);
     }
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(OBS_BLOCK) void k_oe_points(MapPts src, MapPts dst,
         dst.off[i] = na;
         under += nb - na < b - a && nb - na < 2;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { dst.off[n_pts] = total; st[ST_NPTS] = n_pts; st[ST_NOBS] = total; }   // (the next call's live counts)
+    if (blockIdx.x == 0 && threadIdx.x == 0) map_store_end(dst, st, n_pts, total);
     under = wave_sum_int(under);
     if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = under;
     __syncthreads();
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(OBS_BLOCK) void k_oe_entries(MapPts src, MapPts dst
 static int oe_reserve(mo_map* m, ObsEditBufs& b) {
     const size_t np = (size_t)m->n_pts, no = (size_t)m->n_obs;
     if (int rc = mo_reserve(m->c, b.keep, no, b.S, no, b.res)) return rc;
-    return map_pts_reserve(m, m->cur ^ 1, np, no, false);
+    return map_pts_reserve(m, m->cur ^ 1, np, no, false);   // (not rebuild_reserve: the scans here run over the entries, in keep and S)
 }
 
 // keep -> S and the two copies enqueued, the result block's download behind them (behind oe_reserve, the block zeroed in front)
@@ -113,7 +113,7 @@ static int oe_enqueue(mo_map* m, ObsEditBufs& b, const uint8_t* flag, const int3
 // behind the synchronisation: the copies flipped, the count taken
 static void oe_finish(mo_map* m, const OeRes& r, int32_t* n_erased, int32_t* n_under) {
     const int64_t gone = m->n_obs - r.n_obs;
-    if (gone) { m->cur ^= 1; m->n_obs = r.n_obs; }
+    if (gone) map_commit(m, m->n_pts, r.n_obs);
     *n_erased = (int32_t)gone; *n_under = r.n_under;
 }
 
@@ -174,20 +174,15 @@ __global__ __launch_bounds__(OBS_BLOCK) void k_obs_count(MapView v, int kf_pos, 
     cnt[i] = o1 - o0 + add;
 }
 
-// every field of every point into the other copy, the observations at their new offsets, the new one behind them
-__global__ __launch_bounds__(OBS_BLOCK) void k_obs_scatter(MapPts src, MapPts dst, int n_pts, const int32_t* __restrict__ claim, const int32_t* __restrict__ base,
-                                                           const int32_t* __restrict__ total, int kf_pos, const int32_t* __restrict__ row,
-                                                           int32_t* __restrict__ st) {
-    const int i = blockIdx.x * OBS_BLOCK + threadIdx.x;
-    if (i == 0) { dst.off[n_pts] = *total; st[ST_NPTS] = n_pts; st[ST_NOBS] = *total; }   // (the next call's live counts)
-    if (i >= n_pts) return;
-    map_point_copy(src, i, dst, i);
-    const int o0 = src.off[i], o1 = src.off[i + 1], ob = base[i];
-    dst.off[i] = ob;
-    for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; }
-    const int cl = claim[i];
-    if (cl != INT_MAX) { dst.okf[ob + o1 - o0] = kf_pos; dst.okp[ob + o1 - o0] = row[cl]; }
-}
+// the add as a rebuild: every point stays at its index with its entries as stored, a claimed point's new observation behind them
+struct ObsAdd : RebuildEdit {
+    static constexpr bool all_kept = true;
+    MapView map; const int32_t* claim; const int32_t* row; int kf_pos; OeRes* res;
+    __device__ void tail(int i, const MapPts& dst, int, int at) const {
+        const int cl = claim[i];
+        if (cl != INT_MAX) { dst.okf[at] = kf_pos; dst.okp[at] = row[cl]; }
+    }
+};
 
 extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32_t* point, const int32_t* row) {
     if (!m) return MO_ERR_ARG;
@@ -201,25 +196,19 @@ extern "C" int mo_map_add_observations(mo_map* m, int kf_pos, int n, const int32
     ObsEditBufs& b = map_feature<ObsEditBufs>(m);
     const size_t np = (size_t)m->n_pts;
     int rc;
-    if ((rc = mo_reserve(c, b.ao_pt, (size_t)n, b.ao_row, (size_t)n, b.ao_claim, np, b.ao_cnt, np, b.ao_base, np, b.ao_total, 4))) return rc;
-    const size_t new_obs = (size_t)m->n_obs + std::min<size_t>((size_t)n, np);
-    if ((rc = map_pts_reserve(m, m->cur ^ 1, np, new_obs, false))) return rc;
+    if ((rc = mo_reserve(c, b.ao_pt, (size_t)n, b.ao_row, (size_t)n, b.ao_claim, np, b.res))) return rc;
+    if ((rc = rebuild_reserve(m, np, (size_t)m->n_obs + std::min<size_t>((size_t)n, np)))) return rc;
     if ((rc = upload_pos_slot(m))) return rc;
     HIPCHK(c, hipMemcpyAsync(b.ao_pt, point, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.ao_row, row, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.ao_claim, INT_MAX, np, c->stream));
-    const MapPts src = m->P[m->cur].view(), dst = m->P[m->cur ^ 1].view();
+    const MapView v = map_view(m);
     const unsigned pblocks = (unsigned)((np + OBS_BLOCK - 1) / OBS_BLOCK);
     hipLaunchKernelGGL(k_obs_claim, dim3((unsigned)((n + OBS_BLOCK - 1) / OBS_BLOCK)), dim3(OBS_BLOCK), 0, c->stream, b.ao_pt, n, (int)np, b.ao_claim);
-    hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(OBS_BLOCK), 0, c->stream, map_view(m), kf_pos, b.ao_claim, b.ao_cnt);
+    hipLaunchKernelGGL(k_obs_count, dim3(pblocks), dim3(OBS_BLOCK), 0, c->stream, v, kf_pos, b.ao_claim, m->kobs);
     HIPCHK(c, hipGetLastError());
-    if ((rc = map_scan_excl(m, b.ao_cnt, b.ao_base, (int)np, b.ao_total))) return rc;
-    hipLaunchKernelGGL(k_obs_scatter, dim3(pblocks), dim3(OBS_BLOCK), 0, c->stream, src, dst, (int)np, b.ao_claim, b.ao_base, b.ao_total, kf_pos, b.ao_row, m->st);
-    HIPCHK(c, hipGetLastError());
-    int32_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, b.ao_total, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = rebuild_enqueue(m, ObsAdd{{}, v, b.ao_claim, b.ao_row, kf_pos, b.res}, nullptr)) || (rc = b.res.download(c))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    m->cur ^= 1;
-    m->n_obs = total;
+    map_commit(m, m->n_pts, b.res.host().n_obs);
     return MO_OK;
 }

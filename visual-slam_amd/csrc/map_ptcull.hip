@@ -10,14 +10,14 @@
 //             k_pc_note     one thread per point: seen (trk_project, trk_frustum), the flags, the record updated once
 //   decide    k_pc_decide   one thread per point: age, the positions that observe it, the reason, keep and the kept entry count
 //   erase     k_pc_flags    (mo_map_erase_points) keep and the kept entry count from the caller's mask
-//             map_scan_excl twice, k_pc_scatter: survivors in order into the other copy, entries as stored; remap.  With nothing removed
-//             the scatter writes remap alone and the host does not flip the copies.
+//             rebuild_enqueue (map_rebuild.h) with the edit PcErase: survivors in order into the other copy, entries as stored; remap.
+//             With nothing removed the rebuild writes remap alone and the host does not commit.
 // Integer atomics on flags and counts only, never on a record; the one floating-point decision is the f64 compare found < ratio * visible.
 #include <climits>
 #include <cmath>
 
 #include "common.h"
-#include "map_store.h"
+#include "map_rebuild.h"   // (map_store.h with it)
 #include "map_search.h"
 #include "pnp.h"
 
@@ -167,23 +167,14 @@ __global__ __launch_bounds__(PC_BLOCK) void k_pc_flags(MapPts src, int n_pts, co
     pc_block_add(c, &res->n_removed);
 }
 
-// remap of every point; with a removal, every survivor's fields and its entries as stored, in entry order, at its new index
-__global__ __launch_bounds__(PC_BLOCK) void k_pc_scatter(MapPts src, MapPts dst, int n_pts, const int32_t* __restrict__ keep, const int32_t* __restrict__ rank,
-                                                         const int32_t* __restrict__ obase, int32_t* __restrict__ remap, const PcRes* __restrict__ res,
-                                                         int32_t* __restrict__ st) {
-    const int i = blockIdx.x * PC_BLOCK + threadIdx.x;
-    if (i >= n_pts) return;
-    const bool k = keep[i] != 0;
-    const int r = rank[i];
-    remap[i] = k ? r : -1;
-    if (!res->n_removed) return;
-    if (i == 0) { dst.off[res->n_points] = res->n_obs; st[ST_NPTS] = res->n_points; st[ST_NOBS] = res->n_obs; }   // (the next call's live counts)
-    if (!k) return;
-    map_point_copy(src, i, dst, r);
-    const int ob = obase[i], o0 = src.off[i], o1 = src.off[i + 1];
-    dst.off[r] = ob;
-    for (int o = o0; o < o1; o++) { dst.okf[ob + o - o0] = src.okf[o]; dst.okp[ob + o - o0] = src.okp[o]; }
-}
+// the erase as a rebuild: remap of every point in front of the gate (a call that removes nothing still returns the identity); with a
+// removal, every survivor's fields and its entries as stored at its new index
+struct PcErase : RebuildEdit {
+    static constexpr bool side_first = true;
+    MapView map; PcRes* res; int32_t* remap;
+    __device__ bool changed() const { return res->n_removed != 0; }
+    __device__ void side_first_out(int i, bool kept, int r) const { remap[i] = kept ? r : -1; }
+};
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 static unsigned pc_blocks(size_t n) { return (unsigned)((n + PC_BLOCK - 1) / PC_BLOCK); }
@@ -272,27 +263,6 @@ static int pc_check(mo_map* m, const mo_map_ptcull_params* prm, const mo_map_ptc
     return MO_OK;
 }
 
-// keep / kobs -> rank / obase and the scatter into the other copy enqueued (the other copy reserved by the caller, res zeroed in front of
-// the kernel that wrote keep / kobs)
-static int pc_erase_enqueue(mo_map* m, PtCullBufs& b) {
-    mo_ctx* c = m->c;
-    const size_t np = (size_t)m->n_pts;
-    int rc;
-    if ((rc = map_scan_excl(m, m->keep, m->rank, (int)np, &b.res.p->n_points)) || (rc = map_scan_excl(m, m->kobs, m->obase, (int)np, &b.res.p->n_obs))) return rc;
-    hipLaunchKernelGGL(k_pc_scatter, dim3(pc_blocks(np)), dim3(PC_BLOCK), 0, c->stream, m->P[m->cur].view(), m->P[m->cur ^ 1].view(), (int)np, m->keep, m->rank,
-                       m->obase, b.remap, b.res, m->st);
-    HIPCHK(c, hipGetLastError());
-    mo_stage_mark(c, "ptcull_erase");
-    return MO_OK;
-}
-
-// behind the synchronisation: the copies flipped, the counts taken
-static void pc_erase_finish(mo_map* m, const PcRes& r) {
-    if (!r.n_removed) return;
-    m->cur ^= 1;
-    m->n_pts = r.n_points; m->n_obs = r.n_obs;
-}
-
 static int pc_cull(mo_map* m, const mo_map_ptcull_params* prm, mo_map_ptcull_out* out, bool erase) {
     mo_ctx* c = m->c;
     int rc;
@@ -306,8 +276,8 @@ static int pc_cull(mo_map* m, const mo_map_ptcull_params* prm, mo_map_ptcull_out
     HostClock clk(c);
     PtCullBufs& b = map_feature<PtCullBufs>(m);
     const size_t np = (size_t)m->n_pts;
-    if ((rc = mo_reserve(c, b.mask, np, b.reason, np, b.removed, np, b.remap, np, b.res, m->keep, np, m->kobs, np, m->rank, np, m->obase, np)) ||
-        (erase && (rc = map_pts_reserve(m, m->cur ^ 1, np, (size_t)m->n_obs, false))) || (rc = upload_pos_slot(m)))
+    if ((rc = mo_reserve(c, b.mask, np, b.reason, np, b.removed, np, b.remap, np, b.res)) ||
+        (rc = erase ? rebuild_reserve(m, np, (size_t)m->n_obs) : mo_reserve(c, m->keep, np, m->kobs, np)) || (rc = upload_pos_slot(m)))
         return rc;
     mo_stage_begin(c);
     HIPCHK(c, hipMemsetAsync(b.res, 0, sizeof(PcRes), c->stream));
@@ -317,7 +287,7 @@ static int pc_cull(mo_map* m, const mo_map_ptcull_params* prm, mo_map_ptcull_out
     hipLaunchKernelGGL(k_pc_decide, dim3(pc_stride_blocks(np)), dim3(PC_BLOCK), 0, c->stream, map_view(m), p, b.mask, b.reason, b.removed, m->keep, m->kobs, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "ptcull_decide");
-    if (erase && (rc = pc_erase_enqueue(m, b))) return rc;
+    if (erase && (rc = rebuild_enqueue(m, PcErase{{}, map_view(m), b.res, b.remap}, "ptcull_erase"))) return rc;
     if ((rc = b.res.download(c))) return rc;
     if (out->reason) HIPCHK(c, hipMemcpyAsync(out->reason, b.reason, np, hipMemcpyDeviceToHost, c->stream));
     if (out->removed) HIPCHK(c, hipMemcpyAsync(out->removed, b.removed, np, hipMemcpyDeviceToHost, c->stream));
@@ -326,7 +296,7 @@ static int pc_cull(mo_map* m, const mo_map_ptcull_params* prm, mo_map_ptcull_out
     const PcRes& r = b.res.host();
     out->n_tested = r.n_tested; out->n_removed = r.n_removed;
     for (int k = 0; k < 4; k++) out->n_reason[k] = r.n_reason[k];
-    if (erase) pc_erase_finish(m, r);
+    if (erase && r.n_removed) map_commit(m, r.n_points, r.n_obs);
     out->n_points = m->n_pts; out->n_obs = m->n_obs;
     return MO_OK;
 }
@@ -353,20 +323,18 @@ extern "C" int mo_map_erase_points(mo_map* m, const uint8_t* remove, int32_t* re
     HostClock clk(c);
     PtCullBufs& b = map_feature<PtCullBufs>(m);
     const size_t np = (size_t)m->n_pts;
-    if ((rc = mo_reserve(c, b.mask, np, b.remap, np, b.res, m->keep, np, m->kobs, np, m->rank, np, m->obase, np)) ||
-        (rc = map_pts_reserve(m, m->cur ^ 1, np, (size_t)m->n_obs, false)))
-        return rc;
+    if ((rc = mo_reserve(c, b.mask, np, b.remap, np, b.res)) || (rc = rebuild_reserve(m, np, (size_t)m->n_obs))) return rc;
     mo_stage_begin(c);
     HIPCHK(c, hipMemsetAsync(b.res, 0, sizeof(PcRes), c->stream));
     HIPCHK(c, hipMemcpyAsync(b.mask, remove, np, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_pc_flags, dim3(pc_stride_blocks(np)), dim3(PC_BLOCK), 0, c->stream, m->P[m->cur].view(), (int)np, b.mask, m->keep, m->kobs, b.res);
     HIPCHK(c, hipGetLastError());
-    if ((rc = pc_erase_enqueue(m, b)) || (rc = b.res.download(c))) return rc;
+    if ((rc = rebuild_enqueue(m, PcErase{{}, map_view(m), b.res, b.remap}, "ptcull_erase")) || (rc = b.res.download(c))) return rc;
     if (remap) HIPCHK(c, hipMemcpyAsync(remap, b.remap, np * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = map_sync(c, clk))) return rc;
     const PcRes& r = b.res.host();
     out->n_removed = r.n_removed;
-    pc_erase_finish(m, r);
+    if (r.n_removed) map_commit(m, r.n_points, r.n_obs);
     out->n_points = m->n_pts; out->n_obs = m->n_obs;
     return MO_OK;
 }

@@ -10,7 +10,8 @@
 //   MapView / map_view: the live map as every kernel receives it (by value);
 //   MatchView / map_match_point: the matcher's outputs read through a point_of table (restated only by lp_match of map_loop.hip, which says why);
 //   map_obs: the one reader of an observation; map_each_obs / map_observes: the walks over a point's valid observations;
-//   map_point_copy / map_life_new / map_life_merge: a point's own fields, its life record among them, through every rebuild;
+//   map_point_copy / map_life_new / map_life_merge: a point's own fields, its life record among them, through every rebuild (the
+//   rebuild itself - the scans, the one scatter kernel, the flip of the copies - is map_rebuild.h);
 //   map_point_of: the one rule of the point_of tables (k_point_of / map_launch_point_of in map_kernels.hip, k_fuse_prep);
 //   wave_sum / wave_sum_all / block_sum / block_max (f64, fixed order), wave_sum_int, wave_count_add, the block scans, sort_run, pose_split;
 //   host helpers: map_now, map_window_lo, map_int32_guard, map_sync, map_stage_frame.
@@ -108,7 +109,7 @@ struct mo_map {
     DevBuf<int32_t> kf_red;
     // scratch
     DevBuf<int32_t> st;                               // [ST_NWORDS] status
-    DevBuf<int32_t> keep, kobs, rank, obase;
+    DevBuf<int32_t> keep, kobs, rank, obase;          // [point] every rebuild's decision and its scans (map_rebuild.h); a chain holds one rebuild
     DevBuf<int32_t> part;                             // tile sums of the device-wide scan
     DevBuf<int32_t> ent_id;                           // id of the point of every observation entry (compacted map)
     DevBuf<int32_t> hist, hbase, first;
