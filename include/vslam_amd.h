@@ -1238,6 +1238,67 @@ int mo_map_set_vocabulary(mo_map*, mo_vocab*);
 int mo_map_query_keyframes(mo_map*, const mo_frame_ref* f, const mo_map_query_params*, mo_map_query_out*);
 int mo_map_relocalize_pre(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, int32_t n_pre, mo_map_reloc_out*);
 
+/* ---- Tracking against the reference keyframe (map_trackref.hip) ---------------------------------------------------------------------------
+ * mo_map_track_reference: the pose of a frame from its matches by appearance to ONE keyframe of the map (ORB-SLAM2's
+ * TrackReferenceKeyFrame: SearchByBoW, the rotation-consistency check, PoseOptimization): what a tracker runs when it has no velocity
+ * yet, or when the search by projection found too little.  It needs no good prior - pose0 only starts the refinement - and costs what a
+ * tracking call costs.  Reads the map, never changes it; needs a vocabulary (MO_ERR_ARG without one); the frame is given and staged like
+ * mo_map_track's.  One chain on the context stream, one synchronisation; integer atomics only: equal inputs give equal bytes.
+ * tests/trackref_restatement.py restates every rule below in numpy.
+ *   words         word[slot][row], the word of every keyframe row under the database's quantisation (lowest Hamming distance to a word,
+ *                 ties to the lower word index), kept by keyframe slot beside the term counts and made by the same lazy rule (a stale
+ *                 slot is quantised once, by the next call that needs it); the spare slot's are the staged frame's.  They survive a
+ *                 regrow of the database and a restride of the keyframe store.  mo_map_keyframe_words brings the stale rows up to date
+ *                 and copies the words of the keyframe at kf_pos (negative: from the end) to out [rows of that keyframe].
+ *   buckets       the frame's rows grouped by word, ascending row order within a word (a stable counting sort): woff [W + 1], wrows [n].
+ *   candidates    the rows r of the reference keyframe (kf_pos; negative counts from the end, -1 = the last keyframe; MO_ERR_INDEX out of
+ *                 range) that have a map point p = point_of[kf_pos][r]: the lowest point with a valid observation of (kf_pos, r), the
+ *                 table of mo_map_relocalize.  n_cand counts them.
+ *   search        candidate r walks the bucket of word[r] with the keyframe row's own descriptor (not the point's representative): best =
+ *                 the lowest Hamming distance (ties to the lower frame row), second = the next lowest distance; accepted when best <=
+ *                 max_dist and, if a second exists, (double)best <= ratio * (double)second; the accepted candidate claims frame row bq
+ *                 for its point: key[bq] = min(key[bq], best << 32 | p) - mo_map_track's search tail and conflict rule, unchanged.  It
+ *                 records cq[r] = bq and cd[r] = best (-1, -1 when it claimed nothing).  n_claims counts the candidates that claimed.
+ *   kf_row        of a claimed frame row q: the lowest candidate row r with cq[r] == q and (cd[r] << 32 | point_of[r]) == key[q].
+ *   orientation   only when check_orientation != 0 (leave it off for keypoints without angles).  For every claimed q:
+ *                 rot = (double)kf.angle[kf_row[q]] - (double)frame.angle[q]; if (rot < 0) rot += 360; bin = (int)rint(rot / 12.0);
+ *                 if (bin >= 30) bin -= 30.  hist[30] counts the bins (a bin outside 0 .. 29 - angles outside [0, 360) - is counted
+ *                 nowhere and is never kept).  The three highest bins, ties to the lower bin; the second is kept iff 10 * c2 >= c1, the
+ *                 third iff the second is kept and 10 * c3 >= c1; a bin of count 0 is never kept.  Claims in any other bin are dropped.
+ *                 (ORB-SLAM2's ComputeThreeMaxima over the 12-degree bins its histogram length of 30 intends.)  n_matches_raw counts the
+ *                 claims before this stage, n_matches after it.
+ *   pose          one pass of mo_map_track's refinement from pose0 over the matches, no retry: fewer than min_matches matches end the
+ *                 call without a refinement (ok = 0, pose = pose0).  ok = the pass was refined and has >= min_inliers inliers.
+ * An empty frame, a map without keyframes or points, a keyframe none of whose rows has a point: not ok, MO_OK.  A frame or keyframe above
+ * MO_BOW_MAX_ROWS: MO_ERR_UNSUPPORTED.  Stage marks trackref_words, trackref_prep, trackref_search, trackref_orient, trackref_refine. */
+typedef struct {
+    int32_t kf_pos;            /* the reference keyframe's position; negative counts from the end (-1) */
+    int32_t check_orientation; /* run the orientation stage (1) */
+    double scale_factor;       /* scales the information of an octave (1.2) */
+    double ratio;              /* best-to-second ratio (0.7) */
+    double chi2;               /* outlier threshold; the Huber width is its square root (5.991) */
+    int32_t max_dist;          /* ORB-SLAM2's TH_LOW (50) */
+    int32_t min_matches;       /* fewer matches: no refinement (15) */
+    int32_t min_inliers;       /* ok needs this many inliers (10) */
+} mo_map_trackref_params;
+typedef struct {
+    /* caller-allocated, may be NULL; n_q = keypoints of the frame */
+    int32_t* point;          /* [n_q] map point matched to each keypoint (-1: none) */
+    int32_t* dist;           /* [n_q] its Hamming distance (-1: none) */
+    uint8_t* inlier;         /* [n_q] final classification of the refinement (0 where it did not refine) */
+    int32_t* kf_row;         /* [n_q] the row of the reference keyframe the match came from (-1: none) */
+    /* filled by the call */
+    double pose[12];         /* [R | t] row-major: the refined pose, else pose0 */
+    int32_t n_cand, n_claims, n_matches_raw, n_matches, n_inliers;
+    int32_t hist[30];        /* the orientation histogram (zeros when the stage did not run) */
+    int32_t kept_bin[3];     /* the bins kept, highest first (-1: none) */
+    int32_t ok;              /* 1: refined with >= min_inliers inliers */
+    int32_t from_token;      /* 1: the frame was read from its resident slot */
+} mo_map_trackref_out;
+int mo_map_track_reference(mo_map*, const mo_frame_ref* f, const double K[9], const double pose0[12], const mo_map_trackref_params*,
+                           mo_map_trackref_out*);
+int mo_map_keyframe_words(mo_map*, int32_t kf_pos, int32_t* out);
+
 /* ---- Loop candidates (map_loop.hip) --------------------------------------------------------------------------------------------------------
  * "Which old keyframe, if any, does this keyframe close a loop with, and which map points of the two correspond": ORB-SLAM2's
  * KeyFrameDatabase::DetectLoopCandidates on the keyframe database above and on mo_map_covisibility's matrix, then the map-point matching

@@ -34,6 +34,16 @@ int bow_require(mo_map* m);
 // context stream inside the caller's stage set (marks bow_quantise, bow_hist, bow_score, bow_rank); no synchronisation
 int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel);
 
+// The per-row words of the database (valid behind bow_words_enqueue on the context stream): word [slot][stride], the word of every row
+// of every keyframe slot under the quantisation rule, and in the spare slot (m->kslots) those of the staged frame; W words.
+struct BowWords {
+    const uint16_t* word = nullptr;
+    int stride = 0, W = 0;
+};
+// every stale row of the database and the row of the frame staged in the spare slot (n rows) brought up to date, as the query does,
+// inside the caller's stage set with no stage mark of its own; enqueued, no synchronisation.  MO_ERR_UNSUPPORTED above MO_BOW_MAX_ROWS.
+int bow_words_enqueue(mo_map* m, int n, BowWords* out);
+
 // What the scoring of mo_map_loop_candidates (map_loop.hip) leaves on the device, valid behind bow_loop_score_enqueue on the context
 // stream: cnt = the row counts by keyframe slot as the database update uploaded them (frame `empty` has 0 rows), score [n_kf] and
 // common [n_kf] by keyframe position.

@@ -15,9 +15,10 @@
 
 struct BowBufs : MapFeature {
     mo_vocab* v = nullptr;
-    int Wp = 0, db_rows = 0;
+    int Wp = 0, db_rows = 0, word_rows = 0;
     DevBuf<uint16_t> db;                 // [db_rows][Wp] term counts by keyframe slot; the row of the spare slot is the query frame's
     DevBuf<long long> norm;              // [db_rows] sum of count * weight
+    DevBuf<uint16_t> word; int wstride = 0;   // [db_rows][wstride] the word of every row, by keyframe slot like db; the spare slot's are the staged frame's
     std::vector<uint32_t> done;          // by slot: the serial of the keyframe store (mo_map::kserial) the row was made from, 0: none
     std::vector<int32_t> h_lst;          // the slots quantised by the call in flight, the spare slot last
     // one block, built on the host and uploaded in one copy per call (the host knows every row count): cnt [kslots + 3] = the store's
@@ -30,8 +31,8 @@ struct BowBufs : MapFeature {
     DevBuf<int32_t> common;              // [n_kf] common words with the asking keyframe (mo_map_loop_candidates)
     DevBuf<int32_t> out_pos, out_n; DevBuf<double> out_score;
     DevBuf<int32_t> sel_qf, sel_tf, mrow;
-    // scratch: what every call's chain writes before it reads.  db and norm are state (the rows `done` vouches for are read by later
-    // calls); a DevBuf added above is named here or in this sentence
+    // scratch: what every call's chain writes before it reads.  db, norm and word are state (the rows `done` vouches for are read by
+    // later calls); a DevBuf added above is named here or in this sentence
     template <class F> void each_scratch(F f) {
         f(up); match.each_scratch(f); f(score); f(common); f(out_pos); f(out_n); f(out_score); f(sel_qf); f(sel_tf); f(mrow);
     }
@@ -47,10 +48,11 @@ __device__ __forceinline__ long long bow_block_sum(long long v, long long* red) 
 }
 
 // ---- k_bow_hist: the words of one frame -> its row of term counts and its norm; one workgroup per listed slot ---------------------------
-// LDS counters (one per word), then the row written with plain 16-byte vector stores (8 counts each).
+// LDS counters (one per word), then the row written with plain 16-byte vector stores (8 counts each).  The word of every row is kept
+// too (word [slot][wstride], uint16: W <= 8192): the rows mo_map_track_reference buckets and mo_map_keyframe_words hands out.
 __global__ __launch_bounds__(256) void k_bow_hist(const int32_t* __restrict__ lst, const int32_t* __restrict__ cnt, int stride,
                                                   const int32_t* __restrict__ qidx, int W, int Wp, const int32_t* __restrict__ weights,
-                                                  uint16_t* __restrict__ db, long long* __restrict__ norm) {
+                                                  uint16_t* __restrict__ db, long long* __restrict__ norm, uint16_t* __restrict__ word, int wstride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int32_t* s_cnt = (int32_t*)smem;
     long long* red = (long long*)(smem + (size_t)Wp * 4);
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(256) void k_bow_hist(const int32_t* __restrict__ ls
     for (int q = tid; q < n; q += 256) {
         const int w = qidx[2 * ((size_t)b * stride + q)];
         if ((unsigned)w < (unsigned)W) atomicAdd(&s_cnt[w], 1);
+        if (q < wstride) word[(size_t)slot * wstride + q] = (uint16_t)w;
     }
     __syncthreads();
     uint4* row = (uint4*)(db + (size_t)slot * Wp);
@@ -370,7 +373,8 @@ int bow_require(mo_map* m) {
 // every stale row and the frame's row brought up to date: one quantise launch (a pair per stale keyframe and one for the frame), one
 // histogram launch.  frame false (mo_map_loop_candidates: no frame is staged): the spare slot is in neither list and its row stays as
 // it is; with no stale keyframe nothing is launched, the two stage marks are still set.
-static int bow_update(mo_map* m, int n, bool frame = true) {
+// marks false (mo_map_track_reference, which sets one mark of its own): neither mark is set.
+static int bow_update(mo_map* m, int n, bool frame = true, bool marks = true) {
     mo_ctx* c = m->c;
     BowBufs& b = *map_feature_if<BowBufs>(m);
     const mo_vocab& v = *b.v;
@@ -392,6 +396,16 @@ static int bow_update(mo_map* m, int n, bool frame = true) {
         if ((rc = b.db.regrow(c, (size_t)nr * b.Wp, keep * b.Wp)) || (rc = b.norm.regrow(c, (size_t)nr, keep))) return rc;
         b.db_rows = nr;
     }
+    if (b.db_rows > b.word_rows || row > b.wstride) {   // ... and so do the words, which also follow a restride of the store
+        DevBuf<uint16_t> w2;
+        const int ns = std::max(row, b.wstride);
+        if ((rc = w2.regrow(c, (size_t)b.db_rows * ns, 0))) return rc;
+        const size_t keep = (size_t)std::min(b.word_rows, m->n_slots);
+        if (keep && b.wstride)
+            HIPCHK(c, hipMemcpy2DAsync(w2, (size_t)ns * 2, b.word, (size_t)b.wstride * 2, (size_t)b.wstride * 2, keep, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        b.word.swap(w2); b.wstride = ns; b.word_rows = b.db_rows;   // (the old block is freed here, behind the synchronisation)
+    }
     const int stride = std::max(row, v.W);   // the matcher clips both sides of a pair to its output stride
     const size_t out_n = (size_t)n_list * stride;
     b.h_up.assign((size_t)rows + 2 + 2 * (size_t)n_list, 0);
@@ -405,13 +419,13 @@ static int bow_update(mo_map* m, int n, bool frame = true) {
     // train frame `rows` of a stride of 0 bytes: the words themselves
     if ((rc = match_launch_pairs(c, m->kdesc, v.words, (size_t)row * 32, 0, b.cnt, b.lst, b.ltf, 0, 0, n_list, stride, -1.0, b.match.idx, b.match.dist, b.match.pass)))
         return rc;
-    mo_stage_mark(c, "bow_quantise");
+    if (marks) mo_stage_mark(c, "bow_quantise");
     if (n_list > 0) {
         hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.match.idx, v.W, b.Wp,
-                           v.weights, b.db, b.norm);
+                           v.weights, b.db, b.norm, b.word, b.wstride);
         HIPCHK(c, hipGetLastError());
     }
-    mo_stage_mark(c, "bow_hist");
+    if (marks) mo_stage_mark(c, "bow_hist");
     for (int i = 0; i < n_list - (frame ? 1 : 0); i++) b.done[b.h_lst[i]] = m->kserial[b.h_lst[i]];
     return MO_OK;
 }
@@ -446,6 +460,35 @@ int bow_select_enqueue(mo_map* m, int n, int n_pre, BowSel* sel) {
 }
 
 int bow_update_enqueue(mo_map* m) { return bow_update(m, 0, false); }
+
+int bow_words_enqueue(mo_map* m, int n, BowWords* out) {
+    if (int rc = bow_update(m, n, true, false)) return rc;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
+    out->word = b.word; out->stride = b.wstride; out->W = b.v->W;
+    return MO_OK;
+}
+
+extern "C" int mo_map_keyframe_words(mo_map* m, int32_t kf_pos, int32_t* out) {
+    if (!m) return MO_ERR_ARG;
+    mo_ctx* c = m->c;
+    if (!out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
+    int rc;
+    if ((rc = bow_require(m))) return rc;
+    const int n_kf = (int)m->pos_slot.size();
+    const int pos = kf_pos < 0 ? kf_pos + n_kf : kf_pos;
+    if (pos < 0 || pos >= n_kf) return mo_fail(c, MO_ERR_INDEX, "keyframe position out of range");
+    MAP_ENTER(m);
+    HostClock clk(c);
+    mo_stage_begin(c);
+    if ((rc = bow_update(m, 0, false))) return rc;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
+    const int slot = m->pos_slot[pos], n = m->h_kcnt[slot];
+    std::vector<uint16_t> h((size_t)n);
+    if (n) HIPCHK(c, hipMemcpyAsync(h.data(), b.word + (size_t)slot * b.wstride, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = map_sync(c, clk))) return rc;
+    for (int i = 0; i < n; i++) out[i] = h[i];
+    return MO_OK;
+}
 
 int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w, BowLoop* out) {
     mo_ctx* c = m->c;

@@ -58,18 +58,27 @@ __device__ __forceinline__ bool trk_active(const TrackRes* res, int attempt) {
 // The tail of every search: candidate point i (descriptor rep + 32 i) against the keypoints its window walk visits - walk(visit) is
 // trk_window or trk_window_oct with the candidate's pixel, radius and octaves bound - the best and second distance, the max_dist and
 // ratio gates, and the claim on the best keypoint by a 64-bit atomicMin of (dist << 32) | point.
-template <class Walk> __device__ __forceinline__ void trk_claim(const TrackPrm& prm, int i, const uint8_t* __restrict__ rep, const uint8_t* __restrict__ fdesc,
-                                                                unsigned long long* __restrict__ key, Walk walk) {
-    const uint8_t* d = rep + (size_t)i * 32;
+// trk_claim_as: the same tail for a candidate whose descriptor d is not its point's representative (mo_map_track_reference: a keyframe
+// row claims for the point i it observes); returns the keypoint claimed, its distance in *dist, or -1 with *dist = -1.
+template <class Walk> __device__ __forceinline__ int trk_claim_as(const TrackPrm& prm, int i, const uint8_t* __restrict__ d, const uint8_t* __restrict__ fdesc,
+                                                                  unsigned long long* __restrict__ key, Walk walk, int* dist) {
     int bd = INT_MAX, bq = INT_MAX, sd = INT_MAX;
+    *dist = -1;
     walk([&](int q, const mo_keypoint&, double, double) {
         const int dist = trk_ham(d, fdesc + (size_t)q * 32), was = bd;
         if (trk_take(dist, q, bd, bq)) sd = was;
         else if (dist < sd) sd = dist;
     });
-    if (bd == INT_MAX || bd > prm.max_dist) return;
-    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return;
+    if (bd == INT_MAX || bd > prm.max_dist) return -1;
+    if (sd != INT_MAX && !((double)bd <= prm.ratio * (double)sd)) return -1;
     atomicMin(key + bq, ((unsigned long long)(unsigned)bd << 32) | (unsigned)i);
+    *dist = bd;
+    return bq;
+}
+template <class Walk> __device__ __forceinline__ void trk_claim(const TrackPrm& prm, int i, const uint8_t* __restrict__ rep, const uint8_t* __restrict__ fdesc,
+                                                                unsigned long long* __restrict__ key, Walk walk) {
+    int dist;
+    trk_claim_as(prm, i, rep + (size_t)i * 32, fdesc, key, walk, &dist);
 }
 
 // ---- the single-workgroup stages, one workgroup per frame of fr (map_track.hip), enqueued on the context stream -----------------------

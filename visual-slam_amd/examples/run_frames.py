@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes]]
 """
 import argparse
 import os
@@ -123,6 +123,9 @@ def main(argv=None):
                     "relocalization and saved there")
     ap.add_argument("--reloc-preselect", type=int, default=0, help="with --vocabulary: N > 0: relocalize matches the frame only against the N "
                     "keyframes the vocabulary query ranks first (LocalMapper.relocalize(preselect=N))")
+    ap.add_argument("--track-reference", action="store_true", help="with --map --track-map --vocabulary: when the search by projection fails, "
+                    "the frame is tracked against the last keyframe by appearance (LocalMapper.track_reference_keyframe) and the local map is "
+                    "tracked from that pose; the essential-matrix step and --relocalize come only after that")
     ap.add_argument("--detect-loops", action="store_true", help="with --map --vocabulary: after each keyframe, look for a loop (LocalMapper.detect_loop: "
                     "place-recognition candidates on the covisibility graph, three consistent detections in a row, map-point matches); one "
                     "line per keyframe with candidates, one when a loop is found")
@@ -189,8 +192,10 @@ def main(argv=None):
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
     if args.relocalize and not args.map:
         ap.error("--relocalize needs --map")
-    if args.vocabulary and not ((args.relocalize or args.detect_loops) and args.map):
-        ap.error("--vocabulary needs --map and --relocalize or --detect-loops")
+    if args.vocabulary and not ((args.relocalize or args.detect_loops or args.track_reference) and args.map):
+        ap.error("--vocabulary needs --map and --relocalize, --detect-loops or --track-reference")
+    if args.track_reference and not (args.map and args.track_map and args.vocabulary):
+        ap.error("--track-reference needs --map, --track-map and --vocabulary")
     if args.detect_loops and not args.vocabulary:
         ap.error("--detect-loops needs --map and --vocabulary")
     if args.loop_global_ba and not args.detect_loops:
@@ -234,6 +239,7 @@ def main(argv=None):
     n_cull = [0, 0]      # --cull-keyframes: calls, keyframes removed
     n_grow = [0, 0, 0]   # --grow-neighbours: calls, points created, their observations
     n_ptcull = [0, 0, 0, 0]   # --cull-points: frames noted, culls, points removed, points tested
+    n_trackref = [0]   # --track-reference: frames it gave a pose
     recent = []   # --track-map: the last two poses, for the constant-velocity prediction
     n_loop = [0, 0]   # --detect-loops: calls, loops found
     seeds = [None]   # --covisible: the previous frame's matched map points (indices into the map as it stands: dropped when the map changes)
@@ -354,6 +360,19 @@ def main(argv=None):
             seeds[0] = info["point"] if ok else None
         else:
             ok, T, info = mapper.track_local_map(kps, desc, pred, **frustum_kw)
+        if not ok and args.track_reference:   # ORB-SLAM2's TrackReferenceKeyFrame: the last keyframe by appearance, then the local map from its pose
+            ensure_vocabulary(idx)
+            if mapper.vocabulary is not None:
+                rok, rT, rinfo = mapper.track_reference_keyframe(kps, desc)
+                print("frame %d: track reference keyframe %s, %d candidates, %d matches (%d before the orientation check), %d inliers"
+                      % (idx, "ok" if rok else "failed", rinfo["n_cand"], rinfo["n_matches"], rinfo["n_matches_raw"], rinfo["n_inliers"]))
+                if rok:
+                    n_trackref[0] += 1
+                    if args.covisible:
+                        ok, T, info = mapper.track_local_map(kps, desc, rT, local="covisible", seed_points=rinfo["point"], **frustum_kw)
+                        seeds[0] = info["point"] if ok else None
+                    else:
+                        ok, T, info = mapper.track_local_map(kps, desc, rT, **frustum_kw)
         if idx % 5 == 0:
             print("frame %d: track map %s, %d matches, %d inliers, t = %s" % (idx, "ok" if ok else "failed", info["pass_matches"][-1] if
                   info["n_pass_run"] else 0, info["pass_inliers"][-1] if info["n_pass_run"] else 0, np.round(T[:3, 3], 3)))

@@ -221,6 +221,17 @@ class MapQueryOut(C.Structure):
     _fields_ = [("pos", C.c_void_p), ("score", C.c_void_p), ("n", C.c_int32), ("from_token", C.c_int32)]
 
 
+class MapTrackRefParams(C.Structure):
+    _fields_ = [("kf_pos", C.c_int32), ("check_orientation", C.c_int32), ("scale_factor", C.c_double), ("ratio", C.c_double), ("chi2", C.c_double),
+                ("max_dist", C.c_int32), ("min_matches", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+class MapTrackRefOut(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("dist", C.c_void_p), ("inlier", C.c_void_p), ("kf_row", C.c_void_p), ("pose", C.c_double * 12),
+                ("n_cand", C.c_int32), ("n_claims", C.c_int32), ("n_matches_raw", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32),
+                ("hist", C.c_int32 * 30), ("kept_bin", C.c_int32 * 3), ("ok", C.c_int32), ("from_token", C.c_int32)]
+
+
 class MapLoopParams(C.Structure):
     _fields_ = [("kf_pos", C.c_int32), ("min_weight", C.c_int32), ("n_best", C.c_int32), ("max_cand", C.c_int32), ("ratio", C.c_double)]
 
@@ -422,6 +433,8 @@ SIGNATURES = {
     "mo_map_set_vocabulary": (_i, [_vp, _vp]),
     "mo_map_query_keyframes": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "mo_map_track_reference": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mo_map_keyframe_words": (_i, [_vp, C.c_int32, _vp]),
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
     "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -958,6 +958,55 @@ class LocalMapper:
             info["ref_keyframe"] = int(lout.ref)
         return bool(out.ok), T, info
 
+    def keyframe_words(self, kf_position):
+        """The vocabulary word of every row of the keyframe at kf_position (negative: from the end), int32 [rows], as the keyframe
+        database holds them (mo_map_keyframe_words: stale keyframes are quantised first).  Needs a vocabulary."""
+        n_kf = len(self.keyframes)
+        pos = int(kf_position) + n_kf if int(kf_position) < 0 else int(kf_position)
+        if not 0 <= pos < n_kf:
+            raise IndexError("keyframe position out of range")
+        rows = int(self.keyframes[pos]._rows)
+        out = np.zeros(max(rows, 1), np.int32)
+        self._check(self.lib.mo_map_keyframe_words(self._h, pos, V._ptr(out)))
+        return out[:rows]
+
+    def track_reference_keyframe(self, keypoints, descriptors, kf_position=-1, pose=None, max_dist=50, ratio=0.7, check_orientation=True,
+                                 scale_factor=1.2, chi2=5.991, min_matches=15, min_inliers=10):
+        """The pose of a frame from its matches by appearance to one keyframe (ORB-SLAM2's TrackReferenceKeyFrame;
+        mo_map_track_reference in include/vslam_amd.h states the rules): the keyframe rows that have a map point are matched to the
+        frame rows of the same vocabulary word, the matches are checked for a consistent rotation, and the pose is refined from them.
+        The step between track_local_map, which needs a good predicted pose, and relocalize, which matches against many keyframes: it
+        needs no good prior and costs what a tracking call costs.  Needs a vocabulary; the map is not changed.
+        kf_position: the reference keyframe (negative: from the end).  pose: the 4x4 the refinement starts from, by default the
+        keyframe's stored pose.  check_orientation=False for keypoints without angles (angle -1).  The frame is given like relocalize's.
+        Returns (ok, pose, info) shaped like track_local_map's: info holds per keypoint `point`, `dist`, `inlier` and `kf_row` (the
+        keyframe row of the match, -1: none), the counts `n_cand`, `n_claims`, `n_matches_raw`, `n_matches`, `n_inliers`, the
+        orientation histogram `hist` [30] with `kept_bin` [3] (-1: none), and `from_token`; `point` and `inlier` feed
+        add_keyframe(..., tracked=) and note_tracking as track_local_map's do."""
+        n_kf = len(self.keyframes)
+        pos = int(kf_position)
+        if pose is None:
+            at = pos + n_kf if pos < 0 else pos
+            pose = self.keyframes[at]["pose"] if 0 <= at < n_kf else np.eye(4)
+        ref, n, _keep = self._frame_ref(keypoints, descriptors)
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        pose0 = np.ascontiguousarray(np.asarray(pose, np.float64)[:3, :4]).reshape(12)
+        point = np.full(max(n, 1), -1, np.int32)
+        dist = np.full(max(n, 1), -1, np.int32)
+        inlier = np.zeros(max(n, 1), np.uint8)
+        kf_row = np.full(max(n, 1), -1, np.int32)
+        prm = V.MapTrackRefParams(pos, int(bool(check_orientation)), float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches),
+                                  int(min_inliers))
+        out = V.MapTrackRefOut(point.ctypes.data, dist.ctypes.data, inlier.ctypes.data, kf_row.ctypes.data)
+        self._check(self.lib.mo_map_track_reference(self._h, C.byref(ref), V._ptr(K), V._ptr(pose0), C.byref(prm), C.byref(out)))
+        T = np.eye(4)
+        T[:3, :] = np.array(out.pose).reshape(3, 4)
+        info = {"point": point[:n], "dist": dist[:n], "inlier": inlier[:n].astype(bool), "kf_row": kf_row[:n],
+                "n_cand": int(out.n_cand), "n_claims": int(out.n_claims), "n_matches_raw": int(out.n_matches_raw), "n_matches": int(out.n_matches),
+                "n_inliers": int(out.n_inliers), "hist": np.array(out.hist, np.int32), "kept_bin": np.array(out.kept_bin, np.int32),
+                "from_token": bool(out.from_token)}
+        return bool(out.ok), T, info
+
     def track_local_map_batch(self, frames, poses, window=10, radii=(15.0, 4.0), scale_factor=1.2, max_dist=100, ratio=0.8, chi2=5.991,
                               min_matches=20, min_inliers=30, image_size=None):
         """track_local_map for many frames in one device chain (mo_map_track_batch in include/vslam_amd.h states the rules): the cameras
