@@ -1169,6 +1169,71 @@ int mo_map_points_bad(mo_map*, const mo_map_ptcull_params*, mo_map_ptcull_out*);
 int mo_map_erase_points(mo_map*, const uint8_t* remove, int32_t* remap, mo_map_pterase_out*);
 int mo_map_cull_points(mo_map*, const mo_map_ptcull_params*, mo_map_ptcull_out*);
 
+/* ---- Snapshot: the whole state of a device map as host arrays, and a map made from them (map_snapshot.hip) -----------------------------
+ * mo_map_export writes the map in a canonical form, mo_map_import makes a map from one; an imported map gives the bytes the exported one
+ * gives, for every call above and for every later edit.  Additive: no call above launches anything different.
+ *
+ * The canonical form: keyframes in position order, their rows packed (no row stride, no dead slots).  It does not depend on capacities,
+ * on which copy of the double-buffered store or lists is live, or on how often the store was regrown or restrided.
+ *   dims          n_kf keyframes; kf_rows = sum of kf_cnt; n_pts, n_obs; list_rows and list_ids (rows and entries of the per-keyframe lists of
+ *                 the last cull; list_off has list_rows + 1 entries, none when list_rows == 0); kf_stored = keyframes ever stored (the
+ *                 ordinal counter: mo_map_point_life's now is kf_stored - 1, 0 on a map that never stored one); id_bound; the two keyframe
+ *                 images' w, h, ch and bytes (= w * h * ch) and img_cur, the one mo_map_grow reads and the next mo_map_add_keyframe
+ *                 colours its points from; st_live = the status words {points, observations, new points} that carry over between calls.
+ *   keyframes     kf_cnt [n_kf]; kf_ord [n_kf] the ordinal of each (strictly increasing: positions keep creation order); kf_kps [kf_rows]
+ *                 mo_keypoint; kf_desc [kf_rows][32]; kf_P [n_kf][12] f64.
+ *   points        xyz [n_pts][3] f32, col [n_pts][3], id, dref_kf, dref_row [n_pts], obs_off [n_pts + 1], obs_kf, obs_kp [n_obs], life
+ *                 [n_pts][4].  dref_kf of a point the library made is the ordinal of the keyframe its descriptor came from; the library
+ *                 never reads dref_* and takes them as given.
+ *   lists, images list_off, list_ids, kf_red [list_rows], img[2] [img_bytes].
+ *   stale entries observation entries with negative keys, or positions or rows that do not exist, are state (every reader skips them): they
+ *                 round-trip unchanged.
+ *   not state     the spare slot, every scratch buffer, every feature's scratch, the keyframe database and the per-row words (after an
+ *                 import every slot is stale by the serial rule: the next query recounts it), an attached vocabulary.
+ *
+ * mo_map_snapshot_dims: the sizes a caller allocates for (one 4-byte read from the device for list_ids).
+ * mo_map_export: every array filled.  dims comes in as mo_map_snapshot_dims filled it, and the arrays are caller-allocated for its sizes;
+ *   an array whose count is 0 may be NULL.  The keyframe rows are gathered from the slot-strided store by one launch for the keypoints
+ *   and one for the descriptors, everything else is one copy per array; one chain on the context stream, one synchronisation.  The map
+ *   is read, never changed.  Dims that are not the map's return MO_ERR_CAPACITY, and the arrays then hold nothing to rely on.
+ * mo_map_import: a new map in *out with capacities the larger of what is asked (as mo_map_create) and what the snapshot needs; slots ==
+ *   keyframes afterwards (mo_map_sizes out[5] == out[0]: dead slots are shed), ordinals and now are the snapshot's.  The snapshot is
+ *   checked on the host before anything is uploaded or launched (csrc/snapshot.h lists every rule with the reader that needs it); a
+ *   violation returns MO_ERR_ARG with the rule's text in mo_last_error, *out stays NULL, nothing leaks and the context stays usable. */
+typedef struct {
+    int32_t n_kf, list_rows;
+    int64_t kf_rows, n_pts, n_obs, list_ids;
+    int64_t kf_stored, id_bound;
+    int32_t img_w[2], img_h[2], img_ch[2];
+    int32_t img_cur;
+    int32_t st_live[3];
+    int64_t img_bytes[2];
+} mo_map_snapshot_dims_t;   /* (the _t: C keeps typedefs and functions in one namespace, and the call below has the name) */
+typedef struct {
+    mo_map_snapshot_dims_t dims;
+    int32_t* kf_cnt;
+    int32_t* kf_ord;
+    mo_keypoint* kf_kps;
+    uint8_t* kf_desc;
+    double* kf_P;
+    float* xyz;
+    uint8_t* col;
+    int32_t* id;
+    int32_t* dref_kf;
+    int32_t* dref_row;
+    int32_t* obs_off;
+    int32_t* obs_kf;
+    int32_t* obs_kp;
+    int32_t* life;
+    int32_t* list_off;
+    int32_t* list_ids;
+    int32_t* kf_red;
+    uint8_t* img[2];
+} mo_map_snapshot;
+int mo_map_snapshot_dims(mo_map*, mo_map_snapshot_dims_t*);
+int mo_map_export(mo_map*, mo_map_snapshot*);
+int mo_map_import(mo_ctx*, const mo_map_snapshot*, int kf_slots, int kf_rows, int64_t pts_cap, int64_t obs_cap, mo_map** out);
+
 /* ---- Place recognition: a binary vocabulary, the keyframe database of a map, relocalization with preselection (bow.hip) ----------------
  * "Which keyframes look like this frame": DBoW2's L1 score of tf-idf vectors over a flat vocabulary of binary words.  Everything is
  * integer work except the logarithm of the weights (host, once per training) and the one division of the score; tests/bow_restatement.py

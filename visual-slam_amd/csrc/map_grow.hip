@@ -319,7 +319,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_grow_points(GrowPrm prm, const Gro
 __global__ __launch_bounds__(GR_BLOCK) void k_grow_append(GrowPrm prm, const GrowPair* __restrict__ pairs, const mo_keypoint* __restrict__ kkps,
                                                            const int32_t* __restrict__ frow, const int32_t* __restrict__ prop, const double* __restrict__ Xo,
                                                            const int32_t* __restrict__ isnew, const int32_t* __restrict__ rank, const int32_t* __restrict__ obase,
-                                                           const uint8_t* __restrict__ img, int w, int h, int ch, int n0, int o0, int born, MapPts dst,
+                                                           const uint8_t* __restrict__ img, int w, int h, int ch, int n0, int o0, int born, int tgt_ord, MapPts dst,
                                                            double* __restrict__ outX, int32_t* __restrict__ point, int32_t* __restrict__ st,
                                                            const GrowRes* __restrict__ res) {
     const int n_new = res->n_new;
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_grow_append(GrowPrm prm, const Gro
     }
     dst.col[(size_t)i * 3] = c0; dst.col[(size_t)i * 3 + 1] = c1; dst.col[(size_t)i * 3 + 2] = c2;
     dst.id[i] = i;
-    dst.dkf[i] = prm.tgt.slot; dst.drow[i] = row1;
+    dst.dkf[i] = tgt_ord; dst.drow[i] = row1;   // (the target's ordinal: its slot, except on an imported map)
     map_life_new(dst, i, born);
     int o = o0 + obase[f];
     dst.off[i] = o;
@@ -421,7 +421,7 @@ extern "C" int mo_map_grow(mo_map* m, const double* K, const double* poses, cons
     const bool has_img = m->img[ib] && m->img_w[ib] > 0;
     hipLaunchKernelGGL(k_grow_append, dim3(rblocks), dim3(GR_BLOCK), 0, c->stream, p, b.pairs, m->kkps, b.frow, b.prop, b.X, m->keep, m->rank, m->obase,
                        has_img ? m->img[ib].p : m->kdesc.p, has_img ? m->img_w[ib] : 0, has_img ? m->img_h[ib] : 0, has_img ? m->img_ch[ib] : 1, (int)np,
-                       (int)m->n_obs, map_now(m), dst, b.outX, b.point, m->st, b.res);
+                       (int)m->n_obs, map_now(m), n_kf ? m->slot_ord[tslot] : 0, dst, b.outX, b.point, m->st, b.res);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "grow_points");
     if ((rc = b.res.download(c))) return rc;

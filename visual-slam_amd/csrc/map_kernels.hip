@@ -85,7 +85,7 @@ int map_scan_excl(mo_map* m, const int32_t* in, int32_t* out, int n, int32_t* d_
 // midx: MatchBufs::idx of the one pair, midx[2 * q] the best neighbour of query q (the layout is emit_match's, match_kernels.hip).
 __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__ inl, const int32_t* __restrict__ midx, const float* __restrict__ gpts,
                                                      const double* __restrict__ F, const mo_keypoint* __restrict__ qkps, const int32_t* __restrict__ qcnt,
-                                                     const uint8_t* __restrict__ img, int w, int h, int ch, int prev_id, int cur_id, int prev_slot,
+                                                     const uint8_t* __restrict__ img, int w, int h, int ch, int prev_id, int cur_id, int prev_ord,
                                                      int born, MapPts dst, int32_t* __restrict__ st) {
     __shared__ int lw[40];
     const int nq = *qcnt;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(1024) void k_map_append(const uint8_t* __restrict__
             }
             dst.col[(size_t)i * 3 + 0] = c0; dst.col[(size_t)i * 3 + 1] = c1; dst.col[(size_t)i * 3 + 2] = c2;
             dst.id[i] = i;                             // len(self.map_points) at creation
-            dst.dkf[i] = prev_slot; dst.drow[i] = q;
+            dst.dkf[i] = prev_ord; dst.drow[i] = q;      // (the ordinal: the slot, except on an imported map)
             map_life_new(dst, i, born);
             const int o = o0 + 2 * (added + r);
             dst.off[i] = o;
@@ -497,6 +497,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
     m->h_kcnt.push_back(n);
     m->kserial.resize((size_t)slot + 1, 0); m->kserial[slot]++;
     m->n_slots = slot + 1;
+    m->slot_ord.resize((size_t)slot + 1); m->slot_ord[slot] = (int32_t)m->kf_stored++;
     m->pos_slot.push_back(slot);
     const int n_kf = (int)m->pos_slot.size();
     // the image of this keyframe (the colours of the points the NEXT keyframe grows)
@@ -536,7 +537,7 @@ extern "C" int mo_map_add_keyframe(mo_map* m, const mo_frame_ref* f, const doubl
         const int pi = m->img_cur ^ 1;  // the previous keyframe's image
         if (!m->img[pi]) { m->img_w[pi] = m->img_h[pi] = 0; }
         hipLaunchKernelGGL(k_map_append, dim3(1), dim3(1024), 0, c->stream, m->inl, m->match.idx, m->gpts, m->F, m->kkps + (size_t)ps * rows, m->kcnt + ps,
-                           m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, ps, map_now(m),
+                           m->img[pi] ? m->img[pi].p : m->kdesc.p, m->img_w[pi], m->img_h[pi], m->img_ch[pi], n_kf - 2, n_kf - 1, m->slot_ord[ps], map_now(m),
                            m->P[m->cur].view(), m->st);
         HIPCHK(c, hipGetLastError());
         mo_stage_mark(c, "map_append");

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip and map_gba.hip (bundle adjustment; ba_problem.h is what those two share), map_obs.hip (added and erased observations), map_fuse.hip (fusion
-// of duplicate points) and map_correct.hip (loop correction; map_merge.h is what those two share), map_sim3.hip and map_confirm.hip (loop alignment and confirmation; sim3_device.h is what those two share), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase) and map_io.hip (PLY text).
+// of duplicate points) and map_correct.hip (loop correction; map_merge.h is what those two share), map_sim3.hip and map_confirm.hip (loop alignment and confirmation; sim3_device.h is what those two share), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase), map_io.hip (PLY text) and map_snapshot.hip (export / import of the whole state).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
 //   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),
@@ -94,6 +94,11 @@ struct mo_map {
     std::vector<int32_t> h_kcnt;
     std::vector<uint32_t> kserial;                    // by slot: bumped whenever mo_map_add_keyframe stores rows there (the keyframe database's staleness test)
     std::vector<int32_t> pos_slot;                    // keyframe position -> slot
+    // Ordinals: the k-th keyframe ever stored has ordinal k (include/vslam_amd.h, the life record).  On a map that grew in this process
+    // ordinal == slot; a map made by mo_map_import has its slots packed (slot == position then) and keeps the ordinals of the map it
+    // was exported from.  kf_stored: keyframes ever stored (map_now); slot_ord: by slot, what a new point's dref_kf names.
+    int64_t kf_stored = 0;
+    std::vector<int32_t> slot_ord;
     DevBuf<int32_t> d_pos_slot;
     // the previous and the new keyframe image (colours of the grown points)
     DevBuf<uint8_t> img[2]; int img_w[2] = {0, 0}, img_h[2] = {0, 0}, img_ch[2] = {0, 0};
@@ -338,9 +343,9 @@ int map_pts_reserve(mo_map* m, int which, size_t pcap, size_t ocap, bool keep);
 int map_launch_point_of(mo_map* m, int lo_pos, int n_tab_kf, int32_t* tab);
 
 // ---- host helpers of the calls ---------------------------------------------------------------------------------------------------
-// the ordinal of the last stored keyframe (0 on a map without one): slots are handed out in creation order and never reused, so the slot
-// count is the number of keyframes stored so far, whatever was removed since (ORB-SLAM2's mnId)
-inline int map_now(const mo_map* m) { return m->n_slots > 0 ? m->n_slots - 1 : 0; }
+// the ordinal of the last stored keyframe (0 on a map without one): the number of keyframes stored so far, whatever was removed since
+// (ORB-SLAM2's mnId).  Kept apart from the slot count: an imported map has fewer slots than its history has keyframes.
+inline int map_now(const mo_map* m) { return m->kf_stored > 0 ? (int)(m->kf_stored - 1) : 0; }
 // the first position of a window of the last `window` keyframes (0: all of them)
 inline int map_window_lo(int window, int n_kf) { return window > 0 && window < n_kf ? n_kf - window : 0; }
 // points and observations stay below half of int32 (sums of two of them are formed in int)

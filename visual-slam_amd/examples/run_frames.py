@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes] [--save-state FILE] [--load-state FILE]]
 """
 import argparse
 import os
@@ -171,6 +171,10 @@ def main(argv=None):
     ap.add_argument("--ba-erase-outliers", action="store_true", help="with --local-ba: the observations a bundle adjustment ends with as outliers are "
                     "erased from the map on the device (LocalMapper.bundle_adjust(erase_outliers=True)); with --cull-points the cull that follows "
                     "removes the points left under-observed")
+    ap.add_argument("--save-state", default="", help="with --map: FILE the whole mapper is written to at the end (LocalMapper.save_state: the device "
+                    "map's snapshot, the keyframes, the vocabulary), to localise in later with --load-state")
+    ap.add_argument("--load-state", default="", help="with --map: start from the mapper saved in FILE (LocalMapper.load_state) instead of initialising; "
+                    "with --relocalize or --track-map the first frame is relocalised against it, otherwise tracking goes on from its last keyframe's pose")
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
@@ -192,6 +196,8 @@ def main(argv=None):
         return run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0)
     if args.relocalize and not args.map:
         ap.error("--relocalize needs --map")
+    if (args.save_state or args.load_state) and not args.map:
+        ap.error("--save-state and --load-state need --map")
     if args.vocabulary and not ((args.relocalize or args.detect_loops or args.track_reference) and args.map):
         ap.error("--vocabulary needs --map and --relocalize, --detect-loops or --track-reference")
     if args.track_reference and not (args.map and args.track_map and args.vocabulary):
@@ -245,7 +251,15 @@ def main(argv=None):
     seeds = [None]   # --covisible: the previous frame's matched map points (indices into the map as it stands: dropped when the map changes)
     if args.map:
         from vslam_amd.mapper import LocalMapper, predict_pose
-        mapper = LocalMapper(K, args.map)
+        if args.load_state:   # localise in a saved map: no initialisation, the frames are tracked in its frame and scale
+            mapper = LocalMapper.load_state(args.load_state, output_path=args.map)
+            state = "TRACKING"
+            if mapper.keyframes:
+                ref_pose = mapper.keyframes[-1]["pose"].copy()
+            print("loaded %s: %d keyframes, %d map points%s" % (args.load_state, len(mapper.keyframes), len(mapper.map_points),
+                                                              ", vocabulary of %d words" % len(mapper.vocabulary) if mapper.vocabulary is not None else ""))
+        else:
+            mapper = LocalMapper(K, args.map)
         if args.cull_keyframes:
             mapper.redundancy_threshold = float("inf")
         if args.vocabulary and os.path.exists(args.vocabulary):
@@ -445,7 +459,10 @@ def main(argv=None):
             kps, desc = extractor.distribute_keypoints(frame, aligned=True)
         else:
             kps, desc = extractor.extract_features(frame, distributed=False)
-        if state == "NOT_INITIALIZED":
+        if args.load_state and last is None:   # the first frame against a loaded map
+            if args.relocalize or args.track_map:
+                relocalize(frame, kps, desc, idx)
+        elif state == "NOT_INITIALIZED":
             if initializer.first_frame_keypoints is None:
                 initializer.set_first_frame(kps, desc, frame)
                 first = (frame, kps, desc)
@@ -503,6 +520,9 @@ def main(argv=None):
     if mapper is not None:
         mapper.save_map()
         print("map statistics: %s" % mapper.get_map_statistics())
+        if args.save_state:
+            mapper.save_state(args.save_state)
+            print("state saved to %s (%d bytes)" % (args.save_state, os.path.getsize(args.save_state)))
         if args.local_ba:
             print("bundle adjustment: %d calls, %d ok" % (n_ba[0], n_ba[1]))
             if args.ba_covisible or args.ba_erase_outliers:

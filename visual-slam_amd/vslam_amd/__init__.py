@@ -196,6 +196,19 @@ class MapPtEraseOut(C.Structure):
     _fields_ = [("n_removed", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64)]
 
 
+class MapSnapshotDims(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("list_rows", C.c_int32), ("kf_rows", C.c_int64), ("n_pts", C.c_int64), ("n_obs", C.c_int64),
+                ("list_ids", C.c_int64), ("kf_stored", C.c_int64), ("id_bound", C.c_int64), ("img_w", C.c_int32 * 2), ("img_h", C.c_int32 * 2),
+                ("img_ch", C.c_int32 * 2), ("img_cur", C.c_int32), ("st_live", C.c_int32 * 3), ("img_bytes", C.c_int64 * 2)]
+
+
+class MapSnapshot(C.Structure):
+    _fields_ = [("dims", MapSnapshotDims), ("kf_cnt", C.c_void_p), ("kf_ord", C.c_void_p), ("kf_kps", C.c_void_p), ("kf_desc", C.c_void_p),
+                ("kf_P", C.c_void_p), ("xyz", C.c_void_p), ("col", C.c_void_p), ("id", C.c_void_p), ("dref_kf", C.c_void_p),
+                ("dref_row", C.c_void_p), ("obs_off", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_kp", C.c_void_p), ("life", C.c_void_p),
+                ("list_off", C.c_void_p), ("list_ids", C.c_void_p), ("kf_red", C.c_void_p), ("img", C.c_void_p * 2)]
+
+
 class MapViewParams(C.Structure):
     _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32)]
 
@@ -422,6 +435,9 @@ SIGNATURES = {
     "mo_map_points_bad": (_i, [_vp, _vp, _vp]),
     "mo_map_erase_points": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_cull_points": (_i, [_vp, _vp, _vp]),
+    "mo_map_snapshot_dims": (_i, [_vp, _vp]),
+    "mo_map_export": (_i, [_vp, _vp]),
+    "mo_map_import": (_i, [_vp, _vp, _i, _i, C.c_int64, C.c_int64, _vp]),
     "mo_map_point_views": (_i, [_vp, _vp, _vp]),
     "mo_map_track_frustum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_fuse_frustum": (_i, [_vp, _vp, _vp, _vp]),

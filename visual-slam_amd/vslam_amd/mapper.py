@@ -104,6 +104,15 @@ class LocalMapper:
 
     def __init__(self, camera_matrix, output_path=None, save_every_keyframe=True, context=None, n_hyp=_N_HYP, seed=_SEED,
                  pair_index_base=0, capacity=(64, 2048, 1 << 16, 1 << 17)):
+        self._init_host_state(camera_matrix, output_path, save_every_keyframe, context, n_hyp, seed, pair_index_base)
+        kf_slots, rows, pts, obs = capacity
+        h = self.lib.mo_map_create(self.ctx.h, int(kf_slots), int(rows), int(pts), int(obs))
+        if not h:
+            raise V.NativeError(V.MO_ERR_HIP, self.lib.mo_last_error(self.ctx.h).decode())
+        self._adopt(h)
+
+    def _init_host_state(self, camera_matrix, output_path, save_every_keyframe, context, n_hyp, seed, pair_index_base):
+        """every host attribute of a mapper without a device map yet (the constructor and load_state both start here)"""
         self.camera_matrix = camera_matrix
         self.keyframes = []
         self.output_path = output_path if output_path else "map.ply"
@@ -115,14 +124,8 @@ class LocalMapper:
         self.n_hyp, self.seed, self.pair_index_base = int(n_hyp), int(seed), int(pair_index_base)
         self.ctx = context if context is not None else V.default_context()
         self.lib = self.ctx.lib
-        kf_slots, rows, pts, obs = capacity
-        self._h = self.lib.mo_map_create(self.ctx.h, int(kf_slots), int(rows), int(pts), int(obs))
-        if not self._h:
-            raise V.NativeError(V.MO_ERR_HIP, self.lib.mo_last_error(self.ctx.h).decode())
-        if not hasattr(self.ctx, "_maps"):
-            self.ctx._maps = weakref.WeakSet()
-        self.ctx._maps.add(self)   # closing the context closes this map first
-        self._records = []        # every keyframe dict ever added, by store slot (the descriptor references)
+        self._h = None
+        self._records = []        # every keyframe dict ever added, by ordinal (the descriptor references; on a loaded mapper a removed keyframe's entry is None or holds the rows points still name)
         self._rec_n = []          # their keypoint counts
         self._injected = []       # the dicts given to update_map_points (dref_kf = -(j + 1))
         self._n_points = 0
@@ -133,9 +136,28 @@ class LocalMapper:
         self._version = 0
         self._cache = None
         self._lists = None
+        self._image_size = None   # load_state: (w, h) of the saved last keyframe's image, for when no keyframe dict carries one
         self.last = None          # the growth step of the last add_keyframe (match lists, inlier mask, F, new points)
         self.map_points = _MapPoints(self)
         self.vocabulary = None
+
+    def _adopt(self, handle):
+        """the device map of this mapper; closing the context closes it first"""
+        self._h = handle
+        if not hasattr(self.ctx, "_maps"):
+            self.ctx._maps = weakref.WeakSet()
+        self.ctx._maps.add(self)
+
+    def _default_image_size(self):
+        """(w, h) a projection must land in when the caller names none: the last keyframe's image (on a loaded mapper the latest
+        keyframe that carries one, else the saved one's size), else twice the principal point"""
+        for kf in reversed(self.keyframes):
+            if kf["image"] is not None:
+                return kf["image"].shape[1::-1]
+        if self._image_size is not None:
+            return self._image_size
+        Km = np.asarray(self.camera_matrix, np.float64)
+        return (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "h", None):
@@ -467,11 +489,7 @@ class LocalMapper:
         Returns info: n_targets, n_local, n_pairs, n_cand, n_proposals, n_gained, n_edges, n_absorbed, n_points, n_obs and `into`
         (the new index of the point each old point now is)."""
         if image_size is None:
-            if self.keyframes:
-                image_size = self.keyframes[-1]["image"].shape[1::-1]
-            else:
-                Km = np.asarray(self.camera_matrix, np.float64)
-                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+            image_size = self._default_image_size()
         n0 = self._n_points
         before = self.arrays() if n0 else None
         into = np.arange(max(n0, 1), dtype=np.int32)
@@ -668,11 +686,7 @@ class LocalMapper:
         track_local_map's dict (`point`, `inlier`; its `local_keyframes`, when there, are the local map unless local_keyframes names
         positions itself; else the last `window` keyframes, 0: all).  Returns n_local, n_seen, n_matched, n_found."""
         if image_size is None:
-            if self.keyframes:
-                image_size = self.keyframes[-1]["image"].shape[1::-1]
-            else:
-                Km = np.asarray(self.camera_matrix, np.float64)
-                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+            image_size = self._default_image_size()
         n_kf = len(self.keyframes)
         if local_keyframes is None:
             local_keyframes = info.get("local_keyframes")
@@ -880,11 +894,7 @@ class LocalMapper:
         if not 1 <= len(radii) <= 4:
             raise ValueError("radii: one to four passes")
         if image_size is None:
-            if self.keyframes:
-                image_size = self.keyframes[-1]["image"].shape[1::-1]
-            else:
-                Km = np.asarray(self.camera_matrix, np.float64)
-                image_size = (max(int(round(2 * Km[0, 2])), 1), max(int(round(2 * Km[1, 2])), 1))
+            image_size = self._default_image_size()
         return V.MapTrackParams(int(image_size[0]), int(image_size[1]), int(window), len(radii), (C.c_double * 4)(*(radii + [0.0] * (4 - len(radii)))),
                                 float(scale_factor), float(ratio), float(chi2), int(max_dist), int(min_matches), int(min_inliers))
 
@@ -1600,6 +1610,162 @@ class LocalMapper:
     def save_map(self):
         """writes the PLY now (for save_every_keyframe=False)"""
         self._save_map()
+
+    # ---- the whole state in one file ------------------------------------------------------------------------------------------------
+    def export_state(self):
+        """The device map's snapshot as a dict of numpy arrays (mo_map_export in include/vslam_amd.h states the canonical form):
+        `dims` (int64, vslam_amd.snapshot.DIM_NAMES) and the arrays vslam_amd.snapshot.array_specs names.  The map is not changed."""
+        from vslam_amd import snapshot as S
+        return S.export_map(self.lib, self._h, self._check)
+
+    def save_state(self, path, images="last", compressed=False):
+        """Writes the mapper - the device map's snapshot, the camera matrix and the host's bookkeeping - to one .npz at `path` (the path
+        as given), from which load_state makes a mapper that returns the bytes this one returns, for every call and every later edit.
+        images="last": the file holds the image the next add_keyframe colours its points from (the device's copy) and the last
+        keyframe dict's own image; the loaded keyframe dicts of earlier keyframes carry image=None; "all": every keyframe's image as
+        well.  An attached vocabulary's two arrays are embedded.  Of a dict given to update_map_points the keys id, position, color,
+        descriptor and observed_keyframes are kept.  No call may be in flight on the map."""
+        from vslam_amd import snapshot as S
+        if images not in ("last", "all"):
+            raise ValueError("images: \"last\" or \"all\"")
+        a = self.export_state()
+        out = {"format_version": np.array(S.FORMAT_VERSION, np.int64), "dims": a["dims"]}
+        out.update({"map_" + k: v for k, v in a.items() if k != "dims"})
+        n_kf = len(self.keyframes)
+        out["camera_matrix"] = np.asarray(self.camera_matrix, np.float64).reshape(3, 3)
+        out["settings"] = np.array([self.redundancy_threshold, self.min_observations, self.culling_threshold, float(bool(self.save_every_keyframe))],
+                                   np.float64)
+        out["sampling"] = np.array([self.n_hyp, self.seed, self.pair_index_base], np.uint64)
+        out["kf_ids"] = np.array([int(kf["id"]) for kf in self.keyframes], np.int64)
+        out["kf_poses"] = np.array([np.asarray(kf["pose"], np.float64).reshape(4, 4) for kf in self.keyframes], np.float64).reshape(n_kf, 4, 4)
+        out["kf_serials"] = np.array(self._kf_serials, np.int64)
+        out["next_serial"] = np.array(self._next_serial, np.int64)
+        out["list_rows"] = np.array([-1 if r is None else int(r) for r in self._list_rows], np.int64)
+        out["covis"] = np.array([(int(p), int(q), int(n)) for p, row in self.co_visibility_graph.items() for q, n in row.items()],
+                                np.int64).reshape(-1, 3)
+        rec_n = list(self._rec_n) + [0] * (len(self._records) - len(self._rec_n))
+        out["rec_n"] = np.array(rec_n, np.int64)
+        # the descriptor rows that points name in keyframes no longer in the map
+        ref, row = a["dref_kf"].astype(np.int64), a["dref_row"].astype(np.int64)
+        live = np.zeros(len(self._records) + 1, bool)
+        live[a["kf_ord"]] = True
+        dead = np.unique(np.stack([ref, row], 1)[(ref >= 0) & ~live[np.clip(ref, 0, len(self._records))]], axis=0) if len(ref) else np.zeros((0, 2), np.int64)
+        out["dead_ref"] = dead.reshape(-1, 2)
+        out["dead_desc"] = np.array([np.asarray(self._records[int(k)]["descriptors"][int(r)], np.uint8).reshape(32) for k, r in dead.tolist()],
+                                    np.uint8).reshape(-1, 32)
+        # the injected dicts that points still name
+        inj = np.unique(-ref[ref < 0] - 1) if len(ref) else np.zeros(0, np.int64)
+        nj = len(inj)
+        flags, col, desc = np.zeros((nj, 3), np.uint8), np.zeros((nj, 3), np.uint8), np.zeros((nj, 32), np.uint8)
+        ids, pos, obs, obs_off = np.zeros(nj, np.int64), np.zeros((nj, 3), np.float64), [], np.zeros(nj + 1, np.int64)
+        for x, j in enumerate(inj.tolist()):
+            mp = self._injected[j]
+            ids[x] = int(mp.get("id", 0))
+            pos[x] = np.asarray(mp["position"], np.float64).reshape(3)
+            if "color" in mp:
+                c = np.asarray(mp["color"]).reshape(-1)
+                flags[x, 0], col[x] = 1, (c[:3] if c.size >= 3 else np.repeat(c[:1], 3))
+            if mp.get("descriptor") is not None:
+                flags[x, 1], desc[x] = 1, np.asarray(mp["descriptor"], np.uint8).reshape(32)
+            if "observed_keyframes" in mp:
+                flags[x, 2] = 1
+                obs += [(int(k), int(v)) for k, v in mp["observed_keyframes"].items()]
+            obs_off[x + 1] = len(obs)
+        out.update(n_injected=np.array(len(self._injected), np.int64), inj_index=inj.astype(np.int64), inj_id=ids, inj_pos=pos, inj_flags=flags,
+                   inj_color=col, inj_desc=desc, inj_obs_off=obs_off, inj_obs=np.array(obs, np.int64).reshape(-1, 2))
+        lc = self._loop_consistency
+        groups = lc.groups if lc is not None else []
+        out["lc_threshold"] = np.array(lc.threshold if lc is not None else -1, np.int64)
+        out["lc_counts"] = np.array([int(n) for _, n in groups], np.int64)
+        out["lc_off"] = np.concatenate([[0], np.cumsum([len(g) for g, _ in groups])]).astype(np.int64)
+        out["lc_serials"] = np.array([s for g, _ in groups for s in sorted(g)], np.int64)
+        voc = self.vocabulary
+        out["vocab_words"] = np.array(voc.words, np.uint8).reshape(-1, 32) if voc is not None else np.zeros((0, 32), np.uint8)
+        out["vocab_weights"] = np.array(voc.weights, np.int32).reshape(-1) if voc is not None else np.zeros(0, np.int32)
+        out["images_all"] = np.array(1 if images == "all" else 0, np.int64)
+        shapes = []
+        if images == "all":
+            for k, kf in enumerate(self.keyframes):
+                img = np.ascontiguousarray(kf["image"], np.uint8) if kf["image"] is not None else np.zeros((0, 0), np.uint8)
+                shapes.append((img.shape[0], img.shape[1], 0 if img.ndim == 2 else img.shape[2]))
+                out["kf_image_%d" % k] = img
+        out["image_shapes"] = np.array(shapes, np.int64).reshape(-1, 3)
+        # the last keyframe dict's own image: the device's current image is that of the last keyframe ever stored, which may be gone
+        last = self.keyframes[-1]["image"] if self.keyframes else None
+        last = np.ascontiguousarray(last, np.uint8) if last is not None else np.zeros((0, 0), np.uint8)
+        out["last_image"] = last
+        out["last_image_size"] = np.array(self._default_image_size() if self.keyframes else (0, 0), np.int64)
+        with open(path, "wb") as fh:   # (the path as given: np.savez would append .npz to a name without it)
+            (np.savez_compressed if compressed else np.savez)(fh, **out)
+
+    @classmethod
+    def load_state(cls, path, context=None, capacity=None, output_path=None):
+        """A mapper from a file save_state wrote.  The file is checked completely - version, presence, dtype, shape and mutual
+        consistency of every array (vslam_amd.snapshot.check_file) - before a context is created or the library touched; a bad file
+        raises ValueError naming the array.  capacity: as the constructor's, by default what the snapshot needs (the library takes the
+        larger of the two anyway).  The loaded map has no dead keyframe slots; keyframe ordinals, serials, ids and the sampling stream of
+        the next keyframe pair continue.  Keyframe dicts carry the stored rows as `keypoints` (vslam_amd.KP_DTYPE) and `descriptors`."""
+        from vslam_amd import snapshot as S
+        from vslam_amd.loop import LoopConsistency
+        with np.load(path, allow_pickle=False) as z:
+            f = S.check_file(z)
+        d = dict(zip(S.DIM_NAMES, (int(x) for x in f["dims"])))
+        self = cls.__new__(cls)
+        n_hyp, seed, base = (int(v) for v in f["sampling"])
+        self._init_host_state(f["camera_matrix"].copy(), output_path, bool(f["settings"][3]), context, n_hyp, seed, base)
+        self.redundancy_threshold, self.culling_threshold = float(f["settings"][0]), float(f["settings"][2])
+        self.min_observations = int(f["settings"][1])
+        ctx = self.ctx
+        cap = capacity if capacity is not None else (0, 0, 0, 0)
+
+        def check(rc):
+            if rc != V.MO_OK:
+                err = self.lib.mo_last_error(ctx.h).decode()
+                raise (ValueError("state file: the library refuses the snapshot: " + err) if rc == V.MO_ERR_ARG else V.NativeError(rc, err))
+        self._adopt(S.import_map(self.lib, ctx.h, f, cap, check))
+        # the keyframes: the stored rows by position
+        n_kf = d["n_kf"]
+        off = np.concatenate([[0], np.cumsum(f["kf_cnt"], dtype=np.int64)])
+        last_img = f["last_image"].copy() if f["last_image"].size else None
+        if n_kf:
+            self._image_size = tuple(int(v) for v in f["last_image_size"])
+        self._records = [None] * len(f["rec_n"])
+        self._rec_n = [int(v) for v in f["rec_n"]]
+        for k in range(n_kf):
+            img = f["kf_image_%d" % k].copy() if int(f["images_all"]) else (last_img if k == n_kf - 1 else None)
+            kf = _Keyframe({"id": int(f["kf_ids"][k]), "image": img, "keypoints": f["kf_kps"][off[k]:off[k + 1]].copy(),
+                            "descriptors": f["kf_desc"][off[k]:off[k + 1]].copy(), "pose": f["kf_poses"][k].copy()})
+            kf._mapper, kf._extra, kf._rows = self, [], int(f["kf_cnt"][k])
+            self.keyframes.append(kf)
+            self._records[int(f["kf_ord"][k])] = kf
+        # the descriptor rows of removed keyframes that points still name: a record of those rows alone
+        for (k, r), desc in zip(f["dead_ref"].tolist(), f["dead_desc"]):
+            if self._records[k] is None:
+                self._records[k] = {"descriptors": {}}
+            self._records[k]["descriptors"][r] = desc.copy()
+        self._injected = [None] * int(f["n_injected"])
+        for x, j in enumerate(f["inj_index"].tolist()):
+            mp = {"id": int(f["inj_id"][x]), "position": f["inj_pos"][x].copy()}
+            if f["inj_flags"][x, 0]:
+                mp["color"] = f["inj_color"][x].copy()
+            if f["inj_flags"][x, 1]:
+                mp["descriptor"] = f["inj_desc"][x].copy()
+            if f["inj_flags"][x, 2]:
+                mp["observed_keyframes"] = {int(a): int(b) for a, b in f["inj_obs"][f["inj_obs_off"][x]:f["inj_obs_off"][x + 1]].tolist()}
+            self._injected[j] = mp
+        for p, q, n in f["covis"].tolist():
+            self.co_visibility_graph[p][q] = n
+        self._list_rows = [None if r < 0 else int(r) for r in f["list_rows"].tolist()]
+        self._kf_serials = [int(v) for v in f["kf_serials"]]
+        self._next_serial = int(f["next_serial"])
+        if int(f["lc_threshold"]) >= 0:
+            self._loop_consistency = LoopConsistency(int(f["lc_threshold"]))
+            lo = f["lc_off"]
+            self._loop_consistency.groups = [(frozenset(f["lc_serials"][lo[g]:lo[g + 1]].tolist()), int(n)) for g, n in enumerate(f["lc_counts"].tolist())]
+        self._sync_size()
+        if len(f["vocab_weights"]):
+            self.set_vocabulary(V.Vocabulary.from_arrays(f["vocab_words"], f["vocab_weights"], context=ctx))
+        return self
 
     def _filter_map_points(self):
         a = self.arrays()
