@@ -1234,6 +1234,53 @@ int mo_map_snapshot_dims(mo_map*, mo_map_snapshot_dims_t*);
 int mo_map_export(mo_map*, mo_map_snapshot*);
 int mo_map_import(mo_ctx*, const mo_map_snapshot*, int kf_slots, int kf_rows, int64_t pts_cap, int64_t obs_cap, mo_map** out);
 
+/* ---- Absorb: one device map appended to another (map_absorb.hip, absorb.h) ----------------------------------------------------------------
+ * mo_map_absorb appends src to dst on the device and src becomes dst's tail: the absorbed map is the later one, positions keep creation
+ * order.  src is only read and stays usable.  Nothing aligns the two frames: that is the loop calls' work (LocalMapper.merge_map).
+ * Additive: no call above launches anything different.  The contract: mo_map_export(dst) after the call equals, array for array and in
+ * dims, tests/absorb_restatement.py applied to the exports of dst before and of src; the restated snapshot obeys csrc/snapshot.h.
+ * With n_kf, n_slots, n_pts, n_obs, id_bound, kf_stored the counters of dst in front of the call:
+ *   keyframes     src position k becomes dst position n_kf + k in the new slot n_slots + k.  Dead slots of src are shed, those of dst
+ *                 stay.  Its ordinal becomes kf_stored + its ordinal in src.  The slot's serial is bumped: the keyframe database recounts
+ *                 it by the lazy rule.  Count and rows are copied, the projection matrix byte for byte.  A src keyframe with more rows
+ *                 than dst's row stride restrides dst's store first, as a wide frame does.
+ *   points        src point i becomes dst point n_pts + i.  xyz, col and dref_row keep their bytes; id += id_bound; dref_kf >= 0 (an
+ *                 ordinal) += kf_stored, dref_kf < 0 (the host's index into its injected dicts, never read here) -= dref_injected_shift;
+ *                 life becomes {visible, found, born + kf_stored, 0}, born held at the new now (that binds only for a src that never
+ *                 stored a keyframe: its points are then as old as dst's last keyframe, and born <= now stays true).  Consequence: now jumps by src's kf_stored, so the young points of
+ *                 dst age past the young-point rules of mo_map_points_bad at once (max_age), as if that many keyframes had been stored.
+ *   observations  entries keep their order; obs_off[n_pts + i + 1] = n_obs + src's obs_off[i + 1].  An entry that names a row of a src
+ *                 keyframe (as every reader reads it: negative values from the end) is written normalised as (n_kf + position, row), both
+ *                 non-negative.  An entry that names nothing in src is written as (INT32_MIN, its row value unchanged): it names nothing
+ *                 in dst whatever is added later.  dst's own entries are not touched - their negative keys already change meaning
+ *                 with every mo_map_add_keyframe, and do so here: a key -1 of dst names src's last keyframe afterwards.
+ *   counters      kf_stored, id_bound, n_pts, n_obs and the live status words {points, observations} take the sums.  The third live
+ *                 word (new points) stays dst's: its one reader, mo_map_add_keyframe, reads what its own chain wrote and clears it.
+ *   images        when src has a keyframe, dst takes src's two keyframe images, their sizes and img_cur: the tail's image is the one the
+ *                 next mo_map_add_keyframe colours from.
+ *   lists         dst's per-keyframe lists and kf_red are untouched (list_rows stays): absorbed keyframes have no list row until the next
+ *                 cull.
+ *   dst's bytes   apart from a restride, no byte of dst's own keyframes, points or entries changes: everything is appended in place in
+ *                 the live copy, the store is not flipped.
+ *   errors        checked before anything is reserved or written, dst unchanged: MO_ERR_ARG for NULL arguments, src == dst, maps of
+ *                 different contexts, dref_injected_shift outside 0 .. INT32_MAX; MO_ERR_CAPACITY for a sum past the snapshot's bounds
+ *                 (n_pts, n_obs <= INT32_MAX / 2, id_bound <= 2^31, kf_stored <= INT32_MAX); MO_ERR_UNSUPPORTED for more than 65535
+ *                 keyframes after the call.  A src without keyframes and without points is a complete no-op (no counter moves): MO_OK.
+ *   chain         reserve, then on the context stream: one launch for the keypoint rows and one for the descriptor rows (slot-strided to
+ *                 slot-strided, no staging; 16-byte units when both ends of a keyframe's run are aligned, else 4-byte units), one launch
+ *                 over the points, one over the entries, the image copies; one synchronisation.  No atomics: equal inputs give equal
+ *                 bytes.  Stage marks absorb_rows, absorb_points, absorb_obs.
+ * out: the offsets that were applied (also on the no-op) and dst's counters after the call. */
+typedef struct {
+    int64_t dref_injected_shift;   /* subtracted from every negative dref_kf of src, >= 0 (the caller's count of injected dicts) */
+} mo_map_absorb_params;
+typedef struct {
+    int32_t kf_offset, slot_offset;                             /* n_kf, n_slots of dst in front of the call */
+    int64_t point_offset, obs_offset, id_offset, ordinal_offset; /* n_pts, n_obs, id_bound, kf_stored in front of the call */
+    int64_t n_kf, n_slots, n_pts, n_obs, id_bound, kf_stored;   /* after the call */
+} mo_map_absorb_out;
+int mo_map_absorb(mo_map* dst, mo_map* src, const mo_map_absorb_params*, mo_map_absorb_out*);
+
 /* ---- Place recognition: a binary vocabulary, the keyframe database of a map, relocalization with preselection (bow.hip) ----------------
  * "Which keyframes look like this frame": DBoW2's L1 score of tf-idf vectors over a flat vocabulary of binary words.  Everything is
  * integer work except the logarithm of the weights (host, once per training) and the one division of the score; tests/bow_restatement.py
@@ -1433,6 +1480,13 @@ typedef struct {
     double  min_score;
 } mo_map_loop_out;
 int mo_map_loop_candidates(mo_map*, const mo_map_loop_params*, mo_map_loop_out*);
+/* mo_map_loop_candidates_among: the candidates among a given keyframe set only (the merge of two maps asks one side about the other: an
+ * unrelated keyframe of the asking side would otherwise outscore the true match and push it under the retain test).  among: [n_kf] on the
+ * host, or NULL, which behaves as mo_map_loop_candidates.  One added rule: common_k = 0 where among[k] == 0; such a keyframe takes no part
+ * in S, M, the group sums or the candidates, exactly like a connected one.  connected, min_score and every other rule are unchanged.  The
+ * mask is applied by one [n_kf] launch between the score and the selection (stage mark loop_among); the kernels of the plain call are
+ * the same code and the plain call launches what it launched. */
+int mo_map_loop_candidates_among(mo_map*, const mo_map_loop_params*, const uint8_t* among /* [n_kf] */, mo_map_loop_out*);
 
 /* ---- Loop alignment (map_sim3.hip, sim3.h) ------------------------------------------------------------------------------------------------
  * "Is the candidate the same place, and at which relative scale": ORB-SLAM2's ComputeSim3 on the correspondences

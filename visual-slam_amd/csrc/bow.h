@@ -60,3 +60,6 @@ int bow_update_enqueue(mo_map* m);
 // the same pass the common-word counts (0 for q_pos and for every k with wrow[k] >= min_w; wrow = row q_pos of the covisibility matrix,
 // on the device); mark loop_score; behind bow_update_enqueue
 int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w, BowLoop* out);
+// mo_map_loop_candidates_among's one rule, behind bow_loop_score_enqueue: common[k] = 0 where among[k] == 0 (among [n_kf] on the device);
+// mark loop_among
+int bow_loop_among_enqueue(mo_map* m, const uint8_t* among);

@@ -504,6 +504,22 @@ int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w,
     return MO_OK;
 }
 
+// a thread per keyframe position; the scoring kernel stays the code it is
+__global__ __launch_bounds__(256) void k_bow_among(const uint8_t* __restrict__ among, int n_kf, int32_t* __restrict__ common) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n_kf && !among[k]) common[k] = 0;
+}
+
+int bow_loop_among_enqueue(mo_map* m, const uint8_t* among) {
+    mo_ctx* c = m->c;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
+    const int n_kf = (int)m->pos_slot.size();
+    hipLaunchKernelGGL(k_bow_among, dim3((unsigned)((n_kf + 255) / 256)), dim3(256), 0, c->stream, among, n_kf, b.common.p);
+    HIPCHK(c, hipGetLastError());
+    mo_stage_mark(c, "loop_among");
+    return MO_OK;
+}
+
 extern "C" int mo_map_query_keyframes(mo_map* m, const mo_frame_ref* f, const mo_map_query_params* prm, mo_map_query_out* out) {
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;

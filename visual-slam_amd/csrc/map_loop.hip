@@ -45,10 +45,11 @@ struct LoopBufs : MapFeature {
     MatchBufs match;                          // [pair][row]
     DevBuf<unsigned long long> claim;         // [pair][row] per train row: (distance << 32) | query row of the match that keeps it
     DevBuf<int32_t> cur, mpt, mrow;           // [row], [pair][row], [pair][row]
+    DevBuf<uint8_t> among;                    // [n_kf] mo_map_loop_candidates_among's mask as uploaded
     ResBlock<LoopRes> res;
     // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
     template <class F> void each_scratch(F f) {
-        f(flag); f(acc); f(best); f(cacc); f(connected); f(group); f(qf); f(tf); f(tab); match.each_scratch(f); f(claim); f(cur); f(mpt); f(mrow); f(res);
+        f(flag); f(acc); f(best); f(cacc); f(connected); f(group); f(qf); f(tf); f(tab); match.each_scratch(f); f(claim); f(cur); f(mpt); f(mrow); f(among); f(res);
     }
     int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
 };
@@ -241,7 +242,9 @@ __global__ __launch_bounds__(256) void k_loop_gather(const int32_t* __restrict__
     wave_count_add(kept, &res->n_match[c]);
 }
 
-extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, mo_map_loop_out* out) {
+// among: NULL, or [n_kf] on the host; the keyframes where it is 0 lose their common-word count between the loop_score and loop_select
+// stages (bow_loop_among_enqueue), which is all it takes: k_loop_select admits a keyframe to S, M and a group's sum through common_k > 0
+static int loop_candidates(mo_map* m, const mo_map_loop_params* prm, const uint8_t* among, mo_map_loop_out* out) {
     if (!m) return MO_ERR_ARG;
     mo_ctx* c = m->c;
     if (!prm || !out) return mo_fail(c, MO_ERR_ARG, "NULL argument");
@@ -274,6 +277,11 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
     if ((rc = bow_loop_score_enqueue(m, p, W + (size_t)p * n_kf, min_w, &sc))) return rc;
     LoopBufs& b = map_feature<LoopBufs>(m);
     const size_t nk = (size_t)n_kf, pair_n = (size_t)std::max(mc, 1) * row;
+    if (among) {
+        if ((rc = b.among.reserve(c, nk))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.among, among, nk, hipMemcpyHostToDevice, c->stream));
+        if ((rc = bow_loop_among_enqueue(m, b.among))) return rc;
+    }
     if ((rc = mo_reserve(c, b.flag, nk, b.acc, nk, b.best, nk, b.cacc, nk, b.connected, nk, b.group, nk * std::max(mc, 1), b.qf, LP_MAX_CAND,
                          b.tf, LP_MAX_CAND, b.res)))
         return rc;
@@ -324,4 +332,10 @@ extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, 
         if (out->n_match) out->n_match[i] = r.n_match[i];
     }
     return MO_OK;
+}
+
+extern "C" int mo_map_loop_candidates(mo_map* m, const mo_map_loop_params* prm, mo_map_loop_out* out) { return loop_candidates(m, prm, nullptr, out); }
+
+extern "C" int mo_map_loop_candidates_among(mo_map* m, const mo_map_loop_params* prm, const uint8_t* among, mo_map_loop_out* out) {
+    return loop_candidates(m, prm, among, out);
 }

@@ -1,6 +1,6 @@
 // map_store.h -- the device-resident map (mo_map) shared by the map sources: map_kernels.hip (stores, device-wide scan, growth, cull),
 // map_reloc.hip (relocalization), map_track.hip (tracking), map_ba.hip and map_gba.hip (bundle adjustment; ba_problem.h is what those two share), map_obs.hip (added and erased observations), map_fuse.hip (fusion
-// of duplicate points) and map_correct.hip (loop correction; map_merge.h is what those two share), map_sim3.hip and map_confirm.hip (loop alignment and confirmation; sim3_device.h is what those two share), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase), map_io.hip (PLY text) and map_snapshot.hip (export / import of the whole state).
+// of duplicate points) and map_correct.hip (loop correction; map_merge.h is what those two share), map_sim3.hip and map_confirm.hip (loop alignment and confirmation; sim3_device.h is what those two share), map_grow.hip (new points from neighbour keyframes), map_covis.hip (covisibility, local keyframes), bow.hip (place recognition), map_loop.hip (loop candidates), map_posegraph.hip (essential graph), map_view_geom.hip (point views), map_ptcull.hip (the life of a point: counters, cull, erase), map_io.hip (PLY text), map_snapshot.hip (export / import of the whole state) and map_absorb.hip (one map appended to another).
 // Here, in this order:
 //   the stores (their owning buffer types DevBuf / PinnedBuf are common.h's);
 //   what a feature's host side is made of: MapFeature (its scratch struct's base), ResBlock (a result block, device and pinned copy),

@@ -24,7 +24,7 @@ Inputs:
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
-       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes] [--save-state FILE] [--load-state FILE]]
+       [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes] [--save-state FILE] [--load-state FILE] [--merge-into FILE]]
 """
 import argparse
 import os
@@ -175,6 +175,9 @@ def main(argv=None):
                     "map's snapshot, the keyframes, the vocabulary), to localise in later with --load-state")
     ap.add_argument("--load-state", default="", help="with --map: start from the mapper saved in FILE (LocalMapper.load_state) instead of initialising; "
                     "with --relocalize or --track-map the first frame is relocalised against it, otherwise tracking goes on from its last keyframe's pose")
+    ap.add_argument("--merge-into", default="", help="with --map: at the end of the run FILE (a mapper saved by --save-state) is loaded as the base and "
+                    "the run's map is merged into it (LocalMapper.merge_map: absorbed on the device, aligned by the loop calls; the base's vocabulary "
+                    "is used, else --vocabulary's); --save-state then writes the merged mapper")
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
@@ -198,8 +201,10 @@ def main(argv=None):
         ap.error("--relocalize needs --map")
     if (args.save_state or args.load_state) and not args.map:
         ap.error("--save-state and --load-state need --map")
-    if args.vocabulary and not ((args.relocalize or args.detect_loops or args.track_reference) and args.map):
-        ap.error("--vocabulary needs --map and --relocalize, --detect-loops or --track-reference")
+    if args.merge_into and not args.map:
+        ap.error("--merge-into needs --map")
+    if args.vocabulary and not ((args.relocalize or args.detect_loops or args.track_reference or args.merge_into) and args.map):
+        ap.error("--vocabulary needs --map and --relocalize, --detect-loops, --track-reference or --merge-into")
     if args.track_reference and not (args.map and args.track_map and args.vocabulary):
         ap.error("--track-reference needs --map, --track-map and --vocabulary")
     if args.detect_loops and not args.vocabulary:
@@ -520,6 +525,22 @@ def main(argv=None):
     if mapper is not None:
         mapper.save_map()
         print("map statistics: %s" % mapper.get_map_statistics())
+        if args.merge_into:   # two sessions, one map: the saved mapper is the base, this run's map its tail
+            base = LocalMapper.load_state(args.merge_into, context=mapper.ctx, output_path=args.map)
+            if base.vocabulary is None:
+                ensure_vocabulary(n_seen)   # (--vocabulary: loaded at the start, or trained on this run's keyframes now)
+                if mapper.vocabulary is not None:
+                    base.set_vocabulary(mapper.vocabulary)
+            if base.vocabulary is None:
+                print("--merge-into: neither %s nor this run carries a vocabulary; the maps are not merged" % args.merge_into)
+            else:
+                res = base.merge_map(mapper)
+                print("merged into %s: aligned %s after %d tries%s; %d keyframes, %d map points"
+                      % (args.merge_into, res["aligned"], res["tries"],
+                         ", keyframe %d onto %d at scale %.4f, %d duplicates fused" % (res["kf_pos"], res["cand_pos"], res["scale"], res["correct"]["n_absorbed"])
+                         if res["aligned"] else " (the run's map was taken out again)", len(base.keyframes), len(base.map_points)))
+                mapper = base
+                mapper.save_map()
         if args.save_state:
             mapper.save_state(args.save_state)
             print("state saved to %s (%d bytes)" % (args.save_state, os.path.getsize(args.save_state)))

@@ -245,6 +245,16 @@ class MapTrackRefOut(C.Structure):
                 ("hist", C.c_int32 * 30), ("kept_bin", C.c_int32 * 3), ("ok", C.c_int32), ("from_token", C.c_int32)]
 
 
+class MapAbsorbParams(C.Structure):
+    _fields_ = [("dref_injected_shift", C.c_int64)]
+
+
+class MapAbsorbOut(C.Structure):
+    _fields_ = [("kf_offset", C.c_int32), ("slot_offset", C.c_int32), ("point_offset", C.c_int64), ("obs_offset", C.c_int64),
+                ("id_offset", C.c_int64), ("ordinal_offset", C.c_int64), ("n_kf", C.c_int64), ("n_slots", C.c_int64), ("n_pts", C.c_int64),
+                ("n_obs", C.c_int64), ("id_bound", C.c_int64), ("kf_stored", C.c_int64)]
+
+
 class MapLoopParams(C.Structure):
     _fields_ = [("kf_pos", C.c_int32), ("min_weight", C.c_int32), ("n_best", C.c_int32), ("max_cand", C.c_int32), ("ratio", C.c_double)]
 
@@ -452,6 +462,8 @@ SIGNATURES = {
     "mo_map_track_reference": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_keyframe_words": (_i, [_vp, C.c_int32, _vp]),
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),
+    "mo_map_loop_candidates_among": (_i, [_vp, _vp, _vp, _vp]),
+    "mo_map_absorb": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_loop_sim3": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_confirm": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mo_map_loop_correct": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -209,7 +209,7 @@ class LocalMapper:
         P = np.ascontiguousarray(compute_projection_matrix(pose[:3, :3], pose[:3, 3], self.camera_matrix), np.float64).reshape(12)
         img = np.ascontiguousarray(image, np.uint8)
         ch = 1 if img.ndim == 2 else img.shape[2]
-        n_prev = self._rec_n[-1] if self.keyframes else 0
+        n_prev = self.keyframes[-1]._rows if self.keyframes else 0   # (the last keyframe in the map, which an absorb or an erase may leave different from the last record)
         n_kf = len(self.keyframes) + 1
         midx = np.full((max(n_prev, 1), 2), -1, np.int32)
         mpass = np.zeros(max(n_prev, 1), np.uint8)
@@ -1118,7 +1118,7 @@ class LocalMapper:
                 "ref": int(out.ref)}
 
     # ---- loop detection --------------------------------------------------------------------------------------------------------------
-    def loop_candidates(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75):
+    def loop_candidates(self, kf_position=-1, min_weight=15, n_best=10, max_candidates=4, ratio=0.75, among=None):
         """The old keyframes keyframe `kf_position` (-1: the last) may close a loop with, and the map points of the two that correspond
         (ORB-SLAM2's DetectLoopCandidates and the matching that opens ComputeSim3; mo_map_loop_candidates in include/vslam_amd.h states
         the rules).  Needs a vocabulary; stateless; the map is not changed.  Returns a dict: `candidates`, a list of dicts in rank order
@@ -1126,8 +1126,24 @@ class LocalMapper:
         connected to it), `n_match`, `cur_point` (the asking keyframe's map point per keypoint row, -1: none), `match_point` (the
         candidate's map point matched to that row, -1) and `match_row` (its keypoint row in the candidate, -1); `cur_point` once more at the top (also there
         without a candidate); `connected` (positions connected to the asking keyframe, itself included), `min_score`, `max_common`, `n_scored`, `n_passed`, `n_found` (candidates
-        before the cut at max_candidates) and `n_connected`."""
+        before the cut at max_candidates) and `n_connected`.
+        among: keyframe positions, or a bool mask with one entry per keyframe: only these can be candidates or add to a group's score
+        (mo_map_loop_candidates_among; merge_map asks the absorbed side about the absorbing one).  None: every keyframe."""
         n_kf, mc = len(self.keyframes), int(max_candidates)
+        amask = None
+        if among is not None:
+            sel = np.asarray(among)
+            if sel.dtype == np.bool_:
+                if sel.shape != (n_kf,):
+                    raise ValueError("a mask must have one entry per keyframe")
+                amask = np.ascontiguousarray(sel, np.uint8)
+            else:
+                idx = sel.astype(np.int64).reshape(-1)
+                if len(idx) and (idx.min() < 0 or idx.max() >= n_kf):
+                    raise IndexError("keyframe position out of range")
+                amask = np.zeros(n_kf, np.uint8)
+                amask[idx] = 1
+            amask = np.concatenate([amask, np.zeros(1, np.uint8)])   # (never empty)
         p = n_kf - 1 if int(kf_position) < 0 else int(kf_position)
         n_p = self.keyframes[p]._rows if 0 <= p < n_kf else 0
         m1 = max(mc, 1)
@@ -1141,7 +1157,10 @@ class LocalMapper:
         prm = V.MapLoopParams(int(kf_position), int(min_weight), int(n_best), mc, float(ratio))
         out = V.MapLoopOut(cand.ctypes.data, acc.ctypes.data, score.ctypes.data, connected.ctypes.data, group.ctypes.data, cur.ctypes.data,
                            mpt.ctypes.data, mrow.ctypes.data, n_match.ctypes.data)
-        self._check(self.lib.mo_map_loop_candidates(self._h, C.byref(prm), C.byref(out)))
+        if amask is None:
+            self._check(self.lib.mo_map_loop_candidates(self._h, C.byref(prm), C.byref(out)))
+        else:
+            self._check(self.lib.mo_map_loop_candidates_among(self._h, C.byref(prm), V._ptr(amask), C.byref(out)))
         # (the device writes the arrays packed: [max_cand][n_kf] and [max_cand][rows], which is their shape whenever they hold anything)
         cur = cur[:n_p]
         cands = [{"pos": int(cand[i]), "acc": float(acc[i]), "score": float(score[i]), "group": np.flatnonzero(group[i, :n_kf]).tolist(),
@@ -1539,6 +1558,128 @@ class LocalMapper:
                         c["global_ba"] = dict(ginfo, ok=gok)
                 break
         return info["accepted"] is not None, info
+
+    # ---- two maps into one --------------------------------------------------------------------------------------------------------------
+    def absorb(self, other):
+        """Appends the map of `other` - a LocalMapper on this context, or the path of a file save_state wrote, which is loaded on this
+        context - to this one on the device (mo_map_absorb in include/vslam_amd.h states the rules): its keyframes become the last
+        positions, its points the last indices, every key, id, ordinal and offset relocated.  Nothing aligns the two frames (merge_map
+        does).  `other` is only read and stays usable.  Both must have the same context and bit-equal camera matrices: ValueError
+        otherwise, before the library is touched.
+        The host's bookkeeping is spliced: the absorbed keyframe dicts are appended (copies; their ids shifted by 1 + the largest id
+        here), the keyframe records and injected dicts concatenated, the serials shifted by this mapper's next serial, the co-visibility
+        graph re-keyed by the shifted ids.  Absorbed keyframes have no per-keyframe list until the next cull.  This mapper's
+        loop-consistency state, vocabulary, settings and sampling parameters stay.
+        Returns the offsets: kf_offset, slot_offset, point_offset, obs_offset, id_offset, ordinal_offset (the library's), kf_id_offset,
+        serial_offset, injected_offset, and n_kf / n_points / n_obs after the call."""
+        loaded = None
+        if not isinstance(other, LocalMapper):
+            other = loaded = LocalMapper.load_state(other, context=self.ctx)
+        try:
+            if other.ctx is not self.ctx:
+                raise ValueError("absorb: the two mappers must share one context")
+            Ka, Kb = np.asarray(self.camera_matrix, np.float64), np.asarray(other.camera_matrix, np.float64)
+            if Ka.shape != Kb.shape or Ka.tobytes() != Kb.tobytes():
+                raise ValueError("absorb: the two mappers must have the same camera matrix, bit for bit")
+            shift = len(self._injected)
+            prm = V.MapAbsorbParams(shift)
+            out = V.MapAbsorbOut()
+            self._check(self.lib.mo_map_absorb(self._h, other._h, C.byref(prm), C.byref(out)))
+            id_base = 1 + max([int(kf["id"]) for kf in self.keyframes], default=-1)
+            off = {k: int(getattr(out, k)) for k in ("kf_offset", "slot_offset", "point_offset", "obs_offset", "id_offset", "ordinal_offset")}
+            off.update(kf_id_offset=id_base, serial_offset=self._next_serial, injected_offset=shift)
+            if other.keyframes or other._n_points:   # (else the library's no-op: no counter moved)
+                ordinal = off["ordinal_offset"]
+                self._records += [None] * (ordinal - len(self._records))
+                self._rec_n += [0] * (ordinal - len(self._rec_n))
+                copy_of = {}
+                for kf in other.keyframes:
+                    k2 = _Keyframe({k: v for k, v in dict.items(kf)})
+                    k2["id"] = int(kf["id"]) + id_base
+                    k2["pose"] = np.array(kf["pose"], np.float64)
+                    k2._mapper, k2._rows = self, kf._rows
+                    k2._extra = [int(i) + off["id_offset"] for i in kf._extra]
+                    copy_of[id(kf)] = k2
+                    self.keyframes.append(k2)
+                self._records += [copy_of.get(id(r), r) for r in other._records]
+                self._rec_n += list(other._rec_n) + [0] * (len(other._records) - len(other._rec_n))
+                self._injected += list(other._injected)
+                self._kf_serials += [int(s) + self._next_serial for s in other._kf_serials]
+                self._next_serial += other._next_serial
+                self._list_rows += [None] * len(other.keyframes)
+                for p, row in other.co_visibility_graph.items():
+                    for q, n in row.items():
+                        self.co_visibility_graph[int(p) + id_base][int(q) + id_base] = n
+                self._version += 1
+                self._cache = None
+            self._sync_size()
+            off.update(n_kf=len(self.keyframes), n_points=self._n_points, n_obs=self._n_obs)
+            return off
+        finally:
+            if loaded is not None:
+                loaded.close()
+
+    def merge_map(self, other, max_tries=3, keep_unaligned=False, global_ba=False, min_weight=15, n_best=10, max_candidates=4, ratio=0.75,
+                  sim3_kw=None, confirm_kw=None, correct_kw=None, global_ba_kw=None):
+        """Two maps of one place into one (ORB-SLAM3's Atlas merge on this library's loop calls): absorb(other), then the absorbed side is
+        aligned onto this one.  The absorbed keyframes that have map points are walked from the last backwards, at most max_tries of
+        them: loop_candidates(kf_position=p, among=this mapper's own positions; min_weight, n_best, max_candidates, ratio), compute_sim3
+        (sim3_kw), confirm_loop (confirm_kw).  On the first confirmed candidate correct_loop(corrected=every absorbed position, group=the
+        candidate's group; correct_kw) moves the absorbed keyframes and points onto this map's frame and fuses the duplicates;
+        global_ba=True then runs global_bundle_adjust (global_ba_kw).  Needs a vocabulary (this mapper's is used; the database
+        recounts the absorbed keyframes lazily).
+        When nothing confirms and keep_unaligned is false, the absorbed points and keyframes are taken out again by erase_map_points and
+        erase_keyframes: arrays() and the keyframe list are those of before the call.  As after any erase, nothing is rewound: ordinals,
+        the id bound, serials, the keyframe records and the injected dicts keep the absorbed side's share.
+        Returns a dict: `aligned`, `kf_pos` and `cand_pos` (the asking absorbed position and the winning position of this side, -1), `scale`,
+        `R`, `t` and `world` of the confirmed similarity (None), `tries`, `offsets` (absorb's), `kept` (the absorbed side is still in the
+        map), `correct` (correct_loop's info, its counts among it; None) and `global_ba` ((ok, info); None)."""
+        if self.vocabulary is None:
+            raise ValueError("merge_map needs a vocabulary (set_vocabulary or train_vocabulary)")
+        off = self.absorb(other)
+        n0, n_kf = off["kf_offset"], len(self.keyframes)
+        absorbed = list(range(n0, n_kf))
+        res = {"aligned": False, "kf_pos": -1, "cand_pos": -1, "scale": None, "R": None, "t": None, "world": None, "tries": 0, "offsets": off,
+               "kept": True, "correct": None, "global_ba": None}
+        own = np.zeros(n_kf, bool)
+        own[:n0] = True
+        seen = np.zeros(n_kf, bool)
+        if self._n_points and n_kf:
+            k = self.arrays()["obs_kf"].astype(np.int64)
+            k = np.where(k < 0, k + n_kf, k)
+            seen[k[(k >= 0) & (k < n_kf)]] = True
+        if n0:
+            for p in reversed(absorbed):
+                if res["tries"] >= int(max_tries):
+                    break
+                if not seen[p]:
+                    continue
+                res["tries"] += 1
+                info = self.loop_candidates(p, min_weight, n_best, max_candidates, ratio, among=own)
+                if not info["candidates"]:
+                    continue
+                ok, al = self.compute_sim3(info, **(sim3_kw or {}))
+                if not ok:
+                    continue
+                ok, cf = self.confirm_loop(info, al, **(confirm_kw or {}))
+                if not ok:
+                    continue
+                win = cf["candidates"][int(cf["win"])]
+                group = info["candidates"][int(cf["win"])]["group"]
+                res["correct"] = self.correct_loop(cf, kf_position=p, corrected=absorbed, group=group, **(correct_kw or {}))
+                res.update(aligned=True, kf_pos=p, cand_pos=int(win["pos"]), scale=float(win["scale"]), R=win["R"].copy(), t=win["t"].copy(),
+                           world=cf["world"])
+                break
+        if res["aligned"]:
+            if global_ba:
+                res["global_ba"] = self.global_bundle_adjust(**(global_ba_kw or {}))
+        elif not keep_unaligned:
+            if self._n_points > off["point_offset"]:
+                self.erase_map_points(np.arange(off["point_offset"], self._n_points))
+            if absorbed:
+                self.erase_keyframes(absorbed)
+            res["kept"] = False
+        return res
 
     # ---- device map -> host -----------------------------------------------------------------------------------------------------
     def _sync_size(self):
