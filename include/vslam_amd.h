@@ -1350,6 +1350,62 @@ int mo_map_set_vocabulary(mo_map*, mo_vocab*);
 int mo_map_query_keyframes(mo_map*, const mo_frame_ref* f, const mo_map_query_params*, mo_map_query_out*);
 int mo_map_relocalize_pre(mo_map*, const mo_frame_ref* f, const double K[9], const mo_map_reloc_params*, int32_t n_pre, mo_map_reloc_out*);
 
+/* mo_map_relocalize_batch: n_frames frames relocalized against the map as it stands in one device chain (a directory of query images
+ * against a saved map, the cameras of a rig after a tracking loss, the frames of one stream chunk behind a break); reads the map, never
+ * changes it - but for what the single call does too: the keyframe store is grown first so that its row stride holds the widest frame.
+ *   the rule      for every i, everything the call returns for frame i is what the matching single call returns for that frame alone on
+ *                 the same map: mo_map_relocalize(m, &frames[i], K, &p, ...) with n_pre < 0, else mo_map_relocalize_pre(..., n_pre, ...).
+ *                 Every integer equal, every double equal bit for bit.  The order, the company and the grouping of the frames change
+ *                 nothing (the sampling stream is (seed, keyframe position, h): it does not depend on the frame).  One K and one
+ *                 parameter set serve every frame.
+ *   layout        frame i's per-keypoint rows start at i * stride, its candidate rows at i * max_candidates; rows past a frame's n are
+ *                 not written.
+ *   no work       n_frames = 0: nothing runs.  A frame without keypoints: ok = 0, no candidates, a NaN pose, the others go on.  A map
+ *                 without keyframes: every frame gets those defaults.  None of these is an error.
+ *   errors        MO_ERR_ARG for a NULL required pointer, n_frames outside 0 .. MO_RELOC_BATCH_MAX, a frame of more than `stride` rows,
+ *                 n_pre = 0, n_pre >= 1 without a vocabulary, max_pairs < 0 and everything mo_map_relocalize refuses;
+ *                 MO_ERR_UNSUPPORTED where mo_map_relocalize_pre returns it (MO_BOW_MAX_ROWS).  On MO_ERR_ARG nothing is written.  A token
+ *                 that is no longer resident falls back to the frame's arrays.
+ *   groups        the matcher's outputs are 17 bytes per (pair, row): the frames are processed in groups of whole frames, enqueued back
+ *                 to back.  A group has at most max_pairs (frame, keyframe) pairs (0: 1 GiB of matcher output / (17 * row stride)), never
+ *                 more than 65535, and always at least one frame.  mo_map_reloc_batch_plan is that rule on the host: pairs_per_frame =
+ *                 the keyframes matched per frame (all of them, or n_pre when that is fewer), row = the store's row stride.
+ * One chain on the context stream, one synchronisation (the copy-out).  Integer atomics only: equal inputs give equal bytes on every
+ * run.  Stage marks rlb_stage, rlb_select, then per group rlb_match, rlb_candidates, rlb_p3p, rlb_refine (mo_stage_times; the marks past
+ * the 16th of a call are dropped).
+ * mo_map_query_keyframes_batch obeys the same rule against mo_map_query_keyframes: frame i's places are pos / score + i * n_best, n[i]
+ * of them filled. */
+#define MO_RELOC_BATCH_MAX 1024
+typedef struct {
+    mo_map_reloc_params p;
+    int32_t n_pre;           /* < 0: every keyframe is matched (mo_map_relocalize); >= 1: mo_map_relocalize_pre's n_pre; 0: MO_ERR_ARG */
+    int64_t max_pairs;       /* 0: the default budget; else the most (frame, keyframe) pairs matched per group */
+} mo_map_reloc_batch_params;
+typedef struct {
+    /* caller-allocated; point and inlier may be NULL.  Frame i's rows start at i * stride. */
+    int32_t stride;          /* rows per frame in point / inlier, >= every frame's n */
+    int32_t* point;          /* [n_frames][stride] as mo_map_reloc_out.point */
+    uint8_t* inlier;         /* [n_frames][stride] */
+    int32_t* cand_pos;       /* [n_frames][max_candidates]  required, like every array below */
+    int32_t* cand_score;     /* [n_frames][max_candidates] */
+    int32_t* cand_inliers;   /* [n_frames][max_candidates] */
+    double* pose;            /* [n_frames][12], NaN without a winner */
+    int32_t* ok;             /* [n_frames] */
+    int32_t* kf_pos;         /* [n_frames] */
+    int32_t* n_cand;         /* [n_frames] */
+    int32_t* n_corr;         /* [n_frames] */
+    int32_t* n_inliers;      /* [n_frames] */
+    int32_t* from_token;     /* [n_frames] */
+    /* filled by the call */
+    int32_t n_ok;            /* frames with ok = 1 */
+    int32_t n_groups;        /* groups the frames ran in (0: nothing ran) */
+} mo_map_reloc_batch_out;
+int mo_map_relocalize_batch(mo_map*, const mo_frame_ref* frames, int32_t n_frames, const double K[9], const mo_map_reloc_batch_params*,
+                            mo_map_reloc_batch_out*);
+int mo_map_reloc_batch_plan(int32_t n_frames, int64_t pairs_per_frame, int32_t row, int64_t max_pairs, int32_t* frames_per_group, int32_t* n_groups);
+int mo_map_query_keyframes_batch(mo_map*, const mo_frame_ref* frames, int32_t n_frames, const mo_map_query_params*, int32_t* pos, double* score,
+                                 int32_t* n, int32_t* from_token);
+
 /* ---- Tracking against the reference keyframe (map_trackref.hip) ---------------------------------------------------------------------------
  * mo_map_track_reference: the pose of a frame from its matches by appearance to ONE keyframe of the map (ORB-SLAM2's
  * TrackReferenceKeyFrame: SearchByBoW, the rotation-consistency check, PoseOptimization): what a tracker runs when it has no velocity

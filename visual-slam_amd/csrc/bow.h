@@ -63,3 +63,22 @@ int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w,
 // mo_map_loop_candidates_among's one rule, behind bow_loop_score_enqueue: common[k] = 0 where among[k] == 0 (among [n_kf] on the device);
 // mark loop_among
 int bow_loop_among_enqueue(mo_map* m, const uint8_t* among);
+
+// ---- a batch of query frames (mo_map_relocalize_batch, mo_map_query_keyframes_batch) ---------------------------------------------------
+// The frames are staged by the caller in fdesc [frame][stride][32]; cnt is the matcher's combined count array, built by the caller:
+// [0, S) the store's row counts by slot (S = kslots + 1), [S, S + nf) the frames', [S + nf] = W (the words as a train frame),
+// [S + nf + 1] = 0 (the empty frame).  Frame f is query frame S + f of a matcher launch whose query base is bow_batch_qbase.
+// Enqueued on the context stream inside the caller's stage set, no mark, no synchronisation: the database update of the stale keyframe
+// slots (once), one quantisation launch (a pair per frame), one histogram and norm per frame in the batch's own rows (the database's
+// spare row is not used), the scores over (frame, keyframe), the ranking with one workgroup per frame.  Valid behind it: pos / score
+// [frame][n_best], n [frame]; with sel, qf / tf [frame][n_best] = frame f's slice of the matcher's pair list (pairs past the selected
+// keyframes name the empty frame) and mrow [frame][n_kf] = the pair of (frame, position) inside its slice, -1: none.
+struct BowBatch {
+    const int32_t* pos = nullptr; const double* score = nullptr; const int32_t* n = nullptr;
+    const int32_t* qf = nullptr; const int32_t* tf = nullptr; const int32_t* mrow = nullptr;
+};
+// the vocabulary's words (0 without one): what the caller writes at cnt[S + nf]
+int bow_words(const mo_map* m);
+// the query base that makes frame S + f of the matcher frame f of fdesc
+inline const uint8_t* bow_batch_qbase(const uint8_t* fdesc, int S, size_t stride) { return (const uint8_t*)((uintptr_t)fdesc - (size_t)S * stride * 32); }
+int bow_batch_enqueue(mo_map* m, const uint8_t* fdesc, const int32_t* cnt, const int32_t* h_fcnt, int nf, int stride, int n_best, bool sel, BowBatch* out);

@@ -50,14 +50,16 @@ __device__ __forceinline__ long long bow_block_sum(long long v, long long* red) 
 // ---- k_bow_hist: the words of one frame -> its row of term counts and its norm; one workgroup per listed slot ---------------------------
 // LDS counters (one per word), then the row written with plain 16-byte vector stores (8 counts each).  The word of every row is kept
 // too (word [slot][wstride], uint16: W <= 8192): the rows mo_map_track_reference buckets and mo_map_keyframe_words hands out.
+// A listed frame `slot` of the matcher's numbering owns row slot - row0 of db, norm and word (the database: row0 = 0; a batch's own
+// rows, bow_batch_enqueue: row0 = its first frame, wstride = 0: no words kept).
 __global__ __launch_bounds__(256) void k_bow_hist(const int32_t* __restrict__ lst, const int32_t* __restrict__ cnt, int stride,
-                                                  const int32_t* __restrict__ qidx, int W, int Wp, const int32_t* __restrict__ weights,
+                                                  const int32_t* __restrict__ qidx, int W, int Wp, const int32_t* __restrict__ weights, int row0,
                                                   uint16_t* __restrict__ db, long long* __restrict__ norm, uint16_t* __restrict__ word, int wstride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int32_t* s_cnt = (int32_t*)smem;
     long long* red = (long long*)(smem + (size_t)Wp * 4);
-    const int b = blockIdx.x, slot = lst[b], tid = threadIdx.x;
-    const int n = min(cnt[slot], stride);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(cnt[lst[b]], stride), slot = lst[b] - row0;
     for (int w = tid; w < Wp; w += 256) s_cnt[w] = 0;
     __syncthreads();
     for (int q = tid; q < n; q += 256) {
@@ -101,14 +103,19 @@ template <> struct BowCommonArg<true> {
     int32_t* common;
 };
 
-template <bool COMMON> __global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ pos_slot, int n_kf, int spare, const uint16_t* __restrict__ db,
+// The query: row q0 + blockIdx.y of (qdb, qnorm) - the database's own spare or keyframe row for the one-frame calls, a batch's rows for
+// bow_batch_enqueue - and its scores in row blockIdx.y of score [frame][n_kf].
+template <bool COMMON> __global__ __launch_bounds__(256) void k_bow_score(const int32_t* __restrict__ pos_slot, int n_kf, int q0, const uint16_t* __restrict__ qdb,
+                                                                          const long long* __restrict__ qnorm, const uint16_t* __restrict__ db,
                                                                           const long long* __restrict__ norm, const int32_t* __restrict__ weights, int Wp,
                                                                           double* __restrict__ score, BowCommonArg<COMMON> ca) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int32_t* s_q = (int32_t*)smem;
     long long* red = (long long*)(smem + (size_t)Wp * 4);
     const int tid = threadIdx.x;
-    const uint4* qrow = (const uint4*)(db + (size_t)spare * Wp);
+    const int qi = q0 + (int)blockIdx.y;
+    const uint4* qrow = (const uint4*)(qdb + (size_t)qi * Wp);
+    score += (size_t)blockIdx.y * n_kf;
     for (int g = tid; g < Wp / 8; g += 256) {
         const uint4 c = qrow[g];
         const int4 w0 = *(const int4*)(weights + 8 * g), w1 = *(const int4*)(weights + 8 * g + 4);
@@ -116,7 +123,7 @@ template <bool COMMON> __global__ __launch_bounds__(256) void k_bow_score(const 
         *(int4*)(s_q + 8 * g + 4) = make_int4((int)(c.z & 0xffffu) * w1.x, (int)(c.z >> 16) * w1.y, (int)(c.w & 0xffffu) * w1.z, (int)(c.w >> 16) * w1.w);
     }
     __syncthreads();
-    const long long nq = norm[spare];
+    const long long nq = qnorm[qi];
     for (int k = blockIdx.x; k < n_kf; k += gridDim.x) {
         const int s = pos_slot[k];
         const long long nk = norm[s];
@@ -152,18 +159,24 @@ template <bool COMMON> __global__ __launch_bounds__(256) void k_bow_score(const 
 // its own positions in steps of 1024 and, for each step, every tile.
 // sel_qf != NULL (mo_map_relocalize_pre): the pair list of the matcher - pair r = the frame in the spare slot against the slot of the
 // keyframe at rank r, the pairs past the selected keyframes name the empty frame - and mrow[k] = the pair of position k, -1: none.
+// One workgroup per frame (bow_batch_enqueue; the one-frame calls launch one): frame f = blockIdx.x reads row f of score [frame][n_kf],
+// writes row f of out_pos / out_score / sel_qf / sel_tf [frame][n_best], of mrow [frame][n_kf] and out_n[f]; its query frame in the
+// matcher's numbering is q0 + f, and a pair without a keyframe names the train frame tf_none (any frame the counts cover).
 __global__ __launch_bounds__(1024) void k_bow_rank(const double* __restrict__ score, int n_kf, int n_best, int32_t* __restrict__ out_pos,
                                                    double* __restrict__ out_score, int32_t* __restrict__ out_n, const int32_t* __restrict__ pos_slot,
-                                                   int spare, int empty, int32_t* __restrict__ sel_qf, int32_t* __restrict__ sel_tf,
+                                                   int q0, int tf_none, int empty, int32_t* __restrict__ sel_qf, int32_t* __restrict__ sel_tf,
                                                    int32_t* __restrict__ mrow) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* s_s = (double*)smem;
     int* s_n = (int*)(smem + 1024 * 8);
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, f = blockIdx.x, spare = q0 + f;
+    score += (size_t)f * n_kf; out_pos += (size_t)f * n_best; out_score += (size_t)f * n_best; out_n += f;
+    if (sel_qf) { sel_qf += (size_t)f * n_best; sel_tf += (size_t)f * n_best; }
+    if (mrow) mrow += (size_t)f * n_kf;
     if (tid == 0) *s_n = 0;
     for (int i = tid; i < n_best; i += 1024) {
         out_pos[i] = -1; out_score[i] = 0.0;
-        if (sel_qf) { sel_qf[i] = empty; sel_tf[i] = spare; }
+        if (sel_qf) { sel_qf[i] = empty; sel_tf[i] = tf_none; }
     }
     __syncthreads();
     for (int base = 0; base < n_kf; base += 1024) {
@@ -421,8 +434,8 @@ static int bow_update(mo_map* m, int n, bool frame = true, bool marks = true) {
         return rc;
     if (marks) mo_stage_mark(c, "bow_quantise");
     if (n_list > 0) {
-        hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.match.idx, v.W, b.Wp,
-                           v.weights, b.db, b.norm, b.word, b.wstride);
+        hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)n_list), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, b.lst, b.cnt, stride, b.match.idx.p, v.W, b.Wp,
+                           v.weights.p, 0, b.db.p, b.norm.p, b.word.p, b.wstride);
         HIPCHK(c, hipGetLastError());
     }
     if (marks) mo_stage_mark(c, "bow_hist");
@@ -442,11 +455,11 @@ static int bow_enqueue(mo_map* m, int n, int n_best, bool sel) {
         (sel && (rc = mo_reserve(c, b.sel_qf, nb, b.sel_tf, nb, b.mrow, (size_t)n_kf))))
         return rc;
     hipLaunchKernelGGL(k_bow_score<false>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf, spare,
-                       b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<false>{});
+                       b.db.p, b.norm.p, b.db.p, b.norm.p, b.v->weights.p, b.Wp, b.score.p, BowCommonArg<false>{});
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "bow_score");
     hipLaunchKernelGGL(k_bow_rank, dim3(1), dim3(1024), 1024 * 8 + 16, c->stream, b.score, n_kf, n_best, b.out_pos, b.out_score, b.out_n, m->d_pos_slot, spare,
-                       m->kslots + 2, sel ? (int32_t*)b.sel_qf : nullptr, sel ? (int32_t*)b.sel_tf : nullptr, sel ? (int32_t*)b.mrow : nullptr);
+                       spare, m->kslots + 2, sel ? (int32_t*)b.sel_qf : nullptr, sel ? (int32_t*)b.sel_tf : nullptr, sel ? (int32_t*)b.mrow : nullptr);
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "bow_rank");
     return MO_OK;
@@ -497,7 +510,7 @@ int bow_loop_score_enqueue(mo_map* m, int q_pos, const int32_t* wrow, int min_w,
     int rc;
     if ((rc = mo_reserve(c, b.score, (size_t)n_kf, b.common, (size_t)n_kf))) return rc;
     hipLaunchKernelGGL(k_bow_score<true>, dim3((unsigned)std::min(n_kf, 1024)), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot, n_kf,
-                       q_slot, b.db, b.norm, b.v->weights, b.Wp, b.score, BowCommonArg<true>{wrow, q_pos, min_w, b.common});
+                       q_slot, b.db.p, b.norm.p, b.db.p, b.norm.p, b.v->weights.p, b.Wp, b.score.p, BowCommonArg<true>{wrow, q_pos, min_w, b.common});
     HIPCHK(c, hipGetLastError());
     mo_stage_mark(c, "loop_score");
     out->cnt = b.cnt; out->score = b.score; out->common = b.common; out->empty = m->kslots + 2;
@@ -542,4 +555,61 @@ extern "C" int mo_map_query_keyframes(mo_map* m, const mo_frame_ref* f, const mo
     HIPCHK(c, hipMemcpyAsync(out->score, b.out_score, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&out->n, b.out_n, 4, hipMemcpyDeviceToHost, c->stream));
     return map_sync(c, clk);
+}
+
+// ---- a batch of query frames (bow.h) ------------------------------------------------------------------------------------------------
+struct BowBatchBufs : MapFeature {
+    DevBuf<int32_t> lst;                 // [2 nf]: the quantisation's pair list - query frame S + f (also the histogram's list), then the words' frame
+    MatchBufs match;                     // [nf][max(stride, W)]: idx[2 * r] is the word of query row r
+    DevBuf<uint16_t> db;                 // [nf][Wp] term counts of every frame
+    DevBuf<long long> norm;              // [nf]
+    DevBuf<double> score;                // [nf][n_kf]
+    DevBuf<int32_t> out_pos, out_n; DevBuf<double> out_score;   // [nf][n_best], [nf]
+    DevBuf<int32_t> sel_qf, sel_tf, mrow;                       // [nf][n_best], [nf][n_kf]
+    // all of it is scratch: every call's chain writes what it reads (a DevBuf added above is named here, or kept out with a reason)
+    template <class F> void each_scratch(F f) {
+        f(lst); match.each_scratch(f); f(db); f(norm); f(score); f(out_pos); f(out_n); f(out_score); f(sel_qf); f(sel_tf); f(mrow);
+    }
+    int poison(mo_ctx* c) override { return mo_poison_scratch(c, *this); }
+    PinnedBuf<int32_t> h_lst;            // (pinned host side, not device scratch)
+};
+
+int bow_words(const mo_map* m) {
+    const BowBufs* b = map_feature_if<BowBufs>(m);
+    return b ? b->v->W : 0;
+}
+
+int bow_batch_enqueue(mo_map* m, const uint8_t* fdesc, const int32_t* cnt, const int32_t* h_fcnt, int nf, int stride, int n_best, bool sel, BowBatch* out) {
+    mo_ctx* c = m->c;
+    BowBufs& b = *map_feature_if<BowBufs>(m);
+    const mo_vocab& v = *b.v;
+    const int n_kf = (int)m->pos_slot.size(), S = m->kslots + 1;
+    int rc;
+    for (int f = 0; f < nf; f++)
+        if (h_fcnt[f] > MO_BOW_MAX_ROWS) return mo_fail(c, MO_ERR_UNSUPPORTED, "a frame of more than 65535 rows would wrap a term count");
+    if ((rc = bow_update(m, 0, false, false))) return rc;   // the stale keyframe slots, once; the spare row stays as it is
+    BowBatchBufs& bb = map_feature<BowBatchBufs>(m);
+    const int qs = std::max(stride, v.W);   // the matcher clips both sides of a pair to its output stride
+    const size_t nb = (size_t)nf * std::max(n_best, 1), nk = (size_t)nf * n_kf;
+    if ((rc = mo_reserve(c, bb.h_lst, 2 * (size_t)nf, bb.lst, 2 * (size_t)nf, bb.match, (size_t)nf * qs, bb.db, (size_t)nf * b.Wp, bb.norm, (size_t)nf, bb.score, nk,
+                         bb.out_pos, nb, bb.out_score, nb, bb.out_n, (size_t)nf)) ||
+        (sel && (rc = mo_reserve(c, bb.sel_qf, nb, bb.sel_tf, nb, bb.mrow, nk))))
+        return rc;
+    for (int f = 0; f < nf; f++) { bb.h_lst[f] = S + f; bb.h_lst[nf + f] = S + nf; }
+    HIPCHK(c, hipMemcpyAsync(bb.lst, bb.h_lst, 2 * (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+    // one pair per frame; the words are train frame S + nf of a stride of 0 bytes
+    if ((rc = match_launch_pairs(c, bow_batch_qbase(fdesc, S, (size_t)stride), v.words, (size_t)stride * 32, 0, cnt, bb.lst, bb.lst + nf, 0, 0, nf, qs, -1.0,
+                                 bb.match.idx, bb.match.dist, bb.match.pass)))
+        return rc;
+    hipLaunchKernelGGL(k_bow_hist, dim3((unsigned)nf), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, bb.lst.p, cnt, qs, bb.match.idx.p, v.W, b.Wp,
+                       v.weights.p, S, bb.db.p, bb.norm.p, (uint16_t*)nullptr, 0);
+    // a frame's workgroups keep its q_w in LDS and stride over the keyframes: fewer per frame as the batch grows
+    const unsigned gx = (unsigned)std::max(1, std::min(std::min(n_kf, 1024), 4096 / nf));
+    hipLaunchKernelGGL(k_bow_score<false>, dim3(gx, (unsigned)nf), dim3(256), (size_t)b.Wp * 4 + BOW_RED_BYTES, c->stream, m->d_pos_slot.p, n_kf, 0, bb.db.p,
+                       bb.norm.p, b.db.p, b.norm.p, v.weights.p, b.Wp, bb.score.p, BowCommonArg<false>{});
+    hipLaunchKernelGGL(k_bow_rank, dim3((unsigned)nf), dim3(1024), 1024 * 8 + 16, c->stream, bb.score.p, n_kf, n_best, bb.out_pos.p, bb.out_score.p, bb.out_n.p,
+                       m->d_pos_slot.p, S, S + nf + 1, S + nf + 1, sel ? bb.sel_qf.p : nullptr, sel ? bb.sel_tf.p : nullptr, sel ? bb.mrow.p : nullptr);
+    HIPCHK(c, hipGetLastError());
+    out->pos = bb.out_pos; out->score = bb.out_score; out->n = bb.out_n; out->qf = bb.sel_qf; out->tf = bb.sel_tf; out->mrow = bb.mrow;
+    return MO_OK;
 }

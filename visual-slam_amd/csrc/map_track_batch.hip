@@ -7,7 +7,7 @@
 //
 // Chain (one synchronisation, the copy-out; a frame's retry and early exits are flags in its TrackRes that every later workgroup of that
 // frame reads first):
-//   staging         host frames packed into pinned memory and uploaded in one copy per array, resident frames copied on the device,
+//   staging         (map_frames.h, shared with mo_map_relocalize_batch) host frames packed into pinned memory and uploaded in one copy per array, resident frames copied on the device,
 //                   into [frame][stride] batch buffers; the store's spare slot is not used
 //   k_trk_init      one workgroup per frame: its result block, keys and per-keypoint outputs; a frame without keypoints starts ended
 //   k_trk_rep       (trk_launch_rep, as mo_map_track runs it) local-map membership, representative descriptors, octaves: once per batch
@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "map_store.h"
+#include "map_frames.h"
 #include "map_track.h"
 #include "ba.h"           // pnp.h comes with it
 
@@ -169,16 +170,10 @@ extern "C" int mo_map_track_batch(mo_map* m, const mo_frame_ref* frames, int32_t
     };
     if ((rc = mo_reserve(c, b.h_fcnt, (size_t)nf, b.h_pose0, (size_t)nf * 12, b.h_res, (size_t)nf))) return rc;
     // the frames looked up: every row count known and checked before anything is written
-    std::vector<int> slot(nf);
-    bool any_host = false, any_rows = false;
-    for (int i = 0; i < nf; i++) {
-        int n;
-        if ((rc = mo_frame_lookup(c, &frames[i], "frame", &slot[i], &n))) return rc;
-        if (n > stride) return mo_fail(c, MO_ERR_ARG, "a frame has more rows than stride");
-        b.h_fcnt[i] = n;
-        any_host |= slot[i] < 0 && n > 0;
-        any_rows |= n > 0;
-    }
+    BatchFrames bf;
+    if ((rc = batch_frames_lookup(c, frames, nf, stride, "a frame has more rows than stride", b.h_fcnt, &bf))) return rc;
+    const std::vector<int>& slot = bf.slot;
+    const bool any_rows = bf.any_rows;
     for (int i = 0; i < nf; i++) {
         track_defaults(dst(i), pose0 + (size_t)i * 12);
         track_row_defaults(dst(i), b.h_fcnt[i]);
@@ -193,24 +188,12 @@ extern "C" int mo_map_track_batch(mo_map* m, const mo_frame_ref* frames, int32_t
                          b.list, np, b.cell, (size_t)nf * (TK_CELLS + 1), b.sorted, rows, b.key, rows, b.match, rows, b.minl, rows, b.qpt, rows, b.qdist,
                          rows, b.qinl, rows, b.res, (size_t)nf, b.head)))
         return rc;
-    if (any_host && (rc = mo_reserve(c, b.h_fk, rows, b.h_fdesc, rows * 32))) return rc;
+    if ((rc = batch_frames_reserve_host(c, bf, rows, b.h_fk, b.h_fdesc))) return rc;
     if ((out->point && (rc = b.h_qpt.reserve(c, rows))) || (out->dist && (rc = b.h_qdist.reserve(c, rows))) || (out->inlier && (rc = b.h_qinl.reserve(c, rows))))
         return rc;
     mo_stage_begin(c);
-    // ---- staging: the host frames in one upload per array, then the resident frames device to device
-    if (any_host) {
-        for (int i = 0; i < nf; i++) {
-            if (slot[i] >= 0 || b.h_fcnt[i] == 0) continue;
-            const size_t at = (size_t)i * stride, n = (size_t)b.h_fcnt[i];
-            std::memcpy(b.h_fk + at, frames[i].kps, n * sizeof(mo_keypoint));
-            std::memcpy(b.h_fdesc + at * 32, frames[i].desc, n * 32);
-        }
-        HIPCHK(c, hipMemcpyAsync(b.fk, b.h_fk, rows * sizeof(mo_keypoint), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b.fdesc, b.h_fdesc, rows * 32, hipMemcpyHostToDevice, c->stream));
-    }
-    for (int i = 0; i < nf; i++)
-        if (slot[i] >= 0 && (rc = mo_frame_copy_rows(c, &frames[i], slot[i], b.h_fcnt[i], b.fk + (size_t)i * stride, b.fdesc + (size_t)i * stride * 32)))
-            return rc;
+    // ---- staging (map_frames.h): the host frames in one upload per array, then the resident frames device to device
+    if ((rc = batch_frames_stage(c, frames, nf, (size_t)stride, bf, b.h_fcnt, b.h_fk, b.h_fdesc, b.fk, b.fdesc))) return rc;
     std::memcpy(b.h_pose0, pose0, (size_t)nf * 12 * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(b.fcnt, b.h_fcnt, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.pose0, b.h_pose0, (size_t)nf * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));

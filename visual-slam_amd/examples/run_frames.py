@@ -23,8 +23,15 @@ Inputs:
                       compute); the first two frames still initialise the map through MapInitializer, every later frame takes its
                       tracking result (against the previous frame) from the stream.  Same keypoints, descriptors, kept matches and
                       poses as the per-frame loop - at the batched mode's rate.
+    --load-state FILE --localize [--batch N] [--reloc-preselect P]
+                      localise every frame of the input in the saved map: no tracking, no initialisation, the map is not extended.
+                      Without --batch every frame is extracted and relocalised on its own (LocalMapper.relocalize); with --batch N the
+                      extraction runs through FrameStream and every chunk of N frames is ONE LocalMapper.relocalize_batch, fed with the
+                      chunk's keypoint and descriptor arrays.  One line per frame: ok, keyframe id, inliers, pose - the same lines
+                      either way.
 Usage: python visual-slam_amd/examples/run_frames.py [--config cfg.yaml] [--frames dir|file] [--max-frames 30] [--grid] [--python-filters] [--batch 64]
        [--map PATH [--relocalize [--vocabulary PATH [--reloc-preselect N]]] [--vocabulary PATH --detect-loops [--loop-sim3 [--loop-confirm [--loop-correct [--loop-optimize [--loop-global-ba]]]]]] [--track-map [--vocabulary PATH --track-reference] [--covisible] [--grow-neighbours] [--fuse] [--local-ba [--ba-window 10] [--ba-covisible] [--ba-erase-outliers]] [--cull-points]] [--cull-keyframes] [--save-state FILE] [--load-state FILE] [--merge-into FILE]]
+       [--load-state FILE --localize [--batch N] [--vocabulary PATH --reloc-preselect P]]
 """
 import argparse
 import os
@@ -181,6 +188,8 @@ def main(argv=None):
     ap.add_argument("--init-model-selection", action="store_true", help="initialise with ORB-SLAM2's homography / fundamental model selection "
                     "(MapInitializer(model_selection=True)): prints model, RH, parallax and good counts of every attempt")
     ap.add_argument("--batch", type=int, default=0, help="N > 0: the sequence through FrameStream in chunks of N frames (one batched device call each)")
+    ap.add_argument("--localize", action="store_true", help="with --load-state: every frame of the input is relocalised in the saved map, which is "
+                    "not extended; with --batch N one LocalMapper.relocalize_batch per chunk of N frames")
     args = ap.parse_args(argv)
     cfg, K, D = load_config(args.config)
     orb, mt = cfg["orb"], cfg["matcher"]
@@ -193,6 +202,12 @@ def main(argv=None):
     source = frames_from(args.frames) if args.frames else synthetic_sequence(limit if limit < 10 ** 9 else 30)
     state, last, poses, n_map, n_seen = "NOT_INITIALIZED", None, [], 0, 0
     t0 = time.perf_counter()
+    if args.localize:
+        if not args.load_state:
+            ap.error("--localize needs --load-state")
+        if args.reloc_preselect < 0:
+            ap.error("--reloc-preselect must be >= 0")
+        return run_localize(args, K, D, orb, extractor, source, limit, skip, t0)
     if args.batch > 0:
         if args.map:
             ap.error("--map runs frame by frame: it cannot be combined with --batch")
@@ -573,6 +588,84 @@ def _print_selection(idx, initializer):
         print("frame %d: model %s, RH %.3f, parallax %.2f deg, good %d (H candidates %s), %s" % (
             idx, {1: "H", 0: "F"}.get(sel["model"], "none"), sel["RH"], sel["parallax"], sel["n_good"], list(map(int, sel["n_good_h"])),
             "accepted" if sel["accepted"] else "refused"))
+
+
+def localize_line(idx, ok, T, info):
+    """the line --localize prints for a frame: ok, keyframe id, inliers and the pose's 12 numbers as they round-trip"""
+    pose = "none" if T is None else " ".join("%.17g" % v for v in np.asarray(T)[:3, :].ravel())
+    return "frame %d: localize %s, keyframe id %s, %d inliers, pose %s" % (idx, "ok" if ok else "failed", info["kf_id"], info["n_inliers"], pose)
+
+
+def run_localize(args, K, D, orb, extractor, source, limit, skip, t0):
+    """--load-state FILE --localize: every selected frame relocalised in the loaded map, one by one or - with --batch N - a chunk of N
+    at a time through LocalMapper.relocalize_batch on FrameStream's extraction.  The map is read, never changed."""
+    import vslam_amd as V
+    from vslam_amd.mapper import LocalMapper
+    mapper = LocalMapper.load_state(args.load_state, output_path=args.map or None)
+    print("loaded %s: %d keyframes, %d map points%s" % (args.load_state, len(mapper.keyframes), len(mapper.map_points),
+                                                      ", vocabulary of %d words" % len(mapper.vocabulary) if mapper.vocabulary is not None else ""))
+    if args.vocabulary and os.path.exists(args.vocabulary):   # (else the vocabulary the state embeds, if it has one)
+        mapper.set_vocabulary(V.Vocabulary.load(args.vocabulary, context=mapper.ctx))
+        print("vocabulary: %d words from %s" % (len(mapper.vocabulary), args.vocabulary))
+    pre = args.reloc_preselect if args.reloc_preselect > 0 and mapper.vocabulary is not None else None
+
+    def selected():
+        seen = 0
+        for idx, frame in enumerate(source):
+            if seen >= limit:
+                return
+            if skip and idx % (skip + 1) != 0:
+                continue
+            seen += 1
+            yield geom.undistort_image(frame, K, D) if np.any(D) else frame
+    n_seen = n_ok = 0
+    if args.batch > 0:
+        from vslam_amd.stream import FrameStream
+        frames = selected()
+        first = next(frames, None)
+        if first is None:
+            return "TRACKING", [], 0
+        h, w = first.shape[:2]
+        prm = V.orb_params(nfeatures=orb["n_features"], scale_factor=orb["scale_factor"], nlevels=orb["n_levels"], fast_threshold=orb["min_threshold"])
+        fs = FrameStream(K, width=w, height=h, channels=3 if first.ndim == 3 else 1, chunk=args.batch, prm=prm,
+                         detector=V.DETECT_GRID if args.grid else V.DETECT_ORB, copy=True)
+
+        def chain():
+            yield first
+            yield from frames
+
+        def flush(chunk):
+            oks, Ts, infos = mapper.relocalize_batch([(r.keypoints, r.descriptors) for r in chunk], preselect=pre)
+            for r, ok, T, info in zip(chunk, oks, Ts, infos):
+                print(localize_line(r.index, ok, T, info))
+            return int(oks.sum())
+        try:
+            chunk = []
+            for r in fs.run(chain()):
+                n_seen += 1
+                chunk.append(r)
+                if len(chunk) == args.batch:
+                    n_ok += flush(chunk)
+                    chunk = []
+            if chunk:
+                n_ok += flush(chunk)
+        finally:
+            fs.close()
+    else:
+        for idx, frame in enumerate(selected()):
+            n_seen += 1
+            if args.grid:
+                kps, desc = extractor.distribute_keypoints(frame, aligned=True)
+            else:
+                kps, desc = extractor.extract_features(frame, distributed=False)
+            ok, T, info = mapper.relocalize(kps, desc, preselect=pre)
+            n_ok += bool(ok)
+            print(localize_line(idx, ok, T, info))
+    dt = time.perf_counter() - t0
+    print("%d frames localised in %.2f s, %d ok%s%s" % (n_seen, dt, n_ok, ", chunks of %d" % args.batch if args.batch > 0 else "",
+                                                      "" if pre is None else ", preselect %d" % pre))
+    mapper.close()
+    return "TRACKING", [], 0
 
 
 def run_batched(args, cfg, K, D, orb, mt, initializer, source, limit, skip, t0):

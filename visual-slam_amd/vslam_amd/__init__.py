@@ -18,6 +18,7 @@ MO_OK, MO_ERR_ARG, MO_ERR_HIP, MO_ERR_CAPACITY, MO_ERR_UNSUPPORTED, MO_ERR_INDEX
 ABI_VERSION = 7  # MO_ABI_VERSION of include/vslam_amd.h: the struct layouts mirrored below
 ORDER_LIBSTDCXX, ORDER_MSVC = 0, 1
 TRACK_BATCH_MAX = 1024  # MO_TRACK_BATCH_MAX: frames of one mo_map_track_batch
+RELOC_BATCH_MAX = 1024  # MO_RELOC_BATCH_MAX: frames of one mo_map_relocalize_batch / mo_map_query_keyframes_batch
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4"), ("class_id", "<i4")])
@@ -101,6 +102,16 @@ class MapRelocOut(C.Structure):
     _fields_ = [("point", C.c_void_p), ("inlier", C.c_void_p), ("cand_pos", C.c_void_p), ("cand_score", C.c_void_p), ("cand_inliers", C.c_void_p),
                 ("pose", C.c_double * 12), ("ok", C.c_int32), ("kf_pos", C.c_int32), ("n_cand", C.c_int32), ("n_corr", C.c_int32),
                 ("n_inliers", C.c_int32), ("from_token", C.c_int32)]
+
+
+class MapRelocBatchParams(C.Structure):
+    _fields_ = [("p", MapRelocParams), ("n_pre", C.c_int32), ("max_pairs", C.c_int64)]
+
+
+class MapRelocBatchOut(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("point", C.c_void_p), ("inlier", C.c_void_p), ("cand_pos", C.c_void_p), ("cand_score", C.c_void_p),
+                ("cand_inliers", C.c_void_p), ("pose", C.c_void_p), ("ok", C.c_void_p), ("kf_pos", C.c_void_p), ("n_cand", C.c_void_p),
+                ("n_corr", C.c_void_p), ("n_inliers", C.c_void_p), ("from_token", C.c_void_p), ("n_ok", C.c_int32), ("n_groups", C.c_int32)]
 
 
 class MapTrackParams(C.Structure):
@@ -459,6 +470,9 @@ SIGNATURES = {
     "mo_map_set_vocabulary": (_i, [_vp, _vp]),
     "mo_map_query_keyframes": (_i, [_vp, _vp, _vp, _vp]),
     "mo_map_relocalize_pre": (_i, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "mo_map_relocalize_batch": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "mo_map_reloc_batch_plan": (_i, [C.c_int32, C.c_int64, C.c_int32, C.c_int64, _vp, _vp]),
+    "mo_map_query_keyframes_batch": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_track_reference": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mo_map_keyframe_words": (_i, [_vp, C.c_int32, _vp]),
     "mo_map_loop_candidates": (_i, [_vp, _vp, _vp]),

@@ -870,6 +870,103 @@ class LocalMapper:
                 "from_token": bool(out.from_token)}
         return bool(out.ok), pose, info
 
+    @staticmethod
+    def _batch_frames(frames, limit):
+        """the (keypoints, descriptors) pairs of a batch call as a list, checked before anything touches the map"""
+        frames = list(frames)
+        if len(frames) > limit:
+            raise ValueError("at most %d frames in a batch" % limit)
+        for fr in frames:
+            if not isinstance(fr, (tuple, list)) or len(fr) != 2:
+                raise ValueError("frames: a sequence of (keypoints, descriptors) pairs")
+        return frames
+
+    def _batch_refs(self, frames):
+        """(FrameRef array, row counts, the arrays they point into) of the frames of a batch call"""
+        refs = (V.FrameRef * max(len(frames), 1))()
+        ns, keep = [], []
+        for i, (kp, de) in enumerate(frames):
+            refs[i], n, arrays = self._frame_ref(kp, de)
+            ns.append(n)
+            keep.append(arrays)
+        return refs, ns, keep
+
+    @staticmethod
+    def reloc_batch_plan(n_frames, pairs_per_frame, row, max_pairs=None):
+        """(frames per group, groups) of relocalize_batch (mo_map_reloc_batch_plan): whole frames under the pair budget - max_pairs,
+        by default 1 GiB of matcher output at `row` rows per frame, never more than 65535 pairs -, at least one frame per group.
+        pairs_per_frame: the keyframes matched per frame.  Runs on the host."""
+        fpg, ng = C.c_int32(0), C.c_int32(0)
+        rc = V.load_library().mo_map_reloc_batch_plan(int(n_frames), int(pairs_per_frame), int(row), int(max_pairs or 0), C.byref(fpg), C.byref(ng))
+        if rc != 0:
+            raise ValueError("reloc_batch_plan: negative argument")
+        return fpg.value, ng.value
+
+    def relocalize_batch(self, frames, ratio_threshold=0.75, threshold=3.0, min_inliers=50, max_candidates=4, n_hyp=512, seed=None,
+                         preselect=None, max_pairs=None):
+        """relocalize for many frames in one device chain (mo_map_relocalize_batch in include/vslam_amd.h states the rules): a directory
+        of query images against a saved map, the cameras of a rig after a tracking loss, the frames of a stream chunk behind a break.
+        frames: a sequence of (keypoints, descriptors) as relocalize takes them (arrays that still carry a token are used resident).
+        One camera matrix and one parameter set serve every frame.  max_pairs: the most (frame, keyframe) pairs matched per group of
+        frames (None: 1 GiB of matcher output); the grouping changes no result.
+        Returns (ok [n] bool, poses, infos): every frame's results are what relocalize (with the same preselect) returns for it alone on
+        the same map, bit for bit, whatever the order and the company; poses[i] is None without a winner; infos[i] has the keys of
+        relocalize's info.  The groups the call ran in are kept in `last_reloc_groups`."""
+        frames = self._batch_frames(frames, V.RELOC_BATCH_MAX)
+        nf = len(frames)
+        if max_pairs is not None and int(max_pairs) < 1:
+            raise ValueError("max_pairs: at least one pair, or None")
+        nc = int(max_candidates)
+        if not 1 <= nc <= 64:
+            raise ValueError("max_candidates must be in 1 .. 64")
+        seed = self.seed if seed is None else int(seed)
+        refs, ns, _keep = self._batch_refs(frames)
+        stride = max(ns + [1])
+        m = max(nf, 1)
+        point = np.full((m, stride), -1, np.int32)
+        inlier = np.zeros((m, stride), np.uint8)
+        cpos = np.full((m, nc), -1, np.int32)
+        cscore, cinl = np.zeros((m, nc), np.int32), np.zeros((m, nc), np.int32)
+        pose = np.full((m, 12), np.nan)
+        ok, kf_pos, n_cand, n_corr, n_inl, tok = (np.zeros(m, np.int32) for _ in range(6))
+        K = np.ascontiguousarray(self.camera_matrix, np.float64).reshape(9)
+        prm = V.MapRelocBatchParams(V.MapRelocParams(float(ratio_threshold), float(threshold), int(min_inliers), nc, int(n_hyp), seed),
+                                    -1 if preselect is None else int(preselect), int(max_pairs or 0))
+        out = V.MapRelocBatchOut(stride, *[a.ctypes.data for a in (point, inlier, cpos, cscore, cinl, pose, ok, kf_pos, n_cand, n_corr, n_inl, tok)])
+        self._check(self.lib.mo_map_relocalize_batch(self._h, refs, nf, V._ptr(K), C.byref(prm), C.byref(out)))
+        self.last_reloc_groups = int(out.n_groups)
+        poses, infos = [], []
+        for i in range(nf):
+            kp = int(kf_pos[i])
+            T = None
+            if kp >= 0:
+                T = np.eye(4)
+                T[:3, :] = pose[i].reshape(3, 4)
+            poses.append(T)
+            infos.append({"kf_pos": kp, "kf_id": self.keyframes[kp]["id"] if kp >= 0 else None,
+                          "candidates": [(int(cpos[i, j]), int(cscore[i, j]), int(cinl[i, j])) for j in range(int(n_cand[i]))],
+                          "n_corr": int(n_corr[i]), "n_inliers": int(n_inl[i]), "point": point[i, :ns[i]].copy(),
+                          "inlier": inlier[i, :ns[i]].astype(bool), "from_token": bool(tok[i])})
+        return ok[:nf].astype(bool), poses, infos
+
+    def query_keyframes_batch(self, frames, n_best=10):
+        """query_keyframes for many frames in one device chain (mo_map_query_keyframes_batch): a list of (positions, scores), frame i's
+        what query_keyframes returns for it alone.  frames are given like relocalize_batch's; the map is not changed."""
+        frames = self._batch_frames(frames, V.RELOC_BATCH_MAX)
+        nf, nb = len(frames), int(n_best)
+        if nb < 0:
+            raise ValueError("n_best must be >= 0")
+        refs, _ns, _keep = self._batch_refs(frames)
+        pos = np.full((max(nf, 1), max(nb, 1)), -1, np.int32)
+        score = np.zeros((max(nf, 1), max(nb, 1)), np.float64)
+        n, tok = np.zeros(max(nf, 1), np.int32), np.zeros(max(nf, 1), np.int32)
+        prm = V.MapQueryParams(nb)
+        if nb == 0:   # (the places are [n][n_best]: with none asked for there is no row to address)
+            pos, score = pos[:, :0], score[:, :0]
+        self._check(self.lib.mo_map_query_keyframes_batch(self._h, refs, nf, C.byref(prm), pos.ctypes.data if nb else None,
+                                                          score.ctypes.data if nb else None, n.ctypes.data, tok.ctypes.data))
+        return [(pos[i, :int(n[i])].copy(), score[i, :int(n[i])].copy()) for i in range(nf)]
+
     def _frame_ref(self, keypoints, descriptors):
         """(FrameRef, n, arrays it points into) of a query frame: by token when the arrays are a resident detect_and_compute result,
         else the host arrays"""
